@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput bench of the hot path: stereo frames/s, 1080p, Depth-Anything-v2 ViT-B, Full-SBS.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 with WORLD_SIZE unset: bench.py re-launches itself as N ranks (one per GPU) under torch.distributed.run on
 127.0.0.1; launched BY torch.distributed.run (the driver's way) it reads RANK / LOCAL_RANK / WORLD_SIZE from the env.
@@ -367,6 +367,29 @@ def compact_line(res: dict, full_path: str) -> dict:
     return _r(out)
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict, step: int) -> dict:
+    """--dump-outputs: write each array as out_dir/<name>.npy in float32, so that two builds run with the same arguments can be
+    compared output for output.  Past DUMP_BYTES in all, each array keeps the same share of its rows (leading axes flattened, the
+    last two kept whole), drawn with seed 0 and left in their original order.  -> what was written, for the full report."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    written = {}
+    for name, a in arrays.items():
+        entry = {"shape": list(a.shape), "step": step}
+        if total > DUMP_BYTES:
+            rows = a.reshape((-1,) + a.shape[-2:])
+            keep = max(1, len(rows) * DUMP_BYTES // total)
+            a = rows[np.sort(np.random.default_rng(0).choice(len(rows), keep, replace=False))]
+            entry["sampled_rows"] = {"kept": keep, "of": len(rows), "seed": 0}
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+        written[name] = entry
+    return {"dir": out_dir, "dtype": "float32", "arrays": written}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -401,7 +424,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--full-out", default="", help="where the full report goes (default gpurun_out/bench_full.json); stdout carries one compact line")
     ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE configs[2] sub-run (ViT-L, 3840x2160, Full-TAB: bf16 and fp8 engines)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what rank 0's last timed step returned (the packed stereo frames) to DIR/sbs_frames.npy "
+                         "as float32; the inputs and weights are seeded, so two builds run with the same arguments compare output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.ingest == "rank0":
+        ap.error("--dump-outputs writes the headline step's frames: use --ingest own or both")
+    return args
 
 
 def respawn_as_ranks(n: int):
@@ -508,7 +539,11 @@ def rank_body(args, engine_factory=None, device=None):
         # a small pool of distinct batches, resident in HBM before the timed region
         pool = [frames_for(1000 * rank + 100 * j, nb).to(dev) for j in range(4 if nb <= 4 else 2)]
         out = torch.empty((nb, oh, ow, 3), dtype=torch.uint8, device=dev)
-        return lambda i: engine.pipeline(pool[i % len(pool)], p, sp, use_ema=False, out=out)
+
+        def step(i):
+            return engine.pipeline(pool[i % len(pool)], p, sp, use_ema=False, out=out)
+        step.out = out                                   # every call writes here: after a timed run it holds the last step's frames
+        return step
 
     def barrier():
         if world > 1:
@@ -555,6 +590,9 @@ def rank_body(args, engine_factory=None, device=None):
         dt = timed(step, args.warmup, args.steps)
         result["value"] = args.steps * B * world / dt
         result["ms_per_step"] = 1e3 * dt / args.steps
+        if args.dump_outputs and rank == 0:
+            # before any later sub-run reuses the buffer
+            result["dump_outputs"] = dump_outputs(args.dump_outputs, {"sbs_frames": step.out.cpu().numpy()}, args.steps - 1)
 
     if rank == 0 and world == 1 and not fake and B == 1 and not args.vda and not args.no_profile and step is not None:
         # Two frames in flight (reported beside `value`, never in it): the reference's own main loop overlaps consecutive frames -- capture,

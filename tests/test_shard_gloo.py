@@ -313,3 +313,40 @@ def test_bench_refuses_mismatched_world(monkeypatch):
     args = bench.parse_args(["--gpus", "4"])
     with pytest.raises(SystemExit):
         bench.rank_body(args, engine_factory=_StandInEngine, device=torch.device("cpu"))
+
+
+def test_bench_dump_outputs(monkeypatch, tmp_path):
+    """--dump-outputs DIR: the frames the LAST timed step returned, as float32, the same on every run; a seeded row sample past the
+    size cap; --steps below 1 refused."""
+    sys.path.insert(0, REPO)
+    import bench
+    from desktop2stereo_amd import synth
+    for k in ("RANK", "LOCAL_RANK", "D2S_DIST_BACKEND"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    H, W, B, steps = 6, 8, 3, 7
+
+    def run(out_dir):
+        args = bench.parse_args(["--steps", str(steps), "--warmup", "2", "--batch", str(B), "--height", str(H), "--width", str(W),
+                                 "--no-profile", "--no-cpu-baseline", "--sink-quality", "0", "--also-batch", "0", "--dump-outputs", str(out_dir)])
+        res = bench.rank_body(args, engine_factory=_StandInEngine, device=torch.device("cpu"))
+        return res, np.load(os.path.join(out_dir, "sbs_frames.npy"))
+
+    res, got = run(tmp_path / "a")
+    j = (steps - 1) % 4                              # make_step's pool of four batches, seeds 100 * j + frame
+    frames = np.stack([synth.noise_frame(H, W, 100 * j + i) for i in range(B)])
+    want = np.concatenate([frames, 255 - frames], axis=2).astype(np.float32)
+    assert got.dtype == np.float32 and got.shape == (B, H, 2 * W, 3) and np.array_equal(got, want)
+    assert res["dump_outputs"]["arrays"]["sbs_frames"] == {"shape": [B, H, 2 * W, 3], "step": steps - 1}
+    assert np.array_equal(run(tmp_path / "b")[1], got)
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", want.nbytes // 3)
+    res, got = run(tmp_path / "c")
+    s = res["dump_outputs"]["arrays"]["sbs_frames"]["sampled_rows"]
+    assert s["of"] == B * H and got.shape == (s["kept"], 2 * W, 3) and got.nbytes <= bench.DUMP_BYTES
+    idx = np.sort(np.random.default_rng(0).choice(B * H, s["kept"], replace=False))
+    assert np.array_equal(got, want.reshape(B * H, 2 * W, 3)[idx])
+
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--ingest", "rank0", "--dump-outputs", str(tmp_path)]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
