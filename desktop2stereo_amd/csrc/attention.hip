@@ -627,10 +627,10 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
     // prescaled: the q columns already carry 64^-0.5 * log2(e) (folded into W_q / b_q, engine.hip): scores are log2-domain as they are
     const float scale_log2e = prescaled ? 1.0f : ATTN_SCALE_LOG2E;
     if (fp8_qscale > 0.f && prec != D2S_PREC_BF16) { set_error("attention: e4m3 output needs bf16 inputs"); return D2S_E_UNSUPPORTED; }
-    static EnvInt attn32_min{"D2S_ATTN32_MIN", 168};        // (from batch 2 at N = 778: +0.3 % at 2, +1.5 % at 4, +4.5 % at 6; batch 1 -6 %)
-    // batched bf16: the 32 x 32 kernel from ~170 blocks of 128 rows (D2S_ATTN32=0: the 16-row kernel everywhere)
-    // (read per call, only for launches in that regime: the parity test flips it inside one process)
-    if (prescaled && prec == D2S_PREC_BF16 && (long)cdiv(N, 128) * heads * B >= attn32_min.get() && !(getenv("D2S_ATTN32") && atoi(getenv("D2S_ATTN32")) == 0)) {
+    // batched bf16: the 32 x 32 kernel from 168 blocks of 128 rows (D2S_ATTN32=0: the 16-row kernel everywhere)
+    // (168: from batch 2 at N = 778: +0.3 % at 2, +1.5 % at 4, +4.5 % at 6; batch 1 -6 %)
+    static EnvInt attn32{"D2S_ATTN32", 1};
+    if (prescaled && prec == D2S_PREC_BF16 && (long)cdiv(N, 128) * heads * B >= 168 && attn32.get()) {
         if ((long)N * 3 * heads * 64 * 2 >= (1L << 31)) { set_error("attention: frame too large for 32-bit buffer offsets"); return D2S_E_UNSUPPORTED; }
         const dim3 grid(attn_grid(cdiv(N, 128), heads * B));
         if (fp8_qscale > 0.f)
@@ -642,10 +642,9 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
     }
     // q rows per block: 128 as 8 waves x 1 fragment once that fills the chip (batch >= ~8), else 64 as 4 waves.
     // Swept at batch 1 / 16: 4 waves x 2 fragments 80 us, ring depth 2 / 4 within 3 %, 8 x 2 (256 rows) 68 us,
-    // 8 x 1 67 us (444 TFLOP/s); 32-row blocks slower (K/V tile loads not amortised).  D2S_ATTN_BQ forces 128 / 64 / 32.
-    static const int force = getenv("D2S_ATTN_BQ") ? atoi(getenv("D2S_ATTN_BQ")) : 0;
+    // 8 x 1 67 us (444 TFLOP/s); 32-row blocks slower (K/V tile loads not amortised).
     long hb = (long)heads * B;
-    int bq = force ? force : (cdiv(N, 128) * hb >= 512 ? 128 : 64);
+    const int bq = cdiv(N, 128) * hb >= 512 ? 128 : 64;
     const int pairs = heads * B;
 #define D2S_ATT(TT, QF_, NW_) hipLaunchKernelGGL((attention_kernel<TT, QF_, NW_>), dim3(attn_grid(cdiv(N, NW_ * QF_ * 16), pairs)), dim3(64 * NW_), 0, st, \
         (const TT*)qkv, (const TT*)vt, (TT*)out, N, Npad, heads, pairs, scale_log2e, 1.0f)
@@ -653,8 +652,7 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
         (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, pairs, scale_log2e, fp8_qscale)
     // too few (q-tile, head) blocks to fill 256 CUs (batch 1: 156): split the keys over 2 / 4 wave groups per block
     // (batch 1, N = 778: 18.9 us -> 13.8 us with 2 groups, 13.2 us with 4)
-    static const int force_ks = getenv("D2S_ATTN_KS") ? atoi(getenv("D2S_ATTN_KS")) : 0;
-    const int ks = force_ks ? force_ks : (bq == 64 && (long)cdiv(N, 64) * hb < 256 ? (N >= 512 ? 4 : (N >= 256 ? 2 : 1)) : 1);
+    const int ks = bq == 64 && (long)cdiv(N, 64) * hb < 256 ? (N >= 512 ? 4 : (N >= 256 ? 2 : 1)) : 1;
     if (fp8_qscale > 0.f) {
         if (bq == 128) D2S_ATT8(1, 8);
         else if (ks >= 2)
@@ -662,38 +660,31 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
                                (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, pairs, scale_log2e, fp8_qscale);
         else D2S_ATT8(1, 4);
     } else if (prec == D2S_PREC_BF16) {
-        if (bq == 64 && ks == 2)
+        // (Three groups of three ring stages each -- two key tiles in flight per group -- measured 10.5 us against 10.6 / 10.8 with
+        //  4 / 2 groups at N = 778: the batch-1 launch is not waiting for its key tiles -- 156 blocks keep 156 of 256 CUs at four
+        //  waves per SIMD of softmax VALU work.  Not kept.)
+        if (ks == 2)
             hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 3, bf16_t, 2>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(512), 0, st,
                                (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
-        else if (bq == 64 && ks == 4)
+        else if (ks == 4)
             hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 2, bf16_t, 4>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(1024), 0, st,
                                (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
-        else if (bq == 64 && ks == 3)       // (D2S_ATTN_KS=3: three groups, three ring stages each = two key tiles in flight per group.
-                                            //  10.5 us against 10.6 / 10.8 with 4 / 2 groups at N = 778: the batch-1 launch is not waiting
-                                            //  for its key tiles -- 156 blocks keep 156 of 256 CUs at four waves per SIMD of softmax VALU work)
-            hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 3, bf16_t, 3>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(768), 0, st,
-                               (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
         else if (bq == 128) D2S_ATT(bf16_t, 1, 8);
-        else if (bq == 64) D2S_ATT(bf16_t, 1, 4);
-        else D2S_ATT(bf16_t, 1, 2);
+        else D2S_ATT(bf16_t, 1, 4);
     } else if (prec == D2S_PREC_BF16X3) {
         // split-precision inputs (q | k and V^T pre-split by the QKV epilogue) and output; batch-1-sized launches split the keys.
         // (64-element rows are 256 bytes: two ring stages of K | V^T are 64 KiB -> two blocks per CU)
 #define D2S_ATT3(NW_, NS_, KS_) hipLaunchKernelGGL((attention_kernel<bx3_t, 1, NW_, NS_, bx3_t, KS_>), dim3(attn_grid(cdiv(N, NW_ * 16), pairs)), dim3(64 * NW_ * KS_), 0, st, \
         (const bx3_t*)qkv, (const bx3_t*)vt, (bx3_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f)
         if (bq == 128) D2S_ATT3(8, 2, 1);
-        else if (bq == 64 && ks >= 2) D2S_ATT3(4, 2, 2);
-        else if (bq == 64) D2S_ATT3(4, 2, 1);
-        else D2S_ATT3(2, 3, 1);
+        else if (ks >= 2) D2S_ATT3(4, 2, 2);
+        else D2S_ATT3(4, 2, 1);
 #undef D2S_ATT3
     } else if (bx3_out) {
-#define D2S_ATTX(NW_) hipLaunchKernelGGL((attention_kernel<float, 1, NW_, 3, bx3_t>), dim3(attn_grid(cdiv(N, NW_ * 16), pairs)), dim3(64 * NW_), 0, st, \
-        (const float*)qkv, (const float*)vt, (bx3_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f)
-        if (bq >= 64) D2S_ATTX(4); else D2S_ATTX(2);
-#undef D2S_ATTX
+        hipLaunchKernelGGL((attention_kernel<float, 1, 4, 3, bx3_t>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(256), 0, st,
+                           (const float*)qkv, (const float*)vt, (bx3_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
     } else {
-        if (bq >= 64) D2S_ATT(float, 1, 4);
-        else D2S_ATT(float, 1, 2);
+        D2S_ATT(float, 1, 4);
     }
 #undef D2S_ATT
 #undef D2S_ATT8

@@ -56,8 +56,12 @@ struct KernargWarm { int d0, d1, d2, d3, d4, d5; };
 #define KERNARG_WARM_BYTES 0x144
 #endif
 
-// Integer switch from the environment (kernel selection for A/B runs and tests): cached, re-read after
-// d2s_debug_reload_env() so that one process can run both sides.  Usage:  static EnvInt f{"D2S_NO_X", 0};  if (f.get()) ...
+// Integer switches from the environment (A/B aids and test switches; INTEGRATION.md 2d lists them), read one of two ways:
+//  - a switch read while launching or in forward() is a `static EnvInt f{"D2S_NO_X", 0};  if (f.get()) ...`: cached, and re-read
+//    after d2s_debug_reload_env() so that one process can run both sides;
+//  - a switch read when an engine is created or finalised is env_int() once per engine, stored on the engine.
+// env_int: atoi of the variable, dflt when it is unset.  (D2S_FP8_HEADROOM, a float, is the one switch read otherwise.)
+int env_int(const char* name, int dflt);
 int env_generation();
 struct EnvInt {
     const char* name; int dflt;
@@ -79,6 +83,9 @@ struct EnvInt {
     do {                                                                        \
         if (!(cond)) { ::d2s::set_error(std::string("invalid argument: ") + msg); return D2S_E_INVALID; } \
     } while (0)
+
+// CU count of the device current at the first call (256 if the query fails), looked up once per process
+int device_cu_count();
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

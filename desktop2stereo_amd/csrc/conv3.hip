@@ -1338,12 +1338,11 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
     if (N != 32 && N != 64 && (N & 127)) return false;
     const int nimg = M / (a.Ho * a.Wo);
     if ((long)nimg * a.Ho * a.Wo != M) return false;
-    static EnvInt no_persist{"D2S_NO_HEADP", 0};
     // (from ~8 tiles per CU: at batch 1-2 the 627 / 1 254 tiles are 2.4 / 4.9 rounds of 256 persistent blocks, and the one-shot blocks
     //  below -- 1 221 per frame, many per CU -- finish sooner: 25.9 -> 20.3 us at batch 1, even at batch 4)
     static EnvInt headp_min{"D2S_HEADP_MIN", 2048};
-    if (!no_persist.get() && e.map == MAP_HEAD && a.C == 64 && N <= 32 && (long)nimg * cdiv(a.Ho, 16) * cdiv(a.Wo, 16) >= headp_min.get()) {
-        static const int ncu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
+    if (e.map == MAP_HEAD && a.C == 64 && N <= 32 && (long)nimg * cdiv(a.Ho, 16) * cdiv(a.Wo, 16) >= headp_min.get()) {
+        const int ncu = device_cu_count();
         const int ntiles = nimg * cdiv(a.Ho, 16) * cdiv(a.Wo, 16);
         static EnvInt no_headups{"D2S_NO_HEADUPS", 0};
         // (the staged 13 x 13 source window holds scales <= 0.6; ReLU-on-load is not part of the interpolating loader)
@@ -1365,7 +1364,7 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         c128_min.get() > 0 && (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) >= c128_min.get() &&
         (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) < (1L << 30) && (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31)) {
         if (dry) return true;
-        static const int ncu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
+        const int ncu = device_cu_count();
         const int ntl = (int)((long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16));
         GemmEpi e1 = e; e1.ksplit = 1;
         hipLaunchKernelGGL(conv3_c128_ups_kernel, dim3(std::min(ncu & ~7, ntl)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, ntl);
@@ -1374,12 +1373,11 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
     static EnvInt no_wide{"D2S_NO_WIDE", 0};
     if (!no_wide.get() && !a.ups && e.map == MAP_ROWS && a.C == 128 && N == 128 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
         (e.out_type == OUT_T || e.out_type == OUT_BF16) && !e.scale && !e.res2 && !e.res1_mod && (e.act == ACT_NONE || e.act == ACT_RELU)) {
-        static const int ncu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-        static EnvInt wide_min{"D2S_WIDE_MIN", 384};                                                       // tiles (1.5 rounds of the CUs)
+        const int ncu = device_cu_count();
         const long pad_a = (long)cdiv(a.Ho, 8) * cdiv(a.Wo, 32), pad_b = (long)cdiv(a.Ho, 16) * cdiv(a.Wo, 16);   // 256-pixel tiles per image
         const long ntl = nimg * std::min(pad_a, pad_b);
         const int grid_w = ncu & ~7;
-        if (ntl >= wide_min.get() && ntl < (1L << 30) && grid_w >= 8) {
+        if (ntl >= 384 && ntl < (1L << 30) && grid_w >= 8) {          // 384 tiles: 1.5 rounds of the CUs
             if (dry) return true;
             GemmEpi e1 = e; e1.ksplit = 1;
             if (pad_a <= pad_b) hipLaunchKernelGGL((conv3_wide_kernel<8, 32>), dim3(grid_w), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, (int)ntl);
@@ -1395,11 +1393,9 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
     // trips here): 19.5 -> 15.5 us, two launches per frame.  The SMALLER maps (11 x 19 ... 42 x 74: 16-120 blocks) were tried the same
     // way with all 72 KB of a 32-channel block's weights up front (NS = 19, HG = 12): 11.6-12.7 us before, 11.4-14.9 after -- those
     // launches are not paced by the K loop's round trips (boundary, cold code and the epilogue are what is left); not kept.
-    // D2S_HALO2_DEEP=0: off
-    static EnvInt deep_on{"D2S_HALO2_DEEP", 1};
-    static const int ncu_d = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-    if (deep_on.get() && a.C == 128 && e.map == MAP_ROWS && N % 64 == 0 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
-        tiles_m * (N / 64) <= ncu_d && tiles_m * (N / 64) * 2 > ncu_d) {
+    const int ncu = device_cu_count();
+    if (a.C == 128 && e.map == MAP_ROWS && N % 64 == 0 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
+        tiles_m * (N / 64) <= ncu && tiles_m * (N / 64) * 2 > ncu) {
         if (dry) return true;
         GemmEpi e1 = e; e1.ksplit = 1;
         unsigned grid = 0;
@@ -1408,18 +1404,17 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         return true;
     }
     const int bn = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
-    static EnvInt halo2_min{"D2S_HALO2_MIN", 384};        // (head conv1 at batch 1: 399 tiles, 26.5 -> 21.8 us here; 110-tile maps lose)
-    if (tiles_m * cdiv(N, bn) < halo2_min.get()) return false;    // small maps: latency-bound, the small-tile kernels do better
+    // small maps: latency-bound, the small-tile kernels do better (head conv1 at batch 1: 399 tiles, 26.5 -> 21.8 us here; 110-tile maps lose)
+    if (tiles_m * cdiv(N, bn) < 384) return false;
     if ((long)gemm_npad(N) * Kpad * 2 >= (1L << 31)) return false;
     if (dry) return true;
-    static const int pst16 = getenv("D2S_HALO2_PST") ? atoi(getenv("D2S_HALO2_PST")) : 17;      // tuning aid: 17 (2 blocks / CU) | 18 (conflict-free)
     GemmEpi e1 = e; e1.ksplit = 1;
     unsigned grid = 0;
     const int xn = pick_xn((int)tiles_m, cdiv(N, bn), bn, Kpad, 2, grid);
 #define C3_LAUNCH(CPP_, PST_, BN_, WM_, WN_, NS_)                                                                                      \
     hipLaunchKernelGGL((conv3_halo2_kernel<CPP_, PST_, BN_, WM_, WN_, NS_>), dim3(grid), dim3(64 * WM_ * WN_), 0, st, a, (const bf16_t*)W, M, N, Kpad, e1, xn)
     if (a.C == 128) {
-        if (bn == 128) { if (pst16 == 18) C3_LAUNCH(16, 18, 128, 2, 4, 2); else C3_LAUNCH(16, 17, 128, 2, 4, 2); }
+        if (bn == 128) C3_LAUNCH(16, 17, 128, 2, 4, 2);          // (row pitch 17 chunks: 2 blocks / CU; 18 would be conflict-free)
         else if (bn == 64) C3_LAUNCH(16, 17, 64, 4, 2, 3);
         else C3_LAUNCH(16, 17, 32, 4, 1, 3);
     } else {

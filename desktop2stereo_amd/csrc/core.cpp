@@ -16,19 +16,28 @@ int hip_fail(hipError_t err, const char* what, const char* file, int line) {
     return D2S_E_HIP;
 }
 
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+
 static std::atomic<int> g_env_gen{1};
 int env_generation() { return g_env_gen.load(std::memory_order_relaxed); }
 // Two host threads may enter a launcher at once (two engines, or the depth and the warp thread of the reference's main loop): the
 // cached (generation, value) pair is ONE 64-bit atomic -- the hot read is a relaxed load and a compare; only the first read after
-// d2s_debug_reload_env() calls getenv (two racing refreshers store the same pair).
+// d2s_debug_reload_env() reads the environment (two racing refreshers store the same pair).
 int EnvInt::get() {
     const uint32_t g = (uint32_t)env_generation();
     const uint64_t c = cached.load(std::memory_order_relaxed);
     if ((uint32_t)(c >> 32) == g) return (int)(uint32_t)c;
-    const char* v = getenv(name);
-    const int val = v ? atoi(v) : dflt;
+    const int val = env_int(name, dflt);
     cached.store(((uint64_t)g << 32) | (uint32_t)val, std::memory_order_relaxed);
     return val;
+}
+
+int device_cu_count() {
+    static const int n = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
+    return n;
 }
 
 }  // namespace d2s

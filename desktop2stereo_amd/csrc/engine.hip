@@ -119,6 +119,7 @@ struct d2s_engine {
     bool fp8 = false, fp8_ready = false, calib = false;
     bool fp8_mlp = false;             // D2S_PREC_FP8_MLP: e4m3 on FC1 / FC2 only (60 % of the encoder FLOPs), QKV / proj stay bf16
     bool lnf = false;                 // LayerNorm folded into the producing / consuming linears (bf16, not fp8)
+    bool no_lnfuse = false;           // D2S_NO_LNFUSE=1 at creation: the LayerNorms stay kernels (e4m3 engines too)
     bool attn_prescaled = false;      // softmax scale folded into W_q / b_q (bf16 and fp8 engines)
     float* lnstats = nullptr;         // [slots][M][2] partial row sums written by the residual-update GEMMs
     float* amax = nullptr;                         // device [layers][4]: max |.| of LN1 out, attention out, LN2 out, GELU out
@@ -309,9 +310,7 @@ GemmA convA(const void* p, int Hi, int Wi, int C, int Ho, int Wo, int stride, in
 }
 // tile of the fused head launch: MAP_HEAD needs a tile whose waves own all N columns of their rows (WN == 1)
 int head_tile(int bn) {
-    static const int t32 = getenv("D2S_HEAD_T32") ? atoi(getenv("D2S_HEAD_T32")) : 0;      // tuning aid
-    static const int t64 = getenv("D2S_HEAD_T64") ? atoi(getenv("D2S_HEAD_T64")) : 0;
-    return bn == 32 ? (t32 ? t32 : 912832) : (t64 ? t64 : 9256648);
+    return bn == 32 ? 912832 : 9256648;
 }
 
 GemmEpi rowsE(void* out, int out_type, long ldc, const float* bias) {
@@ -513,22 +512,19 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     // Re-measured at the end of round 3 (the ping-pong kernel now takes launches from 100 tiles, i.e. QKV / FC1 from 4 frames): folding
     // keeps those linears on the small-tile kernels, and from 4 frames that costs more than the LayerNorm launches:
     // 1 670 -> 1 758 frames/s at batch 4, 1 815 -> 2 000 at 5, 2 052 -> 2 275 at 8 with the limit at 3 (same box).
-    static const int lnf_maxb = getenv("D2S_LNF_MAXB") ? atoi(getenv("D2S_LNF_MAXB")) : 3;       // tuning aid
-    static const bool no_lnf = getenv("D2S_NO_LNFUSE") && atoi(getenv("D2S_NO_LNFUSE")) != 0;
     // Round 4: the ping-pong kernel folds LayerNorm itself (gemm_pp.hip, PP_K_*_LN) once the residual-update linears (N = D) run on
     // it too, i.e. from gemm_pp_min_tiles() tiles of 256 x 256 over [M, D]: the 24 LayerNorm launches of the batched regime (0.66 ms of
     // a 9.8 ms step at batch 32) are gone as well.  In between (QKV / FC1 on the ping-pong kernel, proj / FC2 not yet) nothing folds.
     static EnvInt lnf_pp{"D2S_LNF_PP", 1};
     const bool pp_fold = lnf_pp.get() && e->lnf && !e->fp8 && !x3 && prec == D2S_PREC_BF16 && !e->calib && !e->taps && D % 256 == 0 && D <= 1024 &&
                          gemm_pp_min_tiles() > 0 && (long)cdiv(M, 256) * (D / 256) >= gemm_pp_min_tiles();
-    const bool lnf = (((e->lnf && !e->fp8) || (f8 && !no_lnf)) && !e->calib && (prec == D2S_PREC_BF16 || x3) && B <= (x3 ? 8 : lnf_maxb)) || pp_fold;   // (bf16x3: no ping-pong kernel to give way to)
+    const bool lnf = (((e->lnf && !e->fp8) || (f8 && !e->no_lnfuse)) && !e->calib && (prec == D2S_PREC_BF16 || x3) && B <= (x3 ? 8 : 3)) || pp_fold;   // (bf16x3: no ping-pong kernel to give way to)
     int ln_slots = 0;
     // batch 1, bf16: the four tap LayerNorms fold into the reassemble projections the same way (the statistics and the raw
     // residual of a tap layer are still in lnbuf / lnstats when its projection runs; the main stream waits for that launch
     // -- ev_ln -- before the next layer's projection GEMM overwrites them)
     // round 4: also in the batched regime where the ping-pong kernel produces the statistics (3-4 partials per row)
-    static EnvInt tapf_pp{"D2S_TAPFOLD_PP", 1};
-    const bool tap_fold = lnf && !f8 && !x3 && e->lnf && (B == 1 || (pp_fold && tapf_pp.get()));           // (bf16x3: the tap LayerNorms stay kernels)
+    const bool tap_fold = lnf && !f8 && !x3 && e->lnf && (B == 1 || pp_fold);           // (bf16x3: the tap LayerNorms stay kernels)
     bool tap_folded[4] = {false, false, false, false};
     int pending_ln = -1;
     for (int l = 0; l < d.layers; ++l) {
@@ -700,15 +696,14 @@ extern "C" int d2s_engine_create(const d2s_model_desc* desc, int device_id, d2s_
     e->d = *desc; e->device = device_id;
     e->fp8 = desc->precision == D2S_PREC_FP8 || desc->precision == D2S_PREC_FP8_MLP;
     e->fp8_mlp = desc->precision == D2S_PREC_FP8_MLP;
-    {   // LayerNorm fusion: bf16 and bf16x3 engines (not the plain fp32 engine; the e4m3 path quantises the LN output itself)
-        const char* no = getenv("D2S_NO_LNFUSE");
-        e->lnf = (desc->precision == D2S_PREC_BF16 || desc->precision == D2S_PREC_BF16X3) && !(no && atoi(no) != 0);
-    }                  // bf16 engine whose encoder linears switch to e4m3 operands
+    // LayerNorm fusion: bf16 and bf16x3 engines (not the plain fp32 engine; the e4m3 path quantises the LN output itself)
+    e->no_lnfuse = env_int("D2S_NO_LNFUSE", 0) != 0;
+    e->lnf = (desc->precision == D2S_PREC_BF16 || desc->precision == D2S_PREC_BF16X3) && !e->no_lnfuse;
+    // (the e4m3 engines are bf16 engines whose encoder linears switch to e4m3 operands)
     e->prec = e->fp8 ? D2S_PREC_BF16 : (desc->precision == D2S_PREC_BF16X3 ? D2S_PREC_FP32 : desc->precision);
     e->wprec = desc->precision == D2S_PREC_BF16X3 ? D2S_PREC_BF16X3 : e->prec;      // split-precision GEMM operands on the fp32 engine
     e->attn_prescaled = e->prec == D2S_PREC_BF16;
-    const char* t = getenv("D2S_TAPS");
-    e->taps = t && atoi(t) != 0;
+    e->taps = env_int("D2S_TAPS", 0) != 0;
     *out = e;
     return D2S_OK;
 }
@@ -913,25 +908,19 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     for (int i = 0; i < 3; ++i) RC(dev_alloc(e, &e->r1[i], (size_t)B * e->fH[i] * e->fW[i] * F * es));
     RC(dev_alloc(e, &e->r1tmp, (size_t)B * e->fH[0] * e->fW[0] * F * es));
     RC(dev_alloc(e, (void**)&e->splitk_ws_side, (e->splitk_elems + GEMM_PART_CTR_WORDS) * 4, true));
-    {
-        const char* no = getenv("D2S_NO_OVERLAP");
-        e->overlap = !(no && atoi(no) != 0);
-        if (e->overlap) {
-            D2S_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-            for (int i = 0; i < 4; ++i) D2S_HIP(hipEventCreateWithFlags(&e->ev_tap[i], hipEventDisableTiming));
-            for (int i = 0; i < 4; ++i) D2S_HIP(hipEventCreateWithFlags(&e->ev_ln[i], hipEventDisableTiming));
-            D2S_HIP(hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming));
-        }
+    e->overlap = env_int("D2S_NO_OVERLAP", 0) == 0;
+    if (e->overlap) {
+        D2S_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+        for (int i = 0; i < 4; ++i) D2S_HIP(hipEventCreateWithFlags(&e->ev_tap[i], hipEventDisableTiming));
+        for (int i = 0; i < 4; ++i) D2S_HIP(hipEventCreateWithFlags(&e->ev_ln[i], hipEventDisableTiming));
+        D2S_HIP(hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming));
     }
     if (d.temporal) {
         // ---- Video-Depth-Anything temporal modules (reference dpt_temporal.py:50-60): layer_3, layer_4, path_4, path_3
         const int tC[4] = {d.neck[2], d.neck[3], F, F};
         const int tS[4] = {e->fH[2] * e->fW[2], e->fH[3] * e->fW[3], e->fH[2] * e->fW[2], e->fH[1] * e->fW[1]};
         size_t sc_max = 0, max_sites = 0;
-        {
-            const char* nf = getenv("D2S_VDA_FUSE");
-            e->tm_fold = e->prec == D2S_PREC_BF16 && e->wprec != D2S_PREC_BF16X3 && !(nf && atoi(nf) == 0);
-        }
+        e->tm_fold = e->prec == D2S_PREC_BF16 && e->wprec != D2S_PREC_BF16X3 && env_int("D2S_VDA_FUSE", 1) != 0;
         // LN(x) W^T + b  =  rstd * (x W'^T - mean * colsum(W')) + (b + W beta),  W' = W diag(gamma): colsum over the bf16-rounded W'
         auto fold_ln = [&](const float* g, const float* bt, int Nn, int K, auto at, const float* bias, PackedW& out, float** csum) -> int {
             std::vector<float> b2(Nn), cs(Nn);
@@ -1204,14 +1193,14 @@ extern "C" int d2s_engine_profile_read(d2s_engine* e, int max_classes, double* m
     D2S_REQUIRE(e && ms && flops && bytes && launches && n_classes && max_classes >= PC_N, "bad argument");
     D2S_ON_DEVICE(e->device);
     for (int c = 0; c < PC_N; ++c) { ms[c] = 0; flops[c] = 0; bytes[c] = 0; launches[c] = 0; }
-    const char* dump = getenv("D2S_PROF_DUMP");             // tuning aid: one line per recorded launch on stderr
+    const bool dump = env_int("D2S_PROF_DUMP", 0) != 0;     // tuning aid: one line per recorded launch on stderr
     int idx = 0;
     for (auto& r : e->prof_recs) {
         D2S_HIP(hipEventSynchronize(r.b));
         float t = 0.f;
         D2S_HIP(hipEventElapsedTime(&t, r.a, r.b));
         ms[r.cls] += t; flops[r.cls] += r.flops; bytes[r.cls] += r.bytes; launches[r.cls] += 1;
-        if (dump && atoi(dump))
+        if (dump)
             fprintf(stderr, "[d2s-prof] %4d %-12s %8.2f us %9.3f GF %7.1f TF/s\n", idx, PC_NAMES[r.cls], t * 1e3, r.flops * 1e-9,
                     t > 0.f ? r.flops / (t * 1e-3) * 1e-12 : 0.0);
         ++idx;

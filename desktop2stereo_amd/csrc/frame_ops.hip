@@ -909,7 +909,6 @@ static void launch_generic(const void* rgb, const float* depth, void* out, int o
         hipLaunchKernelGGL((stereo_warp_generic<IN_FMT, D2S_FMT_F32_CHW>), grid, block, 0, st, rgb, depth, out, batch, g);
 }
 
-// `force_generic` (env D2S_WARP_GENERIC=1) lets tests compare the two paths.
 extern "C" int d2s_make_sbs(const void* rgb, int rgb_fmt, const float* depth, int dh, int dw, int batch, int H, int W,
                             const d2s_sbs_params* p, void* out, int out_fmt, void* stream) {
     D2S_REQUIRE(rgb && depth && out && p, "null pointer");
@@ -918,9 +917,8 @@ extern "C" int d2s_make_sbs(const void* rgb, int rgb_fmt, const float* depth, in
     WarpGeom g;
     if (make_geom(H, W, dh, dw, p, g) != D2S_OK) { set_error("d2s_make_sbs: bad display_mode"); return D2S_E_INVALID; }
     hipStream_t st = (hipStream_t)stream;
-    static const bool force_generic = getenv("D2S_WARP_GENERIC") && atoi(getenv("D2S_WARP_GENERIC")) != 0;
     bool nopad = (g.Hp == H && g.Wp == W);
-    bool fast_ok = !force_generic && rgb_fmt == D2S_FMT_U8_HWC && out_fmt == D2S_FMT_U8_HWC && nopad && ((long)batch * H * cdiv(W, 256) < (1L << 30)) &&
+    bool fast_ok = rgb_fmt == D2S_FMT_U8_HWC && out_fmt == D2S_FMT_U8_HWC && nopad && ((long)batch * H * cdiv(W, 256) < (1L << 30)) &&
                    (W % 4 == 0) && dw <= W && dh <= H && ((uintptr_t)rgb % 4 == 0) && ((uintptr_t)out % 4 == 0) &&
                    ((long)H * W * 3 % 4 == 0);
     if (fast_ok && g.mode == D2S_MODE_HALF_TAB && (H % 2 != 0)) fast_ok = false;

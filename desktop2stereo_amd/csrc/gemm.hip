@@ -639,12 +639,20 @@ static inline bool buf_eligible(const GemmA& a, int M, int N, int K, int Kpad, i
     return a.mode == A_PLAIN && !a.relu && K % bk == 0 && (long)M * a.lda * (long)es < (1L << 31) && (long)gemm_npad(N) * Kpad * (long)es < (1L << 31);
 }
 
+// split K below this many blocks (launch_glds)
+constexpr int SPLITK_GRID = 128;
+
 // would launch_glds split K for this launch (tiny grid, long K loop, caller-provided workspace)?  The lean instantiations take one K
 // range per block (their ring is primed from preloaded arguments before e.ksplit could be read): the dispatchers send such
 // launches to the general instantiations.
 static inline bool splitk_wanted(const GemmEpi& e, long tiles, int K, int bk) {
-    static const int sk_grid = getenv("D2S_SPLITK_GRID") ? atoi(getenv("D2S_SPLITK_GRID")) : 128;
-    return e.part && e.part_elems > 0 && !e.stats_out && tiles < sk_grid && cdiv(K, bk) >= 24;     // (splitk_reduce_kernel writes no LN statistics)
+    return e.part && e.part_elems > 0 && !e.stats_out && tiles < SPLITK_GRID && cdiv(K, bk) >= 24;     // (splitk_reduce_kernel writes no LN statistics)
+}
+
+// deep-ring lean instantiations in the latency regime (launch_t, launch_bx3); D2S_GEMM_DEEP=0: off
+static bool gemm_deep() {
+    static EnvInt deep{"D2S_GEMM_DEEP", 1};
+    return deep.get() != 0;
 }
 
 // tile codes: 64 (64x64), 128 (128x128), 256128 / 256256 (8 waves), 25664 / 25632 (256 x 64|32, 4 waves); 0 = auto
@@ -656,10 +664,8 @@ static void launch_glds(const GemmA& a, const void* W, int M, int N, int K, int 
     // 21x37 maps with 768 input channels: 14-112 blocks x 108 K tiles): the caller provides e.part
     int nkt = cdiv(K, CPR * (16 / (int)sizeof(T)));
     int ks = 1;
-    static const int sk_grid = getenv("D2S_SPLITK_GRID") ? atoi(getenv("D2S_SPLITK_GRID")) : 128;       // tuning aids
-    static const int sk_div = getenv("D2S_SPLITK_DIV") ? atoi(getenv("D2S_SPLITK_DIV")) : 6;
-    if (STG != 2 && e.part && e.part_elems > 0 && !e.stats_out && (int)grid < sk_grid && nkt >= 24) {
-        ks = nkt / sk_div; if (ks > 16) ks = 16;
+    if (STG != 2 && e.part && e.part_elems > 0 && !e.stats_out && (int)grid < SPLITK_GRID && nkt >= 24) {
+        ks = nkt / 6; if (ks > 16) ks = 16;
         while (ks > 1 && (size_t)ks * M * N > e.part_elems) --ks;
     }
     static EnvInt sk_force{"D2S_SPLITK_FORCE", 0};          // measurement aid (tools/splitk_probe.py): this many K ranges whatever the grid
@@ -674,9 +680,8 @@ static void launch_glds(const GemmA& a, const void* W, int M, int N, int K, int 
     if (e.stats_slots) *e.stats_slots = WN > 1 ? cdiv(N, BN) : 1 << 20;        // WN == 1 tiles write no statistics: the caller falls back
     GemmA a1 = a;
     {   // descriptor-addressed LDS-DMA: plain A, whole K tiles (the W zero padding covers nothing then), 32-bit byte offsets
-        static const bool nobuf = getenv("D2S_GEMM_NOBUF") && atoi(getenv("D2S_GEMM_NOBUF")) != 0;
         constexpr int bk = CPR * (16 / (int)sizeof(T));
-        a1.buf = !nobuf && STG != 1 && buf_eligible(a, M, N, K, Kpad, bk, sizeof(T));
+        a1.buf = STG != 1 && buf_eligible(a, M, N, K, Kpad, bk, sizeof(T));
     }
     hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WM, WN, NS, CPR, STG>), dim3(grid), dim3(64 * WM * WN), 0, st, (const T*)W, a1.ptr, a1.lda, M, N, K, Kpad, xn, a1, e1);
 }
@@ -713,22 +718,16 @@ static bool launch_conv_halo(const GemmA& a, const void* W, int M, int N, int K,
 // Same rule as the other types -- resident waves first, then tile intensity -- on the staged instantiations.
 static int launch_bx3(int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
     typedef bx3_t T;
-    static const int force_tile = getenv("D2S_GEMM_TILE_BX3") ? atoi(getenv("D2S_GEMM_TILE_BX3")) : 0;
     if (a.bx3) {
         // A pre-split by its producer (LayerNorm / attention / GELU epilogue): LDS-DMA rings for both operands, the bf16 tile rule
         if (a.mode != A_PLAIN || a.relu) { set_error("launch_gemm: a pre-split bf16x3 A operand must be a plain matrix"); return D2S_E_UNSUPPORTED; }
-        static const int force_dma = getenv("D2S_GEMM_TILE_BX3D") ? atoi(getenv("D2S_GEMM_TILE_BX3D")) : 0;
-        int t = force_dma;
-        if (t == 0) {
-            const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
-            if (b128 >= 400 && (N >= 1536 || b128 >= 900)) t = 1281288;
-            else if (b64128 >= 280) t = 641288;
-            else if (b64 >= 384) t = 64648;
-            else t = 3264;
-        }
+        const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
+        int t = 3264;
+        if (b128 >= 400 && (N >= 1536 || b128 >= 900)) t = 1281288;
+        else if (b64128 >= 280) t = 641288;
+        else if (b64 >= 384) t = 64648;
         // (latency regime: the deep-ring lean instantiations, as in launch_t)
-        static const int deep = getenv("D2S_GEMM_DEEP") ? atoi(getenv("D2S_GEMM_DEEP")) : 1;
-        const bool dp = deep && buf_eligible(a, M, N, K, Kpad, 32, 4) &&
+        const bool dp = gemm_deep() && buf_eligible(a, M, N, K, Kpad, 32, 4) &&
                         !splitk_wanted(e, (long)cdiv(M, t == 3264 ? 32 : 64) * cdiv(N, t == 641288 ? 128 : 64), K, 32);
         if (t == 3264 && dp && (long)cdiv(M, 32) * cdiv(N, 64) <= 512) launch_glds<T, 32, 64, 2, 2, 6, 8, 2>(a, W, M, N, K, Kpad, e, st);
         else if (t == 64648 && dp && (long)cdiv(M, 64) * cdiv(N, 64) <= 512) launch_glds<T, 64, 64, 4, 2, 4, 8, 2>(a, W, M, N, K, Kpad, e, st);
@@ -736,12 +735,11 @@ static int launch_bx3(int tile, const GemmA& a, const void* W, int M, int N, int
         else if (t == 3264) launch_glds<T, 32, 64, 2, 2, 4>(a, W, M, N, K, Kpad, e, st);
         else if (t == 64648) launch_glds<T, 64, 64, 4, 2, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);
         else if (t == 641288) launch_glds<T, 64, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);
-        else if (t == 1281288) launch_glds<T, 128, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);
-        else { set_error("launch_gemm: bad tile code for pre-split bf16x3 operands"); return D2S_E_INVALID; }
+        else launch_glds<T, 128, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);      // t == 1281288
         D2S_CHECK_LAUNCH();
         return D2S_OK;
     }
-    if (tile == 0 || tile == 256256) tile = force_tile;
+    if (tile == 256256) tile = 0;           // (the ping-pong tile code names no bf16x3 kernel: the automatic rule)
     if (tile == 0) {
         const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
         if (N <= 64) tile = (long)cdiv(M, 256) >= 224 ? (N <= 32 ? 912832 : 9256648) : 93264;
@@ -781,11 +779,7 @@ int gemm_pp_min_tiles() {
 
 template <typename T>
 static int launch_t(int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
-    static const int force_tile = getenv("D2S_GEMM_TILE") ? atoi(getenv("D2S_GEMM_TILE")) : 0;
-    if (tile == 0) tile = force_tile;
     if (tile == 0 && launch_conv_halo<T>(a, W, M, N, K, Kpad, e, st)) { D2S_CHECK_LAUNCH(); return D2S_OK; }
-    static EnvInt conv_tile{"D2S_CONV_TILE", 0};          // tuning aid: tile code for the implicit 3x3 convolutions
-    if (tile == 0 && a.mode == A_CONV3 && N > 64) tile = conv_tile.get();
     if constexpr (std::is_same<T, bf16_t>::value) {
         // thin linears (K <= 256: ConvTranspose(k = s), fusion 1x1 projections): HBM-bound, one prologue per block instead of per tile
         if (tile == 0 && sk_supported(D2S_PREC_BF16, a, M, N, K, Kpad, e)) return launch_gemm_sk(a, W, M, N, K, Kpad, e, st);
@@ -808,11 +802,9 @@ static int launch_t(int tile, const GemmA& a, const void* W, int M, int N, int K
         // resident waves per CU in DIFFERENT phases of the K loop (8-wave blocks, 2-5 blocks per CU), then tile intensity;
         // with that in place the LDS-DMA path beats register staging (no VGPR / ds_write pass).  The 4-wave 32 x 64 ring
         // (NS = 4: deepest prefetch, shortest prologue) keeps the launches with the fewest tiles (batch 1: proj, FC2).
-        static const int t64 = getenv("D2S_GEMM_T64") ? atoi(getenv("D2S_GEMM_T64")) : 0;    // tuning: N <= 64 tiles
-        static const int t32 = getenv("D2S_GEMM_T32") ? atoi(getenv("D2S_GEMM_T32")) : 0;
         const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
         if (N <= 64) {                              // DPT head: 64 / 32 output channels, M = pixels
-            if ((long)cdiv(M, 256) >= 224) tile = N <= 32 ? (t32 ? t32 : 912832) : (t64 ? t64 : 9256648);
+            if ((long)cdiv(M, 256) >= 224) tile = N <= 32 ? 912832 : 9256648;
             else tile = 3264;
         }
         else {
@@ -821,9 +813,8 @@ static int launch_t(int tile, const GemmA& a, const void* W, int M, int N, int K
             tile = bm == 128 ? 1281288 : (bn == 128 ? 641288 : (bm == 64 ? 64648 : 3264));     // 3264: skinny launches (batch 1, N = 768)
             // long-K implicit convolutions (tap 3's stride-2 768 -> 768: K = 6 912) from ~300 tiles of 128 x 128: the 64 x 128 tile falls off a
             // cliff there (batch 28: 130 us, batch 32: 188 us for 1.14 x the work) where the 128 x 128 tile stays at 128-134 us at every batch from
-            // 16 to 32 -- below 300 tiles the smaller tile is 5-15 % faster.  D2S_CONV_B128: the threshold
-            static EnvInt conv_b128{"D2S_CONV_B128", 300};
-            if (a.mode == A_CONV3 && K >= 4096 && (long)cdiv(M, 128) * cdiv(N, 128) >= conv_b128.get()) tile = 1281288;
+            // 16 to 32 -- below 300 tiles the smaller tile is 5-15 % faster
+            if (a.mode == A_CONV3 && K >= 4096 && (long)cdiv(M, 128) * cdiv(N, 128) >= 300) tile = 1281288;
         }
     }
     // Latency regime (batch 1-2: every block of the launch is resident at once, 1-2 per CU).  In-kernel stamps (tools/glds_timeline.py)
@@ -831,9 +822,7 @@ static int launch_t(int tile, const GemmA& a, const void* W, int M, int N, int K
     // with the 2-stage rings of the 8-wave tiles, next to 64-256 cycles of MFMA work.  The LDS those few blocks leave unused buys
     // ring depth: as many stages as still let ALL blocks be resident.  "Lean" instantiations (descriptor loader only).
     if constexpr (std::is_same<T, bf16_t>::value || std::is_same<T, fp8_t>::value) {
-        static const int deep = getenv("D2S_GEMM_DEEP") ? atoi(getenv("D2S_GEMM_DEEP")) : 1;
-        static const bool nobuf = getenv("D2S_GEMM_NOBUF") && atoi(getenv("D2S_GEMM_NOBUF")) != 0;
-        if (deep && !nobuf && !(e.part && e.ksplit > 1) && buf_eligible(a, M, N, K, Kpad, 128 / (int)sizeof(T), sizeof(T)) && e.map != MAP_HEAD &&
+        if (gemm_deep() && !(e.part && e.ksplit > 1) && buf_eligible(a, M, N, K, Kpad, 128 / (int)sizeof(T), sizeof(T)) && e.map != MAP_HEAD &&
             !splitk_wanted(e, (long)cdiv(M, tile == 3264 ? 32 : 64) * cdiv(N, tile == 641288 ? 128 : 64), K, 128 / (int)sizeof(T))) {
             bool done = true;
             if (tile == 3264 && (long)cdiv(M, 32) * cdiv(N, 64) <= 512) launch_glds<T, 32, 64, 2, 2, 6, 8, 2>(a, W, M, N, K, Kpad, e, st);            // 72 KiB: 2 blocks / CU

@@ -386,12 +386,10 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 namespace d2s {
 // pick the XCD grid (xn x 8/xn) for a tiles_m x tiles_n tile space: least padding, W chunk within L2
 static inline int pick_xn(int tiles_m, int tiles_n, int BN, int Kpad, size_t es, unsigned& grid) {
-    static const int force = getenv("D2S_GEMM_XN") ? atoi(getenv("D2S_GEMM_XN")) : -1;
     long total = (long)tiles_m * tiles_n;
-    if (force == 0 || total < 16) { grid = (unsigned)total; return 0; }
+    if (total < 16) { grid = (unsigned)total; return 0; }
     int best = 0; double best_score = 1e30; long best_grid = total;
     for (int xn = 1; xn <= 8; xn *= 2) {
-        if (force > 0 && xn != force) continue;
         int xm = 8 / xn;
         long g = 8L * cdiv(tiles_n, xn) * cdiv(tiles_m, xm);
         double score = (double)(g - total) / (double)total;

@@ -919,16 +919,14 @@ bool pp_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, 
     if (ln_cons || ln_prod) {
         // LayerNorm folded in (bf16 only): the consumer reads <= 4 partials per row (N of the producer <= 1024), the producer is the
         // fp32 in-place residual update writing the bf16 copy + one partial per 256-column tile
-        static EnvInt off{"D2S_PP_NO_LN", 0};
-        if (off.get() || precision != D2S_PREC_BF16 || (ln_cons && ln_prod)) return false;
+        if (precision != D2S_PREC_BF16 || (ln_cons && ln_prod)) return false;
         if (ln_cons && !(e.ln_stats && e.ln_csum && e.ln_slots >= 1 && e.ln_slots <= 4 && e.out_type != OUT_F32 && (e.map == MAP_QKV || e.act == ACT_GELU))) return false;
         if (ln_prod && !(e.stats_out && e.out2 && e.stats_slots && e.out_type == OUT_F32 && e.res1 && e.res1 == e.out && !e.out2_bx3 && e.out2_qscale == 0.f && N <= 1024)) return false;
     }
     if (e.rows_per_img || e.res1_mod || (e.ldc & 7) || e.res2 || N > PP_MAXN) return false;
     bool out_bf16 = e.out_type == OUT_BF16 || (e.out_type == OUT_T && precision == D2S_PREC_BF16);
     // e4m3 operands: the GELU kind writes e4m3 and nothing else (FC1 -> FC2 of the e4m3 schemes), 8-byte aligned rows
-    static EnvInt no_out8{"D2S_PP_NO_OUT8", 0};                         // (bisecting aid: FC1 of the e4m3 schemes back on the 128 x 128 tiles)
-    if (precision == D2S_PREC_FP8_OPERANDS && e.act == ACT_GELU) out_bf16 = e.out_type == OUT_T && e.map == MAP_ROWS && e.out_qscale > 0.f && !no_out8.get();
+    if (precision == D2S_PREC_FP8_OPERANDS && e.act == ACT_GELU) out_bf16 = e.out_type == OUT_T && e.map == MAP_ROWS && e.out_qscale > 0.f;
     if (e.out_type == OUT_F32) { if (e.act != ACT_NONE || e.map != MAP_ROWS) return false; }
     else if (!(out_bf16 && !e.res1 && !e.res2 && !e.scale && (e.act == ACT_NONE || (e.act == ACT_GELU && e.map == MAP_ROWS)))) return false;
     if (e.map == MAP_QKV && (e.qk_cols & 255)) return false;            // a block tile is entirely q|k or entirely v
@@ -972,7 +970,7 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     static EnvInt f32_xn1{"D2S_PP_F32_XN1", 1};
     if (e.out_type == OUT_F32 && f32_xn1.get()) xn = 1;
     // one 160-KiB block per CU, cpx blocks per XCD (blocks beyond an XCD's list exit at once)
-    static const int ncu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int ncu = device_cu_count();
     const int lxn = xn <= 1 ? 0 : (xn == 2 ? 1 : (xn == 4 ? 2 : 3));
     const bool ln = e.ln_csum != nullptr || e.stats_out != nullptr;
     if (ln && e.out_type != OUT_F32 && e.map != MAP_QKV && e.act != ACT_GELU) { set_error("launch_gemm_pp: LN-folded consumer: QKV or FC1 only"); return D2S_E_UNSUPPORTED; }
@@ -981,7 +979,6 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     // K-split tail (see the kernel): when the last round would be less than 45 % full and the launch is a residual update
     const int tiles = tiles_m * tiles_n, nkt = K / (128 / (int)elem_size(precision));
     int tw = tiles, ks = 1, kps = nkt;
-    static const int split_pct = getenv("D2S_PP_SPLIT") ? atoi(getenv("D2S_PP_SPLIT")) : 45;
     // (only for long K loops: the slab round trip + the second launch cost ~30 us, a 12-K-tile round of proj costs 25 --
     //  measured at batch 32: FC2 164 -> 144 us, proj 65 -> 71)
     // Round 4: the K splits of a tail tile share an XCD and are reduced inside the kernel (pp_tail_reduce_inkernel): no second launch,
@@ -991,14 +988,14 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     //  costs more than the idle CUs.)
     static EnvInt ink_on{"D2S_PP_INK", 1};
     int ink = 0;
-    if (pp_kind_f32(kind) && e.part && split_pct > 0) {
+    if (pp_kind_f32(kind) && e.part) {
         const int rounds = tiles / ncu, rem = tiles - rounds * ncu;
-        if (rounds >= 1 && rem > 0 && rem * 100 <= split_pct * ncu) {
-            static EnvInt ink_mink{"D2S_PP_INK_MINK", 24};            // fewest K tiles per output tile for which the tail is split (proj, 12 K tiles, measured at batch 32: 82 -> 86-94 us split, the slab traffic costs more than its second round)
-            if (ink_on.get() && nkt >= ink_mink.get() && rem <= PP_TAIL_MAX && (ncu & 7) == 0) {
+        if (rounds >= 1 && rem > 0 && rem * 100 <= 45 * ncu) {
+            // from 24 K tiles per output tile (proj, 12 K tiles, measured at batch 32: 82 -> 86-94 us split, the slab traffic costs
+            // more than its second round); at most 8 K ranges per tail tile
+            if (ink_on.get() && nkt >= 24 && rem <= PP_TAIL_MAX && (ncu & 7) == 0) {
                 const int per_xcd = cdiv(rem, 8);                     // tail tiles of the busiest XCD
-                static EnvInt ink_ks{"D2S_PP_INK_KS", 8};             // tuning aid: most K ranges per tail tile
-                for (int s = std::min(8, ink_ks.get()); s >= 2; --s)
+                for (int s = 8; s >= 2; --s)
                     if (nkt % (2 * s) == 0 && per_xcd * s <= ncu / 8 && (size_t)rem * s * 65536 <= e.part_elems) { ks = s; kps = nkt / s; tw = tiles - rem; ink = ink_on.get() == 2 ? 3 : 1; break; }     // D2S_PP_INK=2 (test aid): nobody waits, the last arrival of a tile sums all of it
             }
             // short K loops (proj: 12 K tiles): a K split costs more in slab traffic than the round it removes (section 3.1f); cut the
@@ -1030,9 +1027,9 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     if (!e1.deq) e1.deq = pp_const_vec(true);
     if (!e1.bias || !e1.scale || !e1.deq) { set_error("launch_gemm_pp: constant vectors"); return D2S_E_HIP; }
     // half a tile time: K tiles x ~1.5 us + ~8 us of prologue / epilogue (D2S_PP_SKEW: percent of that; 0 = off)
-    static const int skew_pct = getenv("D2S_PP_SKEW") ? atoi(getenv("D2S_PP_SKEW")) : 50;
+    static EnvInt skew_pct{"D2S_PP_SKEW", 50};
     // (with a K-split tail the lists end in short units: a block without one is not half a tile "lighter")
-    const int skew_us = ks > 1 ? 0 : (int)((K / (128 / (int)elem_size(precision)) * 1.5 + 8.0) * skew_pct / 100.0);
+    const int skew_us = ks > 1 ? 0 : (int)((K / (128 / (int)elem_size(precision)) * 1.5 + 8.0) * skew_pct.get() / 100.0);
 #define PP_LAUNCH(T_, KIND_) hipLaunchKernelGGL((gemm_pp_kernel<T_, KIND_>), dim3(grid), dim3(512), 0, st, (const T_*)a.ptr, a.lda, (const T_*)W, M, N, K, Kpad, e1, lxn, skew_us, tw, ks, kps, ink)
     if (precision == D2S_PREC_BF16) {
         if (kind == PP_K_F32) PP_LAUNCH(bf16_t, PP_K_F32); else if (kind == PP_K_QKV) PP_LAUNCH(bf16_t, PP_K_QKV);

@@ -98,8 +98,7 @@ gemm_sk_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict_
 
 // what the streaming kernel takes: plain bf16 rows in and out, whole K in registers, no residuals / LayerNorm folding / split K
 bool sk_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e) {
-    static EnvInt off{"D2S_NO_SK", 0};
-    if (off.get() || precision != D2S_PREC_BF16 || a.mode != A_PLAIN || a.relu || a.bx3) return false;
+    if (precision != D2S_PREC_BF16 || a.mode != A_PLAIN || a.relu || a.bx3) return false;
     if (K < 32 || K > 256 || (K & 31) || (N & (SK_BN - 1)) || (a.lda & 7) || M < SK_ROWS) return false;
     if (e.out_type != OUT_T && e.out_type != OUT_BF16) return false;
     if (e.map == MAP_SHUFFLE) { if ((e.cout & 7) || e.gw <= 0 || e.gh <= 0 || e.ks <= 0) return false; }
@@ -110,7 +109,7 @@ bool sk_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, 
 
 int launch_gemm_sk(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
     if (!sk_supported(D2S_PREC_BF16, a, M, N, K, Kpad, e)) { set_error("launch_gemm_sk: unsupported problem"); return D2S_E_UNSUPPORTED; }
-    static const int ncu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int ncu = device_cu_count();
     const int cols = N / SK_BN, tiles_m = cdiv(M, SK_ROWS);
     // two blocks per CU (<= 83 KiB of LDS each); every block streams >= 2 row tiles where there are that many
     int per_col = std::max(1, std::min(tiles_m, (2 * ncu) / cols));

@@ -489,7 +489,9 @@ class Engine:
 
 
 def reload_env() -> int:
-    """Make libd2s_hip.so re-read its kernel-selection switches (D2S_NO_HALO2, D2S_NO_WIDE, ...) from the environment."""
+    """Make libd2s_hip.so re-read the switches it reads while launching (D2S_NO_HALO2, D2S_NO_WIDE, ...) from the environment.
+    Switches read when an engine is created or finalised (D2S_NO_LNFUSE, D2S_TAPS, D2S_NO_OVERLAP, D2S_VDA_FUSE) are not re-read
+    for an engine that exists."""
     return int(_lib.load().d2s_debug_reload_env())
 
 

@@ -470,27 +470,30 @@ def test_attention_probe(dev, monkeypatch):
     random data never takes after the first tiles)."""
     from desktop2stereo_amd import ops
     g = torch.Generator().manual_seed(1)
-    for (B, H, N) in [(1, 12, 778), (44, 12, 778), (30, 16, 1370), (64, 2, 296), (90, 6, 37), (6, 12, 1000)]:
-        q, k, v = (torch.randn((B, H, N, 64), generator=g) for _ in range(3))
-        v[..., 0] += torch.arange(N)[None, None, :] % 5 * 0.5
-        v[..., 63] -= 1.0
-        q[:, :, N // 2] *= 3.0
-        k[:, :, N - 3] = q[:, :, N // 2] * 1.5                     # q . k / 8 ~ 100 for that pair: the max jumps in the last tile
-        for prec, cast, tol in (("bf16", torch.bfloat16, 2e-2), ("fp32", torch.float32, 2e-5), ("bf16x3", torch.float32, 2e-4)):
-            if prec == "fp32" and B * H * N > 12 * 778 * 8:
-                continue
-            qd, kd, vd = (t.to(cast).double() for t in (q, k, v))
-            if prec == "bf16":                                     # as in the bf16 engines: the softmax scale is folded into W_q, so the
-                c = 0.125 * 1.4426950408889634                     # q the kernel sees is bf16(q * 64^-0.5 * log2 e)
-                qd = (q * c).to(cast).double() / c
-            p = torch.softmax(qd @ kd.transpose(-1, -2) / 8.0, dim=-1)
-            want = (p @ vd).permute(0, 2, 1, 3).reshape(B, N, H * 64)
-            for a32 in (("1", "0") if prec == "bf16" else ("1",)):
-                monkeypatch.setenv("D2S_ATTN32", a32)
-                got, _ = ops.attention_probe(q.to(dev), k.to(dev), v.to(dev), prec)
-                err = (got.cpu().double() - want).abs().max().item()
-                assert err <= tol * max(1.0, want.abs().max().item() / 4), (B, H, N, prec, a32, err)   # bf16: P and O are rounded to 8 bits
-                assert torch.equal(ops.attention_probe(q.to(dev), k.to(dev), v.to(dev), prec)[0], got), "not reproducible"
+    try:
+        for (B, H, N) in [(1, 12, 778), (44, 12, 778), (30, 16, 1370), (64, 2, 296), (90, 6, 37), (6, 12, 1000)]:
+            q, k, v = (torch.randn((B, H, N, 64), generator=g) for _ in range(3))
+            v[..., 0] += torch.arange(N)[None, None, :] % 5 * 0.5
+            v[..., 63] -= 1.0
+            q[:, :, N // 2] *= 3.0
+            k[:, :, N - 3] = q[:, :, N // 2] * 1.5                     # q . k / 8 ~ 100 for that pair: the max jumps in the last tile
+            for prec, cast, tol in (("bf16", torch.bfloat16, 2e-2), ("fp32", torch.float32, 2e-5), ("bf16x3", torch.float32, 2e-4)):
+                if prec == "fp32" and B * H * N > 12 * 778 * 8:
+                    continue
+                qd, kd, vd = (t.to(cast).double() for t in (q, k, v))
+                if prec == "bf16":                                     # as in the bf16 engines: the softmax scale is folded into W_q, so the
+                    c = 0.125 * 1.4426950408889634                     # q the kernel sees is bf16(q * 64^-0.5 * log2 e)
+                    qd = (q * c).to(cast).double() / c
+                p = torch.softmax(qd @ kd.transpose(-1, -2) / 8.0, dim=-1)
+                want = (p @ vd).permute(0, 2, 1, 3).reshape(B, N, H * 64)
+                for a32 in (("1", "0") if prec == "bf16" else ("1",)):
+                    monkeypatch.setenv("D2S_ATTN32", a32); ops.reload_env()
+                    got, _ = ops.attention_probe(q.to(dev), k.to(dev), v.to(dev), prec)
+                    err = (got.cpu().double() - want).abs().max().item()
+                    assert err <= tol * max(1.0, want.abs().max().item() / 4), (B, H, N, prec, a32, err)   # bf16: P and O are rounded to 8 bits
+                    assert torch.equal(ops.attention_probe(q.to(dev), k.to(dev), v.to(dev), prec)[0], got), "not reproducible"
+    finally:
+        monkeypatch.delenv("D2S_ATTN32", raising=False); ops.reload_env()
 
 
 # ------------------------------------------------------------------------------------------------
