@@ -54,6 +54,16 @@ class DibrParams(C.Structure):
 DIBR_ALPHA = {"window": 0, "premultiplied": 1, "rgba": 2}      # D2S_DIBR_ALPHA_*
 
 
+class Conv3ProbeParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("precision", C.c_int32), ("tile", C.c_int32),
+                ("batch", C.c_int32), ("C", C.c_int32), ("N", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
+                ("Hi", C.c_int32), ("Wi", C.c_int32), ("stride", C.c_int32), ("relu_in", C.c_int32), ("act", C.c_int32),
+                ("out_f32", C.c_int32), ("map_head", C.c_int32), ("b3", C.c_float), ("max_depth", C.c_float),
+                ("reserved", C.c_int32), ("splitk_elems", C.c_int64),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p), ("w3", C.c_void_p),
+                ("out", C.c_void_p), ("kernel", C.c_char * 128)]
+
+
 # every symbol include/d2s.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -108,6 +118,7 @@ SYMBOLS = {
     "d2s_profile_class_name": (C.c_char_p, [C.c_int]),
     "d2s_gemm_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "d2s_attention_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "d2s_conv3_probe": (C.c_int, [C.POINTER(Conv3ProbeParams), _P]),
 }
 
 _lib = None

@@ -1352,9 +1352,16 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         // (the source map is read through one buffer descriptor; a tap's source-column byte offset travels in the low 16 bits of the
         //  bpermute word of h_request: a source row must stay within 64 KiB, i.e. Ws <= 512 at C = 64 -- wider maps take <1>)
         const bool ups_fits = (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31) && (long)a.Ws * a.C * 2 <= 65536;
-        if (a.ups && !ups_v1.get() && ups_fits) hipLaunchKernelGGL(conv3_head_ups_kernel, dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
-        else if (a.ups) hipLaunchKernelGGL((conv3_head_kernel<1>), dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
-        else hipLaunchKernelGGL((conv3_head_kernel<0>), dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
+        if (a.ups && !ups_v1.get() && ups_fits) {
+            note_kernel("conv3_head_ups_kernel");
+            hipLaunchKernelGGL(conv3_head_ups_kernel, dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
+        } else if (a.ups) {
+            note_kernel("conv3_head_kernel<1>");
+            hipLaunchKernelGGL((conv3_head_kernel<1>), dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
+        } else {
+            note_kernel("conv3_head_kernel<0>");
+            hipLaunchKernelGGL((conv3_head_kernel<0>), dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
+        }
         return true;
     }
     // the head's conv1 at batch: persistent blocks with W in registers and the up-sample in the loader (conv3_c128_ups_kernel)
@@ -1367,6 +1374,7 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         const int ncu = device_cu_count();
         const int ntl = (int)((long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16));
         GemmEpi e1 = e; e1.ksplit = 1;
+        note_kernel("conv3_c128_ups_kernel");
         hipLaunchKernelGGL(conv3_c128_ups_kernel, dim3(std::min(ncu & ~7, ntl)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, ntl);
         return true;
     }
@@ -1380,6 +1388,7 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         if (ntl >= 384 && ntl < (1L << 30) && grid_w >= 8) {          // 384 tiles: 1.5 rounds of the CUs
             if (dry) return true;
             GemmEpi e1 = e; e1.ksplit = 1;
+            note_kernel(pad_a <= pad_b ? "conv3_wide_kernel<8,32>" : "conv3_wide_kernel<16,16>");
             if (pad_a <= pad_b) hipLaunchKernelGGL((conv3_wide_kernel<8, 32>), dim3(grid_w), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, (int)ntl);
             else hipLaunchKernelGGL((conv3_wide_kernel<16, 16>), dim3(grid_w), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, (int)ntl);
             return true;
@@ -1400,6 +1409,7 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         GemmEpi e1 = e; e1.ksplit = 1;
         unsigned grid = 0;
         const int xn = pick_xn((int)tiles_m, N / 64, 64, Kpad, 2, grid);
+        note_kernel("conv3_halo2_kernel<16,17,64,4,2,10,6>");
         hipLaunchKernelGGL((conv3_halo2_kernel<16, 17, 64, 4, 2, 10, 6>), dim3(grid), dim3(512), 0, st, a, (const bf16_t*)W, M, N, Kpad, e1, xn);
         return true;
     }
@@ -1412,7 +1422,8 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
     unsigned grid = 0;
     const int xn = pick_xn((int)tiles_m, cdiv(N, bn), bn, Kpad, 2, grid);
 #define C3_LAUNCH(CPP_, PST_, BN_, WM_, WN_, NS_)                                                                                      \
-    hipLaunchKernelGGL((conv3_halo2_kernel<CPP_, PST_, BN_, WM_, WN_, NS_>), dim3(grid), dim3(64 * WM_ * WN_), 0, st, a, (const bf16_t*)W, M, N, Kpad, e1, xn)
+    do { note_kernel("conv3_halo2_kernel<" #CPP_ "," #PST_ "," #BN_ "," #WM_ "," #WN_ "," #NS_ ">");                                         \
+         hipLaunchKernelGGL((conv3_halo2_kernel<CPP_, PST_, BN_, WM_, WN_, NS_>), dim3(grid), dim3(64 * WM_ * WN_), 0, st, a, (const bf16_t*)W, M, N, Kpad, e1, xn); } while (0)
     if (a.C == 128) {
         if (bn == 128) C3_LAUNCH(16, 17, 128, 2, 4, 2);          // (row pitch 17 chunks: 2 blocks / CU; 18 would be conflict-free)
         else if (bn == 64) C3_LAUNCH(16, 17, 64, 4, 2, 3);

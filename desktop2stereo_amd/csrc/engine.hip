@@ -243,7 +243,7 @@ int pack_conv3(d2s_engine* e, const std::string& wname, const std::string& bname
     const float* b = nullptr;
     if (!bname.empty()) { const HostT* bt = find(e, bname); if (!bt || bt->data.size() != (size_t)Co) { set_error("bad bias " + bname); return D2S_E_MISSING; } b = bt->data.data(); }
     const float* p = w->data.data();
-    return pack_matrix(e, Co, 9 * Ci, [&](int n, int k) { int tap = k / Ci, ci = k % Ci; return p[((size_t)n * Ci + ci) * 9 + tap]; }, b, out);
+    return pack_matrix(e, Co, 9 * Ci, [&](int n, int k) { return p[conv3_weight_index(n, k, Ci)]; }, b, out);
 }
 
 // ConvTranspose2d k==s weight [Ci,Co,k,k] -> rows n = (ky*k+kx)*Co + co, K = Ci; bias expanded
@@ -308,11 +308,6 @@ GemmA splitA(const void* p, long lda, bool split) { GemmA a = plainA(p, lda); a.
 GemmA convA(const void* p, int Hi, int Wi, int C, int Ho, int Wo, int stride, int relu) {
     GemmA a = {}; a.ptr = p; a.mode = A_CONV3; a.Hi = Hi; a.Wi = Wi; a.C = C; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.relu = relu; return a;
 }
-// tile of the fused head launch: MAP_HEAD needs a tile whose waves own all N columns of their rows (WN == 1)
-int head_tile(int bn) {
-    return bn == 32 ? 912832 : 9256648;
-}
-
 GemmEpi rowsE(void* out, int out_type, long ldc, const float* bias) {
     GemmEpi e = {}; e.out = out; e.out_type = out_type; e.ldc = ldc; e.bias = bias; return e;
 }

@@ -95,6 +95,19 @@ int launch_gemm_sk(const GemmA& a, const void* W, int M, int N, int K, int Kpad,
 // smallest number of 256 x 256 tiles from which plain linears go to the ping-pong kernel (D2S_GEMM_PP; 0 = never)
 int gemm_pp_min_tiles();
 
+// Which kernel the last launch_gemm of this host thread ran: the launch sites record it (host side only, a few stores), and only
+// d2s_conv3_probe reads it -- the tests pin the dispatch with it.  tile: the implicit-GEMM tile code the launcher settled on (0 for
+// the LDS-resident-input kernels); ksplit > 1: split-K partials + splitk_reduce_kernel.
+struct KernelNote { const char* name; int tile; int ksplit; };
+KernelNote& kernel_note();
+static inline void note_kernel(const char* name, int ksplit = 1) { KernelNote& n = kernel_note(); n.name = name; n.ksplit = ksplit; }
+
+// tile of the fused head launch: MAP_HEAD needs a tile whose waves own all N columns of their rows (WN == 1)
+static inline int head_tile(int bn) { return bn == 32 ? 912832 : 9256648; }
+
+// Conv2d 3x3 weight [Co, Ci, 3, 3] in K order: element k = tap * Ci + ci (tap = ky * 3 + kx) of packed row n
+static inline size_t conv3_weight_index(int n, int k, int Ci) { const int tap = k / Ci, ci = k % Ci; return ((size_t)n * Ci + ci) * 9 + tap; }
+
 // packed-weight geometry
 static inline size_t elem_size(int precision) { return precision == D2S_PREC_BF16 ? 2 : (precision == D2S_PREC_FP8_OPERANDS ? 1 : 4); }   // fp32, bf16x3: 4
 // host-side packing of one bf16x3 weight row: element k of a row lives in unit k / 8

@@ -16,6 +16,8 @@
 //    convolution over an NHWC activation, with optional ReLU-on-load (pre-activation units); stride-1 convs on
 //    the large maps use conv3_halo_kernel (input tile resident in LDS) instead.
 #include "gemm_epi.h"
+#include <cstdio>
+#include <vector>
 
 namespace d2s {
 
@@ -656,8 +658,17 @@ static bool gemm_deep() {
 }
 
 // tile codes: 64 (64x64), 128 (128x128), 256128 / 256256 (8 waves), 25664 / 25632 (256 x 64|32, 4 waves); 0 = auto
+template <typename T> static const char* type_tag() {
+    if constexpr (std::is_same<T, bf16_t>::value) return "bf16";
+    else if constexpr (std::is_same<T, fp8_t>::value) return "e4m3";
+    else if constexpr (std::is_same<T, bx3_t>::value) return "bx3";
+    else return "f32";
+}
+
 template <typename T, int BM, int BN, int WM, int WN, int NS, int CPR = 8, int STG = 0>
 static void launch_glds(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
+    static const std::string name = std::string("gemm_glds_kernel<") + type_tag<T>() + "," + std::to_string(BM) + "," + std::to_string(BN) + "," +
+                                    std::to_string(WM) + "," + std::to_string(WN) + "," + std::to_string(NS) + "," + std::to_string(CPR) + "," + std::to_string(STG) + ">";
     unsigned grid = 0;
     int xn = pick_xn(cdiv(M, BM), cdiv(N, BN), BN, Kpad, sizeof(T), grid);
     // split-K for the few launches with almost no tiles but a long K loop (DPT 3x3 convs on the 11x19 /
@@ -670,6 +681,7 @@ static void launch_glds(const GemmA& a, const void* W, int M, int N, int K, int 
     }
     static EnvInt sk_force{"D2S_SPLITK_FORCE", 0};          // measurement aid (tools/splitk_probe.py): this many K ranges whatever the grid
     if (sk_force.get() > 1 && STG != 2 && e.part && !e.stats_out && nkt >= sk_force.get() && (size_t)sk_force.get() * M * N <= e.part_elems) ks = sk_force.get();
+    note_kernel(name.c_str(), ks);
     if (ks > 1) {
         GemmEpi e2 = e; e2.ksplit = ks;
         hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WM, WN, NS, CPR, STG>), dim3(grid, ks), dim3(64 * WM * WN), 0, st, (const T*)W, a.ptr, a.lda, M, N, K, Kpad, xn, a, e2);
@@ -704,7 +716,9 @@ static bool launch_conv_halo(const GemmA& a, const void* W, int M, int N, int K,
     GemmEpi e1 = e; e1.ksplit = 1;
     unsigned grid = 0;
 #define D2S_HALO(BN_, WM_, WN_, NS_)                                                                                  \
-    { int xn = pick_xn((int)tiles_m, cdiv(N, BN_), BN_, Kpad, sizeof(T), grid);                                       \
+    { static const std::string name = std::string("conv3_halo_kernel<") + type_tag<T>() + "," #BN_ "," #WM_ "," #WN_ "," #NS_ ">"; \
+      note_kernel(name.c_str());                                                                                      \
+      int xn = pick_xn((int)tiles_m, cdiv(N, BN_), BN_, Kpad, sizeof(T), grid);                                       \
       hipLaunchKernelGGL((conv3_halo_kernel<T, BN_, WM_, WN_, NS_>), dim3(grid), dim3(64 * WM_ * WN_), 0, st, a, (const T*)W, M, N, K, Kpad, e1, xn); }
     // (ring depth: what keeps two blocks per CU beside the 46 KB halo -- four 8 KB stages for 64 output channels, two 16 KB stages for 128)
     if (N <= 64) D2S_HALO(64, 4, 2, 4)
@@ -748,6 +762,7 @@ static int launch_bx3(int tile, const GemmA& a, const void* W, int M, int N, int
         else if (b64 >= 384) tile = 964;
         else tile = 93264;
     }
+    kernel_note().tile = tile;
     if (tile == 93264 || tile == 3264) launch_glds<T, 32, 64, 2, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
     else if (tile == 964 || tile == 64) launch_glds<T, 64, 64, 2, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
     else if (tile == 964128) launch_glds<T, 64, 128, 2, 4, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
@@ -817,6 +832,7 @@ static int launch_t(int tile, const GemmA& a, const void* W, int M, int N, int K
             if (a.mode == A_CONV3 && K >= 4096 && (long)cdiv(M, 128) * cdiv(N, 128) >= 300) tile = 1281288;
         }
     }
+    kernel_note().tile = tile;
     // Latency regime (batch 1-2: every block of the launch is resident at once, 1-2 per CU).  In-kernel stamps (tools/glds_timeline.py)
     // put a K tile at (LDS-DMA latency ~ 1 800 cycles) / (tiles in flight): 615 cycles with the 4-stage ring of the 32 x 64 tile, 1 100-1 300
     // with the 2-stage rings of the 8-wave tiles, next to 64-256 cycles of MFMA work.  The LDS those few blocks leave unused buys
@@ -926,6 +942,33 @@ __global__ void cast_pad_kernel(const float* __restrict__ src, void* __restrict_
 
 using namespace d2s;
 
+// ---- probes: host-side helpers -----------------------------------------------------------------
+namespace d2s {
+
+static thread_local KernelNote g_kernel_note = {};
+KernelNote& kernel_note() { return g_kernel_note; }
+
+namespace {
+struct ProbeBuf {                    // device scratch of a probe, freed on every return path
+    void* p = nullptr;
+    ProbeBuf() = default;
+    ProbeBuf(const ProbeBuf&) = delete;
+    ProbeBuf& operator=(const ProbeBuf&) = delete;
+    ~ProbeBuf() { if (p) (void)hipFree(p); }
+};
+
+// a split-K workspace as the engine holds one (engine.hip splitk_ws): elems fp32 partials followed by GEMM_PART_CTR_WORDS counter
+// words, zeroed in stream order -- the words behind the partials must be zero when a launch reads them (gemm.h)
+int alloc_splitk_ws(ProbeBuf& buf, size_t elems, hipStream_t st) {
+    const size_t bytes = (elems + GEMM_PART_CTR_WORDS) * sizeof(float);
+    D2S_HIP(hipMalloc(&buf.p, bytes));
+    D2S_HIP(hipMemsetAsync(buf.p, 0, bytes, st));
+    return D2S_OK;
+}
+}  // namespace
+
+}  // namespace d2s
+
 extern "C" int d2s_gemm_probe(const float* A, const float* Wt, const float* bias, float* Cout, int M, int N, int K,
                               int precision, int tile, int iters, void* stream) {
     D2S_REQUIRE(A && Wt && Cout && M > 0 && N > 0 && K > 0 && (N % 4 == 0) && iters >= 1, "bad argument");
@@ -934,28 +977,103 @@ extern "C" int d2s_gemm_probe(const float* A, const float* Wt, const float* bias
     int bf = precision;
     int Kp = gemm_kpad(K, precision), Np = gemm_npad(N);
     size_t es = elem_size(precision);
-    void *dA = nullptr, *dW = nullptr;
-    D2S_HIP(hipMalloc(&dA, (size_t)M * Kp * es));
-    D2S_HIP(hipMalloc(&dW, (size_t)Np * Kp * es));
-    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv((long)M * Kp, 256)), dim3(256), 0, st, A, dA, M, K, M, Kp, bf);
-    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv((long)Np * Kp, 256)), dim3(256), 0, st, Wt, dW, N, K, Np, Kp, bf == D2S_PREC_BF16X3 ? -bf : bf);
+    ProbeBuf dA, dW, dP;
+    D2S_HIP(hipMalloc(&dA.p, (size_t)M * Kp * es));
+    D2S_HIP(hipMalloc(&dW.p, (size_t)Np * Kp * es));
+    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv((long)M * Kp, 256)), dim3(256), 0, st, A, dA.p, M, K, M, Kp, bf);
+    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv((long)Np * Kp, 256)), dim3(256), 0, st, Wt, dW.p, N, K, Np, Kp, bf == D2S_PREC_BF16X3 ? -bf : bf);
     GemmA a = {};
-    a.ptr = dA; a.mode = A_PLAIN; a.lda = Kp;
+    a.ptr = dA.p; a.mode = A_PLAIN; a.lda = Kp;
     GemmEpi e = {};
     e.out = Cout; e.out_type = OUT_F32; e.ldc = N; e.bias = bias;
-    void* dP = nullptr;
     static EnvInt sk_force{"D2S_SPLITK_FORCE", 0};          // measurement aid: give the launch a split-K workspace
     if (sk_force.get() > 1) {
         const size_t pe = (size_t)sk_force.get() * M * N;
-        D2S_HIP(hipMalloc(&dP, pe * sizeof(float) + GEMM_PART_CTR_WORDS * 4));
-        e.part = (float*)dP; e.part_elems = pe;
+        int rc = alloc_splitk_ws(dP, pe, st);
+        if (rc != D2S_OK) return rc;
+        e.part = (float*)dP.p; e.part_elems = pe;
     }
     int rc = D2S_OK;
-    for (int i = 0; i < iters && rc == D2S_OK; ++i) rc = launch_gemm(precision, tile, a, dW, M, N, Kp, Kp, e, st);
+    for (int i = 0; i < iters && rc == D2S_OK; ++i) rc = launch_gemm(precision, tile, a, dW.p, M, N, Kp, Kp, e, st);
     hipError_t err = hipStreamSynchronize(st);
-    (void)hipFree(dA); (void)hipFree(dW); if (dP) (void)hipFree(dP);
     if (rc != D2S_OK) return rc;
     D2S_HIP(err);
+    return D2S_OK;
+}
+
+extern "C" int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream) {
+    D2S_REQUIRE(p && p->struct_size == sizeof(d2s_conv3_probe_params), "d2s_conv3_probe_params.struct_size must be sizeof(d2s_conv3_probe_params)");
+    p->kernel[0] = 0;
+    const int prec = p->precision, B = p->batch, C = p->C, N = p->N;
+    D2S_REQUIRE(prec == D2S_PREC_BF16 || prec == D2S_PREC_FP32 || prec == D2S_PREC_BF16X3, "bad precision (bf16, fp32 or bf16x3)");
+    D2S_REQUIRE(p->x && p->w && p->out && B > 0 && C > 0 && N > 0 && p->Hs > 0 && p->Ws > 0 && p->Hi > 0 && p->Wi > 0, "bad argument");
+    D2S_REQUIRE(p->stride == 1 || p->stride == 2, "stride must be 1 or 2");
+    const bool ups = p->Hs != p->Hi || p->Ws != p->Wi;
+    D2S_REQUIRE(!ups || p->stride == 1, "a folded up-sample needs stride 1");
+    D2S_REQUIRE(!p->map_head || (p->w3 && !p->res && p->act == 0 && p->stride == 1), "map_head: w3 needed; no residual, no act, stride 1");
+    hipStream_t st = (hipStream_t)stream;
+    const int Ho = (p->Hi + 2 - 3) / p->stride + 1, Wo = (p->Wi + 2 - 3) / p->stride + 1;
+    const long M = (long)B * Ho * Wo, nsrc = (long)B * p->Hs * p->Ws;
+    D2S_REQUIRE(M < (1L << 31) && nsrc * C < (1L << 31), "too large");
+    const int K = 9 * C, Kp = gemm_kpad(K, prec), Np = gemm_npad(N);
+    const bool bf = prec == D2S_PREC_BF16;             // bf16 engine: bf16 activations; fp32 / bf16x3 engines: fp32 activations
+    const bool out_t = !p->out_f32 && !p->map_head;    // OUT_T: bf16 on the bf16 engine, fp32 otherwise
+    ProbeBuf dWk, dW, dX, dR, dP;
+    // the weight in pack_conv3's K order (host permutation, the engine's index expression), then packed like d2s_gemm_probe's
+    {
+        std::vector<float> w((size_t)N * C * 9), wk((size_t)N * K);
+        D2S_HIP(hipMemcpy(w.data(), p->w, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int n = 0; n < N; ++n)
+            for (int k = 0; k < K; ++k) wk[(size_t)n * K + k] = w[conv3_weight_index(n, k, C)];
+        D2S_HIP(hipMalloc(&dWk.p, wk.size() * sizeof(float)));
+        D2S_HIP(hipMemcpy(dWk.p, wk.data(), wk.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    D2S_HIP(hipMalloc(&dW.p, (size_t)Np * Kp * elem_size(prec)));
+    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv((long)Np * Kp, 256)), dim3(256), 0, st, (const float*)dWk.p, dW.p, N, K, Np, Kp, prec == D2S_PREC_BF16X3 ? -prec : prec);
+    const void* x = p->x;
+    if (bf) {
+        D2S_HIP(hipMalloc(&dX.p, (size_t)nsrc * C * 2));
+        hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv(nsrc * C, 256)), dim3(256), 0, st, p->x, dX.p, (int)nsrc, C, (int)nsrc, C, D2S_PREC_BF16);
+        x = dX.p;
+    }
+    const void* res = p->res;                         // residual: the output's type
+    if (res && bf && out_t) {
+        D2S_HIP(hipMalloc(&dR.p, (size_t)M * N * 2));
+        hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv(M * N, 256)), dim3(256), 0, st, p->res, dR.p, (int)M, N, (int)M, N, D2S_PREC_BF16);
+        res = dR.p;
+    }
+    D2S_HIP(hipExtGetLastError());
+    // GemmA / GemmEpi as engine.hip builds them: convA() + conv3()'s rowsE for a convolution, the head's MAP_HEAD tail for conv2,
+    // the up-sample fields of the head's conv1 / conv2 launches
+    GemmA a = {};
+    a.ptr = x; a.mode = A_CONV3; a.Hi = p->Hi; a.Wi = p->Wi; a.C = C; a.Ho = Ho; a.Wo = Wo; a.stride = p->stride; a.relu = p->relu_in;
+    if (ups) { a.ups = 1; a.Hs = p->Hs; a.Ws = p->Ws; a.usy = linear_scale(p->Hs, p->Hi, true); a.usx = linear_scale(p->Ws, p->Wi, true); }
+    GemmEpi e = {};
+    e.out = p->out; e.out_type = out_t ? OUT_T : OUT_F32; e.ldc = N; e.bias = p->bias;
+    e.act = p->act ? ACT_RELU : ACT_NONE; e.res1 = res;
+    if (p->map_head) { e.ldc = 1; e.map = MAP_HEAD; e.scale = p->w3; e.head_b3 = p->b3; e.head_max_depth = p->max_depth; }
+    const int tile = p->tile ? p->tile : (p->map_head ? head_tile(N <= 32 ? 32 : 64) : 0);
+    if (p->splitk_elems > 0) {
+        int rc = alloc_splitk_ws(dP, (size_t)p->splitk_elems, st);
+        if (rc != D2S_OK) return rc;
+        e.part = (float*)dP.p; e.part_elems = (size_t)p->splitk_elems;
+    }
+    if (ups && !conv3_upsample_ok(prec, tile, a, (int)M, N, K, Kp, e)) {
+        set_error("d2s_conv3_probe: conv3_upsample_ok refuses to fold this up-sample");
+        return D2S_E_UNSUPPORTED;
+    }
+    kernel_note() = KernelNote{nullptr, 0, 1};
+    int rc = launch_gemm(prec, tile, a, dW.p, (int)M, N, K, Kp, e, st);
+    hipError_t err = hipStreamSynchronize(st);
+    if (rc != D2S_OK) return rc;
+    D2S_HIP(err);
+    const KernelNote kn = kernel_note();
+    std::string name = kn.name ? kn.name : "unrecorded";
+    if (kn.name && !strncmp(kn.name, "gemm_glds_kernel", 16)) {
+        name += " tile=" + std::to_string(kn.tile);
+        if (kn.ksplit > 1) name += " splitk=" + std::to_string(kn.ksplit);
+    }
+    snprintf(p->kernel, sizeof(p->kernel), "%s", name.c_str());
     return D2S_OK;
 }
 

@@ -507,6 +507,50 @@ def gemm_probe(A: torch.Tensor, Wt: torch.Tensor, bias: Optional[torch.Tensor], 
     return out
 
 
+def conv3_probe(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, precision: str = "bf16", *,
+                up: Optional[tuple] = None, stride: int = 1, relu_in: bool = False, act: str = "none",
+                res: Optional[torch.Tensor] = None, out_f32: bool = False, head: Optional[tuple] = None, tile: int = 0,
+                splitk_elems: int = 0):
+    """One 3x3 convolution (pad 1) of the DPT neck / head through the engine's own dispatcher (test probe, include/d2s.h).
+    x: float32 [B, Hs, Ws, C], w: float32 [N, C, 3, 3] (PyTorch layout), bias [N].  up = (Hi, Wi): an align_corners bilinear
+    up-sample of x to that size in front of the convolution, folded into its loader; stride 1 | 2; relu_in: ReLU on load;
+    act "none" | "relu" after the bias; res [B, Ho, Wo, N] added last; head = (w3 [N], b3, max_depth): the fused DPT head tail
+    (out = float depth [B, Ho, Wo]); splitk_elems > 0: a split-K workspace of that many partials, as the engine's.
+    Returns (out, kernel name): out [B, Ho, Wo, N] in the operand type (bfloat16 for "bf16") or float32 (out_f32 / head)."""
+    _need_cuda(x, "x")
+    B, Hs, Ws, Cin = x.shape
+    N = w.shape[0]
+    if tuple(w.shape) != (N, Cin, 3, 3):
+        raise ValueError("conv3_probe: w must be [N, C, 3, 3]")
+    Hi, Wi = up if up is not None else (Hs, Ws)
+    Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+    prec = {"bf16": PREC_BF16, "fp32": PREC_FP32, "bf16x3": _lib.PREC_BF16X3}[precision]
+    keep = [x.float().contiguous(), w.float().contiguous()]
+    p = _lib.Conv3ProbeParams()
+    p.struct_size = C.sizeof(_lib.Conv3ProbeParams)
+    p.precision, p.tile, p.batch, p.C, p.N = prec, int(tile), B, Cin, N
+    p.Hs, p.Ws, p.Hi, p.Wi, p.stride = Hs, Ws, Hi, Wi, int(stride)
+    p.relu_in, p.act, p.out_f32 = int(bool(relu_in)), {"none": 0, "relu": 1}[act], int(bool(out_f32))
+    p.splitk_elems = int(splitk_elems)
+    p.x, p.w = _ptr(keep[0]), _ptr(keep[1])
+    if bias is not None:
+        keep.append(bias.float().contiguous()); p.bias = _ptr(keep[-1])
+    if res is not None:
+        keep.append(res.float().contiguous()); p.res = _ptr(keep[-1])
+    if head is not None:
+        w3, b3, max_depth = head
+        keep.append(w3.float().contiguous()); p.w3 = _ptr(keep[-1])
+        p.map_head, p.b3, p.max_depth = 1, float(b3), float(max_depth)
+        out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=x.device)
+    else:
+        dt = torch.bfloat16 if precision == "bf16" and not out_f32 else torch.float32
+        out = torch.empty((B, Ho, Wo, N), dtype=dt, device=x.device)
+    p.out = _ptr(out)
+    with _on(x.device) as st:
+        check(_lib.load().d2s_conv3_probe(C.byref(p), st), "d2s_conv3_probe")
+    return out, p.kernel.decode()
+
+
 def attention_probe(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str = "bf16", iters: int = 1):
     """softmax(q k^T / 8) v for float32 [B, heads, N, 64] device tensors through the engine's attention kernel
     (test / micro-benchmark).  Returns (out [B, N, heads * 64] float32, ms per launch or 0)."""

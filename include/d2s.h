@@ -356,6 +356,35 @@ int d2s_gemm_probe(const float* A, const float* Wt, const float* bias, float* C,
 int d2s_attention_probe(const float* q, const float* k, const float* v, float* out, int B, int heads, int N,
                         int precision, int iters, float* ms_per_iter, void* stream);
 
+/* Stand-alone 3x3 convolution probe (tests): one convolution of the DPT neck / head through the engine's own dispatcher
+ * (launch_gemm), with the operands cast and packed as the engine casts and packs them.  Reports the kernel it ran. */
+typedef struct d2s_conv3_probe_params {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_conv3_probe_params) = 256 */
+    int32_t precision;         /* D2S_PREC_BF16 / D2S_PREC_FP32 / D2S_PREC_BF16X3 (operands; bf16: bf16 activations, else fp32) */
+    int32_t tile;              /* 0: what the engine passes (automatic; map_head: the fused head's tile); else a tile code */
+    int32_t batch, C, N;       /* images, input channels (multiple of 8 for bf16, of 4 otherwise), output channels (multiple of 4) */
+    int32_t Hs, Ws;            /* the input map x [batch, Hs, Ws, C] */
+    int32_t Hi, Wi;            /* the map the convolution sees; (Hs, Ws) != (Hi, Wi): an align_corners bilinear up-sample of x in front
+                                  of it, folded into the loader (bf16 only; D2S_E_UNSUPPORTED where the engine would not fold it) */
+    int32_t stride;            /* 1 | 2, pad 1: output Ho = (Hi - 1) / stride + 1, Wo likewise */
+    int32_t relu_in;           /* max(x, 0) on load */
+    int32_t act;               /* 0: none, 1: ReLU after the bias, before the residual */
+    int32_t out_f32;           /* 0: the operand type (bf16 for D2S_PREC_BF16, fp32 otherwise); 1: fp32 */
+    int32_t map_head;          /* 1: the DPT head's fused tail: out = float depth [batch, Ho, Wo] = act(b3 + sum_n w3[n] relu(conv + bias)),
+                                  act = ReLU (max_depth 0) or sigmoid * max_depth */
+    float   b3, max_depth;
+    int32_t reserved;          /* 0 */
+    int64_t splitk_elems;      /* > 0: a split-K workspace of this many fp32 partials, as the engine's (0: none) */
+    const float* x;            /* device, [batch, Hs, Ws, C] */
+    const float* w;            /* device, PyTorch layout [N, C, 3, 3] */
+    const float* bias;         /* device, [N] or null */
+    const float* res;          /* device, [batch, Ho, Wo, N] or null: added last */
+    const float* w3;           /* device, [N] (map_head) */
+    void* out;                 /* device, [batch, Ho, Wo, N] of the output type (bf16 = 2 bytes), or float [batch, Ho, Wo] (map_head) */
+    char kernel[128];          /* out: the kernel that ran, e.g. "conv3_wide_kernel<8,32>" or "gemm_glds_kernel<bf16,...> tile=3264 splitk=4" */
+} d2s_conv3_probe_params;
+int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,9 @@ def test_struct_layout_matches_header():
     assert (C.sizeof(_lib.DibrParams) == 80 and _lib.DibrParams.corner_radius.offset == 52 and _lib.DibrParams.viewport.offset == 56
             and _lib.DibrParams.alpha_mode.offset == 72 and _lib.DibrParams.struct_size.offset == 76)   # struct_size sits in what was tail padding
     assert C.sizeof(_lib.PreParams) == 32 and _lib.PreParams.std.offset == 12 and _lib.PreParams.resample.offset == 24 and _lib.PreParams.square.offset == 28
+    P = _lib.Conv3ProbeParams                                                                # d2s_conv3_probe_params
+    assert (C.sizeof(P) == 256 and P.precision.offset == 4 and P.map_head.offset == 56 and P.b3.offset == 60 and P.max_depth.offset == 64
+            and P.splitk_elems.offset == 72 and P.x.offset == 80 and P.out.offset == 120 and P.kernel.offset == 128)
 
 
 def test_sbs_shape_matches_reference_padding(lib):
