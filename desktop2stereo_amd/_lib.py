@@ -64,6 +64,23 @@ class Conv3ProbeParams(C.Structure):
                 ("out", C.c_void_p), ("kernel", C.c_char * 128)]
 
 
+class LinearProbeParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("site", C.c_int32), ("precision", C.c_int32), ("ln_fold", C.c_int32),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ntok", C.c_int32), ("heads", C.c_int32), ("npad", C.c_int32),
+                ("gh", C.c_int32), ("gw", C.c_int32), ("ks", C.c_int32), ("pK", C.c_int32), ("ln_eps", C.c_float),
+                ("s_act", C.c_float), ("s_out", C.c_float), ("s_res", C.c_float), ("s_pact", C.c_float), ("tile", C.c_int32),
+                ("splitk_elems", C.c_int64),
+                ("a", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_void_p), ("res", C.c_void_p), ("res2", C.c_void_p),
+                ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("pa", C.c_void_p), ("pw", C.c_void_p), ("pbias", C.c_void_p),
+                ("pscale", C.c_void_p), ("x", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p), ("vt", C.c_void_p),
+                ("stats", C.c_void_p), ("stats_slots", C.c_int32), ("reserved", C.c_int32),
+                ("kernel", C.c_char * 128), ("kernel2", C.c_char * 128)]
+
+
+LINEAR_SITES = {"patch": 0, "qkv": 1, "proj": 2, "fc1": 3, "fc2": 4, "neck_proj": 5, "neck_resize": 6, "tm_proj_in": 7,    # D2S_LIN_*
+                "tm_kvq": 8, "tm_ff1": 9, "tm_to_out": 10, "tm_ff2": 11, "tm_proj_out": 12}
+
+
 # every symbol include/d2s.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -119,6 +136,7 @@ SYMBOLS = {
     "d2s_gemm_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "d2s_attention_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "d2s_conv3_probe": (C.c_int, [C.POINTER(Conv3ProbeParams), _P]),
+    "d2s_linear_probe": (C.c_int, [C.POINTER(LinearProbeParams), _P]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "gemm.h"
+#include "linear_site.h"
 #include "vit_ops.h"
 
 using namespace d2s;
@@ -182,16 +183,8 @@ int upload_f32(d2s_engine* e, const std::string& name, size_t n, float** out) {
 // pack a logical [N][K] float matrix (given by accessor) into device [Npad][Kpad] T
 template <typename F>
 int pack_matrix(d2s_engine* e, int N, int K, F at, const float* bias_host, PackedW& out) {
-    int Kp = gemm_kpad(K, e->wprec), Np = gemm_npad(N);
-    size_t es = elem_size(e->wprec);
-    std::vector<uint8_t> buf((size_t)Np * Kp * es, 0);
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < K; ++k) {
-            float v = at(n, k);
-            if (e->wprec == D2S_PREC_BF16) ((bf16_t*)buf.data())[(size_t)n * Kp + k] = f2bf(v);
-            else if (e->wprec == D2S_PREC_BF16X3) bx3_pack_elem(buf.data() + (size_t)n * Kp * 4, k, v);      // [8 hi | 8 lo] units
-            else ((float*)buf.data())[(size_t)n * Kp + k] = v;
-        }
+    const int Kp = gemm_kpad(K, e->wprec);
+    const std::vector<uint8_t> buf = pack_rows_host(e->wprec, N, K, at);     // (linear_site.h)
     int rc = dev_alloc(e, &out.w, buf.size());
     if (rc) return rc;
     D2S_HIP(hipMemcpy(out.w, buf.data(), buf.size(), hipMemcpyHostToDevice));
@@ -208,16 +201,8 @@ int pack_matrix(d2s_engine* e, int N, int K, F at, const float* bias_host, Packe
 // e4m3 copy of a logical [N][K] matrix: row n is divided by s_w[n] = max|row| / 448 and rounded to e4m3 (RNE)
 template <typename F>
 int pack_matrix_fp8(d2s_engine* e, int N, int K, F at, const float* bias_dev, PackedW& out, std::vector<float>& sw) {
-    int Kp = gemm_kpad(K, D2S_PREC_FP8_OPERANDS), Np = gemm_npad(N);
-    std::vector<uint8_t> buf((size_t)Np * Kp, 0);
-    sw.assign(N, 1.f);
-    for (int n = 0; n < N; ++n) {
-        float amax = 0.f;
-        for (int k = 0; k < K; ++k) amax = fmaxf(amax, fabsf(at(n, k)));
-        float s = amax > 0.f ? amax / FP8_MAX : 1.f;
-        sw[n] = s;
-        for (int k = 0; k < K; ++k) buf[(size_t)n * Kp + k] = f2e4m3(at(n, k) / s);
-    }
+    const int Kp = gemm_kpad(K, D2S_PREC_FP8_OPERANDS);
+    const std::vector<uint8_t> buf = pack_rows_fp8_host(N, K, at, sw);      // (linear_site.h)
     int rc = dev_alloc(e, &out.w, buf.size());
     if (rc) return rc;
     D2S_HIP(hipMemcpy(out.w, buf.data(), buf.size(), hipMemcpyHostToDevice));
@@ -256,7 +241,7 @@ int pack_convT(d2s_engine* e, const std::string& wname, const std::string& bname
     int N = ks * ks * C;
     std::vector<float> bias(N);
     for (int n = 0; n < N; ++n) bias[n] = bt->data[n % C];
-    return pack_matrix(e, N, C, [&](int n, int k) { int tap = n / C, co = n % C; return p[((size_t)k * C + co) * ks * ks + tap]; }, bias.data(), out);
+    return pack_matrix(e, N, C, [&](int n, int k) { return p[convT_weight_index(n, k, C, ks)]; }, bias.data(), out);
 }
 
 // ---- bicubic (align_corners=False, A=-0.75) resample of the position table, float32 like torch ----
@@ -308,9 +293,6 @@ GemmA splitA(const void* p, long lda, bool split) { GemmA a = plainA(p, lda); a.
 GemmA convA(const void* p, int Hi, int Wi, int C, int Ho, int Wo, int stride, int relu) {
     GemmA a = {}; a.ptr = p; a.mode = A_CONV3; a.Hi = Hi; a.Wi = Wi; a.C = C; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.relu = relu; return a;
 }
-GemmEpi rowsE(void* out, int out_type, long ldc, const float* bias) {
-    GemmEpi e = {}; e.out = out; e.out_type = out_type; e.ldc = ldc; e.bias = bias; return e;
-}
 
 int gemm(d2s_engine* e, const GemmA& a, const PackedW& w, int M, const GemmEpi& ep, hipStream_t st) {
     int Kl = w.K % (e->prec == D2S_PREC_BF16 ? 8 : 4) ? w.Kpad : w.K;   // ragged K (patch embed): A is zero padded to Kpad
@@ -355,8 +337,8 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st,
     // 18 -> 11 launches per module.
     const bool fold = e->tm_fold && prec == D2S_PREC_BF16 && e->wprec != D2S_PREC_BF16X3;
     int slots = 0;
-    auto producer = [&](GemmEpi& ep) { if (fold) { ep.out2 = e->tm_a; ep.stats_out = e->tm_stats; ep.stats_slots = &slots; } };
-    auto consumer = [&](GemmEpi& ep, const float* csum) { ep.ln_stats = e->tm_stats; ep.ln_slots = slots; ep.ln_csum = csum; ep.ln_eps = 1e-5f; ep.ln_dim = C; };
+    auto producer = [&](GemmEpi& ep) { if (fold) epi_ln_producer(ep, e->tm_a, e->tm_stats, &slots); };
+    auto consumer = [&](GemmEpi& ep, const float* csum) { epi_ln_consumer(ep, e->tm_stats, slots, csum, 1e-5f, C); };
     // (folded: proj_in leaves its bf16 copy in tm_a, so the GroupNorm output it reads goes to tm_out -- free until the attention writes it)
     void* gn_out = fold ? e->tm_out : e->tm_a;
     PROF(PC_ELT, 0, 0, launch_groupnorm(prec, x, t.gn_g, t.gn_b, gn_out, S, C, 32, 1e-6f, st));
@@ -379,8 +361,7 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st,
         const int store_slot = (fold && e->tm_init) ? e->tm_head : -1;
         PROF(PC_ATTN, 4.0 * S * Tw * C, 0, launch_temporal_attn(prec, e->tm_kv, t.cache[a], t.ptab[a], e->tm_out, S, C, Tw, 31, e->tm_head, st, store_slot));
         {
-            GemmEpi ep = rowsE(e->tm_hs, OUT_F32, C, t.to_out[a].bias);
-            ep.res1 = e->tm_hs;
+            GemmEpi ep = epi_residual(e->tm_hs, C, t.to_out[a].bias, nullptr);
             producer(ep);
             RC(gemm(e, plainA(e->tm_out, C), t.to_out[a], S, ep, st));
         }
@@ -403,9 +384,8 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st,
         }
     }
     {
-        GemmEpi ep = rowsE(e->tm_hs, OUT_F32, C, t.ff2.bias);
-        ep.res1 = e->tm_hs;
-        if (fold) ep.out2 = e->tm_a;                    // the bf16 copy proj_out multiplies (no statistics: nothing normalises it)
+        GemmEpi ep = epi_residual(e->tm_hs, C, t.ff2.bias, nullptr);
+        if (fold) epi_ln_producer(ep, e->tm_a, nullptr, nullptr);     // the bf16 copy proj_out multiplies (no statistics: nothing normalises it)
         RC(gemm(e, plainA(e->tm_g, 4 * C), t.ff2, S, ep, st));
     }
     const void* a_out = e->tm_a;
@@ -431,16 +411,9 @@ int neck_proj(d2s_engine* e, int i, int B, hipStream_t st, bool fold) {
     const int D = d.hidden, Mp = B * e->P, c = d.neck[i];
     if (!fold) return gemm(e, plainA(e->tapbuf[i], D), e->re[i].proj, Mp, rowsE(e->rproj[i], OUT_T, c, e->re[i].proj.bias), st);
     GemmEpi ep = rowsE(e->rproj[i], OUT_T, c, e->re[i].proj_ln.bias);
-    ep.ln_slots = e->tap_slots; ep.ln_csum = e->re[i].csum; ep.ln_eps = d.ln_eps; ep.ln_dim = D;
-    if (B == 1) {                                      // one frame: skip its cls row by starting one row in
-        ep.ln_stats = e->lnstats + 2; ep.ln_M = e->N;
-        return gemm(e, plainA((const bf16_t*)e->lnbuf + D, D), e->re[i].proj_ln, Mp, ep, st);
-    }
-    // several frames: the projection runs over ALL token rows (one cls row per frame: 0.13 % more rows) and the store mapping drops
-    // them -- token t of frame b lands on patch row b * P + t - 1 (gemm_epi.h epilogue4: row_off < 0)
-    ep.ln_stats = e->lnstats;
-    ep.rows_per_img = e->N; ep.img_rows = e->P; ep.row_off = -1;
-    return gemm(e, plainA(e->lnbuf, D), e->re[i].proj_ln, B * e->N, ep, st);
+    epi_ln_consumer(ep, e->lnstats, e->tap_slots, e->re[i].csum, d.ln_eps, D);
+    const int skip = epi_tap_fold_rows(ep, B, e->N, e->P);     // one frame: start one row in; several: all token rows, cls rows dropped
+    return gemm(e, plainA((const bf16_t*)e->lnbuf + (size_t)skip * D, D), e->re[i].proj_ln, skip ? Mp : B * e->N, ep, st);
 }
 
 int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
@@ -450,9 +423,7 @@ int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
     int Hs = gh, Ws = gw;
     if (i < 2) {
         int ks = i == 0 ? 4 : 2;
-        GemmEpi ep = rowsE(e->rres[i], OUT_T, c, e->re[i].resize.bias);
-        ep.map = MAP_SHUFFLE; ep.gh = gh; ep.gw = gw; ep.ks = ks; ep.cout = c;
-        RC(gemm(e, plainA(e->rproj[i], c), e->re[i].resize, Mp, ep, st));
+        RC(gemm(e, plainA(e->rproj[i], c), e->re[i].resize, Mp, epi_convT(e->rres[i], c, e->re[i].resize.bias, gh, gw, ks), st));
         src = e->rres[i]; Hs = gh * ks; Ws = gw * ks;
     } else if (i == 3) {
         RC(conv3(e, e->rproj[i], B, gh, gw, c, 2, 0, e->re[i].resize, e->rres[i], ACT_NONE, nullptr, nullptr, st));
@@ -482,10 +453,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     // ---- embeddings (HF Dinov2Embeddings)
     if (x) PROF(PC_ELT, 0, 0, launch_patchify(prec, x, e->patchA, B, e->h, e->w, d.patch, e->patch.Kpad, e->cls, e->pos, e->resid, N, D, st));
     {
-        GemmEpi ep = rowsE(e->resid, OUT_F32, D, e->patch.bias);
-        ep.rows_per_img = P; ep.img_rows = N; ep.row_off = 1;
-        ep.res1 = e->pos; ep.res1_mod = P; ep.res1_off = 1;
-        RC(gemm(e, plainA(e->patchA, e->patch.Kpad), e->patch, Mp, ep, st));
+        RC(gemm(e, plainA(e->patchA, e->patch.Kpad), e->patch, Mp, epi_patch_embed(e->resid, D, e->patch.bias, e->pos, P, N), st));
     }
     if (e->taps) D2S_HIP(hipMemcpyAsync(e->tap_hidden, e->resid, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
     // ---- encoder (HF Dinov2Layer x L)
@@ -532,9 +500,8 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (!ln1_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, ly.ln1g, ly.ln1b, e->lnbuf, M, D, d.ln_eps, 0, 0, 0, st, f8a ? 1.0f / sa[0] : 0.f, x3));
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 0, st));
         {
-            GemmEpi ep = rowsE(e->qkv, f8 ? OUT_BF16 : (x3 ? OUT_BX3 : OUT_T), 3 * D, ln1_folded ? (f8a ? ly.w8_ln[0].bias : ly.qkv_ln.bias) : ly.qkv.bias);
-            ep.map = MAP_QKV; ep.vt = e->vt; ep.ntok = N; ep.npad = e->Npad; ep.qk_cols = 2 * D; ep.heads = d.heads;
-            if (ln1_folded) { ep.ln_stats = e->lnstats; ep.ln_slots = ln_slots; ep.ln_csum = f8a ? ly.csum8[0] : ly.csum_qkv; ep.ln_eps = d.ln_eps; ep.ln_dim = D; }
+            GemmEpi ep = epi_qkv(e->qkv, qkv_out_type(f8, x3), D, ln1_folded ? (f8a ? ly.w8_ln[0].bias : ly.qkv_ln.bias) : ly.qkv.bias, e->vt, N, e->Npad, d.heads);
+            if (ln1_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, f8a ? ly.csum8[0] : ly.csum_qkv, d.ln_eps, D);
             if (f8a) { ep.deq = ln1_folded ? ly.deq_ln[0] : ly.deq[0]; RC(gemm8(e, plainA(e->lnbuf, D), ln1_folded ? ly.w8_ln[0] : ly.w8[0], M, ep, st)); }
             else RC(gemm(e, splitA(e->lnbuf, D, x3), ln1_folded ? ly.qkv_ln : ly.qkv, M, ep, st));
         }
@@ -543,9 +510,8 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (am) RC(launch_amax(prec, e->attn, (long)M * D, am + 1, st));
         {
             if (pending_ln >= 0) { D2S_HIP(hipStreamWaitEvent(st, e->ev_ln[pending_ln], 0)); pending_ln = -1; }
-            GemmEpi ep = rowsE(e->resid, OUT_F32, D, ly.proj.bias);
-            ep.scale = ly.ls1; ep.res1 = e->resid;
-            if (lnf) { ep.out2 = e->lnbuf; ep.out2_bx3 = x3; ep.stats_out = e->lnstats; ep.stats_slots = &ln_slots; ep.out2_qscale = f8 ? 1.0f / sa[4] : 0.f; }
+            GemmEpi ep = epi_residual(e->resid, D, ly.proj.bias, ly.ls1);
+            if (lnf) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[4] : 0.f);
             if (f8a) { ep.deq = ly.deq[1]; RC(gemm8(e, plainA(e->attn, D), ly.w8[1], M, ep, st)); }
             else RC(gemm(e, splitA(e->attn, D, x3), ly.proj, M, ep, st));
         }
@@ -554,17 +520,15 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (am) RC(launch_amax(D2S_PREC_FP32, e->resid, (long)M * D, am + 4, st));       // (raw residual: the LN-folded FC1's A operand)
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 2, st));
         {
-            GemmEpi ep = rowsE(e->mlp, x3 ? OUT_BX3 : OUT_T, d.mlp, ln2_folded ? (f8 ? ly.w8_ln[1].bias : ly.fc1_ln.bias) : ly.fc1.bias);
-            ep.act = ACT_GELU;
-            if (ln2_folded) { ep.ln_stats = e->lnstats; ep.ln_slots = ln_slots; ep.ln_csum = f8 ? ly.csum8[1] : ly.csum_fc1; ep.ln_eps = d.ln_eps; ep.ln_dim = D; }
+            GemmEpi ep = epi_fc1(e->mlp, fc1_out_type(x3), d.mlp, ln2_folded ? (f8 ? ly.w8_ln[1].bias : ly.fc1_ln.bias) : ly.fc1.bias);
+            if (ln2_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, f8 ? ly.csum8[1] : ly.csum_fc1, d.ln_eps, D);
             if (f8) { ep.deq = ln2_folded ? ly.deq_ln[1] : ly.deq[2]; ep.out_qscale = 1.0f / sa[3]; RC(gemm8(e, plainA(e->lnbuf, D), ln2_folded ? ly.w8_ln[1] : ly.w8[2], M, ep, st)); }
             else RC(gemm(e, splitA(e->lnbuf, D, x3), ln2_folded ? ly.fc1_ln : ly.fc1, M, ep, st));
         }
         if (am) RC(launch_amax(prec, e->mlp, (long)M * d.mlp, am + 3, st));
         {
-            GemmEpi ep = rowsE(e->resid, OUT_F32, D, ly.fc2.bias);
-            ep.scale = ly.ls2; ep.res1 = e->resid;
-            if (lnf && (l + 1 < d.layers || tap_fold) && !(f8 && !f8a)) { ep.out2 = e->lnbuf; ep.out2_bx3 = x3; ep.stats_out = e->lnstats; ep.stats_slots = &ln_slots; ep.out2_qscale = f8 ? 1.0f / sa[5] : 0.f; }
+            GemmEpi ep = epi_residual(e->resid, D, ly.fc2.bias, ly.ls2);
+            if (lnf && (l + 1 < d.layers || tap_fold) && !(f8 && !f8a)) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[5] : 0.f);
             if (f8) { ep.deq = ly.deq[3]; RC(gemm8(e, plainA(e->mlp, d.mlp), ly.w8[3], M, ep, st)); }
             else RC(gemm(e, splitA(e->mlp, d.mlp, x3), ly.fc2, M, ep, st));
         }
@@ -771,16 +735,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
             // LN(x) W^T + b  =  rstd * (x W'^T - mean * colsum(W')) + (b + W beta),  W' = W diag(gamma)
             auto fold = [&](const HostT* g, const HostT* bt, int Nn, auto at, const float* bias, PackedW& out, float** csum) -> int {
                 std::vector<float> b2(Nn), cs(Nn);
-                for (int n = 0; n < Nn; ++n) {
-                    double sb = bias[n], sc = 0.0;
-                    for (int k = 0; k < D; ++k) {
-                        sb += (double)bt->data[k] * at(n, k);
-                        const float v = g->data[k] * at(n, k);              // colsum over what the MFMAs sum: bf16(W'), or its hi + lo halves
-                        const float hi = bf2f(f2bf(v));
-                        sc += e->wprec == D2S_PREC_BF16X3 ? (double)hi + (double)bf2f(f2bf(v - hi)) : (double)hi;
-                    }
-                    b2[n] = (float)sb; cs[n] = (float)sc;
-                }
+                for (int n = 0; n < Nn; ++n) ln_fold_row(e->wprec, D, g->data.data(), bt->data.data(), at, n, bias[n], b2[n], cs[n]);
                 int rc = pack_matrix(e, Nn, D, [&](int n, int k) { return g->data[k] * at(n, k); }, b2.data(), out);
                 if (rc) return rc;
                 rc = dev_alloc(e, (void**)csum, (size_t)Nn * sizeof(float));
@@ -808,12 +763,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
             auto fold8 = [&](const HostT* g, const HostT* bt, int Nn, auto at, const float* bias, int slot) -> int {
                 RC(pack_matrix_fp8(e, Nn, D, [&](int n, int k) { return g->data[k] * at(n, k); }, nullptr, ly.w8_ln[slot], ly.sw_ln[slot]));
                 std::vector<float> b2(Nn), cs(Nn);
-                for (int n = 0; n < Nn; ++n) {
-                    double sb = bias[n], sc = 0.0;
-                    const float sw = ly.sw_ln[slot][n];
-                    for (int k = 0; k < D; ++k) { sb += (double)bt->data[k] * at(n, k); sc += e4m32f(f2e4m3(g->data[k] * at(n, k) / sw)); }
-                    b2[n] = (float)sb; cs[n] = (float)(sc * sw);
-                }
+                for (int n = 0; n < Nn; ++n) ln_fold_row_fp8(D, g->data.data(), bt->data.data(), at, n, bias[n], ly.sw_ln[slot][n], b2[n], cs[n]);
                 RC(dev_alloc(e, (void**)&ly.w8_ln[slot].bias, (size_t)Nn * sizeof(float)));
                 D2S_HIP(hipMemcpy(ly.w8_ln[slot].bias, b2.data(), (size_t)Nn * sizeof(float), hipMemcpyHostToDevice));
                 RC(dev_alloc(e, (void**)&ly.csum8[slot], (size_t)Nn * sizeof(float)));
@@ -853,11 +803,8 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
             const int c = d.neck[i];
             const float* wp = wt->data.data();
             std::vector<float> b2(c), cs(c);
-            for (int n = 0; n < c; ++n) {
-                double sb = bt->data[n], sc = 0.0;
-                for (int k = 0; k < D; ++k) { sb += (double)bf->data[k] * wp[(size_t)n * D + k]; sc += bf2f(f2bf(gf->data[k] * wp[(size_t)n * D + k])); }
-                b2[n] = (float)sb; cs[n] = (float)sc;
-            }
+            auto at = [&](int n, int k) { return wp[(size_t)n * D + k]; };
+            for (int n = 0; n < c; ++n) ln_fold_row(D2S_PREC_BF16, D, gf->data.data(), bf->data.data(), at, n, bt->data[n], b2[n], cs[n]);     // (bf16 engines only: tap_fold)
             RC(pack_matrix(e, c, D, [&](int n, int k) { return gf->data[k] * wp[(size_t)n * D + k]; }, b2.data(), e->re[i].proj_ln));
             RC(dev_alloc(e, (void**)&e->re[i].csum, (size_t)c * sizeof(float)));
             D2S_HIP(hipMemcpy(e->re[i].csum, cs.data(), (size_t)c * sizeof(float), hipMemcpyHostToDevice));
@@ -919,11 +866,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
         // LN(x) W^T + b  =  rstd * (x W'^T - mean * colsum(W')) + (b + W beta),  W' = W diag(gamma): colsum over the bf16-rounded W'
         auto fold_ln = [&](const float* g, const float* bt, int Nn, int K, auto at, const float* bias, PackedW& out, float** csum) -> int {
             std::vector<float> b2(Nn), cs(Nn);
-            for (int n = 0; n < Nn; ++n) {
-                double sb = bias ? bias[n] : 0.0, sc = 0.0;
-                for (int k = 0; k < K; ++k) { sb += (double)bt[k] * at(n, k); sc += (double)bf2f(f2bf(g[k] * at(n, k))); }
-                b2[n] = (float)sb; cs[n] = (float)sc;
-            }
+            for (int n = 0; n < Nn; ++n) ln_fold_row(D2S_PREC_BF16, K, g, bt, at, n, bias ? bias[n] : 0.0, b2[n], cs[n]);     // (bf16 engines only: tm_fold)
             int rc = pack_matrix(e, Nn, K, [&](int n, int k) { return g[k] * at(n, k); }, b2.data(), out);
             if (rc) return rc;
             rc = dev_alloc(e, (void**)csum, (size_t)Nn * sizeof(float));
@@ -987,7 +930,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                 if (!g || !bt || !w1 || !b1) return D2S_E_MISSING;
                 const float* w1p = w1->data.data();
                 // GEGLU in the epilogue (ACT_GEGLU): packed row n' = 8 g + w holds x row 4 g + w (w < 4) or gate row 4C + 4 g + (w - 4)
-                auto orig = [C](int n) { const int g = n >> 3, w = n & 7; return w < 4 ? 4 * g + w : 4 * C + 4 * g + (w - 4); };
+                auto orig = [C](int n) { return geglu_row(n, C); };
                 std::vector<float> b1p((size_t)8 * C);
                 for (int n = 0; n < 8 * C; ++n) b1p[n] = b1->data[orig(n)];
                 RC(fold_ln(g->data.data(), bt->data.data(), 8 * C, C, [&](int n, int k) { return w1p[(size_t)orig(n) * C + k]; }, b1p.data(), t.ff1_ln, &t.csum_ff1));

@@ -96,11 +96,15 @@ int launch_gemm_sk(const GemmA& a, const void* W, int M, int N, int K, int Kpad,
 int gemm_pp_min_tiles();
 
 // Which kernel the last launch_gemm of this host thread ran: the launch sites record it (host side only, a few stores), and only
-// d2s_conv3_probe reads it -- the tests pin the dispatch with it.  tile: the implicit-GEMM tile code the launcher settled on (0 for
-// the LDS-resident-input kernels); ksplit > 1: split-K partials + splitk_reduce_kernel.
-struct KernelNote { const char* name; int tile; int ksplit; };
+// the probes (d2s_conv3_probe, d2s_linear_probe) read it -- the tests pin the dispatch with it.  tile: the implicit-GEMM tile code
+// the launcher settled on (0 for the other kernels); ksplit > 1: split-K partials + splitk_reduce_kernel (gemm_glds_kernel), or the
+// ping-pong kernel's tail tiles cut into ksplit units, tail = how they are finished.
+enum { NOTE_TAIL_NONE = 0, NOTE_TAIL_INKERNEL = 1, NOTE_TAIL_TWO_LAUNCH = 2, NOTE_TAIL_ROWSPLIT = 3 };
+struct KernelNote { const char* name; int tile; int ksplit; int tail; };
 KernelNote& kernel_note();
-static inline void note_kernel(const char* name, int ksplit = 1) { KernelNote& n = kernel_note(); n.name = name; n.ksplit = ksplit; }
+static inline void note_kernel(const char* name, int ksplit = 1, int tail = NOTE_TAIL_NONE) {
+    KernelNote& n = kernel_note(); n.name = name; n.ksplit = ksplit; n.tail = tail;
+}
 
 // tile of the fused head launch: MAP_HEAD needs a tile whose waves own all N columns of their rows (WN == 1)
 static inline int head_tile(int bn) { return bn == 32 ? 912832 : 9256648; }

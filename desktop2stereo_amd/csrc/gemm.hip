@@ -16,6 +16,7 @@
 //    convolution over an NHWC activation, with optional ReLU-on-load (pre-activation units); stride-1 convs on
 //    the large maps use conv3_halo_kernel (input tile resident in LDS) instead.
 #include "gemm_epi.h"
+#include "linear_site.h"
 #include <cstdio>
 #include <vector>
 
@@ -740,6 +741,7 @@ static int launch_bx3(int tile, const GemmA& a, const void* W, int M, int N, int
         if (b128 >= 400 && (N >= 1536 || b128 >= 900)) t = 1281288;
         else if (b64128 >= 280) t = 641288;
         else if (b64 >= 384) t = 64648;
+        kernel_note().tile = t;
         // (latency regime: the deep-ring lean instantiations, as in launch_t)
         const bool dp = gemm_deep() && buf_eligible(a, M, N, K, Kpad, 32, 4) &&
                         !splitk_wanted(e, (long)cdiv(M, t == 3264 ? 32 : 64) * cdiv(N, t == 641288 ? 128 : 64), K, 32);
@@ -965,6 +967,21 @@ int alloc_splitk_ws(ProbeBuf& buf, size_t elems, hipStream_t st) {
     D2S_HIP(hipMemsetAsync(buf.p, 0, bytes, st));
     return D2S_OK;
 }
+
+// the kernel the last launch recorded (kernel_note), as the probes report it: gemm_glds_kernel with its tile code and split-K ranges,
+// the ping-pong kernel with its tail units and how they are finished
+std::string noted_kernel() {
+    const KernelNote kn = kernel_note();
+    std::string name = kn.name ? kn.name : "unrecorded";
+    if (kn.name && !strncmp(kn.name, "gemm_glds_kernel", 16)) {
+        name += " tile=" + std::to_string(kn.tile);
+        if (kn.ksplit > 1) name += " splitk=" + std::to_string(kn.ksplit);
+    } else if (kn.name && kn.tail != NOTE_TAIL_NONE) {
+        static const char* const tails[4] = {"", "in-kernel", "two-launch", "row-split"};
+        name += " ks=" + std::to_string(kn.ksplit) + " tail=" + tails[kn.tail];
+    }
+    return name;
+}
 }  // namespace
 
 }  // namespace d2s
@@ -1067,13 +1084,233 @@ extern "C" int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream) {
     hipError_t err = hipStreamSynchronize(st);
     if (rc != D2S_OK) return rc;
     D2S_HIP(err);
-    const KernelNote kn = kernel_note();
-    std::string name = kn.name ? kn.name : "unrecorded";
-    if (kn.name && !strncmp(kn.name, "gemm_glds_kernel", 16)) {
-        name += " tile=" + std::to_string(kn.tile);
-        if (kn.ksplit > 1) name += " splitk=" + std::to_string(kn.ksplit);
+    snprintf(p->kernel, sizeof(p->kernel), "%s", noted_kernel().c_str());
+    return D2S_OK;
+}
+
+// ---- d2s_linear_probe ---------------------------------------------------------------------------------------------------
+namespace d2s {
+namespace {
+enum { ACT_F32 = 0, ACT_BF16 = 1, ACT_BX3 = 2, ACT_E4M3 = 3 };   // activation formats the engine's producers write
+size_t act_bytes(int fmt) { return fmt == ACT_BF16 ? 2 : (fmt == ACT_E4M3 ? 1 : 4); }
+
+// host copy of a device float matrix
+int fetch_f32(std::vector<float>& h, const float* d, size_t n) {
+    h.resize(n);
+    D2S_HIP(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2S_OK;
+}
+int upload(ProbeBuf& buf, const void* h, size_t bytes) {
+    D2S_HIP(hipMalloc(&buf.p, bytes));
+    D2S_HIP(hipMemcpy(buf.p, h, bytes, hipMemcpyHostToDevice));
+    return D2S_OK;
+}
+// an activation matrix [M, K] (device fp32) as the engine's producers leave it, rows lda elements apart (zero padded): bf16 (RNE), the
+// pre-split bf16x3 units, e4m3 of x * qscale (RNE, saturating at +-448: the LayerNorm kernel's / GELU epilogue's conversion) or fp32
+int act_operand(ProbeBuf& buf, const float* x, int M, int K, int lda, int fmt, float qscale) {
+    std::vector<float> h;
+    int rc = fetch_f32(h, x, (size_t)M * K);
+    if (rc != D2S_OK) return rc;
+    std::vector<uint8_t> o((size_t)M * lda * act_bytes(fmt), 0);
+    for (int m = 0; m < M; ++m)
+        for (int k = 0; k < K; ++k) {
+            const float v = h[(size_t)m * K + k];
+            const size_t i = (size_t)m * lda + k;
+            if (fmt == ACT_BF16) ((bf16_t*)o.data())[i] = f2bf(v);
+            else if (fmt == ACT_E4M3) o[i] = f2e4m3(v * qscale);
+            else if (fmt == ACT_BX3) bx3_pack_elem(o.data() + (size_t)m * lda * 4, k, v);
+            else ((float*)o.data())[i] = v;
+        }
+    return upload(buf, o.data(), o.size());
+}
+
+// one packed linear: weight rows in the kernel's order, bias / csum / deq vectors
+struct ProbeLinear {
+    ProbeBuf w, bias, csum, deq;
+    int Kp = 0;
+};
+// W [N, K] through at(n, k) (the packed row order), bias through b(n); LayerNorm gamma / beta folded in (g != null) as engine.hip
+// folds it; e4m3 (fp8): per-row scales, deq = s_a * s_w (d2s_engine_calibrate)
+template <typename F, typename Bf>
+int pack_probe_linear(ProbeLinear& L, int wprec, bool fp8, int N, int K, F at, Bf b, bool has_bias, const float* g, const float* beta, float s_a) {
+    std::vector<float> bias(N, 0.f), cs(N, 0.f);
+    for (int n = 0; n < N; ++n) bias[n] = has_bias ? b(n) : 0.f;
+    auto atg = [&](int n, int k) { return g ? g[k] * at(n, k) : at(n, k); };
+    std::vector<uint8_t> wb;
+    std::vector<float> sw;
+    if (fp8) { wb = pack_rows_fp8_host(N, K, atg, sw); L.Kp = gemm_kpad(K, D2S_PREC_FP8_OPERANDS); }
+    else { wb = pack_rows_host(wprec, N, K, atg); L.Kp = gemm_kpad(K, wprec); }
+    int rc = D2S_OK;
+    if (g) {
+        for (int n = 0; n < N; ++n) {
+            const double b0 = has_bias ? (double)b(n) : 0.0;
+            if (fp8) ln_fold_row_fp8(K, g, beta, at, n, b0, sw[n], bias[n], cs[n]);
+            else ln_fold_row(wprec, K, g, beta, at, n, b0, bias[n], cs[n]);
+        }
+        rc = upload(L.csum, cs.data(), cs.size() * sizeof(float));
+        if (rc != D2S_OK) return rc;
     }
-    snprintf(p->kernel, sizeof(p->kernel), "%s", name.c_str());
+    rc = upload(L.w, wb.data(), wb.size());
+    if (rc != D2S_OK) return rc;
+    if (has_bias || g) { rc = upload(L.bias, bias.data(), bias.size() * sizeof(float)); if (rc != D2S_OK) return rc; }
+    if (fp8) {
+        std::vector<float> dq(N);
+        for (int n = 0; n < N; ++n) dq[n] = s_a * sw[n];
+        rc = upload(L.deq, dq.data(), dq.size() * sizeof(float));
+    }
+    return rc;
+}
+}  // namespace
+}  // namespace d2s
+
+extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
+    D2S_REQUIRE(p && p->struct_size == sizeof(d2s_linear_probe_params), "d2s_linear_probe_params.struct_size must be sizeof(d2s_linear_probe_params)");
+    p->kernel[0] = 0; p->kernel2[0] = 0; p->stats_slots = 0;
+    const int prec = p->precision, site = p->site, M = p->M, N = p->N, K = p->K;
+    D2S_REQUIRE(prec == D2S_PREC_FP32 || prec == D2S_PREC_BF16 || prec == D2S_PREC_BF16X3 || prec == D2S_PREC_FP8 || prec == D2S_PREC_FP8_MLP, "bad precision");
+    D2S_REQUIRE(site >= D2S_LIN_PATCH && site <= D2S_LIN_TM_PROJ_OUT, "bad site");
+    D2S_REQUIRE(M > 0 && N > 0 && K > 0 && p->w, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    // the engine's precisions (d2s_engine_create): e->prec (activations), e->wprec (weights, GEMM operands); f8 / f8a as in forward()
+    const bool x3 = prec == D2S_PREC_BF16X3, f8 = prec == D2S_PREC_FP8 || prec == D2S_PREC_FP8_MLP, f8a = prec == D2S_PREC_FP8;
+    const int wprec = x3 ? D2S_PREC_BF16X3 : (f8 ? D2S_PREC_BF16 : prec);
+    const int aprec = x3 ? D2S_PREC_FP32 : (f8 ? D2S_PREC_BF16 : prec);
+    const bool enc = site == D2S_LIN_QKV || site == D2S_LIN_PROJ || site == D2S_LIN_FC1 || site == D2S_LIN_FC2;
+    const bool e8 = f8 && (site == D2S_LIN_FC1 || site == D2S_LIN_FC2 || (f8a && (site == D2S_LIN_QKV || site == D2S_LIN_PROJ)));   // gemm8
+    const bool fold = p->ln_fold != 0;
+    const bool consumer = fold && (site == D2S_LIN_QKV || site == D2S_LIN_FC1 || site == D2S_LIN_NECK_PROJ || site == D2S_LIN_TM_KVQ || site == D2S_LIN_TM_FF1);
+    const bool producer = fold && !consumer;
+    D2S_REQUIRE(!producer || site == D2S_LIN_PROJ || site == D2S_LIN_FC2 || site == D2S_LIN_TM_PROJ_IN || site == D2S_LIN_TM_TO_OUT || site == D2S_LIN_TM_FF2,
+                "ln_fold: not a LayerNorm consumer or producer site");
+    // where the engine folds: forward() lnf / ln1_folded (encoder: bf16, bf16x3, e4m3 -- MLP-only e4m3: not around QKV), tap_fold and
+    // run_temporal's tm_fold (bf16 only)
+    D2S_REQUIRE(!fold || (enc ? (prec != D2S_PREC_FP32 && !(prec == D2S_PREC_FP8_MLP && (site == D2S_LIN_QKV || site == D2S_LIN_FC2))) : prec == D2S_PREC_BF16),
+                "ln_fold: the engine does not fold LayerNorm there in this precision");
+    const bool per_frame = site == D2S_LIN_QKV || site == D2S_LIN_PATCH || site == D2S_LIN_NECK_PROJ;
+    const int P = p->ntok - 1;
+    D2S_REQUIRE(!per_frame || (p->ntok > 1 && M % (site == D2S_LIN_PATCH ? P : p->ntok) == 0), "M must be a multiple of the rows per frame");
+    const int B = per_frame ? M / (site == D2S_LIN_PATCH ? P : p->ntok) : 1;
+    D2S_REQUIRE(site != D2S_LIN_QKV || (p->vt && p->heads > 0 && N == 3 * K && K == 64 * p->heads && p->npad >= p->ntok), "QKV: N = 3 K, K = 64 heads, vt, npad >= ntok");
+    D2S_REQUIRE(site != D2S_LIN_NECK_RESIZE || (p->ks > 0 && p->gh > 0 && p->gw > 0 && N == p->ks * p->ks * K && M % (p->gh * p->gw) == 0), "NECK_RESIZE: N = ks^2 K, M = B gh gw");
+    D2S_REQUIRE(site != D2S_LIN_TM_FF1 || !consumer || N % 8 == 0, "GEGLU: N must be a multiple of 8");
+    D2S_REQUIRE(!x3 || (site != D2S_LIN_QKV && site != D2S_LIN_FC1) || (N % 8 == 0 && K % 8 == 0), "bf16x3 unit-format outputs: whole units (N % 8 == 0)");
+    D2S_REQUIRE(!consumer || (p->pa && p->pw && p->pK > 0 && p->ln_g && p->ln_b && p->x && p->out2 && p->stats), "ln_fold consumer: pa, pw, ln_g, ln_b, x, out2, stats");
+    D2S_REQUIRE(!producer || (p->out2 && (site == D2S_LIN_TM_FF2 || p->stats)), "ln_fold producer: out2, stats");
+    const bool x_out = site == D2S_LIN_PATCH || site == D2S_LIN_PROJ || site == D2S_LIN_FC2 || site == D2S_LIN_TM_PROJ_IN || site == D2S_LIN_TM_TO_OUT || site == D2S_LIN_TM_FF2;
+    D2S_REQUIRE(x_out ? p->x != nullptr : p->out != nullptr, "x (residual-stream sites) / out needed");
+    // e->splitk_ws: gemm() hands it to every row-mapped launch; gemm8 hands over none
+    ProbeBuf ws;
+    if (p->splitk_elems > 0) { int rc = alloc_splitk_ws(ws, (size_t)p->splitk_elems, st); if (rc != D2S_OK) return rc; }
+    auto launch = [&](bool fp8_ops, const GemmA& a, const ProbeLinear& L, int rows, int n, int Kl, GemmEpi ep, char* name) -> int {
+        if (!fp8_ops && ep.map == MAP_ROWS && ws.p) { ep.part = (float*)ws.p; ep.part_elems = (size_t)p->splitk_elems; }
+        kernel_note() = KernelNote{nullptr, 0, 1, NOTE_TAIL_NONE};
+        int rc = launch_gemm(fp8_ops ? D2S_PREC_FP8_OPERANDS : wprec, p->tile, a, L.w.p, rows, n, Kl, L.Kp, ep, st);
+        if (rc != D2S_OK) return rc;
+        snprintf(name, 128, "%s", noted_kernel().c_str());
+        return D2S_OK;
+    };
+    auto ragged_k = [&](int k, int kp) { return k % (aprec == D2S_PREC_BF16 ? 8 : 4) ? kp : k; };    // gemm(): ragged K -> zero-padded Kpad
+    // the raw residual copy: bf16, the unit format (bf16x3), e4m3 of v / s_res where an e4m3 linear consumes it
+    const int ofmt = x3 ? ACT_BX3 : ((consumer ? e8 : f8) ? ACT_E4M3 : ACT_BF16);
+    const float o2q = ofmt == ACT_E4M3 ? 1.0f / p->s_res : 0.f;
+    // ---- the producer of a LayerNorm-folded consumer: the residual update x += pscale * (pa pW^T + pbias) -> out2, stats, slots
+    int slots = 0;
+    ProbeBuf dPa;
+    ProbeLinear Lp;
+    if (consumer) {
+        const bool p8 = f8a;                               // (all-four e4m3: FC2 / proj on e4m3 operands; MLP-only: proj in bf16)
+        const int pK = p->pK, D = K;
+        std::vector<float> hw, hb;
+        int rc = fetch_f32(hw, p->pw, (size_t)D * pK);
+        if (rc == D2S_OK && p->pbias) rc = fetch_f32(hb, p->pbias, D);
+        if (rc != D2S_OK) return rc;
+        rc = pack_probe_linear(Lp, wprec, p8, D, pK, [&](int n, int k) { return hw[(size_t)n * pK + k]; }, [&](int n) { return hb[n]; }, p->pbias != nullptr,
+                               nullptr, nullptr, p->s_pact);
+        if (rc != D2S_OK) return rc;
+        const int pfmt = p8 ? ACT_E4M3 : (x3 ? ACT_BX3 : (aprec == D2S_PREC_BF16 ? ACT_BF16 : ACT_F32));
+        rc = act_operand(dPa, p->pa, M, pK, pK, pfmt, p8 ? 1.0f / p->s_pact : 0.f);
+        if (rc != D2S_OK) return rc;
+        GemmA a = {}; a.ptr = dPa.p; a.mode = A_PLAIN; a.lda = pK; a.bx3 = pfmt == ACT_BX3;
+        GemmEpi ep = epi_residual(p->x, D, (const float*)Lp.bias.p, p->pscale);
+        epi_ln_producer(ep, p->out2, p->stats, &slots, x3, o2q);
+        if (p8) ep.deq = (const float*)Lp.deq.p;
+        rc = launch(p8, a, Lp, M, D, p8 ? pK : ragged_k(pK, Lp.Kp), ep, p->kernel2);
+        if (rc != D2S_OK) return rc;
+        p->stats_slots = slots;
+        if (slots < 1 || slots > 16) { set_error("d2s_linear_probe: the producer leaves no statistics a consumer takes (the engine runs the LayerNorm kernel)"); return D2S_E_UNSUPPORTED; }
+    }
+    // ---- this linear's weights, in the packed row order: pack_convT's taps, the GEGLU interleave (x | gate in groups of four), else W's own
+    ProbeLinear L;
+    {
+        std::vector<float> hw, hb, hg, hbt;
+        const int Co = site == D2S_LIN_NECK_RESIZE ? K : 0, ks = p->ks;
+        int rc = fetch_f32(hw, p->w, (size_t)N * K);
+        if (rc == D2S_OK && p->bias) rc = fetch_f32(hb, p->bias, Co ? Co : N);
+        if (rc == D2S_OK && consumer) rc = fetch_f32(hg, p->ln_g, K);
+        if (rc == D2S_OK && consumer) rc = fetch_f32(hbt, p->ln_b, K);
+        if (rc != D2S_OK) return rc;
+        const bool geglu = consumer && site == D2S_LIN_TM_FF1;
+        auto row = [&](int n) { return geglu ? geglu_row(n, N / 8) : n; };
+        auto at = [&](int n, int k) { return Co ? hw[convT_weight_index(n, k, Co, ks)] : hw[(size_t)row(n) * K + k]; };
+        auto bias = [&](int n) { return Co ? hb[n % Co] : hb[row(n)]; };
+        rc = pack_probe_linear(L, wprec, e8, N, K, at, bias, p->bias != nullptr, consumer ? hg.data() : nullptr, consumer ? hbt.data() : nullptr,
+                               consumer ? p->s_res : p->s_act);
+        if (rc != D2S_OK) return rc;
+    }
+    // ---- A: the producer's raw residual copy (folded consumers), else the operand as its producer in the engine writes it
+    ProbeBuf dA, dR, dR2;
+    const int afmt = consumer ? ofmt : (e8 ? ACT_E4M3 : (x3 && enc ? ACT_BX3 : (aprec == D2S_PREC_BF16 ? ACT_BF16 : ACT_F32)));
+    int rows = site == D2S_LIN_NECK_PROJ ? B * P : M;
+    const int lda = site == D2S_LIN_PATCH ? L.Kp : K;                                // patchify's rows: Kpad, zero padded
+    if (!consumer) {
+        D2S_REQUIRE(p->a, "a needed");
+        int rc = act_operand(dA, p->a, rows, K, lda, afmt, e8 ? 1.0f / p->s_act : 0.f);
+        if (rc != D2S_OK) return rc;
+    }
+    GemmA a = {}; a.ptr = consumer ? p->out2 : dA.p; a.mode = A_PLAIN; a.lda = lda; a.bx3 = afmt == ACT_BX3;
+    // ---- the epilogue, as the engine's launch site builds it
+    const float* bias = (const float*)L.bias.p;
+    GemmEpi ep = {};
+    switch (site) {
+        case D2S_LIN_PATCH: ep = epi_patch_embed(p->x, N, bias, p->res, P, p->ntok); break;
+        case D2S_LIN_QKV: ep = epi_qkv(p->out, qkv_out_type(f8, x3), K, bias, p->vt, p->ntok, p->npad, p->heads); break;
+        case D2S_LIN_PROJ: case D2S_LIN_FC2: ep = epi_residual(p->x, N, bias, p->scale); break;
+        case D2S_LIN_TM_TO_OUT: case D2S_LIN_TM_FF2: ep = epi_residual(p->x, N, bias, nullptr); break;
+        case D2S_LIN_TM_PROJ_IN: ep = rowsE(p->x, OUT_F32, N, bias); break;
+        case D2S_LIN_FC1: ep = epi_fc1(p->out, fc1_out_type(x3), N, bias); if (e8) ep.out_qscale = 1.0f / p->s_out; break;
+        case D2S_LIN_NECK_RESIZE: ep = epi_convT(p->out, K, bias, p->gh, p->gw, p->ks); break;
+        case D2S_LIN_TM_FF1:
+            if (consumer) { ep = rowsE(p->out, OUT_T, N / 2, bias); ep.act = ACT_GEGLU; }
+            else ep = rowsE(p->out, OUT_T, N, bias);
+            break;
+        case D2S_LIN_TM_PROJ_OUT: {
+            ep = rowsE(p->out, OUT_T, N, bias);
+            const int rfmt = aprec == D2S_PREC_BF16 ? ACT_BF16 : ACT_F32;               // residuals: the output's type
+            if (p->res) { int rc = act_operand(dR, p->res, M, N, N, rfmt, 0.f); if (rc != D2S_OK) return rc; ep.res1 = dR.p; }
+            if (p->res2) { int rc = act_operand(dR2, p->res2, M, N, N, rfmt, 0.f); if (rc != D2S_OK) return rc; ep.res2 = dR2.p; }
+            break;
+        }
+        default: ep = rowsE(p->out, OUT_T, N, bias); break;                             // NECK_PROJ, TM_KVQ
+    }
+    if (e8) ep.deq = (const float*)L.deq.p;
+    if (producer) {
+        if (site == D2S_LIN_TM_FF2) epi_ln_producer(ep, p->out2, nullptr, nullptr);
+        else epi_ln_producer(ep, p->out2, p->stats, &slots, x3, o2q);
+    }
+    if (consumer) {
+        epi_ln_consumer(ep, p->stats, slots, (const float*)L.csum.p, p->ln_eps, K);
+        rows = M;
+        if (site == D2S_LIN_NECK_PROJ) {
+            const int skip = epi_tap_fold_rows(ep, B, p->ntok, P);
+            a.ptr = (const uint8_t*)p->out2 + (size_t)skip * K * act_bytes(afmt);
+            if (skip) rows = P;
+        }
+    }
+    int rc = launch(e8, a, L, rows, N, e8 ? K : ragged_k(K, L.Kp), ep, p->kernel);
+    hipError_t err = hipStreamSynchronize(st);
+    if (rc != D2S_OK) return rc;
+    D2S_HIP(err);
+    if (producer) p->stats_slots = slots;
     return D2S_OK;
 }
 

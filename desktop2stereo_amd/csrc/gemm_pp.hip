@@ -1020,6 +1020,16 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     }
     const int list_max = cdiv(tw, 8) + (ks > 1 ? ((ink & 1) ? cdiv(tiles - tw, 8) * ks : cdiv((tiles - tw) * ks, 8)) : 0);      // longest XCD unit list
     const unsigned grid = 8u * (unsigned)std::max(1, std::min(ncu / 8, list_max));
+    {
+        static const char* const names[2][7] = {
+            {"gemm_pp_kernel<bf16,PP_K_BF16>", "gemm_pp_kernel<bf16,PP_K_GELU>", "gemm_pp_kernel<bf16,PP_K_QKV>", "gemm_pp_kernel<bf16,PP_K_F32>",
+             "gemm_pp_kernel<bf16,PP_K_GELU_LN>", "gemm_pp_kernel<bf16,PP_K_QKV_LN>", "gemm_pp_kernel<bf16,PP_K_F32_LN>"},
+            {"gemm_pp_kernel<e4m3,PP_K_BF16>", "gemm_pp_kernel<e4m3,PP_K_GELU>", "gemm_pp_kernel<e4m3,PP_K_QKV>", "gemm_pp_kernel<e4m3,PP_K_F32>",
+             nullptr, nullptr, nullptr}};                      // (the LN kinds: bf16 only, pp_supported)
+        note_kernel(names[precision == D2S_PREC_BF16 ? 0 : 1][kind], ks,
+                    ks == 1 ? NOTE_TAIL_NONE : ((ink & 4) ? NOTE_TAIL_ROWSPLIT : (ink ? NOTE_TAIL_INKERNEL : NOTE_TAIL_TWO_LAUNCH)));
+        kernel_note().tile = 256256;
+    }
     GemmEpi e1 = e;
     e1.ksplit = 1;
     if (!e1.bias) e1.bias = pp_const_vec(false);

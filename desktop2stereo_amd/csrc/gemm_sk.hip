@@ -115,6 +115,10 @@ int launch_gemm_sk(const GemmA& a, const void* W, int M, int N, int K, int Kpad,
     int per_col = std::max(1, std::min(tiles_m, (2 * ncu) / cols));
     GemmEpi e1 = e; e1.ksplit = 1;
     const dim3 grid(cols, per_col), block(256);
+    static const char* const names[8] = {"gemm_sk_kernel<1>", "gemm_sk_kernel<2>", "gemm_sk_kernel<3>", "gemm_sk_kernel<4>",
+                                         "gemm_sk_kernel<5>", "gemm_sk_kernel<6>", "gemm_sk_kernel<7>", "gemm_sk_kernel<8>"};
+    note_kernel(names[std::min(std::max(K / 32, 1), 8) - 1]);        // (sk_supported, checked above: 32 <= K <= 256)
+    kernel_note().tile = 0;
 #define SK_LAUNCH(KS_) hipLaunchKernelGGL((gemm_sk_kernel<KS_>), grid, block, 0, st, (const bf16_t*)a.ptr, a.lda, (const bf16_t*)W, Kpad, M, N, e1)
     switch (K / 32) {
         case 1: SK_LAUNCH(1); break; case 2: SK_LAUNCH(2); break; case 3: SK_LAUNCH(3); break; case 4: SK_LAUNCH(4); break;

@@ -1,0 +1,140 @@
+// The engine's linears, site by site: the GemmEpi each launch site builds (engine.hip forward, neck_proj, neck_rest, run_temporal)
+// and the host-side packing of their weights (plain, e4m3, LayerNorm folded).  Shared with d2s_linear_probe (gemm.hip), which
+// launches exactly what the engine launches.  Host side only.
+#pragma once
+#include "gemm.h"
+#include <cmath>
+#include <vector>
+
+namespace d2s {
+
+// ---- epilogues -----------------------------------------------------------------------------------------------------------
+static inline GemmEpi rowsE(void* out, int out_type, long ldc, const float* bias) {
+    GemmEpi e = {}; e.out = out; e.out_type = out_type; e.ldc = ldc; e.bias = bias; return e;
+}
+
+// patch embedding: patch row m of frame b lands on token row b * ntok + 1 + m % P of the fp32 residual stream (row 0: the cls token,
+// written by patchify), plus the position embedding of that token (pos [ntok, D])
+static inline GemmEpi epi_patch_embed(float* resid, int D, const float* bias, const float* pos, int P, int ntok) {
+    GemmEpi e = rowsE(resid, OUT_F32, D, bias);
+    e.rows_per_img = P; e.img_rows = ntok; e.row_off = 1;
+    e.res1 = pos; e.res1_mod = P; e.res1_off = 1;
+    return e;
+}
+
+// QKV output type: bf16 for the attention on the e4m3 engines, the pre-split unit format on bf16x3 engines, else the operand type
+static inline int qkv_out_type(bool f8, bool x3) { return f8 ? OUT_BF16 : (x3 ? OUT_BX3 : OUT_T); }
+// FC1 output type: the A operand of FC2 (pre-split on bf16x3 engines)
+static inline int fc1_out_type(bool x3) { return x3 ? OUT_BX3 : OUT_T; }
+
+// QKV: q | k as rows [M, 3D] (the first 2D columns), v transposed to vt [B, heads, 64, npad] (token t of frame b = row b * ntok + t)
+static inline GemmEpi epi_qkv(void* qkv, int out_type, int D, const float* bias, void* vt, int ntok, int npad, int heads) {
+    GemmEpi e = rowsE(qkv, out_type, 3 * D, bias);
+    e.map = MAP_QKV; e.vt = vt; e.ntok = ntok; e.npad = npad; e.qk_cols = 2 * D; e.heads = heads;
+    return e;
+}
+
+// the fp32 residual stream updated in place (proj / FC2 with LayerScale ls, a temporal module's to_out / ff2 without):
+// x += ls * (A W^T + b)
+static inline GemmEpi epi_residual(float* resid, int D, const float* bias, const float* ls) {
+    GemmEpi e = rowsE(resid, OUT_F32, D, bias);
+    e.scale = ls; e.res1 = resid;
+    return e;
+}
+
+// FC1: GELU(A W^T + b)
+static inline GemmEpi epi_fc1(void* out, int out_type, int N, const float* bias) {
+    GemmEpi e = rowsE(out, out_type, N, bias);
+    e.act = ACT_GELU;
+    return e;
+}
+
+// ConvTranspose2d(k = s) of the reassemble stage as a linear: [B gh gw, C] x [s s C, C]^T, pixel-shuffled into [B, s gh, s gw, C]
+static inline GemmEpi epi_convT(void* out, int C, const float* bias, int gh, int gw, int ks) {
+    GemmEpi e = rowsE(out, OUT_T, C, bias);
+    e.map = MAP_SHUFFLE; e.gh = gh; e.gw = gw; e.ks = ks; e.cout = C;
+    return e;
+}
+
+// LayerNorm folded into the linear that consumes it (DESIGN.md §3.1 "LayerNorm fusion"): A = the RAW residual, W' = W diag(gamma),
+// v = rstd (acc - mean csum) before bias' = b + W beta; stats = the producer's partials, slots = the column blocks it reported
+static inline void epi_ln_consumer(GemmEpi& e, const float* stats, int slots, const float* csum, float eps, int dim) {
+    e.ln_stats = stats; e.ln_slots = slots; e.ln_csum = csum; e.ln_eps = eps; e.ln_dim = dim;
+}
+// ... and the residual update in front of it: the raw residual copy out2 (bf16; the unit format on bf16x3 engines; e4m3 of
+// v * out2_qscale on the e4m3 engines) and the (sum, sum of squares) partials of every row (stats null: the copy only)
+static inline void epi_ln_producer(GemmEpi& e, void* out2, float* stats, int* slots, bool bx3 = false, float out2_qscale = 0.f) {
+    e.out2 = out2; e.out2_bx3 = bx3 ? 1 : 0; e.stats_out = stats; e.stats_slots = slots; e.out2_qscale = out2_qscale;
+}
+// the reassemble projection with the final LayerNorm folded in, several frames: it runs over ALL token rows and the store mapping
+// drops the cls row of every frame -- token t of frame b lands on patch row b * P + t - 1 (gemm_epi.h epilogue4: row_off < 0)
+static inline void epi_drop_cls(GemmEpi& e, int ntok, int P) { e.rows_per_img = ntok; e.img_rows = P; e.row_off = -1; }
+// The rows of the folded reassemble projection (after epi_ln_consumer with the statistics of all token rows): one frame skips its cls
+// row by starting one row in -- A and the statistics (ln_M = ntok rows per slot); returns that A row offset, 1, and the launch has P
+// rows -- while several frames run over all B * ntok token rows and drop the cls rows on store (returns 0).  (0.13 % more rows.)
+static inline int epi_tap_fold_rows(GemmEpi& e, int B, int ntok, int P) {
+    if (B == 1) { e.ln_stats += 2; e.ln_M = ntok; return 1; }
+    epi_drop_cls(e, ntok, P);
+    return 0;
+}
+
+// ---- weights -------------------------------------------------------------------------------------------------------------
+// a logical [N][K] float matrix (given by accessor) -> host [Npad][Kpad] of the weight precision: bf16 (RNE), bf16x3 units, fp32
+template <typename F>
+static inline std::vector<uint8_t> pack_rows_host(int wprec, int N, int K, F at) {
+    const int Kp = gemm_kpad(K, wprec), Np = gemm_npad(N);
+    std::vector<uint8_t> buf((size_t)Np * Kp * elem_size(wprec), 0);
+    for (int n = 0; n < N; ++n)
+        for (int k = 0; k < K; ++k) {
+            float v = at(n, k);
+            if (wprec == D2S_PREC_BF16) ((bf16_t*)buf.data())[(size_t)n * Kp + k] = f2bf(v);
+            else if (wprec == D2S_PREC_BF16X3) bx3_pack_elem(buf.data() + (size_t)n * Kp * 4, k, v);      // [8 hi | 8 lo] units
+            else ((float*)buf.data())[(size_t)n * Kp + k] = v;
+        }
+    return buf;
+}
+
+// e4m3 weights: row n is divided by s_w[n] = max|row| / 448 (1 for a zero row) and rounded to e4m3 (RNE, saturating)
+static inline float fp8_row_scale(float amax) { return amax > 0.f ? amax / FP8_MAX : 1.f; }
+template <typename F>
+static inline std::vector<uint8_t> pack_rows_fp8_host(int N, int K, F at, std::vector<float>& sw) {
+    const int Kp = gemm_kpad(K, D2S_PREC_FP8_OPERANDS), Np = gemm_npad(N);
+    std::vector<uint8_t> buf((size_t)Np * Kp, 0);
+    sw.assign(N, 1.f);
+    for (int n = 0; n < N; ++n) {
+        float amax = 0.f;
+        for (int k = 0; k < K; ++k) amax = fmaxf(amax, fabsf(at(n, k)));
+        const float s = fp8_row_scale(amax);
+        sw[n] = s;
+        for (int k = 0; k < K; ++k) buf[(size_t)n * Kp + k] = f2e4m3(at(n, k) / s);
+    }
+    return buf;
+}
+
+// LN(x) W^T + b  =  rstd * (x W'^T - mean * colsum(W')) + (b + W beta),  W' = W diag(gamma).  One output row n of the fold: bias'
+// (accumulated in double) and the colsum over what the MFMAs sum -- bf16(W'), or its hi + lo halves on bf16x3 engines.  at(n, k): W.
+template <typename F>
+static inline void ln_fold_row(int wprec, int K, const float* g, const float* beta, F at, int n, double b, float& bias2, float& csum) {
+    double sb = b, sc = 0.0;
+    for (int k = 0; k < K; ++k) {
+        sb += (double)beta[k] * at(n, k);
+        const float v = g[k] * at(n, k);
+        const float hi = bf2f(f2bf(v));
+        sc += wprec == D2S_PREC_BF16X3 ? (double)hi + (double)bf2f(f2bf(v - hi)) : (double)hi;
+    }
+    bias2 = (float)sb; csum = (float)sc;
+}
+// the same on e4m3 weights: the colsum over the de-quantised W' (sw: the row scale of W'[n])
+template <typename F>
+static inline void ln_fold_row_fp8(int K, const float* g, const float* beta, F at, int n, double b, float sw, float& bias2, float& csum) {
+    double sb = b, sc = 0.0;
+    for (int k = 0; k < K; ++k) { sb += (double)beta[k] * at(n, k); sc += e4m32f(f2e4m3(g[k] * at(n, k) / sw)); }
+    bias2 = (float)sb; csum = (float)(sc * sw);
+}
+
+// ConvTranspose2d(k = s) weight [Ci, Co, s, s] as a linear's row n = (ky * s + kx) * Co + co, column k = ci
+static inline size_t convT_weight_index(int n, int k, int Co, int ks) { const int tap = n / Co, co = n % Co; return ((size_t)k * Co + co) * ks * ks + tap; }
+// GEGLU folded into ff1 (ACT_GEGLU): packed row n' = 8 g + w holds x row 4 g + w (w < 4) or gate row 4C + 4 g + (w - 4) of [8C, C]
+static inline int geglu_row(int n, int C) { const int g = n >> 3, w = n & 7; return w < 4 ? 4 * g + w : 4 * C + 4 * g + (w - 4); }
+
+}  // namespace d2s

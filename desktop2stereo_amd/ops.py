@@ -551,6 +551,103 @@ def conv3_probe(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     return out, p.kernel.decode()
 
 
+def linear_probe(site: str, precision: str, a: Optional[torch.Tensor], w: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+                 scale: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+                 res2: Optional[torch.Tensor] = None, ln: Optional[tuple] = None, producer: Optional[tuple] = None, fold: bool = False,
+                 ntok: int = 0, heads: int = 0, npad: int = 0, grid: Optional[tuple] = None, scales: tuple = (0.0, 0.0, 0.0, 0.0),
+                 ln_eps: float = 1e-6, tile: int = 0, splitk_elems: int = 0) -> dict:
+    """One linear of the engine (include/d2s.h d2s_linear_probe, sites D2S_LIN_*) through its own dispatcher, epilogue and packing (test
+    probe).  Float32 device operands: a [rows, K], w [N, K] (neck_resize: ConvTranspose2d [K, K, ks, ks]), bias, LayerScale scale,
+    x: the fp32 residual stream the site updates (cloned; the result comes back), res / res2 (patch: pos), grid = (gh, gw, ks);
+    fold: LayerNorm folding -- consumers take ln = (gamma, beta) and producer = (pa, pw, pbias, pscale), x = the residual before it;
+    scales = (s_act, s_out, s_res, s_pact) of the e4m3 engines.  precision: "fp32" | "bf16" | "bf16x3" | "fp8" | "fp8_mlp" (the engine's).
+    Returns a dict: out / vt / out2 as raw storage (bfloat16, float32, uint8 e4m3 bytes, int32 bf16x3 unit words), with one guard row
+    before and after out (out_guard: the whole buffer, filled with 0x7f bytes before the launch), x, stats [D / 16 + 1, M, 2], slots,
+    kernel, kernel2."""
+    _need_cuda(w, "w")
+    dev = w.device
+    prec = {"fp32": PREC_FP32, "bf16": PREC_BF16, "bf16x3": _lib.PREC_BF16X3, "fp8": _lib.PREC_FP8, "fp8_mlp": _lib.PREC_FP8_MLP}[precision]
+    sid = _lib.LINEAR_SITES[site]
+    N = w.shape[0] if site != "neck_resize" else w.shape[1] * w.shape[2] * w.shape[3]
+    K = w.shape[1] if site != "neck_resize" else w.shape[0]
+    consumer = fold and site in ("qkv", "fc1", "neck_proj", "tm_kvq", "tm_ff1")
+    M = producer[0].shape[0] if consumer else (x.shape[0] if site in ("proj", "fc2", "tm_proj_in", "tm_to_out", "tm_ff2") else a.shape[0])
+    if site == "neck_proj":
+        M = (producer[0].shape[0] if consumer else a.shape[0] // (ntok - 1) * ntok)
+    x3, f8, f8a = precision == "bf16x3", precision in ("fp8", "fp8_mlp"), precision == "fp8"
+    e8 = f8 and (site in ("fc1", "fc2") or (f8a and site in ("qkv", "proj")))
+    act16 = precision in ("bf16", "fp8", "fp8_mlp")
+    t_out = torch.bfloat16 if act16 else torch.float32        # OUT_T
+
+    def alloc(rows, cols, dtype):
+        buf = torch.empty((rows + 2, cols), dtype=dtype, device=dev)
+        buf.view(torch.uint8).fill_(0x7f)
+        return buf
+    keep = []
+
+    def fp(t):
+        if t is None:
+            return None
+        keep.append(t.float().contiguous())
+        return _ptr(keep[-1])
+    p = _lib.LinearProbeParams()
+    p.struct_size = C.sizeof(_lib.LinearProbeParams)
+    p.site, p.precision, p.ln_fold, p.M, p.N, p.K = sid, prec, int(bool(fold)), M, N, K
+    p.ntok, p.heads, p.npad = int(ntok), int(heads), int(npad)
+    if grid is not None:
+        p.gh, p.gw, p.ks = grid
+    p.ln_eps, p.tile, p.splitk_elems = float(ln_eps), int(tile), int(splitk_elems)
+    p.s_act, p.s_out, p.s_res, p.s_pact = (float(v) for v in scales)
+    p.a, p.w, p.bias, p.scale, p.res, p.res2 = fp(a), fp(w), fp(bias), fp(scale), fp(res), fp(res2)
+    if ln is not None:
+        p.ln_g, p.ln_b = fp(ln[0]), fp(ln[1])
+    if producer is not None:
+        p.pK = producer[0].shape[1]
+        p.pa, p.pw, p.pbias, p.pscale = fp(producer[0]), fp(producer[1]), fp(producer[2]), fp(producer[3])
+    r = {"out": None, "out_guard": None, "vt": None, "out2": None, "x": None, "stats": None}
+    if x is not None:
+        r["x"] = x.float().clone().contiguous()
+        p.x = _ptr(r["x"])
+    # the output in the site's type (linear_site.h qkv_out_type / fc1_out_type, OUT_T)
+    if site == "qkv":
+        odt = torch.bfloat16 if f8 else (torch.int32 if x3 else t_out)
+        rows, cols = M, N
+    elif site == "fc1":
+        odt = torch.int32 if x3 else (torch.uint8 if e8 else t_out)
+        rows, cols = M, N
+    elif site == "neck_proj":
+        odt, rows, cols = t_out, M // ntok * (ntok - 1), N
+    elif site == "neck_resize":
+        odt, rows, cols = t_out, M * grid[2] * grid[2], K
+    elif site == "tm_ff1":
+        odt, rows, cols = t_out, M, N // 2 if fold else N
+    elif site in ("tm_kvq", "tm_proj_out"):
+        odt, rows, cols = t_out, M, N
+    else:
+        odt = None
+    if odt is not None:
+        g = alloc(rows, cols, odt)
+        r["out_guard"], r["out"] = g, g[1:rows + 1]
+        p.out = _ptr(r["out"])
+    if site == "qkv":
+        B = M // ntok
+        r["vt"] = torch.empty((B, heads, 64, npad), dtype=odt, device=dev)
+        r["vt"].view(torch.uint8).fill_(0x7f)
+        p.vt = _ptr(r["vt"])
+    if fold:
+        D = K if consumer else N
+        r["out2"] = torch.empty((M, D), dtype=torch.int32 if x3 else (torch.uint8 if (e8 if consumer else f8) else torch.bfloat16), device=dev)
+        r["out2"].view(torch.uint8).fill_(0x7f)
+        p.out2 = _ptr(r["out2"])
+        if site != "tm_ff2":
+            r["stats"] = torch.full((D // 16 + 1, M, 2), float("nan"), dtype=torch.float32, device=dev)
+            p.stats = _ptr(r["stats"])
+    with _on(dev) as st:
+        check(_lib.load().d2s_linear_probe(C.byref(p), st), "d2s_linear_probe")
+    r["slots"], r["kernel"], r["kernel2"] = p.stats_slots, p.kernel.decode(), p.kernel2.decode()
+    return r
+
+
 def attention_probe(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str = "bf16", iters: int = 1):
     """softmax(q k^T / 8) v for float32 [B, heads, N, 64] device tensors through the engine's attention kernel
     (test / micro-benchmark).  Returns (out [B, N, heads * 64] float32, ms per launch or 0)."""

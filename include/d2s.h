@@ -385,6 +385,67 @@ typedef struct d2s_conv3_probe_params {
 } d2s_conv3_probe_params;
 int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream);
 
+/* Stand-alone linear probe (tests): one linear of the encoder, the DPT neck or a temporal module through the engine's own dispatcher
+ * (launch_gemm), its epilogue built by the engine's per-site helpers and its operands cast and packed as the engine casts and packs
+ * them (bf16 / bf16x3 units / e4m3 with s_w[n] = max|row n| / 448; LayerNorm folding W' = W diag(gamma), bias' = b + W beta,
+ * csum[n] = sum_k of the rounded W'[n, k]).  A LayerNorm-folded consumer takes its statistics from a real producer launch, run first
+ * as the engine chains them.  Reports the kernel(s) it ran.  Matrices are row-major float32 device tensors unless noted. */
+enum {
+    D2S_LIN_PATCH = 0,         /* patch embedding: a [M = B*P, K] patch rows -> x [B*ntok, N] rows 1..P of every frame (+ res = pos [ntok, N]) */
+    D2S_LIN_QKV = 1,           /* a [M, K = D] -> out q | k [M, 3D] (columns < 2D), vt [B, heads, 64, npad] (M = B*ntok) */
+    D2S_LIN_PROJ = 2,          /* x [M, N] += scale * (a W^T + bias)            (in place; ln_fold: the producer -> out2, stats) */
+    D2S_LIN_FC1 = 3,           /* out [M, N] = GELU(a W^T + bias) */
+    D2S_LIN_FC2 = 4,           /* as D2S_LIN_PROJ */
+    D2S_LIN_NECK_PROJ = 5,     /* out [B*P, N] = a W^T + bias, a [B*P, K] (M = B*ntok); ln_fold: the final LayerNorm folded in (bf16) */
+    D2S_LIN_NECK_RESIZE = 6,   /* ConvTranspose2d(k = s = ks): a [M = B*gh*gw, K] -> out [B, ks*gh, ks*gw, K]; w [K, K, ks, ks], bias [K],
+                                  N = ks*ks*K */
+    D2S_LIN_TM_PROJ_IN = 7,    /* x [M, N] = a W^T + bias (ln_fold: the producer) */
+    D2S_LIN_TM_KVQ = 8,        /* out [M, N] = a W^T (+ bias) */
+    D2S_LIN_TM_FF1 = 9,        /* out [M, N] = a W^T + bias; ln_fold: GEGLU in the epilogue, out [M, N/2] = x * gelu(gate) (w rows: x | gate) */
+    D2S_LIN_TM_TO_OUT = 10,    /* x [M, N] += a W^T + bias (ln_fold: the producer) */
+    D2S_LIN_TM_FF2 = 11,       /* as D2S_LIN_TM_TO_OUT; ln_fold: out2 only, no statistics */
+    D2S_LIN_TM_PROJ_OUT = 12   /* out [M, N] = a W^T + bias + res [M, N] + res2 [M, N] */
+};
+typedef struct d2s_linear_probe_params {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_linear_probe_params) = 488 */
+    int32_t site;              /* D2S_LIN_* */
+    int32_t precision;         /* the ENGINE's: D2S_PREC_FP32 / BF16 / BF16X3 / FP8 (e4m3 on all four encoder linears) / FP8_MLP */
+    int32_t ln_fold;           /* consumers (QKV, FC1, NECK_PROJ, TM_KVQ, TM_FF1): LayerNorm (ln_g, ln_b, ln_eps) folded in, statistics
+                                  from a producer launch x += pscale * (pa pW^T + pbias) run first; producers (PROJ, FC2, TM_PROJ_IN,
+                                  TM_TO_OUT, TM_FF2): write out2 and stats */
+    int32_t M, N, K;           /* rows (see the sites), weight rows (packed order), reduction length */
+    int32_t ntok, heads, npad; /* tokens per frame (PATCH, QKV, NECK_PROJ); QKV: heads (64 channels each), V^T row length */
+    int32_t gh, gw, ks;        /* NECK_RESIZE: patch grid and ConvTranspose kernel = stride */
+    int32_t pK;                /* ln_fold consumers: K of the producer (pa [M, pK], pw [K, pK], pbias / pscale [K]) */
+    float   ln_eps;
+    float   s_act, s_out, s_res, s_pact;   /* e4m3 scales: this linear's A, an e4m3 output (FC1), the raw residual copy out2, the producer's A */
+    int32_t tile;              /* 0: what the engine passes (automatic); else a tile code */
+    int64_t splitk_elems;      /* > 0: a split-K workspace of this many fp32 partials, as the engine's (row-mapped launches, bf16 / fp32 /
+                                  bf16x3 operands: what the engine's gemm() hands over) */
+    const float* a;            /* [M, K] (ln_fold consumers: unused -- A is the producer's out2) */
+    const float* w;            /* [N, K] PyTorch layout (NECK_RESIZE: ConvTranspose2d [K, K, ks, ks]) */
+    const float* bias;         /* [N] or null (NECK_RESIZE: [K]) */
+    const float* scale;        /* [N] LayerScale or null (PROJ, FC2) */
+    const float* res;          /* PATCH: pos [ntok, N]; TM_PROJ_OUT: [M, N] */
+    const float* res2;         /* TM_PROJ_OUT: [M, N] or null */
+    const float* ln_g;         /* [K] (ln_fold consumers) */
+    const float* ln_b;         /* [K] */
+    const float* pa;           /* [M, pK] */
+    const float* pw;           /* [K, pK] */
+    const float* pbias;        /* [K] or null */
+    const float* pscale;       /* [K] or null */
+    float* x;                  /* the fp32 residual stream [M, N] (PATCH: [B*ntok, N]; ln_fold consumers: [M, K], the producer's), in / out */
+    void* out;                 /* the output in the engine's type for the site (bf16, fp32, bf16x3 units, e4m3) */
+    void* out2;                /* ln_fold: the raw residual copy [M, D] (D = K for consumers, N for producers): bf16 / units / e4m3 */
+    void* vt;                  /* QKV: [B, heads, 64, npad] of the output type */
+    float* stats;              /* ln_fold (not TM_FF2): [D / 16 + 1][M][2] (sum, sum of squares) partials */
+    int32_t stats_slots;       /* out: the column blocks the producer reported */
+    int32_t reserved;          /* 0 */
+    char kernel[128];          /* out: the kernel this linear ran, e.g. "gemm_pp_kernel<bf16,PP_K_F32_LN> ks=3 tail=row-split" */
+    char kernel2[128];         /* out: the producer's (ln_fold consumers), else "" */
+} d2s_linear_probe_params;
+int d2s_linear_probe(d2s_linear_probe_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

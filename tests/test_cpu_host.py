@@ -42,6 +42,11 @@ def test_struct_layout_matches_header():
     P = _lib.Conv3ProbeParams                                                                # d2s_conv3_probe_params
     assert (C.sizeof(P) == 256 and P.precision.offset == 4 and P.map_head.offset == 56 and P.b3.offset == 60 and P.max_depth.offset == 64
             and P.splitk_elems.offset == 72 and P.x.offset == 80 and P.out.offset == 120 and P.kernel.offset == 128)
+    L = _lib.LinearProbeParams                                                               # d2s_linear_probe_params
+    assert (C.sizeof(L) == 488 and L.precision.offset == 8 and L.ln_fold.offset == 12 and L.M.offset == 16 and L.ntok.offset == 28
+            and L.gh.offset == 40 and L.pK.offset == 52 and L.ln_eps.offset == 56 and L.s_act.offset == 60 and L.s_pact.offset == 72
+            and L.tile.offset == 76 and L.splitk_elems.offset == 80 and L.a.offset == 88 and L.pscale.offset == 176 and L.x.offset == 184
+            and L.stats.offset == 216 and L.stats_slots.offset == 224 and L.kernel.offset == 232 and L.kernel2.offset == 360)
 
 
 def test_sbs_shape_matches_reference_padding(lib):

@@ -21,6 +21,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from f64_ref import bf16q, pow2, rne_bf16
+
 GPU = pytest.mark.gpu
 
 
@@ -60,21 +62,6 @@ def ups_operand_f32(x: torch.Tensor, Hi: int, Wi: int) -> torch.Tensor:
 def ups_operand(x: torch.Tensor, Hi: int, Wi: int) -> torch.Tensor:
     """The operand a folded up-sample feeds the MFMAs: bf16 (round to nearest even) of ups_operand_f32, as float32."""
     return ups_operand_f32(x, Hi, Wi).to(torch.bfloat16).float()
-
-
-def pow2(k: torch.Tensor) -> torch.Tensor:
-    """2^k as float64, exactly (built from the exponent bits; torch.ldexp goes through a float32 pow on the device)."""
-    return ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
-
-
-def rne_bf16(r: torch.Tensor) -> torch.Tensor:
-    """float64 -> the float64 value of its bf16 rounding to nearest even (8 significant bits), in one rounding."""
-    m, e = torch.frexp(r)
-    return torch.round(m * 256.0) * pow2(e - 8)
-
-
-def bf16q(t: torch.Tensor) -> torch.Tensor:
-    return t.to(torch.bfloat16).float()
 
 
 def test_ups_operand_matches_interpolate():
