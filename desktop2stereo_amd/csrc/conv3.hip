@@ -1327,9 +1327,40 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
 // ring is two K tiles deep at most beside two halo buffers, i.e. ~1 000 cycles of cover for an LDS-DMA that needs ~2 000 under
 // load; two independent blocks per CU hide that better than one deeper-pipelined one.  Removed.)
 
+// The conv3_halo2_kernel instantiations (CPP, PST, BN, WM, WN, NS[, HG]); the other kernels of this file take one each
+#define C3_HALO2(X)                                                                                                              \
+    X(C3_H2_MID, 16,17,64,4,2,10,6)      /* mid-size maps, one block per CU (plan_conv3_halo2) */                                \
+    X(C3_H2_C128_N128, 16,17,128,2,4,2)  /* (row pitch 17 chunks: 2 blocks / CU; 18 would be conflict-free) */                   \
+    X(C3_H2_C128_N64, 16,17,64,4,2,3)                                                                                            \
+    X(C3_H2_C128_N32, 16,17,32,4,1,3)                                                                                            \
+    X(C3_H2_C64_N128, 8,10,128,2,4,3)                                                                                            \
+    X(C3_H2_C64_N64, 8,10,64,4,2,3)                                                                                              \
+    X(C3_H2_C64_N32, 8,10,32,4,1,3)
+enum { C3_HEAD_UPS, C3_HEAD_1, C3_HEAD_0, C3_C128_UPS, C3_WIDE_8_32, C3_WIDE_16_16,
+#define X(ID, ...) ID,
+       C3_HALO2(X)
+#undef X
+};
+static const char* const c3_names[] = {"conv3_head_ups_kernel", "conv3_head_kernel<1>", "conv3_head_kernel<0>", "conv3_c128_ups_kernel",
+                                       "conv3_wide_kernel<8,32>", "conv3_wide_kernel<16,16>",
+#define X(ID, ...) "conv3_halo2_kernel<" #__VA_ARGS__ ">",
+                                       C3_HALO2(X)
+#undef X
+};
+#define C3_BLOCK(CPP, PST, BN, WM, WN, ...) 64 * WM * WN
+static constexpr int c3_block[] = {512, 512, 512, 512, 512, 512,
+#define X(ID, ...) C3_BLOCK(__VA_ARGS__),
+                                   C3_HALO2(X)
+#undef X
+};
+#undef C3_BLOCK
+static void c3_plan(GemmPlan& p, int inst, unsigned grid, int xn, const GemmA& a) {
+    p.family = GEMM_CONV3; p.inst = inst; p.name = c3_names[inst]; p.grid = grid; p.block = c3_block[inst]; p.xn = xn; p.ups = a.ups;
+}
+
 // Eligible: bf16, stride 1, same-size output, C = 64 | 128, K = 9 C, plain row mapping or the fused head, enough tiles to fill the
 // chip.  D2S_NO_HALO2=1 keeps the first-generation kernels (the parity tests run both).
-bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st, bool dry) {
+bool plan_conv3_halo2(const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p) {
     static EnvInt off{"D2S_NO_HALO2", 0};
     if (off.get()) return false;
     if (a.mode != A_CONV3 || a.stride != 1 || a.Hi != a.Ho || a.Wi != a.Wo || (a.C != 64 && a.C != 128) || K != 9 * a.C) return false;
@@ -1347,21 +1378,11 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         static EnvInt no_headups{"D2S_NO_HEADUPS", 0};
         // (the staged 13 x 13 source window holds scales <= 0.6; ReLU-on-load is not part of the interpolating loader)
         if (a.ups && (no_headups.get() || a.usy > 0.6f || a.usx > 0.6f || a.relu)) return false;
-        if (dry) return true;
         static EnvInt ups_v1{"D2S_HEADUPS_V1", 0};             // A/B aid: the lock-step kernel of round 3
         // (the source map is read through one buffer descriptor; a tap's source-column byte offset travels in the low 16 bits of the
         //  bpermute word of h_request: a source row must stay within 64 KiB, i.e. Ws <= 512 at C = 64 -- wider maps take <1>)
         const bool ups_fits = (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31) && (long)a.Ws * a.C * 2 <= 65536;
-        if (a.ups && !ups_v1.get() && ups_fits) {
-            note_kernel("conv3_head_ups_kernel");
-            hipLaunchKernelGGL(conv3_head_ups_kernel, dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
-        } else if (a.ups) {
-            note_kernel("conv3_head_kernel<1>");
-            hipLaunchKernelGGL((conv3_head_kernel<1>), dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
-        } else {
-            note_kernel("conv3_head_kernel<0>");
-            hipLaunchKernelGGL((conv3_head_kernel<0>), dim3(std::min(ncu, ntiles)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e, ntiles);
-        }
+        c3_plan(p, a.ups ? (!ups_v1.get() && ups_fits ? C3_HEAD_UPS : C3_HEAD_1) : C3_HEAD_0, std::min(ncu, ntiles), ntiles, a);
         return true;
     }
     // the head's conv1 at batch: persistent blocks with W in registers and the up-sample in the loader (conv3_c128_ups_kernel)
@@ -1370,12 +1391,9 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         (e.out_type == OUT_T || e.out_type == OUT_BF16) && !e.scale && !e.res1 && !e.res2 && e.act == ACT_NONE && !e.deq && !e.out2 && !(e.ldc & 7) &&
         c128_min.get() > 0 && (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) >= c128_min.get() &&
         (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) < (1L << 30) && (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31)) {
-        if (dry) return true;
         const int ncu = device_cu_count();
         const int ntl = (int)((long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16));
-        GemmEpi e1 = e; e1.ksplit = 1;
-        note_kernel("conv3_c128_ups_kernel");
-        hipLaunchKernelGGL(conv3_c128_ups_kernel, dim3(std::min(ncu & ~7, ntl)), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, ntl);
+        c3_plan(p, C3_C128_UPS, std::min(ncu & ~7, ntl), ntl, a);
         return true;
     }
     static EnvInt no_wide{"D2S_NO_WIDE", 0};
@@ -1386,11 +1404,7 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
         const long ntl = nimg * std::min(pad_a, pad_b);
         const int grid_w = ncu & ~7;
         if (ntl >= 384 && ntl < (1L << 30) && grid_w >= 8) {          // 384 tiles: 1.5 rounds of the CUs
-            if (dry) return true;
-            GemmEpi e1 = e; e1.ksplit = 1;
-            note_kernel(pad_a <= pad_b ? "conv3_wide_kernel<8,32>" : "conv3_wide_kernel<16,16>");
-            if (pad_a <= pad_b) hipLaunchKernelGGL((conv3_wide_kernel<8, 32>), dim3(grid_w), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, (int)ntl);
-            else hipLaunchKernelGGL((conv3_wide_kernel<16, 16>), dim3(grid_w), dim3(512), 0, st, a, (const bf16_t*)W, N, Kpad, e1, (int)ntl);
+            c3_plan(p, pad_a <= pad_b ? C3_WIDE_8_32 : C3_WIDE_16_16, grid_w, (int)ntl, a);
             return true;
         }
     }
@@ -1403,38 +1417,37 @@ bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int 
     // way with all 72 KB of a 32-channel block's weights up front (NS = 19, HG = 12): 11.6-12.7 us before, 11.4-14.9 after -- those
     // launches are not paced by the K loop's round trips (boundary, cold code and the epilogue are what is left); not kept.
     const int ncu = device_cu_count();
+    unsigned grid = 0;
     if (a.C == 128 && e.map == MAP_ROWS && N % 64 == 0 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
         tiles_m * (N / 64) <= ncu && tiles_m * (N / 64) * 2 > ncu) {
-        if (dry) return true;
-        GemmEpi e1 = e; e1.ksplit = 1;
-        unsigned grid = 0;
         const int xn = pick_xn((int)tiles_m, N / 64, 64, Kpad, 2, grid);
-        note_kernel("conv3_halo2_kernel<16,17,64,4,2,10,6>");
-        hipLaunchKernelGGL((conv3_halo2_kernel<16, 17, 64, 4, 2, 10, 6>), dim3(grid), dim3(512), 0, st, a, (const bf16_t*)W, M, N, Kpad, e1, xn);
+        c3_plan(p, C3_H2_MID, grid, xn, a);
         return true;
     }
     const int bn = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
     // small maps: latency-bound, the small-tile kernels do better (head conv1 at batch 1: 399 tiles, 26.5 -> 21.8 us here; 110-tile maps lose)
     if (tiles_m * cdiv(N, bn) < 384) return false;
     if ((long)gemm_npad(N) * Kpad * 2 >= (1L << 31)) return false;
-    if (dry) return true;
-    GemmEpi e1 = e; e1.ksplit = 1;
-    unsigned grid = 0;
     const int xn = pick_xn((int)tiles_m, cdiv(N, bn), bn, Kpad, 2, grid);
-#define C3_LAUNCH(CPP_, PST_, BN_, WM_, WN_, NS_)                                                                                      \
-    do { note_kernel("conv3_halo2_kernel<" #CPP_ "," #PST_ "," #BN_ "," #WM_ "," #WN_ "," #NS_ ">");                                         \
-         hipLaunchKernelGGL((conv3_halo2_kernel<CPP_, PST_, BN_, WM_, WN_, NS_>), dim3(grid), dim3(64 * WM_ * WN_), 0, st, a, (const bf16_t*)W, M, N, Kpad, e1, xn); } while (0)
-    if (a.C == 128) {
-        if (bn == 128) C3_LAUNCH(16, 17, 128, 2, 4, 2);          // (row pitch 17 chunks: 2 blocks / CU; 18 would be conflict-free)
-        else if (bn == 64) C3_LAUNCH(16, 17, 64, 4, 2, 3);
-        else C3_LAUNCH(16, 17, 32, 4, 1, 3);
-    } else {
-        if (bn == 128) C3_LAUNCH(8, 10, 128, 2, 4, 3);
-        else if (bn == 64) C3_LAUNCH(8, 10, 64, 4, 2, 3);
-        else C3_LAUNCH(8, 10, 32, 4, 1, 3);
-    }
-#undef C3_LAUNCH
+    if (a.C == 128) c3_plan(p, bn == 128 ? C3_H2_C128_N128 : (bn == 64 ? C3_H2_C128_N64 : C3_H2_C128_N32), grid, xn, a);
+    else c3_plan(p, bn == 128 ? C3_H2_C64_N128 : (bn == 64 ? C3_H2_C64_N64 : C3_H2_C64_N32), grid, xn, a);
     return true;
+}
+
+void launch_conv3_halo2(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int Kpad, const GemmEpi& e, hipStream_t st) {
+    const bf16_t* w = (const bf16_t*)W;
+    const dim3 grid(p.grid), block(p.block);
+    switch (p.inst) {
+        case C3_HEAD_UPS: hipLaunchKernelGGL(conv3_head_ups_kernel, grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+        case C3_HEAD_1: hipLaunchKernelGGL((conv3_head_kernel<1>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+        case C3_HEAD_0: hipLaunchKernelGGL((conv3_head_kernel<0>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+        case C3_C128_UPS: hipLaunchKernelGGL(conv3_c128_ups_kernel, grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+        case C3_WIDE_8_32: hipLaunchKernelGGL((conv3_wide_kernel<8, 32>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+        case C3_WIDE_16_16: hipLaunchKernelGGL((conv3_wide_kernel<16, 16>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+#define X(ID, ...) case ID: hipLaunchKernelGGL((conv3_halo2_kernel<__VA_ARGS__>), grid, block, 0, st, a, w, M, N, Kpad, e, p.xn); break;
+        C3_HALO2(X)
+#undef X
+    }
 }
 
 }  // namespace d2s

@@ -78,33 +78,51 @@ struct GemmEpi {
 int launch_gemm(int precision, int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad,
                 const GemmEpi& e, hipStream_t st);
 
-// stride-1 3x3 convolutions with the input tile resident in LDS, second generation (conv3.hip): false = not eligible, nothing launched
-bool launch_conv3_halo2(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st, bool dry = false);   // dry: eligibility only
-
 // would launch_gemm fold the up-sample a.ups describes into this convolution's halo loader? (engine: skip the bilinear launch)
 bool conv3_upsample_ok(int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
-
-// 256 x 256 ping-pong kernel (gemm_pp.hip): batched plain linears
-bool pp_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
-int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st);
-
-// streaming kernel for the thin linears of the DPT neck (gemm_sk.hip: K <= 256, W tile resident in LDS, A streamed)
-bool sk_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
-int launch_gemm_sk(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st);
 
 // smallest number of 256 x 256 tiles from which plain linears go to the ping-pong kernel (D2S_GEMM_PP; 0 = never)
 int gemm_pp_min_tiles();
 
-// Which kernel the last launch_gemm of this host thread ran: the launch sites record it (host side only, a few stores), and only
-// the probes (d2s_conv3_probe, d2s_linear_probe) read it -- the tests pin the dispatch with it.  tile: the implicit-GEMM tile code
-// the launcher settled on (0 for the other kernels); ksplit > 1: split-K partials + splitk_reduce_kernel (gemm_glds_kernel), or the
-// ping-pong kernel's tail tiles cut into ksplit units, tail = how they are finished.
+// What launch_gemm runs, decided on the host before anything is launched (plan_gemm, gemm.hip): the kernel family and the entry of
+// that family's instantiation table, its grid, and everything the launch sets up around it.  The family launchers start a plan as is.
+enum { GEMM_GLDS = 0, GEMM_HALO = 1, GEMM_CONV3 = 2, GEMM_PP = 3, GEMM_SK = 4 };   // gemm_glds_kernel, conv3_halo_kernel, conv3.hip, gemm_pp, gemm_sk
 enum { NOTE_TAIL_NONE = 0, NOTE_TAIL_INKERNEL = 1, NOTE_TAIL_TWO_LAUNCH = 2, NOTE_TAIL_ROWSPLIT = 3 };
+struct GemmPlan {
+    int family, inst;            // GEMM_*, entry of the family's table
+    const char* name;            // the instantiation, as the probes report it
+    int tile;                    // gemm_glds_kernel: the tile code the dispatch settled on; ping-pong kernel: 256256; 0 otherwise
+    unsigned grid, gridy;        // blocks (gridy: split-K ranges of gemm_glds_kernel, column groups of gemm_sk_kernel)
+    int block;                   // threads per block
+    unsigned grid2;              // blocks of the second launch (splitk_reduce_kernel, pp_tail_reduce_kernel); 0: none
+    int xn;                      // the tile map's XCD grid (pick_xn); the persistent conv3.hip kernels: their tile count
+    int buf;                     // GemmA::buf of the launch (descriptor-addressed operands)
+    int ksplit, tail;            // split-K ranges (gemm_glds_kernel) or units per tail tile (ping-pong kernel); NOTE_TAIL_*
+    int stats_slots;             // what *e.stats_slots receives (LayerNorm statistics partials per row); -1: left unwritten
+    int ups;                     // the up-sample a.ups describes is folded into the loader
+    int kps, tw, ink, lxn, skew_us;   // ping-pong kernel: K tiles per unit, whole-tile units, tail mode, log2(xn), start skew
+    const char* error;           // plan_gemm failed: the message launch_gemm reports
+};
+int plan_gemm(int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);
+
+// the families outside gemm.hip: eligibility / plan (host only) and the launcher of a plan
+bool plan_conv3_halo2(const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);   // stride-1 3x3 convs, input in LDS
+void launch_conv3_halo2(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int Kpad, const GemmEpi& e, hipStream_t st);
+// 256 x 256 ping-pong kernel (gemm_pp.hip): batched plain linears
+bool pp_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
+int plan_gemm_pp(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);
+int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st);
+// streaming kernel for the thin linears of the DPT neck (gemm_sk.hip: K <= 256, W tile resident in LDS, A streamed)
+bool sk_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
+void plan_gemm_sk(const GemmA& a, int M, int N, int K, GemmPlan& p);
+void launch_gemm_sk(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int Kpad, const GemmEpi& e, hipStream_t st);
+
+// Which kernel the last launch_gemm of this host thread ran: launch_gemm records its plan (host side only, a few stores), and only
+// the probes (d2s_conv3_probe, d2s_linear_probe) read it -- the tests pin the dispatch with it.  tile: the implicit-GEMM tile code
+// the plan settled on (0 for the other kernels); ksplit > 1: split-K partials + splitk_reduce_kernel (gemm_glds_kernel), or the
+// ping-pong kernel's tail tiles cut into ksplit units, tail = how they are finished.
 struct KernelNote { const char* name; int tile; int ksplit; int tail; };
 KernelNote& kernel_note();
-static inline void note_kernel(const char* name, int ksplit = 1, int tail = NOTE_TAIL_NONE) {
-    KernelNote& n = kernel_note(); n.name = name; n.ksplit = ksplit; n.tail = tail;
-}
 
 // tile of the fused head launch: MAP_HEAD needs a tile whose waves own all N columns of their rows (WN == 1)
 static inline int head_tile(int bn) { return bn == 32 ? 912832 : 9256648; }

@@ -3,7 +3,7 @@
 //  * operands bf16 (v_mfma_f32_16x16x32_bf16), e4m3 (v_mfma_f32_16x16x32_fp8_fp8) or f32 (v_mfma_f32_16x16x4_f32,
 //    exact fp32), fp32 accumulate;
 //  * tile BM x BN x 128 bytes of K, WM x WN waves; two data paths for the K tiles (gemm_glds_kernel): LDS-DMA into an
-//    NS-stage ring, or register staging into two LDS stages (STG) -- the tile rule in launch_t picks per launch;
+//    NS-stage ring, or register staging into two LDS stages (STG) -- the tile rule in plan_gemm picks per launch;
 //  * both operands are K-contiguous; a 16-byte chunk per lane is the unit everywhere:
 //      global -> LDS (16 B/lane, 8 lanes cover one 128-B row = full cache lines), chunk XOR-swizzle
 //      phys = chunk ^ ((row >> 1) & 7), applied on the source address for LDS-DMA
@@ -642,147 +642,194 @@ static inline bool buf_eligible(const GemmA& a, int M, int N, int K, int Kpad, i
     return a.mode == A_PLAIN && !a.relu && K % bk == 0 && (long)M * a.lda * (long)es < (1L << 31) && (long)gemm_npad(N) * Kpad * (long)es < (1L << 31);
 }
 
-// split K below this many blocks (launch_glds)
+// split K below this many blocks (plan_glds)
 constexpr int SPLITK_GRID = 128;
 
-// would launch_glds split K for this launch (tiny grid, long K loop, caller-provided workspace)?  The lean instantiations take one K
-// range per block (their ring is primed from preloaded arguments before e.ksplit could be read): the dispatchers send such
-// launches to the general instantiations.
+// would plan_glds split K for this launch (tiny grid, long K loop, caller-provided workspace)?  The lean instantiations take one K
+// range per block (their ring is primed from preloaded arguments before e.ksplit could be read): lean_of sends such launches to the
+// general instantiations.
 static inline bool splitk_wanted(const GemmEpi& e, long tiles, int K, int bk) {
     return e.part && e.part_elems > 0 && !e.stats_out && tiles < SPLITK_GRID && cdiv(K, bk) >= 24;     // (splitk_reduce_kernel writes no LN statistics)
 }
 
-// deep-ring lean instantiations in the latency regime (launch_t, launch_bx3); D2S_GEMM_DEEP=0: off
+// deep-ring lean instantiations in the latency regime (lean_of); D2S_GEMM_DEEP=0: off
 static bool gemm_deep() {
     static EnvInt deep{"D2S_GEMM_DEEP", 1};
     return deep.get() != 0;
 }
 
-// tile codes: 64 (64x64), 128 (128x128), 256128 / 256256 (8 waves), 25664 / 25632 (256 x 64|32, 4 waves); 0 = auto
-template <typename T> static const char* type_tag() {
-    if constexpr (std::is_same<T, bf16_t>::value) return "bf16";
-    else if constexpr (std::is_same<T, fp8_t>::value) return "e4m3";
-    else if constexpr (std::is_same<T, bx3_t>::value) return "bx3";
-    else return "f32";
+// ---- the gemm_glds_kernel instantiations, one line each: X(id, operand types, BM,BN,WM,WN,NS,CPR,STG).  The kernel name, the
+// geometry the planner reads and the launch all come from this list; an instantiation exists for the types its line names.
+enum { TY_BF16 = 1, TY_E4M3 = 2, TY_F32 = 4, TY_BX3 = 8, TY_BEF = TY_BF16 | TY_E4M3 | TY_F32, TY_ALL = TY_BEF | TY_BX3 };
+#define GLDS_INSTANCES(X)                                                                                                        \
+    /* LDS-DMA ring (NS stages) */                                                                                               \
+    X(G_256128, TY_BEF, 256,128,4,2,3,8,0)                                                                                       \
+    X(G_128, TY_BEF, 128,128,2,2,4,8,0)                                                                                          \
+    X(G_64, TY_BEF, 64,64,2,2,4,8,0)                                                                                             \
+    /* (256-byte K tiles for this tile -- half the barrier-paced iterations -- measured at batch 1: 768 vs 766 frames/s with    \
+        three ring stages, 726 with two: the batch-1 launches are not paced by their K-loop iteration count) */                  \
+    X(G_3264, TY_ALL, 32,64,2,2,4,8,0)                                                                                           \
+    /* (One-round shapes for M = 778 -- 48 x 64, 96 x 64, 48 / 96 / 80 / 112 x 128, 112 x 96: 108-240 blocks of 2-4 waves,     \
+        fewer fill bytes per CU than two rounds of a small tile -- were instantiated and swept at batch 1: 1.2-4 x SLOWER than  \
+        the 32 x 64 / 64 x 64 / 64 x 128 tiles on every encoder linear.  Resident waves per CU decide the fill rate a CU reaches.) \
+       LDS-DMA, 8 waves, two stages: the winners of the second sweep (profiles/r1_05), code <BM><BN>8 */                         \
+    X(G_1281288, TY_ALL, 128,128,2,4,2,8,0)    /* wave tile 64 x 32, 2 blocks / CU */                                            \
+    X(G_641288, TY_ALL, 64,128,2,4,2,8,0)      /* 3 blocks / CU */                                                               \
+    X(G_64648, TY_ALL, 64,64,4,2,2,8,0)        /* 5 blocks / CU */                                                               \
+    X(G_256648, TY_BEF, 256,64,8,1,2,8,0)      /* WN == 1: MAP_HEAD capable */                                                   \
+    X(G_128324, TY_BEF, 128,32,4,1,2,8,0)      /* WN == 1, 4 waves */                                                            \
+    /* register-staged variants (STG), code = 9 <BM> <BN> [waves].  Removed after losing the sweeps: 256 x 128 / 256 x 256 with \
+       8 waves (1 block / CU, lock-step), 128 x 128 with 4 or 16 waves, deeper rings, 64- and 256-byte K tiles, two register     \
+       sets, intra-block split-K.  bf16x3 launches with an fp32 A run these only (the split happens on the way into LDS). */      \
+    X(G_964, TY_ALL, 64,64,2,2,2,8,1)                                                                                            \
+    X(G_91288, TY_ALL, 128,128,4,2,2,8,1)      /* 8 waves, 2 blocks / CU */                                                      \
+    X(G_912832, TY_ALL, 128,32,4,1,2,8,1)      /* WN == 1: MAP_HEAD capable */                                                   \
+    X(G_9256648, TY_ALL, 256,64,8,1,2,8,1)     /* WN == 1, 8 waves */                                                            \
+    X(G_93264, TY_BX3, 32,64,2,2,2,8,1)                                                                                          \
+    X(G_964128, TY_BX3, 64,128,2,4,2,8,1)                                                                                        \
+    /* "lean" deep rings of the latency regime (lean_of): descriptor loader only */                                              \
+    X(G_L3264, TY_BF16 | TY_E4M3 | TY_BX3, 32,64,2,2,6,8,2)      /* 72 KiB: 2 blocks / CU */                                    \
+    X(G_L64648, TY_BF16 | TY_E4M3 | TY_BX3, 64,64,4,2,4,8,2)     /* 64 KiB: 2 blocks / CU */                                    \
+    X(G_L641288, TY_BF16 | TY_E4M3 | TY_BX3, 64,128,2,4,3,8,2)   /* 72 KiB: 2 blocks / CU */
+
+enum {
+#define X(ID, ...) ID,
+    GLDS_INSTANCES(X)
+#undef X
+};
+struct GldsCfg { int types, BM, BN, WM, WN, NS, CPR, STG; };
+static constexpr GldsCfg glds_cfg[] = {
+#define X(ID, ...) {__VA_ARGS__},
+    GLDS_INSTANCES(X)
+#undef X
+};
+// [instantiation][operand type: bf16, e4m3, f32, bx3]
+static const char* const glds_names[][4] = {
+#define X(ID, TY, ...) {"gemm_glds_kernel<bf16," #__VA_ARGS__ ">", "gemm_glds_kernel<e4m3," #__VA_ARGS__ ">", \
+                        "gemm_glds_kernel<f32," #__VA_ARGS__ ">", "gemm_glds_kernel<bx3," #__VA_ARGS__ ">"},
+    GLDS_INSTANCES(X)
+#undef X
+};
+
+// tile code -> instantiation, bf16 / e4m3 / fp32 operands (and a pre-split bf16x3 A, which the tile rule gives one of
+// 3264 / 64648 / 641288 / 1281288)
+static constexpr int glds_codes[][2] = {{256128, G_256128}, {128, G_128}, {64, G_64}, {3264, G_3264}, {1281288, G_1281288},
+                                        {641288, G_641288}, {64648, G_64648}, {256648, G_256648}, {128324, G_128324}, {964, G_964},
+                                        {91288, G_91288}, {912832, G_912832}, {9256648, G_9256648}};
+// bf16x3 with an fp32 A: the register-staged tiles.  code (also reported), alias (the bf16 code of the same tile), the automatic
+// rule's code this tile stands in for
+static constexpr struct { int code, alias, auto_of, inst; } bx3_codes[] = {
+    {93264, 3264, 3264, G_93264}, {964, 64, 64648, G_964}, {964128, 0, 641288, G_964128}, {91288, 128, 1281288, G_91288},
+    {912832, 0, 912832, G_912832}, {9256648, 0, 9256648, G_9256648}};
+
+// the conv3_halo_kernel instantiations: X(id, BN,WM,WN,NS), fp32 and bf16 operands.  (Ring depth: what keeps two blocks per CU beside
+// the 46 KB halo -- four 8 KB stages for 64 output channels, two 16 KB stages for 128.)
+#define HALO_INSTANCES(X) X(H_64, 64,4,2,4) X(H_128, 128,2,4,2)
+enum {
+#define X(ID, ...) ID,
+    HALO_INSTANCES(X)
+#undef X
+};
+static constexpr struct { int BN, WM, WN, NS; } halo_cfg[] = {
+#define X(ID, ...) {__VA_ARGS__},
+    HALO_INSTANCES(X)
+#undef X
+};
+static const char* const halo_names[][4] = {
+#define X(ID, ...) {"conv3_halo_kernel<bf16," #__VA_ARGS__ ">", nullptr, "conv3_halo_kernel<f32," #__VA_ARGS__ ">", nullptr},
+    HALO_INSTANCES(X)
+#undef X
+};
+
+// column of the name tables: the operand type of a GEMM precision (anything else runs as fp32, like elem_size)
+static inline int type_index(int precision) {
+    return precision == D2S_PREC_BF16 ? 0 : (precision == D2S_PREC_FP8_OPERANDS ? 1 : (precision == D2S_PREC_BF16X3 ? 3 : 2));
+}
+template <typename T> constexpr int type_bit() {
+    return std::is_same<T, bf16_t>::value ? TY_BF16 : std::is_same<T, fp8_t>::value ? TY_E4M3 : std::is_same<T, bx3_t>::value ? TY_BX3 : TY_F32;
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NS, int CPR = 8, int STG = 0>
-static void launch_glds(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
-    static const std::string name = std::string("gemm_glds_kernel<") + type_tag<T>() + "," + std::to_string(BM) + "," + std::to_string(BN) + "," +
-                                    std::to_string(WM) + "," + std::to_string(WN) + "," + std::to_string(NS) + "," + std::to_string(CPR) + "," + std::to_string(STG) + ">";
-    unsigned grid = 0;
-    int xn = pick_xn(cdiv(M, BM), cdiv(N, BN), BN, Kpad, sizeof(T), grid);
+static int plan_fail(GemmPlan& p, int rc, const char* msg) { p.error = msg; return rc; }
+static int glds_inst_of(int code) {
+    for (const auto& c : glds_codes) if (c[0] == code) return c[1];
+    return -1;
+}
+
+// gemm_glds_kernel instantiation inst, reported as tile code `tile`: XCD grid, split-K, descriptor addressing, statistics slots
+static int plan_glds(int inst, int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p) {
+    const GldsCfg& c = glds_cfg[inst];
+    const int es = (int)elem_size(precision), bk = c.CPR * (16 / es);
+    p.family = GEMM_GLDS; p.inst = inst; p.name = glds_names[inst][type_index(precision)]; p.tile = tile; p.block = 64 * c.WM * c.WN;
+    p.xn = pick_xn(cdiv(M, c.BM), cdiv(N, c.BN), c.BN, Kpad, es, p.grid);
     // split-K for the few launches with almost no tiles but a long K loop (DPT 3x3 convs on the 11x19 /
     // 21x37 maps with 768 input channels: 14-112 blocks x 108 K tiles): the caller provides e.part
-    int nkt = cdiv(K, CPR * (16 / (int)sizeof(T)));
+    const int nkt = cdiv(K, bk);
     int ks = 1;
-    if (STG != 2 && e.part && e.part_elems > 0 && !e.stats_out && (int)grid < SPLITK_GRID && nkt >= 24) {
+    if (c.STG != 2 && e.part && e.part_elems > 0 && !e.stats_out && (int)p.grid < SPLITK_GRID && nkt >= 24) {
         ks = nkt / 6; if (ks > 16) ks = 16;
         while (ks > 1 && (size_t)ks * M * N > e.part_elems) --ks;
     }
     static EnvInt sk_force{"D2S_SPLITK_FORCE", 0};          // measurement aid (tools/splitk_probe.py): this many K ranges whatever the grid
-    if (sk_force.get() > 1 && STG != 2 && e.part && !e.stats_out && nkt >= sk_force.get() && (size_t)sk_force.get() * M * N <= e.part_elems) ks = sk_force.get();
-    note_kernel(name.c_str(), ks);
-    if (ks > 1) {
-        GemmEpi e2 = e; e2.ksplit = ks;
-        hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WM, WN, NS, CPR, STG>), dim3(grid, ks), dim3(64 * WM * WN), 0, st, (const T*)W, a.ptr, a.lda, M, N, K, Kpad, xn, a, e2);
-        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(cdiv((long)M * (N / 4), 256)), dim3(256), 0, st, e2, M, N);
-        return;
-    }
-    GemmEpi e1 = e; e1.ksplit = 1;
-    if (e.stats_slots) *e.stats_slots = WN > 1 ? cdiv(N, BN) : 1 << 20;        // WN == 1 tiles write no statistics: the caller falls back
-    GemmA a1 = a;
-    {   // descriptor-addressed LDS-DMA: plain A, whole K tiles (the W zero padding covers nothing then), 32-bit byte offsets
-        constexpr int bk = CPR * (16 / (int)sizeof(T));
-        a1.buf = STG != 1 && buf_eligible(a, M, N, K, Kpad, bk, sizeof(T));
-    }
-    hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, WM, WN, NS, CPR, STG>), dim3(grid), dim3(64 * WM * WN), 0, st, (const T*)W, a1.ptr, a1.lda, M, N, K, Kpad, xn, a1, e1);
+    if (sk_force.get() > 1 && c.STG != 2 && e.part && !e.stats_out && nkt >= sk_force.get() && (size_t)sk_force.get() * M * N <= e.part_elems) ks = sk_force.get();
+    p.ksplit = ks; p.gridy = ks;
+    if (ks > 1) { p.grid2 = cdiv((long)M * (N / 4), 256); return D2S_OK; }      // partials, then splitk_reduce_kernel
+    p.stats_slots = c.WN > 1 ? cdiv(N, c.BN) : 1 << 20;        // WN == 1 tiles write no statistics: the caller falls back
+    // descriptor-addressed LDS-DMA: plain A, whole K tiles (the W zero padding covers nothing then), 32-bit byte offsets
+    p.buf = c.STG != 1 && buf_eligible(a, M, N, K, Kpad, bk, es);
+    return D2S_OK;
+}
+
+// Latency regime (batch 1-2: every block of the launch is resident at once, 1-2 per CU).  In-kernel stamps (tools/glds_timeline.py)
+// put a K tile at (LDS-DMA latency ~ 1 800 cycles) / (tiles in flight): 615 cycles with the 4-stage ring of the 32 x 64 tile, 1 100-1 300
+// with the 2-stage rings of the 8-wave tiles, next to 64-256 cycles of MFMA work.  The LDS those few blocks leave unused buys
+// ring depth: as many stages as still let ALL blocks be resident.  The "lean" instantiation for tile code t (descriptor loader only),
+// or -1.
+// (one block per CU with a 128 KiB ring -- 64 x 192 x 4 stages, 128 x 128 on 64-byte K tiles x 4 stages -- for FC1, whose 312
+//  blocks of 64 x 128 leave 56 CUs with two blocks: 13.5 / 15.6 us against 13.4 back to back; a single block does not reach
+//  the fill rate two reach together.  Measured, removed.)
+// (The same deeper rings for the implicit 3x3 convolutions of the small DPT maps at batch 1 -- general loaders, 32 x 64 x 6 / 64 x 64 x 4 /
+//  64 x 128 x 3 stages when every block is resident: 866-873 frames/s with and without, ViT-S 1 200 vs 1 227.  Measured, removed.)
+static int lean_of(int t, int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e) {
+    const int inst = t == 3264 ? G_L3264 : (t == 64648 ? G_L64648 : (t == 641288 ? G_L641288 : -1));
+    if (inst < 0 || !gemm_deep() || !buf_eligible(a, M, N, K, Kpad, gemm_bk(precision), elem_size(precision))) return -1;
+    const long tiles = (long)cdiv(M, glds_cfg[inst].BM) * cdiv(N, glds_cfg[inst].BN);
+    return tiles <= 512 && !splitk_wanted(e, tiles, K, gemm_bk(precision)) ? inst : -1;
+}
+
+// the tile code of a plain linear of this shape, N > 64: 1281288, 641288, 64648, or 3264 for the skinny launches (batch 1, N = 768)
+static int small_tile_of(int M, int N) {
+    const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
+    if (b128 >= 400 && (N >= 1536 || b128 >= 900)) return 1281288;
+    if (b64128 >= 280) return 641288;
+    if (b64 >= 384) return 64648;
+    return 3264;
+}
+
+// The automatic tile rule (tile == 0).  Measured on the ViT-B shapes at batch 1..32 (tools/gemm_bench.py, profiles/r1_05): what matters
+// most is 16-24 resident waves per CU in DIFFERENT phases of the K loop (8-wave blocks, 2-5 blocks per CU), then tile intensity; with
+// that in place the LDS-DMA path beats register staging (no VGPR / ds_write pass).  The 4-wave 32 x 64 ring (NS = 4: deepest prefetch,
+// shortest prologue) keeps the launches with the fewest tiles (batch 1: proj, FC2).
+static int auto_tile(int M, int N) {
+    if (N <= 64) return (long)cdiv(M, 256) >= 224 ? (N <= 32 ? 912832 : 9256648) : 3264;      // DPT head: 64 / 32 output channels, M = pixels
+    return small_tile_of(M, N);
 }
 
 // stride-1 3x3 convs on the large maps go to conv3_halo_kernel (input tile resident in LDS); D2S_NO_HALO=1 keeps the
 // implicit-GEMM loader (the parity tests run both)
-template <typename T>
-static bool launch_conv_halo(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st, bool dry = false) {
+static bool plan_halo(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p) {
     static EnvInt off{"D2S_NO_HALO", 0};
-    if (off.get()) return false;
-    if constexpr (std::is_same<T, fp8_t>::value) return false;
-    else {
-    const int cpp = a.C * (int)sizeof(T) / 16;
-    if (a.mode != A_CONV3 || a.stride != 1 || a.Hi != a.Ho || a.Wi != a.Wo || (a.C * (int)sizeof(T)) % 128 || cpp > 16 || (cpp & (cpp - 1))) return false;
+    if (off.get() || precision == D2S_PREC_FP8_OPERANDS) return false;
+    const int es = (int)elem_size(precision), cpp = a.C * es / 16;
+    if (a.mode != A_CONV3 || a.stride != 1 || a.Hi != a.Ho || a.Wi != a.Wo || (a.C * es) % 128 || cpp > 16 || (cpp & (cpp - 1))) return false;
     if (e.map != MAP_ROWS || e.rows_per_img || K != 9 * a.C || N <= 32) return false;   // (the N = 32 head conv measured 20 % slower here)
     const int nimg = M / (a.Ho * a.Wo);
     const long tiles_m = (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16);
     if (tiles_m * cdiv(N, 128) < 200 || (long)nimg * a.Ho * a.Wo != M) return false;      // small maps: too few tiles, latency-bound anyway
-    if (dry) return true;
-    GemmEpi e1 = e; e1.ksplit = 1;
-    unsigned grid = 0;
-#define D2S_HALO(BN_, WM_, WN_, NS_)                                                                                  \
-    { static const std::string name = std::string("conv3_halo_kernel<") + type_tag<T>() + "," #BN_ "," #WM_ "," #WN_ "," #NS_ ">"; \
-      note_kernel(name.c_str());                                                                                      \
-      int xn = pick_xn((int)tiles_m, cdiv(N, BN_), BN_, Kpad, sizeof(T), grid);                                       \
-      hipLaunchKernelGGL((conv3_halo_kernel<T, BN_, WM_, WN_, NS_>), dim3(grid), dim3(64 * WM_ * WN_), 0, st, a, (const T*)W, M, N, K, Kpad, e1, xn); }
-    // (ring depth: what keeps two blocks per CU beside the 46 KB halo -- four 8 KB stages for 64 output channels, two 16 KB stages for 128)
-    if (N <= 64) D2S_HALO(64, 4, 2, 4)
-    else D2S_HALO(128, 2, 4, 2)
-#undef D2S_HALO
+    const int inst = N <= 64 ? H_64 : H_128, bn = halo_cfg[inst].BN;
+    p.family = GEMM_HALO; p.inst = inst; p.block = 64 * halo_cfg[inst].WM * halo_cfg[inst].WN; p.ups = a.ups;
+    p.name = halo_names[inst][type_index(precision)];
+    p.xn = pick_xn((int)tiles_m, cdiv(N, bn), bn, Kpad, es, p.grid);
     return true;
-    }
-}
-
-// bf16x3 operands: the register-staged tiles only (the fp32 -> hi / lo split happens between the staging registers and LDS).
-// Same rule as the other types -- resident waves first, then tile intensity -- on the staged instantiations.
-static int launch_bx3(int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
-    typedef bx3_t T;
-    if (a.bx3) {
-        // A pre-split by its producer (LayerNorm / attention / GELU epilogue): LDS-DMA rings for both operands, the bf16 tile rule
-        if (a.mode != A_PLAIN || a.relu) { set_error("launch_gemm: a pre-split bf16x3 A operand must be a plain matrix"); return D2S_E_UNSUPPORTED; }
-        const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
-        int t = 3264;
-        if (b128 >= 400 && (N >= 1536 || b128 >= 900)) t = 1281288;
-        else if (b64128 >= 280) t = 641288;
-        else if (b64 >= 384) t = 64648;
-        kernel_note().tile = t;
-        // (latency regime: the deep-ring lean instantiations, as in launch_t)
-        const bool dp = gemm_deep() && buf_eligible(a, M, N, K, Kpad, 32, 4) &&
-                        !splitk_wanted(e, (long)cdiv(M, t == 3264 ? 32 : 64) * cdiv(N, t == 641288 ? 128 : 64), K, 32);
-        if (t == 3264 && dp && (long)cdiv(M, 32) * cdiv(N, 64) <= 512) launch_glds<T, 32, 64, 2, 2, 6, 8, 2>(a, W, M, N, K, Kpad, e, st);
-        else if (t == 64648 && dp && (long)cdiv(M, 64) * cdiv(N, 64) <= 512) launch_glds<T, 64, 64, 4, 2, 4, 8, 2>(a, W, M, N, K, Kpad, e, st);
-        else if (t == 641288 && dp && (long)cdiv(M, 64) * cdiv(N, 128) <= 512) launch_glds<T, 64, 128, 2, 4, 3, 8, 2>(a, W, M, N, K, Kpad, e, st);
-        else if (t == 3264) launch_glds<T, 32, 64, 2, 2, 4>(a, W, M, N, K, Kpad, e, st);
-        else if (t == 64648) launch_glds<T, 64, 64, 4, 2, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);
-        else if (t == 641288) launch_glds<T, 64, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);
-        else launch_glds<T, 128, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);      // t == 1281288
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-    if (tile == 256256) tile = 0;           // (the ping-pong tile code names no bf16x3 kernel: the automatic rule)
-    if (tile == 0) {
-        const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
-        if (N <= 64) tile = (long)cdiv(M, 256) >= 224 ? (N <= 32 ? 912832 : 9256648) : 93264;
-        else if (b128 >= 400 && (N >= 1536 || b128 >= 900)) tile = 91288;
-        else if (b64128 >= 280) tile = 964128;
-        else if (b64 >= 384) tile = 964;
-        else tile = 93264;
-    }
-    kernel_note().tile = tile;
-    if (tile == 93264 || tile == 3264) launch_glds<T, 32, 64, 2, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 964 || tile == 64) launch_glds<T, 64, 64, 2, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 964128) launch_glds<T, 64, 128, 2, 4, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 91288 || tile == 128) launch_glds<T, 128, 128, 4, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 912832) launch_glds<T, 128, 32, 4, 1, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);      // WN == 1: MAP_HEAD capable
-    else if (tile == 9256648) launch_glds<T, 256, 64, 8, 1, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);     // WN == 1, 8 waves
-    else { set_error("launch_gemm: bad tile code for bf16x3 operands"); return D2S_E_INVALID; }
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
-}
-
-// the (BM, BN) of the LDS-DMA tile launch_t picks for a plain linear of this shape (tile == 0 rule below, N > 64)
-static void small_tile_of(int M, int N, int& bm, int& bn) {
-    const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
-    if (b128 >= 400 && (N >= 1536 || b128 >= 900)) { bm = 128; bn = 128; }
-    else if (b64128 >= 280) { bm = 64; bn = 128; }
-    else if (b64 >= 384) { bm = 64; bn = 64; }
-    else { bm = 32; bn = 64; }
 }
 
 // (Weight warm-up, measured and removed: a small kernel on its own stream pulling the NEXT linear's weight rows into the L2 of the
@@ -794,133 +841,127 @@ int gemm_pp_min_tiles() {
     return v.get();
 }
 
-template <typename T>
-static int launch_t(int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
-    if (tile == 0 && launch_conv_halo<T>(a, W, M, N, K, Kpad, e, st)) { D2S_CHECK_LAUNCH(); return D2S_OK; }
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        // thin linears (K <= 256: ConvTranspose(k = s), fusion 1x1 projections): HBM-bound, one prologue per block instead of per tile
-        if (tile == 0 && sk_supported(D2S_PREC_BF16, a, M, N, K, Kpad, e)) return launch_gemm_sk(a, W, M, N, K, Kpad, e, st);
+// Everything launch_gemm does, decided from the arguments, the D2S_* switches and the CU count.  Host only: no launch, allocation or
+// stream work, so conv3_upsample_ok can ask it too.  On a rejected input p.error says why.
+int plan_gemm(int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p) {
+    p = GemmPlan{};
+    p.gridy = 1; p.ksplit = 1; p.buf = a.buf; p.stats_slots = -1;
+    const int ce = 16 / (int)elem_size(precision);
+    if (M <= 0 || N <= 0 || K <= 0 || (N & 3) || (K % ce) || Kpad % (2 * gemm_bk(precision)))
+        return plan_fail(p, D2S_E_INVALID, "launch_gemm: bad dims (N % 4, K % chunk, Kpad % BK)");
+    if (a.mode == A_PLAIN && (a.lda % ce)) return plan_fail(p, D2S_E_INVALID, "launch_gemm: lda not chunk aligned");
+    if (a.mode == A_CONV3 && (a.C % ce)) return plan_fail(p, D2S_E_INVALID, "launch_gemm: conv channels not chunk aligned");
+    if (precision == D2S_PREC_BF16X3) {
+        if (e.deq || (e.out2 && !e.out2_bx3))
+            return plan_fail(p, D2S_E_UNSUPPORTED, "launch_gemm: bf16x3 operands: no de-quantisation, raw-residual copies in the unit format only");
+        if (a.bx3) {
+            // A pre-split by its producer (LayerNorm / attention / GELU epilogue): LDS-DMA rings for both operands, the bf16 tile rule
+            // and, in the latency regime, its lean rings
+            if (a.mode != A_PLAIN || a.relu) return plan_fail(p, D2S_E_UNSUPPORTED, "launch_gemm: a pre-split bf16x3 A operand must be a plain matrix");
+            const int t = small_tile_of(M, N), lean = lean_of(t, precision, a, M, N, K, Kpad, e);
+            return plan_glds(lean >= 0 ? lean : glds_inst_of(t), precision, t, a, M, N, K, Kpad, e, p);
+        }
+        // fp32 A: the register-staged tiles only (the fp32 -> hi / lo split happens between the staging registers and LDS), picked by
+        // the same rule as the other types -- resident waves first, then tile intensity
+        if (tile == 256256) tile = 0;           // (the ping-pong tile code names no bf16x3 kernel: the automatic rule)
+        const int t = tile ? tile : auto_tile(M, N);
+        for (const auto& c : bx3_codes)
+            if (tile ? (tile == c.code || tile == c.alias) : t == c.auto_of) return plan_glds(c.inst, precision, tile ? tile : c.code, a, M, N, K, Kpad, e, p);
+        return plan_fail(p, D2S_E_INVALID, "launch_gemm: bad tile code for bf16x3 operands");
     }
-    if constexpr (!std::is_same<T, float>::value) {
-        // batched plain linears: the 256 x 256 ping-pong kernel (gemm_pp.hip) once the launch has enough tiles to fill the chip
-        // measured (tools/pp_check.py, ViT-B shapes): from ~140 tiles of 256 x 256 the ping-pong kernel wins every encoder
-        // linear (batch 16: +14..+30 %, batch 32: +9..+48 %); at 75 tiles (batch 8, N = 768) it loses.  D2S_GEMM_PP=0: off
-        const int pp_min_tiles = gemm_pp_min_tiles();                                       // (100 vs 140: +5 % at batch 12, proj / FC2 there)
-        const int prec = std::is_same<T, bf16_t>::value ? D2S_PREC_BF16 : D2S_PREC_FP8_OPERANDS;
-        if (tile == 0 && pp_min_tiles > 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= pp_min_tiles && pp_supported(prec, a, M, N, K, Kpad, e))
-            return launch_gemm_pp(prec, a, W, M, N, K, Kpad, e, st);
-        // (Tile rounding, batch 32: 294 tiles of N = 768 pay a second round for 38 tiles.  Giving the ping-pong kernel only the
-        //  tile rows that fill whole rounds and the remaining 3136 rows to the small-tile kernel -- two launches, disjoint rows --
-        //  was built and measured: FC2 156 -> 148 us, proj unchanged; the small-tile kernel needs as long for those rows as the
-        //  half-empty round.  Removed.)
+    if (tile == 256256) return plan_gemm_pp(precision, a, M, N, K, Kpad, e, p);      // the ping-pong kernel, forced (tests / sweeps)
+    // batched 3x3 convolutions (and the fused head, whose caller names a tile): input tile resident in LDS, conv3.hip
+    if (precision == D2S_PREC_BF16 && a.mode == A_CONV3 && (tile == 0 || e.map == MAP_HEAD) && plan_conv3_halo2(a, M, N, K, Kpad, e, p)) return D2S_OK;
+    if (a.ups) {        // only the LDS-resident-input kernels fold the up-sample (conv3_upsample_ok says when)
+        if (precision == D2S_PREC_BF16 && tile == 0 && plan_halo(precision, a, M, N, K, Kpad, e, p)) return D2S_OK;
+        return plan_fail(p, D2S_E_UNSUPPORTED, "launch_gemm: this launch cannot fold the up-sample into its loader (conv3_upsample_ok says when)");
     }
+    if (precision == D2S_PREC_FP8_OPERANDS && (a.mode != A_PLAIN || a.relu)) return plan_fail(p, D2S_E_UNSUPPORTED, "launch_gemm: e4m3 operands are for plain linears");
+    if (tile == 0 && plan_halo(precision, a, M, N, K, Kpad, e, p)) return D2S_OK;
+    // thin linears (K <= 256: ConvTranspose(k = s), fusion 1x1 projections): HBM-bound, one prologue per block instead of per tile
+    if (tile == 0 && sk_supported(precision, a, M, N, K, Kpad, e)) { plan_gemm_sk(a, M, N, K, p); return D2S_OK; }
+    // batched plain linears: the 256 x 256 ping-pong kernel (gemm_pp.hip) once the launch has enough tiles to fill the chip (bf16 and
+    // e4m3 operands: pp_supported).  Measured (tools/pp_check.py, ViT-B shapes): from ~140 tiles of 256 x 256 the ping-pong kernel wins
+    // every encoder linear (batch 16: +14..+30 %, batch 32: +9..+48 %); at 75 tiles (batch 8, N = 768) it loses.  D2S_GEMM_PP=0: off
+    // (100 vs 140: +5 % at batch 12, proj / FC2 there)
+    // (Tile rounding, batch 32: 294 tiles of N = 768 pay a second round for 38 tiles.  Giving the ping-pong kernel only the
+    //  tile rows that fill whole rounds and the remaining 3136 rows to the small-tile kernel -- two launches, disjoint rows --
+    //  was built and measured: FC2 156 -> 148 us, proj unchanged; the small-tile kernel needs as long for those rows as the
+    //  half-empty round.  Removed.)
+    const int pp_min_tiles = gemm_pp_min_tiles();
+    if (tile == 0 && pp_min_tiles > 0 && (long)cdiv(M, 256) * cdiv(N, 256) >= pp_min_tiles && pp_supported(precision, a, M, N, K, Kpad, e))
+        return plan_gemm_pp(precision, a, M, N, K, Kpad, e, p);
     if (tile == 0) {
-        // Measured on the ViT-B shapes at batch 1..32 (tools/gemm_bench.py, profiles/r1_05): what matters most is 16-24
-        // resident waves per CU in DIFFERENT phases of the K loop (8-wave blocks, 2-5 blocks per CU), then tile intensity;
-        // with that in place the LDS-DMA path beats register staging (no VGPR / ds_write pass).  The 4-wave 32 x 64 ring
-        // (NS = 4: deepest prefetch, shortest prologue) keeps the launches with the fewest tiles (batch 1: proj, FC2).
-        const long b128 = (long)cdiv(M, 128) * cdiv(N, 128), b64128 = (long)cdiv(M, 64) * cdiv(N, 128), b64 = (long)cdiv(M, 64) * cdiv(N, 64);
-        if (N <= 64) {                              // DPT head: 64 / 32 output channels, M = pixels
-            if ((long)cdiv(M, 256) >= 224) tile = N <= 32 ? 912832 : 9256648;
-            else tile = 3264;
-        }
-        else {
-            int bm = 0, bn = 0;
-            small_tile_of(M, N, bm, bn);
-            tile = bm == 128 ? 1281288 : (bn == 128 ? 641288 : (bm == 64 ? 64648 : 3264));     // 3264: skinny launches (batch 1, N = 768)
-            // long-K implicit convolutions (tap 3's stride-2 768 -> 768: K = 6 912) from ~300 tiles of 128 x 128: the 64 x 128 tile falls off a
-            // cliff there (batch 28: 130 us, batch 32: 188 us for 1.14 x the work) where the 128 x 128 tile stays at 128-134 us at every batch from
-            // 16 to 32 -- below 300 tiles the smaller tile is 5-15 % faster
-            if (a.mode == A_CONV3 && K >= 4096 && (long)cdiv(M, 128) * cdiv(N, 128) >= 300) tile = 1281288;
-        }
+        tile = auto_tile(M, N);
+        // long-K implicit convolutions (tap 3's stride-2 768 -> 768: K = 6 912) from ~300 tiles of 128 x 128: the 64 x 128 tile falls off a
+        // cliff there (batch 28: 130 us, batch 32: 188 us for 1.14 x the work) where the 128 x 128 tile stays at 128-134 us at every batch from
+        // 16 to 32 -- below 300 tiles the smaller tile is 5-15 % faster
+        if (N > 64 && a.mode == A_CONV3 && K >= 4096 && (long)cdiv(M, 128) * cdiv(N, 128) >= 300) tile = 1281288;
     }
-    kernel_note().tile = tile;
-    // Latency regime (batch 1-2: every block of the launch is resident at once, 1-2 per CU).  In-kernel stamps (tools/glds_timeline.py)
-    // put a K tile at (LDS-DMA latency ~ 1 800 cycles) / (tiles in flight): 615 cycles with the 4-stage ring of the 32 x 64 tile, 1 100-1 300
-    // with the 2-stage rings of the 8-wave tiles, next to 64-256 cycles of MFMA work.  The LDS those few blocks leave unused buys
-    // ring depth: as many stages as still let ALL blocks be resident.  "Lean" instantiations (descriptor loader only).
-    if constexpr (std::is_same<T, bf16_t>::value || std::is_same<T, fp8_t>::value) {
-        if (gemm_deep() && !(e.part && e.ksplit > 1) && buf_eligible(a, M, N, K, Kpad, 128 / (int)sizeof(T), sizeof(T)) && e.map != MAP_HEAD &&
-            !splitk_wanted(e, (long)cdiv(M, tile == 3264 ? 32 : 64) * cdiv(N, tile == 641288 ? 128 : 64), K, 128 / (int)sizeof(T))) {
-            bool done = true;
-            if (tile == 3264 && (long)cdiv(M, 32) * cdiv(N, 64) <= 512) launch_glds<T, 32, 64, 2, 2, 6, 8, 2>(a, W, M, N, K, Kpad, e, st);            // 72 KiB: 2 blocks / CU
-            else if (tile == 64648 && (long)cdiv(M, 64) * cdiv(N, 64) <= 512) launch_glds<T, 64, 64, 4, 2, 4, 8, 2>(a, W, M, N, K, Kpad, e, st);       // 64 KiB: 2 blocks / CU
-            else if (tile == 641288 && (long)cdiv(M, 64) * cdiv(N, 128) <= 512) launch_glds<T, 64, 128, 2, 4, 3, 8, 2>(a, W, M, N, K, Kpad, e, st);    // 72 KiB: 2 blocks / CU
-            // (one block per CU with a 128 KiB ring -- 64 x 192 x 4 stages, 128 x 128 on 64-byte K tiles x 4 stages -- for FC1, whose 312
-            //  blocks of 64 x 128 leave 56 CUs with two blocks: 13.5 / 15.6 us against 13.4 back to back; a single block does not reach
-            //  the fill rate two reach together.  Measured, removed.)
-            else done = false;
-            if (done) { D2S_CHECK_LAUNCH(); return D2S_OK; }
-        }
+    // the lean rings (bf16 and e4m3 operands) keep to launches without a MAP_HEAD epilogue or a caller-chosen K split
+    if ((precision == D2S_PREC_BF16 || precision == D2S_PREC_FP8_OPERANDS) && !(e.part && e.ksplit > 1) && e.map != MAP_HEAD) {
+        const int lean = lean_of(tile, precision, a, M, N, K, Kpad, e);
+        if (lean >= 0) return plan_glds(lean, precision, tile, a, M, N, K, Kpad, e, p);
     }
-    // (The same deeper rings for the implicit 3x3 convolutions of the small DPT maps at batch 1 -- general loaders, 32 x 64 x 6 / 64 x 64 x 4 /
-    //  64 x 128 x 3 stages when every block is resident: 866-873 frames/s with and without, ViT-S 1 200 vs 1 227.  Measured, removed.)
-    // LDS-DMA ring (NS stages)
-    if (tile == 256128) launch_glds<T, 256, 128, 4, 2, 3>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 128) launch_glds<T, 128, 128, 2, 2, 4>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 64) launch_glds<T, 64, 64, 2, 2, 4>(a, W, M, N, K, Kpad, e, st);
-    // (256-byte K tiles for this tile -- half the barrier-paced iterations -- measured at batch 1: 768 vs 766 frames/s with three
-    //  ring stages, 726 with two: the batch-1 launches are not paced by their K-loop iteration count)
-    else if (tile == 3264) launch_glds<T, 32, 64, 2, 2, 4>(a, W, M, N, K, Kpad, e, st);
-    // (One-round shapes for M = 778 -- 48 x 64, 96 x 64, 48 / 96 / 80 / 112 x 128, 112 x 96: 108-240 blocks of 2-4 waves, fewer
-    //  fill bytes per CU than two rounds of a small tile -- were instantiated and swept at batch 1: 1.2-4 x SLOWER than the
-    //  32 x 64 / 64 x 64 / 64 x 128 tiles on every encoder linear.  Resident waves per CU decide the fill rate a CU reaches.)
-    // LDS-DMA, 8 waves, two stages: the winners of the second sweep (profiles/r1_05), code <BM><BN>8
-    else if (tile == 1281288) launch_glds<T, 128, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);    // wave tile 64 x 32, 2 blocks / CU
-    else if (tile == 641288) launch_glds<T, 64, 128, 2, 4, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);      // 3 blocks / CU
-    else if (tile == 64648) launch_glds<T, 64, 64, 4, 2, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);        // 5 blocks / CU
-    else if (tile == 256648) launch_glds<T, 256, 64, 8, 1, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);      // WN == 1: MAP_HEAD capable
-    else if (tile == 128324) launch_glds<T, 128, 32, 4, 1, 2, 8, 0>(a, W, M, N, K, Kpad, e, st);      // WN == 1, 4 waves
-    // register-staged variants (STG), code = 9 <BM> <BN> [waves].  Removed after losing the sweeps: 256 x 128 / 256 x 256
-    // with 8 waves (1 block / CU, lock-step), 128 x 128 with 4 or 16 waves, deeper rings, 64- and 256-byte K tiles, two
-    // register sets, intra-block split-K
-    else if (tile == 964) launch_glds<T, 64, 64, 2, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);
-    else if (tile == 91288) launch_glds<T, 128, 128, 4, 2, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);       // 8 waves, 2 blocks / CU
-    else if (tile == 912832) launch_glds<T, 128, 32, 4, 1, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);       // WN == 1: MAP_HEAD capable
-    else if (tile == 9256648) launch_glds<T, 256, 64, 8, 1, 2, 8, 1>(a, W, M, N, K, Kpad, e, st);      // WN == 1, 8 waves
-    else { set_error("launch_gemm: bad tile code"); return D2S_E_INVALID; }
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
+    const int inst = glds_inst_of(tile);
+    if (inst < 0) return plan_fail(p, D2S_E_INVALID, "launch_gemm: bad tile code");
+    return plan_glds(inst, precision, tile, a, M, N, K, Kpad, e, p);
 }
 
 // Would launch_gemm fold the up-sample described by a.ups / Hs / Ws / usy / usx into this convolution's loader?  (The engine asks
-// before it skips the stand-alone up-sample launch.)  Same order of kernels as launch_gemm below.
+// before it skips the stand-alone up-sample launch.)
 bool conv3_upsample_ok(int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e) {
     static EnvInt no_ups{"D2S_NO_UPSFOLD", 0};
     if (no_ups.get() || precision != D2S_PREC_BF16 || a.mode != A_CONV3 || !a.ups || a.Hs < 2 || a.Ws < 2 || a.usy <= 0.f || a.usx <= 0.f) return false;
-    if ((tile == 0 || e.map == MAP_HEAD) && launch_conv3_halo2(a, nullptr, M, N, K, Kpad, e, nullptr, true)) return true;
-    return tile == 0 && launch_conv_halo<bf16_t>(a, nullptr, M, N, K, Kpad, e, nullptr, true);
+    GemmPlan p;
+    return plan_gemm(precision, tile, a, M, N, K, Kpad, e, p) == D2S_OK && p.ups;
 }
+
+// the planned gemm_glds_kernel / conv3_halo_kernel instantiation for operand type T (and the split-K reduce)
+template <typename T>
+static void launch_glds(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
+    const dim3 grid(p.grid, p.gridy), block(p.block);
+    if (p.family == GEMM_HALO) {
+        if constexpr ((type_bit<T>() & (TY_BF16 | TY_F32)) != 0) switch (p.inst) {
+#define X(ID, ...) case ID: hipLaunchKernelGGL((conv3_halo_kernel<T, __VA_ARGS__>), grid, block, 0, st, a, (const T*)W, M, N, K, Kpad, e, p.xn); break;
+            HALO_INSTANCES(X)
+#undef X
+        }
+        return;
+    }
+    switch (p.inst) {
+#define X(ID, TY, ...) case ID: if constexpr (((TY) & type_bit<T>()) != 0) \
+        hipLaunchKernelGGL((gemm_glds_kernel<T, __VA_ARGS__>), grid, block, 0, st, (const T*)W, a.ptr, a.lda, M, N, K, Kpad, p.xn, a, e); break;
+        GLDS_INSTANCES(X)
+#undef X
+    }
+    if (p.grid2) hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(p.grid2), dim3(256), 0, st, e, M, N);
+}
+
+static void note_kernel(const GemmPlan& p) { kernel_note() = KernelNote{p.name, p.tile, p.ksplit, p.tail}; }
 
 int launch_gemm(int precision, int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad,
                 const GemmEpi& e, hipStream_t st) {
-    const int ce = 16 / (int)elem_size(precision);
-    if (M <= 0 || N <= 0 || K <= 0 || (N & 3) || (K % ce) || Kpad % (2 * gemm_bk(precision))) {
-        set_error("launch_gemm: bad dims (N % 4, K % chunk, Kpad % BK)"); return D2S_E_INVALID;
+    GemmPlan p;
+    if (const int rc = plan_gemm(precision, tile, a, M, N, K, Kpad, e, p)) { set_error(p.error); return rc; }
+    note_kernel(p);
+    if (e.stats_slots && p.stats_slots >= 0) *e.stats_slots = p.stats_slots;
+    GemmA a1 = a;
+    a1.buf = p.buf;
+    GemmEpi e1 = e;
+    e1.ksplit = p.family == GEMM_GLDS ? p.ksplit : 1;
+    switch (p.family) {
+        case GEMM_CONV3: launch_conv3_halo2(p, a1, W, M, N, Kpad, e1, st); break;
+        case GEMM_SK: launch_gemm_sk(p, a1, W, M, N, Kpad, e1, st); break;
+        case GEMM_PP: if (const int rc = launch_gemm_pp(p, precision, a1, W, M, N, K, Kpad, e1, st)) return rc; break;
+        default:
+            if (precision == D2S_PREC_BF16) launch_glds<bf16_t>(p, a1, W, M, N, K, Kpad, e1, st);
+            else if (precision == D2S_PREC_FP8_OPERANDS) launch_glds<fp8_t>(p, a1, W, M, N, K, Kpad, e1, st);
+            else if (precision == D2S_PREC_BF16X3) launch_glds<bx3_t>(p, a1, W, M, N, K, Kpad, e1, st);
+            else launch_glds<float>(p, a1, W, M, N, K, Kpad, e1, st);
     }
-    if (a.mode == A_PLAIN && (a.lda % ce)) { set_error("launch_gemm: lda not chunk aligned"); return D2S_E_INVALID; }
-    if (a.mode == A_CONV3 && (a.C % ce)) { set_error("launch_gemm: conv channels not chunk aligned"); return D2S_E_INVALID; }
-    if (precision == D2S_PREC_BF16X3) {
-        if (e.deq || (e.out2 && !e.out2_bx3)) { set_error("launch_gemm: bf16x3 operands: no de-quantisation, raw-residual copies in the unit format only"); return D2S_E_UNSUPPORTED; }
-        return launch_bx3(tile, a, W, M, N, K, Kpad, e, st);
-    }
-    if (tile == 256256) return launch_gemm_pp(precision, a, W, M, N, K, Kpad, e, st);      // the ping-pong kernel, forced (tests / sweeps)
-    // batched 3x3 convolutions (and the fused head, whose caller names a tile): input tile resident in LDS, conv3.hip
-    if (precision == D2S_PREC_BF16 && a.mode == A_CONV3 && (tile == 0 || e.map == MAP_HEAD) && launch_conv3_halo2(a, W, M, N, K, Kpad, e, st)) {
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-    if (a.ups) {        // only the LDS-resident-input kernels fold the up-sample (conv3_upsample_ok says when)
-        if (precision == D2S_PREC_BF16 && tile == 0 && launch_conv_halo<bf16_t>(a, W, M, N, K, Kpad, e, st)) { D2S_CHECK_LAUNCH(); return D2S_OK; }
-        set_error("launch_gemm: this launch cannot fold the up-sample into its loader (conv3_upsample_ok says when)");
-        return D2S_E_UNSUPPORTED;
-    }
-    if (precision == D2S_PREC_BF16) return launch_t<bf16_t>(tile, a, W, M, N, K, Kpad, e, st);
-    if (precision == D2S_PREC_FP8_OPERANDS) {
-        if (a.mode != A_PLAIN || a.relu) { set_error("launch_gemm: e4m3 operands are for plain linears"); return D2S_E_UNSUPPORTED; }
-        return launch_t<fp8_t>(tile, a, W, M, N, K, Kpad, e, st);
-    }
-    return launch_t<float>(tile, a, W, M, N, K, Kpad, e, st);
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
 }
 
 // ---- test / micro-benchmark probe -----------------------------------------------------------------

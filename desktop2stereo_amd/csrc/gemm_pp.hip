@@ -955,8 +955,9 @@ static const float* pp_const_vec(bool ones) {
     return buf[d] + (ones ? PP_MAXN : 0);
 }
 
-int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
-    if (!pp_supported(precision, a, M, N, K, Kpad, e)) { set_error("launch_gemm_pp: unsupported problem"); return D2S_E_UNSUPPORTED; }
+// the ping-pong launch: kernel kind, XCD grid, K-split tail and start skew
+int plan_gemm_pp(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p) {
+    if (!pp_supported(precision, a, M, N, K, Kpad, e)) { p.error = "launch_gemm_pp: unsupported problem"; return D2S_E_UNSUPPORTED; }
     const int tiles_m = cdiv(M, 256), tiles_n = cdiv(N, 256);
     unsigned vgrid = 0;
     int xn = pick_xn(tiles_m, tiles_n, 256, Kpad, elem_size(precision), vgrid);
@@ -973,9 +974,9 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     const int ncu = device_cu_count();
     const int lxn = xn <= 1 ? 0 : (xn == 2 ? 1 : (xn == 4 ? 2 : 3));
     const bool ln = e.ln_csum != nullptr || e.stats_out != nullptr;
-    if (ln && e.out_type != OUT_F32 && e.map != MAP_QKV && e.act != ACT_GELU) { set_error("launch_gemm_pp: LN-folded consumer: QKV or FC1 only"); return D2S_E_UNSUPPORTED; }
+    if (ln && e.out_type != OUT_F32 && e.map != MAP_QKV && e.act != ACT_GELU) { p.error = "launch_gemm_pp: LN-folded consumer: QKV or FC1 only"; return D2S_E_UNSUPPORTED; }
     const int kind = e.out_type == OUT_F32 ? (ln ? PP_K_F32_LN : PP_K_F32) : (e.map == MAP_QKV ? (ln ? PP_K_QKV_LN : PP_K_QKV) : (e.act == ACT_GELU ? (ln ? PP_K_GELU_LN : PP_K_GELU) : PP_K_BF16));
-    if (e.stats_slots) *e.stats_slots = e.stats_out ? tiles_n : 1 << 20;                 // partials per row the consumer will find
+    p.stats_slots = e.stats_out ? tiles_n : 1 << 20;                                    // partials per row the consumer will find
     // K-split tail (see the kernel): when the last round would be less than 45 % full and the launch is a residual update
     const int tiles = tiles_m * tiles_n, nkt = K / (128 / (int)elem_size(precision));
     int tw = tiles, ks = 1, kps = nkt;
@@ -1019,28 +1020,31 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
         }
     }
     const int list_max = cdiv(tw, 8) + (ks > 1 ? ((ink & 1) ? cdiv(tiles - tw, 8) * ks : cdiv((tiles - tw) * ks, 8)) : 0);      // longest XCD unit list
-    const unsigned grid = 8u * (unsigned)std::max(1, std::min(ncu / 8, list_max));
-    {
-        static const char* const names[2][7] = {
-            {"gemm_pp_kernel<bf16,PP_K_BF16>", "gemm_pp_kernel<bf16,PP_K_GELU>", "gemm_pp_kernel<bf16,PP_K_QKV>", "gemm_pp_kernel<bf16,PP_K_F32>",
-             "gemm_pp_kernel<bf16,PP_K_GELU_LN>", "gemm_pp_kernel<bf16,PP_K_QKV_LN>", "gemm_pp_kernel<bf16,PP_K_F32_LN>"},
-            {"gemm_pp_kernel<e4m3,PP_K_BF16>", "gemm_pp_kernel<e4m3,PP_K_GELU>", "gemm_pp_kernel<e4m3,PP_K_QKV>", "gemm_pp_kernel<e4m3,PP_K_F32>",
-             nullptr, nullptr, nullptr}};                      // (the LN kinds: bf16 only, pp_supported)
-        note_kernel(names[precision == D2S_PREC_BF16 ? 0 : 1][kind], ks,
-                    ks == 1 ? NOTE_TAIL_NONE : ((ink & 4) ? NOTE_TAIL_ROWSPLIT : (ink ? NOTE_TAIL_INKERNEL : NOTE_TAIL_TWO_LAUNCH)));
-        kernel_note().tile = 256256;
-    }
+    static const char* const names[2][7] = {
+        {"gemm_pp_kernel<bf16,PP_K_BF16>", "gemm_pp_kernel<bf16,PP_K_GELU>", "gemm_pp_kernel<bf16,PP_K_QKV>", "gemm_pp_kernel<bf16,PP_K_F32>",
+         "gemm_pp_kernel<bf16,PP_K_GELU_LN>", "gemm_pp_kernel<bf16,PP_K_QKV_LN>", "gemm_pp_kernel<bf16,PP_K_F32_LN>"},
+        {"gemm_pp_kernel<e4m3,PP_K_BF16>", "gemm_pp_kernel<e4m3,PP_K_GELU>", "gemm_pp_kernel<e4m3,PP_K_QKV>", "gemm_pp_kernel<e4m3,PP_K_F32>",
+         nullptr, nullptr, nullptr}};                      // (the LN kinds: bf16 only, pp_supported)
+    p.family = GEMM_PP; p.inst = kind; p.name = names[precision == D2S_PREC_BF16 ? 0 : 1][kind]; p.tile = 256256;
+    p.grid = 8u * (unsigned)std::max(1, std::min(ncu / 8, list_max)); p.block = 512;
+    p.grid2 = ks > 1 && !ink ? (unsigned)(tiles - tw) * 64u : 0;       // (two-launch K-split path: D2S_PP_INK=0)
+    p.ksplit = ks; p.kps = kps; p.tw = tw; p.ink = ink; p.lxn = lxn;
+    p.tail = ks == 1 ? NOTE_TAIL_NONE : ((ink & 4) ? NOTE_TAIL_ROWSPLIT : (ink ? NOTE_TAIL_INKERNEL : NOTE_TAIL_TWO_LAUNCH));
+    // half a tile time: K tiles x ~1.5 us + ~8 us of prologue / epilogue (D2S_PP_SKEW: percent of that; 0 = off)
+    static EnvInt skew_pct{"D2S_PP_SKEW", 50};
+    // (with a K-split tail the lists end in short units: a block without one is not half a tile "lighter")
+    p.skew_us = ks > 1 ? 0 : (int)((K / (128 / (int)elem_size(precision)) * 1.5 + 8.0) * skew_pct.get() / 100.0);
+    return D2S_OK;
+}
+
+int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
     GemmEpi e1 = e;
-    e1.ksplit = 1;
     if (!e1.bias) e1.bias = pp_const_vec(false);
     if (!e1.scale) e1.scale = pp_const_vec(true);
     if (!e1.deq) e1.deq = pp_const_vec(true);
     if (!e1.bias || !e1.scale || !e1.deq) { set_error("launch_gemm_pp: constant vectors"); return D2S_E_HIP; }
-    // half a tile time: K tiles x ~1.5 us + ~8 us of prologue / epilogue (D2S_PP_SKEW: percent of that; 0 = off)
-    static EnvInt skew_pct{"D2S_PP_SKEW", 50};
-    // (with a K-split tail the lists end in short units: a block without one is not half a tile "lighter")
-    const int skew_us = ks > 1 ? 0 : (int)((K / (128 / (int)elem_size(precision)) * 1.5 + 8.0) * skew_pct.get() / 100.0);
-#define PP_LAUNCH(T_, KIND_) hipLaunchKernelGGL((gemm_pp_kernel<T_, KIND_>), dim3(grid), dim3(512), 0, st, (const T_*)a.ptr, a.lda, (const T_*)W, M, N, K, Kpad, e1, lxn, skew_us, tw, ks, kps, ink)
+#define PP_LAUNCH(T_, KIND_) hipLaunchKernelGGL((gemm_pp_kernel<T_, KIND_>), dim3(p.grid), dim3(p.block), 0, st, (const T_*)a.ptr, a.lda, (const T_*)W, M, N, K, Kpad, e1, p.lxn, p.skew_us, p.tw, p.ksplit, p.kps, p.ink)
+    const int kind = p.inst;
     if (precision == D2S_PREC_BF16) {
         if (kind == PP_K_F32) PP_LAUNCH(bf16_t, PP_K_F32); else if (kind == PP_K_QKV) PP_LAUNCH(bf16_t, PP_K_QKV);
         else if (kind == PP_K_GELU) PP_LAUNCH(bf16_t, PP_K_GELU);
@@ -1052,13 +1056,9 @@ int launch_gemm_pp(int precision, const GemmA& a, const void* W, int M, int N, i
     }
 #undef PP_LAUNCH
     D2S_CHECK_LAUNCH();
-    if (ks > 1 && !ink) {                          // (two-launch K-split path: D2S_PP_INK=0)
-        GemmEpi e2 = e;
-        e2.ksplit = 1;
-        const unsigned rgrid = (unsigned)(tiles - tw) * 64u;
-        if (precision == D2S_PREC_BF16) hipLaunchKernelGGL((pp_tail_reduce_kernel<bf16_t>), dim3(rgrid), dim3(256), 0, st, e2, M, N, tw, ks, lxn);
-        else hipLaunchKernelGGL((pp_tail_reduce_kernel<fp8_t>), dim3(rgrid), dim3(256), 0, st, e2, M, N, tw, ks, lxn);
-        D2S_CHECK_LAUNCH();
+    if (p.grid2) {
+        if (precision == D2S_PREC_BF16) hipLaunchKernelGGL((pp_tail_reduce_kernel<bf16_t>), dim3(p.grid2), dim3(256), 0, st, e, M, N, p.tw, p.ksplit, p.lxn);
+        else hipLaunchKernelGGL((pp_tail_reduce_kernel<fp8_t>), dim3(p.grid2), dim3(256), 0, st, e, M, N, p.tw, p.ksplit, p.lxn);
     }
     return D2S_OK;
 }

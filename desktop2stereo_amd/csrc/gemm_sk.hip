@@ -107,26 +107,25 @@ bool sk_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, 
     return true;
 }
 
-int launch_gemm_sk(const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
-    if (!sk_supported(D2S_PREC_BF16, a, M, N, K, Kpad, e)) { set_error("launch_gemm_sk: unsupported problem"); return D2S_E_UNSUPPORTED; }
-    const int ncu = device_cu_count();
-    const int cols = N / SK_BN, tiles_m = cdiv(M, SK_ROWS);
-    // two blocks per CU (<= 83 KiB of LDS each); every block streams >= 2 row tiles where there are that many
-    int per_col = std::max(1, std::min(tiles_m, (2 * ncu) / cols));
-    GemmEpi e1 = e; e1.ksplit = 1;
-    const dim3 grid(cols, per_col), block(256);
+// the instantiation is the number of 32-wide K steps (sk_supported: 32 <= K <= 256)
+void plan_gemm_sk(const GemmA& a, int M, int N, int K, GemmPlan& p) {
     static const char* const names[8] = {"gemm_sk_kernel<1>", "gemm_sk_kernel<2>", "gemm_sk_kernel<3>", "gemm_sk_kernel<4>",
                                          "gemm_sk_kernel<5>", "gemm_sk_kernel<6>", "gemm_sk_kernel<7>", "gemm_sk_kernel<8>"};
-    note_kernel(names[std::min(std::max(K / 32, 1), 8) - 1]);        // (sk_supported, checked above: 32 <= K <= 256)
-    kernel_note().tile = 0;
-#define SK_LAUNCH(KS_) hipLaunchKernelGGL((gemm_sk_kernel<KS_>), grid, block, 0, st, (const bf16_t*)a.ptr, a.lda, (const bf16_t*)W, Kpad, M, N, e1)
-    switch (K / 32) {
+    const int ncu = device_cu_count();
+    const int cols = N / SK_BN, tiles_m = cdiv(M, SK_ROWS);
+    p.family = GEMM_SK; p.inst = std::min(std::max(K / 32, 1), 8); p.name = names[p.inst - 1];
+    // two blocks per CU (<= 83 KiB of LDS each); every block streams >= 2 row tiles where there are that many
+    p.grid = cols; p.gridy = std::max(1, std::min(tiles_m, (2 * ncu) / cols)); p.block = 256;
+}
+
+void launch_gemm_sk(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int Kpad, const GemmEpi& e, hipStream_t st) {
+    const dim3 grid(p.grid, p.gridy), block(p.block);
+#define SK_LAUNCH(KS_) hipLaunchKernelGGL((gemm_sk_kernel<KS_>), grid, block, 0, st, (const bf16_t*)a.ptr, a.lda, (const bf16_t*)W, Kpad, M, N, e)
+    switch (p.inst) {
         case 1: SK_LAUNCH(1); break; case 2: SK_LAUNCH(2); break; case 3: SK_LAUNCH(3); break; case 4: SK_LAUNCH(4); break;
         case 5: SK_LAUNCH(5); break; case 6: SK_LAUNCH(6); break; case 7: SK_LAUNCH(7); break; default: SK_LAUNCH(8); break;
     }
 #undef SK_LAUNCH
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
 }
 
 }  // namespace d2s

@@ -141,7 +141,7 @@ def engine_cases(model: str, B: int, prec: str, frame=(1080, 1920, 518)):
 
 def ragged_cases(ncu: int):
     """Small shapes that reach each kernel of the dispatcher at, just below and just above its thresholds (conv3.hip
-    launch_conv3_halo2, gemm.hip launch_gemm): ragged maps, maps smaller than one tile, odd batches, persistent grids whose
+    plan_conv3_halo2, gemm.hip plan_gemm): ragged maps, maps smaller than one tile, odd batches, persistent grids whose
     tile count is not a multiple of the grid, up-sample scales at and just above the limits.  The persistent head kernels'
     tile minimums are lowered so that they run at these sizes."""
     hp = {"D2S_HEADP_MIN": "8"}            # conv3_head*_kernel from 8 tiles of 16 x 16

@@ -130,12 +130,12 @@ def temporal_cases(model: str, frame, prec: str = "bf16"):
 
 
 def ragged_cases():
-    """Both sides of every dispatch threshold, ragged shapes, and one case per kernel behind launch_gemm / launch_bx3 / launch_gemm_pp /
-    launch_gemm_sk that no engine case of this file reaches (rules: gemm.hip launch_t / launch_bx3 / splitk_wanted, gemm_pp.hip
-    pp_supported / launch_gemm_pp, gemm_sk.hip sk_supported)."""
+    """Both sides of every dispatch threshold, ragged shapes, and one case per kernel plan_gemm can choose
+    that no engine case of this file reaches (rules: gemm.hip plan_gemm / lean_of / splitk_wanted, gemm_pp.hip pp_supported /
+    plan_gemm_pp, gemm_sk.hip sk_supported)."""
     cs = []
     ws = 1 << 24
-    # launch_t's lean-ring limit: 512 blocks of 32 x 64 (3264: M = 32 * 8, N = 64 * 64 / 64 * 65)
+    # lean_of's lean-ring limit: 512 blocks of 32 x 64 (3264: M = 32 * 8, N = 64 * 64 / 64 * 65)
     cs += [Case("lean-3264-512", "proj", "bf16", 256, 4096, 256, scale=True), Case("lean-3264-520", "proj", "bf16", 256, 4160, 256, scale=True)]
     # gemm_pp_min_tiles (100 tiles of 256 x 256): FC1-like GELU launches at 99 / 100 tiles, and the residual update at 99 / 100
     cs += [Case("pp-min-99", "fc1", "bf16", 99 * 256, 256, 256), Case("pp-min-100", "fc1", "bf16", 100 * 256, 256, 256),
@@ -166,7 +166,7 @@ def ragged_cases():
         cs += [Case(f"ragged-m1-{prec}", "fc1", prec, 1, 256, 256), Case(f"ragged-m777-{prec}", wide, prec, 777, 260, 128),
                Case(f"ragged-n252-{prec}", wide, prec, 333, 252, 64), Case(f"ragged-n132-{prec}", "tm_kvq", prec, 129, 132, 64, bias=False),
                Case(f"ragged-patch-{prec}", "patch", prec, 3 * 37, 256, 588, ntok=38)]
-    # the register-staged / 8-wave / pre-split bf16x3 tiles of launch_bx3 and launch_t's automatic rule at large M
+    # the register-staged / 8-wave / pre-split bf16x3 tiles and plan_gemm's automatic rule at large M
     cs += [Case("bx3-presplit-641288", "fc1", "bf16x3", 8 * 778, 1536, 384), Case("bx3-presplit-1281288", "fc1", "bf16x3", 32 * 778, 1536, 384),
            Case("bx3-presplit-64648", "proj", "bf16x3", 8 * 778, 384, 384, scale=True),
            Case("bx3-964128", "neck_proj", "bf16x3", 8 * 778, 384, 384, ntok=778), Case("bx3-91288", "neck_proj", "bf16x3", 32 * 778, 1536, 384, ntok=778),
