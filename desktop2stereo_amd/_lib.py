@@ -52,6 +52,7 @@ class DibrParams(C.Structure):
 
 
 DIBR_ALPHA = {"window": 0, "premultiplied": 1, "rgba": 2}      # D2S_DIBR_ALPHA_*
+COMPOSITE = {"Anaglyph": 0, "Interleaved": 1, "Interleaved-V": 2, "Depth Map": 3}      # D2S_COMPOSITE_*
 
 
 class Conv3ProbeParams(C.Structure):
@@ -114,6 +115,8 @@ SYMBOLS = {
     "d2s_sbs_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(SbsParams), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "d2s_dibr_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "d2s_dibr_warp": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), _P, C.c_int, _P]),
+    "d2s_dibr_composite_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "d2s_dibr_composite": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, _P, C.c_int, _P]),
     "d2s_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "d2s_jpeg_encode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "d2s_present_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),

@@ -8,224 +8,10 @@
 // (viewer.py:395, 413: pixel_size = 1/0), so the resolution is a parameter here (0 -> source size).  Colours are kept
 // in 0..255; frag_color.a follows d2s_dibr_params.alpha_mode (the reference draws these quads with blending off: WINDOW = rgb as written).
 // Line numbers in the comments below are viewer.py.
-#include "common.h"
-#include <math.h>
+#include "dibr_tex.h"
 #include <algorithm>
 
 namespace d2s {
-
-struct DibrGeom {
-    int H, W;              // source frame == depth size
-    int oh, ow;            // per-eye viewport
-    int mode;              // D2S_MODE_*: where the two eyes land in the output
-    int out_h, out_w;      // packed output
-    float c, s;            // cos / sin(u_roll)
-    float psx, psy;        // pixel_size
-    float half_ipd, strength, conv;
-    float tol, blur, feather_w;
-    int search, feather;
-    int alpha_mode;        // D2S_DIBR_ALPHA_*
-    float corner_r, vpx, vpy, vpw, vph;             // u_corner_radius; u_viewport in eye-image pixels (y up)
-    float w1[20], w2[20];  // exp(-i*0.15), exp(-i*0.2), i < 16 (the sweeps index in groups of four: up to [16..18], never used)
-};
-
-// GL_REPEAT index: one conditional add / subtract covers every coordinate within one period of the texture (all but
-// absurd parallax settings); the integer modulo (~25 instructions on this ISA) is the fallback
-__device__ __forceinline__ int wrapi(int i, int n) {
-    if (i < 0) i += n; else if (i >= n) i -= n;
-    if ((unsigned)i >= (unsigned)n) { i %= n; if (i < 0) i += n; }
-    return i;
-}
-
-struct TexTap { int x0, x1, y0, y1; float fx, fy; };
-__device__ __forceinline__ TexTap tex_tap(float u, float v, int H, int W) {
-    float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    float x0f = floorf(x), y0f = floorf(y);
-    TexTap t;
-    t.fx = x - x0f; t.fy = y - y0f;
-    t.x0 = wrapi((int)x0f, W); t.y0 = wrapi((int)y0f, H);
-    t.x1 = t.x0 + 1 == W ? 0 : t.x0 + 1;
-    t.y1 = t.y0 + 1 == H ? 0 : t.y0 + 1;
-    return t;
-}
-__device__ __forceinline__ float lerp2(float a, float b, float c, float d, float fx, float fy) {
-    float top = a + (b - a) * fx, bot = c + (d - c) * fx;
-    return top + (bot - top) * fy;
-}
-// The two texels of a row are adjacent except across the GL_REPEAT seam: one 8-byte load per row (gfx950 runs with
-// unaligned access enabled: a dwordx2 at a 4-byte / a byte address is one instruction) instead of two 4-byte / six
-// 1-byte loads -- the kernel is bound by the number of gather instructions, not by bytes.
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-__device__ __forceinline__ float tex_depth(const float* __restrict__ dep, int H, int W, float u, float v) {
-    TexTap t = tex_tap(u, v, H, W);
-    const float* r0 = dep + t.y0 * W;                // (H * W < 2^31 / 3 is checked by the launcher: 32-bit texel indices)
-    const float* r1 = dep + t.y1 * W;
-    if (t.x1 == t.x0 + 1) {
-        f32x2u a = *(const f32x2u*)(r0 + t.x0), b = *(const f32x2u*)(r1 + t.x0);
-        return lerp2(a.x, a.y, b.x, b.y, t.fx, t.fy);
-    }
-    return lerp2(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.fx, t.fy);
-}
-__device__ __forceinline__ void tex_color(const uint8_t* __restrict__ rgb, int H, int W, float u, float v, float o[3]) {
-    TexTap t = tex_tap(u, v, H, W);
-    const int ia = (t.y0 * W + t.x0) * 3, ic = (t.y1 * W + t.x0) * 3, end = H * W * 3;
-    if (t.x1 == t.x0 + 1 && ia + 8 <= end && ic + 8 <= end) {          // (the 8-byte window must stay inside the frame)
-        uint2 p, q;
-        __builtin_memcpy(&p, rgb + ia, 8);
-        __builtin_memcpy(&q, rgb + ic, 8);
-        const float a[3] = {(float)(p.x & 255u), (float)((p.x >> 8) & 255u), (float)((p.x >> 16) & 255u)};
-        const float b[3] = {(float)(p.x >> 24), (float)(p.y & 255u), (float)((p.y >> 8) & 255u)};
-        const float c[3] = {(float)(q.x & 255u), (float)((q.x >> 8) & 255u), (float)((q.x >> 16) & 255u)};
-        const float d[3] = {(float)(q.x >> 24), (float)(q.y & 255u), (float)((q.y >> 8) & 255u)};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = lerp2(a[k], b[k], c[k], d[k], t.fx, t.fy);
-        return;
-    }
-    const uint8_t* a = rgb + ia;
-    const uint8_t* b = rgb + (t.y0 * W + t.x1) * 3;
-    const uint8_t* c = rgb + ic;
-    const uint8_t* d = rgb + (t.y1 * W + t.x1) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = lerp2((float)a[k], (float)b[k], (float)c[k], (float)d[k], t.fx, t.fy);
-}
-// roll == 0 (the desktop viewer; OpenXR sets a roll): every tap of a pixel except the two vertical-blur taps lies on the pixel's own
-// texture row pair, so the y half of tex_tap -- v * H - 0.5, floor, GL_REPEAT wrap, the two row bases -- is formed ONCE per pixel
-// (same expressions on the same v: the same bits as a per-tap evaluation) and a tap is its x half alone.
-struct RowCtx { const float* d0; const float* d1; int c0, c1; float fy; };
-__device__ __forceinline__ RowCtx row_ctx(const float* __restrict__ dep, int H, int W, float v) {
-    const float y = v * (float)H - 0.5f, y0f = floorf(y);
-    RowCtx r;
-    r.fy = y - y0f;
-    const int y0 = wrapi((int)y0f, H), y1 = y0 + 1 == H ? 0 : y0 + 1;
-    r.d0 = dep + y0 * W; r.d1 = dep + y1 * W;
-    r.c0 = y0 * W * 3; r.c1 = y1 * W * 3;
-    return r;
-}
-struct XTap { int x0, x1; float fx; };
-__device__ __forceinline__ XTap x_tap(float u, int W) {
-    const float x = u * (float)W - 0.5f, x0f = floorf(x);
-    XTap t;
-    t.fx = x - x0f;
-    t.x0 = wrapi((int)x0f, W);
-    t.x1 = t.x0 + 1 == W ? 0 : t.x0 + 1;
-    return t;
-}
-__device__ __forceinline__ float tex_depth_row(const RowCtx& r, int W, float u) {
-    const XTap t = x_tap(u, W);
-    if (t.x1 == t.x0 + 1) {
-        f32x2u a = *(const f32x2u*)(r.d0 + t.x0), b = *(const f32x2u*)(r.d1 + t.x0);
-        return lerp2(a.x, a.y, b.x, b.y, t.fx, r.fy);
-    }
-    return lerp2(r.d0[t.x0], r.d0[t.x1], r.d1[t.x0], r.d1[t.x1], t.fx, r.fy);
-}
-__device__ __forceinline__ void tex_color_row(const uint8_t* __restrict__ rgb, const RowCtx& r, int H, int W, float u, float o[3]) {
-    const XTap t = x_tap(u, W);
-    const int ia = r.c0 + t.x0 * 3, ic = r.c1 + t.x0 * 3, end = H * W * 3;
-    if (t.x1 == t.x0 + 1 && ia + 8 <= end && ic + 8 <= end) {
-        uint2 p, q;
-        __builtin_memcpy(&p, rgb + ia, 8);
-        __builtin_memcpy(&q, rgb + ic, 8);
-        const float a[3] = {(float)(p.x & 255u), (float)((p.x >> 8) & 255u), (float)((p.x >> 16) & 255u)};
-        const float b[3] = {(float)(p.x >> 24), (float)(p.y & 255u), (float)((p.y >> 8) & 255u)};
-        const float c[3] = {(float)(q.x & 255u), (float)((q.x >> 8) & 255u), (float)((q.x >> 16) & 255u)};
-        const float d[3] = {(float)(q.x >> 24), (float)(q.y & 255u), (float)((q.y >> 8) & 255u)};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = lerp2(a[k], b[k], c[k], d[k], t.fx, r.fy);
-        return;
-    }
-    const uint8_t* a = rgb + ia;
-    const uint8_t* b = rgb + r.c0 + t.x1 * 3;
-    const uint8_t* c = rgb + ic;
-    const uint8_t* d = rgb + r.c1 + t.x1 * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = lerp2((float)a[k], (float)b[k], (float)c[k], (float)d[k], t.fx, r.fy);
-}
-// Where a pixel's taps come from.  own_*: taps on the pixel's own texture row pair when roll == 0 (any (u, v) otherwise);
-// any_*: the two vertical-blur taps of the in-painting (other rows), always the general gather.
-struct GenSmp {                                    // general: every tap evaluates both coordinates (roll != 0)
-    const uint8_t* rgb; const float* dep; int H, W;
-    __device__ __forceinline__ float own_depth(float u, float v) const { return tex_depth(dep, H, W, u, v); }
-    __device__ __forceinline__ void own_color(float u, float v, float o[3]) const { tex_color(rgb, H, W, u, v, o); }
-    __device__ __forceinline__ float any_depth(float u, float v) const { return tex_depth(dep, H, W, u, v); }
-    __device__ __forceinline__ void any_color(float u, float v, float o[3]) const { tex_color(rgb, H, W, u, v, o); }
-};
-struct RowSmp : GenSmp {                           // roll == 0: the row pair is formed once per pixel
-    RowCtx rc;
-    __device__ __forceinline__ float own_depth(float u, float) const { return tex_depth_row(rc, W, u); }
-    __device__ __forceinline__ void own_color(float u, float, float o[3]) const { tex_color_row(rgb, rc, H, W, u, o); }
-};
-// roll == 0, the block's row pair staged in LDS: a window of WW texels starting at (unwrapped) texel wx0, GL_REPEAT applied by
-// the staging loop; planes d0 | d1 | R0 G0 B0 | R1 G1 B1 as floats (the same byte -> float conversions the gather path makes per
-// tap).  A tap is index arithmetic + ds_read2_b32 pairs; taps that leave the window (parallax settings beyond the margin the
-// launcher sized it for) take the row gather: same values either way.
-struct WinSmp : RowSmp {
-    const float* dwin;          // [2][WW]: the row pair of the depth texture
-    const float* cwin;          // [6][WW]: R0 G0 B0 R1 G1 B1 as floats
-    int wx0, WW;
-    __device__ __forceinline__ float own_depth(float u, float v) const {
-        const float x = u * (float)W - 0.5f, x0f = floorf(x), fx = x - x0f;
-        const int j = (int)x0f - wx0;
-        if ((unsigned)j < (unsigned)(WW - 1)) {
-            const float* p = dwin + j;
-            return lerp2(p[0], p[1], p[WW], p[WW + 1], fx, rc.fy);
-        }
-        return RowSmp::own_depth(u, v);
-    }
-    __device__ __forceinline__ void own_color(float u, float v, float o[3]) const {
-        const float x = u * (float)W - 0.5f, x0f = floorf(x), fx = x - x0f;
-        const int j = (int)x0f - wx0;
-        if ((unsigned)j < (unsigned)(WW - 1)) {
-            const float* p = cwin + j;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) o[k] = lerp2(p[k * WW], p[k * WW + 1], p[(3 + k) * WW], p[(3 + k) * WW + 1], fx, rc.fy);
-            return;
-        }
-        RowSmp::own_color(u, v, o);
-    }
-};
-__device__ __forceinline__ float smoothstepf(float e0, float e1, float x) {
-    float t = fminf(fmaxf((x - e0) / (e1 - e0), 0.f), 1.f);
-    return t * t * (3.f - 2.f * t);
-}
-// constant edges: 1 / (e1 - e0) is a literal (an IEEE division is ~20 instructions here and the kernel is VALU-bound:
-// profiles/r1_09: 610 VALU instructions per pixel before, 7 of these per pixel)
-#define SMOOTHSTEP_C(E0, E1, X) smoothstep_inv((E0), (float)(1.0 / ((double)(E1) - (double)(E0))), (X))
-__device__ __forceinline__ float smoothstep_inv(float e0, float inv, float x) {
-    float t = fminf(fmaxf((x - e0) * inv, 0.f), 1.f);
-    return t * t * (3.f - 2.f * t);
-}
-__device__ __forceinline__ bool oob(float u, float v) { return u < 0.f || v < 0.f || u > 1.f || v > 1.f; }
-
-__device__ __forceinline__ float g_w_phase1(float w1i, float sdi, float cdi) { return w1i * (1.0f + (sdi - cdi) * 10.0f); }   // :459
-// phase 3 of push_pull_inpaint (:484-505): normalise + 3-tap vertical blur, or the pixel's own colour when nothing was found
-template <class S>
-__device__ __forceinline__ void push_pull_finish(const S& smp, const DibrGeom& g, float u, float v, float cdi, const float best[3], float bw, float out[3]) {
-    if (bw > 0.01f) {                                                                 // phase 3 (:484-502)
-        float va[3] = {best[0] / bw * 0.5f, best[1] / bw * 0.5f, best[2] / bw * 0.5f}, vw = 0.5f;
-        // the two vertical taps touch other texture rows: global gathers.  All six of their loads are requested before the first is
-        // used (the depth test decides what is ADDED, not what is fetched): one round trip instead of up to four dependent ones at
-        // the end of every in-painted pixel; the sums keep the order dy = -1, +1
-        float vdi[2], vc[2][3];
-        bool ok[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const float vv = v + (float)(2 * t - 1) * g.psy * g.blur;
-            ok[t] = vv >= 0.f && vv <= 1.f;
-            const float vs = ok[t] ? vv : v;                                          // (a valid row for the unconditional loads)
-            vdi[t] = 1.0f - smp.any_depth(u, vs);
-            smp.any_color(u, vs, vc[t]);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            if (ok[t] && vdi[t] > cdi + g.tol * 0.5f) {
-                va[0] += vc[t][0] * 0.25f; va[1] += vc[t][1] * 0.25f; va[2] += vc[t][2] * 0.25f;
-                vw += 0.25f;
-            }
-        out[0] = va[0] / vw; out[1] = va[1] / vw; out[2] = va[2] / vw;
-        return;
-    }
-    smp.own_color(u, v, out);                                                         // :505
-}
 
 // push_pull_inpaint (:437-506)
 template <class S>
@@ -380,19 +166,6 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const DibrGeom& g, int 
     for (int k = 0; k < 3; ++k) outc[k] = g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED ? col[k] * alpha : col[k];
     outc[3] = alpha;
     return false;
-}
-
-template <int OUT_FMT>
-__device__ __forceinline__ void dibr_store(void* __restrict__ out_all, long o, int nch, const float c[4]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (OUT_FMT == D2S_FMT_U8_HWC) ((uint8_t*)out_all)[o + k] = (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(c[k], 0, 0);
-        else ((float*)out_all)[o + k] = c[k];
-    }
-    if (nch == 4) {
-        if (OUT_FMT == D2S_FMT_U8_HWC) ((uint8_t*)out_all)[o + 3] = (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(c[3] * 255.0f, 0, 0);
-        else ((float*)out_all)[o + 3] = c[3];
-    }
 }
 
 // General kernel: one thread = one output pixel of one eye, every tap a global gather.  (4 pixels per thread with packed dword

@@ -284,6 +284,28 @@ def make_sbs(rgb_c, depth, ipd_uv=0.064, depth_ratio=2.0, convergence=0.0, fill_
     return ops.make_sbs(rgb, depth, sp, _lib.FMT_F32_HWC).cpu().numpy()
 
 
+def composite_view(rgb, depth, display_mode, ipd_uv=0.064, depth_ratio=2.0, convergence=0.0, viewport=None):
+    """The viewer's other display modes -> HWC float32 numpy 0..255, like make_sbs: "Anaglyph", "Interleaved", "Interleaved-V"
+    (the reference's composite shaders, viewer.py:678-1197, with disocclusion in-painting) and "Depth Map" (its spectral preview,
+    viewer.py:633-675).  The parallax is viewer.depth_strength (0.1) * depth_ratio in uv units, as for make_sbs(inpaint=True).
+    viewport: (x, y, w, h) of the viewer's viewport in window pixels, y up -- the output is h x w, and x, y decide which eye an
+    interleaved row / column shows; None = the frame itself.  rgb may be None for "Depth Map"."""
+    if display_mode not in _lib.COMPOSITE:
+        raise ValueError(f"display_mode must be one of {list(_lib.COMPOSITE)}")
+    frames = None
+    if rgb is not None:
+        frames = torch.from_numpy(np.ascontiguousarray(rgb)) if isinstance(rgb, np.ndarray) else rgb
+        frames = frames.to(device=_device())
+        if frames.dim() == 3 and frames.shape[0] == 3 and frames.shape[-1] != 3:
+            frames = frames.permute(1, 2, 0)
+        if frames.dtype != torch.uint8:                                # viewer.py:2417: clamp(0,255).to(uint8)
+            frames = frames.clamp(0, 255).to(torch.uint8)
+        frames = frames.contiguous()
+    d = torch.from_numpy(depth) if isinstance(depth, np.ndarray) else depth
+    dp = ops.dibr_params(ipd_uv, depth_ratio, convergence, viewport=tuple(viewport) if viewport is not None else (0.0, 0.0, 0.0, 0.0))
+    return ops.dibr_composite(frames, d.to(device=_device()), dp, display_mode, out_u8=False).cpu().numpy()
+
+
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False):
     """Batched predict_depth + make_sbs: uint8 [B,H,W,3] (numpy or device tensor) -> device tensor
     [B,H',W',3] (uint8, or float32 when out_u8=False) in one stream-ordered native call."""

@@ -315,6 +315,42 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
     return out if batched else out[0]
 
 
+def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
+                   out_u8: bool = True) -> torch.Tensor:
+    """The viewer's composite display modes (reference viewer.py:633-1197): "Anaglyph" | "Interleaved" | "Interleaved-V" |
+    "Depth Map".  uint8 HWC frames [B,H,W,3] or [H,W,3] (None for "Depth Map") + full-resolution depth -> the program's viewport,
+    dp.viewport = (x, y, w, h) in window pixels, y up (zeros: the frame itself); dp.display_mode is not used (include/d2s.h)."""
+    if mode not in _lib.COMPOSITE:
+        raise ValueError(f"mode must be one of {list(_lib.COMPOSITE)}")
+    _need_cuda(depth, "depth")
+    d = depth.to(torch.float32).contiguous()
+    batched = d.dim() == 3
+    d = d if batched else d.unsqueeze(0)
+    if d.dim() != 3:
+        raise ValueError("dibr_composite: depth must be [B,H,W] or [H,W]")
+    B, H, W = d.shape
+    f = None
+    if frames is not None:
+        _need_cuda(frames, "frames")
+        if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() != (4 if batched else 3):
+            raise ValueError("dibr_composite: frames must be uint8 [B,H,W,3] or [H,W,3], batched like depth")
+        f = frames.contiguous() if batched else frames.contiguous().unsqueeze(0)
+        if tuple(f.shape[:3]) != (B, H, W):
+            raise ValueError(f"dibr_composite: depth must be full resolution {tuple(f.shape[:3])}, got {(B, H, W)}")
+        _same_device(f, d, "dibr_composite")
+    elif mode != "Depth Map":
+        raise ValueError(f"dibr_composite: {mode} needs the frames")
+    lib = _lib.load()
+    oh, ow = C.c_int(), C.c_int()
+    check(lib.d2s_dibr_composite_shape(H, W, C.byref(dp), _lib.COMPOSITE[mode], C.byref(oh), C.byref(ow)), "d2s_dibr_composite_shape")
+    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+    out = torch.empty((B, oh.value, ow.value, nch), dtype=torch.uint8 if out_u8 else torch.float32, device=d.device)
+    with _on(d.device) as st:
+        check(lib.d2s_dibr_composite(_ptr(f) if f is not None else None, _ptr(d), B, H, W, C.byref(dp), _lib.COMPOSITE[mode],
+                                     _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st), "d2s_dibr_composite")
+    return out if batched else out[0]
+
+
 _JPEG_WS: Dict[Tuple[int, int], torch.Tensor] = {}
 
 

@@ -279,6 +279,28 @@ int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* out_w);
 int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream);
 
+/* The viewer's other four `Display Mode`s (gui.py:1666, viewer.py:1340), each one program the reference runs over its letter-boxed
+ * viewport (viewer.py:2604-2662: u_eye_offset = +ipd_uv/2, u_depth_strength = 0.1 * depth_ratio, blending off):
+ *   ANAGLYPH       ANAGLYPH_FRAGMENT (viewer.py:678-832): both eyes per pixel, no depth shaping, hard disocclusion test
+ *                  (|d(-2px) - d(+2px)| > 0.08), out = (left.r, right.g, right.b), alpha = both eyes' 0.015-wide border bands;
+ *   INTERLEAVED    INTERLEAVED_FRAGMENT (viewer.py:835-1017): even window rows (gl_FragCoord.y) the left eye, odd rows the right;
+ *                  in-painting REPLACES the colour where smoothstep(0.06, 0.12, jump) > 0.001;
+ *   INTERLEAVED_V  VERTICAL_INTERLEAVED_FRAGMENT (viewer.py:1020-1197): the same by window column, push-pull swept the other way;
+ *   DEPTH_MAP      DEPTH_FRAGMENT (viewer.py:633-675): spectral_r_ultrafast(depth) (rgb 0..255 like the other modes), alpha 1.
+ * d2s_dibr_params is read as for d2s_dibr_warp except:
+ *   - viewport = (x, y, w, h) of the program's viewport in WINDOW pixels, y up -- it is also u_viewport.  The output is h x w; its
+ *     row r (0 = top) and column c are the fragment at gl_FragCoord = (x + c + 0.5, y + (h - 1 - r) + 0.5), so x and y decide which
+ *     eye an interleaved row / column shows.  x, y >= 0 and w, h > 0 must be whole numbers (glViewport takes integers); all zeros =
+ *     (0, 0, W, H).  w x h may differ from the source (a 1080p frame on a 2160-row interleaved panel: the taps filter bilinearly);
+ *   - display_mode is ignored.
+ * rgb may be NULL for DEPTH_MAP.  Output: three channels per pixel (four with alpha_mode == D2S_DIBR_ALPHA_RGBA) as
+ * D2S_FMT_U8_HWC (round-half-even) or D2S_FMT_F32_HWC (0..255), batch-major.  Every argument is checked before any HIP call.
+ * Pinned by tests/golden/composite.npz: the reference's four programs run off-screen (tests/golden/make_golden_composite.py). */
+enum { D2S_COMPOSITE_ANAGLYPH = 0, D2S_COMPOSITE_INTERLEAVED = 1, D2S_COMPOSITE_INTERLEAVED_V = 2, D2S_COMPOSITE_DEPTH_MAP = 3 };
+int d2s_dibr_composite_shape(int H, int W, const d2s_dibr_params* p, int composite, int* out_h, int* out_w);
+int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
+                       int composite, void* out, int out_fmt, void* stream);
+
 /* f3: the MJPEG sink of the Streamer modes.  Replaces `cv2.imencode('.jpg', bgr, [IMWRITE_JPEG_QUALITY, q])` on the
  * frame make_sbs returns (reference streamer.py:249-256, 285-291; quality = settings.yaml "Stream Quality",
  * utils.py:821): convertTo(CV_8U) (round-half-even, saturate) + baseline JPEG as libjpeg(-turbo) writes it with
