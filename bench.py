@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput bench of the hot path: stereo frames/s, 1080p, Depth-Anything-v2 ViT-B, Full-SBS.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 with WORLD_SIZE unset: bench.py re-launches itself as N ranks (one per GPU) under torch.distributed.run on
 127.0.0.1; launched BY torch.distributed.run (the driver's way) it reads RANK / LOCAL_RANK / WORLD_SIZE from the env.
@@ -11,20 +11,24 @@ resident in HBM.  Workload = BASELINE.json configs[1]: DA-v2 ViT-B bf16, 1920x10
 Resolution 518 (model input 294x518), seeded synthetic weights.  Frames shard across ranks with no data-path
 collective (weak scaling: per-GPU work fixed).
 
-Rank 0 prints ONE JSON line: the contract fields plus
+A plain run builds the engine, runs W untimed and K timed steps, writes --dump-outputs if given, and rank 0 prints ONE
+JSON line: the contract fields (metric, value, unit, ms_per_step, ..., rccl_ranks = the number of ranks an actual
+all-reduce counted).  --full then runs every other measurement, each in runs of its own, and adds
   roofline      -- the dominant kernel class, timed live with HIP events on the launch stream
                    (d2s_engine_profile) in a second pass over the same workload;
   kernels       -- the same numbers for every kernel class;
   roofline_warp -- the stereo-warp kernel against the HBM roofline;
   ingest_rank0  -- the other deployment SURVEY.md section 8(e) asks to report: rank 0 holds all frames, scatters uint8
-                   frames / gathers packed stereo frames point-to-point over RCCL (shard.scatter_frames / gather_outputs);
-  rccl_ranks    -- the number of ranks an actual all-reduce counted;
+                   frames / gathers packed stereo frames point-to-point over RCCL (shard.scatter_frames / gather_outputs)
+                   (--ingest rank0 makes this leg the headline, with or without --full);
   batched       -- (N=1 only) the same pipeline at --also-batch frames per step (throughput regime:
                    M = batch*778 tokens fills the chip), with its own roofline;
   parity_class  -- (N=1 only) the same step on the fp32 engine, the one that meets north_star's 1e-3 depth tolerance;
   cpu_baseline  -- the numpy oracle (a port of the reference's CPU path) on a bounded sample,
                    rank 0 at N=1 only: all host threads, and one thread (the reference ships torch.set_num_threads(1),
-                   depth.py:19).
+                   depth.py:19);
+  and the parity figures against the committed reference fixtures, the MJPEG sink, the f1 DIBR warp and BASELINE
+  configs 1, 3 and 4 (see rank_body).
 """
 from __future__ import annotations
 
@@ -396,6 +400,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1, help="frames per step per GPU (configs[1]: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other measurement too (profile pass and rooflines, batched sizes, parity "
+                         "figures, sink, DIBR, host boundary, CPU baseline, configs 1 / 3 / 4), shaped by --also-batch, --no-tile-fit, "
+                         "--profile-steps, --mixed, --sink-quality and the --no-* options.  Without it the run times the headline and "
+                         "nothing else")
     ap.add_argument("--also-batch", type=int, default=32, help="extra batched measurement at N=1 (0 = off)")
     ap.add_argument("--no-tile-fit", dest="tile_fit", action="store_false",
                     help="skip the extra batched measurement at the tile-fitting batch size (see tile_fit_batch)")
@@ -416,7 +425,8 @@ def parse_args(argv=None):
                          "{1280x720, 1920x1080, 2560x1440} -- one batched model pass, per-size pre-process and warp")
     ap.add_argument("--ingest", default="both", choices=["own", "rank0", "both"],
                     help="own: every rank generates its frames (headline value, no data-path collective); rank0: rank 0 holds all "
-                         "frames, RCCL point-to-point scatter / gather each step; both: headline = own, rank0 reported beside it")
+                         "frames, RCCL point-to-point scatter / gather each step; both: headline = own, rank0 reported beside it "
+                         "under --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-class", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the depth / warp parity leg against the committed reference fixtures (counter passes)")
@@ -517,6 +527,7 @@ def rank_body(args, engine_factory=None, device=None):
             weights = make_vda_weights(cfg, 0)
         else:
             weights = make_weights(cfg, 0)
+        # sized for the --full sub-runs whether or not they run: the headline steps run on the same engine either way
         eng = ops.Engine(cfg, weights, h, w, max_batch=max(B, B2, NM), precision=args.precision, device=local_rank, temporal=args.vda)
         sbs_params_, sbs_shape_ = ops.sbs_params, ops.sbs_shape
     default_wl = (args.model, args.precision, args.res, H, W, args.vda, args.resample) == ("vitb", "bf16", 518, 1080, 1920, False, "bilinear")
@@ -594,7 +605,7 @@ def rank_body(args, engine_factory=None, device=None):
             # before any later sub-run reuses the buffer
             result["dump_outputs"] = dump_outputs(args.dump_outputs, {"sbs_frames": step.out.cpu().numpy()}, args.steps - 1)
 
-    if rank == 0 and world == 1 and not fake and B == 1 and not args.vda and not args.no_profile and step is not None:
+    if args.full and rank == 0 and world == 1 and not fake and B == 1 and not args.vda and not args.no_profile and step is not None:
         # Two frames in flight (reported beside `value`, never in it): the reference's own main loop overlaps consecutive frames -- capture,
         # depth and warp run in separate threads with queues between them (main.py) -- while `value` above issues frame i + 1 only after
         # frame i on ONE stream, so the serial tail of a frame (~0.2 ms of small dependent launches on a mostly idle chip) overlaps with
@@ -621,7 +632,7 @@ def rank_body(args, engine_factory=None, device=None):
                                           "note": "two engines on two HIP streams, batch 1 per call, frames issued alternately; `value` (one stream, one frame at a time) is the headline"}
         eng_b.close()
 
-    if args.ingest in ("rank0", "both") and not args.vda:
+    if (args.ingest == "rank0" or args.ingest == "both" and args.full) and not args.vda:
         # SURVEY.md section 8(e), the other deployment: frames arrive on rank 0 (the capture host's GPU); every step rank 0
         # scatters uint8 frames point-to-point (RCCL send/recv over xGMI; xGMI has no switch, a root-centric scatter is
         # bounded by the root's egress), every rank runs the pipeline on its block, packed stereo frames are gathered back.
@@ -668,8 +679,6 @@ def rank_body(args, engine_factory=None, device=None):
             result["value"], result["ms_per_step"] = ing["value"], ing["ms_per_step"]
             result["config"]["parallelism"] = f"frame-sharded dp{world}, rank-0 ingest: point-to-point scatter / gather per step ({backend})"
         result["ingest_rank0"] = ing
-    if step is None:
-        step = make_step(B)
 
     if args.model != "vitb" or (H, W) != (1080, 1920):
         result["metric"] = f"stereo frames/sec @{W}x{H} DepthAnything-v2-{cfg.name}"
@@ -679,6 +688,18 @@ def rank_body(args, engine_factory=None, device=None):
         result["config"]["parallelism"] = f"{world} independent stream(s), stream s on rank s % {world} (shard.stream_owner); replicas only"
         args.no_cpu_baseline = True                      # the CPU leg times the DA-v2 oracle only
         args.no_parity_class = True
+
+    def finish():
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return result if rank == 0 else None
+
+    if not args.full:
+        eng.close()
+        return finish()
+    if step is None:
+        step = make_step(B)
 
     if rank == 0 and not args.no_profile:
         result.update(profile_pass(eng, step, args.profile_steps, B, args.precision, sync, default_wl))
@@ -1031,10 +1052,7 @@ def rank_body(args, engine_factory=None, device=None):
             e4.close()
         result["config4_vda"] = dict(rows4, workload="VideoDepthAnything streaming forward (32-frame window) + post-process + Full-SBS warp through d2s_pipeline, "
                                                       "1920x1080 uint8 noise frames, one stream on this GPU, bf16 engine, EMA off")
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return result if rank == 0 else None
+    return finish()
 
 
 def main():

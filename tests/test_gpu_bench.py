@@ -39,7 +39,7 @@ def _run(args, env_extra=None, timeout=900, tmp=None):
 
 
 def test_bench_contract_n1():
-    res = _run(["--steps", "6", "--warmup", "2", "--profile-steps", "2", "--also-batch", "2", "--model", "vits", "--no-cpu-baseline"])
+    res = _run(["--full", "--steps", "6", "--warmup", "2", "--profile-steps", "2", "--also-batch", "2", "--model", "vits", "--no-cpu-baseline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "roofline_warp", "parity_class", "batched", "ingest_rank0", "rccl_ranks"):
         assert k in res, k
@@ -61,8 +61,17 @@ def test_bench_contract_n1():
     assert pc["depth_max_vs_ref"] <= 1e-3 and res["parity"]["bf16x3"]["depth_l1_vs_ref"] <= 1e-4
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """The driver's plain command on the default workload: the headline and nothing after it (every other measurement is --full's)."""
+    res = _run(["--gpus", "1", "--steps", "6", "--warmup", "2"])
+    assert set(res) - {"_compact"} == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                       "vs_baseline", "dtype", "data", "rccl_ranks", "hip_force_dev_kernarg", "config"}
+    assert res["metric"] == "stereo frames/sec @1080p DepthAnything-v2-ViT-B" and res["dtype"] == "bf16" and res["steps"] == 6
+    assert abs(res["value"] - 1e3 / res["ms_per_step"]) < 1e-6 * res["value"]
+
+
 def test_bench_spawns_its_own_ranks():
-    res = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--model", "vits", "--no-profile", "--no-cpu-baseline"],
+    res = _run(["--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--model", "vits", "--no-profile", "--no-cpu-baseline"],
                {"D2S_DIST_BACKEND": "gloo"})
     assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2
     assert res["ingest_rank0"]["frames_per_step"] == 2 and res["ingest_rank0"]["value"] > 0
@@ -76,7 +85,7 @@ def test_bench_two_ranks_over_rccl():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip(f"{torch.cuda.device_count()} ROCm device(s) visible: two RCCL ranks need two (covered over gloo above)")
-    res = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--model", "vits", "--no-profile", "--no-cpu-baseline"])
+    res = _run(["--full", "--gpus", "2", "--steps", "6", "--warmup", "2", "--model", "vits", "--no-profile", "--no-cpu-baseline"])
     assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2
     assert res["ingest_rank0"]["frames_per_step"] == 2 and res["ingest_rank0"]["value"] > 0
     assert abs(res["value"] - 2 * 1e3 / res["ms_per_step"]) < 1e-6 * res["value"]

@@ -277,7 +277,7 @@ def _bench_worker(rank, world, port, q):
                       D2S_DIST_BACKEND="gloo")
     import bench
     args = bench.parse_args(["--gpus", str(world), "--steps", "6", "--warmup", "2", "--batch", "3", "--height", "6", "--width", "8",
-                             "--no-profile", "--no-cpu-baseline", "--sink-quality", "0", "--also-batch", "0"])
+                             "--full", "--no-profile", "--no-cpu-baseline", "--sink-quality", "0", "--also-batch", "0"])
     res = bench.rank_body(args, engine_factory=_StandInEngine, device=torch.device("cpu"))
     if rank == 0:
         q.put(res)
@@ -313,6 +313,31 @@ def test_bench_refuses_mismatched_world(monkeypatch):
     args = bench.parse_args(["--gpus", "4"])
     with pytest.raises(SystemExit):
         bench.rank_body(args, engine_factory=_StandInEngine, device=torch.device("cpu"))
+
+
+def test_bench_plain_run_is_the_headline_alone(monkeypatch):
+    """Without --full bench.py runs the W + K headline steps and nothing else, whatever the other options say (the default
+    --ingest both adds its rank-0 leg, the default --profile-steps its profile pass, only under --full)."""
+    sys.path.insert(0, REPO)
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "D2S_DIST_BACKEND"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    engines = []
+
+    def factory(max_batch):
+        engines.append(_StandInEngine(max_batch))
+        return engines[-1]
+
+    argv = ["--steps", "7", "--warmup", "2", "--batch", "3", "--height", "6", "--width", "8"]
+    res = bench.rank_body(bench.parse_args(argv), engine_factory=factory, device=torch.device("cpu"))
+    assert len(engines) == 1 and engines[0].calls == 2 + 7
+    assert set(res) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                        "dtype", "data", "rccl_ranks", "hip_force_dev_kernarg", "config"}
+    assert abs(res["value"] - 7 * 3 / (res["ms_per_step"] * 7e-3)) < 1e-6 * res["value"]
+    # (the stand-in engine has no per-kernel profile: --no-profile)
+    res = bench.rank_body(bench.parse_args(argv + ["--full", "--no-profile"]), engine_factory=factory, device=torch.device("cpu"))
+    assert "ingest_rank0" in res and engines[1].calls > 2 + 7
 
 
 def test_bench_dump_outputs(monkeypatch, tmp_path):
