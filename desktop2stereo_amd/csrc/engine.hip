@@ -118,7 +118,6 @@ struct d2s_engine {
     int last_batch = 0;
     // D2S_PREC_FP8 (BASELINE config 3): encoder linears on e4m3 operands once calibrated
     bool fp8 = false, fp8_ready = false, calib = false;
-    bool fp8_mlp = false;             // D2S_PREC_FP8_MLP: e4m3 on FC1 / FC2 only (60 % of the encoder FLOPs), QKV / proj stay bf16
     bool lnf = false;                 // LayerNorm folded into the producing / consuming linears (bf16, not fp8)
     bool no_lnfuse = false;           // D2S_NO_LNFUSE=1 at creation: the LayerNorms stay kernels (e4m3 engines too)
     bool attn_prescaled = false;      // softmax scale folded into W_q / b_q (bf16 and fp8 engines)
@@ -143,6 +142,15 @@ int dev_alloc(d2s_engine* e, void** p, size_t bytes, bool zero = false) {
     if (zero) D2S_HIP(hipMemset(*p, 0, bytes));
     return D2S_OK;
 }
+
+int dev_upload(d2s_engine* e, void** p, const void* host, size_t bytes) {
+    int rc = dev_alloc(e, p, bytes);
+    if (rc) return rc;
+    D2S_HIP(hipMemcpy(*p, host, bytes, hipMemcpyHostToDevice));
+    return D2S_OK;
+}
+
+#define RC(x) do { int _rc = (x); if (_rc != D2S_OK) return _rc; } while (0)
 
 enum { PC_GEMM = 0, PC_CONV, PC_ATTN, PC_LN, PC_ELT, PC_PRE, PC_POST, PC_WARP, PC_N };
 const char* const PC_NAMES[PC_N] = {"gemm_linear", "gemm_conv3x3", "attention", "layernorm", "elementwise", "preprocess",
@@ -174,39 +182,21 @@ int upload_f32(d2s_engine* e, const std::string& name, size_t n, float** out) {
     const HostT* t = find(e, name);
     if (!t) return D2S_E_MISSING;
     if (t->data.size() != n) { set_error("weight " + name + ": wrong element count"); return D2S_E_MISSING; }
-    int rc = dev_alloc(e, (void**)out, n * sizeof(float));
-    if (rc) return rc;
-    D2S_HIP(hipMemcpy(*out, t->data.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    return D2S_OK;
+    return dev_upload(e, (void**)out, t->data.data(), n * sizeof(float));
 }
 
-// pack a logical [N][K] float matrix (given by accessor) into device [Npad][Kpad] T
-template <typename F>
-int pack_matrix(d2s_engine* e, int N, int K, F at, const float* bias_host, PackedW& out) {
-    const int Kp = gemm_kpad(K, e->wprec);
-    const std::vector<uint8_t> buf = pack_rows_host(e->wprec, N, K, at);     // (linear_site.h)
-    int rc = dev_alloc(e, &out.w, buf.size());
-    if (rc) return rc;
-    D2S_HIP(hipMemcpy(out.w, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    out.N = N; out.K = K; out.Kpad = Kp;
+// a prepared linear (linear_site.h prepare_linear) on the device: W and its bias (none when the image has none); a folded one's colsum
+// to *csum, an e4m3 one's row scales to *sw
+int upload_linear(d2s_engine* e, LinearImage im, PackedW& out, float** csum = nullptr, std::vector<float>* sw = nullptr) {
+    RC(dev_upload(e, &out.w, im.w.data(), im.w.size()));
+    out.N = im.N; out.K = im.K; out.Kpad = im.Kpad;
     out.bias = nullptr;
-    if (bias_host) {
-        rc = dev_alloc(e, (void**)&out.bias, (size_t)N * sizeof(float));
-        if (rc) return rc;
-        D2S_HIP(hipMemcpy(out.bias, bias_host, (size_t)N * sizeof(float), hipMemcpyHostToDevice));
+    if (!im.bias.empty()) RC(dev_upload(e, (void**)&out.bias, im.bias.data(), im.bias.size() * sizeof(float)));
+    if (csum) {
+        D2S_REQUIRE(!im.csum.empty(), "upload_linear: a colsum was asked for, but no LayerNorm is folded into this linear");
+        RC(dev_upload(e, (void**)csum, im.csum.data(), im.csum.size() * sizeof(float)));
     }
-    return D2S_OK;
-}
-
-// e4m3 copy of a logical [N][K] matrix: row n is divided by s_w[n] = max|row| / 448 and rounded to e4m3 (RNE)
-template <typename F>
-int pack_matrix_fp8(d2s_engine* e, int N, int K, F at, const float* bias_dev, PackedW& out, std::vector<float>& sw) {
-    const int Kp = gemm_kpad(K, D2S_PREC_FP8_OPERANDS);
-    const std::vector<uint8_t> buf = pack_rows_fp8_host(N, K, at, sw);      // (linear_site.h)
-    int rc = dev_alloc(e, &out.w, buf.size());
-    if (rc) return rc;
-    D2S_HIP(hipMemcpy(out.w, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    out.N = N; out.K = K; out.Kpad = Kp; out.bias = const_cast<float*>(bias_dev);   // shares the bf16 copy's bias vector
+    if (sw) *sw = std::move(im.sw);
     return D2S_OK;
 }
 
@@ -217,7 +207,7 @@ int pack_linear(d2s_engine* e, const std::string& wname, const std::string& bnam
     const float* b = nullptr;
     if (!bname.empty()) { const HostT* bt = find(e, bname); if (!bt || bt->data.size() != (size_t)N) { set_error("bad bias " + bname); return D2S_E_MISSING; } b = bt->data.data(); }
     const float* p = w->data.data();
-    return pack_matrix(e, N, K, [&](int n, int k) { return p[(size_t)n * K + k]; }, b, out);
+    return upload_linear(e, prepare_linear(e->wprec, N, K, [&](int n, int k) { return p[(size_t)n * K + k]; }, b), out);
 }
 
 // Conv2d 3x3 weight [Co,Ci,3,3] -> [Co][(ky*3+kx)*Ci + ci]
@@ -228,7 +218,7 @@ int pack_conv3(d2s_engine* e, const std::string& wname, const std::string& bname
     const float* b = nullptr;
     if (!bname.empty()) { const HostT* bt = find(e, bname); if (!bt || bt->data.size() != (size_t)Co) { set_error("bad bias " + bname); return D2S_E_MISSING; } b = bt->data.data(); }
     const float* p = w->data.data();
-    return pack_matrix(e, Co, 9 * Ci, [&](int n, int k) { return p[conv3_weight_index(n, k, Ci)]; }, b, out);
+    return upload_linear(e, prepare_linear(e->wprec, Co, 9 * Ci, [&](int n, int k) { return p[conv3_weight_index(n, k, Ci)]; }, b), out);
 }
 
 // ConvTranspose2d k==s weight [Ci,Co,k,k] -> rows n = (ky*k+kx)*Co + co, K = Ci; bias expanded
@@ -241,7 +231,7 @@ int pack_convT(d2s_engine* e, const std::string& wname, const std::string& bname
     int N = ks * ks * C;
     std::vector<float> bias(N);
     for (int n = 0; n < N; ++n) bias[n] = bt->data[n % C];
-    return pack_matrix(e, N, C, [&](int n, int k) { return p[convT_weight_index(n, k, C, ks)]; }, bias.data(), out);
+    return upload_linear(e, prepare_linear(e->wprec, N, C, [&](int n, int k) { return p[convT_weight_index(n, k, C, ks)]; }, bias.data()), out);
 }
 
 // ---- bicubic (align_corners=False, A=-0.75) resample of the position table, float32 like torch ----
@@ -311,8 +301,6 @@ int gemm8(d2s_engine* e, const GemmA& a, const PackedW& w, int M, const GemmEpi&
     return D2S_OK;
 }
 
-#define RC(x) do { int _rc = (x); if (_rc != D2S_OK) return _rc; } while (0)
-
 // 3x3 conv (pad 1) as implicit GEMM over NHWC
 int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int stride, int relu_in, const PackedW& w,
           void* out, int act, const void* res1, const void* res2, hipStream_t st) {
@@ -335,7 +323,7 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st,
     // store of a frame's k' | v' rows happens inside the attention kernel (the lanes that read the oldest slot's segment overwrite it
     // once both of their passes over it are done); (iii) ff2's epilogue leaves the bf16 copy proj_out reads (no cast kernel).
     // 18 -> 11 launches per module.
-    const bool fold = e->tm_fold && prec == D2S_PREC_BF16 && e->wprec != D2S_PREC_BF16X3;
+    const bool fold = e->tm_fold;
     int slots = 0;
     auto producer = [&](GemmEpi& ep) { if (fold) epi_ln_producer(ep, e->tm_a, e->tm_stats, &slots); };
     auto consumer = [&](GemmEpi& ep, const float* csum) { epi_ln_consumer(ep, e->tm_stats, slots, csum, 1e-5f, C); };
@@ -445,6 +433,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     const d2s_model_desc& d = e->d;
     const int D = d.hidden, N = e->N, P = e->P, M = B * N, Mp = B * P, prec = e->prec;
     const int F = d.fusion;
+    const PrecRules pr = prec_rules(d.precision);
     const bool use_side = e->overlap && e->side != nullptr && !e->prof_on;   // per-kernel timing passes run un-overlapped
     if (e->fp8 && !e->fp8_ready && !e->calib) {
         set_error("D2S_PREC_FP8 engine: activation scales are not set, call d2s_engine_calibrate first");
@@ -463,7 +452,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     const bool f8 = e->fp8 && !e->calib;
     // D2S_PREC_FP8_MLP (round 5): only FC1 / FC2 take e4m3 operands; LN-1 output / attention output stay bf16 and QKV / proj run the bf16
     // kernels.  f8a = "the attention-side linears are e4m3 too" (the all-four scheme)
-    const bool f8a = f8 && !e->fp8_mlp;
+    const bool f8a = f8 && pr.e4m3_attn;
     // bf16x3 engines: the A operands of the four encoder linears are written PRE-SPLIT (bf16 hi | lo units, common.h) by their
     // producers -- LayerNorm, attention, the GELU epilogue -- so that they travel by LDS-DMA like the bf16 engine's; every other
     // GEMM / conv reads fp32 activations and splits them between its staging registers and LDS
@@ -479,15 +468,16 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     // it too, i.e. from gemm_pp_min_tiles() tiles of 256 x 256 over [M, D]: the 24 LayerNorm launches of the batched regime (0.66 ms of
     // a 9.8 ms step at batch 32) are gone as well.  In between (QKV / FC1 on the ping-pong kernel, proj / FC2 not yet) nothing folds.
     static EnvInt lnf_pp{"D2S_LNF_PP", 1};
-    const bool pp_fold = lnf_pp.get() && e->lnf && !e->fp8 && !x3 && prec == D2S_PREC_BF16 && !e->calib && !e->taps && D % 256 == 0 && D <= 1024 &&
+    // (the ping-pong kernel folds LayerNorm on bf16 operands only: pp_supported, gemm_pp.hip)
+    const bool pp_fold = lnf_pp.get() && e->lnf && e->wprec == D2S_PREC_BF16 && !e->calib && !e->taps && D % 256 == 0 && D <= 1024 &&
                          gemm_pp_min_tiles() > 0 && (long)cdiv(M, 256) * (D / 256) >= gemm_pp_min_tiles();
-    const bool lnf = (((e->lnf && !e->fp8) || (f8 && !e->no_lnfuse)) && !e->calib && (prec == D2S_PREC_BF16 || x3) && B <= (x3 ? 8 : 3)) || pp_fold;   // (bf16x3: no ping-pong kernel to give way to)
+    const bool lnf = (pr.ln_folds(D2S_LIN_FC1) && !e->no_lnfuse && !e->calib && B <= (x3 ? 8 : 3)) || pp_fold;   // (bf16x3: no ping-pong kernel to give way to)
     int ln_slots = 0;
     // batch 1, bf16: the four tap LayerNorms fold into the reassemble projections the same way (the statistics and the raw
     // residual of a tap layer are still in lnbuf / lnstats when its projection runs; the main stream waits for that launch
     // -- ev_ln -- before the next layer's projection GEMM overwrites them)
     // round 4: also in the batched regime where the ping-pong kernel produces the statistics (3-4 partials per row)
-    const bool tap_fold = lnf && !f8 && !x3 && e->lnf && (B == 1 || pp_fold);           // (bf16x3: the tap LayerNorms stay kernels)
+    const bool tap_fold = lnf && pr.ln_folds(D2S_LIN_NECK_PROJ) && (B == 1 || pp_fold);
     bool tap_folded[4] = {false, false, false, false};
     int pending_ln = -1;
     for (int l = 0; l < d.layers; ++l) {
@@ -496,7 +486,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         float* am = e->calib ? e->amax + (size_t)l * NSITE : nullptr;
         // lnf: the previous layer's FC2 epilogue left the raw bf16 residual in lnbuf and the row statistics in lnstats;
         // LN1 then happens inside the QKV linear (layer 0 has no such producer and runs the LN kernel)
-        const bool ln1_folded = lnf && l > 0 && ln_slots <= 16 && !(f8 && !f8a);     // (MLP-only e4m3: LN-1 stays a kernel, bf16 out)
+        const bool ln1_folded = lnf && l > 0 && ln_slots <= 16 && pr.ln_folds(D2S_LIN_QKV);
         if (!ln1_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, ly.ln1g, ly.ln1b, e->lnbuf, M, D, d.ln_eps, 0, 0, 0, st, f8a ? 1.0f / sa[0] : 0.f, x3));
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 0, st));
         {
@@ -528,7 +518,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (am) RC(launch_amax(prec, e->mlp, (long)M * d.mlp, am + 3, st));
         {
             GemmEpi ep = epi_residual(e->resid, D, ly.fc2.bias, ly.ls2);
-            if (lnf && (l + 1 < d.layers || tap_fold) && !(f8 && !f8a)) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[5] : 0.f);
+            if (lnf && (l + 1 < d.layers || tap_fold) && pr.ln_folds(D2S_LIN_FC2)) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[5] : 0.f);
             if (f8) { ep.deq = ly.deq[3]; RC(gemm8(e, plainA(e->mlp, d.mlp), ly.w8[3], M, ep, st)); }
             else RC(gemm(e, splitA(e->mlp, d.mlp, x3), ly.fc2, M, ep, st));
         }
@@ -653,14 +643,13 @@ extern "C" int d2s_engine_create(const d2s_model_desc* desc, int device_id, d2s_
     D2S_ON_DEVICE(device_id);
     d2s_engine* e = new d2s_engine();
     e->d = *desc; e->device = device_id;
-    e->fp8 = desc->precision == D2S_PREC_FP8 || desc->precision == D2S_PREC_FP8_MLP;
-    e->fp8_mlp = desc->precision == D2S_PREC_FP8_MLP;
-    // LayerNorm fusion: bf16 and bf16x3 engines (not the plain fp32 engine; the e4m3 path quantises the LN output itself)
+    const PrecRules pr = prec_rules(desc->precision);
+    e->fp8 = pr.e4m3;
+    // LayerNorm fusion into the encoder's own bf16 / bf16x3 linears (the e4m3 engines fold into their e4m3 copies)
     e->no_lnfuse = env_int("D2S_NO_LNFUSE", 0) != 0;
-    e->lnf = (desc->precision == D2S_PREC_BF16 || desc->precision == D2S_PREC_BF16X3) && !e->no_lnfuse;
-    // (the e4m3 engines are bf16 engines whose encoder linears switch to e4m3 operands)
-    e->prec = e->fp8 ? D2S_PREC_BF16 : (desc->precision == D2S_PREC_BF16X3 ? D2S_PREC_FP32 : desc->precision);
-    e->wprec = desc->precision == D2S_PREC_BF16X3 ? D2S_PREC_BF16X3 : e->prec;      // split-precision GEMM operands on the fp32 engine
+    e->lnf = pr.ln_folds(D2S_LIN_FC1) && !pr.e4m3 && !e->no_lnfuse;
+    e->prec = pr.act;
+    e->wprec = pr.w;
     e->attn_prescaled = e->prec == D2S_PREC_BF16;
     e->taps = env_int("D2S_TAPS", 0) != 0;
     *out = e;
@@ -727,55 +716,35 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
             for (int i = 0; i < D; ++i) bias[i] *= ATTN_SCALE_LOG2E;
         }
         const float* ws[3] = {e->attn_prescaled ? wq_scaled.data() : wq->data.data(), wk->data.data(), wv->data.data()};
-        RC(pack_matrix(e, 3 * D, D, [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; }, bias.data(), ly.qkv));
+        auto qkv_at = [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; };
+        RC(upload_linear(e, prepare_linear(e->wprec, 3 * D, D, qkv_at, bias.data()), ly.qkv));
         RC(pack_linear(e, p + "attention.output.dense.weight", p + "attention.output.dense.bias", D, D, ly.proj));
         RC(pack_linear(e, p + "mlp.fc1.weight", p + "mlp.fc1.bias", d.mlp, D, ly.fc1));
         RC(pack_linear(e, p + "mlp.fc2.weight", p + "mlp.fc2.bias", D, d.mlp, ly.fc2));
-        if (e->lnf) {
-            // LN(x) W^T + b  =  rstd * (x W'^T - mean * colsum(W')) + (b + W beta),  W' = W diag(gamma)
-            auto fold = [&](const HostT* g, const HostT* bt, int Nn, auto at, const float* bias, PackedW& out, float** csum) -> int {
-                std::vector<float> b2(Nn), cs(Nn);
-                for (int n = 0; n < Nn; ++n) ln_fold_row(e->wprec, D, g->data.data(), bt->data.data(), at, n, bias[n], b2[n], cs[n]);
-                int rc = pack_matrix(e, Nn, D, [&](int n, int k) { return g->data[k] * at(n, k); }, b2.data(), out);
-                if (rc) return rc;
-                rc = dev_alloc(e, (void**)csum, (size_t)Nn * sizeof(float));
-                if (rc) return rc;
-                D2S_HIP(hipMemcpy(*csum, cs.data(), (size_t)Nn * sizeof(float), hipMemcpyHostToDevice));
-                return D2S_OK;
-            };
-            const HostT *g1 = find(e, p + "norm1.weight"), *b1 = find(e, p + "norm1.bias"), *g2 = find(e, p + "norm2.weight"), *b2 = find(e, p + "norm2.bias");
-            const HostT *w1t = find(e, p + "mlp.fc1.weight"), *b1t = find(e, p + "mlp.fc1.bias");
-            if (!g1 || !b1 || !g2 || !b2 || !w1t || !b1t) return D2S_E_MISSING;
-            RC(fold(g1, b1, 3 * D, [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; }, bias.data(), ly.qkv_ln, &ly.csum_qkv));
-            const float* w1p = w1t->data.data();
-            RC(fold(g2, b2, d.mlp, [&](int n, int k) { return w1p[(size_t)n * D + k]; }, b1t->data.data(), ly.fc1_ln, &ly.csum_fc1));
+        const HostT *g1 = find(e, p + "norm1.weight"), *bn1 = find(e, p + "norm1.bias"), *g2 = find(e, p + "norm2.weight"), *bn2 = find(e, p + "norm2.bias");
+        const HostT *wo = find(e, p + "attention.output.dense.weight"), *w1 = find(e, p + "mlp.fc1.weight"), *b1 = find(e, p + "mlp.fc1.bias"),
+                    *w2 = find(e, p + "mlp.fc2.weight");
+        if (!g1 || !bn1 || !g2 || !bn2 || !wo || !w1 || !b1 || !w2) return D2S_E_MISSING;
+        auto fc1_at = [&](int n, int k) { return w1->data[(size_t)n * D + k]; };
+        if (e->lnf) {                                   // LN1 / LN2 folded into QKV / FC1 (see Layer)
+            RC(upload_linear(e, prepare_linear(e->wprec, 3 * D, D, qkv_at, bias.data(), g1->data.data(), bn1->data.data()), ly.qkv_ln, &ly.csum_qkv));
+            RC(upload_linear(e, prepare_linear(e->wprec, d.mlp, D, fc1_at, b1->data.data(), g2->data.data(), bn2->data.data()), ly.fc1_ln, &ly.csum_fc1));
         }
-        if (e->fp8) {
-            const float* wo = find(e, p + "attention.output.dense.weight")->data.data();
-            const float* w1 = find(e, p + "mlp.fc1.weight")->data.data();
-            const float* w2 = find(e, p + "mlp.fc2.weight")->data.data();
-            RC(pack_matrix_fp8(e, 3 * D, D, [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; }, ly.qkv.bias, ly.w8[0], ly.sw[0]));
-            RC(pack_matrix_fp8(e, D, D, [&](int n, int k) { return wo[(size_t)n * D + k]; }, ly.proj.bias, ly.w8[1], ly.sw[1]));
-            RC(pack_matrix_fp8(e, d.mlp, D, [&](int n, int k) { return w1[(size_t)n * D + k]; }, ly.fc1.bias, ly.w8[2], ly.sw[2]));
-            RC(pack_matrix_fp8(e, D, d.mlp, [&](int n, int k) { return w2[(size_t)n * d.mlp + k]; }, ly.fc2.bias, ly.w8[3], ly.sw[3]));
-            for (int i = 0; i < 4; ++i) RC(dev_alloc(e, (void**)&ly.deq[i], (size_t)ly.w8[i].N * sizeof(float), true));
-            // LN-folded e4m3 copies of QKV / FC1 (see Layer): W' = W diag(gamma), bias' = b + W beta, csum over the de-quantised W'
-            auto fold8 = [&](const HostT* g, const HostT* bt, int Nn, auto at, const float* bias, int slot) -> int {
-                RC(pack_matrix_fp8(e, Nn, D, [&](int n, int k) { return g->data[k] * at(n, k); }, nullptr, ly.w8_ln[slot], ly.sw_ln[slot]));
-                std::vector<float> b2(Nn), cs(Nn);
-                for (int n = 0; n < Nn; ++n) ln_fold_row_fp8(D, g->data.data(), bt->data.data(), at, n, bias[n], ly.sw_ln[slot][n], b2[n], cs[n]);
-                RC(dev_alloc(e, (void**)&ly.w8_ln[slot].bias, (size_t)Nn * sizeof(float)));
-                D2S_HIP(hipMemcpy(ly.w8_ln[slot].bias, b2.data(), (size_t)Nn * sizeof(float), hipMemcpyHostToDevice));
-                RC(dev_alloc(e, (void**)&ly.csum8[slot], (size_t)Nn * sizeof(float)));
-                D2S_HIP(hipMemcpy(ly.csum8[slot], cs.data(), (size_t)Nn * sizeof(float), hipMemcpyHostToDevice));
-                RC(dev_alloc(e, (void**)&ly.deq_ln[slot], (size_t)Nn * sizeof(float), true));
-                return D2S_OK;
-            };
-            const HostT *g1 = find(e, p + "norm1.weight"), *bn1 = find(e, p + "norm1.bias"), *g2 = find(e, p + "norm2.weight"), *bn2 = find(e, p + "norm2.bias");
-            const HostT* b1t = find(e, p + "mlp.fc1.bias");
-            if (!g1 || !bn1 || !g2 || !bn2 || !b1t) return D2S_E_MISSING;
-            RC(fold8(g1, bn1, 3 * D, [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; }, bias.data(), 0));
-            RC(fold8(g2, bn2, d.mlp, [&](int n, int k) { return w1[(size_t)n * D + k]; }, b1t->data.data(), 1));
+        if (e->fp8) {                                   // the e4m3 copies, plain and LN-folded (see Layer)
+            const int e8 = D2S_PREC_FP8_OPERANDS;
+            RC(upload_linear(e, prepare_linear(e8, 3 * D, D, qkv_at, nullptr), ly.w8[0], nullptr, &ly.sw[0]));
+            RC(upload_linear(e, prepare_linear(e8, D, D, [&](int n, int k) { return wo->data[(size_t)n * D + k]; }, nullptr), ly.w8[1], nullptr, &ly.sw[1]));
+            RC(upload_linear(e, prepare_linear(e8, d.mlp, D, fc1_at, nullptr), ly.w8[2], nullptr, &ly.sw[2]));
+            RC(upload_linear(e, prepare_linear(e8, D, d.mlp, [&](int n, int k) { return w2->data[(size_t)n * d.mlp + k]; }, nullptr), ly.w8[3], nullptr, &ly.sw[3]));
+            const PackedW* w16[4] = {&ly.qkv, &ly.proj, &ly.fc1, &ly.fc2};
+            for (int i = 0; i < 4; ++i) {
+                ly.w8[i].bias = w16[i]->bias;                                      // shares the bf16 copy's bias vector
+                RC(dev_alloc(e, (void**)&ly.deq[i], (size_t)ly.w8[i].N * sizeof(float), true));
+            }
+            RC(upload_linear(e, prepare_linear(e8, 3 * D, D, qkv_at, bias.data(), g1->data.data(), bn1->data.data()), ly.w8_ln[0], &ly.csum8[0], &ly.sw_ln[0]));
+            RC(dev_alloc(e, (void**)&ly.deq_ln[0], (size_t)3 * D * sizeof(float), true));
+            RC(upload_linear(e, prepare_linear(e8, d.mlp, D, fc1_at, b1->data.data(), g2->data.data(), bn2->data.data()), ly.w8_ln[1], &ly.csum8[1], &ly.sw_ln[1]));
+            RC(dev_alloc(e, (void**)&ly.deq_ln[1], (size_t)d.mlp * sizeof(float), true));
         }
     }
     if (e->fp8) {
@@ -800,14 +769,8 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
             std::string p = "neck.reassemble_stage.layers." + std::to_string(i) + ".projection.";
             const HostT *wt = find(e, p + "weight"), *bt = find(e, p + "bias");
             if (!wt || !bt) return D2S_E_MISSING;
-            const int c = d.neck[i];
-            const float* wp = wt->data.data();
-            std::vector<float> b2(c), cs(c);
-            auto at = [&](int n, int k) { return wp[(size_t)n * D + k]; };
-            for (int n = 0; n < c; ++n) ln_fold_row(D2S_PREC_BF16, D, gf->data.data(), bf->data.data(), at, n, bt->data[n], b2[n], cs[n]);     // (bf16 engines only: tap_fold)
-            RC(pack_matrix(e, c, D, [&](int n, int k) { return gf->data[k] * wp[(size_t)n * D + k]; }, b2.data(), e->re[i].proj_ln));
-            RC(dev_alloc(e, (void**)&e->re[i].csum, (size_t)c * sizeof(float)));
-            D2S_HIP(hipMemcpy(e->re[i].csum, cs.data(), (size_t)c * sizeof(float), hipMemcpyHostToDevice));
+            RC(upload_linear(e, prepare_linear(e->wprec, d.neck[i], D, [&](int n, int k) { return wt->data[(size_t)n * D + k]; }, bt->data.data(),
+                                               gf->data.data(), bf->data.data()), e->re[i].proj_ln, &e->re[i].csum));
         }
     }
     for (int i = 0; i < 4; ++i) {
@@ -862,18 +825,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
         const int tC[4] = {d.neck[2], d.neck[3], F, F};
         const int tS[4] = {e->fH[2] * e->fW[2], e->fH[3] * e->fW[3], e->fH[2] * e->fW[2], e->fH[1] * e->fW[1]};
         size_t sc_max = 0, max_sites = 0;
-        e->tm_fold = e->prec == D2S_PREC_BF16 && e->wprec != D2S_PREC_BF16X3 && env_int("D2S_VDA_FUSE", 1) != 0;
-        // LN(x) W^T + b  =  rstd * (x W'^T - mean * colsum(W')) + (b + W beta),  W' = W diag(gamma): colsum over the bf16-rounded W'
-        auto fold_ln = [&](const float* g, const float* bt, int Nn, int K, auto at, const float* bias, PackedW& out, float** csum) -> int {
-            std::vector<float> b2(Nn), cs(Nn);
-            for (int n = 0; n < Nn; ++n) ln_fold_row(D2S_PREC_BF16, K, g, bt, at, n, bias ? bias[n] : 0.0, b2[n], cs[n]);     // (bf16 engines only: tm_fold)
-            int rc = pack_matrix(e, Nn, K, [&](int n, int k) { return g[k] * at(n, k); }, b2.data(), out);
-            if (rc) return rc;
-            rc = dev_alloc(e, (void**)csum, (size_t)Nn * sizeof(float));
-            if (rc) return rc;
-            D2S_HIP(hipMemcpy(*csum, cs.data(), (size_t)Nn * sizeof(float), hipMemcpyHostToDevice));
-            return D2S_OK;
-        };
+        e->tm_fold = prec_rules(d.precision).ln_folds(D2S_LIN_TM_KVQ) && env_int("D2S_VDA_FUSE", 1) != 0;
         for (int m = 0; m < 4; ++m) {
             d2s_engine::TMod& t = e->tm[m];
             t.C = tC[m]; t.sites = tS[m];
@@ -900,7 +852,8 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                 if (!wq || !wk || !wv) return D2S_E_MISSING;
                 for (const HostT* w3 : {wq, wk, wv}) if (w3->data.size() != (size_t)C * C) { set_error("to_q/to_k/to_v: wrong shape"); return D2S_E_MISSING; }
                 const float* kvq[3] = {wk->data.data(), wv->data.data(), wq->data.data()};      // fused rows: k | v | q (no biases)
-                RC(pack_matrix(e, 3 * C, C, [&](int n, int k) { return kvq[n / C][(size_t)(n % C) * C + k]; }, nullptr, t.kvq[a]));
+                auto kvq_at = [&](int n, int k) { return kvq[n / C][(size_t)(n % C) * C + k]; };
+                RC(upload_linear(e, prepare_linear(e->wprec, 3 * C, C, kvq_at, nullptr), t.kvq[a]));
                 // W (x + pe_j) = W x + W pe_j: the positional share of every window position, float32
                 std::vector<float> pt((size_t)32 * 3 * C);
                 for (int j = 0; j < 32; ++j)
@@ -917,8 +870,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                 if (e->tm_fold) {
                     const HostT *g = find(e, b + "norms." + std::to_string(a) + ".weight"), *bt = find(e, b + "norms." + std::to_string(a) + ".bias");
                     if (!g || !bt) return D2S_E_MISSING;
-                    RC(fold_ln(g->data.data(), bt->data.data(), 3 * C, C, [&](int n, int k) { return kvq[n / C][(size_t)(n % C) * C + k]; }, nullptr,
-                               t.kvq_ln[a], &t.csum_kvq[a]));
+                    RC(upload_linear(e, prepare_linear(e->wprec, 3 * C, C, kvq_at, nullptr, g->data.data(), bt->data.data()), t.kvq_ln[a], &t.csum_kvq[a]));
                 }
             }
             RC(upload_f32(e, b + "ff_norm.weight", C, &t.ffn_g)); RC(upload_f32(e, b + "ff_norm.bias", C, &t.ffn_b));
@@ -933,7 +885,8 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                 auto orig = [C](int n) { return geglu_row(n, C); };
                 std::vector<float> b1p((size_t)8 * C);
                 for (int n = 0; n < 8 * C; ++n) b1p[n] = b1->data[orig(n)];
-                RC(fold_ln(g->data.data(), bt->data.data(), 8 * C, C, [&](int n, int k) { return w1p[(size_t)orig(n) * C + k]; }, b1p.data(), t.ff1_ln, &t.csum_ff1));
+                RC(upload_linear(e, prepare_linear(e->wprec, 8 * C, C, [&](int n, int k) { return w1p[(size_t)orig(n) * C + k]; }, b1p.data(),
+                                                   g->data.data(), bt->data.data()), t.ff1_ln, &t.csum_ff1));
             }
         }
         if (e->tm_fold) RC(dev_alloc(e, (void**)&e->tm_stats, (size_t)17 * max_sites * 2 * sizeof(float)));
@@ -1014,16 +967,14 @@ extern "C" int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, vo
             e->act_scale[(size_t)l * NSITE + s] = a * headroom / FP8_MAX;
         }
         for (int i = 0; i < 4; ++i) {                         // linear i reads site i (qkv <- LN1, proj <- attention, fc1 <- LN2, fc2 <- GELU)
-            std::vector<float> dq(ly.sw[i].size());
-            for (size_t n = 0; n < dq.size(); ++n) dq[n] = e->act_scale[(size_t)l * NSITE + i] * ly.sw[i][n];
+            const std::vector<float> dq = deq_scales(e->act_scale[(size_t)l * NSITE + i], ly.sw[i]);
             D2S_HIP(hipMemcpy(ly.deq[i], dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         // LN-folded linears read the raw residual: FC1 <- site 4 of this layer, QKV <- site 5 of the previous layer
         for (int i = 0; i < 2; ++i) {
             if (i == 0 && l == 0) continue;
             const float sraw = i == 0 ? e->act_scale[(size_t)(l - 1) * NSITE + 5] : e->act_scale[(size_t)l * NSITE + 4];
-            std::vector<float> dq(ly.sw_ln[i].size());
-            for (size_t n = 0; n < dq.size(); ++n) dq[n] = sraw * ly.sw_ln[i][n];
+            const std::vector<float> dq = deq_scales(sraw, ly.sw_ln[i]);
             D2S_HIP(hipMemcpy(ly.deq_ln[i], dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
         }
     }

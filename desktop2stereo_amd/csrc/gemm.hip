@@ -1000,6 +1000,18 @@ struct ProbeBuf {                    // device scratch of a probe, freed on ever
     ~ProbeBuf() { if (p) (void)hipFree(p); }
 };
 
+// host copy of a device float matrix
+int fetch_f32(std::vector<float>& h, const float* d, size_t n) {
+    h.resize(n);
+    D2S_HIP(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2S_OK;
+}
+int upload(ProbeBuf& buf, const void* h, size_t bytes) {
+    D2S_HIP(hipMalloc(&buf.p, bytes));
+    D2S_HIP(hipMemcpy(buf.p, h, bytes, hipMemcpyHostToDevice));
+    return D2S_OK;
+}
+
 // a split-K workspace as the engine holds one (engine.hip splitk_ws): elems fp32 partials followed by GEMM_PART_CTR_WORDS counter
 // words, zeroed in stream order -- the words behind the partials must be zero when a launch reads them (gemm.h)
 int alloc_splitk_ws(ProbeBuf& buf, size_t elems, hipStream_t st) {
@@ -1073,21 +1085,19 @@ extern "C" int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream) {
     const int Ho = (p->Hi + 2 - 3) / p->stride + 1, Wo = (p->Wi + 2 - 3) / p->stride + 1;
     const long M = (long)B * Ho * Wo, nsrc = (long)B * p->Hs * p->Ws;
     D2S_REQUIRE(M < (1L << 31) && nsrc * C < (1L << 31), "too large");
-    const int K = 9 * C, Kp = gemm_kpad(K, prec), Np = gemm_npad(N);
+    const int K = 9 * C, Kp = gemm_kpad(K, prec);
     const bool bf = prec == D2S_PREC_BF16;             // bf16 engine: bf16 activations; fp32 / bf16x3 engines: fp32 activations
     const bool out_t = !p->out_f32 && !p->map_head;    // OUT_T: bf16 on the bf16 engine, fp32 otherwise
-    ProbeBuf dWk, dW, dX, dR, dP;
-    // the weight in pack_conv3's K order (host permutation, the engine's index expression), then packed like d2s_gemm_probe's
-    {
-        std::vector<float> w((size_t)N * C * 9), wk((size_t)N * K);
-        D2S_HIP(hipMemcpy(w.data(), p->w, w.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (int n = 0; n < N; ++n)
-            for (int k = 0; k < K; ++k) wk[(size_t)n * K + k] = w[conv3_weight_index(n, k, C)];
-        D2S_HIP(hipMalloc(&dWk.p, wk.size() * sizeof(float)));
-        D2S_HIP(hipMemcpy(dWk.p, wk.data(), wk.size() * sizeof(float), hipMemcpyHostToDevice));
+    ProbeBuf dW, dX, dR, dP;
+    {   // the weight packed as pack_conv3 packs it
+        std::vector<float> w;
+        int rc = fetch_f32(w, p->w, (size_t)N * C * 9);
+        if (rc == D2S_OK) {
+            const LinearImage im = prepare_linear(prec, N, K, [&](int n, int k) { return w[conv3_weight_index(n, k, C)]; }, nullptr);
+            rc = upload(dW, im.w.data(), im.w.size());
+        }
+        if (rc != D2S_OK) return rc;
     }
-    D2S_HIP(hipMalloc(&dW.p, (size_t)Np * Kp * elem_size(prec)));
-    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv((long)Np * Kp, 256)), dim3(256), 0, st, (const float*)dWk.p, dW.p, N, K, Np, Kp, prec == D2S_PREC_BF16X3 ? -prec : prec);
     const void* x = p->x;
     if (bf) {
         D2S_HIP(hipMalloc(&dX.p, (size_t)nsrc * C * 2));
@@ -1135,17 +1145,6 @@ namespace {
 enum { ACT_F32 = 0, ACT_BF16 = 1, ACT_BX3 = 2, ACT_E4M3 = 3 };   // activation formats the engine's producers write
 size_t act_bytes(int fmt) { return fmt == ACT_BF16 ? 2 : (fmt == ACT_E4M3 ? 1 : 4); }
 
-// host copy of a device float matrix
-int fetch_f32(std::vector<float>& h, const float* d, size_t n) {
-    h.resize(n);
-    D2S_HIP(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
-    return D2S_OK;
-}
-int upload(ProbeBuf& buf, const void* h, size_t bytes) {
-    D2S_HIP(hipMalloc(&buf.p, bytes));
-    D2S_HIP(hipMemcpy(buf.p, h, bytes, hipMemcpyHostToDevice));
-    return D2S_OK;
-}
 // an activation matrix [M, K] (device fp32) as the engine's producers leave it, rows lda elements apart (zero padded): bf16 (RNE), the
 // pre-split bf16x3 units, e4m3 of x * qscale (RNE, saturating at +-448: the LayerNorm kernel's / GELU epilogue's conversion) or fp32
 int act_operand(ProbeBuf& buf, const float* x, int M, int K, int lda, int fmt, float qscale) {
@@ -1165,38 +1164,19 @@ int act_operand(ProbeBuf& buf, const float* x, int M, int K, int lda, int fmt, f
     return upload(buf, o.data(), o.size());
 }
 
-// one packed linear: weight rows in the kernel's order, bias / csum / deq vectors
+// one packed linear on the device (prepare_linear's image): weight rows in the kernel's order, bias / csum / deq vectors
 struct ProbeLinear {
     ProbeBuf w, bias, csum, deq;
     int Kp = 0;
 };
-// W [N, K] through at(n, k) (the packed row order), bias through b(n); LayerNorm gamma / beta folded in (g != null) as engine.hip
-// folds it; e4m3 (fp8): per-row scales, deq = s_a * s_w (d2s_engine_calibrate)
-template <typename F, typename Bf>
-int pack_probe_linear(ProbeLinear& L, int wprec, bool fp8, int N, int K, F at, Bf b, bool has_bias, const float* g, const float* beta, float s_a) {
-    std::vector<float> bias(N, 0.f), cs(N, 0.f);
-    for (int n = 0; n < N; ++n) bias[n] = has_bias ? b(n) : 0.f;
-    auto atg = [&](int n, int k) { return g ? g[k] * at(n, k) : at(n, k); };
-    std::vector<uint8_t> wb;
-    std::vector<float> sw;
-    if (fp8) { wb = pack_rows_fp8_host(N, K, atg, sw); L.Kp = gemm_kpad(K, D2S_PREC_FP8_OPERANDS); }
-    else { wb = pack_rows_host(wprec, N, K, atg); L.Kp = gemm_kpad(K, wprec); }
-    int rc = D2S_OK;
-    if (g) {
-        for (int n = 0; n < N; ++n) {
-            const double b0 = has_bias ? (double)b(n) : 0.0;
-            if (fp8) ln_fold_row_fp8(K, g, beta, at, n, b0, sw[n], bias[n], cs[n]);
-            else ln_fold_row(wprec, K, g, beta, at, n, b0, bias[n], cs[n]);
-        }
-        rc = upload(L.csum, cs.data(), cs.size() * sizeof(float));
-        if (rc != D2S_OK) return rc;
-    }
-    rc = upload(L.w, wb.data(), wb.size());
-    if (rc != D2S_OK) return rc;
-    if (has_bias || g) { rc = upload(L.bias, bias.data(), bias.size() * sizeof(float)); if (rc != D2S_OK) return rc; }
-    if (fp8) {
-        std::vector<float> dq(N);
-        for (int n = 0; n < N; ++n) dq[n] = s_a * sw[n];
+// e4m3: deq = s_a * s_w, as d2s_engine_calibrate sets it
+int upload_linear(ProbeLinear& L, const LinearImage& im, float s_a) {
+    L.Kp = im.Kpad;
+    int rc = upload(L.w, im.w.data(), im.w.size());
+    if (rc == D2S_OK && !im.bias.empty()) rc = upload(L.bias, im.bias.data(), im.bias.size() * sizeof(float));
+    if (rc == D2S_OK && !im.csum.empty()) rc = upload(L.csum, im.csum.data(), im.csum.size() * sizeof(float));
+    if (rc == D2S_OK && !im.sw.empty()) {
+        const std::vector<float> dq = deq_scales(s_a, im.sw);
         rc = upload(L.deq, dq.data(), dq.size() * sizeof(float));
     }
     return rc;
@@ -1212,21 +1192,19 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
     D2S_REQUIRE(site >= D2S_LIN_PATCH && site <= D2S_LIN_TM_PROJ_OUT, "bad site");
     D2S_REQUIRE(M > 0 && N > 0 && K > 0 && p->w, "bad argument");
     hipStream_t st = (hipStream_t)stream;
-    // the engine's precisions (d2s_engine_create): e->prec (activations), e->wprec (weights, GEMM operands); f8 / f8a as in forward()
-    const bool x3 = prec == D2S_PREC_BF16X3, f8 = prec == D2S_PREC_FP8 || prec == D2S_PREC_FP8_MLP, f8a = prec == D2S_PREC_FP8;
-    const int wprec = x3 ? D2S_PREC_BF16X3 : (f8 ? D2S_PREC_BF16 : prec);
-    const int aprec = x3 ? D2S_PREC_FP32 : (f8 ? D2S_PREC_BF16 : prec);
+    const PrecRules pr = prec_rules(prec);
+    const int wprec = pr.w, aprec = pr.act;
+    const bool x3 = wprec == D2S_PREC_BF16X3, f8 = pr.e4m3;
     const bool enc = site == D2S_LIN_QKV || site == D2S_LIN_PROJ || site == D2S_LIN_FC1 || site == D2S_LIN_FC2;
-    const bool e8 = f8 && (site == D2S_LIN_FC1 || site == D2S_LIN_FC2 || (f8a && (site == D2S_LIN_QKV || site == D2S_LIN_PROJ)));   // gemm8
+    const bool e8 = pr.e4m3_site(site);                                              // gemm8
     const bool fold = p->ln_fold != 0;
     const bool consumer = fold && (site == D2S_LIN_QKV || site == D2S_LIN_FC1 || site == D2S_LIN_NECK_PROJ || site == D2S_LIN_TM_KVQ || site == D2S_LIN_TM_FF1);
     const bool producer = fold && !consumer;
     D2S_REQUIRE(!producer || site == D2S_LIN_PROJ || site == D2S_LIN_FC2 || site == D2S_LIN_TM_PROJ_IN || site == D2S_LIN_TM_TO_OUT || site == D2S_LIN_TM_FF2,
                 "ln_fold: not a LayerNorm consumer or producer site");
-    // where the engine folds: forward() lnf / ln1_folded (encoder: bf16, bf16x3, e4m3 -- MLP-only e4m3: not around QKV), tap_fold and
-    // run_temporal's tm_fold (bf16 only)
-    D2S_REQUIRE(!fold || (enc ? (prec != D2S_PREC_FP32 && !(prec == D2S_PREC_FP8_MLP && (site == D2S_LIN_QKV || site == D2S_LIN_FC2))) : prec == D2S_PREC_BF16),
-                "ln_fold: the engine does not fold LayerNorm there in this precision");
+    // where the engine folds (ln_folds); on the e4m3 precisions the encoder's folds only: an e4m3 engine packs its temporal modules'
+    // folded copies but never runs them (d2s_engine_calibrate refuses a temporal engine), and the e4m3 formats below are the encoder's
+    D2S_REQUIRE(!fold || (pr.ln_folds(site) && (enc || !f8)), "ln_fold: the engine does not fold LayerNorm there in this precision");
     const bool per_frame = site == D2S_LIN_QKV || site == D2S_LIN_PATCH || site == D2S_LIN_NECK_PROJ;
     const int P = p->ntok - 1;
     D2S_REQUIRE(!per_frame || (p->ntok > 1 && M % (site == D2S_LIN_PATCH ? P : p->ntok) == 0), "M must be a multiple of the rows per frame");
@@ -1259,14 +1237,14 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
     ProbeBuf dPa;
     ProbeLinear Lp;
     if (consumer) {
-        const bool p8 = f8a;                               // (all-four e4m3: FC2 / proj on e4m3 operands; MLP-only: proj in bf16)
+        const bool p8 = pr.e4m3_attn;                      // (all-four e4m3: FC2 / proj on e4m3 operands; MLP-only: proj in bf16)
         const int pK = p->pK, D = K;
         std::vector<float> hw, hb;
         int rc = fetch_f32(hw, p->pw, (size_t)D * pK);
         if (rc == D2S_OK && p->pbias) rc = fetch_f32(hb, p->pbias, D);
         if (rc != D2S_OK) return rc;
-        rc = pack_probe_linear(Lp, wprec, p8, D, pK, [&](int n, int k) { return hw[(size_t)n * pK + k]; }, [&](int n) { return hb[n]; }, p->pbias != nullptr,
-                               nullptr, nullptr, p->s_pact);
+        rc = upload_linear(Lp, prepare_linear(p8 ? D2S_PREC_FP8_OPERANDS : wprec, D, pK, [&](int n, int k) { return hw[(size_t)n * pK + k]; },
+                                              p->pbias ? hb.data() : nullptr), p->s_pact);
         if (rc != D2S_OK) return rc;
         const int pfmt = p8 ? ACT_E4M3 : (x3 ? ACT_BX3 : (aprec == D2S_PREC_BF16 ? ACT_BF16 : ACT_F32));
         rc = act_operand(dPa, p->pa, M, pK, pK, pfmt, p8 ? 1.0f / p->s_pact : 0.f);
@@ -1283,7 +1261,7 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
     // ---- this linear's weights, in the packed row order: pack_convT's taps, the GEGLU interleave (x | gate in groups of four), else W's own
     ProbeLinear L;
     {
-        std::vector<float> hw, hb, hg, hbt;
+        std::vector<float> hw, hb, hg, hbt, pb;
         const int Co = site == D2S_LIN_NECK_RESIZE ? K : 0, ks = p->ks;
         int rc = fetch_f32(hw, p->w, (size_t)N * K);
         if (rc == D2S_OK && p->bias) rc = fetch_f32(hb, p->bias, Co ? Co : N);
@@ -1293,9 +1271,9 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
         const bool geglu = consumer && site == D2S_LIN_TM_FF1;
         auto row = [&](int n) { return geglu ? geglu_row(n, N / 8) : n; };
         auto at = [&](int n, int k) { return Co ? hw[convT_weight_index(n, k, Co, ks)] : hw[(size_t)row(n) * K + k]; };
-        auto bias = [&](int n) { return Co ? hb[n % Co] : hb[row(n)]; };
-        rc = pack_probe_linear(L, wprec, e8, N, K, at, bias, p->bias != nullptr, consumer ? hg.data() : nullptr, consumer ? hbt.data() : nullptr,
-                               consumer ? p->s_res : p->s_act);
+        if (p->bias) { pb.resize(N); for (int n = 0; n < N; ++n) pb[n] = Co ? hb[n % Co] : hb[row(n)]; }
+        rc = upload_linear(L, prepare_linear(e8 ? D2S_PREC_FP8_OPERANDS : wprec, N, K, at, p->bias ? pb.data() : nullptr, consumer ? hg.data() : nullptr,
+                                             consumer ? hbt.data() : nullptr), consumer ? p->s_res : p->s_act);
         if (rc != D2S_OK) return rc;
     }
     // ---- A: the producer's raw residual copy (folded consumers), else the operand as its producer in the engine writes it

@@ -1,12 +1,53 @@
-// The engine's linears, site by site: the GemmEpi each launch site builds (engine.hip forward, neck_proj, neck_rest, run_temporal)
-// and the host-side packing of their weights (plain, e4m3, LayerNorm folded).  Shared with d2s_linear_probe (gemm.hip), which
-// launches exactly what the engine launches.  Host side only.
+// The engine's linears, site by site: what an engine precision decides for them, the GemmEpi each launch site builds (engine.hip
+// forward, neck_proj, neck_rest, run_temporal) and the host-side preparation of their weights (plain, e4m3, LayerNorm folded).  Shared
+// with d2s_linear_probe and d2s_conv3_probe (gemm.hip), which launch exactly what the engine launches.  Host side only.
 #pragma once
 #include "gemm.h"
 #include <cmath>
 #include <vector>
 
 namespace d2s {
+
+// ---- precision -----------------------------------------------------------------------------------------------------------
+// What an engine precision (d2s_model_desc.precision, D2S_PREC_*) decides for its linears.  Which batches fold a LayerNorm, and the
+// switches that keep one a kernel, stay with the callers.
+struct PrecRules {
+    int precision;
+    int act;            // activations and the kernels that write them: fp32 or bf16 (the e4m3 engines are bf16 engines whose encoder
+                        // linears switch to e4m3 operands)
+    int w;              // weight packing and GEMM operands: = act, or bf16x3 (split precision on fp32 activations)
+    bool e4m3;          // FC1 / FC2 take e4m3 operands once calibrated (D2S_PREC_FP8, D2S_PREC_FP8_MLP) ...
+    bool e4m3_attn;     // ... and QKV / proj too (D2S_PREC_FP8)
+
+    // the linear at engine site s (D2S_LIN_*) runs on e4m3 operands
+    bool e4m3_site(int s) const {
+        return e4m3 && (s == D2S_LIN_FC1 || s == D2S_LIN_FC2 || (e4m3_attn && (s == D2S_LIN_QKV || s == D2S_LIN_PROJ)));
+    }
+    // a LayerNorm can fold into the linear at engine site s that consumes it, or out of the one that produces it:
+    // not on fp32 engines; LN1 (QKV; FC2 produces) not on the MLP-only e4m3 engine either, whose LN1 writes QKV's bf16 operand; the
+    // final LayerNorm (reassemble projections) on bf16 engines only, its bf16x3 and e4m3 forms stay kernels; the temporal modules'
+    // wherever they run on bf16 operands
+    bool ln_folds(int s) const {
+        switch (s) {
+            case D2S_LIN_QKV: case D2S_LIN_FC2: return precision != D2S_PREC_FP32 && precision != D2S_PREC_FP8_MLP;
+            case D2S_LIN_FC1: case D2S_LIN_PROJ: return precision != D2S_PREC_FP32;
+            case D2S_LIN_NECK_PROJ: return precision == D2S_PREC_BF16;
+            case D2S_LIN_TM_PROJ_IN: case D2S_LIN_TM_KVQ: case D2S_LIN_TM_FF1: case D2S_LIN_TM_TO_OUT: case D2S_LIN_TM_FF2:
+                return act == D2S_PREC_BF16 && w == D2S_PREC_BF16;
+            default: return false;
+        }
+    }
+};
+static inline PrecRules prec_rules(int precision) {
+    PrecRules r = {};
+    const bool x3 = precision == D2S_PREC_BF16X3;
+    r.precision = precision;
+    r.e4m3 = precision == D2S_PREC_FP8 || precision == D2S_PREC_FP8_MLP;
+    r.e4m3_attn = precision == D2S_PREC_FP8;
+    r.act = r.e4m3 ? D2S_PREC_BF16 : (x3 ? D2S_PREC_FP32 : precision);
+    r.w = x3 ? D2S_PREC_BF16X3 : r.act;
+    return r;
+}
 
 // ---- epilogues -----------------------------------------------------------------------------------------------------------
 static inline GemmEpi rowsE(void* out, int out_type, long ldc, const float* bias) {
@@ -130,6 +171,44 @@ static inline void ln_fold_row_fp8(int K, const float* g, const float* beta, F a
     double sb = b, sc = 0.0;
     for (int k = 0; k < K; ++k) { sb += (double)beta[k] * at(n, k); sc += e4m32f(f2e4m3(g[k] * at(n, k) / sw)); }
     bias2 = (float)sb; csum = (float)(sc * sw);
+}
+
+// One linear's weights as the GEMM takes them (host side): what the engine's PackedW / Layer and the probes upload
+struct LinearImage {
+    int N = 0, K = 0, Kpad = 0;
+    std::vector<uint8_t> w;             // [Npad][Kpad] in the GEMM precision
+    std::vector<float> bias;            // [N]: the bias, or bias' = b + W beta when a LayerNorm is folded in; empty: none
+    std::vector<float> csum;            // [N], folded: the colsum over what the MFMAs add (ln_fold_row*)
+    std::vector<float> sw;              // [N], e4m3: the row scales s_w
+};
+// W [N][K] through at(n, k) in the packed row order, with its bias [N] (or null), for the GEMM precision gprec: the weight precision
+// (bf16, bf16x3, fp32) or D2S_PREC_FP8_OPERANDS (e4m3 with per-row scales).  gamma / beta (not null): the LayerNorm in front of the
+// linear folded in -- W' = W diag(gamma) packed, bias' = b + W beta (b = 0 without a bias) and its colsum.
+template <typename F>
+static inline LinearImage prepare_linear(int gprec, int N, int K, F at, const float* bias, const float* gamma = nullptr,
+                                         const float* beta = nullptr) {
+    LinearImage im;
+    im.N = N; im.K = K; im.Kpad = gemm_kpad(K, gprec);
+    const bool e4m3 = gprec == D2S_PREC_FP8_OPERANDS;
+    auto atg = [&](int n, int k) { return gamma ? gamma[k] * at(n, k) : at(n, k); };
+    im.w = e4m3 ? pack_rows_fp8_host(N, K, atg, im.sw) : pack_rows_host(gprec, N, K, atg);
+    if (gamma) {
+        im.bias.resize(N); im.csum.resize(N);
+        for (int n = 0; n < N; ++n) {
+            const double b = bias ? bias[n] : 0.0;
+            if (e4m3) ln_fold_row_fp8(K, gamma, beta, at, n, b, im.sw[n], im.bias[n], im.csum[n]);
+            else ln_fold_row(gprec, K, gamma, beta, at, n, b, im.bias[n], im.csum[n]);
+        }
+    } else if (bias) {
+        im.bias.assign(bias, bias + N);
+    }
+    return im;
+}
+// an e4m3 linear's de-quantisation: deq[n] = s_act * s_w[n], s_act the scale of its A operand
+static inline std::vector<float> deq_scales(float s_act, const std::vector<float>& sw) {
+    std::vector<float> dq(sw.size());
+    for (size_t n = 0; n < dq.size(); ++n) dq[n] = s_act * sw[n];
+    return dq;
 }
 
 // ConvTranspose2d(k = s) weight [Ci, Co, s, s] as a linear's row n = (ky * s + kx) * Co + co, column k = ci
