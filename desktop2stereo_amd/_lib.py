@@ -104,6 +104,8 @@ SYMBOLS = {
     "d2s_process_area": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "d2s_overlay_text": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_char_p, _P]),
     "d2s_model_forward": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "d2s_model_forward_streams": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int), _P]),
+    "d2s_engine_reset_stream_at": (C.c_int, [_P, C.c_int]),
     "d2s_engine_calibrate": (C.c_int, [_P, _P, C.c_int, _P]),
     "d2s_post_process": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(PostParams), _P, C.c_uint64, _P]),
     "d2s_post_process_workspace": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
@@ -130,6 +132,8 @@ SYMBOLS = {
     "d2s_present_destroy": (C.c_int, [_P]),
     "d2s_pipeline": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PreParams), C.POINTER(PostParams),
                                C.POINTER(SbsParams), C.c_int, _P, C.c_int, _P, _P]),
+    "d2s_pipeline_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                       C.POINTER(PostParams), C.POINTER(SbsParams), C.c_int, _P, C.c_int, _P, _P]),
     "d2s_engine_reset_stream": (C.c_int, [_P]),
     "d2s_engine_tap": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "d2s_engine_profile": (C.c_int, [_P, C.c_int]),

@@ -95,7 +95,8 @@ struct d2s_engine {
         float *ln_g[2] = {nullptr, nullptr}, *ln_b[2] = {nullptr, nullptr}, *ffn_g = nullptr, *ffn_b = nullptr;
         PackedW proj_in, proj_out, kvq[2], to_out[2], ff1, ff2;     // kvq: fused to_k | to_v | to_q, [3C][C]
         float* ptab[2] = {nullptr, nullptr};       // [32][3C] = pe @ kvq^T: the positional encoding's share of k | v | q
-        void* cache[2] = {nullptr, nullptr};       // ring [31][sites][2C] T per attention block: projected k' | v' rows
+        void* cache[2] = {nullptr, nullptr};       // rings [max_batch][31][sites][2C] T per attention block: projected k' | v' rows, one ring per stream slot
+        size_t ring_bytes = 0;                     // one slot's ring (the single-stream layout: 32-bit offsets hold inside a ring)
         // round 5 (bf16 engine): the three LayerNorms of a module folded into the linears that consume them, like the ViT's (DESIGN.md
         // section 3.1b): W' = W diag(gamma), bias' = b + W beta, colsum over the bf16-rounded W'
         PackedW kvq_ln[2], ff1_ln;                  // (ff1_ln: rows interleaved x | gate in groups of four -- GEGLU happens in its epilogue)
@@ -103,15 +104,18 @@ struct d2s_engine {
     } tm[4];
     float* tm_stats = nullptr;                     // (sum, sum of squares) partials per (row, column block) of the folded LayerNorms
     bool tm_fold = false;
-    int tm_head = 0, tm_init = 0;                  // oldest ring slot; 0 until the first frame has filled the rings
-    float* tm_hs = nullptr;                        // [sites_max, C_max] fp32 residual of the temporal transformer
+    struct TSlot { int head = 0, filled = 0; };    // a stream slot's window: oldest ring slot; filled = 0 until its first frame has filled the rings
+    std::vector<TSlot> tm_slot;                    // [max_batch]
+    int row_ids[D2S_MAX_STREAMS] = {0};            // temporal engines: the stream slot of every batch row of the call in flight
+    float* tm_hs = nullptr;                        // [max_batch * sites_max, C_max] fp32 residual of the temporal transformer
     void *tm_a = nullptr, *tm_kv = nullptr, *tm_u = nullptr, *tm_g = nullptr, *tm_out = nullptr;
     // pipeline buffers
     float *pre_x = nullptr, *depth_small = nullptr, *depth_post = nullptr;    // model output; post-processed copy (d2s_pipeline)
     void* post_ws = nullptr;
     uint64_t post_ws_bytes = 0;
-    float* ema_state = nullptr;
+    float* ema_state = nullptr;                    // [h w]; temporal engines: [max_batch][h w], one state per stream slot
     int ema_init = 0;
+    std::vector<int> ema_slot_init;                // temporal engines: [max_batch]
     // debug taps (env D2S_TAPS=1): hidden states of frame 0 after embeddings and each layer
     bool taps = false;
     float* tap_hidden = nullptr;                   // [(layers+1), N, D]
@@ -311,12 +315,19 @@ int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int strid
     return gemm(e, a, w, B * Ho * Wo, ep, st);
 }
 
-// One streaming TemporalModule on an NHWC map x [sites, C] -> out; reads then updates its ring caches.
-// (reference motion_module.py:102-134, 164-196, 242-321; cache semantics vda2_s.py:177-218)
-int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st, const void* add = nullptr) {   // out = module(x) [+ add]
+// One streaming TemporalModule on NHWC maps x [B][sites, C] -> out; row r is the next frame of stream slot e->row_ids[r] and reads, then
+// updates, that slot's ring caches.  The linears, LayerNorms and GEGLU see M = B sites rows; GroupNorm, the attention and the ring
+// stores are per row.  (reference motion_module.py:102-134, 164-196, 242-321; cache semantics vda2_s.py:177-218)
+int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStream_t st, const void* add = nullptr) {   // out = module(x) [+ add]
     d2s_engine::TMod& t = e->tm[m];
-    const int C = t.C, S = t.sites, prec = e->prec;
-    const int Tw = e->tm_init ? 32 : 1;                 // first frame: a window of one (the frame itself at position 0)
+    const int C = t.C, S = B * t.sites, prec = e->prec;   // S: rows of every token matrix of this call
+    const int* ids = e->row_ids;
+    const d2s_engine::TSlot sl0 = e->tm_slot[ids[0]];
+    const int Tw = sl0.filled ? 32 : 1;                 // (B == 1) first frame: a window of one (the frame itself at position 0)
+    auto ring_of = [&](int a, int r) { return (void*)((char*)t.cache[a] + (size_t)ids[r] * t.ring_bytes); };
+    bool any_fresh = false;
+    double win_rows = 0;                                // sum of the rows' window lengths (attention FLOPs)
+    for (int r = 0; r < B; ++r) { const bool f = e->tm_slot[ids[r]].filled != 0; any_fresh |= !f; win_rows += f ? 32 : 1; }
     // Round 5, bf16 engine (D2S_VDA_FUSE=0 restores round 4's 18 launches per module): (i) the three LayerNorms live in the linears
     // either side of them -- the residual-update GEMM (proj_in, to_out) also leaves the raw residual as bf16 in tm_a and the row
     // statistics in tm_stats, the consumer (kvq, ff1) runs on gamma-folded weights (section 3.1b's algebra, eps 1e-5); (ii) the ring
@@ -329,7 +340,7 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st,
     auto consumer = [&](GemmEpi& ep, const float* csum) { epi_ln_consumer(ep, e->tm_stats, slots, csum, 1e-5f, C); };
     // (folded: proj_in leaves its bf16 copy in tm_a, so the GroupNorm output it reads goes to tm_out -- free until the attention writes it)
     void* gn_out = fold ? e->tm_out : e->tm_a;
-    PROF(PC_ELT, 0, 0, launch_groupnorm(prec, x, t.gn_g, t.gn_b, gn_out, S, C, 32, 1e-6f, st));
+    PROF(PC_ELT, 0, 0, launch_groupnorm(prec, x, t.gn_g, t.gn_b, gn_out, t.sites, C, 32, 1e-6f, st, B));
     {
         GemmEpi ep = rowsE(e->tm_hs, OUT_F32, C, t.proj_in.bias);
         producer(ep);
@@ -346,15 +357,33 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, hipStream_t st,
         }
         // the frame's projected rows join the window: the first frame fills all 31 slots (its own launch); later frames replace the
         // oldest slot -- inside the attention kernel when fused
-        const int store_slot = (fold && e->tm_init) ? e->tm_head : -1;
-        PROF(PC_ATTN, 4.0 * S * Tw * C, 0, launch_temporal_attn(prec, e->tm_kv, t.cache[a], t.ptab[a], e->tm_out, S, C, Tw, 31, e->tm_head, st, store_slot));
+        const int store_slot = (fold && sl0.filled) ? sl0.head : -1;
+        if (B == 1) {
+            PROF(PC_ATTN, 4.0 * S * Tw * C, 0, launch_temporal_attn(prec, e->tm_kv, ring_of(a, 0), t.ptab[a], e->tm_out, S, C, Tw, 31, sl0.head, st, store_slot));
+        } else {                                        // rows of different streams: per-row ring / head / window / store slot by value
+            AttnRows tab = {};
+            for (int r = 0; r < B; ++r) {
+                const d2s_engine::TSlot sl = e->tm_slot[ids[r]];
+                tab.r[r] = AttnRow{ring_of(a, r), (int16_t)sl.head, (int16_t)(sl.filled ? 32 : 1), (fold && sl.filled) ? sl.head : -1};
+            }
+            PROF(PC_ATTN, 4.0 * t.sites * win_rows * C, 0, launch_temporal_attn_rows(prec, e->tm_kv, t.ptab[a], e->tm_out, t.sites, C, 31, B, tab, st));
+        }
         {
             GemmEpi ep = epi_residual(e->tm_hs, C, t.to_out[a].bias, nullptr);
             producer(ep);
             RC(gemm(e, plainA(e->tm_out, C), t.to_out[a], S, ep, st));
         }
-        if (store_slot < 0)
-            PROF(PC_ELT, 0, 0, launch_cache_store(prec, t.cache[a], e->tm_kv, S, C, e->tm_init ? e->tm_head : 0, e->tm_init ? 1 : 31, st));
+        if (B == 1) {
+            if (store_slot < 0)
+                PROF(PC_ELT, 0, 0, launch_cache_store(prec, ring_of(a, 0), e->tm_kv, S, C, sl0.filled ? sl0.head : 0, sl0.filled ? 1 : 31, st));
+        } else if (!fold || any_fresh) {                // fused: only the fresh rows are left to store (their first-frame fill)
+            CacheRows tab = {};
+            for (int r = 0; r < B; ++r) {
+                const d2s_engine::TSlot sl = e->tm_slot[ids[r]];
+                tab.r[r] = CacheRow{ring_of(a, r), sl.filled ? sl.head : 0, sl.filled ? (fold ? 0 : 1) : 31};
+            }
+            PROF(PC_ELT, 0, 0, launch_cache_store_rows(prec, e->tm_kv, t.sites, C, B, tab, st));
+        }
     }
     {
         const bool folded = fold && slots >= 1 && slots <= 16;
@@ -417,8 +446,8 @@ int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
         RC(conv3(e, e->rproj[i], B, gh, gw, c, 2, 0, e->re[i].resize, e->rres[i], ACT_NONE, nullptr, nullptr, st));
         src = e->rres[i]; Hs = (gh - 1) / 2 + 1; Ws = (gw - 1) / 2 + 1;
     }
-    if (d.temporal && i == 2) { RC(run_temporal(e, 0, src, e->rres[2], st)); src = e->rres[2]; }     // layer_3
-    if (d.temporal && i == 3) { RC(run_temporal(e, 1, src, e->scr[0], st)); src = e->scr[0]; }       // layer_4
+    if (d.temporal && i == 2) { RC(run_temporal(e, 0, src, e->rres[2], B, st)); src = e->rres[2]; }     // layer_3
+    if (d.temporal && i == 3) { RC(run_temporal(e, 1, src, e->scr[0], B, st)); src = e->scr[0]; }       // layer_4
     RC(conv3(e, src, B, Hs, Ws, c, 1, 0, e->re[i].conv, e->feat[i], ACT_NONE, nullptr, nullptr, st));
     if (i < 3) {
         const int idx = 3 - i;                          // the fusion layer that consumes this map
@@ -574,7 +603,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (d.temporal && idx < 2) {                     // path_4 / path_3 (dpt_temporal.py:98-103)
             PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st));
             void* alt = e->scr[3 + ((idx + 1) & 1)];
-            RC(run_temporal(e, 2 + idx, pout, alt, st, next_r1));
+            RC(run_temporal(e, 2 + idx, pout, alt, B, st, next_r1));
             pout = alt;
         } else {
             if (idx == 3) {
@@ -619,9 +648,12 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
             PROF(PC_ELT, 0, 0, launch_head_final(prec, Z, e->w3, e->b3, d.max_depth, depth, (long)B * e->h * e->w, d.head_hidden, st));
         }
     }
-    if (d.temporal) {                                    // one window step per frame (vda2_s.py:177-187, 214-221)
-        if (e->tm_init) e->tm_head = (e->tm_head + 1) % 31;
-        e->tm_init = 1;
+    if (d.temporal) {                                    // one window step per frame (vda2_s.py:177-187, 214-221), for the streams of this call only
+        for (int r = 0; r < B; ++r) {
+            d2s_engine::TSlot& sl = e->tm_slot[e->row_ids[r]];
+            if (sl.filled) sl.head = (sl.head + 1) % 31;
+            sl.filled = 1;
+        }
     }
     e->last_batch = B;
     return D2S_OK;
@@ -672,6 +704,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     if (e->finalized) { set_error("engine already finalized"); return D2S_E_STATE; }
     const d2s_model_desc& d = e->d;
     D2S_REQUIRE(h > 0 && w > 0 && h % d.patch == 0 && w % d.patch == 0 && max_batch >= 1, "h, w must be patch multiples");
+    D2S_REQUIRE(!d.temporal || max_batch <= D2S_MAX_STREAMS, "a Video-Depth-Anything engine has at most D2S_MAX_STREAMS (32) stream slots: max_batch too large");
     D2S_ON_DEVICE(e->device);
     const int D = d.hidden, F = d.fusion;
     e->h = h; e->w = w; e->gh = h / d.patch; e->gw = w / d.patch; e->P = e->gh * e->gw; e->N = e->P + 1;
@@ -866,7 +899,8 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                 RC(dev_alloc(e, (void**)&t.ptab[a], pt.size() * 4));
                 D2S_HIP(hipMemcpy(t.ptab[a], pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
                 RC(pack_linear(e, q + "to_out.0.weight", q + "to_out.0.bias", C, C, t.to_out[a]));
-                RC(dev_alloc(e, &t.cache[a], (size_t)31 * t.sites * 2 * C * es, true));
+                t.ring_bytes = (size_t)31 * t.sites * 2 * C * es;
+                RC(dev_alloc(e, &t.cache[a], (size_t)B * t.ring_bytes, true));
                 if (e->tm_fold) {
                     const HostT *g = find(e, b + "norms." + std::to_string(a) + ".weight"), *bt = find(e, b + "norms." + std::to_string(a) + ".bias");
                     if (!g || !bt) return D2S_E_MISSING;
@@ -889,6 +923,9 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                                                    g->data.data(), bt->data.data()), t.ff1_ln, &t.csum_ff1));
             }
         }
+        sc_max *= (size_t)B; max_sites *= (size_t)B;      // every row of a call runs through the same workspaces
+        e->tm_slot.assign(B, d2s_engine::TSlot());
+        e->ema_slot_init.assign(B, 0);
         if (e->tm_fold) RC(dev_alloc(e, (void**)&e->tm_stats, (size_t)17 * max_sites * 2 * sizeof(float)));
         RC(dev_alloc(e, (void**)&e->tm_hs, sc_max * 4));
         RC(dev_alloc(e, &e->tm_a, sc_max * es)); RC(dev_alloc(e, &e->tm_out, sc_max * es));
@@ -901,7 +938,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     RC(dev_alloc(e, (void**)&e->depth_post, (size_t)B * h * w * 4));
     e->post_ws_bytes = d2s_post_process_workspace(B, h, w);
     RC(dev_alloc(e, &e->post_ws, e->post_ws_bytes));
-    RC(dev_alloc(e, (void**)&e->ema_state, (size_t)h * w * 4));
+    RC(dev_alloc(e, (void**)&e->ema_state, (size_t)(d.temporal ? B : 1) * h * w * 4));
     if (e->taps) RC(dev_alloc(e, (void**)&e->tap_hidden, (size_t)(d.layers + 1) * N * D * 4));
     D2S_HIP(hipDeviceSynchronize());
     e->finalized = true;
@@ -927,13 +964,36 @@ extern "C" int d2s_engine_memory(const d2s_engine* e, uint64_t* bytes) {
     return D2S_OK;
 }
 
-extern "C" int d2s_model_forward(d2s_engine* e, const float* x, float* depth, int batch, void* stream) {
+namespace {
+// the stream slot of every batch row of a call (e->row_ids), checked before anything is launched
+int resolve_streams(d2s_engine* e, int batch, const int* stream_ids) {
+    if (!e->d.temporal) {
+        D2S_REQUIRE(!stream_ids, "stream_ids on an engine that is not a Video-Depth-Anything engine: its batch rows are not streams");
+        return D2S_OK;
+    }
+    uint32_t seen = 0;
+    for (int r = 0; r < batch; ++r) {
+        const int id = stream_ids ? stream_ids[r] : r;
+        if (id < 0 || id >= e->maxB) { set_error("stream id " + std::to_string(id) + " out of range: the engine has " + std::to_string(e->maxB) + " stream slot(s)"); return D2S_E_INVALID; }
+        if (seen >> id & 1u) { set_error("stream id " + std::to_string(id) + " named twice in one call"); return D2S_E_INVALID; }
+        seen |= 1u << id;
+    }
+    for (int r = 0; r < batch; ++r) e->row_ids[r] = stream_ids ? stream_ids[r] : r;
+    return D2S_OK;
+}
+}  // namespace
+
+extern "C" int d2s_model_forward_streams(d2s_engine* e, const float* x, float* depth, int batch, const int* stream_ids, void* stream) {
     D2S_REQUIRE(e && x && depth, "null pointer");
     if (!e->finalized) { set_error("d2s_model_forward before d2s_engine_finalize"); return D2S_E_STATE; }
     D2S_REQUIRE(batch >= 1 && batch <= e->maxB, "batch exceeds max_batch");
-    D2S_REQUIRE(!e->d.temporal || batch == 1, "a Video-Depth-Anything engine is one stream: batch must be 1");
+    RC(resolve_streams(e, batch, stream_ids));
     D2S_ON_DEVICE(e->device);
     return forward(e, x, depth, batch, (hipStream_t)stream);
+}
+
+extern "C" int d2s_model_forward(d2s_engine* e, const float* x, float* depth, int batch, void* stream) {
+    return d2s_model_forward_streams(e, x, depth, batch, nullptr, stream);
 }
 
 extern "C" int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, void* stream) {
@@ -985,17 +1045,37 @@ extern "C" int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, vo
 extern "C" int d2s_engine_reset_stream(d2s_engine* e) {
     D2S_REQUIRE(e, "null engine");
     e->ema_init = 0;
-    e->tm_init = 0; e->tm_head = 0;                     // VDA: drop the temporal window (next frame re-seeds it)
+    for (auto& sl : e->tm_slot) sl = d2s_engine::TSlot();     // VDA: drop every temporal window (a slot's next frame re-seeds it)
+    for (auto& i : e->ema_slot_init) i = 0;
+    return D2S_OK;
+}
+
+extern "C" int d2s_engine_reset_stream_at(d2s_engine* e, int stream_id) {
+    D2S_REQUIRE(e, "null engine");
+    const int slots = e->d.temporal ? (int)e->tm_slot.size() : 1;       // (not a temporal engine: one EMA state, slot 0)
+    if (stream_id < 0 || stream_id >= slots) {
+        set_error("d2s_engine_reset_stream_at: stream " + std::to_string(stream_id) + " does not exist (the engine has " + std::to_string(slots) + " slot(s))");
+        return D2S_E_INVALID;
+    }
+    if (!e->d.temporal) { e->ema_init = 0; return D2S_OK; }
+    e->tm_slot[stream_id] = d2s_engine::TSlot();
+    e->ema_slot_init[stream_id] = 0;
     return D2S_OK;
 }
 
 extern "C" int d2s_pipeline(d2s_engine* e, const uint8_t* frames, int batch, int H, int W, int depth_resolution,
                             const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_sbs_params* sp, int use_ema,
                             void* out, int out_fmt, float* depth_full, void* stream) {
+    return d2s_pipeline_streams(e, frames, batch, nullptr, H, W, depth_resolution, pre, pp, sp, use_ema, out, out_fmt, depth_full, stream);
+}
+
+extern "C" int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
+                                    const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_sbs_params* sp, int use_ema,
+                                    void* out, int out_fmt, float* depth_full, void* stream) {
     D2S_REQUIRE(e && frames && pp && sp && out, "null pointer");
     if (!e->finalized) { set_error("d2s_pipeline before d2s_engine_finalize"); return D2S_E_STATE; }
     D2S_REQUIRE(batch >= 1 && batch <= e->maxB, "batch exceeds max_batch");
-    D2S_REQUIRE(!e->d.temporal || batch == 1, "a Video-Depth-Anything engine is one stream: batch must be 1");
+    RC(resolve_streams(e, batch, stream_ids));
     // model-input shape of this frame size must be the engine's (reference: fixed at first frame, depth.py:1951-1953)
     D2S_REQUIRE(H > 0 && W > 0 && depth_resolution > 0, "bad frame shape");
     int longest = H > W ? H : W;
@@ -1027,7 +1107,12 @@ extern "C" int d2s_pipeline(d2s_engine* e, const uint8_t* frames, int batch, int
     }
     // post-process out of place (raw model output -> depth_post): few frames take the one-launch form (post.hip)
     PROF(PC_POST, 0, 0, d2s_post_process_to(e->depth_small, e->depth_post, batch, e->h, e->w, pp, e->post_ws, e->post_ws_bytes, stream));
-    if (use_ema) {
+    if (use_ema && e->d.temporal) {                      // one state per stream slot: a row continues (or starts) its own
+        EmaRows tab = {};
+        for (int r = 0; r < batch; ++r) tab.r[r] = EmaRow{e->row_ids[r], e->ema_slot_init[e->row_ids[r]]};
+        RC(ema_rows(e->depth_post, e->ema_state, batch, tab, e->h * e->w, pp->ema_alpha, st));
+        for (int r = 0; r < batch; ++r) e->ema_slot_init[e->row_ids[r]] = 1;
+    } else if (use_ema) {
         RC(ema_batch(e->depth_post, e->ema_state, e->ema_init, batch, e->h * e->w, pp->ema_alpha, st));
         e->ema_init = 1;
     }

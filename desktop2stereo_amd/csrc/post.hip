@@ -4,6 +4,7 @@
 //   A11  anti_alias: separable Gaussian, zero padding, H then V     reference depth.py:740-765
 //   A12  DepthStabilizer (EMA)                                      reference depth.py:1865-1887
 #include "common.h"
+#include "vit_ops.h"
 #include <math.h>
 
 namespace d2s {
@@ -554,6 +555,20 @@ ema_kernel(float* __restrict__ depth, float* __restrict__ state, int initialised
     state[i] = prev;
 }
 
+// EMA per stream slot (temporal engines): batch row blockIdx.y is ONE new frame of stream tab.r[row].slot; no chain across rows.
+__global__ void __launch_bounds__(256)
+ema_rows_kernel(float* __restrict__ depth, float* __restrict__ state, int hw, float wgt, const EmaRows tab) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hw) return;
+    const EmaRow r = tab.r[blockIdx.y];
+    float* d = depth + (long)blockIdx.y * hw + i;
+    float* s = state + (long)r.slot * hw + i;
+    float prev = *d;
+    if (r.initialised) { const float p0 = *s; prev = p0 + wgt * (prev - p0); }     // torch lerp_, weight < 0.5
+    *d = prev;
+    *s = prev;
+}
+
 }  // namespace d2s
 
 using namespace d2s;
@@ -654,6 +669,13 @@ extern "C" int d2s_ema_update(float* depth, float* state, int initialised, int h
 
 namespace d2s {
 // engine-internal: EMA over a batch of frames in order
+int ema_rows(float* depth, float* state, int rows, const EmaRows& tab, int hw, float alpha, hipStream_t st) {
+    if (rows < 1 || rows > TA_MAX_ROWS) { set_error("ema_rows: bad row count"); return D2S_E_INVALID; }
+    hipLaunchKernelGGL(ema_rows_kernel, dim3(cdiv(hw, 256), rows), dim3(256), 0, st, depth, state, hw, 1.0f - alpha, tab);
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
 int ema_batch(float* depth, float* state, int initialised, int nframes, int hw, float alpha, hipStream_t st) {
     hipLaunchKernelGGL(ema_kernel, dim3(cdiv(hw, 256)), dim3(256), 0, st, depth, state, initialised, nframes, hw, 1.0f - alpha);
     D2S_CHECK_LAUNCH();

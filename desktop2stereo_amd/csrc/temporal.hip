@@ -10,6 +10,7 @@
 // cache of hidden states every frame and re-projects all 32 window positions; here the oldest slot of projected
 // rows is overwritten in place and only the new frame is projected).
 #include "vit_ops.h"
+#include <algorithm>
 #include <type_traits>
 
 namespace d2s {
@@ -31,7 +32,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return s;
 }
 
-// nn.GroupNorm(32 groups, eps) on an NHWC map [sites, C]: one block per group, two-pass statistics (mean, then the sum of squared
+// nn.GroupNorm(32 groups, eps) on NHWC maps [rows][sites, C]: one block per (group, row), two-pass statistics (mean, then the sum of squared
 // deviations) over values that STAY IN REGISTERS.  Round 4's kernel took 16 us for 2-9 k elements: three passes of scalar bf16 loads in a
 // run-time loop, every load waited for before the next was issued (rocprofv3, profiles/r5_04) -- 64 us of a 1.06 ms VDA frame.  Here a
 // thread owns whole sites (the group's cpg channels of a site are contiguous: one 8 / 16-byte aligned vector load per chunk), all of a
@@ -43,6 +44,7 @@ groupnorm_reg_kernel(const T* __restrict__ x, const float* __restrict__ g, const
                      int sites, int C, float eps) {
     __shared__ float red[16];
     const int c0 = blockIdx.x * CPG, tid = threadIdx.x;
+    x += (long)blockIdx.y * sites * C; out += (long)blockIdx.y * sites * C;      // blockIdx.y: the row (stream) of a batched call -- statistics never cross rows
     float v[RPT][CPG];
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
@@ -103,6 +105,7 @@ groupnorm_kernel(const T* __restrict__ x, const float* __restrict__ g, const flo
                  int sites, int C, int groups, float eps) {
     __shared__ float red[4];
     const int cpg = C / groups, c0 = blockIdx.x * cpg;
+    x += (long)blockIdx.y * sites * C; out += (long)blockIdx.y * sites * C;
     const int n = sites * cpg;
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += tf(x[(long)(i / cpg) * C + c0 + i % cpg]);
@@ -133,6 +136,21 @@ cache_store_kernel(T* __restrict__ cache, const T* __restrict__ cur, int sites, 
     if (idx >= per * nslots) return;
     long r = idx % per;
     cache[(long)slot0 * per + idx] = cur[(r / C2) * 3 * C + r % C2];
+}
+
+// The same for the rows of a batched call (blockIdx.y = batch row): row r copies its k' | v' rows of cur [rows][S][3C] into slots
+// [slot0, slot0 + nslots) of ITS stream's ring -- 31 slots for a stream's first frame, one (or none) otherwise.  The table travels by
+// value in the kernel arguments and is read with a block-uniform index.
+template <typename T>
+__global__ void __launch_bounds__(256)
+cache_store_rows_kernel(const T* __restrict__ cur, int sites, int C, const CacheRows tab) {
+    const CacheRow r = tab.r[blockIdx.y];
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int C2 = 2 * C;
+    const long per = (long)sites * C2;
+    if (idx >= per * r.nslots) return;
+    const long q = idx % per;
+    ((T*)r.ring)[(long)r.slot0 * per + idx] = cur[((long)blockIdx.y * sites + q / C2) * 3 * C + q % C2];
 }
 
 template <int CH> __device__ __forceinline__ void load_ch(const float* p, float v[CH]) {
@@ -264,6 +282,99 @@ temporal_attn_ring_kernel(const T* __restrict__ cur, T* __restrict__ ring, const
     }
 }
 
+// The same attention over the rows of a batched call: row r of cur [rows][S][3C] is the next frame of ONE stream with its own ring, oldest
+// slot, window length (1 for a stream's first frame, else 32) and store slot (-1: none).  These come from a by-value table in the kernel
+// arguments (no upload, no dependent launch) and are looked up PER LANE: a 256-thread block usually straddles two rows, and a wave does
+// whenever upl = 16 (C <= 64) and the site count is odd.  A unit never straddles rows, so every shuffle stays inside one row's lanes; a
+// fresh row (Tw = 1) beside a warm one (Tw = 32) differs in masks and addresses only -- no branch encloses a shuffle.
+template <typename T, int CH>
+__global__ void __launch_bounds__(256)
+temporal_attn_rows_kernel(const T* __restrict__ cur, const float* __restrict__ ptab, T* __restrict__ out,
+                          int sites, int C, int slots, float scale, int lpu, int rows, const AttnRows tab) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int upl = lpu * TA_KG;                                   // lanes per unit (<= 64: a unit never straddles a wave)
+    const int unit = gid / upl, sub = gid % upl, kg = sub / lpu, li = sub % lpu;
+    const bool live = unit < rows * sites * 8;                     // (no early return: the shuffles below need every lane)
+    const int gs = live ? unit >> 3 : 0, h = unit & 7, dh = C >> 3, C2 = 2 * C, C3 = 3 * C;   // gs: site over all rows
+    const int row = gs / sites, s = gs - row * sites;              // row < rows <= TA_MAX_ROWS for every lane (dead lanes: row 0)
+    const AttnRow ar = tab.r[row];                                 // per LANE: a wave holds units of two rows at a row boundary
+    T* const ring = (T*)ar.ring;
+    const int Tw = ar.Tw, head = ar.head, store_slot = ar.store_slot;
+    const bool act = live && li * CH < dh;                         // lanes beyond the head's channels only take part in shuffles
+    const int c = h * dh + (act ? li * CH : 0);                    // this lane's first channel
+    const T* cur_row = cur + (long)gs * C3;
+    // this lane's 8 window positions and their rows (32-bit element offsets: a ring is < 2^31 elements, checked by the launcher);
+    // positions >= Tw (first frame only: Tw = 1) re-read the last valid row and are masked out of the softmax
+    const int slot_stride = sites * C2, base_s = s * C2 + c;
+    const T* krow[TA_KPG];
+    int jpos[TA_KPG];
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) {
+        const int j = kg * TA_KPG + t, jj = min(j, Tw - 1);
+        int slot = head + jj; if (slot >= slots) slot -= slots;    // (head < slots, jj < 32 <= slots + 1: one conditional subtract, no modulo)
+        if (slot >= slots) slot -= slots;
+        krow[t] = (act && jj < Tw - 1) ? ring + (slot * slot_stride + base_s) : cur_row + c;   // (padding / dead lanes never touch the ring: see the store below)
+        jpos[t] = jj;
+    }
+    RawSeg<T, CH> rk[TA_KPG], rv[TA_KPG];
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) rk[t].load(krow[t]);
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) rv[t].load(krow[t] + C);
+    float q[CH];
+    {
+        float pq[CH];
+        load_ch<CH>(cur_row + C2 + c, q);
+        load_ch<CH>(ptab + (long)(Tw - 1) * C3 + C2 + c, pq);
+#pragma unroll
+        for (int i = 0; i < CH; ++i) q[i] = act ? q[i] + pq[i] : 0.f;
+    }
+    float sc[TA_KPG];
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) {
+        float pk[CH];
+        load_ch<CH>(ptab + (long)jpos[t] * C3 + c, pk);
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) a += q[i] * (rk[t].get(i) + pk[i]);
+        for (int o = lpu >> 1; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        sc[t] = kg * TA_KPG + t < Tw ? a * scale : -1e30f;
+    }
+    float mx = -1e30f;
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) mx = fmaxf(mx, sc[t]);
+    mx = fmaxf(mx, __shfl_xor(mx, lpu)); mx = fmaxf(mx, __shfl_xor(mx, 2 * lpu));
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) { sc[t] = kg * TA_KPG + t < Tw ? __expf(sc[t] - mx) : 0.f; sum += sc[t]; }
+    sum += __shfl_xor(sum, lpu); sum += __shfl_xor(sum, 2 * lpu);
+    const float inv = 1.0f / sum;
+    float acc[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int t = 0; t < TA_KPG; ++t) {
+        float pv[CH];
+        load_ch<CH>(ptab + (long)jpos[t] * C3 + C + c, pv);
+        const float p = sc[t] * inv;                               // 0 for masked positions
+#pragma unroll
+        for (int i = 0; i < CH; ++i) acc[i] += p * (rv[t].get(i) + pv[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < CH; ++i) { acc[i] += __shfl_xor(acc[i], lpu); acc[i] += __shfl_xor(acc[i], 2 * lpu); }
+    if (act && kg == 0) {
+#pragma unroll
+        for (int i = 0; i < CH; ++i) out[(long)gs * C + c + i] = tcvt<T>(acc[i]);
+    }
+    // the in-kernel ring store, per row: the lane that owns window position 0 of (site, chunk) overwrites the oldest slot of ITS stream's
+    // ring after its own two loads of it -- the single-stream kernel's ordering argument, unchanged (no other lane reads that segment)
+    if (act && kg == 0 && store_slot >= 0) {
+        T* dst = ring + ((long)store_slot * slot_stride + base_s);
+#pragma unroll
+        for (int i = 0; i < CH; ++i) { dst[i] = cur_row[c + i]; dst[C + i] = cur_row[C + c + i]; }
+    }
+}
+
 // GEGLU: g[r, c] = u[r, c] * gelu_exact(u[r, 4C + c]),  u [rows, 8C] -> g [rows, 4C]
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -290,9 +401,9 @@ cast_f32_kernel(const float* __restrict__ in, T* __restrict__ out, long n) {
     } while (0)
 
 template <typename T>
-static bool launch_groupnorm_reg(const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st) {
+static bool launch_groupnorm_reg(const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, int rows, hipStream_t st) {
     const int cpg = C / groups, rpt = (sites + 1023) / 1024;
-#define D2S_GN(CPG_, RPT_) { hipLaunchKernelGGL((groupnorm_reg_kernel<T, CPG_, RPT_>), dim3(groups), dim3(1024), 0, st, (const T*)x, g, b, (T*)out, sites, C, eps); return true; }
+#define D2S_GN(CPG_, RPT_) { hipLaunchKernelGGL((groupnorm_reg_kernel<T, CPG_, RPT_>), dim3(groups, rows), dim3(1024), 0, st, (const T*)x, g, b, (T*)out, sites, C, eps); return true; }
 #define D2S_GN_R(CPG_) { if (rpt == 1) D2S_GN(CPG_, 1) if (rpt == 2) D2S_GN(CPG_, 2) if (rpt <= 4 && (CPG_) * 4 <= 96) D2S_GN(CPG_, 4) return false; }
     switch (cpg) {          // C / 32 of the model zoo: fusion 64 / 128 / 256, neck 192 / 384 / 512 / 768 / 1024
         case 2: D2S_GN_R(2) case 4: D2S_GN_R(4) case 6: D2S_GN_R(6) case 8: D2S_GN_R(8) case 12: D2S_GN_R(12)
@@ -303,16 +414,17 @@ static bool launch_groupnorm_reg(const void* x, const float* g, const float* b, 
 #undef D2S_GN
 }
 
-int launch_groupnorm(int prec, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st) {
+int launch_groupnorm(int prec, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st, int rows) {
+    if (rows < 1 || rows > 65535) { set_error("groupnorm: bad row count"); return D2S_E_INVALID; }
     if (C % groups) { set_error("groupnorm: C must be a multiple of the group count"); return D2S_E_INVALID; }
     static EnvInt old{"D2S_GN_OLD", 0};                   // A/B aid: round 4's kernel
     const bool reg_ok = !old.get() && ((C / groups) & 1) == 0;
     if (prec == D2S_PREC_BF16) {
-        if (!(reg_ok && launch_groupnorm_reg<bf16_t>(x, g, b, out, sites, C, groups, eps, st)))
-            hipLaunchKernelGGL(groupnorm_kernel<bf16_t>, dim3(groups), dim3(256), 0, st, (const bf16_t*)x, g, b, (bf16_t*)out, sites, C, groups, eps);
+        if (!(reg_ok && launch_groupnorm_reg<bf16_t>(x, g, b, out, sites, C, groups, eps, rows, st)))
+            hipLaunchKernelGGL(groupnorm_kernel<bf16_t>, dim3(groups, rows), dim3(256), 0, st, (const bf16_t*)x, g, b, (bf16_t*)out, sites, C, groups, eps);
     } else {
-        if (!(reg_ok && launch_groupnorm_reg<float>(x, g, b, out, sites, C, groups, eps, st)))
-            hipLaunchKernelGGL(groupnorm_kernel<float>, dim3(groups), dim3(256), 0, st, (const float*)x, g, b, (float*)out, sites, C, groups, eps);
+        if (!(reg_ok && launch_groupnorm_reg<float>(x, g, b, out, sites, C, groups, eps, rows, st)))
+            hipLaunchKernelGGL(groupnorm_kernel<float>, dim3(groups, rows), dim3(256), 0, st, (const float*)x, g, b, (float*)out, sites, C, groups, eps);
     }
     D2S_CHECK_LAUNCH();
     return D2S_OK;
@@ -338,6 +450,45 @@ int launch_temporal_attn(int prec, const void* cur, void* ring, const float* pta
     const dim3 grid(cdiv((long)sites * 8 * lpu * TA_KG, 256)), block(256);
 #define D2S_TATT(TT, CH) hipLaunchKernelGGL((temporal_attn_ring_kernel<TT, CH>), grid, block, 0, st, (const TT*)cur, (TT*)ring, ptab, (TT*)out, \
                                             sites, C, Tw, slots, head, scale, lpu, store_slot)
+    if (prec == D2S_PREC_BF16) { if (ch8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
+    else { if (ch8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
+#undef D2S_TATT
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+int launch_cache_store_rows(int prec, const void* cur, int sites, int C, int rows, const CacheRows& tab, hipStream_t st) {
+    if (rows < 1 || rows > TA_MAX_ROWS) { set_error("cache_store: bad row count"); return D2S_E_INVALID; }
+    int most = 0;
+    for (int r = 0; r < rows; ++r) most = std::max(most, tab.r[r].nslots);
+    if (most == 0) return D2S_OK;
+    const dim3 grid(cdiv((long)sites * 2 * C * most, 256), rows);
+    if (prec == D2S_PREC_BF16) hipLaunchKernelGGL(cache_store_rows_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)cur, sites, C, tab);
+    else hipLaunchKernelGGL(cache_store_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)cur, sites, C, tab);
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+int launch_temporal_attn_rows(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
+                              const AttnRows& tab, hipStream_t st) {
+    if (C % 32 || rows < 1 || rows > TA_MAX_ROWS) { set_error("temporal_attn: C % 32 == 0 and 1 <= rows <= 32 required"); return D2S_E_INVALID; }
+    for (int r = 0; r < rows; ++r) {
+        const AttnRow& a = tab.r[r];
+        if (!a.ring || (a.Tw != 1 && a.Tw != 32) || a.head < 0 || a.head >= slots || a.store_slot < -1 || a.store_slot >= slots) {
+            set_error("temporal_attn: bad row table"); return D2S_E_INVALID;
+        }
+    }
+    const float scale = 1.0f / sqrtf((float)(C / 8));
+    const bool ch8 = (C / 8) % 8 == 0;
+    int lpu = 1;
+    while (lpu * (ch8 ? 8 : 4) < C / 8) lpu <<= 1;
+    if (lpu * TA_KG > 64) { set_error("temporal_attn: head dim too large"); return D2S_E_UNSUPPORTED; }
+    // (per-stream limit, as in the single-stream launcher: offsets inside ONE ring are 32-bit; rows are reached through 64-bit pointers)
+    if ((long)slots * sites * 2 * C >= (1L << 31) || slots < 31) { set_error("temporal_attn: ring too large for 32-bit offsets (or fewer than 31 slots)"); return D2S_E_UNSUPPORTED; }
+    if ((long)rows * sites * 8 * lpu * TA_KG >= (1L << 31)) { set_error("temporal_attn: too many units"); return D2S_E_UNSUPPORTED; }
+    const dim3 grid(cdiv((long)rows * sites * 8 * lpu * TA_KG, 256)), block(256);
+#define D2S_TATT(TT, CH) hipLaunchKernelGGL((temporal_attn_rows_kernel<TT, CH>), grid, block, 0, st, (const TT*)cur, ptab, (TT*)out, \
+                                            sites, C, slots, scale, lpu, rows, tab)
     if (prec == D2S_PREC_BF16) { if (ch8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
     else { if (ch8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
 #undef D2S_TATT

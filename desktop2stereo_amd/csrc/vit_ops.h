@@ -32,15 +32,32 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
                      float fp8_qscale = 0.f, bool prescaled = false, bool bx3_out = false);
 
 // Video-Depth-Anything temporal-module kernels (temporal.hip)
-int launch_groupnorm(int prec, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st);
+// x, out [rows][sites, C]: one normalisation per (row, group)
+int launch_groupnorm(int prec, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st,
+                     int rows = 1);
 // cur [S, 3C] = k' | v' | q' of this frame; ring [slots][S][2C] = k' | v' of the past frames; ptab [32][3C] = pe @ W^T
 int launch_cache_store(int prec, void* ring, const void* cur, int sites, int C, int slot0, int nslots, hipStream_t st);
 int launch_temporal_attn(int prec, const void* cur, void* ring, const float* ptab, void* out, int sites, int C, int Tw, int slots,
                          int head, hipStream_t st, int store_slot = -1 /* >= 0: also write this frame's k' | v' rows into that ring slot */);
+// Several streams in one call (a temporal engine with max_batch > 1): batch row r is the next frame of one stream.  What differs
+// per row travels BY VALUE in the kernel arguments -- TA_MAX_ROWS entries of 16 bytes -- so a call needs no upload and no extra launch.
+constexpr int TA_MAX_ROWS = D2S_MAX_STREAMS;
+struct AttnRow { void* ring; int16_t head, Tw; int32_t store_slot; };      // the stream's ring, its oldest slot, window 1 | 32, slot to fill or -1
+struct AttnRows { AttnRow r[TA_MAX_ROWS]; };
+struct CacheRow { void* ring; int32_t slot0, nslots; };                    // ring[slot0 .. slot0 + nslots) = this row's k' | v' rows (nslots 0: none)
+struct CacheRows { CacheRow r[TA_MAX_ROWS]; };
+struct EmaRow { int32_t slot, initialised; };
+struct EmaRows { EmaRow r[TA_MAX_ROWS]; };
+static_assert(sizeof(AttnRow) == 16 && sizeof(CacheRow) == 16, "row tables are 16 bytes per row");
+int launch_cache_store_rows(int prec, const void* cur, int sites, int C, int rows, const CacheRows& tab, hipStream_t st);
+int launch_temporal_attn_rows(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
+                              const AttnRows& tab, hipStream_t st);
 int launch_geglu(int prec, const void* u, void* g, long rows, int C4, hipStream_t st);
 int launch_cast_f32(int prec, const float* in, void* out, long n, hipStream_t st);
 
 // engine-internal (post.hip)
 int ema_batch(float* depth, float* state, int initialised, int nframes, int hw, float alpha, hipStream_t st);
+// one EMA state per stream slot: row r of depth [rows][hw] updates state[tab.r[r].slot][hw] (started by it when not initialised)
+int ema_rows(float* depth, float* state, int rows, const EmaRows& tab, int hw, float alpha, hipStream_t st);
 
 }  // namespace d2s

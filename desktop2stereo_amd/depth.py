@@ -44,7 +44,8 @@ def configure(model="vitb", weights: Optional[Dict[str, np.ndarray]] = None, par
     `model`: "vits" | "vitb" | "vitl" | "tiny" | a reference MODEL_ID | a ModelConfig.
     `weights`: HF-keyed float arrays, a path to model.safetensors, or None (seeded synthetic)."""
     from .weights import load_safetensors, make_weights
-    # Video-Depth-Anything ids (reference utils.py model map; depth.py:875-893): streaming temporal head, one stream
+    # Video-Depth-Anything ids (reference utils.py model map; depth.py:875-893): streaming temporal head; max_batch = the number
+    # of independent streams one engine serves (pipeline(streams=...)), 1 = the reference's single stream
     vda = {"depth-anything/Video-Depth-Anything-Small": "vits", "depth-anything/Video-Depth-Anything-Base": "vitb",
            "depth-anything/Video-Depth-Anything-Large": "vitl", "vda_tiny": "tiny", "vda_vits": "vits", "vda_vitb": "vitb",
            "vda_vitl": "vitl"}
@@ -74,8 +75,6 @@ def configure(model="vitb", weights: Optional[Dict[str, np.ndarray]] = None, par
             weights = vda_to_hf({k: v.float().numpy() for k, v in sd.items()}, cfg)
         else:
             weights = load_safetensors(weights, cfg)
-    if temporal and max_batch != 1:
-        raise _lib.D2SError("a Video-Depth-Anything engine is one stream: max_batch must be 1")
     with lock:
         if _state["engine"] is not None:
             _state["engine"].close()
@@ -207,7 +206,9 @@ def predict_depth(image_rgb, return_tuple=False, use_temporal_smooth: bool = Tru
     depth.py:1897-2025).  `dtype` (reference default: DTYPE = float16 with the FP16 setting, else float32; the reference only threads it
     through its XPU retry, depth.py:1959, its result carries the model's dtype): None / float32 return the float32 map the kernels
     produce, float16 / bfloat16 return it cast (what an FP16 reference hands its callers); anything else is a TypeError -- never
-    silently ignored."""
+    silently ignored.
+    One frame per call; on a Video-Depth-Anything engine it is the next frame of stream 0.  `pipeline(frames, streams=...)` is the
+    batched surface (several frames, or several streams, per call)."""
     if dtype is not None and dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise TypeError(f"predict_depth(dtype=...) must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
     p = _state["params"]
@@ -306,9 +307,11 @@ def composite_view(rgb, depth, display_mode, ipd_uv=0.064, depth_ratio=2.0, conv
     return ops.dibr_composite(frames, d.to(device=_device()), dp, display_mode, out_u8=False).cpu().numpy()
 
 
-def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False):
+def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None):
     """Batched predict_depth + make_sbs: uint8 [B,H,W,3] (numpy or device tensor) -> device tensor
-    [B,H',W',3] (uint8, or float32 when out_u8=False) in one stream-ordered native call."""
+    [B,H',W',3] (uint8, or float32 when out_u8=False) in one stream-ordered native call.
+    Video-Depth-Anything: frame r is the next frame of stream `streams[r]` (distinct slots < max_batch; None: streams 0..B-1);
+    only the named streams advance, and use_temporal_smooth keeps one EMA state per stream."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -319,7 +322,18 @@ def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, 
     eng = _ensure_engine_built(h, w, _fp8_first_inputs(t, (h, w)))
     sp = ops.sbs_params(p.ipd, p.depth_strength, p.convergence, display_mode or p.display_mode, p.fill_16_9)
     return eng.pipeline(t, p, sp, use_ema=use_temporal_smooth, out_fmt=_lib.FMT_U8_HWC if out_u8 else _lib.FMT_F32_HWC,
-                        want_depth=want_depth)
+                        want_depth=want_depth, streams=streams)
+
+
+def reset_stream(stream: Optional[int] = None) -> None:
+    """Forget the stream state of the engine (temporal window, pipeline EMA): every stream, or the one slot `stream`."""
+    if stream is None:
+        depth_stabilizer.prev = None
+    eng = _state["engine"]
+    if eng is not None:
+        eng.reset_stream(stream)
+    elif stream is not None and not 0 <= int(stream) < _state["max_batch"]:
+        raise _lib.D2SError(f"reset_stream({stream}): the engine is configured with {_state['max_batch']} stream slot(s)")
 
 
 def pipeline_mixed(frames_list, display_mode=None, out_u8=True):

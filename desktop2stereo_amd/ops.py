@@ -403,7 +403,8 @@ class Engine:
 
     def __init__(self, cfg: ModelConfig, weights: Dict[str, np.ndarray], h: int, w: int, max_batch: int = 1,
                  precision: str = "bf16", device: int = 0, temporal: bool = False, max_depth: float = 0.0):
-        """temporal=True: streaming Video-Depth-Anything (weights from vda_weights; one stream, batch 1).
+        """temporal=True: streaming Video-Depth-Anything (weights from vda_weights); max_batch = the number of independent stream
+        slots (at most 32), each with its own 32-frame window -- see __call__ / pipeline(streams=...).
         max_depth > 0: metric head, sigmoid * max_depth (HF depth_estimation_type "metric")."""
         if not torch.cuda.is_available():
             raise _lib.D2SError("no ROCm device: the HIP engine cannot run (and there is no fallback)")
@@ -437,7 +438,19 @@ class Engine:
         check(self.lib.d2s_engine_memory(self._h, C.byref(b)))
         return b.value
 
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+    @staticmethod
+    def _stream_ids(streams, B: int):
+        """streams=None -> NULL (rows 0..B-1 are streams 0..B-1); else a C int array of B stream slots (the library checks them)."""
+        if streams is None:
+            return None
+        ids = [int(s) for s in streams]
+        if len(ids) != B:
+            raise ValueError(f"streams names {len(ids)} slots for a batch of {B} frames")
+        return (C.c_int * B)(*ids)
+
+    def __call__(self, x: torch.Tensor, streams=None) -> torch.Tensor:
+        """temporal engines: batch row r is the next frame of stream slot streams[r] (distinct slots; None: rows are slots 0..B-1).
+        Only the named streams advance."""
         self._mine(x, "pixel_values")
         x = x.to(torch.float32).contiguous()
         if x.dim() == 3:
@@ -447,7 +460,7 @@ class Engine:
             raise ValueError(f"engine was built for [B,3,{self.h},{self.w}], got {tuple(x.shape)}")
         out = torch.empty((B, self.h, self.w), dtype=torch.float32, device=x.device)
         with _on(self.device) as st:
-            check(self.lib.d2s_model_forward(self._h, _ptr(x), _ptr(out), B, st), "d2s_model_forward")
+            check(self.lib.d2s_model_forward_streams(self._h, _ptr(x), _ptr(out), B, self._stream_ids(streams, B), st), "d2s_model_forward")
         return out
 
     def calibrate(self, x: torch.Tensor):
@@ -483,12 +496,17 @@ class Engine:
         return {self.lib.d2s_profile_class_name(i).decode(): {"ms": ms[i], "flops": fl[i], "bytes": by[i], "launches": cnt[i]}
                 for i in range(nc.value)}
 
-    def reset_stream(self):
-        check(self.lib.d2s_engine_reset_stream(self._h))
+    def reset_stream(self, stream: Optional[int] = None):
+        """Forget the stream state (temporal window, EMA): of every slot, or of the one slot `stream`."""
+        if stream is None:
+            check(self.lib.d2s_engine_reset_stream(self._h))
+        else:
+            check(self.lib.d2s_engine_reset_stream_at(self._h, int(stream)), "d2s_engine_reset_stream_at")
 
     def pipeline(self, frames: torch.Tensor, p: PipelineParams, sp: SbsParams, use_ema: bool = False,
-                 out_fmt: int = FMT_U8_HWC, want_depth: bool = False, out: Optional[torch.Tensor] = None):
-        """predict_depth + make_sbs for uint8 HWC frames [B,H,W,3] in one stream-ordered call."""
+                 out_fmt: int = FMT_U8_HWC, want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
+        """predict_depth + make_sbs for uint8 HWC frames [B,H,W,3] in one stream-ordered call.
+        temporal engines: `streams` as in __call__; use_ema keeps one EMA state per stream slot."""
         self._mine(frames, "frames")
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
             raise ValueError("frames must be uint8 [B,H,W,3]")
@@ -508,8 +526,9 @@ class Engine:
         pp = post_params(p)
         pre = pre_params(p.mean, p.std, p.resample, p.square_input)
         with _on(self.device) as st:
-            check(self.lib.d2s_pipeline(self._h, _ptr(frames), B, H, W, p.depth_resolution, C.byref(pre), C.byref(pp), C.byref(sp),
-                                        int(use_ema), _ptr(out), out_fmt, _ptr(depth) if want_depth else None, st), "d2s_pipeline")
+            check(self.lib.d2s_pipeline_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution, C.byref(pre),
+                                                C.byref(pp), C.byref(sp), int(use_ema), _ptr(out), out_fmt,
+                                                _ptr(depth) if want_depth else None, st), "d2s_pipeline")
         return (out, depth) if want_depth else out
 
     def close(self):

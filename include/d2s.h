@@ -79,7 +79,8 @@ typedef struct d2s_model_desc {
     float   ln_eps;            /* 1e-6 */
     int32_t precision;         /* D2S_PREC_* */
     int32_t temporal;          /* 1: Video-Depth-Anything streaming head (4 temporal modules, 32-frame window; reference
-                                  models/video_depth_anything/vda2_s.py, dpt_temporal.py); batch must be 1 */
+                                  models/video_depth_anything/vda2_s.py, dpt_temporal.py); max_batch = the number of
+                                  independent stream slots, at most D2S_MAX_STREAMS (see d2s_model_forward_streams) */
     float   max_depth;         /* 0: relative head (conv3 -> ReLU).  > 0: metric head, sigmoid(conv3) * max_depth
                                   (HF depth_estimation_type="metric": 20 indoor / 80 outdoor; reference model ids
                                   utils.py:761-769) */
@@ -183,6 +184,9 @@ int d2s_engine_set_weight(d2s_engine* e, const char* name, const float* host,
 /* Fix the model-input shape (cf. _ensure_engine_built, depth.py:1842-1862): h, w multiples of
  * patch; allocates workspaces for up to max_batch frames and pre-interpolates the position
  * embedding (HF Dinov2Embeddings.interpolate_pos_encoding, bicubic).  Synchronous. */
+/* A temporal (Video-Depth-Anything) engine owns max_batch STREAM SLOTS, each with its own 32-frame window; more than this many is
+ * refused (the per-call row table travels in the kernel arguments: 32 rows of 16 bytes). */
+#define D2S_MAX_STREAMS 32
 int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch);
 int d2s_engine_destroy(d2s_engine* e);
 /* bytes of device memory the engine holds (weights + workspaces) */
@@ -229,6 +233,22 @@ int d2s_preprocess(const void* frames, int fmt, int batch, int H, int W,
 /* A5-A9: model(pixel_values=x).predicted_depth  (reference depth.py:1763-1781 -> HF
  * DepthAnythingForDepthEstimation).  x: float [batch,3,h,w]; depth: float [batch,h,w]. */
 int d2s_model_forward(d2s_engine* e, const float* x, float* depth, int batch, void* stream);
+
+/* Several Video-Depth-Anything streams on one engine (d2s_version() >= 112).  A temporal engine finalised with max_batch = N owns
+ * N stream slots 0 .. N-1: per slot one 32-frame window (the rings of projected k' | v' rows of the 8 attention blocks) and, inside
+ * d2s_pipeline_streams, one EMA state.  max_batch = 1 is the single-stream engine.
+ *   - One call carries batch <= N frames and a HOST array stream_ids[batch] of DISTINCT slot indices: batch row r is the next frame of
+ *     stream stream_ids[r].  Only the named streams advance; the others are untouched, so streams may run at different frame
+ *     rates, join and leave.  stream_ids == NULL means rows 0 .. batch-1 are streams 0 .. batch-1: d2s_model_forward / d2s_pipeline
+ *     on a temporal engine are exactly that form.
+ *   - A slot starts fresh: its first frame sees a window of one, then all 31 ring slots hold that frame's rows (the reference's
+ *     update_cache, vda2_s.py:177-218).  d2s_engine_reset_stream_at makes ONE slot fresh again (window and EMA state);
+ *     d2s_engine_reset_stream all of them.  Resetting, feeding or skipping stream i never changes what stream j computes.
+ *   - Duplicate or out-of-range ids, batch > N, a reset of a slot that does not exist: an error status, d2s_last_error() says which,
+ *     and nothing is launched.  On a non-temporal engine a non-NULL stream_ids is refused (its batch rows are not streams).
+ *   - All rows share the engine's model-input shape.  One engine, one caller at a time (as for every entry point). */
+int d2s_model_forward_streams(d2s_engine* e, const float* x, float* depth, int batch, const int* stream_ids, void* stream);
+int d2s_engine_reset_stream_at(d2s_engine* e, int stream_id);
 
 /* D2S_PREC_FP8 engines only: post-training calibration of the static per-tensor activation scales.  Runs one bf16
  * forward over x (float [batch,3,h,w], the engine's input layout) recording max |activation| at the four e4m3
@@ -348,7 +368,12 @@ int d2s_pipeline(d2s_engine* e, const uint8_t* frames, int batch, int H, int W,
                  int depth_resolution, const d2s_pre_params* pre /* NULL: ImageNet constants, CPU-branch resize */,
                  const d2s_post_params* pp, const d2s_sbs_params* sp,
                  int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
-int d2s_engine_reset_stream(d2s_engine* e);
+/* d2s_pipeline with a stream table (see d2s_model_forward_streams).  use_ema on a temporal engine: one DepthStabilizer state per
+ * stream slot, each row updating its own; on a Depth-Anything-v2 engine (stream_ids must be NULL) the in-order chain over the batch. */
+int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                         int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_sbs_params* sp,
+                         int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
+int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the
  * roofline figures; not part of the throughput path).  enable=1 clears the records and starts
