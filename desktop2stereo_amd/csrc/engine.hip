@@ -315,6 +315,17 @@ int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int strid
     return gemm(e, a, w, B * Ho * Wo, ep, st);
 }
 
+// One row's entries of an attention block's two row tables, from its stream slot's window and ring.  THE rule for where a frame's
+// projected k' | v' rows join the window:
+//   fused, filled    the attention kernel overwrites the oldest slot (head) itself, nothing is left for the store launch
+//   unfused, filled  the store launch replaces the oldest slot
+//   fresh            a window of one (the frame itself at position 0); the store launch fills all 31 slots from 0
+void window_rows(const d2s_engine::TSlot& sl, bool fold, void* ring, AttnRow& attn, CacheRow& store) {
+    const bool in_attn = fold && sl.filled;
+    attn = AttnRow{ring, (int16_t)sl.head, (int16_t)(sl.filled ? 32 : 1), in_attn ? sl.head : -1};
+    store = CacheRow{ring, sl.filled ? sl.head : 0, sl.filled ? (in_attn ? 0 : 1) : 31};
+}
+
 // One streaming TemporalModule on NHWC maps x [B][sites, C] -> out; row r is the next frame of stream slot e->row_ids[r] and reads, then
 // updates, that slot's ring caches.  The linears, LayerNorms and GEGLU see M = B sites rows; GroupNorm, the attention and the ring
 // stores are per row.  (reference motion_module.py:102-134, 164-196, 242-321; cache semantics vda2_s.py:177-218)
@@ -322,12 +333,6 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
     d2s_engine::TMod& t = e->tm[m];
     const int C = t.C, S = B * t.sites, prec = e->prec;   // S: rows of every token matrix of this call
     const int* ids = e->row_ids;
-    const d2s_engine::TSlot sl0 = e->tm_slot[ids[0]];
-    const int Tw = sl0.filled ? 32 : 1;                 // (B == 1) first frame: a window of one (the frame itself at position 0)
-    auto ring_of = [&](int a, int r) { return (void*)((char*)t.cache[a] + (size_t)ids[r] * t.ring_bytes); };
-    bool any_fresh = false;
-    double win_rows = 0;                                // sum of the rows' window lengths (attention FLOPs)
-    for (int r = 0; r < B; ++r) { const bool f = e->tm_slot[ids[r]].filled != 0; any_fresh |= !f; win_rows += f ? 32 : 1; }
     // Round 5, bf16 engine (D2S_VDA_FUSE=0 restores round 4's 18 launches per module): (i) the three LayerNorms live in the linears
     // either side of them -- the residual-update GEMM (proj_in, to_out) also leaves the raw residual as bf16 in tm_a and the row
     // statistics in tm_stats, the consumer (kvq, ff1) runs on gamma-folded weights (section 3.1b's algebra, eps 1e-5); (ii) the ring
@@ -355,35 +360,23 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
             if (folded) consumer(ep, t.csum_kvq[a]);
             RC(gemm(e, plainA(e->tm_a, C), folded ? t.kvq_ln[a] : t.kvq[a], S, ep, st));
         }
-        // the frame's projected rows join the window: the first frame fills all 31 slots (its own launch); later frames replace the
-        // oldest slot -- inside the attention kernel when fused
-        const int store_slot = (fold && sl0.filled) ? sl0.head : -1;
-        if (B == 1) {
-            PROF(PC_ATTN, 4.0 * S * Tw * C, 0, launch_temporal_attn(prec, e->tm_kv, ring_of(a, 0), t.ptab[a], e->tm_out, S, C, Tw, 31, sl0.head, st, store_slot));
-        } else {                                        // rows of different streams: per-row ring / head / window / store slot by value
-            AttnRows tab = {};
-            for (int r = 0; r < B; ++r) {
-                const d2s_engine::TSlot sl = e->tm_slot[ids[r]];
-                tab.r[r] = AttnRow{ring_of(a, r), (int16_t)sl.head, (int16_t)(sl.filled ? 32 : 1), (fold && sl.filled) ? sl.head : -1};
-            }
-            PROF(PC_ATTN, 4.0 * t.sites * win_rows * C, 0, launch_temporal_attn_rows(prec, e->tm_kv, t.ptab[a], e->tm_out, t.sites, C, 31, B, tab, st));
+        // the frame's projected rows join the window (window_rows): per-row ring / head / window / store slot by value
+        AttnRows attn = {};
+        CacheRows store = {};
+        double win_rows = 0;                            // sum of the rows' window lengths (attention FLOPs)
+        bool store_due = false;                         // fused: only fresh rows are left to store (their first-frame fill)
+        for (int r = 0; r < B; ++r) {
+            window_rows(e->tm_slot[ids[r]], fold, (char*)t.cache[a] + (size_t)ids[r] * t.ring_bytes, attn.r[r], store.r[r]);
+            win_rows += attn.r[r].Tw;
+            store_due |= store.r[r].nslots > 0;
         }
+        PROF(PC_ATTN, 4.0 * t.sites * win_rows * C, 0, launch_temporal_attn(prec, e->tm_kv, t.ptab[a], e->tm_out, t.sites, C, 31, B, attn, st));
         {
             GemmEpi ep = epi_residual(e->tm_hs, C, t.to_out[a].bias, nullptr);
             producer(ep);
             RC(gemm(e, plainA(e->tm_out, C), t.to_out[a], S, ep, st));
         }
-        if (B == 1) {
-            if (store_slot < 0)
-                PROF(PC_ELT, 0, 0, launch_cache_store(prec, ring_of(a, 0), e->tm_kv, S, C, sl0.filled ? sl0.head : 0, sl0.filled ? 1 : 31, st));
-        } else if (!fold || any_fresh) {                // fused: only the fresh rows are left to store (their first-frame fill)
-            CacheRows tab = {};
-            for (int r = 0; r < B; ++r) {
-                const d2s_engine::TSlot sl = e->tm_slot[ids[r]];
-                tab.r[r] = CacheRow{ring_of(a, r), sl.filled ? sl.head : 0, sl.filled ? (fold ? 0 : 1) : 31};
-            }
-            PROF(PC_ELT, 0, 0, launch_cache_store_rows(prec, e->tm_kv, t.sites, C, B, tab, st));
-        }
+        if (store_due) PROF(PC_ELT, 0, 0, launch_cache_store(prec, e->tm_kv, t.sites, C, B, store, st));
     }
     {
         const bool folded = fold && slots >= 1 && slots <= 16;

@@ -126,21 +126,9 @@ groupnorm_kernel(const T* __restrict__ x, const float* __restrict__ g, const flo
 // 32 x 3C table per attention block.  So a frame projects only its own rows (one [S, C] x [C, 3C] GEMM instead of
 // [32 S, C] x [C, 2C]), and the attention adds the table rows on the fly.
 
-// ring[slot][s][0:2C] = cur[s][0:2C] for slot in [slot0, slot0 + nslots); cur rows are 3C wide (k | v | q)
-template <typename T>
-__global__ void __launch_bounds__(256)
-cache_store_kernel(T* __restrict__ cache, const T* __restrict__ cur, int sites, int C, int slot0, int nslots) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int C2 = 2 * C;
-    long per = (long)sites * C2;
-    if (idx >= per * nslots) return;
-    long r = idx % per;
-    cache[(long)slot0 * per + idx] = cur[(r / C2) * 3 * C + r % C2];
-}
-
-// The same for the rows of a batched call (blockIdx.y = batch row): row r copies its k' | v' rows of cur [rows][S][3C] into slots
-// [slot0, slot0 + nslots) of ITS stream's ring -- 31 slots for a stream's first frame, one (or none) otherwise.  The table travels by
-// value in the kernel arguments and is read with a block-uniform index.
+// ring[slot][s][0:2C] = cur[s][0:2C] for slot in [slot0, slot0 + nslots); cur rows are 3C wide (k | v | q).  blockIdx.y = batch row: row r
+// copies its k' | v' rows of cur [rows][S][3C] into slots [slot0, slot0 + nslots) of ITS stream's ring -- 31 slots for a stream's first
+// frame, one (or none) otherwise.  The table travels by value in the kernel arguments and is read with a block-uniform index.
 template <typename T>
 __global__ void __launch_bounds__(256)
 cache_store_rows_kernel(const T* __restrict__ cur, int sites, int C, const CacheRows tab) {
@@ -186,118 +174,47 @@ template <typename T, int CH> struct RawSeg {
 // KG = 4 key groups own 8 of the 32 window positions each.  Every K' / V' row segment of a head is read once, coalesced (head_dim *
 // sizeof(T) contiguous bytes per key); score partials are xor-reduced over the unit's channel lanes, softmax statistics and the output
 // over its key groups (lanes LPU and 2 LPU apart).
-// cur [S, 3C] (k' | v' | q' of this frame), ring [slots][S][2C] (k' | v' of the past frames, oldest at `head`),
-// ptab [32][3C] float = pe @ [W_k | W_v | W_q]^T.  Window position j < Tw-1 is ring slot (head + j) % slots, j = Tw-1 the
-// current frame (reference motion_module.py:259-300: q from the last position, k / v from all).  out [S, C].
+// cur [rows][S][3C] (k' | v' | q' of this frame; row r is the next frame of ONE stream), that stream's ring [slots][S][2C] (k' | v' of
+// its past frames, oldest at `head`), ptab [32][3C] float = pe @ [W_k | W_v | W_q]^T.  Window position j < Tw-1 is ring slot
+// (head + j) % slots, j = Tw-1 the current frame (reference motion_module.py:259-300: q from the last position, k / v from all).
+// out [rows][S][C]; units = rows * S * 8.
 // Round 5.  Round 4's kernel gave a lane all 32 keys: ~3 500 instructions per lane (32 x 2 row addresses with an integer modulo each,
 // 32 x 3 shuffles, fully unrolled), ONE 4-wave block per CU (194 blocks for a ViT-B stream) -- 19-28 us per launch, 8 launches per
 // frame, and the time did not move when its ring requests were batched 8 / 16 / 32 at a time (variant builds, gpurun_out/r5j): it was
 // bound by its own instruction stream at one wave per SIMD, not by the rings' latency.  Splitting the keys over lanes gives 4 x the
 // threads with ~1/7 of the instructions each: all 16 ring segments of a lane are requested up front, 3+ waves per SIMD cover them.
 constexpr int TA_KG = 4, TA_KPG = 8;           // key groups per unit, keys per group (TA_KG * TA_KPG = the 32-frame window)
-template <typename T, int CH>
-__global__ void __launch_bounds__(256)
-temporal_attn_ring_kernel(const T* __restrict__ cur, T* __restrict__ ring, const float* __restrict__ ptab, T* __restrict__ out,
-                          int sites, int C, int Tw, int slots, int head, float scale, int lpu, int store_slot) {
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int upl = lpu * TA_KG;                                   // lanes per unit (<= 64: a unit never straddles a wave)
-    const int unit = gid / upl, sub = gid % upl, kg = sub / lpu, li = sub % lpu;
-    const bool live = unit < sites * 8;                            // (no early return: the shuffles below need every lane)
-    const int s = live ? unit >> 3 : 0, h = unit & 7, dh = C >> 3, C2 = 2 * C, C3 = 3 * C;
-    const bool act = live && li * CH < dh;                         // lanes beyond the head's channels only take part in shuffles
-    const int c = h * dh + (act ? li * CH : 0);                    // this lane's first channel
-    const T* cur_row = cur + (long)s * C3;
-    // this lane's 8 window positions and their rows (32-bit element offsets: a ring is < 2^31 elements, checked by the launcher);
-    // positions >= Tw (first frame only: Tw = 1) re-read the last valid row and are masked out of the softmax
-    const int slot_stride = sites * C2, base_s = s * C2 + c;
-    const T* krow[TA_KPG];
-    int jpos[TA_KPG];
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) {
-        const int j = kg * TA_KPG + t, jj = min(j, Tw - 1);
-        int slot = head + jj; if (slot >= slots) slot -= slots;    // (head < slots, jj < 32 <= slots + 1: one conditional subtract, no modulo)
-        if (slot >= slots) slot -= slots;
-        krow[t] = (act && jj < Tw - 1) ? ring + (slot * slot_stride + base_s) : cur_row + c;   // (padding / dead lanes never touch the ring: see the store below)
-        jpos[t] = jj;
-    }
-    RawSeg<T, CH> rk[TA_KPG], rv[TA_KPG];
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) rk[t].load(krow[t]);
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) rv[t].load(krow[t] + C);
-    float q[CH];
-    {
-        float pq[CH];
-        load_ch<CH>(cur_row + C2 + c, q);
-        load_ch<CH>(ptab + (long)(Tw - 1) * C3 + C2 + c, pq);
-#pragma unroll
-        for (int i = 0; i < CH; ++i) q[i] = act ? q[i] + pq[i] : 0.f;
-    }
-    float sc[TA_KPG];
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) {
-        float pk[CH];
-        load_ch<CH>(ptab + (long)jpos[t] * C3 + c, pk);
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) a += q[i] * (rk[t].get(i) + pk[i]);
-        for (int o = lpu >> 1; o > 0; o >>= 1) a += __shfl_xor(a, o);
-        sc[t] = kg * TA_KPG + t < Tw ? a * scale : -1e30f;
-    }
-    float mx = -1e30f;
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) mx = fmaxf(mx, sc[t]);
-    mx = fmaxf(mx, __shfl_xor(mx, lpu)); mx = fmaxf(mx, __shfl_xor(mx, 2 * lpu));
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) { sc[t] = kg * TA_KPG + t < Tw ? __expf(sc[t] - mx) : 0.f; sum += sc[t]; }
-    sum += __shfl_xor(sum, lpu); sum += __shfl_xor(sum, 2 * lpu);
-    const float inv = 1.0f / sum;
-    float acc[CH];
-#pragma unroll
-    for (int i = 0; i < CH; ++i) acc[i] = 0.f;
-#pragma unroll
-    for (int t = 0; t < TA_KPG; ++t) {
-        float pv[CH];
-        load_ch<CH>(ptab + (long)jpos[t] * C3 + C + c, pv);
-        const float p = sc[t] * inv;                               // 0 for masked positions
-#pragma unroll
-        for (int i = 0; i < CH; ++i) acc[i] += p * (rv[t].get(i) + pv[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < CH; ++i) { acc[i] += __shfl_xor(acc[i], lpu); acc[i] += __shfl_xor(acc[i], 2 * lpu); }
-    if (act && kg == 0) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) out[(long)s * C + c + i] = tcvt<T>(acc[i]);
-    }
-    // round 5: the frame's k' | v' rows join the window HERE (cache_store_kernel's launch is gone for every frame but the first).  The
-    // oldest slot's segment [c, c + CH) of site s is READ by the key group that owns window position 0 -- kg 0's ACTIVE lane -- and by nobody
-    // else (the padding lanes of a head, li * CH >= head_dim, and the lanes of dead units read the current frame's row instead of the ring:
-    // their q is 0 and they store nothing, but they used to load this segment too -- an unordered read beside the store), so
-    // that lane overwrites it once its own two loads of it are behind it: program order within one thread is all the ordering needed.
-    if (act && kg == 0 && store_slot >= 0) {
-        T* dst = ring + ((long)store_slot * slot_stride + base_s);
-#pragma unroll
-        for (int i = 0; i < CH; ++i) { dst[i] = cur_row[c + i]; dst[C + i] = cur_row[C + c + i]; }
-    }
-}
 
-// The same attention over the rows of a batched call: row r of cur [rows][S][3C] is the next frame of ONE stream with its own ring, oldest
-// slot, window length (1 for a stream's first frame, else 32) and store slot (-1: none).  These come from a by-value table in the kernel
-// arguments (no upload, no dependent launch) and are looked up PER LANE: a 256-thread block usually straddles two rows, and a wave does
-// whenever upl = 16 (C <= 64) and the site count is odd.  A unit never straddles rows, so every shuffle stays inside one row's lanes; a
-// fresh row (Tw = 1) beside a warm one (Tw = 32) differs in masks and addresses only -- no branch encloses a shuffle.
-template <typename T, int CH>
+// Where a lane's window lives.  A Win travels BY VALUE in the kernel arguments (no upload, no dependent launch) and maps a lane's site
+// over all rows, gs, to its row's entry -- ring, oldest slot, window length (1 for a stream's first frame, else 32), store slot (-1: none)
+// -- and the site s inside that row.
+struct WinRow {                                // a call of one row: the entry is wave-uniform, no divide, no table read
+    AttnRow r;
+    __device__ __forceinline__ AttnRow at(int gs, int, int& s) const { s = gs; return r; }
+};
+// Several rows: looked up PER LANE -- a 256-thread block usually straddles two rows, and a wave does whenever upl = 16 (C <= 64) and the
+// site count is odd.  A unit never straddles rows, so every shuffle stays inside one row's lanes; a fresh row (Tw = 1) beside a warm
+// one (Tw = 32) differs in masks and addresses only -- no branch encloses a shuffle.
+struct WinTable {
+    AttnRows t;
+    __device__ __forceinline__ AttnRow at(int gs, int sites, int& s) const {
+        const int row = gs / sites;                                // row < rows <= TA_MAX_ROWS for every lane (dead lanes: row 0)
+        s = gs - row * sites;
+        return t.r[row];
+    }
+};
+
+template <typename T, int CH, typename Win>
 __global__ void __launch_bounds__(256)
-temporal_attn_rows_kernel(const T* __restrict__ cur, const float* __restrict__ ptab, T* __restrict__ out,
-                          int sites, int C, int slots, float scale, int lpu, int rows, const AttnRows tab) {
+temporal_attn_kernel(const T* __restrict__ cur, const float* __restrict__ ptab, T* __restrict__ out,
+                     int sites, int C, int slots, float scale, int lpu, int units, const Win win) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     const int upl = lpu * TA_KG;                                   // lanes per unit (<= 64: a unit never straddles a wave)
     const int unit = gid / upl, sub = gid % upl, kg = sub / lpu, li = sub % lpu;
-    const bool live = unit < rows * sites * 8;                     // (no early return: the shuffles below need every lane)
+    const bool live = unit < units;                                // (no early return: the shuffles below need every lane)
     const int gs = live ? unit >> 3 : 0, h = unit & 7, dh = C >> 3, C2 = 2 * C, C3 = 3 * C;   // gs: site over all rows
-    const int row = gs / sites, s = gs - row * sites;              // row < rows <= TA_MAX_ROWS for every lane (dead lanes: row 0)
-    const AttnRow ar = tab.r[row];                                 // per LANE: a wave holds units of two rows at a row boundary
+    int s;
+    const AttnRow ar = win.at(gs, sites, s);
     T* const ring = (T*)ar.ring;
     const int Tw = ar.Tw, head = ar.head, store_slot = ar.store_slot;
     const bool act = live && li * CH < dh;                         // lanes beyond the head's channels only take part in shuffles
@@ -366,8 +283,12 @@ temporal_attn_rows_kernel(const T* __restrict__ cur, const float* __restrict__ p
 #pragma unroll
         for (int i = 0; i < CH; ++i) out[(long)gs * C + c + i] = tcvt<T>(acc[i]);
     }
-    // the in-kernel ring store, per row: the lane that owns window position 0 of (site, chunk) overwrites the oldest slot of ITS stream's
-    // ring after its own two loads of it -- the single-stream kernel's ordering argument, unchanged (no other lane reads that segment)
+    // round 5: the frame's k' | v' rows join the window HERE, in the row's own ring (the store kernel's launch is gone for every frame but a
+    // stream's first).  The oldest slot's segment [c, c + CH) of site s is READ by the key group that owns window position 0 -- kg 0's ACTIVE
+    // lane -- and by nobody else (the padding lanes of a head, li * CH >= head_dim, and the lanes of dead units read the current frame's row
+    // instead of the ring: their q is 0 and they store nothing, but they used to load this segment too -- an unordered read beside the store,
+    // ADVICE r5), so that lane overwrites it once its own two loads of it are behind it: program order within one thread is all the
+    // ordering needed.  Rows do not change the argument: a row's lanes touch that row's ring only.
     if (act && kg == 0 && store_slot >= 0) {
         T* dst = ring + ((long)store_slot * slot_stride + base_s);
 #pragma unroll
@@ -393,12 +314,6 @@ cast_f32_kernel(const float* __restrict__ in, T* __restrict__ out, long n) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < n) out[idx] = tcvt<T>(in[idx]);
 }
-
-#define TDISPATCH(prec, KERNEL, GRID, ...)                                                                    \
-    do {                                                                                                      \
-        if ((prec) == D2S_PREC_BF16) hipLaunchKernelGGL(KERNEL<bf16_t>, GRID, dim3(256), 0, st, __VA_ARGS__);  \
-        else hipLaunchKernelGGL(KERNEL<float>, GRID, dim3(256), 0, st, __VA_ARGS__);                           \
-    } while (0)
 
 template <typename T>
 static bool launch_groupnorm_reg(const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, int rows, hipStream_t st) {
@@ -430,34 +345,8 @@ int launch_groupnorm(int prec, const void* x, const float* g, const float* b, vo
     return D2S_OK;
 }
 
-int launch_cache_store(int prec, void* cache, const void* cur, int sites, int C, int slot0, int nslots, hipStream_t st) {
-    long total = (long)sites * 2 * C * nslots;
-    if (prec == D2S_PREC_BF16) hipLaunchKernelGGL(cache_store_kernel<bf16_t>, dim3(cdiv(total, 256)), dim3(256), 0, st, (bf16_t*)cache, (const bf16_t*)cur, sites, C, slot0, nslots);
-    else hipLaunchKernelGGL(cache_store_kernel<float>, dim3(cdiv(total, 256)), dim3(256), 0, st, (float*)cache, (const float*)cur, sites, C, slot0, nslots);
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
-}
-
-int launch_temporal_attn(int prec, const void* cur, void* ring, const float* ptab, void* out, int sites, int C, int Tw, int slots,
-                         int head, hipStream_t st, int store_slot) {
-    if (C % 32 || Tw < 1 || Tw > 32) { set_error("temporal_attn: C % 32 == 0 and 1 <= window <= 32 required"); return D2S_E_INVALID; }
-    const float scale = 1.0f / sqrtf((float)(C / 8));
-    const bool ch8 = (C / 8) % 8 == 0;                 // head dim multiple of 8: 16-byte bf16 chunks
-    int lpu = 1;                                       // lanes per (site, head) unit: power of two >= head_dim / chunk
-    while (lpu * (ch8 ? 8 : 4) < C / 8) lpu <<= 1;
-    if (lpu * TA_KG > 64) { set_error("temporal_attn: head dim too large"); return D2S_E_UNSUPPORTED; }
-    if ((long)slots * sites * 2 * C >= (1L << 31) || slots < 31) { set_error("temporal_attn: ring too large for 32-bit offsets (or fewer than 31 slots)"); return D2S_E_UNSUPPORTED; }
-    const dim3 grid(cdiv((long)sites * 8 * lpu * TA_KG, 256)), block(256);
-#define D2S_TATT(TT, CH) hipLaunchKernelGGL((temporal_attn_ring_kernel<TT, CH>), grid, block, 0, st, (const TT*)cur, (TT*)ring, ptab, (TT*)out, \
-                                            sites, C, Tw, slots, head, scale, lpu, store_slot)
-    if (prec == D2S_PREC_BF16) { if (ch8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
-    else { if (ch8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
-#undef D2S_TATT
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
-}
-
-int launch_cache_store_rows(int prec, const void* cur, int sites, int C, int rows, const CacheRows& tab, hipStream_t st) {
+// rows >= 1 batch rows; returns without a launch when no row has slots to fill
+int launch_cache_store(int prec, const void* cur, int sites, int C, int rows, const CacheRows& tab, hipStream_t st) {
     if (rows < 1 || rows > TA_MAX_ROWS) { set_error("cache_store: bad row count"); return D2S_E_INVALID; }
     int most = 0;
     for (int r = 0; r < rows; ++r) most = std::max(most, tab.r[r].nslots);
@@ -469,8 +358,8 @@ int launch_cache_store_rows(int prec, const void* cur, int sites, int C, int row
     return D2S_OK;
 }
 
-int launch_temporal_attn_rows(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
-                              const AttnRows& tab, hipStream_t st) {
+int launch_temporal_attn(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
+                         const AttnRows& tab, hipStream_t st) {
     if (C % 32 || rows < 1 || rows > TA_MAX_ROWS) { set_error("temporal_attn: C % 32 == 0 and 1 <= rows <= 32 required"); return D2S_E_INVALID; }
     for (int r = 0; r < rows; ++r) {
         const AttnRow& a = tab.r[r];
@@ -479,19 +368,23 @@ int launch_temporal_attn_rows(int prec, const void* cur, const float* ptab, void
         }
     }
     const float scale = 1.0f / sqrtf((float)(C / 8));
-    const bool ch8 = (C / 8) % 8 == 0;
-    int lpu = 1;
+    const bool ch8 = (C / 8) % 8 == 0;                 // head dim multiple of 8: 16-byte bf16 chunks
+    int lpu = 1;                                       // lanes per (site, head) unit: power of two >= head_dim / chunk
     while (lpu * (ch8 ? 8 : 4) < C / 8) lpu <<= 1;
     if (lpu * TA_KG > 64) { set_error("temporal_attn: head dim too large"); return D2S_E_UNSUPPORTED; }
-    // (per-stream limit, as in the single-stream launcher: offsets inside ONE ring are 32-bit; rows are reached through 64-bit pointers)
+    // (per-stream limit: offsets inside ONE ring are 32-bit; rows are reached through 64-bit pointers)
     if ((long)slots * sites * 2 * C >= (1L << 31) || slots < 31) { set_error("temporal_attn: ring too large for 32-bit offsets (or fewer than 31 slots)"); return D2S_E_UNSUPPORTED; }
     if ((long)rows * sites * 8 * lpu * TA_KG >= (1L << 31)) { set_error("temporal_attn: too many units"); return D2S_E_UNSUPPORTED; }
-    const dim3 grid(cdiv((long)rows * sites * 8 * lpu * TA_KG, 256)), block(256);
-#define D2S_TATT(TT, CH) hipLaunchKernelGGL((temporal_attn_rows_kernel<TT, CH>), grid, block, 0, st, (const TT*)cur, ptab, (TT*)out, \
-                                            sites, C, slots, scale, lpu, rows, tab)
-    if (prec == D2S_PREC_BF16) { if (ch8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
-    else { if (ch8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
+    const int units = rows * sites * 8;
+    const dim3 grid(cdiv((long)units * lpu * TA_KG, 256)), block(256);
+    auto launch = [&](auto win) {                      // one row: the instance without the per-lane divide and table read
+#define D2S_TATT(TT, CH) hipLaunchKernelGGL((temporal_attn_kernel<TT, CH, decltype(win)>), grid, block, 0, st, (const TT*)cur, ptab, (TT*)out, \
+                                            sites, C, slots, scale, lpu, units, win)
+        if (prec == D2S_PREC_BF16) { if (ch8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
+        else { if (ch8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
 #undef D2S_TATT
+    };
+    if (rows == 1) launch(WinRow{tab.r[0]}); else launch(WinTable{tab});
     D2S_CHECK_LAUNCH();
     return D2S_OK;
 }

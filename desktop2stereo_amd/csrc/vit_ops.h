@@ -35,12 +35,9 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
 // x, out [rows][sites, C]: one normalisation per (row, group)
 int launch_groupnorm(int prec, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st,
                      int rows = 1);
-// cur [S, 3C] = k' | v' | q' of this frame; ring [slots][S][2C] = k' | v' of the past frames; ptab [32][3C] = pe @ W^T
-int launch_cache_store(int prec, void* ring, const void* cur, int sites, int C, int slot0, int nslots, hipStream_t st);
-int launch_temporal_attn(int prec, const void* cur, void* ring, const float* ptab, void* out, int sites, int C, int Tw, int slots,
-                         int head, hipStream_t st, int store_slot = -1 /* >= 0: also write this frame's k' | v' rows into that ring slot */);
-// Several streams in one call (a temporal engine with max_batch > 1): batch row r is the next frame of one stream.  What differs
-// per row travels BY VALUE in the kernel arguments -- TA_MAX_ROWS entries of 16 bytes -- so a call needs no upload and no extra launch.
+// cur [rows][S][3C] = k' | v' | q' of this frame, batch row r = the next frame of one stream; that stream's ring [slots][S][2C] = k' | v' of
+// its past frames; ptab [32][3C] = pe @ W^T.  What differs per row travels BY VALUE in the kernel arguments -- TA_MAX_ROWS entries of
+// 16 bytes -- so a call needs no upload and no extra launch.
 constexpr int TA_MAX_ROWS = D2S_MAX_STREAMS;
 struct AttnRow { void* ring; int16_t head, Tw; int32_t store_slot; };      // the stream's ring, its oldest slot, window 1 | 32, slot to fill or -1
 struct AttnRows { AttnRow r[TA_MAX_ROWS]; };
@@ -49,9 +46,9 @@ struct CacheRows { CacheRow r[TA_MAX_ROWS]; };
 struct EmaRow { int32_t slot, initialised; };
 struct EmaRows { EmaRow r[TA_MAX_ROWS]; };
 static_assert(sizeof(AttnRow) == 16 && sizeof(CacheRow) == 16, "row tables are 16 bytes per row");
-int launch_cache_store_rows(int prec, const void* cur, int sites, int C, int rows, const CacheRows& tab, hipStream_t st);
-int launch_temporal_attn_rows(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
-                              const AttnRows& tab, hipStream_t st);
+int launch_cache_store(int prec, const void* cur, int sites, int C, int rows, const CacheRows& tab, hipStream_t st);
+int launch_temporal_attn(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
+                         const AttnRows& tab, hipStream_t st);
 int launch_geglu(int prec, const void* u, void* g, long rows, int C4, hipStream_t st);
 int launch_cast_f32(int prec, const float* in, void* out, long n, hipStream_t st);
 
