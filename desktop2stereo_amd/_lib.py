@@ -119,6 +119,8 @@ SYMBOLS = {
     "d2s_dibr_warp": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), _P, C.c_int, _P]),
     "d2s_dibr_composite_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "d2s_dibr_composite": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, _P, C.c_int, _P]),
+    "d2s_dibr_warp_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), _P, C.c_int, _P]),
+    "d2s_dibr_composite_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, _P, C.c_int, _P]),
     "d2s_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "d2s_jpeg_encode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "d2s_present_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
@@ -134,6 +136,8 @@ SYMBOLS = {
                                C.POINTER(SbsParams), C.c_int, _P, C.c_int, _P, _P]),
     "d2s_pipeline_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                        C.POINTER(PostParams), C.POINTER(SbsParams), C.c_int, _P, C.c_int, _P, _P]),
+    "d2s_view_pipeline_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "d2s_engine_reset_stream": (C.c_int, [_P]),
     "d2s_engine_tap": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "d2s_engine_profile": (C.c_int, [_P, C.c_int]),

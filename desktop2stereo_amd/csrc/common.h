@@ -213,6 +213,20 @@ __device__ static inline float bilerp1(const Tap& tx, const Tap& ty, float v00, 
     const float bot = fmaf(tx.w1, v11, tx.w0 * v10);
     return fmaf(ty.w1, bot, ty.w0 * top);
 }
+// One texel of the depth up-sample (A13, align_corners = False): what upsample_depth_kernel (frame_ops.hip) stores, and what the
+// DIBR kernels' model-resolution depth source (dibr_tex.h UpDep) evaluates in place of reading that store -- one expression for
+// both, products and sums rounded separately whatever the including file's contraction setting is.  r0 / r1: the two source rows
+// (ty.i0, ty.i1) of the [h, w] map.
+__device__ static inline float upsample_texel_rows(const float* __restrict__ r0, const float* __restrict__ r1, const Tap& ty, const Tap& tx) {
+#pragma clang fp contract(off)
+    float top = tx.w0 * r0[tx.i0] + tx.w1 * r0[tx.i1];
+    float bot = tx.w0 * r1[tx.i0] + tx.w1 * r1[tx.i1];
+    return ty.w0 * top + ty.w1 * bot;
+}
+__device__ static inline float upsample_texel(const float* __restrict__ p, int h, int w, float sy, float sx, int y, int x) {
+    const Tap ty = linear_tap(y, sy, h, false), tx = linear_tap(x, sx, w, false);
+    return upsample_texel_rows(p + ty.i0 * w, p + ty.i1 * w, ty, tx);
+}
 static inline float linear_scale(int in_size, int out_size, bool align_corners) {
     if (align_corners) return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
     return (float)in_size / (float)out_size;

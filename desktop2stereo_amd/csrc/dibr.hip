@@ -171,26 +171,26 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const DibrGeom& g, int 
 // General kernel: one thread = one output pixel of one eye, every tap a global gather.  (4 pixels per thread with packed dword
 // stores measured SLOWER -- 113 -> 120 us Full-SBS, 38 -> 97 us Half-SBS at 1080p: this kernel lives on the locality of neighbouring
 // threads' gathers, not on its stores.)  ROLL0: the row pair of a pixel formed once (104.5 -> 89.5 us Full-SBS 1080p, same bits).
-template <int OUT_FMT, bool ROLL0>
+template <int OUT_FMT, bool ROLL0, class D = FullDep>
 __global__ void __launch_bounds__(256)
 dibr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, DibrGeom g) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y % g.oh, eye = blockIdx.y / g.oh, b = blockIdx.z;
     if (x >= g.ow) return;
     const uint8_t* rgb = rgb_all + (long)b * g.H * g.W * 3;
-    const float* dep = dep_all + (long)b * g.H * g.W;
+    const D dep = D::make(dep_all, b, g);
     const bool sbs = g.mode == D2S_MODE_HALF_SBS || g.mode == D2S_MODE_FULL_SBS;
     const int ox = sbs ? eye * g.ow + x : x, oy = sbs ? y : eye * g.oh + y;
     const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
     const long o = (((long)b * g.out_h + oy) * g.out_w + ox) * nch;
     float c[4];
     if constexpr (ROLL0) {
-        RowSmp smp;
+        RowSmp<D> smp;
         smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
         smp.rc = row_ctx(dep, g.H, g.W, ((float)y + 0.5f) / (float)g.oh);     // (the v dibr_pixel forms)
         dibr_pixel(smp, g, x, y, eye, c);
     } else {
-        GenSmp smp;
+        GenSmp<D> smp;
         smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
         dibr_pixel(smp, g, x, y, eye, c);
     }
@@ -208,7 +208,9 @@ dibr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_a
 #endif
 // COLS (round 6): output columns per block, 256 per thread-pass.  The second pass costs one mostly-empty wave per block that has
 // queued pixels whatever their number; a block twice as wide halves those waves (and stages a window 2 x as wide once).
-template <int OUT_FMT, bool FX, int COLS>
+// D = UpDep: the staging loop evaluates the two depth texels of a window entry from the model-resolution map (four source values
+// each, L2-resident) instead of loading them; everything after the barrier runs on the staged values as it does for FullDep.
+template <int OUT_FMT, bool FX, int COLS, class D = FullDep>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIBR_WAVES)))
 dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, DibrGeom g, int margin, int WW) {
     extern __shared__ float dibr_win[];                // [2][WW] the row pair of the depth texture | [6][WW] R0 G0 B0 R1 G1 B1 as floats
@@ -216,9 +218,9 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
     const int tid = threadIdx.x, xb = blockIdx.x * COLS;
     const int y = blockIdx.y, b = blockIdx.z;
     const uint8_t* rgb = rgb_all + (long)b * g.H * g.W * 3;
-    const float* dep = dep_all + (long)b * g.H * g.W;
+    const D dep = D::make(dep_all, b, g);
     if (tid == 0) qn = 0;
-    WinSmp smp;
+    WinSmp<D> smp;
     smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
     smp.rc = row_ctx(dep, g.H, g.W, ((float)y + 0.5f) / (float)g.oh);         // block-uniform (the v dibr_pixel forms)
     smp.dwin = dibr_win; smp.cwin = dibr_win + 2 * WW; smp.WW = WW;
@@ -231,8 +233,10 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
     for (int j = tid; j < WW; j += 256) {
 #endif
         const int xs = wrapi(smp.wx0 + j, g.W);        // (one conditional add / subtract unless the window is wider than the texture: then the modulo)
-        dibr_win[j] = smp.rc.d0[xs];
-        dibr_win[WW + j] = smp.rc.d1[xs];
+        float da, db;
+        dep.pair(smp.rc.d, xs, da, db);
+        dibr_win[j] = da;
+        dibr_win[WW + j] = db;
         const uint8_t* p0 = rgb + smp.rc.c0 + xs * 3;
         const uint8_t* p1 = rgb + smp.rc.c1 + xs * 3;
 #pragma unroll
@@ -294,6 +298,9 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
     }
 }
 
+int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                  void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
+
 }  // namespace d2s
 
 using namespace d2s;
@@ -306,18 +313,23 @@ extern "C" int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* o
     return D2S_OK;
 }
 
-extern "C" int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
-                             void* out, int out_fmt, void* stream) {
+// d2s_dibr_warp (dh == H && dw == W: depth IS the texture, the FullDep kernels) and d2s_dibr_warp_depth (any other [dh, dw]: the
+// UpDep kernels).  Every argument is checked before any HIP call.
+int d2s::dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                       void* out, int out_fmt, void* stream, bool check_only) {
     D2S_REQUIRE(rgb && depth && p && out, "null pointer");
     D2S_REQUIRE(p->struct_size == sizeof(d2s_dibr_params),
                 "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80 (header of d2s_version() >= 110; the 72-byte struct of "
                 "version 100 has no alpha_mode)");
     D2S_REQUIRE(batch > 0 && H > 1 && W > 1, "bad shape");
-    D2S_REQUIRE((long)H * W * 3 + 8 < (1L << 31), "frame too large (32-bit texel indices)");
+    D2S_REQUIRE(dh > 0 && dw > 0, "bad depth shape (dh, dw > 0)");
+    D2S_REQUIRE((long)H * W * 3 + 8 < (1L << 31) && (long)dh * dw < (1L << 31), "frame too large (32-bit texel indices)");
     D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC, "bad out_fmt (U8_HWC or F32_HWC)");
     D2S_REQUIRE(p->search_radius >= 0.f && p->search_radius < 16.f, "search_radius must be in [0,16)");
     DibrGeom g;
     g.H = H; g.W = W; g.mode = p->display_mode;
+    const bool up = dh != H || dw != W;
+    g.dh = dh; g.dw = dw; g.dsy = linear_scale(dh, H, false); g.dsx = linear_scale(dw, W, false);      // (d2s_upsample_depth's scales)
     int rc = d2s_dibr_shape(H, W, p->display_mode, &g.out_h, &g.out_w);
     if (rc) return rc;
     g.oh = p->display_mode == D2S_MODE_HALF_TAB ? H / 2 : H;
@@ -340,6 +352,7 @@ extern "C" int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, 
     g.vpw = vp0 ? (float)g.ow : p->viewport[2]; g.vph = vp0 ? (float)g.oh : p->viewport[3];
     for (int i = 0; i < 20; ++i) { g.w1[i] = i < 16 ? expf((float)(-i * 0.15)) : 0.f; g.w2[i] = i < 16 ? expf((float)(-i * 0.2)) : 0.f; }
     D2S_REQUIRE(2 * g.oh <= 65535 && batch <= 65535, "frame / batch too large for one launch");
+    if (check_only) return D2S_OK;
     dim3 grid(cdiv(g.ow, 256), 2 * g.oh, batch), block(256);
     static EnvInt no_roll0{"D2S_DIBR_NO_ROLL0", 0};        // (A/B aids: the general per-tap evaluation for roll == 0 too;
     static EnvInt no_rows{"D2S_DIBR_NO_ROWS", 0};          //  the gather kernel instead of the LDS-window kernel)
@@ -356,26 +369,40 @@ extern "C" int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, 
         // 50.8 -> 46.8 us (half the second-pass waves); Half-SBS (two source texels per column) keeps 256: 24.4 us against 26.8;
         // 1024 columns: 63.9 us (34 KB per block).  D2S_DIBR_COLS = 256 | 512 | 1024 caps it (A/B aid).
         static EnvInt cols_env{"D2S_DIBR_COLS", 512};
-        int cols = cols_env.get() >= 1024 ? 1024 : (cols_env.get() >= 512 ? 512 : 256);
+        const bool wide = cols_env.get() >= 1024 && !up;       // (1024 columns is an A/B aid of the FullDep kernels only)
+        int cols = wide ? 1024 : (cols_env.get() >= 512 ? 512 : 256);
         auto win_words = [&](int c) { return (int)ceil((double)(c - 1) * (double)W / (double)g.ow) + 2 * margin + 4; };
-        while (cols > 256 && (win_words(cols) > (cols_env.get() >= 1024 ? 1536 : 640) || g.ow <= cols / 2)) cols >>= 1;   // (1536: 48 KB + the queue stay under 64 KB)
+        while (cols > 256 && (win_words(cols) > (wide ? 1536 : 640) || g.ow <= cols / 2)) cols >>= 1;   // (1536: 48 KB + the queue stay under 64 KB)
         const int WWc = win_words(cols);
         dim3 rgrid(cdiv(g.ow, cols), g.oh, batch);
         const size_t lds = (size_t)8 * WWc * sizeof(float);
         const bool fx = g.feather || g.corner_r > 0.f;
-#define DIBR_ROWS(FMT, FXV, COLS) hipLaunchKernelGGL((dibr_rows_kernel<FMT, FXV, COLS>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, g, margin, WWc)
-#define DIBR_ROWS_C(FMT, FXV) do { if (cols == 1024) DIBR_ROWS(FMT, FXV, 1024); else if (cols == 512) DIBR_ROWS(FMT, FXV, 512); else DIBR_ROWS(FMT, FXV, 256); } while (0)
+#define DIBR_ROWS(FMT, FXV, COLS, D) hipLaunchKernelGGL((dibr_rows_kernel<FMT, FXV, COLS, D>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, g, margin, WWc)
+#define DIBR_ROWS_C(FMT, FXV) do { if (up) { if (cols == 512) DIBR_ROWS(FMT, FXV, 512, UpDep); else DIBR_ROWS(FMT, FXV, 256, UpDep); } \
+                                   else if (cols == 1024) DIBR_ROWS(FMT, FXV, 1024, FullDep); else if (cols == 512) DIBR_ROWS(FMT, FXV, 512, FullDep); \
+                                   else DIBR_ROWS(FMT, FXV, 256, FullDep); } while (0)
         if (out_fmt == D2S_FMT_U8_HWC) { if (fx) DIBR_ROWS_C(D2S_FMT_U8_HWC, true); else DIBR_ROWS_C(D2S_FMT_U8_HWC, false); }
         else { if (fx) DIBR_ROWS_C(D2S_FMT_F32_HWC, true); else DIBR_ROWS_C(D2S_FMT_F32_HWC, false); }
 #undef DIBR_ROWS_C
 #undef DIBR_ROWS
-    } else if (out_fmt == D2S_FMT_U8_HWC) {
-        if (roll0) hipLaunchKernelGGL((dibr_kernel<D2S_FMT_U8_HWC, true>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g);
-        else hipLaunchKernelGGL((dibr_kernel<D2S_FMT_U8_HWC, false>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g);
     } else {
-        if (roll0) hipLaunchKernelGGL((dibr_kernel<D2S_FMT_F32_HWC, true>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g);
-        else hipLaunchKernelGGL((dibr_kernel<D2S_FMT_F32_HWC, false>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g);
+#define DIBR_GEN(FMT, R0, D) hipLaunchKernelGGL((dibr_kernel<FMT, R0, D>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g)
+#define DIBR_GEN_D(FMT, R0) do { if (up) DIBR_GEN(FMT, R0, UpDep); else DIBR_GEN(FMT, R0, FullDep); } while (0)
+        if (out_fmt == D2S_FMT_U8_HWC) { if (roll0) DIBR_GEN_D(D2S_FMT_U8_HWC, true); else DIBR_GEN_D(D2S_FMT_U8_HWC, false); }
+        else { if (roll0) DIBR_GEN_D(D2S_FMT_F32_HWC, true); else DIBR_GEN_D(D2S_FMT_F32_HWC, false); }
+#undef DIBR_GEN_D
+#undef DIBR_GEN
     }
     D2S_CHECK_LAUNCH();
     return D2S_OK;
+}
+
+extern "C" int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
+                             void* out, int out_fmt, void* stream) {
+    return dibr_warp_any(rgb, depth, H, W, batch, H, W, p, out, out_fmt, stream, false);
+}
+
+extern "C" int d2s_dibr_warp_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                   const d2s_dibr_params* p, void* out, int out_fmt, void* stream) {
+    return dibr_warp_any(rgb, depth, dh, dw, batch, H, W, p, out, out_fmt, stream, false);
 }

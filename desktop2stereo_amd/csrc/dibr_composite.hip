@@ -6,6 +6,7 @@
 // Line numbers in the comments are viewer.py.
 #include "dibr_tex.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace d2s {
 
@@ -183,7 +184,8 @@ __device__ __forceinline__ bool comp_pixel(const S& smp, const CompGeom& G, int 
 // The queue is filled per wave -- one LDS atomic per wave that has queued fragments, slots by lane rank -- instead of one returning
 // atomic per fragment on the same address.  COLS = 512 (two columns per thread) halves the mostly-empty second-pass waves, as
 // for f1 (dibr.hip: 50.8 -> 46.8 us at 1080p Full-SBS).
-template <int MODE, int OUT_FMT, bool FX, int COLS>
+// D = UpDep: the depth rows of the window are evaluated from the model-resolution map by the staging loop (dibr.hip).
+template <int MODE, int OUT_FMT, bool FX, int COLS, class D = FullDep>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7)))
 comp_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, CompGeom G, int margin, int WW) {
     extern __shared__ float comp_win[];                // [2][WW] depth row pair | [6][WW] R0 G0 B0 R1 G1 B1 as floats
@@ -192,17 +194,19 @@ comp_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
     const int tid = threadIdx.x, xb = blockIdx.x * COLS;
     const int y = blockIdx.y, b = blockIdx.z;
     const uint8_t* rgb = rgb_all + (long)b * g.H * g.W * 3;
-    const float* dep = dep_all + (long)b * g.H * g.W;
+    const D dep = D::make(dep_all, b, g);
     if (tid == 0) qn = 0;
-    WinSmp smp;
+    WinSmp<D> smp;
     smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
     smp.rc = row_ctx(dep, g.H, g.W, ((float)y + 0.5f) / (float)g.oh);         // block-uniform (the v the pixel functions form)
     smp.dwin = comp_win; smp.cwin = comp_win + 2 * WW; smp.WW = WW;
     smp.wx0 = (int)floorf((((float)xb + 0.5f) / (float)g.ow) * (float)g.W - 0.5f) - margin;
     for (int j = tid; j < WW; j += 256) {
         const int xs = wrapi(smp.wx0 + j, g.W);
-        comp_win[j] = smp.rc.d0[xs];
-        comp_win[WW + j] = smp.rc.d1[xs];
+        float da, db;
+        dep.pair(smp.rc.d, xs, da, db);
+        comp_win[j] = da;
+        comp_win[WW + j] = db;
         const uint8_t* p0 = rgb + smp.rc.c0 + xs * 3;
         const uint8_t* p1 = rgb + smp.rc.c1 + xs * 3;
 #pragma unroll
@@ -238,23 +242,23 @@ comp_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
 }
 
 // Any roll (the OpenXR screen), or a window too wide for LDS: one thread = one fragment, every tap a global gather.
-template <int MODE, int OUT_FMT, bool ROLL0>
+template <int MODE, int OUT_FMT, bool ROLL0, class D = FullDep>
 __global__ void __launch_bounds__(256)
 comp_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, CompGeom G) {
     const DibrGeom& g = G.g;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
     if (x >= g.ow) return;
     const uint8_t* rgb = rgb_all + (long)b * g.H * g.W * 3;
-    const float* dep = dep_all + (long)b * g.H * g.W;
+    const D dep = D::make(dep_all, b, g);
     const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
     float c[4];
     if constexpr (ROLL0) {
-        RowSmp smp;
+        RowSmp<D> smp;
         smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
         smp.rc = row_ctx(dep, g.H, g.W, ((float)y + 0.5f) / (float)g.oh);
         comp_pixel<MODE, false, true>(smp, G, x, y, c);
     } else {
-        GenSmp smp;
+        GenSmp<D> smp;
         smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
         comp_pixel<MODE, false, true>(smp, G, x, y, c);
     }
@@ -277,9 +281,11 @@ __device__ __forceinline__ void spectral(float t, float o[3]) {
 // Depth Map: element-wise and byte-bound.  A thread = 4 consecutive output pixels of the flattened [batch, h, w] output: one bilinear
 // depth tap each (8-byte row loads; the viewport may differ from the source), stored as one 12 / 16-byte (u8: 3 / 4 channels) or
 // 48 / 64-byte (f32) vector store.  VEC = false: an output pointer not 16-byte aligned, byte / float stores.
-template <int OUT_FMT, int NCH, bool VEC>
+// D = UpDep (up = the [dh, dw] map and its scales): the tap's four texels are evaluated from the model-resolution map.
+struct UpArgs { int dh, dw; float sy, sx; };
+template <int OUT_FMT, int NCH, bool VEC, class D = FullDep>
 __global__ void __launch_bounds__(256)
-depth_map_kernel(const float* __restrict__ dep_all, void* __restrict__ out_all, int H, int W, int oh, int ow, long npix) {
+depth_map_kernel(const float* __restrict__ dep_all, void* __restrict__ out_all, int H, int W, int oh, int ow, long npix, UpArgs up) {
     const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (p0 >= npix) return;
     const long img = (long)oh * ow;
@@ -290,7 +296,10 @@ depth_map_kernel(const float* __restrict__ dep_all, void* __restrict__ out_all, 
     for (int k = 0; k < 4; ++k) {
         // the last thread's pixels past npix would index frame b == batch, which does not exist: no taps for them (never stored)
         if (p0 + k < npix) {
-            const float t = tex_depth(dep_all + b * H * W, H, W, ((float)c + 0.5f) / (float)ow, ((float)r + 0.5f) / (float)oh);
+            const float cu = ((float)c + 0.5f) / (float)ow, cv = ((float)r + 0.5f) / (float)oh;
+            float t;
+            if constexpr (std::is_same<D, UpDep>::value) t = tex_depth(UpDep{dep_all + b * up.dh * up.dw, up.dh, up.dw, up.sy, up.sx}, H, W, cu, cv);
+            else t = tex_depth(dep_all + b * H * W, H, W, cu, cv);
             spectral(t, v[k]);
             v[k][3] = 1.0f;
         }
@@ -335,6 +344,9 @@ static int comp_viewport(int H, int W, const d2s_dibr_params* p, int* vx, int* v
     return D2S_OK;
 }
 
+int dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                       int composite, void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
+
 }  // namespace d2s
 
 using namespace d2s;
@@ -350,8 +362,9 @@ extern "C" int d2s_dibr_composite_shape(int H, int W, const d2s_dibr_params* p, 
     return D2S_OK;
 }
 
-extern "C" int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
-                                  int composite, void* out, int out_fmt, void* stream) {
+// d2s_dibr_composite (dh == H && dw == W: depth IS the texture) and d2s_dibr_composite_depth (any other [dh, dw]: the UpDep kernels)
+int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                            int composite, void* out, int out_fmt, void* stream, bool check_only) {
     D2S_REQUIRE(depth && p && out, "null pointer");
     D2S_REQUIRE(p->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     D2S_REQUIRE(composite >= D2S_COMPOSITE_ANAGLYPH && composite <= D2S_COMPOSITE_DEPTH_MAP, "bad composite (D2S_COMPOSITE_*)");
@@ -366,22 +379,30 @@ extern "C" int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int ba
     int vw, vh;
     int rc = comp_viewport(H, W, p, &G.vx, &G.vy, &vw, &vh);
     if (rc) return rc;
+    D2S_REQUIRE(dh > 0 && dw > 0 && (long)dh * dw < (1L << 31), "bad depth shape (dh, dw > 0)");
     const int nch = p->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    const bool up = dh != H || dw != W;
+    const UpArgs ua = {dh, dw, linear_scale(dh, H, false), linear_scale(dw, W, false)};      // (d2s_upsample_depth's scales)
     if (composite == D2S_COMPOSITE_DEPTH_MAP) {
         const long npix = (long)batch * vh * vw;
         D2S_REQUIRE(cdiv(npix, 1024L) < (1L << 31), "output too large for one launch");
+        if (check_only) return D2S_OK;
         dim3 grid((unsigned)cdiv(npix, 1024L)), block(256);
         const bool vec = ((uintptr_t)out & 15) == 0;
-#define DM(FMT, N, V) hipLaunchKernelGGL((depth_map_kernel<FMT, N, V>), grid, block, 0, (hipStream_t)stream, depth, out, H, W, vh, vw, npix)
-#define DM_V(FMT, N) do { if (vec) DM(FMT, N, true); else DM(FMT, N, false); } while (0)
+#define DM(FMT, N, V, D) hipLaunchKernelGGL((depth_map_kernel<FMT, N, V, D>), grid, block, 0, (hipStream_t)stream, depth, out, H, W, vh, vw, npix, ua)
+#define DM_D(FMT, N, V) do { if (up) DM(FMT, N, V, UpDep); else DM(FMT, N, V, FullDep); } while (0)
+#define DM_V(FMT, N) do { if (vec) DM_D(FMT, N, true); else DM_D(FMT, N, false); } while (0)
         if (out_fmt == D2S_FMT_U8_HWC) { if (nch == 4) DM_V(D2S_FMT_U8_HWC, 4); else DM_V(D2S_FMT_U8_HWC, 3); }
         else { if (nch == 4) DM_V(D2S_FMT_F32_HWC, 4); else DM_V(D2S_FMT_F32_HWC, 3); }
 #undef DM_V
+#undef DM_D
 #undef DM
         D2S_CHECK_LAUNCH();
         return D2S_OK;
     }
+    if (check_only) return D2S_OK;
     g.H = H; g.W = W; g.oh = vh; g.ow = vw;
+    g.dh = ua.dh; g.dw = ua.dw; g.dsy = ua.sy; g.dsx = ua.sx;
     g.mode = -1; g.out_h = vh; g.out_w = vw;
     g.c = cosf(p->roll); g.s = sinf(p->roll);
     g.psx = 1.0f / (p->res_w > 0.f ? p->res_w : (float)W);
@@ -410,9 +431,10 @@ extern "C" int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int ba
     if (roll0 && WW <= 1536) {                        // (8 planes x 1536 floats = 48 KB + the queue)
         const size_t lds = (size_t)8 * WW * sizeof(float);
         dim3 rgrid(cdiv(vw, cols), vh, batch);
-#define CR(M, FMT, FXV) do { if (cols == 512) hipLaunchKernelGGL((comp_rows_kernel<M, FMT, FXV, 512>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, G, margin, WW); \
-                             else hipLaunchKernelGGL((comp_rows_kernel<M, FMT, FXV, 256>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, G, margin, WW); } while (0)
-#define CR_F(M, FMT) do { if (fx) CR(M, FMT, true); else CR(M, FMT, false); } while (0)
+#define CR_K(M, FMT, FXV, COLS, D) hipLaunchKernelGGL((comp_rows_kernel<M, FMT, FXV, COLS, D>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, G, margin, WW)
+#define CR(M, FMT, FXV, D) do { if (cols == 512) CR_K(M, FMT, FXV, 512, D); else CR_K(M, FMT, FXV, 256, D); } while (0)
+#define CR_F(M, FMT) do { if (up) { if (fx) CR(M, FMT, true, UpDep); else CR(M, FMT, false, UpDep); } \
+                          else if (fx) CR(M, FMT, true, FullDep); else CR(M, FMT, false, FullDep); } while (0)
 #define CR_M(FMT) do { if (composite == D2S_COMPOSITE_ANAGLYPH) CR_F(D2S_COMPOSITE_ANAGLYPH, FMT); \
                        else if (composite == D2S_COMPOSITE_INTERLEAVED) CR_F(D2S_COMPOSITE_INTERLEAVED, FMT); \
                        else CR_F(D2S_COMPOSITE_INTERLEAVED_V, FMT); } while (0)
@@ -420,9 +442,11 @@ extern "C" int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int ba
 #undef CR_M
 #undef CR_F
 #undef CR
+#undef CR_K
     } else {
-#define CG(M, FMT, R0) hipLaunchKernelGGL((comp_kernel<M, FMT, R0>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, G)
-#define CG_R(M, FMT) do { if (roll0) CG(M, FMT, true); else CG(M, FMT, false); } while (0)
+#define CG(M, FMT, R0, D) hipLaunchKernelGGL((comp_kernel<M, FMT, R0, D>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, G)
+#define CG_R(M, FMT) do { if (up) { if (roll0) CG(M, FMT, true, UpDep); else CG(M, FMT, false, UpDep); } \
+                          else if (roll0) CG(M, FMT, true, FullDep); else CG(M, FMT, false, FullDep); } while (0)
 #define CG_M(FMT) do { if (composite == D2S_COMPOSITE_ANAGLYPH) CG_R(D2S_COMPOSITE_ANAGLYPH, FMT); \
                        else if (composite == D2S_COMPOSITE_INTERLEAVED) CG_R(D2S_COMPOSITE_INTERLEAVED, FMT); \
                        else CG_R(D2S_COMPOSITE_INTERLEAVED_V, FMT); } while (0)
@@ -433,4 +457,14 @@ extern "C" int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int ba
     }
     D2S_CHECK_LAUNCH();
     return D2S_OK;
+}
+
+extern "C" int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
+                                  int composite, void* out, int out_fmt, void* stream) {
+    return dibr_composite_any(rgb, depth, H, W, batch, H, W, p, composite, out, out_fmt, stream, false);
+}
+
+extern "C" int d2s_dibr_composite_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                        const d2s_dibr_params* p, int composite, void* out, int out_fmt, void* stream) {
+    return dibr_composite_any(rgb, depth, dh, dw, batch, H, W, p, composite, out, out_fmt, stream, false);
 }

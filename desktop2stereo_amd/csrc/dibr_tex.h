@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace d2s {
 
@@ -20,6 +21,8 @@ struct DibrGeom {
     int alpha_mode;        // D2S_DIBR_ALPHA_*
     float corner_r, vpx, vpy, vpw, vph;             // u_corner_radius; u_viewport in eye-image pixels (y up)
     float w1[20], w2[20];  // exp(-i*0.15), exp(-i*0.2), i < 16 (the sweeps index in groups of four: up to [16..18], never used)
+    int dh, dw;            // UpDep only: the [dh, dw] map the H x W depth texture is up-sampled from, and its scales
+    float dsy, dsx;        //   linear_scale(dh, H, false), linear_scale(dw, W, false) as d2s_upsample_depth forms them
 };
 
 // GL_REPEAT index: one conditional add / subtract covers every coordinate within one period of the texture (all but
@@ -45,6 +48,46 @@ __device__ __forceinline__ float lerp2(float a, float b, float c, float d, float
     float top = a + (b - a) * fx, bot = c + (d - c) * fx;
     return top + (bot - top) * fy;
 }
+// Where a texel of the H x W depth texture comes from -- a template parameter of the samplers and kernels below.
+//   FullDep: the texture itself, float [H, W] in memory (d2s_dibr_warp / d2s_dibr_composite).
+//   UpDep:   a [dh, dw] map at model resolution (d2s_dibr_*_depth, d2s_view_pipeline_streams).  Texel (y, x) is the value
+//            upsample_depth_kernel would have stored there (common.h upsample_texel: the same linear_tap calls, the same
+//            w0 * a + w1 * b order, no contraction), so every filtered tap -- lerp2 over four texels, as FullDep's -- has the bits
+//            of the two-call form without the full-resolution map ever existing.  The 0.6 MB map stays in L2.
+// Row: the depth half of a texture row pair (y0, y1); pair(): texels (y0, x) and (y1, x).
+struct FullDep {
+    const float* dep;
+    struct Row { const float* d0; const float* d1; };
+    __device__ __forceinline__ static FullDep make(const float* dep_all, int b, const DibrGeom& g) { return FullDep{dep_all + (long)b * g.H * g.W}; }
+    __device__ __forceinline__ Row row(int y0, int y1, int W) const { return Row{dep + y0 * W, dep + y1 * W}; }
+    __device__ __forceinline__ void pair(const Row& r, int x, float& a, float& b) const { a = r.d0[x]; b = r.d1[x]; }
+};
+// Orders two on-demand texel evaluations: x becomes available only once `after` exists.  Left to itself the compiler requests the
+// 16 (a row tap) or 32 (the two vertical-blur taps) source loads of the rare paths below at once, and their addresses and values
+// take the row kernels past the 72 VGPRs of seven waves per SIMD into scratch.  No arithmetic: the bits are not affected.
+__device__ __forceinline__ int ordered_after(int x, float after) { asm volatile("" : "+v"(x) : "v"(after)); return x; }
+struct UpDep {
+    const float* dep; int dh, dw; float sy, sx;
+    // a texture row = two source rows (offsets into the map) and the weight of the second; w0 = 1 - w1 is re-formed where it is used
+    // (linear_tap's own expression: the same bits) -- six block-uniform values instead of eight, the row kernels live at their SGPR limit
+    struct RowTap { int o0, o1; float w1; };
+    struct Row { RowTap t0, t1; };
+    __device__ __forceinline__ static UpDep make(const float* dep_all, int b, const DibrGeom& g) {
+        return UpDep{dep_all + (long)b * g.dh * g.dw, g.dh, g.dw, g.dsy, g.dsx};
+    }
+    __device__ __forceinline__ RowTap row_tap(int y) const { const Tap t = linear_tap(y, sy, dh, false); return RowTap{t.i0 * dw, t.i1 * dw, t.w1}; }
+    __device__ __forceinline__ Row row(int y0, int y1, int) const { return Row{row_tap(y0), row_tap(y1)}; }
+    __device__ __forceinline__ float one(const RowTap& r, const Tap& tx) const {
+        Tap ty; ty.i0 = 0; ty.i1 = 0; ty.w1 = r.w1; ty.w0 = 1.0f - r.w1;
+        return upsample_texel_rows(dep + r.o0, dep + r.o1, ty, tx);
+    }
+    __device__ __forceinline__ float one(const RowTap& r, int x) const { return one(r, linear_tap(x, sx, dw, false)); }
+    __device__ __forceinline__ void pair(const Row& r, int x, float& a, float& b) const {
+        const Tap tx = linear_tap(x, sx, dw, false);
+        a = one(r.t0, tx);
+        b = one(r.t1, tx);
+    }
+};
 // The two texels of a row are adjacent except across the GL_REPEAT seam: one 8-byte load per row (gfx950 runs with
 // unaligned access enabled: a dwordx2 at a 4-byte / a byte address is one instruction) instead of two 4-byte / six
 // 1-byte loads -- the kernel is bound by the number of gather instructions, not by bytes.
@@ -58,6 +101,18 @@ __device__ __forceinline__ float tex_depth(const float* __restrict__ dep, int H,
         return lerp2(a.x, a.y, b.x, b.y, t.fx, t.fy);
     }
     return lerp2(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.fx, t.fy);
+}
+__device__ __forceinline__ float tex_depth(const FullDep& d, int H, int W, float u, float v) { return tex_depth(d.dep, H, W, u, v); }
+// ORD (the LDS-window kernels, which live at 72 VGPRs): one texel -- four source loads -- at a time (ordered_after); the gather
+// kernels have the registers to request all sixteen at once.
+template <bool ORD = false>
+__device__ __forceinline__ float tex_depth(const UpDep& d, int H, int W, float u, float v) {
+    const TexTap t = tex_tap(u, v, H, W);
+    const float a = upsample_texel(d.dep, d.dh, d.dw, d.sy, d.sx, t.y0, t.x0);
+    const float b = upsample_texel(d.dep, d.dh, d.dw, d.sy, d.sx, t.y0, ORD ? ordered_after(t.x1, a) : t.x1);
+    const float c = upsample_texel(d.dep, d.dh, d.dw, d.sy, d.sx, t.y1, ORD ? ordered_after(t.x0, b) : t.x0);
+    const float e = upsample_texel(d.dep, d.dh, d.dw, d.sy, d.sx, t.y1, ORD ? ordered_after(t.x1, c) : t.x1);
+    return lerp2(a, b, c, e, t.fx, t.fy);
 }
 __device__ __forceinline__ void tex_color(const uint8_t* __restrict__ rgb, int H, int W, float u, float v, float o[3]) {
     TexTap t = tex_tap(u, v, H, W);
@@ -84,13 +139,14 @@ __device__ __forceinline__ void tex_color(const uint8_t* __restrict__ rgb, int H
 // roll == 0 (the desktop viewer; OpenXR sets a roll): every tap of a pixel except the two vertical-blur taps lies on the pixel's own
 // texture row pair, so the y half of tex_tap -- v * H - 0.5, floor, GL_REPEAT wrap, the two row bases -- is formed ONCE per pixel
 // (same expressions on the same v: the same bits as a per-tap evaluation) and a tap is its x half alone.
-struct RowCtx { const float* d0; const float* d1; int c0, c1; float fy; };
-__device__ __forceinline__ RowCtx row_ctx(const float* __restrict__ dep, int H, int W, float v) {
+template <class D> struct RowCtx { typename D::Row d; int c0, c1; float fy; };
+template <class D>
+__device__ __forceinline__ RowCtx<D> row_ctx(const D& dep, int H, int W, float v) {
     const float y = v * (float)H - 0.5f, y0f = floorf(y);
-    RowCtx r;
+    RowCtx<D> r;
     r.fy = y - y0f;
     const int y0 = wrapi((int)y0f, H), y1 = y0 + 1 == H ? 0 : y0 + 1;
-    r.d0 = dep + y0 * W; r.d1 = dep + y1 * W;
+    r.d = dep.row(y0, y1, W);
     r.c0 = y0 * W * 3; r.c1 = y1 * W * 3;
     return r;
 }
@@ -103,15 +159,25 @@ __device__ __forceinline__ XTap x_tap(float u, int W) {
     t.x1 = t.x0 + 1 == W ? 0 : t.x0 + 1;
     return t;
 }
-__device__ __forceinline__ float tex_depth_row(const RowCtx& r, int W, float u) {
+__device__ __forceinline__ float tex_depth_row(const FullDep&, const RowCtx<FullDep>& r, int W, float u) {
     const XTap t = x_tap(u, W);
     if (t.x1 == t.x0 + 1) {
-        f32x2u a = *(const f32x2u*)(r.d0 + t.x0), b = *(const f32x2u*)(r.d1 + t.x0);
+        f32x2u a = *(const f32x2u*)(r.d.d0 + t.x0), b = *(const f32x2u*)(r.d.d1 + t.x0);
         return lerp2(a.x, a.y, b.x, b.y, t.fx, r.fy);
     }
-    return lerp2(r.d0[t.x0], r.d0[t.x1], r.d1[t.x0], r.d1[t.x1], t.fx, r.fy);
+    return lerp2(r.d.d0[t.x0], r.d.d0[t.x1], r.d.d1[t.x0], r.d.d1[t.x1], t.fx, r.fy);
 }
-__device__ __forceinline__ void tex_color_row(const uint8_t* __restrict__ rgb, const RowCtx& r, int H, int W, float u, float o[3]) {
+template <bool ORD = false>       // (ORD: a tap that left the LDS window, as above)
+__device__ __forceinline__ float tex_depth_row(const UpDep& d, const RowCtx<UpDep>& r, int W, float u) {
+    const XTap t = x_tap(u, W);
+    const float a = d.one(r.d.t0, t.x0);
+    const float b = d.one(r.d.t0, ORD ? ordered_after(t.x1, a) : t.x1);
+    const float c = d.one(r.d.t1, ORD ? ordered_after(t.x0, b) : t.x0);
+    const float e = d.one(r.d.t1, ORD ? ordered_after(t.x1, c) : t.x1);
+    return lerp2(a, b, c, e, t.fx, r.fy);
+}
+template <class D>
+__device__ __forceinline__ void tex_color_row(const uint8_t* __restrict__ rgb, const RowCtx<D>& r, int H, int W, float u, float o[3]) {
     const XTap t = x_tap(u, W);
     const int ia = r.c0 + t.x0 * 3, ic = r.c1 + t.x0 * 3, end = H * W * 3;
     if (t.x1 == t.x0 + 1 && ia + 8 <= end && ic + 8 <= end) {
@@ -135,45 +201,54 @@ __device__ __forceinline__ void tex_color_row(const uint8_t* __restrict__ rgb, c
 }
 // Where a pixel's taps come from.  own_*: taps on the pixel's own texture row pair when roll == 0 (any (u, v) otherwise);
 // any_*: the two vertical-blur taps of the in-painting (other rows), always the general gather.
+template <class D>
 struct GenSmp {                                    // general: every tap evaluates both coordinates (roll != 0)
-    const uint8_t* rgb; const float* dep; int H, W;
+    const uint8_t* rgb; D dep; int H, W;
     __device__ __forceinline__ float own_depth(float u, float v) const { return tex_depth(dep, H, W, u, v); }
     __device__ __forceinline__ void own_color(float u, float v, float o[3]) const { tex_color(rgb, H, W, u, v, o); }
     __device__ __forceinline__ float any_depth(float u, float v) const { return tex_depth(dep, H, W, u, v); }
     __device__ __forceinline__ void any_color(float u, float v, float o[3]) const { tex_color(rgb, H, W, u, v, o); }
+    static constexpr bool up = std::is_same<D, UpDep>::value;
 };
-struct RowSmp : GenSmp {                           // roll == 0: the row pair is formed once per pixel
-    RowCtx rc;
-    __device__ __forceinline__ float own_depth(float u, float) const { return tex_depth_row(rc, W, u); }
-    __device__ __forceinline__ void own_color(float u, float, float o[3]) const { tex_color_row(rgb, rc, H, W, u, o); }
+template <class D>
+struct RowSmp : GenSmp<D> {                        // roll == 0: the row pair is formed once per pixel
+    RowCtx<D> rc;
+    __device__ __forceinline__ float own_depth(float u, float) const { return tex_depth_row(this->dep, rc, this->W, u); }
+    __device__ __forceinline__ void own_color(float u, float, float o[3]) const { tex_color_row(this->rgb, rc, this->H, this->W, u, o); }
 };
 // roll == 0, the block's row pair staged in LDS: a window of WW texels starting at (unwrapped) texel wx0, GL_REPEAT applied by
 // the staging loop; planes d0 | d1 | R0 G0 B0 | R1 G1 B1 as floats (the same byte -> float conversions the gather path makes per
 // tap).  A tap is index arithmetic + ds_read2_b32 pairs; taps that leave the window (parallax settings beyond the margin the
 // launcher sized it for) take the row gather: same values either way.
-struct WinSmp : RowSmp {
+template <class D>
+struct WinSmp : RowSmp<D> {
     const float* dwin;          // [2][WW]: the row pair of the depth texture
     const float* cwin;          // [6][WW]: R0 G0 B0 R1 G1 B1 as floats
     int wx0, WW;
     __device__ __forceinline__ float own_depth(float u, float v) const {
-        const float x = u * (float)W - 0.5f, x0f = floorf(x), fx = x - x0f;
+        const float x = u * (float)this->W - 0.5f, x0f = floorf(x), fx = x - x0f;
         const int j = (int)x0f - wx0;
         if ((unsigned)j < (unsigned)(WW - 1)) {
             const float* p = dwin + j;
-            return lerp2(p[0], p[1], p[WW], p[WW + 1], fx, rc.fy);
+            return lerp2(p[0], p[1], p[WW], p[WW + 1], fx, this->rc.fy);
         }
-        return RowSmp::own_depth(u, v);
+        if constexpr (RowSmp<D>::up) return tex_depth_row<true>(this->dep, this->rc, this->W, u);
+        else return RowSmp<D>::own_depth(u, v);
     }
     __device__ __forceinline__ void own_color(float u, float v, float o[3]) const {
-        const float x = u * (float)W - 0.5f, x0f = floorf(x), fx = x - x0f;
+        const float x = u * (float)this->W - 0.5f, x0f = floorf(x), fx = x - x0f;
         const int j = (int)x0f - wx0;
         if ((unsigned)j < (unsigned)(WW - 1)) {
             const float* p = cwin + j;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) o[k] = lerp2(p[k * WW], p[k * WW + 1], p[(3 + k) * WW], p[(3 + k) * WW + 1], fx, rc.fy);
+            for (int k = 0; k < 3; ++k) o[k] = lerp2(p[k * WW], p[k * WW + 1], p[(3 + k) * WW], p[(3 + k) * WW + 1], fx, this->rc.fy);
             return;
         }
-        RowSmp::own_color(u, v, o);
+        RowSmp<D>::own_color(u, v, o);
+    }
+    __device__ __forceinline__ float any_depth(float u, float v) const {
+        if constexpr (RowSmp<D>::up) return tex_depth<true>(this->dep, this->H, this->W, u, v);
+        else return RowSmp<D>::any_depth(u, v);
     }
 };
 __device__ __forceinline__ float smoothstepf(float e0, float e1, float x) {
@@ -195,6 +270,24 @@ template <class S>
 __device__ __forceinline__ void push_pull_finish(const S& smp, const DibrGeom& g, float u, float v, float cdi, const float best[3], float bw, float out[3]) {
     if (bw > 0.01f) {                                                                 // phase 3 (:484-502)
         float va[3] = {best[0] / bw * 0.5f, best[1] / bw * 0.5f, best[2] / bw * 0.5f}, vw = 0.5f;
+        if constexpr (S::up) {
+            // UpDep: a depth tap is sixteen source loads, not two: the taps run one after the other in a loop that is not unrolled
+            // (requested together they take the row kernels past their register budget into scratch).  The same values added in the
+            // same order dy = -1, +1: the same bits.
+#pragma clang loop unroll(disable)
+            for (int t = 0; t < 2; ++t) {
+                const float vv = v + (float)(2 * t - 1) * g.psy * g.blur;
+                if (!(vv >= 0.f && vv <= 1.f)) continue;
+                if (1.0f - smp.any_depth(u, vv) > cdi + g.tol * 0.5f) {
+                    float vc[3];
+                    smp.any_color(u, vv, vc);
+                    va[0] += vc[0] * 0.25f; va[1] += vc[1] * 0.25f; va[2] += vc[2] * 0.25f;
+                    vw += 0.25f;
+                }
+            }
+            out[0] = va[0] / vw; out[1] = va[1] / vw; out[2] = va[2] / vw;
+            return;
+        }
         // the two vertical taps touch other texture rows: global gathers.  All six of their loads are requested before the first is
         // used (the depth test decides what is ADDED, not what is fetched): one round trip instead of up to four dependent ones at
         // the end of every in-painted pixel; the sums keep the order dy = -1, +1

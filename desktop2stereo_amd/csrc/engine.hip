@@ -1062,10 +1062,18 @@ extern "C" int d2s_pipeline(d2s_engine* e, const uint8_t* frames, int batch, int
     return d2s_pipeline_streams(e, frames, batch, nullptr, H, W, depth_resolution, pre, pp, sp, use_ema, out, out_fmt, depth_full, stream);
 }
 
-extern "C" int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
-                                    const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_sbs_params* sp, int use_ema,
-                                    void* out, int out_fmt, float* depth_full, void* stream) {
-    D2S_REQUIRE(e && frames && pp && sp && out, "null pointer");
+namespace d2s {      // (dibr.hip, dibr_composite.hip) check_only: every argument check of the entry point, nothing launched
+int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                  void* out, int out_fmt, void* stream, bool check_only);
+int dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                       int composite, void* out, int out_fmt, void* stream, bool check_only);
+}
+
+namespace {
+// d2s_pipeline_streams and d2s_view_pipeline_streams are one call up to and including the EMA step; they differ in the warp that
+// reads e->depth_post.  pipeline_check: every refusal of that shared part (nothing is launched); *stride: the decimation of the
+// pre-process.  pipeline_depth: frames -> e->depth_post at model resolution (+ depth_full, predict_depth's return value).
+int pipeline_check(d2s_engine* e, int batch, const int* stream_ids, int H, int W, int depth_resolution, const d2s_pre_params* pre, int* stride_out) {
     if (!e->finalized) { set_error("d2s_pipeline before d2s_engine_finalize"); return D2S_E_STATE; }
     D2S_REQUIRE(batch >= 1 && batch <= e->maxB, "batch exceeds max_batch");
     RC(resolve_streams(e, batch, stream_ids));
@@ -1088,7 +1096,12 @@ extern "C" int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int ba
         stride = longest / (depth_resolution * 2);
         if (stride < 1) stride = 1;
     }
-    D2S_ON_DEVICE(e->device);
+    *stride_out = stride;
+    return D2S_OK;
+}
+
+int pipeline_depth(d2s_engine* e, const uint8_t* frames, int batch, int H, int W, int stride, const d2s_pre_params* pre,
+                   const d2s_post_params* pp, int use_ema, float* depth_full, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     {   // pre-process straight into the patch rows where that form exists (bilinear branch), else planes + the engine's patchify
         const bool fused = !e->taps && preprocess_patches_ok(e->prec, D2S_FMT_U8_HWC, pre, H, W, e->h, e->w, e->d.patch, e->patch.Kpad);
@@ -1110,12 +1123,58 @@ extern "C" int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int ba
         e->ema_init = 1;
     }
     if (depth_full) RC(d2s_upsample_depth(e->depth_post, batch, e->h, e->w, depth_full, H, W, stream));
+    return D2S_OK;
+}
+}  // namespace
+
+extern "C" int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
+                                    const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_sbs_params* sp, int use_ema,
+                                    void* out, int out_fmt, float* depth_full, void* stream) {
+    D2S_REQUIRE(e && frames && pp && sp && out, "null pointer");
+    int stride = 1;
+    RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
+    D2S_ON_DEVICE(e->device);
+    hipStream_t st = (hipStream_t)stream;
+    RC(pipeline_depth(e, frames, batch, H, W, stride, pre, pp, use_ema, depth_full, stream));
     {
         int oh = 0, ow = 0;
         RC(d2s_sbs_shape(H, W, sp, &oh, &ow));
         double obytes = (double)oh * ow * 3 * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
         PROF(PC_WARP, 0, batch * ((double)H * W * 3 + (double)e->h * e->w * 4 + obytes),
              d2s_make_sbs(frames, D2S_FMT_U8_HWC, e->depth_post, e->h, e->w, batch, H, W, sp, out, out_fmt, stream));
+    }
+    return D2S_OK;
+}
+
+extern "C" int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
+                                         const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp, int view, int use_ema,
+                                         void* out, int out_fmt, float* depth_full, void* stream) {
+    D2S_REQUIRE(frames && pp && dp && out, "null pointer");
+    D2S_REQUIRE(view >= -1 && view <= D2S_COMPOSITE_DEPTH_MAP, "bad view (-1: the stereo warp, or D2S_COMPOSITE_*)");
+    D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
+    {   // what depends on the frame and the uniforms alone (display mode / viewport), then the engine
+        int oh = 0, ow = 0;
+        RC(view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
+    }
+    D2S_REQUIRE(e, "null engine");
+    int stride = 1;
+    RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
+    // the warp's own refusals (struct_size, viewport, formats, limits) before anything is launched
+    auto warp = [&](bool check_only) {
+        return view < 0 ? dibr_warp_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, out, out_fmt, stream, check_only)
+                        : dibr_composite_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, view, out, out_fmt, stream, check_only);
+    };
+    RC(warp(true));
+    D2S_ON_DEVICE(e->device);
+    hipStream_t st = (hipStream_t)stream;
+    RC(pipeline_depth(e, frames, batch, H, W, stride, pre, pp, use_ema, depth_full, stream));
+    {
+        int oh = 0, ow = 0;
+        RC(view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
+        const int nch = dp->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+        double obytes = (double)oh * ow * nch * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
+        const double ibytes = view == D2S_COMPOSITE_DEPTH_MAP ? 0.0 : (double)H * W * 3;
+        PROF(PC_WARP, 0, batch * (ibytes + (double)e->h * e->w * 4 + obytes), warp(false));
     }
     return D2S_OK;
 }

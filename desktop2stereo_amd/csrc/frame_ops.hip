@@ -217,12 +217,7 @@ upsample_depth_kernel(const float* __restrict__ in, int B, int h, int w, float* 
     int x = (int)(idx % W);
     int y = (int)((idx / W) % H);
     int b = (int)(idx / ((long)W * H));
-    Tap ty = linear_tap(y, sy, h, false);
-    Tap tx = linear_tap(x, sx, w, false);
-    const float* p = in + (long)b * h * w;
-    float top = tx.w0 * p[ty.i0 * w + tx.i0] + tx.w1 * p[ty.i0 * w + tx.i1];
-    float bot = tx.w0 * p[ty.i1 * w + tx.i0] + tx.w1 * p[ty.i1 * w + tx.i1];
-    out[idx] = ty.w0 * top + ty.w1 * bot;
+    out[idx] = upsample_texel(in + (long)b * h * w, h, w, sy, sx, y, x);      // (common.h: shared with the DIBR kernels' UpDep source)
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -307,11 +307,18 @@ def composite_view(rgb, depth, display_mode, ipd_uv=0.064, depth_ratio=2.0, conv
     return ops.dibr_composite(frames, d.to(device=_device()), dp, display_mode, out_u8=False).cpu().numpy()
 
 
-def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None):
+def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,
+             viewport=None):
     """Batched predict_depth + make_sbs: uint8 [B,H,W,3] (numpy or device tensor) -> device tensor
     [B,H',W',3] (uint8, or float32 when out_u8=False) in one stream-ordered native call.
     Video-Depth-Anything: frame r is the next frame of stream `streams[r]` (distinct slots < max_batch; None: streams 0..B-1);
-    only the named streams advance, and use_temporal_smooth keeps one EMA state per stream."""
+    only the named streams advance, and use_temporal_smooth keeps one EMA state per stream.
+    The Viewer's warps, in the same one call (the shader warp reads the model-resolution depth; no full-resolution map in between):
+    inpaint=True with an SBS / TAB display_mode renders the DIBR shader with disocclusion in-painting (make_sbs(inpaint=True)), and a
+    display_mode of "Anaglyph" | "Interleaved" | "Interleaved-V" | "Depth Map" renders that composite (composite_view) over
+    `viewport` = (x, y, w, h) in window pixels, None = the frame.  Their uniforms are ops.dibr_params(ipd, depth_strength,
+    convergence, ...) of the configured parameters; fill_16_9 is a window-layout matter of the torch warp and is ignored on
+    this path."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -320,7 +327,18 @@ def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, 
     if B > _state["max_batch"]:
         raise _lib.D2SError(f"batch {B} > configured max_batch {_state['max_batch']}")
     eng = _ensure_engine_built(h, w, _fp8_first_inputs(t, (h, w)))
-    sp = ops.sbs_params(p.ipd, p.depth_strength, p.convergence, display_mode or p.display_mode, p.fill_16_9)
+    mode = display_mode or p.display_mode
+    if mode in _lib.COMPOSITE or inpaint:
+        vp = tuple(viewport) if viewport is not None else (0.0, 0.0, 0.0, 0.0)
+        if mode in _lib.COMPOSITE:
+            dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, viewport=vp)
+        else:
+            dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, mode, viewport=vp)
+        return eng.view_pipeline(t, p, dp, view=mode if mode in _lib.COMPOSITE else None, use_ema=use_temporal_smooth, out_u8=out_u8,
+                                 want_depth=want_depth, streams=streams)
+    if viewport is not None:
+        raise ValueError("pipeline(viewport=...) belongs to the Viewer's warps (inpaint=True or a composite display_mode)")
+    sp = ops.sbs_params(p.ipd, p.depth_strength, p.convergence, mode, p.fill_16_9)
     return eng.pipeline(t, p, sp, use_ema=use_temporal_smooth, out_fmt=_lib.FMT_U8_HWC if out_u8 else _lib.FMT_F32_HWC,
                         want_depth=want_depth, streams=streams)
 

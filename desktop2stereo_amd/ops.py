@@ -290,8 +290,9 @@ def dibr_params(ipd_uv=0.064, depth_ratio=1.0, convergence=0.0, display_mode="Fu
 
 
 def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", out_u8: bool = True) -> torch.Tensor:
-    """f1 (reference viewer.py:386-631): uint8 HWC frames [B,H,W,3] or [H,W,3] + full-resolution depth -> both eyes
-    with disocclusion in-painting, packed per dp.display_mode."""
+    """f1 (reference viewer.py:386-631): uint8 HWC frames [B,H,W,3] or [H,W,3] + depth [B,dh,dw] or [dh,dw] -> both eyes
+    with disocclusion in-painting, packed per dp.display_mode.  Depth of the frame's size is the shader's depth texture itself;
+    any other size (the model's) is up-sampled inside the kernel, bit-identical to upsample_depth(depth, H, W) first."""
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
@@ -301,8 +302,9 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
     d = depth.to(torch.float32).contiguous()
     d = d if d.dim() == 3 else d.unsqueeze(0)
     B, H, W, _ = f.shape
-    if tuple(d.shape) != (B, H, W):
-        raise ValueError(f"dibr_warp: depth must be full resolution {(B, H, W)}, got {tuple(d.shape)}")
+    if d.dim() != 3 or d.shape[0] != B:
+        raise ValueError(f"dibr_warp: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
+    dh, dw = d.shape[1:]
     lib = _lib.load()
     oh, ow = C.c_int(), C.c_int()
     check(lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
@@ -310,16 +312,18 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
     out = torch.empty((B, oh.value, ow.value, nch), dtype=torch.uint8 if out_u8 else torch.float32, device=f.device)
     _same_device(f, d, "dibr_warp")
     with _on(f.device) as st:
-        check(lib.d2s_dibr_warp(_ptr(f), _ptr(d), B, H, W, C.byref(dp), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st),
-              "d2s_dibr_warp")
+        check(lib.d2s_dibr_warp_depth(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st),
+              "d2s_dibr_warp_depth")
     return out if batched else out[0]
 
 
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
-                   out_u8: bool = True) -> torch.Tensor:
+                   out_u8: bool = True, size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """The viewer's composite display modes (reference viewer.py:633-1197): "Anaglyph" | "Interleaved" | "Interleaved-V" |
-    "Depth Map".  uint8 HWC frames [B,H,W,3] or [H,W,3] (None for "Depth Map") + full-resolution depth -> the program's viewport,
-    dp.viewport = (x, y, w, h) in window pixels, y up (zeros: the frame itself); dp.display_mode is not used (include/d2s.h)."""
+    "Depth Map".  uint8 HWC frames [B,H,W,3] or [H,W,3] (None for "Depth Map") + depth [B,dh,dw] or [dh,dw] -> the program's viewport,
+    dp.viewport = (x, y, w, h) in window pixels, y up (zeros: the frame itself); dp.display_mode is not used (include/d2s.h).
+    Depth of another size than the frame's (the model's) is up-sampled inside the kernel, bit-identical to upsample_depth first.
+    size = (H, W): the frame size when there are no frames ("Depth Map" from a model-resolution map); default: the depth's own."""
     if mode not in _lib.COMPOSITE:
         raise ValueError(f"mode must be one of {list(_lib.COMPOSITE)}")
     _need_cuda(depth, "depth")
@@ -328,15 +332,17 @@ def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_li
     d = d if batched else d.unsqueeze(0)
     if d.dim() != 3:
         raise ValueError("dibr_composite: depth must be [B,H,W] or [H,W]")
-    B, H, W = d.shape
+    B, dh, dw = d.shape
+    H, W = (int(size[0]), int(size[1])) if size is not None else (dh, dw)
     f = None
     if frames is not None:
         _need_cuda(frames, "frames")
         if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() != (4 if batched else 3):
             raise ValueError("dibr_composite: frames must be uint8 [B,H,W,3] or [H,W,3], batched like depth")
         f = frames.contiguous() if batched else frames.contiguous().unsqueeze(0)
-        if tuple(f.shape[:3]) != (B, H, W):
-            raise ValueError(f"dibr_composite: depth must be full resolution {tuple(f.shape[:3])}, got {(B, H, W)}")
+        if f.shape[0] != B or (size is not None and tuple(f.shape[1:3]) != (H, W)):
+            raise ValueError(f"dibr_composite: frames {tuple(f.shape)} do not match depth {tuple(d.shape)} / size {size}")
+        H, W = f.shape[1:3]
         _same_device(f, d, "dibr_composite")
     elif mode != "Depth Map":
         raise ValueError(f"dibr_composite: {mode} needs the frames")
@@ -346,8 +352,8 @@ def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_li
     nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
     out = torch.empty((B, oh.value, ow.value, nch), dtype=torch.uint8 if out_u8 else torch.float32, device=d.device)
     with _on(d.device) as st:
-        check(lib.d2s_dibr_composite(_ptr(f) if f is not None else None, _ptr(d), B, H, W, C.byref(dp), _lib.COMPOSITE[mode],
-                                     _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st), "d2s_dibr_composite")
+        check(lib.d2s_dibr_composite_depth(_ptr(f) if f is not None else None, _ptr(d), dh, dw, B, H, W, C.byref(dp), _lib.COMPOSITE[mode],
+                                           _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st), "d2s_dibr_composite_depth")
     return out if batched else out[0]
 
 
@@ -529,6 +535,44 @@ class Engine:
             check(self.lib.d2s_pipeline_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution, C.byref(pre),
                                                 C.byref(pp), C.byref(sp), int(use_ema), _ptr(out), out_fmt,
                                                 _ptr(depth) if want_depth else None, st), "d2s_pipeline")
+        return (out, depth) if want_depth else out
+
+    def view_pipeline(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", view: Optional[str] = None,
+                      use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,
+                      streams=None):
+        """predict_depth + the Viewer's shader warp for uint8 HWC frames [B,H,W,3] in one stream-ordered call: `pipeline` with
+        dibr_warp (view=None: both eyes with disocclusion in-painting, packed per dp.display_mode) or dibr_composite (view =
+        "Anaglyph" | "Interleaved" | "Interleaved-V" | "Depth Map", over dp.viewport) in place of make_sbs.  The warp reads the
+        engine's model-resolution depth; bit-identical to pipeline(want_depth=True) followed by dibr_warp / dibr_composite on that
+        map.  out: a caller-allocated result (e.g. a present-ring slot), [B,oh,ow,3|4] uint8 / float32.  streams, use_ema: as pipeline."""
+        self._mine(frames, "frames")
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError("frames must be uint8 [B,H,W,3]")
+        if view is not None and view not in _lib.COMPOSITE:
+            raise ValueError(f"view must be None or one of {list(_lib.COMPOSITE)}")
+        frames = frames.contiguous()
+        B, H, W, _ = frames.shape
+        oh, ow = C.c_int(), C.c_int()
+        if view is None:
+            check(self.lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
+        else:
+            check(self.lib.d2s_dibr_composite_shape(H, W, C.byref(dp), _lib.COMPOSITE[view], C.byref(oh), C.byref(ow)), "d2s_dibr_composite_shape")
+        nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+        want = ((B, oh.value, ow.value, nch), torch.uint8 if out_u8 else torch.float32)
+        if out is None:
+            out = torch.empty(want[0], dtype=want[1], device=frames.device)
+        else:
+            self._mine(out, "out")
+            if out.numel() != B * oh.value * ow.value * nch or out.dtype != want[1] or not out.is_contiguous():
+                raise ValueError(f"view_pipeline: out must be a contiguous {want[1]} tensor of {want[0]}")
+        depth = torch.empty((B, H, W), dtype=torch.float32, device=frames.device) if want_depth else None
+        pp = post_params(p)
+        pre = pre_params(p.mean, p.std, p.resample, p.square_input)
+        with _on(self.device) as st:
+            check(self.lib.d2s_view_pipeline_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution,
+                                                     C.byref(pre), C.byref(pp), C.byref(dp), -1 if view is None else _lib.COMPOSITE[view],
+                                                     int(use_ema), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC,
+                                                     _ptr(depth) if want_depth else None, st), "d2s_view_pipeline_streams")
         return (out, depth) if want_depth else out
 
     def close(self):

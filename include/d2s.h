@@ -298,6 +298,12 @@ int d2s_sbs_shape(int H, int W, const d2s_sbs_params* p, int* out_h, int* out_w)
 int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* out_w);
 int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream);
+/* d2s_dibr_warp with depth at ANY resolution, float [batch,dh,dw] -- typically the model's (d2s_version() >= 113).  The shader's
+ * H x W depth texture is the bilinear up-sample d2s_upsample_depth(depth, dh, dw -> H, W) would store, evaluated inside the warp
+ * kernel instead of being written to memory and read back: the output is BIT-IDENTICAL to d2s_upsample_depth + d2s_dibr_warp
+ * (tests/test_gpu_view_pipeline.py).  dh == H && dw == W is exactly d2s_dibr_warp.  Shape from d2s_dibr_shape. */
+int d2s_dibr_warp_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                        const d2s_dibr_params* p, void* out, int out_fmt, void* stream);
 
 /* The viewer's other four `Display Mode`s (gui.py:1666, viewer.py:1340), each one program the reference runs over its letter-boxed
  * viewport (viewer.py:2604-2662: u_eye_offset = +ipd_uv/2, u_depth_strength = 0.1 * depth_ratio, blending off):
@@ -320,6 +326,10 @@ enum { D2S_COMPOSITE_ANAGLYPH = 0, D2S_COMPOSITE_INTERLEAVED = 1, D2S_COMPOSITE_
 int d2s_dibr_composite_shape(int H, int W, const d2s_dibr_params* p, int composite, int* out_h, int* out_w);
 int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
                        int composite, void* out, int out_fmt, void* stream);
+/* d2s_dibr_composite with depth float [batch,dh,dw] at any resolution, as d2s_dibr_warp_depth (d2s_version() >= 113): bit-identical
+ * to d2s_upsample_depth + d2s_dibr_composite; dh == H && dw == W is exactly d2s_dibr_composite.  Shape from d2s_dibr_composite_shape. */
+int d2s_dibr_composite_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                             const d2s_dibr_params* p, int composite, void* out, int out_fmt, void* stream);
 
 /* f3: the MJPEG sink of the Streamer modes.  Replaces `cv2.imencode('.jpg', bgr, [IMWRITE_JPEG_QUALITY, q])` on the
  * frame make_sbs returns (reference streamer.py:249-256, 285-291; quality = settings.yaml "Stream Quality",
@@ -373,6 +383,18 @@ int d2s_pipeline(d2s_engine* e, const uint8_t* frames, int batch, int H, int W,
 int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
                          int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_sbs_params* sp,
                          int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
+/* The Viewer pipeline (d2s_version() >= 113): d2s_pipeline_streams with the warp the reference's Viewer / OpenXR modes show.  The
+ * same call up to and including the EMA step (one code path); then the DIBR shader warp reads the engine's model-resolution depth
+ * directly (d2s_dibr_warp_depth / d2s_dibr_composite_depth: no full-resolution depth map is written unless depth_full asks for it).
+ *   view = -1: the stereo warp with disocclusion in-painting, both eyes packed per dp->display_mode (shape: d2s_dibr_shape);
+ *   view = D2S_COMPOSITE_*: that composite program over dp->viewport (shape: d2s_dibr_composite_shape).
+ * out: D2S_FMT_U8_HWC or D2S_FMT_F32_HWC, three channels (four with dp->alpha_mode == D2S_DIBR_ALPHA_RGBA); it may be a
+ * d2s_present slot pointer.  depth_full (may be NULL) receives the same map d2s_pipeline gives.  Refuses what d2s_pipeline_streams
+ * and the DIBR entries refuse (frame / engine shape, stream ids, struct_size, view, viewport, formats); nothing is launched on a
+ * refusal.  Bit-identical to d2s_pipeline(depth_full) followed by d2s_dibr_warp / d2s_dibr_composite on that map. */
+int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                              int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
+                              int view, int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """d2s_dibr_warp alone: 1080p scene with hard depth edges -> both eyes; us per launch and HBM fraction.
     python tools/dibr_bench.py [--mode Full-SBS] [--batch 1 8]
-    python tools/dibr_bench.py --composite Anaglyph|Interleaved|Interleaved-V|"Depth Map" [--viewport X Y W H]   (d2s_dibr_composite)"""
+    python tools/dibr_bench.py --composite Anaglyph|Interleaved|Interleaved-V|"Depth Map" [--viewport X Y W H]   (d2s_dibr_composite)
+    python tools/dibr_bench.py --pipeline [--model vitb] [--precision bf16] [--mode Full-SBS | --composite Anaglyph] [--batch 1 16] [--json FILE]
+        frames -> views end to end: Engine.view_pipeline (the warp reads the model-resolution depth) against the two-call path it
+        replaces (Engine.pipeline(want_depth=True) for the full-resolution depth map, then dibr_warp / dibr_composite on it), alternated
+        in one process with inputs resident, device events; the parent is also timed against itself (the run-to-run spread), and
+        the warp stage alone is timed both ways (upsample_depth + warp on the full map against the warp on the small map)."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,8 +18,89 @@ ap.add_argument("--height", type=int, default=1080); ap.add_argument("--width", 
 ap.add_argument("--kind", default="boxes")
 ap.add_argument("--composite", default=None, help="a composite mode instead of the f1 warp")
 ap.add_argument("--viewport", type=int, nargs=4, default=None, help="composite viewport x y w h in window pixels (default: the frame)")
+ap.add_argument("--pipeline", action="store_true", help="time Engine.view_pipeline against pipeline(want_depth) + the warp")
+ap.add_argument("--model", default="vitb"); ap.add_argument("--precision", default="bf16")
+ap.add_argument("--depth-resolution", type=int, default=518)
+ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--json", default=None, help="--pipeline: also write the figures to this file")
 a = ap.parse_args()
 dev = torch.device("cuda")
+
+
+def pipeline_bench():
+    import json
+    import numpy as np
+    from desktop2stereo_amd.config import MODELS, PipelineParams, engine_shape
+    from desktop2stereo_amd.weights import make_weights
+    H, W = a.height, a.width
+    cfg = MODELS[a.model]
+    p = PipelineParams(depth_resolution=a.depth_resolution)
+    h, w, _ = engine_shape(H, W, p.depth_resolution, cfg.patch)
+    dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, a.mode, viewport=tuple(a.viewport) if a.viewport else (0.0, 0.0, 0.0, 0.0))
+    sp = ops.sbs_params(p.ipd, p.depth_strength, p.convergence, "Half-SBS", False)
+    eng = ops.Engine(cfg, make_weights(cfg, 0), h, w, max(a.batch), a.precision)
+    results = []
+    for B in a.batch:
+        f = torch.from_numpy(np.stack([synth.dibr_scene(H, W, 11 + i, a.kind)[0] for i in range(min(B, 4))])).to(dev)
+        f = f.repeat((B + f.shape[0] - 1) // f.shape[0], 1, 1, 1)[:B].contiguous()
+        warp_full = (lambda d: ops.dibr_composite(f, d, dp, a.composite)) if a.composite else (lambda d: ops.dibr_warp(f, d, dp))
+
+        def parent():
+            _, depth = eng.pipeline(f, p, sp, want_depth=True)
+            return warp_full(depth)
+
+        def fused():
+            return eng.view_pipeline(f, p, dp, view=a.composite)
+
+        _, depth_full = eng.pipeline(f, p, sp, want_depth=True)
+        d_small = torch.rand((B, h, w), device=dev)
+        d_small[:, h // 4: h // 2, w // 4: w // 2] = 0.05                       # hard edges: the in-painting runs
+
+        def warp_parent():
+            return warp_full(ops.upsample_depth(d_small, H, W))
+
+        def warp_fused():
+            return warp_full(d_small)
+
+        assert torch.equal(parent(), fused()) and torch.equal(warp_parent(), warp_fused()), "fused != two-call"
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            for _ in range(a.iters): fn()
+            e1.record(); torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / a.iters
+
+        for fn in (parent, fused, warp_parent, warp_fused):
+            for _ in range(3): fn()
+        t = {k: [] for k in ("parent", "fused", "parent_again", "warp_parent", "warp_fused", "warp_parent_again")}
+        for _ in range(a.rounds):                                                # alternated: drift hits every path alike
+            t["parent"].append(timed(parent)); t["fused"].append(timed(fused)); t["parent_again"].append(timed(parent))
+            t["warp_parent"].append(timed(warp_parent)); t["warp_fused"].append(timed(warp_fused)); t["warp_parent_again"].append(timed(warp_parent))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        out_bytes = fused().numel() // B
+        src = 0 if a.composite == "Depth Map" else H * W * 3
+        alg_fused = src + h * w * 4 + out_bytes                                  # per frame, the warp stage: frame + small depth + output
+        alg_parent = alg_fused + 2 * H * W * 4                                   # + the full-resolution map written once and read once
+        r = dict(view=a.composite or a.mode, model=a.model, precision=a.precision, H=H, W=W, h=h, w=w, batch=B, rounds=a.rounds, iters=a.iters,
+                 us=med, us_all=t, spread_pipeline_us=abs(med["parent"] - med["parent_again"]), spread_warp_us=abs(med["warp_parent"] - med["warp_parent_again"]),
+                 warp_bytes_per_frame=dict(parent=alg_parent, fused=alg_fused))
+        results.append(r)
+        print(f"{r['view']} {H}x{W} {a.model} {a.precision} B={B}: pipeline parent {med['parent']:9.1f} us  fused {med['fused']:9.1f} us  "
+              f"(parent again {med['parent_again']:9.1f}: spread {r['spread_pipeline_us']:.1f})   fused - parent = {med['fused'] - med['parent']:+.1f} us", flush=True)
+        print(f"    warp stage alone: upsample + warp {med['warp_parent']:8.1f} us  fused warp {med['warp_fused']:8.1f} us  "
+              f"(again {med['warp_parent_again']:8.1f}: spread {r['spread_warp_us']:.1f})   algorithmic bytes / frame: parent {alg_parent / 1e6:.1f} MB, fused {alg_fused / 1e6:.1f} MB",
+              flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(results, fh, indent=1)
+    eng.close()
+
+
+if a.pipeline:
+    pipeline_bench()
+    sys.exit(0)
 img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
 f1, d1 = torch.from_numpy(img).to(dev)[None], torch.from_numpy(dep).to(dev)[None]
 dp = ops.dibr_params(display_mode=a.mode, viewport=tuple(a.viewport) if a.viewport else (0.0, 0.0, 0.0, 0.0))
