@@ -121,6 +121,12 @@ SYMBOLS = {
     "d2s_dibr_composite": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, _P, C.c_int, _P]),
     "d2s_dibr_warp_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), _P, C.c_int, _P]),
     "d2s_dibr_composite_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, _P, C.c_int, _P]),
+    # the OpenXR movie crop (xr_viewer/crop.py:165-173, 298-435; xr_viewer/implementation.py:111-126)
+    "d2s_dibr_crop_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "d2s_dibr_warp_crop": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                     _P, C.c_int, _P]),
+    "d2s_crop_detect_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "d2s_crop_detect": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, _P]),
     "d2s_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "d2s_jpeg_encode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "d2s_present_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
@@ -138,6 +144,9 @@ SYMBOLS = {
                                        C.POINTER(PostParams), C.POINTER(SbsParams), C.c_int, _P, C.c_int, _P, _P]),
     "d2s_view_pipeline_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                             C.POINTER(PostParams), C.POINTER(DibrParams), C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "d2s_view_pipeline_crop_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                                 C.POINTER(PostParams), C.POINTER(DibrParams), C.c_int, C.POINTER(C.c_double), C.c_int, _P,
+                                                 C.c_int, _P, _P]),
     "d2s_engine_reset_stream": (C.c_int, [_P]),
     "d2s_engine_tap": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "d2s_engine_profile": (C.c_int, [_P, C.c_int]),

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libd2s_hip.so")
-SOURCES = ["core.cpp", "present.cpp", "ingest.hip", "frame_ops.hip", "dibr.hip", "dibr_composite.hip", "jpeg.hip", "post.hip", "gemm.hip", "conv3.hip", "gemm_pp.hip", "gemm_sk.hip", "vit_ops.hip", "attention.hip", "temporal.hip", "engine.hip"]
+SOURCES = ["core.cpp", "present.cpp", "ingest.hip", "frame_ops.hip", "dibr.hip", "dibr_composite.hip", "crop_detect.hip", "jpeg.hip", "post.hip", "gemm.hip", "conv3.hip", "gemm_pp.hip", "gemm_sk.hip", "vit_ops.hip", "attention.hip", "temporal.hip", "engine.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          # kernarg preload (gfx950): the first 16 argument dwords of a kernel arrive in SGPRs with the wave instead of through a cold
          # s_load -- scalar / pointer arguments up to the first by-value struct.  gemm_glds_kernel's argument order is built around it
@@ -26,7 +26,7 @@ FLAGS += os.environ.get("D2S_HIPCC_DEFS", "").split()          # tuning aids onl
 # no FMA contraction in the frame-side / post-process kernels: keeps their float32 op sequence
 # comparable with the oracle's (the matrix kernels keep the default fast contraction)
 EXTRA = {"frame_ops.hip": ["-ffp-contract=off"], "post.hip": ["-ffp-contract=off"], "ingest.hip": ["-ffp-contract=off"],
-         "dibr.hip": ["-ffp-contract=off"], "dibr_composite.hip": ["-ffp-contract=off"],
+         "dibr.hip": ["-ffp-contract=off"], "dibr_composite.hip": ["-ffp-contract=off"], "crop_detect.hip": ["-ffp-contract=off"],
          # the softmax never produces a NaN (masked scores are -1e30, exp2 of them is 0): without IEEE mode the compiler
          # drops the canonicalising v_max_f32 x, x it otherwise puts in front of every fmaxf on an MFMA result
          # (30 of ~200 VALU instructions per key tile of the batched kernel, which is VALU-bound)

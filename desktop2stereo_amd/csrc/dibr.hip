@@ -10,6 +10,7 @@
 // Line numbers in the comments below are viewer.py.
 #include "dibr_tex.h"
 #include <algorithm>
+#include <cmath>
 
 namespace d2s {
 
@@ -59,12 +60,12 @@ __device__ void push_pull(const S& smp, const DibrGeom& g,
 // They are evaluated once per output column with the left eye's offsets and handed to both eyes (dm / dp change places for the right
 // eye, |a - b| == |b - a|): 5 taps instead of 10 per column of the row kernel, the same bits.
 struct PixTaps { float d0, dA, dB, jA, jB; };      // depth at u, u - dsx(left), u + dsx(left), u - s2x(left), u + s2x(left)
-template <class S>
-__device__ __forceinline__ PixTaps pix_taps(const S& smp, const DibrGeom& g, int x, int y) {
+template <class S, class G>
+__device__ __forceinline__ PixTaps pix_taps(const S& smp, const G& g, int x, int y) {
     const float eye_offset = -g.half_ipd;
     const float sg = eye_offset > 0.f ? 1.f : (eye_offset < 0.f ? -1.f : 0.f);
     const float parx = g.c * sg;
-    const float u = ((float)x + 0.5f) / (float)g.ow, v = ((float)y + 0.5f) / (float)g.oh;
+    const float u = tex_u(g, ((float)x + 0.5f) / (float)g.ow), v = tex_v(g, ((float)y + 0.5f) / (float)g.oh);
     const float dsx = parx * g.psx * 1.5f, s2x = parx * g.psx * 2.0f;
     // (One window test for the five taps instead of a branch pair per tap: measured, no faster, 12 bytes of scratch.)
     PixTaps t;
@@ -83,13 +84,16 @@ __device__ __forceinline__ PixTaps pix_taps(const S& smp, const DibrGeom& g, int
 // FX = false: u_feather_enabled == 0 and u_corner_radius == 0 (the desktop viewer's state) as a compile-time fact.  As run-time branches
 // the two blocks depend on the column and row only, so the compiler hoists them out of the eye loop and -- free of side effects --
 // speculates them: every pixel paid for four IEEE divisions, a powf and a sqrtf it did not use (~250 of ~900 instructions of pass 1).
-template <bool DEFER = false, bool SHARED = false, bool FX = true, class S>
-__device__ __forceinline__ bool dibr_pixel(const S& smp, const DibrGeom& g, int x, int y, int eye, float outc[4], const PixTaps* sh = nullptr) {
+// G = DibrGeomCrop (the OpenXR screen shader, implementation.py:111-126): every texture coordinate -- the depth taps, the edge
+// fall-off, the shift, the in-painting, the border alpha -- follows the CROPPED uv (u, v); the rounded-corner SDF stays on the quad's
+// own uv (us, vs) and the feathering on the pixel index and u_viewport.
+template <bool DEFER = false, bool SHARED = false, bool FX = true, class S, class G>
+__device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int y, int eye, float outc[4], const PixTaps* sh = nullptr) {
     const float eye_offset = eye ? g.half_ipd : -g.half_ipd;                          // :2701, 2714
     const float sg = eye_offset > 0.f ? 1.f : (eye_offset < 0.f ? -1.f : 0.f);
     const float parx = g.c * sg, pary = g.s * sg;                                     // :540
     const float sweep_sign = eye_offset > 0.f ? -1.f : 1.f;                           // :541
-    const float u = ((float)x + 0.5f) / (float)g.ow, v = ((float)y + 0.5f) / (float)g.oh;
+    const float u = tex_u(g, ((float)x + 0.5f) / (float)g.ow), v = tex_v(g, ((float)y + 0.5f) / (float)g.oh);
     auto depth_at = [&](float su, float sv) { return smp.own_depth(su, sv); };       // (roll == 0: v - 0 * k == v, every tap below shares the row pair)
     // 3-tap depth smoothing along the parallax direction (:545-549)
     const float dsx = parx * g.psx * 1.5f, dsy = pary * g.psy * 1.5f;
@@ -145,9 +149,13 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const DibrGeom& g, int 
         float by = SMOOTHSTEP_C(-0.001f, 0.001f, sv) * SMOOTHSTEP_C(1.001f, 0.999f, sv);
         alpha = fminf(bx, by);
     }
+    // (G = DibrGeomCrop: the two blocks below depend on the column and the row alone, so the compiler forms them ahead of the eye loop
+    //  and keeps their results across the whole pixel -- 12 of the 24 bytes of scratch the FullDep row kernels with FX would have.  fx / fy are x / y made available only once the colour exists (ordered_after: no arithmetic, the same bits).)
+    int fx = x, fy = y;
+    if constexpr (FX && G::crop) { fx = ordered_after(x, col[0]); fy = ordered_after(y, col[1]); }
     if (FX && g.feather) {                                                             // :587-616
         // (gl_FragCoord.xy - u_viewport.xy) / u_viewport.zw; gl_FragCoord is y-up, pixel centres at +0.5
-        float fu = (((float)x + 0.5f) - g.vpx) / g.vpw, fv = (((float)g.oh - ((float)y + 0.5f)) - g.vpy) / g.vph, fw = g.feather_w;
+        float fu = (((float)fx + 0.5f) - g.vpx) / g.vpw, fv = (((float)g.oh - ((float)fy + 0.5f)) - g.vpy) / g.vph, fw = g.feather_w;
         float fo = smoothstepf(0.f, fw, fu) * smoothstepf(0.f, fw, 1.0f - fu) * smoothstepf(0.f, fw, fv) * smoothstepf(0.f, fw, 1.0f - fv);
         float sh = powf(fo, 0.7f);
 #pragma unroll
@@ -155,7 +163,10 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const DibrGeom& g, int 
     }
     if (FX && g.corner_r > 0.f) {
         // rounded-box SDF over the quad's own uv (the shader's inner `uv` of the feather block shadows only that block), :617-624
-        const float dx = fabsf(u - 0.5f) - 0.5f + g.corner_r, dy = fabsf(v - 0.5f) - 0.5f + g.corner_r;
+        // (with a crop the quad's own uv is formed here: the same expressions dibr_pixel starts with)
+        float qu = u, qv = v;
+        if constexpr (G::crop) { qu = ((float)fx + 0.5f) / (float)g.ow; qv = ((float)fy + 0.5f) / (float)g.oh; }
+        const float dx = fabsf(qu - 0.5f) - 0.5f + g.corner_r, dy = fabsf(qv - 0.5f) - 0.5f + g.corner_r;
         const float mx = fmaxf(dx, 0.f), my = fmaxf(dy, 0.f);
         const float sdf = sqrtf(mx * mx + my * my) + fminf(fmaxf(dx, dy), 0.f) - g.corner_r;
         alpha = fminf(alpha, 1.0f - smoothstepf(0.f, 0.01f, sdf));
@@ -171,9 +182,9 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const DibrGeom& g, int 
 // General kernel: one thread = one output pixel of one eye, every tap a global gather.  (4 pixels per thread with packed dword
 // stores measured SLOWER -- 113 -> 120 us Full-SBS, 38 -> 97 us Half-SBS at 1080p: this kernel lives on the locality of neighbouring
 // threads' gathers, not on its stores.)  ROLL0: the row pair of a pixel formed once (104.5 -> 89.5 us Full-SBS 1080p, same bits).
-template <int OUT_FMT, bool ROLL0, class D = FullDep>
+template <int OUT_FMT, bool ROLL0, class D = FullDep, class G = DibrGeom>
 __global__ void __launch_bounds__(256)
-dibr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, DibrGeom g) {
+dibr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, G g) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y % g.oh, eye = blockIdx.y / g.oh, b = blockIdx.z;
     if (x >= g.ow) return;
@@ -187,7 +198,7 @@ dibr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_a
     if constexpr (ROLL0) {
         RowSmp<D> smp;
         smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
-        smp.rc = row_ctx(dep, g.H, g.W, ((float)y + 0.5f) / (float)g.oh);     // (the v dibr_pixel forms)
+        smp.rc = row_ctx(dep, g.H, g.W, tex_v(g, ((float)y + 0.5f) / (float)g.oh));     // (the v dibr_pixel forms)
         dibr_pixel(smp, g, x, y, eye, c);
     } else {
         GenSmp<D> smp;
@@ -210,9 +221,11 @@ dibr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_a
 // queued pixels whatever their number; a block twice as wide halves those waves (and stages a window 2 x as wide once).
 // D = UpDep: the staging loop evaluates the two depth texels of a window entry from the model-resolution map (four source values
 // each, L2-resident) instead of loading them; everything after the barrier runs on the staged values as it does for FullDep.
-template <int OUT_FMT, bool FX, int COLS, class D = FullDep>
+// G = DibrGeomCrop: the block's texture row and the window's first texel follow the cropped coordinate; the reach (margin) is in
+// source texels and does not change; a window that starts left of the texture or runs past its right edge wraps as before (wrapi).
+template <int OUT_FMT, bool FX, int COLS, class D = FullDep, class G = DibrGeom>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIBR_WAVES)))
-dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, DibrGeom g, int margin, int WW) {
+dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, G g, int margin, int WW) {
     extern __shared__ float dibr_win[];                // [2][WW] the row pair of the depth texture | [6][WW] R0 G0 B0 R1 G1 B1 as floats
     __shared__ int queue[2 * COLS], qn;                // (column - xb) * 2 + eye of the pixels that need the in-painting
     const int tid = threadIdx.x, xb = blockIdx.x * COLS;
@@ -220,11 +233,11 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
     const uint8_t* rgb = rgb_all + (long)b * g.H * g.W * 3;
     const D dep = D::make(dep_all, b, g);
     if (tid == 0) qn = 0;
-    WinSmp<D> smp;
+    WinSmp<D, FX && G::crop> smp;
     smp.rgb = rgb; smp.dep = dep; smp.H = g.H; smp.W = g.W;
-    smp.rc = row_ctx(dep, g.H, g.W, ((float)y + 0.5f) / (float)g.oh);         // block-uniform (the v dibr_pixel forms)
+    smp.rc = row_ctx(dep, g.H, g.W, tex_v(g, ((float)y + 0.5f) / (float)g.oh));         // block-uniform (the v dibr_pixel forms)
     smp.dwin = dibr_win; smp.cwin = dibr_win + 2 * WW; smp.WW = WW;
-    smp.wx0 = (int)floorf((((float)xb + 0.5f) / (float)g.ow) * (float)g.W - 0.5f) - margin;
+    smp.wx0 = (int)floorf(tex_u(g, ((float)xb + 0.5f) / (float)g.ow) * (float)g.W - 0.5f) - margin;
     // (Four texels per thread -- 16-byte depth loads, 12-byte colour loads, vector LDS writes, a sixth of the load instructions -- was
     //  built and measured: 54.2 us against 51.6 at 1080p Full-SBS; a quarter of the threads then carry the whole round trip.)
 #if defined(DIBR_CUT) && (DIBR_CUT == 8 || DIBR_CUT == 10)      // (timing only: no staging, no second pass)
@@ -300,6 +313,8 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
 
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
+int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                       const double* crop, void* out, int out_fmt, void* stream, bool check_only);      // (d2s_view_pipeline_crop_streams)
 
 }  // namespace d2s
 
@@ -313,10 +328,47 @@ extern "C" int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* o
     return D2S_OK;
 }
 
+// _movie_crop_pixel_bounds (xr_viewer/crop.py:165-173): Python's round() is half-to-even = nearbyint on doubles
+static void crop_pixel_bounds(int W, int H, const double crop[4], int b[4]) {
+    auto clampi = [](long v, long lo, long hi) { return (int)std::max(lo, std::min(v, hi)); };
+    b[0] = clampi((long)nearbyint(crop[0] * W), 0, std::max(0, W - 1));
+    b[1] = clampi((long)nearbyint(crop[1] * H), 0, std::max(0, H - 1));
+    b[2] = std::max(b[0] + 1, (int)std::min((long)nearbyint((crop[0] + crop[2]) * W), (long)W));
+    b[3] = std::max(b[1] + 1, (int)std::min((long)nearbyint((crop[1] + crop[3]) * H), (long)H));
+}
+static int crop_check(const double* crop) {
+    D2S_REQUIRE(crop, "null pointer (crop)");
+    for (int i = 0; i < 4; ++i) D2S_REQUIRE(std::isfinite(crop[i]), "crop must be finite");
+    const double e = 1e-6;
+    D2S_REQUIRE(crop[0] >= -e && crop[1] >= -e, "crop x, y must be >= 0");
+    D2S_REQUIRE(crop[2] > 0.0 && crop[3] > 0.0, "crop w, h must be > 0");
+    D2S_REQUIRE(crop[0] + crop[2] <= 1.0 + e && crop[1] + crop[3] <= 1.0 + e, "crop x + w, y + h must be <= 1");
+    return D2S_OK;
+}
+// the per-eye viewport of a cropped warp: the crop's pixel size, halved by the Half modes as d2s_dibr_shape halves the frame
+static int crop_eye_shape(int H, int W, const double* crop, int display_mode, int* oh, int* ow, int* out_h, int* out_w) {
+    D2S_REQUIRE(H > 1 && W > 1, "bad shape");
+    D2S_REQUIRE(display_mode >= D2S_MODE_HALF_SBS && display_mode <= D2S_MODE_FULL_TAB, "bad display_mode");
+    int rc = crop_check(crop);
+    if (rc) return rc;
+    int b[4];
+    crop_pixel_bounds(W, H, crop, b);
+    const int ew = b[2] - b[0], eh = b[3] - b[1];
+    *oh = display_mode == D2S_MODE_HALF_TAB ? eh / 2 : eh;
+    *ow = display_mode == D2S_MODE_HALF_SBS ? ew / 2 : ew;
+    D2S_REQUIRE(*oh >= 2 && *ow >= 2, "crop: the eye viewport must be at least 2 x 2 pixels");
+    *out_h = display_mode == D2S_MODE_FULL_TAB || display_mode == D2S_MODE_HALF_TAB ? 2 * *oh : *oh;
+    *out_w = display_mode == D2S_MODE_FULL_SBS || display_mode == D2S_MODE_HALF_SBS ? 2 * *ow : *ow;
+    return D2S_OK;
+}
+
 // d2s_dibr_warp (dh == H && dw == W: depth IS the texture, the FullDep kernels) and d2s_dibr_warp_depth (any other [dh, dw]: the
 // UpDep kernels).  Every argument is checked before any HIP call.
-int d2s::dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                       void* out, int out_fmt, void* stream, bool check_only) {
+// G = DibrGeom: crop == nullptr; G = DibrGeomCrop: d2s_dibr_warp_crop.
+template <class G>
+static int dibr_warp_impl(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                          const double* crop, void* out, int out_fmt, void* stream, bool check_only) {
+    constexpr bool CR = G::crop;
     D2S_REQUIRE(rgb && depth && p && out, "null pointer");
     D2S_REQUIRE(p->struct_size == sizeof(d2s_dibr_params),
                 "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80 (header of d2s_version() >= 110; the 72-byte struct of "
@@ -326,15 +378,21 @@ int d2s::dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
     D2S_REQUIRE((long)H * W * 3 + 8 < (1L << 31) && (long)dh * dw < (1L << 31), "frame too large (32-bit texel indices)");
     D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC, "bad out_fmt (U8_HWC or F32_HWC)");
     D2S_REQUIRE(p->search_radius >= 0.f && p->search_radius < 16.f, "search_radius must be in [0,16)");
-    DibrGeom g;
+    G g;
     g.H = H; g.W = W; g.mode = p->display_mode;
     const bool up = dh != H || dw != W;
     g.dh = dh; g.dw = dw; g.dsy = linear_scale(dh, H, false); g.dsx = linear_scale(dw, W, false);      // (d2s_upsample_depth's scales)
-    int rc = d2s_dibr_shape(H, W, p->display_mode, &g.out_h, &g.out_w);
-    if (rc) return rc;
-    g.oh = p->display_mode == D2S_MODE_HALF_TAB ? H / 2 : H;
-    g.ow = p->display_mode == D2S_MODE_HALF_SBS ? W / 2 : W;
-    D2S_REQUIRE(g.oh > 0 && g.ow > 0, "frame too small for a Half mode");
+    if constexpr (CR) {
+        int rc = crop_eye_shape(H, W, crop, p->display_mode, &g.oh, &g.ow, &g.out_h, &g.out_w);
+        if (rc) return rc;
+        g.cx = (float)crop[0]; g.cy = (float)crop[1]; g.cw = (float)crop[2]; g.ch = (float)crop[3];
+    } else {
+        int rc = d2s_dibr_shape(H, W, p->display_mode, &g.out_h, &g.out_w);
+        if (rc) return rc;
+        g.oh = p->display_mode == D2S_MODE_HALF_TAB ? H / 2 : H;
+        g.ow = p->display_mode == D2S_MODE_HALF_SBS ? W / 2 : W;
+        D2S_REQUIRE(g.oh > 0 && g.ow > 0, "frame too small for a Half mode");
+    }
     g.c = cosf(p->roll); g.s = sinf(p->roll);
     g.psx = 1.0f / (p->res_w > 0.f ? p->res_w : (float)W);
     g.psy = 1.0f / (p->res_h > 0.f ? p->res_h : (float)H);
@@ -363,30 +421,37 @@ int d2s::dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
     const double reach = std::max(std::max(2.0, (double)g.search) * tex_per_px,
                                   fabs((double)g.half_ipd) * (1.0 + fabs((double)g.conv)) * fabs((double)g.strength) * (double)W);
     const int margin = (int)ceil(reach) + 2;
-    const int WW = (int)ceil(255.0 * (double)W / (double)g.ow) + 2 * margin + 4;
+    // source texels per output column: W / ow, of the cropped span with a crop (1 when the eye viewport is the crop's pixel size)
+    double tex_per_col = (double)W / (double)g.ow;
+    if constexpr (CR) tex_per_col *= (double)g.cw;
+    const int WW = (int)ceil(255.0 * tex_per_col) + 2 * margin + 4;
     if (roll0 && !no_rows.get() && WW <= 2048 && g.oh <= 65535) {
         // columns per block: 512 while the window stays <= 640 texels (20 KB of LDS: seven blocks per CU either way).  1080p Full-SBS
         // 50.8 -> 46.8 us (half the second-pass waves); Half-SBS (two source texels per column) keeps 256: 24.4 us against 26.8;
         // 1024 columns: 63.9 us (34 KB per block).  D2S_DIBR_COLS = 256 | 512 | 1024 caps it (A/B aid).
         static EnvInt cols_env{"D2S_DIBR_COLS", 512};
-        const bool wide = cols_env.get() >= 1024 && !up;       // (1024 columns is an A/B aid of the FullDep kernels only)
+        const bool wide = cols_env.get() >= 1024 && !up && !CR;       // (1024 columns is an A/B aid of the uncropped FullDep kernels only)
         int cols = wide ? 1024 : (cols_env.get() >= 512 ? 512 : 256);
-        auto win_words = [&](int c) { return (int)ceil((double)(c - 1) * (double)W / (double)g.ow) + 2 * margin + 4; };
+        auto win_words = [&](int c) { return (int)ceil((double)(c - 1) * tex_per_col) + 2 * margin + 4; };
         while (cols > 256 && (win_words(cols) > (wide ? 1536 : 640) || g.ow <= cols / 2)) cols >>= 1;   // (1536: 48 KB + the queue stay under 64 KB)
         const int WWc = win_words(cols);
         dim3 rgrid(cdiv(g.ow, cols), g.oh, batch);
         const size_t lds = (size_t)8 * WWc * sizeof(float);
         const bool fx = g.feather || g.corner_r > 0.f;
-#define DIBR_ROWS(FMT, FXV, COLS, D) hipLaunchKernelGGL((dibr_rows_kernel<FMT, FXV, COLS, D>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, g, margin, WWc)
-#define DIBR_ROWS_C(FMT, FXV) do { if (up) { if (cols == 512) DIBR_ROWS(FMT, FXV, 512, UpDep); else DIBR_ROWS(FMT, FXV, 256, UpDep); } \
-                                   else if (cols == 1024) DIBR_ROWS(FMT, FXV, 1024, FullDep); else if (cols == 512) DIBR_ROWS(FMT, FXV, 512, FullDep); \
+#define DIBR_ROWS(FMT, FXV, COLS, D) hipLaunchKernelGGL((dibr_rows_kernel<FMT, FXV, COLS, D, G>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, g, margin, WWc)
+// (the 1 024-column form exists for the uncropped FullDep kernels only: `wide` is false otherwise, and it is not instantiated with a crop)
+#define DIBR_ROWS_C(FMT, FXV) do { bool wide_done = false; \
+                                   if constexpr (!CR) { if (cols == 1024) { DIBR_ROWS(FMT, FXV, 1024, FullDep); wide_done = true; } } \
+                                   if (wide_done) break; \
+                                   if (up) { if (cols == 512) DIBR_ROWS(FMT, FXV, 512, UpDep); else DIBR_ROWS(FMT, FXV, 256, UpDep); } \
+                                   else if (cols == 512) DIBR_ROWS(FMT, FXV, 512, FullDep); \
                                    else DIBR_ROWS(FMT, FXV, 256, FullDep); } while (0)
         if (out_fmt == D2S_FMT_U8_HWC) { if (fx) DIBR_ROWS_C(D2S_FMT_U8_HWC, true); else DIBR_ROWS_C(D2S_FMT_U8_HWC, false); }
         else { if (fx) DIBR_ROWS_C(D2S_FMT_F32_HWC, true); else DIBR_ROWS_C(D2S_FMT_F32_HWC, false); }
 #undef DIBR_ROWS_C
 #undef DIBR_ROWS
     } else {
-#define DIBR_GEN(FMT, R0, D) hipLaunchKernelGGL((dibr_kernel<FMT, R0, D>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g)
+#define DIBR_GEN(FMT, R0, D) hipLaunchKernelGGL((dibr_kernel<FMT, R0, D, G>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g)
 #define DIBR_GEN_D(FMT, R0) do { if (up) DIBR_GEN(FMT, R0, UpDep); else DIBR_GEN(FMT, R0, FullDep); } while (0)
         if (out_fmt == D2S_FMT_U8_HWC) { if (roll0) DIBR_GEN_D(D2S_FMT_U8_HWC, true); else DIBR_GEN_D(D2S_FMT_U8_HWC, false); }
         else { if (roll0) DIBR_GEN_D(D2S_FMT_F32_HWC, true); else DIBR_GEN_D(D2S_FMT_F32_HWC, false); }
@@ -397,6 +462,16 @@ int d2s::dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
     return D2S_OK;
 }
 
+int d2s::dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                       void* out, int out_fmt, void* stream, bool check_only) {
+    return dibr_warp_impl<DibrGeom>(rgb, depth, dh, dw, batch, H, W, p, nullptr, out, out_fmt, stream, check_only);
+}
+int d2s::dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                            const double* crop, void* out, int out_fmt, void* stream, bool check_only) {
+    D2S_REQUIRE(crop, "null pointer (crop)");
+    return dibr_warp_impl<DibrGeomCrop>(rgb, depth, dh, dw, batch, H, W, p, crop, out, out_fmt, stream, check_only);
+}
+
 extern "C" int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, int H, int W, const d2s_dibr_params* p,
                              void* out, int out_fmt, void* stream) {
     return dibr_warp_any(rgb, depth, H, W, batch, H, W, p, out, out_fmt, stream, false);
@@ -405,4 +480,16 @@ extern "C" int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, 
 extern "C" int d2s_dibr_warp_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                                    const d2s_dibr_params* p, void* out, int out_fmt, void* stream) {
     return dibr_warp_any(rgb, depth, dh, dw, batch, H, W, p, out, out_fmt, stream, false);
+}
+
+// The OpenXR screen's cropped warp (xr_viewer/implementation.py:111-126, crop.py:165-173).
+extern "C" int d2s_dibr_crop_shape(int H, int W, const double crop[4], int display_mode, int* out_h, int* out_w) {
+    D2S_REQUIRE(out_h && out_w, "null pointer (out_h, out_w)");
+    int oh = 0, ow = 0;
+    return crop_eye_shape(H, W, crop, display_mode, &oh, &ow, out_h, out_w);
+}
+
+extern "C" int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                  const d2s_dibr_params* p, const double crop[4], void* out, int out_fmt, void* stream) {
+    return dibr_warp_crop_any(rgb, depth, dh, dw, batch, H, W, p, crop, out, out_fmt, stream, false);
 }

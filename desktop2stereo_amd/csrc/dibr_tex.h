@@ -23,7 +23,18 @@ struct DibrGeom {
     float w1[20], w2[20];  // exp(-i*0.15), exp(-i*0.2), i < 16 (the sweeps index in groups of four: up to [16..18], never used)
     int dh, dw;            // UpDep only: the [dh, dw] map the H x W depth texture is up-sampled from, and its scales
     float dsy, dsx;        //   linear_scale(dh, H, false), linear_scale(dw, W, false) as d2s_upsample_depth forms them
+    static constexpr bool crop = false;
 };
+// d2s_dibr_warp_crop: the OpenXR screen shader's u_source_crop (xr_viewer/implementation.py:111-126) as (float) of the caller's
+// doubles, the way GL receives a uniform.  A geometry TYPE of its own: the kernels are templates over it, so the instantiations
+// over DibrGeom -- every kernel that existed before the crop -- keep their argument block and their device code.
+struct DibrGeomCrop : DibrGeom {
+    float cx, cy, cw, ch;  // xy = source top-left, zw = source size, in uv of the full texture
+    static constexpr bool crop = true;
+};
+// flipped_uv = u_source_crop.xy + screen_flipped_uv * u_source_crop.zw (implementation.py:123): quad uv -> texture uv
+template <class G> __device__ __forceinline__ float tex_u(const G& g, float us) { if constexpr (G::crop) return g.cx + us * g.cw; else return us; }
+template <class G> __device__ __forceinline__ float tex_v(const G& g, float vs) { if constexpr (G::crop) return g.cy + vs * g.ch; else return vs; }
 
 // GL_REPEAT index: one conditional add / subtract covers every coordinate within one period of the texture (all but
 // absurd parallax settings); the integer modulo (~25 instructions on this ISA) is the fallback
@@ -209,6 +220,7 @@ struct GenSmp {                                    // general: every tap evaluat
     __device__ __forceinline__ float any_depth(float u, float v) const { return tex_depth(dep, H, W, u, v); }
     __device__ __forceinline__ void any_color(float u, float v, float o[3]) const { tex_color(rgb, H, W, u, v, o); }
     static constexpr bool up = std::is_same<D, UpDep>::value;
+    static constexpr bool serial_blur = up;        // push_pull_finish: the two vertical-blur taps one after the other
 };
 template <class D>
 struct RowSmp : GenSmp<D> {                        // roll == 0: the row pair is formed once per pixel
@@ -220,8 +232,11 @@ struct RowSmp : GenSmp<D> {                        // roll == 0: the row pair is
 // the staging loop; planes d0 | d1 | R0 G0 B0 | R1 G1 B1 as floats (the same byte -> float conversions the gather path makes per
 // tap).  A tap is index arithmetic + ds_read2_b32 pairs; taps that leave the window (parallax settings beyond the margin the
 // launcher sized it for) take the row gather: same values either way.
-template <class D>
+// SERIAL: take the vertical-blur taps one after the other for FullDep too (the cropped row kernels with feather / corner code: their
+// six loads requested together are 12 bytes of scratch at the 72 VGPRs of seven waves per SIMD).
+template <class D, bool SERIAL = false>
 struct WinSmp : RowSmp<D> {
+    static constexpr bool serial_blur = SERIAL || RowSmp<D>::up;
     const float* dwin;          // [2][WW]: the row pair of the depth texture
     const float* cwin;          // [6][WW]: R0 G0 B0 R1 G1 B1 as floats
     int wx0, WW;
@@ -270,7 +285,7 @@ template <class S>
 __device__ __forceinline__ void push_pull_finish(const S& smp, const DibrGeom& g, float u, float v, float cdi, const float best[3], float bw, float out[3]) {
     if (bw > 0.01f) {                                                                 // phase 3 (:484-502)
         float va[3] = {best[0] / bw * 0.5f, best[1] / bw * 0.5f, best[2] / bw * 0.5f}, vw = 0.5f;
-        if constexpr (S::up) {
+        if constexpr (S::serial_blur) {
             // UpDep: a depth tap is sixteen source loads, not two: the taps run one after the other in a loop that is not unrolled
             // (requested together they take the row kernels past their register budget into scratch).  The same values added in the
             // same order dy = -1, +1: the same bits.

@@ -1067,6 +1067,8 @@ int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int ba
                   void* out, int out_fmt, void* stream, bool check_only);
 int dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                        int composite, void* out, int out_fmt, void* stream, bool check_only);
+int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                       const double* crop, void* out, int out_fmt, void* stream, bool check_only);
 }
 
 namespace {
@@ -1146,21 +1148,25 @@ extern "C" int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int ba
     return D2S_OK;
 }
 
-extern "C" int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
-                                         const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp, int view, int use_ema,
-                                         void* out, int out_fmt, float* depth_full, void* stream) {
+// d2s_view_pipeline_streams (crop == nullptr) and d2s_view_pipeline_crop_streams: one code path, the warp differs
+static int view_pipeline_any(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
+                             const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp, int view, const double* crop,
+                             int use_ema, void* out, int out_fmt, float* depth_full, void* stream) {
     D2S_REQUIRE(frames && pp && dp && out, "null pointer");
     D2S_REQUIRE(view >= -1 && view <= D2S_COMPOSITE_DEPTH_MAP, "bad view (-1: the stereo warp, or D2S_COMPOSITE_*)");
+    D2S_REQUIRE(!crop || view == -1, "bad view with a crop (the composites are not an OpenXR path: view must be -1)");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     {   // what depends on the frame and the uniforms alone (display mode / viewport), then the engine
         int oh = 0, ow = 0;
-        RC(view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
+        RC(crop ? d2s_dibr_crop_shape(H, W, crop, dp->display_mode, &oh, &ow)
+                : view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
     }
     D2S_REQUIRE(e, "null engine");
     int stride = 1;
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
     // the warp's own refusals (struct_size, viewport, formats, limits) before anything is launched
     auto warp = [&](bool check_only) {
+        if (crop) return dibr_warp_crop_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, out, out_fmt, stream, check_only);
         return view < 0 ? dibr_warp_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, out, out_fmt, stream, check_only)
                         : dibr_composite_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, view, out, out_fmt, stream, check_only);
     };
@@ -1170,13 +1176,28 @@ extern "C" int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, i
     RC(pipeline_depth(e, frames, batch, H, W, stride, pre, pp, use_ema, depth_full, stream));
     {
         int oh = 0, ow = 0;
-        RC(view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
+        RC(crop ? d2s_dibr_crop_shape(H, W, crop, dp->display_mode, &oh, &ow)
+                : view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
         const int nch = dp->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
         double obytes = (double)oh * ow * nch * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
         const double ibytes = view == D2S_COMPOSITE_DEPTH_MAP ? 0.0 : (double)H * W * 3;
         PROF(PC_WARP, 0, batch * (ibytes + (double)e->h * e->w * 4 + obytes), warp(false));
     }
     return D2S_OK;
+}
+
+extern "C" int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W, int depth_resolution,
+                                         const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp, int view, int use_ema,
+                                         void* out, int out_fmt, float* depth_full, void* stream) {
+    return view_pipeline_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, view, nullptr, use_ema, out, out_fmt, depth_full, stream);
+}
+
+extern "C" int d2s_view_pipeline_crop_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                              int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                              const d2s_dibr_params* dp, int view, const double* crop, int use_ema, void* out, int out_fmt,
+                                              float* depth_full, void* stream) {
+    D2S_REQUIRE(crop, "null pointer (crop)");
+    return view_pipeline_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, view, crop, use_ema, out, out_fmt, depth_full, stream);
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

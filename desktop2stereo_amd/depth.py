@@ -307,8 +307,18 @@ def composite_view(rgb, depth, display_mode, ipd_uv=0.064, depth_ratio=2.0, conv
     return ops.dibr_composite(frames, d.to(device=_device()), dp, display_mode, out_u8=False).cpu().numpy()
 
 
+def movie_crop(stream: int = 0):
+    """The MovieCrop (crop.py) that pipeline(inpaint=True, crop="auto") keeps for stream slot `stream`: its mode ("auto" | "manual" |
+    "off"), set_manual, detection interval and state are the caller's to set."""
+    from .crop import MovieCrop
+    slots = _state.setdefault("movie_crops", {})
+    if int(stream) not in slots:
+        slots[int(stream)] = MovieCrop()
+    return slots[int(stream)]
+
+
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,
-             viewport=None):
+             viewport=None, crop=None):
     """Batched predict_depth + make_sbs: uint8 [B,H,W,3] (numpy or device tensor) -> device tensor
     [B,H',W',3] (uint8, or float32 when out_u8=False) in one stream-ordered native call.
     Video-Depth-Anything: frame r is the next frame of stream `streams[r]` (distinct slots < max_batch; None: streams 0..B-1);
@@ -318,7 +328,15 @@ def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, 
     display_mode of "Anaglyph" | "Interleaved" | "Interleaved-V" | "Depth Map" renders that composite (composite_view) over
     `viewport` = (x, y, w, h) in window pixels, None = the frame.  Their uniforms are ops.dibr_params(ipd, depth_strength,
     convergence, ...) of the configured parameters; fill_16_9 is a window-layout matter of the torch warp and is ignored on
-    this path."""
+    this path.
+    crop (inpaint=True with an SBS / TAB display_mode only): the OpenXR screen's source crop (reference xr_viewer/crop.py,
+    implementation.py:111-126).  (x, y, w, h) in uv, top-left origin: that rectangle; each eye is its pixel size.  "auto": one
+    MovieCrop per stream slot (movie_crop(slot)) -- every call polls the slot's pending detection and, when its interval has passed,
+    launches the next one on the frame's stream; the crop in force is the last accepted one, so detection never blocks the frame.
+    When the slots of a batch disagree on the crop the rows have different sizes: the result is then a list of B [1,H',W',C]
+    tensors (with want_depth: (list, depth)), one call per row in row order.  On a Video-Depth-Anything engine row r names its own
+    slot (streams[r], or r) in that call, so each slot's temporal window and EMA state advance exactly as in the one-call form; on a
+    Depth-Anything-v2 engine there are no slots and the EMA is the in-order chain over the rows either way."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -334,8 +352,31 @@ def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, 
             dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, viewport=vp)
         else:
             dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, mode, viewport=vp)
+        if crop is not None:
+            if mode in _lib.COMPOSITE:
+                raise ValueError("pipeline(crop=...): the composite display modes are not an OpenXR path")
+            slots = list(range(B)) if streams is None else [int(v) for v in streams]
+            if isinstance(crop, str):
+                if crop != "auto":
+                    raise ValueError('crop must be None, (x, y, w, h) or "auto"')
+                crops = []
+                for r, slot in enumerate(slots):
+                    mc = movie_crop(slot)
+                    mc.update(t[r])
+                    crops.append(tuple(mc.crop_uv))
+            else:
+                crops = [tuple(float(v) for v in crop)] * B
+            if all(c == crops[0] for c in crops):
+                return eng.view_pipeline_crop(t, p, dp, crops[0], use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
+                                              streams=streams)
+            rows = [eng.view_pipeline_crop(t[r:r + 1], p, dp, crops[r], use_ema=use_temporal_smooth, out_u8=out_u8,
+                                           want_depth=want_depth, streams=[slots[r]] if _state.get("temporal", False) else None)
+                    for r in range(B)]
+            return ([o for o, _ in rows], torch.cat([d for _, d in rows])) if want_depth else rows
         return eng.view_pipeline(t, p, dp, view=mode if mode in _lib.COMPOSITE else None, use_ema=use_temporal_smooth, out_u8=out_u8,
                                  want_depth=want_depth, streams=streams)
+    if crop is not None:
+        raise ValueError("pipeline(crop=...) belongs to the Viewer's stereo warp (inpaint=True)")
     if viewport is not None:
         raise ValueError("pipeline(viewport=...) belongs to the Viewer's warps (inpaint=True or a composite display_mode)")
     sp = ops.sbs_params(p.ipd, p.depth_strength, p.convergence, mode, p.fill_16_9)

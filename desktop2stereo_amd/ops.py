@@ -289,10 +289,69 @@ def dibr_params(ipd_uv=0.064, depth_ratio=1.0, convergence=0.0, display_mode="Fu
                            C.sizeof(_lib.DibrParams))
 
 
-def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", out_u8: bool = True) -> torch.Tensor:
+def _crop4(crop) -> "C.Array":
+    if len(crop) != 4:
+        raise ValueError("crop must be (x, y, w, h) in uv of the source, top-left origin")
+    return (C.c_double * 4)(*[float(v) for v in crop])
+
+
+def dibr_crop_shape(H: int, W: int, crop, display_mode: int) -> Tuple[int, int]:
+    oh, ow = C.c_int(), C.c_int()
+    check(_lib.load().d2s_dibr_crop_shape(H, W, _crop4(crop), display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_crop_shape")
+    return oh.value, ow.value
+
+
+_CROP_WS: Dict[Tuple, torch.Tensor] = {}
+
+
+def crop_detect_workspace(B: int, H: int, W: int, device) -> torch.Tensor:
+    """A workspace for crop_detect(workspace=) on [B,.,H,W] frames: the detector's partial sums live there between its two launches, so
+    calls that may overlap (different streams) must not share one."""
+    nbytes = C.c_uint64()
+    check(_lib.load().d2s_crop_detect_workspace(B, H, W, C.byref(nbytes)), "d2s_crop_detect_workspace")
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def crop_detect(frames: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The OpenXR viewer's letterbox / pillarbox detector (reference xr_viewer/crop.py:368-435, tensor path): device frames, uint8
+    [B,H,W,3] / uint8 [B,3,H,W] / float32 [B,3,H,W] (or one frame without the batch axis) -> device float32 [B,6] (or [6]) =
+    (top_i, bottom_count, center_mean, center_bright, left_i, right_count) per frame, two launches on the current stream, no
+    synchronisation.  crop.crop_from_stats turns a row into the crop rectangle.  out: a caller-kept [B,6] float32 device tensor.
+    workspace: a caller-kept crop_detect_workspace (MovieCrop owns one per capture); None: one kept here per (device, current
+    stream, batch, size) -- calls on one stream are ordered, calls on different streams never share partial sums."""
+    _need_cuda(frames, "frames")
+    fmt, B, H, W = _frame_fmt(frames)
+    batched = frames.dim() == 4
+    f = frames.contiguous()
+    lib = _lib.load()
+    nbytes = C.c_uint64()
+    check(lib.d2s_crop_detect_workspace(B, H, W, C.byref(nbytes)), "d2s_crop_detect_workspace")
+    if workspace is not None:
+        ws = workspace
+        if not ws.is_cuda or ws.device != f.device or not ws.is_contiguous() or ws.numel() * ws.element_size() < nbytes.value:
+            raise ValueError(f"crop_detect: workspace must be a contiguous tensor of >= {nbytes.value} bytes on {f.device}")
+    else:
+        key = (f.device, torch.cuda.current_stream(f.device).cuda_stream, B, H, W)
+        ws = _CROP_WS.get(key)
+        if ws is None:
+            if len(_CROP_WS) >= 16:      # (capture sizes come and go; a workspace is ~0.1 MB per frame)
+                _CROP_WS.clear()
+            ws = _CROP_WS[key] = torch.empty(nbytes.value, dtype=torch.uint8, device=f.device)
+    if out is None:
+        out = torch.empty((B, 6), dtype=torch.float32, device=f.device)
+    elif not out.is_cuda or out.device != f.device or out.dtype != torch.float32 or out.numel() != B * 6 or not out.is_contiguous():
+        raise ValueError(f"crop_detect: out must be a contiguous float32 [{B},6] tensor on {f.device}")
+    with _on(f.device) as st:
+        check(lib.d2s_crop_detect(_ptr(f), fmt, B, H, W, _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), st), "d2s_crop_detect")
+    return out if batched else out.view(-1)
+
+
+def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", out_u8: bool = True, crop=None) -> torch.Tensor:
     """f1 (reference viewer.py:386-631): uint8 HWC frames [B,H,W,3] or [H,W,3] + depth [B,dh,dw] or [dh,dw] -> both eyes
     with disocclusion in-painting, packed per dp.display_mode.  Depth of the frame's size is the shader's depth texture itself;
-    any other size (the model's) is up-sampled inside the kernel, bit-identical to upsample_depth(depth, H, W) first."""
+    any other size (the model's) is up-sampled inside the kernel, bit-identical to upsample_depth(depth, H, W) first.
+    crop = (x, y, w, h) in uv, top-left origin: the OpenXR screen shader's u_source_crop (xr_viewer/implementation.py:111-126) --
+    each eye is the crop's pixel size (crop.pixel_bounds), the texture taps follow the cropped coordinate."""
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
@@ -307,11 +366,19 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
     dh, dw = d.shape[1:]
     lib = _lib.load()
     oh, ow = C.c_int(), C.c_int()
-    check(lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
+    if crop is not None:
+        c4 = _crop4(crop)
+        check(lib.d2s_dibr_crop_shape(H, W, c4, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_crop_shape")
+    else:
+        check(lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
     nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
     out = torch.empty((B, oh.value, ow.value, nch), dtype=torch.uint8 if out_u8 else torch.float32, device=f.device)
     _same_device(f, d, "dibr_warp")
     with _on(f.device) as st:
+        if crop is not None:
+            check(lib.d2s_dibr_warp_crop(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), c4, _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st),
+                  "d2s_dibr_warp_crop")
+            return out if batched else out[0]
         check(lib.d2s_dibr_warp_depth(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st),
               "d2s_dibr_warp_depth")
     return out if batched else out[0]
@@ -573,6 +640,36 @@ class Engine:
                                                      C.byref(pre), C.byref(pp), C.byref(dp), -1 if view is None else _lib.COMPOSITE[view],
                                                      int(use_ema), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC,
                                                      _ptr(depth) if want_depth else None, st), "d2s_view_pipeline_streams")
+        return (out, depth) if want_depth else out
+
+    def view_pipeline_crop(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", crop, use_ema: bool = False,
+                           out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
+        """view_pipeline(view=None) with the OpenXR screen's source crop (d2s_view_pipeline_crop_streams): crop = (x, y, w, h) in uv,
+        top-left origin, one rectangle for the batch; each eye is the crop's pixel size.  Bit-identical to pipeline(want_depth=True)'s
+        engine depth followed by dibr_warp(crop=).  (A method of its own: view_pipeline's parameter list is pinned by the ABI tests.)"""
+        self._mine(frames, "frames")
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError("frames must be uint8 [B,H,W,3]")
+        frames = frames.contiguous()
+        B, H, W, _ = frames.shape
+        c4 = _crop4(crop)
+        oh, ow = dibr_crop_shape(H, W, crop, dp.display_mode)
+        nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+        want = ((B, oh, ow, nch), torch.uint8 if out_u8 else torch.float32)
+        if out is None:
+            out = torch.empty(want[0], dtype=want[1], device=frames.device)
+        else:
+            self._mine(out, "out")
+            if out.numel() != B * oh * ow * nch or out.dtype != want[1] or not out.is_contiguous():
+                raise ValueError(f"view_pipeline_crop: out must be a contiguous {want[1]} tensor of {want[0]}")
+        depth = torch.empty((B, H, W), dtype=torch.float32, device=frames.device) if want_depth else None
+        pp = post_params(p)
+        pre = pre_params(p.mean, p.std, p.resample, p.square_input)
+        with _on(self.device) as st:
+            check(self.lib.d2s_view_pipeline_crop_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution,
+                                                          C.byref(pre), C.byref(pp), C.byref(dp), -1, c4, int(use_ema), _ptr(out),
+                                                          FMT_U8_HWC if out_u8 else FMT_F32_HWC, _ptr(depth) if want_depth else None, st),
+                  "d2s_view_pipeline_crop_streams")
         return (out, depth) if want_depth else out
 
     def close(self):

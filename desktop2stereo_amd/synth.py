@@ -4,6 +4,7 @@ S1 ``noise_frame``      : uniform uint8 noise -- worst case for the warp's gathe
 S2 ``structured_frame`` : smooth gradients + filled rectangles / discs, so the depth field and the
                           percentile normalisation downstream are well conditioned (parity runs).
 ``smooth_depth``        : a smooth [0,1] depth map with a few step edges, for warp-only tests.
+``letterbox_frame``     : a structured frame inside letterbox / pillarbox bars, for the movie-crop detector.
 (SURVEY.md section 8d "Synthetic inputs".)
 """
 from __future__ import annotations
@@ -59,3 +60,32 @@ def dibr_scene(h: int, w: int, seed: int, kind: str = "boxes"):
             hh, ww = int(rng.integers(h // 8, h // 3)), int(rng.integers(w // 10, w // 3))
             dep[y0:y0 + hh, x0:x0 + ww] = np.float32(0.05 + 0.1 * k)
     return img, np.clip(dep, 0, 1).astype(np.float32)
+
+
+def letterbox_frame(h: int, w: int, seed: int = 0, top: int = 0, bottom: int = 0, left: int = 0, right: int = 0,
+                    bar: str = "black", dark_centre: bool = False) -> np.ndarray:
+    """uint8 [h,w,3]: structured_frame content of (h - top - bottom) x (w - left - right) pixels inside bars of the given widths --
+    a letterboxed / pillarboxed film as the OpenXR viewer's movie-crop detector sees it.  bar: "black" (0), "noisy" (a grey level with
+    sigma-2 noise: still `uniform` to the detector, luma std < 6), "solid" (one colour) or "gradient" (a ramp along every bar line,
+    luma std ~ 10: NOT uniform, so nothing is detected).  dark_centre: the middle third of the rows is black (the detector's centre
+    brightness vote then refuses the top / bottom crop).  The recipe behind tests/golden/crop_detect.npz."""
+    g = np.random.default_rng(3000 + seed)
+    if bar == "black":
+        img = np.zeros((h, w, 3), np.float32)
+    elif bar == "noisy":
+        img = 16.0 + g.normal(0.0, 2.0, (h, w, 3)).astype(np.float32)
+    elif bar == "solid":
+        img = np.broadcast_to(g.integers(20, 200, 3).astype(np.float32), (h, w, 3)).copy()
+    elif bar == "gradient":
+        yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+        img = 35.0 * np.repeat(((xx * 6.0 / max(w - 1, 1) + yy * 6.0 / max(h - 1, 1)) % 1.0)[..., None], 3, -1)
+    else:
+        raise ValueError('bar must be "black", "noisy", "solid" or "gradient"')
+    ih, iw = h - top - bottom, w - left - right
+    if ih <= 0 or iw <= 0:
+        raise ValueError("the bars leave no picture")
+    inner = structured_frame(ih, iw, seed).astype(np.float32)
+    if dark_centre:
+        inner[max(0, h // 3 - top): max(0, h - h // 3 - top)] = 0.0
+    img[top:top + ih, left:left + iw] = inner
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)

@@ -305,6 +305,33 @@ int d2s_dibr_warp(const uint8_t* rgb, const float* depth, int batch, int H, int 
 int d2s_dibr_warp_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                         const d2s_dibr_params* p, void* out, int out_fmt, void* stream);
 
+/* The OpenXR viewer's automatic movie crop (d2s_version() >= 114), application half: the OpenXR screen shader is FRAGMENT_SHADER with
+ * one line changed (xr_viewer/implementation.py:111-126): flipped_uv = u_source_crop.xy + screen_flipped_uv * u_source_crop.zw.
+ * crop = (x, y, w, h) in uv of the source, top-left origin, as u_source_crop; the kernel sees (float) of each, as GL does.  The depth
+ * taps, the 5 % edge fall-off (relative to the FULL source), the parallax shift, the in-painting and the border alpha follow the
+ * cropped texture coordinate; the rounded-corner SDF and the feathering stay on the quad's uv / p->viewport.  Each eye is rendered
+ * into the crop's pixel size (x1 - x0) x (y1 - y0) of _movie_crop_pixel_bounds (xr_viewer/crop.py:165-173; round() there is
+ * half-to-even: nearbyint on doubles here), halved by the Half modes as d2s_dibr_shape halves the frame, so the texel : pixel ratio
+ * stays 1; packed as d2s_dibr_warp packs.  Refused (nothing launched): a non-finite value; x, y < 0, w, h <= 0, x + w or y + h > 1
+ * (1e-6 of slack); an eye viewport under 2 x 2 pixels; everything d2s_dibr_warp_depth refuses.  crop = (0, 0, 1, 1) is bit-identical
+ * to d2s_dibr_warp_depth.  Pinned by tests/golden/xr_crop.npz: the reference's XR shader run off-screen (make_golden_xr_crop.py). */
+int d2s_dibr_crop_shape(int H, int W, const double crop[4], int display_mode, int* out_h, int* out_w);
+int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                       const d2s_dibr_params* p, const double crop[4], void* out, int out_fmt, void* stream);
+
+/* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
+ * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
+ * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.
+ * stats: device float [batch][6] = (top_i, bottom_count, center_mean, center_bright, left_i, right_count), exactly stats_t of
+ * crop.py:413: the leading / trailing run lengths of sampled rows resp. columns whose unbiased luma std is < 6, and the mean luma /
+ * mean `luma > 20` fraction of the sampled rows of the middle 30 %.  Host integer logic turns them into a crop rectangle
+ * (desktop2stereo_amd/crop.py crop_from_stats = _movie_crop_from_stats, crop.py:235-296).  workspace: device, 4-byte aligned, at
+ * least d2s_crop_detect_workspace bytes.  H < 64 or W < 64 is refused (the reference returns the identity crop before sampling,
+ * crop.py:369).  Every argument is checked before any HIP call. */
+int d2s_crop_detect_workspace(int batch, int H, int W, uint64_t* bytes);
+int d2s_crop_detect(const void* frames, int fmt, int batch, int H, int W, float* stats /* device [batch][6] */,
+                    void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* The viewer's other four `Display Mode`s (gui.py:1666, viewer.py:1340), each one program the reference runs over its letter-boxed
  * viewport (viewer.py:2604-2662: u_eye_offset = +ipd_uv/2, u_depth_strength = 0.1 * depth_ratio, blending off):
  *   ANAGLYPH       ANAGLYPH_FRAGMENT (viewer.py:678-832): both eyes per pixel, no depth shaping, hard disocclusion test
@@ -395,6 +422,13 @@ int d2s_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const 
 int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
                               int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
                               int view, int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
+/* d2s_view_pipeline_streams with the OpenXR screen's source crop (d2s_version() >= 114; xr_viewer/implementation.py:111-126): the
+ * same pipeline_check + depth code path, then d2s_dibr_warp_crop on the engine's model-resolution depth (shape: d2s_dibr_crop_shape).
+ * view must be -1: the composites are not an OpenXR path and are refused with a crop.  Bit-identical to d2s_pipeline(depth_full)
+ * followed by d2s_dibr_warp_crop on the engine's map. */
+int d2s_view_pipeline_crop_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                   int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
+                                   int view, const double* crop, int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

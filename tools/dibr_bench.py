@@ -6,7 +6,14 @@
         frames -> views end to end: Engine.view_pipeline (the warp reads the model-resolution depth) against the two-call path it
         replaces (Engine.pipeline(want_depth=True) for the full-resolution depth map, then dibr_warp / dibr_composite on it), alternated
         in one process with inputs resident, device events; the parent is also timed against itself (the run-to-run spread), and
-        the warp stage alone is timed both ways (upsample_depth + warp on the full map against the warp on the small map)."""
+        the warp stage alone is timed both ways (upsample_depth + warp on the full map against the warp on the small map).
+    python tools/dibr_bench.py --crop [X Y W H] [--corner-radius 0.03]
+        d2s_dibr_warp_crop (the OpenXR screen's source crop; default: the 2.39:1 letterbox of a 16:9 frame) against the UNCROPPED
+        d2s_dibr_warp_depth on a frame of the crop's pixel size, alternated in one process, us per launch and ns per output pixel.
+        Both sides run THIS library (the uncropped kernels' device code does not change with the crop).  A library of
+        the parent commit cannot be put under this mode with D2S_LIB -- it has no d2s_dibr_warp_crop, and D2S_LIB replaces the
+        library of the whole process; to time the parent, run its own checkout's `tools/dibr_bench.py --height <eye rows>` (and the
+        plain `tools/dibr_bench.py` for the uncropped 1080p warp) alternated with this one on the same box."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,6 +30,8 @@ ap.add_argument("--model", default="vitb"); ap.add_argument("--precision", defau
 ap.add_argument("--depth-resolution", type=int, default=518)
 ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--json", default=None, help="--pipeline: also write the figures to this file")
+ap.add_argument("--crop", type=float, nargs="*", default=None, help="time d2s_dibr_warp_crop: x y w h in uv (no values: a 2.39:1 letterbox)")
+ap.add_argument("--corner-radius", type=float, default=0.0, help="--crop: u_corner_radius (0.03 is the OpenXR screen's)")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -100,6 +109,36 @@ def pipeline_bench():
 
 if a.pipeline:
     pipeline_bench()
+    sys.exit(0)
+if a.crop is not None:
+    from desktop2stereo_amd import crop as K
+    if len(a.crop) not in (0, 4):
+        sys.exit("--crop takes no values or x y w h")
+    bar = round((a.height - a.width / 2.39) / 2) + max(2, min(8, round(a.height * 0.004)))
+    crop = tuple(a.crop) if a.crop else (0.0, bar / a.height, 1.0, (a.height - 2 * bar) / a.height)
+    x0, y0, x1, y1 = K.pixel_bounds(a.width, a.height, crop)
+    img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
+    dp = ops.dibr_params(display_mode=a.mode, corner_radius=a.corner_radius, alpha="rgba" if a.corner_radius > 0 else "window")
+    for B in a.batch:
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        fc, dc = f[:, y0:y1, x0:x1].contiguous(), d[:, y0:y1, x0:x1].contiguous()
+        runs = {"cropped": lambda: ops.dibr_warp(f, d, dp, crop=crop), "uncropped_at_crop_size": lambda: ops.dibr_warp(fc, dc, dp)}
+        px = {k: fn().numel() // fn().shape[-1] for k, fn in runs.items()}
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"{a.mode} {a.height}x{a.width} crop {tuple(round(c, 4) for c in crop)} -> eye {y1 - y0}x{x1 - x0} B={B}: " +
+              "  ".join(f"{k} {med[k]:8.1f} us ({1e3 * med[k] / px[k]:.4f} ns / output pixel)" for k in runs) +
+              f"   cropped / uncropped per pixel = {med['cropped'] / px['cropped'] / (med['uncropped_at_crop_size'] / px['uncropped_at_crop_size']):.3f}",
+              flush=True)
     sys.exit(0)
 img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
 f1, d1 = torch.from_numpy(img).to(dev)[None], torch.from_numpy(dep).to(dev)[None]
