@@ -322,10 +322,8 @@ using namespace d2s;
 
 extern "C" int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* out_w) {
     D2S_REQUIRE(out_h && out_w && H > 0 && W > 0, "bad argument");
-    D2S_REQUIRE(display_mode >= D2S_MODE_HALF_SBS && display_mode <= D2S_MODE_FULL_TAB, "bad display_mode");
-    *out_h = display_mode == D2S_MODE_FULL_TAB ? 2 * H : (display_mode == D2S_MODE_HALF_TAB ? (H / 2) * 2 : H);
-    *out_w = display_mode == D2S_MODE_FULL_SBS ? 2 * W : (display_mode == D2S_MODE_HALF_SBS ? (W / 2) * 2 : W);
-    return D2S_OK;
+    int oh = 0, ow = 0;
+    return dibr_eye_shape(H, W, display_mode, &oh, &ow, out_h, out_w);
 }
 
 // _movie_crop_pixel_bounds (xr_viewer/crop.py:165-173): Python's round() is half-to-even = nearbyint on doubles
@@ -348,17 +346,13 @@ static int crop_check(const double* crop) {
 // the per-eye viewport of a cropped warp: the crop's pixel size, halved by the Half modes as d2s_dibr_shape halves the frame
 static int crop_eye_shape(int H, int W, const double* crop, int display_mode, int* oh, int* ow, int* out_h, int* out_w) {
     D2S_REQUIRE(H > 1 && W > 1, "bad shape");
-    D2S_REQUIRE(display_mode >= D2S_MODE_HALF_SBS && display_mode <= D2S_MODE_FULL_TAB, "bad display_mode");
     int rc = crop_check(crop);
     if (rc) return rc;
     int b[4];
     crop_pixel_bounds(W, H, crop, b);
-    const int ew = b[2] - b[0], eh = b[3] - b[1];
-    *oh = display_mode == D2S_MODE_HALF_TAB ? eh / 2 : eh;
-    *ow = display_mode == D2S_MODE_HALF_SBS ? ew / 2 : ew;
+    rc = dibr_eye_shape(b[3] - b[1], b[2] - b[0], display_mode, oh, ow, out_h, out_w);
+    if (rc) return rc;
     D2S_REQUIRE(*oh >= 2 && *ow >= 2, "crop: the eye viewport must be at least 2 x 2 pixels");
-    *out_h = display_mode == D2S_MODE_FULL_TAB || display_mode == D2S_MODE_HALF_TAB ? 2 * *oh : *oh;
-    *out_w = display_mode == D2S_MODE_FULL_SBS || display_mode == D2S_MODE_HALF_SBS ? 2 * *ow : *ow;
     return D2S_OK;
 }
 
@@ -370,71 +364,39 @@ static int dibr_warp_impl(const uint8_t* rgb, const float* depth, int dh, int dw
                           const double* crop, void* out, int out_fmt, void* stream, bool check_only) {
     constexpr bool CR = G::crop;
     D2S_REQUIRE(rgb && depth && p && out, "null pointer");
-    D2S_REQUIRE(p->struct_size == sizeof(d2s_dibr_params),
-                "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80 (header of d2s_version() >= 110; the 72-byte struct of "
-                "version 100 has no alpha_mode)");
-    D2S_REQUIRE(batch > 0 && H > 1 && W > 1, "bad shape");
-    D2S_REQUIRE(dh > 0 && dw > 0, "bad depth shape (dh, dw > 0)");
-    D2S_REQUIRE((long)H * W * 3 + 8 < (1L << 31) && (long)dh * dw < (1L << 31), "frame too large (32-bit texel indices)");
-    D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC, "bad out_fmt (U8_HWC or F32_HWC)");
-    D2S_REQUIRE(p->search_radius >= 0.f && p->search_radius < 16.f, "search_radius must be in [0,16)");
+    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
+    if (rc) return rc;
     G g;
-    g.H = H; g.W = W; g.mode = p->display_mode;
+    dibr_fill_geom(g, p, H, W, dh, dw);
+    g.mode = p->display_mode;
     const bool up = dh != H || dw != W;
-    g.dh = dh; g.dw = dw; g.dsy = linear_scale(dh, H, false); g.dsx = linear_scale(dw, W, false);      // (d2s_upsample_depth's scales)
-    if constexpr (CR) {
-        int rc = crop_eye_shape(H, W, crop, p->display_mode, &g.oh, &g.ow, &g.out_h, &g.out_w);
-        if (rc) return rc;
-        g.cx = (float)crop[0]; g.cy = (float)crop[1]; g.cw = (float)crop[2]; g.ch = (float)crop[3];
-    } else {
-        int rc = d2s_dibr_shape(H, W, p->display_mode, &g.out_h, &g.out_w);
-        if (rc) return rc;
-        g.oh = p->display_mode == D2S_MODE_HALF_TAB ? H / 2 : H;
-        g.ow = p->display_mode == D2S_MODE_HALF_SBS ? W / 2 : W;
-        D2S_REQUIRE(g.oh > 0 && g.ow > 0, "frame too small for a Half mode");
-    }
-    g.c = cosf(p->roll); g.s = sinf(p->roll);
-    g.psx = 1.0f / (p->res_w > 0.f ? p->res_w : (float)W);
-    g.psy = 1.0f / (p->res_h > 0.f ? p->res_h : (float)H);
-    g.half_ipd = (float)(p->ipd_uv / 2.0);                                            // viewer.py:2701
-    g.strength = p->depth_strength; g.conv = p->convergence;
-    g.tol = p->depth_tolerance; g.blur = p->blur_radius; g.feather_w = p->feather_width;
-    g.search = (int)p->search_radius; g.feather = p->feather_enabled != 0;
-    D2S_REQUIRE(p->corner_radius >= 0.f && p->corner_radius <= 0.5f, "corner_radius must be in [0, 0.5]");
-    g.corner_r = p->corner_radius;
-    D2S_REQUIRE(p->alpha_mode >= D2S_DIBR_ALPHA_WINDOW && p->alpha_mode <= D2S_DIBR_ALPHA_RGBA, "bad alpha_mode");
-    g.alpha_mode = p->alpha_mode;
+    rc = CR ? crop_eye_shape(H, W, crop, p->display_mode, &g.oh, &g.ow, &g.out_h, &g.out_w)
+            : dibr_eye_shape(H, W, p->display_mode, &g.oh, &g.ow, &g.out_h, &g.out_w);
+    if (rc) return rc;
+    if constexpr (CR) { g.cx = (float)crop[0]; g.cy = (float)crop[1]; g.cw = (float)crop[2]; g.ch = (float)crop[3]; }
     const bool vp0 = p->viewport[2] == 0.f && p->viewport[3] == 0.f;
     D2S_REQUIRE(vp0 || (p->viewport[2] > 0.f && p->viewport[3] > 0.f), "viewport width / height must be positive (or all zero)");
     g.vpx = vp0 ? 0.f : p->viewport[0]; g.vpy = vp0 ? 0.f : p->viewport[1];
     g.vpw = vp0 ? (float)g.ow : p->viewport[2]; g.vph = vp0 ? (float)g.oh : p->viewport[3];
-    for (int i = 0; i < 20; ++i) { g.w1[i] = i < 16 ? expf((float)(-i * 0.15)) : 0.f; g.w2[i] = i < 16 ? expf((float)(-i * 0.2)) : 0.f; }
-    D2S_REQUIRE(2 * g.oh <= 65535 && batch <= 65535, "frame / batch too large for one launch");
+    D2S_REQUIRE(2 * g.oh <= 65535, "frame too large for one launch");
     if (check_only) return D2S_OK;
     dim3 grid(cdiv(g.ow, 256), 2 * g.oh, batch), block(256);
     static EnvInt no_roll0{"D2S_DIBR_NO_ROLL0", 0};        // (A/B aids: the general per-tap evaluation for roll == 0 too;
-    static EnvInt no_rows{"D2S_DIBR_NO_ROWS", 0};          //  the gather kernel instead of the LDS-window kernel)
+    static EnvInt no_rows{"D2S_DIBR_NO_ROWS", 0};          //  the gather kernel instead of the LDS-window kernel;
+    static EnvInt cols_env{"D2S_DIBR_COLS", 512};          //  256 | 512 | 1024 caps the columns per block)
     const bool roll0 = g.s == 0.f && g.c == 1.f && !no_roll0.get();
-    // LDS-window kernel: how far from its own texel a pixel's same-row taps can land -- the sweeps (search texels of pixel_size.x),
-    // the +-2 pixel_size confidence taps, the parallax shift (|shaped| <= 1 for depth in 0..1) -- in texels of the source
-    const double tex_per_px = (double)W * (double)g.psx;
-    const double reach = std::max(std::max(2.0, (double)g.search) * tex_per_px,
-                                  fabs((double)g.half_ipd) * (1.0 + fabs((double)g.conv)) * fabs((double)g.strength) * (double)W);
-    const int margin = (int)ceil(reach) + 2;
     // source texels per output column: W / ow, of the cropped span with a crop (1 when the eye viewport is the crop's pixel size)
     double tex_per_col = (double)W / (double)g.ow;
     if constexpr (CR) tex_per_col *= (double)g.cw;
-    const int WW = (int)ceil(255.0 * tex_per_col) + 2 * margin + 4;
-    if (roll0 && !no_rows.get() && WW <= 2048 && g.oh <= 65535) {
-        // columns per block: 512 while the window stays <= 640 texels (20 KB of LDS: seven blocks per CU either way).  1080p Full-SBS
-        // 50.8 -> 46.8 us (half the second-pass waves); Half-SBS (two source texels per column) keeps 256: 24.4 us against 26.8;
-        // 1024 columns: 63.9 us (34 KB per block).  D2S_DIBR_COLS = 256 | 512 | 1024 caps it (A/B aid).
-        static EnvInt cols_env{"D2S_DIBR_COLS", 512};
-        const bool wide = cols_env.get() >= 1024 && !up && !CR;       // (1024 columns is an A/B aid of the uncropped FullDep kernels only)
-        int cols = wide ? 1024 : (cols_env.get() >= 512 ? 512 : 256);
-        auto win_words = [&](int c) { return (int)ceil((double)(c - 1) * tex_per_col) + 2 * margin + 4; };
-        while (cols > 256 && (win_words(cols) > (wide ? 1536 : 640) || g.ow <= cols / 2)) cols >>= 1;   // (1536: 48 KB + the queue stay under 64 KB)
-        const int WWc = win_words(cols);
+    // columns per block: 512 while the window stays <= 640 texels (20 KB of LDS: seven blocks per CU either way).  1080p Full-SBS
+    // 50.8 -> 46.8 us (half the second-pass waves); Half-SBS (two source texels per column) keeps 256: 24.4 us against 26.8;
+    // 1024 columns: 63.9 us (34 KB per block), an A/B aid of the uncropped FullDep kernels only, up to 1536 texels (48 KB).
+    // Windows above 2048 texels take the gather kernel.
+    const bool wide = cols_env.get() >= 1024 && !up && !CR;
+    const DibrWindow win = dibr_plan_window(g, tex_per_col, roll0 && !no_rows.get(), wide ? 1024 : (cols_env.get() >= 512 ? 512 : 256),
+                                            wide ? 1536 : 640, 2048);
+    if (win.rows) {
+        const int margin = win.margin, cols = win.cols, WWc = win.WW;
         dim3 rgrid(cdiv(g.ow, cols), g.oh, batch);
         const size_t lds = (size_t)8 * WWc * sizeof(float);
         const bool fx = g.feather || g.corner_r > 0.f;

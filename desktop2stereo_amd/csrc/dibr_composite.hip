@@ -330,8 +330,8 @@ depth_map_kernel(const float* __restrict__ dep_all, void* __restrict__ out_all, 
 // viewport = (x, y, w, h) in window pixels; all zeros = (0, 0, W, H).  Also every frame / viewport limit of d2s_dibr_composite, so
 // that d2s_dibr_composite_shape accepts exactly what the launch accepts.
 static int comp_viewport(int H, int W, const d2s_dibr_params* p, int* vx, int* vy, int* vw, int* vh) {
-    D2S_REQUIRE(H > 1 && W > 1, "bad shape (H, W > 1)");
-    D2S_REQUIRE((long)H * W * 3 + 8 < (1L << 31), "frame too large (32-bit texel indices)");
+    const int rc = dibr_check_frame(H, W);
+    if (rc) return rc;
     const float* q = p->viewport;
     if (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f && q[3] == 0.f) { *vx = 0; *vy = 0; *vw = W; *vh = H; }
     else {
@@ -366,20 +366,15 @@ extern "C" int d2s_dibr_composite_shape(int H, int W, const d2s_dibr_params* p, 
 int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                             int composite, void* out, int out_fmt, void* stream, bool check_only) {
     D2S_REQUIRE(depth && p && out, "null pointer");
-    D2S_REQUIRE(p->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     D2S_REQUIRE(composite >= D2S_COMPOSITE_ANAGLYPH && composite <= D2S_COMPOSITE_DEPTH_MAP, "bad composite (D2S_COMPOSITE_*)");
     D2S_REQUIRE(rgb || composite == D2S_COMPOSITE_DEPTH_MAP, "rgb may be NULL for D2S_COMPOSITE_DEPTH_MAP only");
-    D2S_REQUIRE(batch > 0 && batch <= 65535, "bad batch (1 .. 65535)");
-    D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC, "bad out_fmt (U8_HWC or F32_HWC)");
-    D2S_REQUIRE(p->search_radius >= 0.f && p->search_radius < 16.f, "search_radius must be in [0,16)");
-    D2S_REQUIRE(p->corner_radius >= 0.f && p->corner_radius <= 0.5f, "corner_radius must be in [0, 0.5]");
-    D2S_REQUIRE(p->alpha_mode >= D2S_DIBR_ALPHA_WINDOW && p->alpha_mode <= D2S_DIBR_ALPHA_RGBA, "bad alpha_mode");
+    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
+    if (rc) return rc;
     CompGeom G;
     DibrGeom& g = G.g;
     int vw, vh;
-    int rc = comp_viewport(H, W, p, &G.vx, &G.vy, &vw, &vh);
+    rc = comp_viewport(H, W, p, &G.vx, &G.vy, &vw, &vh);
     if (rc) return rc;
-    D2S_REQUIRE(dh > 0 && dw > 0 && (long)dh * dw < (1L << 31), "bad depth shape (dh, dw > 0)");
     const int nch = p->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
     const bool up = dh != H || dw != W;
     const UpArgs ua = {dh, dw, linear_scale(dh, H, false), linear_scale(dw, W, false)};      // (d2s_upsample_depth's scales)
@@ -401,34 +396,17 @@ int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int 
         return D2S_OK;
     }
     if (check_only) return D2S_OK;
-    g.H = H; g.W = W; g.oh = vh; g.ow = vw;
-    g.dh = ua.dh; g.dw = ua.dw; g.dsy = ua.sy; g.dsx = ua.sx;
-    g.mode = -1; g.out_h = vh; g.out_w = vw;
-    g.c = cosf(p->roll); g.s = sinf(p->roll);
-    g.psx = 1.0f / (p->res_w > 0.f ? p->res_w : (float)W);
-    g.psy = 1.0f / (p->res_h > 0.f ? p->res_h : (float)H);
-    g.half_ipd = (float)(p->ipd_uv / 2.0);                                            // u_eye_offset (viewer.py:2638)
-    g.strength = p->depth_strength; g.conv = p->convergence;
-    g.tol = p->depth_tolerance; g.blur = p->blur_radius; g.feather_w = p->feather_width;
-    g.search = (int)p->search_radius; g.feather = p->feather_enabled != 0;
-    g.corner_r = p->corner_radius;
-    g.alpha_mode = p->alpha_mode;
+    dibr_fill_geom(g, p, H, W, dh, dw);
+    g.oh = vh; g.ow = vw; g.mode = -1; g.out_h = vh; g.out_w = vw;
     g.vpx = (float)G.vx; g.vpy = (float)G.vy; g.vpw = (float)vw; g.vph = (float)vh;   // u_viewport
-    for (int i = 0; i < 20; ++i) { g.w1[i] = i < 16 ? expf((float)(-i * 0.15)) : 0.f; g.w2[i] = i < 16 ? expf((float)(-i * 0.2)) : 0.f; }
     const bool roll0 = g.s == 0.f && g.c == 1.f;
-    // the LDS window: how far from its own texel a fragment's same-row taps can land (sweeps, +-2 pixel_size taps, the parallax
-    // shift: |shaped| <= 1 and |depth_inv + conv| <= 1 + |conv| for depth in 0..1), as for f1; taps beyond it take the row gather
-    const double tex_per_px = (double)W * (double)g.psx;
-    const double reach = std::max(std::max(2.0, (double)g.search) * tex_per_px,
-                                  fabs((double)g.half_ipd) * (1.0 + fabs((double)g.conv)) * fabs((double)g.strength) * (double)W);
-    const int margin = (int)ceil(reach) + 2;
-    auto win_words = [&](int cols) { return (int)ceil((double)(cols - 1) * (double)W / (double)vw) + 2 * margin + 4; };
-    // 512 columns per block while the window stays <= 640 texels (20 KB: seven blocks per CU either way), as f1 chooses
-    const int cols = win_words(512) <= 640 && vw > 256 ? 512 : 256;
-    const int WW = win_words(cols);
+    // 512 columns per block while the window stays <= 640 texels, as f1 chooses; windows above 1536 texels (8 planes x 1536 floats =
+    // 48 KB + the queue) take the gather kernel
+    const DibrWindow win = dibr_plan_window(g, (double)W / (double)vw, roll0, 512, 640, 1536);
+    const int margin = win.margin, cols = win.cols, WW = win.WW;
     const bool fx = g.feather || g.corner_r > 0.f;
     dim3 block(256), grid(cdiv(vw, 256), vh, batch);
-    if (roll0 && WW <= 1536) {                        // (8 planes x 1536 floats = 48 KB + the queue)
+    if (win.rows) {
         const size_t lds = (size_t)8 * WW * sizeof(float);
         dim3 rgrid(cdiv(vw, cols), vh, batch);
 #define CR_K(M, FMT, FXV, COLS, D) hipLaunchKernelGGL((comp_rows_kernel<M, FMT, FXV, COLS, D>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, G, margin, WW)

@@ -341,4 +341,79 @@ __device__ __forceinline__ void dibr_store(void* __restrict__ out_all, long o, i
     }
 }
 
+// ---- Host side: the launch plan of f1 (dibr.hip) and of the composites (dibr_composite.hip), DESIGN.md 3.4 ----
+
+// H x W frame limits of every DIBR entry, the shape queries included (32-bit texel indices: tex_color's 8-byte window)
+inline int dibr_check_frame(int H, int W) {
+    D2S_REQUIRE(H > 1 && W > 1, "bad shape (H, W > 1)");
+    D2S_REQUIRE((long)H * W * 3 + 8 < (1L << 31), "frame too large (32-bit texel indices)");
+    return D2S_OK;
+}
+// What every launching entry refuses, whatever the program; the launchers add their own (pointers, display_mode / composite,
+// viewport, crop).  No HIP call here or before it.
+inline int dibr_check(const d2s_dibr_params* p, int dh, int dw, int batch, int H, int W, int out_fmt) {
+    D2S_REQUIRE(p->struct_size == sizeof(d2s_dibr_params),
+                "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80 (header of d2s_version() >= 110; the 72-byte struct of "
+                "version 100 has no alpha_mode)");
+    D2S_REQUIRE(batch > 0 && batch <= 65535, "bad batch (1 .. 65535)");
+    const int rc = dibr_check_frame(H, W);
+    if (rc) return rc;
+    D2S_REQUIRE(dh > 0 && dw > 0 && (long)dh * dw < (1L << 31), "bad depth shape (dh, dw > 0)");
+    D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC, "bad out_fmt (U8_HWC or F32_HWC)");
+    D2S_REQUIRE(p->search_radius >= 0.f && p->search_radius < 16.f, "search_radius must be in [0,16)");
+    D2S_REQUIRE(p->corner_radius >= 0.f && p->corner_radius <= 0.5f, "corner_radius must be in [0, 0.5]");
+    D2S_REQUIRE(p->alpha_mode >= D2S_DIBR_ALPHA_WINDOW && p->alpha_mode <= D2S_DIBR_ALPHA_RGBA, "bad alpha_mode");
+    return D2S_OK;
+}
+
+// The uniforms every program shares, from checked parameters.  Left to the launcher: oh, ow, mode, out_h, out_w, vpx .. vph (and the
+// crop): f1's eye shape and defaulted float viewport, the composites' integer window viewport.
+inline void dibr_fill_geom(DibrGeom& g, const d2s_dibr_params* p, int H, int W, int dh, int dw) {
+    g.H = H; g.W = W;
+    g.dh = dh; g.dw = dw; g.dsy = linear_scale(dh, H, false); g.dsx = linear_scale(dw, W, false);      // (d2s_upsample_depth's scales)
+    g.c = cosf(p->roll); g.s = sinf(p->roll);
+    g.psx = 1.0f / (p->res_w > 0.f ? p->res_w : (float)W);
+    g.psy = 1.0f / (p->res_h > 0.f ? p->res_h : (float)H);
+    g.half_ipd = (float)(p->ipd_uv / 2.0);                                            // u_eye_offset (viewer.py:2638, 2701)
+    g.strength = p->depth_strength; g.conv = p->convergence;
+    g.tol = p->depth_tolerance; g.blur = p->blur_radius; g.feather_w = p->feather_width;
+    g.search = (int)p->search_radius; g.feather = p->feather_enabled != 0;
+    g.corner_r = p->corner_radius;
+    g.alpha_mode = p->alpha_mode;
+    for (int i = 0; i < 20; ++i) { g.w1[i] = i < 16 ? expf((float)(-i * 0.15)) : 0.f; g.w2[i] = i < 16 ? expf((float)(-i * 0.2)) : 0.f; }
+}
+
+// Per-eye viewport (oh, ow) and packed output of an eh x ew eye image: the Half modes halve the eye along the packing axis, and
+// the packed size is twice the eye along it (d2s_dibr_shape, d2s_dibr_crop_shape, the f1 launcher).
+inline int dibr_eye_shape(int eh, int ew, int display_mode, int* oh, int* ow, int* out_h, int* out_w) {
+    D2S_REQUIRE(display_mode >= D2S_MODE_HALF_SBS && display_mode <= D2S_MODE_FULL_TAB, "bad display_mode");
+    *oh = display_mode == D2S_MODE_HALF_TAB ? eh / 2 : eh;
+    *ow = display_mode == D2S_MODE_HALF_SBS ? ew / 2 : ew;
+    *out_h = display_mode == D2S_MODE_FULL_TAB || display_mode == D2S_MODE_HALF_TAB ? 2 * *oh : *oh;
+    *out_w = display_mode == D2S_MODE_FULL_SBS || display_mode == D2S_MODE_HALF_SBS ? 2 * *ow : *ow;
+    return D2S_OK;
+}
+
+// The LDS window of the row kernels (roll == 0).  margin: how far from its own texel a pixel's same-row taps can land -- the sweeps
+// (search texels of pixel_size.x), the +-2 pixel_size confidence taps, the parallax shift (|shaped| <= 1 and |depth_inv + conv| <=
+// 1 + |conv| for depth in 0..1) -- in texels of the source; taps beyond it take the row gather, the same values.
+// tex_per_col: source texels per output column (W / ow, of the cropped span with a crop).  A block of `cols` columns stages
+// win_words(cols) texels of 8 float planes.  cols starts at col_cap and halves down to 256 while the window exceeds widen_words or
+// half the block would lie past the viewport; the row kernel is taken when rows_ok (roll == 0 and the launcher's own switches)
+// and the 256-column window fits rows_words, else the gather kernel.
+struct DibrWindow { int margin, cols, WW; bool rows; };
+inline DibrWindow dibr_plan_window(const DibrGeom& g, double tex_per_col, bool rows_ok, int col_cap, int widen_words, int rows_words) {
+    const double tex_per_px = (double)g.W * (double)g.psx;
+    const double reach = fmax(fmax(2.0, (double)g.search) * tex_per_px,
+                              fabs((double)g.half_ipd) * (1.0 + fabs((double)g.conv)) * fabs((double)g.strength) * (double)g.W);
+    DibrWindow w;
+    w.margin = (int)ceil(reach) + 2;
+    auto win_words = [&](int c) { return (int)ceil((double)(c - 1) * tex_per_col) + 2 * w.margin + 4; };
+    w.rows = rows_ok && win_words(256) <= rows_words;
+    w.cols = col_cap;
+    while (w.cols > 256 && (win_words(w.cols) > widen_words || g.ow <= w.cols / 2)) w.cols >>= 1;
+    w.WW = win_words(w.cols);
+    return w;
+}
+
 }  // namespace d2s

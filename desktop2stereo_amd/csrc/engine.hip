@@ -1156,11 +1156,10 @@ static int view_pipeline_any(d2s_engine* e, const uint8_t* frames, int batch, co
     D2S_REQUIRE(view >= -1 && view <= D2S_COMPOSITE_DEPTH_MAP, "bad view (-1: the stereo warp, or D2S_COMPOSITE_*)");
     D2S_REQUIRE(!crop || view == -1, "bad view with a crop (the composites are not an OpenXR path: view must be -1)");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
-    {   // what depends on the frame and the uniforms alone (display mode / viewport), then the engine
-        int oh = 0, ow = 0;
-        RC(crop ? d2s_dibr_crop_shape(H, W, crop, dp->display_mode, &oh, &ow)
-                : view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
-    }
+    // what depends on the frame and the uniforms alone (display mode / viewport), then the engine
+    int oh = 0, ow = 0;
+    RC(crop ? d2s_dibr_crop_shape(H, W, crop, dp->display_mode, &oh, &ow)
+            : view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
     D2S_REQUIRE(e, "null engine");
     int stride = 1;
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
@@ -1174,15 +1173,10 @@ static int view_pipeline_any(d2s_engine* e, const uint8_t* frames, int batch, co
     D2S_ON_DEVICE(e->device);
     hipStream_t st = (hipStream_t)stream;
     RC(pipeline_depth(e, frames, batch, H, W, stride, pre, pp, use_ema, depth_full, stream));
-    {
-        int oh = 0, ow = 0;
-        RC(crop ? d2s_dibr_crop_shape(H, W, crop, dp->display_mode, &oh, &ow)
-                : view < 0 ? d2s_dibr_shape(H, W, dp->display_mode, &oh, &ow) : d2s_dibr_composite_shape(H, W, dp, view, &oh, &ow));
-        const int nch = dp->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
-        double obytes = (double)oh * ow * nch * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
-        const double ibytes = view == D2S_COMPOSITE_DEPTH_MAP ? 0.0 : (double)H * W * 3;
-        PROF(PC_WARP, 0, batch * (ibytes + (double)e->h * e->w * 4 + obytes), warp(false));
-    }
+    const int nch = dp->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    const double obytes = (double)oh * ow * nch * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
+    const double ibytes = view == D2S_COMPOSITE_DEPTH_MAP ? 0.0 : (double)H * W * 3;
+    PROF(PC_WARP, 0, batch * (ibytes + (double)e->h * e->w * 4 + obytes), warp(false));
     return D2S_OK;
 }
 

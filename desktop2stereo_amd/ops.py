@@ -237,6 +237,11 @@ def upsample_depth(depth: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return out
 
 
+def _sbs_out_spec(B: int, oh: int, ow: int, out_fmt: int):
+    """(shape, dtype) of a make_sbs / Engine.pipeline result in out_fmt."""
+    return (B, 3, oh, ow) if out_fmt == FMT_F32_CHW else (B, oh, ow, 3), torch.uint8 if out_fmt == FMT_U8_HWC else torch.float32
+
+
 def make_sbs(frames: torch.Tensor, depth: torch.Tensor, sp: SbsParams, out_fmt: int = FMT_U8_HWC, out: torch.Tensor = None) -> torch.Tensor:
     """A14 (+A13 fused when depth is at model resolution) (reference depth.py:2122-2184).  `out`: a caller-allocated result (the
     C-ABI's own convention), shape [B, oh, ow, 3] / [B, 3, oh, ow] of the format's dtype."""
@@ -252,18 +257,14 @@ def make_sbs(frames: torch.Tensor, depth: torch.Tensor, sp: SbsParams, out_fmt: 
     dh, dw = d.shape[-2:]
     oh, ow = sbs_shape(H, W, sp)
     batched = frames.dim() == 4
+    want = _sbs_out_spec(B, oh, ow, out_fmt)
     if out is not None:
-        want = ((B, 3, oh, ow) if out_fmt == FMT_F32_CHW else (B, oh, ow, 3), torch.uint8 if out_fmt == FMT_U8_HWC else torch.float32)
         if tuple(out.shape) != want[0] or out.dtype != want[1] or not out.is_contiguous() or out.device != frames.device:
             raise ValueError(f"make_sbs: out must be a contiguous {want[1]} tensor of shape {want[0]} on {frames.device}")
-    elif out_fmt == FMT_U8_HWC:
-        out = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=frames.device)
-    elif out_fmt == FMT_F32_HWC:
-        out = torch.empty((B, oh, ow, 3), dtype=torch.float32, device=frames.device)
-    elif out_fmt == FMT_F32_CHW:
-        out = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=frames.device)
-    else:
+    elif out_fmt not in (FMT_U8_HWC, FMT_F32_HWC, FMT_F32_CHW):
         raise ValueError("bad out_fmt")
+    else:
+        out = torch.empty(want[0], dtype=want[1], device=frames.device)
     with _on(frames.device) as st:
         check(_lib.load().d2s_make_sbs(_ptr(frames), fmt, _ptr(d), dh, dw, B, H, W, C.byref(sp), _ptr(out), out_fmt, st),
               "d2s_make_sbs")
@@ -346,6 +347,12 @@ def crop_detect(frames: torch.Tensor, out: Optional[torch.Tensor] = None, worksp
     return out if batched else out.view(-1)
 
 
+def _dibr_out_spec(B: int, oh: int, ow: int, dp: "_lib.DibrParams", out_u8: bool):
+    """(shape, dtype, D2S_FMT_*) of a dibr_warp / dibr_composite / Engine.view_pipeline result: three channels, four with alpha "rgba"."""
+    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+    return (B, oh, ow, nch), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
+
+
 def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", out_u8: bool = True, crop=None) -> torch.Tensor:
     """f1 (reference viewer.py:386-631): uint8 HWC frames [B,H,W,3] or [H,W,3] + depth [B,dh,dw] or [dh,dw] -> both eyes
     with disocclusion in-painting, packed per dp.display_mode.  Depth of the frame's size is the shader's depth texture itself;
@@ -371,16 +378,14 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
         check(lib.d2s_dibr_crop_shape(H, W, c4, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_crop_shape")
     else:
         check(lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
-    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-    out = torch.empty((B, oh.value, ow.value, nch), dtype=torch.uint8 if out_u8 else torch.float32, device=f.device)
+    shape, dtype, fmt = _dibr_out_spec(B, oh.value, ow.value, dp, out_u8)
+    out = torch.empty(shape, dtype=dtype, device=f.device)
     _same_device(f, d, "dibr_warp")
     with _on(f.device) as st:
         if crop is not None:
-            check(lib.d2s_dibr_warp_crop(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), c4, _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st),
-                  "d2s_dibr_warp_crop")
-            return out if batched else out[0]
-        check(lib.d2s_dibr_warp_depth(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st),
-              "d2s_dibr_warp_depth")
+            check(lib.d2s_dibr_warp_crop(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), c4, _ptr(out), fmt, st), "d2s_dibr_warp_crop")
+        else:
+            check(lib.d2s_dibr_warp_depth(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), _ptr(out), fmt, st), "d2s_dibr_warp_depth")
     return out if batched else out[0]
 
 
@@ -416,11 +421,11 @@ def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_li
     lib = _lib.load()
     oh, ow = C.c_int(), C.c_int()
     check(lib.d2s_dibr_composite_shape(H, W, C.byref(dp), _lib.COMPOSITE[mode], C.byref(oh), C.byref(ow)), "d2s_dibr_composite_shape")
-    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-    out = torch.empty((B, oh.value, ow.value, nch), dtype=torch.uint8 if out_u8 else torch.float32, device=d.device)
+    shape, dtype, fmt = _dibr_out_spec(B, oh.value, ow.value, dp, out_u8)
+    out = torch.empty(shape, dtype=dtype, device=d.device)
     with _on(d.device) as st:
         check(lib.d2s_dibr_composite_depth(_ptr(f) if f is not None else None, _ptr(d), dh, dw, B, H, W, C.byref(dp), _lib.COMPOSITE[mode],
-                                           _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC, st), "d2s_dibr_composite_depth")
+                                           _ptr(out), fmt, st), "d2s_dibr_composite_depth")
     return out if batched else out[0]
 
 
@@ -576,33 +581,39 @@ class Engine:
         else:
             check(self.lib.d2s_engine_reset_stream_at(self._h, int(stream)), "d2s_engine_reset_stream_at")
 
-    def pipeline(self, frames: torch.Tensor, p: PipelineParams, sp: SbsParams, use_ema: bool = False,
-                 out_fmt: int = FMT_U8_HWC, want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
-        """predict_depth + make_sbs for uint8 HWC frames [B,H,W,3] in one stream-ordered call.
-        temporal engines: `streams` as in __call__; use_ema keeps one EMA state per stream slot."""
+    def _run_pipeline(self, fn, name: str, frames: torch.Tensor, p: PipelineParams, spec, mid: tuple, want_depth: bool,
+                      out: Optional[torch.Tensor], streams, who: Optional[str] = None):
+        """The body the pipeline methods share: frames [B,H,W,3] uint8 -> fn(engine, frames, B, streams, H, W, depth_resolution, pre, post,
+        *mid, out, out_fmt, depth_full, stream).  spec(B, H, W) -> (shape, dtype, D2S_FMT_*) of the result; a caller's `out` is checked
+        against it when `who` names the method (pipeline itself takes any tensor of the engine's device)."""
         self._mine(frames, "frames")
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
             raise ValueError("frames must be uint8 [B,H,W,3]")
         frames = frames.contiguous()
         B, H, W, _ = frames.shape
-        oh, ow = sbs_shape(H, W, sp)
+        shape, dtype, fmt = spec(B, H, W)
         if out is None:
-            if out_fmt == FMT_U8_HWC:
-                out = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=frames.device)
-            elif out_fmt == FMT_F32_HWC:
-                out = torch.empty((B, oh, ow, 3), dtype=torch.float32, device=frames.device)
-            else:
-                out = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=frames.device)
+            out = torch.empty(shape, dtype=dtype, device=frames.device)
         else:
             self._mine(out, "out")
+            if who and (out.numel() != torch.Size(shape).numel() or out.dtype != dtype or not out.is_contiguous()):
+                raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of {shape}")
         depth = torch.empty((B, H, W), dtype=torch.float32, device=frames.device) if want_depth else None
         pp = post_params(p)
         pre = pre_params(p.mean, p.std, p.resample, p.square_input)
         with _on(self.device) as st:
-            check(self.lib.d2s_pipeline_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution, C.byref(pre),
-                                                C.byref(pp), C.byref(sp), int(use_ema), _ptr(out), out_fmt,
-                                                _ptr(depth) if want_depth else None, st), "d2s_pipeline")
+            check(fn(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution, C.byref(pre), C.byref(pp), *mid,
+                     _ptr(out), fmt, _ptr(depth) if want_depth else None, st), name)
         return (out, depth) if want_depth else out
+
+    def pipeline(self, frames: torch.Tensor, p: PipelineParams, sp: SbsParams, use_ema: bool = False,
+                 out_fmt: int = FMT_U8_HWC, want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
+        """predict_depth + make_sbs for uint8 HWC frames [B,H,W,3] in one stream-ordered call.
+        temporal engines: `streams` as in __call__; use_ema keeps one EMA state per stream slot."""
+        def spec(B, H, W):
+            return _sbs_out_spec(B, *sbs_shape(H, W, sp), out_fmt) + (out_fmt,)
+        return self._run_pipeline(self.lib.d2s_pipeline_streams, "d2s_pipeline", frames, p, spec, (C.byref(sp), int(use_ema)),
+                                  want_depth, out, streams)
 
     def view_pipeline(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", view: Optional[str] = None,
                       use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,
@@ -612,65 +623,29 @@ class Engine:
         "Anaglyph" | "Interleaved" | "Interleaved-V" | "Depth Map", over dp.viewport) in place of make_sbs.  The warp reads the
         engine's model-resolution depth; bit-identical to pipeline(want_depth=True) followed by dibr_warp / dibr_composite on that
         map.  out: a caller-allocated result (e.g. a present-ring slot), [B,oh,ow,3|4] uint8 / float32.  streams, use_ema: as pipeline."""
-        self._mine(frames, "frames")
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
-            raise ValueError("frames must be uint8 [B,H,W,3]")
-        if view is not None and view not in _lib.COMPOSITE:
-            raise ValueError(f"view must be None or one of {list(_lib.COMPOSITE)}")
-        frames = frames.contiguous()
-        B, H, W, _ = frames.shape
-        oh, ow = C.c_int(), C.c_int()
-        if view is None:
-            check(self.lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
-        else:
-            check(self.lib.d2s_dibr_composite_shape(H, W, C.byref(dp), _lib.COMPOSITE[view], C.byref(oh), C.byref(ow)), "d2s_dibr_composite_shape")
-        nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-        want = ((B, oh.value, ow.value, nch), torch.uint8 if out_u8 else torch.float32)
-        if out is None:
-            out = torch.empty(want[0], dtype=want[1], device=frames.device)
-        else:
-            self._mine(out, "out")
-            if out.numel() != B * oh.value * ow.value * nch or out.dtype != want[1] or not out.is_contiguous():
-                raise ValueError(f"view_pipeline: out must be a contiguous {want[1]} tensor of {want[0]}")
-        depth = torch.empty((B, H, W), dtype=torch.float32, device=frames.device) if want_depth else None
-        pp = post_params(p)
-        pre = pre_params(p.mean, p.std, p.resample, p.square_input)
-        with _on(self.device) as st:
-            check(self.lib.d2s_view_pipeline_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution,
-                                                     C.byref(pre), C.byref(pp), C.byref(dp), -1 if view is None else _lib.COMPOSITE[view],
-                                                     int(use_ema), _ptr(out), FMT_U8_HWC if out_u8 else FMT_F32_HWC,
-                                                     _ptr(depth) if want_depth else None, st), "d2s_view_pipeline_streams")
-        return (out, depth) if want_depth else out
+        def spec(B, H, W):
+            if view is not None and view not in _lib.COMPOSITE:
+                raise ValueError(f"view must be None or one of {list(_lib.COMPOSITE)}")
+            oh, ow = C.c_int(), C.c_int()
+            if view is None:
+                check(self.lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
+            else:
+                check(self.lib.d2s_dibr_composite_shape(H, W, C.byref(dp), _lib.COMPOSITE[view], C.byref(oh), C.byref(ow)), "d2s_dibr_composite_shape")
+            return _dibr_out_spec(B, oh.value, ow.value, dp, out_u8)
+        mid = (C.byref(dp), -1 if view is None else _lib.COMPOSITE.get(view), int(use_ema))
+        return self._run_pipeline(self.lib.d2s_view_pipeline_streams, "d2s_view_pipeline_streams", frames, p, spec, mid, want_depth, out,
+                                  streams, who="view_pipeline")
 
     def view_pipeline_crop(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", crop, use_ema: bool = False,
                            out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
         """view_pipeline(view=None) with the OpenXR screen's source crop (d2s_view_pipeline_crop_streams): crop = (x, y, w, h) in uv,
         top-left origin, one rectangle for the batch; each eye is the crop's pixel size.  Bit-identical to pipeline(want_depth=True)'s
         engine depth followed by dibr_warp(crop=).  (A method of its own: view_pipeline's parameter list is pinned by the ABI tests.)"""
-        self._mine(frames, "frames")
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
-            raise ValueError("frames must be uint8 [B,H,W,3]")
-        frames = frames.contiguous()
-        B, H, W, _ = frames.shape
-        c4 = _crop4(crop)
-        oh, ow = dibr_crop_shape(H, W, crop, dp.display_mode)
-        nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-        want = ((B, oh, ow, nch), torch.uint8 if out_u8 else torch.float32)
-        if out is None:
-            out = torch.empty(want[0], dtype=want[1], device=frames.device)
-        else:
-            self._mine(out, "out")
-            if out.numel() != B * oh * ow * nch or out.dtype != want[1] or not out.is_contiguous():
-                raise ValueError(f"view_pipeline_crop: out must be a contiguous {want[1]} tensor of {want[0]}")
-        depth = torch.empty((B, H, W), dtype=torch.float32, device=frames.device) if want_depth else None
-        pp = post_params(p)
-        pre = pre_params(p.mean, p.std, p.resample, p.square_input)
-        with _on(self.device) as st:
-            check(self.lib.d2s_view_pipeline_crop_streams(self._h, _ptr(frames), B, self._stream_ids(streams, B), H, W, p.depth_resolution,
-                                                          C.byref(pre), C.byref(pp), C.byref(dp), -1, c4, int(use_ema), _ptr(out),
-                                                          FMT_U8_HWC if out_u8 else FMT_F32_HWC, _ptr(depth) if want_depth else None, st),
-                  "d2s_view_pipeline_crop_streams")
-        return (out, depth) if want_depth else out
+        def spec(B, H, W):
+            return _dibr_out_spec(B, *dibr_crop_shape(H, W, crop, dp.display_mode), dp, out_u8)
+        mid = (C.byref(dp), -1, _crop4(crop), int(use_ema))
+        return self._run_pipeline(self.lib.d2s_view_pipeline_crop_streams, "d2s_view_pipeline_crop_streams", frames, p, spec, mid,
+                                  want_depth, out, streams, who="view_pipeline_crop")
 
     def close(self):
         if getattr(self, "_h", None):
