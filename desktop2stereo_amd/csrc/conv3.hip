@@ -14,7 +14,7 @@
 //     0.6 GB of input) and spends ~19 VALU instructions per MFMA on per-chunk tap / bounds arithmetic.
 // Same MFMA fragments (16 x 16 x 32 bf16, operands swapped: a lane ends with 4 consecutive n of one pixel), accumulators and
 // epilogues as gemm_glds_kernel.
-#include "gemm_epi.h"
+#include "conv3_tile.h"
 #include <algorithm>
 
 namespace d2s {
@@ -68,6 +68,8 @@ conv3_halo2_kernel(GemmA a, const bf16_t* __restrict__ W, int M, int N, int Kpad
     const int nimg = M / (a.Ho * a.Wo);
     int tm_, tn_;
     if (!tile_of_block(blockIdx.x, nimg * tiles_y * tiles_x, (N + BN - 1) / BN, xn, tm_, tn_)) return;
+    // (the tile origin inline, not C3Tiles::org: with its two divisions instead of these three the block prologue is laid out
+    //  differently, and the one-block-per-CU instantiation measured 1-3 % slower -- profiles/conv3_shared_ab.md)
     const int b = tm_ / (tiles_y * tiles_x), ty0 = ((tm_ / tiles_x) % tiles_y) * TH, tx0 = (tm_ % tiles_x) * TW;
     const int bn0 = tn_ * BN;
 
@@ -92,15 +94,10 @@ conv3_halo2_kernel(GemmA a, const bf16_t* __restrict__ W, int M, int N, int Kpad
     // ---- the input halo, once: 10 x 18 pixels x C channels, zero outside the image, ReLU-on-load (pre-activation units); a.ups: the
     // align_corners up-sample in front of this convolution happens here (gemm_epi.h conv_halo_fill)
     {
-        const short floor_ = a.relu ? (short)0 : (short)0x8000;      // max as int16: 0 = ReLU, most negative = identity
-        typedef short s16x8_ __attribute__((ext_vector_type(8)));
+        const int floor_ = relu_floor_bf16(a);
         conv_halo_fill<bf16_t, 64 * NW, HG>(a, b, ty0, tx0, HWD, HPX, CPP, tid, halo,
             [&](int p, int c) { return p * PST + c3_chunk_slot<PST>(c); },
-            [&](u32x4 v) {
-                s16x8_ x = __builtin_bit_cast(s16x8_, v);
-                x = __builtin_elementwise_max(x, (s16x8_){floor_, floor_, floor_, floor_, floor_, floor_, floor_, floor_});
-                return __builtin_bit_cast(u32x4, x);
-            });
+            [&](u32x4 v) { return relu_frag(v, floor_, bf16_t()); });
     }
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -158,8 +155,7 @@ conv3_halo2_kernel(GemmA a, const bf16_t* __restrict__ W, int M, int N, int Kpad
                     if (n0 < N) {
                         float bb[4], w[4];
                         load4(e.bias + n0, bb); load4(e.scale + n0, w);
-                        s += fmaxf(acc[i][j][0] + bb[0], 0.f) * w[0] + fmaxf(acc[i][j][1] + bb[1], 0.f) * w[1] +
-                             fmaxf(acc[i][j][2] + bb[2], 0.f) * w[2] + fmaxf(acc[i][j][3] + bb[3], 0.f) * w[3];
+                        s += c3_head_dot(acc[i][j], bb, w);
                     }
                 });
                 s += __shfl_xor(s, 16);
@@ -169,40 +165,12 @@ conv3_halo2_kernel(GemmA a, const bf16_t* __restrict__ W, int M, int N, int Kpad
             return;
         }
     }
+    const int nb = bn0 + wave_n * (BN / WN) + fg * 4;        // this lane's first column
     EpiCols cols[FN];
 #pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int n0 = bn0 + wave_n * (BN / WN) + j * 16 + fg * 4;
-        if (n0 < N) epi_cols_load(e, n0, cols[j]);
-    }
-    float pre[FM][FN][4];                                   // residual values, all requested before the first store (gemm_epi.h)
-    const bool pre_on = epi_res1_ahead(e);
-    if (pre_on) {
-        static_for<FM>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            const int y = ty0 + wave_m * FM + i;
-            static_for<FN>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                const int n0 = bn0 + wave_n * (BN / WN) + j * 16 + fg * 4;
-                if (y < a.Ho && x < a.Wo && n0 < N) epi_res1_load<bf16_t>(e, (b * a.Ho + y) * a.Wo + x, n0, pre[i][j]);
-            });
-        });
-    }
-    static_for<FM>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const int y = ty0 + wave_m * FM + i;
-        if (y < a.Ho && x < a.Wo) {
-            const int m = (b * a.Ho + y) * a.Wo + x;
-            static_for<FN>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                const int n0 = bn0 + wave_n * (BN / WN) + j * 16 + fg * 4;
-                if (n0 < N) {
-                    float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                    epilogue_dispatch<bf16_t>(e, m, n0, v, false, pre_on ? pre[i][j] : nullptr, &cols[j]);
-                }
-            });
-        }
-    });
+    for (int j = 0; j < FN; ++j)
+        if (nb + j * 16 < N) epi_cols_load(e, nb + j * 16, cols[j]);
+    conv_tile_epilogue<bf16_t, FM, FN>(a, e, acc, cols, b, ty0 + wave_m * FM, x, nb, N);
 }
 
 // ================================================================================================
@@ -240,47 +208,23 @@ conv3_head_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
-    const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
+    const C3Tiles<TH, TW> tiles(a);
 
-    // ---- W fragments, once: MFMA row j * 16 + fr, K step (tap, ks) -> chunk ks * 4 + fg of the tap's 64 channels
+    // ---- W fragments, once (MFMA row j * 16 + fr), and the epilogue constants of this lane's columns (conv2 bias, conv3 weights)
     u32x4 wf[9][2][2];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int n = j * 16 + fr;
-                wf[tap][ks][j] = n < N ? *(const u32x4*)(W + (long)n * Kpad + tap * 64 + (ks * 4 + fg) * 8) : (u32x4){0u, 0u, 0u, 0u};
-            }
-    // epilogue constants of this lane's columns (conv2 bias, conv3 weights)
+    c3_load_wfrags<64>(wf, W, N, Kpad, 0, fr, fg);
     float cb[2][4], cw[2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n0 = j * 16 + fg * 4;
-        if (n0 < N) { load4(e.bias + n0, cb[j]); load4(e.scale + n0, cw[j]); }
-        else { cb[j][0] = cb[j][1] = cb[j][2] = cb[j][3] = 0.f; cw[j][0] = cw[j][1] = cw[j][2] = cw[j][3] = 0.f; }
-    }
+    c3_head_consts(e, N, fg, cb, cw);
 
-    typedef short s16x8_ __attribute__((ext_vector_type(8)));
-    const short floor_ = a.relu ? (short)0 : (short)0x8000;
+    const int floor_ = relu_floor_bf16(a);
     u32x4 hr[NLD];
-    auto tile_org = [&](int t, int& b, int& ty0, int& tx0) {
-        b = t / (tiles_y * tiles_x);
-        const int r = t - b * (tiles_y * tiles_x);
-        ty0 = (r / tiles_x) * TH; tx0 = (r % tiles_x) * TW;
-    };
-    // UPS: first source row / column under the halo of the tile at (ty0, tx0); the window is SR x SR pixels from there
-    auto src_org = [&](int ty0, int tx0, int& rs0, int& cs0) {
-        rs0 = linear_tap(ty0 > 0 ? ty0 - 1 : 0, a.usy, a.Hs, true).i0;
-        cs0 = linear_tap(tx0 > 0 ? tx0 - 1 : 0, a.usx, a.Ws, true).i0;
-    };
+    // (UPS: the staged source window is SR x SR pixels from the tile's src_org)
     auto load_halo = [&](int t) {
         int b, ty0, tx0;
-        tile_org(t, b, ty0, tx0);
+        tiles.org(t, b, ty0, tx0);
         if constexpr (UPS) {
             int rs0, cs0;
-            src_org(ty0, tx0, rs0, cs0);
+            tiles.src_org(a, ty0, tx0, rs0, cs0);
             const bf16_t* img = (const bf16_t*)a.ptr + (long)b * a.Hs * a.Ws * a.C;
 #pragma unroll
             for (int k = 0; k < NSL; ++k) {
@@ -299,6 +243,7 @@ conv3_head_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
                 const int p = idx >> 3, c = idx & 7;
                 const int hy = p / HWD, hx = p - hy * HWD;
                 const int iy = ty0 + hy - 1, ix = tx0 + hx - 1;
+                // loads only inside the image: no wait here counts them (conv3_wide_kernel's loader issues every one for its vmcnt arithmetic)
                 hr[k] = (u32x4){0u, 0u, 0u, 0u};
                 if (idx < NCH && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi) hr[k] = *(const u32x4*)(img + ((long)iy * a.Wi + ix) * a.C + c * 8);
             }
@@ -318,8 +263,8 @@ conv3_head_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
             }
             __syncthreads();
             int b, ty0, tx0, rs0, cs0;
-            tile_org(t, b, ty0, tx0);
-            src_org(ty0, tx0, rs0, cs0);
+            tiles.org(t, b, ty0, tx0);
+            tiles.src_org(a, ty0, tx0, rs0, cs0);
 #pragma unroll
             for (int k = 0; k < NLD; ++k) {
                 const int idx = tid + k * 512;
@@ -349,36 +294,21 @@ conv3_head_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
                             }
                         }
                     }
-                    s16x8_ x = __builtin_bit_cast(s16x8_, r);
-                    x = __builtin_elementwise_max(x, (s16x8_){floor_, floor_, floor_, floor_, floor_, floor_, floor_, floor_});
-                    lds[buf * HALO + p * PST + c] = __builtin_bit_cast(u32x4, x);
+                    lds[buf * HALO + p * PST + c] = relu_frag(r, floor_, bf16_t());
                 }
             }
         } else {
 #pragma unroll
             for (int k = 0; k < NLD; ++k) {
                 const int idx = tid + k * 512;
-                if (idx < NCH) {
-                    s16x8_ x = __builtin_bit_cast(s16x8_, hr[k]);
-                    x = __builtin_elementwise_max(x, (s16x8_){floor_, floor_, floor_, floor_, floor_, floor_, floor_, floor_});
-                    lds[buf * HALO + (idx >> 3) * PST + (idx & 7)] = __builtin_bit_cast(u32x4, x);
-                }
+                if (idx < NCH) lds[buf * HALO + (idx >> 3) * PST + (idx & 7)] = relu_frag(hr[k], floor_, bf16_t());
             }
         }
     };
 
-    // tile walk: XCD x (= blockIdx % 8) owns the contiguous run [x per, (x + 1) per) and its CUs take consecutive tiles of it, so the
-    // overlapping windows of neighbouring tiles meet in ONE L2 (in launch order -- tile = block + k grid -- neighbours sat on eight
-    // XCDs: PMC with the up-sample folded in, profiles/r3_06: L2 hit 0.15, 376 MB fetched per launch for a 204 MB source)
-    const bool xcd_walk = (gridDim.x & 7) == 0;
-    const int xcd_ = blockIdx.x & 7, slot_ = blockIdx.x >> 3, nslot_ = gridDim.x >> 3, per_ = (ntiles + 7) >> 3;
-    auto tile_at = [&](int k) {
-        if (!xcd_walk) { const int tt = blockIdx.x + k * gridDim.x; return tt < ntiles ? tt : -1; }
-        const int j = slot_ + k * nslot_, tt = xcd_ * per_ + j;
-        return (j < per_ && tt < ntiles) ? tt : -1;
-    };
+    const C3Walk<> walk(ntiles);
     int kk = 0;
-    int t = tile_at(0);
+    int t = walk.at(0);
     if (t < 0) return;
     load_halo(t);
     store_halo(0, t);
@@ -387,7 +317,7 @@ conv3_head_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     const int hb0 = ((wid * 2) * HWD + fr) * PST + fg;
     int buf = 0;
     for (; t >= 0;) {
-        const int tn = tile_at(++kk);
+        const int tn = walk.at(++kk);
         if (tn >= 0) load_halo(tn);                            // in flight under the 72 MFMAs below
         const u32x4* hp = lds + buf * HALO + hb0;
         f32x4 acc[2][2];
@@ -408,16 +338,14 @@ conv3_head_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
         });
         // ---- epilogue: depth = act(b3 + sum_n w3[n] relu(acc + bias[n]))
         int b, ty0, tx0;
-        tile_org(t, b, ty0, tx0);
+        tiles.org(t, b, ty0, tx0);
         const int x = tx0 + fr;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int y = ty0 + wid * 2 + i;
             float s = 0.f;
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-                s += fmaxf(acc[i][j][0] + cb[j][0], 0.f) * cw[j][0] + fmaxf(acc[i][j][1] + cb[j][1], 0.f) * cw[j][1] +
-                     fmaxf(acc[i][j][2] + cb[j][2], 0.f) * cw[j][2] + fmaxf(acc[i][j][3] + cb[j][3], 0.f) * cw[j][3];
+            for (int j = 0; j < 2; ++j) s += c3_head_dot(acc[i][j], cb[j], cw[j]);
             s += __shfl_xor(s, 16);
             s += __shfl_xor(s, 32);
             if (fg == 0 && y < a.Ho && x < a.Wo) ((float*)e.out)[((long)b * a.Ho + y) * a.Wo + x] = head_activation(s + e.head_b3, e.head_max_depth);
@@ -489,26 +417,16 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     const int nq = wid & 3;
     const int fr = lane & 15, fg = lane >> 4;
     const int px = c3_lane_pixel<PST>(fr);                     // tile column of this lane's pixel
-    const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
+    const C3Tiles<TH, TW> tiles(a);
     const int ptid = tid - 256;                                // producer thread number
 
-    typedef short s16x8_ __attribute__((ext_vector_type(8)));
-    const short floor_ = a.relu ? (short)0 : (short)0x8000;
-    auto tile_org = [&](int t, int& b, int& ty0, int& tx0) {
-        b = t / (tiles_y * tiles_x);
-        const int r = t - b * (tiles_y * tiles_x);
-        ty0 = (r / tiles_x) * TH; tx0 = (r % tiles_x) * TW;
-    };
-    auto src_org = [&](int ty0, int tx0, int& rs0, int& cs0) {
-        rs0 = linear_tap(ty0 > 0 ? ty0 - 1 : 0, a.usy, a.Hs, true).i0;
-        cs0 = linear_tap(tx0 > 0 ? tx0 - 1 : 0, a.usx, a.Ws, true).i0;
-    };
+    const int floor_ = relu_floor_bf16(a);
     // ---- the loader (the 256 producer threads)
     u32x4 hr[NSLP];
     auto load_src = [&](int t) {                               // raw source window of tile t -> registers
         int b, ty0, tx0, rs0, cs0;
-        tile_org(t, b, ty0, tx0);
-        src_org(ty0, tx0, rs0, cs0);
+        tiles.org(t, b, ty0, tx0);
+        tiles.src_org(a, ty0, tx0, rs0, cs0);
         const bf16_t* img = (const bf16_t*)a.ptr + (long)b * a.Hs * a.Ws * a.C;
 #pragma unroll
         for (int k = 0; k < NSLP; ++k) {
@@ -522,8 +440,8 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     };
     auto stage = [&](int t, int sb) {                          // registers -> staging buffer sb + the tile's tap tables (no barrier here)
         int b, ty0, tx0, rs0, cs0;
-        tile_org(t, b, ty0, tx0);
-        src_org(ty0, tx0, rs0, cs0);
+        tiles.org(t, b, ty0, tx0);
+        tiles.src_org(a, ty0, tx0, rs0, cs0);
 #pragma unroll
         for (int k = 0; k < NSLP; ++k) {
             const int idx = ptid + k * 256;
@@ -558,9 +476,6 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     // arithmetic and linear_tap per chunk the four producer waves needed 4.3 us per tile against 1.9 us of MFMA work.)
     auto lerp_chunks = [&](int sb, int hbuf, auto k0c, auto k1c) {
         const u32x4* stg = stg0 + sb * STG;
-#if defined(C128_CUT) && (C128_CUT == 1 || C128_CUT == 3)     // (tuning aid, timing only: no interpolation)
-        if (a.Hs > 0) return;
-#endif
         constexpr int k0 = decltype(k0c)::value, NB = 6;       // chunks per batch: all their table reads, then all 24 tap reads, are in flight together
         static_for<(decltype(k1c)::value - k0) / NB>([&](auto jc) {
             constexpr int k = k0 + NB * decltype(jc)::value;
@@ -590,26 +505,17 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
 #pragma unroll
                         for (int q = 0; q < 4; ++q) r[q] = lerp_pair_bf16(v[u][0][q], v[u][1][q], v[u][2][q], v[u][3][q], wx[u].x, wx[u].y, wy[u].x, wy[u].y);   // = lerp_chunk
                     }
-                    s16x8_ x = __builtin_bit_cast(s16x8_, r);
-                    x = __builtin_elementwise_max(x, (s16x8_){floor_, floor_, floor_, floor_, floor_, floor_, floor_, floor_});
-                    lds[hbuf * HALO + (pk & 4095)] = __builtin_bit_cast(u32x4, x);
+                    lds[hbuf * HALO + (pk & 4095)] = relu_frag(r, floor_, bf16_t());
                 }
             }
         });
     };
 
-    // tile walk: XCD x owns a contiguous run of tiles, its CUs take consecutive tiles of it (conv3_head_kernel)
-    const bool xcd_walk = (gridDim.x & 7) == 0;
-    const int xcd_ = blockIdx.x & 7, slot_ = blockIdx.x >> 3, nslot_ = gridDim.x >> 3, per_ = (ntiles + 7) >> 3;
-    auto tile_at = [&](int k) {
-        if (!xcd_walk) { const int tt = blockIdx.x + k * gridDim.x; return tt < ntiles ? tt : -1; }
-        const int j = slot_ + k * nslot_, tt = xcd_ * per_ + j;
-        return (j < per_ && tt < ntiles) ? tt : -1;
-    };
+    const C3Walk<> walk(ntiles);
     int kk = 0;
-    int t = tile_at(0);
+    int t = walk.at(0);
     if (t < 0) return;
-    int t1 = tile_at(1);
+    int t1 = walk.at(1);
     constexpr std::integral_constant<int, 0> K0{};
     constexpr std::integral_constant<int, NLDP / 2> KH{};
     constexpr std::integral_constant<int, NLDP> KE{};
@@ -629,7 +535,7 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     int buf = 0, sb = 0;
     if (!consumer) {
         for (; t >= 0;) {
-            const int t2 = tile_at(kk + 2);
+            const int t2 = walk.at(kk + 2);
             ++kk;
             __syncthreads();                                   // A
             if (t2 >= 0) load_src(t2);                         // the source window of tile t2 is requested,
@@ -645,14 +551,8 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     }
     // ---- consumers: W fragments (MFMA row 16 nq + fr; K step (tap, g) -> chunk 4 g + fg of the tap's 128 channels), bias
     // (s_setprio 2 for these waves -- the MFMA stream first when both waves of a SIMD can issue: 308 vs 306 us, no effect)
-    u32x4 wf[9][4];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int n = nq * 16 + fr;
-            wf[tap][g] = n < N ? *(const u32x4*)(W + (long)n * Kpad + tap * 128 + (g * 4 + fg) * 8) : (u32x4){0u, 0u, 0u, 0u};
-        }
+    u32x4 wf[9][4][1];
+    c3_load_wfrags<128>(wf, W, N, Kpad, nq * 16, fr, fg);
     EpiCols cols;
     const int n0 = nq * 16 + fg * 4;
     if (n0 < N) epi_cols_load(e, n0, cols);
@@ -660,7 +560,7 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     const int hb0 = px * PST + c3_chunk_slot<PST>(fg);
     auto store_rows = [&](int tp) {                            // the patch -> global memory, whole 128-byte lines
         int b, ty0, tx0;
-        tile_org(tp, b, ty0, tx0);
+        tiles.org(tp, b, ty0, tx0);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int idx = tid + k * 256, pp = idx >> 3, c = idx & 7;
@@ -672,7 +572,7 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     int tprev = -1;                                            // the tile whose output rows sit in the patch
     constexpr int DEPTH = 6, NFR = 10 * 12;                    // fragments in flight; fragments per tile (halo row, kx, g)
     for (; t >= 0;) {
-        const int t2 = tile_at(kk + 2);
+        const int t2 = walk.at(kk + 2);
         ++kk;
         __syncthreads();                                       // A
         const u32x4* hp = lds + buf * HALO + hb0;
@@ -696,7 +596,7 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
                 // output row i = ir - ky: ky ascends with ir for a fixed i, so each accumulator sees (ky, kx, g) in conv3_halo2's order
                 static_for<3>([&](auto kyc) {
                     constexpr int ky = decltype(kyc)::value, i = ir - ky;
-                    if constexpr (i >= 0 && i < 8) mma_chunk(acc[i], wf[ky * 3 + kx][g], fa, bf16_t());
+                    if constexpr (i >= 0 && i < 8) mma_chunk(acc[i], wf[ky * 3 + kx][g][0], fa, bf16_t());
                 });
                 if constexpr (idx + DEPTH < NFR) {
                     asm volatile("" : "+v"(acc[ir < 8 ? ir : 7]));                              // (the refill stays BEHIND this fragment's MFMAs)
@@ -706,9 +606,7 @@ conv3_c128_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
         };
         // phase 1: the previous tile's rows leave the patch; halo rows 0-4
         static_for<DEPTH>([&](auto ic) { frag_issue(ic); });
-#if !(defined(C128_CUT) && C128_CUT == 3)    // (CUT 3, timing only: no interpolation, no output path -- the K loop and the barriers)
         if (tprev >= 0) store_rows(tprev);
-#endif
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
         kloop(std::integral_constant<int, 0>{}, std::integral_constant<int, NFR / 2>{});
@@ -784,21 +682,9 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool consumer = wid < 4;
     const int fr = lane & 15, fg = lane >> 4;
-    const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
+    const C3Tiles<TH, TW> tiles(a);
+    const C3Walk<> walk(ntiles);
     typedef float f2_ __attribute__((ext_vector_type(2)));
-
-    auto tile_org = [&](int t, int& b, int& ty0, int& tx0) {
-        b = t / (tiles_y * tiles_x);
-        const int r = t - b * (tiles_y * tiles_x);
-        ty0 = (r / tiles_x) * TH; tx0 = (r % tiles_x) * TW;
-    };
-    const bool xcd_walk = (gridDim.x & 7) == 0;
-    const int xcd_ = blockIdx.x & 7, slot_ = blockIdx.x >> 3, nslot_ = gridDim.x >> 3, per_ = (ntiles + 7) >> 3;
-    auto tile_at = [&](int k) {
-        if (!xcd_walk) { const int tt = blockIdx.x + k * gridDim.x; return tt < ntiles ? tt : -1; }
-        const int j = slot_ + k * nslot_, tt = xcd_ * per_ + j;
-        return (j < per_ && tt < ntiles) ? tt : -1;
-    };
 
     // ---------------- producer side.  Thread = (chunk pc of 8 channels, pixel slot ps of 32): a wave covers 8 consecutive cells /
     // halo pixels x 8 chunks, so that every ds_read_b128 / ds_write_b128 service group of 16 lanes meets 16 distinct bank quads (four
@@ -806,7 +692,7 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     const int ptid = tid & 255, pc = ptid & 7, ps = ptid >> 3;
     // source map through a buffer descriptor: taps outside the image are requested past num_records and come back as zeros
     const unsigned src_frame = (unsigned)a.Hs * a.Ws * a.C * 2u;
-    const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.ptr), 0, (unsigned)(ntiles / (tiles_y * tiles_x)) * src_frame, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.ptr), 0, (unsigned)(ntiles / tiles.per_img()) * src_frame, 0x00020000);
     u32x4 hv0[HU], hv1[HU];                                  // the H-pass taps of the tile in production, requested one phase ahead
     float hw1[HU];                                           // ... and their horizontal weights
     // Tile-invariant coordinates of this thread's work items (the per-item arithmetic that is left inside the tile loop is what the
@@ -821,13 +707,15 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
     // item fetches its own through ds_bpermute_b32 (the LDS crossbar, no LDS memory): packed word = offset | step << 16 | valid << 31,
     // and the weight w1.
     const int tl = lane < HWD ? lane : HWD - 1;
-    // geometry of a tile, worked out once (tile_org's integer divisions are ~40 scalar instructions, and a lone wave per SIMD issues
+    // geometry of a tile, worked out once (C3Tiles::org's integer divisions are ~40 scalar instructions, and a lone wave per SIMD issues
     // one instruction of ANY kind per 4 cycles: the producers are bound by their instruction count, scalar ones included)
     struct TileGeo { int b, ty0, tx0, rs0; };
     auto tile_geo = [&](int t) {
         TileGeo g;
-        tile_org(t, g.b, g.ty0, g.tx0);
-        g.rs0 = __builtin_amdgcn_readfirstlane(linear_tap(g.ty0 > 0 ? g.ty0 - 1 : 0, a.usy, a.Hs, true).i0);
+        int cs0;                                             // (the H pass addresses source columns absolutely: only the row origin is kept)
+        tiles.org(t, g.b, g.ty0, g.tx0);
+        tiles.src_org(a, g.ty0, g.tx0, g.rs0, cs0);
+        g.rs0 = __builtin_amdgcn_readfirstlane(g.rs0);
         return g;
     };
     // H pass, part 1: request the two horizontal taps of cells ps + 32 k of tile t (source row rs0 + hr, halo column hxx)
@@ -855,14 +743,12 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
 #pragma unroll
         for (int k = 0; k < HU; ++k) {
             const float w0 = 1.0f - hw1[k];
-            const f2_ w0x = {w0, w0}, w1x = {hw1[k], hw1[k]};
             f32x4 o[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const unsigned p0 = hv0[k][2 * h], p1 = hv0[k][2 * h + 1], q0 = hv1[k][2 * h], q1 = hv1[k][2 * h + 1];
                 const f2_ a0 = {__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xffff0000u)}, b0 = {__uint_as_float(q0 << 16), __uint_as_float(q0 & 0xffff0000u)};
                 const f2_ a1 = {__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)}, b1 = {__uint_as_float(q1 << 16), __uint_as_float(q1 & 0xffff0000u)};
-#if !defined(C3U_PACKED_H)
                 // (beside the consumers' MFMAs a packed f32 instruction costs more than the two plain ones it replaces: MI355X_MICROARCH.md)
                 float t_[4];
                 asm volatile("v_mul_f32 %0, %4, %5\n\tv_mul_f32 %1, %4, %6\n\tv_mul_f32 %2, %4, %7\n\tv_mul_f32 %3, %4, %8"
@@ -870,12 +756,6 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
                 asm volatile("v_fmac_f32 %0, %4, %5\n\tv_fmac_f32 %1, %4, %6\n\tv_fmac_f32 %2, %4, %7\n\tv_fmac_f32 %3, %4, %8"
                              : "+v"(t_[0]), "+v"(t_[1]), "+v"(t_[2]), "+v"(t_[3]) : "v"(hw1[k]), "v"(b0[0]), "v"(b0[1]), "v"(b1[0]), "v"(b1[1]));
                 o[h] = (f32x4){t_[0], t_[1], t_[2], t_[3]};
-                (void)w0x; (void)w1x;
-#else
-                const f2_ t0 = __builtin_elementwise_fma(w1x, b0, w0x * a0);
-                const f2_ t1 = __builtin_elementwise_fma(w1x, b1, w0x * a1);
-                o[h] = (f32x4){t0[0], t0[1], t1[0], t1[1]};
-#endif
             }
             if (k < HU - 1 || ps + 32 * k < NPAIR) { hbuf[ps * CPP + pc + 32 * CPP * k] = o[0]; hbuf[HPL + ps * CPP + pc + 32 * CPP * k] = o[1]; }
         }
@@ -929,16 +809,13 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
             }
         });
     };
-#ifndef C3U_VS
-#define C3U_VS 6
-#endif
-    constexpr int VS = C3U_VS;                               // V-pass items per pixel slot that stay with the producers
+    constexpr int VS = 6;                                    // V-pass items per pixel slot that stay with the producers
     typedef std::integral_constant<int, 0> K0_;
     typedef std::integral_constant<int, VS> KS_;
     typedef std::integral_constant<int, VU> KU_;
 
     int kk = 0;
-    int t = tile_at(0);
+    int t = walk.at(0);
     if (t < 0) return;
     // The two roles run SEPARATE loops over the same tile sequence with the same number of barriers (the hardware barrier counts
     // waves, not program counters): in one shared loop the register allocator keeps the consumers' 144 W registers live through
@@ -947,23 +824,10 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
         // W fragments + epilogue constants (as conv3_head_kernel)
         u32x4 wf[9][2][2];
         float cb[2][4], cw[2][4];
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int n = j * 16 + fr;
-                    wf[tap][ks][j] = n < N ? *(const u32x4*)(W + (long)n * Kpad + tap * 64 + (ks * 4 + fg) * 8) : (u32x4){0u, 0u, 0u, 0u};
-                }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n0 = j * 16 + fg * 4;
-            if (n0 < N) { load4(e.bias + n0, cb[j]); load4(e.scale + n0, cw[j]); }
-            else { cb[j][0] = cb[j][1] = cb[j][2] = cb[j][3] = 0.f; cw[j][0] = cw[j][1] = cw[j][2] = cw[j][3] = 0.f; }
-        }
+        c3_load_wfrags<64>(wf, W, N, Kpad, 0, fr, fg);
+        c3_head_consts(e, N, fg, cb, cw);
         __syncthreads();                                       // (prologue: H rows of the first tile)
-        int tn = tile_at(++kk);
+        int tn = walk.at(++kk);
         __syncthreads();                                       // (prologue: its halo)
         const int cw4 = wid * 4;                               // first output row of this wave
         const int hb0 = (cw4 * HWD + fr) * PST + fg;
@@ -1004,10 +868,10 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
             C3U_T(u1)
             __syncthreads();
             C3U_T(u2)
-            const int tnn = tn >= 0 ? tile_at(++kk) : -1;
+            const int tnn = tn >= 0 ? walk.at(++kk) : -1;
             mma_rows(std::integral_constant<int, 3>());
             int b, ty0, tx0;
-            tile_org(t, b, ty0, tx0);
+            tiles.org(t, b, ty0, tx0);
             // depth = act(b3 + sum_n w3[n] relu(acc + bias[n])): the four lane groups of a pixel hold 8 channels each.  Summed as
             // (g0 + g1) + (g2 + g3) like conv3_head_kernel's two xor-shuffles, but through v_permlane16_swap / v_permlane32_swap on two
             // rows at a time: no LDS round trips, and lane group fg ends up with output row fg -- one full-wave store per tile
@@ -1016,9 +880,7 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
             for (int i = 0; i < 4; ++i) {
                 float s = 0.f;
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    s += fmaxf(acc[i][j][0] + cb[j][0], 0.f) * cw[j][0] + fmaxf(acc[i][j][1] + cb[j][1], 0.f) * cw[j][1] +
-                         fmaxf(acc[i][j][2] + cb[j][2], 0.f) * cw[j][2] + fmaxf(acc[i][j][3] + cb[j][3], 0.f) * cw[j][3];
+                for (int j = 0; j < 2; ++j) s += c3_head_dot(acc[i][j], cb[j], cw[j]);
                 sr[i] = s;
             }
             typedef unsigned u2_ __attribute__((ext_vector_type(2)));
@@ -1045,7 +907,7 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
         h_request(gn);
         h_compute();
         __syncthreads();
-        int tn = tile_at(++kk);
+        int tn = walk.at(++kk);
         v_pass(gn, 0, K0_(), KU_());
         if (tn >= 0) { gn = tile_geo(tn); h_request(gn); }
         __syncthreads();
@@ -1056,7 +918,7 @@ conv3_head_ups_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, Ge
             C3U_T(u1)
             __syncthreads();                                   // H rows of tile tn are in place
             C3U_T(u2)
-            const int tnn = tn >= 0 ? tile_at(++kk) : -1;
+            const int tnn = tn >= 0 ? walk.at(++kk) : -1;
             if (tn >= 0) {
                 if (tnn >= 0) { gnn = tile_geo(tnn); h_request(gnn); }     // in flight under the V pass and the barrier
                 v_pass(gn, buf ^ 1, K0_(), KS_());
@@ -1115,7 +977,7 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     KERNARG_WARM_END(kaw_)
     constexpr int CPP = 16, PST = 17, HWD = TW + 2, HPX = (TH + 2) * HWD, HALO = HPX * PST;
     constexpr int NCH = HPX * CPP, NLD = (NCH + 511) / 512;
-    constexpr int NW = 8, WN = 2, FM = 4, FN = 4, FPR = TW / 16;
+    constexpr int WN = 2, FM = 4, FN = 4, FPR = TW / 16;
     constexpr int NS = 8, WST = 128 * 4, NKT = 36, PD = NS - 1;  // W ring: 8 stages of 128 rows x 64 B (32 channels of one tap), 36 K tiles
     constexpr int HKT = 28;                                   // K tile whose issue slot also requests the next halo (see below)
     static_assert(TH * TW == 256 && TW % 16 == 0, "256-pixel tiles of 16-pixel fragments");
@@ -1127,12 +989,9 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wid / WN, wave_n = wid % WN, grp = wid >> 2;
     const int fr = lane & 15, fg = lane >> 4, px = c3_lane_pixel<PST>(fr);
-    const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
-
-    // tiles: XCD x (= blockIdx % 8) owns the contiguous run [x per, (x + 1) per) and its CUs walk it together
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3, per = (ntiles + 7) >> 3;
-    auto tile_id = [&](int j) { return (j < per && xcd * per + j < ntiles) ? xcd * per + j : -1; };
-    int j = slot, t = tile_id(j);
+    const C3Tiles<TH, TW> tiles(a);
+    const C3Walk<true> walk(ntiles);                        // (c3_wide_ok: the grid is a multiple of 8 blocks)
+    int kk = 0, t = walk.at(0);
     if (t < 0) return;
 
     // W stage = 128 rows x 4 chunks; one LDS-DMA instruction per wave per stage: wave w brings rows 16 w .. 16 w + 15, lane l row
@@ -1147,17 +1006,11 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     }
     auto issue_w = [&](int stage, int kt) { lds_dma16(rsW, lds + stage * WST + wid * 64, voW, kt * 64); };
 
-    typedef short s16x8_ __attribute__((ext_vector_type(8)));
-    const short floor_ = a.relu ? (short)0 : (short)0x8000;
+    const int floor_ = relu_floor_bf16(a);
     u32x4 hr[NLD];
-    auto tile_org = [&](int tt, int& b, int& ty0, int& tx0) {
-        b = tt / (tiles_y * tiles_x);
-        const int r = tt - b * (tiles_y * tiles_x);
-        ty0 = (r / tiles_x) * TH; tx0 = (r % tiles_x) * TW;
-    };
     auto load_halo = [&](int tt) {
         int b, ty0, tx0;
-        tile_org(tt, b, ty0, tx0);
+        tiles.org(tt, b, ty0, tx0);
         const bf16_t* img = (const bf16_t*)a.ptr + (long)b * a.Hi * a.Wi * a.C;
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
@@ -1166,7 +1019,8 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
             const int hy = p / HWD, hx = p - hy * HWD;
             int iy = ty0 + hy - 1, ix = tx0 + hx - 1;
             const bool in = idx < NCH && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi;
-            iy = in ? iy : 0; ix = in ? ix : 0;                 // (always ONE load per k: the vmcnt arithmetic counts them)
+            // always ONE load per k, at a valid address: the vmcnt arithmetic counts them (conv3_head_kernel<0>'s loader, which nothing counts, skips them)
+            iy = in ? iy : 0; ix = in ? ix : 0;
             const u32x4 v = *(const u32x4*)(img + ((long)iy * a.Wi + ix) * a.C + c * 8);
             hr[k] = in ? v : (u32x4){0u, 0u, 0u, 0u};
         }
@@ -1175,11 +1029,7 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const int idx = tid + k * 512;
-            if (idx < NCH) {
-                s16x8_ x = __builtin_bit_cast(s16x8_, hr[k]);
-                x = __builtin_elementwise_max(x, (s16x8_){floor_, floor_, floor_, floor_, floor_, floor_, floor_, floor_});
-                halo[(idx >> 4) * PST + c3_chunk_slot<PST>(idx & 15)] = __builtin_bit_cast(u32x4, x);
-            }
+            if (idx < NCH) halo[(idx >> 4) * PST + c3_chunk_slot<PST>(idx & 15)] = relu_frag(hr[k], floor_, bf16_t());
         }
     };
 
@@ -1204,7 +1054,7 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     C3_T(t_begin)
     while (t >= 0) {
         C3_T(t_a)
-        const int tn = tile_id(j + nslot);
+        const int tn = walk.at(++kk);
         const int tl = tn >= 0 ? tn : t;                      // (no next tile: the loads are still issued -- counted -- and dropped)
         f32x4 acc[FM][FN];
 #pragma unroll
@@ -1269,7 +1119,7 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
         // (requesting the residual values inside the K loop -- K tile 28 with the halo, or K tile 33 -- made the loop 3-4 us slower
         // per tile than it saved here, measured)
         int b, ty0, tx0;
-        tile_org(t, b, ty0, tx0);
+        tiles.org(t, b, ty0, tx0);
         bool ok[FM];
         long mo[FM];
         uint2 rr[FM][FN];
@@ -1315,7 +1165,7 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
             }
         C3_ACC(6, wall_clock64() - t_d)
         C3_ACC(3, 1)
-        gb = (gb + NKT) & (NS - 1); t = tn; j += nslot;
+        gb = (gb + NKT) & (NS - 1); t = tn;
     }
     c3_wait_vm<0>();                                          // the ring's last requests must land before the LDS is released
     C3_ACC(5, wall_clock64() - t_begin)
@@ -1327,35 +1177,73 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
 // ring is two K tiles deep at most beside two halo buffers, i.e. ~1 000 cycles of cover for an LDS-DMA that needs ~2 000 under
 // load; two independent blocks per CU hide that better than one deeper-pipelined one.  Removed.)
 
-// The conv3_halo2_kernel instantiations (CPP, PST, BN, WM, WN, NS[, HG]); the other kernels of this file take one each
-#define C3_HALO2(X)                                                                                                              \
-    X(C3_H2_MID, 16,17,64,4,2,10,6)      /* mid-size maps, one block per CU (plan_conv3_halo2) */                                \
-    X(C3_H2_C128_N128, 16,17,128,2,4,2)  /* (row pitch 17 chunks: 2 blocks / CU; 18 would be conflict-free) */                   \
-    X(C3_H2_C128_N64, 16,17,64,4,2,3)                                                                                            \
-    X(C3_H2_C128_N32, 16,17,32,4,1,3)                                                                                            \
-    X(C3_H2_C64_N128, 8,10,128,2,4,3)                                                                                            \
-    X(C3_H2_C64_N64, 8,10,64,4,2,3)                                                                                              \
-    X(C3_H2_C64_N32, 8,10,32,4,1,3)
-enum { C3_HEAD_UPS, C3_HEAD_1, C3_HEAD_0, C3_C128_UPS, C3_WIDE_8_32, C3_WIDE_16_16,
-#define X(ID, ...) ID,
-       C3_HALO2(X)
-#undef X
-};
-static const char* const c3_names[] = {"conv3_head_ups_kernel", "conv3_head_kernel<1>", "conv3_head_kernel<0>", "conv3_c128_ups_kernel",
-                                       "conv3_wide_kernel<8,32>", "conv3_wide_kernel<16,16>",
-#define X(ID, ...) "conv3_halo2_kernel<" #__VA_ARGS__ ">",
-                                       C3_HALO2(X)
-#undef X
-};
+// Every kernel instantiation of this file, once: P(id, kernel) a persistent kernel (512 threads, launched with the tile count),
+// H(id, CPP, PST, BN, WM, WN, NS[, HG]) a one-shot conv3_halo2_kernel.  The enum, the names GemmPlan reports (the tests pin them),
+// the block sizes and the launch switch are generated from this list.
+#define C3_INSTANCES(P, H)                                                                                                       \
+    P(C3_HEAD_UPS, conv3_head_ups_kernel)                                                                                        \
+    P(C3_HEAD_1, conv3_head_kernel<1>)                                                                                           \
+    P(C3_HEAD_0, conv3_head_kernel<0>)                                                                                           \
+    P(C3_C128_UPS, conv3_c128_ups_kernel)                                                                                        \
+    P(C3_WIDE_8_32, conv3_wide_kernel<8,32>)                                                                                     \
+    P(C3_WIDE_16_16, conv3_wide_kernel<16,16>)                                                                                   \
+    H(C3_H2_MID, 16,17,64,4,2,10,6)      /* mid-size maps, one block per CU (c3_mid_ok) */                                       \
+    H(C3_H2_C128_N128, 16,17,128,2,4,2)  /* (row pitch 17 chunks: 2 blocks / CU; 18 would be conflict-free) */                   \
+    H(C3_H2_C128_N64, 16,17,64,4,2,3)                                                                                            \
+    H(C3_H2_C128_N32, 16,17,32,4,1,3)                                                                                            \
+    H(C3_H2_C64_N128, 8,10,128,2,4,3)                                                                                            \
+    H(C3_H2_C64_N64, 8,10,64,4,2,3)                                                                                              \
+    H(C3_H2_C64_N32, 8,10,32,4,1,3)
+#define C3_ID(ID, ...) ID,
+enum { C3_INSTANCES(C3_ID, C3_ID) };
+#undef C3_ID
 #define C3_BLOCK(CPP, PST, BN, WM, WN, ...) 64 * WM * WN
-static constexpr int c3_block[] = {512, 512, 512, 512, 512, 512,
-#define X(ID, ...) C3_BLOCK(__VA_ARGS__),
-                                   C3_HALO2(X)
-#undef X
-};
+#define C3_P(ID, ...) {#__VA_ARGS__, 512},
+#define C3_H(ID, ...) {"conv3_halo2_kernel<" #__VA_ARGS__ ">", C3_BLOCK(__VA_ARGS__)},
+static const struct { const char* name; int block; } c3_inst[] = { C3_INSTANCES(C3_P, C3_H) };
+#undef C3_P
+#undef C3_H
 #undef C3_BLOCK
 static void c3_plan(GemmPlan& p, int inst, unsigned grid, int xn, const GemmA& a) {
-    p.family = GEMM_CONV3; p.inst = inst; p.name = c3_names[inst]; p.grid = grid; p.block = c3_block[inst]; p.xn = xn; p.ups = a.ups;
+    p.family = GEMM_CONV3; p.inst = inst; p.name = c3_inst[inst].name; p.grid = grid; p.block = c3_inst[inst].block; p.xn = xn; p.ups = a.ups;
+}
+
+// The four eligibility rules of plan_conv3_halo2, in the order it asks them.  t16 / t8 / t256: the batch's tiles of 16 x 16, 8 x 16
+// and 256 pixels.
+
+// The persistent head kernels (conv3_head_ups / conv3_head<1> / conv3_head<0>): the fused head tail from D2S_HEADP_MIN tiles.
+// (from ~8 tiles per CU: at batch 1-2 the 627 / 1 254 tiles are 2.4 / 4.9 rounds of 256 persistent blocks, and the one-shot blocks
+//  -- 1 221 per frame, many per CU -- finish sooner: 25.9 -> 20.3 us at batch 1, even at batch 4)
+static bool c3_head_persistent_ok(const GemmA& a, int N, const GemmEpi& e, long t16) {
+    static EnvInt headp_min{"D2S_HEADP_MIN", 2048};
+    return e.map == MAP_HEAD && a.C == 64 && N <= 32 && t16 >= headp_min.get();
+}
+// the head's conv1 at batch: persistent blocks with W in registers and the up-sample in the loader (conv3_c128_ups_kernel)
+static bool c3_c128_ups_ok(const GemmA& a, int N, const GemmEpi& e, int nimg, long t8) {
+    static EnvInt c128_min{"D2S_HEAD1P_MIN", 2048};          // fewest tiles of 8 x 16 pixels (2048 = 6 frames of 168 x 296); 0 = off
+    return a.ups && a.C == 128 && N == 64 && e.map == MAP_ROWS && !a.relu && a.usy <= 0.5f && a.usx <= 0.5f && a.Hs >= 2 && a.Ws >= 2 &&
+           (e.out_type == OUT_T || e.out_type == OUT_BF16) && !e.scale && !e.res1 && !e.res2 && e.act == ACT_NONE && !e.deq && !e.out2 && !(e.ldc & 7) &&
+           c128_min.get() > 0 && t8 >= c128_min.get() && t8 < (1L << 30) && (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31);
+}
+// conv3_wide_kernel: C = 128 -> N = 128 without a folded up-sample, on a grid of whole XCD rounds (ncu & ~7 blocks)
+// (the grid plan_conv3_halo2 gives it, ncu & ~7 >= 8, must stay a multiple of 8: the kernel walks its tiles with C3Walk<true>, which has
+//  no launch-order branch)
+static bool c3_wide_ok(const GemmA& a, int N, int Kpad, const GemmEpi& e, long t256, int ncu) {
+    static EnvInt no_wide{"D2S_NO_WIDE", 0};
+    return !no_wide.get() && !a.ups && e.map == MAP_ROWS && a.C == 128 && N == 128 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
+           (e.out_type == OUT_T || e.out_type == OUT_BF16) && !e.scale && !e.res2 && !e.res1_mod && (e.act == ACT_NONE || e.act == ACT_RELU) &&
+           t256 >= 384 && t256 < (1L << 30) && (ncu & ~7) >= 8;     // 384 tiles: 1.5 rounds of the CUs
+}
+// Mid-size maps (round 5): the fusion stage on the 84 x 148 map of the batch-1 frame (110 tiles x 2 blocks of 64 channels = 220
+// blocks, every one resident at once) ran as implicit-GEMM tiles + a split-K reduce launch, 19.5 us per convolution of 3.7 GF.  With
+// one block per CU a block can afford the LDS: ten 8 KB weight stages requested ahead (NS = 10: half of its 18 K tiles in the
+// prologue) and the halo fill with all of a thread's chunks in flight (HG = 6 instead of 3 per pass: nobody else covers its round
+// trips here): 19.5 -> 15.5 us, two launches per frame.  The SMALLER maps (11 x 19 ... 42 x 74: 16-120 blocks) were tried the same
+// way with all 72 KB of a 32-channel block's weights up front (NS = 19, HG = 12): 11.6-12.7 us before, 11.4-14.9 after -- those
+// launches are not paced by the K loop's round trips (boundary, cold code and the epilogue are what is left); not kept.
+static bool c3_mid_ok(const GemmA& a, int N, int Kpad, const GemmEpi& e, long t8, int ncu) {
+    return a.C == 128 && e.map == MAP_ROWS && N % 64 == 0 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
+           t8 * (N / 64) <= ncu && t8 * (N / 64) * 2 > ncu;
 }
 
 // Eligible: bf16, stride 1, same-size output, C = 64 | 128, K = 9 C, plain row mapping or the fused head, enough tiles to fill the
@@ -1369,12 +1257,11 @@ bool plan_conv3_halo2(const GemmA& a, int M, int N, int K, int Kpad, const GemmE
     if (N != 32 && N != 64 && (N & 127)) return false;
     const int nimg = M / (a.Ho * a.Wo);
     if ((long)nimg * a.Ho * a.Wo != M) return false;
-    // (from ~8 tiles per CU: at batch 1-2 the 627 / 1 254 tiles are 2.4 / 4.9 rounds of 256 persistent blocks, and the one-shot blocks
-    //  below -- 1 221 per frame, many per CU -- finish sooner: 25.9 -> 20.3 us at batch 1, even at batch 4)
-    static EnvInt headp_min{"D2S_HEADP_MIN", 2048};
-    if (e.map == MAP_HEAD && a.C == 64 && N <= 32 && (long)nimg * cdiv(a.Ho, 16) * cdiv(a.Wo, 16) >= headp_min.get()) {
-        const int ncu = device_cu_count();
-        const int ntiles = nimg * cdiv(a.Ho, 16) * cdiv(a.Wo, 16);
+    const int ncu = device_cu_count();
+    const long per16 = (long)cdiv(a.Ho, 16) * cdiv(a.Wo, 16), per8x32 = (long)cdiv(a.Ho, 8) * cdiv(a.Wo, 32);   // tiles per image
+    const long t16 = nimg * per16, t8 = (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16);
+    const long t256 = nimg * std::min(per8x32, per16);      // conv3_wide's 256-pixel tiles: 8 x 32 or 16 x 16, whichever pads the map less
+    if (c3_head_persistent_ok(a, N, e, t16)) {
         static EnvInt no_headups{"D2S_NO_HEADUPS", 0};
         // (the staged 13 x 13 source window holds scales <= 0.6; ReLU-on-load is not part of the interpolating loader)
         if (a.ups && (no_headups.get() || a.usy > 0.6f || a.usx > 0.6f || a.relu)) return false;
@@ -1382,53 +1269,28 @@ bool plan_conv3_halo2(const GemmA& a, int M, int N, int K, int Kpad, const GemmE
         // (the source map is read through one buffer descriptor; a tap's source-column byte offset travels in the low 16 bits of the
         //  bpermute word of h_request: a source row must stay within 64 KiB, i.e. Ws <= 512 at C = 64 -- wider maps take <1>)
         const bool ups_fits = (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31) && (long)a.Ws * a.C * 2 <= 65536;
-        c3_plan(p, a.ups ? (!ups_v1.get() && ups_fits ? C3_HEAD_UPS : C3_HEAD_1) : C3_HEAD_0, std::min(ncu, ntiles), ntiles, a);
+        c3_plan(p, a.ups ? (!ups_v1.get() && ups_fits ? C3_HEAD_UPS : C3_HEAD_1) : C3_HEAD_0, std::min(ncu, (int)t16), (int)t16, a);
         return true;
     }
-    // the head's conv1 at batch: persistent blocks with W in registers and the up-sample in the loader (conv3_c128_ups_kernel)
-    static EnvInt c128_min{"D2S_HEAD1P_MIN", 2048};          // fewest tiles of 8 x 16 pixels (2048 = 6 frames of 168 x 296); 0 = off
-    if (a.ups && a.C == 128 && N == 64 && e.map == MAP_ROWS && !a.relu && a.usy <= 0.5f && a.usx <= 0.5f && a.Hs >= 2 && a.Ws >= 2 &&
-        (e.out_type == OUT_T || e.out_type == OUT_BF16) && !e.scale && !e.res1 && !e.res2 && e.act == ACT_NONE && !e.deq && !e.out2 && !(e.ldc & 7) &&
-        c128_min.get() > 0 && (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) >= c128_min.get() &&
-        (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) < (1L << 30) && (long)nimg * a.Hs * a.Ws * a.C * 2 < (1L << 31)) {
-        const int ncu = device_cu_count();
-        const int ntl = (int)((long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16));
-        c3_plan(p, C3_C128_UPS, std::min(ncu & ~7, ntl), ntl, a);
+    if (c3_c128_ups_ok(a, N, e, nimg, t8)) {
+        c3_plan(p, C3_C128_UPS, std::min(ncu & ~7, (int)t8), (int)t8, a);
         return true;
     }
-    static EnvInt no_wide{"D2S_NO_WIDE", 0};
-    if (!no_wide.get() && !a.ups && e.map == MAP_ROWS && a.C == 128 && N == 128 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
-        (e.out_type == OUT_T || e.out_type == OUT_BF16) && !e.scale && !e.res2 && !e.res1_mod && (e.act == ACT_NONE || e.act == ACT_RELU)) {
-        const int ncu = device_cu_count();
-        const long pad_a = (long)cdiv(a.Ho, 8) * cdiv(a.Wo, 32), pad_b = (long)cdiv(a.Ho, 16) * cdiv(a.Wo, 16);   // 256-pixel tiles per image
-        const long ntl = nimg * std::min(pad_a, pad_b);
-        const int grid_w = ncu & ~7;
-        if (ntl >= 384 && ntl < (1L << 30) && grid_w >= 8) {          // 384 tiles: 1.5 rounds of the CUs
-            c3_plan(p, pad_a <= pad_b ? C3_WIDE_8_32 : C3_WIDE_16_16, grid_w, (int)ntl, a);
-            return true;
-        }
+    if (c3_wide_ok(a, N, Kpad, e, t256, ncu)) {
+        c3_plan(p, per8x32 <= per16 ? C3_WIDE_8_32 : C3_WIDE_16_16, ncu & ~7, (int)t256, a);
+        return true;
     }
-    const long tiles_m = (long)nimg * cdiv(a.Ho, 8) * cdiv(a.Wo, 16);
-    // Mid-size maps (round 5): the fusion stage on the 84 x 148 map of the batch-1 frame (110 tiles x 2 blocks of 64 channels = 220
-    // blocks, every one resident at once) ran as implicit-GEMM tiles + a split-K reduce launch, 19.5 us per convolution of 3.7 GF.  With
-    // one block per CU a block can afford the LDS: ten 8 KB weight stages requested ahead (NS = 10: half of its 18 K tiles in the
-    // prologue) and the halo fill with all of a thread's chunks in flight (HG = 6 instead of 3 per pass: nobody else covers its round
-    // trips here): 19.5 -> 15.5 us, two launches per frame.  The SMALLER maps (11 x 19 ... 42 x 74: 16-120 blocks) were tried the same
-    // way with all 72 KB of a 32-channel block's weights up front (NS = 19, HG = 12): 11.6-12.7 us before, 11.4-14.9 after -- those
-    // launches are not paced by the K loop's round trips (boundary, cold code and the epilogue are what is left); not kept.
-    const int ncu = device_cu_count();
     unsigned grid = 0;
-    if (a.C == 128 && e.map == MAP_ROWS && N % 64 == 0 && (long)gemm_npad(N) * Kpad * 2 < (1L << 31) &&
-        tiles_m * (N / 64) <= ncu && tiles_m * (N / 64) * 2 > ncu) {
-        const int xn = pick_xn((int)tiles_m, N / 64, 64, Kpad, 2, grid);
+    if (c3_mid_ok(a, N, Kpad, e, t8, ncu)) {
+        const int xn = pick_xn((int)t8, N / 64, 64, Kpad, 2, grid);
         c3_plan(p, C3_H2_MID, grid, xn, a);
         return true;
     }
     const int bn = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
     // small maps: latency-bound, the small-tile kernels do better (head conv1 at batch 1: 399 tiles, 26.5 -> 21.8 us here; 110-tile maps lose)
-    if (tiles_m * cdiv(N, bn) < 384) return false;
+    if (t8 * cdiv(N, bn) < 384) return false;
     if ((long)gemm_npad(N) * Kpad * 2 >= (1L << 31)) return false;
-    const int xn = pick_xn((int)tiles_m, cdiv(N, bn), bn, Kpad, 2, grid);
+    const int xn = pick_xn((int)t8, cdiv(N, bn), bn, Kpad, 2, grid);
     if (a.C == 128) c3_plan(p, bn == 128 ? C3_H2_C128_N128 : (bn == 64 ? C3_H2_C128_N64 : C3_H2_C128_N32), grid, xn, a);
     else c3_plan(p, bn == 128 ? C3_H2_C64_N128 : (bn == 64 ? C3_H2_C64_N64 : C3_H2_C64_N32), grid, xn, a);
     return true;
@@ -1438,15 +1300,11 @@ void launch_conv3_halo2(const GemmPlan& p, const GemmA& a, const void* W, int M,
     const bf16_t* w = (const bf16_t*)W;
     const dim3 grid(p.grid), block(p.block);
     switch (p.inst) {
-        case C3_HEAD_UPS: hipLaunchKernelGGL(conv3_head_ups_kernel, grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
-        case C3_HEAD_1: hipLaunchKernelGGL((conv3_head_kernel<1>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
-        case C3_HEAD_0: hipLaunchKernelGGL((conv3_head_kernel<0>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
-        case C3_C128_UPS: hipLaunchKernelGGL(conv3_c128_ups_kernel, grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
-        case C3_WIDE_8_32: hipLaunchKernelGGL((conv3_wide_kernel<8, 32>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
-        case C3_WIDE_16_16: hipLaunchKernelGGL((conv3_wide_kernel<16, 16>), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
-#define X(ID, ...) case ID: hipLaunchKernelGGL((conv3_halo2_kernel<__VA_ARGS__>), grid, block, 0, st, a, w, M, N, Kpad, e, p.xn); break;
-        C3_HALO2(X)
-#undef X
+#define C3_P(ID, ...) case ID: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
+#define C3_H(ID, ...) case ID: hipLaunchKernelGGL((conv3_halo2_kernel<__VA_ARGS__>), grid, block, 0, st, a, w, M, N, Kpad, e, p.xn); break;
+        C3_INSTANCES(C3_P, C3_H)
+#undef C3_P
+#undef C3_H
     }
 }
 

@@ -47,16 +47,8 @@ __device__ unsigned long long glds_timing[4096 * 8];
 #define GL_STAMP(SLOT) {}
 #endif
 
-// max(x, floor) on a fragment: floor = 0 gives ReLU, floor = lowest gives identity (no branch in the MFMA stream).
-// bf16 as int16: sign bit set <=> negative, and positive bf16 order like positive int16 -> v_pk_max_i16.
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ u32x4 relu_frag(u32x4 v, int floor_bits, bf16_t) {
-    s16x8 x = __builtin_bit_cast(s16x8, v);
-    short f = (short)floor_bits;
-    x = __builtin_elementwise_max(x, (s16x8){f, f, f, f, f, f, f, f});
-    return __builtin_bit_cast(u32x4, x);
-}
+// max(x, floor) on a fragment: floor = 0 gives ReLU, floor = lowest gives identity (no branch in the MFMA stream).  The bf16 form is
+// in gemm_epi.h (the convolutions of conv3.hip use it too).
 __device__ __forceinline__ u32x4 relu_frag(u32x4 v, int, fp8_t) { return v; }
 __device__ __forceinline__ u32x4 relu_frag(u32x4 v, int, bx3_t) { return v; }   // bf16x3: ReLU-on-load happens on the fp32 values as they are staged   // e4m3 operands: encoder linears only, no ReLU-on-load
 __device__ __forceinline__ u32x4 relu_frag(u32x4 v, int floor_bits, float) {
@@ -543,6 +535,8 @@ conv3_halo_kernel(GemmA a, const T* __restrict__ W, int M, int N, int K, int Kpa
     const int nimg = M / (a.Ho * a.Wo);
     int tm_, tn_;
     if (!tile_of_block(blockIdx.x, nimg * tiles_y * tiles_x, (N + BN - 1) / BN, xn, tm_, tn_)) return;
+    // (the tile origin inline, not conv3_tile.h's C3Tiles::org, as in conv3_halo2_kernel: with that prologue <f32,64,4,2,4> measured
+    //  1-1.5 % slower -- profiles/conv3_shared_ab.md)
     const int b = tm_ / (tiles_y * tiles_x), ty0 = ((tm_ / tiles_x) % tiles_y) * TH, tx0 = (tm_ % tiles_x) * TW;
     const int bn0 = tn_ * BN;
     const int cpp = a.C / CE, smask = cpp - 1;          // chunks per pixel: a power of two <= 16
@@ -600,41 +594,12 @@ conv3_halo_kernel(GemmA a, const T* __restrict__ W, int M, int N, int K, int Kpa
     }
 #undef D2S_ISSUE_W
     // ---- epilogue: tile row ty -> output pixel (ty0 + ty, tx0 + fr)
-    const int x = tx0 + fr;
+    const int nb = bn0 + wave_n * (BN / WN) + fg * 4;   // this lane's first column
     EpiCols cols[FN];
 #pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int n0 = bn0 + wave_n * (BN / WN) + j * 16 + fg * 4;
-        if (n0 < N) epi_cols_load(e, n0, cols[j]);
-    }
-    float pre[FM][FN][4];                               // residual values, all requested before the first store (gemm_epi.h)
-    const bool pre_on = epi_res1_ahead(e);
-    if (pre_on) {
-        static_for<FM>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            const int y = ty0 + wave_m * FM + i;
-            static_for<FN>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                const int n0 = bn0 + wave_n * (BN / WN) + j * 16 + fg * 4;
-                if (y < a.Ho && x < a.Wo && n0 < N) epi_res1_load<T>(e, (b * a.Ho + y) * a.Wo + x, n0, pre[i][j]);
-            });
-        });
-    }
-    static_for<FM>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const int y = ty0 + wave_m * FM + i;
-        if (y < a.Ho && x < a.Wo) {
-            const int m = (b * a.Ho + y) * a.Wo + x;
-            static_for<FN>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                const int n0 = bn0 + wave_n * (BN / WN) + j * 16 + fg * 4;
-                if (n0 < N) {
-                    float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                    epilogue_dispatch<T>(e, m, n0, v, false, pre_on ? pre[i][j] : nullptr, &cols[j]);
-                }
-            });
-        }
-    });
+    for (int j = 0; j < FN; ++j)
+        if (nb + j * 16 < N) epi_cols_load(e, nb + j * 16, cols[j]);
+    conv_tile_epilogue<T, FM, FN>(a, e, acc, cols, b, ty0 + wave_m * FM, tx0 + fr, nb, N);
 }
 
 // descriptor-addressed LDS-DMA: plain A, whole K tiles, 32-bit byte offsets

@@ -136,6 +136,18 @@ __device__ __forceinline__ u32x4 ups_chunk(const T* src_img /* [Hs, Ws, C] of th
     return lerp_chunk(v00, v01, v10, v11, tx, ty, T());
 }
 
+// max(x, floor) on a 16-byte chunk of bf16: floor = 0 gives ReLU, floor = 0x8000 (the most negative int16) gives identity (no branch
+// in the MFMA stream, none around an LDS store).  bf16 as int16: sign bit set <=> negative, and positive bf16 order like positive
+// int16 -> v_pk_max_i16.  The ReLU-on-load of every bf16 loader (gemm.hip's register-staged tiles, the convolutions' halo stores).
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ u32x4 relu_frag(u32x4 v, int floor_bits, bf16_t) {
+    s16x8 x = __builtin_bit_cast(s16x8, v);
+    short f = (short)floor_bits;
+    x = __builtin_elementwise_max(x, (s16x8){f, f, f, f, f, f, f, f});
+    return __builtin_bit_cast(u32x4, x);
+}
+__device__ __forceinline__ int relu_floor_bf16(const GemmA& a) { return a.relu ? 0 : (short)0x8000; }
+
 // Halo fill of the LDS-resident-input convolutions: the (TH + 2) x (TW + 2) x C input window of an output tile, zero outside the image,
 // optionally interpolated on the fly (a.ups).  GRP chunks per thread are REQUESTED before the first is used: written as a plain loop
 // (load, wait, store; run-time trip count) the ~6 chunks of a thread were six dependent L2 round trips at the head of every block.
@@ -379,6 +391,43 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for_i
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for_impl<I + 1, N>(f); }
 }
 template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl<0, N>(f); }
+
+// Epilogue of a wave's FM tile rows x FN column fragments in the row-tile convolutions (conv3_halo_kernel, conv3_halo2_kernel): tile
+// row i is output pixel (y0 + i, x) of frame b, fragment j the columns n0 + 16 j .. + 3.  Every residual value is requested before
+// the first store (epi_res1_load above), then epilogue_dispatch per (row, fragment).  cols: the column vectors of the FN fragments,
+// loaded by the KERNEL (`if (n0 + 16 j < N) epi_cols_load(...)`, five lines): with that loop in here the compiler merges the column
+// guard with epi_cols_load's null test of e.bias while this function is still on its own, where e is any GemmEpi and not the kernel's
+// argument -- the bias pointer then stays a generic pointer after inlining, its loads come out as flat_load instead of global_load
+// (MAP_HEAD's too) and the K loop of every row-tile kernel is scheduled differently (conv3_halo2<16,17,128,2,4,2>: 71 more s_waitcnt).
+template <typename T, int FM, int FN>
+__device__ __forceinline__ void conv_tile_epilogue(const GemmA& a, const GemmEpi& e, const f32x4 (&acc)[FM][FN], const EpiCols (&cols)[FN], int b, int y0, int x, int n0, int N) {
+    float pre[FM][FN][4];
+    const bool pre_on = epi_res1_ahead(e);
+    if (pre_on) {
+        static_for<FM>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const int y = y0 + i;
+            static_for<FN>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if (y < a.Ho && x < a.Wo && n0 + j * 16 < N) epi_res1_load<T>(e, (b * a.Ho + y) * a.Wo + x, n0 + j * 16, pre[i][j]);
+            });
+        });
+    }
+    static_for<FM>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int y = y0 + i;
+        if (y < a.Ho && x < a.Wo) {
+            const int m = (b * a.Ho + y) * a.Wo + x;
+            static_for<FN>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if (n0 + j * 16 < N) {
+                    float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                    epilogue_dispatch<T>(e, m, n0 + j * 16, v, false, pre_on ? pre[i][j] : nullptr, &cols[j]);
+                }
+            });
+        }
+    });
+}
 
 
 }  // namespace d2s
