@@ -51,6 +51,19 @@ class DibrParams(C.Structure):
                 ("viewport", C.c_float * 4), ("alpha_mode", C.c_int32), ("struct_size", C.c_uint32)]
 
 
+class XrScreen(C.Structure):
+    """d2s_xr_screen: the OpenXR viewer's screen in world space (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("curve", C.c_int32), ("width", C.c_double), ("height", C.c_double),
+                ("distance", C.c_double), ("pan_x", C.c_double), ("pan_y", C.c_double), ("yaw", C.c_double), ("pitch", C.c_double),
+                ("roll", C.c_double), ("normal_offset", C.c_double), ("clear", C.c_float * 4)]
+
+
+class XrEye(C.Structure):
+    """d2s_xr_eye: one swapchain image -- vp = proj @ view row-major, its size, and which eye's offset the shader takes."""
+    _fields_ = [("vp", C.c_double * 16), ("width", C.c_int32), ("height", C.c_int32), ("eye", C.c_int32), ("struct_size", C.c_uint32)]
+
+
+XR_CURVE = {"flat": 0, "horizontal": 1, "vertical": 2}      # D2S_XR_CURVE_*
 DIBR_ALPHA = {"window": 0, "premultiplied": 1, "rgba": 2}      # D2S_DIBR_ALPHA_*
 COMPOSITE = {"Anaglyph": 0, "Interleaved": 1, "Interleaved-V": 2, "Depth Map": 3}      # D2S_COMPOSITE_*
 
@@ -125,6 +138,11 @@ SYMBOLS = {
     "d2s_dibr_crop_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "d2s_dibr_warp_crop": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
                                      _P, C.c_int, _P]),
+    # the OpenXR eye views (xr_viewer/effects.py:1023-1137, xr_viewer/screen.py:29-173)
+    "d2s_dibr_xr_shape": (C.c_int, [C.POINTER(XrEye), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "d2s_dibr_xr_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "d2s_dibr_xr_eyes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                   C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, _P]),
     "d2s_crop_detect_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "d2s_crop_detect": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, _P]),
     "d2s_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -147,6 +165,9 @@ SYMBOLS = {
     "d2s_view_pipeline_crop_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                  C.POINTER(PostParams), C.POINTER(DibrParams), C.c_int, C.POINTER(C.c_double), C.c_int, _P,
                                                  C.c_int, _P, _P]),
+    "d2s_view_pipeline_xr_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                               C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double), C.POINTER(XrScreen),
+                                               C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, _P]),
     "d2s_engine_reset_stream": (C.c_int, [_P]),
     "d2s_engine_tap": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "d2s_engine_profile": (C.c_int, [_P, C.c_int]),

@@ -9,6 +9,7 @@
 // in 0..255; frag_color.a follows d2s_dibr_params.alpha_mode (the reference draws these quads with blending off: WINDOW = rgb as written).
 // Line numbers in the comments below are viewer.py.
 #include "dibr_tex.h"
+#include "dibr_xr.h"
 #include <algorithm>
 #include <cmath>
 
@@ -87,13 +88,18 @@ __device__ __forceinline__ PixTaps pix_taps(const S& smp, const G& g, int x, int
 // G = DibrGeomCrop (the OpenXR screen shader, implementation.py:111-126): every texture coordinate -- the depth taps, the edge
 // fall-off, the shift, the in-painting, the border alpha -- follows the CROPPED uv (u, v); the rounded-corner SDF stays on the quad's
 // own uv (us, vs) and the feathering on the pixel index and u_viewport.
+// G = DibrGeomProj (d2s_dibr_xr_eyes): quv = the screen's own uv (u, 1 - v of the interpolated vertex uv) of this pixel; x, y are not used.
 template <bool DEFER = false, bool SHARED = false, bool FX = true, class S, class G>
-__device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int y, int eye, float outc[4], const PixTaps* sh = nullptr) {
+__device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int y, int eye, float outc[4], const PixTaps* sh = nullptr,
+                                           const float* quv = nullptr) {
     const float eye_offset = eye ? g.half_ipd : -g.half_ipd;                          // :2701, 2714
     const float sg = eye_offset > 0.f ? 1.f : (eye_offset < 0.f ? -1.f : 0.f);
     const float parx = g.c * sg, pary = g.s * sg;                                     // :540
     const float sweep_sign = eye_offset > 0.f ? -1.f : 1.f;                           // :541
-    const float u = tex_u(g, ((float)x + 0.5f) / (float)g.ow), v = tex_v(g, ((float)y + 0.5f) / (float)g.oh);
+    float us, vs;
+    if constexpr (G::proj) { us = quv[0]; vs = quv[1]; }
+    else { us = ((float)x + 0.5f) / (float)g.ow; vs = ((float)y + 0.5f) / (float)g.oh; }
+    const float u = tex_u(g, us), v = tex_v(g, vs);
     auto depth_at = [&](float su, float sv) { return smp.own_depth(su, sv); };       // (roll == 0: v - 0 * k == v, every tap below shares the row pair)
     // 3-tap depth smoothing along the parallax direction (:545-549)
     const float dsx = parx * g.psx * 1.5f, dsy = pary * g.psy * 1.5f;
@@ -152,8 +158,8 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int 
     // (G = DibrGeomCrop: the two blocks below depend on the column and the row alone, so the compiler forms them ahead of the eye loop
     //  and keeps their results across the whole pixel -- 12 of the 24 bytes of scratch the FullDep row kernels with FX would have.  fx / fy are x / y made available only once the colour exists (ordered_after: no arithmetic, the same bits).)
     int fx = x, fy = y;
-    if constexpr (FX && G::crop) { fx = ordered_after(x, col[0]); fy = ordered_after(y, col[1]); }
-    if (FX && g.feather) {                                                             // :587-616
+    if constexpr (FX && G::crop && !G::proj) { fx = ordered_after(x, col[0]); fy = ordered_after(y, col[1]); }
+    if (FX && !G::proj && g.feather) {                                                 // :587-616 (never with a projected screen: refused)
         // (gl_FragCoord.xy - u_viewport.xy) / u_viewport.zw; gl_FragCoord is y-up, pixel centres at +0.5
         float fu = (((float)fx + 0.5f) - g.vpx) / g.vpw, fv = (((float)g.oh - ((float)fy + 0.5f)) - g.vpy) / g.vph, fw = g.feather_w;
         float fo = smoothstepf(0.f, fw, fu) * smoothstepf(0.f, fw, 1.0f - fu) * smoothstepf(0.f, fw, fv) * smoothstepf(0.f, fw, 1.0f - fv);
@@ -165,7 +171,8 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int 
         // rounded-box SDF over the quad's own uv (the shader's inner `uv` of the feather block shadows only that block), :617-624
         // (with a crop the quad's own uv is formed here: the same expressions dibr_pixel starts with)
         float qu = u, qv = v;
-        if constexpr (G::crop) { qu = ((float)fx + 0.5f) / (float)g.ow; qv = ((float)fy + 0.5f) / (float)g.oh; }
+        if constexpr (G::proj) { qu = us; qv = vs; }
+        else if constexpr (G::crop) { qu = ((float)fx + 0.5f) / (float)g.ow; qv = ((float)fy + 0.5f) / (float)g.oh; }
         const float dx = fabsf(qu - 0.5f) - 0.5f + g.corner_r, dy = fabsf(qv - 0.5f) - 0.5f + g.corner_r;
         const float mx = fmaxf(dx, 0.f), my = fmaxf(dy, 0.f);
         const float sdf = sqrtf(mx * mx + my * my) + fminf(fmaxf(dx, dy), 0.f) - g.corner_r;
@@ -311,10 +318,65 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
     }
 }
 
+// d2s_dibr_xr_eyes: the OpenXR screen drawn into each eye's swapchain image (xr_viewer/effects.py:1023-1137).  One thread = one pixel
+// of one eye image; a wave = a 16 x 4 pixel tile (block = 16 x 16), so that along the screen's outline covered and uncovered pixels
+// share few waves and the taps of a wave stay within a few texture rows whatever the minification.  Every facet of the eye's table
+// (dibr_xr.h; block-uniform addresses) is tested: ~14 float operations each, at most 48.  Covered: the facet's homography gives the
+// interpolated vertex uv, and the pixel function runs on (u, 1 - v) as the shader's screen_flipped_uv; uncovered: the clear colour.
+struct XrEyeDev { int w, h, eye, nf; long out_off; };      // out_off: the eye image's first element in out; its table: eye index * 48
+struct XrEyes { XrEyeDev e[2]; int n; float clear[4]; };
+// (set-up: up to 24 facets of one eye's table travel in the arguments and are copied to the workspace, one float per thread)
+__global__ void __launch_bounds__(256) dibr_xr_table_kernel(XrFacetChunk c, float* __restrict__ dst, int n_floats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_floats) dst[i] = ((const float*)&c)[i];
+}
+template <int OUT_FMT, class D>
+__global__ void __launch_bounds__(256)
+dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+               const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex) {
+    const int ei = blockIdx.z % ex.n, b = blockIdx.z / ex.n;
+    const XrEyeDev e = ex.e[ei];
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= e.w || y >= e.h) return;
+    const XrFacet* __restrict__ tab = tab_all + ei * XR_MAX_FACETS;
+    const float xc = ((float)x + 0.5f) - 0.5f * (float)e.w, yc = ((float)y + 0.5f) - 0.5f * (float)e.h;      // exact: multiples of 0.5 below 2^13
+    int best = -1;
+    float bz = 1.0f, ba = 0.f, bb = 0.f, bw = 1.f;      // the depth buffer is cleared to 1: LESS fails at and beyond the far plane
+    for (int f = 0; f < e.nf; ++f) {
+        const XrFacet& F = tab[f];
+        const float na = F.ha[0] * xc + F.ha[1] * yc + F.ha[2], nb = F.hb[0] * xc + F.hb[1] * yc + F.hb[2];
+        const float nw = F.hw[0] * xc + F.hw[1] * yc + F.hw[2];
+        const float ne = F.he[0] * xc + F.he[1] * yc + F.he[2];      // the upper a-edge: the next facet's na, negated (dibr_xr.h)
+        if (na >= 0.f && ne >= 0.f && nb >= 0.f && nb <= nw && nw > 0.f) {
+            const float z = F.hz[0] * xc + F.hz[1] * yc + F.hz[2];
+            // (GL clips at the near plane, NDC z = -1)
+            if (z >= -1.0f && z < bz) { bz = z; best = f; ba = na; bb = nb; bw = nw; }      // GL_LESS: a tie keeps the lower facet index
+        }
+    }
+    const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    const long o = e.out_off + (((long)b * e.h + y) * e.w + x) * nch;
+    float c[4];
+    if (best < 0) {
+        c[0] = ex.clear[0] * 255.0f; c[1] = ex.clear[1] * 255.0f; c[2] = ex.clear[2] * 255.0f; c[3] = ex.clear[3];
+        dibr_store<OUT_FMT>(out_all, o, nch, c);
+        return;
+    }
+    const XrFacet& F = tab[best];
+    const float a = ba / bw, bq = bb / bw;
+    const float quv[2] = {F.u0 + a * F.ua + bq * F.ub, 1.0f - (F.v0 + a * F.va + bq * F.vb)};
+    GenSmp<D> smp;
+    smp.rgb = rgb_all + (long)b * g.H * g.W * 3; smp.dep = D::make(dep_all, b, g); smp.H = g.H; smp.W = g.W;
+    dibr_pixel(smp, g, 0, 0, e.eye, c, nullptr, quv);
+    dibr_store<OUT_FMT>(out_all, o, nch, c);
+}
+
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
 int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                        const double* crop, void* out, int out_fmt, void* stream, bool check_only);      // (d2s_view_pipeline_crop_streams)
+int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
+                const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                uint64_t workspace_bytes, void* stream, bool check_only);                              // (d2s_view_pipeline_xr_streams)
 
 }  // namespace d2s
 
@@ -454,4 +516,100 @@ extern "C" int d2s_dibr_crop_shape(int H, int W, const double crop[4], int displ
 extern "C" int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                                   const d2s_dibr_params* p, const double crop[4], void* out, int out_fmt, void* stream) {
     return dibr_warp_crop_any(rgb, depth, dh, dw, batch, H, W, p, crop, out, out_fmt, stream, false);
+}
+
+// The OpenXR eye views (xr_viewer/effects.py:1023-1137).  Every argument is checked, and both eyes' tables are formed, before any HIP call.
+static int xr_out_layout(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets, uint64_t* total) {
+    D2S_REQUIRE(eyes && n_eyes >= 1 && n_eyes <= 2, "bad eyes (n_eyes must be 1 or 2)");
+    D2S_REQUIRE(batch > 0 && batch <= 65535, "bad batch (1 .. 65535)");
+    D2S_REQUIRE(alpha_mode >= D2S_DIBR_ALPHA_WINDOW && alpha_mode <= D2S_DIBR_ALPHA_RGBA, "bad alpha_mode");
+    const uint64_t nch = alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    uint64_t at = 0;
+    for (int i = 0; i < n_eyes; ++i) {
+        D2S_REQUIRE(eyes[i].struct_size == sizeof(d2s_xr_eye), "d2s_xr_eye.struct_size must be sizeof(d2s_xr_eye) = 144");
+        D2S_REQUIRE(eyes[i].width >= 2 && eyes[i].height >= 2 && eyes[i].width <= 8192 && eyes[i].height <= 8192, "eye image must be 2 .. 8192 on a side");
+        if (offsets) offsets[i] = at;
+        at += (uint64_t)batch * eyes[i].height * eyes[i].width * nch;
+    }
+    if (total) *total = at;
+    return D2S_OK;
+}
+
+extern "C" int d2s_dibr_xr_shape(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets, uint64_t* total) {
+    D2S_REQUIRE(offsets && total, "null pointer (offsets, total)");
+    return xr_out_layout(eyes, n_eyes, batch, alpha_mode, offsets, total);
+}
+
+extern "C" int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes) {
+    D2S_REQUIRE(bytes, "null pointer (bytes)");
+    D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
+    *bytes = (uint64_t)n_eyes * XR_MAX_FACETS * sizeof(XrFacet);
+    return D2S_OK;
+}
+
+int d2s::dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                     const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                     void* workspace, uint64_t workspace_bytes, void* stream, bool check_only) {
+    D2S_REQUIRE(rgb && depth && p && out, "null pointer");
+    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
+    if (rc) return rc;
+    D2S_REQUIRE(!p->feather_enabled, "feather_enabled must be 0 (the OpenXR viewer never enables the feathering)");
+    if (crop) {                                            // what d2s_dibr_warp_crop refuses about a crop, its 2 x 2 pixel floor included
+        int a, b2, c2, d2;
+        rc = crop_eye_shape(H, W, crop, D2S_MODE_FULL_SBS, &a, &b2, &c2, &d2);
+        if (rc) return rc;
+    }
+    rc = xr_check(screen, eyes, n_eyes, batch, workspace, workspace_bytes);
+    if (rc) return rc;
+    uint64_t offs[2] = {0, 0}, total = 0;
+    rc = xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, offs, &total);
+    if (rc) return rc;
+    XrSurface S;
+    xr_surface(screen, S);
+    for (int i = 0; i < n_eyes; ++i)
+        if (!(xr_min_w(S, eyes[i].vp) > 1e-6)) {
+            set_error("unsupported: a vertex of the screen has clip w <= 1e-6 (the screen crosses the eye plane)");
+            return D2S_E_UNSUPPORTED;
+        }
+    DibrGeomProj g;
+    dibr_fill_geom(g, p, H, W, dh, dw);
+    g.c = cosf((float)screen->roll); g.s = sinf((float)screen->roll);                 // u_roll = screen_roll (effects.py:1113, 1129)
+    g.feather = 0;
+    g.mode = 0; g.oh = g.ow = g.out_h = g.out_w = 0;
+    g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
+    g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
+    XrEyes ex = {};
+    ex.n = n_eyes;
+    for (int k = 0; k < 4; ++k) ex.clear[k] = screen->clear[k];
+    int mw = 0, mh = 0;
+    XrFacet facets[2][XR_MAX_FACETS];
+    for (int i = 0; i < n_eyes; ++i) {
+        ex.e[i] = XrEyeDev{eyes[i].width, eyes[i].height, eyes[i].eye, S.n, (long)offs[i]};
+        mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
+        xr_facets(S, eyes[i].vp, eyes[i].width, eyes[i].height, facets[i]);
+    }
+    if (check_only) return D2S_OK;
+    XrFacet* tab = (XrFacet*)workspace;
+    for (int i = 0; i < n_eyes; ++i)
+        for (int f0 = 0; f0 < S.n; f0 += XR_CHUNK_FACETS) {                            // 1 launch per eye (flat), 2 (curved)
+            const int nf = std::min(XR_CHUNK_FACETS, S.n - f0), n_floats = nf * (int)(sizeof(XrFacet) / sizeof(float));
+            XrFacetChunk chunk;
+            for (int f = 0; f < nf; ++f) chunk.f[f] = facets[i][f0 + f];
+            hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, (hipStream_t)stream, chunk,
+                               (float*)(tab + i * XR_MAX_FACETS + f0), n_floats);
+        }
+    const bool up = dh != H || dw != W;
+    dim3 grid(cdiv(mw, 16), cdiv(mh, 16), n_eyes * batch), block(256);
+#define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex)
+    if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
+    else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
+#undef DIBR_XR
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+extern "C" int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                int out_fmt, void* workspace, uint64_t workspace_bytes, void* stream) {
+    return dibr_xr_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, stream, false);
 }

@@ -24,6 +24,7 @@ struct DibrGeom {
     int dh, dw;            // UpDep only: the [dh, dw] map the H x W depth texture is up-sampled from, and its scales
     float dsy, dsx;        //   linear_scale(dh, H, false), linear_scale(dw, W, false) as d2s_upsample_depth forms them
     static constexpr bool crop = false;
+    static constexpr bool proj = false;
 };
 // d2s_dibr_warp_crop: the OpenXR screen shader's u_source_crop (xr_viewer/implementation.py:111-126) as (float) of the caller's
 // doubles, the way GL receives a uniform.  A geometry TYPE of its own: the kernels are templates over it, so the instantiations
@@ -31,6 +32,12 @@ struct DibrGeom {
 struct DibrGeomCrop : DibrGeom {
     float cx, cy, cw, ch;  // xy = source top-left, zw = source size, in uv of the full texture
     static constexpr bool crop = true;
+};
+// d2s_dibr_xr_eyes: the screen's own uv of a pixel comes from a projected facet (the kernel hands it to dibr_pixel) instead of the
+// pixel index; everything after it is the cropped shader (crop NULL = (0, 0, 1, 1): x * 1 + 0 is x).  oh, ow, mode, out_h, out_w and
+// the viewport are not used: the eye images have their own table (XrEyes, dibr.hip).
+struct DibrGeomProj : DibrGeomCrop {
+    static constexpr bool proj = true;
 };
 // flipped_uv = u_source_crop.xy + screen_flipped_uv * u_source_crop.zw (implementation.py:123): quad uv -> texture uv
 template <class G> __device__ __forceinline__ float tex_u(const G& g, float us) { if constexpr (G::crop) return g.cx + us * g.cw; else return us; }

@@ -1,0 +1,145 @@
+// d2s_dibr_xr_eyes, host side: the OpenXR screen as planar facets and, per eye, the facet table the render kernel searches
+// (DESIGN.md 3.4).  Everything here is double precision; the table is rounded to float once, at the end.  References:
+// _build_model_mat4 (xr_viewer/screen.py:29-70), _build_curved_screen_verts (screen.py:110-173), _screen_effect_basis
+// (xr_viewer/effects.py:65-82), _CURVED_HALF_ANGLE_RAD (xr_viewer/constants.py:50-51), _render_eye (effects.py:1023-1137).
+#pragma once
+#include "common.h"
+#include <cmath>
+
+namespace d2s {
+
+constexpr int XR_MAX_FACETS = 48;                 // the strip's N (effects.py:1116: n_verts = (48 + 1) * 2)
+constexpr double XR_HALF_ANGLE = 0.6 * 0.8;       // _CURVED_HALF_ANGLE_RAD = 0.6 * _CURVED_CURVATURE_SCALE
+
+// One planar facet of one eye, over the pixel centre RELATIVE TO THE IMAGE CENTRE (xc, yc) = (x + 0.5 - w / 2, y + 0.5 - h / 2), y down:
+//   (na, nb, nw) = (ha, hb, hw) . (xc, yc, 1);  nw = 1 / clip w > 0;  the facet's own coordinates a = na / nw, b = nb / nw in 0..1;
+//   covered <=> 0 <= na <= nw and 0 <= nb <= nw;  depth (NDC z, what GL_LESS compares) = hz . (xc, yc, 1);
+//   uv (GL's, v up) = (u0 + a * ua + b * ub, v0 + a * va + b * vb): the vertex uvs are affine over a facet.
+//   he = the upper a-edge, hw - ha, as a row of its own: covered <=> na >= 0, he . (xc, yc, 1) >= 0, 0 <= nb <= nw.  Along the strip facet
+//   f's he is the exact NEGATION of facet f + 1's float32 ha row -- one edge function per interior seam, evaluated by both sides with the
+//   same operations (no contraction in this file's kernels), so -x >= 0 or x >= 0 always holds: the strip is watertight, as GL's is.
+struct XrFacet { float ha[3], hb[3], hw[3], hz[3], he[3]; float u0, ua, ub, v0, va, vb, pad[3]; };
+static_assert(sizeof(XrFacet) == 96, "XrFacet is 24 floats");
+constexpr int XR_CHUNK_FACETS = 24;
+struct XrFacetChunk { XrFacet f[XR_CHUNK_FACETS]; };    // 2 304 bytes: a set-up launch carries half an eye's table in its arguments
+
+struct XrVert { double p[3], u, v; };
+// The surface as facets: corner (a, b) = (0, 0), (1, 0), (0, 1); the fourth corner is p10 + p01 - p00 (flat: the model matrix is
+// affine; curved: two generator lines of a cylinder).  all[]: every vertex GL would transform (the clip-w refusal looks at each).
+struct XrSurface { int n; XrVert p00[XR_MAX_FACETS], p10[XR_MAX_FACETS], p01[XR_MAX_FACETS]; int n_all; XrVert all[2 * (XR_MAX_FACETS + 1)]; };
+
+inline void xr_basis(const d2s_xr_screen* s, double R[3][3], double centre[3]) {
+    const double cy = cos(s->yaw), sy = sin(s->yaw), cp = cos(s->pitch), sp = sin(s->pitch), cr = cos(s->roll), sr = sin(s->roll);
+    const double r[3][3] = {{cy * cr + sy * sp * sr, -cy * sr + sy * sp * cr, sy * cp},
+                            {cp * sr, cp * cr, -sp},
+                            {-sy * cr + cy * sp * sr, sy * sr + cy * sp * cr, cy * cp}};
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[i][j] = r[i][j];
+    centre[0] = s->pan_x; centre[1] = s->pan_y; centre[2] = -s->distance;
+}
+
+inline void xr_surface(const d2s_xr_screen* s, XrSurface& S) {
+    double R[3][3], c[3];
+    xr_basis(s, R, c);
+    auto world = [&](double lx, double ly, double lz, double u, double v) {
+        XrVert w;
+        for (int i = 0; i < 3; ++i) w.p[i] = c[i] + R[i][0] * lx + R[i][1] * ly + R[i][2] * lz + R[i][2] * s->normal_offset;
+        w.u = u; w.v = v;
+        return w;
+    };
+    const double hw = s->width / 2.0, hh = s->height / 2.0;
+    if (s->curve == D2S_XR_CURVE_FLAT) {                   // T @ R @ S applied to (+-1, +-1, 0, 1), uv as quad_vao has them
+        S.n = 1; S.n_all = 4;
+        S.all[0] = world(-hw, -hh, 0, 0, 0); S.all[1] = world(hw, -hh, 0, 1, 0); S.all[2] = world(-hw, hh, 0, 0, 1); S.all[3] = world(hw, hh, 0, 1, 1);
+        S.p00[0] = S.all[0]; S.p10[0] = S.all[1]; S.p01[0] = S.all[2];
+        return;
+    }
+    const int N = XR_MAX_FACETS;
+    const bool vert = s->curve == D2S_XR_CURVE_VERTICAL;
+    const double radius = (vert ? hh : hw) / XR_HALF_ANGLE, step = 2.0 * XR_HALF_ANGLE / N;
+    S.n = N; S.n_all = 2 * (N + 1);
+    for (int i = 0; i <= N; ++i) {                         // column pair i of the strip; the vertex uv is the float32 the strip stores
+        const double ang = i == N ? XR_HALF_ANGLE : -XR_HALF_ANGLE + i * step, t = (double)(float)((double)i / N);
+        const double along = radius * sin(ang), lz = radius * (1.0 - cos(ang));
+        S.all[2 * i] = vert ? world(-hw, along, lz, 0, t) : world(along, -hh, lz, t, 0);
+        S.all[2 * i + 1] = vert ? world(hw, along, lz, 1, t) : world(along, hh, lz, t, 1);
+    }
+    for (int i = 0; i < N; ++i) {
+        S.p00[i] = S.all[2 * i];
+        S.p10[i] = S.all[2 * i + 2];                       // a runs ALONG the strip for both curves (xr_facets: the shared seams),
+        S.p01[i] = S.all[2 * i + 1];                       // b across it; the uv affine says which of u, v each one moves
+    }
+}
+
+inline void xr_clip(const double vp[16], const double p[3], double w1, double out[4]) {
+    for (int r = 0; r < 4; ++r) out[r] = vp[4 * r] * p[0] + vp[4 * r + 1] * p[1] + vp[4 * r + 2] * p[2] + vp[4 * r + 3] * w1;
+}
+// smallest clip w over the surface's vertices
+inline double xr_min_w(const XrSurface& S, const double vp[16]) {
+    double m = INFINITY;
+    for (int i = 0; i < S.n_all; ++i) { double c[4]; xr_clip(vp, S.all[i].p, 1.0, c); m = c[3] < m ? c[3] : m; }
+    return m;
+}
+// One eye's table.  clip(a, b) = C0 + a * CA + b * CB; with D = diag(w / 2, -h / 2, 1): (xc, yc, 1) * clip.w = D * M * (a, b, 1),
+// M = [CA.xyw | CB.xyw | C0.xyw], so (a, b, 1) / clip.w = inverse(D * M) * (xc, yc, 1).  A facet seen edge-on (no inverse) covers no
+// pixel centre: its ha row becomes the constant -1.
+inline void xr_facets(const XrSurface& S, const double vp[16], int w, int h, XrFacet* out) {
+    for (int f = 0; f < S.n; ++f) {
+        double dA[3], dB[3], C0[4], CA[4], CB[4];
+        for (int i = 0; i < 3; ++i) { dA[i] = S.p10[f].p[i] - S.p00[f].p[i]; dB[i] = S.p01[f].p[i] - S.p00[f].p[i]; }
+        xr_clip(vp, S.p00[f].p, 1.0, C0); xr_clip(vp, dA, 0.0, CA); xr_clip(vp, dB, 0.0, CB);
+        const double sx = w / 2.0, sy = -h / 2.0;
+        const double m[3][3] = {{sx * CA[0], sx * CB[0], sx * C0[0]}, {sy * CA[1], sy * CB[1], sy * C0[1]}, {CA[3], CB[3], C0[3]}};
+        double adj[3][3];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+            const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+            adj[i][j] = m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0];
+        }
+        const double det = m[0][0] * adj[0][0] + m[0][1] * adj[1][0] + m[0][2] * adj[2][0];
+        double scale = 0.0;
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) scale = fmax(scale, fabs(m[i][j]));
+        XrFacet& F = out[f];
+        F = XrFacet{};
+        if (!(fabs(det) > 1e-14 * scale * scale * scale)) { F.ha[2] = -1.f; continue; }
+        double inv[3][3];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) inv[i][j] = adj[i][j] / det;
+        for (int j = 0; j < 3; ++j) {
+            F.ha[j] = (float)inv[0][j]; F.hb[j] = (float)inv[1][j]; F.hw[j] = (float)inv[2][j];
+            F.hz[j] = (float)(CA[2] * inv[0][j] + CB[2] * inv[1][j] + C0[2] * inv[2][j]);
+            F.he[j] = (float)(inv[2][j] - inv[0][j]);
+        }
+        F.u0 = (float)S.p00[f].u; F.ua = (float)(S.p10[f].u - S.p00[f].u); F.ub = (float)(S.p01[f].u - S.p00[f].u);
+        F.v0 = (float)S.p00[f].v; F.va = (float)(S.p10[f].v - S.p00[f].v); F.vb = (float)(S.p01[f].v - S.p00[f].v);
+    }
+    // interior seams: facet f ends where facet f + 1 begins (a runs along the strip) -- one edge function for both
+    auto live = [&](int f) { return !(out[f].ha[0] == 0.f && out[f].ha[1] == 0.f && out[f].ha[2] == -1.f); };
+    for (int f = 0; f + 1 < S.n; ++f)
+        if (live(f) && live(f + 1))
+            for (int j = 0; j < 3; ++j) out[f].he[j] = -out[f + 1].ha[j];
+}
+
+inline bool xr_finite(const double* v, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false; return true; }
+
+// What d2s_dibr_xr_eyes refuses about the screen, the eyes and the workspace, in the header's order; no HIP call.
+inline int xr_check(const d2s_xr_screen* s, const d2s_xr_eye* eyes, int n_eyes, int batch, const void* ws, uint64_t ws_bytes) {
+    D2S_REQUIRE(s && eyes, "null pointer (screen, eyes)");
+    D2S_REQUIRE(s->struct_size == sizeof(d2s_xr_screen), "d2s_xr_screen.struct_size must be sizeof(d2s_xr_screen) = 96");
+    D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
+    D2S_REQUIRE(s->curve >= D2S_XR_CURVE_FLAT && s->curve <= D2S_XR_CURVE_VERTICAL, "bad curve (0 flat, 1 horizontal, 2 vertical)");
+    const double geo[9] = {s->width, s->height, s->distance, s->pan_x, s->pan_y, s->yaw, s->pitch, s->roll, s->normal_offset};
+    D2S_REQUIRE(xr_finite(geo, 9) && std::isfinite(s->clear[0]) && std::isfinite(s->clear[1]) && std::isfinite(s->clear[2]) &&
+                std::isfinite(s->clear[3]), "the screen must be finite");
+    D2S_REQUIRE(s->width > 0.0 && s->height > 0.0 && s->distance > 0.0, "screen width, height and distance must be > 0");
+    for (int i = 0; i < n_eyes; ++i) {
+        D2S_REQUIRE(eyes[i].struct_size == sizeof(d2s_xr_eye), "d2s_xr_eye.struct_size must be sizeof(d2s_xr_eye) = 144");
+        D2S_REQUIRE(xr_finite(eyes[i].vp, 16), "eye vp must be finite");
+        D2S_REQUIRE(eyes[i].width >= 2 && eyes[i].height >= 2 && eyes[i].width <= 8192 && eyes[i].height <= 8192, "eye image must be 2 .. 8192 on a side");
+        D2S_REQUIRE(eyes[i].eye == 0 || eyes[i].eye == 1, "eye must be 0 (left) or 1 (right)");
+    }
+    D2S_REQUIRE((long)n_eyes * batch <= 65535, "n_eyes * batch too large for one launch");
+    D2S_REQUIRE(ws, "null pointer (workspace)");
+    D2S_REQUIRE(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
+    D2S_REQUIRE(ws_bytes >= (uint64_t)n_eyes * XR_MAX_FACETS * sizeof(XrFacet), "workspace_bytes below d2s_dibr_xr_workspace");
+    return D2S_OK;
+}
+
+}  // namespace d2s

@@ -1069,6 +1069,9 @@ int dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
                        int composite, void* out, int out_fmt, void* stream, bool check_only);
 int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                        const double* crop, void* out, int out_fmt, void* stream, bool check_only);
+int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
+                const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                uint64_t workspace_bytes, void* stream, bool check_only);
 }
 
 namespace {
@@ -1192,6 +1195,32 @@ extern "C" int d2s_view_pipeline_crop_streams(d2s_engine* e, const uint8_t* fram
                                               float* depth_full, void* stream) {
     D2S_REQUIRE(crop, "null pointer (crop)");
     return view_pipeline_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, view, crop, use_ema, out, out_fmt, depth_full, stream);
+}
+
+// d2s_view_pipeline_crop_streams with the OpenXR eye views (d2s_dibr_xr_eyes) as the last stage: the same checks and depth path
+extern "C" int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                            int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                            const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                            const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                            void* workspace, uint64_t workspace_bytes, void* stream) {
+    D2S_REQUIRE(frames && pp && dp && out && screen && eyes, "null pointer");
+    D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
+    uint64_t offs[2], total = 0;
+    RC(d2s_dibr_xr_shape(eyes, n_eyes, batch > 0 ? batch : 1, dp->alpha_mode, offs, &total));
+    D2S_REQUIRE(e, "null engine");
+    int stride = 1;
+    RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
+    auto warp = [&](bool check_only) {
+        return dibr_xr_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                           workspace_bytes, stream, check_only);
+    };
+    RC(warp(true));
+    D2S_ON_DEVICE(e->device);
+    hipStream_t st = (hipStream_t)stream;
+    RC(pipeline_depth(e, frames, batch, H, W, stride, pre, pp, use_ema, depth_full, stream));
+    const double obytes = (double)total / batch * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
+    PROF(PC_WARP, 0, batch * ((double)H * W * 3 + (double)e->h * e->w * 4 + obytes), warp(false));
+    return D2S_OK;
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

@@ -317,6 +317,33 @@ def movie_crop(stream: int = 0):
     return slots[int(stream)]
 
 
+def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False,
+                 streams=None, alpha="rgba"):
+    """The OpenXR viewer's frame in one stream-ordered native call: uint8 [B,H,W,3] frames (numpy or device tensor) -> predict_depth ->
+    the screen `screen` (xr.XrScreen) drawn into each eye image of `eyes` (xr.xr_eye, 1 or 2) with that eye's view-projection matrix,
+    as the reference's _render_eye draws it (xr_viewer/effects.py:1023-1137).  Returns one device tensor per eye, [B,h,w,4|3].
+    crop: None, (x, y, w, h) in uv, or "auto" (the MovieCrop of the first row's stream slot: the screen shows one crop).  The uniforms
+    are the configured parameters', with the OpenXR screen's corner_radius (0.03) and frag_color.a kept (alpha="rgba") for the
+    compositor.  Glow, frost, border, controllers and environment stay with the caller."""
+    p = _state["params"]
+    t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+    t = t.to(device=_device())
+    B, H, W, _ = t.shape
+    h, w, _s = engine_shape(H, W, p.depth_resolution, _state["cfg"].patch, p.square_input)
+    if B > _state["max_batch"]:
+        raise _lib.D2SError(f"batch {B} > configured max_batch {_state['max_batch']}")
+    eng = _ensure_engine_built(h, w, _fp8_first_inputs(t, (h, w)))
+    if isinstance(crop, str):
+        if crop != "auto":
+            raise ValueError('crop must be None, (x, y, w, h) or "auto"')
+        mc = movie_crop(0 if streams is None else int(streams[0]))
+        mc.update(t[0])
+        crop = tuple(mc.crop_uv)
+    dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
+    return eng.view_pipeline_xr(t, p, dp, screen, eyes, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
+                                streams=streams)
+
+
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,
              viewport=None, crop=None):
     """Batched predict_depth + make_sbs: uint8 [B,H,W,3] (numpy or device tensor) -> device tensor

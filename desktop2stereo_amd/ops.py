@@ -389,6 +389,82 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
     return out if batched else out[0]
 
 
+_XR_WS: Dict[Tuple, torch.Tensor] = {}
+
+
+def _xr_args(screen, eyes):
+    """(d2s_xr_screen, d2s_xr_eye array) of an xr.XrScreen (or the struct itself) and 1 or 2 eye images (xr.xr_eye)."""
+    from . import xr as _xr
+    sc = screen if isinstance(screen, _lib.XrScreen) else screen.c_struct()
+    ea = eyes if isinstance(eyes, C.Array) and getattr(eyes, "_type_", None) is _lib.XrEye else _xr.eye_array(eyes)
+    return sc, ea
+
+
+def dibr_xr_shape(eyes, batch: int, alpha_mode: int = 0) -> Tuple[list, int]:
+    """(offsets, total) in elements of the eye images of dibr_xr_eyes laid one after another: eye i is [batch, height_i, width_i, nch] at
+    offsets[i] (d2s_dibr_xr_shape)."""
+    from . import xr as _xr
+    ea = eyes if isinstance(eyes, C.Array) else _xr.eye_array(eyes)
+    offs, total = (C.c_uint64 * len(ea))(), C.c_uint64()
+    check(_lib.load().d2s_dibr_xr_shape(ea, len(ea), int(batch), int(alpha_mode), offs, C.byref(total)), "d2s_dibr_xr_shape")
+    return list(offs), total.value
+
+
+def _xr_workspace(n_eyes: int, device) -> torch.Tensor:
+    """The facet table's home for calls on the current stream of `device`: one per (device, stream), since calls on one stream are
+    ordered and calls on different streams must not share it."""
+    nbytes = C.c_uint64()
+    check(_lib.load().d2s_dibr_xr_workspace(n_eyes, C.byref(nbytes)), "d2s_dibr_xr_workspace")
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _XR_WS.get(key)
+    if ws is None or ws.numel() < nbytes.value:
+        if len(_XR_WS) >= 16:      # (streams come and go; a table is a few KB, but the cache is bounded as _CROP_WS is)
+            _XR_WS.clear()
+        ws = _XR_WS[key] = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _xr_views(out: torch.Tensor, ea, B: int, nch: int, offs) -> list:
+    return [out[o:o + B * e.height * e.width * nch].view(B, e.height, e.width, nch) for e, o in zip(ea, offs)]
+
+
+def dibr_xr_eyes(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, crop=None, out_u8: bool = True,
+                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> list:
+    """The OpenXR viewer's eye views (reference xr_viewer/effects.py:1023-1137): the screen `screen` (xr.XrScreen) drawn into each
+    eye image of `eyes` (1 or 2 xr.xr_eye) with that eye's own view-projection matrix -- the XR shader at the projected uv, the
+    clear colour elsewhere.  frames uint8 [B,H,W,3] or [H,W,3]; depth [B,dh,dw] or [dh,dw] at any resolution; crop = u_source_crop or
+    None; dp as dibr_warp(crop=) reads it except display_mode, viewport and roll (screen.roll is u_roll); feathering is refused.
+    Returns one tensor per eye, [B,h,w,3|4] uint8 / float32 0..255 (views of one flat buffer: `out`, a caller-kept 1-D tensor of
+    dibr_xr_shape's total, or a new one).  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_workspace bytes."""
+    _need_cuda(frames, "frames")
+    _need_cuda(depth, "depth")
+    if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+        raise ValueError("dibr_xr_eyes: frames must be uint8 [B,H,W,3] or [H,W,3]")
+    f = frames.contiguous() if frames.dim() == 4 else frames.contiguous().unsqueeze(0)
+    d = depth.to(torch.float32).contiguous()
+    d = d if d.dim() == 3 else d.unsqueeze(0)
+    B, H, W, _ = f.shape
+    if d.dim() != 3 or d.shape[0] != B:
+        raise ValueError(f"dibr_xr_eyes: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
+    _same_device(f, d, "dibr_xr_eyes")
+    sc, ea = _xr_args(screen, eyes)
+    offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
+    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+    dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
+    if out is None:
+        out = torch.empty(total, dtype=dtype, device=f.device)
+    elif not out.is_cuda or out.device != f.device or out.dtype != dtype or out.numel() != total or not out.is_contiguous():
+        raise ValueError(f"dibr_xr_eyes: out must be a contiguous {dtype} tensor of {total} elements on {f.device}")
+    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device)
+    _need_cuda(ws, "workspace")
+    _same_device(f, ws, "dibr_xr_eyes workspace")
+    c4 = _crop4(crop) if crop is not None else None
+    with _on(f.device) as st:
+        check(_lib.load().d2s_dibr_xr_eyes(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
+                                           _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(), st), "d2s_dibr_xr_eyes")
+    return _xr_views(out.view(-1), ea, B, nch, offs)
+
+
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
                    out_u8: bool = True, size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """The viewer's composite display modes (reference viewer.py:633-1197): "Anaglyph" | "Interleaved" | "Interleaved-V" |
@@ -646,6 +722,32 @@ class Engine:
         mid = (C.byref(dp), -1, _crop4(crop), int(use_ema))
         return self._run_pipeline(self.lib.d2s_view_pipeline_crop_streams, "d2s_view_pipeline_crop_streams", frames, p, spec, mid,
                                   want_depth, out, streams, who="view_pipeline_crop")
+
+    def view_pipeline_xr(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, crop=None,
+                         use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,
+                         streams=None):
+        """view_pipeline with the OpenXR eye views as its last stage (d2s_view_pipeline_xr_streams): screen, eyes, crop as
+        ops.dibr_xr_eyes.  Returns one tensor per eye (with want_depth: (list, depth)); bit-identical to pipeline(want_depth=True)'s
+        engine depth followed by dibr_xr_eyes.  out: a caller-kept 1-D tensor of dibr_xr_shape's total.  (A method of its own, as
+        view_pipeline_crop is: view_pipeline's parameter list is pinned by the ABI tests.)"""
+        sc, ea = _xr_args(screen, eyes)
+        nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+        lay = {}
+
+        def spec(B, H, W):
+            lay["offs"], lay["total"] = dibr_xr_shape(ea, B, dp.alpha_mode)
+            lay["B"] = B
+            return (lay["total"],), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
+        ws = _xr_workspace(len(ea), self.device)
+        nbytes = ws.numel()
+
+        def fn(*a):      # (_run_pipeline ends every call with out, out_fmt, depth_full, stream: the workspace goes in front of the stream)
+            return self.lib.d2s_view_pipeline_xr_streams(*a[:-1], _ptr(ws), nbytes, a[-1])
+        mid = (C.byref(dp), _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea), int(use_ema))
+        r = self._run_pipeline(fn, "d2s_view_pipeline_xr_streams", frames, p, spec, mid, want_depth, out, streams, who="view_pipeline_xr")
+        flat = (r[0] if want_depth else r).view(-1)
+        views = _xr_views(flat, ea, lay["B"], nch, lay["offs"])
+        return (views, r[1]) if want_depth else views
 
     def close(self):
         if getattr(self, "_h", None):

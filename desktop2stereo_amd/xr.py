@@ -1,0 +1,132 @@
+"""The OpenXR viewer's screen and eye images for ops.dibr_xr_eyes / Engine.view_pipeline_xr (include/d2s.h d2s_xr_screen, d2s_xr_eye).
+
+XrScreen is the screen in world space; its host helpers restate the reference's geometry for callers and for the tests --
+model_mat4 = _build_model_mat4 (xr_viewer/screen.py:29-70), curved_verts = _build_curved_screen_verts (screen.py:110-173),
+basis = _screen_effect_basis (xr_viewer/effects.py:65-82), fov_to_proj_mat4 / pose_to_view_mat4 = _fov_to_proj_mat4 /
+_pose_to_view_mat4 (xr_viewer/render.py:981-1041) -- in float64 (the reference rounds each to float32).  The library does not call
+them: it forms the surface itself, in double precision, from the struct.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+
+CURVED_HALF_ANGLE_RAD = 0.6 * 0.8          # xr_viewer/constants.py:50-51
+CURVED_SEGMENTS = 48                       # effects.py:1116
+
+
+@dataclass
+class XrScreen:
+    """The reference's screen_* state.  curve: "flat" | "horizontal" | "vertical"; sizes in metres, angles in radians; roll is also
+    the shader's u_roll; clear: the background (r, g, b in 0..1, a)."""
+    width: float = 2.4
+    height: float = 1.35
+    distance: float = 2.0
+    pan_x: float = 0.0
+    pan_y: float = 0.0
+    yaw: float = 0.0
+    pitch: float = 0.0
+    roll: float = 0.0
+    curve: str = "flat"
+    normal_offset: float = 0.0
+    clear: Tuple[float, float, float, float] = (0.0, 0.0, 0.0, 1.0)
+
+    def c_struct(self) -> "_lib.XrScreen":
+        if self.curve not in _lib.XR_CURVE:
+            raise ValueError(f"curve must be one of {list(_lib.XR_CURVE)}")
+        if len(self.clear) != 4:
+            raise ValueError("clear must be (r, g, b, a)")
+        return _lib.XrScreen(C.sizeof(_lib.XrScreen), _lib.XR_CURVE[self.curve], float(self.width), float(self.height),
+                             float(self.distance), float(self.pan_x), float(self.pan_y), float(self.yaw), float(self.pitch),
+                             float(self.roll), float(self.normal_offset), (C.c_float * 4)(*[float(v) for v in self.clear]))
+
+    def basis(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(R [4,4], centre [3]): the screen's rotation (yaw, pitch, roll) and its centre (pan_x, pan_y, -distance)."""
+        cy, sy = math.cos(self.yaw), math.sin(self.yaw)
+        cp, sp = math.cos(self.pitch), math.sin(self.pitch)
+        cr, sr = math.cos(self.roll), math.sin(self.roll)
+        R = np.array([[cy * cr + sy * sp * sr, -cy * sr + sy * sp * cr, sy * cp, 0.0],
+                      [cp * sr, cp * cr, -sp, 0.0],
+                      [-sy * cr + cy * sp * sr, sy * sr + cy * sp * cr, cy * cp, 0.0],
+                      [0.0, 0.0, 0.0, 1.0]])
+        return R, np.array([self.pan_x, self.pan_y, -self.distance], np.float64)
+
+    def model_mat4(self) -> np.ndarray:
+        """T @ R @ S: the flat quad's corners are model @ (+-1, +-1, 0, 1)."""
+        R, centre = self.basis()
+        S = np.diag([self.width / 2.0, self.height / 2.0, 1.0, 1.0])
+        T = np.eye(4)
+        T[:3, 3] = centre + R[:3, 2] * self.normal_offset
+        return T @ R @ S
+
+    def curved_verts(self) -> np.ndarray:
+        """[(48 + 1) * 2, 5] = x y z u v of the curved TRIANGLE_STRIP in world space (curve "flat" builds the horizontal arc, as the
+        reference does)."""
+        R, centre = self.basis()
+        rot, n = R[:3, :3], CURVED_SEGMENTS + 1
+        half_w, half_h = self.width / 2.0, self.height / 2.0
+        angles = np.linspace(-CURVED_HALF_ANGLE_RAD, CURVED_HALF_ANGLE_RAD, n)
+        ts = np.linspace(0.0, 1.0, n)
+        vert = self.curve == "vertical"
+        radius = (half_h if vert else half_w) / CURVED_HALF_ANGLE_RAD
+        out = np.empty((n * 2, 5), np.float64)
+        for i, (ang, t) in enumerate(zip(angles, ts)):
+            along, lz = radius * math.sin(ang), radius * (1.0 - math.cos(ang))
+            for j in range(2):
+                local = np.array([(-half_w, half_w)[j], along, lz]) if vert else np.array([along, (-half_h, half_h)[j], lz])
+                out[i * 2 + j, :3] = centre + rot @ local + rot[:, 2] * self.normal_offset
+                out[i * 2 + j, 3:] = (float(j), t) if vert else (t, float(j))
+        return out
+
+
+def fov_to_proj_mat4(angle_left: float, angle_right: float, angle_up: float, angle_down: float, near: float = 0.05,
+                     far: float = 100.0) -> np.ndarray:
+    """XrFovf -> the OpenGL asymmetric-frustum projection (numpy's row / column convention)."""
+    l, r = math.tan(angle_left) * near, math.tan(angle_right) * near
+    t, b = math.tan(angle_up) * near, math.tan(angle_down) * near
+    if abs(r - l) < 1e-6:
+        r += 1e-6
+    if abs(t - b) < 1e-6:
+        t += 1e-6
+    p = np.zeros((4, 4))
+    p[0, 0], p[0, 2] = 2 * near / (r - l), (r + l) / (r - l)
+    p[1, 1], p[1, 2] = 2 * near / (t - b), (t + b) / (t - b)
+    p[2, 2], p[2, 3] = -(far + near) / (far - near), -2 * far * near / (far - near)
+    p[3, 2] = -1.0
+    return p
+
+
+def pose_to_view_mat4(orientation: Sequence[float], position: Sequence[float]) -> np.ndarray:
+    """XrPosef (orientation = quaternion x, y, z, w; position) -> the view matrix (the pose's inverse)."""
+    x, y, z, w = (float(v) for v in orientation)
+    tx, ty, tz = (float(v) for v in position)
+    r00, r01, r02 = 1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)
+    r10, r11, r12 = 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)
+    r20, r21, r22 = 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)
+    return np.array([[r00, r10, r20, -(r00 * tx + r10 * ty + r20 * tz)],
+                     [r01, r11, r21, -(r01 * tx + r11 * ty + r21 * tz)],
+                     [r02, r12, r22, -(r02 * tx + r12 * ty + r22 * tz)],
+                     [0.0, 0.0, 0.0, 1.0]])
+
+
+def xr_eye(vp, width: int, height: int, eye: int, flip_y: bool = False) -> "_lib.XrEye":
+    """One swapchain image: vp = proj @ view [4,4], its size, eye 0 (left) | 1 (right).  flip_y: negate proj's row 1 -- which is row 1
+    of proj @ view -- as the reference's _render_eye(flip_y=True) does (the library leaves it to the caller)."""
+    m = np.array(vp, np.float64).reshape(4, 4)
+    if flip_y:
+        m[1, :] = -m[1, :]
+    return _lib.XrEye((C.c_double * 16)(*m.ravel()), int(width), int(height), int(eye), C.sizeof(_lib.XrEye))
+
+
+def eye_array(eyes) -> "C.Array":
+    """A sequence of 1 or 2 xr_eye structs (or (vp, width, height, eye) tuples) as the C array the library takes."""
+    es = [e if isinstance(e, _lib.XrEye) else xr_eye(*e) for e in eyes]
+    if len(es) not in (1, 2):
+        raise ValueError("eyes must name 1 or 2 eye images")
+    return (_lib.XrEye * len(es))(*es)

@@ -159,6 +159,32 @@ typedef struct d2s_dibr_params {
 } d2s_dibr_params;
 enum { D2S_DIBR_ALPHA_WINDOW = 0, D2S_DIBR_ALPHA_PREMULTIPLIED = 1, D2S_DIBR_ALPHA_RGBA = 2 };
 
+/* The OpenXR viewer's screen in world space (d2s_version() >= 115), for d2s_dibr_xr_eyes: the surface EffectsMixin._render_eye draws
+ * (xr_viewer/effects.py:1023-1137).  curve 0: the flat quad model * (+-1, +-1, 0, 1) of _build_model_mat4 (xr_viewer/screen.py:29-70);
+ * curve 1 / 2: the 48-segment strip of _build_curved_screen_verts (screen.py:110-173) curved horizontally / vertically, half angle
+ * _CURVED_HALF_ANGLE_RAD = 0.48 (xr_viewer/constants.py), radius = (width | height) / 2 / 0.48, basis and centre as _screen_effect_basis.
+ * The library forms the surface in double precision (the reference rounds its matrices and vertices to float32). */
+typedef struct d2s_xr_screen {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_screen) = 96 */
+    int32_t  curve;            /* D2S_XR_CURVE_*: 0 flat, 1 horizontal, 2 vertical */
+    double   width, height;    /* screen_width, screen_height in metres (> 0) */
+    double   distance;         /* screen_distance (> 0): the centre sits at (pan_x, pan_y, -distance) */
+    double   pan_x, pan_y;
+    double   yaw, pitch, roll; /* radians.  roll is ALSO the shader's u_roll (effects.py:1113, 1129): d2s_dibr_params.roll is not read */
+    double   normal_offset;    /* shifts the surface along its forward axis (the reference's depth bias against a room model) */
+    float    clear[4];         /* the background the image is cleared to: rgb in 0..1 (_BG_COLORS) and a (the reference clears to 1) */
+} d2s_xr_screen;
+enum { D2S_XR_CURVE_FLAT = 0, D2S_XR_CURVE_HORIZONTAL = 1, D2S_XR_CURVE_VERTICAL = 2 };
+/* One swapchain image.  vp = proj @ view (_fov_to_proj_mat4 @ _pose_to_view_mat4, xr_viewer/render.py:981-1041), row-major as numpy
+ * holds it: clip = vp * (world, 1).  The reference's flip_y (effects.py:1032-1034) negates row 1 of proj before the product: the
+ * CALLER applies it to vp; row 0 of the image is the top row of the GL framebuffer either way. */
+typedef struct d2s_xr_eye {
+    double   vp[16];
+    int32_t  width, height;    /* 2 .. 8192 each */
+    int32_t  eye;              /* 0: u_eye_offset = -ipd_uv / 2 (left), 1: +ipd_uv / 2 (right) */
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_eye) = 144 */
+} d2s_xr_eye;
+
 const char* d2s_last_error(void);
 int d2s_version(void);
 /* Kernel-selection switches (D2S_NO_HALO2, D2S_NO_WIDE, ... -- tuning aids) are read from the environment once and
@@ -319,6 +345,39 @@ int d2s_dibr_crop_shape(int H, int W, const double crop[4], int display_mode, in
 int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                        const d2s_dibr_params* p, const double crop[4], void* out, int out_fmt, void* stream);
 
+/* The OpenXR viewer's eye views (d2s_version() >= 115): the screen of d2s_xr_screen drawn into each eye's swapchain image with that
+ * eye's own view-projection matrix, as EffectsMixin._render_eye does (xr_viewer/effects.py:1023-1137: depth test LESS against a
+ * cleared buffer, blending off, the image cleared to the background first) -- the XR fragment shader of d2s_dibr_warp_crop run at the
+ * uv the rasteriser interpolates.  The surface is one planar facet (flat) or the strip's 48 planar facets (curved); inside a facet
+ * GL's perspective-correct interpolation is a homography from the pixel centre to uv, formed on the host in double precision.  A
+ * pixel is covered when its centre lies inside a projected facet; where several cover it the smallest depth wins, ties to the lower
+ * facet index; as in GL a fragment with NDC depth outside [-1, 1) is not drawn (near / far plane, the buffer cleared to 1), and the
+ * facets of a strip share one edge function per seam, so no pixel inside the surface is left uncovered.  The outline itself (which
+ * centres ON an edge count) is the rasteriser's fill rule and is not reproduced.
+ *   p:     read as by d2s_dibr_warp_crop (pixel_size = 1 / source size unless res_w / res_h say otherwise; alpha_mode as everywhere)
+ *          EXCEPT display_mode and viewport (not consulted), roll (screen->roll is u_roll) and feather_enabled, which must be 0: the
+ *          XR viewer never enables the feathering.  The rounded-corner SDF runs on the surface's own uv, every texture coordinate
+ *          on the cropped uv.  crop: u_source_crop, NULL = (0, 0, 1, 1).
+ *   depth: float [batch, dh, dw] at any resolution, as d2s_dibr_warp_depth.
+ *   Textures are plain GL_LINEAR + GL_REPEAT WITHOUT mipmaps, the colour texture's state whenever the reference's frost and glow modes
+ *   are off (effects.py:590-614); mipmapped filtering is out of scope.
+ *   out:   the eye images one after another, eye i at element offsets[i] of d2s_dibr_xr_shape: [batch][height_i][width_i][nch],
+ *          nch = 3 (4 with D2S_DIBR_ALPHA_RGBA), uint8 (D2S_FMT_U8_HWC) or float 0..255 (D2S_FMT_F32_HWC).  offsets[0] = 0,
+ *          offsets[i] = offsets[i-1] + batch * height_(i-1) * width_(i-1) * nch; *total = the element count of out.  An uncovered
+ *          pixel is clear.rgb * 255 (alpha: clear.a).
+ *   workspace: device, 16-byte aligned, >= d2s_dibr_xr_workspace bytes: the facet table (small set-up launches, one per eye for the flat
+ *          screen and two for a curved one, write it in front of the render launch, which draws both eyes and the whole batch).
+ * Refused with D2S_E_UNSUPPORTED, nothing launched: a vertex of the surface with clip w <= 1e-6 (the screen crosses the eye plane).
+ * Refused with D2S_E_INVALID: a non-finite value; curve outside 0..2; width, height or distance <= 0; an eye image under 2 x 2 or
+ * over 8192 on a side; eye outside 0..1; n_eyes outside 1..2; a bad struct_size; feather_enabled; a short or misaligned workspace;
+ * everything d2s_dibr_warp_crop refuses.  Stream-ordered, no host synchronisation, no allocation; every argument is checked before
+ * any HIP call.  Pinned by tests/golden/xr_eye.npz: the reference's shaders drawn off-screen (make_golden_xr_eye.py). */
+int d2s_dibr_xr_shape(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets /* [n_eyes] */, uint64_t* total);
+int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes);
+int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                     const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                     void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
  * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.
@@ -429,6 +488,14 @@ int d2s_view_pipeline_streams(d2s_engine* e, const uint8_t* frames, int batch, c
 int d2s_view_pipeline_crop_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
                                    int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
                                    int view, const double* crop, int use_ema, void* out, int out_fmt, float* depth_full, void* stream);
+
+/* d2s_view_pipeline_crop_streams with the OpenXR eye views as its last stage (d2s_version() >= 115): the same pipeline_check + depth
+ * code path, then d2s_dibr_xr_eyes on the engine's model-resolution depth, read directly (crop may be NULL = identity; out, workspace:
+ * as d2s_dibr_xr_eyes).  Bit-identical to d2s_pipeline(depth_full) followed by d2s_dibr_xr_eyes on the engine's map. */
+int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                 int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
+                                 const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int use_ema,
+                                 void* out, int out_fmt, float* depth_full, void* workspace, uint64_t workspace_bytes, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

@@ -13,7 +13,12 @@
         Both sides run THIS library (the uncropped kernels' device code does not change with the crop).  A library of
         the parent commit cannot be put under this mode with D2S_LIB -- it has no d2s_dibr_warp_crop, and D2S_LIB replaces the
         library of the whole process; to time the parent, run its own checkout's `tools/dibr_bench.py --height <eye rows>` (and the
-        plain `tools/dibr_bench.py` for the uncropped 1080p warp) alternated with this one on the same box."""
+        plain `tools/dibr_bench.py` for the uncropped 1080p warp) alternated with this one on the same box.
+    python tools/dibr_bench.py --xr-eye [--curve h|v] [--eye-size 2064 2208]
+        d2s_dibr_xr_eyes: the OpenXR screen drawn into two swapchain-size eye images from one 1080p frame (flat, or curved
+        horizontally / vertically: 48 facets), against d2s_dibr_warp_crop's gather kernel (D2S_DIBR_NO_ROWS=1, identity crop, both eyes
+        at the frame's size) -- the same pixel function on a regular grid.  The screen's distance is set so that the flat screen is
+        one source texel per pixel wide; us per launch and ns per COVERED pixel, alternated in one process."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,6 +37,9 @@ ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--iters", typ
 ap.add_argument("--json", default=None, help="--pipeline: also write the figures to this file")
 ap.add_argument("--crop", type=float, nargs="*", default=None, help="time d2s_dibr_warp_crop: x y w h in uv (no values: a 2.39:1 letterbox)")
 ap.add_argument("--corner-radius", type=float, default=0.0, help="--crop: u_corner_radius (0.03 is the OpenXR screen's)")
+ap.add_argument("--xr-eye", action="store_true", help="time d2s_dibr_xr_eyes against the cropped warp's gather kernel")
+ap.add_argument("--curve", default=None, choices=["h", "v"], help="--xr-eye: the curved screen (horizontal / vertical)")
+ap.add_argument("--eye-size", type=int, nargs=2, default=[2064, 2208], help="--xr-eye: swapchain image width height")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -109,6 +117,43 @@ def pipeline_bench():
 
 if a.pipeline:
     pipeline_bench()
+    sys.exit(0)
+if a.xr_eye:
+    import math
+    import numpy as np
+    from desktop2stereo_amd import xr
+    os.environ["D2S_DIBR_NO_ROWS"] = "1"                                           # the comparison is the gather kernel
+    ops.reload_env()
+    ew, eh = a.eye_size
+    fovs = ((-0.85, 0.75, 0.80, -0.85), (-0.75, 0.85, 0.80, -0.85))
+    px_per_tan = ew / (math.tan(0.85) + math.tan(0.75))
+    width = 2.4
+    screen = xr.XrScreen(width=width, height=width * a.height / a.width, distance=width * px_per_tan / a.width,
+                         curve={None: "flat", "h": "horizontal", "v": "vertical"}[a.curve], clear=(0.0, 0.0, 0.0, 0.5))
+    eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
+    img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
+    dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
+    for B in a.batch:
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        probe = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)      # clear alpha 0.5 marks the uncovered pixels
+        covered = B * sum(int((e[..., 3] != 0.5).sum()) for e in probe)
+        runs = {"xr_eyes": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes), "cropped_warp_gather": lambda: ops.dibr_warp(f, d, dp, crop=(0.0, 0.0, 1.0, 1.0))}
+        px = {"xr_eyes": covered, "cropped_warp_gather": B * 2 * a.height * a.width}
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"xr-eye {screen.curve} {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}: covered {covered / (B * 2 * ew * eh):.3f} of the images "
+              f"({covered // B} pixels, the cropped warp {2 * a.height * a.width})  " +
+              "  ".join(f"{k} {med[k]:8.1f} us ({1e3 * med[k] / px[k]:.4f} ns / covered pixel; min {min(t[k]):.1f} max {max(t[k]):.1f})" for k in runs) +
+              f"   xr / cropped per covered pixel = {med['xr_eyes'] / px['xr_eyes'] / (med['cropped_warp_gather'] / px['cropped_warp_gather']):.3f}", flush=True)
     sys.exit(0)
 if a.crop is not None:
     from desktop2stereo_amd import crop as K
