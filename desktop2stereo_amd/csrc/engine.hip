@@ -17,32 +17,11 @@ namespace {
 
 struct HostT { std::vector<float> data; std::vector<int64_t> shape; };
 
-struct PackedW {           // device: W [Npad][Kpad] T, bias [N] f32 (or null)
-    void* w = nullptr;
-    float* bias = nullptr;
-    int N = 0, K = 0, Kpad = 0;
-};
-
 struct Layer {
     float *ln1g, *ln1b, *ln2g, *ln2b, *ls1, *ls2;
-    PackedW qkv, proj, fc1, fc2;
-    // D2S_PREC_FP8: e4m3 copies of the four linears (index 0 qkv, 1 proj, 2 fc1, 3 fc2) with per-output-channel weight
-    // scales; deq[i][n] = s_act(site feeding linear i) * s_w[i][n] is filled in by d2s_engine_calibrate
-    PackedW w8[4];
-    std::vector<float> sw[4];
-    // LayerNorm folded into the linears that consume it (bf16 engines): W' = W diag(gamma) packed like qkv / fc1,
-    // bias' = b + W beta in *_ln.bias, csum[n] = sum_k bf16(W'[n][k]) (the values the MFMA actually sums)
-    PackedW qkv_ln, fc1_ln;
-    float *csum_qkv = nullptr, *csum_fc1 = nullptr;
-    float* deq[4] = {nullptr, nullptr, nullptr, nullptr};
-    // the same folding on the e4m3 path: [0] QKV, [1] FC1.  A operand = e4m3 of the RAW residual (static scale from the
-    // calibration pass, sites 4 / 5), W' quantised per output channel, csum8 over the de-quantised W'
-    PackedW w8_ln[2];
-    std::vector<float> sw_ln[2];
-    float *csum8[2] = {nullptr, nullptr}, *deq_ln[2] = {nullptr, nullptr};
+    LinearForms qkv, proj, fc1, fc2;        // the forms of each (linear_site.h): plain / LayerNorm folded, on e4m3 operands or not
+    LinearForms& lin(int i) { LinearForms* const a[4] = {&qkv, &proj, &fc1, &fc2}; return *a[i]; }     // in CALIB_SITE's order
 };
-
-constexpr int NSITE = 6;   // calibration sites per layer: LN1 out, attention out, LN2 out, GELU out, residual after proj, residual after FC2
 
 }  // namespace
 
@@ -58,13 +37,13 @@ struct d2s_engine {
     std::vector<void*> allocs;
 
     // weights
-    PackedW patch;
+    DevLinear patch;
     float *cls = nullptr, *pos = nullptr;          // pos: [N, D] interpolated (row 0 = cls position)
     std::vector<Layer> L;
     float *lnfg = nullptr, *lnfb = nullptr;
-    struct { PackedW proj, resize, conv; PackedW proj_ln; float* csum = nullptr; } re[4];   // proj_ln: final LayerNorm folded in (bf16, batch 1)
-    struct { PackedW proj, r1c1, r1c2, r2c1, r2c2; } fu[4];
-    PackedW head1, head2;
+    struct { LinearForms proj; DevLinear resize, conv; } re[4];     // proj's folded form: the final LayerNorm folded in (bf16)
+    struct { DevLinear proj, r1c1, r1c2, r2c1, r2c2; } fu[4];
+    DevLinear head1, head2;
     float* w3 = nullptr;
     float b3 = 0.f;
 
@@ -93,14 +72,13 @@ struct d2s_engine {
         int C = 0, sites = 0;
         float *gn_g = nullptr, *gn_b = nullptr;
         float *ln_g[2] = {nullptr, nullptr}, *ln_b[2] = {nullptr, nullptr}, *ffn_g = nullptr, *ffn_b = nullptr;
-        PackedW proj_in, proj_out, kvq[2], to_out[2], ff1, ff2;     // kvq: fused to_k | to_v | to_q, [3C][C]
+        DevLinear proj_in, proj_out, to_out[2], ff2;
+        // kvq: fused to_k | to_v | to_q, [3C][C].  Folded forms (round 5, bf16 engine): the module's three LayerNorms folded into their
+        // consumers, like the ViT's; ff1's has its rows interleaved x | gate in fours, GEGLU in its epilogue
+        LinearForms kvq[2], ff1;
         float* ptab[2] = {nullptr, nullptr};       // [32][3C] = pe @ kvq^T: the positional encoding's share of k | v | q
         void* cache[2] = {nullptr, nullptr};       // rings [max_batch][31][sites][2C] T per attention block: projected k' | v' rows, one ring per stream slot
         size_t ring_bytes = 0;                     // one slot's ring (the single-stream layout: 32-bit offsets hold inside a ring)
-        // round 5 (bf16 engine): the three LayerNorms of a module folded into the linears that consume them, like the ViT's (DESIGN.md
-        // section 3.1b): W' = W diag(gamma), bias' = b + W beta, colsum over the bf16-rounded W'
-        PackedW kvq_ln[2], ff1_ln;                  // (ff1_ln: rows interleaved x | gate in groups of four -- GEGLU happens in its epilogue)
-        float *csum_kvq[2] = {nullptr, nullptr}, *csum_ff1 = nullptr;
     } tm[4];
     float* tm_stats = nullptr;                     // (sum, sum of squares) partials per (row, column block) of the folded LayerNorms
     bool tm_fold = false;
@@ -182,59 +160,66 @@ const HostT* find(d2s_engine* e, const std::string& name) {
     return &it->second;
 }
 
-int upload_f32(d2s_engine* e, const std::string& name, size_t n, float** out) {
+// THE read of a host tensor: its n values, or null (-> D2S_E_MISSING) with the error set: missing (find), or not n elements (err)
+const float* host_f32(d2s_engine* e, const std::string& name, size_t n, const std::string& err) {
     const HostT* t = find(e, name);
-    if (!t) return D2S_E_MISSING;
-    if (t->data.size() != n) { set_error("weight " + name + ": wrong element count"); return D2S_E_MISSING; }
-    return dev_upload(e, (void**)out, t->data.data(), n * sizeof(float));
+    if (t && t->data.size() != n) { set_error(err); t = nullptr; }
+    return t ? t->data.data() : nullptr;
 }
-
-// a prepared linear (linear_site.h prepare_linear) on the device: W and its bias (none when the image has none); a folded one's colsum
-// to *csum, an e4m3 one's row scales to *sw
-int upload_linear(d2s_engine* e, LinearImage im, PackedW& out, float** csum = nullptr, std::vector<float>* sw = nullptr) {
-    RC(dev_upload(e, &out.w, im.w.data(), im.w.size()));
-    out.N = im.N; out.K = im.K; out.Kpad = im.Kpad;
-    out.bias = nullptr;
-    if (!im.bias.empty()) RC(dev_upload(e, (void**)&out.bias, im.bias.data(), im.bias.size() * sizeof(float)));
-    if (csum) {
-        D2S_REQUIRE(!im.csum.empty(), "upload_linear: a colsum was asked for, but no LayerNorm is folded into this linear");
-        RC(dev_upload(e, (void**)csum, im.csum.data(), im.csum.size() * sizeof(float)));
-    }
-    if (sw) *sw = std::move(im.sw);
+const float* host_vec(d2s_engine* e, const std::string& name, size_t n) { return host_f32(e, name, n, "weight " + name + ": wrong element count"); }
+// a linear's weight (n values) and its bias (N values; bname empty: none, *b = null)
+int host_wb(d2s_engine* e, const std::string& wname, size_t n, const std::string& bname, size_t N, const float** w, const float** b) {
+    *b = nullptr;
+    if (!(*w = host_f32(e, wname, n, "weight " + wname + ": wrong shape"))) return D2S_E_MISSING;
+    if (!bname.empty() && !(*b = host_f32(e, bname, N, "bad bias " + bname))) { set_error("bad bias " + bname); return D2S_E_MISSING; }
     return D2S_OK;
 }
 
-int pack_linear(d2s_engine* e, const std::string& wname, const std::string& bname, int N, int K, PackedW& out) {
-    const HostT* w = find(e, wname);
-    if (!w) return D2S_E_MISSING;
-    if (w->data.size() != (size_t)N * K) { set_error("weight " + wname + ": wrong shape"); return D2S_E_MISSING; }
-    const float* b = nullptr;
-    if (!bname.empty()) { const HostT* bt = find(e, bname); if (!bt || bt->data.size() != (size_t)N) { set_error("bad bias " + bname); return D2S_E_MISSING; } b = bt->data.data(); }
-    const float* p = w->data.data();
-    return upload_linear(e, prepare_linear(e->wprec, N, K, [&](int n, int k) { return p[(size_t)n * K + k]; }, b), out);
+int upload_f32(d2s_engine* e, const std::string& name, size_t n, float** out) {
+    const float* t = host_vec(e, name, n);
+    return t ? dev_upload(e, (void**)out, t, n * sizeof(float)) : D2S_E_MISSING;
+}
+
+// a prepared linear on the device (linear_site.h upload_linear), in memory the engine tracks
+int upload_linear(d2s_engine* e, LinearImage im, DevLinear& out, bool folded = false, const float* twin_bias = nullptr) {
+    auto alloc = [e](void** p, const void* host, size_t bytes) { return host ? dev_upload(e, p, host, bytes) : dev_alloc(e, p, bytes, true); };
+    return d2s::upload_linear(alloc, std::move(im), out, folded, twin_bias);
+}
+
+// The forms of one linear that this engine launches, from W = at(n, k) and its bias: plain; fold: LayerNorm gamma / beta folded in; e8:
+// both on e4m3 operands instead (the calibration pass, the one user of an e4m3 engine's bf16 forms, runs the LayerNorm kernels)
+template <typename F>
+int build_forms(d2s_engine* e, LinearForms& lf, int N, int K, F at, const float* bias, bool fold, const float* gamma, const float* beta, bool e8 = false) {
+    RC(upload_linear(e, prepare_linear(e->wprec, N, K, at, bias), lf.form(false, false)));
+    if (fold && !e8) RC(upload_linear(e, prepare_linear(e->wprec, N, K, at, bias, gamma, beta), lf.form(false, true), true));
+    if (e8) RC(upload_linear(e, prepare_linear(D2S_PREC_FP8_OPERANDS, N, K, at, nullptr), lf.form(true, false), false, lf.form(false, false).bias));
+    if (e8 && fold) RC(upload_linear(e, prepare_linear(D2S_PREC_FP8_OPERANDS, N, K, at, bias, gamma, beta), lf.form(true, true), true));
+    return D2S_OK;
+}
+// W [N][K] row-major
+auto rows_at(const float* w, int K) { return [w, K](int n, int k) { return w[(size_t)n * K + k]; }; }
+
+int pack_linear(d2s_engine* e, const std::string& wname, const std::string& bname, int N, int K, DevLinear& out) {
+    const float *p, *b;
+    RC(host_wb(e, wname, (size_t)N * K, bname, N, &p, &b));
+    return upload_linear(e, prepare_linear(e->wprec, N, K, rows_at(p, K), b), out);
 }
 
 // Conv2d 3x3 weight [Co,Ci,3,3] -> [Co][(ky*3+kx)*Ci + ci]
-int pack_conv3(d2s_engine* e, const std::string& wname, const std::string& bname, int Co, int Ci, PackedW& out) {
-    const HostT* w = find(e, wname);
-    if (!w) return D2S_E_MISSING;
-    if (w->data.size() != (size_t)Co * Ci * 9) { set_error("weight " + wname + ": wrong shape"); return D2S_E_MISSING; }
-    const float* b = nullptr;
-    if (!bname.empty()) { const HostT* bt = find(e, bname); if (!bt || bt->data.size() != (size_t)Co) { set_error("bad bias " + bname); return D2S_E_MISSING; } b = bt->data.data(); }
-    const float* p = w->data.data();
+int pack_conv3(d2s_engine* e, const std::string& wname, const std::string& bname, int Co, int Ci, DevLinear& out) {
+    const float *p, *b;
+    RC(host_wb(e, wname, (size_t)Co * Ci * 9, bname, Co, &p, &b));
     return upload_linear(e, prepare_linear(e->wprec, Co, 9 * Ci, [&](int n, int k) { return p[conv3_weight_index(n, k, Ci)]; }, b), out);
 }
 
 // ConvTranspose2d k==s weight [Ci,Co,k,k] -> rows n = (ky*k+kx)*Co + co, K = Ci; bias expanded
-int pack_convT(d2s_engine* e, const std::string& wname, const std::string& bname, int C, int ks, PackedW& out) {
-    const HostT* w = find(e, wname);
-    const HostT* bt = find(e, bname);
-    if (!w || !bt) return D2S_E_MISSING;
-    if (w->data.size() != (size_t)C * C * ks * ks || bt->data.size() != (size_t)C) { set_error("weight " + wname + ": wrong shape"); return D2S_E_MISSING; }
-    const float* p = w->data.data();
+int pack_convT(d2s_engine* e, const std::string& wname, const std::string& bname, int C, int ks, DevLinear& out) {
+    const std::string err = "weight " + wname + ": wrong shape";
+    const float *p = host_f32(e, wname, (size_t)C * C * ks * ks, err), *bt = host_f32(e, bname, C, err);
+    if (!p || !bt) return D2S_E_MISSING;
     int N = ks * ks * C;
     std::vector<float> bias(N);
-    for (int n = 0; n < N; ++n) bias[n] = bt->data[n % C];
+    for (int n = 0; n < N; ++n) bias[n] = bt[n % C];
     return upload_linear(e, prepare_linear(e->wprec, N, C, [&](int n, int k) { return p[convT_weight_index(n, k, C, ks)]; }, bias.data()), out);
 }
 
@@ -288,31 +273,21 @@ GemmA convA(const void* p, int Hi, int Wi, int C, int Ho, int Wo, int stride, in
     GemmA a = {}; a.ptr = p; a.mode = A_CONV3; a.Hi = Hi; a.Wi = Wi; a.C = C; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.relu = relu; return a;
 }
 
-int gemm(d2s_engine* e, const GemmA& a, const PackedW& w, int M, const GemmEpi& ep, hipStream_t st) {
-    int Kl = w.K % (e->prec == D2S_PREC_BF16 ? 8 : 4) ? w.Kpad : w.K;   // ragged K (patch embed): A is zero padded to Kpad
-    GemmEpi ep2 = ep;
-    if (ep.map == MAP_ROWS) {     // launcher decides whether to split K (never the small-tile kernels when LN statistics are due); each stream has its own partials
-        ep2.part = (e->side && st == e->side) ? e->splitk_ws_side : e->splitk_ws;
-        ep2.part_elems = e->splitk_elems;
-    }
-    PROF(a.mode == A_CONV3 ? PC_CONV : PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_gemm(e->wprec, 0, a, w.w, M, w.N, Kl, w.Kpad, ep2, st));
-    return D2S_OK;
-}
-
-// the same linear on e4m3 operands (A rows are e4m3 bytes, lda in elements); the epilogue de-quantises with ep.deq
-int gemm8(d2s_engine* e, const GemmA& a, const PackedW& w, int M, const GemmEpi& ep, hipStream_t st) {
-    PROF(PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_gemm(D2S_PREC_FP8_OPERANDS, 0, a, w.w, M, w.N, w.K, w.Kpad, ep, st));
+// a packed linear (convA: an implicit-GEMM convolution): launch_linear with the split-K partials of its stream, each has its own
+int linear(d2s_engine* e, const GemmA& a, const DevLinear& w, int M, const GemmEpi& ep, hipStream_t st) {
+    float* ws = (e->side && st == e->side) ? e->splitk_ws_side : e->splitk_ws;
+    PROF(a.mode == A_CONV3 ? PC_CONV : PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_linear(w, a, M, ep, ws, e->splitk_elems, 0, st));
     return D2S_OK;
 }
 
 // 3x3 conv (pad 1) as implicit GEMM over NHWC
-int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int stride, int relu_in, const PackedW& w,
+int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int stride, int relu_in, const DevLinear& w,
           void* out, int act, const void* res1, const void* res2, hipStream_t st) {
     int Ho = (Hi + 2 - 3) / stride + 1, Wo = (Wi + 2 - 3) / stride + 1;
     GemmA a = convA(in, Hi, Wi, C, Ho, Wo, stride, relu_in);
     GemmEpi ep = rowsE(out, OUT_T, w.N, w.bias);
     ep.act = act; ep.res1 = res1; ep.res2 = res2;
-    return gemm(e, a, w, B * Ho * Wo, ep, st);
+    return linear(e, a, w, B * Ho * Wo, ep, st);
 }
 
 // One row's entries of an attention block's two row tables, from its stream slot's window and ring.  THE rule for where a frame's
@@ -349,16 +324,17 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
     {
         GemmEpi ep = rowsE(e->tm_hs, OUT_F32, C, t.proj_in.bias);
         producer(ep);
-        RC(gemm(e, plainA(gn_out, C), t.proj_in, S, ep, st));
+        RC(linear(e, plainA(gn_out, C), t.proj_in, S, ep, st));
     }
     for (int a = 0; a < 2; ++a) {
         const bool folded = fold && slots >= 1 && slots <= 16;
         if (!folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->tm_hs, t.ln_g[a], t.ln_b[a], e->tm_a, S, C, 1e-5f, 0, 0, 0, st));
         // project THIS frame only (k' | v' | q'); the window's other 31 positions are already projected in the ring
         {
-            GemmEpi ep = rowsE(e->tm_kv, OUT_T, 3 * C, folded ? t.kvq_ln[a].bias : nullptr);
-            if (folded) consumer(ep, t.csum_kvq[a]);
-            RC(gemm(e, plainA(e->tm_a, C), folded ? t.kvq_ln[a] : t.kvq[a], S, ep, st));
+            const DevLinear& W = t.kvq[a].form(false, folded);
+            GemmEpi ep = rowsE(e->tm_kv, OUT_T, 3 * C, W.bias);
+            if (folded) consumer(ep, W.csum);
+            RC(linear(e, plainA(e->tm_a, C), W, S, ep, st));
         }
         // the frame's projected rows join the window (window_rows): per-row ring / head / window / store slot by value
         AttnRows attn = {};
@@ -374,29 +350,24 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
         {
             GemmEpi ep = epi_residual(e->tm_hs, C, t.to_out[a].bias, nullptr);
             producer(ep);
-            RC(gemm(e, plainA(e->tm_out, C), t.to_out[a], S, ep, st));
+            RC(linear(e, plainA(e->tm_out, C), t.to_out[a], S, ep, st));
         }
         if (store_due) PROF(PC_ELT, 0, 0, launch_cache_store(prec, e->tm_kv, t.sites, C, B, store, st));
     }
     {
         const bool folded = fold && slots >= 1 && slots <= 16;
         if (!folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->tm_hs, t.ffn_g, t.ffn_b, e->tm_a, S, C, 1e-5f, 0, 0, 0, st));
-        if (folded) {
-            // x * gelu(gate) in ff1's own epilogue (interleaved rows): tm_g [S, 4C] directly, no [S, 8C] intermediate, no GEGLU launch
-            GemmEpi ep = rowsE(e->tm_g, OUT_T, 4 * C, t.ff1_ln.bias);
-            ep.act = ACT_GEGLU;
-            consumer(ep, t.csum_ff1);
-            RC(gemm(e, plainA(e->tm_a, C), t.ff1_ln, S, ep, st));
-        } else {
-            GemmEpi ep = rowsE(e->tm_u, OUT_T, 8 * C, t.ff1.bias);
-            RC(gemm(e, plainA(e->tm_a, C), t.ff1, S, ep, st));
-            PROF(PC_ELT, 0, 0, launch_geglu(prec, e->tm_u, e->tm_g, S, 4 * C, st));
-        }
+        // folded: x * gelu(gate) in ff1's own epilogue (interleaved rows): tm_g [S, 4C] directly, no [S, 8C] intermediate, no GEGLU launch
+        const DevLinear& W = t.ff1.form(false, folded);
+        GemmEpi ep = rowsE(folded ? e->tm_g : e->tm_u, OUT_T, (folded ? 4 : 8) * C, W.bias);
+        if (folded) { ep.act = ACT_GEGLU; consumer(ep, W.csum); }
+        RC(linear(e, plainA(e->tm_a, C), W, S, ep, st));
+        if (!folded) PROF(PC_ELT, 0, 0, launch_geglu(prec, e->tm_u, e->tm_g, S, 4 * C, st));
     }
     {
         GemmEpi ep = epi_residual(e->tm_hs, C, t.ff2.bias, nullptr);
         if (fold) epi_ln_producer(ep, e->tm_a, nullptr, nullptr);     // the bf16 copy proj_out multiplies (no statistics: nothing normalises it)
-        RC(gemm(e, plainA(e->tm_g, 4 * C), t.ff2, S, ep, st));
+        RC(linear(e, plainA(e->tm_g, 4 * C), t.ff2, S, ep, st));
     }
     const void* a_out = e->tm_a;
     if (!fold) {
@@ -406,7 +377,7 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
     {
         GemmEpi ep = rowsE(out, OUT_T, C, t.proj_out.bias);
         ep.res1 = x; ep.res2 = add;
-        RC(gemm(e, plainA(a_out, C), t.proj_out, S, ep, st));
+        RC(linear(e, plainA(a_out, C), t.proj_out, S, ep, st));
     }
     return D2S_OK;
 }
@@ -419,11 +390,12 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
 int neck_proj(d2s_engine* e, int i, int B, hipStream_t st, bool fold) {
     const d2s_model_desc& d = e->d;
     const int D = d.hidden, Mp = B * e->P, c = d.neck[i];
-    if (!fold) return gemm(e, plainA(e->tapbuf[i], D), e->re[i].proj, Mp, rowsE(e->rproj[i], OUT_T, c, e->re[i].proj.bias), st);
-    GemmEpi ep = rowsE(e->rproj[i], OUT_T, c, e->re[i].proj_ln.bias);
-    epi_ln_consumer(ep, e->lnstats, e->tap_slots, e->re[i].csum, d.ln_eps, D);
+    const DevLinear& W = e->re[i].proj.form(false, fold);
+    GemmEpi ep = rowsE(e->rproj[i], OUT_T, c, W.bias);
+    if (!fold) return linear(e, plainA(e->tapbuf[i], D), W, Mp, ep, st);
+    epi_ln_consumer(ep, e->lnstats, e->tap_slots, W.csum, d.ln_eps, D);
     const int skip = epi_tap_fold_rows(ep, B, e->N, e->P);     // one frame: start one row in; several: all token rows, cls rows dropped
-    return gemm(e, plainA((const bf16_t*)e->lnbuf + (size_t)skip * D, D), e->re[i].proj_ln, skip ? Mp : B * e->N, ep, st);
+    return linear(e, plainA((const bf16_t*)e->lnbuf + (size_t)skip * D, D), W, skip ? Mp : B * e->N, ep, st);
 }
 
 int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
@@ -433,7 +405,7 @@ int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
     int Hs = gh, Ws = gw;
     if (i < 2) {
         int ks = i == 0 ? 4 : 2;
-        RC(gemm(e, plainA(e->rproj[i], c), e->re[i].resize, Mp, epi_convT(e->rres[i], c, e->re[i].resize.bias, gh, gw, ks), st));
+        RC(linear(e, plainA(e->rproj[i], c), e->re[i].resize, Mp, epi_convT(e->rres[i], c, e->re[i].resize.bias, gh, gw, ks), st));
         src = e->rres[i]; Hs = gh * ks; Ws = gw * ks;
     } else if (i == 3) {
         RC(conv3(e, e->rproj[i], B, gh, gw, c, 2, 0, e->re[i].resize, e->rres[i], ACT_NONE, nullptr, nullptr, st));
@@ -464,7 +436,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     // ---- embeddings (HF Dinov2Embeddings)
     if (x) PROF(PC_ELT, 0, 0, launch_patchify(prec, x, e->patchA, B, e->h, e->w, d.patch, e->patch.Kpad, e->cls, e->pos, e->resid, N, D, st));
     {
-        RC(gemm(e, plainA(e->patchA, e->patch.Kpad), e->patch, Mp, epi_patch_embed(e->resid, D, e->patch.bias, e->pos, P, N), st));
+        RC(linear(e, plainA(e->patchA, e->patch.Kpad), e->patch, Mp, epi_patch_embed(e->resid, D, e->patch.bias, e->pos, P, N), st));
     }
     if (e->taps) D2S_HIP(hipMemcpyAsync(e->tap_hidden, e->resid, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
     // ---- encoder (HF Dinov2Layer x L)
@@ -512,37 +484,38 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (!ln1_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, ly.ln1g, ly.ln1b, e->lnbuf, M, D, d.ln_eps, 0, 0, 0, st, f8a ? 1.0f / sa[0] : 0.f, x3));
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 0, st));
         {
-            GemmEpi ep = epi_qkv(e->qkv, qkv_out_type(f8, x3), D, ln1_folded ? (f8a ? ly.w8_ln[0].bias : ly.qkv_ln.bias) : ly.qkv.bias, e->vt, N, e->Npad, d.heads);
-            if (ln1_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, f8a ? ly.csum8[0] : ly.csum_qkv, d.ln_eps, D);
-            if (f8a) { ep.deq = ln1_folded ? ly.deq_ln[0] : ly.deq[0]; RC(gemm8(e, plainA(e->lnbuf, D), ln1_folded ? ly.w8_ln[0] : ly.w8[0], M, ep, st)); }
-            else RC(gemm(e, splitA(e->lnbuf, D, x3), ln1_folded ? ly.qkv_ln : ly.qkv, M, ep, st));
+            const DevLinear& W = ly.qkv.form(f8a, ln1_folded);
+            GemmEpi ep = epi_qkv(e->qkv, qkv_out_type(f8, x3), D, W.bias, e->vt, N, e->Npad, d.heads);
+            if (ln1_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, W.csum, d.ln_eps, D);
+            RC(linear(e, splitA(e->lnbuf, D, x3), W, M, ep, st));
         }
         PROF(PC_ATTN, 4.0 * B * d.heads * (double)N * N * 64, 0,
              launch_attention(x3 ? D2S_PREC_BF16X3 : prec, e->qkv, e->vt, e->attn, B, N, e->Npad, d.heads, st, f8a ? 1.0f / sa[1] : 0.f, e->attn_prescaled));
         if (am) RC(launch_amax(prec, e->attn, (long)M * D, am + 1, st));
         {
             if (pending_ln >= 0) { D2S_HIP(hipStreamWaitEvent(st, e->ev_ln[pending_ln], 0)); pending_ln = -1; }
-            GemmEpi ep = epi_residual(e->resid, D, ly.proj.bias, ly.ls1);
+            const DevLinear& W = ly.proj.form(f8a, false);
+            GemmEpi ep = epi_residual(e->resid, D, W.bias, ly.ls1);
             if (lnf) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[4] : 0.f);
-            if (f8a) { ep.deq = ly.deq[1]; RC(gemm8(e, plainA(e->attn, D), ly.w8[1], M, ep, st)); }
-            else RC(gemm(e, splitA(e->attn, D, x3), ly.proj, M, ep, st));
+            RC(linear(e, splitA(e->attn, D, x3), W, M, ep, st));
         }
         const bool ln2_folded = lnf && ln_slots <= 16;              // (more than 16 column blocks: the LN kernel runs instead)
         if (!ln2_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, ly.ln2g, ly.ln2b, e->lnbuf, M, D, d.ln_eps, 0, 0, 0, st, f8 ? 1.0f / sa[2] : 0.f, x3));
         if (am) RC(launch_amax(D2S_PREC_FP32, e->resid, (long)M * D, am + 4, st));       // (raw residual: the LN-folded FC1's A operand)
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 2, st));
         {
-            GemmEpi ep = epi_fc1(e->mlp, fc1_out_type(x3), d.mlp, ln2_folded ? (f8 ? ly.w8_ln[1].bias : ly.fc1_ln.bias) : ly.fc1.bias);
-            if (ln2_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, f8 ? ly.csum8[1] : ly.csum_fc1, d.ln_eps, D);
-            if (f8) { ep.deq = ln2_folded ? ly.deq_ln[1] : ly.deq[2]; ep.out_qscale = 1.0f / sa[3]; RC(gemm8(e, plainA(e->lnbuf, D), ln2_folded ? ly.w8_ln[1] : ly.w8[2], M, ep, st)); }
-            else RC(gemm(e, splitA(e->lnbuf, D, x3), ln2_folded ? ly.fc1_ln : ly.fc1, M, ep, st));
+            const DevLinear& W = ly.fc1.form(f8, ln2_folded);
+            GemmEpi ep = epi_fc1(e->mlp, fc1_out_type(x3), d.mlp, W.bias);
+            if (ln2_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, W.csum, d.ln_eps, D);
+            if (f8) ep.out_qscale = 1.0f / sa[3];
+            RC(linear(e, splitA(e->lnbuf, D, x3), W, M, ep, st));
         }
         if (am) RC(launch_amax(prec, e->mlp, (long)M * d.mlp, am + 3, st));
         {
-            GemmEpi ep = epi_residual(e->resid, D, ly.fc2.bias, ly.ls2);
+            const DevLinear& W = ly.fc2.form(f8, false);
+            GemmEpi ep = epi_residual(e->resid, D, W.bias, ly.ls2);
             if (lnf && (l + 1 < d.layers || tap_fold) && pr.ln_folds(D2S_LIN_FC2)) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[5] : 0.f);
-            if (f8) { ep.deq = ly.deq[3]; RC(gemm8(e, plainA(e->mlp, d.mlp), ly.w8[3], M, ep, st)); }
-            else RC(gemm(e, splitA(e->mlp, d.mlp, x3), ly.fc2, M, ep, st));
+            RC(linear(e, splitA(e->mlp, d.mlp, x3), W, M, ep, st));
         }
         if (am) RC(launch_amax(D2S_PREC_FP32, e->resid, (long)M * D, am + 5, st));       // (raw residual: the next layer's LN-folded QKV)
         if (e->taps) D2S_HIP(hipMemcpyAsync(e->tap_hidden + (size_t)(l + 1) * N * D, e->resid, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
@@ -592,7 +565,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         // (interpolation weights sum to 1), so it runs BEFORE the up-sample on 4x fewer pixels.
         void* pout = e->scr[3 + (idx & 1)];
         const void* next_r1 = idx < 3 ? e->r1[2 - idx] : nullptr;      // RCU1 of the next (shallower) stage's map
-        RC(gemm(e, plainA(Z, F), e->fu[idx].proj, B * Hc * Wc, rowsE(X, OUT_T, F, e->fu[idx].proj.bias), st));
+        RC(linear(e, plainA(Z, F), e->fu[idx].proj, B * Hc * Wc, rowsE(X, OUT_T, F, e->fu[idx].proj.bias), st));
         if (d.temporal && idx < 2) {                     // path_4 / path_3 (dpt_temporal.py:98-103)
             PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st));
             void* alt = e->scr[3 + ((idx + 1) & 1)];
@@ -700,6 +673,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     D2S_REQUIRE(!d.temporal || max_batch <= D2S_MAX_STREAMS, "a Video-Depth-Anything engine has at most D2S_MAX_STREAMS (32) stream slots: max_batch too large");
     D2S_ON_DEVICE(e->device);
     const int D = d.hidden, F = d.fusion;
+    const PrecRules pr = prec_rules(d.precision);
     e->h = h; e->w = w; e->gh = h / d.patch; e->gw = w / d.patch; e->P = e->gh * e->gw; e->N = e->P + 1;
     e->Npad = (e->N + 63) / 64 * 64; e->maxB = max_batch;
     const int N = e->N, P = e->P, B = max_batch;
@@ -709,11 +683,10 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     RC(pack_linear(e, pe + "patch_embeddings.projection.weight", pe + "patch_embeddings.projection.bias", D, 3 * d.patch * d.patch, e->patch));
     RC(upload_f32(e, pe + "cls_token", D, &e->cls));
     {
-        const HostT* pt = find(e, pe + "position_embeddings");
+        const float* pt = host_f32(e, pe + "position_embeddings", (size_t)(d.pos_grid * d.pos_grid + 1) * D, "position_embeddings: wrong shape");
         if (!pt) return D2S_E_MISSING;
-        if (pt->data.size() != (size_t)(d.pos_grid * d.pos_grid + 1) * D) { set_error("position_embeddings: wrong shape"); return D2S_E_MISSING; }
         std::vector<float> pos;
-        interp_pos(pt->data.data(), d.pos_grid, D, e->gh, e->gw, pos, d.temporal ? 0.1 : 0.0);
+        interp_pos(pt, d.pos_grid, D, e->gh, e->gw, pos, d.temporal ? 0.1 : 0.0);
         RC(dev_alloc(e, (void**)&e->pos, pos.size() * 4));
         D2S_HIP(hipMemcpy(e->pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
     }
@@ -724,54 +697,40 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
         RC(upload_f32(e, p + "norm1.weight", D, &ly.ln1g)); RC(upload_f32(e, p + "norm1.bias", D, &ly.ln1b));
         RC(upload_f32(e, p + "norm2.weight", D, &ly.ln2g)); RC(upload_f32(e, p + "norm2.bias", D, &ly.ln2b));
         RC(upload_f32(e, p + "layer_scale1.lambda1", D, &ly.ls1)); RC(upload_f32(e, p + "layer_scale2.lambda1", D, &ly.ls2));
+        const float *g1 = host_vec(e, p + "norm1.weight", D), *bn1 = host_vec(e, p + "norm1.bias", D), *g2 = host_vec(e, p + "norm2.weight", D),
+                    *bn2 = host_vec(e, p + "norm2.bias", D);                    // (uploaded above: all there)
+        // encoder linear `site`: folded where the precision folds there (bf16 / bf16x3: unless switched off), e4m3 where it runs on it
+        auto forms = [&](LinearForms& lf, int site, int N, int K, auto at, const float* bias, const float* gamma, const float* beta) {
+            const bool e8 = pr.e4m3_site(site);
+            return build_forms(e, lf, N, K, at, bias, gamma && pr.ln_folds(site) && (e8 || e->lnf), gamma, beta, e8);
+        };
         // fused QKV: rows q | k | v
-        const HostT *wq = find(e, p + "attention.attention.query.weight"), *wk = find(e, p + "attention.attention.key.weight"),
-                    *wv = find(e, p + "attention.attention.value.weight"), *bq = find(e, p + "attention.attention.query.bias"),
-                    *bk = find(e, p + "attention.attention.key.bias"), *bv = find(e, p + "attention.attention.value.bias");
-        if (!wq || !wk || !wv || !bq || !bk || !bv) return D2S_E_MISSING;
-        for (const HostT* t : {wq, wk, wv}) if (t->data.size() != (size_t)D * D) { set_error("qkv weight: wrong shape"); return D2S_E_MISSING; }
+        const std::string qa = p + "attention.attention.";
+        const char* const qkv_err = "qkv weight: wrong shape";
+        const float* ws[3] = {host_f32(e, qa + "query.weight", (size_t)D * D, qkv_err), host_f32(e, qa + "key.weight", (size_t)D * D, qkv_err), host_f32(e, qa + "value.weight", (size_t)D * D, qkv_err)};
+        const float *bq = host_vec(e, qa + "query.bias", D), *bk = host_vec(e, qa + "key.bias", D), *bv = host_vec(e, qa + "value.bias", D);
+        if (!ws[0] || !ws[1] || !ws[2] || !bq || !bk || !bv) return D2S_E_MISSING;
         std::vector<float> bias(3 * D);
-        for (int i = 0; i < D; ++i) { bias[i] = bq->data[i]; bias[D + i] = bk->data[i]; bias[2 * D + i] = bv->data[i]; }
+        for (int i = 0; i < D; ++i) { bias[i] = bq[i]; bias[D + i] = bk[i]; bias[2 * D + i] = bv[i]; }
         // bf16 / fp8 engines: the softmax scale 64^-0.5 log2(e) goes into the q rows of the fused QKV weight and bias (fp32
         // product, then the ONE rounding every weight gets): the attention kernels see log2-domain scores, the batched one
         // straight from the matrix pipe (attention.hip).  The fp32 engine (parity class) keeps the reference's order of operations.
         std::vector<float> wq_scaled;
         if (e->attn_prescaled) {
-            wq_scaled.resize(wq->data.size());
-            for (size_t i = 0; i < wq_scaled.size(); ++i) wq_scaled[i] = wq->data[i] * ATTN_SCALE_LOG2E;
+            wq_scaled.assign(ws[0], ws[0] + (size_t)D * D);
+            for (float& v : wq_scaled) v *= ATTN_SCALE_LOG2E;
             for (int i = 0; i < D; ++i) bias[i] *= ATTN_SCALE_LOG2E;
+            ws[0] = wq_scaled.data();
         }
-        const float* ws[3] = {e->attn_prescaled ? wq_scaled.data() : wq->data.data(), wk->data.data(), wv->data.data()};
-        auto qkv_at = [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; };
-        RC(upload_linear(e, prepare_linear(e->wprec, 3 * D, D, qkv_at, bias.data()), ly.qkv));
-        RC(pack_linear(e, p + "attention.output.dense.weight", p + "attention.output.dense.bias", D, D, ly.proj));
-        RC(pack_linear(e, p + "mlp.fc1.weight", p + "mlp.fc1.bias", d.mlp, D, ly.fc1));
-        RC(pack_linear(e, p + "mlp.fc2.weight", p + "mlp.fc2.bias", D, d.mlp, ly.fc2));
-        const HostT *g1 = find(e, p + "norm1.weight"), *bn1 = find(e, p + "norm1.bias"), *g2 = find(e, p + "norm2.weight"), *bn2 = find(e, p + "norm2.bias");
-        const HostT *wo = find(e, p + "attention.output.dense.weight"), *w1 = find(e, p + "mlp.fc1.weight"), *b1 = find(e, p + "mlp.fc1.bias"),
-                    *w2 = find(e, p + "mlp.fc2.weight");
-        if (!g1 || !bn1 || !g2 || !bn2 || !wo || !w1 || !b1 || !w2) return D2S_E_MISSING;
-        auto fc1_at = [&](int n, int k) { return w1->data[(size_t)n * D + k]; };
-        if (e->lnf) {                                   // LN1 / LN2 folded into QKV / FC1 (see Layer)
-            RC(upload_linear(e, prepare_linear(e->wprec, 3 * D, D, qkv_at, bias.data(), g1->data.data(), bn1->data.data()), ly.qkv_ln, &ly.csum_qkv));
-            RC(upload_linear(e, prepare_linear(e->wprec, d.mlp, D, fc1_at, b1->data.data(), g2->data.data(), bn2->data.data()), ly.fc1_ln, &ly.csum_fc1));
-        }
-        if (e->fp8) {                                   // the e4m3 copies, plain and LN-folded (see Layer)
-            const int e8 = D2S_PREC_FP8_OPERANDS;
-            RC(upload_linear(e, prepare_linear(e8, 3 * D, D, qkv_at, nullptr), ly.w8[0], nullptr, &ly.sw[0]));
-            RC(upload_linear(e, prepare_linear(e8, D, D, [&](int n, int k) { return wo->data[(size_t)n * D + k]; }, nullptr), ly.w8[1], nullptr, &ly.sw[1]));
-            RC(upload_linear(e, prepare_linear(e8, d.mlp, D, fc1_at, nullptr), ly.w8[2], nullptr, &ly.sw[2]));
-            RC(upload_linear(e, prepare_linear(e8, D, d.mlp, [&](int n, int k) { return w2->data[(size_t)n * d.mlp + k]; }, nullptr), ly.w8[3], nullptr, &ly.sw[3]));
-            const PackedW* w16[4] = {&ly.qkv, &ly.proj, &ly.fc1, &ly.fc2};
-            for (int i = 0; i < 4; ++i) {
-                ly.w8[i].bias = w16[i]->bias;                                      // shares the bf16 copy's bias vector
-                RC(dev_alloc(e, (void**)&ly.deq[i], (size_t)ly.w8[i].N * sizeof(float), true));
-            }
-            RC(upload_linear(e, prepare_linear(e8, 3 * D, D, qkv_at, bias.data(), g1->data.data(), bn1->data.data()), ly.w8_ln[0], &ly.csum8[0], &ly.sw_ln[0]));
-            RC(dev_alloc(e, (void**)&ly.deq_ln[0], (size_t)3 * D * sizeof(float), true));
-            RC(upload_linear(e, prepare_linear(e8, d.mlp, D, fc1_at, b1->data.data(), g2->data.data(), bn2->data.data()), ly.w8_ln[1], &ly.csum8[1], &ly.sw_ln[1]));
-            RC(dev_alloc(e, (void**)&ly.deq_ln[1], (size_t)d.mlp * sizeof(float), true));
-        }
+        RC(forms(ly.qkv, D2S_LIN_QKV, 3 * D, D, [&](int n, int k) { return ws[n / D][(size_t)(n % D) * D + k]; }, bias.data(), g1, bn1));
+        auto dense = [&](LinearForms& lf, int site, const std::string& nm, int N, int K, const float* gamma, const float* beta) {
+            const float *w, *b;
+            RC(host_wb(e, nm + "weight", (size_t)N * K, nm + "bias", N, &w, &b));
+            return forms(lf, site, N, K, rows_at(w, K), b, gamma, beta);
+        };
+        RC(dense(ly.proj, D2S_LIN_PROJ, p + "attention.output.dense.", D, D, nullptr, nullptr));
+        RC(dense(ly.fc1, D2S_LIN_FC1, p + "mlp.fc1.", d.mlp, D, g2, bn2));
+        RC(dense(ly.fc2, D2S_LIN_FC2, p + "mlp.fc2.", D, d.mlp, nullptr, nullptr));
     }
     if (e->fp8) {
         RC(dev_alloc(e, (void**)&e->amax, (size_t)d.layers * NSITE * sizeof(float), true));
@@ -782,22 +741,14 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     for (int i = 0; i < 4; ++i) {
         std::string p = "neck.reassemble_stage.layers." + std::to_string(i) + ".";
         int c = d.neck[i];
-        RC(pack_linear(e, p + "projection.weight", p + "projection.bias", c, D, e->re[i].proj));
+        // (the final LayerNorm folded into the reassemble projection too)
+        const float *wt, *bt, *gf = host_vec(e, "backbone.layernorm.weight", D), *bf = host_vec(e, "backbone.layernorm.bias", D);   // (uploaded above)
+        RC(host_wb(e, p + "projection.weight", (size_t)c * D, p + "projection.bias", c, &wt, &bt));
+        RC(build_forms(e, e->re[i].proj, c, D, rows_at(wt, D), bt, e->lnf, gf, bf));
         if (i == 0) RC(pack_convT(e, p + "resize.weight", p + "resize.bias", c, 4, e->re[i].resize));
         if (i == 1) RC(pack_convT(e, p + "resize.weight", p + "resize.bias", c, 2, e->re[i].resize));
         if (i == 3) RC(pack_conv3(e, p + "resize.weight", p + "resize.bias", c, c, e->re[i].resize));
         RC(pack_conv3(e, "neck.convs." + std::to_string(i) + ".weight", "", F, c, e->re[i].conv));
-    }
-    if (e->lnf) {                                       // final LayerNorm folded into the four reassemble projections (batch 1)
-        const HostT *gf = find(e, "backbone.layernorm.weight"), *bf = find(e, "backbone.layernorm.bias");
-        if (!gf || !bf) return D2S_E_MISSING;
-        for (int i = 0; i < 4; ++i) {
-            std::string p = "neck.reassemble_stage.layers." + std::to_string(i) + ".projection.";
-            const HostT *wt = find(e, p + "weight"), *bt = find(e, p + "bias");
-            if (!wt || !bt) return D2S_E_MISSING;
-            RC(upload_linear(e, prepare_linear(e->wprec, d.neck[i], D, [&](int n, int k) { return wt->data[(size_t)n * D + k]; }, bt->data.data(),
-                                               gf->data.data(), bf->data.data()), e->re[i].proj_ln, &e->re[i].csum));
-        }
     }
     for (int i = 0; i < 4; ++i) {
         std::string p = "neck.fusion_stage.layers." + std::to_string(i) + ".";
@@ -851,7 +802,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
         const int tC[4] = {d.neck[2], d.neck[3], F, F};
         const int tS[4] = {e->fH[2] * e->fW[2], e->fH[3] * e->fW[3], e->fH[2] * e->fW[2], e->fH[1] * e->fW[1]};
         size_t sc_max = 0, max_sites = 0;
-        e->tm_fold = prec_rules(d.precision).ln_folds(D2S_LIN_TM_KVQ) && env_int("D2S_VDA_FUSE", 1) != 0;
+        e->tm_fold = pr.ln_folds(D2S_LIN_TM_KVQ) && env_int("D2S_VDA_FUSE", 1) != 0;
         for (int m = 0; m < 4; ++m) {
             d2s_engine::TMod& t = e->tm[m];
             t.C = tC[m]; t.sites = tS[m];
@@ -872,14 +823,15 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
             }
             for (int a = 0; a < 2; ++a) {
                 std::string q = b + "attention_blocks." + std::to_string(a) + ".";
-                RC(upload_f32(e, b + "norms." + std::to_string(a) + ".weight", C, &t.ln_g[a]));
-                RC(upload_f32(e, b + "norms." + std::to_string(a) + ".bias", C, &t.ln_b[a]));
-                const HostT *wq = find(e, q + "to_q.weight"), *wk = find(e, q + "to_k.weight"), *wv = find(e, q + "to_v.weight");
-                if (!wq || !wk || !wv) return D2S_E_MISSING;
-                for (const HostT* w3 : {wq, wk, wv}) if (w3->data.size() != (size_t)C * C) { set_error("to_q/to_k/to_v: wrong shape"); return D2S_E_MISSING; }
-                const float* kvq[3] = {wk->data.data(), wv->data.data(), wq->data.data()};      // fused rows: k | v | q (no biases)
+                const std::string nm = b + "norms." + std::to_string(a);
+                RC(upload_f32(e, nm + ".weight", C, &t.ln_g[a]));
+                RC(upload_f32(e, nm + ".bias", C, &t.ln_b[a]));
+                const char* const kvq_err = "to_q/to_k/to_v: wrong shape";
+                const float* kvq[3] = {host_f32(e, q + "to_k.weight", (size_t)C * C, kvq_err), host_f32(e, q + "to_v.weight", (size_t)C * C, kvq_err),
+                                       host_f32(e, q + "to_q.weight", (size_t)C * C, kvq_err)};      // fused rows: k | v | q (no biases)
+                if (!kvq[0] || !kvq[1] || !kvq[2]) return D2S_E_MISSING;
                 auto kvq_at = [&](int n, int k) { return kvq[n / C][(size_t)(n % C) * C + k]; };
-                RC(upload_linear(e, prepare_linear(e->wprec, 3 * C, C, kvq_at, nullptr), t.kvq[a]));
+                RC(build_forms(e, t.kvq[a], 3 * C, C, kvq_at, nullptr, e->tm_fold, host_vec(e, nm + ".weight", C), host_vec(e, nm + ".bias", C)));
                 // W (x + pe_j) = W x + W pe_j: the positional share of every window position, float32
                 std::vector<float> pt((size_t)32 * 3 * C);
                 for (int j = 0; j < 32; ++j)
@@ -894,26 +846,20 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
                 RC(pack_linear(e, q + "to_out.0.weight", q + "to_out.0.bias", C, C, t.to_out[a]));
                 t.ring_bytes = (size_t)31 * t.sites * 2 * C * es;
                 RC(dev_alloc(e, &t.cache[a], (size_t)B * t.ring_bytes, true));
-                if (e->tm_fold) {
-                    const HostT *g = find(e, b + "norms." + std::to_string(a) + ".weight"), *bt = find(e, b + "norms." + std::to_string(a) + ".bias");
-                    if (!g || !bt) return D2S_E_MISSING;
-                    RC(upload_linear(e, prepare_linear(e->wprec, 3 * C, C, kvq_at, nullptr, g->data.data(), bt->data.data()), t.kvq_ln[a], &t.csum_kvq[a]));
-                }
             }
             RC(upload_f32(e, b + "ff_norm.weight", C, &t.ffn_g)); RC(upload_f32(e, b + "ff_norm.bias", C, &t.ffn_b));
-            RC(pack_linear(e, b + "ff.net.0.proj.weight", b + "ff.net.0.proj.bias", 8 * C, C, t.ff1));
+            RC(pack_linear(e, b + "ff.net.0.proj.weight", b + "ff.net.0.proj.bias", 8 * C, C, t.ff1.form(false, false)));
             RC(pack_linear(e, b + "ff.net.2.weight", b + "ff.net.2.bias", C, 4 * C, t.ff2));
             if (e->tm_fold) {
-                const HostT *g = find(e, b + "ff_norm.weight"), *bt = find(e, b + "ff_norm.bias"), *w1 = find(e, b + "ff.net.0.proj.weight"),
-                            *b1 = find(e, b + "ff.net.0.proj.bias");
-                if (!g || !bt || !w1 || !b1) return D2S_E_MISSING;
-                const float* w1p = w1->data.data();
+                const float *g = host_vec(e, b + "ff_norm.weight", C), *bt = host_vec(e, b + "ff_norm.bias", C),
+                            *w1p = host_vec(e, b + "ff.net.0.proj.weight", (size_t)8 * C * C), *b1 = host_vec(e, b + "ff.net.0.proj.bias", 8 * C);
+                if (!g || !bt || !w1p || !b1) return D2S_E_MISSING;
                 // GEGLU in the epilogue (ACT_GEGLU): packed row n' = 8 g + w holds x row 4 g + w (w < 4) or gate row 4C + 4 g + (w - 4)
                 auto orig = [C](int n) { return geglu_row(n, C); };
                 std::vector<float> b1p((size_t)8 * C);
-                for (int n = 0; n < 8 * C; ++n) b1p[n] = b1->data[orig(n)];
-                RC(upload_linear(e, prepare_linear(e->wprec, 8 * C, C, [&](int n, int k) { return w1p[(size_t)orig(n) * C + k]; }, b1p.data(),
-                                                   g->data.data(), bt->data.data()), t.ff1_ln, &t.csum_ff1));
+                for (int n = 0; n < 8 * C; ++n) b1p[n] = b1[orig(n)];
+                RC(upload_linear(e, prepare_linear(e->wprec, 8 * C, C, [&](int n, int k) { return w1p[(size_t)orig(n) * C + k]; }, b1p.data(), g, bt),
+                                 t.ff1.form(false, true), true));
             }
         }
         sc_max *= (size_t)B; max_sites *= (size_t)B;      // every row of a call runs through the same workspaces
@@ -1019,17 +965,14 @@ extern "C" int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, vo
             if (!(a > 0.f) || !std::isfinite(a)) { set_error("d2s_engine_calibrate: degenerate activation range"); return D2S_E_INVALID; }
             e->act_scale[(size_t)l * NSITE + s] = a * headroom / FP8_MAX;
         }
-        for (int i = 0; i < 4; ++i) {                         // linear i reads site i (qkv <- LN1, proj <- attention, fc1 <- LN2, fc2 <- GELU)
-            const std::vector<float> dq = deq_scales(e->act_scale[(size_t)l * NSITE + i], ly.sw[i]);
-            D2S_HIP(hipMemcpy(ly.deq[i], dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        // LN-folded linears read the raw residual: FC1 <- site 4 of this layer, QKV <- site 5 of the previous layer
-        for (int i = 0; i < 2; ++i) {
-            if (i == 0 && l == 0) continue;
-            const float sraw = i == 0 ? e->act_scale[(size_t)(l - 1) * NSITE + 5] : e->act_scale[(size_t)l * NSITE + 4];
-            const std::vector<float> dq = deq_scales(sraw, ly.sw_ln[i]);
-            D2S_HIP(hipMemcpy(ly.deq_ln[i], dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
+        for (int i = 0; i < 4; ++i)                           // every e4m3 form: deq from the scale of the site that feeds it (CALIB_SITE)
+            for (int folded = 0; folded < 2; ++folded) {
+                const DevLinear& W = ly.lin(i).form(true, folded);
+                const CalibSite cs = CALIB_SITE[i][folded];
+                if (!W.w || l + cs.dlayer < 0) continue;
+                const std::vector<float> dq = deq_scales(e->act_scale[(size_t)(l + cs.dlayer) * NSITE + cs.site], W.sw);
+                D2S_HIP(hipMemcpy(W.deq, dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
+            }
     }
     e->fp8_ready = true;
     return D2S_OK;

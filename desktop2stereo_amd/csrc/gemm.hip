@@ -18,6 +18,7 @@
 #include "gemm_epi.h"
 #include "linear_site.h"
 #include <cstdio>
+#include <deque>
 #include <vector>
 
 namespace d2s {
@@ -1129,23 +1130,6 @@ int act_operand(ProbeBuf& buf, const float* x, int M, int K, int lda, int fmt, f
     return upload(buf, o.data(), o.size());
 }
 
-// one packed linear on the device (prepare_linear's image): weight rows in the kernel's order, bias / csum / deq vectors
-struct ProbeLinear {
-    ProbeBuf w, bias, csum, deq;
-    int Kp = 0;
-};
-// e4m3: deq = s_a * s_w, as d2s_engine_calibrate sets it
-int upload_linear(ProbeLinear& L, const LinearImage& im, float s_a) {
-    L.Kp = im.Kpad;
-    int rc = upload(L.w, im.w.data(), im.w.size());
-    if (rc == D2S_OK && !im.bias.empty()) rc = upload(L.bias, im.bias.data(), im.bias.size() * sizeof(float));
-    if (rc == D2S_OK && !im.csum.empty()) rc = upload(L.csum, im.csum.data(), im.csum.size() * sizeof(float));
-    if (rc == D2S_OK && !im.sw.empty()) {
-        const std::vector<float> dq = deq_scales(s_a, im.sw);
-        rc = upload(L.deq, dq.data(), dq.size() * sizeof(float));
-    }
-    return rc;
-}
 }  // namespace
 }  // namespace d2s
 
@@ -1161,7 +1145,7 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
     const int wprec = pr.w, aprec = pr.act;
     const bool x3 = wprec == D2S_PREC_BF16X3, f8 = pr.e4m3;
     const bool enc = site == D2S_LIN_QKV || site == D2S_LIN_PROJ || site == D2S_LIN_FC1 || site == D2S_LIN_FC2;
-    const bool e8 = pr.e4m3_site(site);                                              // gemm8
+    const bool e8 = pr.e4m3_site(site);                                              // this linear runs on e4m3 operands
     const bool fold = p->ln_fold != 0;
     const bool consumer = fold && (site == D2S_LIN_QKV || site == D2S_LIN_FC1 || site == D2S_LIN_NECK_PROJ || site == D2S_LIN_TM_KVQ || site == D2S_LIN_TM_FF1);
     const bool producer = fold && !consumer;
@@ -1182,25 +1166,29 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
     D2S_REQUIRE(!producer || (p->out2 && (site == D2S_LIN_TM_FF2 || p->stats)), "ln_fold producer: out2, stats");
     const bool x_out = site == D2S_LIN_PATCH || site == D2S_LIN_PROJ || site == D2S_LIN_FC2 || site == D2S_LIN_TM_PROJ_IN || site == D2S_LIN_TM_TO_OUT || site == D2S_LIN_TM_FF2;
     D2S_REQUIRE(x_out ? p->x != nullptr : p->out != nullptr, "x (residual-stream sites) / out needed");
-    // e->splitk_ws: gemm() hands it to every row-mapped launch; gemm8 hands over none
+    // the engine's own upload and launch (linear_site.h upload_linear, launch_linear), with e->splitk_ws and device memory of this call:
+    // e4m3 forms get deq = s_a * s_w at once, as d2s_engine_calibrate would set it
     ProbeBuf ws;
     if (p->splitk_elems > 0) { int rc = alloc_splitk_ws(ws, (size_t)p->splitk_elems, st); if (rc != D2S_OK) return rc; }
-    auto launch = [&](bool fp8_ops, const GemmA& a, const ProbeLinear& L, int rows, int n, int Kl, GemmEpi ep, char* name) -> int {
-        if (!fp8_ops && ep.map == MAP_ROWS && ws.p) { ep.part = (float*)ws.p; ep.part_elems = (size_t)p->splitk_elems; }
-        kernel_note() = KernelNote{nullptr, 0, 1, NOTE_TAIL_NONE};
-        int rc = launch_gemm(fp8_ops ? D2S_PREC_FP8_OPERANDS : wprec, p->tile, a, L.w.p, rows, n, Kl, L.Kp, ep, st);
-        if (rc != D2S_OK) return rc;
-        snprintf(name, 128, "%s", noted_kernel().c_str());
-        return D2S_OK;
+    std::deque<ProbeBuf> mem;
+    auto put = [&](LinearImage im, DevLinear& L, float s_a) {
+        auto alloc = [&](void** d, const void* h, size_t bytes) { mem.emplace_back(); int rc = upload(mem.back(), h, bytes); *d = mem.back().p; return rc; };
+        const bool folded = !im.csum.empty();
+        return upload_linear(alloc, std::move(im), L, folded, nullptr, &s_a);
     };
-    auto ragged_k = [&](int k, int kp) { return k % (aprec == D2S_PREC_BF16 ? 8 : 4) ? kp : k; };    // gemm(): ragged K -> zero-padded Kpad
+    auto launch = [&](const GemmA& a, const DevLinear& L, int rows, const GemmEpi& ep, char* name) -> int {
+        kernel_note() = KernelNote{nullptr, 0, 1, NOTE_TAIL_NONE};
+        const int rc = launch_linear(L, a, rows, ep, (float*)ws.p, ws.p ? (size_t)p->splitk_elems : 0, p->tile, st);
+        if (rc == D2S_OK) snprintf(name, 128, "%s", noted_kernel().c_str());
+        return rc;
+    };
     // the raw residual copy: bf16, the unit format (bf16x3), e4m3 of v / s_res where an e4m3 linear consumes it
     const int ofmt = x3 ? ACT_BX3 : ((consumer ? e8 : f8) ? ACT_E4M3 : ACT_BF16);
     const float o2q = ofmt == ACT_E4M3 ? 1.0f / p->s_res : 0.f;
     // ---- the producer of a LayerNorm-folded consumer: the residual update x += pscale * (pa pW^T + pbias) -> out2, stats, slots
     int slots = 0;
     ProbeBuf dPa;
-    ProbeLinear Lp;
+    DevLinear Lp;
     if (consumer) {
         const bool p8 = pr.e4m3_attn;                      // (all-four e4m3: FC2 / proj on e4m3 operands; MLP-only: proj in bf16)
         const int pK = p->pK, D = K;
@@ -1208,23 +1196,22 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
         int rc = fetch_f32(hw, p->pw, (size_t)D * pK);
         if (rc == D2S_OK && p->pbias) rc = fetch_f32(hb, p->pbias, D);
         if (rc != D2S_OK) return rc;
-        rc = upload_linear(Lp, prepare_linear(p8 ? D2S_PREC_FP8_OPERANDS : wprec, D, pK, [&](int n, int k) { return hw[(size_t)n * pK + k]; },
-                                              p->pbias ? hb.data() : nullptr), p->s_pact);
+        rc = put(prepare_linear(p8 ? D2S_PREC_FP8_OPERANDS : wprec, D, pK, [&](int n, int k) { return hw[(size_t)n * pK + k]; }, p->pbias ? hb.data() : nullptr),
+                 Lp, p->s_pact);
         if (rc != D2S_OK) return rc;
         const int pfmt = p8 ? ACT_E4M3 : (x3 ? ACT_BX3 : (aprec == D2S_PREC_BF16 ? ACT_BF16 : ACT_F32));
         rc = act_operand(dPa, p->pa, M, pK, pK, pfmt, p8 ? 1.0f / p->s_pact : 0.f);
         if (rc != D2S_OK) return rc;
         GemmA a = {}; a.ptr = dPa.p; a.mode = A_PLAIN; a.lda = pK; a.bx3 = pfmt == ACT_BX3;
-        GemmEpi ep = epi_residual(p->x, D, (const float*)Lp.bias.p, p->pscale);
+        GemmEpi ep = epi_residual(p->x, D, Lp.bias, p->pscale);
         epi_ln_producer(ep, p->out2, p->stats, &slots, x3, o2q);
-        if (p8) ep.deq = (const float*)Lp.deq.p;
-        rc = launch(p8, a, Lp, M, D, p8 ? pK : ragged_k(pK, Lp.Kp), ep, p->kernel2);
+        rc = launch(a, Lp, M, ep, p->kernel2);
         if (rc != D2S_OK) return rc;
         p->stats_slots = slots;
         if (slots < 1 || slots > 16) { set_error("d2s_linear_probe: the producer leaves no statistics a consumer takes (the engine runs the LayerNorm kernel)"); return D2S_E_UNSUPPORTED; }
     }
     // ---- this linear's weights, in the packed row order: pack_convT's taps, the GEGLU interleave (x | gate in groups of four), else W's own
-    ProbeLinear L;
+    DevLinear L;
     {
         std::vector<float> hw, hb, hg, hbt, pb;
         const int Co = site == D2S_LIN_NECK_RESIZE ? K : 0, ks = p->ks;
@@ -1237,15 +1224,15 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
         auto row = [&](int n) { return geglu ? geglu_row(n, N / 8) : n; };
         auto at = [&](int n, int k) { return Co ? hw[convT_weight_index(n, k, Co, ks)] : hw[(size_t)row(n) * K + k]; };
         if (p->bias) { pb.resize(N); for (int n = 0; n < N; ++n) pb[n] = Co ? hb[n % Co] : hb[row(n)]; }
-        rc = upload_linear(L, prepare_linear(e8 ? D2S_PREC_FP8_OPERANDS : wprec, N, K, at, p->bias ? pb.data() : nullptr, consumer ? hg.data() : nullptr,
-                                             consumer ? hbt.data() : nullptr), consumer ? p->s_res : p->s_act);
+        rc = put(prepare_linear(e8 ? D2S_PREC_FP8_OPERANDS : wprec, N, K, at, p->bias ? pb.data() : nullptr, consumer ? hg.data() : nullptr,
+                                consumer ? hbt.data() : nullptr), L, consumer ? p->s_res : p->s_act);
         if (rc != D2S_OK) return rc;
     }
     // ---- A: the producer's raw residual copy (folded consumers), else the operand as its producer in the engine writes it
     ProbeBuf dA, dR, dR2;
     const int afmt = consumer ? ofmt : (e8 ? ACT_E4M3 : (x3 && enc ? ACT_BX3 : (aprec == D2S_PREC_BF16 ? ACT_BF16 : ACT_F32)));
     int rows = site == D2S_LIN_NECK_PROJ ? B * P : M;
-    const int lda = site == D2S_LIN_PATCH ? L.Kp : K;                                // patchify's rows: Kpad, zero padded
+    const int lda = site == D2S_LIN_PATCH ? L.Kpad : K;                                // patchify's rows: Kpad, zero padded
     if (!consumer) {
         D2S_REQUIRE(p->a, "a needed");
         int rc = act_operand(dA, p->a, rows, K, lda, afmt, e8 ? 1.0f / p->s_act : 0.f);
@@ -1253,7 +1240,7 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
     }
     GemmA a = {}; a.ptr = consumer ? p->out2 : dA.p; a.mode = A_PLAIN; a.lda = lda; a.bx3 = afmt == ACT_BX3;
     // ---- the epilogue, as the engine's launch site builds it
-    const float* bias = (const float*)L.bias.p;
+    const float* bias = L.bias;
     GemmEpi ep = {};
     switch (site) {
         case D2S_LIN_PATCH: ep = epi_patch_embed(p->x, N, bias, p->res, P, p->ntok); break;
@@ -1276,13 +1263,12 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
         }
         default: ep = rowsE(p->out, OUT_T, N, bias); break;                             // NECK_PROJ, TM_KVQ
     }
-    if (e8) ep.deq = (const float*)L.deq.p;
     if (producer) {
         if (site == D2S_LIN_TM_FF2) epi_ln_producer(ep, p->out2, nullptr, nullptr);
         else epi_ln_producer(ep, p->out2, p->stats, &slots, x3, o2q);
     }
     if (consumer) {
-        epi_ln_consumer(ep, p->stats, slots, (const float*)L.csum.p, p->ln_eps, K);
+        epi_ln_consumer(ep, p->stats, slots, L.csum, p->ln_eps, K);
         rows = M;
         if (site == D2S_LIN_NECK_PROJ) {
             const int skip = epi_tap_fold_rows(ep, B, p->ntok, P);
@@ -1290,7 +1276,7 @@ extern "C" int d2s_linear_probe(d2s_linear_probe_params* p, void* stream) {
             if (skip) rows = P;
         }
     }
-    int rc = launch(e8, a, L, rows, N, e8 ? K : ragged_k(K, L.Kp), ep, p->kernel);
+    int rc = launch(a, L, rows, ep, p->kernel);
     hipError_t err = hipStreamSynchronize(st);
     if (rc != D2S_OK) return rc;
     D2S_HIP(err);

@@ -1,6 +1,8 @@
 // The engine's linears, site by site: what an engine precision decides for them, the GemmEpi each launch site builds (engine.hip
-// forward, neck_proj, neck_rest, run_temporal) and the host-side preparation of their weights (plain, e4m3, LayerNorm folded).  Shared
-// with d2s_linear_probe and d2s_conv3_probe (gemm.hip), which launch exactly what the engine launches.  Host side only.
+// forward, neck_proj, neck_rest, run_temporal), the host-side preparation of their weights (LinearImage: plain, e4m3, LayerNorm
+// folded), the packed linear on the device (DevLinear, upload_linear), the forms a launch site picks from (LinearForms) and THE launch
+// (launch_linear).  The engine and d2s_linear_probe (gemm.hip) upload and launch through these same two functions, so the probe
+// launches what the engine launches by construction; d2s_conv3_probe shares the packing.  Host side only.
 #pragma once
 #include "gemm.h"
 #include <cmath>
@@ -173,9 +175,10 @@ static inline void ln_fold_row_fp8(int K, const float* g, const float* beta, F a
     bias2 = (float)sb; csum = (float)(sc * sw);
 }
 
-// One linear's weights as the GEMM takes them (host side): what the engine's PackedW / Layer and the probes upload
+// One linear's weights as the GEMM takes them (host side): what upload_linear puts on the device
 struct LinearImage {
     int N = 0, K = 0, Kpad = 0;
+    int prec = 0;                       // the GEMM precision it was packed for
     std::vector<uint8_t> w;             // [Npad][Kpad] in the GEMM precision
     std::vector<float> bias;            // [N]: the bias, or bias' = b + W beta when a LayerNorm is folded in; empty: none
     std::vector<float> csum;            // [N], folded: the colsum over what the MFMAs add (ln_fold_row*)
@@ -188,7 +191,7 @@ template <typename F>
 static inline LinearImage prepare_linear(int gprec, int N, int K, F at, const float* bias, const float* gamma = nullptr,
                                          const float* beta = nullptr) {
     LinearImage im;
-    im.N = N; im.K = K; im.Kpad = gemm_kpad(K, gprec);
+    im.N = N; im.K = K; im.Kpad = gemm_kpad(K, gprec); im.prec = gprec;
     const bool e4m3 = gprec == D2S_PREC_FP8_OPERANDS;
     auto atg = [&](int n, int k) { return gamma ? gamma[k] * at(n, k) : at(n, k); };
     im.w = e4m3 ? pack_rows_fp8_host(N, K, atg, im.sw) : pack_rows_host(gprec, N, K, atg);
@@ -215,5 +218,70 @@ static inline std::vector<float> deq_scales(float s_act, const std::vector<float
 static inline size_t convT_weight_index(int n, int k, int Co, int ks) { const int tap = n / Co, co = n % Co; return ((size_t)k * Co + co) * ks * ks + tap; }
 // GEGLU folded into ff1 (ACT_GEGLU): packed row n' = 8 g + w holds x row 4 g + w (w < 4) or gate row 4C + 4 g + (w - 4) of [8C, C]
 static inline int geglu_row(int n, int C) { const int g = n >> 3, w = n & 7; return w < 4 ? 4 * g + w : 4 * C + 4 * g + (w - 4); }
+
+// ---- a packed linear on the device -----------------------------------------------------------------------------------------
+// A LinearImage on the device: W [Npad][Kpad] in the GEMM precision prec (the engine's weight precision, or D2S_PREC_FP8_OPERANDS)
+struct DevLinear {
+    void* w = nullptr;                  // null: this form was not built
+    const float *bias = nullptr, *csum = nullptr;   // [N] or null: the bias (bias' of a folded form); folded: the colsum
+    float* deq = nullptr;               // [N], e4m3: deq[n] = s_act * sw[n], s_act the scale of the A operand
+    int N = 0, K = 0, Kpad = 0, prec = 0;
+    std::vector<float> sw;              // e4m3: the row scales (host), for whoever sets deq later
+};
+// im on the device.  alloc(void** dev, const void* host, size_t bytes) -> D2S_OK or an error: the caller's device memory holding the
+// host bytes (null: zeroes); the engine tracks it, a probe frees it on return.  folded: a LayerNorm is folded in, the image must have
+// its colsum.  twin_bias: an e4m3 form packed without a bias shares its bf16 twin's.  deq: from *s_act, or zeroed until calibrated.
+template <typename Alloc>
+static inline int upload_linear(Alloc&& alloc, LinearImage im, DevLinear& out, bool folded = false, const float* twin_bias = nullptr,
+                                const float* s_act = nullptr) {
+    D2S_REQUIRE(!folded || !im.csum.empty(), "upload_linear: a colsum was asked for, but no LayerNorm is folded into this linear");
+    out = DevLinear();
+    out.N = im.N; out.K = im.K; out.Kpad = im.Kpad; out.prec = im.prec;
+    out.bias = twin_bias;
+    int rc = alloc(&out.w, im.w.data(), im.w.size());
+    if (rc == D2S_OK && !im.bias.empty()) rc = alloc((void**)&out.bias, im.bias.data(), im.bias.size() * sizeof(float));
+    if (rc == D2S_OK && folded) rc = alloc((void**)&out.csum, im.csum.data(), im.csum.size() * sizeof(float));
+    if (rc == D2S_OK && !im.sw.empty()) {
+        const std::vector<float> dq = s_act ? deq_scales(*s_act, im.sw) : std::vector<float>();
+        rc = alloc((void**)&out.deq, s_act ? dq.data() : nullptr, im.sw.size() * sizeof(float));
+    }
+    out.sw = std::move(im.sw);
+    return rc;
+}
+
+// The forms of one linear, f[e4m3][folded]; a launch site picks by what its A operand is:
+//   form(0, 0)  W in the engine's weight precision; A = the LayerNorm-ed (or plain) activation            every linear
+//   form(0, 1)  W' = W diag(gamma), bias', colsum; A = the RAW residual copy its producer left             QKV, FC1, reassemble proj, kvq, ff1
+//   form(1, 0)  e4m3 W, row scales, deq, the bias vector of form(0, 0); A = e4m3 of the activation         QKV, proj, FC1, FC2
+//   form(1, 1)  e4m3 W', bias', colsum over the de-quantised W'; A = e4m3 of the raw residual              QKV, FC1
+// Finalize builds those the engine's precision can launch (PrecRules); the others stay empty (w null).
+struct LinearForms {
+    DevLinear f[2][2];
+    DevLinear& form(bool e4m3, bool folded) { return f[e4m3][folded]; }
+    const DevLinear& form(bool e4m3, bool folded) const { return f[e4m3][folded]; }
+};
+
+// The encoder's calibration sites per layer: LN1 out, attention out, LN2 out, GELU out, the residual after proj, after FC2.
+// CALIB_SITE[lin][folded]: the one whose scale is s_act of an e4m3 form of encoder linear lin (0 QKV, 1 proj, 2 FC1, 3 FC2): plain
+// forms read their own operand (0..3), folded ones the raw residual -- FC1 site 4 of its layer, QKV site 5 of the layer before
+// (dlayer -1: none for layer 0); site -1: no such form
+constexpr int NSITE = 6;
+struct CalibSite { int site, dlayer; };
+constexpr CalibSite CALIB_SITE[4][2] = {{{0, 0}, {5, -1}}, {{1, 0}, {-1, 0}}, {{2, 0}, {4, 0}}, {{3, 0}, {-1, 0}}};
+
+// THE launch of a packed linear, [M, K] x W^T through ep, in the record's GEMM precision.  ws / ws_elems: the caller's split-K workspace
+// (GemmEpi::part); tile: 0, or a probe's override.  e4m3: the record's deq, K as it is, NO partials -- launch_gemm dispatches on their
+// presence.  Otherwise a ragged K (patch embedding) runs to Kpad, A zero padded, and a row-mapped epilogue gets the workspace.
+static inline int launch_linear(const DevLinear& L, const GemmA& a, int M, GemmEpi ep, float* ws, size_t ws_elems, int tile, hipStream_t st) {
+    D2S_REQUIRE(L.w, "launch_linear: this form of the linear was not built for the engine's precision");
+    int Kl = L.K;
+    if (L.prec == D2S_PREC_FP8_OPERANDS) {
+        ep.deq = L.deq;
+    } else {
+        if (L.K % (L.prec == D2S_PREC_BF16 ? 8 : 4)) Kl = L.Kpad;      // (bf16 activations: 8 per chunk; fp32, also under bf16x3 weights: 4)
+        if (ep.map == MAP_ROWS) { ep.part = ws; ep.part_elems = ws_elems; }
+    }
+    return launch_gemm(L.prec, tile, a, L.w, M, L.N, Kl, L.Kpad, ep, st);
+}
 
 }  // namespace d2s

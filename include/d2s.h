@@ -591,7 +591,7 @@ typedef struct d2s_linear_probe_params {
     float   s_act, s_out, s_res, s_pact;   /* e4m3 scales: this linear's A, an e4m3 output (FC1), the raw residual copy out2, the producer's A */
     int32_t tile;              /* 0: what the engine passes (automatic); else a tile code */
     int64_t splitk_elems;      /* > 0: a split-K workspace of this many fp32 partials, as the engine's (row-mapped launches, bf16 / fp32 /
-                                  bf16x3 operands: what the engine's gemm() hands over) */
+                                  bf16x3 operands: what the engine's linear() hands over) */
     const float* a;            /* [M, K] (ln_fold consumers: unused -- A is the producer's out2) */
     const float* w;            /* [N, K] PyTorch layout (NECK_RESIZE: ConvTranspose2d [K, K, ks, ks]) */
     const float* bias;         /* [N] or null (NECK_RESIZE: [K]) */
