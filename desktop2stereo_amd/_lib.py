@@ -78,6 +78,12 @@ class Conv3ProbeParams(C.Structure):
                 ("out", C.c_void_p), ("kernel", C.c_char * 128)]
 
 
+class AttentionProbeParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("precision", C.c_int32), ("B", C.c_int32), ("heads", C.c_int32), ("N", C.c_int32),
+                ("out_e4m3", C.c_int32), ("oscale", C.c_float), ("reserved", C.c_int32),
+                ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p), ("kernel", C.c_char * 128)]
+
+
 class LinearProbeParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("site", C.c_int32), ("precision", C.c_int32), ("ln_fold", C.c_int32),
                 ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("ntok", C.c_int32), ("heads", C.c_int32), ("npad", C.c_int32),
@@ -176,6 +182,7 @@ SYMBOLS = {
     "d2s_profile_class_name": (C.c_char_p, [C.c_int]),
     "d2s_gemm_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "d2s_attention_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "d2s_attention_probe_ex": (C.c_int, [C.POINTER(AttentionProbeParams), _P]),
     "d2s_conv3_probe": (C.c_int, [C.POINTER(Conv3ProbeParams), _P]),
     "d2s_linear_probe": (C.c_int, [C.POINTER(LinearProbeParams), _P]),
 }

@@ -27,7 +27,8 @@ FLAGS += os.environ.get("D2S_HIPCC_DEFS", "").split()          # tuning aids onl
 # comparable with the oracle's (the matrix kernels keep the default fast contraction)
 EXTRA = {"frame_ops.hip": ["-ffp-contract=off"], "post.hip": ["-ffp-contract=off"], "ingest.hip": ["-ffp-contract=off"],
          "dibr.hip": ["-ffp-contract=off"], "dibr_composite.hip": ["-ffp-contract=off"], "crop_detect.hip": ["-ffp-contract=off"],
-         # the softmax never produces a NaN (masked scores are -1e30, exp2 of them is 0): without IEEE mode the compiler
+         # the softmax never produces a NaN (masked scores are -1e30, exp2 of them is 0; tests/test_gpu_attention.py holds every
+         # kernel to it, scores far below zero included): without IEEE mode the compiler
          # drops the canonicalising v_max_f32 x, x it otherwise puts in front of every fmaxf on an MFMA result
          # (30 of ~200 VALU instructions per key tile of the batched kernel, which is VALU-bound)
          "attention.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"]}

@@ -556,7 +556,9 @@ attention32_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ vt
         mx = xmax32(mx);
         if (t == 0 || !__all(mx <= 8.0f)) {
             const float delta = t == 0 ? mx : fmaxf(mx, 0.f);                  // 0 for the rows that stay as they are
-            const float alpha = __builtin_amdgcn_exp2f(-delta);
+            // (tile 0: O and l are still zero, and delta may lie below -128, where 2^-delta is +inf and 0 x inf a NaN: the factor is
+            //  kept finite.  Later tiles have delta >= 0.  One v_min_f32 in this block; the per-tile test in front of it is untouched.)
+            const float alpha = __builtin_amdgcn_exp2f(fminf(-delta, 126.0f));
 #pragma unroll
             for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; s0[r] -= delta; s1[r] -= delta; negm[r] -= delta; }
             lacc *= alpha;
@@ -622,8 +624,14 @@ attention32_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ vt
     }
 }
 
+// the kernel the last launch_attention of this host thread launched (host side only, one store): the probe reports it and the
+// tests pin the dispatch with it.  The name carries every template argument that distinguishes two instantiations.
+static thread_local const char* g_attention_note = nullptr;
+const char* attention_note() { return g_attention_note; }
+void attention_note_reset() { g_attention_note = nullptr; }
+
 int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B, int N, int Npad, int heads, hipStream_t st,
-                     float fp8_qscale, bool prescaled, bool bx3_out) {
+                     float fp8_qscale, bool prescaled) {
     // prescaled: the q columns already carry 64^-0.5 * log2(e) (folded into W_q / b_q, engine.hip): scores are log2-domain as they are
     const float scale_log2e = prescaled ? 1.0f : ATTN_SCALE_LOG2E;
     if (fp8_qscale > 0.f && prec != D2S_PREC_BF16) { set_error("attention: e4m3 output needs bf16 inputs"); return D2S_E_UNSUPPORTED; }
@@ -633,6 +641,7 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
     if (prescaled && prec == D2S_PREC_BF16 && (long)cdiv(N, 128) * heads * B >= 168 && attn32.get()) {
         if ((long)N * 3 * heads * 64 * 2 >= (1L << 31)) { set_error("attention: frame too large for 32-bit buffer offsets"); return D2S_E_UNSUPPORTED; }
         const dim3 grid(attn_grid(cdiv(N, 128), heads * B));
+        g_attention_note = fp8_qscale > 0.f ? "attention32_kernel<out=fp8>" : "attention32_kernel<out=bf16>";
         if (fp8_qscale > 0.f)
             hipLaunchKernelGGL((attention32_kernel<fp8_t>), grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, heads * B, fp8_qscale);
         else
@@ -654,36 +663,37 @@ int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B
     // (batch 1, N = 778: 18.9 us -> 13.8 us with 2 groups, 13.2 us with 4)
     const int ks = bq == 64 && (long)cdiv(N, 64) * hb < 256 ? (N >= 512 ? 4 : (N >= 256 ? 2 : 1)) : 1;
     if (fp8_qscale > 0.f) {
-        if (bq == 128) D2S_ATT8(1, 8);
-        else if (ks >= 2)
+        if (bq == 128) { g_attention_note = "attention_kernel<bf16,NW=8,NS=3,out=fp8>"; D2S_ATT8(1, 8); }
+        else if (ks >= 2) {
+            g_attention_note = "attention_kernel<bf16,NW=4,NS=2,out=fp8,KS=4>";
             hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 2, fp8_t, 4>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(1024), 0, st,
                                (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, pairs, scale_log2e, fp8_qscale);
-        else D2S_ATT8(1, 4);
+        } else { g_attention_note = "attention_kernel<bf16,NW=4,NS=3,out=fp8>"; D2S_ATT8(1, 4); }
     } else if (prec == D2S_PREC_BF16) {
         // (Three groups of three ring stages each -- two key tiles in flight per group -- measured 10.5 us against 10.6 / 10.8 with
         //  4 / 2 groups at N = 778: the batch-1 launch is not waiting for its key tiles -- 156 blocks keep 156 of 256 CUs at four
         //  waves per SIMD of softmax VALU work.  Not kept.)
-        if (ks == 2)
+        if (ks == 2) {
+            g_attention_note = "attention_kernel<bf16,NW=4,NS=3,out=bf16,KS=2>";
             hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 3, bf16_t, 2>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(512), 0, st,
                                (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
-        else if (ks == 4)
+        } else if (ks == 4) {
+            g_attention_note = "attention_kernel<bf16,NW=4,NS=2,out=bf16,KS=4>";
             hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 2, bf16_t, 4>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(1024), 0, st,
                                (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
-        else if (bq == 128) D2S_ATT(bf16_t, 1, 8);
-        else D2S_ATT(bf16_t, 1, 4);
+        } else if (bq == 128) { g_attention_note = "attention_kernel<bf16,NW=8,NS=3,out=bf16>"; D2S_ATT(bf16_t, 1, 8); }
+        else { g_attention_note = "attention_kernel<bf16,NW=4,NS=3,out=bf16>"; D2S_ATT(bf16_t, 1, 4); }
     } else if (prec == D2S_PREC_BF16X3) {
         // split-precision inputs (q | k and V^T pre-split by the QKV epilogue) and output; batch-1-sized launches split the keys.
         // (64-element rows are 256 bytes: two ring stages of K | V^T are 64 KiB -> two blocks per CU)
 #define D2S_ATT3(NW_, NS_, KS_) hipLaunchKernelGGL((attention_kernel<bx3_t, 1, NW_, NS_, bx3_t, KS_>), dim3(attn_grid(cdiv(N, NW_ * 16), pairs)), dim3(64 * NW_ * KS_), 0, st, \
         (const bx3_t*)qkv, (const bx3_t*)vt, (bx3_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f)
-        if (bq == 128) D2S_ATT3(8, 2, 1);
-        else if (ks >= 2) D2S_ATT3(4, 2, 2);
-        else D2S_ATT3(4, 2, 1);
+        if (bq == 128) { g_attention_note = "attention_kernel<bx3,NW=8,NS=2,out=bx3>"; D2S_ATT3(8, 2, 1); }
+        else if (ks >= 2) { g_attention_note = "attention_kernel<bx3,NW=4,NS=2,out=bx3,KS=2>"; D2S_ATT3(4, 2, 2); }
+        else { g_attention_note = "attention_kernel<bx3,NW=4,NS=2,out=bx3>"; D2S_ATT3(4, 2, 1); }
 #undef D2S_ATT3
-    } else if (bx3_out) {
-        hipLaunchKernelGGL((attention_kernel<float, 1, 4, 3, bx3_t>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(256), 0, st,
-                           (const float*)qkv, (const float*)vt, (bx3_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
     } else {
+        g_attention_note = "attention_kernel<f32,NW=4,NS=3,out=f32>";
         D2S_ATT(float, 1, 4);
     }
 #undef D2S_ATT
@@ -769,5 +779,41 @@ extern "C" int d2s_attention_probe(const float* q, const float* k, const float* 
     (void)hipFree(dqkv); (void)hipFree(dvt); (void)hipFree(dout);
     if (rc != D2S_OK) return rc;
     D2S_HIP(err);
+    return D2S_OK;
+}
+
+// d2s_attention_probe with everything a launch of the engine can be given, the output raw and guarded, the kernel named
+extern "C" int d2s_attention_probe_ex(d2s_attention_probe_params* p, void* stream) {
+    using namespace d2s;
+    D2S_REQUIRE(p && p->struct_size == sizeof(d2s_attention_probe_params), "d2s_attention_probe_params.struct_size must be sizeof(d2s_attention_probe_params)");
+    p->kernel[0] = 0;
+    const int precision = p->precision, B = p->B, heads = p->heads, N = p->N;
+    D2S_REQUIRE(precision == D2S_PREC_BF16 || precision == D2S_PREC_FP32 || precision == D2S_PREC_BF16X3, "bad precision (bf16, fp32 or bf16x3)");
+    D2S_REQUIRE(p->q && p->k && p->v && p->out && B > 0 && heads > 0 && N > 0, "bad argument");
+    D2S_REQUIRE(!p->out_e4m3 || (precision == D2S_PREC_BF16 && p->oscale > 0.f), "out_e4m3 needs bf16 inputs and oscale > 0");
+    const int Npad = (N + 63) / 64 * 64, D = heads * 64;
+    const long total = (long)B * heads * N * 64;
+    D2S_REQUIRE(total * 3 < (1L << 31), "too large");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = precision == D2S_PREC_BF16 ? 2 : 4, eo = p->out_e4m3 ? 1 : es;
+    struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } dqkv, dvt;
+    D2S_HIP(hipMalloc(&dqkv.p, (size_t)B * N * 3 * D * es));
+    D2S_HIP(hipMalloc(&dvt.p, (size_t)B * D * Npad * es));
+    D2S_HIP(hipMemsetAsync(dvt.p, 0, (size_t)B * D * Npad * es, st));               // V^T is zero beyond N (the engine's contract)
+    D2S_HIP(hipMemsetAsync(p->out, 0x7f, ((size_t)B * N + 2) * D * eo, st));         // guards and output alike
+    if (precision == D2S_PREC_BF16)
+        hipLaunchKernelGGL((attn_probe_pack_kernel<bf16_t>), dim3(cdiv(total, 256)), dim3(256), 0, st, p->q, p->k, p->v, (bf16_t*)dqkv.p, (bf16_t*)dvt.p, B, heads, N, Npad, ATTN_SCALE_LOG2E);
+    else if (precision == D2S_PREC_BF16X3)
+        hipLaunchKernelGGL((attn_probe_pack_kernel<bx3_t>), dim3(cdiv(total, 256)), dim3(256), 0, st, p->q, p->k, p->v, (bx3_t*)dqkv.p, (bx3_t*)dvt.p, B, heads, N, Npad, 1.0f);
+    else
+        hipLaunchKernelGGL((attn_probe_pack_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, p->q, p->k, p->v, (float*)dqkv.p, (float*)dvt.p, B, heads, N, Npad, 1.0f);
+    D2S_CHECK_LAUNCH();
+    attention_note_reset();
+    const bool pre = precision == D2S_PREC_BF16;      // as the engines do (d2s_attention_probe)
+    const int rc = launch_attention(precision, dqkv.p, dvt.p, (char*)p->out + (size_t)D * eo, B, N, Npad, heads, st, p->out_e4m3 ? p->oscale : 0.f, pre);
+    const hipError_t err = hipStreamSynchronize(st);
+    if (rc != D2S_OK) return rc;
+    D2S_HIP(err);
+    snprintf(p->kernel, sizeof(p->kernel), "%s", attention_note() ? attention_note() : "unrecorded");
     return D2S_OK;
 }

@@ -934,3 +934,29 @@ def attention_probe(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision
                                               _ptr(out), B, H, N, {"bf16": PREC_BF16, "fp32": PREC_FP32, "bf16x3": _lib.PREC_BF16X3}[precision], iters,
                                               C.byref(ms), st), "d2s_attention_probe")
     return out, ms.value
+
+
+def attention_probe_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str = "bf16", *, out_e4m3: bool = False,
+                       oscale: float = 0.0) -> dict:
+    """One attention launch of the engine through its own dispatcher (test probe, include/d2s.h d2s_attention_probe_ex): float32
+    [B, heads, N, 64] device tensors, packed as the engine's QKV linear leaves them.  out_e4m3 (bf16 only): the fp8 engines' e4m3
+    output sat(result * oscale).  Returns a dict: out [B * N, heads * 64] as raw storage (bfloat16, float32, int32 bf16x3 unit
+    words, uint8 e4m3 bytes), a view of guard [B * N + 2, heads * 64] -- one guard row before and one after, the whole buffer filled
+    with 0x7f bytes before the launch -- and kernel, the name of the kernel that ran."""
+    _need_cuda(q, "q")
+    B, H, N, d = q.shape
+    if d != 64 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("attention_probe_ex: q, k, v must be [B, heads, N, 64]")
+    if out_e4m3 and precision != "bf16":
+        raise ValueError("attention_probe_ex: out_e4m3 needs bf16 operands")
+    dt = torch.uint8 if out_e4m3 else {"bf16": torch.bfloat16, "fp32": torch.float32, "bf16x3": torch.int32}[precision]
+    guard = torch.empty((B * N + 2, H * 64), dtype=dt, device=q.device)
+    keep = [t.float().contiguous() for t in (q, k, v)]
+    p = _lib.AttentionProbeParams()
+    p.struct_size = C.sizeof(_lib.AttentionProbeParams)
+    p.precision = {"bf16": PREC_BF16, "fp32": PREC_FP32, "bf16x3": _lib.PREC_BF16X3}[precision]
+    p.B, p.heads, p.N, p.out_e4m3, p.oscale = B, H, N, int(bool(out_e4m3)), float(oscale)
+    p.q, p.k, p.v, p.out = _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(guard)
+    with _on(q.device) as st:
+        check(_lib.load().d2s_attention_probe_ex(C.byref(p), st), "d2s_attention_probe_ex")
+    return {"out": guard[1:B * N + 1], "guard": guard, "kernel": p.kernel.decode()}

@@ -526,6 +526,26 @@ int d2s_gemm_probe(const float* A, const float* Wt, const float* bias, float* C,
 int d2s_attention_probe(const float* q, const float* k, const float* v, float* out, int B, int heads, int N,
                         int precision, int iters, float* ms_per_iter, void* stream);
 
+/* d2s_attention_probe for the tests (d2s_version() >= 116): every launch the engine can make of its attention kernels -- the e4m3
+ * output of the fp8 engines included -- with the operands packed as d2s_attention_probe packs them (V^T zero beyond N; bf16: the q
+ * columns pre-scaled by 64^-0.5 log2 e as the engine folds it into W_q, fp32 / bf16x3: unscaled).  The output comes back raw, in
+ * the kernel's own type, between two guard rows; reports the kernel it ran. */
+typedef struct d2s_attention_probe_params {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_attention_probe_params) = 192 */
+    int32_t precision;         /* D2S_PREC_BF16 / D2S_PREC_FP32 / D2S_PREC_BF16X3 (operands and, but for out_e4m3, the output) */
+    int32_t B, heads, N;       /* frames, heads (64 channels each), tokens */
+    int32_t out_e4m3;          /* 1 (bf16 only): out = e4m3 sat(result * oscale), what the fp8 engines hand their output projection */
+    float   oscale;            /* out_e4m3: the kernel's fp8_qscale, as the engine passes 1 / s_act */
+    int32_t reserved;          /* 0 */
+    const float* q;            /* device, [B, heads, N, 64] */
+    const float* k;
+    const float* v;
+    void* out;                 /* device, [1 + B*N + 1, heads*64] elements of the output type (bf16 2 bytes, fp32 4, bf16x3 unit words 4,
+                                  e4m3 1): the probe fills ALL of it with 0x7f bytes, then the kernel writes rows 1 .. B*N */
+    char kernel[128];          /* out: the kernel that ran, e.g. "attention32_kernel<out=fp8>" */
+} d2s_attention_probe_params;
+int d2s_attention_probe_ex(d2s_attention_probe_params* p, void* stream);
+
 /* Stand-alone 3x3 convolution probe (tests): one convolution of the DPT neck / head through the engine's own dispatcher
  * (launch_gemm), with the operands cast and packed as the engine casts and packs them.  Reports the kernel it ran. */
 typedef struct d2s_conv3_probe_params {

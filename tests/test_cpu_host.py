@@ -42,6 +42,9 @@ def test_struct_layout_matches_header():
     P = _lib.Conv3ProbeParams                                                                # d2s_conv3_probe_params
     assert (C.sizeof(P) == 256 and P.precision.offset == 4 and P.map_head.offset == 56 and P.b3.offset == 60 and P.max_depth.offset == 64
             and P.splitk_elems.offset == 72 and P.x.offset == 80 and P.out.offset == 120 and P.kernel.offset == 128)
+    A = _lib.AttentionProbeParams                                                            # d2s_attention_probe_params
+    assert (C.sizeof(A) == 192 and A.precision.offset == 4 and A.N.offset == 16 and A.out_e4m3.offset == 20 and A.oscale.offset == 24
+            and A.q.offset == 32 and A.out.offset == 56 and A.kernel.offset == 64)
     L = _lib.LinearProbeParams                                                               # d2s_linear_probe_params
     assert (C.sizeof(L) == 488 and L.precision.offset == 8 and L.ln_fold.offset == 12 and L.M.offset == 16 and L.ntok.offset == 28
             and L.gh.offset == 40 and L.pK.offset == 52 and L.ln_eps.offset == 56 and L.s_act.offset == 60 and L.s_pact.offset == 72
