@@ -24,48 +24,81 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // native vector: stays in registers (HIP's u32x4 struct arrays went to scratch)
 
-template <typename T> struct AT;
-template <> struct AT<bf16_t> {
-    static constexpr int CE = 8, CPR = 8, NKS = 2;
-    __device__ static int swzK(int r) { return ((r >> 1) & 1) | (((r >> 3) & 3) << 1); }
-    __device__ static int swzV(int r) { return (r >> 1) & 7; }
+// What differs between the operand types of attention_kernel.  A row of 64 elements is CPR 16-byte chunks of CE elements; one MFMA
+// K step of the kernel takes, per lane group, a FRAGMENT of NF chunks from it: one chunk, or for bf16x3 the hi and the lo chunk of one
+// unit.  NKS: K steps per 64-wide row.
+struct ATChunk1 {                                       // one chunk per K step, lane group fg takes chunk 4 step + fg
+    static constexpr int NF = 1;
+    __device__ static int kchunk(int ks, int fg) { return ks * 4 + fg; }       // Q / K rows, K step ks
+    __device__ static int vchunk(int pc, int fg) { return pc * 4 + fg; }       // V^T rows, PV step pc
+};
+struct ATKeys8 {                                        // S registers of two fragments = 8 consecutive keys = one V^T chunk / unit
     // tile key held by MFMA A-row i of S fragment j
     __device__ static int key_of(int j, int i) { return (j >> 1) * 32 + (i >> 2) * 8 + (i & 3) + 4 * (j & 1); }
 };
-template <> struct AT<float> {
+template <typename T> struct AT;
+template <> struct AT<bf16_t> : ATChunk1, ATKeys8 {
+    static constexpr int CE = 8, CPR = 8, NKS = 2;
+    __device__ static int swzK(int r) { return ((r >> 1) & 1) | (((r >> 3) & 3) << 1); }
+    __device__ static int swzV(int r) { return (r >> 1) & 7; }
+};
+template <> struct AT<float> : ATChunk1 {
     static constexpr int CE = 4, CPR = 16, NKS = 4;
     __device__ static int swzK(int r) { return r & 15; }
     __device__ static int swzV(int r) { return r & 15; }
     __device__ static int key_of(int j, int i) { return j * 16 + i; }
 };
-
 // bf16x3 (split precision, common.h): rows of 64 elements = 8 units of [8 hi | 8 lo] = 16 chunks; a K = 32 step takes, per lane
 // group, the hi and the lo chunk of ONE unit; keys are permuted like the bf16 kernel's so that a lane group's P values of two S
 // fragments are the 8 consecutive keys of one V^T unit.
-template <> struct AT<bx3_t> {
-    static constexpr int CE = 4, CPR = 16, NKS = 2;
+template <> struct AT<bx3_t> : ATKeys8 {
+    static constexpr int CE = 4, CPR = 16, NKS = 2, NF = 2;
     __device__ static int swzK(int r) { return r & 15; }
     __device__ static int swzV(int r) { return r & 15; }
-    __device__ static int key_of(int j, int i) { return (j >> 1) * 32 + (i >> 2) * 8 + (i & 3) + 4 * (j & 1); }
+    // Q / K: lane group -> unit of a K = 32 step (gemm_epi.h BX3_UNIT); hi chunk of unit 4 ks + that
+    __device__ static int kchunk(int ks, int fg) { return 2 * (ks * 4 + ((0x2130 >> (4 * fg)) & 3)); }
+    // V^T: lane group fg holds keys 32 pc + 8 fg .. + 7 of the tile = unit 4 pc + fg of a V^T row (both operands agree)
+    __device__ static int vchunk(int pc, int fg) { return 2 * (pc * 4 + fg); }
 };
-#define ATT_BX3_UNIT(fg) ((0x2130 >> (4 * (fg))) & 3)               /* lane group -> unit of a K = 32 step (gemm_epi.h BX3_UNIT) */
-// x = hi + lo per operand: three bf16 MFMAs, small terms first
-__device__ __forceinline__ void mma16x3(f32x4& acc, const u32x4& a_hi, const u32x4& a_lo, const u32x4& b_hi, const u32x4& b_lo) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a_lo, *(const bf16x8*)&b_hi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a_hi, *(const bf16x8*)&b_lo, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a_hi, *(const bf16x8*)&b_hi, acc, 0, 0, 0);
-}
-// 8 fp32 P values -> the hi chunk and the lo chunk of their unit
-__device__ __forceinline__ void pack_p3(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo);
 
-__device__ __forceinline__ void mma16(f32x4& acc, const u32x4& a, const u32x4& b, bf16_t) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a, *(const bf16x8*)&b, acc, 0, 0, 0);
+template <int NF> struct AFrag { u32x4 c[NF]; };
+// chunks c .. c + NF - 1 of a global row (zeros for a row that does not exist).  Two spellings of the same load, chosen by the
+// caller: one branch around the whole fragment, or (PER_CHUNK) the parent form of one select per chunk.  For one-chunk fragments
+// both compile to the same code.  For bf16x3 they do not: with the select <bx3,NW=8> and <bx3,NW=4,KS=2> get one exec branch per
+// chunk (13 instructions more), with the one branch <bx3,NW=4> loses the per-chunk branches its first form had and measured ~1 %
+// slower; attention_kernel therefore asks for PER_CHUNK in its NW = 4, KS = 1 form only (profiles/attention_shared_isa.md, _ab.md)
+template <typename T, bool PER_CHUNK> __device__ __forceinline__ AFrag<AT<T>::NF> frag_row(const T* row, int c, bool ok) {
+    AFrag<AT<T>::NF> f;
+#pragma unroll
+    for (int n = 0; n < AT<T>::NF; ++n) f.c[n] = PER_CHUNK && ok ? *(const u32x4*)(row + (c + n) * AT<T>::CE) : (u32x4){0u, 0u, 0u, 0u};
+    if (!PER_CHUNK && ok) {
+#pragma unroll
+        for (int n = 0; n < AT<T>::NF; ++n) f.c[n] = *(const u32x4*)(row + (c + n) * AT<T>::CE);
+    }
+    return f;
 }
-__device__ __forceinline__ void mma16(f32x4& acc, const u32x4& a, const u32x4& b, float) {
-    const float* af = (const float*)&a;
-    const float* bf = (const float*)&b;
+// the same chunks of row r of an LDS tile, stored under the row's XOR swizzle
+template <typename T> __device__ __forceinline__ AFrag<AT<T>::NF> frag_lds(const u32x4* tile, int r, int c, int swz) {
+    AFrag<AT<T>::NF> f;
+#pragma unroll
+    for (int n = 0; n < AT<T>::NF; ++n) f.c[n] = tile[r * AT<T>::CPR + ((c + n) ^ swz)];
+    return f;
+}
+
+__device__ __forceinline__ void mma16(f32x4& acc, const AFrag<1>& a, const AFrag<1>& b, bf16_t) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a.c[0], *(const bf16x8*)&b.c[0], acc, 0, 0, 0);
+}
+__device__ __forceinline__ void mma16(f32x4& acc, const AFrag<1>& a, const AFrag<1>& b, float) {
+    const float* af = (const float*)&a.c[0];
+    const float* bf = (const float*)&b.c[0];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[t], bf[t], acc, 0, 0, 0);
+}
+// x = hi + lo per operand (c[0] | c[1]): three bf16 MFMAs, small terms first
+__device__ __forceinline__ void mma16(f32x4& acc, const AFrag<2>& a, const AFrag<2>& b, bx3_t) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a.c[1], *(const bf16x8*)&b.c[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a.c[0], *(const bf16x8*)&b.c[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)&a.c[0], *(const bf16x8*)&b.c[0], acc, 0, 0, 0);
 }
 
 // two floats -> packed bf16 pair, round-to-nearest-even: v_cvt_pk_bf16_f32 (gfx950) instead of ~5 VALU ops per value
@@ -88,27 +121,30 @@ __device__ __forceinline__ float xmax32(float v) {
     const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-// pack the P values a lane group contributes to one V^T chunk
-__device__ __forceinline__ u32x4 pack_p(const f32x4& lo, const f32x4& hi, bf16_t) {
-    u32x4 r;
-    r.x = pk_bf16(lo[0], lo[1]);
-    r.y = pk_bf16(lo[2], lo[3]);
-    r.z = pk_bf16(hi[0], hi[1]);
-    r.w = pk_bf16(hi[2], hi[3]);
+// pack the P values a lane group contributes to one V^T fragment (a, b: the S registers of its 8 keys; fp32: a alone, 4 keys)
+__device__ __forceinline__ AFrag<1> pack_p(const f32x4& a, const f32x4& b, bf16_t) {
+    AFrag<1> r;
+    r.c[0].x = pk_bf16(a[0], a[1]);
+    r.c[0].y = pk_bf16(a[2], a[3]);
+    r.c[0].z = pk_bf16(b[0], b[1]);
+    r.c[0].w = pk_bf16(b[2], b[3]);
     return r;
 }
-__device__ __forceinline__ u32x4 pack_p(const f32x4& lo, const f32x4&, float) {
-    u32x4 r;
-    r.x = __float_as_uint(lo[0]); r.y = __float_as_uint(lo[1]); r.z = __float_as_uint(lo[2]); r.w = __float_as_uint(lo[3]);
+__device__ __forceinline__ AFrag<1> pack_p(const f32x4& a, const f32x4&, float) {
+    AFrag<1> r;
+    r.c[0].x = __float_as_uint(a[0]); r.c[0].y = __float_as_uint(a[1]); r.c[0].z = __float_as_uint(a[2]); r.c[0].w = __float_as_uint(a[3]);
     return r;
 }
-
-__device__ __forceinline__ void pack_p3(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
+// 8 fp32 P values -> the hi chunk and the lo chunk of their unit
+__device__ __forceinline__ AFrag<2> pack_p(const f32x4& a, const f32x4& b, bx3_t) {
+    AFrag<2> r;
+    u32x4 &hi = r.c[0], &lo = r.c[1];
     hi.x = pk_bf16(a[0], a[1]); hi.y = pk_bf16(a[2], a[3]); hi.z = pk_bf16(b[0], b[1]); hi.w = pk_bf16(b[2], b[3]);
     lo.x = pk_bf16(a[0] - __uint_as_float(hi.x << 16), a[1] - __uint_as_float(hi.x & 0xffff0000u));
     lo.y = pk_bf16(a[2] - __uint_as_float(hi.y << 16), a[3] - __uint_as_float(hi.y & 0xffff0000u));
     lo.z = pk_bf16(b[0] - __uint_as_float(hi.z << 16), b[1] - __uint_as_float(hi.z & 0xffff0000u));
     lo.w = pk_bf16(b[2] - __uint_as_float(hi.w << 16), b[3] - __uint_as_float(hi.w & 0xffff0000u));
+    return r;
 }
 __device__ __forceinline__ void store_o4(float* p, const float v[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
 __device__ __forceinline__ void store_o4(bf16_t* p, const float v[4]) {
@@ -127,6 +163,15 @@ __device__ __forceinline__ void store_o4(fp8_t* p, const float v[4]) {     // va
 }
 
 __device__ u32x4 d2s_attn_zero_page[4];
+
+// Both kernels' wait for a key tile of their LDS ring: this thread's LDS-DMA requests of the tile have landed -- all but the
+// IN_FLIGHT ones issued after them while later tiles are still on their way, all of them at the tail of the key range -- then one raw
+// barrier makes every thread's part visible (and says that the stage about to be refilled has been read).
+template <int IN_FLIGHT> __device__ __forceinline__ void attn_ring_wait(bool tiles_ahead) {
+    if (tiles_ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IN_FLIGHT) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
 
 // XCD-aware block -> (q tile, head, frame).  Workgroup b lands on XCD b % 8 (observed; speed only), each XCD has its own L2.
 // With a (q tile, head, frame) grid the q tiles of one (frame, head) -- which all read the SAME K / V^T -- sit on 7 different
@@ -175,23 +220,16 @@ attention_kernel(const T* __restrict__ qkv, const T* __restrict__ vt, OT* __rest
     const T* kbase = qbase + D;
     const T* vbase = vt + ((long)b * heads + h) * 64 * Npad;
 
-    // ---- Q fragments (B operand of S^T): Q[q][chunk ks*4+fg]   (bf16x3: the hi and the lo chunk of unit ks * 4 + ATT_BX3_UNIT(fg))
-    constexpr bool X3 = std::is_same<T, bx3_t>::value;
-    u32x4 qf[QF][NKS], qfl[QF][X3 ? NKS : 1];
+    // ---- Q fragments (B operand of S^T): Q[q][fragment at chunk kchunk(ks, fg)]
+    using Frag = AFrag<A::NF>;
+    Frag qf[QF][NKS];
     int qrow[QF];
 #pragma unroll
     for (int f = 0; f < QF; ++f) {
         qrow[f] = qt * BQ + (wid * QF + f) * 16 + fr;
         bool ok = qrow[f] < N;
 #pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if constexpr (X3) {
-                const int c_ = 2 * (ks * 4 + ATT_BX3_UNIT(fg));
-                qf[f][ks] = ok ? *(const u32x4*)(qbase + (long)qrow[f] * row3 + c_ * CE) : (u32x4){0u, 0u, 0u, 0u};
-                qfl[f][ks] = ok ? *(const u32x4*)(qbase + (long)qrow[f] * row3 + (c_ + 1) * CE) : (u32x4){0u, 0u, 0u, 0u};
-            } else
-                qf[f][ks] = ok ? *(const u32x4*)(qbase + (long)qrow[f] * row3 + (ks * 4 + fg) * CE) : (u32x4){0u, 0u, 0u, 0u};
-        }
+        for (int ks = 0; ks < NKS; ++ks) qf[f][ks] = frag_row<T, NW == 4 && KS == 1>(qbase + (long)qrow[f] * row3, A::kchunk(ks, fg), ok);
     }
 
     f32x4 o[QF][4];
@@ -233,9 +271,7 @@ attention_kernel(const T* __restrict__ qkv, const T* __restrict__ vt, OT* __rest
     for (int t = 0; t < PD; ++t)
         if (t < ntiles) ATT_ISSUE(t)
     for (int t = 0; t < nit; ++t) {
-        if (t + PD - 1 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PD - 1) * LPTA) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        attn_ring_wait<(PD - 1) * LPTA>(t + PD - 1 < ntiles);
         if (t + PD < ntiles) ATT_ISSUE(t + PD)
         if (KS > 1 && t >= ntiles) continue;
         const u32x4* Kl = lds + (t % NS) * 2 * TILE_CHUNKS;
@@ -251,16 +287,9 @@ attention_kernel(const T* __restrict__ qkv, const T* __restrict__ vt, OT* __rest
             int kr = A::key_of(j, fr);
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) {
-                if constexpr (X3) {
-                    const int c_ = 2 * (ks * 4 + ATT_BX3_UNIT(fg));
-                    const u32x4 kh = Kl[kr * CPR + (c_ ^ A::swzK(kr))], kl = Kl[kr * CPR + ((c_ + 1) ^ A::swzK(kr))];
+                const Frag kf = frag_lds<T>(Kl, kr, A::kchunk(ks, fg), A::swzK(kr));
 #pragma unroll
-                    for (int f = 0; f < QF; ++f) mma16x3(s[f][j], kh, kl, qf[f][ks], qfl[f][ks]);
-                } else {
-                    u32x4 kf = Kl[kr * CPR + ((ks * 4 + fg) ^ A::swzK(kr))];
-#pragma unroll
-                    for (int f = 0; f < QF; ++f) mma16(s[f][j], kf, qf[f][ks], T());
-                }
+                for (int f = 0; f < QF; ++f) mma16(s[f][j], kf, qf[f][ks], T());
             }
         }
         // ---- mask the ragged last tile: key of register r in fragment j = key_of(j, fg*4 + r)
@@ -306,36 +335,19 @@ attention_kernel(const T* __restrict__ qkv, const T* __restrict__ vt, OT* __rest
                 for (int d = 0; d < 4; ++d) { o[f][d][0] *= alpha; o[f][d][1] *= alpha; o[f][d][2] *= alpha; o[f][d][3] *= alpha; }
             }
         }
-        // ---- O^T += V^T P^T
+        // ---- O^T += V^T P^T: PV step pc takes the P of SPF S fragments (8 keys of a lane group; fp32: 4)
+        constexpr int SPF = 4 / NKS;
 #pragma unroll
         for (int pc = 0; pc < NKS; ++pc) {
-            if constexpr (X3) {
-                // lane group fg holds keys 32 pc + 8 fg .. + 7 of the tile = unit 4 pc + fg of a V^T row (both operands agree)
-                u32x4 ph[QF], pl[QF];
+            Frag pf[QF];
 #pragma unroll
-                for (int f = 0; f < QF; ++f) pack_p3(s[f][2 * pc], s[f][2 * pc + 1], ph[f], pl[f]);
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const int vr = d * 16 + fr, c_ = 2 * (pc * 4 + fg);
-                    const u32x4 vh = Vl[vr * CPR + (c_ ^ A::swzV(vr))], vl = Vl[vr * CPR + ((c_ + 1) ^ A::swzV(vr))];
-#pragma unroll
-                    for (int f = 0; f < QF; ++f) mma16x3(o[f][d], vh, vl, ph[f], pl[f]);
-                }
-            } else {
-            u32x4 pf[QF];
-#pragma unroll
-            for (int f = 0; f < QF; ++f)
-            {
-                if constexpr (NKS == 2) pf[f] = pack_p(s[f][2 * pc], s[f][2 * pc + 1], T());
-                else pf[f] = pack_p(s[f][pc], s[f][pc], T());
-            }
+            for (int f = 0; f < QF; ++f) pf[f] = pack_p(s[f][SPF * pc], s[f][SPF * pc + SPF - 1], T());
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
-                int vr = d * 16 + fr;
-                u32x4 vf = Vl[vr * CPR + ((pc * 4 + fg) ^ A::swzV(vr))];
+                const int vr = d * 16 + fr;
+                const Frag vf = frag_lds<T>(Vl, vr, A::vchunk(pc, fg), A::swzV(vr));
 #pragma unroll
                 for (int f = 0; f < QF; ++f) mma16(o[f][d], vf, pf[f], T());
-            }
             }
         }
     }
@@ -510,9 +522,7 @@ attention32_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ vt
     for (int t = 0; t < PD; ++t)
         if (t < ntiles) ATT_ISSUE(t)
     for (int t = 0; t < ntiles; ++t) {
-        if (t + PD - 1 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PD - 1) * LPTA) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        attn_ring_wait<(PD - 1) * LPTA>(t + PD - 1 < ntiles);
         if (t + PD < ntiles) ATT_ISSUE(t + PD)
         if (dead) continue;
         const u32x4* Kl = lds + (t % NS) * 2 * TILE;
@@ -624,82 +634,114 @@ attention32_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ vt
     }
 }
 
-// the kernel the last launch_attention of this host thread launched (host side only, one store): the probe reports it and the
-// tests pin the dispatch with it.  The name carries every template argument that distinguishes two instantiations.
-static thread_local const char* g_attention_note = nullptr;
-const char* attention_note() { return g_attention_note; }
-void attention_note_reset() { g_attention_note = nullptr; }
+// Every kernel instantiation of this file, once: K(id, T, NW, NS, OT, KS) an attention_kernel<T, 1, NW, NS, OT, KS> (operand type, waves per
+// key group, ring stages, output type, key groups), K32(id, OT) an attention32_kernel<OT>.  The enum, the names the probe reports (the
+// tests pin the dispatch with them), block size, query rows per block and the launch switch are generated from this list.
+#define ATT_INSTANCES(K, K32)            \
+    K32(ATT32_BF16, bf16)                \
+    K32(ATT32_E4M3, fp8)                 \
+    K(ATT_BF16_NW4, bf16, 4, 3, bf16, 1) \
+    K(ATT_BF16_NW8, bf16, 8, 3, bf16, 1) \
+    K(ATT_BF16_KS2, bf16, 4, 3, bf16, 2) \
+    K(ATT_BF16_KS4, bf16, 4, 2, bf16, 4) \
+    K(ATT_E4M3_NW4, bf16, 4, 3, fp8, 1)  \
+    K(ATT_E4M3_NW8, bf16, 8, 3, fp8, 1)  \
+    K(ATT_E4M3_KS4, bf16, 4, 2, fp8, 4)  \
+    K(ATT_BX3_NW4, bx3, 4, 2, bx3, 1)    /* (64-element rows are 256 bytes: two ring stages of K | V^T are 64 KiB -> two blocks per CU) */ \
+    K(ATT_BX3_NW8, bx3, 8, 2, bx3, 1)    \
+    K(ATT_BX3_KS2, bx3, 4, 2, bx3, 2)    \
+    K(ATT_F32_NW4, f32, 4, 3, f32, 1)
+// the list's type tokens
+#define ATT_T_bf16 bf16_t
+#define ATT_T_bx3 bx3_t
+#define ATT_T_f32 float
+#define ATT_T_fp8 fp8_t
+// a name carries every template argument that distinguishes two instantiations; one key group is not spelled
+#define ATT_KS_1(s) ""
+#define ATT_KS_2(s) s
+#define ATT_KS_4(s) s
+#define ATT_ID(ID, ...) ID,
+enum { ATT_INSTANCES(ATT_ID, ATT_ID) };
+#undef ATT_ID
+#define ATT_K(ID, T, NW, NS, OT, KS) {"attention_kernel<" #T ",NW=" #NW ",NS=" #NS ",out=" #OT ATT_KS_##KS(",KS=" #KS) ">", 64 * NW * KS, NW * 16},
+#define ATT_K32(ID, OT) {"attention32_kernel<out=" #OT ">", 256, 128},
+static const struct { const char* name; int block, rows; } att_inst[] = { ATT_INSTANCES(ATT_K, ATT_K32) };     // rows: query rows per block
+#undef ATT_K
+#undef ATT_K32
+
+struct AttnPlan { int inst; const char* name; unsigned grid; int block, pairs; float scale_log2e, oscale; };
+
+// The three rules of plan_attention, in the order it asks them.  q128 / k64: the launch's blocks of 128 query rows, of 64 (which is
+// also its key tiles x pairs).
+
+// batched bf16: the 32 x 32 kernel from 168 blocks of 128 rows (D2S_ATTN32=0: the 16-row kernel everywhere)
+// (168: from batch 2 at N = 778: +0.3 % at 2, +1.5 % at 4, +4.5 % at 6; batch 1 -6 %)
+static bool attn32_ok(int prec, bool prescaled, long q128) {
+    static EnvInt attn32{"D2S_ATTN32", 1};
+    return prescaled && prec == D2S_PREC_BF16 && q128 >= 168 && attn32.get();
+}
+// q rows per block: 128 as 8 waves x 1 fragment once that fills the chip (batch >= ~8), else 64 as 4 waves.
+// Swept at batch 1 / 16: 4 waves x 2 fragments 80 us, ring depth 2 / 4 within 3 %, 8 x 2 (256 rows) 68 us,
+// 8 x 1 67 us (444 TFLOP/s); 32-row blocks slower (K/V tile loads not amortised).
+static bool attn_nw8_ok(long q128) { return q128 >= 512; }
+// too few (q-tile, head) blocks to fill 256 CUs (batch 1: 156): split the keys over 2 / 4 wave groups per block
+// (batch 1, N = 778: 18.9 us -> 13.8 us with 2 groups, 13.2 us with 4)
+// (Three groups of three ring stages each -- two key tiles in flight per group -- measured 10.5 us against 10.6 / 10.8 with
+//  4 / 2 groups at N = 778: the batch-1 launch is not waiting for its key tiles -- 156 blocks keep 156 of 256 CUs at four
+//  waves per SIMD of softmax VALU work.  Not kept.)
+static int attn_key_groups(int N, long k64) { return k64 < 256 ? (N >= 512 ? 4 : (N >= 256 ? 2 : 1)) : 1; }
+
+// Which kernel a launch takes, its grid and its scales: host arithmetic only.  D2S_OK, or the error launch_attention reports.
+static int plan_attention(int prec, int B, int N, int heads, float fp8_qscale, bool prescaled, AttnPlan& p) {
+    const bool e4m3 = fp8_qscale > 0.f;
+    if (e4m3 && prec != D2S_PREC_BF16) { set_error("attention: e4m3 output needs bf16 inputs"); return D2S_E_UNSUPPORTED; }
+    const long hb = (long)heads * B, q128 = cdiv(N, 128) * hb, k64 = cdiv(N, 64) * hb;
+    if (attn32_ok(prec, prescaled, q128)) {
+        if ((long)N * 3 * heads * 64 * 2 >= (1L << 31)) { set_error("attention: frame too large for 32-bit buffer offsets"); return D2S_E_UNSUPPORTED; }
+        p.inst = e4m3 ? ATT32_E4M3 : ATT32_BF16;
+    } else {
+        const bool nw8 = attn_nw8_ok(q128);
+        const int ks = nw8 ? 1 : attn_key_groups(N, k64);
+        // the key-split forms that exist: bf16 output KS = 2 and KS = 4 as the rule says; e4m3 output KS = 4 only, also for
+        // 256 <= N < 512; bf16x3 KS = 2 only, also for N >= 512; fp32 none, and no 8-wave form
+        if (prec == D2S_PREC_BF16 && e4m3) p.inst = nw8 ? ATT_E4M3_NW8 : (ks >= 2 ? ATT_E4M3_KS4 : ATT_E4M3_NW4);
+        else if (prec == D2S_PREC_BF16) p.inst = nw8 ? ATT_BF16_NW8 : (ks == 4 ? ATT_BF16_KS4 : (ks == 2 ? ATT_BF16_KS2 : ATT_BF16_NW4));
+        // split-precision inputs (q | k and V^T pre-split by the QKV epilogue) and output; batch-1-sized launches split the keys
+        else if (prec == D2S_PREC_BF16X3) p.inst = nw8 ? ATT_BX3_NW8 : (ks >= 2 ? ATT_BX3_KS2 : ATT_BX3_NW4);
+        else p.inst = ATT_F32_NW4;
+    }
+    p.name = att_inst[p.inst].name;
+    p.pairs = heads * B;
+    p.grid = attn_grid(cdiv(N, att_inst[p.inst].rows), p.pairs);
+    p.block = att_inst[p.inst].block;
+    // prescaled: the q columns already carry 64^-0.5 * log2(e) (folded into W_q / b_q, engine.hip): scores are log2-domain as they are
+    p.scale_log2e = prescaled ? 1.0f : ATTN_SCALE_LOG2E;
+    p.oscale = e4m3 ? fp8_qscale : 1.0f;
+    return D2S_OK;
+}
+
+static int launch_attn_plan(const AttnPlan& p, const void* qkv, const void* vt, void* out, int N, int Npad, int heads, hipStream_t st) {
+    const dim3 grid(p.grid), block(p.block);
+    switch (p.inst) {
+#define ATT_K(ID, T, NW, NS, OT, KS)                                                                                                   \
+    case ID: hipLaunchKernelGGL((attention_kernel<ATT_T_##T, 1, NW, NS, ATT_T_##OT, KS>), grid, block, 0, st, (const ATT_T_##T*)qkv,  \
+                                (const ATT_T_##T*)vt, (ATT_T_##OT*)out, N, Npad, heads, p.pairs, p.scale_log2e, p.oscale); break;
+#define ATT_K32(ID, OT)                                                                                                                \
+    case ID: hipLaunchKernelGGL((attention32_kernel<ATT_T_##OT>), grid, block, 0, st, (const bf16_t*)qkv, (const bf16_t*)vt,          \
+                                (ATT_T_##OT*)out, N, Npad, heads, p.pairs, p.oscale); break;
+        ATT_INSTANCES(ATT_K, ATT_K32)
+#undef ATT_K
+#undef ATT_K32
+    }
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
 
 int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B, int N, int Npad, int heads, hipStream_t st,
                      float fp8_qscale, bool prescaled) {
-    // prescaled: the q columns already carry 64^-0.5 * log2(e) (folded into W_q / b_q, engine.hip): scores are log2-domain as they are
-    const float scale_log2e = prescaled ? 1.0f : ATTN_SCALE_LOG2E;
-    if (fp8_qscale > 0.f && prec != D2S_PREC_BF16) { set_error("attention: e4m3 output needs bf16 inputs"); return D2S_E_UNSUPPORTED; }
-    // batched bf16: the 32 x 32 kernel from 168 blocks of 128 rows (D2S_ATTN32=0: the 16-row kernel everywhere)
-    // (168: from batch 2 at N = 778: +0.3 % at 2, +1.5 % at 4, +4.5 % at 6; batch 1 -6 %)
-    static EnvInt attn32{"D2S_ATTN32", 1};
-    if (prescaled && prec == D2S_PREC_BF16 && (long)cdiv(N, 128) * heads * B >= 168 && attn32.get()) {
-        if ((long)N * 3 * heads * 64 * 2 >= (1L << 31)) { set_error("attention: frame too large for 32-bit buffer offsets"); return D2S_E_UNSUPPORTED; }
-        const dim3 grid(attn_grid(cdiv(N, 128), heads * B));
-        g_attention_note = fp8_qscale > 0.f ? "attention32_kernel<out=fp8>" : "attention32_kernel<out=bf16>";
-        if (fp8_qscale > 0.f)
-            hipLaunchKernelGGL((attention32_kernel<fp8_t>), grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, heads * B, fp8_qscale);
-        else
-            hipLaunchKernelGGL((attention32_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, heads * B, 1.0f);
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-    // q rows per block: 128 as 8 waves x 1 fragment once that fills the chip (batch >= ~8), else 64 as 4 waves.
-    // Swept at batch 1 / 16: 4 waves x 2 fragments 80 us, ring depth 2 / 4 within 3 %, 8 x 2 (256 rows) 68 us,
-    // 8 x 1 67 us (444 TFLOP/s); 32-row blocks slower (K/V tile loads not amortised).
-    long hb = (long)heads * B;
-    const int bq = cdiv(N, 128) * hb >= 512 ? 128 : 64;
-    const int pairs = heads * B;
-#define D2S_ATT(TT, QF_, NW_) hipLaunchKernelGGL((attention_kernel<TT, QF_, NW_>), dim3(attn_grid(cdiv(N, NW_ * QF_ * 16), pairs)), dim3(64 * NW_), 0, st, \
-        (const TT*)qkv, (const TT*)vt, (TT*)out, N, Npad, heads, pairs, scale_log2e, 1.0f)
-#define D2S_ATT8(QF_, NW_) hipLaunchKernelGGL((attention_kernel<bf16_t, QF_, NW_, 3, fp8_t>), dim3(attn_grid(cdiv(N, NW_ * QF_ * 16), pairs)), dim3(64 * NW_), 0, st, \
-        (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, pairs, scale_log2e, fp8_qscale)
-    // too few (q-tile, head) blocks to fill 256 CUs (batch 1: 156): split the keys over 2 / 4 wave groups per block
-    // (batch 1, N = 778: 18.9 us -> 13.8 us with 2 groups, 13.2 us with 4)
-    const int ks = bq == 64 && (long)cdiv(N, 64) * hb < 256 ? (N >= 512 ? 4 : (N >= 256 ? 2 : 1)) : 1;
-    if (fp8_qscale > 0.f) {
-        if (bq == 128) { g_attention_note = "attention_kernel<bf16,NW=8,NS=3,out=fp8>"; D2S_ATT8(1, 8); }
-        else if (ks >= 2) {
-            g_attention_note = "attention_kernel<bf16,NW=4,NS=2,out=fp8,KS=4>";
-            hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 2, fp8_t, 4>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(1024), 0, st,
-                               (const bf16_t*)qkv, (const bf16_t*)vt, (fp8_t*)out, N, Npad, heads, pairs, scale_log2e, fp8_qscale);
-        } else { g_attention_note = "attention_kernel<bf16,NW=4,NS=3,out=fp8>"; D2S_ATT8(1, 4); }
-    } else if (prec == D2S_PREC_BF16) {
-        // (Three groups of three ring stages each -- two key tiles in flight per group -- measured 10.5 us against 10.6 / 10.8 with
-        //  4 / 2 groups at N = 778: the batch-1 launch is not waiting for its key tiles -- 156 blocks keep 156 of 256 CUs at four
-        //  waves per SIMD of softmax VALU work.  Not kept.)
-        if (ks == 2) {
-            g_attention_note = "attention_kernel<bf16,NW=4,NS=3,out=bf16,KS=2>";
-            hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 3, bf16_t, 2>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(512), 0, st,
-                               (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
-        } else if (ks == 4) {
-            g_attention_note = "attention_kernel<bf16,NW=4,NS=2,out=bf16,KS=4>";
-            hipLaunchKernelGGL((attention_kernel<bf16_t, 1, 4, 2, bf16_t, 4>), dim3(attn_grid(cdiv(N, 64), pairs)), dim3(1024), 0, st,
-                               (const bf16_t*)qkv, (const bf16_t*)vt, (bf16_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f);
-        } else if (bq == 128) { g_attention_note = "attention_kernel<bf16,NW=8,NS=3,out=bf16>"; D2S_ATT(bf16_t, 1, 8); }
-        else { g_attention_note = "attention_kernel<bf16,NW=4,NS=3,out=bf16>"; D2S_ATT(bf16_t, 1, 4); }
-    } else if (prec == D2S_PREC_BF16X3) {
-        // split-precision inputs (q | k and V^T pre-split by the QKV epilogue) and output; batch-1-sized launches split the keys.
-        // (64-element rows are 256 bytes: two ring stages of K | V^T are 64 KiB -> two blocks per CU)
-#define D2S_ATT3(NW_, NS_, KS_) hipLaunchKernelGGL((attention_kernel<bx3_t, 1, NW_, NS_, bx3_t, KS_>), dim3(attn_grid(cdiv(N, NW_ * 16), pairs)), dim3(64 * NW_ * KS_), 0, st, \
-        (const bx3_t*)qkv, (const bx3_t*)vt, (bx3_t*)out, N, Npad, heads, pairs, scale_log2e, 1.0f)
-        if (bq == 128) { g_attention_note = "attention_kernel<bx3,NW=8,NS=2,out=bx3>"; D2S_ATT3(8, 2, 1); }
-        else if (ks >= 2) { g_attention_note = "attention_kernel<bx3,NW=4,NS=2,out=bx3,KS=2>"; D2S_ATT3(4, 2, 2); }
-        else { g_attention_note = "attention_kernel<bx3,NW=4,NS=2,out=bx3>"; D2S_ATT3(4, 2, 1); }
-#undef D2S_ATT3
-    } else {
-        g_attention_note = "attention_kernel<f32,NW=4,NS=3,out=f32>";
-        D2S_ATT(float, 1, 4);
-    }
-#undef D2S_ATT
-#undef D2S_ATT8
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
+    AttnPlan p;
+    const int rc = plan_attention(prec, B, N, heads, fp8_qscale, prescaled, p);
+    return rc != D2S_OK ? rc : launch_attn_plan(p, qkv, vt, out, N, Npad, heads, st);
 }
 
 }  // namespace d2s
@@ -736,6 +778,33 @@ __global__ void attn_probe_unpack_kernel(const T* __restrict__ o, float* __restr
     if constexpr (std::is_same<T, bx3_t>::value) out[idx] = bx3_load1(o + idx);
     else if constexpr (sizeof(T) == 2) out[idx] = bf2f(o[idx]); else out[idx] = o[idx];
 }
+
+// Device memory of a probe call, freed however the call returns
+struct ProbeBuf { void* p = nullptr; ~ProbeBuf() { if (p) (void)hipFree(p); } };
+// The operands of both probes as the engine's QKV linear leaves them: allocates qkv and V^T, zeroes V^T (zero beyond N is the
+// engine's contract) and packs q | k | v in the operand type.  bf16: the q columns pre-scaled, as the engine folds it into W_q.
+struct AttnProbeOperands {
+    ProbeBuf qkv, vt;
+    int Npad = 0;
+    int pack(int precision, const float* q, const float* k, const float* v, int B, int heads, int N, hipStream_t st) {
+        Npad = (N + 63) / 64 * 64;
+        const int D = heads * 64;
+        const size_t es = precision == D2S_PREC_BF16 ? 2 : 4;
+        D2S_HIP(hipMalloc(&qkv.p, (size_t)B * N * 3 * D * es));
+        D2S_HIP(hipMalloc(&vt.p, (size_t)B * D * Npad * es));
+        D2S_HIP(hipMemsetAsync(vt.p, 0, (size_t)B * D * Npad * es, st));
+        const long total = (long)B * heads * N * 64;
+        const dim3 grid(cdiv(total, 256)), block(256);
+        if (precision == D2S_PREC_BF16)
+            hipLaunchKernelGGL((attn_probe_pack_kernel<bf16_t>), grid, block, 0, st, q, k, v, (bf16_t*)qkv.p, (bf16_t*)vt.p, B, heads, N, Npad, ATTN_SCALE_LOG2E);
+        else if (precision == D2S_PREC_BF16X3)
+            hipLaunchKernelGGL((attn_probe_pack_kernel<bx3_t>), grid, block, 0, st, q, k, v, (bx3_t*)qkv.p, (bx3_t*)vt.p, B, heads, N, Npad, 1.0f);
+        else
+            hipLaunchKernelGGL((attn_probe_pack_kernel<float>), grid, block, 0, st, q, k, v, (float*)qkv.p, (float*)vt.p, B, heads, N, Npad, 1.0f);
+        D2S_CHECK_LAUNCH();
+        return D2S_OK;
+    }
+};
 }  // namespace d2s
 
 extern "C" int d2s_attention_probe(const float* q, const float* k, const float* v, float* out, int B, int heads, int N,
@@ -744,39 +813,31 @@ extern "C" int d2s_attention_probe(const float* q, const float* k, const float* 
     D2S_REQUIRE(q && k && v && out && B > 0 && heads > 0 && N > 0 && iters >= 1, "bad argument");
     D2S_REQUIRE(precision == D2S_PREC_BF16 || precision == D2S_PREC_FP32 || precision == D2S_PREC_BF16X3, "bad precision");
     hipStream_t st = (hipStream_t)stream;
-    const int Npad = (N + 63) / 64 * 64, D = heads * 64;
+    const int D = heads * 64;
     const size_t es = precision == D2S_PREC_BF16 ? 2 : 4;
-    void *dqkv = nullptr, *dvt = nullptr, *dout = nullptr;
-    D2S_HIP(hipMalloc(&dqkv, (size_t)B * N * 3 * D * es));
-    D2S_HIP(hipMalloc(&dvt, (size_t)B * D * Npad * es));
-    D2S_HIP(hipMalloc(&dout, (size_t)B * N * D * es));
-    D2S_HIP(hipMemsetAsync(dvt, 0, (size_t)B * D * Npad * es, st));
-    const long total = (long)B * heads * N * 64;
-    if (precision == D2S_PREC_BF16)
-        hipLaunchKernelGGL((attn_probe_pack_kernel<bf16_t>), dim3(cdiv(total, 256)), dim3(256), 0, st, q, k, v, (bf16_t*)dqkv, (bf16_t*)dvt, B, heads, N, Npad, ATTN_SCALE_LOG2E);
-    else if (precision == D2S_PREC_BF16X3)
-        hipLaunchKernelGGL((attn_probe_pack_kernel<bx3_t>), dim3(cdiv(total, 256)), dim3(256), 0, st, q, k, v, (bx3_t*)dqkv, (bx3_t*)dvt, B, heads, N, Npad, 1.0f);
-    else
-        hipLaunchKernelGGL((attn_probe_pack_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, q, k, v, (float*)dqkv, (float*)dvt, B, heads, N, Npad, 1.0f);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    D2S_HIP(hipEventCreate(&e0)); D2S_HIP(hipEventCreate(&e1));
+    AttnProbeOperands in;
+    ProbeBuf dout;
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+    int rc = in.pack(precision, q, k, v, B, heads, N, st);
+    if (rc != D2S_OK) return rc;
+    D2S_HIP(hipMalloc(&dout.p, (size_t)B * N * D * es));
+    D2S_HIP(hipEventCreate(&e0.e)); D2S_HIP(hipEventCreate(&e1.e));
     const bool pre = precision == D2S_PREC_BF16;      // as the engines do: bf16 engines fold the scale into W_q, fp32 keeps the reference's order
-    int rc = launch_attention(precision, dqkv, dvt, dout, B, N, Npad, heads, st, 0.f, pre);      // warm-up (and the result)
-    D2S_HIP(hipEventRecord(e0, st));
-    for (int i = 1; i < iters && rc == D2S_OK; ++i) rc = launch_attention(precision, dqkv, dvt, dout, B, N, Npad, heads, st, 0.f, pre);
-    D2S_HIP(hipEventRecord(e1, st));
+    rc = launch_attention(precision, in.qkv.p, in.vt.p, dout.p, B, N, in.Npad, heads, st, 0.f, pre);      // warm-up (and the result)
+    D2S_HIP(hipEventRecord(e0.e, st));
+    for (int i = 1; i < iters && rc == D2S_OK; ++i) rc = launch_attention(precision, in.qkv.p, in.vt.p, dout.p, B, N, in.Npad, heads, st, 0.f, pre);
+    D2S_HIP(hipEventRecord(e1.e, st));
+    const long n = (long)B * N * D;
     if (precision == D2S_PREC_BF16)
-        hipLaunchKernelGGL((attn_probe_unpack_kernel<bf16_t>), dim3(cdiv((long)B * N * D, 256)), dim3(256), 0, st, (const bf16_t*)dout, out, (long)B * N * D);
+        hipLaunchKernelGGL((attn_probe_unpack_kernel<bf16_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const bf16_t*)dout.p, out, n);
     else if (precision == D2S_PREC_BF16X3)
-        hipLaunchKernelGGL((attn_probe_unpack_kernel<bx3_t>), dim3(cdiv((long)B * N * D, 256)), dim3(256), 0, st, (const bx3_t*)dout, out, (long)B * N * D);
+        hipLaunchKernelGGL((attn_probe_unpack_kernel<bx3_t>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const bx3_t*)dout.p, out, n);
     else
-        hipLaunchKernelGGL((attn_probe_unpack_kernel<float>), dim3(cdiv((long)B * N * D, 256)), dim3(256), 0, st, (const float*)dout, out, (long)B * N * D);
+        hipLaunchKernelGGL((attn_probe_unpack_kernel<float>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)dout.p, out, n);
     hipError_t err = hipStreamSynchronize(st);
     float ms = 0.f;
-    if (err == hipSuccess && iters > 1) (void)hipEventElapsedTime(&ms, e0, e1);
+    if (err == hipSuccess && iters > 1) (void)hipEventElapsedTime(&ms, e0.e, e1.e);
     if (ms_per_iter) *ms_per_iter = iters > 1 ? ms / (float)(iters - 1) : 0.f;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(dqkv); (void)hipFree(dvt); (void)hipFree(dout);
     if (rc != D2S_OK) return rc;
     D2S_HIP(err);
     return D2S_OK;
@@ -791,29 +852,21 @@ extern "C" int d2s_attention_probe_ex(d2s_attention_probe_params* p, void* strea
     D2S_REQUIRE(precision == D2S_PREC_BF16 || precision == D2S_PREC_FP32 || precision == D2S_PREC_BF16X3, "bad precision (bf16, fp32 or bf16x3)");
     D2S_REQUIRE(p->q && p->k && p->v && p->out && B > 0 && heads > 0 && N > 0, "bad argument");
     D2S_REQUIRE(!p->out_e4m3 || (precision == D2S_PREC_BF16 && p->oscale > 0.f), "out_e4m3 needs bf16 inputs and oscale > 0");
-    const int Npad = (N + 63) / 64 * 64, D = heads * 64;
-    const long total = (long)B * heads * N * 64;
-    D2S_REQUIRE(total * 3 < (1L << 31), "too large");
+    const int D = heads * 64;
+    D2S_REQUIRE((long)B * heads * N * 64 * 3 < (1L << 31), "too large");
     hipStream_t st = (hipStream_t)stream;
-    const size_t es = precision == D2S_PREC_BF16 ? 2 : 4, eo = p->out_e4m3 ? 1 : es;
-    struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } dqkv, dvt;
-    D2S_HIP(hipMalloc(&dqkv.p, (size_t)B * N * 3 * D * es));
-    D2S_HIP(hipMalloc(&dvt.p, (size_t)B * D * Npad * es));
-    D2S_HIP(hipMemsetAsync(dvt.p, 0, (size_t)B * D * Npad * es, st));               // V^T is zero beyond N (the engine's contract)
+    const size_t eo = p->out_e4m3 ? 1 : (precision == D2S_PREC_BF16 ? 2 : 4);
+    AttnProbeOperands in;
+    int rc = in.pack(precision, p->q, p->k, p->v, B, heads, N, st);
+    if (rc != D2S_OK) return rc;
     D2S_HIP(hipMemsetAsync(p->out, 0x7f, ((size_t)B * N + 2) * D * eo, st));         // guards and output alike
-    if (precision == D2S_PREC_BF16)
-        hipLaunchKernelGGL((attn_probe_pack_kernel<bf16_t>), dim3(cdiv(total, 256)), dim3(256), 0, st, p->q, p->k, p->v, (bf16_t*)dqkv.p, (bf16_t*)dvt.p, B, heads, N, Npad, ATTN_SCALE_LOG2E);
-    else if (precision == D2S_PREC_BF16X3)
-        hipLaunchKernelGGL((attn_probe_pack_kernel<bx3_t>), dim3(cdiv(total, 256)), dim3(256), 0, st, p->q, p->k, p->v, (bx3_t*)dqkv.p, (bx3_t*)dvt.p, B, heads, N, Npad, 1.0f);
-    else
-        hipLaunchKernelGGL((attn_probe_pack_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, p->q, p->k, p->v, (float*)dqkv.p, (float*)dvt.p, B, heads, N, Npad, 1.0f);
-    D2S_CHECK_LAUNCH();
-    attention_note_reset();
+    AttnPlan plan;
     const bool pre = precision == D2S_PREC_BF16;      // as the engines do (d2s_attention_probe)
-    const int rc = launch_attention(precision, dqkv.p, dvt.p, (char*)p->out + (size_t)D * eo, B, N, Npad, heads, st, p->out_e4m3 ? p->oscale : 0.f, pre);
+    rc = plan_attention(precision, B, N, heads, p->out_e4m3 ? p->oscale : 0.f, pre, plan);
+    if (rc == D2S_OK) rc = launch_attn_plan(plan, in.qkv.p, in.vt.p, (char*)p->out + (size_t)D * eo, N, in.Npad, heads, st);
     const hipError_t err = hipStreamSynchronize(st);
     if (rc != D2S_OK) return rc;
     D2S_HIP(err);
-    snprintf(p->kernel, sizeof(p->kernel), "%s", attention_note() ? attention_note() : "unrecorded");
+    snprintf(p->kernel, sizeof(p->kernel), "%s", plan.name);
     return D2S_OK;
 }

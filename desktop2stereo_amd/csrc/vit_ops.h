@@ -27,12 +27,10 @@ int launch_to_f32(int prec, const void* in, float* out, long n, hipStream_t st);
 // prescaled: the q third of qkv already carries ATTN_SCALE_LOG2E (bf16 / fp8 engines fold it into W_q and b_q: one rounding, and
 // the batched kernel gets log2-domain scores straight from the matrix pipe); false: the kernel applies it (fp32 parity class).
 constexpr float ATTN_SCALE_LOG2E = 0.125f * 1.4426950408889634f;          // 64^-0.5 * log2(e)
+// Plans the launch (attention.hip plan_attention: host arithmetic on (prec, e4m3 output, B heads, N) picks one row of the file's
+// instance list, its grid and scales) and launches that plan; an unsupported combination is an error, nothing is launched.
 int launch_attention(int prec, const void* qkv, const void* vt, void* out, int B, int N, int Npad, int heads, hipStream_t st,
                      float fp8_qscale = 0.f, bool prescaled = false);
-// the kernel the last launch_attention of this host thread launched, e.g. "attention_kernel<bf16,NW=4,NS=2,out=bf16,KS=4>" (null: none
-// since the reset); read by d2s_attention_probe_ex only
-const char* attention_note();
-void attention_note_reset();
 
 // Video-Depth-Anything temporal-module kernels (temporal.hip)
 // x, out [rows][sites, C]: one normalisation per (row, group)
