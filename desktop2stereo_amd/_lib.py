@@ -97,6 +97,20 @@ class LinearProbeParams(C.Structure):
                 ("kernel", C.c_char * 128), ("kernel2", C.c_char * 128)]
 
 
+class TemporalProbeParams(C.Structure):
+    """d2s_temporal_probe_params (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("op", C.c_int32), ("precision", C.c_int32), ("rows", C.c_int32), ("sites", C.c_int32),
+                ("C", C.c_int32), ("groups", C.c_int32), ("slots", C.c_int32), ("eps", C.c_float), ("qscale", C.c_float),
+                ("bx3_out", C.c_int32), ("rows_per_img", C.c_int32), ("img_rows", C.c_int32), ("row_off", C.c_int32), ("n", C.c_int64),
+                ("x", C.c_void_p), ("out", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("ptab", C.c_void_p),
+                ("x_elems", C.c_uint64), ("out_elems", C.c_uint64), ("gamma_elems", C.c_uint64), ("beta_elems", C.c_uint64),
+                ("ptab_elems", C.c_uint64), ("ring", C.c_void_p * 32), ("ring_elems", C.c_uint64 * 32),
+                ("head", C.c_int32 * 32), ("Tw", C.c_int32 * 32), ("store_slot", C.c_int32 * 32),
+                ("slot0", C.c_int32 * 32), ("nslots", C.c_int32 * 32), ("kernel", C.c_char * 128)]
+
+
+TEMPORAL_OPS = {"groupnorm": 0, "temporal_attn": 1, "cache_store": 2, "geglu": 3, "cast_f32": 4, "layernorm": 5}      # D2S_TP_*
+
 LINEAR_SITES = {"patch": 0, "qkv": 1, "proj": 2, "fc1": 3, "fc2": 4, "neck_proj": 5, "neck_resize": 6, "tm_proj_in": 7,    # D2S_LIN_*
                 "tm_kvq": 8, "tm_ff1": 9, "tm_to_out": 10, "tm_ff2": 11, "tm_proj_out": 12}
 
@@ -185,6 +199,7 @@ SYMBOLS = {
     "d2s_attention_probe_ex": (C.c_int, [C.POINTER(AttentionProbeParams), _P]),
     "d2s_conv3_probe": (C.c_int, [C.POINTER(Conv3ProbeParams), _P]),
     "d2s_linear_probe": (C.c_int, [C.POINTER(LinearProbeParams), _P]),
+    "d2s_temporal_probe": (C.c_int, [C.POINTER(TemporalProbeParams), _P]),
 }
 
 _lib = None

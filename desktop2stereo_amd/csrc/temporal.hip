@@ -11,6 +11,7 @@
 // rows is overwritten in place and only the new frame is projected).
 #include "vit_ops.h"
 #include <algorithm>
+#include <cstdio>
 #include <type_traits>
 
 namespace d2s {
@@ -315,32 +316,47 @@ cast_f32_kernel(const float* __restrict__ in, T* __restrict__ out, long n) {
     if (idx < n) out[idx] = tcvt<T>(in[idx]);
 }
 
-template <typename T>
-static bool launch_groupnorm_reg(const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, int rows, hipStream_t st) {
-    const int cpg = C / groups, rpt = (sites + 1023) / 1024;
-#define D2S_GN(CPG_, RPT_) { hipLaunchKernelGGL((groupnorm_reg_kernel<T, CPG_, RPT_>), dim3(groups, rows), dim3(1024), 0, st, (const T*)x, g, b, (T*)out, sites, C, eps); return true; }
-#define D2S_GN_R(CPG_) { if (rpt == 1) D2S_GN(CPG_, 1) if (rpt == 2) D2S_GN(CPG_, 2) if (rpt <= 4 && (CPG_) * 4 <= 96) D2S_GN(CPG_, 4) return false; }
-    switch (cpg) {          // C / 32 of the model zoo: fusion 64 / 128 / 256, neck 192 / 384 / 512 / 768 / 1024
-        case 2: D2S_GN_R(2) case 4: D2S_GN_R(4) case 6: D2S_GN_R(6) case 8: D2S_GN_R(8) case 12: D2S_GN_R(12)
-        case 16: D2S_GN_R(16) case 24: D2S_GN_R(24) case 32: D2S_GN_R(32)
-        default: return false;
+static const char* prec_tag(int prec) { return prec == D2S_PREC_BF16 ? "bf16" : "f32"; }
+
+// groupnorm_reg_kernel's instances: C / 32 of the model zoo (fusion 64 / 128 / 256, neck 192 / 384 / 512 / 768 / 1024) x sites per thread;
+// RPT 4 while CPG * 4 <= 96 registers of values
+#define D2S_GN_INSTANCES(X) X(2, 1) X(2, 2) X(2, 4) X(4, 1) X(4, 2) X(4, 4) X(6, 1) X(6, 2) X(6, 4) X(8, 1) X(8, 2) X(8, 4) \
+    X(12, 1) X(12, 2) X(12, 4) X(16, 1) X(16, 2) X(16, 4) X(24, 1) X(24, 2) X(24, 4) X(32, 1) X(32, 2)
+
+GnPlan plan_groupnorm(int /*prec*/, int sites, int C, int groups) {
+    static EnvInt old{"D2S_GN_OLD", 0};                   // A/B aid: round 4's kernel
+    GnPlan p{false, C / groups, 0};
+    const int need = (sites + 1023) / 1024;               // sites per thread of a 1024-thread block
+    const int rpt = need <= 2 ? need : 4;
+    if (!old.get() && need <= 4) {
+#define D2S_GN(CPG_, RPT_) if (p.cpg == CPG_ && rpt == RPT_) { p.reg = true; p.rpt = rpt; }
+        D2S_GN_INSTANCES(D2S_GN)
+#undef D2S_GN
     }
-#undef D2S_GN_R
+    return p;
+}
+void plan_name(const GnPlan& p, int prec, char* buf, size_t n) {
+    if (p.reg) snprintf(buf, n, "groupnorm_reg_kernel<%s,CPG=%d,RPT=%d>", prec_tag(prec), p.cpg, p.rpt);
+    else snprintf(buf, n, "groupnorm_kernel<%s>", prec_tag(prec));
+}
+
+template <typename T>
+static void launch_groupnorm_plan(const GnPlan& p, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, int rows, hipStream_t st) {
+    if (!p.reg) {
+        hipLaunchKernelGGL(groupnorm_kernel<T>, dim3(groups, rows), dim3(256), 0, st, (const T*)x, g, b, (T*)out, sites, C, groups, eps);
+        return;
+    }
+#define D2S_GN(CPG_, RPT_) if (p.cpg == CPG_ && p.rpt == RPT_) hipLaunchKernelGGL((groupnorm_reg_kernel<T, CPG_, RPT_>), dim3(groups, rows), dim3(1024), 0, st, (const T*)x, g, b, (T*)out, sites, C, eps);
+    D2S_GN_INSTANCES(D2S_GN)
 #undef D2S_GN
 }
 
 int launch_groupnorm(int prec, const void* x, const float* g, const float* b, void* out, int sites, int C, int groups, float eps, hipStream_t st, int rows) {
     if (rows < 1 || rows > 65535) { set_error("groupnorm: bad row count"); return D2S_E_INVALID; }
-    if (C % groups) { set_error("groupnorm: C must be a multiple of the group count"); return D2S_E_INVALID; }
-    static EnvInt old{"D2S_GN_OLD", 0};                   // A/B aid: round 4's kernel
-    const bool reg_ok = !old.get() && ((C / groups) & 1) == 0;
-    if (prec == D2S_PREC_BF16) {
-        if (!(reg_ok && launch_groupnorm_reg<bf16_t>(x, g, b, out, sites, C, groups, eps, rows, st)))
-            hipLaunchKernelGGL(groupnorm_kernel<bf16_t>, dim3(groups, rows), dim3(256), 0, st, (const bf16_t*)x, g, b, (bf16_t*)out, sites, C, groups, eps);
-    } else {
-        if (!(reg_ok && launch_groupnorm_reg<float>(x, g, b, out, sites, C, groups, eps, rows, st)))
-            hipLaunchKernelGGL(groupnorm_kernel<float>, dim3(groups, rows), dim3(256), 0, st, (const float*)x, g, b, (float*)out, sites, C, groups, eps);
-    }
+    if (groups < 1 || C % groups) { set_error("groupnorm: C must be a multiple of the group count"); return D2S_E_INVALID; }
+    const GnPlan p = plan_groupnorm(prec, sites, C, groups);
+    if (prec == D2S_PREC_BF16) launch_groupnorm_plan<bf16_t>(p, x, g, b, out, sites, C, groups, eps, rows, st);
+    else launch_groupnorm_plan<float>(p, x, g, b, out, sites, C, groups, eps, rows, st);
     D2S_CHECK_LAUNCH();
     return D2S_OK;
 }
@@ -358,6 +374,15 @@ int launch_cache_store(int prec, const void* cur, int sites, int C, int rows, co
     return D2S_OK;
 }
 
+TattPlan plan_temporal_attn(int /*prec*/, int C, int rows) {
+    TattPlan p{(C / 8) % 8 == 0 ? 8 : 4, 1, rows > 1};           // head dim multiple of 8: 16-byte bf16 chunks
+    while (p.lpu * p.ch < C / 8) p.lpu <<= 1;                    // lanes per (site, head) unit: power of two >= head_dim / chunk
+    return p;
+}
+void plan_name(const TattPlan& p, int prec, char* buf, size_t n) {
+    snprintf(buf, n, "temporal_attn_kernel<%s,CH=%d,%s>", prec_tag(prec), p.ch, p.table ? "WinTable" : "WinRow");
+}
+
 int launch_temporal_attn(int prec, const void* cur, const float* ptab, void* out, int sites, int C, int slots, int rows,
                          const AttnRows& tab, hipStream_t st) {
     if (C % 32 || rows < 1 || rows > TA_MAX_ROWS) { set_error("temporal_attn: C % 32 == 0 and 1 <= rows <= 32 required"); return D2S_E_INVALID; }
@@ -368,9 +393,8 @@ int launch_temporal_attn(int prec, const void* cur, const float* ptab, void* out
         }
     }
     const float scale = 1.0f / sqrtf((float)(C / 8));
-    const bool ch8 = (C / 8) % 8 == 0;                 // head dim multiple of 8: 16-byte bf16 chunks
-    int lpu = 1;                                       // lanes per (site, head) unit: power of two >= head_dim / chunk
-    while (lpu * (ch8 ? 8 : 4) < C / 8) lpu <<= 1;
+    const TattPlan p = plan_temporal_attn(prec, C, rows);
+    const int lpu = p.lpu;
     if (lpu * TA_KG > 64) { set_error("temporal_attn: head dim too large"); return D2S_E_UNSUPPORTED; }
     // (per-stream limit: offsets inside ONE ring are 32-bit; rows are reached through 64-bit pointers)
     if ((long)slots * sites * 2 * C >= (1L << 31) || slots < 31) { set_error("temporal_attn: ring too large for 32-bit offsets (or fewer than 31 slots)"); return D2S_E_UNSUPPORTED; }
@@ -380,11 +404,11 @@ int launch_temporal_attn(int prec, const void* cur, const float* ptab, void* out
     auto launch = [&](auto win) {                      // one row: the instance without the per-lane divide and table read
 #define D2S_TATT(TT, CH) hipLaunchKernelGGL((temporal_attn_kernel<TT, CH, decltype(win)>), grid, block, 0, st, (const TT*)cur, ptab, (TT*)out, \
                                             sites, C, slots, scale, lpu, units, win)
-        if (prec == D2S_PREC_BF16) { if (ch8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
-        else { if (ch8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
+        if (prec == D2S_PREC_BF16) { if (p.ch == 8) D2S_TATT(bf16_t, 8); else D2S_TATT(bf16_t, 4); }
+        else { if (p.ch == 8) D2S_TATT(float, 8); else D2S_TATT(float, 4); }
 #undef D2S_TATT
     };
-    if (rows == 1) launch(WinRow{tab.r[0]}); else launch(WinTable{tab});
+    if (p.table) launch(WinTable{tab}); else launch(WinRow{tab.r[0]});
     D2S_CHECK_LAUNCH();
     return D2S_OK;
 }
@@ -405,3 +429,100 @@ int launch_cast_f32(int prec, const float* in, void* out, long n, hipStream_t st
 }
 
 }  // namespace d2s
+
+// ---- test probe ------------------------------------------------------------------------------------
+// One call of a launcher above (or of launch_layernorm) on the caller's device buffers, as they are: nothing is packed, allocated or
+// copied.  Everything the kernel will index is checked against the element counts the caller states before the launcher is reached.
+extern "C" int d2s_temporal_probe(d2s_temporal_probe_params* p, void* stream) {
+    using namespace d2s;
+    D2S_REQUIRE(p && p->struct_size == sizeof(d2s_temporal_probe_params), "d2s_temporal_probe_params.struct_size must be sizeof(d2s_temporal_probe_params)");
+    p->kernel[0] = 0;
+    const int prec = p->precision, rows = p->rows, sites = p->sites, C = p->C, slots = p->slots;
+    D2S_REQUIRE(prec == D2S_PREC_BF16 || prec == D2S_PREC_FP32, "bad precision (bf16 or fp32)");
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t LIM = 1ull << 31;                       // (a b and c d at most 2^31 each: the product stays inside 64 bits)
+    auto holds = [&](uint64_t have, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {      // have >= a b c d, without overflow
+        return a <= LIM && b <= LIM && a * b <= LIM && c <= LIM && d <= LIM && c * d <= LIM && a * b * (c * d) <= have;
+    };
+    int rc = D2S_OK;
+    switch (p->op) {
+    case D2S_TP_GROUPNORM: {
+        D2S_REQUIRE(p->x && p->out && p->gamma && p->beta, "groupnorm: null buffer");
+        D2S_REQUIRE(rows >= 1 && rows <= 65535 && sites >= 1 && C >= 1 && p->groups >= 1 && p->groups <= 65535 && C % p->groups == 0, "groupnorm: bad shape");
+        D2S_REQUIRE(holds(p->x_elems, rows, sites, C, 1) && holds(p->out_elems, rows, sites, C, 1), "groupnorm: x / out smaller than rows * sites * C");
+        D2S_REQUIRE(p->gamma_elems >= (uint64_t)C && p->beta_elems >= (uint64_t)C, "groupnorm: gamma / beta smaller than C");
+        D2S_REQUIRE((long)sites * C < (1L << 31), "groupnorm: sites * C must stay below 2^31");
+        rc = launch_groupnorm(prec, p->x, p->gamma, p->beta, p->out, sites, C, p->groups, p->eps, st, rows);
+        if (rc == D2S_OK) plan_name(plan_groupnorm(prec, sites, C, p->groups), prec, p->kernel, sizeof(p->kernel));
+        break;
+    }
+    case D2S_TP_TEMPORAL_ATTN: {
+        D2S_REQUIRE(p->x && p->out && p->ptab, "temporal_attn: null buffer");
+        D2S_REQUIRE(rows >= 1 && rows <= TA_MAX_ROWS && sites >= 1 && C >= 32 && C % 32 == 0 && slots >= 31 && slots <= 32767, "temporal_attn: bad shape");
+        D2S_REQUIRE(holds(p->x_elems, rows, sites, 3, C) && holds(p->out_elems, rows, sites, C, 1), "temporal_attn: cur / out smaller than rows * sites * 3C / C");
+        D2S_REQUIRE(p->ptab_elems >= (uint64_t)32 * 3 * C, "temporal_attn: ptab smaller than 32 * 3C");
+        AttnRows tab{};
+        for (int r = 0; r < rows; ++r) {
+            D2S_REQUIRE(p->ring[r] && holds(p->ring_elems[r], slots, sites, 2, C), "temporal_attn: a ring is null or smaller than slots * sites * 2C");
+            D2S_REQUIRE((p->Tw[r] == 1 || p->Tw[r] == 32) && p->head[r] >= 0 && p->head[r] < slots && p->store_slot[r] >= -1 && p->store_slot[r] < slots,
+                        "temporal_attn: bad row table");
+            for (int q = 0; q < r; ++q) D2S_REQUIRE(p->ring[q] != p->ring[r], "temporal_attn: two rows share a ring");
+            tab.r[r] = AttnRow{p->ring[r], (int16_t)p->head[r], (int16_t)p->Tw[r], p->store_slot[r]};
+        }
+        rc = launch_temporal_attn(prec, p->x, p->ptab, p->out, sites, C, slots, rows, tab, st);
+        if (rc == D2S_OK) plan_name(plan_temporal_attn(prec, C, rows), prec, p->kernel, sizeof(p->kernel));
+        break;
+    }
+    case D2S_TP_CACHE_STORE: {
+        D2S_REQUIRE(p->x, "cache_store: null buffer");
+        D2S_REQUIRE(rows >= 1 && rows <= TA_MAX_ROWS && sites >= 1 && C >= 1 && slots >= 1 && slots <= 32767, "cache_store: bad shape");
+        D2S_REQUIRE(holds(p->x_elems, rows, sites, 3, C), "cache_store: cur smaller than rows * sites * 3C");
+        CacheRows tab{};
+        bool any = false;
+        for (int r = 0; r < rows; ++r) {
+            D2S_REQUIRE(p->slot0[r] >= 0 && p->nslots[r] >= 0 && p->slot0[r] <= slots && p->nslots[r] <= slots - p->slot0[r], "cache_store: slots outside the ring");
+            D2S_REQUIRE(p->nslots[r] == 0 || (p->ring[r] && holds(p->ring_elems[r], slots, sites, 2, C)), "cache_store: a ring is null or smaller than slots * sites * 2C");
+            tab.r[r] = CacheRow{p->ring[r], p->slot0[r], p->nslots[r]};
+            any = any || p->nslots[r] > 0;
+        }
+        rc = launch_cache_store(prec, p->x, sites, C, rows, tab, st);
+        if (rc == D2S_OK && any) snprintf(p->kernel, sizeof(p->kernel), "cache_store_rows_kernel<%s>", prec_tag(prec));
+        break;
+    }
+    case D2S_TP_GEGLU: {
+        D2S_REQUIRE(p->x && p->out && rows >= 1 && C >= 1, "geglu: null buffer or bad shape");
+        D2S_REQUIRE(holds(p->x_elems, rows, 2, C, 1) && holds(p->out_elems, rows, C, 1, 1), "geglu: u / g smaller than rows * 2C / rows * C");
+        rc = launch_geglu(prec, p->x, p->out, rows, C, st);
+        if (rc == D2S_OK) snprintf(p->kernel, sizeof(p->kernel), "geglu_kernel<%s>", prec_tag(prec));
+        break;
+    }
+    case D2S_TP_CAST_F32: {
+        D2S_REQUIRE(p->x && p->out && p->n >= 1 && p->n <= (1ll << 40), "cast_f32: null buffer or bad count");
+        D2S_REQUIRE(p->x_elems >= (uint64_t)p->n && p->out_elems >= (uint64_t)p->n, "cast_f32: in / out smaller than n");
+        rc = launch_cast_f32(prec, (const float*)p->x, p->out, p->n, st);
+        if (rc == D2S_OK) snprintf(p->kernel, sizeof(p->kernel), "cast_f32_kernel<%s>", prec_tag(prec));
+        break;
+    }
+    case D2S_TP_LAYERNORM: {
+        D2S_REQUIRE(p->x && p->out && p->gamma && p->beta && rows >= 1 && C >= 1, "layernorm: null buffer or bad shape");
+        D2S_REQUIRE(p->rows_per_img >= 0 && p->row_off >= 0 && (p->rows_per_img == 0 || p->img_rows >= p->rows_per_img + p->row_off), "layernorm: bad row map");
+        const uint64_t last_in = p->rows_per_img ? (uint64_t)((rows - 1) / p->rows_per_img) * p->img_rows + (rows - 1) % p->rows_per_img + p->row_off
+                                                 : (uint64_t)rows - 1;
+        D2S_REQUIRE(holds(p->x_elems, last_in + 1, C, 1, 1) && holds(p->out_elems, rows, C, 1, 1), "layernorm: x / out smaller than the rows read / written");
+        D2S_REQUIRE(p->gamma_elems >= (uint64_t)C && p->beta_elems >= (uint64_t)C, "layernorm: gamma / beta smaller than D");
+        D2S_REQUIRE(!(p->qscale < 0.f) && p->qscale == p->qscale, "layernorm: bad qscale");
+        D2S_REQUIRE(((uintptr_t)p->x & 15) == 0 && ((uintptr_t)p->gamma & 15) == 0 && ((uintptr_t)p->beta & 15) == 0 &&
+                    ((uintptr_t)p->out & (p->bx3_out ? 31 : 15)) == 0, "layernorm: buffers must be 16-byte aligned (bf16x3 output: 32)");
+        rc = launch_layernorm(prec, (const float*)p->x, p->gamma, p->beta, p->out, rows, C, p->eps, p->rows_per_img, p->img_rows, p->row_off, st,
+                              p->qscale, p->bx3_out != 0);
+        if (rc == D2S_OK) snprintf(p->kernel, sizeof(p->kernel), "%s", layernorm_kernel_name(layernorm_out_type(prec, p->qscale, p->bx3_out != 0)));
+        break;
+    }
+    default:
+        D2S_REQUIRE(false, "d2s_temporal_probe: unknown op");
+    }
+    const hipError_t err = hipStreamSynchronize(st);
+    if (rc != D2S_OK) { p->kernel[0] = 0; return rc; }
+    D2S_HIP(err);
+    return D2S_OK;
+}

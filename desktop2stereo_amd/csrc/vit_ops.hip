@@ -182,18 +182,30 @@ int launch_cls_rows(const float* cls, const float* pos, float* resid, int B, int
     return D2S_OK;
 }
 
+LnOut layernorm_out_type(int prec, float fp8_qscale, bool bx3_out) {
+    if (bx3_out) return LN_OUT_BX3;                 // bf16x3 engines: the unit format, so the consuming linear's A operand can travel by LDS-DMA
+    if (fp8_qscale > 0.f) return LN_OUT_E4M3;       // e4m3 output for an fp8 linear: out = sat(LN(x) * qscale)
+    return prec == D2S_PREC_BF16 ? LN_OUT_BF16 : LN_OUT_F32;
+}
+const char* layernorm_kernel_name(LnOut t) {
+    static const char* const names[] = {"layernorm_kernel<f32>", "layernorm_kernel<bf16>", "layernorm_kernel<bx3>", "layernorm_kernel<e4m3>"};
+    return names[t];
+}
+
 int launch_layernorm(int prec, const float* x, const float* g, const float* b, void* out, int rows_out, int D, float eps,
                      int rows_per_img, int img_rows, int row_off, hipStream_t st, float fp8_qscale, bool bx3_out) {
     if (D > 1024 || (D & 3)) { set_error("layernorm: D must be a multiple of 4 and <= 1024"); return D2S_E_UNSUPPORTED; }
     dim3 grid(cdiv(rows_out, 4)), block(256);
-    if (bx3_out) {              // bf16x3 engines: the unit format, so the consuming linear's A operand can travel by LDS-DMA
-        if (prec != D2S_PREC_FP32 || (D & 7)) { set_error("layernorm: bf16x3 output needs the fp32 engine and D % 8 == 0"); return D2S_E_UNSUPPORTED; }
-        hipLaunchKernelGGL(layernorm_kernel<bx3_t>, grid, block, 0, st, x, g, b, (bx3_t*)out, rows_out, D, eps, rows_per_img, img_rows, row_off, 0.f);
-    } else if (fp8_qscale > 0.f)       // e4m3 output for an fp8 linear: out = sat(LN(x) * qscale)
-        hipLaunchKernelGGL(layernorm_kernel<fp8_t>, grid, block, 0, st, x, g, b, (fp8_t*)out, rows_out, D, eps, rows_per_img, img_rows, row_off, fp8_qscale);
-    else
-        DISPATCH_T(prec, hipLaunchKernelGGL(layernorm_kernel<bf16_t>, grid, block, 0, st, x, g, b, (bf16_t*)out, rows_out, D, eps, rows_per_img, img_rows, row_off, 0.f),
-                         hipLaunchKernelGGL(layernorm_kernel<float>, grid, block, 0, st, x, g, b, (float*)out, rows_out, D, eps, rows_per_img, img_rows, row_off, 0.f));
+    const LnOut ot = layernorm_out_type(prec, fp8_qscale, bx3_out);
+    if (ot == LN_OUT_BX3 && (prec != D2S_PREC_FP32 || (D & 7))) { set_error("layernorm: bf16x3 output needs the fp32 engine and D % 8 == 0"); return D2S_E_UNSUPPORTED; }
+#define D2S_LN(TT, QS) hipLaunchKernelGGL(layernorm_kernel<TT>, grid, block, 0, st, x, g, b, (TT*)out, rows_out, D, eps, rows_per_img, img_rows, row_off, QS)
+    switch (ot) {
+        case LN_OUT_BX3: D2S_LN(bx3_t, 0.f); break;
+        case LN_OUT_E4M3: D2S_LN(fp8_t, fp8_qscale); break;
+        case LN_OUT_BF16: D2S_LN(bf16_t, 0.f); break;
+        case LN_OUT_F32: D2S_LN(float, 0.f); break;
+    }
+#undef D2S_LN
     D2S_CHECK_LAUNCH();
     return D2S_OK;
 }

@@ -960,3 +960,44 @@ def attention_probe_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precis
     with _on(q.device) as st:
         check(_lib.load().d2s_attention_probe_ex(C.byref(p), st), "d2s_attention_probe_ex")
     return {"out": guard[1:B * N + 1], "guard": guard, "kernel": p.kernel.decode()}
+
+
+def temporal_probe(op: str, precision: str, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, rows: int = 0, sites: int = 0,
+                   channels: int = 0, groups: int = 32, slots: int = 31, eps: float = 1e-6, gamma: Optional[torch.Tensor] = None,
+                   beta: Optional[torch.Tensor] = None, ptab: Optional[torch.Tensor] = None, rings=(), head=(), Tw=(), store_slot=(),
+                   slot0=(), nslots=(), n: int = 0, qscale: float = 0.0, bx3_out: bool = False, row_map=(0, 0, 0)) -> str:
+    """One launch of a temporal-module or LayerNorm launcher of the engine (test probe, include/d2s.h d2s_temporal_probe).  op:
+    "groupnorm" | "temporal_attn" | "cache_store" | "geglu" | "cast_f32" | "layernorm"; precision "bf16" | "fp32" (the engine class).
+    The tensors are device buffers ALREADY in the kernel's storage type (torch.bfloat16 = raw bf16 bits) and are used in place -- views
+    into larger guarded buffers are fine; the element counts the library checks against are what each tensor holds from its first
+    element (numel of a contiguous tensor).  channels: C of the header (GEGLU: the output width, LayerNorm: D).  rings: one tensor per row; row_map = (rows_per_img, img_rows, row_off) of LayerNorm.
+    Returns the name of the kernel that ran ("" when cache_store had nothing to store); raises D2SError where the library refuses."""
+    _need_cuda(x, "x")
+    p = _lib.TemporalProbeParams()
+    p.struct_size = C.sizeof(_lib.TemporalProbeParams)
+    p.op = _lib.TEMPORAL_OPS[op]
+    p.precision = {"bf16": PREC_BF16, "fp32": PREC_FP32}[precision]
+    p.rows, p.sites, p.C, p.groups, p.slots = int(rows), int(sites), int(channels), int(groups), int(slots)
+    p.eps, p.qscale, p.bx3_out, p.n = float(eps), float(qscale), int(bool(bx3_out)), int(n)
+    p.rows_per_img, p.img_rows, p.row_off = (int(v) for v in row_map)
+
+    def buf(t):
+        if t is None:
+            return None, 0
+        if not t.is_contiguous():
+            raise ValueError("temporal_probe: tensors must be contiguous")
+        return _ptr(t), t.numel()
+    (p.x, p.x_elems), (p.out, p.out_elems) = buf(x), buf(out)
+    (p.gamma, p.gamma_elems), (p.beta, p.beta_elems), (p.ptab, p.ptab_elems) = buf(gamma), buf(beta), buf(ptab)
+    for r, t in enumerate(rings):
+        _need_cuda(t, "ring")
+        if not t.is_contiguous():
+            raise ValueError("temporal_probe: tensors must be contiguous")
+        p.ring[r], p.ring_elems[r] = t.data_ptr(), t.numel()
+    for name, vals in (("head", head), ("Tw", Tw), ("store_slot", store_slot), ("slot0", slot0), ("nslots", nslots)):
+        arr = getattr(p, name)
+        for r, v in enumerate(vals):
+            arr[r] = int(v)
+    with _on(x.device) as st:
+        check(_lib.load().d2s_temporal_probe(C.byref(p), st), "d2s_temporal_probe")
+    return p.kernel.decode()

@@ -636,6 +636,47 @@ typedef struct d2s_linear_probe_params {
 } d2s_linear_probe_params;
 int d2s_linear_probe(d2s_linear_probe_params* p, void* stream);
 
+/* Stand-alone probe of the temporal-module and LayerNorm launchers (tests; d2s_version() >= 117): one call of the launcher the engine's
+ * run_temporal / encoder calls, on device operands ALREADY in the kernel's storage type (bf16 = raw bf16 bits, outputs raw: bf16x3 unit
+ * words, e4m3 bytes).  The probe packs nothing and allocates nothing.  Before anything is launched every size and count is checked
+ * against the element counts the caller states for each buffer; a malformed case is an error return.  Reports the kernel it launched. */
+enum {
+    D2S_TP_GROUPNORM = 0,      /* launch_groupnorm: x, out [rows][sites, C], gamma / beta [C], groups, eps */
+    D2S_TP_TEMPORAL_ATTN = 1,  /* launch_temporal_attn: x = cur [rows][sites][3C] (k' | v' | q'), ptab float [32][3C], out [rows][sites][C],
+                                  row r: ring[r] [slots][sites][2C], head[r], Tw[r] (1 | 32), store_slot[r] (-1: none) */
+    D2S_TP_CACHE_STORE = 2,    /* launch_cache_store: x = cur; row r: ring[r], slot0[r], nslots[r] (slot0 + nslots <= slots); kernel = ""
+                                  when no row has a slot to fill (nothing is launched) */
+    D2S_TP_GEGLU = 3,          /* launch_geglu: x = u [rows, 2 C], out [rows, C] = u[:, :C] * gelu(u[:, C:])   (C = the engine's 4 C) */
+    D2S_TP_CAST_F32 = 4,       /* launch_cast_f32: x float [n] -> out [n] of the precision's type */
+    D2S_TP_LAYERNORM = 5       /* launch_layernorm: x float, gamma / beta [C], out [rows, C] (C = D); rows_per_img > 0: output row r reads
+                                  input row (r / rows_per_img) img_rows + r % rows_per_img + row_off; qscale > 0: e4m3 output;
+                                  bx3_out: bf16x3 units (out 32-byte aligned) */
+};
+typedef struct d2s_temporal_probe_params {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_temporal_probe_params) */
+    int32_t op;                /* D2S_TP_* */
+    int32_t precision;         /* D2S_PREC_BF16 / D2S_PREC_FP32: the engine class, i.e. the storage type of x and out (see the ops) */
+    int32_t rows, sites, C;    /* batch rows (LAYERNORM, GEGLU: matrix rows), sites per row, channels */
+    int32_t groups, slots;     /* GROUPNORM: groups; TEMPORAL_ATTN / CACHE_STORE: slots of a ring (the engine: 31) */
+    float   eps;               /* GROUPNORM, LAYERNORM */
+    float   qscale;            /* LAYERNORM: > 0 = e4m3 output sat(LN(x) * qscale) */
+    int32_t bx3_out;           /* LAYERNORM: 1 = bf16x3 unit output */
+    int32_t rows_per_img, img_rows, row_off;   /* LAYERNORM row map (0, 0, 0: plain) */
+    int64_t n;                 /* CAST_F32: elements */
+    const void* x;             /* the input (device) */
+    void* out;                 /* the output (device); CACHE_STORE: unused */
+    const float* gamma;        /* GROUPNORM, LAYERNORM */
+    const float* beta;
+    const float* ptab;         /* TEMPORAL_ATTN */
+    uint64_t x_elems, out_elems, gamma_elems, beta_elems, ptab_elems;   /* elements each buffer holds, from the pointer given */
+    void* ring[D2S_MAX_STREAMS];            /* per row (device), in / out */
+    uint64_t ring_elems[D2S_MAX_STREAMS];
+    int32_t head[D2S_MAX_STREAMS], Tw[D2S_MAX_STREAMS], store_slot[D2S_MAX_STREAMS];   /* TEMPORAL_ATTN */
+    int32_t slot0[D2S_MAX_STREAMS], nslots[D2S_MAX_STREAMS];                           /* CACHE_STORE */
+    char kernel[128];          /* out: the kernel that ran, e.g. "groupnorm_reg_kernel<bf16,CPG=8,RPT=2>", "temporal_attn_kernel<f32,CH=4,WinRow>" */
+} d2s_temporal_probe_params;
+int d2s_temporal_probe(d2s_temporal_probe_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
