@@ -109,6 +109,23 @@ class TemporalProbeParams(C.Structure):
                 ("slot0", C.c_int32 * 32), ("nslots", C.c_int32 * 32), ("kernel", C.c_char * 128)]
 
 
+class WarpPlanResult(C.Structure):
+    """d2s_warp_plan_result (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("gather", C.c_int32), ("direct", C.c_int32), ("nc", C.c_int32), ("ntx", C.c_int32),
+                ("wpc", C.c_int32), ("rpw", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("grid", C.c_uint32),
+                ("waves", C.c_int64), ("kernel", C.c_char * 64)]
+
+
+class PrepatchProbeParams(C.Structure):
+    """d2s_prepatch_probe_params (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("precision", C.c_int32), ("fmt", C.c_int32), ("batch", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("decim_stride", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("p", C.c_int32), ("Kp", C.c_int32),
+                ("N", C.c_int32), ("D", C.c_int32), ("reserved", C.c_int32), ("pre", C.POINTER(PreParams)), ("frames", C.c_void_p),
+                ("A", C.c_void_p), ("cls", C.c_void_p), ("pos", C.c_void_p), ("resid", C.c_void_p),
+                ("frames_elems", C.c_uint64), ("A_elems", C.c_uint64), ("cls_elems", C.c_uint64), ("pos_elems", C.c_uint64),
+                ("resid_elems", C.c_uint64), ("kernel", C.c_char * 64)]
+
+
 TEMPORAL_OPS = {"groupnorm": 0, "temporal_attn": 1, "cache_store": 2, "geglu": 3, "cast_f32": 4, "layernorm": 5}      # D2S_TP_*
 
 LINEAR_SITES = {"patch": 0, "qkv": 1, "proj": 2, "fc1": 3, "fc2": 4, "neck_proj": 5, "neck_resize": 6, "tm_proj_in": 7,    # D2S_LIN_*
@@ -200,6 +217,9 @@ SYMBOLS = {
     "d2s_conv3_probe": (C.c_int, [C.POINTER(Conv3ProbeParams), _P]),
     "d2s_linear_probe": (C.c_int, [C.POINTER(LinearProbeParams), _P]),
     "d2s_temporal_probe": (C.c_int, [C.POINTER(TemporalProbeParams), _P]),
+    "d2s_warp_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SbsParams), C.c_int, C.c_int, C.c_int,
+                                C.POINTER(WarpPlanResult)]),
+    "d2s_preprocess_patches_probe": (C.c_int, [C.POINTER(PrepatchProbeParams), _P]),
 }
 
 _lib = None

@@ -543,7 +543,7 @@ stereo_warp_gather(const uint8_t* __restrict__ rgb, const float* __restrict__ de
     float tap_w0 = 0.f, tap_w1 = 0.f;
     auto tap_fill = [&](int fb, int fy) {                   // (fb, fy): frame / row of the band's row 64 q
         int yl = fy + lane, bl = fb;
-        if (yl >= g.H) { yl -= g.H; ++bl; }                 // (a band is shorter than a frame)
+        if (yl >= g.H) { yl -= g.H; ++bl; }                 // (a band is at most a frame long: plan_warp caps rpw at H)
         if (bl >= B) { bl = B - 1; yl = g.H - 1; }
         const Tap t = linear_tap(yl, g.dsy, g.dh, false);
         tap_o0 = (uint32_t)bl * dplane + (uint32_t)t.i0 * drow_b; tap_o1 = (uint32_t)bl * dplane + (uint32_t)t.i1 * drow_b;
@@ -891,17 +891,95 @@ extern "C" int d2s_sbs_shape(int H, int W, const d2s_sbs_params* p, int* out_h, 
     return D2S_OK;
 }
 
+// Everything d2s_make_sbs decides, stated once on the host (d2s_warp_plan reports it; the tests pin it).  The gather kernel (round 6:
+// wave-private LDS window, fixed-point blend) serves every display mode for u8 HWC frames in and out without padding, W % 4 == 0, when a
+// lane's 4 pixels touch at most 3 (3 dw < W: model-resolution depth under 1080p and larger frames) or 4 (3 dw < 2 W: 720p) depth columns,
+// and when the depth map has the frame's size (the drop-in make_sbs(rgb, depth[H, W]) surface); everything else -- other formats, padding,
+// W % 4 != 0, a depth grid between 2/3 of the frame's width and the frame's width, Half-TAB with odd H -- takes the generic kernel.
+// D2S_WARP_GATHER=0: generic too (tests).
+struct WarpPlan {
+    bool gather = false, direct = false;
+    int nc = 0;                    // depth columns per lane (gather)
+    int ntx = 0;                   // 256-pixel column tiles
+    long wpc = 0, rpw = 0;         // resident waves per CU the grid is cut for; source rows per wave (even for Half-TAB)
+    long waves = 0;
+    unsigned grid = 0;             // blocks of 256 threads
+    char name[64] = {0};
+};
+static int plan_warp(int rgb_fmt, int out_fmt, int dh, int dw, int batch, const WarpGeom& g, uintptr_t rgb_align, uintptr_t out_align, WarpPlan& pl) {
+    static const char* const fmt_name[4] = {"U8_HWC", "F32_CHW", "F32_HWC", "U8_CHW"};
+    static const char* const mode_name[4] = {"HALF_SBS", "FULL_SBS", "HALF_TAB", "FULL_TAB"};
+    if (rgb_fmt != D2S_FMT_U8_HWC && rgb_fmt != D2S_FMT_U8_CHW && rgb_fmt != D2S_FMT_F32_CHW) return D2S_E_UNSUPPORTED;
+    const int H = g.H, W = g.W;
+    pl = WarpPlan();
+    bool nopad = (g.Hp == H && g.Wp == W);
+    bool fast_ok = rgb_fmt == D2S_FMT_U8_HWC && out_fmt == D2S_FMT_U8_HWC && nopad && ((long)batch * H * cdiv(W, 256) < (1L << 30)) &&
+                   (W % 4 == 0) && dw <= W && dh <= H && (rgb_align % 4 == 0) && (out_align % 4 == 0) &&
+                   ((long)H * W * 3 % 4 == 0);
+    if (fast_ok && g.mode == D2S_MODE_HALF_TAB && (H % 2 != 0)) fast_ok = false;
+    static EnvInt gather_env{"D2S_WARP_GATHER", 1};
+    pl.direct = dw == W && dh == H;
+    pl.nc = pl.direct ? 4 : (3L * dw < W ? 3 : (3L * dw < 2L * W ? 4 : 0));
+    if (fast_ok && gather_env.get() && pl.nc && dw >= pl.nc && W >= 8 && W < 16384 && (long)batch * dh * dw * 4 < (1L << 32)) {
+        pl.gather = true;
+        pl.ntx = cdiv(W, 256);
+        const long rows = (long)H * batch;
+        // resident waves per CU the grid is cut for: 32 (tuned at batch 32); a launch of <= 12 288 row tiles (one 1080p frame: 8 640) is cut
+        // for 12 -- three rows per wave instead of two amortise the per-wave set-up: 10.5 -> 9.7 us at 1080p batch 1 (profiles/r6_01)
+        static EnvInt wpc_env{"D2S_WARP_WPC", 0};
+        pl.wpc = wpc_env.get() > 0 ? wpc_env.get() : (rows * pl.ntx <= 12288 ? 12 : 32);
+        long rpw = cdiv(rows * (long)pl.ntx, 256L * pl.wpc);
+        if (g.mode == D2S_MODE_HALF_TAB) rpw += rpw & 1;           // whole row pairs (H is even)
+        // a band is at most one frame long: the kernel's tap table (tap_fill) wraps a band row into the NEXT frame once, so a band of more
+        // than H + 1 rows would take the depth rows of its third frame from the second.  Only thousands of frames of a few rows each get
+        // here (rows ntx > 256 wpc H); no video launch does.  (Half-TAB: H is even, so the cap keeps whole row pairs.)
+        if (rpw > H) rpw = H;
+        pl.rpw = rpw;
+        pl.waves = cdiv(rows, rpw) * pl.ntx;
+        pl.grid = (unsigned)cdiv(pl.waves, 4L);
+        snprintf(pl.name, sizeof(pl.name), "stereo_warp_gather<%s,NC=%d,DIRECT=%d>", mode_name[g.mode], pl.direct ? 4 : pl.nc, pl.direct ? 1 : 0);
+        return D2S_OK;
+    }
+    pl.nc = 0; pl.direct = false;
+    pl.waves = cdiv((long)batch * g.out_h * g.out_w, 64L);
+    pl.grid = (unsigned)cdiv((long)batch * g.out_h * g.out_w, 256L);
+    snprintf(pl.name, sizeof(pl.name), "stereo_warp_generic<%s,%s>", fmt_name[rgb_fmt], fmt_name[out_fmt]);
+    return D2S_OK;
+}
+
 template <int IN_FMT>
 static void launch_generic(const void* rgb, const float* depth, void* out, int out_fmt, int batch,
-                           const WarpGeom& g, hipStream_t st) {
-    long total = (long)batch * g.out_h * g.out_w;
-    dim3 grid(cdiv(total, 256)), block(256);
+                           const WarpGeom& g, const WarpPlan& pl, hipStream_t st) {
+    dim3 grid(pl.grid), block(256);
     if (out_fmt == D2S_FMT_U8_HWC)
         hipLaunchKernelGGL((stereo_warp_generic<IN_FMT, D2S_FMT_U8_HWC>), grid, block, 0, st, rgb, depth, out, batch, g);
     else if (out_fmt == D2S_FMT_F32_HWC)
         hipLaunchKernelGGL((stereo_warp_generic<IN_FMT, D2S_FMT_F32_HWC>), grid, block, 0, st, rgb, depth, out, batch, g);
     else
         hipLaunchKernelGGL((stereo_warp_generic<IN_FMT, D2S_FMT_F32_CHW>), grid, block, 0, st, rgb, depth, out, batch, g);
+}
+
+static void launch_warp(const WarpPlan& pl, const void* rgb, int rgb_fmt, const float* depth, int batch, const WarpGeom& g, void* out, int out_fmt,
+                        hipStream_t st) {
+    if (pl.gather) {
+        const dim3 grid(pl.grid), block(256);
+        const int ntx = pl.ntx;
+        // register budget: 128 VGPRs (4 waves per SIMD): two window sets in flight + the row loop without a spill.  At 96 (5 waves) the Full-TAB /
+        // Half modes reload loop constants from scratch every row -- a scratch reload queues behind the window prefetch in the same in-order
+        // vmcnt -- and Full-SBS gains nothing (155-159 us against 153-158; profiles/r6_01_warp_gather.md)
+#define WG_LAUNCH_N(MODE_, NC_, DIR_) hipLaunchKernelGGL((stereo_warp_gather<MODE_, NC_, DIR_>), grid, block, 0, st, (const uint8_t*)rgb, depth, (uint8_t*)out, batch, g, (int)pl.rpw, ntx)
+#define WG_LAUNCH(MODE_) { if (pl.direct) WG_LAUNCH_N(MODE_, 4, true); else if (pl.nc == 3) WG_LAUNCH_N(MODE_, 3, false); else WG_LAUNCH_N(MODE_, 4, false); }
+        if (g.mode == D2S_MODE_FULL_SBS) WG_LAUNCH(D2S_MODE_FULL_SBS)
+        else if (g.mode == D2S_MODE_FULL_TAB) WG_LAUNCH(D2S_MODE_FULL_TAB)
+        else if (g.mode == D2S_MODE_HALF_SBS) WG_LAUNCH(D2S_MODE_HALF_SBS)
+        else WG_LAUNCH(D2S_MODE_HALF_TAB)
+#undef WG_LAUNCH
+#undef WG_LAUNCH_N
+        return;
+    }
+    if (rgb_fmt == D2S_FMT_U8_HWC) launch_generic<D2S_FMT_U8_HWC>(rgb, depth, out, out_fmt, batch, g, pl, st);
+    else if (rgb_fmt == D2S_FMT_U8_CHW) launch_generic<D2S_FMT_U8_CHW>(rgb, depth, out, out_fmt, batch, g, pl, st);
+    else launch_generic<D2S_FMT_F32_CHW>(rgb, depth, out, out_fmt, batch, g, pl, st);
 }
 
 extern "C" int d2s_make_sbs(const void* rgb, int rgb_fmt, const float* depth, int dh, int dw, int batch, int H, int W,
@@ -911,50 +989,48 @@ extern "C" int d2s_make_sbs(const void* rgb, int rgb_fmt, const float* depth, in
     D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC || out_fmt == D2S_FMT_F32_CHW, "bad out_fmt");
     WarpGeom g;
     if (make_geom(H, W, dh, dw, p, g) != D2S_OK) { set_error("d2s_make_sbs: bad display_mode"); return D2S_E_INVALID; }
-    hipStream_t st = (hipStream_t)stream;
-    bool nopad = (g.Hp == H && g.Wp == W);
-    bool fast_ok = rgb_fmt == D2S_FMT_U8_HWC && out_fmt == D2S_FMT_U8_HWC && nopad && ((long)batch * H * cdiv(W, 256) < (1L << 30)) &&
-                   (W % 4 == 0) && dw <= W && dh <= H && ((uintptr_t)rgb % 4 == 0) && ((uintptr_t)out % 4 == 0) &&
-                   ((long)H * W * 3 % 4 == 0);
-    if (fast_ok && g.mode == D2S_MODE_HALF_TAB && (H % 2 != 0)) fast_ok = false;
-    // round 6: the gather kernel (wave-private LDS window, fixed-point blend) serves every display mode when a lane's 4 pixels touch at most
-    // 3 (3 dw < W: model-resolution depth under 1080p and larger frames) or 4 (3 dw < 2 W: 720p) depth columns, and when the depth map
-    // has the frame's size (the drop-in make_sbs(rgb, depth[H, W]) surface); everything else -- other formats, padding, W % 4 != 0, a depth
-    // grid between 2/3 of the frame's width and the frame's width -- takes the generic kernel.  D2S_WARP_GATHER=0: generic too (tests)
-    static EnvInt gather_env{"D2S_WARP_GATHER", 1};
-    const bool direct = dw == W && dh == H;
-    const int nc = direct ? 4 : (3L * dw < W ? 3 : (3L * dw < 2L * W ? 4 : 0));
-    if (fast_ok && gather_env.get() && nc && dw >= nc && W >= 8 && W < 16384 && (long)batch * dh * dw * 4 < (1L << 32)) {
-        const int ntx = cdiv(W, 256);
-        const long rows = (long)H * batch;
-        // resident waves per CU the grid is cut for: 32 (tuned at batch 32); a launch of <= 12 288 row tiles (one 1080p frame: 8 640) is cut
-        // for 12 -- three rows per wave instead of two amortise the per-wave set-up: 10.5 -> 9.7 us at 1080p batch 1 (profiles/r6_01)
-        static EnvInt wpc_env{"D2S_WARP_WPC", 0};
-        const long wpc = wpc_env.get() > 0 ? wpc_env.get() : (rows * ntx <= 12288 ? 12 : 32);
-        long rpw = cdiv(rows * ntx, 256L * wpc);
-        if (g.mode == D2S_MODE_HALF_TAB) rpw += rpw & 1;           // whole row pairs (H is even)
-        const long waves = cdiv(rows, rpw) * ntx;
-        const dim3 grid((unsigned)cdiv(waves, 4L)), block(256);
-        // register budget: 128 VGPRs (4 waves per SIMD): two window sets in flight + the row loop without a spill.  At 96 (5 waves) the Full-TAB /
-        // Half modes reload loop constants from scratch every row -- a scratch reload queues behind the window prefetch in the same in-order
-        // vmcnt -- and Full-SBS gains nothing (155-159 us against 153-158; profiles/r6_01_warp_gather.md)
-#define WG_LAUNCH_N(MODE_, NC_, DIR_) hipLaunchKernelGGL((stereo_warp_gather<MODE_, NC_, DIR_>), grid, block, 0, st, (const uint8_t*)rgb, depth, (uint8_t*)out, batch, g, (int)rpw, ntx)
-#define WG_LAUNCH(MODE_) { if (direct) WG_LAUNCH_N(MODE_, 4, true); else if (nc == 3) WG_LAUNCH_N(MODE_, 3, false); else WG_LAUNCH_N(MODE_, 4, false); }
-        if (g.mode == D2S_MODE_FULL_SBS) WG_LAUNCH(D2S_MODE_FULL_SBS)
-        else if (g.mode == D2S_MODE_FULL_TAB) WG_LAUNCH(D2S_MODE_FULL_TAB)
-        else if (g.mode == D2S_MODE_HALF_SBS) WG_LAUNCH(D2S_MODE_HALF_SBS)
-        else WG_LAUNCH(D2S_MODE_HALF_TAB)
-#undef WG_LAUNCH
-#undef WG_LAUNCH_N
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-    {
-        if (rgb_fmt == D2S_FMT_U8_HWC) launch_generic<D2S_FMT_U8_HWC>(rgb, depth, out, out_fmt, batch, g, st);
-        else if (rgb_fmt == D2S_FMT_U8_CHW) launch_generic<D2S_FMT_U8_CHW>(rgb, depth, out, out_fmt, batch, g, st);
-        else if (rgb_fmt == D2S_FMT_F32_CHW) launch_generic<D2S_FMT_F32_CHW>(rgb, depth, out, out_fmt, batch, g, st);
-        else { set_error("d2s_make_sbs: unsupported rgb_fmt"); return D2S_E_UNSUPPORTED; }
-    }
+    WarpPlan pl;
+    if (plan_warp(rgb_fmt, out_fmt, dh, dw, batch, g, (uintptr_t)rgb, (uintptr_t)out, pl) != D2S_OK) { set_error("d2s_make_sbs: unsupported rgb_fmt"); return D2S_E_UNSUPPORTED; }
+    launch_warp(pl, rgb, rgb_fmt, depth, batch, g, out, out_fmt, (hipStream_t)stream);
     D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+extern "C" int d2s_warp_plan(int rgb_fmt, int dh, int dw, int batch, int H, int W, const d2s_sbs_params* p, int out_fmt,
+                             int rgb_align, int out_align, d2s_warp_plan_result* res) {
+    D2S_REQUIRE(p && res, "null pointer");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_warp_plan_result), "d2s_warp_plan_result.struct_size must be sizeof(d2s_warp_plan_result)");
+    D2S_REQUIRE(batch > 0 && H > 0 && W > 0 && dh > 0 && dw > 0, "bad shape");
+    D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC || out_fmt == D2S_FMT_F32_CHW, "bad out_fmt");
+    D2S_REQUIRE(rgb_align > 0 && out_align > 0, "alignments are positive byte counts");
+    WarpGeom g;
+    if (make_geom(H, W, dh, dw, p, g) != D2S_OK) { set_error("d2s_warp_plan: bad display_mode"); return D2S_E_INVALID; }
+    WarpPlan pl;
+    if (plan_warp(rgb_fmt, out_fmt, dh, dw, batch, g, (uintptr_t)rgb_align, (uintptr_t)out_align, pl) != D2S_OK) { set_error("d2s_warp_plan: unsupported rgb_fmt"); return D2S_E_UNSUPPORTED; }
+    res->gather = pl.gather; res->direct = pl.direct; res->nc = pl.nc; res->ntx = pl.ntx;
+    res->wpc = (int32_t)pl.wpc; res->rpw = (int32_t)pl.rpw; res->waves = pl.waves; res->grid = pl.grid;
+    res->out_h = g.out_h; res->out_w = g.out_w;
+    snprintf(res->kernel, sizeof(res->kernel), "%s", pl.name);
+    return D2S_OK;
+}
+
+// Test probe of launch_preprocess_patches (d2s_pipeline's fused pre-process + patchify) on caller-owned device buffers
+extern "C" int d2s_preprocess_patches_probe(d2s_prepatch_probe_params* q, void* stream) {
+    D2S_REQUIRE(q && q->struct_size == sizeof(d2s_prepatch_probe_params), "d2s_prepatch_probe_params.struct_size must be sizeof(d2s_prepatch_probe_params)");
+    q->kernel[0] = 0;
+    D2S_REQUIRE(q->batch > 0 && q->H > 0 && q->W > 0 && q->h > 0 && q->w > 0 && q->p > 0 && q->Kp > 0 && q->decim_stride >= 1 && q->D > 0, "bad shape");
+    D2S_REQUIRE(q->frames && q->A && q->resid && (q->pos || !q->cls), "null pointer");
+    D2S_REQUIRE(q->h % q->p == 0 && q->w % q->p == 0, "h, w must be multiples of p");
+    const uint64_t npatch = (uint64_t)(q->h / q->p) * (uint64_t)(q->w / q->p);
+    D2S_REQUIRE((uint64_t)q->N >= npatch + 1, "N must hold the cls row and every patch row");
+    const uint64_t px = (uint64_t)q->batch * q->H * q->W * 3;
+    D2S_REQUIRE(q->frames_elems >= px, "frames buffer too small");
+    D2S_REQUIRE(q->A_elems >= (uint64_t)q->batch * npatch * (uint64_t)q->Kp, "A buffer too small");
+    D2S_REQUIRE(!q->cls || (q->pos_elems >= (uint64_t)q->D && q->cls_elems >= (uint64_t)q->D), "cls / pos buffer too small");
+    D2S_REQUIRE(q->resid_elems >= (uint64_t)q->batch * (uint64_t)q->N * (uint64_t)q->D, "resid buffer too small");
+    const int rc = launch_preprocess_patches(q->precision, q->frames, q->fmt, q->batch, q->H, q->W, q->decim_stride, q->pre, q->A, q->h, q->w, q->p, q->Kp,
+                                             q->cls, q->pos, q->resid, q->N, q->D, (hipStream_t)stream);
+    if (rc != D2S_OK) return rc;
+    snprintf(q->kernel, sizeof(q->kernel), "preprocess_patch_kernel<U8_HWC,%s>", q->precision == D2S_PREC_BF16 ? "bf16" : "float");
     return D2S_OK;
 }

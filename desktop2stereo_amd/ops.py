@@ -1001,3 +1001,69 @@ def temporal_probe(op: str, precision: str, x: torch.Tensor, out: Optional[torch
     with _on(x.device) as st:
         check(_lib.load().d2s_temporal_probe(C.byref(p), st), "d2s_temporal_probe")
     return p.kernel.decode()
+
+
+def preprocess_to(frames: torch.Tensor, out: torch.Tensor, decim_stride: int = 1, pre: Optional[PreParams] = None) -> torch.Tensor:
+    """d2s_preprocess with the C-ABI's own arguments: `out` float32 [B,3,h,w] caller-allocated (a view into a larger buffer is fine), explicit
+    decimation stride and d2s_pre_params (None: ImageNet mean / std, bilinear)."""
+    _need_cuda(frames, "frames")
+    _same_device(frames, out, "preprocess_to")
+    fmt, B, H, W = _frame_fmt(frames)
+    if not (frames.is_contiguous() and out.is_contiguous()) or out.dtype != torch.float32 or out.dim() != 4 or out.shape[:2] != (B, 3):
+        raise ValueError("preprocess_to: frames / out must be contiguous, out float32 [B,3,h,w]")
+    with _on(frames.device) as st:
+        check(_lib.load().d2s_preprocess(_ptr(frames), fmt, B, H, W, _ptr(out), out.shape[2], out.shape[3], int(decim_stride),
+                                         C.byref(pre) if pre is not None else None, st), "d2s_preprocess")
+    return out
+
+
+def upsample_depth_to(depth: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """d2s_upsample_depth into a caller-allocated float32 [B,H,W] (a view into a larger buffer is fine)."""
+    _need_cuda(depth, "depth")
+    _same_device(depth, out, "upsample_depth_to")
+    if not (depth.is_contiguous() and out.is_contiguous()) or depth.dtype != torch.float32 or out.dtype != torch.float32 or depth.dim() != 3 \
+            or out.dim() != 3 or out.shape[0] != depth.shape[0]:
+        raise ValueError("upsample_depth_to: depth / out must be contiguous float32 [B,h,w] / [B,H,W]")
+    with _on(depth.device) as st:
+        check(_lib.load().d2s_upsample_depth(_ptr(depth), depth.shape[0], depth.shape[1], depth.shape[2], _ptr(out), out.shape[1], out.shape[2], st),
+              "d2s_upsample_depth")
+    return out
+
+
+def warp_plan(rgb_fmt: int, dh: int, dw: int, batch: int, H: int, W: int, sp: SbsParams, out_fmt: int = FMT_U8_HWC, rgb_align: int = 256,
+              out_align: int = 256) -> dict:
+    """What d2s_make_sbs would launch for these arguments (include/d2s.h d2s_warp_plan; host code, no GPU): kernel name, rpw, ntx, wpc,
+    waves, grid."""
+    r = _lib.WarpPlanResult()
+    r.struct_size = C.sizeof(_lib.WarpPlanResult)
+    check(_lib.load().d2s_warp_plan(int(rgb_fmt), int(dh), int(dw), int(batch), int(H), int(W), C.byref(sp), int(out_fmt), int(rgb_align),
+                                    int(out_align), C.byref(r)), "d2s_warp_plan")
+    return {"kernel": r.kernel.decode(), "gather": bool(r.gather), "direct": bool(r.direct), "nc": r.nc, "ntx": r.ntx, "wpc": r.wpc, "rpw": r.rpw,
+            "waves": r.waves, "grid": r.grid, "out_h": r.out_h, "out_w": r.out_w}
+
+
+def preprocess_patches_probe(precision: str, frames: torch.Tensor, A: torch.Tensor, resid: torch.Tensor, *, h: int, w: int, p: int, Kp: int,
+                             N: int, D: int, cls: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None, decim_stride: int = 1,
+                             pre: Optional[PreParams] = None, fmt: Optional[int] = None) -> str:
+    """One launch of d2s_pipeline's fused pre-process + patchify (test probe, include/d2s.h d2s_preprocess_patches_probe) on caller-owned
+    device buffers, used in place: frames [B,H,W,3] uint8 (fmt overrides the format the library is told), A the patch rows (torch.bfloat16
+    / float32), resid float32 [B,N,D].  Returns the kernel's name; raises D2SError where the library refuses (status in the message)."""
+    _need_cuda(frames, "frames")
+    q = _lib.PrepatchProbeParams()
+    q.struct_size = C.sizeof(_lib.PrepatchProbeParams)
+    q.precision = {"bf16": PREC_BF16, "fp32": PREC_FP32}[precision]
+    f, B, H, W = _frame_fmt(frames)
+    q.fmt = f if fmt is None else int(fmt)
+    q.batch, q.H, q.W, q.decim_stride = B, H, W, int(decim_stride)
+    q.h, q.w, q.p, q.Kp, q.N, q.D = int(h), int(w), int(p), int(Kp), int(N), int(D)
+    q.pre = C.pointer(pre) if pre is not None else None
+    for name, t in (("frames", frames), ("A", A), ("cls", cls), ("pos", pos), ("resid", resid)):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError("preprocess_patches_probe: tensors must be contiguous")
+        setattr(q, name, t.data_ptr())
+        setattr(q, name + "_elems", t.numel())
+    with _on(frames.device) as st:
+        check(_lib.load().d2s_preprocess_patches_probe(C.byref(q), st), "d2s_preprocess_patches_probe")
+    return q.kernel.decode()

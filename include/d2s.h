@@ -314,6 +314,23 @@ int d2s_make_sbs(const void* rgb, int rgb_fmt, const float* depth, int dh, int d
                  void* out, int out_fmt, void* stream);
 /* output frame size of make_sbs_core for an H x W input (pad_to_aspect_tensor, depth.py:2106-2119) */
 int d2s_sbs_shape(int H, int W, const d2s_sbs_params* p, int* out_h, int* out_w);
+/* What d2s_make_sbs would launch for these arguments (d2s_version() >= 118; pure host code: launches nothing, needs no GPU).  The shape,
+ * format and parameter arguments are d2s_make_sbs's; rgb_align / out_align stand for the two pointers: their alignment in bytes (any
+ * positive integer with the pointer's residue modulo 4, e.g. 256 for an allocation, 1 for an odd address).  kernel is
+ * "stereo_warp_generic<IN,OUT>" (IN, OUT in U8_HWC / U8_CHW / F32_CHW / F32_HWC) or "stereo_warp_gather<MODE,NC=3|4,DIRECT=0|1>" (MODE in
+ * HALF_SBS / FULL_SBS / HALF_TAB / FULL_TAB); for the gather kernel rpw = source rows per wave (even for Half-TAB, never more than H),
+ * ntx = 256-pixel column tiles, wpc = resident waves per CU the grid was cut for; grid = blocks of 256 threads. */
+typedef struct d2s_warp_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_warp_plan_result) */
+    int32_t gather, direct, nc;
+    int32_t ntx, wpc, rpw;
+    int32_t out_h, out_w;
+    uint32_t grid;
+    int64_t waves;
+    char kernel[64];
+} d2s_warp_plan_result;
+int d2s_warp_plan(int rgb_fmt, int dh, int dw, int batch, int H, int W, const d2s_sbs_params* p, int out_fmt,
+                  int rgb_align, int out_align, d2s_warp_plan_result* res);
 
 /* f1: the GLSL DIBR warp with disocclusion in-painting the reference's Viewer / OpenXR modes render
  * (FRAGMENT_SHADER, viewer.py:386-631): rgb uint8 HWC [batch,H,W,3], depth float [batch,H,W] (full resolution, as
@@ -676,6 +693,29 @@ typedef struct d2s_temporal_probe_params {
     char kernel[128];          /* out: the kernel that ran, e.g. "groupnorm_reg_kernel<bf16,CPG=8,RPT=2>", "temporal_attn_kernel<f32,CH=4,WinRow>" */
 } d2s_temporal_probe_params;
 int d2s_temporal_probe(d2s_temporal_probe_params* p, void* stream);
+
+/* Stand-alone probe of d2s_pipeline's fused pre-process + patchify launch (tests; d2s_version() >= 118): launch_preprocess_patches on
+ * caller-owned device buffers.  frames u8 HWC [batch,H,W,3]; A [batch * (h/p) * (w/p)][Kp] of the precision's type (bf16 bits / float):
+ * columns c p^2 + i p + j < 3 p^2 are written, the rest left alone; resid float [batch][N][D]: row 0 of every frame = cls + pos[0] when
+ * cls != NULL (pos may then not be NULL), nothing otherwise.  Every size is checked against the element counts stated here before the
+ * launch; the probe packs and allocates nothing.  D2S_E_UNSUPPORTED, nothing launched, where the pipeline would not take this path (a
+ * format other than U8_HWC, a frame already at (h, w), 3 p^2 > Kp, bicubic resampling, another precision). */
+typedef struct d2s_prepatch_probe_params {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_prepatch_probe_params) */
+    int32_t precision;         /* D2S_PREC_BF16 / D2S_PREC_FP32 */
+    int32_t fmt, batch, H, W, decim_stride;
+    int32_t h, w, p, Kp, N, D;
+    int32_t reserved;
+    const d2s_pre_params* pre; /* NULL: ImageNet mean / std, bilinear */
+    const void* frames;
+    void* A;
+    const float* cls;          /* [D] or NULL */
+    const float* pos;          /* [>= D]: row 0 of the position embedding */
+    float* resid;
+    uint64_t frames_elems, A_elems, cls_elems, pos_elems, resid_elems;   /* elements each buffer holds (frames: bytes) */
+    char kernel[64];           /* out: "preprocess_patch_kernel<U8_HWC,bf16>" / "...,float>" */
+} d2s_prepatch_probe_params;
+int d2s_preprocess_patches_probe(d2s_prepatch_probe_params* p, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@ def test_header_symbols_exported(lib):
     for name in declared:
         assert getattr(lib, name) is not None
     assert lib.d2s_version() >= 110          # 110: d2s_dibr_params.struct_size
+    assert lib.d2s_version() >= 118 and {"d2s_warp_plan", "d2s_preprocess_patches_probe"} <= declared
 
 
 def test_struct_layout_matches_header():
@@ -50,6 +51,12 @@ def test_struct_layout_matches_header():
             and L.gh.offset == 40 and L.pK.offset == 52 and L.ln_eps.offset == 56 and L.s_act.offset == 60 and L.s_pact.offset == 72
             and L.tile.offset == 76 and L.splitk_elems.offset == 80 and L.a.offset == 88 and L.pscale.offset == 176 and L.x.offset == 184
             and L.stats.offset == 216 and L.stats_slots.offset == 224 and L.kernel.offset == 232 and L.kernel2.offset == 360)
+    Wp = _lib.WarpPlanResult                                                                 # d2s_warp_plan_result
+    assert (C.sizeof(Wp) == 112 and Wp.gather.offset == 4 and Wp.rpw.offset == 24 and Wp.out_h.offset == 28 and Wp.grid.offset == 36
+            and Wp.waves.offset == 40 and Wp.kernel.offset == 48)
+    Q = _lib.PrepatchProbeParams                                                             # d2s_prepatch_probe_params
+    assert (C.sizeof(Q) == 208 and Q.precision.offset == 4 and Q.decim_stride.offset == 24 and Q.D.offset == 48 and Q.pre.offset == 56
+            and Q.frames.offset == 64 and Q.resid.offset == 96 and Q.frames_elems.offset == 104 and Q.kernel.offset == 144)
 
 
 def test_sbs_shape_matches_reference_padding(lib):
