@@ -63,6 +63,12 @@ class XrEye(C.Structure):
     _fields_ = [("vp", C.c_double * 16), ("width", C.c_int32), ("height", C.c_int32), ("eye", C.c_int32), ("struct_size", C.c_uint32)]
 
 
+class XrGlow(C.Structure):
+    """d2s_xr_glow: the glow around the flat screen (mode 0 off, 1 glow, 2 glow2)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("range_m", C.c_double), ("inner_edge_fraction", C.c_double)]
+
+
+XR_GLOW = {"off": 0, "glow": 1, "glow2": 2}
 XR_CURVE = {"flat": 0, "horizontal": 1, "vertical": 2}      # D2S_XR_CURVE_*
 DIBR_ALPHA = {"window": 0, "premultiplied": 1, "rgba": 2}      # D2S_DIBR_ALPHA_*
 COMPOSITE = {"Anaglyph": 0, "Interleaved": 1, "Interleaved-V": 2, "Depth Map": 3}      # D2S_COMPOSITE_*
@@ -180,7 +186,16 @@ SYMBOLS = {
     "d2s_dibr_xr_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
     "d2s_dibr_xr_eyes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
                                    C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, _P]),
-    "d2s_crop_detect_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    # the colour mip chain and the glow around the flat screen (xr_viewer/effects.py:476-646, xr_viewer/glsl.py:580-666)
+    "d2s_mip_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                C.POINTER(C.c_uint64)]),
+    "d2s_mip_chain": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "d2s_dibr_xr_eyes_glow": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                        C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrGlow), _P, _P]),
+    "d2s_view_pipeline_xr_glow_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                                    C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double), C.POINTER(XrScreen),
+                                                    C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.POINTER(XrGlow), _P, _P]),
+    "d2s_crop_detect_workspace":(C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "d2s_crop_detect": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, _P]),
     "d2s_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "d2s_jpeg_encode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P]),

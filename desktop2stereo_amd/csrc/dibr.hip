@@ -89,7 +89,8 @@ __device__ __forceinline__ PixTaps pix_taps(const S& smp, const G& g, int x, int
 // fall-off, the shift, the in-painting, the border alpha -- follows the CROPPED uv (u, v); the rounded-corner SDF stays on the quad's
 // own uv (us, vs) and the feathering on the pixel index and u_viewport.
 // G = DibrGeomProj (d2s_dibr_xr_eyes): quv = the screen's own uv (u, 1 - v of the interpolated vertex uv) of this pixel; x, y are not used.
-template <bool DEFER = false, bool SHARED = false, bool FX = true, class S, class G>
+// RAW: frag_color as the shader writes it whatever alpha_mode says (the glow passes blend over it first).
+template <bool DEFER = false, bool SHARED = false, bool FX = true, bool RAW = false, class S, class G>
 __device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int y, int eye, float outc[4], const PixTaps* sh = nullptr,
                                            const float* quv = nullptr) {
     const float eye_offset = eye ? g.half_ipd : -g.half_ipd;                          // :2701, 2714
@@ -181,7 +182,7 @@ __device__ __forceinline__ bool dibr_pixel(const S& smp, const G& g, int x, int 
     // frag_color = (col, alpha).  The reference's quads are drawn with blending off: its window shows col as written (WINDOW);
     // PREMULTIPLIED = col * alpha (composited over black); RGBA hands out both (d2s.h)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) outc[k] = g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED ? col[k] * alpha : col[k];
+    for (int k = 0; k < 3; ++k) outc[k] = !RAW && g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED ? col[k] * alpha : col[k];
     outc[3] = alpha;
     return false;
 }
@@ -330,14 +331,101 @@ __global__ void __launch_bounds__(256) dibr_xr_table_kernel(XrFacetChunk c, floa
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_floats) dst[i] = ((const float*)&c)[i];
 }
-template <int OUT_FMT, class D>
-__global__ void __launch_bounds__(256)
-dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
-               const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex) {
+// ---- the glow passes (_GLOW_FRAG, xr_viewer/glsl.py:580-666), GLOW = true only.  lds: levels G.m .. G.q of the frame's mip chain as float
+// RGB, one after another (level l is max(1, W >> l) x max(1, H >> l): floor-halving composes).
+// one GL_LINEAR tap of level l, CLAMP_TO_EDGE (xr_viewer/frame.py:39-40); u, v in 0..1
+__device__ __forceinline__ void glow_level(const float* __restrict__ lds, const XrGlowDev& G, int H, int W, int l, float u, float v, float o[3]) {
+    int off = 0;
+    for (int j = G.m; j < l; ++j) off += max(1, W >> j) * max(1, H >> j);
+    const int w = max(1, W >> l), h = max(1, H >> l);
+    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f, x0f = floorf(x), y0f = floorf(y);
+    const float fx = x - x0f, fy = y - y0f;
+    const int x0 = min(max((int)x0f, 0), w - 1), x1 = min(max((int)x0f + 1, 0), w - 1);
+    const int y0 = min(max((int)y0f, 0), h - 1), y1 = min(max((int)y0f + 1, 0), h - 1);
+    const float* a = lds + (off + y0 * w + x0) * 3;
+    const float* b = lds + (off + y0 * w + x1) * 3;
+    const float* c = lds + (off + y1 * w + x0) * 3;
+    const float* d = lds + (off + y1 * w + x1) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = lerp2(a[k], b[k], c[k], d[k], fx, fy);
+}
+// textureLod(u_source, source_uv(s), lod): LOD clamped to the chain (lod >= 7 >= G.m), trilinear
+__device__ __forceinline__ void glow_texture_lod(const float* __restrict__ lds, const XrGlowDev& G, const DibrGeomProj& g, float su, float sv,
+                                                 float lod, float o[3]) {
+    const float u = fminf(fmaxf(g.cx + fminf(fmaxf(su, 0.f), 1.f) * g.cw, 0.f), 1.f);      // source_uv (:597-600)
+    const float v = fminf(fmaxf(g.cy + fminf(fmaxf(sv, 0.f), 1.f) * g.ch, 0.f), 1.f);
+    const float lam = fminf(fmaxf(lod, (float)G.m), (float)G.q), l0f = floorf(lam), f = lam - l0f;
+    const int l0 = (int)l0f, l1 = min(l0 + 1, G.q);
+    float a[3], b[3];
+    glow_level(lds, G, g.H, g.W, l0, u, v, a);
+    glow_level(lds, G, g.H, g.W, l1, u, v, b);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = a[k] * (1.0f - f) + b[k] * f;
+}
+// the Chebyshev signed distance (:621-623) at the screen's plane coordinates (a, b)
+__device__ __forceinline__ float glow_sd(const XrGlowDev& G, float a, float b, float& cx, float& cy) {
+    cx = (a - 0.5f) * G.inner_w; cy = (b - 0.5f) * G.inner_h;                                // uv - 0.5
+    return fmaxf(fabsf(cx) - G.half_x, fabsf(cy) - G.half_y);
+}
+// main() of one pass: false = discarded, else src = (colour * glow in 0..255, glow).  A non-finite (a, b) -- far from the screen
+// a / nw grows without bound -- ends in a comparison that fails: no glow.
+__device__ __forceinline__ bool glow_frag(const float* __restrict__ lds, const XrGlowDev& G, const DibrGeomProj& g, float a, float b,
+                                          bool inner_only, float src[4]) {
+    float cx, cy;
+    const float sd = glow_sd(G, a, b, cx, cy);
+    const float inv_range = fmaxf(G.inv_range, 0.001f), inner = fmaxf(G.inner, 0.f);
+    if (inner_only) { if (inner <= 0.f || sd > 0.f || sd < -inner) return false; }
+    else if (!(sd > 0.f)) return false;
+    const float edge_t = fminf(fmaxf((inner_only ? sd + inner : sd) * inv_range, 0.f), 1.f);
+    float glow = powf(fmaxf(1.0f - smoothstepf(0.f, 1.f, edge_t), 0.f), 0.58f);
+    if (inner_only) {
+        float dens = smoothstepf(0.f, fmaxf(inner, 1e-6f), sd + inner);
+        dens = dens * dens * (3.0f - 2.0f * dens);
+        glow *= dens;
+    }
+    if (!(glow > 0.001f)) return false;
+    // the screen's own uv again, from the glow's (:654-656), v flipped to the frame's top-left origin
+    const float rx = ((cx + 0.5f) - (0.5f - G.half_x)) / fmaxf(G.half_x * 2.0f, 1e-5f);
+    const float ry = 1.0f - ((cy + 0.5f) - (0.5f - G.half_y)) / fmaxf(G.half_y * 2.0f, 1e-5f);
+    // extended_screen_color (:608-617)
+    float dx = rx - 0.5f + 1e-5f, dy = ry - 0.5f;
+    const float len = sqrtf(dx * dx + dy * dy);
+    dx /= len; dy /= len;
+    const float es = fminf(0.5f / fmaxf(fabsf(dx), 1e-5f), 0.5f / fmaxf(fabsf(dy), 1e-5f));      // edge_point_for_dir (:602-606)
+    const float ex = fminf(fmaxf(0.5f + dx * es, 0.f), 1.f), ey = fminf(fmaxf(0.5f + dy * es, 0.f), 1.f);
+    const float blur_t = inner_only ? 0.f : smoothstepf(0.f, 1.f, edge_t);
+    const float back = 0.015f * (1.0f - blur_t) + 0.060f * blur_t, lod = 7.0f * (1.0f - blur_t) + 9.0f * blur_t;
+    float local[3], edge[3];
+    glow_texture_lod(lds, G, g, ex - dx * back, ey - dy * back, lod, local);
+    if (inner_only) { edge[0] = local[0]; edge[1] = local[1]; edge[2] = local[2]; }      // (mixed in with weight 0: one textureLod)
+    else glow_texture_lod(lds, G, g, ex, ey, lod + 1.0f, edge);
+    const float mt = blur_t * 0.5f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) src[k] = (local[k] * (1.0f - mt) + edge[k] * mt) * glow;      // (u_glow_alpha_cap = 1: min(glow, 1) = glow)
+    src[3] = glow;
+    return true;
+}
+__device__ __forceinline__ void glow_blend(float c[4], const float src[4]) {      // ONE, ONE_MINUS_SRC_ALPHA, rgb and alpha
+    const float k = 1.0f - src[3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = src[i] + c[i] * k;
+}
+
+// GLOW = false: d2s_dibr_xr_eyes.  GLOW = true (flat screen, one facet): _render_eye's order (effects.py:1050-1145) in one pass over
+// the pixel, in float -- clear; the outer band blended over it where the screen does not cover the pixel (where it does the screen,
+// drawn with blending off, overwrites the band); the screen; mode 1: the inner band blended over the screen.  The glow quad is the
+// screen's plane: facet 0's homography without the 0..1 bound gives its coordinates; it is drawn where clip w > 0 and NDC z is in
+// [-1, 1].  (The quad ends at screen + range; the glow reaches 0 there or sooner -- edge_t = 1 -- so the quad's own bound is not
+// tested.)  A block stages the chain's coarse levels in LDS once unless its whole tile is plain screen or undrawn.
+template <int OUT_FMT, class D, bool GLOW>
+__device__ __forceinline__ void dibr_xr_body(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+                                             const XrFacet* __restrict__ tab_all, const DibrGeomProj& g, const XrEyes& ex, const XrGlowDev& G,
+                                             const uint8_t* __restrict__ levels, float* __restrict__ lds) {
     const int ei = blockIdx.z % ex.n, b = blockIdx.z / ex.n;
     const XrEyeDev e = ex.e[ei];
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= e.w || y >= e.h) return;
+    const bool inside = x < e.w && y < e.h;
+    if (!GLOW && !inside) return;
     const XrFacet* __restrict__ tab = tab_all + ei * XR_MAX_FACETS;
     const float xc = ((float)x + 0.5f) - 0.5f * (float)e.w, yc = ((float)y + 0.5f) - 0.5f * (float)e.h;      // exact: multiples of 0.5 below 2^13
     int best = -1;
@@ -353,11 +441,35 @@ dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ de
             if (z >= -1.0f && z < bz) { bz = z; best = f; ba = na; bb = nb; bw = nw; }      // GL_LESS: a tie keeps the lower facet index
         }
     }
+    bool plane = false;                                  // GLOW: the glow quad is drawn at this pixel
+    float ga = 0.f, gb = 0.f;                            // and its point in the screen's coordinates
+    if constexpr (GLOW) {
+        const XrFacet& F = tab[0];
+        const float na = F.ha[0] * xc + F.ha[1] * yc + F.ha[2], nb = F.hb[0] * xc + F.hb[1] * yc + F.hb[2];
+        const float nw = F.hw[0] * xc + F.hw[1] * yc + F.hw[2], z = F.hz[0] * xc + F.hz[1] * yc + F.hz[2];
+        plane = nw > 0.f && z >= -1.0f && z <= 1.0f;
+        ga = na / nw; gb = nb / nw;
+        float cx, cy;
+        const bool need = inside && plane && (best < 0 || (G.mode == 1 && glow_sd(G, ga, gb, cx, cy) >= -G.inner));
+        if (__syncthreads_or(need)) {
+            const uint8_t* __restrict__ src = levels + (long)b * G.chain_total + G.chain_off;
+            for (int i = threadIdx.x; i < G.n_tex * 3; i += 256) lds[i] = (float)src[i];
+            __syncthreads();
+        }
+        if (!inside) return;
+    }
     const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
     const long o = e.out_off + (((long)b * e.h + y) * e.w + x) * nch;
     float c[4];
     if (best < 0) {
         c[0] = ex.clear[0] * 255.0f; c[1] = ex.clear[1] * 255.0f; c[2] = ex.clear[2] * 255.0f; c[3] = ex.clear[3];
+        if constexpr (GLOW) {
+            float src[4];
+            if (plane && glow_frag(lds, G, g, ga, gb, false, src)) {
+                glow_blend(c, src);
+                if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
+            }
+        }
         dibr_store<OUT_FMT>(out_all, o, nch, c);
         return;
     }
@@ -366,8 +478,28 @@ dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ de
     const float quv[2] = {F.u0 + a * F.ua + bq * F.ub, 1.0f - (F.v0 + a * F.va + bq * F.vb)};
     GenSmp<D> smp;
     smp.rgb = rgb_all + (long)b * g.H * g.W * 3; smp.dep = D::make(dep_all, b, g); smp.H = g.H; smp.W = g.W;
-    dibr_pixel(smp, g, 0, 0, e.eye, c, nullptr, quv);
+    if constexpr (GLOW) {
+        dibr_pixel<false, false, true, true>(smp, g, 0, 0, e.eye, c, nullptr, quv);      // the framebuffer's own (rgb, a): alpha_mode acts after the inner band
+        float src[4];
+        if (G.mode == 1 && plane && glow_frag(lds, G, g, ga, gb, true, src)) glow_blend(c, src);
+        if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
+    } else {
+        dibr_pixel(smp, g, 0, 0, e.eye, c, nullptr, quv);
+    }
     dibr_store<OUT_FMT>(out_all, o, nch, c);
+}
+template <int OUT_FMT, class D>
+__global__ void __launch_bounds__(256)
+dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+               const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex) {
+    dibr_xr_body<OUT_FMT, D, false>(rgb_all, dep_all, out_all, tab_all, g, ex, XrGlowDev{}, nullptr, nullptr);
+}
+template <int OUT_FMT, class D>
+__global__ void __launch_bounds__(256)
+dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+                    const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrGlowDev G, const uint8_t* __restrict__ levels) {
+    extern __shared__ float xr_glow_lds[];               // [n_tex][3]
+    dibr_xr_body<OUT_FMT, D, true>(rgb_all, dep_all, out_all, tab_all, g, ex, G, levels, xr_glow_lds);
 }
 
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
@@ -377,6 +509,9 @@ int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
 int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
                 const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
                 uint64_t workspace_bytes, void* stream, bool check_only);                              // (d2s_view_pipeline_xr_streams)
+int dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
+                     const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                     uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
 
 }  // namespace d2s
 
@@ -550,6 +685,15 @@ extern "C" int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes) {
 int d2s::dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                      const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
                      void* workspace, uint64_t workspace_bytes, void* stream, bool check_only) {
+    return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, nullptr,
+                            nullptr, stream, check_only);
+}
+
+// glow == nullptr or mode 0: d2s_dibr_xr_eyes, the same launches
+int d2s::dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                          const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                          void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
+                          bool check_only) {
     D2S_REQUIRE(rgb && depth && p && out, "null pointer");
     int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
     if (rc) return rc;
@@ -561,6 +705,10 @@ int d2s::dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int
     }
     rc = xr_check(screen, eyes, n_eyes, batch, workspace, workspace_bytes);
     if (rc) return rc;
+    rc = xr_glow_check(screen, glow, levels);
+    if (rc) return rc;
+    const bool glow_on = glow && glow->mode != 0;
+    D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
     uint64_t offs[2] = {0, 0}, total = 0;
     rc = xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, offs, &total);
     if (rc) return rc;
@@ -600,6 +748,17 @@ int d2s::dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int
         }
     const bool up = dh != H || dw != W;
     dim3 grid(cdiv(mw, 16), cdiv(mh, 16), n_eyes * batch), block(256);
+    if (glow_on) {
+        XrGlowDev G;
+        xr_glow_dev(screen, glow, H, W, G);
+        const size_t lds = (size_t)G.n_tex * 3 * sizeof(float);      // <= 65 532 bytes (an 8192 x 8192 frame)
+#define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D>), grid, block, lds, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex, G, levels)
+        if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
+        else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
+#undef DIBR_XR
+        D2S_CHECK_LAUNCH();
+        return D2S_OK;
+    }
 #define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex)
     if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
     else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
@@ -612,4 +771,12 @@ extern "C" int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, 
                                 const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
                                 int out_fmt, void* workspace, uint64_t workspace_bytes, void* stream) {
     return dibr_xr_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                     const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                     int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
+                                     void* stream) {
+    return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, glow,
+                            levels, stream, false);
 }

@@ -4,6 +4,7 @@
 // (xr_viewer/effects.py:65-82), _CURVED_HALF_ANGLE_RAD (xr_viewer/constants.py:50-51), _render_eye (effects.py:1023-1137).
 #pragma once
 #include "common.h"
+#include "mip.h"
 #include <cmath>
 
 namespace d2s {
@@ -140,6 +141,55 @@ inline int xr_check(const d2s_xr_screen* s, const d2s_xr_eye* eyes, int n_eyes, 
     D2S_REQUIRE(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
     D2S_REQUIRE(ws_bytes >= (uint64_t)n_eyes * XR_MAX_FACETS * sizeof(XrFacet), "workspace_bytes below d2s_dibr_xr_workspace");
     return D2S_OK;
+}
+
+// ---- the glow around the flat screen (d2s_dibr_xr_eyes_glow; _render_glow, xr_viewer/effects.py:476-585) ----
+constexpr int XR_GLOW_LOD = 7;                    // GLOW_SOURCE_LOD (xr_viewer/glsl.py:595): the glow reads LOD 7 .. 10
+// The uniforms _render_glow sets, rounded to float once, and the part of the mip chain the kernel keeps in LDS.  The glow quad lies in
+// the screen's plane, so with (a, b) the screen facet's own coordinates its uv is 0.5 + ((a, b) - 0.5) * (inner_w, inner_h).
+struct XrGlowDev {
+    int mode;                                     // 1 glow, 2 glow2
+    float half_x, half_y;                         // u_screen_half
+    float inner_w, inner_h;
+    float inv_range, inner;                       // u_glow_inv_range, u_glow_inner
+    int m, q, n_tex;                              // levels m = min(7, q) .. q are staged: n_tex texels, 12 bytes each (<= 5461: 64 KB)
+    uint32_t chain_off, chain_total;              // level m's byte offset within a frame's chain; the chain's bytes per frame
+};
+
+// What d2s_dibr_xr_eyes_glow refuses about the glow, after xr_check has accepted the screen; no HIP call.
+inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, const uint8_t* levels) {
+    if (!glow) return D2S_OK;
+    D2S_REQUIRE(glow->struct_size == sizeof(d2s_xr_glow), "d2s_xr_glow.struct_size must be sizeof(d2s_xr_glow) = 24");
+    D2S_REQUIRE(glow->mode >= 0 && glow->mode <= 2, "bad glow mode (0 off, 1 glow, 2 glow2)");
+    if (glow->mode == 0) return D2S_OK;
+    D2S_REQUIRE(levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
+    D2S_REQUIRE(std::isfinite(glow->range_m) && glow->range_m > 0.0, "glow range_m must be finite and > 0");
+    D2S_REQUIRE(std::isfinite(glow->inner_edge_fraction) && glow->inner_edge_fraction >= 0.0, "glow inner_edge_fraction must be finite and >= 0");
+    if (s->curve != D2S_XR_CURVE_FLAT) {
+        set_error("unsupported: the glow of a curved screen (a band mesh in the reference) is not built; curve must be 0 with glow on");
+        return D2S_E_UNSUPPORTED;
+    }
+    D2S_REQUIRE(s->normal_offset == 0.0, "normal_offset must be 0 with glow on (the reference offsets the screen only under a room model, which has no planar glow)");
+    return D2S_OK;
+}
+
+// _render_glow:486-495 in double precision; H x W: the frame the chain was built from
+inline void xr_glow_dev(const d2s_xr_screen* s, const d2s_xr_glow* glow, int H, int W, XrGlowDev& G) {
+    double range = fmax(glow->range_m, 1e-4);
+    if (glow->mode == 2) range *= 0.5;
+    const double glow_w = s->width + 2.0 * range, glow_h = s->height + 2.0 * range;
+    const double uv_range = range / fmax(glow_w, glow_h), inner_w = s->width / glow_w, inner_h = s->height / glow_h;
+    const double inner_uv = glow->mode == 2 ? 0.0 : fmin(inner_w, inner_h) * fmax(glow->inner_edge_fraction, 0.0);
+    G = XrGlowDev{};
+    G.mode = glow->mode;
+    G.half_x = (float)(inner_w * 0.5); G.half_y = (float)(inner_h * 0.5);
+    G.inner_w = (float)inner_w; G.inner_h = (float)inner_h;
+    G.inv_range = (float)(1.0 / fmax(uv_range, 1e-6)); G.inner = (float)inner_uv;
+    MipShape ms;
+    mip_shape(H, W, ms);
+    G.q = ms.q; G.m = ms.q < XR_GLOW_LOD ? ms.q : XR_GLOW_LOD;
+    G.chain_off = ms.off[G.m]; G.chain_total = ms.total;
+    for (int k = G.m; k <= ms.q; ++k) G.n_tex += ms.h[k] * ms.w[k];
 }
 
 }  // namespace d2s

@@ -1015,6 +1015,9 @@ int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
 int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
                 const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
                 uint64_t workspace_bytes, void* stream, bool check_only);
+int dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
+                     const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                     uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
 }
 
 namespace {
@@ -1141,11 +1144,12 @@ extern "C" int d2s_view_pipeline_crop_streams(d2s_engine* e, const uint8_t* fram
 }
 
 // d2s_view_pipeline_crop_streams with the OpenXR eye views (d2s_dibr_xr_eyes) as the last stage: the same checks and depth path
-extern "C" int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
-                                            int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
-                                            const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
-                                            const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
-                                            void* workspace, uint64_t workspace_bytes, void* stream) {
+// (d2s_view_pipeline_xr_glow_streams: the same call with the glow; glow == nullptr is d2s_view_pipeline_xr_streams)
+static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
     D2S_REQUIRE(frames && pp && dp && out && screen && eyes, "null pointer");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     uint64_t offs[2], total = 0;
@@ -1154,8 +1158,8 @@ extern "C" int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames
     int stride = 1;
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
     auto warp = [&](bool check_only) {
-        return dibr_xr_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                           workspace_bytes, stream, check_only);
+        return dibr_xr_glow_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                                workspace_bytes, glow, levels, stream, check_only);
     };
     RC(warp(true));
     D2S_ON_DEVICE(e->device);
@@ -1164,6 +1168,25 @@ extern "C" int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames
     const double obytes = (double)total / batch * (out_fmt == D2S_FMT_U8_HWC ? 1 : 4);
     PROF(PC_WARP, 0, batch * ((double)H * W * 3 + (double)e->h * e->w * 4 + obytes), warp(false));
     return D2S_OK;
+}
+
+extern "C" int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                            int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                            const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                            const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                            void* workspace, uint64_t workspace_bytes, void* stream) {
+    return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
+                                out_fmt, depth_full, workspace, workspace_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int d2s_view_pipeline_xr_glow_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                                 int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                                 const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                                 const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                                 void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
+                                                 void* stream) {
+    return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
+                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream);
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

@@ -344,6 +344,37 @@ def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_tempor
                                 streams=streams)
 
 
+def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=None, inner_edge_fraction=0.075, head=None, crop=None,
+                      corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
+    """xr_eye_views with the reference's "Default with Glow" looks around the flat screen (_render_glow, xr_viewer/effects.py:476-585)
+    drawn in the same launch.  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
+    frames' colour mip chain (ops.mip_chain); None builds it here, every call -- the reference refreshes its own every
+    _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  Frost, veil, border, controllers and
+    environment stay with the caller."""
+    from . import xr as _xr
+    p = _state["params"]
+    t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+    t = t.to(device=_device())
+    B, H, W, _ = t.shape
+    h, w, _s = engine_shape(H, W, p.depth_resolution, _state["cfg"].patch, p.square_input)
+    if B > _state["max_batch"]:
+        raise _lib.D2SError(f"batch {B} > configured max_batch {_state['max_batch']}")
+    eng = _ensure_engine_built(h, w, _fp8_first_inputs(t, (h, w)))
+    if isinstance(crop, str):
+        if crop != "auto":
+            raise ValueError('crop must be None, (x, y, w, h) or "auto"')
+        mc = movie_crop(0 if streams is None else int(streams[0]))
+        mc.update(t[0])
+        crop = tuple(mc.crop_uv)
+    if isinstance(glow, str):
+        glow = _xr.XrGlow(glow, _xr.glow_range_m(screen, head) if range_m is None else float(range_m), inner_edge_fraction)
+    if levels is None and glow.mode != "off":
+        levels = ops.mip_chain(t)
+    dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
+    return eng.view_pipeline_xr_glow(t, p, dp, screen, eyes, glow, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
+                                     want_depth=want_depth, streams=streams)
+
+
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,
              viewport=None, crop=None):
     """Batched predict_depth + make_sbs: uint8 [B,H,W,3] (numpy or device tensor) -> device tensor

@@ -465,6 +465,87 @@ def dibr_xr_eyes(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams
     return _xr_views(out.view(-1), ea, B, nch, offs)
 
 
+def mip_shape(H: int, W: int) -> Tuple[list, int]:
+    """([(offset, h, w)] of levels 1 .. q, total bytes) of one frame's colour mip chain (d2s_mip_shape): level k is uint8 [h, w, 3] at
+    byte `offset` of the frame's row of mip_chain's result."""
+    n, total = C.c_int(), C.c_uint64()
+    offs, hs, ws = (C.c_uint64 * 14)(), (C.c_int * 14)(), (C.c_int * 14)()
+    check(_lib.load().d2s_mip_shape(int(H), int(W), C.byref(n), offs, hs, ws, C.byref(total)), "d2s_mip_shape")
+    return [(offs[i], hs[i], ws[i]) for i in range(n.value)], total.value
+
+
+def mip_chain(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mip chain glGenerateMipmap builds for the OpenXR viewer's colour texture (reference xr_viewer/effects.py:597-646), which
+    its glow samples: frames uint8 [B,H,W,3] or [H,W,3] -> uint8 [B, total] (mip_shape), levels 1 .. q one after another.  out: a
+    caller-kept tensor of that shape."""
+    _need_cuda(frames, "frames")
+    if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+        raise ValueError("mip_chain: frames must be uint8 [B,H,W,3] or [H,W,3]")
+    f = frames.contiguous() if frames.dim() == 4 else frames.contiguous().unsqueeze(0)
+    B, H, W, _ = f.shape
+    _, total = mip_shape(H, W)
+    if out is None:
+        out = torch.empty((B, total), dtype=torch.uint8, device=f.device)
+    elif not out.is_cuda or out.device != f.device or out.dtype != torch.uint8 or tuple(out.shape) != (B, total) or not out.is_contiguous():
+        raise ValueError(f"mip_chain: out must be a contiguous uint8 tensor of {(B, total)} on {f.device}")
+    with _on(f.device) as st:
+        check(_lib.load().d2s_mip_chain(_ptr(f), B, H, W, _ptr(out), st), "d2s_mip_chain")
+    return out
+
+
+def _xr_glow_args(glow, levels, B: int, H: int, W: int, device, who: str):
+    """(d2s_xr_glow or None, the chain's pointer or None) of an xr.XrGlow (or the struct, or None = off) and mip_chain's result."""
+    if glow is None:
+        return None, None
+    gs = glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
+    if levels is None:
+        return gs, None                                   # (the library refuses a missing chain with glow on)
+    _need_cuda(levels, "levels")
+    _, total = mip_shape(H, W)
+    if levels.dtype != torch.uint8 or levels.device != device or tuple(levels.shape) != (B, total) or not levels.is_contiguous():
+        raise ValueError(f"{who}: levels must be mip_chain's result for these frames, a contiguous uint8 tensor of {(B, total)} on {device}")
+    return gs, levels
+
+
+def dibr_xr_eyes_glow(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
+                      out_u8: bool = True, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> list:
+    """dibr_xr_eyes with the reference's glow around the flat screen in the same launch (d2s_dibr_xr_eyes_glow; reference
+    _render_glow, xr_viewer/effects.py:476-585): glow = xr.XrGlow (None or mode "off": exactly dibr_xr_eyes), levels = mip_chain(frames)
+    -- or an older chain: the reference refreshes its mipmaps every few frames only.  Everything else as dibr_xr_eyes."""
+    _need_cuda(frames, "frames")
+    _need_cuda(depth, "depth")
+    if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+        raise ValueError("dibr_xr_eyes_glow: frames must be uint8 [B,H,W,3] or [H,W,3]")
+    f = frames.contiguous() if frames.dim() == 4 else frames.contiguous().unsqueeze(0)
+    d = depth.to(torch.float32).contiguous()
+    d = d if d.dim() == 3 else d.unsqueeze(0)
+    B, H, W, _ = f.shape
+    if d.dim() != 3 or d.shape[0] != B:
+        raise ValueError(f"dibr_xr_eyes_glow: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
+    _same_device(f, d, "dibr_xr_eyes_glow")
+    sc, ea = _xr_args(screen, eyes)
+    if levels is not None and levels.dim() == 1:
+        levels = levels.unsqueeze(0)
+    gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, "dibr_xr_eyes_glow")
+    offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
+    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+    dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
+    if out is None:
+        out = torch.empty(total, dtype=dtype, device=f.device)
+    elif not out.is_cuda or out.device != f.device or out.dtype != dtype or out.numel() != total or not out.is_contiguous():
+        raise ValueError(f"dibr_xr_eyes_glow: out must be a contiguous {dtype} tensor of {total} elements on {f.device}")
+    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device)
+    _need_cuda(ws, "workspace")
+    _same_device(f, ws, "dibr_xr_eyes_glow workspace")
+    c4 = _crop4(crop) if crop is not None else None
+    with _on(f.device) as st:
+        check(_lib.load().d2s_dibr_xr_eyes_glow(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
+                                                _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(),
+                                                C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None, st),
+              "d2s_dibr_xr_eyes_glow")
+    return _xr_views(out.view(-1), ea, B, nch, offs)
+
+
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
                    out_u8: bool = True, size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """The viewer's composite display modes (reference viewer.py:633-1197): "Anaglyph" | "Interleaved" | "Interleaved-V" |
@@ -730,24 +811,43 @@ class Engine:
         ops.dibr_xr_eyes.  Returns one tensor per eye (with want_depth: (list, depth)); bit-identical to pipeline(want_depth=True)'s
         engine depth followed by dibr_xr_eyes.  out: a caller-kept 1-D tensor of dibr_xr_shape's total.  (A method of its own, as
         view_pipeline_crop is: view_pipeline's parameter list is pinned by the ABI tests.)"""
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, None, None)
+
+    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels):
         sc, ea = _xr_args(screen, eyes)
         nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
+        name, who = ("d2s_view_pipeline_xr_streams", "view_pipeline_xr") if glow is None else ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow")
         lay = {}
 
         def spec(B, H, W):
             lay["offs"], lay["total"] = dibr_xr_shape(ea, B, dp.alpha_mode)
             lay["B"] = B
+            if glow is not None:
+                lay["glow"] = _xr_glow_args(glow, levels, B, H, W, self.device, who)
             return (lay["total"],), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
         ws = _xr_workspace(len(ea), self.device)
         nbytes = ws.numel()
 
         def fn(*a):      # (_run_pipeline ends every call with out, out_fmt, depth_full, stream: the workspace goes in front of the stream)
-            return self.lib.d2s_view_pipeline_xr_streams(*a[:-1], _ptr(ws), nbytes, a[-1])
+            if glow is None:
+                return self.lib.d2s_view_pipeline_xr_streams(*a[:-1], _ptr(ws), nbytes, a[-1])
+            gs, lv = lay["glow"]
+            return self.lib.d2s_view_pipeline_xr_glow_streams(*a[:-1], _ptr(ws), nbytes, C.byref(gs), _ptr(lv) if lv is not None else None, a[-1])
         mid = (C.byref(dp), _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea), int(use_ema))
-        r = self._run_pipeline(fn, "d2s_view_pipeline_xr_streams", frames, p, spec, mid, want_depth, out, streams, who="view_pipeline_xr")
+        r = self._run_pipeline(fn, name, frames, p, spec, mid, want_depth, out, streams, who=who)
         flat = (r[0] if want_depth else r).view(-1)
         views = _xr_views(flat, ea, lay["B"], nch, lay["offs"])
         return (views, r[1]) if want_depth else views
+
+    def view_pipeline_xr_glow(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
+                              use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,
+                              streams=None):
+        """view_pipeline_xr with the glow around the flat screen (d2s_view_pipeline_xr_glow_streams): glow = xr.XrGlow, levels =
+        mip_chain(frames) (the caller's: it decides how often the chain is refreshed).  Bit-identical to pipeline(want_depth=True)'s
+        engine depth followed by dibr_xr_eyes_glow."""
+        if glow is None:
+            raise ValueError("view_pipeline_xr_glow: glow must be an xr.XrGlow (mode \"off\" for none)")
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels)
 
     def close(self):
         if getattr(self, "_h", None):

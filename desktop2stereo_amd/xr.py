@@ -85,6 +85,45 @@ class XrScreen:
         return out
 
 
+@dataclass
+class XrGlow:
+    """The reference's glow around the flat screen (include/d2s.h d2s_xr_glow): mode "glow" | "glow2" | "off"; range_m: what
+    _glow_range_m returns (glow_range_m below; the library halves it for glow2, as _render_glow does); inner_edge_fraction:
+    _glow_inner_edge_fraction, the inner band's width as a share of the screen's shorter side in glow uv."""
+    mode: str = "glow"
+    range_m: float = 15.0
+    inner_edge_fraction: float = 0.075
+
+    def c_struct(self) -> "_lib.XrGlow":
+        if self.mode not in _lib.XR_GLOW:
+            raise ValueError(f"glow mode must be one of {list(_lib.XR_GLOW)}")
+        return _lib.XrGlow(C.sizeof(_lib.XrGlow), _lib.XR_GLOW[self.mode], float(self.range_m), float(self.inner_edge_fraction))
+
+    def uniforms(self, screen: "XrScreen") -> dict:
+        """What _render_glow (xr_viewer/effects.py:486-495, 575-580) hands its shader for this screen, in float64: glow_w, glow_h,
+        inner_w, inner_h, u_screen_half, u_glow_inv_range, u_glow_inner.  The library forms the same numbers itself."""
+        rng = max(float(self.range_m), 1e-4) * (0.5 if self.mode == "glow2" else 1.0)
+        glow_w, glow_h = screen.width + 2 * rng, screen.height + 2 * rng
+        inner_w, inner_h = screen.width / glow_w, screen.height / glow_h
+        inner_uv = 0.0 if self.mode == "glow2" else min(inner_w, inner_h) * max(float(self.inner_edge_fraction), 0.0)
+        return dict(glow_w=glow_w, glow_h=glow_h, inner_w=inner_w, inner_h=inner_h, u_screen_half=(inner_w * 0.5, inner_h * 0.5),
+                    u_glow_inv_range=1.0 / max(rng / max(glow_w, glow_h), 1e-6), u_glow_inner=inner_uv)
+
+
+def glow_range_m(screen: XrScreen, head=None, width_m: float = 0.75, ref_screen: float = 2.4) -> float:
+    """_glow_range_m (xr_viewer/effects.py:280-312) without its rounded-key cache: the glow's reach in metres, growing with the
+    screen's longer side (rounded to centimetres, as the reference's key rounds it) and with the head's distance from the screen's
+    centre (head = the head position in world space, None = the origin)."""
+    base_width = max(float(width_m or 0.75), 0.75)
+    ref = max(float(ref_screen or 2.4), 1e-6)
+    screen_long = max(round(float(screen.width), 2), round(float(screen.height), 2), ref)
+    sd = round(float(screen.distance or 2.0), 1)
+    hx, hy, hz = (0.0, 0.0, 0.0) if head is None else (float(v) for v in head)
+    dx, dy, dz = hx - float(screen.pan_x), hy - float(screen.pan_y), hz + sd
+    dist = max(math.sqrt(dx * dx + dy * dy + dz * dz), 0.5)
+    return base_width * (screen_long / ref) * (dist / 2.0) * 20.0
+
+
 def fov_to_proj_mat4(angle_left: float, angle_right: float, angle_up: float, angle_down: float, near: float = 0.05,
                      far: float = 100.0) -> np.ndarray:
     """XrFovf -> the OpenGL asymmetric-frustum projection (numpy's row / column convention)."""

@@ -395,6 +395,52 @@ int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, int dw, int
                      const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
                      void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* The colour mip chain of the OpenXR viewer's frame texture (d2s_version() >= 119): what glGenerateMipmap builds for the reference's
+ * glow, frost and veil passes (xr_viewer/effects.py:597-646), restated from renders (tests/golden/xr_glow.npz).  Levels 1 .. q of an
+ * H x W frame, q = floor(log2(max(H, W))): level k is max(1, floor(size of level k - 1 / 2)) per axis, and each of its texels is the
+ * bilinear sample of the ALREADY 8-BIT level k - 1 at the texel's normalised centre -- source coordinate (i + 0.5) * n_(k-1) / n_k - 0.5,
+ * clamped to the edge -- rounded half to even (where both sizes are even: the 2 x 2 box).  All-integer arithmetic: exact.
+ *   d2s_mip_shape: *n_levels = q (<= 13); offsets[k-1], hs[k-1], ws[k-1] = level k's byte offset within one frame's chain and its size;
+ *                  *total_bytes = one frame's chain.  Host only.
+ *   d2s_mip_chain: rgb uint8 [batch, H, W, 3] -> levels uint8 [batch, total_bytes], each level RGB HWC, one after another.  The
+ *                  reference regenerates its mipmaps every _glow_mipmap_interval frames only; the caller decides when to call this.
+ * H, W in 2 .. 8192, batch in 1 .. 65535, else D2S_E_INVALID.  Stream-ordered, no host synchronisation, no allocation; every argument
+ * is checked before any HIP call. */
+int d2s_mip_shape(int H, int W, int* n_levels, uint64_t* offsets /* [<= 14] */, int* hs, int* ws, uint64_t* total_bytes);
+int d2s_mip_chain(const uint8_t* rgb, int batch, int H, int W, uint8_t* levels, void* stream);
+
+/* The OpenXR viewer's "Default with Glow" looks around the FLAT screen (d2s_version() >= 119): d2s_dibr_xr_eyes with the two blended
+ * passes of EffectsMixin._render_glow (xr_viewer/effects.py:476-585, shader _GLOW_FRAG xr_viewer/glsl.py:580-666) in the same launch,
+ * in _render_eye's order (effects.py:1050-1145): clear; the outer band, premultiplied-blended over the clear colour (rgb and alpha:
+ * src + dst * (1 - src.a); depth test off; drawn where the plane point has clip w > 0 and NDC z in [-1, 1]); the screen, exactly as
+ * d2s_dibr_xr_eyes draws it (blending off: its rgba overwrites, rounded corners included); mode 1 only: the inner band blended over the
+ * screen.  All of it in float, quantised once at the store; alpha_mode then acts on that (rgb, a) as it does without glow.
+ *   The glow quad is the screen's plane, screen + range_m on every side, so the screen facet's homography evaluated without its
+ *   0..1 bound gives the glow's uv; glow_w, glow_h, inner_w, inner_h, uv_glow_range and inner_uv are formed on the host in double
+ *   precision as _render_glow:486-495 forms them.  u_glow_alpha_cap = 1, u_glow_use_source = 1 (u_glow_color is not read);
+ *   _glow_intensity only gates the draw: mode 0 is the caller's "off".
+ *   mode:  0 off, 1 glow, 2 glow2 (range_m halved, as the reference halves it; no inner band).
+ *   range_m: what _glow_range_m returns (xr.glow_range_m).  inner_edge_fraction: _glow_inner_edge_fraction (0.075).
+ *   levels: d2s_mip_chain's output for the same frames.  textureLod: LOD clamped to [0, q], trilinear between floor(lod) and the next
+ *   level, bilinear within a level, CLAMP_TO_EDGE (xr_viewer/frame.py:39-40).  The glow reads LOD 7 .. 10 only.
+ *   NOT reproduced: with glow on the reference also gives the colour texture LINEAR_MIPMAP_LINEAR (frame.py:34, effects.py:601-608),
+ *   so ITS screen pass is trilinear where the screen is minified.  That filter needs implicit derivatives and is driver-dependent; the
+ *   screen pass here stays GL_LINEAR, as d2s_dibr_xr_eyes has it.  Frost, veil and border stay with the caller.
+ * Refused, nothing launched, out untouched: D2S_E_UNSUPPORTED: screen->curve != 0 with mode != 0 (the curved glow is a band mesh of
+ * ~500 quads, _build_curved_glow_band_verts).  D2S_E_INVALID: normal_offset != 0 with mode != 0 (the reference offsets the screen only
+ * under a room model, which switches the planar glow off); range_m <= 0 or non-finite; inner_edge_fraction < 0 or non-finite; mode
+ * outside 0..2; a bad struct_size; levels NULL with mode != 0; everything d2s_dibr_xr_eyes refuses.  glow == NULL or mode 0 is
+ * bit-identical to d2s_dibr_xr_eyes (the same kernel). */
+typedef struct d2s_xr_glow {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_glow) = 24 */
+    int32_t  mode;             /* 0 off, 1 glow, 2 glow2 */
+    double   range_m;
+    double   inner_edge_fraction;
+} d2s_xr_glow;
+int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                          const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                          void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream);
+
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
  * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.
@@ -513,6 +559,14 @@ int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames, int batch
                                  int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
                                  const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int use_ema,
                                  void* out, int out_fmt, float* depth_full, void* workspace, uint64_t workspace_bytes, void* stream);
+/* d2s_view_pipeline_xr_streams with the glow (d2s_version() >= 119): glow, levels as d2s_dibr_xr_eyes_glow.  levels is the CALLER's
+ * chain of these frames (d2s_mip_chain on the same stream beforehand, or an older one: the reference refreshes its own every few
+ * frames).  Bit-identical to d2s_pipeline(depth_full) followed by d2s_dibr_xr_eyes_glow on the engine's map. */
+int d2s_view_pipeline_xr_glow_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                      int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
+                                      const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int use_ema,
+                                      void* out, int out_fmt, float* depth_full, void* workspace, uint64_t workspace_bytes,
+                                      const d2s_xr_glow* glow, const uint8_t* levels, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

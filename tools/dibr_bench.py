@@ -18,7 +18,11 @@
         d2s_dibr_xr_eyes: the OpenXR screen drawn into two swapchain-size eye images from one 1080p frame (flat, or curved
         horizontally / vertically: 48 facets), against d2s_dibr_warp_crop's gather kernel (D2S_DIBR_NO_ROWS=1, identity crop, both eyes
         at the frame's size) -- the same pixel function on a regular grid.  The screen's distance is set so that the flat screen is
-        one source texel per pixel wide; us per launch and ns per COVERED pixel, alternated in one process."""
+        one source texel per pixel wide; us per launch and ns per COVERED pixel, alternated in one process.
+    python tools/dibr_bench.py --xr-eye --glow glow|glow2 [--glow-range 15.0]
+        d2s_dibr_xr_eyes_glow (the flat screen with the reference's glow in the same launch, every pixel of both eye images drawn) and
+        d2s_mip_chain (the 1080p frame's colour mip chain, which the glow samples), alternated in one process with the flat eye call
+        without glow through the old entry (d2s_dibr_xr_eyes) and through the new one (glow off): us per launch, ns per image pixel."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -40,6 +44,8 @@ ap.add_argument("--corner-radius", type=float, default=0.0, help="--crop: u_corn
 ap.add_argument("--xr-eye", action="store_true", help="time d2s_dibr_xr_eyes against the cropped warp's gather kernel")
 ap.add_argument("--curve", default=None, choices=["h", "v"], help="--xr-eye: the curved screen (horizontal / vertical)")
 ap.add_argument("--eye-size", type=int, nargs=2, default=[2064, 2208], help="--xr-eye: swapchain image width height")
+ap.add_argument("--glow", default=None, choices=["glow", "glow2"], help="--xr-eye: time the glow eye call and mip_chain")
+ap.add_argument("--glow-range", type=float, default=None, help="--glow: range_m (default: xr.glow_range_m of the screen)")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -133,7 +139,36 @@ if a.xr_eye:
     eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
     img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
     dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
-    for B in a.batch:
+    for B in a.batch if a.glow else ():
+        if a.curve:
+            sys.exit("--glow is the flat screen's (the curved glow is not built)")
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        glow = xr.XrGlow(a.glow, a.glow_range if a.glow_range else xr.glow_range_m(screen))
+        levels = ops.mip_chain(f)
+        out = torch.empty(ops.dibr_xr_shape(eyes, B, dp.alpha_mode)[1], dtype=torch.uint8, device=dev)
+        runs = {"eyes_old_entry": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out),
+                "eyes_new_entry_glow_off": lambda: ops.dibr_xr_eyes_glow(f, d, dp, screen, eyes, None, None, out=out),
+                f"eyes_{a.glow}": lambda: ops.dibr_xr_eyes_glow(f, d, dp, screen, eyes, glow, levels, out=out),
+                "eyes_old_entry_again": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out),
+                "mip_chain": lambda: ops.mip_chain(f, out=levels)}
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"xr-eye {a.glow} (range {glow.range_m:.2f} m) {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}, medians of {a.rounds} rounds x {a.iters} launches:", flush=True)
+        for k in runs:
+            per = f"{1e3 * med[k] / (B * 2 * ew * eh):.4f} ns / image pixel" if k != "mip_chain" else f"{B * a.height * a.width * 3 / med[k] / 1e3:.1f} GB/s of the frame"
+            print(f"    {k:26s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {per})", flush=True)
+        print(f"    new entry, glow off - old entry = {med['eyes_new_entry_glow_off'] - med['eyes_old_entry']:+.1f} us; old entry against itself: "
+              f"{med['eyes_old_entry_again'] - med['eyes_old_entry']:+.1f} us", flush=True)
+    for B in () if a.glow else a.batch:
         f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
         d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
         probe = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)      # clear alpha 0.5 marks the uncovered pixels
