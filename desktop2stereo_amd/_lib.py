@@ -122,6 +122,15 @@ class WarpPlanResult(C.Structure):
                 ("waves", C.c_int64), ("kernel", C.c_char * 64)]
 
 
+class PostPlanResult(C.Structure):
+    """d2s_post_plan_result (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_int32), ("launches", C.c_int32), ("k", C.c_int32), ("r", C.c_int32),
+                ("step", C.c_int32), ("m", C.c_int32), ("tail", C.c_int32), ("lds_bytes", C.c_uint32 * 3), ("kernel", (C.c_char * 32) * 3)]
+
+
+POST_FORM = {0: "fused", 1: "tile", 2: "rows"}      # D2S_POST_FORM_*
+
+
 class PrepatchProbeParams(C.Structure):
     """d2s_prepatch_probe_params (include/d2s.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("precision", C.c_int32), ("fmt", C.c_int32), ("batch", C.c_int32), ("H", C.c_int32),
@@ -166,6 +175,7 @@ SYMBOLS = {
     "d2s_post_process": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(PostParams), _P, C.c_uint64, _P]),
     "d2s_post_process_workspace": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
     "d2s_post_process_to": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(PostParams), _P, C.c_uint64, _P]),
+    "d2s_post_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(PostParams), C.c_int, C.POINTER(PostPlanResult)]),
     "d2s_ema_update": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "d2s_upsample_depth": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     "d2s_make_sbs": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -30,12 +30,82 @@ __device__ __forceinline__ float key2f(uint32_t k) {
 // step / m / tail follow from the valid count, and the r-th valid pixel is sample r/step iff r % step == 0.
 __device__ __forceinline__ float metric_inverse(float d) { return d > 0.f ? 1.0f / fmaxf(d, 1e-12f) : d; }
 
+// The subsample of n values under the cap, and the rank of the lower bound in it: the host plans with it (plan_post), the metric
+// kernel restates it for its data-dependent n.
+struct Subsample { int step, m, tail; };
+__host__ __device__ inline Subsample subsample_of(int n, int cap, double lo_q) {
+    Subsample s;
+    s.step = n > cap ? (n + cap - 1) / cap : 1;
+    s.m = (n + s.step - 1) / s.step;
+    s.tail = (int)nearbyint(lo_q * (double)(s.m - 1)) + 1;
+    s.tail = s.tail > s.m ? s.m : s.tail;
+    s.tail = s.tail < 1 ? 1 : s.tail;
+    return s;
+}
+
+typedef unsigned u4_ __attribute__((ext_vector_type(4)));
+
+// WORDS zeros at p, shared among the block's THREADS threads: 16-byte stores (p aligned) where every thread has one, else one word each
+template <int THREADS, int WORDS>
+__device__ __forceinline__ void zero_lds(unsigned* p, int tid) {
+    static_assert(WORDS <= THREADS || WORDS % (4 * THREADS) == 0, "the same number of stores per thread");
+    if constexpr (WORDS > THREADS) {
+#pragma unroll
+        for (int i = 0; i < WORDS / (4 * THREADS); ++i) ((u4_*)p)[tid + i * THREADS] = (u4_){0u, 0u, 0u, 0u};
+    } else if (tid < WORDS) p[tid] = 0u;
+}
+
+// [kmin, kmax] of the block's m keys (thread tid holds keys tid + i * THREADS); one barrier.  m == 0: [~0, 0].  EVERY: in every thread
+// (each reads all the waves' results), else in thread 0 alone, which adds the other waves' to its own.
+template <int THREADS, bool EVERY, int PER>
+__device__ __forceinline__ void block_key_range(const uint32_t (&key)[PER], int m, unsigned* red_min, unsigned* red_max, unsigned& kmin, unsigned& kmax) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    kmin = 0xffffffffu; kmax = 0u;
+#pragma unroll
+    for (int i = 0; i < PER; ++i)
+        if (tid + i * THREADS < m) { kmin = min(kmin, key[i]); kmax = max(kmax, key[i]); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o)); kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o)); }
+    if (lane == 0) { red_min[wid] = kmin; red_max[wid] = kmax; }
+    __syncthreads();
+    if (EVERY || tid == 0)
+        for (int w_ = EVERY ? 0 : 1; w_ < THREADS / 64; ++w_) { kmin = min(kmin, red_min[w_]); kmax = max(kmax, red_max[w_]); }
+}
+
+// One wave scans one histogram of 64 * BINS_PER_LANE bins (16-byte aligned, BINS_PER_LANE consecutive bins per lane).  The lane whose
+// bins hold rank `target` returns hit with the bin, the rank inside it and the bin's count; every other lane returns no hit.
+struct Pick { bool hit; unsigned bin, rank, count; };
+template <int BINS_PER_LANE>
+__device__ __forceinline__ Pick pick_bin(const unsigned* hist, int lane, unsigned target) {
+    constexpr int Q = BINS_PER_LANE / 4;
+    const u4_* hp = (const u4_*)(hist + BINS_PER_LANE * lane);
+    u4_ c[Q];
+    unsigned s_ = 0;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { c[q] = hp[q]; s_ += (c[q][0] + c[q][1]) + (c[q][2] + c[q][3]); }
+    unsigned incl = s_;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+    const unsigned excl = incl - s_;
+    if (target < excl || target >= incl) return Pick{false, 0u, 0u, 0u};
+    unsigned rr = target - excl, b = 0, cnt_b = 0;
+    bool found = false;
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned cnt = c[q][k];
+            if (!found) { if (rr < cnt) { found = true; b = 4 * q + k; cnt_b = cnt; } else rr -= cnt; }
+        }
+    return Pick{true, BINS_PER_LANE * lane + b, rr, cnt_b};
+}
+
 template <bool METRIC>
 __global__ void __launch_bounds__(SORT_THREADS)
 percentile_bounds_kernel(const float* __restrict__ depth, int n, int step, int m, int tail, int cap, double lo_q,
                          float* __restrict__ bounds) {
     constexpr int PER = SORT_N / SORT_THREADS;
-    __shared__ unsigned hist[2][256];
+    __shared__ __attribute__((aligned(16))) unsigned hist[2][256];
     __shared__ unsigned sel_rank[2];
     const float* d = depth + (long)blockIdx.x * n;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -59,10 +129,8 @@ percentile_bounds_kernel(const float* __restrict__ depth, int n, int step, int m
         if (tid == SORT_THREADS - 1) s_nv = base + cnt;
         __syncthreads();
         nvalid = s_nv;
-        step = nvalid > cap ? (nvalid + cap - 1) / cap : 1;
-        m = (nvalid + step - 1) / step;
-        tail = (int)nearbyint(lo_q * (double)(m - 1)) + 1;
-        tail = max(1, min(tail, m));
+        const Subsample sub = subsample_of(nvalid, cap, lo_q);
+        step = sub.step; m = sub.m; tail = sub.tail;
         int r = base;
         for (int i = i0; i < i1; ++i) {
             float v = d[i];
@@ -83,16 +151,9 @@ percentile_bounds_kernel(const float* __restrict__ depth, int n, int step, int m
     __shared__ unsigned red_min[SORT_THREADS / 64], red_max[SORT_THREADS / 64];
     __shared__ unsigned sel_lo[2], sel_shift;
     {
-        unsigned kmin = 0xffffffffu, kmax = 0u;
-#pragma unroll
-        for (int i = 0; i < PER; ++i)
-            if (tid + i * SORT_THREADS < m) { kmin = min(kmin, key[i]); kmax = max(kmax, key[i]); }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o)); kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o)); }
-        if (lane == 0) { red_min[wid] = kmin; red_max[wid] = kmax; }
-        __syncthreads();
+        unsigned kmin, kmax;
+        block_key_range<SORT_THREADS, false>(key, m, red_min, red_max, kmin, kmax);
         if (tid == 0) {
-            for (int w = 1; w < SORT_THREADS / 64; ++w) { kmin = min(kmin, red_min[w]); kmax = max(kmax, red_max[w]); }
             if (m <= 0) { kmin = kmax = 0u; }
             const unsigned span = kmax - kmin;
             const int bits = span ? 32 - __clz((int)span) : 0;              // span < 2^bits
@@ -105,7 +166,7 @@ percentile_bounds_kernel(const float* __restrict__ depth, int n, int step, int m
     }
     while (true) {
         const unsigned shift = sel_shift;
-        if (tid < 512) hist[tid >> 8][tid & 255] = 0;
+        zero_lds<SORT_THREADS, 2 * 256>(&hist[0][0], tid);
         __syncthreads();
         const unsigned l0 = sel_lo[0], l1 = sel_lo[1];
 #pragma unroll
@@ -118,17 +179,8 @@ percentile_bounds_kernel(const float* __restrict__ depth, int n, int step, int m
         }
         __syncthreads();
         if (wid < 2) {                                           // wave r resolves rank r: 4 bins per lane
-            unsigned c0 = hist[wid][4 * lane], c1 = hist[wid][4 * lane + 1], c2 = hist[wid][4 * lane + 2], c3 = hist[wid][4 * lane + 3];
-            unsigned s = c0 + c1 + c2 + c3, incl = s;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-            unsigned excl = incl - s, target = sel_rank[wid];
-            if (target >= excl && target < incl) {
-                unsigned r = target - excl, bin;
-                if (r < c0) bin = 0; else if ((r -= c0) < c1) bin = 1; else if ((r -= c1) < c2) bin = 2; else { r -= c2; bin = 3; }
-                sel_lo[wid] += (4 * lane + bin) << shift;
-                sel_rank[wid] = r;
-            }
+            const Pick pk = pick_bin<4>(hist[wid], lane, sel_rank[wid]);
+            if (pk.hit) { sel_lo[wid] += pk.bin << shift; sel_rank[wid] = pk.rank; }
         }
         __syncthreads();
         if (shift == 0) break;
@@ -164,8 +216,48 @@ __device__ __forceinline__ float shape_depth(float d, float dmin, float dmax, fl
     return fminf(fmaxf(o, 0.f), 1.f);
 }
 
+// One pixel of the shaped map: the raw value is requested first (the one-launch kernel has its bounds only later), then inverted if
+// metric (depth.py:844-846) and shaped; zero outside the image.
+struct ShapeArgs { float dmin, dmax, gamma, fg_exp; bool fg_on, metric; };
+__device__ __forceinline__ float raw_pixel(const float* __restrict__ src, long i, bool inside) { return inside ? src[i] : 0.f; }
+__device__ __forceinline__ float shape_pixel(float v, bool inside, const ShapeArgs& s) {
+    if (!inside) return 0.f;
+    if (s.metric) v = metric_inverse(v);
+    return shape_depth(v, s.dmin, s.dmax, s.gamma, s.fg_exp, s.fg_on);
+}
+
 constexpr int MAX_TAPS = 63;
 struct GaussTaps { int k; float w[MAX_TAPS]; };
+
+// The two tap loops of the separable Gaussian, KT taps known at compile time (unrolled, weights in SGPRs) or KT = 0: nt = taps.k at run
+// time.  Every form of the post-process takes its products from these two in this order, which is why the forms are bit-identical.
+// Horizontal: row points at tap 0 of a zero-padded row (r = nt / 2; nt = 1: no blur, the centre).
+template <int KT>
+__device__ __forceinline__ float hblur_taps(const float* row, const GaussTaps& taps, int nt, int r) {
+    if (nt < 3) return row[r];
+    float acc = 0.f;
+#pragma unroll
+    for (int t = 0; t < nt; ++t) acc += taps.w[t] * row[t];
+    return acc;
+}
+// Vertical: tap t is col[(row0 + t) * stride] and belongs to image row y + t - r; rows outside the image are skipped.
+// (compile-time tap count: all column loads are issued before the first product -- with a run-time count every tap was a scalar
+//  load of its weight plus a dependent global load, 13 round trips per pixel)
+template <int KT>
+__device__ __forceinline__ float vblur_taps(const float* col, long stride, int row0, int y, int h, const GaussTaps& taps, int nt, int r) {
+    float v[KT ? KT : 1];
+    if constexpr (KT != 0) {
+#pragma unroll
+        for (int t = 0; t < KT; ++t) { const int yy = y + t - r; v[t] = (yy >= 0 && yy < h) ? col[(row0 + t) * stride] : 0.f; }
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int t = 0; t < nt; ++t) {
+        const int yy = y + t - r;
+        if (yy >= 0 && yy < h) acc += taps.w[t] * (KT ? v[KT ? t : 0] : col[(row0 + t) * stride]);
+    }
+    return acc;
+}
 
 // normalise + gamma + foreground-scale fused with the horizontal Gaussian pass: one block per row,
 // shaped row staged in LDS (zero padded), k taps out of LDS.
@@ -177,28 +269,16 @@ shape_hblur_kernel(const float* __restrict__ depth, const float* __restrict__ bo
     int y = blockIdx.x % h, b = blockIdx.x / h;
     const int nt = KT ? KT : taps.k;
     int r = nt / 2;
-    float dmin = bounds[2 * b], dmax = bounds[2 * b + 1];
+    const ShapeArgs sa{bounds[2 * b], bounds[2 * b + 1], gamma, fg_exp, fg_on != 0, metric != 0};
     const float* src = depth + ((long)b * h + y) * w;
     for (int i = threadIdx.x; i < w + 2 * r; i += 256) {
-        int x = i - r;
-        float v = 0.f;
-        if (x >= 0 && x < w) {
-            v = src[x];
-            if (metric) v = metric_inverse(v);                                     // depth.py:844-846
-            v = shape_depth(v, dmin, dmax, gamma, fg_exp, fg_on != 0);
-        }
-        row[i] = v;
+        const int x = i - r;
+        const bool inside = x >= 0 && x < w;
+        row[i] = shape_pixel(raw_pixel(src, x, inside), inside, sa);
     }
     __syncthreads();
     float* dst = tmp + ((long)b * h + y) * w;
-    for (int x = threadIdx.x; x < w; x += 256) {
-        float acc = 0.f;
-        if (nt >= 3) {
-#pragma unroll
-            for (int t = 0; t < nt; ++t) acc += taps.w[t] * row[x + t];
-        } else acc = row[x + r];
-        dst[x] = acc;
-    }
+    for (int x = threadIdx.x; x < w; x += 256) dst[x] = hblur_taps<KT>(row + x, taps, nt, r);
 }
 
 template <int KT>
@@ -211,21 +291,8 @@ vblur_kernel(const float* __restrict__ tmp, float* __restrict__ out, int B, int 
     int b = (int)(idx / ((long)w * h));
     const float* p = tmp + (long)b * h * w + x;
     const int nt = KT ? KT : taps.k;
-    int r = nt / 2;
-    // (compile-time tap count: all column loads are issued before the first product -- with a run-time count every tap was a scalar
-    //  load of its weight plus a dependent global load, 13 round trips per pixel)
-    float v[KT ? KT : 1];
-    if constexpr (KT != 0) {
-#pragma unroll
-        for (int t = 0; t < KT; ++t) { const int yy = y + t - r; v[t] = (yy >= 0 && yy < h) ? p[(long)yy * w] : 0.f; }
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int t = 0; t < nt; ++t) {
-        int yy = y + t - r;
-        if (yy >= 0 && yy < h) acc += taps.w[t] * (KT ? v[KT ? t : 0] : p[(long)yy * w]);
-    }
-    out[idx] = acc;
+    const int r = nt / 2;
+    out[idx] = vblur_taps<KT>(p, w, y - r, y, h, taps, nt, r);
 }
 
 // Both passes in one launch (few frames: the two launches above are two launch floors for 0.6 MB): a block owns an 8 x 128 tile, shapes
@@ -241,39 +308,25 @@ shape_blur_kernel(const float* __restrict__ depth_in, const float* __restrict__ 
     float* shp = sb_lds;                 // [HR][WR]
     float* hb = sb_lds + HR * WR;        // [HR][SB_TC]
     const int b = blockIdx.z, y0 = blockIdx.y * SB_TR, x0 = blockIdx.x * SB_TC;
-    const float dmin = bounds[2 * b], dmax = bounds[2 * b + 1];
+    const ShapeArgs sa{bounds[2 * b], bounds[2 * b + 1], gamma, fg_exp, fg_on != 0, metric != 0};
     const float* src = depth_in + (long)b * h * w;
     for (int i = threadIdx.x; i < HR * WR; i += 256) {
         const int ry = i / WR, rx = i - ry * WR;
         const int y = y0 + ry - r, x = x0 + rx - r;
-        float v = 0.f;
-        if (y >= 0 && y < h && x >= 0 && x < w) {
-            v = src[(long)y * w + x];
-            if (metric) v = metric_inverse(v);
-            v = shape_depth(v, dmin, dmax, gamma, fg_exp, fg_on != 0);
-        }
-        shp[i] = v;
+        const bool inside = y >= 0 && y < h && x >= 0 && x < w;
+        shp[i] = shape_pixel(raw_pixel(src, (long)y * w + x, inside), inside, sa);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < HR * SB_TC; i += 256) {
         const int ry = i / SB_TC, cx = i - ry * SB_TC;
-        const float* row = shp + ry * WR + cx;
-        float acc = 0.f;
-        if (taps.k >= 3) { for (int t = 0; t < taps.k; ++t) acc += taps.w[t] * row[t]; }
-        else acc = row[r];
-        hb[i] = acc;
+        hb[i] = hblur_taps<0>(shp + ry * WR + cx, taps, taps.k, r);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < SB_TR * SB_TC; i += 256) {
         const int ty = i / SB_TC, cx = i - ty * SB_TC;
         const int y = y0 + ty, x = x0 + cx;
         if (y >= h || x >= w) continue;
-        float acc = 0.f;
-        for (int t = 0; t < taps.k; ++t) {
-            const int yy = y + t - r;
-            if (yy >= 0 && yy < h) acc += taps.w[t] * hb[(ty + t) * SB_TC + cx];
-        }
-        out[((long)b * h + y) * w + x] = acc;
+        out[((long)b * h + y) * w + x] = vblur_taps<0>(hb + cx, SB_TC, ty, y, h, taps, taps.k, r);
     }
 }
 
@@ -316,31 +369,15 @@ post_fused_kernel(const float* __restrict__ depth_in, float* __restrict__ out, f
             const int ry = wid + 16 * i, rx = lane + 64 * j;
             const int y = y0 + ry - r, x = x0 + rx - r;
             inside[i][j] = ry < HR && rx < WR && y >= 0 && y < h && x >= 0 && x < w;
-            raw[i][j] = inside[i][j] ? src[(long)y * w + x] : 0.f;
+            raw[i][j] = raw_pixel(src, (long)y * w + x, inside[i][j]);
         }
     // (2) the frame's subsample
     uint32_t key[PER];
 #pragma unroll
     for (int i = 0; i < PER; ++i) { const int idx = tid + i * PF_THREADS; key[i] = idx < m ? f2key(src[(long)idx * step]) : 0u; }
-    // both histogram buffers start at zero
-    {
-        typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-        ((u4_*)lds_u)[tid] = (u4_){0u, 0u, 0u, 0u};
-        ((u4_*)lds_u)[tid + PF_THREADS] = (u4_){0u, 0u, 0u, 0u};
-    }
-    unsigned kmin = 0xffffffffu, kmax = 0u;
-#pragma unroll
-    for (int i = 0; i < PER; ++i)
-        if (tid + i * PF_THREADS < m) { kmin = min(kmin, key[i]); kmax = max(kmax, key[i]); }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o)); kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o)); }
-    if (lane == 0) { red_min[wid] = kmin; red_max[wid] = kmax; }
-    __syncthreads();
-#pragma unroll
-    for (int w_ = 0; w_ < PF_THREADS / 64; ++w_) { kmin = min(kmin, red_min[w_]); kmax = max(kmax, red_max[w_]); }
-#if defined(PF_CUT) && PF_CUT == 1              // (tuning aid, tools/build_variant.sh: the kernel ends after phase PF_CUT -- timing only, results wrong)
-    if (kmin == 0x12345u) out[tid] = raw[0][0] + raw[1][2]; return;
-#endif
+    zero_lds<PF_THREADS, 4 * PF_BINS>(lds_u, tid);                      // both histogram buffers start at zero
+    unsigned kmin, kmax;
+    block_key_range<PF_THREADS, true>(key, m, red_min, red_max, kmin, kmax);
     const unsigned span = kmax - kmin;
     const int bits = span ? 32 - __clz((int)span) : 0;                  // span < 2^bits
     int shift = bits > PF_BITS ? bits - PF_BITS : 0;
@@ -378,27 +415,9 @@ post_fused_kernel(const float* __restrict__ depth_in, float* __restrict__ out, f
             if (tid < 2) sel_cnt[tid] = 0u;
             __syncthreads();
             if (wid < 2) {                                              // wave t resolves target t: 32 consecutive bins per lane
-                typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-                const u4_* hp = (const u4_*)(hist + 32 * lane);
-                u4_ c[8];
-                unsigned s_ = 0;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { c[q] = hp[q]; s_ += (c[q][0] + c[q][1]) + (c[q][2] + c[q][3]); }
-                unsigned incl = s_;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-                const unsigned excl = incl - s_, target = wid == 0 ? rk0 : rk1;
-                if (target >= excl && target < incl) {
-                    unsigned rr = target - excl, bin = 0, cnt_b = 0;
-                    bool found = false;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const unsigned cnt = c[q][k];
-                            if (!found) { if (rr < cnt) { found = true; bin = 4 * q + k; cnt_b = cnt; } else rr -= cnt; }
-                        }
-                    const unsigned tb = 32u * lane + bin;
+                const Pick pk = pick_bin<PF_BINS / 64>(hist, lane, wid == 0 ? rk0 : rk1);
+                if (pk.hit) {
+                    const unsigned tb = pk.bin, rr = pk.rank, cnt_b = pk.count;
                     const bool edge = tb == 0u || tb == (unsigned)(PF_BINS - 1);
                     sel_lo[wid] = tb;                                   // (here: the target's BIN)
                     sel_rank[wid] = rr;
@@ -431,9 +450,7 @@ post_fused_kernel(const float* __restrict__ depth_in, float* __restrict__ out, f
             } else {
                 // fall through to the radix passes: they expect both histogram buffers at zero
                 __syncthreads();
-                typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-                ((u4_*)lds_u)[tid] = (u4_){0u, 0u, 0u, 0u};
-                ((u4_*)lds_u)[tid + PF_THREADS] = (u4_){0u, 0u, 0u, 0u};
+                zero_lds<PF_THREADS, 4 * PF_BINS>(lds_u, tid);
                 __syncthreads();
             }
         }
@@ -449,47 +466,21 @@ post_fused_kernel(const float* __restrict__ depth_in, float* __restrict__ out, f
                 if (key[i] >= lo1 && (d1 >> shift) < (unsigned)PF_BINS) atomicAdd(&hist[PF_BINS + (d1 >> shift)], 1u);
             }
         }
-        if (pass >= 1) {                                                // the other buffer (pass - 1's, read for the last time before the barrier behind its scan)
-            typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-            ((u4_*)(lds_u + ((pass + 1) & 1) * (2 * PF_BINS)))[tid] = (u4_){0u, 0u, 0u, 0u};
-        }
+        // the other buffer (pass - 1's, read for the last time before the barrier behind its scan)
+        if (pass >= 1) zero_lds<PF_THREADS, 2 * PF_BINS>(lds_u + ((pass + 1) & 1) * (2 * PF_BINS), tid);
         __syncthreads();
         if (wid < 2) {                                                  // wave t resolves target t: 32 consecutive bins per lane
-            typedef unsigned u4_ __attribute__((ext_vector_type(4)));
-            const u4_* hp = (const u4_*)(hist + wid * PF_BINS + 32 * lane);
-            u4_ c[8];
-            unsigned s_ = 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { c[q] = hp[q]; s_ += (c[q][0] + c[q][1]) + (c[q][2] + c[q][3]); }
-            unsigned incl = s_;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-            const unsigned excl = incl - s_, target = wid == 0 ? rk0 : rk1;
-            if (target >= excl && target < incl) {
-                unsigned rr = target - excl, bin = 0;
-                bool found = false;
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const unsigned cnt = c[q][k];
-                        if (!found) { if (rr < cnt) { found = true; bin = 4 * q + k; } else rr -= cnt; }
-                    }
-                sel_lo[wid] = (wid == 0 ? lo0 : lo1) + ((32u * lane + bin) << shift);
-                sel_rank[wid] = rr;
-            }
+            const Pick pk = pick_bin<PF_BINS / 64>(hist + wid * PF_BINS, lane, wid == 0 ? rk0 : rk1);
+            if (pk.hit) { sel_lo[wid] = (wid == 0 ? lo0 : lo1) + (pk.bin << shift); sel_rank[wid] = pk.rank; }
         }
         __syncthreads();
         lo0 = sel_lo[0]; lo1 = sel_lo[1]; rk0 = sel_rank[0]; rk1 = sel_rank[1];
         if (shift == 0) break;
         shift = shift > PF_BITS ? shift - PF_BITS : 0;
     }
-#if defined(PF_CUT) && PF_CUT == 2
-    if (lo0 == 0x12345u) out[tid] = raw[0][0] + raw[1][2]; return;
-#endif
-    float dmin = key2f(lo0), dmax = key2f(lo1);
-    if (h * w <= 10) { dmin = 0.f; dmax = 0.f; }                     // depth.py:852-854
-    if (bounds_out && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) { bounds_out[2 * b] = dmin; bounds_out[2 * b + 1] = dmax; }
+    ShapeArgs sa{key2f(lo0), key2f(lo1), gamma, fg_exp, fg_on != 0, false};
+    if (h * w <= 10) { sa.dmin = 0.f; sa.dmax = 0.f; }               // depth.py:852-854
+    if (bounds_out && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) { bounds_out[2 * b] = sa.dmin; bounds_out[2 * b + 1] = sa.dmax; }
     // (3) shape the window into LDS (zero outside the image: what the two-pass form's zero padding / skipped rows see)
     float* shp = (float*)lds_u;                  // [HR][WR]
     float* hb = shp + HR * WR;                   // [HR][PF_TC]
@@ -498,45 +489,23 @@ post_fused_kernel(const float* __restrict__ depth_in, float* __restrict__ out, f
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int ry = wid + 16 * i, rx = lane + 64 * j;
-            if (ry < HR && rx < WR) shp[ry * WR + rx] = inside[i][j] ? shape_depth(raw[i][j], dmin, dmax, gamma, fg_exp, fg_on != 0) : 0.f;
+            if (ry < HR && rx < WR) shp[ry * WR + rx] = shape_pixel(raw[i][j], inside[i][j], sa);
         }
     __syncthreads();
-#if defined(PF_CUT) && PF_CUT == 3
-    if (shp[tid] == 123.f) out[tid] = 1.f; return;
-#endif
     // (4) horizontal pass: rows wid, wid + 16; columns lane, lane + 64
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int ry = wid + 16 * i, cx = lane + 64 * j;
-            if (ry < HR) {
-                const float* row = shp + ry * WR + cx;
-                float acc = 0.f;
-                if (nt >= 3) {
-#pragma unroll
-                    for (int t = 0; t < nt; ++t) acc += taps.w[t] * row[t];
-                } else acc = row[r];
-                hb[ry * PF_TC + cx] = acc;
-            }
+            if (ry < HR) hb[ry * PF_TC + cx] = hblur_taps<KT>(shp + ry * WR + cx, taps, nt, r);
         }
     __syncthreads();
-#if defined(PF_CUT) && PF_CUT == 4
-    if (hb[tid] == 123.f) out[tid] = 1.f; return;
-#endif
     // (5) vertical pass: one output per thread
     {
         const int ty = wid >> 1, cx = (wid & 1) * 64 + lane;
         const int y = y0 + ty, x = x0 + cx;
-        if (y < h && x < w) {
-            float acc = 0.f;
-#pragma unroll
-            for (int t = 0; t < nt; ++t) {
-                const int yy = y + t - r;
-                if (yy >= 0 && yy < h) acc += taps.w[t] * hb[(ty + t) * PF_TC + cx];
-            }
-            out[((long)b * h + y) * w + x] = acc;
-        }
+        if (y < h && x < w) out[((long)b * h + y) * w + x] = vblur_taps<KT>(hb + cx, PF_TC, ty, y, h, taps, nt, r);
     }
 }
 
@@ -577,80 +546,109 @@ extern "C" uint64_t d2s_post_process_workspace(int batch, int h, int w) {
     return (uint64_t)batch * h * w * sizeof(float) + (uint64_t)batch * 2 * sizeof(float) + 256;
 }
 
+// Everything d2s_post_process_to decides, stated once on the host (d2s_post_plan reports it; the tests pin it).  Three forms compute the
+// same bits; each is the one production takes for some input:
+//   fused  post_fused_kernel, one launch: relative models, <= D2S_POST_FUSE_MAXB (2) frames, out of place, r <= 8;
+//   tile   percentile_bounds_kernel + shape_blur_kernel: metric models or r > 8, few frames, out of place (tiles tap their neighbours'
+//          inputs, so never in place), the (8 + 2r) x (128 + 2r) window and its blurred rows within 64 KiB of LDS;
+//   rows   percentile_bounds_kernel + shape_hblur_kernel + vblur_kernel: more frames (the tile forms re-shape the window borders,
+//          1.8 x the pow() work: +0.6 % at batch 1, -0.7 % at 4), in place, or a tile too large for LDS.
+// D2S_POST_ONE=0 takes the fused form out, D2S_POST_FUSE_MAXB=0 both tile forms: the tests hold the forms to each other that way.
+struct PostLaunch { const char* name; dim3 grid, block; size_t lds; };
+struct PostPlan {
+    Subsample sub; double lo_q;            // (metric: the kernel derives its own from the valid count)
+    GaussTaps taps; int r; bool k13;       // k13: the <13> tap instantiation, else <0> = run-time count
+    int fg_on; float fg_exp;
+    int form, nlaunch; PostLaunch launch[3];
+};
+// Gaussian taps: k = int(3 s) | 1, sigma = 0.5 s, float32 like the reference (depth.py:746-758)
+static int gauss_k(const d2s_post_params* p) { return ((int)(3.0f * p->aa_strength)) | 1; }
+static int check_post_params(const d2s_post_params* p) {
+    D2S_REQUIRE(p->subsample_cap > 0 && p->subsample_cap <= SORT_N, "subsample_cap must be <= 8192");
+    D2S_REQUIRE(p->foreground_scale > -1.0f + 1e-12f, "scale must be greater than -1.0");   // depth.py:726-727
+    D2S_REQUIRE(gauss_k(p) <= MAX_TAPS, "aa_strength too large");
+    return D2S_OK;
+}
+static PostPlan plan_post(int batch, int h, int w, const d2s_post_params* p, bool in_place) {
+    PostPlan pl;
+    pl.lo_q = fmax(0.0, fmin(1.0, (double)p->percentile / 100.0));
+    pl.sub = subsample_of(h * w, p->subsample_cap, pl.lo_q);
+    const int k = gauss_k(p);
+    pl.taps.k = k >= 3 ? k : 1;
+    if (k >= 3) {
+        float sigma = 0.5f * p->aa_strength, sum = 0.f;
+        for (int i = 0; i < k; ++i) { float c = (float)(i - k / 2); pl.taps.w[i] = expf(-(c * c) / (2.f * sigma * sigma)); sum += pl.taps.w[i]; }
+        for (int i = 0; i < k; ++i) pl.taps.w[i] /= sum;
+    } else pl.taps.w[0] = 1.f;
+    pl.fg_on = fabsf(p->foreground_scale) >= 1e-6f;
+    pl.fg_exp = 1.0f / (1.0f + p->foreground_scale);
+    const int r = pl.r = pl.taps.k / 2;
+    const bool k13 = pl.k13 = pl.taps.k == 13;
+    static EnvInt fuse_max{"D2S_POST_FUSE_MAXB", 2}, one_launch{"D2S_POST_ONE", 1};
+    const size_t sb_bytes = ((size_t)(SB_TR + 2 * r) * (SB_TC + 2 * r) + (size_t)(SB_TR + 2 * r) * SB_TC) * sizeof(float);
+    const bool few = !in_place && batch <= fuse_max.get() && batch <= 65535;
+    const PostLaunch bounds{p->metric ? "percentile_bounds<metric>" : "percentile_bounds<relative>", dim3(batch), dim3(SORT_THREADS), 0};
+    if (one_launch.get() && !p->metric && few && r <= PF_MAXR && cdiv(h, PF_TR) <= 65535) {
+        pl.form = D2S_POST_FORM_FUSED; pl.nlaunch = 1;
+        pl.launch[0] = {k13 ? "post_fused<13>" : "post_fused<0>", dim3(cdiv(w, PF_TC), cdiv(h, PF_TR), batch), dim3(PF_THREADS), 0};
+    } else if (few && sb_bytes <= 64 * 1024 && cdiv(h, SB_TR) <= 65535) {
+        pl.form = D2S_POST_FORM_TILE; pl.nlaunch = 2;
+        pl.launch[0] = bounds;
+        pl.launch[1] = {"shape_blur", dim3(cdiv(w, SB_TC), cdiv(h, SB_TR), batch), dim3(256), sb_bytes};
+    } else {
+        pl.form = D2S_POST_FORM_ROWS; pl.nlaunch = 3;
+        pl.launch[0] = bounds;
+        pl.launch[1] = {k13 ? "shape_hblur<13>" : "shape_hblur<0>", dim3(batch * h), dim3(256), (w + 2 * r) * sizeof(float)};
+        pl.launch[2] = {k13 ? "vblur<13>" : "vblur<0>", dim3(cdiv((long)batch * h * w, 256)), dim3(256), 0};
+    }
+    return pl;
+}
+
+static void launch_post(const PostPlan& pl, const float* depth, float* depth_out, int batch, int h, int w, const d2s_post_params* p,
+                        float* tmp, float* bounds, hipStream_t st) {
+    const PostLaunch* L = pl.launch;
+    const bool k13 = pl.k13;
+    const int metric = p->metric != 0;
+    auto go = [st](auto kernel, const PostLaunch& l, auto... args) { hipLaunchKernelGGL(kernel, l.grid, l.block, l.lds, st, args...); };
+    if (pl.form == D2S_POST_FORM_FUSED)
+        return go(k13 ? post_fused_kernel<13> : post_fused_kernel<0>, L[0], depth, depth_out, bounds, h, w, pl.sub.step, pl.sub.m, pl.sub.tail,
+                  p->gamma, pl.fg_exp, pl.fg_on, pl.taps);
+    go(metric ? percentile_bounds_kernel<true> : percentile_bounds_kernel<false>, L[0], depth, h * w, pl.sub.step, pl.sub.m, pl.sub.tail,
+       p->subsample_cap, pl.lo_q, bounds);
+    if (pl.form == D2S_POST_FORM_TILE) return go(shape_blur_kernel, L[1], depth, bounds, depth_out, h, w, p->gamma, pl.fg_exp, pl.fg_on, metric, pl.taps);
+    go(k13 ? shape_hblur_kernel<13> : shape_hblur_kernel<0>, L[1], depth, bounds, tmp, h, w, p->gamma, pl.fg_exp, pl.fg_on, metric, pl.taps);
+    go(k13 ? vblur_kernel<13> : vblur_kernel<0>, L[2], tmp, depth_out, batch, h, w, pl.taps);
+}
+
 extern "C" int d2s_post_process_to(const float* depth_in, float* depth_out, int batch, int h, int w, const d2s_post_params* p,
                                    void* workspace, uint64_t workspace_bytes, void* stream) {
-    const float* depth = depth_in;
     D2S_REQUIRE(depth_in && depth_out && p && workspace, "null pointer");
     D2S_REQUIRE(batch > 0 && h > 0 && w > 0, "bad shape");
     D2S_REQUIRE(workspace_bytes >= d2s_post_process_workspace(batch, h, w), "workspace too small");
-    D2S_REQUIRE(p->subsample_cap > 0 && p->subsample_cap <= SORT_N, "subsample_cap must be <= 8192");
-    D2S_REQUIRE(p->foreground_scale > -1.0f + 1e-12f, "scale must be greater than -1.0");   // depth.py:726-727
-    hipStream_t st = (hipStream_t)stream;
-    float* tmp = (float*)workspace;
-    float* bounds = (float*)((char*)workspace + (((uint64_t)batch * h * w * sizeof(float) + 255) & ~255ull));
-    int n = h * w;
-    int step = 1, m = n;
-    if (n > p->subsample_cap) { step = (n + p->subsample_cap - 1) / p->subsample_cap; m = (n + step - 1) / step; }
-    double lo_q = fmax(0.0, fmin(1.0, (double)p->percentile / 100.0));
-    int tail = (int)nearbyint(lo_q * (m - 1)) + 1;
-    if (tail < 1) tail = 1;
-    if (tail > m) tail = m;
-    auto launch_percentile = [&]() {
-        if (p->metric)
-            hipLaunchKernelGGL(percentile_bounds_kernel<true>, dim3(batch), dim3(SORT_THREADS), 0, st, depth, n, step, m, tail,
-                               p->subsample_cap, lo_q, bounds);
-        else
-            hipLaunchKernelGGL(percentile_bounds_kernel<false>, dim3(batch), dim3(SORT_THREADS), 0, st, depth, n, step, m, tail,
-                               p->subsample_cap, lo_q, bounds);
-    };
-    // Gaussian taps: k = int(3 s) | 1, sigma = 0.5 s, float32 like the reference (depth.py:746-758)
-    GaussTaps taps;
-    int k = ((int)(3.0f * p->aa_strength)) | 1;
-    D2S_REQUIRE(k <= MAX_TAPS, "aa_strength too large");
-    taps.k = k >= 3 ? k : 1;
-    if (k >= 3) {
-        float sigma = 0.5f * p->aa_strength, sum = 0.f;
-        for (int i = 0; i < k; ++i) { float c = (float)(i - k / 2); taps.w[i] = expf(-(c * c) / (2.f * sigma * sigma)); sum += taps.w[i]; }
-        for (int i = 0; i < k; ++i) taps.w[i] /= sum;
-    } else taps.w[0] = 1.f;
-    int fg_on = fabsf(p->foreground_scale) >= 1e-6f;
-    float fg_exp = 1.0f / (1.0f + p->foreground_scale);
-    int r = taps.k / 2;
-    // out of place and few frames: one launch for both passes (tiles tap their neighbours' inputs, so never in place)
-    static EnvInt fuse_max{"D2S_POST_FUSE_MAXB", 2};        // (it re-shapes the window borders, 1.8 x the pow() work: +0.6 % at batch 1, -0.7 % at 4)
-    const size_t sb_bytes = ((size_t)(SB_TR + 2 * r) * (SB_TC + 2 * r) + (size_t)(SB_TR + 2 * r) * SB_TC) * sizeof(float);
-    {   // in place (equal pointers) or disjoint: a partially overlapping pair would be corrupted silently by either form below
+    if (const int rc = check_post_params(p)) return rc;
+    {   // in place (equal pointers) or disjoint: a partially overlapping pair would be corrupted silently by every form
         const char *i0 = (const char*)depth_in, *o0 = (const char*)depth_out;
         const size_t nb = (size_t)batch * h * w * sizeof(float);
         D2S_REQUIRE(depth_out == depth_in || i0 + nb <= o0 || o0 + nb <= i0, "d2s_post_process_to: depth_in and depth_out overlap without being equal");
     }
-    // round 5: bounds + shape + both blurs in ONE launch (relative models, few frames): post_fused_kernel
-    static EnvInt one_launch{"D2S_POST_ONE", 1};
-    if (one_launch.get() && !p->metric && depth_out != depth_in && batch <= fuse_max.get() && r <= PF_MAXR && cdiv(h, PF_TR) <= 65535 && batch <= 65535) {
-        if (taps.k == 13) hipLaunchKernelGGL(post_fused_kernel<13>, dim3(cdiv(w, PF_TC), cdiv(h, PF_TR), batch), dim3(PF_THREADS), 0, st,
-                                             depth, depth_out, bounds, h, w, step, m, tail, p->gamma, fg_exp, fg_on, taps);
-        else hipLaunchKernelGGL(post_fused_kernel<0>, dim3(cdiv(w, PF_TC), cdiv(h, PF_TR), batch), dim3(PF_THREADS), 0, st,
-                                depth, depth_out, bounds, h, w, step, m, tail, p->gamma, fg_exp, fg_on, taps);
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-    launch_percentile();
-    if (depth_out != depth_in && batch <= fuse_max.get() && sb_bytes <= 64 * 1024 && cdiv(h, SB_TR) <= 65535 && batch <= 65535) {
-        hipLaunchKernelGGL(shape_blur_kernel, dim3(cdiv(w, SB_TC), cdiv(h, SB_TR), batch), dim3(256), sb_bytes, st,
-                           depth, bounds, depth_out, h, w, p->gamma, fg_exp, fg_on, p->metric != 0, taps);
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-    if (taps.k == 13) {
-        hipLaunchKernelGGL(shape_hblur_kernel<13>, dim3(batch * h), dim3(256), (w + 2 * r) * sizeof(float), st,
-                           depth, bounds, tmp, h, w, p->gamma, fg_exp, fg_on, p->metric != 0, taps);
-        hipLaunchKernelGGL(vblur_kernel<13>, dim3(cdiv((long)batch * h * w, 256)), dim3(256), 0, st, tmp, depth_out, batch, h, w, taps);
-    } else {
-        hipLaunchKernelGGL(shape_hblur_kernel<0>, dim3(batch * h), dim3(256), (w + 2 * r) * sizeof(float), st,
-                           depth, bounds, tmp, h, w, p->gamma, fg_exp, fg_on, p->metric != 0, taps);
-        hipLaunchKernelGGL(vblur_kernel<0>, dim3(cdiv((long)batch * h * w, 256)), dim3(256), 0, st, tmp, depth_out, batch, h, w, taps);
-    }
+    float* tmp = (float*)workspace;
+    float* bounds = (float*)((char*)workspace + (((uint64_t)batch * h * w * sizeof(float) + 255) & ~255ull));
+    launch_post(plan_post(batch, h, w, p, depth_out == depth_in), depth_in, depth_out, batch, h, w, p, tmp, bounds, (hipStream_t)stream);
     D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+extern "C" int d2s_post_plan(int batch, int h, int w, const d2s_post_params* p, int in_place, d2s_post_plan_result* res) {
+    D2S_REQUIRE(p && res, "null pointer");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_post_plan_result), "d2s_post_plan_result.struct_size must be sizeof(d2s_post_plan_result)");
+    D2S_REQUIRE(batch > 0 && h > 0 && w > 0, "bad shape");
+    if (const int rc = check_post_params(p)) return rc;
+    const PostPlan pl = plan_post(batch, h, w, p, in_place != 0);
+    *res = d2s_post_plan_result{sizeof(d2s_post_plan_result), pl.form, pl.nlaunch, pl.taps.k, pl.r, pl.sub.step, pl.sub.m, pl.sub.tail, {}, {}};
+    for (int i = 0; i < pl.nlaunch; ++i) {
+        res->lds_bytes[i] = (uint32_t)pl.launch[i].lds;
+        snprintf(res->kernel[i], sizeof(res->kernel[i]), "%s", pl.launch[i].name);
+    }
     return D2S_OK;
 }
 

@@ -185,10 +185,10 @@ def preprocess(frames: torch.Tensor, target: int, patch: int = 14, mean=IMAGENET
     return out
 
 
-def post_process_depth(depth: torch.Tensor, p: PipelineParams) -> torch.Tensor:
-    """A10-A11 (reference depth.py:806-814) on float32 [B,h,w] or [h,w]; returns a new tensor."""
+def _post_process(depth: torch.Tensor, p: PipelineParams, in_place: bool) -> torch.Tensor:
     _need_cuda(depth, "depth")
-    d = depth.to(torch.float32).contiguous().clone()
+    d = depth.to(torch.float32).contiguous()
+    out = d.clone() if in_place else torch.empty_like(d)
     B = d.shape[0] if d.dim() == 3 else 1
     h, w = d.shape[-2:]
     lib = _lib.load()
@@ -196,24 +196,32 @@ def post_process_depth(depth: torch.Tensor, p: PipelineParams) -> torch.Tensor:
     ws = torch.empty(nbytes, dtype=torch.uint8, device=d.device)
     pp = post_params(p)
     with _on(d.device) as st:
-        check(lib.d2s_post_process(_ptr(d), B, h, w, C.byref(pp), _ptr(ws), nbytes, st), "d2s_post_process")
-    return d
+        if in_place:
+            check(lib.d2s_post_process(_ptr(out), B, h, w, C.byref(pp), _ptr(ws), nbytes, st), "d2s_post_process")
+        else:
+            check(lib.d2s_post_process_to(_ptr(d), _ptr(out), B, h, w, C.byref(pp), _ptr(ws), nbytes, st), "d2s_post_process_to")
+    return out
+
+
+def post_process_depth(depth: torch.Tensor, p: PipelineParams) -> torch.Tensor:
+    """A10-A11 (reference depth.py:806-814) on float32 [B,h,w] or [h,w]; returns a new tensor (the library works in place on a copy)."""
+    return _post_process(depth, p, True)
 
 
 def post_process_depth_to(depth: torch.Tensor, p: PipelineParams) -> torch.Tensor:
-    """The same through d2s_post_process_to (out of place: with few frames the one-launch form runs); the input is left untouched."""
-    _need_cuda(depth, "depth")
-    d = depth.to(torch.float32).contiguous()
-    out = torch.empty_like(d)
-    B = d.shape[0] if d.dim() == 3 else 1
-    h, w = d.shape[-2:]
-    lib = _lib.load()
-    nbytes = lib.d2s_post_process_workspace(B, h, w)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=d.device)
+    """The same out of place (with few frames the one-launch form runs); the input is left untouched."""
+    return _post_process(depth, p, False)
+
+
+def post_plan(batch: int, h: int, w: int, p: PipelineParams, in_place: bool = False) -> dict:
+    """What d2s_post_process_to would launch for these arguments (include/d2s.h d2s_post_plan; host code, no GPU): the form, the kernel
+    names and their dynamic LDS bytes, the taps and the subsample."""
+    r = _lib.PostPlanResult()
+    r.struct_size = C.sizeof(_lib.PostPlanResult)
     pp = post_params(p)
-    with _on(d.device) as st:
-        check(lib.d2s_post_process_to(_ptr(d), _ptr(out), B, h, w, C.byref(pp), _ptr(ws), nbytes, st), "d2s_post_process_to")
-    return out
+    check(_lib.load().d2s_post_plan(int(batch), int(h), int(w), C.byref(pp), int(bool(in_place)), C.byref(r)), "d2s_post_plan")
+    return {"form": _lib.POST_FORM[r.form], "kernels": [r.kernel[i].value.decode() for i in range(r.launches)],
+            "lds_bytes": list(r.lds_bytes[:r.launches]), "k": r.k, "r": r.r, "step": r.step, "m": r.m, "tail": r.tail}
 
 
 def ema_update(depth: torch.Tensor, state: torch.Tensor, initialised: bool, alpha: float) -> torch.Tensor:

@@ -292,6 +292,23 @@ uint64_t d2s_post_process_workspace(int batch, int h, int w);
  * step and both blur passes run as one launch. */
 int d2s_post_process_to(const float* depth_in, float* depth_out, int batch, int h, int w, const d2s_post_params* p,
                         void* workspace, uint64_t workspace_bytes, void* stream);
+/* What d2s_post_process_to would launch for these arguments (d2s_version() >= 120; pure host code: launches nothing, needs no GPU);
+ * in_place: depth_out == depth_in, i.e. d2s_post_process.  Three forms compute the same bits: FUSED = one launch ("post_fused<13>" /
+ * "post_fused<0>": 13 taps at compile time, the default aa_strength 4, or a run-time count), TILE = "percentile_bounds<relative>" /
+ * "percentile_bounds<metric>" + "shape_blur", ROWS = percentile_bounds + "shape_hblur<13|0>" + "vblur<13|0>".  k = taps (1: no
+ * blur), r = k / 2; lds_bytes = each launch's dynamic LDS.  step, m, tail: the subsample of h * w pixels (every step-th, m of them)
+ * and the rank of the lower bound in it -- for metric parameters the kernel derives its own from the number of valid pixels, which
+ * depends on the data: the values here are the host's, for h * w valid pixels.  Refuses what d2s_post_process_to refuses of p. */
+enum { D2S_POST_FORM_FUSED = 0, D2S_POST_FORM_TILE = 1, D2S_POST_FORM_ROWS = 2 };
+typedef struct d2s_post_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_post_plan_result) */
+    int32_t form, launches;    /* D2S_POST_FORM_*; 1 .. 3 */
+    int32_t k, r;
+    int32_t step, m, tail;
+    uint32_t lds_bytes[3];
+    char kernel[3][32];
+} d2s_post_plan_result;
+int d2s_post_plan(int batch, int h, int w, const d2s_post_params* p, int in_place, d2s_post_plan_result* res);
 
 /* A12: DepthStabilizer.__call__ (reference depth.py:1865-1887).  state: float [h,w] owned by the
  * caller; *initialised == 0 -> state = depth (first frame), else state = lerp(state, depth, 1-alpha);
