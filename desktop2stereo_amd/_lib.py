@@ -131,6 +131,22 @@ class PostPlanResult(C.Structure):
 POST_FORM = {0: "fused", 1: "tile", 2: "rows"}      # D2S_POST_FORM_*
 
 
+class ForwardPlanResult(C.Structure):
+    """d2s_forward_plan_result (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("f8", C.c_int32), ("f8a", C.c_int32), ("x3", C.c_int32), ("lnf", C.c_int32),
+                ("pp_fold", C.c_int32), ("tap_fold", C.c_int32), ("use_side", C.c_int32), ("ln_slots", C.c_int32 * 2),
+                ("site", C.c_int32 * 11), ("tap_side", C.c_int32 * 4), ("head1_ups", C.c_int32), ("head2_fused", C.c_int32),
+                ("head2_ups", C.c_int32), ("bn", C.c_int32), ("tm_fold", C.c_int32), ("tm_cache_store", C.c_int32),
+                ("tm_slots", (C.c_int32 * 3) * 4), ("tm_folded", (C.c_int32 * 3) * 4), ("gh", C.c_int32), ("gw", C.c_int32),
+                ("P", C.c_int32), ("N", C.c_int32), ("Npad", C.c_int32), ("fH", C.c_int32 * 4), ("fW", C.c_int32 * 4),
+                ("tm_C", C.c_int32 * 4), ("tm_sites", C.c_int32 * 4), ("ln_launches", C.c_int32),
+                ("splitk_elems", C.c_uint64), ("scr_elems", C.c_uint64)]
+
+
+PLAN_FLAGS = {"calibrating": 1, "profiling": 2, "window_filled": 4, "calibrated": 8}      # D2S_PLAN_*
+PLAN_SITES = ("patch", "qkv0", "qkv", "proj", "fc1", "fc2", "fc2_last", "neck0", "neck1", "neck2", "neck3")      # D2S_PLAN_SITE_*
+
+
 class PrepatchProbeParams(C.Structure):
     """d2s_prepatch_probe_params (include/d2s.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("precision", C.c_int32), ("fmt", C.c_int32), ("batch", C.c_int32), ("H", C.c_int32),
@@ -172,6 +188,7 @@ SYMBOLS = {
     "d2s_model_forward_streams": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "d2s_engine_reset_stream_at": (C.c_int, [_P, C.c_int]),
     "d2s_engine_calibrate": (C.c_int, [_P, _P, C.c_int, _P]),
+    "d2s_forward_plan": (C.c_int, [C.POINTER(ModelDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ForwardPlanResult)]),
     "d2s_post_process": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(PostParams), _P, C.c_uint64, _P]),
     "d2s_post_process_workspace": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
     "d2s_post_process_to": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(PostParams), _P, C.c_uint64, _P]),

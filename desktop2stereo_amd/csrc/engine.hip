@@ -8,7 +8,7 @@
 #include <cstring>
 
 #include "gemm.h"
-#include "linear_site.h"
+#include "forward_plan.h"
 #include "vit_ops.h"
 
 using namespace d2s;
@@ -32,7 +32,8 @@ struct d2s_engine {
     int wprec = D2S_PREC_BF16;         // weight packing and GEMM operand precision: = prec, or D2S_PREC_BF16X3 (on fp32 activations)
     std::map<std::string, HostT> host;
     bool finalized = false;
-    int h = 0, w = 0, gh = 0, gw = 0, P = 0, N = 0, Npad = 0, maxB = 0;
+    int h = 0, w = 0, maxB = 0;
+    EngineGeom g = {};                 // token grid, neck maps, workspace sizes (forward_plan.h engine_geom)
     uint64_t bytes = 0;
     std::vector<void*> allocs;
 
@@ -54,15 +55,12 @@ struct d2s_engine {
     void* rproj[4] = {nullptr, nullptr, nullptr, nullptr};
     void* rres[4] = {nullptr, nullptr, nullptr, nullptr};
     void* feat[4] = {nullptr, nullptr, nullptr, nullptr};
-    int fH[4], fW[4];
     void* scr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float* splitk_ws = nullptr;                    // fp32 partials for split-K launches (tiny-M, long-K DPT convs)
-    size_t splitk_elems = 0;
     // Neck branches of taps 0..2 (+ the RCU1 of their fusion layer) only depend on their tap, not on later encoder
     // layers: they run on a second stream under the remaining layers (batch 1 leaves most CUs idle per launch).
     hipStream_t side = nullptr;
     hipEvent_t ev_tap[4] = {nullptr, nullptr, nullptr, nullptr}, ev_ln[4] = {nullptr, nullptr, nullptr, nullptr}, ev_side = nullptr;
-    int tap_slots = 0;                             // column blocks of the statistics the folded tap projection reads
     bool overlap = true;
     float* splitk_ws_side = nullptr;               // the side stream's own split-K partials
     void* r1[3] = {nullptr, nullptr, nullptr};     // RCU1(feat[i]) = feat[i] + conv2(relu(conv1(relu(feat[i])))), i = 0..2
@@ -267,16 +265,23 @@ void interp_pos(const float* pos, int grid, int D, int gh, int gw, std::vector<f
     }
 }
 
-GemmA plainA(const void* p, long lda) { GemmA a = {}; a.ptr = p; a.mode = A_PLAIN; a.lda = lda; return a; }
-GemmA splitA(const void* p, long lda, bool split) { GemmA a = plainA(p, lda); a.bx3 = split ? 1 : 0; return a; }   // bf16x3 engines: pre-split rows
-GemmA convA(const void* p, int Hi, int Wi, int C, int Ho, int Wo, int stride, int relu) {
-    GemmA a = {}; a.ptr = p; a.mode = A_CONV3; a.Hi = Hi; a.Wi = Wi; a.C = C; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.relu = relu; return a;
+// the engine state plan_forward decides on
+FrameState frame_state(const d2s_engine* e) {
+    return FrameState{e->calib, e->fp8_ready, e->taps, e->prof_on, e->overlap && e->side != nullptr, e->no_lnfuse, e->tm_fold};
+}
+
+// The slot guard: a LayerNorm producer reported another number of statistics partials than plan_forward took from plan_gemm for the
+// same launch -- plan and launch have drifted apart, and the consumer behind it would read the wrong slots
+int slots_check(int got, int planned, const char* site) {
+    if (got == planned) return D2S_OK;
+    set_error(std::string("forward: ") + site + " left " + std::to_string(got) + " LayerNorm statistics slots, the frame's plan says " + std::to_string(planned));
+    return D2S_E_STATE;
 }
 
 // a packed linear (convA: an implicit-GEMM convolution): launch_linear with the split-K partials of its stream, each has its own
 int linear(d2s_engine* e, const GemmA& a, const DevLinear& w, int M, const GemmEpi& ep, hipStream_t st) {
     float* ws = (e->side && st == e->side) ? e->splitk_ws_side : e->splitk_ws;
-    PROF(a.mode == A_CONV3 ? PC_CONV : PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_linear(w, a, M, ep, ws, e->splitk_elems, 0, st));
+    PROF(a.mode == A_CONV3 ? PC_CONV : PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_linear(w, a, M, ep, ws, e->g.splitk_elems, 0, st));
     return D2S_OK;
 }
 
@@ -304,36 +309,36 @@ void window_rows(const d2s_engine::TSlot& sl, bool fold, void* ring, AttnRow& at
 // One streaming TemporalModule on NHWC maps x [B][sites, C] -> out; row r is the next frame of stream slot e->row_ids[r] and reads, then
 // updates, that slot's ring caches.  The linears, LayerNorms and GEGLU see M = B sites rows; GroupNorm, the attention and the ring
 // stores are per row.  (reference motion_module.py:102-134, 164-196, 242-321; cache semantics vda2_s.py:177-218)
-int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStream_t st, const void* add = nullptr) {   // out = module(x) [+ add]
+int run_temporal(d2s_engine* e, const ForwardPlan& pl, int m, const void* x, void* out, int B, hipStream_t st, const void* add = nullptr) {   // out = module(x) [+ add]
     d2s_engine::TMod& t = e->tm[m];
     const int C = t.C, S = B * t.sites, prec = e->prec;   // S: rows of every token matrix of this call
     const int* ids = e->row_ids;
-    // Round 5, bf16 engine (D2S_VDA_FUSE=0 restores round 4's 18 launches per module): (i) the three LayerNorms live in the linears
+    // bf16 engine (D2S_VDA_FUSE=0: 18 launches per module instead of 11): (i) the three LayerNorms live in the linears
     // either side of them -- the residual-update GEMM (proj_in, to_out) also leaves the raw residual as bf16 in tm_a and the row
     // statistics in tm_stats, the consumer (kvq, ff1) runs on gamma-folded weights (section 3.1b's algebra, eps 1e-5); (ii) the ring
     // store of a frame's k' | v' rows happens inside the attention kernel (the lanes that read the oldest slot's segment overwrite it
     // once both of their passes over it are done); (iii) ff2's epilogue leaves the bf16 copy proj_out reads (no cast kernel).
-    // 18 -> 11 launches per module.
-    const bool fold = e->tm_fold;
-    int slots = 0;
-    auto producer = [&](GemmEpi& ep) { if (fold) epi_ln_producer(ep, e->tm_a, e->tm_stats, &slots); };
-    auto consumer = [&](GemmEpi& ep, const float* csum) { epi_ln_consumer(ep, e->tm_stats, slots, csum, 1e-5f, C); };
+    const bool fold = pl.tm_fold;
+    // the residual update in front of LayerNorm j (0: proj_in, 1 / 2: to_out); folded engines: the producer of the plan's slots
+    auto residual = [&](int j, const void* A, const DevLinear& W, const char* site) -> int {
+        int slots = -1;
+        const LinearOp o = op_tm_residual(e->tm_hs, C, A, W.bias, j > 0, e->tm_a, e->tm_stats, fold ? &slots : nullptr);
+        RC(linear(e, o.a, W, S, o.ep, st));
+        return fold ? slots_check(slots, pl.tm[m].slots[j], site) : D2S_OK;
+    };
+    auto consumer = [&](GemmEpi& ep, int j, const float* csum) { epi_ln_consumer(ep, e->tm_stats, pl.tm[m].slots[j], csum, 1e-5f, C); };
     // (folded: proj_in leaves its bf16 copy in tm_a, so the GroupNorm output it reads goes to tm_out -- free until the attention writes it)
     void* gn_out = fold ? e->tm_out : e->tm_a;
     PROF(PC_ELT, 0, 0, launch_groupnorm(prec, x, t.gn_g, t.gn_b, gn_out, t.sites, C, 32, 1e-6f, st, B));
-    {
-        GemmEpi ep = rowsE(e->tm_hs, OUT_F32, C, t.proj_in.bias);
-        producer(ep);
-        RC(linear(e, plainA(gn_out, C), t.proj_in, S, ep, st));
-    }
+    RC(residual(0, gn_out, t.proj_in, "a temporal module's proj_in"));
     for (int a = 0; a < 2; ++a) {
-        const bool folded = fold && slots >= 1 && slots <= 16;
+        const bool folded = pl.tm[m].folded[a];
         if (!folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->tm_hs, t.ln_g[a], t.ln_b[a], e->tm_a, S, C, 1e-5f, 0, 0, 0, st));
         // project THIS frame only (k' | v' | q'); the window's other 31 positions are already projected in the ring
         {
             const DevLinear& W = t.kvq[a].form(false, folded);
             GemmEpi ep = rowsE(e->tm_kv, OUT_T, 3 * C, W.bias);
-            if (folded) consumer(ep, W.csum);
+            if (folded) consumer(ep, a, W.csum);
             RC(linear(e, plainA(e->tm_a, C), W, S, ep, st));
         }
         // the frame's projected rows join the window (window_rows): per-row ring / head / window / store slot by value
@@ -347,20 +352,16 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
             store_due |= store.r[r].nslots > 0;
         }
         PROF(PC_ATTN, 4.0 * t.sites * win_rows * C, 0, launch_temporal_attn(prec, e->tm_kv, t.ptab[a], e->tm_out, t.sites, C, 31, B, attn, st));
-        {
-            GemmEpi ep = epi_residual(e->tm_hs, C, t.to_out[a].bias, nullptr);
-            producer(ep);
-            RC(linear(e, plainA(e->tm_out, C), t.to_out[a], S, ep, st));
-        }
+        RC(residual(a + 1, e->tm_out, t.to_out[a], "a temporal module's to_out"));
         if (store_due) PROF(PC_ELT, 0, 0, launch_cache_store(prec, e->tm_kv, t.sites, C, B, store, st));
     }
     {
-        const bool folded = fold && slots >= 1 && slots <= 16;
+        const bool folded = pl.tm[m].folded[2];
         if (!folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->tm_hs, t.ffn_g, t.ffn_b, e->tm_a, S, C, 1e-5f, 0, 0, 0, st));
         // folded: x * gelu(gate) in ff1's own epilogue (interleaved rows): tm_g [S, 4C] directly, no [S, 8C] intermediate, no GEGLU launch
         const DevLinear& W = t.ff1.form(false, folded);
         GemmEpi ep = rowsE(folded ? e->tm_g : e->tm_u, OUT_T, (folded ? 4 : 8) * C, W.bias);
-        if (folded) { ep.act = ACT_GEGLU; consumer(ep, W.csum); }
+        if (folded) { ep.act = ACT_GEGLU; consumer(ep, 2, W.csum); }
         RC(linear(e, plainA(e->tm_a, C), W, S, ep, st));
         if (!folded) PROF(PC_ELT, 0, 0, launch_geglu(prec, e->tm_u, e->tm_g, S, 4 * C, st));
     }
@@ -385,22 +386,22 @@ int run_temporal(d2s_engine* e, int m, const void* x, void* out, int B, hipStrea
 // Tap i of the neck: reassemble (HF DepthAnythingReassembleStage) + 3x3 to fusion width (neck.convs), then -- for the
 // three shallower taps -- the first residual unit of their fusion layer, RCU1(m) = m + conv2(relu(conv1(relu(m)))),
 // which depends on this map only (HF DepthAnythingFeatureFusionLayer adds it to the deeper stage's output later).
-// reassemble projection of tap i.  fold (bf16, batch 1): the shared final LayerNorm happens inside it -- A = the raw bf16
-// residual the last FC2 left in lnbuf (patch rows: skip the cls row), statistics from lnstats (same row offset)
-int neck_proj(d2s_engine* e, int i, int B, hipStream_t st, bool fold) {
+// reassemble projection of tap i.  pl.tap_folded: the shared final LayerNorm happens inside it -- A = the raw bf16
+// residual the tap layer's FC2 left in lnbuf (patch rows: skip the cls row), statistics from lnstats (same row offset)
+int neck_proj(d2s_engine* e, const ForwardPlan& pl, int i, int B, hipStream_t st) {
     const d2s_model_desc& d = e->d;
-    const int D = d.hidden, Mp = B * e->P, c = d.neck[i];
-    const DevLinear& W = e->re[i].proj.form(false, fold);
+    const int D = d.hidden, Mp = B * e->g.P, c = d.neck[i];
+    const DevLinear& W = e->re[i].proj.form(false, pl.tap_folded);
     GemmEpi ep = rowsE(e->rproj[i], OUT_T, c, W.bias);
-    if (!fold) return linear(e, plainA(e->tapbuf[i], D), W, Mp, ep, st);
-    epi_ln_consumer(ep, e->lnstats, e->tap_slots, W.csum, d.ln_eps, D);
-    const int skip = epi_tap_fold_rows(ep, B, e->N, e->P);     // one frame: start one row in; several: all token rows, cls rows dropped
-    return linear(e, plainA((const bf16_t*)e->lnbuf + (size_t)skip * D, D), W, skip ? Mp : B * e->N, ep, st);
+    if (!pl.tap_folded) return linear(e, plainA(e->tapbuf[i], D), W, Mp, ep, st);
+    epi_ln_consumer(ep, e->lnstats, pl.slots_fc2, W.csum, d.ln_eps, D);
+    const int skip = epi_tap_fold_rows(ep, B, e->g.N, e->g.P);     // one frame: start one row in; several: all token rows, cls rows dropped
+    return linear(e, plainA((const bf16_t*)e->lnbuf + (size_t)skip * D, D), W, skip ? Mp : B * e->g.N, ep, st);
 }
 
-int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
+int neck_rest(d2s_engine* e, const ForwardPlan& pl, int i, int B, hipStream_t st) {
     const d2s_model_desc& d = e->d;
-    const int F = d.fusion, gh = e->gh, gw = e->gw, Mp = B * e->P, c = d.neck[i];
+    const int F = d.fusion, gh = e->g.gh, gw = e->g.gw, Mp = B * e->g.P, c = d.neck[i];
     const void* src = e->rproj[i];
     int Hs = gh, Ws = gw;
     if (i < 2) {
@@ -411,8 +412,8 @@ int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
         RC(conv3(e, e->rproj[i], B, gh, gw, c, 2, 0, e->re[i].resize, e->rres[i], ACT_NONE, nullptr, nullptr, st));
         src = e->rres[i]; Hs = (gh - 1) / 2 + 1; Ws = (gw - 1) / 2 + 1;
     }
-    if (d.temporal && i == 2) { RC(run_temporal(e, 0, src, e->rres[2], B, st)); src = e->rres[2]; }     // layer_3
-    if (d.temporal && i == 3) { RC(run_temporal(e, 1, src, e->scr[0], B, st)); src = e->scr[0]; }       // layer_4
+    if (d.temporal && i == 2) { RC(run_temporal(e, pl, 0, src, e->rres[2], B, st)); src = e->rres[2]; }     // layer_3
+    if (d.temporal && i == 3) { RC(run_temporal(e, pl, 1, src, e->scr[0], B, st)); src = e->scr[0]; }       // layer_4
     RC(conv3(e, src, B, Hs, Ws, c, 1, 0, e->re[i].conv, e->feat[i], ACT_NONE, nullptr, nullptr, st));
     if (i < 3) {
         const int idx = 3 - i;                          // the fusion layer that consumes this map
@@ -425,14 +426,11 @@ int neck_rest(d2s_engine* e, int i, int B, hipStream_t st) {
 // x: the pre-processed frames [B,3,h,w], or null when d2s_pipeline has already written the patch rows (and cls rows) itself
 int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) {
     const d2s_model_desc& d = e->d;
-    const int D = d.hidden, N = e->N, P = e->P, M = B * N, Mp = B * P, prec = e->prec;
+    const int D = d.hidden, N = e->g.N, P = e->g.P, M = B * N, Mp = B * P, prec = e->prec;
     const int F = d.fusion;
-    const PrecRules pr = prec_rules(d.precision);
-    const bool use_side = e->overlap && e->side != nullptr && !e->prof_on;   // per-kernel timing passes run un-overlapped
-    if (e->fp8 && !e->fp8_ready && !e->calib) {
-        set_error("D2S_PREC_FP8 engine: activation scales are not set, call d2s_engine_calibrate first");
-        return D2S_E_STATE;
-    }
+    // every decision of this call (forward_plan.h): from here on the launches below branch on pl only
+    ForwardPlan pl;
+    RC(plan_forward(d, e->g, e->h, e->w, B, frame_state(e), pl));
     // ---- embeddings (HF Dinov2Embeddings)
     if (x) PROF(PC_ELT, 0, 0, launch_patchify(prec, x, e->patchA, B, e->h, e->w, d.patch, e->patch.Kpad, e->cls, e->pos, e->resid, N, D, st));
     {
@@ -441,38 +439,14 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     if (e->taps) D2S_HIP(hipMemcpyAsync(e->tap_hidden, e->resid, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
     // ---- encoder (HF Dinov2Layer x L)
     int tap_i = 0;
-    // D2S_PREC_FP8: the producers of the four linears' A operands write e4m3 (x / s_act, saturated); the linears run on
-    // e4m3 operands and de-quantise in their epilogue (deq[n] = s_act * s_w[n]); QKV still emits bf16 for the attention
-    const bool f8 = e->fp8 && !e->calib;
-    // D2S_PREC_FP8_MLP (round 5): only FC1 / FC2 take e4m3 operands; LN-1 output / attention output stay bf16 and QKV / proj run the bf16
-    // kernels.  f8a = "the attention-side linears are e4m3 too" (the all-four scheme)
-    const bool f8a = f8 && pr.e4m3_attn;
-    // bf16x3 engines: the A operands of the four encoder linears are written PRE-SPLIT (bf16 hi | lo units, common.h) by their
+    // pl.f8 (D2S_PREC_FP8, calibrated): the producers of the four linears' A operands write e4m3 (x / s_act, saturated); the linears run
+    // on e4m3 operands and de-quantise in their epilogue (deq[n] = s_act * s_w[n]); QKV still emits bf16 for the attention.
+    // D2S_PREC_FP8_MLP: only FC1 / FC2 take e4m3 operands; LN-1 output / attention output stay bf16 and QKV / proj run the bf16
+    // kernels.  pl.f8a = "the attention-side linears are e4m3 too" (the all-four scheme)
+    // pl.x3 (bf16x3 engines): the A operands of the four encoder linears are written PRE-SPLIT (bf16 hi | lo units, common.h) by their
     // producers -- LayerNorm, attention, the GELU epilogue -- so that they travel by LDS-DMA like the bf16 engine's; every other
     // GEMM / conv reads fp32 activations and splits them between its staging registers and LDS
-    const bool x3 = e->wprec == D2S_PREC_BF16X3;
-    // measured (ViT-B @294x518): folding wins 7 % at 1 frame, 3-5 % at 2-4, 2 % at 8, is even at 16 and loses 1 % at 32
-    // (the LN kernels' launch floor is amortised there and the wider epilogues are not); from ~9 frames the encoder linears
-    // switch to the 256 x 256 ping-pong kernel (gemm_pp.hip: +12 % frames/s at 16, +13 % at 32), which takes plain
-    // LayerNorm-ed operands -> folded up to 8 frames
-    // Re-measured at the end of round 3 (the ping-pong kernel now takes launches from 100 tiles, i.e. QKV / FC1 from 4 frames): folding
-    // keeps those linears on the small-tile kernels, and from 4 frames that costs more than the LayerNorm launches:
-    // 1 670 -> 1 758 frames/s at batch 4, 1 815 -> 2 000 at 5, 2 052 -> 2 275 at 8 with the limit at 3 (same box).
-    // Round 4: the ping-pong kernel folds LayerNorm itself (gemm_pp.hip, PP_K_*_LN) once the residual-update linears (N = D) run on
-    // it too, i.e. from gemm_pp_min_tiles() tiles of 256 x 256 over [M, D]: the 24 LayerNorm launches of the batched regime (0.66 ms of
-    // a 9.8 ms step at batch 32) are gone as well.  In between (QKV / FC1 on the ping-pong kernel, proj / FC2 not yet) nothing folds.
-    static EnvInt lnf_pp{"D2S_LNF_PP", 1};
-    // (the ping-pong kernel folds LayerNorm on bf16 operands only: pp_supported, gemm_pp.hip)
-    const bool pp_fold = lnf_pp.get() && e->lnf && e->wprec == D2S_PREC_BF16 && !e->calib && !e->taps && D % 256 == 0 && D <= 1024 &&
-                         gemm_pp_min_tiles() > 0 && (long)cdiv(M, 256) * (D / 256) >= gemm_pp_min_tiles();
-    const bool lnf = (pr.ln_folds(D2S_LIN_FC1) && !e->no_lnfuse && !e->calib && B <= (x3 ? 8 : 3)) || pp_fold;   // (bf16x3: no ping-pong kernel to give way to)
-    int ln_slots = 0;
-    // batch 1, bf16: the four tap LayerNorms fold into the reassemble projections the same way (the statistics and the raw
-    // residual of a tap layer are still in lnbuf / lnstats when its projection runs; the main stream waits for that launch
-    // -- ev_ln -- before the next layer's projection GEMM overwrites them)
-    // round 4: also in the batched regime where the ping-pong kernel produces the statistics (3-4 partials per row)
-    const bool tap_fold = lnf && pr.ln_folds(D2S_LIN_NECK_PROJ) && (B == 1 || pp_fold);
-    bool tap_folded[4] = {false, false, false, false};
+    const bool f8 = pl.f8, f8a = pl.f8a, x3 = pl.x3;
     int pending_ln = -1;
     for (int l = 0; l < d.layers; ++l) {
         const Layer& ly = e->L[l];
@@ -480,68 +454,69 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         float* am = e->calib ? e->amax + (size_t)l * NSITE : nullptr;
         // lnf: the previous layer's FC2 epilogue left the raw bf16 residual in lnbuf and the row statistics in lnstats;
         // LN1 then happens inside the QKV linear (layer 0 has no such producer and runs the LN kernel)
-        const bool ln1_folded = lnf && l > 0 && ln_slots <= 16 && pr.ln_folds(D2S_LIN_QKV);
+        const bool ln1_folded = pl.ln1_folded && l > 0;
         if (!ln1_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, ly.ln1g, ly.ln1b, e->lnbuf, M, D, d.ln_eps, 0, 0, 0, st, f8a ? 1.0f / sa[0] : 0.f, x3));
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 0, st));
         {
             const DevLinear& W = ly.qkv.form(f8a, ln1_folded);
-            GemmEpi ep = epi_qkv(e->qkv, qkv_out_type(f8, x3), D, W.bias, e->vt, N, e->Npad, d.heads);
-            if (ln1_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, W.csum, d.ln_eps, D);
+            GemmEpi ep = epi_qkv(e->qkv, qkv_out_type(f8, x3), D, W.bias, e->vt, N, e->g.Npad, d.heads);
+            if (ln1_folded) epi_ln_consumer(ep, e->lnstats, pl.slots_fc2, W.csum, d.ln_eps, D);
             RC(linear(e, splitA(e->lnbuf, D, x3), W, M, ep, st));
         }
         PROF(PC_ATTN, 4.0 * B * d.heads * (double)N * N * 64, 0,
-             launch_attention(x3 ? D2S_PREC_BF16X3 : prec, e->qkv, e->vt, e->attn, B, N, e->Npad, d.heads, st, f8a ? 1.0f / sa[1] : 0.f, e->attn_prescaled));
+             launch_attention(x3 ? D2S_PREC_BF16X3 : prec, e->qkv, e->vt, e->attn, B, N, e->g.Npad, d.heads, st, f8a ? 1.0f / sa[1] : 0.f, e->attn_prescaled));
         if (am) RC(launch_amax(prec, e->attn, (long)M * D, am + 1, st));
         {
             if (pending_ln >= 0) { D2S_HIP(hipStreamWaitEvent(st, e->ev_ln[pending_ln], 0)); pending_ln = -1; }
             const DevLinear& W = ly.proj.form(f8a, false);
-            GemmEpi ep = epi_residual(e->resid, D, W.bias, ly.ls1);
-            if (lnf) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[4] : 0.f);
-            RC(linear(e, splitA(e->attn, D, x3), W, M, ep, st));
+            int slots = -1;
+            const LinearOp o = op_residual(e->resid, D, e->attn, D, x3, W.bias, ly.ls1, e->lnbuf, e->lnstats, pl.lnf ? &slots : nullptr, f8 ? 1.0f / sa[4] : 0.f);
+            RC(linear(e, o.a, W, M, o.ep, st));
+            if (pl.lnf) RC(slots_check(slots, pl.slots_proj, "proj"));
         }
-        const bool ln2_folded = lnf && ln_slots <= 16;              // (more than 16 column blocks: the LN kernel runs instead)
+        const bool ln2_folded = pl.ln2_folded;                      // (more than 16 column blocks: the LN kernel runs instead)
         if (!ln2_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, ly.ln2g, ly.ln2b, e->lnbuf, M, D, d.ln_eps, 0, 0, 0, st, f8 ? 1.0f / sa[2] : 0.f, x3));
         if (am) RC(launch_amax(D2S_PREC_FP32, e->resid, (long)M * D, am + 4, st));       // (raw residual: the LN-folded FC1's A operand)
         if (am) RC(launch_amax(prec, e->lnbuf, (long)M * D, am + 2, st));
         {
             const DevLinear& W = ly.fc1.form(f8, ln2_folded);
             GemmEpi ep = epi_fc1(e->mlp, fc1_out_type(x3), d.mlp, W.bias);
-            if (ln2_folded) epi_ln_consumer(ep, e->lnstats, ln_slots, W.csum, d.ln_eps, D);
+            if (ln2_folded) epi_ln_consumer(ep, e->lnstats, pl.slots_proj, W.csum, d.ln_eps, D);
             if (f8) ep.out_qscale = 1.0f / sa[3];
             RC(linear(e, splitA(e->lnbuf, D, x3), W, M, ep, st));
         }
         if (am) RC(launch_amax(prec, e->mlp, (long)M * d.mlp, am + 3, st));
         {
             const DevLinear& W = ly.fc2.form(f8, false);
-            GemmEpi ep = epi_residual(e->resid, D, W.bias, ly.ls2);
-            if (lnf && (l + 1 < d.layers || tap_fold) && pr.ln_folds(D2S_LIN_FC2)) epi_ln_producer(ep, e->lnbuf, e->lnstats, &ln_slots, x3, f8 ? 1.0f / sa[5] : 0.f);
-            RC(linear(e, splitA(e->mlp, d.mlp, x3), W, M, ep, st));
+            const bool stats = l + 1 < d.layers ? pl.fc2_stats : pl.fc2_stats_last;
+            int slots = -1;
+            const LinearOp o = op_residual(e->resid, D, e->mlp, d.mlp, x3, W.bias, ly.ls2, e->lnbuf, e->lnstats, stats ? &slots : nullptr, f8 ? 1.0f / sa[5] : 0.f);
+            RC(linear(e, o.a, W, M, o.ep, st));
+            if (stats) RC(slots_check(slots, pl.slots_fc2, "FC2"));
         }
         if (am) RC(launch_amax(D2S_PREC_FP32, e->resid, (long)M * D, am + 5, st));       // (raw residual: the next layer's LN-folded QKV)
         if (e->taps) D2S_HIP(hipMemcpyAsync(e->tap_hidden + (size_t)(l + 1) * N * D, e->resid, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
         if (tap_i < 4 && l + 1 == d.out_indices[tap_i]) {     // HF Dinov2Backbone: shared final LN, drop cls
-            const bool fold = tap_fold && ln_slots <= 16;
-            tap_folded[tap_i] = fold;
-            e->tap_slots = ln_slots;
-            if (!fold) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, e->lnfg, e->lnfb, e->tapbuf[tap_i], Mp, D, d.ln_eps, P, N, 1, st));
-            // this tap's neck branch runs under the remaining encoder layers.  VDA: the temporal modules of branches 2 and 3
-            // share the tm_* workspaces, so branch 3 queues behind branch 2 on the side stream instead of racing it.
-            if (use_side && (tap_i < 3 || d.temporal)) {
+            // folded: the statistics and the raw residual of the tap layer are still in lnbuf / lnstats when its projection runs; the
+            // main stream waits for that launch -- ev_ln -- before the next layer's projection GEMM overwrites them
+            if (!pl.tap_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, e->lnfg, e->lnfb, e->tapbuf[tap_i], Mp, D, d.ln_eps, P, N, 1, st));
+            // this tap's neck branch runs under the remaining encoder layers (pl.tap_side)
+            if (pl.tap_side[tap_i]) {
                 D2S_HIP(hipEventRecord(e->ev_tap[tap_i], st));
                 D2S_HIP(hipStreamWaitEvent(e->side, e->ev_tap[tap_i], 0));
-                RC(neck_proj(e, tap_i, B, e->side, fold));
-                if (fold) { D2S_HIP(hipEventRecord(e->ev_ln[tap_i], e->side)); pending_ln = tap_i; }
-                RC(neck_rest(e, tap_i, B, e->side));
+                RC(neck_proj(e, pl, tap_i, B, e->side));
+                if (pl.tap_folded) { D2S_HIP(hipEventRecord(e->ev_ln[tap_i], e->side)); pending_ln = tap_i; }
+                RC(neck_rest(e, pl, tap_i, B, e->side));
             } else {
-                RC(neck_proj(e, tap_i, B, st, fold));           // (its inputs are overwritten by the next layer; the rest can wait)
+                RC(neck_proj(e, pl, tap_i, B, st));           // (its inputs are overwritten by the next layer; the rest can wait)
             }
             ++tap_i;
         }
     }
     // ---- neck branches that did not run on the side stream, then join it
     for (int i = 0; i < 4; ++i)
-        if (!(use_side && (i < 3 || d.temporal))) RC(neck_rest(e, i, B, st));
-    if (use_side) {
+        if (!pl.tap_side[i]) RC(neck_rest(e, pl, i, B, st));
+    if (pl.use_side) {
         D2S_HIP(hipEventRecord(e->ev_side, e->side));
         D2S_HIP(hipStreamWaitEvent(st, e->ev_side, 0));
     }
@@ -549,18 +524,16 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     // formed where fused(idx-1) is produced (up-sample / temporal-module epilogue), from the r1[] maps of the neck branches.
     void *X = e->scr[0], *Y = e->scr[1], *Z = e->scr[2];
     void* fused = nullptr;
-    bool fold1 = false;
-    GemmA c1a = {};
     int Hc = 0, Wc = 0;
     for (int idx = 0; idx < 4; ++idx) {
         int mi = 3 - idx;
         void* m = e->feat[mi];
-        Hc = e->fH[mi]; Wc = e->fW[mi];
+        Hc = e->g.fH[mi]; Wc = e->g.fW[mi];
         const void* hcur = idx == 0 ? m : fused;
         RC(conv3(e, hcur, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c1, X, ACT_NONE, nullptr, nullptr, st));
         RC(conv3(e, X, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c2, Z, ACT_NONE, hcur, nullptr, st));
         int Ho, Wo;
-        if (idx < 3) { Ho = e->fH[mi - 1]; Wo = e->fW[mi - 1]; } else { Ho = Hc * 2; Wo = Wc * 2; }
+        if (idx < 3) { Ho = e->g.fH[mi - 1]; Wo = e->g.fW[mi - 1]; } else { Ho = Hc * 2; Wo = Wc * 2; }
         // HF: projection(interpolate(h)).  The 1x1 projection (+bias) commutes with bilinear interpolation
         // (interpolation weights sum to 1), so it runs BEFORE the up-sample on 4x fewer pixels.
         void* pout = e->scr[3 + (idx & 1)];
@@ -569,46 +542,32 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         if (d.temporal && idx < 2) {                     // path_4 / path_3 (dpt_temporal.py:98-103)
             PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st));
             void* alt = e->scr[3 + ((idx + 1) & 1)];
-            RC(run_temporal(e, 2 + idx, pout, alt, B, st, next_r1));
+            RC(run_temporal(e, pl, 2 + idx, pout, alt, B, st, next_r1));
             pout = alt;
         } else {
-            if (idx == 3) {
-                // the last stage's up-sample feeds the head's conv1 only: folded into its halo loader where an LDS-resident-input
-                // kernel runs it (gemm.h conv3_upsample_ok); conv1 then reads X (the projected map) and writes Y
-                c1a = convA(X, Ho, Wo, F, Ho, Wo, 1, 0);
-                c1a.ups = 1; c1a.Hs = Hc; c1a.Ws = Wc; c1a.usy = linear_scale(Hc, Ho, true); c1a.usx = linear_scale(Wc, Wo, true);
-                GemmEpi ep1 = rowsE(Y, OUT_T, e->head1.N, e->head1.bias);
-                fold1 = conv3_upsample_ok(e->wprec, 0, c1a, B * Ho * Wo, e->head1.N, e->head1.K, e->head1.Kpad, ep1);
-            }
-            if (!fold1) PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st, next_r1));
+            // the last stage's up-sample feeds the head's conv1 only: folded into its halo loader where an LDS-resident-input
+            // kernel runs it (pl.head1_ups); conv1 then reads X (the projected map) and writes Y
+            if (!(idx == 3 && pl.head1_ups)) PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st, next_r1));
         }
         fused = pout; Hc = Ho; Wc = Wo;
     }
     // ---- head (HF DepthAnythingDepthEstimationHead)
     void* c1out = X;                                     // conv1 output; the (optional) up-sample between conv1 and conv2 goes c1out -> up2
     void* up2 = Y;
-    if (fold1) {
+    if (pl.head1_ups) {
         c1out = Y; up2 = X;
-        GemmEpi ep1 = rowsE(c1out, OUT_T, e->head1.N, e->head1.bias);
-        PROF(PC_CONV, 2.0 * B * Hc * Wc * e->head1.N * e->head1.K, 0, launch_gemm(e->wprec, 0, c1a, e->head1.w, B * Hc * Wc, e->head1.N, e->head1.K, e->head1.Kpad, ep1, st));
+        const LinearOp o = op_head1_ups(X, e->g.fH[0], e->g.fW[0], F, c1out, e->head1.bias);
+        PROF(PC_CONV, 2.0 * B * Hc * Wc * e->head1.N * e->head1.K, 0, launch_gemm(e->wprec, 0, o.a, e->head1.w, B * Hc * Wc, e->head1.N, e->head1.K, e->head1.Kpad, o.ep, st));
     } else {
         RC(conv3(e, fused, B, Hc, Wc, F, 1, 0, e->head1, c1out, ACT_NONE, nullptr, nullptr, st));
     }
     {
         const int Mh = B * e->h * e->w, Nh = d.head_hidden;
-        const int bn = Nh <= 32 ? 32 : 64;
-        const bool fused_tail = Nh <= 64 && (long)cdiv(Mh, 256) * cdiv(Nh, bn) >= 224;
-        GemmA a = convA(up2, e->h, e->w, F / 2, e->h, e->w, 1, 0);
-        GemmEpi ep = rowsE(depth, OUT_F32, 1, e->head2.bias);
-        ep.map = MAP_HEAD; ep.scale = e->w3; ep.head_b3 = e->b3; ep.head_max_depth = d.max_depth;
         // the interpolate between conv1 and conv2 folded into conv2's halo loader where the persistent head kernel runs (conv3.hip)
-        GemmA au = a;
-        au.ptr = c1out; au.ups = 1; au.Hs = Hc; au.Ws = Wc; au.usy = linear_scale(Hc, e->h, true); au.usx = linear_scale(Wc, e->w, true);
-        const bool ups = fused_tail && conv3_upsample_ok(e->wprec, head_tile(bn), au, Mh, Nh, e->head2.K, e->head2.Kpad, ep);
-        if (!ups) PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, c1out, up2, B, Hc, Wc, e->h, e->w, F / 2, st));
-        if (fused_tail) {
-            // conv2 + ReLU + conv3 (1x1 -> 1 channel) + ReLU | sigmoid in one launch (MAP_HEAD, WN == 1 tiles)
-            PROF(PC_CONV, 2.0 * Mh * Nh * e->head2.K, 0, launch_gemm(e->wprec, head_tile(bn), ups ? au : a, e->head2.w, Mh, Nh, e->head2.K, e->head2.Kpad, ep, st));
+        if (!pl.head2_ups) PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, c1out, up2, B, Hc, Wc, e->h, e->w, F / 2, st));
+        if (pl.head2_fused) {
+            const LinearOp o = op_head_tail(pl.head2_ups ? c1out : up2, pl.head2_ups, Hc, Wc, e->h, e->w, F / 2, depth, e->head2.bias, e->w3, e->b3, d.max_depth);
+            PROF(PC_CONV, 2.0 * Mh * Nh * e->head2.K, 0, launch_gemm(e->wprec, head_tile(pl.bn), o.a, e->head2.w, Mh, Nh, e->head2.K, e->head2.Kpad, o.ep, st));
         } else {
             RC(conv3(e, up2, B, e->h, e->w, F / 2, 1, 0, e->head2, Z, ACT_RELU, nullptr, nullptr, st));
             PROF(PC_ELT, 0, 0, launch_head_final(prec, Z, e->w3, e->b3, d.max_depth, depth, (long)B * e->h * e->w, d.head_hidden, st));
@@ -625,11 +584,8 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     return D2S_OK;
 }
 
-}  // namespace
-
-// ================================================================================================
-extern "C" int d2s_engine_create(const d2s_model_desc* desc, int device_id, d2s_engine** out) {
-    D2S_REQUIRE(desc && out, "null pointer");
+// what d2s_engine_create refuses of a model description, and d2s_engine_finalize of a shape for it (d2s_forward_plan: the same words)
+int check_desc(const d2s_model_desc* desc) {
     D2S_REQUIRE(desc->hidden > 0 && desc->heads > 0 && desc->hidden == desc->heads * 64, "head_dim must be 64");
     D2S_REQUIRE(desc->layers > 0 && desc->patch > 0 && desc->pos_grid > 0 && desc->fusion % 8 == 0, "bad model desc");
     D2S_REQUIRE(desc->precision == D2S_PREC_FP32 || desc->precision == D2S_PREC_BF16 || desc->precision == D2S_PREC_FP8 ||
@@ -638,6 +594,22 @@ extern "C" int d2s_engine_create(const d2s_model_desc* desc, int device_id, d2s_
     D2S_REQUIRE(desc->head_hidden % 4 == 0 && desc->mlp % 8 == 0, "bad head_hidden / mlp");
     D2S_REQUIRE(desc->max_depth >= 0.f && !(desc->temporal && desc->max_depth > 0.f),
                 "max_depth must be >= 0, and 0 for a Video-Depth-Anything engine (its head ends in ReLU, dpt_temporal.py:136)");
+    return D2S_OK;
+}
+int check_shape(const d2s_model_desc& d, int h, int w, int max_batch) {
+    D2S_REQUIRE(h > 0 && w > 0 && h % d.patch == 0 && w % d.patch == 0 && max_batch >= 1, "h, w must be patch multiples");
+    D2S_REQUIRE(!d.temporal || max_batch <= D2S_MAX_STREAMS, "a Video-Depth-Anything engine has at most D2S_MAX_STREAMS (32) stream slots: max_batch too large");
+    for (int c : {d.neck[2], d.neck[3], d.fusion})
+        D2S_REQUIRE(!d.temporal || (c % 32 == 0 && c <= 1024), "temporal module channels must be a multiple of 32 (GroupNorm) and <= 1024");
+    return D2S_OK;
+}
+
+}  // namespace
+
+// ================================================================================================
+extern "C" int d2s_engine_create(const d2s_model_desc* desc, int device_id, d2s_engine** out) {
+    D2S_REQUIRE(desc && out, "null pointer");
+    RC(check_desc(desc));
     D2S_ON_DEVICE(device_id);
     d2s_engine* e = new d2s_engine();
     e->d = *desc; e->device = device_id;
@@ -669,14 +641,13 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     D2S_REQUIRE(e, "null engine");
     if (e->finalized) { set_error("engine already finalized"); return D2S_E_STATE; }
     const d2s_model_desc& d = e->d;
-    D2S_REQUIRE(h > 0 && w > 0 && h % d.patch == 0 && w % d.patch == 0 && max_batch >= 1, "h, w must be patch multiples");
-    D2S_REQUIRE(!d.temporal || max_batch <= D2S_MAX_STREAMS, "a Video-Depth-Anything engine has at most D2S_MAX_STREAMS (32) stream slots: max_batch too large");
+    RC(check_shape(d, h, w, max_batch));
     D2S_ON_DEVICE(e->device);
     const int D = d.hidden, F = d.fusion;
     const PrecRules pr = prec_rules(d.precision);
-    e->h = h; e->w = w; e->gh = h / d.patch; e->gw = w / d.patch; e->P = e->gh * e->gw; e->N = e->P + 1;
-    e->Npad = (e->N + 63) / 64 * 64; e->maxB = max_batch;
-    const int N = e->N, P = e->P, B = max_batch;
+    e->h = h; e->w = w; e->maxB = max_batch;
+    e->g = engine_geom(d, h, w, max_batch);
+    const int N = e->g.N, P = e->g.P, B = max_batch;
     const size_t es = elem_size(e->prec);
     std::string pe = "backbone.embeddings.";
     // ---- weights
@@ -686,7 +657,7 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
         const float* pt = host_f32(e, pe + "position_embeddings", (size_t)(d.pos_grid * d.pos_grid + 1) * D, "position_embeddings: wrong shape");
         if (!pt) return D2S_E_MISSING;
         std::vector<float> pos;
-        interp_pos(pt, d.pos_grid, D, e->gh, e->gw, pos, d.temporal ? 0.1 : 0.0);
+        interp_pos(pt, d.pos_grid, D, e->g.gh, e->g.gw, pos, d.temporal ? 0.1 : 0.0);
         RC(dev_alloc(e, (void**)&e->pos, pos.size() * 4));
         D2S_HIP(hipMemcpy(e->pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
     }
@@ -768,28 +739,23 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     RC(dev_alloc(e, &e->lnbuf, M * D * es));
     if (e->lnf || e->fp8) RC(dev_alloc(e, (void**)&e->lnstats, (size_t)(D / 16 + 1) * M * 2 * sizeof(float)));
     RC(dev_alloc(e, &e->qkv, M * 3 * D * es));
-    RC(dev_alloc(e, &e->vt, (size_t)B * D * e->Npad * es, true));     // zero beyond N, never written there
+    RC(dev_alloc(e, &e->vt, (size_t)B * D * e->g.Npad * es, true));     // zero beyond N, never written there
     RC(dev_alloc(e, &e->attn, M * D * es));
     RC(dev_alloc(e, &e->mlp, M * d.mlp * es));
     RC(dev_alloc(e, &e->patchA, Mp * e->patch.Kpad * es, true));        // (zero: the padding columns are never written again)
-    const int gh = e->gh, gw = e->gw;
-    e->fH[0] = gh * 4; e->fW[0] = gw * 4; e->fH[1] = gh * 2; e->fW[1] = gw * 2; e->fH[2] = gh; e->fW[2] = gw;
-    e->fH[3] = (gh - 1) / 2 + 1; e->fW[3] = (gw - 1) / 2 + 1;
     for (int i = 0; i < 4; ++i) {
         RC(dev_alloc(e, &e->tapbuf[i], Mp * D * es));
         RC(dev_alloc(e, &e->rproj[i], Mp * d.neck[i] * es));
-        RC(dev_alloc(e, &e->rres[i], (size_t)B * e->fH[i] * e->fW[i] * d.neck[i] * es));
-        RC(dev_alloc(e, &e->feat[i], (size_t)B * e->fH[i] * e->fW[i] * F * es));
+        RC(dev_alloc(e, &e->rres[i], (size_t)B * e->g.fH[i] * e->g.fW[i] * d.neck[i] * es));
+        RC(dev_alloc(e, &e->feat[i], (size_t)B * e->g.fH[i] * e->g.fW[i] * F * es));
     }
-    size_t scr_elems = std::max({(size_t)64 * gh * gw * F, (size_t)h * w * (F / 2), (size_t)h * w * d.head_hidden}) * B;
-    for (int i = 0; i < 5; ++i) RC(dev_alloc(e, &e->scr[i], scr_elems * es));
-    e->splitk_elems = (size_t)B * 16 * e->fH[2] * e->fW[2] * std::max(F, d.neck[3]);
+    for (int i = 0; i < 5; ++i) RC(dev_alloc(e, &e->scr[i], e->g.scr_elems * es));
     // (+ GEMM_PART_CTR_WORDS zeroed words BEHIND the partials: the ping-pong kernel's tail counters, which no split-K launch can reach)
-    RC(dev_alloc(e, (void**)&e->splitk_ws, (e->splitk_elems + GEMM_PART_CTR_WORDS) * 4, true));
+    RC(dev_alloc(e, (void**)&e->splitk_ws, (e->g.splitk_elems + GEMM_PART_CTR_WORDS) * 4, true));
     // side stream of the neck branches (D2S_NO_OVERLAP=1 keeps everything on the caller's stream)
-    for (int i = 0; i < 3; ++i) RC(dev_alloc(e, &e->r1[i], (size_t)B * e->fH[i] * e->fW[i] * F * es));
-    RC(dev_alloc(e, &e->r1tmp, (size_t)B * e->fH[0] * e->fW[0] * F * es));
-    RC(dev_alloc(e, (void**)&e->splitk_ws_side, (e->splitk_elems + GEMM_PART_CTR_WORDS) * 4, true));
+    for (int i = 0; i < 3; ++i) RC(dev_alloc(e, &e->r1[i], (size_t)B * e->g.fH[i] * e->g.fW[i] * F * es));
+    RC(dev_alloc(e, &e->r1tmp, (size_t)B * e->g.fH[0] * e->g.fW[0] * F * es));
+    RC(dev_alloc(e, (void**)&e->splitk_ws_side, (e->g.splitk_elems + GEMM_PART_CTR_WORDS) * 4, true));
     e->overlap = env_int("D2S_NO_OVERLAP", 0) == 0;
     if (e->overlap) {
         D2S_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
@@ -799,16 +765,13 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     }
     if (d.temporal) {
         // ---- Video-Depth-Anything temporal modules (reference dpt_temporal.py:50-60): layer_3, layer_4, path_4, path_3
-        const int tC[4] = {d.neck[2], d.neck[3], F, F};
-        const int tS[4] = {e->fH[2] * e->fW[2], e->fH[3] * e->fW[3], e->fH[2] * e->fW[2], e->fH[1] * e->fW[1]};
         size_t sc_max = 0, max_sites = 0;
         e->tm_fold = pr.ln_folds(D2S_LIN_TM_KVQ) && env_int("D2S_VDA_FUSE", 1) != 0;
         for (int m = 0; m < 4; ++m) {
             d2s_engine::TMod& t = e->tm[m];
-            t.C = tC[m]; t.sites = tS[m];
+            t.C = e->g.tmC[m]; t.sites = e->g.tmS[m];
             max_sites = std::max(max_sites, (size_t)t.sites);
             const int C = t.C;
-            D2S_REQUIRE(C % 32 == 0 && C <= 1024, "temporal module channels must be a multiple of 32 (GroupNorm) and <= 1024");
             sc_max = std::max(sc_max, (size_t)t.sites * C);
             std::string p = "head.motion_modules." + std::to_string(m) + ".temporal_transformer.";
             std::string b = p + "transformer_blocks.0.";
@@ -935,6 +898,47 @@ extern "C" int d2s_model_forward(d2s_engine* e, const float* x, float* depth, in
     return d2s_model_forward_streams(e, x, depth, batch, nullptr, stream);
 }
 
+extern "C" int d2s_forward_plan(const d2s_model_desc* desc, int h, int w, int batch, int flags, d2s_forward_plan_result* res) {
+    D2S_REQUIRE(desc && res, "null pointer");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_forward_plan_result), "d2s_forward_plan_result.struct_size must be sizeof(d2s_forward_plan_result)");
+    RC(check_desc(desc));
+    RC(check_shape(*desc, h, w, batch));
+    const d2s_model_desc& d = *desc;
+    const PrecRules pr = prec_rules(d.precision);
+    // the state of an engine created and finalised now (d2s_engine_create, d2s_engine_finalize), in the situation the flags name
+    FrameState s = {};
+    s.calib = (flags & D2S_PLAN_CALIBRATING) != 0; s.fp8_ready = (flags & D2S_PLAN_CALIBRATED) != 0; s.prof = (flags & D2S_PLAN_PROFILING) != 0;
+    s.taps = env_int("D2S_TAPS", 0) != 0; s.side = env_int("D2S_NO_OVERLAP", 0) == 0; s.no_lnfuse = env_int("D2S_NO_LNFUSE", 0) != 0;
+    s.tm_fold = d.temporal && pr.ln_folds(D2S_LIN_TM_KVQ) && env_int("D2S_VDA_FUSE", 1) != 0;
+    D2S_REQUIRE(!s.calib || (pr.e4m3 && !d.temporal), "D2S_PLAN_CALIBRATING: not a D2S_PREC_FP8 engine (or a Video-Depth-Anything engine)");
+    const EngineGeom g = engine_geom(d, h, w, batch);
+    ForwardPlan pl;
+    RC(plan_forward(d, g, h, w, batch, s, pl));
+    d2s_forward_plan_result r = {};
+    r.struct_size = sizeof(r);
+    r.f8 = pl.f8; r.f8a = pl.f8a; r.x3 = pl.x3; r.lnf = pl.lnf; r.pp_fold = pl.pp_fold; r.tap_fold = pl.tap_fold; r.use_side = pl.use_side;
+    r.ln_slots[0] = pl.slots_proj; r.ln_slots[1] = pl.slots_fc2;
+    const int e4a = pl.f8a ? D2S_PLAN_E4M3 : 0, e4 = pl.f8 ? D2S_PLAN_E4M3 : 0;
+    r.site[D2S_PLAN_SITE_QKV0] = e4a;
+    r.site[D2S_PLAN_SITE_QKV] = e4a | (pl.ln1_folded ? D2S_PLAN_FOLDED : 0);
+    r.site[D2S_PLAN_SITE_PROJ] = e4a | (pl.lnf ? D2S_PLAN_STATS : 0);
+    r.site[D2S_PLAN_SITE_FC1] = e4 | (pl.ln2_folded ? D2S_PLAN_FOLDED : 0);
+    r.site[D2S_PLAN_SITE_FC2] = e4 | (pl.fc2_stats ? D2S_PLAN_STATS : 0);
+    r.site[D2S_PLAN_SITE_FC2_LAST] = e4 | (pl.fc2_stats_last ? D2S_PLAN_STATS : 0);
+    for (int i = 0; i < 4; ++i) { r.site[D2S_PLAN_SITE_NECK0 + i] = pl.tap_folded ? D2S_PLAN_FOLDED : 0; r.tap_side[i] = pl.tap_side[i]; }
+    r.head1_ups = pl.head1_ups; r.head2_fused = pl.head2_fused; r.head2_ups = pl.head2_ups; r.bn = pl.bn;
+    r.tm_fold = s.tm_fold;
+    r.tm_cache_store = d.temporal && !(s.tm_fold && (flags & D2S_PLAN_WINDOW_FILLED));       // (window_rows: fused and filled rows store in-kernel)
+    for (int m = 0; m < 4; ++m)
+        for (int j = 0; j < 3; ++j) { r.tm_slots[m][j] = pl.tm[m].slots[j]; r.tm_folded[m][j] = pl.tm[m].folded[j]; }
+    r.gh = g.gh; r.gw = g.gw; r.P = g.P; r.N = g.N; r.Npad = g.Npad;
+    for (int i = 0; i < 4; ++i) { r.fH[i] = g.fH[i]; r.fW[i] = g.fW[i]; r.tm_C[i] = d.temporal ? g.tmC[i] : 0; r.tm_sites[i] = d.temporal ? g.tmS[i] : 0; }
+    r.ln_launches = pl.ln_launches;
+    r.splitk_elems = g.splitk_elems; r.scr_elems = g.scr_elems;
+    *res = r;
+    return D2S_OK;
+}
+
 extern "C" int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, void* stream) {
     D2S_REQUIRE(e && x, "null pointer");
     if (!e->finalized) { set_error("d2s_engine_calibrate before d2s_engine_finalize"); return D2S_E_STATE; }
@@ -1058,7 +1062,7 @@ int pipeline_depth(d2s_engine* e, const uint8_t* frames, int batch, int H, int W
         const bool fused = !e->taps && preprocess_patches_ok(e->prec, D2S_FMT_U8_HWC, pre, H, W, e->h, e->w, e->d.patch, e->patch.Kpad);
         if (fused) PROF(PC_PRE, 0, (double)batch * ((double)H * W * 3 + (double)e->h * e->w * 6),
                         launch_preprocess_patches(e->prec, frames, D2S_FMT_U8_HWC, batch, H, W, stride, pre, e->patchA, e->h, e->w, e->d.patch, e->patch.Kpad,
-                                                  e->cls, e->pos, e->resid, e->N, e->d.hidden, st));
+                                                  e->cls, e->pos, e->resid, e->g.N, e->d.hidden, st));
         if (!fused) PROF(PC_PRE, 0, (double)batch * ((double)H * W * 3 + (double)e->h * e->w * 12), d2s_preprocess(frames, D2S_FMT_U8_HWC, batch, H, W, e->pre_x, e->h, e->w, stride, pre, stream));
         RC(forward(e, fused ? nullptr : e->pre_x, e->depth_small, batch, st));
     }
@@ -1200,15 +1204,15 @@ extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint6
         if (!e->taps) { set_error("hidden-state taps need D2S_TAPS=1 at engine creation"); return D2S_E_STATE; }
         int l = n == "embeddings" ? 0 : atoi(n.c_str() + 5);
         D2S_REQUIRE(l >= 0 && l <= e->d.layers, "bad layer index");
-        *rows = e->N; *cols = D;
-        D2S_REQUIRE(out_elems >= (uint64_t)e->N * D, "tap buffer too small");
-        D2S_HIP(hipMemcpyAsync(out, e->tap_hidden + (size_t)l * e->N * D, (size_t)e->N * D * 4, hipMemcpyDeviceToDevice, st));
+        *rows = e->g.N; *cols = D;
+        D2S_REQUIRE(out_elems >= (uint64_t)e->g.N * D, "tap buffer too small");
+        D2S_HIP(hipMemcpyAsync(out, e->tap_hidden + (size_t)l * e->g.N * D, (size_t)e->g.N * D * 4, hipMemcpyDeviceToDevice, st));
         return D2S_OK;
     }
     if (n.rfind("neck_feat", 0) == 0) {
         int i = atoi(n.c_str() + 9);
         D2S_REQUIRE(i >= 0 && i < 4, "bad neck index");
-        *rows = e->fH[i] * e->fW[i]; *cols = F;
+        *rows = e->g.fH[i] * e->g.fW[i]; *cols = F;
         D2S_REQUIRE(out_elems >= (uint64_t)(*rows) * F, "tap buffer too small");
         return launch_to_f32(e->prec, e->feat[i], out, (long)(*rows) * F, st);
     }

@@ -103,6 +103,10 @@ struct GemmPlan {
     int kps, tw, ink, lxn, skew_us;   // ping-pong kernel: K tiles per unit, whole-tile units, tail mode, log2(xn), start skew
     const char* error;           // plan_gemm failed: the message launch_gemm reports
 };
+// INVARIANT: plan_gemm and everything under it (plan_glds, plan_halo, plan_conv3_halo2, pp_supported / plan_gemm_pp, sk_supported /
+// plan_gemm_sk) read the pointers of GemmA / GemmEpi for PRESENCE only (e.part, e.stats_out, e.stats_slots, e.out2, e.deq, e.res1, ...;
+// and whether e.res1 == e.out), never their value or alignment, and the scales (out_qscale, out2_qscale) for their sign only.  The
+// frame's plan (forward_plan.h plan_forward) relies on it: it asks about a launch with a placeholder address in every pointer.
 int plan_gemm(int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);
 
 // the families outside gemm.hip: eligibility / plan (host only) and the launcher of a plan

@@ -12,7 +12,7 @@ namespace d2s {
 
 // ---- precision -----------------------------------------------------------------------------------------------------------
 // What an engine precision (d2s_model_desc.precision, D2S_PREC_*) decides for its linears.  Which batches fold a LayerNorm, and the
-// switches that keep one a kernel, stay with the callers.
+// switches that keep one a kernel, are the frame's plan's (forward_plan.h plan_forward).
 struct PrecRules {
     int precision;
     int act;            // activations and the kernels that write them: fp32 or bf16 (the e4m3 engines are bf16 engines whose encoder
@@ -269,19 +269,25 @@ constexpr int NSITE = 6;
 struct CalibSite { int site, dlayer; };
 constexpr CalibSite CALIB_SITE[4][2] = {{{0, 0}, {5, -1}}, {{1, 0}, {-1, 0}}, {{2, 0}, {4, 0}}, {{3, 0}, {-1, 0}}};
 
-// THE launch of a packed linear, [M, K] x W^T through ep, in the record's GEMM precision.  ws / ws_elems: the caller's split-K workspace
-// (GemmEpi::part); tile: 0, or a probe's override.  e4m3: the record's deq, K as it is, NO partials -- launch_gemm dispatches on their
-// presence.  Otherwise a ragged K (patch embedding) runs to Kpad, A zero padded, and a row-mapped epilogue gets the workspace.
+// What a packed linear hands launch_gemm beside its operands: the K the launch runs to and the epilogue as launched.  e4m3: the record's
+// deq, K as it is, NO partials -- launch_gemm dispatches on their presence.  Otherwise a ragged K (patch embedding) runs to Kpad, A zero
+// padded, and a row-mapped epilogue gets the split-K workspace ws / ws_elems (GemmEpi::part).
+static inline int linear_args(const DevLinear& L, GemmEpi& ep, float* ws, size_t ws_elems) {
+    if (L.prec == D2S_PREC_FP8_OPERANDS) { ep.deq = L.deq; return L.K; }
+    if (ep.map == MAP_ROWS) { ep.part = ws; ep.part_elems = ws_elems; }
+    return L.K % (L.prec == D2S_PREC_BF16 ? 8 : 4) ? L.Kpad : L.K;      // (bf16 activations: 8 per chunk; fp32, also under bf16x3 weights: 4)
+}
+// THE launch of a packed linear, [M, K] x W^T through ep, in the record's GEMM precision; tile: 0, or a probe's override
 static inline int launch_linear(const DevLinear& L, const GemmA& a, int M, GemmEpi ep, float* ws, size_t ws_elems, int tile, hipStream_t st) {
     D2S_REQUIRE(L.w, "launch_linear: this form of the linear was not built for the engine's precision");
-    int Kl = L.K;
-    if (L.prec == D2S_PREC_FP8_OPERANDS) {
-        ep.deq = L.deq;
-    } else {
-        if (L.K % (L.prec == D2S_PREC_BF16 ? 8 : 4)) Kl = L.Kpad;      // (bf16 activations: 8 per chunk; fp32, also under bf16x3 weights: 4)
-        if (ep.map == MAP_ROWS) { ep.part = ws; ep.part_elems = ws_elems; }
-    }
+    const int Kl = linear_args(L, ep, ws, ws_elems);
     return launch_gemm(L.prec, tile, a, L.w, M, L.N, Kl, L.Kpad, ep, st);
+}
+// ... and what launch_gemm would run for it (plan_gemm): host only.  L may be a shape record (linear_shape) -- plan_gemm reads the
+// pointers of a launch for presence only (gemm.h)
+static inline int plan_linear(const DevLinear& L, const GemmA& a, int M, GemmEpi ep, float* ws, size_t ws_elems, GemmPlan& p) {
+    const int Kl = linear_args(L, ep, ws, ws_elems);
+    return plan_gemm(L.prec, 0, a, M, L.N, Kl, L.Kpad, ep, p);
 }
 
 }  // namespace d2s

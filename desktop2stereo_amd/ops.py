@@ -640,6 +640,40 @@ def jpeg_encode(frames: torch.Tensor, quality: int = 90, out_stride: Optional[in
     return out, sizes
 
 
+def model_desc(cfg: ModelConfig, precision: str = "bf16", temporal: bool = False, max_depth: float = 0.0) -> ModelDesc:
+    """d2s_model_desc of a model configuration at an engine precision."""
+    if precision not in ("bf16", "fp32", "fp8", "bf16x3", "fp8_mlp"):
+        raise ValueError("precision must be 'bf16', 'fp32', 'fp8', 'fp8_mlp' or 'bf16x3'")
+    prec = {"bf16": PREC_BF16, "fp32": PREC_FP32, "fp8": _lib.PREC_FP8, "bf16x3": _lib.PREC_BF16X3, "fp8_mlp": _lib.PREC_FP8_MLP}[precision]
+    return ModelDesc(cfg.hidden, cfg.heads, cfg.layers, (C.c_int32 * 4)(*cfg.out_indices), (C.c_int32 * 4)(*cfg.neck),
+                     cfg.fusion, cfg.head_hidden, cfg.mlp, cfg.patch, cfg.pos_grid, cfg.ln_eps, prec, int(bool(temporal)), float(max_depth))
+
+
+def forward_plan(cfg: ModelConfig, h: int, w: int, batch: int = 1, precision: str = "bf16", *, temporal: bool = False, max_depth: float = 0.0,
+                 calibrating: bool = False, calibrated: bool = True, profiling: bool = False, window_filled: bool = False) -> dict:
+    """What a forward pass of `batch` frames decides before it launches anything (include/d2s.h d2s_forward_plan; host code, no GPU): the
+    regime flags, per linear site {"folded", "stats", "e4m3"}, the taps' streams, the head's folds, the temporal modules' folded forms,
+    the engine geometry and the number of LayerNorm launches -- for an engine created now (the D2S_* switches of the environment) and
+    finalised at (h, w) with max_batch = batch.  calibrated: an e4m3 engine after Engine.calibrate (False: refused as the forward pass
+    refuses it)."""
+    desc = model_desc(cfg, precision, temporal, max_depth)
+    F = _lib.PLAN_FLAGS
+    flags = (F["calibrating"] * bool(calibrating) | F["profiling"] * bool(profiling) | F["window_filled"] * bool(window_filled) |
+             F["calibrated"] * bool(calibrated))
+    r = _lib.ForwardPlanResult()
+    r.struct_size = C.sizeof(_lib.ForwardPlanResult)
+    check(_lib.load().d2s_forward_plan(C.byref(desc), int(h), int(w), int(batch), int(flags), C.byref(r)), "d2s_forward_plan")
+    out = {k: bool(getattr(r, k)) for k in ("f8", "f8a", "x3", "lnf", "pp_fold", "tap_fold", "use_side", "head1_ups", "head2_fused",
+                                            "head2_ups", "tm_fold", "tm_cache_store")}
+    out.update({k: int(getattr(r, k)) for k in ("bn", "gh", "gw", "P", "N", "Npad", "ln_launches", "splitk_elems", "scr_elems")})
+    out.update({k: list(getattr(r, k)) for k in ("ln_slots", "fH", "fW", "tm_C", "tm_sites")})
+    out["sites"] = {n: {"folded": bool(v & 1), "stats": bool(v & 2), "e4m3": bool(v & 4)} for n, v in zip(_lib.PLAN_SITES, r.site)}
+    out["tap_side"] = [bool(v) for v in r.tap_side]
+    out["tm_slots"] = [list(m) for m in r.tm_slots]
+    out["tm_folded"] = [[bool(v) for v in m] for m in r.tm_folded]
+    return out
+
+
 class Engine:
     """The native depth engine: what DepthModelWrapper holds in ``self.model`` for an accelerated
     backend (reference depth.py:1539-1781).  ``__call__(tensor[B,3,h,w]) -> tensor[B,h,w]``."""
@@ -655,12 +689,7 @@ class Engine:
         self.cfg, self.h, self.w, self.max_batch = cfg, h, w, max_batch
         self.precision = precision
         self.device = torch.device("cuda", device)
-        desc = ModelDesc(cfg.hidden, cfg.heads, cfg.layers, (C.c_int32 * 4)(*cfg.out_indices), (C.c_int32 * 4)(*cfg.neck),
-                         cfg.fusion, cfg.head_hidden, cfg.mlp, cfg.patch, cfg.pos_grid, cfg.ln_eps,
-                         {"bf16": PREC_BF16, "fp32": PREC_FP32, "fp8": _lib.PREC_FP8, "bf16x3": _lib.PREC_BF16X3, "fp8_mlp": _lib.PREC_FP8_MLP}.get(precision, -1),
-                         int(bool(temporal)), float(max_depth))
-        if precision not in ("bf16", "fp32", "fp8", "bf16x3", "fp8_mlp"):
-            raise ValueError("precision must be 'bf16', 'fp32', 'fp8', 'fp8_mlp' or 'bf16x3'")
+        desc = model_desc(cfg, precision, temporal, max_depth)
         self._h = C.c_void_p()
         with _on(self.device):
             check(self.lib.d2s_engine_create(C.byref(desc), device, C.byref(self._h)), "d2s_engine_create")

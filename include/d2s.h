@@ -283,6 +283,48 @@ int d2s_engine_reset_stream_at(d2s_engine* e, int stream_id);
  * before a successful calibration fail with D2S_E_STATE.  (No reference counterpart: the reference has FP16 only.) */
 int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, void* stream);
 
+/* What d2s_model_forward decides for one call, before anything is launched (d2s_version() >= 121; pure host code: launches nothing,
+ * needs no GPU): an engine of `desc` created NOW (it reads D2S_NO_LNFUSE, D2S_TAPS, D2S_NO_OVERLAP, D2S_VDA_FUSE as d2s_engine_create /
+ * d2s_engine_finalize do, and D2S_LNF_PP / D2S_GEMM_PP as every call does), finalised at (h, w) with max_batch = batch, running `batch`
+ * frames.  flags: D2S_PLAN_*.  Refuses what d2s_engine_create and d2s_engine_finalize refuse of desc, h, w, batch and what the forward
+ * pass refuses of an e4m3 engine that is not calibrated, in the same words.  The decisions that follow from a GEMM launch (statistics
+ * slots, up-sample folds) depend on the CU count of the device: on a machine without a GPU the report is the 256-CU plan (MI355X).
+ *   regimes      f8 / f8a: FC1 + FC2 / all four encoder linears on e4m3 operands; x3: bf16x3; lnf: LN1 / LN2 fold into QKV / FC1 and
+ *                proj / FC2 produce their statistics; pp_fold: lnf on the ping-pong kernel (batched bf16); tap_fold: the final LayerNorm
+ *                folds into the reassemble projections; use_side: neck branches on the side stream
+ *   ln_slots     statistics partials per row left by proj [0] and FC2 [1] (0: not a producer)
+ *   site         D2S_PLAN_SITE_* -> D2S_PLAN_FOLDED (a LayerNorm is folded into it) | D2S_PLAN_STATS (it produces the raw-residual
+ *                copy and statistics of the LayerNorm behind it) | D2S_PLAN_E4M3 (e4m3 operands)
+ *   tap_side     tap i's neck branch runs on the side stream (else on the caller's, after the encoder)
+ *   head         head1_ups / head2_ups: the up-sample in front of conv1 / conv2 is folded into its loader; head2_fused: conv2 + conv3 in
+ *                one launch, bn its column tile
+ *   tm_*         temporal engines, per module (layer_3, layer_4, path_4, path_3): tm_slots / tm_folded [m][j]: the partials in front of
+ *                and the folded form taken for kvq[0], kvq[1], ff1; tm_fold: the modules' producers run; tm_cache_store: a ring-store
+ *                launch follows each attention for rows whose window is fresh (no D2S_PLAN_WINDOW_FILLED) or on unfolded engines
+ *   geometry     what d2s_engine_finalize sizes the engine with: patch grid, tokens, the four neck maps, split-K / scratch elements,
+ *                the temporal modules' channels and sites
+ *   ln_launches  LayerNorm launches of the call (d2s_engine_profile_read's "layernorm" class) */
+#define D2S_PLAN_CALIBRATING    1   /* the forward pass inside d2s_engine_calibrate */
+#define D2S_PLAN_PROFILING      2   /* d2s_engine_profile is on */
+#define D2S_PLAN_WINDOW_FILLED  4   /* temporal engine: every stream of the call has seen a frame */
+#define D2S_PLAN_CALIBRATED     8   /* e4m3 engine: d2s_engine_calibrate has run */
+enum { D2S_PLAN_SITE_PATCH = 0, D2S_PLAN_SITE_QKV0, D2S_PLAN_SITE_QKV, D2S_PLAN_SITE_PROJ, D2S_PLAN_SITE_FC1, D2S_PLAN_SITE_FC2,
+       D2S_PLAN_SITE_FC2_LAST, D2S_PLAN_SITE_NECK0, D2S_PLAN_SITE_NECK1, D2S_PLAN_SITE_NECK2, D2S_PLAN_SITE_NECK3, D2S_PLAN_SITES };
+enum { D2S_PLAN_FOLDED = 1, D2S_PLAN_STATS = 2, D2S_PLAN_E4M3 = 4 };
+typedef struct d2s_forward_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_forward_plan_result) */
+    int32_t f8, f8a, x3, lnf, pp_fold, tap_fold, use_side;
+    int32_t ln_slots[2];
+    int32_t site[D2S_PLAN_SITES];
+    int32_t tap_side[4];
+    int32_t head1_ups, head2_fused, head2_ups, bn;
+    int32_t tm_fold, tm_cache_store, tm_slots[4][3], tm_folded[4][3];
+    int32_t gh, gw, P, N, Npad, fH[4], fW[4], tm_C[4], tm_sites[4];
+    int32_t ln_launches;
+    uint64_t splitk_elems, scr_elems;
+} d2s_forward_plan_result;
+int d2s_forward_plan(const d2s_model_desc* desc, int h, int w, int batch, int flags, d2s_forward_plan_result* res);
+
 /* A10-A11: post_process_depth = normalize -> gamma -> foreground_scale -> anti_alias
  * (reference depth.py:806-814), in place on float [batch,h,w].  Stateless. */
 int d2s_post_process(float* depth, int batch, int h, int w, const d2s_post_params* p,

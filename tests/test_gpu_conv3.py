@@ -103,20 +103,16 @@ class Case:
     expect: str = ""               # kernel name, or "UNSUPPORTED" (conv3_upsample_ok refuses the fold)
 
 
-def _maps(h: int, w: int):
-    """engine.hip finalize: gh x gw patches, fH / fW of the four neck maps."""
-    gh, gw = h // 14, w // 14
-    return gh, gw, [gh * 4, gh * 2, gh, (gh - 1) // 2 + 1], [gw * 4, gw * 2, gw, (gw - 1) // 2 + 1]
-
-
 def engine_cases(model: str, B: int, prec: str, frame=(1080, 1920, 518)):
-    """Every 3x3 convolution of one forward pass of the engine (engine.hip neck_rest, forward, conv3()), as probe cases."""
+    """Every 3x3 convolution of one forward pass of the engine (engine.hip neck_rest, forward, conv3()), as probe cases: the maps, the
+    split-K workspace and the fused head tail are the frame's plan's (ops.forward_plan: the library's own plan_forward, host code)."""
+    from desktop2stereo_amd import ops
     from desktop2stereo_amd.config import MODELS, engine_shape
     cfg = MODELS[model]
     h, w, _ = engine_shape(*frame)
-    gh, gw, fH, fW = _maps(h, w)
+    pl = ops.forward_plan(cfg, h, w, B, prec)
+    gh, gw, fH, fW, ws, fused = pl["gh"], pl["gw"], pl["fH"], pl["fW"], pl["splitk_elems"], pl["head2_fused"]
     Fu, neck, Nh = cfg.fusion, cfg.neck, cfg.head_hidden
-    ws = B * 16 * fH[2] * fW[2] * max(Fu, neck[3])          # engine.hip: e->splitk_elems
     tag = f"{model}-{frame[2]}-B{B}-{prec}"
     cs = [Case(f"{tag}-resize", neck[3], neck[3], B, gh, gw, stride=2, prec=prec, splitk=ws)]
     for i in range(4):
@@ -128,7 +124,6 @@ def engine_cases(model: str, B: int, prec: str, frame=(1080, 1920, 518)):
     if prec == "bf16":                                    # head conv1: the fusion stage's x2 up-sample folded where a kernel can
         cs.append(Case(f"{tag}-head1-ups", Fu, Fu // 2, B, H1, W1, src=(fH[0], fW[0]), prec=prec))
     cs.append(Case(f"{tag}-head1", Fu, Fu // 2, B, H1, W1, prec=prec, splitk=ws))     # the same conv on the up-sampled map
-    fused = Nh <= 64 and math.ceil(B * h * w / 256) * math.ceil(Nh / (32 if Nh <= 32 else 64)) >= 224
     for md in (0.0, 20.0):
         if not fused:
             break

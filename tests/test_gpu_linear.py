@@ -63,43 +63,35 @@ class Case:
     expect: str = ""
 
 
-def _ws(model, B, frame=(1080, 1920, 518)):
-    """engine.hip finalize: e->splitk_elems."""
+def _plan(model: str, B: int, prec: str, frame=(1080, 1920, 518), **kw):
+    """The frame's plan for this engine (ops.forward_plan: the library's own plan_forward and engine geometry, host code)."""
+    from desktop2stereo_amd import ops
     from desktop2stereo_amd.config import MODELS, engine_shape
-    cfg = MODELS[model]
     h, w, _ = engine_shape(*frame)
-    gh, gw = h // 14, w // 14
-    return B * 16 * gh * gw * max(cfg.fusion, cfg.neck[3])
+    return ops.forward_plan(MODELS[model], h, w, B, prec, **kw)
 
 
 def engine_cases(model: str, B: int, prec: str, frame=(1080, 1920, 518)):
-    """Every linear launch of one forward pass (engine.hip forward / neck_proj / neck_rest) with the engine's folding rules."""
-    from desktop2stereo_amd.config import MODELS, engine_shape
+    """Every linear launch of one forward pass (engine.hip forward / neck_proj / neck_rest), folded as the frame's plan says."""
+    from desktop2stereo_amd.config import MODELS
     cfg = MODELS[model]
-    h, w, _ = engine_shape(*frame)
-    gh, gw = h // 14, w // 14
-    P = gh * gw
-    ntok = P + 1
+    pl = _plan(model, B, prec, frame)
+    gh, gw, P, ntok, site = pl["gh"], pl["gw"], pl["P"], pl["N"], pl["sites"]
     D, mlp, H = cfg.hidden, cfg.mlp, cfg.heads
     M = B * ntok
-    ws = _ws(model, B, frame)
-    tiles = -(-M // 256) * (D // 256)
-    pp_fold = prec == "bf16" and D % 256 == 0 and tiles >= 100
-    lnf = (prec in ("bf16", "fp8", "fp8_mlp") and B <= 3) or (prec == "bf16x3" and B <= 8) or pp_fold
-    tap_fold = lnf and prec == "bf16" and (B == 1 or pp_fold)
     tag = f"{model}-{frame[2]}-B{B}-{prec}"
-    e = dict(splitk=ws, ln_eps=cfg.ln_eps)
+    e = dict(splitk=pl["splitk_elems"], ln_eps=cfg.ln_eps)
     cs = [Case(f"{tag}-patch", "patch", prec, B * P, D, 3 * 14 * 14, ntok=ntok, **e)]
-    fold_qkv = lnf and prec != "fp8_mlp"
+    fold_qkv, fold_fc1, fold_tap = site["qkv"]["folded"], site["fc1"]["folded"], site["neck0"]["folded"]
     cs.append(Case(f"{tag}-qkv", "qkv", prec, M, 3 * D, D, ntok=ntok, heads=H, fold=fold_qkv, pK=mlp if fold_qkv else 0, **e))
-    cs.append(Case(f"{tag}-proj", "proj", prec, M, D, D, scale=True, fold=lnf, **e))
-    cs.append(Case(f"{tag}-fc1", "fc1", prec, M, mlp, D, fold=lnf, pK=D if lnf else 0, **e))
-    cs.append(Case(f"{tag}-fc2", "fc2", prec, M, D, mlp, scale=True, fold=lnf and prec != "fp8_mlp", **e))
+    cs.append(Case(f"{tag}-proj", "proj", prec, M, D, D, scale=True, fold=site["proj"]["stats"], **e))
+    cs.append(Case(f"{tag}-fc1", "fc1", prec, M, mlp, D, fold=fold_fc1, pK=D if fold_fc1 else 0, **e))
+    cs.append(Case(f"{tag}-fc2", "fc2", prec, M, D, mlp, scale=True, fold=site["fc2"]["stats"], **e))
     if prec in ("fp8", "fp8_mlp"):
         return cs                         # (the neck of the e4m3 engines is the bf16 engine's)
     for i in range(4):
         c = cfg.neck[i]
-        cs.append(Case(f"{tag}-neck{i}-proj", "neck_proj", prec, M, c, D, ntok=ntok, fold=tap_fold, pK=mlp if tap_fold else 0, **e))
+        cs.append(Case(f"{tag}-neck{i}-proj", "neck_proj", prec, M, c, D, ntok=ntok, fold=fold_tap, pK=mlp if fold_tap else 0, **e))
     for i, ks in ((0, 4), (1, 2)):
         c = cfg.neck[i]
         cs.append(Case(f"{tag}-neck{i}-resize", "neck_resize", prec, B * P, ks * ks * c, c, grid=(gh, gw, ks), **e))
@@ -107,24 +99,18 @@ def engine_cases(model: str, B: int, prec: str, frame=(1080, 1920, 518)):
 
 
 def temporal_cases(model: str, frame, prec: str = "bf16"):
-    """The linears of the four temporal modules of a Video-Depth-Anything engine (run_temporal), folded as the bf16 engine folds them."""
-    from desktop2stereo_amd.config import MODELS, engine_shape
-    cfg = MODELS[model]
-    h, w, _ = engine_shape(*frame)
-    gh, gw = h // 14, w // 14
-    F = cfg.fusion
-    mods = [(cfg.neck[2], gh * gw), (cfg.neck[3], ((gh - 1) // 2 + 1) * ((gw - 1) // 2 + 1)), (F, gh * gw), (F, 4 * gh * gw)]
-    fold = prec == "bf16"
-    ws = _ws(model, 1, frame)
+    """The linears of the four temporal modules of a Video-Depth-Anything engine (run_temporal), folded as the frame's plan says."""
+    pl = _plan(model, 1, prec, frame, temporal=True)
     cs = []
-    for m, (C, S) in enumerate(mods):
+    for m, (C, S) in enumerate(zip(pl["tm_C"], pl["tm_sites"])):
         tag = f"vda-{model}-{frame[2]}-{prec}-tm{m}"
-        e = dict(splitk=ws, ln_eps=1e-5)
-        cs += [Case(f"{tag}-proj_in", "tm_proj_in", prec, S, C, C, fold=fold, **e),
-               Case(f"{tag}-kvq", "tm_kvq", prec, S, 3 * C, C, fold=fold, pK=C if fold else 0, bias=False, **e),
-               Case(f"{tag}-to_out", "tm_to_out", prec, S, C, C, fold=fold, **e),
-               Case(f"{tag}-ff1", "tm_ff1", prec, S, 8 * C, C, fold=fold, pK=C if fold else 0, **e),
-               Case(f"{tag}-ff2", "tm_ff2", prec, S, C, 4 * C, fold=fold, **e),
+        e = dict(splitk=pl["splitk_elems"], ln_eps=1e-5)
+        prod, (kvq0, kvq1, ff1) = pl["tm_fold"], pl["tm_folded"][m]
+        cs += [Case(f"{tag}-proj_in", "tm_proj_in", prec, S, C, C, fold=prod, **e),
+               Case(f"{tag}-kvq", "tm_kvq", prec, S, 3 * C, C, fold=kvq0 and kvq1, pK=C if kvq0 and kvq1 else 0, bias=False, **e),
+               Case(f"{tag}-to_out", "tm_to_out", prec, S, C, C, fold=prod, **e),
+               Case(f"{tag}-ff1", "tm_ff1", prec, S, 8 * C, C, fold=ff1, pK=C if ff1 else 0, **e),
+               Case(f"{tag}-ff2", "tm_ff2", prec, S, C, 4 * C, fold=prod, **e),
                Case(f"{tag}-proj_out", "tm_proj_out", prec, S, C, C, res2=(m >= 2), **e)]
     return cs
 
@@ -1105,7 +1091,8 @@ def test_ln_fold_stress_rows(dev):
     for stress in ("massive", "mean64", "mean256"):
         for B, tag in ((1, "small"), (11, "pp")):
             M = B * 778
-            cases += [Case(f"stress-{stress}-{tag}-qkv", "qkv", "bf16", M, 2304, 768, ntok=778, heads=12, fold=True, pK=3072, stress=stress, splitk=_ws("vitb", B)),
-                      Case(f"stress-{stress}-{tag}-fc1", "fc1", "bf16", M, 3072, 768, fold=True, pK=768, stress=stress, splitk=_ws("vitb", B)),
-                      Case(f"stress-{stress}-{tag}-tap", "neck_proj", "bf16", M, 768, 768, ntok=778, fold=True, pK=3072, stress=stress, splitk=_ws("vitb", B))]
+            ws = _plan("vitb", B, "bf16")["splitk_elems"]
+            cases += [Case(f"stress-{stress}-{tag}-qkv", "qkv", "bf16", M, 2304, 768, ntok=778, heads=12, fold=True, pK=3072, stress=stress, splitk=ws),
+                      Case(f"stress-{stress}-{tag}-fc1", "fc1", "bf16", M, 3072, 768, fold=True, pK=768, stress=stress, splitk=ws),
+                      Case(f"stress-{stress}-{tag}-tap", "neck_proj", "bf16", M, 768, 768, ntok=778, fold=True, pK=3072, stress=stress, splitk=ws)]
     _run_all(cases, dev, EXPECTED_STRESS)

@@ -611,6 +611,7 @@ def test_layernorm_fusion_in_the_pingpong_kernel(dev, monkeypatch):
             ln_launches = eng.profile_read()["layernorm"]["launches"]
             eng.profile(False)
             assert ln_launches == (1 if on == "1" else 28), (on, ln_launches)      # layer 0's LN1 stays a kernel (the tap LayerNorms fold into the reassemble projections)
+            assert ln_launches == ops.forward_plan(cfg, h, w, B, "bf16", profiling=True)["ln_launches"], (on, ln_launches)      # ... as the frame's plan says for the same state
             assert np.array_equal(outs[-1], eng(x).cpu().numpy())                  # fixed-order partial sums: bit-reproducible
             post = ops.post_process_depth(_t(outs[-1][0], dev), PipelineParams(depth_resolution=518)).cpu().numpy()
             dr = np.abs(post - z["f0_post_depth"])

@@ -40,6 +40,7 @@ frames = torch.from_numpy(np.stack([synth.noise_frame(a.height, a.width, i) for 
 for _ in range(40 if a.vda else 5):
     eng.pipeline(frames, p, sp)
 torch.cuda.synchronize()
+print("plan:", ops.forward_plan(cfg, h, w, 1 if a.vda else a.batch, a.prec, temporal=a.vda, profiling=True, window_filled=True), file=sys.stderr)
 eng.profile(True)
 eng.pipeline(frames, p, sp)
 torch.cuda.synchronize()
