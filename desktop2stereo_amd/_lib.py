@@ -222,6 +222,13 @@ SYMBOLS = {
     "d2s_view_pipeline_xr_glow_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                     C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double), C.POINTER(XrScreen),
                                                     C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.POINTER(XrGlow), _P, _P]),
+    "d2s_dibr_xr_glow_curved_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "d2s_dibr_xr_eyes_glow_curved": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                               C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrGlow), _P, _P]),
+    "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                                           C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                                           C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,
+                                                           C.c_uint64, C.POINTER(XrGlow), _P, _P]),
     "d2s_crop_detect_workspace":(C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "d2s_crop_detect": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, _P]),
     "d2s_jpeg_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

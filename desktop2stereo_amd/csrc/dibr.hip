@@ -502,6 +502,134 @@ dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict
     dibr_xr_body<OUT_FMT, D, true>(rgb_all, dep_all, out_all, tab_all, g, ex, G, levels, xr_glow_lds);
 }
 
+// d2s_dibr_xr_eyes_glow_curved: the curved screen with its glow (_render_curved_glow, xr_viewer/effects.py:408-474, in _render_eye's
+// order, :1050-1145).  Threads and tiles as above.  The eye's 52 piece rows (dibr_xr.h) and 49 seam rows are staged in LDS -- a
+// lane's search index diverges, so they are LDS reads, rows padded to 25 floats and seams 3 floats apart (odd strides: lanes on
+// neighbouring rows read different banks, lanes on one row broadcast).  A pixel finds its piece from the seams' signs: the two arc
+// ends say whether its ray passes the arc (then a binary search over the 47 interior seams, 6 steps), a tangent piece, or -- a ray
+// more than a half turn from one end, both end seams "beyond" -- either tangent piece.  The facet found and its two neighbours then
+// go through dibr_xr_body's rule with its arithmetic, so a screen pixel has the facet, a / w and b / w of dibr_xr_kernel; a pixel no
+// facet covers takes the band on the piece the seams gave it.  Homographies per pixel: at most 3 facets + 2 others, whatever the
+// strip's 48.
+constexpr int XR_LDS_ROW = XR_ROW_FLOATS + 1;
+struct XrPt { float na, nb, nw, z; };
+__device__ __forceinline__ XrPt xr_row_at(const float* __restrict__ r, float xc, float yc) {
+    XrPt p;
+    p.na = r[0] * xc + r[1] * yc + r[2]; p.nb = r[3] * xc + r[4] * yc + r[5];
+    p.nw = r[6] * xc + r[7] * yc + r[8]; p.z = r[9] * xc + r[10] * yc + r[11];
+    return p;
+}
+template <int OUT_FMT, class D>
+__global__ void __launch_bounds__(256)
+dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+                           const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrGlowDev G, XrCurvedDev Q,
+                           const uint8_t* __restrict__ levels) {
+    extern __shared__ float xr_glow_lds[];               // [n_tex][3]
+    __shared__ float rows[XR_PIECES * XR_LDS_ROW];
+    __shared__ float seams[XR_SEAMS * 3];
+    float* __restrict__ lds = xr_glow_lds;
+    const int ei = blockIdx.z % ex.n, b = blockIdx.z / ex.n;
+    const XrEyeDev e = ex.e[ei];
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    const bool inside = x < e.w && y < e.h;
+    {
+        const float* __restrict__ src = (const float*)(tab_all + ei * XR_PIECES);
+        for (int i = threadIdx.x; i < XR_PIECES * XR_ROW_FLOATS; i += 256) rows[(i / XR_ROW_FLOATS) * XR_LDS_ROW + i % XR_ROW_FLOATS] = src[i];
+        if (threadIdx.x < XR_SEAMS * 3) {
+            const int s = threadIdx.x / 3, k = threadIdx.x % 3;
+            seams[threadIdx.x] = s < XR_MAX_FACETS ? src[s * XR_ROW_FLOATS + k] : -src[(XR_MAX_FACETS - 1) * XR_ROW_FLOATS + 12 + k];
+        }
+        __syncthreads();
+    }
+    const float xc = ((float)x + 0.5f) - 0.5f * (float)e.w, yc = ((float)y + 0.5f) - 0.5f * (float)e.h;
+    auto seam = [&](int s) { return seams[s * 3] * xc + seams[s * 3 + 1] * yc + seams[s * 3 + 2]; };
+    // f: the facet the seams give (0 .. 47), -1 / 48: the tangent piece at the lower / upper end, -2: either tangent piece
+    int f;
+    {
+        const bool lo_in = seam(0) >= 0.f, hi_in = seam(XR_MAX_FACETS) < 0.f;
+        if (lo_in && hi_in) {
+            int lo = 0, hi = XR_MAX_FACETS;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (seam(mid) >= 0.f) lo = mid; else hi = mid;
+            }
+            f = lo;
+        } else f = lo_in ? XR_MAX_FACETS : (hi_in ? -1 : -2);
+    }
+    int best = -1;
+    float bz = 1.0f, ba = 0.f, bb = 0.f, bw = 1.f;
+    bool plane = false, band_set = false;                // the band's piece is drawn at this pixel; a facet has claimed the band
+    float pz = 0.f, ga = 0.f, gb = 0.f;                  // its depth and its point in the screen's coordinates
+    auto band = [&](const float* __restrict__ r, const XrPt& p) {
+        if (p.nw > 0.f && p.z >= -1.0f && p.z <= 1.0f && (!plane || p.z < pz)) {
+            const float a = p.na / p.nw, bq = p.nb / p.nw;
+            plane = true; pz = p.z;
+            ga = r[15] + a * r[16] + bq * r[17]; gb = r[18] + a * r[19] + bq * r[20];
+        }
+    };
+    for (int c = max(f - 1, 0); c <= min(f + 1, XR_MAX_FACETS - 1) && f >= -1; ++c) {
+        const float* __restrict__ r = rows + c * XR_LDS_ROW;
+        const XrPt p = xr_row_at(r, xc, yc);
+        const float ne = r[12] * xc + r[13] * yc + r[14];
+        if (p.na >= 0.f && ne >= 0.f) {
+            if (p.nb >= 0.f && p.nb <= p.nw && p.nw > 0.f && p.z >= -1.0f && p.z < bz) { bz = p.z; best = c; ba = p.na; bb = p.nb; bw = p.nw; }
+            if (!band_set && f >= 0 && f < XR_MAX_FACETS) { band_set = true; band(r, p); }      // (the lowest facet between its seams)
+        }
+    }
+    if (f < 0) { const float* r = rows + XR_T0 * XR_LDS_ROW; band(r, xr_row_at(r, xc, yc)); }
+    if (f == XR_MAX_FACETS || f == -2) { const float* r = rows + XR_T1 * XR_LDS_ROW; band(r, xr_row_at(r, xc, yc)); }
+    // the screen pixel: its facet's uv, which is also its point in the screen's coordinates; mode 1: the inner band's two draws
+    bool fband = false, cband = false;
+    float sa = 0.f, sb = 0.f, ca = 0.f, cb = 0.f;
+    if (best >= 0) {
+        const float* __restrict__ r = rows + best * XR_LDS_ROW;
+        const float a = ba / bw, bq = bb / bw;
+        sa = r[15] + a * r[16] + bq * r[17]; sb = r[18] + a * r[19] + bq * r[20];
+        if (G.mode == 1) {
+            const float al = Q.vertical ? sb : sa, ac = Q.vertical ? sa : sb;
+            const bool edge_ac = ac <= Q.e_ac || ac >= 1.0f - Q.e_ac;
+            fband = Q.vertical ? (edge_ac && al >= Q.e_al && al <= 1.0f - Q.e_al) : edge_ac;
+            const float* __restrict__ rc = rows + (al < 0.5f ? XR_C0 : XR_C1) * XR_LDS_ROW;
+            const XrPt p = xr_row_at(rc, xc, yc);
+            if (p.nw > 0.f && p.z >= -1.0f && p.z <= 1.0f && p.na >= 0.f && p.na <= p.nw) {
+                const float a2 = p.na / p.nw, b2 = p.nb / p.nw;
+                ca = rc[15] + a2 * rc[16] + b2 * rc[17]; cb = rc[18] + a2 * rc[19] + b2 * rc[20];
+                const float cac = Q.vertical ? ca : cb;
+                cband = Q.vertical ? (cac >= 0.f && cac <= 1.0f) : (cac >= Q.e_ac && cac <= 1.0f - Q.e_ac);
+            }
+        }
+    }
+    const bool need = inside && (best < 0 ? plane : (fband || cband));
+    if (__syncthreads_or(need)) {
+        const uint8_t* __restrict__ src = levels + (long)b * G.chain_total + G.chain_off;
+        for (int i = threadIdx.x; i < G.n_tex * 3; i += 256) lds[i] = (float)src[i];
+        __syncthreads();
+    }
+    if (!inside) return;
+    const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    const long o = e.out_off + (((long)b * e.h + y) * e.w + x) * nch;
+    float c[4], src[4];
+    if (best < 0) {
+        c[0] = ex.clear[0] * 255.0f; c[1] = ex.clear[1] * 255.0f; c[2] = ex.clear[2] * 255.0f; c[3] = ex.clear[3];
+        if (plane && glow_frag(lds, G, g, ga, gb, false, src)) {
+            glow_blend(c, src);
+            if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
+        }
+        dibr_store<OUT_FMT>(out_all, o, nch, c);
+        return;
+    }
+    const float quv[2] = {sa, 1.0f - sb};
+    GenSmp<D> smp;
+    smp.rgb = rgb_all + (long)b * g.H * g.W * 3; smp.dep = D::make(dep_all, b, g); smp.H = g.H; smp.W = g.W;
+    dibr_pixel<false, false, true, true>(smp, g, 0, 0, e.eye, c, nullptr, quv);
+    // the mesh's draw order (_build_curved_glow_band_verts:401-404): the u-long bands, then the v-long ones
+    const bool cf = Q.vertical != 0;                     // the chord piece's draw comes first
+    if ((cf ? cband : fband) && glow_frag(lds, G, g, cf ? ca : sa, cf ? cb : sb, true, src)) glow_blend(c, src);
+    if ((cf ? fband : cband) && glow_frag(lds, G, g, cf ? sa : ca, cf ? sb : cb, true, src)) glow_blend(c, src);
+    if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
+    dibr_store<OUT_FMT>(out_all, o, nch, c);
+}
+
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
 int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
@@ -512,6 +640,10 @@ int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batc
 int dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
                      const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
                      uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
+int dibr_xr_glow_curved_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                            const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                            void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
+                            bool check_only);                                                          // (d2s_view_pipeline_xr_glow_curved_streams)
 
 }  // namespace d2s
 
@@ -779,4 +911,111 @@ extern "C" int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int
                                      void* stream) {
     return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, glow,
                             levels, stream, false);
+}
+
+// The curved screen with its glow (xr_viewer/effects.py:408-474 in _render_eye's order, :1050-1145).
+extern "C" int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes) {
+    D2S_REQUIRE(bytes, "null pointer (bytes)");
+    D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
+    *bytes = (uint64_t)n_eyes * XR_PIECES * sizeof(XrFacet);
+    return D2S_OK;
+}
+
+// A flat screen, glow == nullptr or mode 0: dibr_xr_glow_any, the same launches.
+int d2s::dibr_xr_glow_curved_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                 const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                 int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
+                                 void* stream, bool check_only) {
+    const bool curved_glow = screen && screen->struct_size == sizeof(d2s_xr_screen) && screen->curve != D2S_XR_CURVE_FLAT && glow &&
+                             glow->struct_size == sizeof(d2s_xr_glow) && glow->mode != 0;
+    if (!curved_glow)
+        return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, glow,
+                                levels, stream, check_only);
+    D2S_REQUIRE(p, "null pointer");      // (the device pointers are looked at last: a call that names none can be refused for any other reason, and launches nothing)
+    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
+    if (rc) return rc;
+    D2S_REQUIRE(!p->feather_enabled, "feather_enabled must be 0 (the OpenXR viewer never enables the feathering)");
+    if (crop) {
+        int a, b2, c2, d2;
+        rc = crop_eye_shape(H, W, crop, D2S_MODE_FULL_SBS, &a, &b2, &c2, &d2);
+        if (rc) return rc;
+    }
+    rc = xr_check(screen, eyes, n_eyes, batch, workspace, workspace_bytes);
+    if (rc) return rc;
+    D2S_REQUIRE(workspace_bytes >= (uint64_t)n_eyes * XR_PIECES * sizeof(XrFacet), "workspace_bytes below d2s_dibr_xr_glow_curved_workspace");
+    rc = xr_glow_check(screen, glow, levels, true);
+    if (rc) return rc;
+    D2S_REQUIRE(H >= 2 && W >= 2 && H <= 8192 && W <= 8192, "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
+    uint64_t offs[2] = {0, 0}, total = 0;
+    rc = xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, offs, &total);
+    if (rc) return rc;
+    XrGlowDev G;
+    xr_glow_dev(screen, glow, H, W, G);
+    const size_t lds = (size_t)G.n_tex * 3 * sizeof(float);
+    if (lds + (XR_PIECES * XR_LDS_ROW + XR_SEAMS * 3) * sizeof(float) > 65536) {      // (only an 8192 x 8192 frame's 5 461 texels)
+        set_error("unsupported: the frame's coarse mip levels and the piece table exceed 64 KB of LDS (a frame of 8192 x 8192)");
+        return D2S_E_UNSUPPORTED;
+    }
+    XrSurface S;
+    xr_surface(screen, S);
+    XrCurvedDev Q;
+    double e_al;
+    xr_curved_dev(screen, glow, Q, &e_al);
+    XrCurvedPieces P;
+    xr_curved_pieces(screen, e_al, P);
+    for (int i = 0; i < n_eyes; ++i) {
+        if (!(xr_min_w(S, eyes[i].vp) > 1e-6)) {
+            set_error("unsupported: a vertex of the screen has clip w <= 1e-6 (the screen crosses the eye plane)");
+            return D2S_E_UNSUPPORTED;
+        }
+        if (!xr_eye_inside(S, P, eyes[i].vp)) {
+            set_error("unsupported: an eye lies outside the convex region the curved screen and its two tangent planes bound (behind the "
+                      "screen or beyond an end of the arc): the glow's pieces would overlap and need blending in draw order");
+            return D2S_E_UNSUPPORTED;
+        }
+    }
+    D2S_REQUIRE(rgb && depth && out, "null pointer");
+    DibrGeomProj g;
+    dibr_fill_geom(g, p, H, W, dh, dw);
+    g.c = cosf((float)screen->roll); g.s = sinf((float)screen->roll);
+    g.feather = 0;
+    g.mode = 0; g.oh = g.ow = g.out_h = g.out_w = 0;
+    g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
+    g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
+    XrEyes ex = {};
+    ex.n = n_eyes;
+    for (int k = 0; k < 4; ++k) ex.clear[k] = screen->clear[k];
+    int mw = 0, mh = 0;
+    XrFacet rows[2][XR_PIECES];
+    for (int i = 0; i < n_eyes; ++i) {
+        ex.e[i] = XrEyeDev{eyes[i].width, eyes[i].height, eyes[i].eye, S.n, (long)offs[i]};
+        mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
+        xr_curved_table(S, P, glow->mode, eyes[i].vp, eyes[i].width, eyes[i].height, rows[i]);
+    }
+    if (check_only) return D2S_OK;
+    XrFacet* tab = (XrFacet*)workspace;
+    for (int i = 0; i < n_eyes; ++i)
+        for (int f0 = 0; f0 < XR_PIECES; f0 += XR_CHUNK_FACETS) {                      // 3 set-up launches per eye
+            const int nf = std::min(XR_CHUNK_FACETS, XR_PIECES - f0), n_floats = nf * XR_ROW_FLOATS;
+            XrFacetChunk chunk;
+            for (int f = 0; f < nf; ++f) chunk.f[f] = rows[i][f0 + f];
+            hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, (hipStream_t)stream, chunk,
+                               (float*)(tab + i * XR_PIECES + f0), n_floats);
+        }
+    const bool up = dh != H || dw != W;
+    dim3 grid(cdiv(mw, 16), cdiv(mh, 16), n_eyes * batch), block(256);
+#define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_glow_curved_kernel<FMT, D>), grid, block, lds, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex, G, Q, levels)
+    if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
+    else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
+#undef DIBR_XR
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+extern "C" int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                            const d2s_dibr_params* p, const double crop[4], const d2s_xr_screen* screen,
+                                            const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                                            uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
+    return dibr_xr_glow_curved_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes,
+                                   glow, levels, stream, false);
 }

@@ -83,34 +83,34 @@ inline double xr_min_w(const XrSurface& S, const double vp[16]) {
 // One eye's table.  clip(a, b) = C0 + a * CA + b * CB; with D = diag(w / 2, -h / 2, 1): (xc, yc, 1) * clip.w = D * M * (a, b, 1),
 // M = [CA.xyw | CB.xyw | C0.xyw], so (a, b, 1) / clip.w = inverse(D * M) * (xc, yc, 1).  A facet seen edge-on (no inverse) covers no
 // pixel centre: its ha row becomes the constant -1.
-inline void xr_facets(const XrSurface& S, const double vp[16], int w, int h, XrFacet* out) {
-    for (int f = 0; f < S.n; ++f) {
-        double dA[3], dB[3], C0[4], CA[4], CB[4];
-        for (int i = 0; i < 3; ++i) { dA[i] = S.p10[f].p[i] - S.p00[f].p[i]; dB[i] = S.p01[f].p[i] - S.p00[f].p[i]; }
-        xr_clip(vp, S.p00[f].p, 1.0, C0); xr_clip(vp, dA, 0.0, CA); xr_clip(vp, dB, 0.0, CB);
-        const double sx = w / 2.0, sy = -h / 2.0;
-        const double m[3][3] = {{sx * CA[0], sx * CB[0], sx * C0[0]}, {sy * CA[1], sy * CB[1], sy * C0[1]}, {CA[3], CB[3], C0[3]}};
-        double adj[3][3];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
-            const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
-            adj[i][j] = m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0];
-        }
-        const double det = m[0][0] * adj[0][0] + m[0][1] * adj[1][0] + m[0][2] * adj[2][0];
-        double scale = 0.0;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) scale = fmax(scale, fabs(m[i][j]));
-        XrFacet& F = out[f];
-        F = XrFacet{};
-        if (!(fabs(det) > 1e-14 * scale * scale * scale)) { F.ha[2] = -1.f; continue; }
-        double inv[3][3];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) inv[i][j] = adj[i][j] / det;
-        for (int j = 0; j < 3; ++j) {
-            F.ha[j] = (float)inv[0][j]; F.hb[j] = (float)inv[1][j]; F.hw[j] = (float)inv[2][j];
-            F.hz[j] = (float)(CA[2] * inv[0][j] + CB[2] * inv[1][j] + C0[2] * inv[2][j]);
-            F.he[j] = (float)(inv[2][j] - inv[0][j]);
-        }
-        F.u0 = (float)S.p00[f].u; F.ua = (float)(S.p10[f].u - S.p00[f].u); F.ub = (float)(S.p01[f].u - S.p00[f].u);
-        F.v0 = (float)S.p00[f].v; F.va = (float)(S.p10[f].v - S.p00[f].v); F.vb = (float)(S.p01[f].v - S.p00[f].v);
+inline void xr_facet_row(const XrVert& p00, const XrVert& p10, const XrVert& p01, const double vp[16], int w, int h, XrFacet& F) {
+    double dA[3], dB[3], C0[4], CA[4], CB[4];
+    for (int i = 0; i < 3; ++i) { dA[i] = p10.p[i] - p00.p[i]; dB[i] = p01.p[i] - p00.p[i]; }
+    xr_clip(vp, p00.p, 1.0, C0); xr_clip(vp, dA, 0.0, CA); xr_clip(vp, dB, 0.0, CB);
+    const double sx = w / 2.0, sy = -h / 2.0;
+    const double m[3][3] = {{sx * CA[0], sx * CB[0], sx * C0[0]}, {sy * CA[1], sy * CB[1], sy * C0[1]}, {CA[3], CB[3], C0[3]}};
+    double adj[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+        const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+        adj[i][j] = m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0];
     }
+    const double det = m[0][0] * adj[0][0] + m[0][1] * adj[1][0] + m[0][2] * adj[2][0];
+    double scale = 0.0;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) scale = fmax(scale, fabs(m[i][j]));
+    F = XrFacet{};
+    if (!(fabs(det) > 1e-14 * scale * scale * scale)) { F.ha[2] = -1.f; return; }
+    double inv[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) inv[i][j] = adj[i][j] / det;
+    for (int j = 0; j < 3; ++j) {
+        F.ha[j] = (float)inv[0][j]; F.hb[j] = (float)inv[1][j]; F.hw[j] = (float)inv[2][j];
+        F.hz[j] = (float)(CA[2] * inv[0][j] + CB[2] * inv[1][j] + C0[2] * inv[2][j]);
+        F.he[j] = (float)(inv[2][j] - inv[0][j]);
+    }
+    F.u0 = (float)p00.u; F.ua = (float)(p10.u - p00.u); F.ub = (float)(p01.u - p00.u);
+    F.v0 = (float)p00.v; F.va = (float)(p10.v - p00.v); F.vb = (float)(p01.v - p00.v);
+}
+inline void xr_facets(const XrSurface& S, const double vp[16], int w, int h, XrFacet* out) {
+    for (int f = 0; f < S.n; ++f) xr_facet_row(S.p00[f], S.p10[f], S.p01[f], vp, w, h, out[f]);
     // interior seams: facet f ends where facet f + 1 begins (a runs along the strip) -- one edge function for both
     auto live = [&](int f) { return !(out[f].ha[0] == 0.f && out[f].ha[1] == 0.f && out[f].ha[2] == -1.f); };
     for (int f = 0; f + 1 < S.n; ++f)
@@ -157,7 +157,7 @@ struct XrGlowDev {
 };
 
 // What d2s_dibr_xr_eyes_glow refuses about the glow, after xr_check has accepted the screen; no HIP call.
-inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, const uint8_t* levels) {
+inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, const uint8_t* levels, bool curved_ok = false) {
     if (!glow) return D2S_OK;
     D2S_REQUIRE(glow->struct_size == sizeof(d2s_xr_glow), "d2s_xr_glow.struct_size must be sizeof(d2s_xr_glow) = 24");
     D2S_REQUIRE(glow->mode >= 0 && glow->mode <= 2, "bad glow mode (0 off, 1 glow, 2 glow2)");
@@ -165,7 +165,7 @@ inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, const 
     D2S_REQUIRE(levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
     D2S_REQUIRE(std::isfinite(glow->range_m) && glow->range_m > 0.0, "glow range_m must be finite and > 0");
     D2S_REQUIRE(std::isfinite(glow->inner_edge_fraction) && glow->inner_edge_fraction >= 0.0, "glow inner_edge_fraction must be finite and >= 0");
-    if (s->curve != D2S_XR_CURVE_FLAT) {
+    if (s->curve != D2S_XR_CURVE_FLAT && !curved_ok) {
         set_error("unsupported: the glow of a curved screen (a band mesh in the reference) is not built; curve must be 0 with glow on");
         return D2S_E_UNSUPPORTED;
     }
@@ -190,6 +190,119 @@ inline void xr_glow_dev(const d2s_xr_screen* s, const d2s_xr_glow* glow, int H, 
     G.q = ms.q; G.m = ms.q < XR_GLOW_LOD ? ms.q : XR_GLOW_LOD;
     G.chain_off = ms.off[G.m]; G.chain_total = ms.total;
     for (int k = G.m; k <= ms.q; ++k) G.n_tex += ms.h[k] * ms.w[k];
+}
+
+// ---- the glow around the curved screen (d2s_dibr_xr_eyes_glow_curved; _render_curved_glow, _build_curved_glow_band_verts,
+// xr_viewer/effects.py:314-474) ----
+// The band mesh as planar pieces.  With "along" the strip's direction (u of a horizontal curve, v of a vertical one)
+// and "across" the other one:
+//   0 .. 47  the strip's facets, each continued without bound across the strip (the outer bands beside the arc; the inner bands that
+//            run along it lie on them);
+//   48, 49   the tangent planes at the arc's two ends (_local_axes at -+0.48 rad; the outer band beyond an end, its two corners
+//            included): origin = the end's generator, a = metres along the tangent / the screen's length, b across as a facet's;
+//   50, 51   mode 1: the chord planes between an end and the strip coordinate e_al = inner_uv / inner_(w | h) (the inner band at that
+//            end, ONE quad along the strip in the mesh), a = 0 at the lower strip coordinate, 1 at the upper.
+// Every row carries the affine map from its own (a, b) to the screen's coordinates (ga, gb) -- what glow_frag takes -- in the uv
+// fields; a facet's is its vertex uv.  The 49 seams (47 interior ones and the arc's two ends) are the facets' own float32 rows: seam
+// s < 48 = facet s's ha, seam 48 = facet 47's he negated, so a tangent piece and the end facet beside it share ONE edge function.
+constexpr int XR_PIECES = 52, XR_T0 = 48, XR_T1 = 49, XR_C0 = 50, XR_C1 = 51, XR_SEAMS = 49;
+constexpr int XR_ROW_FLOATS = sizeof(XrFacet) / sizeof(float);
+// vertical: the strip runs along v.  e_al, e_ac: the inner band's width in screen coordinates along / across the strip (each <= 0.5)
+struct XrCurvedDev { int vertical; float e_al, e_ac; };
+struct XrCurvedPieces { XrVert p00[4], p10[4], p01[4]; double axis[3], radius; };      // pieces 48 .. 51; a point of the cylinder's axis
+
+// _build_curved_glow_band_verts:381-388: u0i - u0 = min(inner_uv, inner_w / 2) in glow uv, / inner_w in the screen's
+inline void xr_curved_dev(const d2s_xr_screen* s, const d2s_xr_glow* glow, XrCurvedDev& Q, double* e_al_out) {
+    double range = fmax(glow->range_m, 1e-4);
+    if (glow->mode == 2) range *= 0.5;
+    const double glow_w = s->width + 2.0 * range, glow_h = s->height + 2.0 * range, inner_w = s->width / glow_w, inner_h = s->height / glow_h;
+    const double inner_uv = fmin(inner_w, inner_h) * fmax(glow->inner_edge_fraction, 0.0);
+    const double eu = fmin(0.5, inner_uv / inner_w), ev = fmin(0.5, inner_uv / inner_h);
+    Q.vertical = s->curve == D2S_XR_CURVE_VERTICAL;
+    Q.e_al = (float)(Q.vertical ? ev : eu); Q.e_ac = (float)(Q.vertical ? eu : ev);
+    *e_al_out = Q.vertical ? ev : eu;
+}
+
+inline void xr_curved_pieces(const d2s_xr_screen* s, double e_al, XrCurvedPieces& P) {
+    double R[3][3], c[3];
+    xr_basis(s, R, c);
+    const bool vert = s->curve == D2S_XR_CURVE_VERTICAL;
+    const double len = vert ? s->height : s->width, wid = vert ? s->width : s->height, radius = len / 2.0 / XR_HALF_ANGLE;
+    // local (along, across, towards the viewer) -> world; uv likewise (along, across)
+    auto make = [&](double al, double ac, double lz, double t_al, double t_ac, bool dir) {
+        const double lx = vert ? ac : al, ly = vert ? al : ac;
+        XrVert w;
+        for (int i = 0; i < 3; ++i) w.p[i] = (dir ? 0.0 : c[i]) + R[i][0] * lx + R[i][1] * ly + R[i][2] * lz;
+        w.u = vert ? t_ac : t_al; w.v = vert ? t_al : t_ac;
+        return w;
+    };
+    auto arc = [&](double t, double ac) {
+        const double ang = -XR_HALF_ANGLE + 2.0 * XR_HALF_ANGLE * t;
+        return make(radius * sin(ang), (ac - 0.5) * wid, radius * (1.0 - cos(ang)), t, ac, false);
+    };
+    auto plus = [&](const XrVert& a, const XrVert& d) {
+        XrVert w;
+        for (int i = 0; i < 3; ++i) w.p[i] = a.p[i] + d.p[i];
+        w.u = a.u + d.u; w.v = a.v + d.v;
+        return w;
+    };
+    for (int k = 0; k < 2; ++k) {                          // the tangent planes
+        const double ang = k ? XR_HALF_ANGLE : -XR_HALF_ANGLE;
+        P.p00[k] = arc((double)k, 0.0);
+        P.p10[k] = plus(P.p00[k], make(cos(ang) * len, 0.0, sin(ang) * len, 1.0, 0.0, true));
+        P.p01[k] = arc((double)k, 1.0);
+    }
+    P.p00[2] = arc(0.0, 0.0); P.p10[2] = arc(e_al, 0.0); P.p01[2] = arc(0.0, 1.0);
+    P.p00[3] = arc(1.0 - e_al, 0.0); P.p10[3] = arc(1.0, 0.0); P.p01[3] = arc(1.0 - e_al, 1.0);
+    const XrVert ax = make(0.0, 0.0, radius, 0.0, 0.0, false);
+    for (int i = 0; i < 3; ++i) P.axis[i] = ax.p[i];
+    P.radius = radius;
+}
+
+// The eye's position: the null space of vp's x, y and w rows (every point of clip x = y = w = 0).  false: no finite one.
+inline bool xr_eye_pos(const double vp[16], double e[3]) {
+    const double* r[3] = {vp, vp + 4, vp + 12};
+    double h[4];
+    for (int k = 0; k < 4; ++k) {
+        int c[3], n = 0;
+        for (int j = 0; j < 4; ++j) if (j != k) c[n++] = j;
+        const double d = r[0][c[0]] * (r[1][c[1]] * r[2][c[2]] - r[1][c[2]] * r[2][c[1]])
+                       - r[0][c[1]] * (r[1][c[0]] * r[2][c[2]] - r[1][c[2]] * r[2][c[0]])
+                       + r[0][c[2]] * (r[1][c[0]] * r[2][c[1]] - r[1][c[1]] * r[2][c[0]]);
+        h[k] = (k & 1) ? -d : d;
+    }
+    const double m = fmax(fmax(fabs(h[0]), fabs(h[1])), fabs(h[2]));
+    if (!(fabs(h[3]) > 1e-12 * m) || !(fabs(h[3]) > 0.0)) return false;
+    for (int i = 0; i < 3; ++i) e[i] = h[i] / h[3];
+    return xr_finite(e, 3);
+}
+// The arc and its two tangent rays bound, extruded, a convex region that opens towards the viewer.  true: the eye lies on the inner
+// side of all 50 outer piece planes (the side of the cylinder's axis) by more than 1e-4 of the radius: then every ray from it meets
+// the surface at most once, and the seams order the pieces monotonically across the image.
+inline bool xr_eye_inside(const XrSurface& S, const XrCurvedPieces& P, const double vp[16]) {
+    double e[3];
+    if (!xr_eye_pos(vp, e)) return false;
+    for (int k = 0; k < XR_MAX_FACETS + 2; ++k) {
+        const XrVert& a = k < XR_MAX_FACETS ? S.p00[k] : P.p00[k - XR_MAX_FACETS];
+        const XrVert& b = k < XR_MAX_FACETS ? S.p10[k] : P.p10[k - XR_MAX_FACETS];
+        const XrVert& d = k < XR_MAX_FACETS ? S.p01[k] : P.p01[k - XR_MAX_FACETS];
+        double dA[3], dB[3];
+        for (int i = 0; i < 3; ++i) { dA[i] = b.p[i] - a.p[i]; dB[i] = d.p[i] - a.p[i]; }
+        const double n[3] = {dA[1] * dB[2] - dA[2] * dB[1], dA[2] * dB[0] - dA[0] * dB[2], dA[0] * dB[1] - dA[1] * dB[0]};
+        const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        double de = 0.0, da = 0.0;
+        for (int i = 0; i < 3; ++i) { de += n[i] * (e[i] - a.p[i]); da += n[i] * (P.axis[i] - a.p[i]); }
+        if (!((da < 0.0 ? -de : de) > 1e-4 * P.radius * nn)) return false;
+    }
+    return true;
+}
+// One eye's 52 rows: the facets exactly as xr_facets forms them, then the tangent and chord pieces (mode 2: the chord rows cover nothing).
+inline void xr_curved_table(const XrSurface& S, const XrCurvedPieces& P, int mode, const double vp[16], int w, int h, XrFacet* out) {
+    xr_facets(S, vp, w, h, out);
+    for (int k = 0; k < 4; ++k) {
+        if (k >= 2 && mode != 1) { out[XR_T0 + k] = XrFacet{}; out[XR_T0 + k].ha[2] = -1.f; continue; }
+        xr_facet_row(P.p00[k], P.p10[k], P.p01[k], vp, w, h, out[XR_T0 + k]);
+    }
 }
 
 }  // namespace d2s

@@ -1022,6 +1022,10 @@ int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batc
 int dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
                      const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
                      uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
+int dibr_xr_glow_curved_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                            const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                            void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
+                            bool check_only);
 }
 
 namespace {
@@ -1148,12 +1152,14 @@ extern "C" int d2s_view_pipeline_crop_streams(d2s_engine* e, const uint8_t* fram
 }
 
 // d2s_view_pipeline_crop_streams with the OpenXR eye views (d2s_dibr_xr_eyes) as the last stage: the same checks and depth path
-// (d2s_view_pipeline_xr_glow_streams: the same call with the glow; glow == nullptr is d2s_view_pipeline_xr_streams)
+// (d2s_view_pipeline_xr_glow_streams: the same call with the glow; glow == nullptr is d2s_view_pipeline_xr_streams;
+//  curved: d2s_view_pipeline_xr_glow_curved_streams, whose last stage is d2s_dibr_xr_eyes_glow_curved)
 static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
                                 int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
                                 const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
                                 const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
-                                void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
+                                void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
+                                bool curved = false) {
     D2S_REQUIRE(frames && pp && dp && out && screen && eyes, "null pointer");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     uint64_t offs[2], total = 0;
@@ -1162,8 +1168,9 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
     int stride = 1;
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
     auto warp = [&](bool check_only) {
-        return dibr_xr_glow_any(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                                workspace_bytes, glow, levels, stream, check_only);
+        return (curved ? dibr_xr_glow_curved_any : dibr_xr_glow_any)(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes,
+                                                                     n_eyes, out, out_fmt, workspace, workspace_bytes, glow, levels, stream,
+                                                                     check_only);
     };
     RC(warp(true));
     D2S_ON_DEVICE(e->device);
@@ -1191,6 +1198,17 @@ extern "C" int d2s_view_pipeline_xr_glow_streams(d2s_engine* e, const uint8_t* f
                                                  void* stream) {
     return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
                                 out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream);
+}
+
+// the engine's pipeline up to the EMA step, then d2s_dibr_xr_eyes_glow_curved on the model-resolution depth
+extern "C" int d2s_view_pipeline_xr_glow_curved_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                                        int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                                        const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                                        const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt,
+                                                        float* depth_full, void* workspace, uint64_t workspace_bytes,
+                                                        const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
+    return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
+                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, true);
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

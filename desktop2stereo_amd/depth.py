@@ -346,8 +346,9 @@ def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_tempor
 
 def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=None, inner_edge_fraction=0.075, head=None, crop=None,
                       corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
-    """xr_eye_views with the reference's "Default with Glow" looks around the flat screen (_render_glow, xr_viewer/effects.py:476-585)
-    drawn in the same launch.  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
+    """xr_eye_views with the reference's "Default with Glow" looks drawn in the same launch: around the flat screen (_render_glow,
+    xr_viewer/effects.py:476-585) and around a curved one (_render_curved_glow, effects.py:408-474; an eye outside the convex region the
+    curved screen bounds, xr.XrScreen.eye_inside, is refused).  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
     frames' colour mip chain (ops.mip_chain); None builds it here, every call -- the reference refreshes its own every
     _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  Frost, veil, border, controllers and
     environment stay with the caller."""
@@ -371,8 +372,9 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
     if levels is None and glow.mode != "off":
         levels = ops.mip_chain(t)
     dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
-    return eng.view_pipeline_xr_glow(t, p, dp, screen, eyes, glow, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
-                                     want_depth=want_depth, streams=streams)
+    run = eng.view_pipeline_xr_glow if getattr(screen, "curve", "flat") == "flat" else eng.view_pipeline_xr_glow_curved
+    return run(t, p, dp, screen, eyes, glow, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
+               streams=streams)
 
 
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,

@@ -418,11 +418,11 @@ def dibr_xr_shape(eyes, batch: int, alpha_mode: int = 0) -> Tuple[list, int]:
     return list(offs), total.value
 
 
-def _xr_workspace(n_eyes: int, device) -> torch.Tensor:
+def _xr_workspace(n_eyes: int, device, query: str = "d2s_dibr_xr_workspace") -> torch.Tensor:
     """The facet table's home for calls on the current stream of `device`: one per (device, stream), since calls on one stream are
-    ordered and calls on different streams must not share it."""
+    ordered and calls on different streams must not share it.  query: the size query of the call it serves."""
     nbytes = C.c_uint64()
-    check(_lib.load().d2s_dibr_xr_workspace(n_eyes, C.byref(nbytes)), "d2s_dibr_xr_workspace")
+    check(getattr(_lib.load(), query)(n_eyes, C.byref(nbytes)), query)
     key = (device, torch.cuda.current_stream(device).cuda_stream)
     ws = _XR_WS.get(key)
     if ws is None or ws.numel() < nbytes.value:
@@ -520,37 +520,52 @@ def dibr_xr_eyes_glow(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrP
     """dibr_xr_eyes with the reference's glow around the flat screen in the same launch (d2s_dibr_xr_eyes_glow; reference
     _render_glow, xr_viewer/effects.py:476-585): glow = xr.XrGlow (None or mode "off": exactly dibr_xr_eyes), levels = mip_chain(frames)
     -- or an older chain: the reference refreshes its mipmaps every few frames only.  Everything else as dibr_xr_eyes."""
+    return _dibr_xr_eyes_glow("d2s_dibr_xr_eyes_glow", "d2s_dibr_xr_workspace", "dibr_xr_eyes_glow", frames, depth, dp, screen, eyes, glow,
+                              levels, crop, out_u8, out, workspace)
+
+
+def dibr_xr_eyes_glow_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
+                             out_u8: bool = True, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> list:
+    """dibr_xr_eyes_glow that also draws the glow around a CURVED screen (d2s_dibr_xr_eyes_glow_curved; reference _render_curved_glow,
+    xr_viewer/effects.py:408-474): screen.curve "horizontal" | "vertical" with glow mode "glow" | "glow2".  A flat screen or no glow is
+    exactly dibr_xr_eyes_glow.  An eye outside the convex region the screen bounds (xr.XrScreen.eye_inside) is refused.  workspace: a
+    caller-kept uint8 device tensor of d2s_dibr_xr_glow_curved_workspace bytes."""
+    return _dibr_xr_eyes_glow("d2s_dibr_xr_eyes_glow_curved", "d2s_dibr_xr_glow_curved_workspace", "dibr_xr_eyes_glow_curved", frames, depth,
+                              dp, screen, eyes, glow, levels, crop, out_u8, out, workspace)
+
+
+def _dibr_xr_eyes_glow(entry, ws_query, who, frames, depth, dp, screen, eyes, glow, levels, crop, out_u8, out, workspace) -> list:
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
-        raise ValueError("dibr_xr_eyes_glow: frames must be uint8 [B,H,W,3] or [H,W,3]")
+        raise ValueError(f"{who}: frames must be uint8 [B,H,W,3] or [H,W,3]")
     f = frames.contiguous() if frames.dim() == 4 else frames.contiguous().unsqueeze(0)
     d = depth.to(torch.float32).contiguous()
     d = d if d.dim() == 3 else d.unsqueeze(0)
     B, H, W, _ = f.shape
     if d.dim() != 3 or d.shape[0] != B:
-        raise ValueError(f"dibr_xr_eyes_glow: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
-    _same_device(f, d, "dibr_xr_eyes_glow")
+        raise ValueError(f"{who}: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
+    _same_device(f, d, who)
     sc, ea = _xr_args(screen, eyes)
     if levels is not None and levels.dim() == 1:
         levels = levels.unsqueeze(0)
-    gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, "dibr_xr_eyes_glow")
+    gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, who)
     offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
     nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
     dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
     if out is None:
         out = torch.empty(total, dtype=dtype, device=f.device)
     elif not out.is_cuda or out.device != f.device or out.dtype != dtype or out.numel() != total or not out.is_contiguous():
-        raise ValueError(f"dibr_xr_eyes_glow: out must be a contiguous {dtype} tensor of {total} elements on {f.device}")
-    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device)
+        raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of {total} elements on {f.device}")
+    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device, ws_query)
     _need_cuda(ws, "workspace")
-    _same_device(f, ws, "dibr_xr_eyes_glow workspace")
+    _same_device(f, ws, f"{who} workspace")
     c4 = _crop4(crop) if crop is not None else None
     with _on(f.device) as st:
-        check(_lib.load().d2s_dibr_xr_eyes_glow(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
+        check(getattr(_lib.load(), entry)(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
                                                 _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(),
                                                 C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None, st),
-              "d2s_dibr_xr_eyes_glow")
+              entry)
     return _xr_views(out.view(-1), ea, B, nch, offs)
 
 
@@ -850,10 +865,12 @@ class Engine:
         view_pipeline_crop is: view_pipeline's parameter list is pinned by the ABI tests.)"""
         return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, None, None)
 
-    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels):
+    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, curved=False):
         sc, ea = _xr_args(screen, eyes)
         nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
         name, who = ("d2s_view_pipeline_xr_streams", "view_pipeline_xr") if glow is None else ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow")
+        if curved:
+            name, who = "d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved"
         lay = {}
 
         def spec(B, H, W):
@@ -862,14 +879,14 @@ class Engine:
             if glow is not None:
                 lay["glow"] = _xr_glow_args(glow, levels, B, H, W, self.device, who)
             return (lay["total"],), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
-        ws = _xr_workspace(len(ea), self.device)
+        ws = _xr_workspace(len(ea), self.device, "d2s_dibr_xr_glow_curved_workspace" if curved else "d2s_dibr_xr_workspace")
         nbytes = ws.numel()
 
         def fn(*a):      # (_run_pipeline ends every call with out, out_fmt, depth_full, stream: the workspace goes in front of the stream)
             if glow is None:
                 return self.lib.d2s_view_pipeline_xr_streams(*a[:-1], _ptr(ws), nbytes, a[-1])
             gs, lv = lay["glow"]
-            return self.lib.d2s_view_pipeline_xr_glow_streams(*a[:-1], _ptr(ws), nbytes, C.byref(gs), _ptr(lv) if lv is not None else None, a[-1])
+            return getattr(self.lib, name)(*a[:-1], _ptr(ws), nbytes, C.byref(gs), _ptr(lv) if lv is not None else None, a[-1])
         mid = (C.byref(dp), _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea), int(use_ema))
         r = self._run_pipeline(fn, name, frames, p, spec, mid, want_depth, out, streams, who=who)
         flat = (r[0] if want_depth else r).view(-1)
@@ -885,6 +902,16 @@ class Engine:
         if glow is None:
             raise ValueError("view_pipeline_xr_glow: glow must be an xr.XrGlow (mode \"off\" for none)")
         return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels)
+
+    def view_pipeline_xr_glow_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels,
+                                     crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
+                                     out: Optional[torch.Tensor] = None, streams=None):
+        """view_pipeline_xr_glow whose last stage also draws the glow around a curved screen
+        (d2s_view_pipeline_xr_glow_curved_streams).  Bit-identical to pipeline(want_depth=True)'s engine depth followed by
+        dibr_xr_eyes_glow_curved."""
+        if glow is None:
+            raise ValueError("view_pipeline_xr_glow_curved: glow must be an xr.XrGlow (mode \"off\" for none)")
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, curved=True)
 
     def close(self):
         if getattr(self, "_h", None):

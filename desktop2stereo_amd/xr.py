@@ -84,6 +84,68 @@ class XrScreen:
                 out[i * 2 + j, 3:] = (float(j), t) if vert else (t, float(j))
         return out
 
+    def _curved_frame(self):
+        """(point(t, ac), direction(ang) * length, length, radius, a point of the cylinder's axis) of the arc: t = the strip coordinate
+        0..1, ac = the coordinate across it 0..1; screen coordinates (u, v) = (t, ac) for a horizontal curve, (ac, t) for a vertical one."""
+        R, centre = self.basis()
+        rot, vert = R[:3, :3], self.curve == "vertical"
+        length, wid = (self.height, self.width) if vert else (self.width, self.height)
+        radius = length / 2.0 / CURVED_HALF_ANGLE_RAD
+
+        def local(al, ac, lz):
+            return rot @ (np.array([ac, al, lz]) if vert else np.array([al, ac, lz]))
+
+        def point(t, ac):
+            ang = -CURVED_HALF_ANGLE_RAD + 2.0 * CURVED_HALF_ANGLE_RAD * t
+            return centre + local(radius * math.sin(ang), (ac - 0.5) * wid, radius * (1.0 - math.cos(ang)))
+        return point, (lambda ang: local(math.cos(ang) * length, 0.0, math.sin(ang) * length)), length, radius, centre + local(0.0, 0.0, radius)
+
+    def glow_pieces(self, glow: "XrGlow" = None) -> list:
+        """The curved glow's band mesh (_build_curved_glow_band_verts, xr_viewer/effects.py:314-406) as the planar pieces the library
+        draws: [(name, p00, p10, p01, g00, g10, g01)] -- three corners in world space and the screen coordinates (ga, gb) there, both
+        affine over the piece.  "facet<i>": the strip's facets, unbounded across the strip; "tangent0" / "tangent1": the tangent planes
+        at the arc's ends (p10 = one screen length along the tangent); with a glow: "chord0" / "chord1", the inner band's planes at
+        the ends, from the end to the strip coordinate inner_uv / inner_(w | h) (the mesh has them for "glow2" too, which never draws
+        its inner vertices)."""
+        if self.curve == "flat":
+            raise ValueError("glow_pieces: the screen is flat")
+        point, tangent, _, _, _ = self._curved_frame()
+        vert = self.curve == "vertical"
+        g = (lambda t, ac: (ac, t)) if vert else (lambda t, ac: (t, ac))
+        n = CURVED_SEGMENTS
+        ts = [i / n for i in range(n + 1)]
+        out = [(f"facet{i}", point(ts[i], 0.0), point(ts[i + 1], 0.0), point(ts[i], 1.0), g(ts[i], 0.0), g(ts[i + 1], 0.0), g(ts[i], 1.0))
+               for i in range(n)]
+        for k, ang in enumerate((-CURVED_HALF_ANGLE_RAD, CURVED_HALF_ANGLE_RAD)):
+            p = point(float(k), 0.0)
+            out.append((f"tangent{k}", p, p + tangent(ang), point(float(k), 1.0), g(float(k), 0.0), g(k + 1.0, 0.0), g(float(k), 1.0)))
+        if glow is not None and glow.mode != "off":
+            u = glow.uniforms(self)
+            inner_uv = min(u["inner_w"], u["inner_h"]) * max(float(glow.inner_edge_fraction), 0.0)
+            e = min(0.5, inner_uv / (u["inner_h"] if vert else u["inner_w"]))
+            for k, (t0, t1) in enumerate(((0.0, e), (1.0 - e, 1.0))):
+                out.append((f"chord{k}", point(t0, 0.0), point(t1, 0.0), point(t0, 1.0), g(t0, 0.0), g(t1, 0.0), g(t0, 1.0)))
+        return out
+
+    def eye_inside(self, vp) -> bool:
+        """Whether the eye of vp = proj @ view (its position: the null space of vp's x, y and w rows) lies inside the convex region the
+        curved screen and its two tangent planes bound, by 1e-4 of the arc's radius: what d2s_dibr_xr_eyes_glow_curved demands of every
+        eye (outside it the glow's translucent pieces overlap).  True for a flat screen."""
+        if self.curve == "flat":
+            return True
+        m = np.array(vp, np.float64).reshape(4, 4)[[0, 1, 3]]
+        h = np.array([(-1.0) ** k * np.linalg.det(np.delete(m, k, axis=1)) for k in range(4)])
+        if not abs(h[3]) > 1e-12 * np.abs(h[:3]).max() or not abs(h[3]) > 0.0:
+            return False
+        eye = h[:3] / h[3]
+        _, _, _, radius, axis = self._curved_frame()
+        for _, p00, p10, p01, *_ in self.glow_pieces():
+            nrm = np.cross(p10 - p00, p01 - p00)
+            de, da = float(nrm @ (eye - p00)), float(nrm @ (axis - p00))
+            if not (-de if da < 0 else de) > 1e-4 * radius * float(np.linalg.norm(nrm)):
+                return False
+        return True
+
 
 @dataclass
 class XrGlow:

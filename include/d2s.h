@@ -486,7 +486,7 @@ int d2s_mip_chain(const uint8_t* rgb, int batch, int H, int W, uint8_t* levels, 
  *   so ITS screen pass is trilinear where the screen is minified.  That filter needs implicit derivatives and is driver-dependent; the
  *   screen pass here stays GL_LINEAR, as d2s_dibr_xr_eyes has it.  Frost, veil and border stay with the caller.
  * Refused, nothing launched, out untouched: D2S_E_UNSUPPORTED: screen->curve != 0 with mode != 0 (the curved glow is a band mesh of
- * ~500 quads, _build_curved_glow_band_verts).  D2S_E_INVALID: normal_offset != 0 with mode != 0 (the reference offsets the screen only
+ * ~500 quads, _build_curved_glow_band_verts: d2s_dibr_xr_eyes_glow_curved below draws it).  D2S_E_INVALID: normal_offset != 0 with mode != 0 (the reference offsets the screen only
  * under a room model, which switches the planar glow off); range_m <= 0 or non-finite; inner_edge_fraction < 0 or non-finite; mode
  * outside 0..2; a bad struct_size; levels NULL with mode != 0; everything d2s_dibr_xr_eyes refuses.  glow == NULL or mode 0 is
  * bit-identical to d2s_dibr_xr_eyes (the same kernel). */
@@ -499,6 +499,32 @@ typedef struct d2s_xr_glow {
 int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                           const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
                           void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream);
+
+/* The glow around the CURVED screen (d2s_version() >= 122): d2s_dibr_xr_eyes_glow's argument list; screen->curve 1 or 2 with mode 1 or 2
+ * draws what EffectsMixin._render_curved_glow draws (xr_viewer/effects.py:408-474; mesh _build_curved_glow_band_verts, effects.py:314-406;
+ * program _CURVED_VERT + _GLOW_FRAG, xr_viewer/glsl.py:580-666) in _render_eye's order (effects.py:1050-1145): clear; the mesh's outer
+ * vertices blended over it; the curved strip exactly as d2s_dibr_xr_eyes draws it (a screen pixel has that call's facet and uv); mode 1:
+ * the mesh's inner vertices blended over the screen.  Blending, quantisation and alpha_mode as d2s_dibr_xr_eyes_glow; glow_w .. inner_uv
+ * as _render_curved_glow:414-423 forms them.
+ *   The mesh is restated as planar pieces, formed on the host in double precision and rounded to float32 once: the strip's 48 facets,
+ *   each continued without bound across the strip; the two tangent planes at the arc's ends (_local_axes at -+0.48 rad); mode 1: the two
+ *   chord planes of the inner band at the arc's ends (one quad along the strip each).  The inner bands that run ALONG the strip are drawn
+ *   on the facets (a horizontal curve's lie on them; a vertical curve's are 48 chords of the arc that do not start at a facet seam and
+ *   lie within radius * (1 - cos(0.01)) = 5e-5 radius of the facets).  A pixel finds its one piece by a search over the 49 seam lines.
+ *   workspace: device, 16-byte aligned, >= d2s_dibr_xr_glow_curved_workspace(n_eyes) bytes (52 rows of 96 bytes per eye), written by
+ *   set-up launches whose arguments carry the rows: no host copy, no allocation, stream-ordered.
+ * A flat screen, glow == NULL or mode 0: d2s_dibr_xr_eyes_glow, bit-identical (the same kernel; the larger workspace is still required
+ * of a curved screen only).  Refused, nothing launched, out untouched: everything d2s_dibr_xr_eyes_glow refuses apart from the
+ * curvature; D2S_E_INVALID: normal_offset != 0; D2S_E_UNSUPPORTED: an eye (the null space of vp's x, y and w rows) that does not lie
+ * on the inner side of all 50 outer piece planes by 1e-4 of the arc's radius -- a viewer behind the screen or beyond an end of the arc.
+ * There translucent pieces overlap and would have to be blended in draw order: an ordered multi-hit kernel, not built.  Also
+ * D2S_E_UNSUPPORTED: a frame of 8192 x 8192 (its coarse levels and the piece table exceed 64 KB of LDS).  Frost, veil, border and the
+ * trilinear screen pass stay with the caller, as above. */
+int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes);
+int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                 const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                 int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
+                                 void* stream);
 
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
@@ -626,6 +652,15 @@ int d2s_view_pipeline_xr_glow_streams(d2s_engine* e, const uint8_t* frames, int 
                                       const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int use_ema,
                                       void* out, int out_fmt, float* depth_full, void* workspace, uint64_t workspace_bytes,
                                       const d2s_xr_glow* glow, const uint8_t* levels, void* stream);
+/* d2s_view_pipeline_xr_glow_streams with d2s_dibr_xr_eyes_glow_curved as its last stage (d2s_version() >= 122; _render_eye,
+ * xr_viewer/effects.py:1023-1145 with _render_curved_glow, :408-474): workspace as d2s_dibr_xr_glow_curved_workspace.  Bit-identical to
+ * d2s_pipeline(depth_full) followed by d2s_dibr_xr_eyes_glow_curved on the engine's map. */
+int d2s_view_pipeline_xr_glow_curved_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                             int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                             const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                             const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                             void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
+                                             void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

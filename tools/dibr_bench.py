@@ -19,6 +19,10 @@
         horizontally / vertically: 48 facets), against d2s_dibr_warp_crop's gather kernel (D2S_DIBR_NO_ROWS=1, identity crop, both eyes
         at the frame's size) -- the same pixel function on a regular grid.  The screen's distance is set so that the flat screen is
         one source texel per pixel wide; us per launch and ns per COVERED pixel, alternated in one process.
+    python tools/dibr_bench.py --xr-eye --curve h|v --glow glow|glow2 [--glow-range 15.0]
+        d2s_dibr_xr_eyes_glow_curved (the curved screen with its glow: a per-pixel search over the band mesh's planar pieces)
+        alternated in one process with (a) the curved screen without glow, (b) the flat screen with glow and (c) the flat screen
+        without glow: us per launch, the shares of the images the screen and the glow cover, and the ceiling (a) + (b) - (c).
     python tools/dibr_bench.py --xr-eye --glow glow|glow2 [--glow-range 15.0]
         d2s_dibr_xr_eyes_glow (the flat screen with the reference's glow in the same launch, every pixel of both eye images drawn) and
         d2s_mip_chain (the 1080p frame's colour mip chain, which the glow samples), alternated in one process with the flat eye call
@@ -139,9 +143,44 @@ if a.xr_eye:
     eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
     img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
     dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
-    for B in a.batch if a.glow else ():
-        if a.curve:
-            sys.exit("--glow is the flat screen's (the curved glow is not built)")
+    for B in a.batch if a.glow and a.curve else ():
+        import dataclasses
+        flat = dataclasses.replace(screen, curve="flat")
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        glow = xr.XrGlow(a.glow, a.glow_range if a.glow_range else xr.glow_range_m(screen))
+        levels = ops.mip_chain(f)
+        out = torch.empty(ops.dibr_xr_shape(eyes, B, dp.alpha_mode)[1], dtype=torch.uint8, device=dev)
+        probe_s = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)      # clear alpha 0.5 marks the pixels nothing drew
+        probe_g = ops.dibr_xr_eyes_glow_curved(f[:1], d[:1], dp, screen, eyes, glow, levels[:1], out_u8=False)
+        n_px = 2 * ew * eh
+        share_screen = sum(int((e[..., 3] != 0.5).sum()) for e in probe_s) / n_px
+        share_drawn = sum(int((e[..., 3] != 0.5).sum()) for e in probe_g) / n_px
+        runs = {"a_curved_no_glow": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out),
+                "b_flat_glow": lambda: ops.dibr_xr_eyes_glow(f, d, dp, flat, eyes, glow, levels, out=out),
+                "c_flat_no_glow": lambda: ops.dibr_xr_eyes(f, d, dp, flat, eyes, out=out),
+                f"curved_{a.glow}": lambda: ops.dibr_xr_eyes_glow_curved(f, d, dp, screen, eyes, glow, levels, out=out),
+                "a_curved_no_glow_again": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)}
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"xr-eye {screen.curve} {a.glow} (range {glow.range_m:.2f} m) {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}, medians of {a.rounds} rounds x "
+              f"{a.iters} launches; the screen covers {share_screen:.3f} of the images, screen + glow {share_drawn:.3f}:", flush=True)
+        for k in runs:
+            print(f"    {k:26s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {1e3 * med[k] / (B * n_px):.4f} ns / image pixel)", flush=True)
+        ceiling = med["a_curved_no_glow"] + med["b_flat_glow"] - med["c_flat_no_glow"]
+        spread = max((max(v) - min(v)) / med[k] for k, v in t.items())
+        print(f"    ceiling (a) + (b) - (c) = {ceiling:.1f} us; curved {a.glow} - ceiling = {med[f'curved_{a.glow}'] - ceiling:+.1f} us "
+              f"({100.0 * (med[f'curved_{a.glow}'] / ceiling - 1.0):+.1f} %); (a) against itself {med['a_curved_no_glow_again'] - med['a_curved_no_glow']:+.1f} us; "
+              f"largest (max - min) / median of a row {100.0 * spread:.1f} %", flush=True)
+    for B in a.batch if a.glow and not a.curve else ():
         f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
         d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
         glow = xr.XrGlow(a.glow, a.glow_range if a.glow_range else xr.glow_range_m(screen))
