@@ -62,6 +62,10 @@ struct d2s_engine {
     hipStream_t side = nullptr;
     hipEvent_t ev_tap[4] = {nullptr, nullptr, nullptr, nullptr}, ev_ln[4] = {nullptr, nullptr, nullptr, nullptr}, ev_side = nullptr;
     bool overlap = true;
+    bool side_sync = true;                         // D2S_SIDE_SYNC=0 at creation: shared LayerNorm operands and ev_ln, the fork a recorded event
+    // LayerNorm operands owned by side tap i (sized like lnbuf / lnstats): see tap_ln_pair
+    void* tap_ln[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* tap_stats[4] = {nullptr, nullptr, nullptr, nullptr};
     float* splitk_ws_side = nullptr;               // the side stream's own split-K partials
     void* r1[3] = {nullptr, nullptr, nullptr};     // RCU1(feat[i]) = feat[i] + conv2(relu(conv1(relu(feat[i])))), i = 0..2
     void* r1tmp = nullptr;
@@ -267,7 +271,24 @@ void interp_pos(const float* pos, int grid, int D, int gh, int gw, std::vector<f
 
 // the engine state plan_forward decides on
 FrameState frame_state(const d2s_engine* e) {
-    return FrameState{e->calib, e->fp8_ready, e->taps, e->prof_on, e->overlap && e->side != nullptr, e->no_lnfuse, e->tm_fold};
+    return FrameState{e->calib, e->fp8_ready, e->taps, e->prof_on, e->overlap && e->side != nullptr, e->no_lnfuse, e->tm_fold, e->tap_ln[0] != nullptr};
+}
+
+// The LayerNorm operands of the launches around tap i: the bf16 raw residual and the row statistics a tap layer's FC2 leaves for the
+// LayerNorm folded into its two consumers.  pl.tap_private[i] (tap i's branch runs on the side stream and its projection is folded):
+// the pair the tap owns.  INVARIANT of that pair, per frame:
+//   one writer    the FC2 launch of tap i's layer, on the main stream;
+//   two readers   the next layer's LN-folded QKV, on the main stream behind the writer, and neck_proj(i), on the side stream behind the
+//                 fork event, which completes with the writer;
+//   nothing else on either stream touches it: the next layer's proj, which overwrites the shared lnbuf / lnstats while neck_proj(i)
+//                 may still be running, no longer writes what neck_proj(i) reads, so the main stream does not wait for it;
+//   next writer   the same FC2 launch of the NEXT frame: it is queued on the main stream behind this frame's join with the side stream
+//                 (forward joins every frame that forked, in front of its fusion stage), so both readers are done.  Callers keep one
+//                 engine's frames on one stream or order them themselves, as for every other workspace of the engine.
+// Every other tap, and every other LayerNorm of the frame, uses the shared pair.
+struct LnPair { void* buf; float* stats; };
+LnPair tap_ln_pair(const d2s_engine* e, const ForwardPlan& pl, int i) {
+    return i >= 0 && i < 4 && pl.tap_private[i] ? LnPair{e->tap_ln[i], e->tap_stats[i]} : LnPair{e->lnbuf, e->lnstats};
 }
 
 // The slot guard: a LayerNorm producer reported another number of statistics partials than plan_forward took from plan_gemm for the
@@ -279,9 +300,10 @@ int slots_check(int got, int planned, const char* site) {
 }
 
 // a packed linear (convA: an implicit-GEMM convolution): launch_linear with the split-K partials of its stream, each has its own
-int linear(d2s_engine* e, const GemmA& a, const DevLinear& w, int M, const GemmEpi& ep, hipStream_t st) {
+// stop: an event that completes with the launch (launch_gemm)
+int linear(d2s_engine* e, const GemmA& a, const DevLinear& w, int M, const GemmEpi& ep, hipStream_t st, hipEvent_t stop = nullptr) {
     float* ws = (e->side && st == e->side) ? e->splitk_ws_side : e->splitk_ws;
-    PROF(a.mode == A_CONV3 ? PC_CONV : PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_linear(w, a, M, ep, ws, e->g.splitk_elems, 0, st));
+    PROF(a.mode == A_CONV3 ? PC_CONV : PC_GEMM, 2.0 * M * w.N * w.K, 0, launch_linear(w, a, M, ep, ws, e->g.splitk_elems, 0, st, stop));
     return D2S_OK;
 }
 
@@ -387,16 +409,17 @@ int run_temporal(d2s_engine* e, const ForwardPlan& pl, int m, const void* x, voi
 // three shallower taps -- the first residual unit of their fusion layer, RCU1(m) = m + conv2(relu(conv1(relu(m)))),
 // which depends on this map only (HF DepthAnythingFeatureFusionLayer adds it to the deeper stage's output later).
 // reassemble projection of tap i.  pl.tap_folded: the shared final LayerNorm happens inside it -- A = the raw bf16
-// residual the tap layer's FC2 left in lnbuf (patch rows: skip the cls row), statistics from lnstats (same row offset)
+// residual the tap layer's FC2 left in the tap's LayerNorm operands (tap_ln_pair; patch rows: skip the cls row), statistics likewise
 int neck_proj(d2s_engine* e, const ForwardPlan& pl, int i, int B, hipStream_t st) {
     const d2s_model_desc& d = e->d;
     const int D = d.hidden, Mp = B * e->g.P, c = d.neck[i];
     const DevLinear& W = e->re[i].proj.form(false, pl.tap_folded);
     GemmEpi ep = rowsE(e->rproj[i], OUT_T, c, W.bias);
     if (!pl.tap_folded) return linear(e, plainA(e->tapbuf[i], D), W, Mp, ep, st);
-    epi_ln_consumer(ep, e->lnstats, pl.slots_fc2, W.csum, d.ln_eps, D);
+    const LnPair ln = tap_ln_pair(e, pl, i);
+    epi_ln_consumer(ep, ln.stats, pl.slots_fc2, W.csum, d.ln_eps, D);
     const int skip = epi_tap_fold_rows(ep, B, e->g.N, e->g.P);     // one frame: start one row in; several: all token rows, cls rows dropped
-    return linear(e, plainA((const bf16_t*)e->lnbuf + (size_t)skip * D, D), W, skip ? Mp : B * e->g.N, ep, st);
+    return linear(e, plainA((const bf16_t*)ln.buf + (size_t)skip * D, D), W, skip ? Mp : B * e->g.N, ep, st);
 }
 
 int neck_rest(d2s_engine* e, const ForwardPlan& pl, int i, int B, hipStream_t st) {
@@ -448,6 +471,8 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
     // GEMM / conv reads fp32 activations and splits them between its staging registers and LDS
     const bool f8 = pl.f8, f8a = pl.f8a, x3 = pl.x3;
     int pending_ln = -1;
+    bool fork_in_launch = false;
+    int ln_tap = -1;                // the tap whose layer ran last, -1: none -- where this layer's folded LN1 finds its operands (tap_ln_pair)
     for (int l = 0; l < d.layers; ++l) {
         const Layer& ly = e->L[l];
         const float* sa = f8 ? &e->act_scale[(size_t)l * NSITE] : nullptr; // s_act of LN1 out, attention out, LN2 out, GELU out, residual x 2
@@ -460,8 +485,10 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         {
             const DevLinear& W = ly.qkv.form(f8a, ln1_folded);
             GemmEpi ep = epi_qkv(e->qkv, qkv_out_type(f8, x3), D, W.bias, e->vt, N, e->g.Npad, d.heads);
-            if (ln1_folded) epi_ln_consumer(ep, e->lnstats, pl.slots_fc2, W.csum, d.ln_eps, D);
-            RC(linear(e, splitA(e->lnbuf, D, x3), W, M, ep, st));
+            const LnPair ln = tap_ln_pair(e, pl, ln1_folded ? ln_tap : -1);      // (the LN kernel writes the shared lnbuf)
+            if (ln1_folded) epi_ln_consumer(ep, ln.stats, pl.slots_fc2, W.csum, d.ln_eps, D);
+            RC(linear(e, splitA(ln.buf, D, x3), W, M, ep, st));
+            ln_tap = -1;
         }
         PROF(PC_ATTN, 4.0 * B * d.heads * (double)N * N * 64, 0,
              launch_attention(x3 ? D2S_PREC_BF16X3 : prec, e->qkv, e->vt, e->attn, B, N, e->g.Npad, d.heads, st, f8a ? 1.0f / sa[1] : 0.f, e->attn_prescaled));
@@ -489,23 +516,29 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         {
             const DevLinear& W = ly.fc2.form(f8, false);
             const bool stats = l + 1 < d.layers ? pl.fc2_stats : pl.fc2_stats_last;
+            const bool tap_layer = tap_i < 4 && l + 1 == d.out_indices[tap_i];
             int slots = -1;
-            const LinearOp o = op_residual(e->resid, D, e->mlp, d.mlp, x3, W.bias, ly.ls2, e->lnbuf, e->lnstats, stats ? &slots : nullptr, f8 ? 1.0f / sa[5] : 0.f);
-            RC(linear(e, o.a, W, M, o.ep, st));
+            const LnPair ln = tap_ln_pair(e, pl, tap_layer ? tap_i : -1);
+            const LinearOp o = op_residual(e->resid, D, e->mlp, d.mlp, x3, W.bias, ly.ls2, ln.buf, ln.stats, stats ? &slots : nullptr, f8 ? 1.0f / sa[5] : 0.f);
+            // a folded side tap forks behind this launch: its own completion is the fork event (no marker packet on the main stream)
+            fork_in_launch = tap_layer && pl.tap_side[tap_i] && pl.tap_folded && e->side_sync;
+            RC(linear(e, o.a, W, M, o.ep, st, fork_in_launch ? e->ev_tap[tap_i] : nullptr));
+            if (tap_layer) ln_tap = tap_i;
             if (stats) RC(slots_check(slots, pl.slots_fc2, "FC2"));
         }
         if (am) RC(launch_amax(D2S_PREC_FP32, e->resid, (long)M * D, am + 5, st));       // (raw residual: the next layer's LN-folded QKV)
         if (e->taps) D2S_HIP(hipMemcpyAsync(e->tap_hidden + (size_t)(l + 1) * N * D, e->resid, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
         if (tap_i < 4 && l + 1 == d.out_indices[tap_i]) {     // HF Dinov2Backbone: shared final LN, drop cls
-            // folded: the statistics and the raw residual of the tap layer are still in lnbuf / lnstats when its projection runs; the
-            // main stream waits for that launch -- ev_ln -- before the next layer's projection GEMM overwrites them
+            // folded: the statistics and the raw residual of the tap layer are still in its LayerNorm operands when its projection runs
+            // (tap_ln_pair).  Where those are the shared lnbuf / lnstats (D2S_SIDE_SYNC=0) the main stream waits for that launch -- ev_ln --
+            // before the next layer's projection GEMM overwrites them
             if (!pl.tap_folded) PROF(PC_LN, 0, 0, launch_layernorm(prec, e->resid, e->lnfg, e->lnfb, e->tapbuf[tap_i], Mp, D, d.ln_eps, P, N, 1, st));
             // this tap's neck branch runs under the remaining encoder layers (pl.tap_side)
             if (pl.tap_side[tap_i]) {
-                D2S_HIP(hipEventRecord(e->ev_tap[tap_i], st));
+                if (!fork_in_launch) D2S_HIP(hipEventRecord(e->ev_tap[tap_i], st));
                 D2S_HIP(hipStreamWaitEvent(e->side, e->ev_tap[tap_i], 0));
                 RC(neck_proj(e, pl, tap_i, B, e->side));
-                if (pl.tap_folded) { D2S_HIP(hipEventRecord(e->ev_ln[tap_i], e->side)); pending_ln = tap_i; }
+                if (pl.tap_folded && !pl.tap_private[tap_i]) { D2S_HIP(hipEventRecord(e->ev_ln[tap_i], e->side)); pending_ln = tap_i; }
                 RC(neck_rest(e, pl, tap_i, B, e->side));
             } else {
                 RC(neck_proj(e, pl, tap_i, B, st));           // (its inputs are overwritten by the next layer; the rest can wait)
@@ -513,7 +546,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
             ++tap_i;
         }
     }
-    // ---- neck branches that did not run on the side stream, then join it
+    // ---- neck branches that did not run on the side stream, then join it (every frame that forked joins here: tap_ln_pair relies on it)
     for (int i = 0; i < 4; ++i)
         if (!pl.tap_side[i]) RC(neck_rest(e, pl, i, B, st));
     if (pl.use_side) {
@@ -737,7 +770,8 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     const size_t M = (size_t)B * N, Mp = (size_t)B * P;
     RC(dev_alloc(e, (void**)&e->resid, M * D * 4));
     RC(dev_alloc(e, &e->lnbuf, M * D * es));
-    if (e->lnf || e->fp8) RC(dev_alloc(e, (void**)&e->lnstats, (size_t)(D / 16 + 1) * M * 2 * sizeof(float)));
+    const size_t lnstats_bytes = (size_t)(D / 16 + 1) * M * 2 * sizeof(float);
+    if (e->lnf || e->fp8) RC(dev_alloc(e, (void**)&e->lnstats, lnstats_bytes));
     RC(dev_alloc(e, &e->qkv, M * 3 * D * es));
     RC(dev_alloc(e, &e->vt, (size_t)B * D * e->g.Npad * es, true));     // zero beyond N, never written there
     RC(dev_alloc(e, &e->attn, M * D * es));
@@ -757,12 +791,20 @@ extern "C" int d2s_engine_finalize(d2s_engine* e, int h, int w, int max_batch) {
     RC(dev_alloc(e, &e->r1tmp, (size_t)B * e->g.fH[0] * e->g.fW[0] * F * es));
     RC(dev_alloc(e, (void**)&e->splitk_ws_side, (e->g.splitk_elems + GEMM_PART_CTR_WORDS) * 4, true));
     e->overlap = env_int("D2S_NO_OVERLAP", 0) == 0;
+    e->side_sync = env_int("D2S_SIDE_SYNC", 1) != 0;
     if (e->overlap) {
         D2S_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
         for (int i = 0; i < 4; ++i) D2S_HIP(hipEventCreateWithFlags(&e->ev_tap[i], hipEventDisableTiming));
         for (int i = 0; i < 4; ++i) D2S_HIP(hipEventCreateWithFlags(&e->ev_ln[i], hipEventDisableTiming));
         D2S_HIP(hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming));
     }
+    // a LayerNorm operand pair per side tap (tap_ln_pair) for the engines whose frames can fold a side tap's projection: the precision
+    // folds there (bf16), any max_batch reaches batch 1, and the side stream exists
+    if (e->side_sync && e->overlap && e->lnf && pr.ln_folds(D2S_LIN_NECK_PROJ))
+        for (int i = 0; i < (d.temporal ? 4 : 3); ++i) {
+            RC(dev_alloc(e, &e->tap_ln[i], M * D * es));
+            RC(dev_alloc(e, (void**)&e->tap_stats[i], lnstats_bytes));
+        }
     if (d.temporal) {
         // ---- Video-Depth-Anything temporal modules (reference dpt_temporal.py:50-60): layer_3, layer_4, path_4, path_3
         size_t sc_max = 0, max_sites = 0;

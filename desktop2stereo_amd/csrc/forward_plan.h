@@ -97,6 +97,7 @@ struct FrameState {
     bool side;           // the engine has its side stream (D2S_NO_OVERLAP unset)
     bool no_lnfuse;      // D2S_NO_LNFUSE at creation
     bool tm_fold;        // temporal engine: the folded forms of its modules were built (bf16, D2S_VDA_FUSE)
+    bool tap_private;    // the engine has a LayerNorm operand pair per side tap (D2S_SIDE_SYNC, bf16 engines that fold)
 };
 // statistics partials per row a consumer kernel takes; a producer that leaves more (or none: WN == 1 tiles) is followed by the LN kernel
 constexpr int LN_SLOTS_MAX = 16;
@@ -110,6 +111,8 @@ struct ForwardPlan {
     bool fc2_stats, fc2_stats_last; // FC2 is a producer; the last layer's too (only the folded reassemble projections read it)
     bool tap_folded;                // the final LayerNorm inside the four reassemble projections
     bool tap_side[4];               // tap i's neck branch runs on the side stream under the remaining encoder layers
+    bool tap_private[4];            // ... and its folded projection reads the tap's own LayerNorm operands, not lnbuf / lnstats (engine.hip
+                                    // tap_ln_pair; where and how the streams fork and join is not a reported field)
     bool head1_ups;                 // the last fusion stage's up-sample folded into head conv1's loader
     bool head2_fused, head2_ups;    // conv2 + conv3 in one launch (bn: its column tile); the interpolate in front folded into its loader
     int bn;
@@ -175,6 +178,7 @@ static inline int plan_forward(const d2s_model_desc& d, const EngineGeom& g, int
     // taps 0..2 (+ the RCU1 of their fusion layer) only depend on their tap: side stream.  VDA: the temporal modules of branches 2 and 3
     // share the tm_* workspaces, so branch 3 queues behind branch 2 on the side stream instead of racing it
     for (int i = 0; i < 4; ++i) pl.tap_side[i] = pl.use_side && (i < 3 || d.temporal);
+    for (int i = 0; i < 4; ++i) pl.tap_private[i] = pl.tap_side[i] && pl.tap_folded && s.tap_private;
     pl.ln_launches = 1 + (d.layers - 1) * !pl.ln1_folded + d.layers * !pl.ln2_folded + 4 * !pl.tap_folded;
     // ---- temporal modules: the LayerNorm in front of kvq[0] / kvq[1] / ff1 folds where its producer (proj_in / to_out[0] / to_out[1])
     // leaves 1 .. 16 partials per row

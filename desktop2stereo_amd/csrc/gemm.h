@@ -2,6 +2,7 @@
 //   C[m, n] = epilogue( sum_k A[m, k] * W[n, k] )          W packed [Npad][Kpad], K contiguous
 #pragma once
 #include "common.h"
+#include <hip/hip_ext.h>
 #include <cstring>
 
 namespace d2s {
@@ -75,8 +76,17 @@ struct GemmEpi {
 };
 
 // precision: D2S_PREC_FP32 (T = float) / D2S_PREC_BF16 (T = bf16) / D2S_PREC_FP8_OPERANDS (T = e4m3).  tile: 0 = auto.
+// stop (optional): an event that completes when the launch -- its last kernel -- has finished.  gemm_glds_kernel and the ping-pong kernel
+// hand it to the dispatch itself (D2S_LAUNCH_STOP: the kernel's own completion signal, no marker packet behind it); behind the other
+// families it is recorded on st.
 int launch_gemm(int precision, int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad,
-                const GemmEpi& e, hipStream_t st);
+                const GemmEpi& e, hipStream_t st, hipEvent_t stop = nullptr);
+// a kernel launch on st whose completion is the event `stop`; stop == nullptr: the plain launch
+#define D2S_LAUNCH_STOP(stop, kernel, grid, block, st, ...)                                                            \
+    do {                                                                                                               \
+        if (stop) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, nullptr, stop, 0, __VA_ARGS__);                    \
+        else hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);                                              \
+    } while (0)
 
 // would launch_gemm fold the up-sample a.ups describes into this convolution's halo loader? (engine: skip the bilinear launch)
 bool conv3_upsample_ok(int precision, int tile, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
@@ -115,7 +125,8 @@ void launch_conv3_halo2(const GemmPlan& p, const GemmA& a, const void* W, int M,
 // 256 x 256 ping-pong kernel (gemm_pp.hip): batched plain linears
 bool pp_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
 int plan_gemm_pp(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);
-int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st);
+int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st,
+                   hipEvent_t stop = nullptr);
 // streaming kernel for the thin linears of the DPT neck (gemm_sk.hip: K <= 256, W tile resident in LDS, A streamed)
 bool sk_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
 void plan_gemm_sk(const GemmA& a, int M, int N, int K, GemmPlan& p);

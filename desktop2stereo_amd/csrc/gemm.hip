@@ -885,8 +885,10 @@ bool conv3_upsample_ok(int precision, int tile, const GemmA& a, int M, int N, in
 
 // the planned gemm_glds_kernel / conv3_halo_kernel instantiation for operand type T (and the split-K reduce)
 template <typename T>
-static void launch_glds(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
+static void launch_glds(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st,
+                        hipEvent_t stop) {
     const dim3 grid(p.grid, p.gridy), block(p.block);
+    const hipEvent_t stop1 = p.grid2 ? nullptr : stop;      // (split-K: the reduce is the launch's last kernel)
     if (p.family == GEMM_HALO) {
         if constexpr ((type_bit<T>() & (TY_BF16 | TY_F32)) != 0) switch (p.inst) {
 #define X(ID, ...) case ID: hipLaunchKernelGGL((conv3_halo_kernel<T, __VA_ARGS__>), grid, block, 0, st, a, (const T*)W, M, N, K, Kpad, e, p.xn); break;
@@ -897,20 +899,21 @@ static void launch_glds(const GemmPlan& p, const GemmA& a, const void* W, int M,
     }
     switch (p.inst) {
 #define X(ID, TY, ...) case ID: if constexpr (((TY) & type_bit<T>()) != 0) \
-        hipLaunchKernelGGL((gemm_glds_kernel<T, __VA_ARGS__>), grid, block, 0, st, (const T*)W, a.ptr, a.lda, M, N, K, Kpad, p.xn, a, e); break;
+        D2S_LAUNCH_STOP(stop1, (gemm_glds_kernel<T, __VA_ARGS__>), grid, block, st, (const T*)W, a.ptr, a.lda, M, N, K, Kpad, p.xn, a, e); break;
         GLDS_INSTANCES(X)
 #undef X
     }
-    if (p.grid2) hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(p.grid2), dim3(256), 0, st, e, M, N);
+    if (p.grid2) D2S_LAUNCH_STOP(stop, (splitk_reduce_kernel<T>), dim3(p.grid2), dim3(256), st, e, M, N);
 }
 
 static void note_kernel(const GemmPlan& p) { kernel_note() = KernelNote{p.name, p.tile, p.ksplit, p.tail}; }
 
 int launch_gemm(int precision, int tile, const GemmA& a, const void* W, int M, int N, int K, int Kpad,
-                const GemmEpi& e, hipStream_t st) {
+                const GemmEpi& e, hipStream_t st, hipEvent_t stop) {
     GemmPlan p;
     if (const int rc = plan_gemm(precision, tile, a, M, N, K, Kpad, e, p)) { set_error(p.error); return rc; }
     note_kernel(p);
+    const bool in_launch = p.family == GEMM_GLDS || p.family == GEMM_PP;     // the families that take `stop` with their dispatch
     if (e.stats_slots && p.stats_slots >= 0) *e.stats_slots = p.stats_slots;
     GemmA a1 = a;
     a1.buf = p.buf;
@@ -919,14 +922,17 @@ int launch_gemm(int precision, int tile, const GemmA& a, const void* W, int M, i
     switch (p.family) {
         case GEMM_CONV3: launch_conv3_halo2(p, a1, W, M, N, Kpad, e1, st); break;
         case GEMM_SK: launch_gemm_sk(p, a1, W, M, N, Kpad, e1, st); break;
-        case GEMM_PP: if (const int rc = launch_gemm_pp(p, precision, a1, W, M, N, K, Kpad, e1, st)) return rc; break;
-        default:
-            if (precision == D2S_PREC_BF16) launch_glds<bf16_t>(p, a1, W, M, N, K, Kpad, e1, st);
-            else if (precision == D2S_PREC_FP8_OPERANDS) launch_glds<fp8_t>(p, a1, W, M, N, K, Kpad, e1, st);
-            else if (precision == D2S_PREC_BF16X3) launch_glds<bx3_t>(p, a1, W, M, N, K, Kpad, e1, st);
-            else launch_glds<float>(p, a1, W, M, N, K, Kpad, e1, st);
+        case GEMM_PP: if (const int rc = launch_gemm_pp(p, precision, a1, W, M, N, K, Kpad, e1, st, stop)) return rc; break;
+        default: {
+            const hipEvent_t ev = in_launch ? stop : nullptr;                  // (GEMM_HALO shares this launcher: recorded below)
+            if (precision == D2S_PREC_BF16) launch_glds<bf16_t>(p, a1, W, M, N, K, Kpad, e1, st, ev);
+            else if (precision == D2S_PREC_FP8_OPERANDS) launch_glds<fp8_t>(p, a1, W, M, N, K, Kpad, e1, st, ev);
+            else if (precision == D2S_PREC_BF16X3) launch_glds<bx3_t>(p, a1, W, M, N, K, Kpad, e1, st, ev);
+            else launch_glds<float>(p, a1, W, M, N, K, Kpad, e1, st, ev);
+        }
     }
     D2S_CHECK_LAUNCH();
+    if (stop && !in_launch) D2S_HIP(hipEventRecord(stop, st));
     return D2S_OK;
 }
 

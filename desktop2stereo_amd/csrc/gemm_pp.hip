@@ -1037,13 +1037,15 @@ int plan_gemm_pp(int precision, const GemmA& a, int M, int N, int K, int Kpad, c
     return D2S_OK;
 }
 
-int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st) {
+int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void* W, int M, int N, int K, int Kpad, const GemmEpi& e, hipStream_t st,
+                   hipEvent_t stop) {
     GemmEpi e1 = e;
+    const hipEvent_t stop1 = p.grid2 ? nullptr : stop;      // (two-launch tail: the reduce is the launch's last kernel)
     if (!e1.bias) e1.bias = pp_const_vec(false);
     if (!e1.scale) e1.scale = pp_const_vec(true);
     if (!e1.deq) e1.deq = pp_const_vec(true);
     if (!e1.bias || !e1.scale || !e1.deq) { set_error("launch_gemm_pp: constant vectors"); return D2S_E_HIP; }
-#define PP_LAUNCH(T_, KIND_) hipLaunchKernelGGL((gemm_pp_kernel<T_, KIND_>), dim3(p.grid), dim3(p.block), 0, st, (const T_*)a.ptr, a.lda, (const T_*)W, M, N, K, Kpad, e1, p.lxn, p.skew_us, p.tw, p.ksplit, p.kps, p.ink)
+#define PP_LAUNCH(T_, KIND_) D2S_LAUNCH_STOP(stop1, (gemm_pp_kernel<T_, KIND_>), dim3(p.grid), dim3(p.block), st, (const T_*)a.ptr, a.lda, (const T_*)W, M, N, K, Kpad, e1, p.lxn, p.skew_us, p.tw, p.ksplit, p.kps, p.ink)
     const int kind = p.inst;
     if (precision == D2S_PREC_BF16) {
         if (kind == PP_K_F32) PP_LAUNCH(bf16_t, PP_K_F32); else if (kind == PP_K_QKV) PP_LAUNCH(bf16_t, PP_K_QKV);
@@ -1057,8 +1059,8 @@ int launch_gemm_pp(const GemmPlan& p, int precision, const GemmA& a, const void*
 #undef PP_LAUNCH
     D2S_CHECK_LAUNCH();
     if (p.grid2) {
-        if (precision == D2S_PREC_BF16) hipLaunchKernelGGL((pp_tail_reduce_kernel<bf16_t>), dim3(p.grid2), dim3(256), 0, st, e, M, N, p.tw, p.ksplit, p.lxn);
-        else hipLaunchKernelGGL((pp_tail_reduce_kernel<fp8_t>), dim3(p.grid2), dim3(256), 0, st, e, M, N, p.tw, p.ksplit, p.lxn);
+        if (precision == D2S_PREC_BF16) D2S_LAUNCH_STOP(stop, (pp_tail_reduce_kernel<bf16_t>), dim3(p.grid2), dim3(256), st, e, M, N, p.tw, p.ksplit, p.lxn);
+        else D2S_LAUNCH_STOP(stop, (pp_tail_reduce_kernel<fp8_t>), dim3(p.grid2), dim3(256), st, e, M, N, p.tw, p.ksplit, p.lxn);
     }
     return D2S_OK;
 }

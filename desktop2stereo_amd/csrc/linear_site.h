@@ -277,11 +277,12 @@ static inline int linear_args(const DevLinear& L, GemmEpi& ep, float* ws, size_t
     if (ep.map == MAP_ROWS) { ep.part = ws; ep.part_elems = ws_elems; }
     return L.K % (L.prec == D2S_PREC_BF16 ? 8 : 4) ? L.Kpad : L.K;      // (bf16 activations: 8 per chunk; fp32, also under bf16x3 weights: 4)
 }
-// THE launch of a packed linear, [M, K] x W^T through ep, in the record's GEMM precision; tile: 0, or a probe's override
-static inline int launch_linear(const DevLinear& L, const GemmA& a, int M, GemmEpi ep, float* ws, size_t ws_elems, int tile, hipStream_t st) {
+// THE launch of a packed linear, [M, K] x W^T through ep, in the record's GEMM precision; tile: 0, or a probe's override; stop: launch_gemm's
+static inline int launch_linear(const DevLinear& L, const GemmA& a, int M, GemmEpi ep, float* ws, size_t ws_elems, int tile, hipStream_t st,
+                                hipEvent_t stop = nullptr) {
     D2S_REQUIRE(L.w, "launch_linear: this form of the linear was not built for the engine's precision");
     const int Kl = linear_args(L, ep, ws, ws_elems);
-    return launch_gemm(L.prec, tile, a, L.w, M, L.N, Kl, L.Kpad, ep, st);
+    return launch_gemm(L.prec, tile, a, L.w, M, L.N, Kl, L.Kpad, ep, st, stop);
 }
 // ... and what launch_gemm would run for it (plan_gemm): host only.  L may be a shape record (linear_shape) -- plan_gemm reads the
 // pointers of a launch for presence only (gemm.h)
