@@ -131,6 +131,17 @@ class PostPlanResult(C.Structure):
 POST_FORM = {0: "fused", 1: "tile", 2: "rows"}      # D2S_POST_FORM_*
 
 
+class XrPlanResult(C.Structure):
+    """d2s_xr_plan_result (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("rows_per_eye", C.c_int32), ("setup_launches", C.c_int32),
+                ("grid", C.c_uint32 * 3), ("lds_dynamic_bytes", C.c_uint32), ("lds_static_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("workspace_bytes", C.c_uint64), ("out_elems", C.c_uint64), ("offsets", C.c_uint64 * 2)]
+
+
+XR_ENTRY = {"eyes": 0, "glow": 1, "glow_curved": 2}      # D2S_XR_ENTRY_*
+XR_KIND = {0: "plain", 1: "glow", 2: "glow_curved"}      # D2S_XR_KIND_*
+
+
 class ForwardPlanResult(C.Structure):
     """d2s_forward_plan_result (include/d2s.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("f8", C.c_int32), ("f8a", C.c_int32), ("x3", C.c_int32), ("lnf", C.c_int32),
@@ -225,6 +236,8 @@ SYMBOLS = {
     "d2s_dibr_xr_glow_curved_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
     "d2s_dibr_xr_eyes_glow_curved": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrGlow), _P, _P]),
+    "d2s_dibr_xr_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                   C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, C.POINTER(XrGlow), C.POINTER(XrPlanResult)]),
     "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,

@@ -324,8 +324,6 @@ dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ 
 // share few waves and the taps of a wave stay within a few texture rows whatever the minification.  Every facet of the eye's table
 // (dibr_xr.h; block-uniform addresses) is tested: ~14 float operations each, at most 48.  Covered: the facet's homography gives the
 // interpolated vertex uv, and the pixel function runs on (u, 1 - v) as the shader's screen_flipped_uv; uncovered: the clear colour.
-struct XrEyeDev { int w, h, eye, nf; long out_off; };      // out_off: the eye image's first element in out; its table: eye index * 48
-struct XrEyes { XrEyeDev e[2]; int n; float clear[4]; };
 // (set-up: up to 24 facets of one eye's table travel in the arguments and are copied to the workspace, one float per thread)
 __global__ void __launch_bounds__(256) dibr_xr_table_kernel(XrFacetChunk c, float* __restrict__ dst, int n_floats) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -411,95 +409,127 @@ __device__ __forceinline__ void glow_blend(float c[4], const float src[4]) {    
     for (int i = 0; i < 4; ++i) c[i] = src[i] + c[i] * k;
 }
 
-// GLOW = false: d2s_dibr_xr_eyes.  GLOW = true (flat screen, one facet): _render_eye's order (effects.py:1050-1145) in one pass over
-// the pixel, in float -- clear; the outer band blended over it where the screen does not cover the pixel (where it does the screen,
-// drawn with blending off, overwrites the band); the screen; mode 1: the inner band blended over the screen.  The glow quad is the
-// screen's plane: facet 0's homography without the 0..1 bound gives its coordinates; it is drawn where clip w > 0 and NDC z is in
-// [-1, 1].  (The quad ends at screen + range; the glow reaches 0 there or sooner -- edge_t = 1 -- so the quad's own bound is not
-// tested.)  A block stages the chain's coarse levels in LDS once unless its whole tile is plain screen or undrawn.
-template <int OUT_FMT, class D, bool GLOW>
-__device__ __forceinline__ void dibr_xr_body(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
-                                             const XrFacet* __restrict__ tab_all, const DibrGeomProj& g, const XrEyes& ex, const XrGlowDev& G,
-                                             const uint8_t* __restrict__ levels, float* __restrict__ lds) {
-    const int ei = blockIdx.z % ex.n, b = blockIdx.z / ex.n;
-    const XrEyeDev e = ex.e[ei];
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    const bool inside = x < e.w && y < e.h;
-    if (!GLOW && !inside) return;
-    const XrFacet* __restrict__ tab = tab_all + ei * XR_MAX_FACETS;
-    const float xc = ((float)x + 0.5f) - 0.5f * (float)e.w, yc = ((float)y + 0.5f) - 0.5f * (float)e.h;      // exact: multiples of 0.5 below 2^13
-    int best = -1;
-    float bz = 1.0f, ba = 0.f, bb = 0.f, bw = 1.f;      // the depth buffer is cleared to 1: LESS fails at and beyond the far plane
-    for (int f = 0; f < e.nf; ++f) {
-        const XrFacet& F = tab[f];
-        const float na = F.ha[0] * xc + F.ha[1] * yc + F.ha[2], nb = F.hb[0] * xc + F.hb[1] * yc + F.hb[2];
-        const float nw = F.hw[0] * xc + F.hw[1] * yc + F.hw[2];
-        const float ne = F.he[0] * xc + F.he[1] * yc + F.he[2];      // the upper a-edge: the next facet's na, negated (dibr_xr.h)
-        if (na >= 0.f && ne >= 0.f && nb >= 0.f && nb <= nw && nw > 0.f) {
-            const float z = F.hz[0] * xc + F.hz[1] * yc + F.hz[2];
-            // (GL clips at the near plane, NDC z = -1)
-            if (z >= -1.0f && z < bz) { bz = z; best = f; ba = na; bb = nb; bw = nw; }      // GL_LESS: a tie keeps the lower facet index
-        }
+// ---- what the three eye-view kernels share.  A table row is 24 floats (XrFacet's fields in order: ha 0, hb 3, hw 6, hz 9, he 12, the uv
+// affine 15 .. 20), read through a const float* so that one function serves a global XrFacet and an LDS row of stride XR_LDS_ROW.
+// The block prologue.  It NEVER returns a thread early: in the glow kernels a thread outside its eye image (the other eye is larger,
+// or a side is no multiple of 16) must still reach every barrier.  dibr_xr_kernel, which has none, returns on !inside itself.
+struct XrPix { int ei, b; XrEyeDev e; int x, y; bool inside; float xc, yc; };
+__device__ __forceinline__ XrPix xr_pix(const XrEyes& ex) {
+    XrPix p;
+    p.ei = blockIdx.z % ex.n; p.b = blockIdx.z / ex.n;
+    p.e = ex.e[p.ei];
+    p.x = blockIdx.x * 16 + (threadIdx.x & 15); p.y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    p.inside = p.x < p.e.w && p.y < p.e.h;
+    p.xc = ((float)p.x + 0.5f) - 0.5f * (float)p.e.w; p.yc = ((float)p.y + 0.5f) - 0.5f * (float)p.e.h;      // exact: multiples of 0.5 below 2^13
+    return p;
+}
+struct XrPt { float na, nb, nw, z; };
+__device__ __forceinline__ XrPt xr_row_at(const float* __restrict__ r, float xc, float yc) {
+    XrPt p;
+    p.na = r[0] * xc + r[1] * yc + r[2]; p.nb = r[3] * xc + r[4] * yc + r[5];
+    p.nw = r[6] * xc + r[7] * yc + r[8]; p.z = r[9] * xc + r[10] * yc + r[11];
+    return p;
+}
+// The cover rule, the one copy: both sides of a seam evaluate its edge function here, with these operations (no contraction in this
+// file), which is what makes the strip watertight.  false: the pixel lies outside facet f's two a-edges (p.z is then not formed).
+struct XrHit { int best; float bz, ba, bb, bw; };      // bz starts at 1, the cleared depth buffer: LESS fails at and beyond the far plane
+__device__ __forceinline__ bool xr_cover(const float* __restrict__ r, int f, float xc, float yc, XrHit& h, XrPt& p) {
+    p.na = r[0] * xc + r[1] * yc + r[2]; p.nb = r[3] * xc + r[4] * yc + r[5];
+    p.nw = r[6] * xc + r[7] * yc + r[8];
+    const float ne = r[12] * xc + r[13] * yc + r[14];      // the upper a-edge: the next facet's na, negated (dibr_xr.h)
+    if (!(p.na >= 0.f && ne >= 0.f)) return false;
+    p.z = r[9] * xc + r[10] * yc + r[11];
+    // (GL clips at the near plane, NDC z = -1)  GL_LESS: a tie keeps the lower facet index
+    if (p.nb >= 0.f && p.nb <= p.nw && p.nw > 0.f && p.z >= -1.0f && p.z < h.bz) { h.bz = p.z; h.best = f; h.ba = p.na; h.bb = p.nb; h.bw = p.nw; }
+    return true;
+}
+// the covering facet's interpolated vertex uv = the pixel's point in the screen's coordinates
+__device__ __forceinline__ void xr_hit_uv(const float* __restrict__ r, const XrHit& h, float& sa, float& sb) {
+    const float a = h.ba / h.bw, bq = h.bb / h.bw;
+    sa = r[15] + a * r[16] + bq * r[17]; sb = r[18] + a * r[19] + bq * r[20];
+}
+// every facet of the eye's table, from global memory (block-uniform addresses)
+__device__ __forceinline__ XrHit xr_search_all(const float* __restrict__ tab, int nf, float xc, float yc) {
+    XrHit h = {-1, 1.0f, 0.f, 0.f, 1.f};
+    XrPt p;
+    for (int f = 0; f < nf; ++f) xr_cover(tab + f * XR_ROW_FLOATS, f, xc, yc, h, p);
+    return h;
+}
+// A block stages the chain's coarse levels in LDS once, unless none of its pixels draws a band.  Every thread of the block calls this.
+__device__ __forceinline__ void xr_stage_chain(bool need, const uint8_t* __restrict__ levels, int b, const XrGlowDev& G, float* __restrict__ lds) {
+    if (__syncthreads_or(need)) {
+        const uint8_t* __restrict__ src = levels + (long)b * G.chain_total + G.chain_off;
+        for (int i = threadIdx.x; i < G.n_tex * 3; i += 256) lds[i] = (float)src[i];
+        __syncthreads();
     }
-    bool plane = false;                                  // GLOW: the glow quad is drawn at this pixel
-    float ga = 0.f, gb = 0.f;                            // and its point in the screen's coordinates
-    if constexpr (GLOW) {
-        const XrFacet& F = tab[0];
-        const float na = F.ha[0] * xc + F.ha[1] * yc + F.ha[2], nb = F.hb[0] * xc + F.hb[1] * yc + F.hb[2];
-        const float nw = F.hw[0] * xc + F.hw[1] * yc + F.hw[2], z = F.hz[0] * xc + F.hz[1] * yc + F.hz[2];
-        plane = nw > 0.f && z >= -1.0f && z <= 1.0f;
-        ga = na / nw; gb = nb / nw;
-        float cx, cy;
-        const bool need = inside && plane && (best < 0 || (G.mode == 1 && glow_sd(G, ga, gb, cx, cy) >= -G.inner));
-        if (__syncthreads_or(need)) {
-            const uint8_t* __restrict__ src = levels + (long)b * G.chain_total + G.chain_off;
-            for (int i = threadIdx.x; i < G.n_tex * 3; i += 256) lds[i] = (float)src[i];
-            __syncthreads();
-        }
-        if (!inside) return;
-    }
+}
+// The tail of a pixel inside its eye image, _render_eye's order (effects.py:1050-1145) in float: clear; the outer band blended over
+// it where no facet covers the pixel (where one does the screen, drawn with blending off, overwrites the band); the screen at
+// (sa, sb); the inner band's draws blended over the screen, in draw order; alpha_mode; the store.  plane: the outer band's piece is
+// drawn at this pixel, (ga, gb) its point in the screen's coordinates.  N = 0: no glow.
+struct XrDraw { bool on; float a, b; };
+template <int OUT_FMT, class D, int N>
+__device__ __forceinline__ void xr_tail(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+                                        const DibrGeomProj& g, const XrEyes& ex, const XrGlowDev& G, const float* __restrict__ lds,
+                                        const XrPix& px, bool covered, float sa, float sb, bool plane, float ga, float gb, const XrDraw* draws) {
     const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
-    const long o = e.out_off + (((long)b * e.h + y) * e.w + x) * nch;
-    float c[4];
-    if (best < 0) {
+    const long o = px.e.out_off + (((long)px.b * px.e.h + px.y) * px.e.w + px.x) * nch;
+    float c[4], src[4];
+    if (!covered) {
         c[0] = ex.clear[0] * 255.0f; c[1] = ex.clear[1] * 255.0f; c[2] = ex.clear[2] * 255.0f; c[3] = ex.clear[3];
-        if constexpr (GLOW) {
-            float src[4];
-            if (plane && glow_frag(lds, G, g, ga, gb, false, src)) {
-                glow_blend(c, src);
-                if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
-            }
+        if (N > 0 && plane && glow_frag(lds, G, g, ga, gb, false, src)) {
+            glow_blend(c, src);
+            if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
         }
         dibr_store<OUT_FMT>(out_all, o, nch, c);
         return;
     }
-    const XrFacet& F = tab[best];
-    const float a = ba / bw, bq = bb / bw;
-    const float quv[2] = {F.u0 + a * F.ua + bq * F.ub, 1.0f - (F.v0 + a * F.va + bq * F.vb)};
+    const float quv[2] = {sa, 1.0f - sb};
     GenSmp<D> smp;
-    smp.rgb = rgb_all + (long)b * g.H * g.W * 3; smp.dep = D::make(dep_all, b, g); smp.H = g.H; smp.W = g.W;
-    if constexpr (GLOW) {
-        dibr_pixel<false, false, true, true>(smp, g, 0, 0, e.eye, c, nullptr, quv);      // the framebuffer's own (rgb, a): alpha_mode acts after the inner band
-        float src[4];
-        if (G.mode == 1 && plane && glow_frag(lds, G, g, ga, gb, true, src)) glow_blend(c, src);
-        if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
-    } else {
-        dibr_pixel(smp, g, 0, 0, e.eye, c, nullptr, quv);
-    }
+    smp.rgb = rgb_all + (long)px.b * g.H * g.W * 3; smp.dep = D::make(dep_all, px.b, g); smp.H = g.H; smp.W = g.W;
+    dibr_pixel<false, false, true, true>(smp, g, 0, 0, px.e.eye, c, nullptr, quv);      // the framebuffer's own (rgb, a): alpha_mode acts after the inner band
+    // (written out, not a loop: unrolled late, the curved kernel's FullDep form took 74 VGPRs for 72 and lost a wave per SIMD)
+    if (N > 0 && draws[0].on && glow_frag(lds, G, g, draws[0].a, draws[0].b, true, src)) glow_blend(c, src);
+    if (N > 1 && draws[1].on && glow_frag(lds, G, g, draws[1].a, draws[1].b, true, src)) glow_blend(c, src);
+    if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
     dibr_store<OUT_FMT>(out_all, o, nch, c);
 }
+
+// d2s_dibr_xr_eyes: every facet of the eye's table is tested.  No barrier in this kernel: a thread outside its image leaves at once.
 template <int OUT_FMT, class D>
 __global__ void __launch_bounds__(256)
 dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
                const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex) {
-    dibr_xr_body<OUT_FMT, D, false>(rgb_all, dep_all, out_all, tab_all, g, ex, XrGlowDev{}, nullptr, nullptr);
+    const XrPix px = xr_pix(ex);
+    if (!px.inside) return;
+    const float* __restrict__ tab = (const float*)(tab_all + px.ei * XR_MAX_FACETS);
+    const XrHit h = xr_search_all(tab, px.e.nf, px.xc, px.yc);
+    float sa = 0.f, sb = 0.f;
+    if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
+    xr_tail<OUT_FMT, D, 0>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f, nullptr);
 }
+// d2s_dibr_xr_eyes_glow (flat screen, one facet).  The glow quad is the screen's plane: facet 0's homography without the 0..1 bound
+// gives its coordinates; it is drawn where clip w > 0 and NDC z is in [-1, 1].  (The quad ends at screen + range; the glow reaches 0
+// there or sooner -- edge_t = 1 -- so the quad's own bound is not tested.)  The chain is staged unless the block's whole tile is plain
+// screen or undrawn.  Barriers: xr_stage_chain's, reached by every thread; the threads outside the image leave after it.
 template <int OUT_FMT, class D>
 __global__ void __launch_bounds__(256)
 dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
                     const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrGlowDev G, const uint8_t* __restrict__ levels) {
     extern __shared__ float xr_glow_lds[];               // [n_tex][3]
-    dibr_xr_body<OUT_FMT, D, true>(rgb_all, dep_all, out_all, tab_all, g, ex, G, levels, xr_glow_lds);
+    const XrPix px = xr_pix(ex);
+    const float* __restrict__ tab = (const float*)(tab_all + px.ei * XR_MAX_FACETS);
+    const XrHit h = xr_search_all(tab, px.e.nf, px.xc, px.yc);
+    const XrPt p = xr_row_at(tab, px.xc, px.yc);
+    const bool plane = p.nw > 0.f && p.z >= -1.0f && p.z <= 1.0f;
+    const float ga = p.na / p.nw, gb = p.nb / p.nw;
+    float cx, cy;
+    xr_stage_chain(px.inside && plane && (h.best < 0 || (G.mode == 1 && glow_sd(G, ga, gb, cx, cy) >= -G.inner)), levels, px.b, G, xr_glow_lds);
+    if (!px.inside) return;
+    float sa = 0.f, sb = 0.f;
+    if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
+    const XrDraw inner = {G.mode == 1 && plane, ga, gb};
+    xr_tail<OUT_FMT, D, 1>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, &inner);
 }
 
 // d2s_dibr_xr_eyes_glow_curved: the curved screen with its glow (_render_curved_glow, xr_viewer/effects.py:408-474, in _render_eye's
@@ -508,17 +538,10 @@ dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict
 // neighbouring rows read different banks, lanes on one row broadcast).  A pixel finds its piece from the seams' signs: the two arc
 // ends say whether its ray passes the arc (then a binary search over the 47 interior seams, 6 steps), a tangent piece, or -- a ray
 // more than a half turn from one end, both end seams "beyond" -- either tangent piece.  The facet found and its two neighbours then
-// go through dibr_xr_body's rule with its arithmetic, so a screen pixel has the facet, a / w and b / w of dibr_xr_kernel; a pixel no
-// facet covers takes the band on the piece the seams gave it.  Homographies per pixel: at most 3 facets + 2 others, whatever the
-// strip's 48.
-constexpr int XR_LDS_ROW = XR_ROW_FLOATS + 1;
-struct XrPt { float na, nb, nw, z; };
-__device__ __forceinline__ XrPt xr_row_at(const float* __restrict__ r, float xc, float yc) {
-    XrPt p;
-    p.na = r[0] * xc + r[1] * yc + r[2]; p.nb = r[3] * xc + r[4] * yc + r[5];
-    p.nw = r[6] * xc + r[7] * yc + r[8]; p.z = r[9] * xc + r[10] * yc + r[11];
-    return p;
-}
+// go through xr_cover, so a screen pixel has the facet, a / w and b / w of dibr_xr_kernel; a pixel no facet covers takes the band on
+// the piece the seams gave it.  Homographies per pixel: at most 3 facets + 2 others, whatever the strip's 48.
+// Barriers: the one after the rows' staging and xr_stage_chain's, each reached by every thread; the threads outside the image leave
+// after the second.
 template <int OUT_FMT, class D>
 __global__ void __launch_bounds__(256)
 dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
@@ -527,13 +550,9 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
     extern __shared__ float xr_glow_lds[];               // [n_tex][3]
     __shared__ float rows[XR_PIECES * XR_LDS_ROW];
     __shared__ float seams[XR_SEAMS * 3];
-    float* __restrict__ lds = xr_glow_lds;
-    const int ei = blockIdx.z % ex.n, b = blockIdx.z / ex.n;
-    const XrEyeDev e = ex.e[ei];
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    const bool inside = x < e.w && y < e.h;
+    const XrPix px = xr_pix(ex);
     {
-        const float* __restrict__ src = (const float*)(tab_all + ei * XR_PIECES);
+        const float* __restrict__ src = (const float*)(tab_all + px.ei * XR_PIECES);
         for (int i = threadIdx.x; i < XR_PIECES * XR_ROW_FLOATS; i += 256) rows[(i / XR_ROW_FLOATS) * XR_LDS_ROW + i % XR_ROW_FLOATS] = src[i];
         if (threadIdx.x < XR_SEAMS * 3) {
             const int s = threadIdx.x / 3, k = threadIdx.x % 3;
@@ -541,7 +560,7 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
         }
         __syncthreads();
     }
-    const float xc = ((float)x + 0.5f) - 0.5f * (float)e.w, yc = ((float)y + 0.5f) - 0.5f * (float)e.h;
+    const float xc = px.xc, yc = px.yc;
     auto seam = [&](int s) { return seams[s * 3] * xc + seams[s * 3 + 1] * yc + seams[s * 3 + 2]; };
     // f: the facet the seams give (0 .. 47), -1 / 48: the tangent piece at the lower / upper end, -2: either tangent piece
     int f;
@@ -556,8 +575,7 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
             f = lo;
         } else f = lo_in ? XR_MAX_FACETS : (hi_in ? -1 : -2);
     }
-    int best = -1;
-    float bz = 1.0f, ba = 0.f, bb = 0.f, bw = 1.f;
+    XrHit h = {-1, 1.0f, 0.f, 0.f, 1.f};
     bool plane = false, band_set = false;                // the band's piece is drawn at this pixel; a facet has claimed the band
     float pz = 0.f, ga = 0.f, gb = 0.f;                  // its depth and its point in the screen's coordinates
     auto band = [&](const float* __restrict__ r, const XrPt& p) {
@@ -569,22 +587,16 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
     };
     for (int c = max(f - 1, 0); c <= min(f + 1, XR_MAX_FACETS - 1) && f >= -1; ++c) {
         const float* __restrict__ r = rows + c * XR_LDS_ROW;
-        const XrPt p = xr_row_at(r, xc, yc);
-        const float ne = r[12] * xc + r[13] * yc + r[14];
-        if (p.na >= 0.f && ne >= 0.f) {
-            if (p.nb >= 0.f && p.nb <= p.nw && p.nw > 0.f && p.z >= -1.0f && p.z < bz) { bz = p.z; best = c; ba = p.na; bb = p.nb; bw = p.nw; }
-            if (!band_set && f >= 0 && f < XR_MAX_FACETS) { band_set = true; band(r, p); }      // (the lowest facet between its seams)
-        }
+        XrPt p;
+        if (xr_cover(r, c, xc, yc, h, p) && !band_set && f >= 0 && f < XR_MAX_FACETS) { band_set = true; band(r, p); }      // (the lowest facet between its seams)
     }
     if (f < 0) { const float* r = rows + XR_T0 * XR_LDS_ROW; band(r, xr_row_at(r, xc, yc)); }
     if (f == XR_MAX_FACETS || f == -2) { const float* r = rows + XR_T1 * XR_LDS_ROW; band(r, xr_row_at(r, xc, yc)); }
     // the screen pixel: its facet's uv, which is also its point in the screen's coordinates; mode 1: the inner band's two draws
     bool fband = false, cband = false;
     float sa = 0.f, sb = 0.f, ca = 0.f, cb = 0.f;
-    if (best >= 0) {
-        const float* __restrict__ r = rows + best * XR_LDS_ROW;
-        const float a = ba / bw, bq = bb / bw;
-        sa = r[15] + a * r[16] + bq * r[17]; sb = r[18] + a * r[19] + bq * r[20];
+    if (h.best >= 0) {
+        xr_hit_uv(rows + h.best * XR_LDS_ROW, h, sa, sb);
         if (G.mode == 1) {
             const float al = Q.vertical ? sb : sa, ac = Q.vertical ? sa : sb;
             const bool edge_ac = ac <= Q.e_ac || ac >= 1.0f - Q.e_ac;
@@ -599,51 +611,18 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
             }
         }
     }
-    const bool need = inside && (best < 0 ? plane : (fband || cband));
-    if (__syncthreads_or(need)) {
-        const uint8_t* __restrict__ src = levels + (long)b * G.chain_total + G.chain_off;
-        for (int i = threadIdx.x; i < G.n_tex * 3; i += 256) lds[i] = (float)src[i];
-        __syncthreads();
-    }
-    if (!inside) return;
-    const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
-    const long o = e.out_off + (((long)b * e.h + y) * e.w + x) * nch;
-    float c[4], src[4];
-    if (best < 0) {
-        c[0] = ex.clear[0] * 255.0f; c[1] = ex.clear[1] * 255.0f; c[2] = ex.clear[2] * 255.0f; c[3] = ex.clear[3];
-        if (plane && glow_frag(lds, G, g, ga, gb, false, src)) {
-            glow_blend(c, src);
-            if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
-        }
-        dibr_store<OUT_FMT>(out_all, o, nch, c);
-        return;
-    }
-    const float quv[2] = {sa, 1.0f - sb};
-    GenSmp<D> smp;
-    smp.rgb = rgb_all + (long)b * g.H * g.W * 3; smp.dep = D::make(dep_all, b, g); smp.H = g.H; smp.W = g.W;
-    dibr_pixel<false, false, true, true>(smp, g, 0, 0, e.eye, c, nullptr, quv);
+    xr_stage_chain(px.inside && (h.best < 0 ? plane : (fband || cband)), levels, px.b, G, xr_glow_lds);
+    if (!px.inside) return;
     // the mesh's draw order (_build_curved_glow_band_verts:401-404): the u-long bands, then the v-long ones
-    const bool cf = Q.vertical != 0;                     // the chord piece's draw comes first
-    if ((cf ? cband : fband) && glow_frag(lds, G, g, cf ? ca : sa, cf ? cb : sb, true, src)) glow_blend(c, src);
-    if ((cf ? fband : cband) && glow_frag(lds, G, g, cf ? sa : ca, cf ? sb : cb, true, src)) glow_blend(c, src);
-    if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
-    dibr_store<OUT_FMT>(out_all, o, nch, c);
+    const XrDraw on_facet = {fband, sa, sb}, on_chord = {cband, ca, cb};
+    const XrDraw draws[2] = {Q.vertical ? on_chord : on_facet, Q.vertical ? on_facet : on_chord};
+    xr_tail<OUT_FMT, D, 2>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, draws);
 }
 
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
 int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                        const double* crop, void* out, int out_fmt, void* stream, bool check_only);      // (d2s_view_pipeline_crop_streams)
-int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
-                const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
-                uint64_t workspace_bytes, void* stream, bool check_only);                              // (d2s_view_pipeline_xr_streams)
-int dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
-                     const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
-                     uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
-int dibr_xr_glow_curved_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                            const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
-                            void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                            bool check_only);                                                          // (d2s_view_pipeline_xr_glow_curved_streams)
 
 }  // namespace d2s
 
@@ -653,36 +632,6 @@ extern "C" int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* o
     D2S_REQUIRE(out_h && out_w && H > 0 && W > 0, "bad argument");
     int oh = 0, ow = 0;
     return dibr_eye_shape(H, W, display_mode, &oh, &ow, out_h, out_w);
-}
-
-// _movie_crop_pixel_bounds (xr_viewer/crop.py:165-173): Python's round() is half-to-even = nearbyint on doubles
-static void crop_pixel_bounds(int W, int H, const double crop[4], int b[4]) {
-    auto clampi = [](long v, long lo, long hi) { return (int)std::max(lo, std::min(v, hi)); };
-    b[0] = clampi((long)nearbyint(crop[0] * W), 0, std::max(0, W - 1));
-    b[1] = clampi((long)nearbyint(crop[1] * H), 0, std::max(0, H - 1));
-    b[2] = std::max(b[0] + 1, (int)std::min((long)nearbyint((crop[0] + crop[2]) * W), (long)W));
-    b[3] = std::max(b[1] + 1, (int)std::min((long)nearbyint((crop[1] + crop[3]) * H), (long)H));
-}
-static int crop_check(const double* crop) {
-    D2S_REQUIRE(crop, "null pointer (crop)");
-    for (int i = 0; i < 4; ++i) D2S_REQUIRE(std::isfinite(crop[i]), "crop must be finite");
-    const double e = 1e-6;
-    D2S_REQUIRE(crop[0] >= -e && crop[1] >= -e, "crop x, y must be >= 0");
-    D2S_REQUIRE(crop[2] > 0.0 && crop[3] > 0.0, "crop w, h must be > 0");
-    D2S_REQUIRE(crop[0] + crop[2] <= 1.0 + e && crop[1] + crop[3] <= 1.0 + e, "crop x + w, y + h must be <= 1");
-    return D2S_OK;
-}
-// the per-eye viewport of a cropped warp: the crop's pixel size, halved by the Half modes as d2s_dibr_shape halves the frame
-static int crop_eye_shape(int H, int W, const double* crop, int display_mode, int* oh, int* ow, int* out_h, int* out_w) {
-    D2S_REQUIRE(H > 1 && W > 1, "bad shape");
-    int rc = crop_check(crop);
-    if (rc) return rc;
-    int b[4];
-    crop_pixel_bounds(W, H, crop, b);
-    rc = dibr_eye_shape(b[3] - b[1], b[2] - b[0], display_mode, oh, ow, out_h, out_w);
-    if (rc) return rc;
-    D2S_REQUIRE(*oh >= 2 && *ow >= 2, "crop: the eye viewport must be at least 2 x 2 pixels");
-    return D2S_OK;
 }
 
 // d2s_dibr_warp (dh == H && dw == W: depth IS the texture, the FullDep kernels) and d2s_dibr_warp_depth (any other [dh, dw]: the
@@ -785,237 +734,105 @@ extern "C" int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh
     return dibr_warp_crop_any(rgb, depth, dh, dw, batch, H, W, p, crop, out, out_fmt, stream, false);
 }
 
-// The OpenXR eye views (xr_viewer/effects.py:1023-1137).  Every argument is checked, and both eyes' tables are formed, before any HIP call.
-static int xr_out_layout(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets, uint64_t* total) {
+// The OpenXR eye views (xr_viewer/effects.py:1023-1137; the curved screen's glow: effects.py:408-474).  xr_plan (dibr_xr.h) checks
+// every argument that is no device pointer and forms both eyes' tables; the launcher below looks at the pointers, then launches.
+extern "C" int d2s_dibr_xr_shape(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets, uint64_t* total) {
+    D2S_REQUIRE(offsets && total, "null pointer (offsets, total)");
     D2S_REQUIRE(eyes && n_eyes >= 1 && n_eyes <= 2, "bad eyes (n_eyes must be 1 or 2)");
     D2S_REQUIRE(batch > 0 && batch <= 65535, "bad batch (1 .. 65535)");
     D2S_REQUIRE(alpha_mode >= D2S_DIBR_ALPHA_WINDOW && alpha_mode <= D2S_DIBR_ALPHA_RGBA, "bad alpha_mode");
-    const uint64_t nch = alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
-    uint64_t at = 0;
     for (int i = 0; i < n_eyes; ++i) {
         D2S_REQUIRE(eyes[i].struct_size == sizeof(d2s_xr_eye), "d2s_xr_eye.struct_size must be sizeof(d2s_xr_eye) = 144");
         D2S_REQUIRE(eyes[i].width >= 2 && eyes[i].height >= 2 && eyes[i].width <= 8192 && eyes[i].height <= 8192, "eye image must be 2 .. 8192 on a side");
-        if (offsets) offsets[i] = at;
-        at += (uint64_t)batch * eyes[i].height * eyes[i].width * nch;
     }
-    if (total) *total = at;
+    xr_out_layout(eyes, n_eyes, batch, alpha_mode, offsets, total);
     return D2S_OK;
 }
 
-extern "C" int d2s_dibr_xr_shape(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets, uint64_t* total) {
-    D2S_REQUIRE(offsets && total, "null pointer (offsets, total)");
-    return xr_out_layout(eyes, n_eyes, batch, alpha_mode, offsets, total);
-}
-
-extern "C" int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes) {
+static int xr_workspace_query(int kind, int n_eyes, uint64_t* bytes) {
     D2S_REQUIRE(bytes, "null pointer (bytes)");
     D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
-    *bytes = (uint64_t)n_eyes * XR_MAX_FACETS * sizeof(XrFacet);
+    *bytes = (uint64_t)n_eyes * xr_table_rows(kind) * sizeof(XrFacet);
+    return D2S_OK;
+}
+extern "C" int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_PLAIN, n_eyes, bytes); }
+extern "C" int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_GLOW_CURVED, n_eyes, bytes); }
+
+extern "C" int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow,
+                                d2s_xr_plan_result* res) {
+    D2S_REQUIRE(res, "null pointer (res)");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
+    D2S_REQUIRE(entry >= D2S_XR_ENTRY_EYES && entry <= D2S_XR_ENTRY_GLOW_CURVED, "bad entry (D2S_XR_ENTRY_*)");
+    D2S_REQUIRE(entry != D2S_XR_ENTRY_EYES || !glow, "d2s_dibr_xr_eyes takes no glow: glow must be NULL with D2S_XR_ENTRY_EYES");
+    XrPlan pl;
+    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, pl);
+    if (rc) return rc;
+    *res = d2s_xr_plan_result{sizeof(d2s_xr_plan_result), pl.kind, pl.rows_per_eye, pl.setup_launches, {pl.grid[0], pl.grid[1], pl.grid[2]},
+                              pl.lds_dynamic, pl.lds_static, 0, pl.workspace_bytes, pl.total, {pl.offs[0], pl.offs[1]}};
     return D2S_OK;
 }
 
-int d2s::dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                     const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
-                     void* workspace, uint64_t workspace_bytes, void* stream, bool check_only) {
-    return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, nullptr,
-                            nullptr, stream, check_only);
-}
-
-// glow == nullptr or mode 0: d2s_dibr_xr_eyes, the same launches
-int d2s::dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                          const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
-                          void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                          bool check_only) {
-    D2S_REQUIRE(rgb && depth && p && out, "null pointer");
-    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
-    if (rc) return rc;
-    D2S_REQUIRE(!p->feather_enabled, "feather_enabled must be 0 (the OpenXR viewer never enables the feathering)");
-    if (crop) {                                            // what d2s_dibr_warp_crop refuses about a crop, its 2 x 2 pixel floor included
-        int a, b2, c2, d2;
-        rc = crop_eye_shape(H, W, crop, D2S_MODE_FULL_SBS, &a, &b2, &c2, &d2);
-        if (rc) return rc;
-    }
-    rc = xr_check(screen, eyes, n_eyes, batch, workspace, workspace_bytes);
-    if (rc) return rc;
-    rc = xr_glow_check(screen, glow, levels);
-    if (rc) return rc;
-    const bool glow_on = glow && glow->mode != 0;
-    D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
-    uint64_t offs[2] = {0, 0}, total = 0;
-    rc = xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, offs, &total);
-    if (rc) return rc;
-    XrSurface S;
-    xr_surface(screen, S);
-    for (int i = 0; i < n_eyes; ++i)
-        if (!(xr_min_w(S, eyes[i].vp) > 1e-6)) {
-            set_error("unsupported: a vertex of the screen has clip w <= 1e-6 (the screen crosses the eye plane)");
-            return D2S_E_UNSUPPORTED;
-        }
-    DibrGeomProj g;
-    dibr_fill_geom(g, p, H, W, dh, dw);
-    g.c = cosf((float)screen->roll); g.s = sinf((float)screen->roll);                 // u_roll = screen_roll (effects.py:1113, 1129)
-    g.feather = 0;
-    g.mode = 0; g.oh = g.ow = g.out_h = g.out_w = 0;
-    g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
-    g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
-    XrEyes ex = {};
-    ex.n = n_eyes;
-    for (int k = 0; k < 4; ++k) ex.clear[k] = screen->clear[k];
-    int mw = 0, mh = 0;
-    XrFacet facets[2][XR_MAX_FACETS];
-    for (int i = 0; i < n_eyes; ++i) {
-        ex.e[i] = XrEyeDev{eyes[i].width, eyes[i].height, eyes[i].eye, S.n, (long)offs[i]};
-        mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
-        xr_facets(S, eyes[i].vp, eyes[i].width, eyes[i].height, facets[i]);
-    }
+// The device pointers and the workspace, the rows' upload, the render launch.
+static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, void* out, int out_fmt, void* workspace, uint64_t workspace_bytes,
+                     const uint8_t* levels, void* stream, bool check_only) {
+    D2S_REQUIRE(workspace, "null pointer (workspace)");
+    D2S_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+    D2S_REQUIRE(workspace_bytes >= pl.workspace_bytes, (pl.kind == D2S_XR_KIND_GLOW_CURVED ? "workspace_bytes below d2s_dibr_xr_glow_curved_workspace"
+                                                                                           : "workspace_bytes below d2s_dibr_xr_workspace"));
+    D2S_REQUIRE(pl.kind == D2S_XR_KIND_PLAIN || levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
+    D2S_REQUIRE(rgb && depth && out, "null pointer");
     if (check_only) return D2S_OK;
-    XrFacet* tab = (XrFacet*)workspace;
-    for (int i = 0; i < n_eyes; ++i)
-        for (int f0 = 0; f0 < S.n; f0 += XR_CHUNK_FACETS) {                            // 1 launch per eye (flat), 2 (curved)
-            const int nf = std::min(XR_CHUNK_FACETS, S.n - f0), n_floats = nf * (int)(sizeof(XrFacet) / sizeof(float));
+    hipStream_t st = (hipStream_t)stream;
+    const XrFacet* tab = (const XrFacet*)workspace;
+    const int stride = xr_table_rows(pl.kind);
+    for (int i = 0; i < pl.ex.n; ++i)
+        for (int f0 = 0; f0 < pl.rows_per_eye; f0 += XR_CHUNK_FACETS) {
+            const int nf = std::min(XR_CHUNK_FACETS, pl.rows_per_eye - f0), n_floats = nf * XR_ROW_FLOATS;
             XrFacetChunk chunk;
-            for (int f = 0; f < nf; ++f) chunk.f[f] = facets[i][f0 + f];
-            hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, (hipStream_t)stream, chunk,
-                               (float*)(tab + i * XR_MAX_FACETS + f0), n_floats);
+            for (int f = 0; f < nf; ++f) chunk.f[f] = pl.rows[i][f0 + f];
+            hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, st, chunk, (float*)(tab + i * stride + f0), n_floats);
         }
-    const bool up = dh != H || dw != W;
-    dim3 grid(cdiv(mw, 16), cdiv(mh, 16), n_eyes * batch), block(256);
-    if (glow_on) {
-        XrGlowDev G;
-        xr_glow_dev(screen, glow, H, W, G);
-        const size_t lds = (size_t)G.n_tex * 3 * sizeof(float);      // <= 65 532 bytes (an 8192 x 8192 frame)
-#define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D>), grid, block, lds, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex, G, levels)
-        if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
-        else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
-#undef DIBR_XR
-        D2S_CHECK_LAUNCH();
-        return D2S_OK;
-    }
-#define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex)
-    if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
-    else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
+#define DIBR_XR(FMT, D) do { \
+        if (pl.kind == D2S_XR_KIND_PLAIN) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex); \
+        else if (pl.kind == D2S_XR_KIND_GLOW) hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, levels); \
+        else hipLaunchKernelGGL((dibr_xr_glow_curved_kernel<FMT, D>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, pl.Q, levels); } while (0)
+    if (out_fmt == D2S_FMT_U8_HWC) { if (pl.up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
+    else { if (pl.up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
 #undef DIBR_XR
     D2S_CHECK_LAUNCH();
     return D2S_OK;
 }
 
+int d2s::dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                           const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                           void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
+                           bool check_only) {
+    XrPlan pl;
+    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, pl);
+    return rc ? rc : xr_launch(pl, rgb, depth, out, out_fmt, workspace, workspace_bytes, levels, stream, check_only);
+}
+
 extern "C" int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                                 const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
                                 int out_fmt, void* workspace, uint64_t workspace_bytes, void* stream) {
-    return dibr_xr_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, stream, false);
+    return dibr_xr_entry_any(D2S_XR_ENTRY_EYES, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, nullptr, nullptr, stream, false);
 }
 
 extern "C" int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                                      const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
                                      int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
                                      void* stream) {
-    return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, glow,
-                            levels, stream, false);
-}
-
-// The curved screen with its glow (xr_viewer/effects.py:408-474 in _render_eye's order, :1050-1145).
-extern "C" int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes) {
-    D2S_REQUIRE(bytes, "null pointer (bytes)");
-    D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
-    *bytes = (uint64_t)n_eyes * XR_PIECES * sizeof(XrFacet);
-    return D2S_OK;
-}
-
-// A flat screen, glow == nullptr or mode 0: dibr_xr_glow_any, the same launches.
-int d2s::dibr_xr_glow_curved_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                                 const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
-                                 int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
-                                 void* stream, bool check_only) {
-    const bool curved_glow = screen && screen->struct_size == sizeof(d2s_xr_screen) && screen->curve != D2S_XR_CURVE_FLAT && glow &&
-                             glow->struct_size == sizeof(d2s_xr_glow) && glow->mode != 0;
-    if (!curved_glow)
-        return dibr_xr_glow_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes, glow,
-                                levels, stream, check_only);
-    D2S_REQUIRE(p, "null pointer");      // (the device pointers are looked at last: a call that names none can be refused for any other reason, and launches nothing)
-    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
-    if (rc) return rc;
-    D2S_REQUIRE(!p->feather_enabled, "feather_enabled must be 0 (the OpenXR viewer never enables the feathering)");
-    if (crop) {
-        int a, b2, c2, d2;
-        rc = crop_eye_shape(H, W, crop, D2S_MODE_FULL_SBS, &a, &b2, &c2, &d2);
-        if (rc) return rc;
-    }
-    rc = xr_check(screen, eyes, n_eyes, batch, workspace, workspace_bytes);
-    if (rc) return rc;
-    D2S_REQUIRE(workspace_bytes >= (uint64_t)n_eyes * XR_PIECES * sizeof(XrFacet), "workspace_bytes below d2s_dibr_xr_glow_curved_workspace");
-    rc = xr_glow_check(screen, glow, levels, true);
-    if (rc) return rc;
-    D2S_REQUIRE(H >= 2 && W >= 2 && H <= 8192 && W <= 8192, "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
-    uint64_t offs[2] = {0, 0}, total = 0;
-    rc = xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, offs, &total);
-    if (rc) return rc;
-    XrGlowDev G;
-    xr_glow_dev(screen, glow, H, W, G);
-    const size_t lds = (size_t)G.n_tex * 3 * sizeof(float);
-    if (lds + (XR_PIECES * XR_LDS_ROW + XR_SEAMS * 3) * sizeof(float) > 65536) {      // (only an 8192 x 8192 frame's 5 461 texels)
-        set_error("unsupported: the frame's coarse mip levels and the piece table exceed 64 KB of LDS (a frame of 8192 x 8192)");
-        return D2S_E_UNSUPPORTED;
-    }
-    XrSurface S;
-    xr_surface(screen, S);
-    XrCurvedDev Q;
-    double e_al;
-    xr_curved_dev(screen, glow, Q, &e_al);
-    XrCurvedPieces P;
-    xr_curved_pieces(screen, e_al, P);
-    for (int i = 0; i < n_eyes; ++i) {
-        if (!(xr_min_w(S, eyes[i].vp) > 1e-6)) {
-            set_error("unsupported: a vertex of the screen has clip w <= 1e-6 (the screen crosses the eye plane)");
-            return D2S_E_UNSUPPORTED;
-        }
-        if (!xr_eye_inside(S, P, eyes[i].vp)) {
-            set_error("unsupported: an eye lies outside the convex region the curved screen and its two tangent planes bound (behind the "
-                      "screen or beyond an end of the arc): the glow's pieces would overlap and need blending in draw order");
-            return D2S_E_UNSUPPORTED;
-        }
-    }
-    D2S_REQUIRE(rgb && depth && out, "null pointer");
-    DibrGeomProj g;
-    dibr_fill_geom(g, p, H, W, dh, dw);
-    g.c = cosf((float)screen->roll); g.s = sinf((float)screen->roll);
-    g.feather = 0;
-    g.mode = 0; g.oh = g.ow = g.out_h = g.out_w = 0;
-    g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
-    g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
-    XrEyes ex = {};
-    ex.n = n_eyes;
-    for (int k = 0; k < 4; ++k) ex.clear[k] = screen->clear[k];
-    int mw = 0, mh = 0;
-    XrFacet rows[2][XR_PIECES];
-    for (int i = 0; i < n_eyes; ++i) {
-        ex.e[i] = XrEyeDev{eyes[i].width, eyes[i].height, eyes[i].eye, S.n, (long)offs[i]};
-        mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
-        xr_curved_table(S, P, glow->mode, eyes[i].vp, eyes[i].width, eyes[i].height, rows[i]);
-    }
-    if (check_only) return D2S_OK;
-    XrFacet* tab = (XrFacet*)workspace;
-    for (int i = 0; i < n_eyes; ++i)
-        for (int f0 = 0; f0 < XR_PIECES; f0 += XR_CHUNK_FACETS) {                      // 3 set-up launches per eye
-            const int nf = std::min(XR_CHUNK_FACETS, XR_PIECES - f0), n_floats = nf * XR_ROW_FLOATS;
-            XrFacetChunk chunk;
-            for (int f = 0; f < nf; ++f) chunk.f[f] = rows[i][f0 + f];
-            hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, (hipStream_t)stream, chunk,
-                               (float*)(tab + i * XR_PIECES + f0), n_floats);
-        }
-    const bool up = dh != H || dw != W;
-    dim3 grid(cdiv(mw, 16), cdiv(mh, 16), n_eyes * batch), block(256);
-#define DIBR_XR(FMT, D) hipLaunchKernelGGL((dibr_xr_glow_curved_kernel<FMT, D>), grid, block, lds, (hipStream_t)stream, rgb, depth, out, (const XrFacet*)tab, g, ex, G, Q, levels)
-    if (out_fmt == D2S_FMT_U8_HWC) { if (up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
-    else { if (up) DIBR_XR(D2S_FMT_F32_HWC, UpDep); else DIBR_XR(D2S_FMT_F32_HWC, FullDep); }
-#undef DIBR_XR
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
+    return dibr_xr_entry_any(D2S_XR_ENTRY_GLOW, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, glow, levels, stream, false);
 }
 
 extern "C" int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                                             const d2s_dibr_params* p, const double crop[4], const d2s_xr_screen* screen,
                                             const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
                                             uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
-    return dibr_xr_glow_curved_any(rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace, workspace_bytes,
-                                   glow, levels, stream, false);
+    return dibr_xr_entry_any(D2S_XR_ENTRY_GLOW_CURVED, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, glow, levels, stream, false);
 }

@@ -4,6 +4,8 @@
 #pragma once
 #include "common.h"
 #include <math.h>
+#include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 namespace d2s {
@@ -398,6 +400,36 @@ inline int dibr_eye_shape(int eh, int ew, int display_mode, int* oh, int* ow, in
     *ow = display_mode == D2S_MODE_HALF_SBS ? ew / 2 : ew;
     *out_h = display_mode == D2S_MODE_FULL_TAB || display_mode == D2S_MODE_HALF_TAB ? 2 * *oh : *oh;
     *out_w = display_mode == D2S_MODE_FULL_SBS || display_mode == D2S_MODE_HALF_SBS ? 2 * *ow : *ow;
+    return D2S_OK;
+}
+
+// _movie_crop_pixel_bounds (xr_viewer/crop.py:165-173): Python's round() is half-to-even = nearbyint on doubles
+inline void crop_pixel_bounds(int W, int H, const double crop[4], int b[4]) {
+    auto clampi = [](long v, long lo, long hi) { return (int)std::max(lo, std::min(v, hi)); };
+    b[0] = clampi((long)nearbyint(crop[0] * W), 0, std::max(0, W - 1));
+    b[1] = clampi((long)nearbyint(crop[1] * H), 0, std::max(0, H - 1));
+    b[2] = std::max(b[0] + 1, (int)std::min((long)nearbyint((crop[0] + crop[2]) * W), (long)W));
+    b[3] = std::max(b[1] + 1, (int)std::min((long)nearbyint((crop[1] + crop[3]) * H), (long)H));
+}
+inline int crop_check(const double* crop) {
+    D2S_REQUIRE(crop, "null pointer (crop)");
+    for (int i = 0; i < 4; ++i) D2S_REQUIRE(std::isfinite(crop[i]), "crop must be finite");
+    const double e = 1e-6;
+    D2S_REQUIRE(crop[0] >= -e && crop[1] >= -e, "crop x, y must be >= 0");
+    D2S_REQUIRE(crop[2] > 0.0 && crop[3] > 0.0, "crop w, h must be > 0");
+    D2S_REQUIRE(crop[0] + crop[2] <= 1.0 + e && crop[1] + crop[3] <= 1.0 + e, "crop x + w, y + h must be <= 1");
+    return D2S_OK;
+}
+// the per-eye viewport of a cropped warp: the crop's pixel size, halved by the Half modes as d2s_dibr_shape halves the frame
+inline int crop_eye_shape(int H, int W, const double* crop, int display_mode, int* oh, int* ow, int* out_h, int* out_w) {
+    D2S_REQUIRE(H > 1 && W > 1, "bad shape");
+    int rc = crop_check(crop);
+    if (rc) return rc;
+    int b[4];
+    crop_pixel_bounds(W, H, crop, b);
+    rc = dibr_eye_shape(b[3] - b[1], b[2] - b[0], display_mode, oh, ow, out_h, out_w);
+    if (rc) return rc;
+    D2S_REQUIRE(*oh >= 2 && *ow >= 2, "crop: the eye viewport must be at least 2 x 2 pixels");
     return D2S_OK;
 }
 

@@ -3,7 +3,7 @@
 // _build_model_mat4 (xr_viewer/screen.py:29-70), _build_curved_screen_verts (screen.py:110-173), _screen_effect_basis
 // (xr_viewer/effects.py:65-82), _CURVED_HALF_ANGLE_RAD (xr_viewer/constants.py:50-51), _render_eye (effects.py:1023-1137).
 #pragma once
-#include "common.h"
+#include "dibr_tex.h"
 #include "mip.h"
 #include <cmath>
 
@@ -120,8 +120,8 @@ inline void xr_facets(const XrSurface& S, const double vp[16], int w, int h, XrF
 
 inline bool xr_finite(const double* v, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false; return true; }
 
-// What d2s_dibr_xr_eyes refuses about the screen, the eyes and the workspace, in the header's order; no HIP call.
-inline int xr_check(const d2s_xr_screen* s, const d2s_xr_eye* eyes, int n_eyes, int batch, const void* ws, uint64_t ws_bytes) {
+// What d2s_dibr_xr_eyes refuses about the screen and the eyes, in the header's order (xr_plan; the workspace is the launcher's).
+inline int xr_screen_check(const d2s_xr_screen* s, const d2s_xr_eye* eyes, int n_eyes, int batch) {
     D2S_REQUIRE(s && eyes, "null pointer (screen, eyes)");
     D2S_REQUIRE(s->struct_size == sizeof(d2s_xr_screen), "d2s_xr_screen.struct_size must be sizeof(d2s_xr_screen) = 96");
     D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
@@ -137,10 +137,17 @@ inline int xr_check(const d2s_xr_screen* s, const d2s_xr_eye* eyes, int n_eyes, 
         D2S_REQUIRE(eyes[i].eye == 0 || eyes[i].eye == 1, "eye must be 0 (left) or 1 (right)");
     }
     D2S_REQUIRE((long)n_eyes * batch <= 65535, "n_eyes * batch too large for one launch");
-    D2S_REQUIRE(ws, "null pointer (workspace)");
-    D2S_REQUIRE(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
-    D2S_REQUIRE(ws_bytes >= (uint64_t)n_eyes * XR_MAX_FACETS * sizeof(XrFacet), "workspace_bytes below d2s_dibr_xr_workspace");
     return D2S_OK;
+}
+// The eye images one after another in out: eye i is [batch][height_i][width_i][nch] at offsets[i] (d2s_dibr_xr_shape, xr_plan)
+inline void xr_out_layout(const d2s_xr_eye* eyes, int n_eyes, int batch, int alpha_mode, uint64_t* offsets, uint64_t* total) {
+    const uint64_t nch = alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    uint64_t at = 0;
+    for (int i = 0; i < n_eyes; ++i) {
+        offsets[i] = at;
+        at += (uint64_t)batch * eyes[i].height * eyes[i].width * nch;
+    }
+    *total = at;
 }
 
 // ---- the glow around the flat screen (d2s_dibr_xr_eyes_glow; _render_glow, xr_viewer/effects.py:476-585) ----
@@ -156,13 +163,13 @@ struct XrGlowDev {
     uint32_t chain_off, chain_total;              // level m's byte offset within a frame's chain; the chain's bytes per frame
 };
 
-// What d2s_dibr_xr_eyes_glow refuses about the glow, after xr_check has accepted the screen; no HIP call.
-inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, const uint8_t* levels, bool curved_ok = false) {
+// What d2s_dibr_xr_eyes_glow refuses about the glow, after xr_screen_check has accepted the screen (levels, a device pointer, is the
+// launcher's).  curved_ok: the asking entry draws the curved screen's glow.
+inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, bool curved_ok) {
     if (!glow) return D2S_OK;
     D2S_REQUIRE(glow->struct_size == sizeof(d2s_xr_glow), "d2s_xr_glow.struct_size must be sizeof(d2s_xr_glow) = 24");
     D2S_REQUIRE(glow->mode >= 0 && glow->mode <= 2, "bad glow mode (0 off, 1 glow, 2 glow2)");
     if (glow->mode == 0) return D2S_OK;
-    D2S_REQUIRE(levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
     D2S_REQUIRE(std::isfinite(glow->range_m) && glow->range_m > 0.0, "glow range_m must be finite and > 0");
     D2S_REQUIRE(std::isfinite(glow->inner_edge_fraction) && glow->inner_edge_fraction >= 0.0, "glow inner_edge_fraction must be finite and >= 0");
     if (s->curve != D2S_XR_CURVE_FLAT && !curved_ok) {
@@ -173,18 +180,25 @@ inline int xr_glow_check(const d2s_xr_screen* s, const d2s_xr_glow* glow, const 
     return D2S_OK;
 }
 
-// _render_glow:486-495 in double precision; H x W: the frame the chain was built from
-inline void xr_glow_dev(const d2s_xr_screen* s, const d2s_xr_glow* glow, int H, int W, XrGlowDev& G) {
+// _render_glow:486-495 and _render_curved_glow:414-423 in double precision: the glow quad's extents.  inner_uv: mode 1's; glow2 has
+// no inner band.
+struct XrGlowExtents { double uv_range, inner_w, inner_h, inner_uv; };
+inline XrGlowExtents xr_glow_extents(const d2s_xr_screen* s, const d2s_xr_glow* glow) {
     double range = fmax(glow->range_m, 1e-4);
     if (glow->mode == 2) range *= 0.5;
     const double glow_w = s->width + 2.0 * range, glow_h = s->height + 2.0 * range;
-    const double uv_range = range / fmax(glow_w, glow_h), inner_w = s->width / glow_w, inner_h = s->height / glow_h;
-    const double inner_uv = glow->mode == 2 ? 0.0 : fmin(inner_w, inner_h) * fmax(glow->inner_edge_fraction, 0.0);
+    XrGlowExtents x;
+    x.uv_range = range / fmax(glow_w, glow_h); x.inner_w = s->width / glow_w; x.inner_h = s->height / glow_h;
+    x.inner_uv = fmin(x.inner_w, x.inner_h) * fmax(glow->inner_edge_fraction, 0.0);
+    return x;
+}
+// H x W: the frame the chain was built from
+inline void xr_glow_dev(const XrGlowExtents& x, int mode, int H, int W, XrGlowDev& G) {
     G = XrGlowDev{};
-    G.mode = glow->mode;
-    G.half_x = (float)(inner_w * 0.5); G.half_y = (float)(inner_h * 0.5);
-    G.inner_w = (float)inner_w; G.inner_h = (float)inner_h;
-    G.inv_range = (float)(1.0 / fmax(uv_range, 1e-6)); G.inner = (float)inner_uv;
+    G.mode = mode;
+    G.half_x = (float)(x.inner_w * 0.5); G.half_y = (float)(x.inner_h * 0.5);
+    G.inner_w = (float)x.inner_w; G.inner_h = (float)x.inner_h;
+    G.inv_range = (float)(1.0 / fmax(x.uv_range, 1e-6)); G.inner = (float)(mode == 2 ? 0.0 : x.inner_uv);
     MipShape ms;
     mip_shape(H, W, ms);
     G.q = ms.q; G.m = ms.q < XR_GLOW_LOD ? ms.q : XR_GLOW_LOD;
@@ -212,12 +226,8 @@ struct XrCurvedDev { int vertical; float e_al, e_ac; };
 struct XrCurvedPieces { XrVert p00[4], p10[4], p01[4]; double axis[3], radius; };      // pieces 48 .. 51; a point of the cylinder's axis
 
 // _build_curved_glow_band_verts:381-388: u0i - u0 = min(inner_uv, inner_w / 2) in glow uv, / inner_w in the screen's
-inline void xr_curved_dev(const d2s_xr_screen* s, const d2s_xr_glow* glow, XrCurvedDev& Q, double* e_al_out) {
-    double range = fmax(glow->range_m, 1e-4);
-    if (glow->mode == 2) range *= 0.5;
-    const double glow_w = s->width + 2.0 * range, glow_h = s->height + 2.0 * range, inner_w = s->width / glow_w, inner_h = s->height / glow_h;
-    const double inner_uv = fmin(inner_w, inner_h) * fmax(glow->inner_edge_fraction, 0.0);
-    const double eu = fmin(0.5, inner_uv / inner_w), ev = fmin(0.5, inner_uv / inner_h);
+inline void xr_curved_dev(const d2s_xr_screen* s, const XrGlowExtents& x, XrCurvedDev& Q, double* e_al_out) {
+    const double eu = fmin(0.5, x.inner_uv / x.inner_w), ev = fmin(0.5, x.inner_uv / x.inner_h);
     Q.vertical = s->curve == D2S_XR_CURVE_VERTICAL;
     Q.e_al = (float)(Q.vertical ? ev : eu); Q.e_ac = (float)(Q.vertical ? eu : ev);
     *e_al_out = Q.vertical ? ev : eu;
@@ -304,5 +314,114 @@ inline void xr_curved_table(const XrSurface& S, const XrCurvedPieces& P, int mod
         xr_facet_row(P.p00[k], P.p10[k], P.p01[k], vp, w, h, out[XR_T0 + k]);
     }
 }
+
+// ---- the eye views' plan: everything the three entries decide from the arguments that are no device pointers ----
+struct XrEyeDev { int w, h, eye, nf; long out_off; };      // out_off: the eye image's first element in out; its table: eye index * rows_per_eye
+struct XrEyes { XrEyeDev e[2]; int n; float clear[4]; };
+// The curved glow's kernel keeps the eye's rows (padded to 25 floats) and the 49 seams in static LDS
+constexpr int XR_LDS_ROW = XR_ROW_FLOATS + 1;
+constexpr uint32_t XR_CURVED_LDS = (XR_PIECES * XR_LDS_ROW + XR_SEAMS * 3) * sizeof(float);
+// rows an eye's table occupies in the workspace (d2s_dibr_xr_workspace, d2s_dibr_xr_glow_curved_workspace, the kernels' stride)
+constexpr int xr_table_rows(int kind) { return kind == D2S_XR_KIND_GLOW_CURVED ? XR_PIECES : XR_MAX_FACETS; }
+
+struct XrPlan {
+    int kind;                                     // D2S_XR_KIND_*: which kernel draws
+    DibrGeomProj g;
+    XrEyes ex;
+    XrGlowDev G;                                  // kind != PLAIN
+    XrCurvedDev Q;                                // kind == GLOW_CURVED
+    bool up;                                      // depth is not at the frame's resolution: the UpDep sampler
+    int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48) or XR_PIECES
+    XrFacet rows[2][XR_PIECES];
+    int setup_launches;                           // all eyes': XR_CHUNK_FACETS rows travel in one launch's arguments
+    unsigned grid[3];
+    uint32_t lds_dynamic, lds_static;
+    uint64_t workspace_bytes;
+    uint64_t offs[2], total;                      // the out layout (xr_out_layout)
+};
+
+// entry: D2S_XR_ENTRY_*, the public call that asks.  EYES takes no glow (the caller passes none); GLOW refuses a curved screen with
+// glow on.  Every refusal of the three entries that needs no device pointer, in their order; no HIP call.
+inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, const d2s_xr_screen* screen,
+                   const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, XrPlan& pl) {
+    D2S_REQUIRE(p, "null pointer");
+    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
+    if (rc) return rc;
+    D2S_REQUIRE(!p->feather_enabled, "feather_enabled must be 0 (the OpenXR viewer never enables the feathering)");
+    if (crop) {                                            // what d2s_dibr_warp_crop refuses about a crop, its 2 x 2 pixel floor included
+        int a, b2, c2, d2;
+        rc = crop_eye_shape(H, W, crop, D2S_MODE_FULL_SBS, &a, &b2, &c2, &d2);
+        if (rc) return rc;
+    }
+    rc = xr_screen_check(screen, eyes, n_eyes, batch);
+    if (rc) return rc;
+    rc = xr_glow_check(screen, glow, entry == D2S_XR_ENTRY_GLOW_CURVED);
+    if (rc) return rc;
+    const bool glow_on = glow && glow->mode != 0;
+    D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
+    pl.kind = !glow_on ? D2S_XR_KIND_PLAIN : screen->curve == D2S_XR_CURVE_FLAT ? D2S_XR_KIND_GLOW : D2S_XR_KIND_GLOW_CURVED;
+    const bool curved = pl.kind == D2S_XR_KIND_GLOW_CURVED;
+    xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, pl.offs, &pl.total);
+    pl.G = XrGlowDev{};
+    pl.Q = XrCurvedDev{};
+    XrSurface S;
+    xr_surface(screen, S);
+    XrCurvedPieces P;
+    if (glow_on) {
+        const XrGlowExtents x = xr_glow_extents(screen, glow);
+        xr_glow_dev(x, glow->mode, H, W, pl.G);
+        if (curved) {
+            double e_al;
+            xr_curved_dev(screen, x, pl.Q, &e_al);
+            xr_curved_pieces(screen, e_al, P);
+        }
+    }
+    pl.lds_dynamic = (uint32_t)pl.G.n_tex * 3 * sizeof(float);      // <= 65 532 bytes (an 8192 x 8192 frame)
+    pl.lds_static = curved ? XR_CURVED_LDS : 0;
+    if (pl.lds_dynamic + pl.lds_static > 65536) {                   // (only an 8192 x 8192 frame's 5 461 texels)
+        set_error("unsupported: the frame's coarse mip levels and the piece table exceed 64 KB of LDS (a frame of 8192 x 8192)");
+        return D2S_E_UNSUPPORTED;
+    }
+    for (int i = 0; i < n_eyes; ++i) {
+        if (!(xr_min_w(S, eyes[i].vp) > 1e-6)) {
+            set_error("unsupported: a vertex of the screen has clip w <= 1e-6 (the screen crosses the eye plane)");
+            return D2S_E_UNSUPPORTED;
+        }
+        if (curved && !xr_eye_inside(S, P, eyes[i].vp)) {
+            set_error("unsupported: an eye lies outside the convex region the curved screen and its two tangent planes bound (behind the "
+                      "screen or beyond an end of the arc): the glow's pieces would overlap and need blending in draw order");
+            return D2S_E_UNSUPPORTED;
+        }
+    }
+    DibrGeomProj& g = pl.g;
+    dibr_fill_geom(g, p, H, W, dh, dw);
+    g.c = cosf((float)screen->roll); g.s = sinf((float)screen->roll);                 // u_roll = screen_roll (effects.py:1113, 1129)
+    g.feather = 0;
+    g.mode = 0; g.oh = g.ow = g.out_h = g.out_w = 0;
+    g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
+    g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
+    pl.up = dh != H || dw != W;
+    pl.rows_per_eye = curved ? XR_PIECES : S.n;
+    pl.ex = XrEyes{};
+    pl.ex.n = n_eyes;
+    for (int k = 0; k < 4; ++k) pl.ex.clear[k] = screen->clear[k];
+    int mw = 0, mh = 0;
+    for (int i = 0; i < n_eyes; ++i) {
+        pl.ex.e[i] = XrEyeDev{eyes[i].width, eyes[i].height, eyes[i].eye, S.n, (long)pl.offs[i]};
+        mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
+        if (curved) xr_curved_table(S, P, glow->mode, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i]);
+        else xr_facets(S, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i]);
+    }
+    pl.setup_launches = n_eyes * cdiv(pl.rows_per_eye, XR_CHUNK_FACETS);               // per eye: 1 (flat), 2 (curved), 3 (curved glow)
+    pl.grid[0] = cdiv(mw, 16); pl.grid[1] = cdiv(mh, 16); pl.grid[2] = n_eyes * batch;
+    pl.workspace_bytes = (uint64_t)n_eyes * xr_table_rows(pl.kind) * sizeof(XrFacet);
+    return D2S_OK;
+}
+
+// The three entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
+// every refusal, nothing launched (the view pipelines ask before they start the model).
+int dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                      const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                      void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
 
 }  // namespace d2s

@@ -9,6 +9,7 @@
 
 #include "gemm.h"
 #include "forward_plan.h"
+#include "dibr_xr.h"
 #include "vit_ops.h"
 
 using namespace d2s;
@@ -1058,16 +1059,6 @@ int dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, i
                        int composite, void* out, int out_fmt, void* stream, bool check_only);
 int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                        const double* crop, void* out, int out_fmt, void* stream, bool check_only);
-int dibr_xr_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
-                const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
-                uint64_t workspace_bytes, void* stream, bool check_only);
-int dibr_xr_glow_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop,
-                     const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
-                     uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
-int dibr_xr_glow_curved_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                            const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
-                            void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                            bool check_only);
 }
 
 namespace {
@@ -1201,7 +1192,7 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
                                 const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
                                 const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
                                 void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                                bool curved = false) {
+                                int entry) {
     D2S_REQUIRE(frames && pp && dp && out && screen && eyes, "null pointer");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     uint64_t offs[2], total = 0;
@@ -1210,9 +1201,8 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
     int stride = 1;
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
     auto warp = [&](bool check_only) {
-        return (curved ? dibr_xr_glow_curved_any : dibr_xr_glow_any)(frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes,
-                                                                     n_eyes, out, out_fmt, workspace, workspace_bytes, glow, levels, stream,
-                                                                     check_only);
+        return dibr_xr_entry_any(entry, frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                                 workspace_bytes, glow, levels, stream, check_only);
     };
     RC(warp(true));
     D2S_ON_DEVICE(e->device);
@@ -1229,7 +1219,7 @@ extern "C" int d2s_view_pipeline_xr_streams(d2s_engine* e, const uint8_t* frames
                                             const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
                                             void* workspace, uint64_t workspace_bytes, void* stream) {
     return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
-                                out_fmt, depth_full, workspace, workspace_bytes, nullptr, nullptr, stream);
+                                out_fmt, depth_full, workspace, workspace_bytes, nullptr, nullptr, stream, D2S_XR_ENTRY_EYES);
 }
 
 extern "C" int d2s_view_pipeline_xr_glow_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
@@ -1239,7 +1229,7 @@ extern "C" int d2s_view_pipeline_xr_glow_streams(d2s_engine* e, const uint8_t* f
                                                  void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
                                                  void* stream) {
     return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
-                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream);
+                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, D2S_XR_ENTRY_GLOW);
 }
 
 // the engine's pipeline up to the EMA step, then d2s_dibr_xr_eyes_glow_curved on the model-resolution depth
@@ -1250,7 +1240,7 @@ extern "C" int d2s_view_pipeline_xr_glow_curved_streams(d2s_engine* e, const uin
                                                         float* depth_full, void* workspace, uint64_t workspace_bytes,
                                                         const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
     return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
-                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, true);
+                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, D2S_XR_ENTRY_GLOW_CURVED);
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

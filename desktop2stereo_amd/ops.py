@@ -398,6 +398,10 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
 
 
 _XR_WS: Dict[Tuple, torch.Tensor] = {}
+# Engine._view_pipeline_xr's entry: (C name, the Python method's name for messages, the workspace size query)
+_XR_PIPELINES = {"eyes": ("d2s_view_pipeline_xr_streams", "view_pipeline_xr", "d2s_dibr_xr_workspace"),
+                 "glow": ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow", "d2s_dibr_xr_workspace"),
+                 "glow_curved": ("d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_glow_curved_workspace")}
 
 
 def _xr_args(screen, eyes):
@@ -444,33 +448,7 @@ def dibr_xr_eyes(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams
     None; dp as dibr_warp(crop=) reads it except display_mode, viewport and roll (screen.roll is u_roll); feathering is refused.
     Returns one tensor per eye, [B,h,w,3|4] uint8 / float32 0..255 (views of one flat buffer: `out`, a caller-kept 1-D tensor of
     dibr_xr_shape's total, or a new one).  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_workspace bytes."""
-    _need_cuda(frames, "frames")
-    _need_cuda(depth, "depth")
-    if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
-        raise ValueError("dibr_xr_eyes: frames must be uint8 [B,H,W,3] or [H,W,3]")
-    f = frames.contiguous() if frames.dim() == 4 else frames.contiguous().unsqueeze(0)
-    d = depth.to(torch.float32).contiguous()
-    d = d if d.dim() == 3 else d.unsqueeze(0)
-    B, H, W, _ = f.shape
-    if d.dim() != 3 or d.shape[0] != B:
-        raise ValueError(f"dibr_xr_eyes: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
-    _same_device(f, d, "dibr_xr_eyes")
-    sc, ea = _xr_args(screen, eyes)
-    offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
-    nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-    dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
-    if out is None:
-        out = torch.empty(total, dtype=dtype, device=f.device)
-    elif not out.is_cuda or out.device != f.device or out.dtype != dtype or out.numel() != total or not out.is_contiguous():
-        raise ValueError(f"dibr_xr_eyes: out must be a contiguous {dtype} tensor of {total} elements on {f.device}")
-    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device)
-    _need_cuda(ws, "workspace")
-    _same_device(f, ws, "dibr_xr_eyes workspace")
-    c4 = _crop4(crop) if crop is not None else None
-    with _on(f.device) as st:
-        check(_lib.load().d2s_dibr_xr_eyes(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
-                                           _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(), st), "d2s_dibr_xr_eyes")
-    return _xr_views(out.view(-1), ea, B, nch, offs)
+    return _dibr_xr_call("d2s_dibr_xr_eyes", "d2s_dibr_xr_workspace", "dibr_xr_eyes", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace)
 
 
 def mip_shape(H: int, W: int) -> Tuple[list, int]:
@@ -520,8 +498,8 @@ def dibr_xr_eyes_glow(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrP
     """dibr_xr_eyes with the reference's glow around the flat screen in the same launch (d2s_dibr_xr_eyes_glow; reference
     _render_glow, xr_viewer/effects.py:476-585): glow = xr.XrGlow (None or mode "off": exactly dibr_xr_eyes), levels = mip_chain(frames)
     -- or an older chain: the reference refreshes its mipmaps every few frames only.  Everything else as dibr_xr_eyes."""
-    return _dibr_xr_eyes_glow("d2s_dibr_xr_eyes_glow", "d2s_dibr_xr_workspace", "dibr_xr_eyes_glow", frames, depth, dp, screen, eyes, glow,
-                              levels, crop, out_u8, out, workspace)
+    return _dibr_xr_call("d2s_dibr_xr_eyes_glow", "d2s_dibr_xr_workspace", "dibr_xr_eyes_glow", frames, depth, dp, screen, eyes, crop, out_u8,
+                         out, workspace, (glow, levels))
 
 
 def dibr_xr_eyes_glow_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
@@ -530,11 +508,13 @@ def dibr_xr_eyes_glow_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_li
     xr_viewer/effects.py:408-474): screen.curve "horizontal" | "vertical" with glow mode "glow" | "glow2".  A flat screen or no glow is
     exactly dibr_xr_eyes_glow.  An eye outside the convex region the screen bounds (xr.XrScreen.eye_inside) is refused.  workspace: a
     caller-kept uint8 device tensor of d2s_dibr_xr_glow_curved_workspace bytes."""
-    return _dibr_xr_eyes_glow("d2s_dibr_xr_eyes_glow_curved", "d2s_dibr_xr_glow_curved_workspace", "dibr_xr_eyes_glow_curved", frames, depth,
-                              dp, screen, eyes, glow, levels, crop, out_u8, out, workspace)
+    return _dibr_xr_call("d2s_dibr_xr_eyes_glow_curved", "d2s_dibr_xr_glow_curved_workspace", "dibr_xr_eyes_glow_curved", frames, depth, dp,
+                         screen, eyes, crop, out_u8, out, workspace, (glow, levels))
 
 
-def _dibr_xr_eyes_glow(entry, ws_query, who, frames, depth, dp, screen, eyes, glow, levels, crop, out_u8, out, workspace) -> list:
+def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow_levels=None) -> list:
+    """The tensor checks and the call of the three eye-view entries.  glow_levels: None for d2s_dibr_xr_eyes, whose argument list has
+    no glow; (glow, levels) for the two that take them."""
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
@@ -547,9 +527,13 @@ def _dibr_xr_eyes_glow(entry, ws_query, who, frames, depth, dp, screen, eyes, gl
         raise ValueError(f"{who}: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
     _same_device(f, d, who)
     sc, ea = _xr_args(screen, eyes)
-    if levels is not None and levels.dim() == 1:
-        levels = levels.unsqueeze(0)
-    gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, who)
+    glow_args = ()
+    if glow_levels is not None:
+        glow, levels = glow_levels
+        if levels is not None and levels.dim() == 1:
+            levels = levels.unsqueeze(0)
+        gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, who)
+        glow_args = (C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None)
     offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
     nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
     dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
@@ -563,10 +547,26 @@ def _dibr_xr_eyes_glow(entry, ws_query, who, frames, depth, dp, screen, eyes, gl
     c4 = _crop4(crop) if crop is not None else None
     with _on(f.device) as st:
         check(getattr(_lib.load(), entry)(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
-                                                _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(),
-                                                C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None, st),
-              entry)
+                                          _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(), *glow_args, st), entry)
     return _xr_views(out.view(-1), ea, B, nch, offs)
+
+
+def dibr_xr_plan(entry: str, dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, crop=None, glow=None,
+                 out_u8: bool = True) -> dict:
+    """What the eye-view call `entry` ("eyes" | "glow" | "glow_curved") decides for these arguments before it looks at a device pointer
+    (include/d2s.h d2s_dibr_xr_plan; host code, no GPU): the kind of kernel, the table rows per eye and the launches that write them, the
+    render launch's grid and LDS bytes, the workspace bytes and the out layout.  Raises D2SError with the entry's own refusal."""
+    sc, ea = _xr_args(screen, eyes)
+    gs = None if glow is None else glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
+    r = _lib.XrPlanResult()
+    r.struct_size = C.sizeof(_lib.XrPlanResult)
+    check(_lib.load().d2s_dibr_xr_plan(_lib.XR_ENTRY[entry], int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
+                                       _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
+                                       FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(gs) if gs is not None else None, C.byref(r)),
+          "d2s_dibr_xr_plan")
+    return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
+            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
+            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
 
 
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
@@ -863,14 +863,12 @@ class Engine:
         ops.dibr_xr_eyes.  Returns one tensor per eye (with want_depth: (list, depth)); bit-identical to pipeline(want_depth=True)'s
         engine depth followed by dibr_xr_eyes.  out: a caller-kept 1-D tensor of dibr_xr_shape's total.  (A method of its own, as
         view_pipeline_crop is: view_pipeline's parameter list is pinned by the ABI tests.)"""
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, None, None)
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, None, None, "eyes")
 
-    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, curved=False):
+    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, entry):
         sc, ea = _xr_args(screen, eyes)
         nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-        name, who = ("d2s_view_pipeline_xr_streams", "view_pipeline_xr") if glow is None else ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow")
-        if curved:
-            name, who = "d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved"
+        name, who, ws_query = _XR_PIPELINES[entry]
         lay = {}
 
         def spec(B, H, W):
@@ -879,14 +877,13 @@ class Engine:
             if glow is not None:
                 lay["glow"] = _xr_glow_args(glow, levels, B, H, W, self.device, who)
             return (lay["total"],), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
-        ws = _xr_workspace(len(ea), self.device, "d2s_dibr_xr_glow_curved_workspace" if curved else "d2s_dibr_xr_workspace")
+        ws = _xr_workspace(len(ea), self.device, ws_query)
         nbytes = ws.numel()
 
         def fn(*a):      # (_run_pipeline ends every call with out, out_fmt, depth_full, stream: the workspace goes in front of the stream)
-            if glow is None:
-                return self.lib.d2s_view_pipeline_xr_streams(*a[:-1], _ptr(ws), nbytes, a[-1])
-            gs, lv = lay["glow"]
-            return getattr(self.lib, name)(*a[:-1], _ptr(ws), nbytes, C.byref(gs), _ptr(lv) if lv is not None else None, a[-1])
+            gs, lv = lay.get("glow", (None, None))
+            glow_args = () if glow is None else (C.byref(gs), _ptr(lv) if lv is not None else None)
+            return getattr(self.lib, name)(*a[:-1], _ptr(ws), nbytes, *glow_args, a[-1])
         mid = (C.byref(dp), _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea), int(use_ema))
         r = self._run_pipeline(fn, name, frames, p, spec, mid, want_depth, out, streams, who=who)
         flat = (r[0] if want_depth else r).view(-1)
@@ -901,7 +898,7 @@ class Engine:
         engine depth followed by dibr_xr_eyes_glow."""
         if glow is None:
             raise ValueError("view_pipeline_xr_glow: glow must be an xr.XrGlow (mode \"off\" for none)")
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels)
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, "glow")
 
     def view_pipeline_xr_glow_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels,
                                      crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
@@ -911,7 +908,7 @@ class Engine:
         dibr_xr_eyes_glow_curved."""
         if glow is None:
             raise ValueError("view_pipeline_xr_glow_curved: glow must be an xr.XrGlow (mode \"off\" for none)")
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, curved=True)
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, "glow_curved")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -526,6 +526,38 @@ int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh,
                                  int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
                                  void* stream);
 
+/* What the three eye-view calls above decide for these arguments, before they look at a device pointer (d2s_version() >= 123; pure host
+ * code: launches nothing, needs no GPU).  entry: the call that asks -- D2S_XR_ENTRY_EYES takes no glow (glow must be NULL here),
+ * D2S_XR_ENTRY_GLOW refuses a curved screen with glow on, D2S_XR_ENTRY_GLOW_CURVED draws it.  Refuses exactly what that call refuses
+ * before it looks at rgb, depth, out, workspace or levels, with the same code and the same d2s_last_error text; those pointers are
+ * the call's last checks (workspace NULL, misaligned, short; levels NULL with glow on; rgb, depth, out NULL).
+ *   kind: the kernel that draws -- PLAIN (no glow, or mode 0), GLOW (flat screen), GLOW_CURVED.
+ *   rows_per_eye: table rows written per eye -- 1 (flat), 48 (curved), 52 (GLOW_CURVED); setup_launches: the launches that write them,
+ *   all eyes' (24 rows travel in one launch's arguments: per eye 1, 2 or 3).
+ *   grid: the render launch, 16 x 16 pixel blocks of 256 threads: (ceil(max width / 16), ceil(max height / 16), n_eyes * batch).
+ *   lds_dynamic_bytes: the chain's levels min(7, q) .. q as float RGB, 12 bytes a texel (0 for PLAIN); lds_static_bytes: the kernel's own.
+ *   workspace_bytes: d2s_dibr_xr_workspace's answer, GLOW_CURVED: d2s_dibr_xr_glow_curved_workspace's.
+ *   out_elems, offsets: d2s_dibr_xr_shape's total and offsets.
+ * D2S_E_INVALID also: res NULL, a bad res->struct_size, entry outside 0..2, a glow with D2S_XR_ENTRY_EYES. */
+enum { D2S_XR_ENTRY_EYES = 0, D2S_XR_ENTRY_GLOW = 1, D2S_XR_ENTRY_GLOW_CURVED = 2 };
+enum { D2S_XR_KIND_PLAIN = 0, D2S_XR_KIND_GLOW = 1, D2S_XR_KIND_GLOW_CURVED = 2 };
+typedef struct d2s_xr_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_plan_result) */
+    int32_t  kind;             /* D2S_XR_KIND_* */
+    int32_t  rows_per_eye;
+    int32_t  setup_launches;
+    uint32_t grid[3];
+    uint32_t lds_dynamic_bytes;
+    uint32_t lds_static_bytes;
+    uint32_t reserved;
+    uint64_t workspace_bytes;
+    uint64_t out_elems;
+    uint64_t offsets[2];
+} d2s_xr_plan_result;
+int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                     const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow,
+                     d2s_xr_plan_result* res);
+
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
  * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.

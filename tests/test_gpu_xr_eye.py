@@ -204,3 +204,39 @@ def test_a_refused_call_leaves_out_untouched(dev, fixtures):
     assert bool((out == -7.0).all())
     ops.dibr_xr_eyes(f, d, dp, screen, eyes, out_u8=False, out=out)                # and an accepted one writes every element
     assert not bool((out == -7.0).any())
+
+
+KINDS = [("plain", "flat", None), ("glow", "flat", "glow"), ("glow_curved", "horizontal", "glow"), ("glow_curved", "vertical", "glow")]
+
+
+@pytest.mark.parametrize("kind,curve,mode", KINDS, ids=[f"{k}-{c}" for k, c, _ in KINDS])
+def test_each_eye_of_two_unequal_eyes_is_its_one_eye_call(dev, kind, curve, mode):
+    """Two eye images of different sizes, neither a multiple of the 16 x 16 block: 34 x 20 (3 x 2 blocks) and 18 x 18 (2 x 2), batch 2.
+    The grid is the larger eye's, so whole blocks and parts of blocks lie outside the smaller eye's image while the other eye's blocks
+    stage the chain: every such thread must pass the kernels' barriers and write nothing.  Each eye's image is, bit for bit, the image
+    of a call with that eye alone."""
+    from desktop2stereo_amd import ops, synth, xr
+    H, W, dh, dw, B = 96, 160, 24, 40, 2
+    f = torch.from_numpy(np.stack([synth.dibr_scene(H, W, 31 + b, "boxes")[0] for b in range(B)])).to(dev)
+    d = torch.from_numpy(np.stack([synth.dibr_scene(dh, dw, 31 + b, "boxes")[1] for b in range(B)])).to(dev)
+    fov = ((-0.75, 0.60, 0.55, -0.60), (-0.60, 0.75, 0.55, -0.60))
+    vp = [xr.fov_to_proj_mat4(*fov[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), (-0.032 if i == 0 else 0.032, 0, 0)) for i in range(2)]
+    eyes = [xr.xr_eye(vp[0], 34, 20, 0), xr.xr_eye(vp[1], 18, 18, 1)]
+    screen = xr.XrScreen(width=1.6, height=0.96, distance=1.5, curve=curve, clear=(0.1, 0.2, 0.3, 1.0))
+    dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
+    want_kind = ops.dibr_xr_plan({"plain": "eyes"}.get(kind, kind), dh, dw, B, H, W, dp, screen, eyes, glow=xr.XrGlow(mode, 10.0) if mode else None,
+                                 out_u8=False)
+    assert want_kind["kind"] == kind and want_kind["grid"] == (3, 2, 2 * B)
+    if kind == "plain":
+        call = lambda e: ops.dibr_xr_eyes(f, d, dp, screen, e, out_u8=False)
+    else:
+        levels = ops.mip_chain(f)
+        fn = ops.dibr_xr_eyes_glow if kind == "glow" else ops.dibr_xr_eyes_glow_curved
+        call = lambda e: fn(f, d, dp, screen, e, xr.XrGlow(mode, 10.0), levels, out_u8=False)
+    both = call(eyes)
+    assert tuple(both[0].shape) == (B, 20, 34, 4) and tuple(both[1].shape) == (B, 18, 18, 4)
+    for i in range(2):
+        _eq(call([eyes[i]])[0], both[i], (kind, curve, "eye", i))
+    if kind != "plain":                                  # the glow is in the picture: it differs from the plain screen's
+        plain = ops.dibr_xr_eyes(f, d, dp, screen, eyes, out_u8=False)
+        assert all(not torch.equal(a, b) for a, b in zip(plain, both))
