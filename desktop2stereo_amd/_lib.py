@@ -68,7 +68,15 @@ class XrGlow(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("range_m", C.c_double), ("inner_edge_fraction", C.c_double)]
 
 
+class XrFrost(C.Structure):
+    """d2s_xr_frost: the veil / frosted look around the flat screen (mode 0 off, 1 veil, 2 frosted)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("head", C.c_double * 3), ("intensity", C.c_double), ("alpha", C.c_double),
+                ("edge_inset", C.c_double), ("beam_softness", C.c_double), ("beam_thickness", C.c_double), ("lod", C.c_double),
+                ("threshold", C.c_double), ("noise_scale", C.c_double), ("blend", C.c_double), ("diffuse", C.c_double), ("time", C.c_double)]
+
+
 XR_GLOW = {"off": 0, "glow": 1, "glow2": 2}
+XR_FROST = {"off": 0, "veil": 1, "frosted": 2}
 XR_CURVE = {"flat": 0, "horizontal": 1, "vertical": 2}      # D2S_XR_CURVE_*
 DIBR_ALPHA = {"window": 0, "premultiplied": 1, "rgba": 2}      # D2S_DIBR_ALPHA_*
 COMPOSITE = {"Anaglyph": 0, "Interleaved": 1, "Interleaved-V": 2, "Depth Map": 3}      # D2S_COMPOSITE_*
@@ -139,7 +147,7 @@ class XrPlanResult(C.Structure):
 
 
 XR_ENTRY = {"eyes": 0, "glow": 1, "glow_curved": 2}      # D2S_XR_ENTRY_*
-XR_KIND = {0: "plain", 1: "glow", 2: "glow_curved"}      # D2S_XR_KIND_*
+XR_KIND = {0: "plain", 1: "glow", 2: "glow_curved", 3: "frost"}      # D2S_XR_KIND_*
 
 
 class ForwardPlanResult(C.Structure):
@@ -238,6 +246,15 @@ SYMBOLS = {
                                                C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrGlow), _P, _P]),
     "d2s_dibr_xr_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
                                    C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, C.POINTER(XrGlow), C.POINTER(XrPlanResult)]),
+    # the veil and frosted looks of the flat screen (xr_viewer/effects.py:102-187, 789-857, xr_viewer/glsl.py:668-791)
+    "d2s_dibr_xr_frost_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "d2s_dibr_xr_eyes_frost": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                         C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrFrost), _P, _P]),
+    "d2s_dibr_xr_frost_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                         C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, C.POINTER(XrFrost), C.POINTER(XrPlanResult)]),
+    "d2s_view_pipeline_xr_frost_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                                     C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double), C.POINTER(XrScreen),
+                                                     C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.POINTER(XrFrost), _P, _P]),
     "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,

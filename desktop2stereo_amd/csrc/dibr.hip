@@ -409,7 +409,76 @@ __device__ __forceinline__ void glow_blend(float c[4], const float src[4]) {    
     for (int i = 0; i < 4; ++i) c[i] = src[i] + c[i] * k;
 }
 
-// ---- what the three eye-view kernels share.  A table row is 24 floats (XrFacet's fields in order: ha 0, hb 3, hw 6, hz 9, he 12, the uv
+// ---- the veil and frosted passes (_FROST_VEIL_FRAG, _FROST_GLOW_FRAG, xr_viewer/glsl.py:698-791) on the flat screen's four walls
+// (dibr_xr.h).  Colours are 0..255 as everywhere in this file; no contraction (built with -ffp-contract=off).
+// one GL_LINEAR tap of a uint8 RGB level [h][w][3] in global memory, CLAMP_TO_EDGE; u, v in 0..1 (every index is clamped to the level)
+__device__ __forceinline__ void frost_level(const uint8_t* __restrict__ lev, int w, int h, float u, float v, float o[3]) {
+    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f, x0f = floorf(x), y0f = floorf(y);
+    const float fx = x - x0f, fy = y - y0f;
+    const int x0 = min(max((int)x0f, 0), w - 1), x1 = min(max((int)x0f + 1, 0), w - 1);
+    const int y0 = min(max((int)y0f, 0), h - 1), y1 = min(max((int)y0f + 1, 0), h - 1);
+    const uint8_t* a = lev + ((long)y0 * w + x0) * 3;
+    const uint8_t* b = lev + ((long)y0 * w + x1) * 3;
+    const uint8_t* c = lev + ((long)y1 * w + x0) * 3;
+    const uint8_t* d = lev + ((long)y1 * w + x1) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = lerp2((float)a[k], (float)b[k], (float)c[k], (float)d[k], fx, fy);
+}
+// hash12 (:718-722) in the shader's operation order, every product and sum rounded on its own.  Its argument is an integer cell; the
+// intermediate values stay below (2 * 104) * 104 = 2.2e4, where a float32 ulp is 2e-3: the result is a fixed function of the cell only
+// when every implementation keeps this order, which the CPU float32 emulation (tests/xr_frost_ref.py) does.
+__device__ __forceinline__ float frost_fract(float x) { return x - floorf(x); }
+__device__ __forceinline__ float frost_hash12(float px, float py) {
+    float x = frost_fract(px * 0.1031f), y = frost_fract(py * 0.1031f), z = x;
+    const float d = (x * (y + 33.33f) + y * (z + 33.33f)) + z * (x + 33.33f);
+    x += d; y += d; z += d;
+    return frost_fract((x + y) * z);
+}
+// main() of either program at the mesh's interpolated (v_uv, v_local.z = t): false = discarded (a NaN alpha discards), else
+// src = (colour * alpha in 0..255, alpha).  MODE 1 veil, 2 frosted.  lev0 / lev1: the two levels textureLod mixes (veil: the frame).
+template <int MODE>
+__device__ __forceinline__ bool frost_frag(const XrFrostDev& F, const DibrGeomProj& g, const uint8_t* __restrict__ lev0,
+                                           const uint8_t* __restrict__ lev1, float su, float sv, float t, float src[4]) {
+    const float u = fminf(fmaxf(g.cx + su * g.cw, 0.f), 1.f), v = fminf(fmaxf(g.cy + sv * g.ch, 0.f), 1.f);      // sample_uv
+    const float depth = fminf(fmaxf(t, 0.f), 1.f);
+    float beam = expf(-depth / fmaxf(F.softness, 0.001f));
+    beam = fmaxf(beam, 0.f);
+    const float inv_thick = 1.0f / fmaxf(F.thickness, 0.1f);
+    beam = beam > 0.f ? __builtin_amdgcn_exp2f(inv_thick * __builtin_amdgcn_logf(beam)) : 0.f;      // pow (post.hip's pow01 form)
+    const float edge_dist = fminf(fminf(su, 1.0f - su), fminf(sv, 1.0f - sv));
+    const float e0 = fmaxf(F.inset, 0.0001f);
+    const float edge = 1.0f - smoothstepf(e0, e0 * 4.0f, edge_dist);
+    float c[3];
+    if (MODE == 1) {
+        float alpha = edge * beam * F.alpha * F.intensity;
+        if (!(alpha > 0.002f)) return false;
+        alpha = fminf(alpha, 1.0f);
+        frost_level(lev0, F.w0, F.h0, u, v, c);                                                  // textureLod(.., 0.0)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) src[k] = c[k] * alpha;
+        src[3] = alpha;
+        return true;
+    }
+    float c1[3];
+    frost_level(lev0, F.w0, F.h0, u, v, c);                                                      // textureLod(.., max(u_lod, 0))
+    frost_level(lev1, F.w1, F.h1, u, v, c1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = c[k] * (1.0f - F.lf) + c1[k] * F.lf;
+    const float n = frost_hash12(floorf((u + F.tx) * F.noise_scale), floorf((v + F.ty) * F.noise_scale));
+    const float luma255 = (c[0] * 0.2126f + c[1] * 0.7152f) + c[2] * 0.0722f, luma = luma255 * (1.0f / 255.0f);
+    const float bright = smoothstepf(F.threshold, 1.0f, luma);
+    const float scatter = fmaxf(bright, luma * fminf(fmaxf(F.diffuse, 0.f), 2.0f) * 0.35f);
+    float alpha = edge * beam * scatter * F.alpha * F.intensity * (0.82f + 0.30f * n);
+    if (!(alpha > 0.002f)) return false;
+    alpha = fminf(alpha, 1.0f);
+    const float gain = 0.55f + F.blend * 0.35f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) src[k] = ((c[k] * (1.0f - 0.28f) + luma255 * 0.28f) * gain + c[k] * bright * 0.35f) * alpha;
+    src[3] = alpha;
+    return true;
+}
+
+// ---- what the four eye-view kernels share.  A table row is 24 floats (XrFacet's fields in order: ha 0, hb 3, hw 6, hz 9, he 12, the uv
 // affine 15 .. 20), read through a const float* so that one function serves a global XrFacet and an LDS row of stride XR_LDS_ROW.
 // The block prologue.  It NEVER returns a thread early: in the glow kernels a thread outside its eye image (the other eye is larger,
 // or a side is no multiple of 16) must still reach every barrier.  dibr_xr_kernel, which has none, returns on !inside itself.
@@ -465,13 +534,57 @@ __device__ __forceinline__ void xr_stage_chain(bool need, const uint8_t* __restr
 }
 // The tail of a pixel inside its eye image, _render_eye's order (effects.py:1050-1145) in float: clear; the outer band blended over
 // it where no facet covers the pixel (where one does the screen, drawn with blending off, overwrites the band); the screen at
-// (sa, sb); the inner band's draws blended over the screen, in draw order; alpha_mode; the store.  plane: the outer band's piece is
+// (sa, sb); the inner band's draws blended over the screen, in draw order; the frost kernel's walls blended over whatever is there
+// (a kernel has a glow or walls, never both); alpha_mode; the store.  plane: the outer band's piece is
 // drawn at this pixel, (ga, gb) its point in the screen's coordinates.  N = 0: no glow.
 struct XrDraw { bool on; float a, b; };
-template <int OUT_FMT, class D, int N>
+// The walls of the veil and frosted looks, drawn after the screen with the depth test off (_render_flat_frost_with_uniforms,
+// effects.py:804-814): operator() blends every wall that covers the pixel into c, in draw order, and says whether one drew.
+struct XrNoWalls {
+    static constexpr bool ON = false;
+    __device__ __forceinline__ bool operator()(float*) const { return false; }
+};
+// rows: the eye's four wall rows (dibr_xr.h).  Per wall: the plane point's (a, t); inside the trapezoid |a| <= g(t), 0 <= t <= 1, with
+// clip w > 0 and NDC z in [-1, 1]; the grid cell -- row i from t, column j between the column lines a = (j / 4 - 1) * g(t); the cell's
+// triangle (the strip's order A (s_j, t_i), B (s_j, t_i+1), C (s_j+1, t_i), D (s_j+1, t_i+1) makes B - C the diagonal); s at the
+// point, affine over the triangle in (a, t): ABC: s_j + (a - a_j(t)) / (2 g(t_i)); BCD: s_j+1 - (a_j+1(t) - a) / (2 g(t_i+1)).
+template <int MODE>
+struct XrWalls {
+    static constexpr bool ON = true;
+    const float* __restrict__ rows;
+    float xc, yc;
+    const XrFrostDev& F;
+    const DibrGeomProj& g;
+    const uint8_t* __restrict__ lev0;
+    const uint8_t* __restrict__ lev1;
+    __device__ __forceinline__ bool operator()(float c[4]) const {
+        bool drew = false;
+        for (int k = 0; k < XR_WALLS; ++k) {
+            const float* __restrict__ r = rows + k * XR_ROW_FLOATS;
+            const XrPt p = xr_row_at(r, xc, yc);
+            if (!(p.nw > 0.f && p.z >= -1.0f && p.z <= 1.0f)) continue;
+            const float a = p.na / p.nw, t = p.nb / p.nw, slope = r[15], gt = 1.0f + slope * t;
+            if (!(t >= 0.f && t <= 1.0f && fabsf(a) <= gt)) continue;
+            const int i = min((int)(t * (float)XR_FROST_GRID), XR_FROST_GRID - 1);
+            const int j = min(max((int)floorf((a / gt + 1.0f) * (0.5f * (float)XR_FROST_GRID)), 0), XR_FROST_GRID - 1);
+            const float t1 = (float)(i + 1) * (1.0f / XR_FROST_GRID), g0 = 1.0f + slope * ((float)i * (1.0f / XR_FROST_GRID)), g1 = 1.0f + slope * t1;
+            const float pj = (float)j * (2.0f / XR_FROST_GRID) - 1.0f, pj1 = (float)(j + 1) * (2.0f / XR_FROST_GRID) - 1.0f;
+            const float xb = pj * g1, xcn = pj1 * g0;
+            const bool abc = (xcn - xb) * (t - t1) + (1.0f / XR_FROST_GRID) * (a - xb) <= 0.f;
+            const float s = abc ? (float)j * (1.0f / XR_FROST_GRID) + (a - pj * gt) / (2.0f * g0)
+                                : (float)(j + 1) * (1.0f / XR_FROST_GRID) - (pj1 * gt - a) / (2.0f * g1);
+            const bool s_is_v = r[16] != 0.f;
+            float src[4];
+            if (frost_frag<MODE>(F, g, lev0, lev1, s_is_v ? r[17] : s, s_is_v ? s : r[17], t, src)) { glow_blend(c, src); drew = true; }
+        }
+        return drew;
+    }
+};
+template <int OUT_FMT, class D, int N, class WALLS = XrNoWalls>
 __device__ __forceinline__ void xr_tail(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
                                         const DibrGeomProj& g, const XrEyes& ex, const XrGlowDev& G, const float* __restrict__ lds,
-                                        const XrPix& px, bool covered, float sa, float sb, bool plane, float ga, float gb, const XrDraw* draws) {
+                                        const XrPix& px, bool covered, float sa, float sb, bool plane, float ga, float gb, const XrDraw* draws,
+                                        const WALLS walls = WALLS()) {
     const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
     const long o = px.e.out_off + (((long)px.b * px.e.h + px.y) * px.e.w + px.x) * nch;
     float c[4], src[4];
@@ -481,6 +594,7 @@ __device__ __forceinline__ void xr_tail(const uint8_t* __restrict__ rgb_all, con
             glow_blend(c, src);
             if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
         }
+        if (WALLS::ON && walls(c) && g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
         dibr_store<OUT_FMT>(out_all, o, nch, c);
         return;
     }
@@ -491,6 +605,7 @@ __device__ __forceinline__ void xr_tail(const uint8_t* __restrict__ rgb_all, con
     // (written out, not a loop: unrolled late, the curved kernel's FullDep form took 74 VGPRs for 72 and lost a wave per SIMD)
     if (N > 0 && draws[0].on && glow_frag(lds, G, g, draws[0].a, draws[0].b, true, src)) glow_blend(c, src);
     if (N > 1 && draws[1].on && glow_frag(lds, G, g, draws[1].a, draws[1].b, true, src)) glow_blend(c, src);
+    if (WALLS::ON) walls(c);
     if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
     dibr_store<OUT_FMT>(out_all, o, nch, c);
 }
@@ -530,6 +645,27 @@ dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict
     if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
     const XrDraw inner = {G.mode == 1 && plane, ga, gb};
     xr_tail<OUT_FMT, D, 1>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, &inner);
+}
+
+// d2s_dibr_xr_eyes_frost (flat screen): dibr_xr_kernel with the four walls of the veil (MODE 1) or frosted (MODE 2) look blended after
+// the screen.  No barrier and no LDS: the wall rows are block-uniform global reads as the facet's are; the frosted taps read the two
+// chain levels textureLod(u_lod) mixes from global memory (at the default LOD 5.4 of a 1080p frame 60 x 33 and 30 x 16 texels).
+template <int OUT_FMT, class D, int MODE>
+__global__ void __launch_bounds__(256)
+dibr_xr_frost_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+                     const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrFrostDev F, const uint8_t* __restrict__ levels) {
+    const XrPix px = xr_pix(ex);
+    if (!px.inside) return;
+    const float* __restrict__ tab = (const float*)(tab_all + px.ei * xr_table_rows(D2S_XR_KIND_FROST));
+    const XrHit h = xr_search_all(tab, px.e.nf, px.xc, px.yc);
+    float sa = 0.f, sb = 0.f;
+    if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
+    const uint8_t* __restrict__ frame = rgb_all + (long)px.b * g.H * g.W * 3;
+    const uint8_t* __restrict__ chain = MODE == 2 ? levels + (long)px.b * F.chain_total : nullptr;      // (the veil never reads levels)
+    const XrWalls<MODE> walls = {tab + px.e.nf * XR_ROW_FLOATS, px.xc, px.yc, F, g, (MODE == 2 && F.l0 > 0) ? chain + F.off0 : frame,
+                                 (MODE == 2 && F.l1 > 0) ? chain + F.off1 : frame};
+    xr_tail<OUT_FMT, D, 0, XrWalls<MODE>>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f,
+                                          nullptr, walls);
 }
 
 // d2s_dibr_xr_eyes_glow_curved: the curved screen with its glow (_render_curved_glow, xr_viewer/effects.py:408-474, in _render_eye's
@@ -757,7 +893,12 @@ static int xr_workspace_query(int kind, int n_eyes, uint64_t* bytes) {
 }
 extern "C" int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_PLAIN, n_eyes, bytes); }
 extern "C" int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_GLOW_CURVED, n_eyes, bytes); }
+extern "C" int d2s_dibr_xr_frost_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_FROST, n_eyes, bytes); }
 
+static void xr_plan_result(const XrPlan& pl, d2s_xr_plan_result* res) {
+    *res = d2s_xr_plan_result{sizeof(d2s_xr_plan_result), pl.kind, pl.rows_per_eye, pl.setup_launches, {pl.grid[0], pl.grid[1], pl.grid[2]},
+                              pl.lds_dynamic, pl.lds_static, 0, pl.workspace_bytes, pl.total, {pl.offs[0], pl.offs[1]}};
+}
 extern "C" int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
                                 const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow,
                                 d2s_xr_plan_result* res) {
@@ -766,10 +907,9 @@ extern "C" int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int
     D2S_REQUIRE(entry >= D2S_XR_ENTRY_EYES && entry <= D2S_XR_ENTRY_GLOW_CURVED, "bad entry (D2S_XR_ENTRY_*)");
     D2S_REQUIRE(entry != D2S_XR_ENTRY_EYES || !glow, "d2s_dibr_xr_eyes takes no glow: glow must be NULL with D2S_XR_ENTRY_EYES");
     XrPlan pl;
-    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, pl);
+    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, nullptr, pl);
     if (rc) return rc;
-    *res = d2s_xr_plan_result{sizeof(d2s_xr_plan_result), pl.kind, pl.rows_per_eye, pl.setup_launches, {pl.grid[0], pl.grid[1], pl.grid[2]},
-                              pl.lds_dynamic, pl.lds_static, 0, pl.workspace_bytes, pl.total, {pl.offs[0], pl.offs[1]}};
+    xr_plan_result(pl, res);
     return D2S_OK;
 }
 
@@ -779,8 +919,10 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
     D2S_REQUIRE(workspace, "null pointer (workspace)");
     D2S_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
     D2S_REQUIRE(workspace_bytes >= pl.workspace_bytes, (pl.kind == D2S_XR_KIND_GLOW_CURVED ? "workspace_bytes below d2s_dibr_xr_glow_curved_workspace"
+                                                        : pl.kind == D2S_XR_KIND_FROST     ? "workspace_bytes below d2s_dibr_xr_frost_workspace"
                                                                                            : "workspace_bytes below d2s_dibr_xr_workspace"));
-    D2S_REQUIRE(pl.kind == D2S_XR_KIND_PLAIN || levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
+    if (pl.kind == D2S_XR_KIND_FROST) D2S_REQUIRE(pl.F.mode != 2 || levels, "null pointer (levels: the frosted look reads d2s_mip_chain's output)");
+    else D2S_REQUIRE(pl.kind == D2S_XR_KIND_PLAIN || levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
     D2S_REQUIRE(rgb && depth && out, "null pointer");
     if (check_only) return D2S_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -796,6 +938,8 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
     const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
 #define DIBR_XR(FMT, D) do { \
         if (pl.kind == D2S_XR_KIND_PLAIN) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex); \
+        else if (pl.kind == D2S_XR_KIND_FROST && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 1>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels); \
+        else if (pl.kind == D2S_XR_KIND_FROST) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 2>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels); \
         else if (pl.kind == D2S_XR_KIND_GLOW) hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, levels); \
         else hipLaunchKernelGGL((dibr_xr_glow_curved_kernel<FMT, D>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, pl.Q, levels); } while (0)
     if (out_fmt == D2S_FMT_U8_HWC) { if (pl.up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
@@ -807,10 +951,10 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
 
 int d2s::dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                            const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
-                           void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                           bool check_only) {
+                           void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const d2s_xr_frost* frost,
+                           const uint8_t* levels, void* stream, bool check_only) {
     XrPlan pl;
-    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, pl);
+    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl);
     return rc ? rc : xr_launch(pl, rgb, depth, out, out_fmt, workspace, workspace_bytes, levels, stream, check_only);
 }
 
@@ -818,7 +962,7 @@ extern "C" int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, 
                                 const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
                                 int out_fmt, void* workspace, uint64_t workspace_bytes, void* stream) {
     return dibr_xr_entry_any(D2S_XR_ENTRY_EYES, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                             workspace_bytes, nullptr, nullptr, stream, false);
+                             workspace_bytes, nullptr, nullptr, nullptr, stream, false);
 }
 
 extern "C" int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
@@ -826,7 +970,7 @@ extern "C" int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int
                                      int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
                                      void* stream) {
     return dibr_xr_entry_any(D2S_XR_ENTRY_GLOW, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                             workspace_bytes, glow, levels, stream, false);
+                             workspace_bytes, glow, nullptr, levels, stream, false);
 }
 
 extern "C" int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
@@ -834,5 +978,26 @@ extern "C" int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* dep
                                             const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
                                             uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
     return dibr_xr_entry_any(D2S_XR_ENTRY_GLOW_CURVED, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                             workspace_bytes, glow, levels, stream, false);
+                             workspace_bytes, glow, nullptr, levels, stream, false);
+}
+
+// The veil and frosted looks of the flat screen (xr_viewer/effects.py:789-857): xr_plan's fourth entry and its host-only query.
+extern "C" int d2s_dibr_xr_eyes_frost(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                      const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                      int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                      void* stream) {
+    return dibr_xr_entry_any(XR_ENTRY_FROST, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, nullptr, frost, levels, stream, false);
+}
+
+extern "C" int d2s_dibr_xr_frost_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                      const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
+                                      d2s_xr_plan_result* res) {
+    D2S_REQUIRE(res, "null pointer (res)");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
+    XrPlan pl;
+    const int rc = xr_plan(XR_ENTRY_FROST, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, nullptr, frost, pl);
+    if (rc) return rc;
+    xr_plan_result(pl, res);
+    return D2S_OK;
 }

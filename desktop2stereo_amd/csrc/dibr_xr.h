@@ -315,23 +315,123 @@ inline void xr_curved_table(const XrSurface& S, const XrCurvedPieces& P, int mod
     }
 }
 
-// ---- the eye views' plan: everything the three entries decide from the arguments that are no device pointers ----
+// ---- the veil and frosted looks of the flat screen (d2s_dibr_xr_eyes_frost; _render_flat_frost_with_uniforms, _frost_front_layout,
+// _build_flat_frost_verts, xr_viewer/effects.py:102-187, 789-857) ----
+// Four planar walls in the screen's local frame (x, y in half-sizes, z in front_depth), from a screen edge (t = 0) to the matching edge
+// of the front rectangle (t = 1): a mesh vertex is (px * (1 + t * (fx - 1)), py * (1 + t * (fy - 1)), t).  Wall k's row is an XrFacet
+// whose own coordinates are a = the local coordinate along the edge, signed so that it grows with the mesh's s (x for top and bottom,
+// -y for left and right), and b = t: origin the edge's midpoint, p10 = one half-size along the edge, p01 = the front edge's midpoint.
+// ha, hb, hw, hz are as a facet's; he is not read.  The uv fields carry what the mesh walk needs instead of an affine map:
+//   u0 = k, the slope of g(t) = 1 + k * t (k = fx - 1 for top and bottom, fy - 1 for left and right): column line j of the 8 x 8 grid
+//        is a = (j / 4 - 1) * g(t);   ua = 0: s is v_uv.x, 1: s is v_uv.y;   ub = the other, constant component of v_uv (0 or 1).
+constexpr int XR_WALLS = 4, XR_FROST_GRID = 8;          // _FLAT_FROST_N = _FLAT_FROST_M = 8 (effects.py:140-141)
+constexpr int XR_ENTRY_FROST = 3;                        // xr_plan's fourth entry: d2s_dibr_xr_eyes_frost (d2s_dibr_xr_plan knows 0..2)
+// The uniforms the two setters hand GL (effects.py:651-718), rounded to float once, and the two chain levels textureLod(u_lod) mixes
+struct XrFrostDev {
+    int mode;                                     // 1 veil, 2 frosted
+    float inset, intensity, alpha, softness, thickness;
+    float threshold, noise_scale, blend, diffuse, tx, ty;      // (tx, ty) = u_time * (0.011, -0.007)
+    int l0, l1;                                   // floor(lambda) and the next level, lambda = clamp(max(u_lod, 0), 0, q); level 0 is the frame
+    float lf;                                     // lambda - l0
+    int w0, h0, w1, h1;
+    uint32_t off0, off1, chain_total;             // byte offsets within a frame's chain (unused for level 0)
+};
+struct XrFrostLayout { double front_depth, front_half_w, front_half_h, fx, fy; };
+
+inline bool xr_frost_on(const d2s_xr_frost* f) {      // the reference's early returns (effects.py:822-857); NaN was refused before
+    return f && f->mode != 0 && f->intensity > 0.0 && !(f->mode == 1 && f->alpha <= 0.002);
+}
+// What d2s_dibr_xr_eyes_frost refuses about the frost, after xr_screen_check has accepted the screen
+inline int xr_frost_check(const d2s_xr_screen* s, const d2s_xr_frost* f) {
+    if (!f) return D2S_OK;
+    D2S_REQUIRE(f->struct_size == sizeof(d2s_xr_frost), "d2s_xr_frost.struct_size must be sizeof(d2s_xr_frost) = 120");
+    D2S_REQUIRE(f->mode >= 0 && f->mode <= 2, "bad frost mode (0 off, 1 veil, 2 frosted)");
+    if (f->mode == 0) return D2S_OK;
+    const double v[14] = {f->head[0], f->head[1], f->head[2], f->intensity, f->alpha, f->edge_inset, f->beam_softness, f->beam_thickness,
+                          f->lod, f->threshold, f->noise_scale, f->blend, f->diffuse, f->time};
+    D2S_REQUIRE(xr_finite(v, 14), "the frost's fields must be finite");
+    D2S_REQUIRE(f->noise_scale >= 0.0 && f->lod >= 0.0, "frost noise_scale and lod must be >= 0");
+    if (!xr_frost_on(f)) return D2S_OK;
+    if (s->curve != D2S_XR_CURVE_FLAT) {
+        set_error("unsupported: the frost and veil of a curved screen (a mesh of its own in the reference, _build_curved_frost_verts) "
+                  "are not built; curve must be 0 with frost on");
+        return D2S_E_UNSUPPORTED;
+    }
+    D2S_REQUIRE(s->normal_offset == 0.0, "normal_offset must be 0 with frost on (the walls start at the screen's own plane)");
+    return D2S_OK;
+}
+// _frost_front_layout:120-128 and _build_flat_frost_verts:146-149 in double precision
+inline XrFrostLayout xr_frost_layout(const d2s_xr_screen* s, const d2s_xr_frost* f) {
+    double R[3][3], c[3], hl[3];
+    xr_basis(s, R, c);
+    for (int j = 0; j < 3; ++j) hl[j] = R[0][j] * (f->head[0] - c[0]) + R[1][j] * (f->head[1] - c[1]) + R[2][j] * (f->head[2] - c[2]);
+    XrFrostLayout L;
+    L.front_depth = fmax(fmax(hl[2] + 0.55, s->distance + 0.35), 0.75);
+    L.front_half_w = fmax(fmax(s->width * 0.5, fabs(hl[0]) + 0.65), 0.65);
+    L.front_half_h = fmax(fmax(s->height * 0.5, fabs(hl[1]) + 0.65), 0.65);
+    L.fx = L.front_half_w / fmax(s->width * 0.5, 1e-6); L.fy = L.front_half_h / fmax(s->height * 0.5, 1e-6);
+    return L;
+}
+// One eye's four wall rows, in draw order: top, bottom, left, right (_build_flat_frost_verts:179-186)
+inline void xr_frost_walls(const d2s_xr_screen* s, const XrFrostLayout& L, const double vp[16], int w, int h, XrFacet* out) {
+    double R[3][3], c[3];
+    xr_basis(s, R, c);
+    const double sx = s->width / 2.0, sy = s->height / 2.0;      // _screen_effect_model(width, height, z_scale = front_depth)
+    auto world = [&](double x, double y, double z) {
+        XrVert v{};
+        for (int i = 0; i < 3; ++i) v.p[i] = c[i] + R[i][0] * sx * x + R[i][1] * sy * y + R[i][2] * L.front_depth * z;
+        return v;
+    };
+    for (int k = 0; k < XR_WALLS; ++k) {
+        const bool horiz = k < 2;                              // top, bottom: s runs along x; left, right: along -y (TL -> BL)
+        const double side = (k == 0 || k == 3) ? 1.0 : -1.0;  // the edge's own coordinate: y = +1 top, -1 bottom; x = -1 left, +1 right
+        const double f_ac = horiz ? L.fy : L.fx, f_al = horiz ? L.fx : L.fy;
+        const XrVert p00 = horiz ? world(0, side, 0) : world(side, 0, 0);
+        const XrVert p10 = horiz ? world(1, side, 0) : world(side, -1, 0);
+        const XrVert p01 = horiz ? world(0, side * f_ac, 1) : world(side * f_ac, 0, 1);
+        xr_facet_row(p00, p10, p01, vp, w, h, out[k]);
+        out[k].u0 = (float)(f_al - 1.0); out[k].ua = horiz ? 0.f : 1.f; out[k].ub = (k == 1 || k == 3) ? 1.f : 0.f;    }
+}
+// H x W: the frame (and its chain, frosted only)
+inline void xr_frost_dev(const d2s_xr_frost* f, int H, int W, XrFrostDev& F) {
+    F = XrFrostDev{};
+    F.mode = f->mode;
+    F.inset = (float)f->edge_inset; F.intensity = (float)f->intensity; F.alpha = (float)f->alpha;
+    F.softness = (float)f->beam_softness; F.thickness = (float)f->beam_thickness;
+    F.w0 = F.w1 = W; F.h0 = F.h1 = H;
+    if (f->mode != 2) return;
+    F.threshold = (float)f->threshold; F.noise_scale = (float)f->noise_scale; F.blend = (float)f->blend; F.diffuse = (float)f->diffuse;
+    const float t = (float)f->time;
+    F.tx = t * 0.011f; F.ty = -t * 0.007f;
+    MipShape ms;
+    mip_shape(H, W, ms);
+    const float lam = fminf(fmaxf((float)f->lod, 0.f), (float)ms.q), l0f = floorf(lam);
+    F.l0 = (int)l0f; F.l1 = F.l0 + 1 < ms.q ? F.l0 + 1 : ms.q; F.lf = lam - l0f;
+    F.w0 = ms.w[F.l0]; F.h0 = ms.h[F.l0]; F.w1 = ms.w[F.l1]; F.h1 = ms.h[F.l1];
+    F.off0 = ms.off[F.l0]; F.off1 = ms.off[F.l1]; F.chain_total = ms.total;
+}
+
+// ---- the eye views' plan: everything the four entries decide from the arguments that are no device pointers ----
 struct XrEyeDev { int w, h, eye, nf; long out_off; };      // out_off: the eye image's first element in out; its table: eye index * rows_per_eye
 struct XrEyes { XrEyeDev e[2]; int n; float clear[4]; };
 // The curved glow's kernel keeps the eye's rows (padded to 25 floats) and the 49 seams in static LDS
 constexpr int XR_LDS_ROW = XR_ROW_FLOATS + 1;
 constexpr uint32_t XR_CURVED_LDS = (XR_PIECES * XR_LDS_ROW + XR_SEAMS * 3) * sizeof(float);
-// rows an eye's table occupies in the workspace (d2s_dibr_xr_workspace, d2s_dibr_xr_glow_curved_workspace, the kernels' stride)
-constexpr int xr_table_rows(int kind) { return kind == D2S_XR_KIND_GLOW_CURVED ? XR_PIECES : XR_MAX_FACETS; }
+// rows an eye's table occupies in the workspace (d2s_dibr_xr_workspace, d2s_dibr_xr_glow_curved_workspace, d2s_dibr_xr_frost_workspace,
+// the kernels' stride).  FROST: the screen's rows, then the four wall rows directly after the rows written (row nf .. nf + 3)
+constexpr int xr_table_rows(int kind) {
+    return kind == D2S_XR_KIND_GLOW_CURVED ? XR_PIECES : kind == D2S_XR_KIND_FROST ? XR_MAX_FACETS + XR_WALLS : XR_MAX_FACETS;
+}
 
 struct XrPlan {
     int kind;                                     // D2S_XR_KIND_*: which kernel draws
     DibrGeomProj g;
     XrEyes ex;
-    XrGlowDev G;                                  // kind != PLAIN
+    XrGlowDev G;                                  // kind GLOW, GLOW_CURVED
+    XrFrostDev F;                                 // kind == FROST
     XrCurvedDev Q;                                // kind == GLOW_CURVED
     bool up;                                      // depth is not at the frame's resolution: the UpDep sampler
-    int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48) or XR_PIECES
+    int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48), XR_PIECES, or FROST: facets + 4
     XrFacet rows[2][XR_PIECES];
     int setup_launches;                           // all eyes': XR_CHUNK_FACETS rows travel in one launch's arguments
     unsigned grid[3];
@@ -340,10 +440,11 @@ struct XrPlan {
     uint64_t offs[2], total;                      // the out layout (xr_out_layout)
 };
 
-// entry: D2S_XR_ENTRY_*, the public call that asks.  EYES takes no glow (the caller passes none); GLOW refuses a curved screen with
-// glow on.  Every refusal of the three entries that needs no device pointer, in their order; no HIP call.
+// entry: D2S_XR_ENTRY_* or XR_ENTRY_FROST, the public call that asks.  EYES takes no glow (the caller passes none); GLOW refuses a curved
+// screen with glow on; FROST takes the frost and no glow.  Every refusal of the four entries that needs no device pointer, in their
+// order; no HIP call.
 inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, const d2s_xr_screen* screen,
-                   const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, XrPlan& pl) {
+                   const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, const d2s_xr_frost* frost, XrPlan& pl) {
     D2S_REQUIRE(p, "null pointer");
     int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
     if (rc) return rc;
@@ -357,13 +458,20 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     if (rc) return rc;
     rc = xr_glow_check(screen, glow, entry == D2S_XR_ENTRY_GLOW_CURVED);
     if (rc) return rc;
-    const bool glow_on = glow && glow->mode != 0;
+    rc = xr_frost_check(screen, entry == XR_ENTRY_FROST ? frost : nullptr);
+    if (rc) return rc;
+    const bool glow_on = glow && glow->mode != 0, frost_on = entry == XR_ENTRY_FROST && xr_frost_on(frost);
+    D2S_REQUIRE(!(frost_on && frost->mode == 2) || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192),
+                "frame must be 2 .. 8192 on a side with the frosted look on (d2s_mip_chain's range)");
     D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
-    pl.kind = !glow_on ? D2S_XR_KIND_PLAIN : screen->curve == D2S_XR_CURVE_FLAT ? D2S_XR_KIND_GLOW : D2S_XR_KIND_GLOW_CURVED;
+    pl.kind = frost_on ? D2S_XR_KIND_FROST : !glow_on ? D2S_XR_KIND_PLAIN : screen->curve == D2S_XR_CURVE_FLAT ? D2S_XR_KIND_GLOW : D2S_XR_KIND_GLOW_CURVED;
     const bool curved = pl.kind == D2S_XR_KIND_GLOW_CURVED;
     xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, pl.offs, &pl.total);
     pl.G = XrGlowDev{};
     pl.Q = XrCurvedDev{};
+    pl.F = XrFrostDev{};
+    XrFrostLayout L{};
+    if (frost_on) { xr_frost_dev(frost, H, W, pl.F); L = xr_frost_layout(screen, frost); }
     XrSurface S;
     xr_surface(screen, S);
     XrCurvedPieces P;
@@ -401,7 +509,7 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
     g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
     pl.up = dh != H || dw != W;
-    pl.rows_per_eye = curved ? XR_PIECES : S.n;
+    pl.rows_per_eye = curved ? XR_PIECES : S.n + (frost_on ? XR_WALLS : 0);
     pl.ex = XrEyes{};
     pl.ex.n = n_eyes;
     for (int k = 0; k < 4; ++k) pl.ex.clear[k] = screen->clear[k];
@@ -411,17 +519,19 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
         mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
         if (curved) xr_curved_table(S, P, glow->mode, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i]);
         else xr_facets(S, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i]);
+        if (frost_on) xr_frost_walls(screen, L, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i] + S.n);
     }
-    pl.setup_launches = n_eyes * cdiv(pl.rows_per_eye, XR_CHUNK_FACETS);               // per eye: 1 (flat), 2 (curved), 3 (curved glow)
+    pl.setup_launches = n_eyes * cdiv(pl.rows_per_eye, XR_CHUNK_FACETS);               // per eye: 1 (flat, frost), 2 (curved), 3 (curved glow)
     pl.grid[0] = cdiv(mw, 16); pl.grid[1] = cdiv(mh, 16); pl.grid[2] = n_eyes * batch;
     pl.workspace_bytes = (uint64_t)n_eyes * xr_table_rows(pl.kind) * sizeof(XrFacet);
     return D2S_OK;
 }
 
-// The three entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
+// The four entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
 // every refusal, nothing launched (the view pipelines ask before they start the model).
 int dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                       const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
-                      void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream, bool check_only);
+                      void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const d2s_xr_frost* frost, const uint8_t* levels, void* stream,
+                      bool check_only);
 
 }  // namespace d2s

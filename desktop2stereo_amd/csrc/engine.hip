@@ -1192,7 +1192,7 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
                                 const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
                                 const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
                                 void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                                int entry) {
+                                int entry, const d2s_xr_frost* frost = nullptr) {
     D2S_REQUIRE(frames && pp && dp && out && screen && eyes, "null pointer");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     uint64_t offs[2], total = 0;
@@ -1202,7 +1202,7 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
     auto warp = [&](bool check_only) {
         return dibr_xr_entry_any(entry, frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                                 workspace_bytes, glow, levels, stream, check_only);
+                                 workspace_bytes, glow, frost, levels, stream, check_only);
     };
     RC(warp(true));
     D2S_ON_DEVICE(e->device);
@@ -1241,6 +1241,17 @@ extern "C" int d2s_view_pipeline_xr_glow_curved_streams(d2s_engine* e, const uin
                                                         const d2s_xr_glow* glow, const uint8_t* levels, void* stream) {
     return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
                                 out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, D2S_XR_ENTRY_GLOW_CURVED);
+}
+
+// the engine's pipeline up to the EMA step, then d2s_dibr_xr_eyes_frost on the model-resolution depth
+extern "C" int d2s_view_pipeline_xr_frost_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                                  int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                                  const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                                  const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                                  void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                                  void* stream) {
+    return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
+                                out_fmt, depth_full, workspace, workspace_bytes, nullptr, levels, stream, XR_ENTRY_FROST, frost);
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

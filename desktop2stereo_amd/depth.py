@@ -324,7 +324,8 @@ def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_tempor
     as the reference's _render_eye draws it (xr_viewer/effects.py:1023-1137).  Returns one device tensor per eye, [B,h,w,4|3].
     crop: None, (x, y, w, h) in uv, or "auto" (the MovieCrop of the first row's stream slot: the screen shows one crop).  The uniforms
     are the configured parameters', with the OpenXR screen's corner_radius (0.03) and frag_color.a kept (alpha="rgba") for the
-    compositor.  Glow, frost, border, controllers and environment stay with the caller."""
+    compositor.  The glow: xr_eye_views_glow; the flat screen's veil and frosted looks: xr_eye_views_frost.  The border, controllers
+    and environment stay with the caller."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -350,8 +351,8 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
     xr_viewer/effects.py:476-585) and around a curved one (_render_curved_glow, effects.py:408-474; an eye outside the convex region the
     curved screen bounds, xr.XrScreen.eye_inside, is refused).  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
     frames' colour mip chain (ops.mip_chain); None builds it here, every call -- the reference refreshes its own every
-    _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  Frost, veil, border, controllers and
-    environment stay with the caller."""
+    _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  The flat screen's veil and frosted looks:
+    xr_eye_views_frost.  The border, controllers and environment stay with the caller."""
     from . import xr as _xr
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
@@ -375,6 +376,39 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
     run = eng.view_pipeline_xr_glow if getattr(screen, "curve", "flat") == "flat" else eng.view_pipeline_xr_glow_curved
     return run(t, p, dp, screen, eyes, glow, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
                streams=streams)
+
+
+def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=None, multiplier=1.0, time=0.0, crop=None, corner_radius=0.03,
+                       use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
+    """xr_eye_views with the reference's "veil" or "frosted" look around the FLAT screen drawn in the same launch
+    (_render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857).  frost: "veil" | "frosted" (the reference's defaults for
+    head, multiplier = _glow_intensity_multiplier and time) | an xr.XrFrost.  levels: the frames' colour mip chain (ops.mip_chain) for
+    "frosted"; None builds it here, every call.  A curved screen's frost, the border, controllers and environment stay with the caller."""
+    from . import xr as _xr
+    p = _state["params"]
+    t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+    t = t.to(device=_device())
+    B, H, W, _ = t.shape
+    h, w, _s = engine_shape(H, W, p.depth_resolution, _state["cfg"].patch, p.square_input)
+    if B > _state["max_batch"]:
+        raise _lib.D2SError(f"batch {B} > configured max_batch {_state['max_batch']}")
+    eng = _ensure_engine_built(h, w, _fp8_first_inputs(t, (h, w)))
+    if isinstance(crop, str):
+        if crop != "auto":
+            raise ValueError('crop must be None, (x, y, w, h) or "auto"')
+        mc = movie_crop(0 if streams is None else int(streams[0]))
+        mc.update(t[0])
+        crop = tuple(mc.crop_uv)
+    if isinstance(frost, str):
+        if frost not in ("veil", "frosted"):
+            raise ValueError('frost must be "veil", "frosted" or an xr.XrFrost')
+        hd = (0.0, 0.0, 0.0) if head is None else tuple(head)
+        frost = _xr.XrFrost.veil(hd, multiplier) if frost == "veil" else _xr.XrFrost.frosted(hd, multiplier, time)
+    if levels is None and frost.mode == "frosted" and frost.draws():
+        levels = ops.mip_chain(t)
+    dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
+    return eng.view_pipeline_xr_frost(t, p, dp, screen, eyes, frost, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
+                                      want_depth=want_depth, streams=streams)
 
 
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,

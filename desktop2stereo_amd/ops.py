@@ -401,7 +401,8 @@ _XR_WS: Dict[Tuple, torch.Tensor] = {}
 # Engine._view_pipeline_xr's entry: (C name, the Python method's name for messages, the workspace size query)
 _XR_PIPELINES = {"eyes": ("d2s_view_pipeline_xr_streams", "view_pipeline_xr", "d2s_dibr_xr_workspace"),
                  "glow": ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow", "d2s_dibr_xr_workspace"),
-                 "glow_curved": ("d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_glow_curved_workspace")}
+                 "glow_curved": ("d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_glow_curved_workspace"),
+                 "frost": ("d2s_view_pipeline_xr_frost_streams", "view_pipeline_xr_frost", "d2s_dibr_xr_frost_workspace")}
 
 
 def _xr_args(screen, eyes):
@@ -480,10 +481,11 @@ def mip_chain(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
 
 
 def _xr_glow_args(glow, levels, B: int, H: int, W: int, device, who: str):
-    """(d2s_xr_glow or None, the chain's pointer or None) of an xr.XrGlow (or the struct, or None = off) and mip_chain's result."""
+    """(d2s_xr_glow or None, the chain's pointer or None) of an xr.XrGlow (or the struct, or None = off) and mip_chain's result.
+    An xr.XrFrost (d2s_xr_frost) travels the same way."""
     if glow is None:
         return None, None
-    gs = glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
+    gs = glow if isinstance(glow, (_lib.XrGlow, _lib.XrFrost)) else glow.c_struct()
     if levels is None:
         return gs, None                                   # (the library refuses a missing chain with glow on)
     _need_cuda(levels, "levels")
@@ -510,6 +512,32 @@ def dibr_xr_eyes_glow_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_li
     caller-kept uint8 device tensor of d2s_dibr_xr_glow_curved_workspace bytes."""
     return _dibr_xr_call("d2s_dibr_xr_eyes_glow_curved", "d2s_dibr_xr_glow_curved_workspace", "dibr_xr_eyes_glow_curved", frames, depth, dp,
                          screen, eyes, crop, out_u8, out, workspace, (glow, levels))
+
+
+def dibr_xr_eyes_frost(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, frost, levels=None, crop=None,
+                       out_u8: bool = True, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> list:
+    """dibr_xr_eyes with the reference's "veil" or "frosted" look around the flat screen in the same launch (d2s_dibr_xr_eyes_frost;
+    reference _render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857): frost = xr.XrFrost (None, mode "off", intensity
+    <= 0 or a veil of alpha <= 0.002: exactly dibr_xr_eyes).  levels = mip_chain(frames) for "frosted"; the veil reads the frame alone.
+    A curved screen with frost on is refused.  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_frost_workspace bytes."""
+    return _dibr_xr_call("d2s_dibr_xr_eyes_frost", "d2s_dibr_xr_frost_workspace", "dibr_xr_eyes_frost", frames, depth, dp, screen, eyes, crop,
+                         out_u8, out, workspace, (frost, levels))
+
+
+def dibr_xr_frost_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, frost, crop=None,
+                       out_u8: bool = True) -> dict:
+    """dibr_xr_plan for dibr_xr_eyes_frost (d2s_dibr_xr_frost_plan; host code, no GPU): kind "plain" or "frost", and the same fields."""
+    sc, ea = _xr_args(screen, eyes)
+    fs = None if frost is None else frost if isinstance(frost, _lib.XrFrost) else frost.c_struct()
+    r = _lib.XrPlanResult()
+    r.struct_size = C.sizeof(_lib.XrPlanResult)
+    check(_lib.load().d2s_dibr_xr_frost_plan(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
+                                             _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
+                                             FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None, C.byref(r)),
+          "d2s_dibr_xr_frost_plan")
+    return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
+            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
+            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
 
 
 def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow_levels=None) -> list:
@@ -909,6 +937,16 @@ class Engine:
         if glow is None:
             raise ValueError("view_pipeline_xr_glow_curved: glow must be an xr.XrGlow (mode \"off\" for none)")
         return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, "glow_curved")
+
+    def view_pipeline_xr_frost(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, frost, levels=None,
+                               crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
+                               out: Optional[torch.Tensor] = None, streams=None):
+        """view_pipeline_xr with the veil or frosted look around the flat screen (d2s_view_pipeline_xr_frost_streams): frost =
+        xr.XrFrost, levels = mip_chain(frames) for "frosted" (the caller's, as view_pipeline_xr_glow's).  Bit-identical to
+        pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_frost."""
+        if frost is None:
+            raise ValueError("view_pipeline_xr_frost: frost must be an xr.XrFrost (mode \"off\" for none)")
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels, "frost")
 
     def close(self):
         if getattr(self, "_h", None):

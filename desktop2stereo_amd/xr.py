@@ -172,6 +172,106 @@ class XrGlow:
                     u_glow_inv_range=1.0 / max(rng / max(glow_w, glow_h), 1e-6), u_glow_inner=inner_uv)
 
 
+FROST_GRID = 8                             # _FLAT_FROST_N = _FLAT_FROST_M (effects.py:140-141)
+
+
+@dataclass
+class XrFrost:
+    """The reference's "veil" and "frosted" looks around the flat screen (include/d2s.h d2s_xr_frost): four translucent walls from the
+    screen's edges towards the viewer, blended over the eye image after the screen.  mode "veil" | "frosted" | "off"; head: the head
+    position in world space; intensity: ALREADY multiplied by max(_glow_intensity_multiplier, 0).  The other fields are the uniforms of
+    _set_frost_veil_uniforms / _set_frost_uniform_values (xr_viewer/effects.py:651-718); veil() and frosted() carry the reference's
+    defaults (xr_viewer/implementation.py:354-366).  The host helpers restate the reference's geometry in float64 for callers and
+    tests; the library forms the same numbers itself from the struct."""
+    mode: str = "veil"
+    head: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    intensity: float = 1.5
+    alpha: float = 1.0
+    edge_inset: float = 0.02
+    beam_softness: float = 0.34
+    beam_thickness: float = 3.0
+    lod: float = 5.4
+    threshold: float = 0.46
+    noise_scale: float = 54.0
+    blend: float = 1.35
+    diffuse: float = 0.85
+    time: float = 0.0
+
+    @classmethod
+    def veil(cls, head=(0.0, 0.0, 0.0), multiplier: float = 1.0, **kw) -> "XrFrost":
+        """_render_frost_veil's defaults: intensity 1.5 * multiplier, alpha 1, inset 0.02, softness 0.34, thickness 3."""
+        return cls(**{**dict(mode="veil", head=tuple(head), intensity=1.5 * max(float(multiplier), 0.0)), **kw})
+
+    @classmethod
+    def frosted(cls, head=(0.0, 0.0, 0.0), multiplier: float = 1.0, time: float = 0.0, **kw) -> "XrFrost":
+        """_render_frost_glow's defaults: intensity 1 * multiplier, alpha 0.42, inset 0.045, thickness 1.6, LOD 5.4, threshold 0.46,
+        noise scale 54, blend 1.35, diffuse 0.85."""
+        return cls(**{**dict(mode="frosted", head=tuple(head), intensity=1.0 * max(float(multiplier), 0.0), alpha=0.42, edge_inset=0.045,
+                             beam_thickness=1.6, time=float(time)), **kw})
+
+    def c_struct(self) -> "_lib.XrFrost":
+        if self.mode not in _lib.XR_FROST:
+            raise ValueError(f"frost mode must be one of {list(_lib.XR_FROST)}")
+        if len(self.head) != 3:
+            raise ValueError("head must be (x, y, z)")
+        return _lib.XrFrost(C.sizeof(_lib.XrFrost), _lib.XR_FROST[self.mode], (C.c_double * 3)(*[float(v) for v in self.head]),
+                            float(self.intensity), float(self.alpha), float(self.edge_inset), float(self.beam_softness),
+                            float(self.beam_thickness), float(self.lod), float(self.threshold), float(self.noise_scale), float(self.blend),
+                            float(self.diffuse), float(self.time))
+
+    def draws(self) -> bool:
+        """Whether the walls are drawn at all (the reference's early returns, effects.py:822-857): otherwise the call is dibr_xr_eyes."""
+        return self.mode != "off" and self.intensity > 0.0 and not (self.mode == "veil" and self.alpha <= 0.002)
+
+    def layout(self, screen: "XrScreen") -> Tuple[float, float, float]:
+        """(front_depth, front_half_w, front_half_h) of _frost_front_layout (effects.py:120-128), without its rounded cache key."""
+        R, centre = screen.basis()
+        hl = R[:3, :3].T @ (np.asarray(self.head, np.float64) - centre)
+        return (max(float(hl[2]) + 0.55, float(screen.distance) + 0.35, 0.75),
+                max(float(screen.width) * 0.5, abs(float(hl[0])) + 0.65, 0.65),
+                max(float(screen.height) * 0.5, abs(float(hl[1])) + 0.65, 0.65))
+
+    def model_mat4(self, screen: "XrScreen") -> np.ndarray:
+        """_screen_effect_model(width, height, z_scale=front_depth): the walls' local frame -> world."""
+        R, centre = screen.basis()
+        T = np.eye(4)
+        T[:3, 3] = centre
+        return T @ R @ np.diag([screen.width / 2.0, screen.height / 2.0, self.layout(screen)[0], 1.0])
+
+    def wall_verts(self, screen: "XrScreen") -> np.ndarray:
+        """[4, 158, 5] = x y t u v: the four TRIANGLE_STRIPs of _build_flat_frost_verts (effects.py:145-187) in draw order top, bottom,
+        left, right, in the walls' local frame -- 8 depth rows of 2 * 9 vertices, stitched with 2 degenerate vertices each."""
+        _, fhw, fhh = self.layout(screen)
+        fx, fy = fhw / max(screen.width * 0.5, 1e-6), fhh / max(screen.height * 0.5, 1e-6)
+        n = FROST_GRID
+        out = []
+        for (ax, ay, uva, bx, by, uvb) in ((-1, 1, (0, 0), 1, 1, (1, 0)), (-1, -1, (0, 1), 1, -1, (1, 1)), (-1, 1, (0, 0), -1, -1, (0, 1)),
+                                           (1, 1, (1, 0), 1, -1, (1, 1))):
+            def vtx(s, t):
+                px, py = ax + s * (bx - ax), ay + s * (by - ay)
+                return [px + t * (px * fx - px), py + t * (py * fy - py), t, uva[0] + s * (uvb[0] - uva[0]), uva[1] + s * (uvb[1] - uva[1])]
+            wall, prev_last = [], None
+            for i in range(n):
+                row = []
+                for j in range(n + 1):
+                    row += [vtx(j / n, i / n), vtx(j / n, (i + 1) / n)]
+                if prev_last is not None:
+                    wall += [prev_last, row[0]]
+                wall += row
+                prev_last = row[-1]
+            out.append(wall)
+        return np.array(out, np.float64)
+
+    def uniforms(self, screen: "XrScreen" = None, crop=(0.0, 0.0, 1.0, 1.0)) -> dict:
+        """What the mode's setter hands its program (effects.py:651-718): the veil's five, frosted's eleven, and u_source_crop."""
+        u = dict(u_source_crop=tuple(float(v) for v in crop), u_edge_inset=float(self.edge_inset), u_intensity=float(self.intensity),
+                 u_frost_alpha=float(self.alpha), u_beam_softness=float(self.beam_softness), u_beam_thickness=float(self.beam_thickness))
+        if self.mode == "frosted":
+            u.update(u_lod=float(self.lod), u_threshold=float(self.threshold), u_noise_scale=float(self.noise_scale),
+                     u_frost_blend=float(self.blend), u_diffuse_scatter=float(self.diffuse), u_time=float(self.time))
+        return u
+
+
 def glow_range_m(screen: XrScreen, head=None, width_m: float = 0.75, ref_screen: float = 2.4) -> float:
     """_glow_range_m (xr_viewer/effects.py:280-312) without its rounded-key cache: the glow's reach in metres, growing with the
     screen's longer side (rounded to centimetres, as the reference's key rounds it) and with the head's distance from the screen's

@@ -484,7 +484,8 @@ int d2s_mip_chain(const uint8_t* rgb, int batch, int H, int W, uint8_t* levels, 
  *   level, bilinear within a level, CLAMP_TO_EDGE (xr_viewer/frame.py:39-40).  The glow reads LOD 7 .. 10 only.
  *   NOT reproduced: with glow on the reference also gives the colour texture LINEAR_MIPMAP_LINEAR (frame.py:34, effects.py:601-608),
  *   so ITS screen pass is trilinear where the screen is minified.  That filter needs implicit derivatives and is driver-dependent; the
- *   screen pass here stays GL_LINEAR, as d2s_dibr_xr_eyes has it.  Frost, veil and border stay with the caller.
+ *   screen pass here stays GL_LINEAR, as d2s_dibr_xr_eyes has it.  The flat screen's veil and frosted looks: d2s_dibr_xr_eyes_frost
+ *   below; the border stays with the caller.
  * Refused, nothing launched, out untouched: D2S_E_UNSUPPORTED: screen->curve != 0 with mode != 0 (the curved glow is a band mesh of
  * ~500 quads, _build_curved_glow_band_verts: d2s_dibr_xr_eyes_glow_curved below draws it).  D2S_E_INVALID: normal_offset != 0 with mode != 0 (the reference offsets the screen only
  * under a room model, which switches the planar glow off); range_m <= 0 or non-finite; inner_edge_fraction < 0 or non-finite; mode
@@ -518,8 +519,8 @@ int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw
  * curvature; D2S_E_INVALID: normal_offset != 0; D2S_E_UNSUPPORTED: an eye (the null space of vp's x, y and w rows) that does not lie
  * on the inner side of all 50 outer piece planes by 1e-4 of the arc's radius -- a viewer behind the screen or beyond an end of the arc.
  * There translucent pieces overlap and would have to be blended in draw order: an ordered multi-hit kernel, not built.  Also
- * D2S_E_UNSUPPORTED: a frame of 8192 x 8192 (its coarse levels and the piece table exceed 64 KB of LDS).  Frost, veil, border and the
- * trilinear screen pass stay with the caller, as above. */
+ * D2S_E_UNSUPPORTED: a frame of 8192 x 8192 (its coarse levels and the piece table exceed 64 KB of LDS).  The curved screen's frost and
+ * veil (_build_curved_frost_verts), the border and the trilinear screen pass stay with the caller. */
 int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes);
 int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                                  const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
@@ -557,6 +558,58 @@ typedef struct d2s_xr_plan_result {
 int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
                      const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow,
                      d2s_xr_plan_result* res);
+
+/* The OpenXR viewer's "veil" and "frosted" looks around the FLAT screen (d2s_version() >= 124): d2s_dibr_xr_eyes followed, in the same
+ * launch, by the four "beam" walls of EffectsMixin._render_flat_frost_with_uniforms (xr_viewer/effects.py:789-817; mesh
+ * _build_flat_frost_verts, effects.py:145-187; layout _frost_front_layout, effects.py:102-132; programs _FROST_GLOW_VERT with
+ * _FROST_VEIL_FRAG or _FROST_GLOW_FRAG, xr_viewer/glsl.py:668-791) in _render_eye's order (effects.py:1023-1145): clear; the screen
+ * (depth test LESS, blending off); then the walls top, bottom, left, right with the depth test OFF, each blended
+ * src + dst * (1 - src.a) on rgb and alpha -- over the clear colour, over the screen and over each other, wherever a wall's plane point
+ * lies inside the wall, has clip w > 0 and NDC z in [-1, 1] (the walls run past the eye: the near plane cuts them).  All of it in
+ * float, quantised once at the store; alpha_mode then acts on that (rgb, a) as it does in d2s_dibr_xr_eyes_glow.
+ *   A wall runs from a screen edge (t = 0) to the matching edge of the front rectangle (t = 1): front_depth, front_half_w and
+ *   front_half_h are formed on the host in double precision from the screen and head[] as _frost_front_layout forms them (without its
+ *   rounded cache keys), the model matrix as _screen_effect_model(width, height, z_scale = front_depth).  v_local.z is t; v_uv follows
+ *   the MESH: an 8 x 8 grid of cells per wall, two triangles a cell, the screen-border uv interpolated over each triangle.
+ *   textureLod as d2s_dibr_xr_eyes_glow has it: LOD clamped to [0, q], trilinear between floor(lod) and the next level, bilinear
+ *   within a level, CLAMP_TO_EDGE; level 0 is the frame itself.  The veil reads level 0 only and never looks at levels (NULL is fine);
+ *   frosted needs levels = d2s_mip_chain's output for the same frames.
+ * frost == NULL, mode 0, intensity <= 0, or veil with alpha <= 0.002 (the reference's early returns, effects.py:822-857): a plain draw
+ * of the screen, bit-identical to d2s_dibr_xr_eyes (the same kernel, d2s_dibr_xr_workspace's bytes suffice).  Otherwise workspace >=
+ * d2s_dibr_xr_frost_workspace bytes (the screen's rows and four wall rows per eye).
+ * Refused, nothing launched, out untouched: D2S_E_UNSUPPORTED: a curved screen with frost on (the curved frost is a mesh of its own,
+ * _build_curved_frost_verts, 588 vertices: not built).  D2S_E_INVALID: normal_offset != 0 with frost on; a bad struct_size; mode
+ * outside 0..2; a non-finite field; noise_scale or lod negative; frosted with levels NULL; everything d2s_dibr_xr_eyes refuses.  The
+ * border and the curved frost stay with the caller. */
+typedef struct d2s_xr_frost {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_frost) = 120 */
+    int32_t  mode;             /* 0 off, 1 veil, 2 frosted (_active_glow_mode, effects.py:43-59) */
+    double   head[3];          /* _head_pos_w, world space (effects.py:105-125); the reference's default: the origin */
+    double   intensity;        /* u_intensity, ALREADY multiplied: _frost_veil_intensity (1.5) or _frost_glow_intensity (1.0) times
+                                  max(_glow_intensity_multiplier, 0) (effects.py:839-840, 823-824) */
+    double   alpha;            /* u_frost_alpha: _frost_veil_alpha 1.0 (effects.py:701) | _frost_glow_alpha 0.42 (effects.py:662) */
+    double   edge_inset;       /* u_edge_inset: 0.02 (effects.py:699) | _frost_glow_inset 0.045 (effects.py:658) */
+    double   beam_softness;    /* u_beam_softness: 0.34 (effects.py:702 | 652) */
+    double   beam_thickness;   /* u_beam_thickness: 3.0 (effects.py:703) | _frost_glow_thickness 1.6 (effects.py:666) */
+    /* frosted only (the veil's program has none of them) */
+    double   lod;              /* u_lod: _frost_glow_lod 5.4 (effects.py:659) */
+    double   threshold;        /* u_threshold: _frost_glow_threshold 0.46 (effects.py:660) */
+    double   noise_scale;      /* u_noise_scale: _frost_glow_noise_scale 54 (effects.py:663) */
+    double   blend;            /* u_frost_blend: _frost_glow_blend 1.35 (effects.py:665) */
+    double   diffuse;          /* u_diffuse_scatter: _frost_glow_diffuse 0.85 (effects.py:667) */
+    double   time;             /* u_time: _frame_now, seconds (effects.py:669); the noise cells drift with it */
+} d2s_xr_frost;
+enum { D2S_XR_KIND_FROST = 3 };          /* d2s_xr_plan_result.kind of d2s_dibr_xr_frost_plan */
+int d2s_dibr_xr_frost_workspace(int n_eyes, uint64_t* bytes);
+int d2s_dibr_xr_eyes_frost(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                           const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
+                           void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels, void* stream);
+/* d2s_dibr_xr_plan for d2s_dibr_xr_eyes_frost: the same host plan through a second door (d2s_dibr_xr_plan itself knows entries 0..2
+ * only).  kind: PLAIN or FROST; FROST: rows_per_eye 5 (the screen's row, then the four walls in draw order), one set-up launch per
+ * eye, no LDS, workspace_bytes = d2s_dibr_xr_frost_workspace's. */
+int d2s_dibr_xr_frost_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                           const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
+                           d2s_xr_plan_result* res);
 
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
@@ -693,6 +746,14 @@ int d2s_view_pipeline_xr_glow_curved_streams(d2s_engine* e, const uint8_t* frame
                                              const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
                                              void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels,
                                              void* stream);
+/* d2s_view_pipeline_xr_glow_streams with d2s_dibr_xr_eyes_frost as its last stage (d2s_version() >= 124): frost, levels and workspace as
+ * that call takes them; every refusal of its plan is made before the model starts.  Bit-identical to d2s_pipeline(depth_full) followed
+ * by d2s_dibr_xr_eyes_frost on the engine's map. */
+int d2s_view_pipeline_xr_frost_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                       int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp, const d2s_dibr_params* dp,
+                                       const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int use_ema,
+                                       void* out, int out_fmt, float* depth_full, void* workspace, uint64_t workspace_bytes,
+                                       const d2s_xr_frost* frost, const uint8_t* levels, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

@@ -26,7 +26,13 @@
     python tools/dibr_bench.py --xr-eye --glow glow|glow2 [--glow-range 15.0]
         d2s_dibr_xr_eyes_glow (the flat screen with the reference's glow in the same launch, every pixel of both eye images drawn) and
         d2s_mip_chain (the 1080p frame's colour mip chain, which the glow samples), alternated in one process with the flat eye call
-        without glow through the old entry (d2s_dibr_xr_eyes) and through the new one (glow off): us per launch, ns per image pixel."""
+        without glow through the old entry (d2s_dibr_xr_eyes) and through the new one (glow off): us per launch, ns per image pixel.
+    python tools/dibr_bench.py --xr-eye --frost veil|frosted [--ab-lib other/libd2s_hip.so]
+        d2s_dibr_xr_eyes_frost (the flat screen with the reference's veil or frosted walls in the same launch), alternated in one
+        process with the plain eye call through d2s_dibr_xr_eyes and through the new entry (frost off), the flat glow (for scale) and
+        d2s_mip_chain.  --ab-lib: another build of the library (the parent commit's), loaded beside this one; its d2s_dibr_xr_eyes
+        and this build's take the same arguments through the same bare C call in the same rounds, twice each, so that the other
+        build's spread against itself is the margin of the comparison."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -50,6 +56,8 @@ ap.add_argument("--curve", default=None, choices=["h", "v"], help="--xr-eye: the
 ap.add_argument("--eye-size", type=int, nargs=2, default=[2064, 2208], help="--xr-eye: swapchain image width height")
 ap.add_argument("--glow", default=None, choices=["glow", "glow2"], help="--xr-eye: time the glow eye call and mip_chain")
 ap.add_argument("--glow-range", type=float, default=None, help="--glow: range_m (default: xr.glow_range_m of the screen)")
+ap.add_argument("--frost", default=None, choices=["veil", "frosted"], help="--xr-eye: time the veil / frosted eye call (flat screen)")
+ap.add_argument("--ab-lib", default=None, help="--frost: another build of libd2s_hip.so whose d2s_dibr_xr_eyes is timed in the same rounds")
 a = ap.parse_args()
 dev = torch.device("cuda")
 
@@ -143,7 +151,71 @@ if a.xr_eye:
     eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
     img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
     dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
-    for B in a.batch if a.glow and a.curve else ():
+    for B in a.batch if a.frost else ():
+        import ctypes as C
+        from desktop2stereo_amd import _lib
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        frost = xr.XrFrost.veil() if a.frost == "veil" else xr.XrFrost.frosted(time=1.0)
+        glow = xr.XrGlow("glow", xr.glow_range_m(screen))
+        levels = ops.mip_chain(f)
+        out = torch.empty(ops.dibr_xr_shape(eyes, B, dp.alpha_mode)[1], dtype=torch.uint8, device=dev)
+        probe_s = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)      # clear alpha 0.5 marks the pixels nothing drew
+        probe_f = ops.dibr_xr_eyes_frost(f[:1], d[:1], dp, screen, eyes, frost, levels[:1], out_u8=False)
+        n_px = 2 * ew * eh
+        share_screen = sum(int((e[..., 3] != 0.5).sum()) for e in probe_s) / n_px
+        share_wall = sum(int((p != q).any(-1).sum()) for p, q in zip(probe_s, probe_f)) / n_px
+        runs = {"eyes_old_entry": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out),
+                "eyes_new_entry_frost_off": lambda: ops.dibr_xr_eyes_frost(f, d, dp, screen, eyes, None, None, out=out),
+                f"eyes_{a.frost}": lambda: ops.dibr_xr_eyes_frost(f, d, dp, screen, eyes, frost, levels, out=out),
+                "eyes_glow": lambda: ops.dibr_xr_eyes_glow(f, d, dp, screen, eyes, glow, levels, out=out),
+                "eyes_old_entry_again": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out),
+                "mip_chain": lambda: ops.mip_chain(f, out=levels)}
+        if a.ab_lib:      # the other build's plain eye call, on the same tensors and stream, through ctypes alone (it may lack newer symbols)
+            other = C.CDLL(os.path.abspath(a.ab_lib))
+            other.d2s_dibr_xr_eyes.restype, other.d2s_dibr_xr_eyes.argtypes = _lib.SYMBOLS["d2s_dibr_xr_eyes"]
+            other.d2s_version.restype = C.c_int
+            sc, ea = screen.c_struct(), xr.eye_array(eyes)
+            ws = torch.empty(2 * 52 * 96, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+
+            def raw_eyes(lib):      # both builds through the SAME host path: the C call alone, no tensor checks in between
+                def call():
+                    rc = lib.d2s_dibr_xr_eyes(f.data_ptr(), d.data_ptr(), d.shape[1], d.shape[2], B, a.height, a.width, C.byref(dp), None, C.byref(sc),
+                                              ea, 2, out.data_ptr(), _lib.FMT_U8_HWC, ws.data_ptr(), ws.numel(), st)
+                    assert rc == 0, rc
+                return call
+            other_eyes, this_eyes = raw_eyes(other), raw_eyes(_lib.load())
+            mine = ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)[0].clone()
+            other_eyes()
+            torch.cuda.synchronize()
+            same = bool(torch.equal(mine, out[:mine.numel()].view(mine.shape)))
+            print(f"--ab-lib {a.ab_lib}: d2s_version {other.d2s_version()} (this build {_lib.load().d2s_version()}); its eye 0 is "
+                  f"{'bit-identical to' if same else 'DIFFERENT from'} this build's", flush=True)
+            runs = dict({"other_lib_eyes": other_eyes, "this_lib_eyes": this_eyes}, **runs, other_lib_eyes_again=other_eyes, this_lib_eyes_again=this_eyes)
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"xr-eye {a.frost} {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}, medians of {a.rounds} rounds x {a.iters} launches; the screen covers "
+              f"{share_screen:.3f} of the images, the walls change {share_wall:.3f}:", flush=True)
+        for k in runs:
+            per = f"{1e3 * med[k] / (B * n_px):.4f} ns / image pixel" if k != "mip_chain" else f"{B * a.height * a.width * 3 / med[k] / 1e3:.1f} GB/s of the frame"
+            print(f"    {k:26s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {per})", flush=True)
+        print(f"    new entry, frost off - old entry = {med['eyes_new_entry_frost_off'] - med['eyes_old_entry']:+.1f} us; old entry against itself: "
+              f"{med['eyes_old_entry_again'] - med['eyes_old_entry']:+.1f} us", flush=True)
+        if a.ab_lib:
+            margin = abs(med["other_lib_eyes_again"] - med["other_lib_eyes"])
+            worst = max(med["this_lib_eyes"], med["this_lib_eyes_again"]) - max(med["other_lib_eyes"], med["other_lib_eyes_again"])
+            print(f"    other build against itself: {med['other_lib_eyes_again'] - med['other_lib_eyes']:+.1f} us (the margin: {margin:.1f} us); this build's "
+                  f"slower run - the other's slower run = {worst:+.1f} us: {'within' if worst <= margin else 'BEYOND'} the margin", flush=True)
+    for B in a.batch if a.glow and a.curve and not a.frost else ():
         import dataclasses
         flat = dataclasses.replace(screen, curve="flat")
         f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
@@ -180,7 +252,7 @@ if a.xr_eye:
         print(f"    ceiling (a) + (b) - (c) = {ceiling:.1f} us; curved {a.glow} - ceiling = {med[f'curved_{a.glow}'] - ceiling:+.1f} us "
               f"({100.0 * (med[f'curved_{a.glow}'] / ceiling - 1.0):+.1f} %); (a) against itself {med['a_curved_no_glow_again'] - med['a_curved_no_glow']:+.1f} us; "
               f"largest (max - min) / median of a row {100.0 * spread:.1f} %", flush=True)
-    for B in a.batch if a.glow and not a.curve else ():
+    for B in a.batch if a.glow and not a.curve and not a.frost else ():
         f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
         d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
         glow = xr.XrGlow(a.glow, a.glow_range if a.glow_range else xr.glow_range_m(screen))
@@ -207,7 +279,7 @@ if a.xr_eye:
             print(f"    {k:26s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {per})", flush=True)
         print(f"    new entry, glow off - old entry = {med['eyes_new_entry_glow_off'] - med['eyes_old_entry']:+.1f} us; old entry against itself: "
               f"{med['eyes_old_entry_again'] - med['eyes_old_entry']:+.1f} us", flush=True)
-    for B in () if a.glow else a.batch:
+    for B in () if a.glow or a.frost else a.batch:
         f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
         d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
         probe = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)      # clear alpha 0.5 marks the uncovered pixels
