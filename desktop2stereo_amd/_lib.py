@@ -92,6 +92,13 @@ class Conv3ProbeParams(C.Structure):
                 ("out", C.c_void_p), ("kernel", C.c_char * 128)]
 
 
+class RcuProbeParams(C.Structure):
+    """d2s_rcu_probe_params (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("batch", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("reserved", C.c_int32), ("x", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p),
+                ("b2", C.c_void_p), ("wp", C.c_void_p), ("bp", C.c_void_p), ("out", C.c_void_p), ("kernel", C.c_char * 128)]
+
+
 class AttentionProbeParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("precision", C.c_int32), ("B", C.c_int32), ("heads", C.c_int32), ("N", C.c_int32),
                 ("out_e4m3", C.c_int32), ("oscale", C.c_float), ("reserved", C.c_int32),
@@ -158,7 +165,7 @@ class ForwardPlanResult(C.Structure):
                 ("head2_ups", C.c_int32), ("bn", C.c_int32), ("tm_fold", C.c_int32), ("tm_cache_store", C.c_int32),
                 ("tm_slots", (C.c_int32 * 3) * 4), ("tm_folded", (C.c_int32 * 3) * 4), ("gh", C.c_int32), ("gw", C.c_int32),
                 ("P", C.c_int32), ("N", C.c_int32), ("Npad", C.c_int32), ("fH", C.c_int32 * 4), ("fW", C.c_int32 * 4),
-                ("tm_C", C.c_int32 * 4), ("tm_sites", C.c_int32 * 4), ("ln_launches", C.c_int32),
+                ("tm_C", C.c_int32 * 4), ("tm_sites", C.c_int32 * 4), ("ln_launches", C.c_int32), ("rcu_fused", C.c_int32),
                 ("splitk_elems", C.c_uint64), ("scr_elems", C.c_uint64)]
 
 
@@ -294,6 +301,7 @@ SYMBOLS = {
     "d2s_attention_probe": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "d2s_attention_probe_ex": (C.c_int, [C.POINTER(AttentionProbeParams), _P]),
     "d2s_conv3_probe": (C.c_int, [C.POINTER(Conv3ProbeParams), _P]),
+    "d2s_rcu_probe": (C.c_int, [C.POINTER(RcuProbeParams), _P]),
     "d2s_linear_probe": (C.c_int, [C.POINTER(LinearProbeParams), _P]),
     "d2s_temporal_probe": (C.c_int, [C.POINTER(TemporalProbeParams), _P]),
     "d2s_warp_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SbsParams), C.c_int, C.c_int, C.c_int,

@@ -1177,10 +1177,275 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
 // ring is two K tiles deep at most beside two halo buffers, i.e. ~1 000 cycles of cover for an LDS-DMA that needs ~2 000 under
 // load; two independent blocks per CU hide that better than one deeper-pipelined one.  Removed.)
 
+// ================================================================================================
+// conv3_rcu_kernel<PROJ>: a fusion stage's residual unit on a small map as ONE launch --
+//     out = x + conv2(relu(conv1(relu(x))))                       PROJ = 0  (RCU1 of a side tap: r1[i])
+//     out = proj(x + conv2(relu(conv1(relu(x)))))                 PROJ = 1  (RCU2 + the 1x1 projection: the stage's X)
+// bf16, C = N = 128.  On the 11 x 19 ... 42 x 74 maps of the batch-1 frame each of these convolutions is a dependent launch of a few
+// microseconds of weight streaming on an almost empty chip (c3_mid_ok above: boundary, cold code and the epilogue are what is
+// left), paid three times per stage.  The chain is tile-local: a block that owns a 4 x 8-pixel output tile of one image and all 128
+// channels needs nothing from any other block, only conv1 recomputed on the one-pixel ring around its tile.
+//   * one 8-wave block per tile; wave w owns output channels 16 w .. + 15 of every pixel fragment, so each weight fragment is read
+//     from LDS by exactly one wave;
+//   * the (4 + 4) x (8 + 4) input halo goes to LDS once, ReLU-on-load (h0); conv1 runs on the 6 x 10 ring-extended tile (60 pixels
+//     in four 16-pixel fragments) and leaves relu(bf16(acc + bias)) in a second halo region (h1) -- ZERO where the position lies
+//     outside the image: that is conv2's zero padding, not conv1 evaluated out there; conv2 reads h1, adds bias and the un-ReLU'd x
+//     (from global memory: the LDS copy is ReLU'd), rounds to bf16; PROJ: that tile goes to LDS (h2, over h0) and through the 1x1;
+//   * ONE weight ring through all three matrices in their packed layout (pack_conv3 / pack_linear rows, 128-byte K tiles):
+//     conv1's 18 K tiles, conv2's 18, the projection's 2, NS - 1 tiles requested ahead across the seams -- it never drains;
+//   * the K loops are ROLLED (a tap's LDS offset is one scalar add per fragment pointer): the whole kernel is three short bodies,
+//     not 38 unrolled tiles of cold code.
+// Every value is formed as the separate launches form it -- one accumulator per output, K tiles tap-major with 64 channels each,
+// the same MFMA and fragment slotting as conv3_halo2_kernel / gemm_glds_kernel / gemm_sk_kernel, bias / residual / rounding in
+// epilogue4's order -- so the result equals theirs bit for bit (tests/test_gpu_rcu_fused.py).
+// LDS: 7 x 16 KiB ring + 26 112 B (h0 | h2) + 16 320 B (h1) = 157 120 B.
+// ================================================================================================
+struct RcuArgs {
+    const bf16_t* x;                 // [nimg, H, W, 128]
+    bf16_t* out;                     // [nimg, H, W, 128]
+    const bf16_t *w1, *w2, *wp;      // packed [256][Kpad] x 2, [256][KpadP] (wp: PROJ only)
+    const float *b1, *b2, *bp;       // [128] each (bp: PROJ only)
+    int H, W, nimg, Kpad, KpadP;
+};
+constexpr int RCU_TH = 4, RCU_TW = 8;
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+// four floats -> four bf16 (RNE, as store4 rounds them); relu: max(., 0) on the ROUNDED values, as relu_frag does on load
+__device__ __forceinline__ uint2 rcu_pack4(const float v[4], bool relu) {
+    uint2 t = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
+    if (relu) t = __builtin_bit_cast(uint2, __builtin_elementwise_max(__builtin_bit_cast(s16x4, t), (s16x4){0, 0, 0, 0}));
+    return t;
+}
+// 8 bytes to LDS as inline asm: written as a plain store the compiler puts s_waitcnt vmcnt(0) in front of it (for all it knows the
+// store may alias what an LDS-DMA in flight writes), which drains the weight ring at every seam.  The regions written this way (h1,
+// h2) are no ring stage; their readers sit behind ring_step's lgkmcnt(0) and barrier.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void rcu_lds_write_b64(const u32x4* chunk, int half, uint2 v) {
+    const unsigned addr = (unsigned)(unsigned long)((__attribute__((address_space(3))) const char*)chunk) + (unsigned)half * 8u;
+    const u32x2 d = {v.x, v.y};
+    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(d) : "memory");
+}
+template <int PROJ>
+__global__ void __launch_bounds__(512)
+conv3_rcu_kernel(RcuArgs r) {
+    constexpr int TH = RCU_TH, TW = RCU_TW, CPP = 16, PST = 17, NW = 8;
+    constexpr int W0 = TW + 4, P0 = (TH + 4) * W0;          // input halo: 8 x 12 pixels
+    constexpr int W1 = TW + 2, P1 = (TH + 2) * W1;          // conv1's ring-extended tile: 6 x 10 pixels
+    constexpr int NKT = 18, NG = 2 * NKT + (PROJ ? 2 : 0);  // K tiles per convolution; tiles through the ring in all
+    constexpr int WST = 128 * 8;                            // chunks per ring stage: 128 rows x 128 bytes
+    constexpr int NS = 7, PD = NS - 1, BI = 128 / (8 * NW); // stages, tiles requested ahead, LDS-DMA instructions per wave per tile
+    static_assert(P1 <= 64 && TH * TW == 32 && BI == 2 && NG > PD, "fragment counts below are for a 4 x 8 tile");
+    __shared__ __attribute__((aligned(16))) u32x4 lds[NS * WST + P0 * PST + P1 * PST];
+    D2S_POISON_LDS(lds, NS * WST + P0 * PST + P1 * PST)
+    u32x4* const h0 = lds + NS * WST;
+    u32x4* const h1 = h0 + P0 * PST;
+    u32x4* const h2 = h0;                                   // PROJ: the rounded RCU tile, once conv1 has read h0 out
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fg = lane >> 4;
+    GemmA a = {};
+    a.ptr = r.x; a.Hi = a.Ho = r.H; a.Wi = a.Wo = r.W; a.C = 128; a.relu = 1;
+    const C3Tiles<TH, TW> tiles(a);
+    int b, ty0, tx0;
+    tiles.org(blockIdx.x, b, ty0, tx0);
+
+    // ---- column vectors of this lane's four channels, requested FIRST: they are older than every ring request, so no counted wait
+    // below sees them (their use is pinned behind the halo fill, where every earlier request has landed anyway)
+    const int n0 = wid * 16 + fg * 4;
+    float c1[4], c2[4], cp[4] = {0.f, 0.f, 0.f, 0.f};
+    load4(r.b1 + n0, c1); load4(r.b2 + n0, c2);
+    if constexpr (PROJ) load4(r.bp + n0, cp);
+
+    // ---- the weight ring (conv3_halo2_kernel's: lane -> row lane / 8 of the instruction's 8, physical chunk lane % 8, the row
+    // swizzle (row >> 1) & 7 on the source chunk and on the fragment read); tile g of the ring is K tile g of w1, g - 18 of w2, g - 36 of wp
+    const unsigned wbytes = 256u * (unsigned)r.Kpad * 2u, pbytes = 256u * (unsigned)r.KpadP * 2u;
+    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r.w1), 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r.w2), 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(PROJ ? r.wp : r.w2), 0, PROJ ? pbytes : wbytes, 0x00020000);
+    unsigned voW[BI], voP[BI];
+#pragma unroll
+    for (int i = 0; i < BI; ++i) {
+        const int row = (i * NW + wid) * 8 + (lane >> 3);
+        const unsigned ch = (unsigned)(((lane & 7) ^ ((row >> 1) & 7)) * 16);
+        voW[i] = (unsigned)(row * r.Kpad * 2) + ch;
+        voP[i] = (unsigned)(row * r.KpadP * 2) + ch;
+    }
+    auto issue = [&](int g, int slot) {
+        u32x4* st_ = lds + slot * WST;
+        if (g < NKT) {
+#pragma unroll
+            for (int i = 0; i < BI; ++i) lds_dma16(rs1, st_ + (i * NW + wid) * 64, voW[i], g * 128);
+        } else if (!PROJ || g < 2 * NKT) {
+#pragma unroll
+            for (int i = 0; i < BI; ++i) lds_dma16(rs2, st_ + (i * NW + wid) * 64, voW[i], (g - NKT) * 128);
+        } else {
+#pragma unroll
+            for (int i = 0; i < BI; ++i) lds_dma16(rsP, st_ + (i * NW + wid) * 64, voP[i], (g - 2 * NKT) * 128);
+        }
+    };
+#pragma unroll
+    for (int t = 0; t < PD; ++t) issue(t, t);
+
+    // ---- the input halo, once: rows ty0 - 2 .. ty0 + 5, columns tx0 - 2 .. tx0 + 9, zero outside the image, ReLU-on-load
+    conv_halo_fill<bf16_t, 64 * NW, 3>(a, b, ty0 - 1, tx0 - 1, W0, P0, CPP, tid, h0,
+        [&](int p, int c) { return p * PST + c; },
+        [&](u32x4 v) { return relu_frag(v, relu_floor_bf16(a), bf16_t()); });
+#pragma unroll
+    for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(c1[q]), "+v"(c2[q]), "+v"(cp[q]));
+
+    // ring bookkeeping: tile g sits in stage g % NS; before it is read, the wave's own requests for it have landed (at most the
+    // min(PD - 1, NG - 1 - g) younger tiles may still be out: vmcnt retires in order), then everybody's (the barrier, which also says
+    // that tile g - 1 is read out: its stage takes tile g + PD)
+    int g = 0, slot = 0, islot = PD;
+    auto ring_step = [&]() -> const u32x4* {
+        const int rem = NG - 1 - g;
+        if (rem >= PD - 1) c3_wait_vm<(PD - 1) * BI>();
+        else if (rem == 4) c3_wait_vm<4 * BI>();
+        else if (rem == 3) c3_wait_vm<3 * BI>();
+        else if (rem == 2) c3_wait_vm<2 * BI>();
+        else if (rem == 1) c3_wait_vm<1 * BI>();
+        else c3_wait_vm<0>();
+        __builtin_amdgcn_s_barrier();
+        if (g + PD < NG) issue(g + PD, islot);
+        const u32x4* B_l = lds + slot * WST;
+        ++g;
+        slot = slot + 1 == NS ? 0 : slot + 1;
+        islot = islot + 1 == NS ? 0 : islot + 1;
+        return B_l;
+    };
+    static_assert(PD == 6, "ring_step spells out the waits of the last PD - 1 tiles");
+    // W fragment of this wave: row 16 wid + fr, chunk (4 ks + fg) ^ swizzle(row)
+    int wo[2];
+    {
+        const int row = wid * 16 + fr;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) wo[ks] = row * 8 + ((ks * 4 + fg) ^ ((row >> 1) & 7));
+    }
+
+    // ---- conv1 on the ring-extended tile: position p = 16 f + fr -> (p / 10, p % 10), image pixel (ty0 - 1 + py, tx0 - 1 + px);
+    // positions 60 .. 63 repeat 59 and are not stored.  A fragment: h0 pixel (py + ky, px + kx), chunk 8 sub + 4 ks + fg
+    {
+        const u32x4* hb[4];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            const int p = f * 16 + fr < P1 ? f * 16 + fr : P1 - 1;
+            hb[f] = h0 + ((p / W1) * W0 + p % W1) * PST + fg;
+        }
+        f32x4 acc[4];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int kt = 0; kt < NKT; ++kt) {
+            const int tap = kt >> 1, ky = (tap * 11) >> 5, kx = tap - 3 * ky;
+            const int toff = (ky * W0 + kx) * PST + (kt & 1) * 8;
+            const u32x4* B_l = ring_step();
+            u32x4 fb[2], fa[2][4];                           // all ten fragments requested before the first MFMA: one LDS round trip per tile
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                fb[ks] = B_l[wo[ks]];
+#pragma unroll
+                for (int f = 0; f < 4; ++f) fa[ks][f] = hb[f][toff + ks * 4];
+            }
+            __builtin_amdgcn_sched_barrier(0);               // (the scheduler otherwise sinks each read to just in front of its MFMA)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int f = 0; f < 4; ++f) mma_chunk(acc[f], fb[ks], fa[ks][f], bf16_t());
+        }
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            const int p = f * 16 + fr;
+            const int py = p / W1, px = p - py * W1;
+            const int iy = ty0 - 1 + py, ix = tx0 - 1 + px;
+            const float v[4] = {acc[f][0] + c1[0], acc[f][1] + c1[1], acc[f][2] + c1[2], acc[f][3] + c1[3]};
+            uint2 t = rcu_pack4(v, true);
+            if (!(iy >= 0 && iy < r.H && ix >= 0 && ix < r.W)) t = make_uint2(0u, 0u);
+            if (p < P1) rcu_lds_write_b64(h1 + p * PST + 2 * wid + (fg >> 1), fg & 1, t);
+        }
+    }
+
+    // ---- conv2 on the tile: pixel p = 16 f + fr -> (p / 8, p % 8); A fragment: h1 position (oy + ky, ox + kx)
+    const int oy0 = fr >> 3, ox = fr & 7;                    // fragment f: tile row 2 f + oy0
+    uint2 rcu[2];
+    {
+        const u32x4* hb[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) hb[f] = h1 + ((2 * f + oy0) * W1 + ox) * PST + fg;
+        f32x4 acc[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int kt = 0; kt < NKT; ++kt) {
+            const int tap = kt >> 1, ky = (tap * 11) >> 5, kx = tap - 3 * ky;
+            const int toff = (ky * W1 + kx) * PST + (kt & 1) * 8;
+            const u32x4* B_l = ring_step();
+            u32x4 fb[2], fa[2][2];
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                fb[ks] = B_l[wo[ks]];
+#pragma unroll
+                for (int f = 0; f < 2; ++f) fa[ks][f] = hb[f][toff + ks * 4];
+            }
+            __builtin_amdgcn_sched_barrier(0);               // (the scheduler otherwise sinks each read to just in front of its MFMA)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int f = 0; f < 2; ++f) mma_chunk(acc[f], fb[ks], fa[ks][f], bf16_t());
+        }
+        // epilogue4's order: + bias, + the residual x, round
+        float xr[2][4];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int y = ty0 + 2 * f + oy0, x = tx0 + ox;
+            const bool ok = y < r.H && x < r.W;
+            load4(r.x + ((long)(b * r.H + (ok ? y : 0)) * r.W + (ok ? x : 0)) * 128 + n0, xr[f]);
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            float v[4] = {acc[f][0] + c2[0], acc[f][1] + c2[1], acc[f][2] + c2[2], acc[f][3] + c2[3]};
+            v[0] += xr[f][0]; v[1] += xr[f][1]; v[2] += xr[f][2]; v[3] += xr[f][3];
+            rcu[f] = rcu_pack4(v, false);
+        }
+    }
+    if constexpr (!PROJ) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int y = ty0 + 2 * f + oy0, x = tx0 + ox;
+            if (y < r.H && x < r.W) *(uint2*)(r.out + ((long)(b * r.H + y) * r.W + x) * 128 + n0) = rcu[f];
+        }
+    } else {
+        // ---- the 1x1 projection of the rounded tile: K = 128 = the ring's last two tiles; A fragment: h2 pixel p, chunk 8 kt + 4 ks + fg
+#pragma unroll
+        for (int f = 0; f < 2; ++f) rcu_lds_write_b64(h2 + (f * 16 + fr) * PST + 2 * wid + (fg >> 1), fg & 1, rcu[f]);
+        f32x4 acc[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int kt = 0; kt < 2; ++kt) {
+            const u32x4* B_l = ring_step();
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const u32x4 fb = B_l[wo[ks]];
+#pragma unroll
+                for (int f = 0; f < 2; ++f) mma_chunk(acc[f], fb, h2[(f * 16 + fr) * PST + fg + kt * 8 + ks * 4], bf16_t());
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int y = ty0 + 2 * f + oy0, x = tx0 + ox;
+            const float v[4] = {acc[f][0] + cp[0], acc[f][1] + cp[1], acc[f][2] + cp[2], acc[f][3] + cp[3]};
+            if (y < r.H && x < r.W) *(uint2*)(r.out + ((long)(b * r.H + y) * r.W + x) * 128 + n0) = rcu_pack4(v, false);
+        }
+    }
+}
+
 // Every kernel instantiation of this file, once: P(id, kernel) a persistent kernel (512 threads, launched with the tile count),
-// H(id, CPP, PST, BN, WM, WN, NS[, HG]) a one-shot conv3_halo2_kernel.  The enum, the names GemmPlan reports (the tests pin them),
-// the block sizes and the launch switch are generated from this list.
-#define C3_INSTANCES(P, H)                                                                                                       \
+// H(id, CPP, PST, BN, WM, WN, NS[, HG]) a one-shot conv3_halo2_kernel, R(id, kernel) a fused residual unit (512 threads, one block
+// per tile, launched by launch_conv3_rcu).  The enum, the names GemmPlan reports (the tests pin them), the block sizes and the
+// launch switches are generated from this list.
+#define C3_INSTANCES(P, H, R)                                                                                                    \
+    R(C3_RCU, conv3_rcu_kernel<0>)                                                                                               \
+    R(C3_RCU_PROJ, conv3_rcu_kernel<1>)                                                                                          \
     P(C3_HEAD_UPS, conv3_head_ups_kernel)                                                                                        \
     P(C3_HEAD_1, conv3_head_kernel<1>)                                                                                           \
     P(C3_HEAD_0, conv3_head_kernel<0>)                                                                                           \
@@ -1195,12 +1460,12 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
     H(C3_H2_C64_N64, 8,10,64,4,2,3)                                                                                              \
     H(C3_H2_C64_N32, 8,10,32,4,1,3)
 #define C3_ID(ID, ...) ID,
-enum { C3_INSTANCES(C3_ID, C3_ID) };
+enum { C3_INSTANCES(C3_ID, C3_ID, C3_ID) };
 #undef C3_ID
 #define C3_BLOCK(CPP, PST, BN, WM, WN, ...) 64 * WM * WN
 #define C3_P(ID, ...) {#__VA_ARGS__, 512},
 #define C3_H(ID, ...) {"conv3_halo2_kernel<" #__VA_ARGS__ ">", C3_BLOCK(__VA_ARGS__)},
-static const struct { const char* name; int block; } c3_inst[] = { C3_INSTANCES(C3_P, C3_H) };
+static const struct { const char* name; int block; } c3_inst[] = { C3_INSTANCES(C3_P, C3_H, C3_P) };
 #undef C3_P
 #undef C3_H
 #undef C3_BLOCK
@@ -1302,10 +1567,44 @@ void launch_conv3_halo2(const GemmPlan& p, const GemmA& a, const void* W, int M,
     switch (p.inst) {
 #define C3_P(ID, ...) case ID: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, a, w, N, Kpad, e, p.xn); break;
 #define C3_H(ID, ...) case ID: hipLaunchKernelGGL((conv3_halo2_kernel<__VA_ARGS__>), grid, block, 0, st, a, w, M, N, Kpad, e, p.xn); break;
-        C3_INSTANCES(C3_P, C3_H)
+#define C3_R(ID, ...) case ID: break;      /* (launch_conv3_rcu) */
+        C3_INSTANCES(C3_P, C3_H, C3_R)
 #undef C3_P
 #undef C3_H
+#undef C3_R
     }
+}
+
+// ---- the fused residual unit ---------------------------------------------------------------------------------------------------
+// Eligible: plain_bf16 (the caller's half: a bf16 engine with plain row epilogues -- no e4m3 operands, not the calibration pass),
+// C = N = fusion width = 128, and every block resident at once, one per CU: tiles x images <= CU count.
+// MEASURED per map size at batch 1, 2 and 4 (profiles/rcu_fused_ab.txt): every map the rule admits is faster fused -- the launch takes
+// 16-17 us whatever the map (one block streams all 622 KB of weights), the two or three launches it replaces 21-24 us without
+// their events -- so the limit that ships is the one it started from.
+bool c3_rcu_ok(bool plain_bf16, int C, int nimg, int H, int W) {
+    return plain_bf16 && C == 128 && nimg > 0 && H > 0 && W > 0 && (long)nimg * H * W * 128 < (1L << 31) &&
+           (long)nimg * cdiv(H, RCU_TH) * cdiv(W, RCU_TW) <= device_cu_count();
+}
+bool plan_conv3_rcu(bool plain_bf16, int C, int nimg, int H, int W, bool proj, GemmPlan& p) {
+    if (!c3_rcu_ok(plain_bf16, C, nimg, H, W)) return false;
+    p = GemmPlan{};
+    const int inst = proj ? C3_RCU_PROJ : C3_RCU;
+    p.family = GEMM_CONV3; p.inst = inst; p.name = c3_inst[inst].name; p.block = c3_inst[inst].block;
+    p.grid = (unsigned)(nimg * cdiv(H, RCU_TH) * cdiv(W, RCU_TW)); p.ksplit = 1;
+    return true;
+}
+void launch_conv3_rcu(const GemmPlan& p, const RcuOp& o, hipStream_t st) {
+    const RcuArgs r = {(const bf16_t*)o.x, (bf16_t*)o.out, (const bf16_t*)o.w1, (const bf16_t*)o.w2, (const bf16_t*)o.wp, o.b1, o.b2, o.bp,
+                       o.H, o.W, o.nimg, o.Kpad, o.KpadP};
+    const dim3 grid(p.grid), block(p.block);
+    switch (p.inst) {
+#define C3_N(ID, ...)
+#define C3_R(ID, ...) case ID: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, r); break;
+        C3_INSTANCES(C3_N, C3_N, C3_R)
+#undef C3_N
+#undef C3_R
+    }
+    kernel_note() = KernelNote{p.name, 0, 1, NOTE_TAIL_NONE};
 }
 
 }  // namespace d2s

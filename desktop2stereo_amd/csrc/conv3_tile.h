@@ -1,7 +1,7 @@
 // Pieces the 3x3 convolution kernels of conv3.hip share: which output tile
 // a block works on, where that tile's input lies, the weight fragments the register-resident kernels preload and the fused head
 // tail.  Plain inlined structs and functions: every kernel keeps its own schedule, LDS layout and loaders.
-//   C3Tiles::org      conv3_head<0|1>, conv3_head_ups, conv3_c128_ups, conv3_wide  (the one-shot row-tile kernels conv3_halo2 and
+//   C3Tiles::org      conv3_head<0|1>, conv3_head_ups, conv3_c128_ups, conv3_wide, conv3_rcu<0|1>  (the one-shot row-tile kernels conv3_halo2 and
 //                     conv3_halo keep their inline origin: with org's prologue they measured slower, profiles/conv3_shared_ab.md)
 //   C3Tiles::src_org  conv3_head<1>, conv3_head_ups (rows only, through its tile_geo), conv3_c128_ups
 //   C3Walk            conv3_head<0|1>, conv3_head_ups, conv3_c128_ups, conv3_wide

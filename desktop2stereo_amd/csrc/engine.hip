@@ -318,6 +318,20 @@ int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int strid
     return linear(e, a, w, B * Ho * Wo, ep, st);
 }
 
+// A fusion stage's residual unit as one launch (pl.rcu_fused / pl.rcu1_fused; conv3.hip conv3_rcu_kernel):
+// out = x + c2(relu(c1(relu(x)))), through proj where given -- what conv3, conv3 (+ linear) compute in two (three) launches, bit for bit
+int rcu(d2s_engine* e, const void* x, int B, int H, int W, const DevLinear& c1, const DevLinear& c2, const DevLinear* proj, void* out, hipStream_t st) {
+    GemmPlan p;
+    if (!plan_conv3_rcu(true, e->d.fusion, B, H, W, proj != nullptr, p) || c1.Kpad != c2.Kpad || !c1.bias || !c2.bias || (proj && !proj->bias)) {
+        set_error("forward: the frame's plan fuses a residual unit that conv3_rcu_kernel does not take");
+        return D2S_E_STATE;
+    }
+    const RcuOp o = {x, out, B, H, W, c1.w, c2.w, proj ? proj->w : nullptr, c1.bias, c2.bias, proj ? proj->bias : nullptr, c1.Kpad, proj ? proj->Kpad : 0};
+    const double macs = (double)c1.N * c1.K + (double)c2.N * c2.K + (proj ? (double)proj->N * proj->K : 0.0);
+    PROF(PC_CONV, 2.0 * B * H * W * macs, 0, (launch_conv3_rcu(p, o, st), D2S_OK));
+    return D2S_OK;
+}
+
 // One row's entries of an attention block's two row tables, from its stream slot's window and ring.  THE rule for where a frame's
 // projected k' | v' rows join the window:
 //   fused, filled    the attention kernel overwrites the oldest slot (head) itself, nothing is left for the store launch
@@ -441,8 +455,11 @@ int neck_rest(d2s_engine* e, const ForwardPlan& pl, int i, int B, hipStream_t st
     RC(conv3(e, src, B, Hs, Ws, c, 1, 0, e->re[i].conv, e->feat[i], ACT_NONE, nullptr, nullptr, st));
     if (i < 3) {
         const int idx = 3 - i;                          // the fusion layer that consumes this map
-        RC(conv3(e, e->feat[i], B, Hs, Ws, F, 1, 1, e->fu[idx].r1c1, e->r1tmp, ACT_NONE, nullptr, nullptr, st));
-        RC(conv3(e, e->r1tmp, B, Hs, Ws, F, 1, 1, e->fu[idx].r1c2, e->r1[i], ACT_NONE, e->feat[i], nullptr, st));
+        if (pl.rcu1_fused[i]) RC(rcu(e, e->feat[i], B, Hs, Ws, e->fu[idx].r1c1, e->fu[idx].r1c2, nullptr, e->r1[i], st));
+        else {
+            RC(conv3(e, e->feat[i], B, Hs, Ws, F, 1, 1, e->fu[idx].r1c1, e->r1tmp, ACT_NONE, nullptr, nullptr, st));
+            RC(conv3(e, e->r1tmp, B, Hs, Ws, F, 1, 1, e->fu[idx].r1c2, e->r1[i], ACT_NONE, e->feat[i], nullptr, st));
+        }
     }
     return D2S_OK;
 }
@@ -564,15 +581,19 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         void* m = e->feat[mi];
         Hc = e->g.fH[mi]; Wc = e->g.fW[mi];
         const void* hcur = idx == 0 ? m : fused;
-        RC(conv3(e, hcur, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c1, X, ACT_NONE, nullptr, nullptr, st));
-        RC(conv3(e, X, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c2, Z, ACT_NONE, hcur, nullptr, st));
+        // RCU2 and the projection behind it (below): X = proj(h + r2c2(relu(r2c1(relu(h))))), one launch where the plan fuses the stage
+        if (pl.rcu_fused[idx]) RC(rcu(e, hcur, B, Hc, Wc, e->fu[idx].r2c1, e->fu[idx].r2c2, &e->fu[idx].proj, X, st));
+        else {
+            RC(conv3(e, hcur, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c1, X, ACT_NONE, nullptr, nullptr, st));
+            RC(conv3(e, X, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c2, Z, ACT_NONE, hcur, nullptr, st));
+        }
         int Ho, Wo;
         if (idx < 3) { Ho = e->g.fH[mi - 1]; Wo = e->g.fW[mi - 1]; } else { Ho = Hc * 2; Wo = Wc * 2; }
         // HF: projection(interpolate(h)).  The 1x1 projection (+bias) commutes with bilinear interpolation
         // (interpolation weights sum to 1), so it runs BEFORE the up-sample on 4x fewer pixels.
         void* pout = e->scr[3 + (idx & 1)];
         const void* next_r1 = idx < 3 ? e->r1[2 - idx] : nullptr;      // RCU1 of the next (shallower) stage's map
-        RC(linear(e, plainA(Z, F), e->fu[idx].proj, B * Hc * Wc, rowsE(X, OUT_T, F, e->fu[idx].proj.bias), st));
+        if (!pl.rcu_fused[idx]) RC(linear(e, plainA(Z, F), e->fu[idx].proj, B * Hc * Wc, rowsE(X, OUT_T, F, e->fu[idx].proj.bias), st));
         if (d.temporal && idx < 2) {                     // path_4 / path_3 (dpt_temporal.py:98-103)
             PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st));
             void* alt = e->scr[3 + ((idx + 1) & 1)];
@@ -977,6 +998,7 @@ extern "C" int d2s_forward_plan(const d2s_model_desc* desc, int h, int w, int ba
     r.gh = g.gh; r.gw = g.gw; r.P = g.P; r.N = g.N; r.Npad = g.Npad;
     for (int i = 0; i < 4; ++i) { r.fH[i] = g.fH[i]; r.fW[i] = g.fW[i]; r.tm_C[i] = d.temporal ? g.tmC[i] : 0; r.tm_sites[i] = d.temporal ? g.tmS[i] : 0; }
     r.ln_launches = pl.ln_launches;
+    for (int i = 0; i < 4; ++i) r.rcu_fused |= (pl.rcu_fused[i] ? 1 << i : 0) | (pl.rcu1_fused[i] ? 256 << i : 0);
     r.splitk_elems = g.splitk_elems; r.scr_elems = g.scr_elems;
     *res = r;
     return D2S_OK;

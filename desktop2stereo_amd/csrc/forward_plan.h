@@ -116,6 +116,8 @@ struct ForwardPlan {
     bool head1_ups;                 // the last fusion stage's up-sample folded into head conv1's loader
     bool head2_fused, head2_ups;    // conv2 + conv3 in one launch (bn: its column tile); the interpolate in front folded into its loader
     int bn;
+    bool rcu_fused[4];              // fusion stage idx: r2c1 + r2c2 + the 1x1 projection as one launch (conv3.hip conv3_rcu_kernel<1>)
+    bool rcu1_fused[4];             // tap i (< 3): the RCU1 of its fusion layer, r1c1 + r1c2, as one launch (conv3_rcu_kernel<0>)
     bool tm_fold;                   // temporal modules: proj_in / to_out / ff2 leave the bf16 copy (and statistics) of the folded forms
     struct { int slots[3]; bool folded[3]; } tm[4];   // per temporal module: norms.0 -> kvq[0], norms.1 -> kvq[1], ff_norm -> ff1
     int ln_launches;                // LayerNorm launches of the frame
@@ -135,6 +137,8 @@ struct ForwardPlan {
 //                                (<= 4 partials per row); D2S_LNF_PP=0 / D2S_GEMM_PP=0: off.
 //   tap_fold                     bf16, B == 1 or pp_fold: the shared final LayerNorm folds into the four reassemble projections (the
 //                                statistics and the raw residual of a tap layer are still in lnbuf / lnstats when its projection runs).
+//   rcu_fused                    bf16, fusion width 128, a map whose 4 x 8-pixel tiles x B fit the CUs: the stage's residual unit and
+//                                projection (the taps' RCU1) are one launch; at 294 x 518 the three small maps at B = 1, two at B = 2-4.
 //   calibrating, D2S_TAPS        calibration folds nothing (it measures the LayerNorm outputs); taps keep pp_fold off.
 static inline int plan_forward(const d2s_model_desc& d, const EngineGeom& g, int h, int w, int B, const FrameState& s, ForwardPlan& pl) {
     pl = ForwardPlan{};
@@ -180,6 +184,18 @@ static inline int plan_forward(const d2s_model_desc& d, const EngineGeom& g, int
     for (int i = 0; i < 4; ++i) pl.tap_side[i] = pl.use_side && (i < 3 || d.temporal);
     for (int i = 0; i < 4; ++i) pl.tap_private[i] = pl.tap_side[i] && pl.tap_folded && s.tap_private;
     pl.ln_launches = 1 + (d.layers - 1) * !pl.ln1_folded + d.layers * !pl.ln2_folded + 4 * !pl.tap_folded;
+    // ---- the fusion stages' residual units: one launch where c3_rcu_ok (conv3.hip) takes the map -- a bf16 engine with plain row
+    // epilogues (no e4m3 operands, not the calibration pass), fusion width 128, every block resident at once.  Stage idx works on neck
+    // map 3 - idx; the RCU1 of tap i < 3 on map i (tap 3's map has none).  The same under profiling; D2S_RCU_FUSE=0: the separate launches
+    {
+        static EnvInt rcu_fuse{"D2S_RCU_FUSE", 1};
+        const bool plain_bf16 = rcu_fuse.get() && pr.precision == D2S_PREC_BF16 && !s.calib;
+        for (int i = 0; i < 4; ++i) {
+            const bool ok = c3_rcu_ok(plain_bf16, F, B, g.fH[i], g.fW[i]);
+            pl.rcu_fused[3 - i] = ok;
+            pl.rcu1_fused[i] = ok && i < 3;
+        }
+    }
     // ---- temporal modules: the LayerNorm in front of kvq[0] / kvq[1] / ff1 folds where its producer (proj_in / to_out[0] / to_out[1])
     // leaves 1 .. 16 partials per row
     pl.tm_fold = d.temporal && s.tm_fold;

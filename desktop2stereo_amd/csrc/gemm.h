@@ -122,6 +122,19 @@ int plan_gemm(int precision, int tile, const GemmA& a, int M, int N, int K, int 
 // the families outside gemm.hip: eligibility / plan (host only) and the launcher of a plan
 bool plan_conv3_halo2(const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);   // stride-1 3x3 convs, input in LDS
 void launch_conv3_halo2(const GemmPlan& p, const GemmA& a, const void* W, int M, int N, int Kpad, const GemmEpi& e, hipStream_t st);
+// A fusion stage's residual unit on a small map as one launch (conv3.hip conv3_rcu_kernel): out = x + conv2(relu(conv1(relu(x)))),
+// and with wp the stage's 1x1 projection of that; bf16, C = 128, weights as pack_conv3 / pack_linear leave them.  c3_rcu_ok: the
+// geometry rule (every block resident at once); which engines ask is plan_forward's (forward_plan.h).
+struct RcuOp {
+    const void* x; void* out;            // [nimg, H, W, 128] bf16
+    int nimg, H, W;
+    const void *w1, *w2, *wp;            // conv1, conv2 [256][Kpad]; the projection [256][KpadP] or null
+    const float *b1, *b2, *bp;           // [128] each (bp with wp)
+    int Kpad, KpadP;
+};
+bool c3_rcu_ok(bool plain_bf16, int C, int nimg, int H, int W);
+bool plan_conv3_rcu(bool plain_bf16, int C, int nimg, int H, int W, bool proj, GemmPlan& p);
+void launch_conv3_rcu(const GemmPlan& p, const RcuOp& o, hipStream_t st);
 // 256 x 256 ping-pong kernel (gemm_pp.hip): batched plain linears
 bool pp_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);
 int plan_gemm_pp(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e, GemmPlan& p);

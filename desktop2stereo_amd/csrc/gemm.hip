@@ -1111,6 +1111,48 @@ extern "C" int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream) {
     return D2S_OK;
 }
 
+// ---- d2s_rcu_probe ------------------------------------------------------------------------------------------------------
+extern "C" int d2s_rcu_probe(d2s_rcu_probe_params* p, void* stream) {
+    D2S_REQUIRE(p && p->struct_size == sizeof(d2s_rcu_probe_params), "d2s_rcu_probe_params.struct_size must be sizeof(d2s_rcu_probe_params)");
+    p->kernel[0] = 0;
+    const int B = p->batch, H = p->H, W = p->W, C = p->C;
+    D2S_REQUIRE(p->x && p->w1 && p->b1 && p->w2 && p->b2 && p->out && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "bad argument");
+    D2S_REQUIRE(!p->wp == !p->bp, "the projection needs its weight and its bias");
+    hipStream_t st = (hipStream_t)stream;
+    const long npx = (long)B * H * W;
+    D2S_REQUIRE(npx * C < (1L << 31), "too large");
+    GemmPlan plan;
+    if (!plan_conv3_rcu(true, C, B, H, W, p->wp != nullptr, plan)) {
+        set_error("d2s_rcu_probe: c3_rcu_ok refuses this map (C = 128 and tiles x images <= CU count)");
+        return D2S_E_UNSUPPORTED;
+    }
+    // the weights packed as pack_conv3 / pack_linear pack them
+    ProbeBuf dW[3], dX;
+    int Kpad[3] = {0, 0, 0};
+    for (int i = 0; i < 3; ++i) {
+        const float* src = i == 0 ? p->w1 : (i == 1 ? p->w2 : p->wp);
+        if (!src) continue;
+        const int K = i < 2 ? 9 * C : C;
+        std::vector<float> w;
+        int rc = fetch_f32(w, src, (size_t)C * K);
+        if (rc != D2S_OK) return rc;
+        const LinearImage im = i < 2 ? prepare_linear(D2S_PREC_BF16, C, K, [&](int n, int k) { return w[conv3_weight_index(n, k, C)]; }, nullptr)
+                                     : prepare_linear(D2S_PREC_BF16, C, K, [&](int n, int k) { return w[(size_t)n * K + k]; }, nullptr);
+        rc = upload(dW[i], im.w.data(), im.w.size());
+        if (rc != D2S_OK) return rc;
+        Kpad[i] = im.Kpad;
+    }
+    D2S_HIP(hipMalloc(&dX.p, (size_t)npx * C * 2));
+    hipLaunchKernelGGL(cast_pad_kernel, dim3(cdiv(npx * C, 256)), dim3(256), 0, st, p->x, dX.p, (int)npx, C, (int)npx, C, D2S_PREC_BF16);
+    D2S_HIP(hipExtGetLastError());
+    const RcuOp o = {dX.p, p->out, B, H, W, dW[0].p, dW[1].p, dW[2].p, p->b1, p->b2, p->bp, Kpad[0], Kpad[2]};
+    kernel_note() = KernelNote{nullptr, 0, 1, NOTE_TAIL_NONE};
+    launch_conv3_rcu(plan, o, st);
+    D2S_HIP(hipStreamSynchronize(st));
+    snprintf(p->kernel, sizeof(p->kernel), "%s", noted_kernel().c_str());
+    return D2S_OK;
+}
+
 // ---- d2s_linear_probe ---------------------------------------------------------------------------------------------------
 namespace d2s {
 namespace {

@@ -714,6 +714,8 @@ def forward_plan(cfg: ModelConfig, h: int, w: int, batch: int = 1, precision: st
     out["tap_side"] = [bool(v) for v in r.tap_side]
     out["tm_slots"] = [list(m) for m in r.tm_slots]
     out["tm_folded"] = [[bool(v) for v in m] for m in r.tm_folded]
+    out["rcu_fused"] = [bool(r.rcu_fused >> i & 1) for i in range(4)]            # fusion stages, deep -> shallow
+    out["rcu1_fused"] = [bool(r.rcu_fused >> (8 + i) & 1) for i in range(3)]     # the RCU1 of taps 0..2
     return out
 
 
@@ -1020,6 +1022,31 @@ def conv3_probe(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     p.out = _ptr(out)
     with _on(x.device) as st:
         check(_lib.load().d2s_conv3_probe(C.byref(p), st), "d2s_conv3_probe")
+    return out, p.kernel.decode()
+
+
+def rcu_probe(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+              wp: Optional[torch.Tensor] = None, bp: Optional[torch.Tensor] = None):
+    """A fusion stage's residual unit as the one launch the engine makes of it on a small map (test probe, include/d2s.h d2s_rcu_probe):
+    x + conv2(relu(conv1(relu(x)))), through the 1x1 projection (wp [C, C], bp) where given.  x: float32 [B, H, W, C], w1 / w2: float32
+    [C, C, 3, 3], biases [C].  Returns (out bfloat16 [B, H, W, C], kernel name); D2SError where the engine would keep the separate launches."""
+    _need_cuda(x, "x")
+    B, H, W, Cc = x.shape
+    if tuple(w1.shape) != (Cc, Cc, 3, 3) or tuple(w2.shape) != (Cc, Cc, 3, 3) or (wp is not None and tuple(wp.shape) != (Cc, Cc)):
+        raise ValueError("rcu_probe: w1, w2 must be [C, C, 3, 3], wp [C, C]")
+    if (wp is None) != (bp is None):
+        raise ValueError("rcu_probe: wp and bp go together")
+    keep = [t.float().contiguous() for t in (x, w1, b1, w2, b2)] + ([wp.float().contiguous(), bp.float().contiguous()] if wp is not None else [])
+    p = _lib.RcuProbeParams()
+    p.struct_size = C.sizeof(_lib.RcuProbeParams)
+    p.batch, p.H, p.W, p.C = B, H, W, Cc
+    p.x, p.w1, p.b1, p.w2, p.b2 = (_ptr(t) for t in keep[:5])
+    if wp is not None:
+        p.wp, p.bp = _ptr(keep[5]), _ptr(keep[6])
+    out = torch.empty((B, H, W, Cc), dtype=torch.bfloat16, device=x.device)
+    p.out = _ptr(out)
+    with _on(x.device) as st:
+        check(_lib.load().d2s_rcu_probe(C.byref(p), st), "d2s_rcu_probe")
     return out, p.kernel.decode()
 
 
