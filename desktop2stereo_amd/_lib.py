@@ -154,7 +154,7 @@ class XrPlanResult(C.Structure):
 
 
 XR_ENTRY = {"eyes": 0, "glow": 1, "glow_curved": 2}      # D2S_XR_ENTRY_*
-XR_KIND = {0: "plain", 1: "glow", 2: "glow_curved", 3: "frost"}      # D2S_XR_KIND_*
+XR_KIND = {0: "plain", 1: "glow", 2: "glow_curved", 3: "frost", 4: "frost_curved"}      # D2S_XR_KIND_*
 
 
 class ForwardPlanResult(C.Structure):
@@ -262,6 +262,16 @@ SYMBOLS = {
     "d2s_view_pipeline_xr_frost_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                      C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double), C.POINTER(XrScreen),
                                                      C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_uint64, C.POINTER(XrFrost), _P, _P]),
+    # the veil and frosted looks of the curved screen (xr_viewer/effects.py:189-254, 759-787): the flat entries' argument lists
+    "d2s_dibr_xr_frost_curved_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "d2s_dibr_xr_eyes_frost_curved": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                                C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrFrost), _P, _P]),
+    "d2s_dibr_xr_frost_curved_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                                C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, C.POINTER(XrFrost), C.POINTER(XrPlanResult)]),
+    "d2s_view_pipeline_xr_frost_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,
+                                                            C.c_uint64, C.POINTER(XrFrost), _P, _P]),
     "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,

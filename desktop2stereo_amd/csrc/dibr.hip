@@ -483,15 +483,17 @@ __device__ __forceinline__ bool frost_frag(const XrFrostDev& F, const DibrGeomPr
 // The block prologue.  It NEVER returns a thread early: in the glow kernels a thread outside its eye image (the other eye is larger,
 // or a side is no multiple of 16) must still reach every barrier.  dibr_xr_kernel, which has none, returns on !inside itself.
 struct XrPix { int ei, b; XrEyeDev e; int x, y; bool inside; float xc, yc; };
-__device__ __forceinline__ XrPix xr_pix(const XrEyes& ex) {
+// (tx, ty): the thread's 16 x 16 tile of the eye image; the block's own, except in the binned kernel, whose block walks several
+__device__ __forceinline__ XrPix xr_pix_at(const XrEyes& ex, int tx, int ty) {
     XrPix p;
     p.ei = blockIdx.z % ex.n; p.b = blockIdx.z / ex.n;
     p.e = ex.e[p.ei];
-    p.x = blockIdx.x * 16 + (threadIdx.x & 15); p.y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    p.x = tx * 16 + (threadIdx.x & 15); p.y = ty * 16 + (threadIdx.x >> 4);
     p.inside = p.x < p.e.w && p.y < p.e.h;
     p.xc = ((float)p.x + 0.5f) - 0.5f * (float)p.e.w; p.yc = ((float)p.y + 0.5f) - 0.5f * (float)p.e.h;      // exact: multiples of 0.5 below 2^13
     return p;
 }
+__device__ __forceinline__ XrPix xr_pix(const XrEyes& ex) { return xr_pix_at(ex, blockIdx.x, blockIdx.y); }
 struct XrPt { float na, nb, nw, z; };
 __device__ __forceinline__ XrPt xr_row_at(const float* __restrict__ r, float xc, float yc) {
     XrPt p;
@@ -666,6 +668,106 @@ dibr_xr_frost_kernel(const uint8_t* __restrict__ rgb_all, const float* __restric
                                  (MODE == 2 && F.l1 > 0) ? chain + F.off1 : frame};
     xr_tail<OUT_FMT, D, 0, XrWalls<MODE>>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f,
                                           nullptr, walls);
+}
+
+// d2s_dibr_xr_eyes_frost_curved: the curved screen with the 196 triangles of its veil (MODE 1) or frosted (MODE 2) walls blended after it
+// in draw order (_render_curved_frost_with_uniforms, xr_viewer/effects.py:759-787; rows: dibr_xr.h).  A block draws
+// XR_BIN_TILES x XR_BIN_TILES tiles of 16 x 16 pixels.  It bins first: thread r < 244 tests row r at the four corners of the block's
+// pixel centres grown by one pixel (the per-pixel test rounds by about 1e-4 pixel) and drops the row when one of its edge functions,
+// or nw, is negative at all four -- each is linear, so it is negative at every pixel of the block.  The rows kept are the four waves'
+// ballots, 32 bytes of LDS: bit r of word r / 64.  One barrier, reached by every thread; a mask word is then read into scalar
+// registers and every pixel walks its set bits in row order, so the row reads stay block-uniform as dibr_xr_kernel's are.  Bits < 48 go through
+// xr_cover (the screen: dibr_xr_kernel's facet, a / w and b / w, since a facet that covers no pixel of the block changes no hit);
+// bits >= 48 are the walls' functor in xr_tail.  bin == 0 (D2S_XR_BIN=0): every row is kept.
+__device__ __forceinline__ uint64_t xr_uniform64(uint64_t v) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+}
+// the row can cover no pixel centre of x0 .. x1, y0 .. y1
+__device__ __forceinline__ bool xr_row_out(const float* __restrict__ r, bool tri, float x0, float y0, float x1, float y1) {
+    const float xs[4] = {x0, x1, x0, x1}, ys[4] = {y0, y0, y1, y1};
+    float na = -INFINITY, nb = -INFINITY, nw = -INFINITY, ne = -INFINITY, nu = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float b = r[3] * xs[k] + r[4] * ys[k] + r[5], w = r[6] * xs[k] + r[7] * ys[k] + r[8];
+        na = fmaxf(na, r[0] * xs[k] + r[1] * ys[k] + r[2]); nb = fmaxf(nb, b); nw = fmaxf(nw, w);
+        ne = fmaxf(ne, r[12] * xs[k] + r[13] * ys[k] + r[14]); nu = fmaxf(nu, w - b);
+    }
+    return na < 0.f || nb < 0.f || nw < 0.f || ne < 0.f || (!tri && nu < 0.f);      // (a facet also ends at b = 1)
+}
+template <int MODE>
+struct XrTriWalls {
+    static constexpr bool ON = true;
+    const float* __restrict__ tab;                       // the eye's table: row 48 is triangle 0
+    const uint64_t* __restrict__ kept;                   // the block's four masks in LDS (re-read per word: one copy of the shading below)
+    float xc, yc;
+    const XrFrostDev& F;
+    const DibrGeomProj& g;
+    const uint8_t* __restrict__ lev0;
+    const uint8_t* __restrict__ lev1;
+    __device__ __forceinline__ bool operator()(float c[4]) const {
+        bool drew = false;
+#pragma unroll 1
+        for (int w = 0; w < 4; ++w) {
+            uint64_t m = xr_uniform64(kept[w]);
+            if (w == 0) m &= ~((1ull << XR_MAX_FACETS) - 1);
+            while (m) {
+                const int row = w * 64 + __builtin_ctzll(m);
+                m &= m - 1;
+                const float* __restrict__ r = tab + row * XR_ROW_FLOATS;
+                const XrPt p = xr_row_at(r, xc, yc);
+                const float ne = r[12] * xc + r[13] * yc + r[14];      // the wall's previous triangle's nb, negated (dibr_xr.h)
+                if (!(p.na >= 0.f && p.nb >= 0.f && (xr_tri_first(row - XR_MAX_FACETS) ? ne >= 0.f : ne > 0.f))) continue;
+                if (!(p.nw > 0.f && p.z >= -1.0f && p.z <= 1.0f)) continue;
+                const float a = p.na / p.nw, b = p.nb / p.nw;
+                float src[4];
+                if (frost_frag<MODE>(F, g, lev0, lev1, r[15] + a * r[16] + b * r[17], r[18] + a * r[19] + b * r[20],
+                                     r[21] + a * r[22] + b * r[23], src)) { glow_blend(c, src); drew = true; }
+            }
+        }
+        return drew;
+    }
+};
+template <int OUT_FMT, class D, int MODE>
+__global__ void __launch_bounds__(256)
+dibr_xr_frost_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
+                            const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrFrostDev F, const uint8_t* __restrict__ levels,
+                            int bin) {
+    __shared__ uint64_t kept[4];
+    const int ei = blockIdx.z % ex.n;
+    const float* __restrict__ tab = (const float*)(tab_all + ei * XR_FROST_CURVED_ROWS);
+    {
+        const int r = threadIdx.x, side = 16 * XR_BIN_TILES;
+        bool keep = r < XR_FROST_CURVED_ROWS;
+        if (keep && bin) {
+            const float x0 = ((float)(blockIdx.x * side) + 0.5f) - 0.5f * (float)ex.e[ei].w - 1.0f;
+            const float y0 = ((float)(blockIdx.y * side) + 0.5f) - 0.5f * (float)ex.e[ei].h - 1.0f;
+            keep = !xr_row_out(tab + r * XR_ROW_FLOATS, r >= XR_MAX_FACETS, x0, y0, x0 + (float)(side + 1), y0 + (float)(side + 1));
+        }
+        const uint64_t m = __ballot(keep);
+        if ((threadIdx.x & 63) == 0) kept[threadIdx.x >> 6] = m;
+    }
+    __syncthreads();
+    const uint64_t facets = xr_uniform64(kept[0]) & ((1ull << XR_MAX_FACETS) - 1);
+#pragma unroll 1
+    for (int t = 0; t < XR_BIN_TILES * XR_BIN_TILES; ++t) {
+        const XrPix px = xr_pix_at(ex, blockIdx.x * XR_BIN_TILES + t % XR_BIN_TILES, blockIdx.y * XR_BIN_TILES + t / XR_BIN_TILES);
+        if (!px.inside) continue;                          // (no barrier below)
+        XrHit h = {-1, 1.0f, 0.f, 0.f, 1.f};
+        XrPt p;
+        for (uint64_t m = facets; m; m &= m - 1) {
+            const int f = __builtin_ctzll(m);
+            xr_cover(tab + f * XR_ROW_FLOATS, f, px.xc, px.yc, h, p);
+        }
+        float sa = 0.f, sb = 0.f;
+        if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
+        const uint8_t* __restrict__ frame = rgb_all + (long)px.b * g.H * g.W * 3;
+        const uint8_t* __restrict__ chain = MODE == 2 ? levels + (long)px.b * F.chain_total : nullptr;      // (the veil never reads levels)
+        const XrTriWalls<MODE> walls = {tab, kept, px.xc, px.yc, F, g, (MODE == 2 && F.l0 > 0) ? chain + F.off0 : frame,
+                                        (MODE == 2 && F.l1 > 0) ? chain + F.off1 : frame};
+        xr_tail<OUT_FMT, D, 0, XrTriWalls<MODE>>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f,
+                                                 nullptr, walls);
+    }
 }
 
 // d2s_dibr_xr_eyes_glow_curved: the curved screen with its glow (_render_curved_glow, xr_viewer/effects.py:408-474, in _render_eye's
@@ -894,6 +996,7 @@ static int xr_workspace_query(int kind, int n_eyes, uint64_t* bytes) {
 extern "C" int d2s_dibr_xr_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_PLAIN, n_eyes, bytes); }
 extern "C" int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_GLOW_CURVED, n_eyes, bytes); }
 extern "C" int d2s_dibr_xr_frost_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_FROST, n_eyes, bytes); }
+extern "C" int d2s_dibr_xr_frost_curved_workspace(int n_eyes, uint64_t* bytes) { return xr_workspace_query(D2S_XR_KIND_FROST_CURVED, n_eyes, bytes); }
 
 static void xr_plan_result(const XrPlan& pl, d2s_xr_plan_result* res) {
     *res = d2s_xr_plan_result{sizeof(d2s_xr_plan_result), pl.kind, pl.rows_per_eye, pl.setup_launches, {pl.grid[0], pl.grid[1], pl.grid[2]},
@@ -918,10 +1021,11 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
                      const uint8_t* levels, void* stream, bool check_only) {
     D2S_REQUIRE(workspace, "null pointer (workspace)");
     D2S_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
-    D2S_REQUIRE(workspace_bytes >= pl.workspace_bytes, (pl.kind == D2S_XR_KIND_GLOW_CURVED ? "workspace_bytes below d2s_dibr_xr_glow_curved_workspace"
-                                                        : pl.kind == D2S_XR_KIND_FROST     ? "workspace_bytes below d2s_dibr_xr_frost_workspace"
-                                                                                           : "workspace_bytes below d2s_dibr_xr_workspace"));
-    if (pl.kind == D2S_XR_KIND_FROST) D2S_REQUIRE(pl.F.mode != 2 || levels, "null pointer (levels: the frosted look reads d2s_mip_chain's output)");
+    D2S_REQUIRE(workspace_bytes >= pl.workspace_bytes, (pl.kind == D2S_XR_KIND_GLOW_CURVED    ? "workspace_bytes below d2s_dibr_xr_glow_curved_workspace"
+                                                        : pl.kind == D2S_XR_KIND_FROST_CURVED ? "workspace_bytes below d2s_dibr_xr_frost_curved_workspace"
+                                                        : pl.kind == D2S_XR_KIND_FROST        ? "workspace_bytes below d2s_dibr_xr_frost_workspace"
+                                                                                              : "workspace_bytes below d2s_dibr_xr_workspace"));
+    if (pl.kind == D2S_XR_KIND_FROST || pl.kind == D2S_XR_KIND_FROST_CURVED) D2S_REQUIRE(pl.F.mode != 2 || levels, "null pointer (levels: the frosted look reads d2s_mip_chain's output)");
     else D2S_REQUIRE(pl.kind == D2S_XR_KIND_PLAIN || levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
     D2S_REQUIRE(rgb && depth && out, "null pointer");
     if (check_only) return D2S_OK;
@@ -936,10 +1040,14 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
             hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, st, chunk, (float*)(tab + i * stride + f0), n_floats);
         }
     const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
+    const char* bin_env = getenv("D2S_XR_BIN");      // "0": the binned kernel walks every row (read at the call)
+    const int bin = !(bin_env && bin_env[0] == '0' && bin_env[1] == 0);
 #define DIBR_XR(FMT, D) do { \
         if (pl.kind == D2S_XR_KIND_PLAIN) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex); \
         else if (pl.kind == D2S_XR_KIND_FROST && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 1>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels); \
         else if (pl.kind == D2S_XR_KIND_FROST) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 2>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels); \
+        else if (pl.kind == D2S_XR_KIND_FROST_CURVED && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_curved_kernel<FMT, D, 1>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, bin); \
+        else if (pl.kind == D2S_XR_KIND_FROST_CURVED) hipLaunchKernelGGL((dibr_xr_frost_curved_kernel<FMT, D, 2>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, bin); \
         else if (pl.kind == D2S_XR_KIND_GLOW) hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, levels); \
         else hipLaunchKernelGGL((dibr_xr_glow_curved_kernel<FMT, D>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, pl.Q, levels); } while (0)
     if (out_fmt == D2S_FMT_U8_HWC) { if (pl.up) DIBR_XR(D2S_FMT_U8_HWC, UpDep); else DIBR_XR(D2S_FMT_U8_HWC, FullDep); }
@@ -997,6 +1105,27 @@ extern "C" int d2s_dibr_xr_frost_plan(int dh, int dw, int batch, int H, int W, c
     D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
     XrPlan pl;
     const int rc = xr_plan(XR_ENTRY_FROST, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, nullptr, frost, pl);
+    if (rc) return rc;
+    xr_plan_result(pl, res);
+    return D2S_OK;
+}
+
+// The veil and frosted looks of the curved screen (xr_viewer/effects.py:189-254, 759-787): xr_plan's fifth entry and its host-only query.
+extern "C" int d2s_dibr_xr_eyes_frost_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                             const d2s_dibr_params* p, const double crop[4], const d2s_xr_screen* screen,
+                                             const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                                             uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels, void* stream) {
+    return dibr_xr_entry_any(XR_ENTRY_FROST_CURVED, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, nullptr, frost, levels, stream, false);
+}
+
+extern "C" int d2s_dibr_xr_frost_curved_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                             const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt,
+                                             const d2s_xr_frost* frost, d2s_xr_plan_result* res) {
+    D2S_REQUIRE(res, "null pointer (res)");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
+    XrPlan pl;
+    const int rc = xr_plan(XR_ENTRY_FROST_CURVED, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, nullptr, frost, pl);
     if (rc) return rc;
     xr_plan_result(pl, res);
     return D2S_OK;

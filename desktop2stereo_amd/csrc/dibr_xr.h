@@ -83,7 +83,8 @@ inline double xr_min_w(const XrSurface& S, const double vp[16]) {
 // One eye's table.  clip(a, b) = C0 + a * CA + b * CB; with D = diag(w / 2, -h / 2, 1): (xc, yc, 1) * clip.w = D * M * (a, b, 1),
 // M = [CA.xyw | CB.xyw | C0.xyw], so (a, b, 1) / clip.w = inverse(D * M) * (xc, yc, 1).  A facet seen edge-on (no inverse) covers no
 // pixel centre: its ha row becomes the constant -1.
-inline void xr_facet_row(const XrVert& p00, const XrVert& p10, const XrVert& p01, const double vp[16], int w, int h, XrFacet& F) {
+// tri: the row is a triangle (the curved frost's), he = hw - ha - hb, the edge p10 - p01
+inline void xr_facet_row(const XrVert& p00, const XrVert& p10, const XrVert& p01, const double vp[16], int w, int h, XrFacet& F, bool tri = false) {
     double dA[3], dB[3], C0[4], CA[4], CB[4];
     for (int i = 0; i < 3; ++i) { dA[i] = p10.p[i] - p00.p[i]; dB[i] = p01.p[i] - p00.p[i]; }
     xr_clip(vp, p00.p, 1.0, C0); xr_clip(vp, dA, 0.0, CA); xr_clip(vp, dB, 0.0, CB);
@@ -104,7 +105,7 @@ inline void xr_facet_row(const XrVert& p00, const XrVert& p10, const XrVert& p01
     for (int j = 0; j < 3; ++j) {
         F.ha[j] = (float)inv[0][j]; F.hb[j] = (float)inv[1][j]; F.hw[j] = (float)inv[2][j];
         F.hz[j] = (float)(CA[2] * inv[0][j] + CB[2] * inv[1][j] + C0[2] * inv[2][j]);
-        F.he[j] = (float)(inv[2][j] - inv[0][j]);
+        F.he[j] = tri ? (float)(inv[2][j] - inv[0][j] - inv[1][j]) : (float)(inv[2][j] - inv[0][j]);
     }
     F.u0 = (float)p00.u; F.ua = (float)(p10.u - p00.u); F.ub = (float)(p01.u - p00.u);
     F.v0 = (float)p00.v; F.va = (float)(p10.v - p00.v); F.vb = (float)(p01.v - p00.v);
@@ -341,8 +342,9 @@ struct XrFrostLayout { double front_depth, front_half_w, front_half_h, fx, fy; }
 inline bool xr_frost_on(const d2s_xr_frost* f) {      // the reference's early returns (effects.py:822-857); NaN was refused before
     return f && f->mode != 0 && f->intensity > 0.0 && !(f->mode == 1 && f->alpha <= 0.002);
 }
-// What d2s_dibr_xr_eyes_frost refuses about the frost, after xr_screen_check has accepted the screen
-inline int xr_frost_check(const d2s_xr_screen* s, const d2s_xr_frost* f) {
+// What d2s_dibr_xr_eyes_frost refuses about the frost, after xr_screen_check has accepted the screen.  curved_ok: the asking entry
+// (d2s_dibr_xr_eyes_frost_curved) draws the curved screen's walls.
+inline int xr_frost_check(const d2s_xr_screen* s, const d2s_xr_frost* f, bool curved_ok) {
     if (!f) return D2S_OK;
     D2S_REQUIRE(f->struct_size == sizeof(d2s_xr_frost), "d2s_xr_frost.struct_size must be sizeof(d2s_xr_frost) = 120");
     D2S_REQUIRE(f->mode >= 0 && f->mode <= 2, "bad frost mode (0 off, 1 veil, 2 frosted)");
@@ -352,7 +354,7 @@ inline int xr_frost_check(const d2s_xr_screen* s, const d2s_xr_frost* f) {
     D2S_REQUIRE(xr_finite(v, 14), "the frost's fields must be finite");
     D2S_REQUIRE(f->noise_scale >= 0.0 && f->lod >= 0.0, "frost noise_scale and lod must be >= 0");
     if (!xr_frost_on(f)) return D2S_OK;
-    if (s->curve != D2S_XR_CURVE_FLAT) {
+    if (s->curve != D2S_XR_CURVE_FLAT && !curved_ok) {
         set_error("unsupported: the frost and veil of a curved screen (a mesh of its own in the reference, _build_curved_frost_verts) "
                   "are not built; curve must be 0 with frost on");
         return D2S_E_UNSUPPORTED;
@@ -392,6 +394,72 @@ inline void xr_frost_walls(const d2s_xr_screen* s, const XrFrostLayout& L, const
         xr_facet_row(p00, p10, p01, vp, w, h, out[k]);
         out[k].u0 = (float)(f_al - 1.0); out[k].ua = horiz ? 0.f : 1.f; out[k].ub = (k == 1 || k == 3) ? 1.f : 0.f;    }
 }
+// ---- the veil and frosted looks of the curved screen (d2s_dibr_xr_eyes_frost_curved; _build_curved_frost_verts,
+// _render_curved_frost_with_uniforms, xr_viewer/effects.py:189-254, 759-787) ----
+// The reference's mesh is 98 quads of two triangles, one TRIANGLES draw: two long walls of 48 quads along the arc's curved edges
+// (horizontal: the top edge, then the bottom; vertical: u = 0, then u = 1), then one quad at each end of the arc.  A quad runs from
+// two strip vertices (rear, t = 0) to their points on the front rectangle (t = 1): (rear0, rear1, front0), (front0, rear1, front1).  A
+// long wall's quad is NOT planar (a chord of the arc against a straight front edge), so the unit is the triangle: 196 rows after the
+// strip's 48, in draw order.  A triangle's row is a facet row over (p00, p10, p01) with he = hw - ha - hb, the uv fields the affine
+// v_uv = (u, 1 - v), pad[] = (t0, ta, tb); covered <=> na >= 0, nb >= 0, he . (xc, yc, 1) >= 0, nw > 0, -1 <= z <= 1.
+// Within a wall the triangles are a chain, each sharing an edge with the next.  They are labelled so that the edge shared with the
+// predecessor is p10 - p01 (he) and the edge shared with the successor is p00 - p10 (b = 0): p00 is the vertex the triangle adds, p10
+// the one that stays.  Triangle k + 1's he row is then set to the exact negation of triangle k's float32 hb row and tested > 0 where
+// triangle k tests nb >= 0: one edge function for both, exactly one of the two covers a pixel centre (the strip's device).  That holds
+// while the eye sees both triangles from the same side.  Where it lies BETWEEN their two planes (a long wall's quads are not planar, so
+// a wall seen edge-on has a silhouette along some interior edge) both triangles lie on one side of the projected edge, as they do in
+// GL's rasteriser: -hb(k) then points the other way than he(k + 1), and the triangle keeps its own edge.  Two different walls share
+// only their first and last edges; there nothing of the kind is done.
+constexpr int XR_TRIS = 4 * XR_MAX_FACETS + 4, XR_FROST_CURVED_ROWS = XR_MAX_FACETS + XR_TRIS;      // 196, 244
+constexpr int XR_ENTRY_FROST_CURVED = 4;                // xr_plan's fifth entry
+constexpr int XR_BIN_TILES = 4;                         // a block bins for XR_BIN_TILES x XR_BIN_TILES tiles of 16 x 16 pixels
+constexpr uint32_t XR_BIN_LDS = 4 * sizeof(uint64_t);   // the bin list: one ballot per wave of the block
+// triangle k (0 .. 195) opens its wall: its he is its own edge, tested >= 0
+constexpr bool xr_tri_first(int k) { return k == 0 || k == 2 * XR_MAX_FACETS || k == 4 * XR_MAX_FACETS || k == 4 * XR_MAX_FACETS + 2; }
+
+struct XrWallVert { double p[3], u, v, t; };
+inline void xr_tri_row(const XrWallVert& p00, const XrWallVert& p10, const XrWallVert& p01, const double vp[16], int w, int h, XrFacet& F) {
+    auto vert = [](const XrWallVert& q) { XrVert x; for (int i = 0; i < 3; ++i) x.p[i] = q.p[i]; x.u = q.u; x.v = 1.0 - q.v; return x; };
+    xr_facet_row(vert(p00), vert(p10), vert(p01), vp, w, h, F, true);
+    F.pad[0] = (float)p00.t; F.pad[1] = (float)(p10.t - p00.t); F.pad[2] = (float)(p01.t - p00.t);
+}
+// One eye's 196 triangle rows from the strip's own double-precision vertices (S.all) and the front rectangle
+inline void xr_frost_curved_tris(const d2s_xr_screen* s, const XrSurface& S, const XrFrostLayout& L, const double vp[16], int w, int h, XrFacet* out) {
+    double R[3][3], c[3];
+    xr_basis(s, R, c);
+    const int N = XR_MAX_FACETS;
+    auto rear = [&](int col, int side) {
+        const XrVert& q = S.all[2 * col + side];
+        return XrWallVert{{q.p[0], q.p[1], q.p[2]}, q.u, q.v, 0.0};
+    };
+    auto front = [&](const XrWallVert& r) {
+        const double lx = (2.0 * r.u - 1.0) * L.front_half_w, ly = (2.0 * r.v - 1.0) * L.front_half_h;
+        XrWallVert f = r;
+        for (int i = 0; i < 3; ++i) f.p[i] = c[i] + R[i][0] * lx + R[i][1] * ly + R[i][2] * L.front_depth;
+        f.t = 1.0;
+        return f;
+    };
+    int k = 0;
+    auto quad = [&](const XrWallVert& r0, const XrWallVert& r1) {      // (rear0, rear1, front0), (front0, rear1, front1), labelled as above
+        const XrWallVert f0 = front(r0), f1 = front(r1);
+        xr_tri_row(r1, f0, r0, vp, w, h, out[k++]);
+        xr_tri_row(f1, r1, f0, vp, w, h, out[k++]);
+    };
+    const bool vert = s->curve == D2S_XR_CURVE_VERTICAL;
+    for (int wall = 0; wall < 2; ++wall) {
+        const int side = vert ? wall : 1 - wall;
+        for (int i = 0; i < N; ++i) quad(rear(i, side), rear(i + 1, side));
+    }
+    for (int end = 0; end < 2; ++end) quad(rear(end * N, 0), rear(end * N, 1));
+    auto live = [&](int t) { return !(out[t].ha[0] == 0.f && out[t].ha[1] == 0.f && out[t].ha[2] == -1.f); };
+    for (int t = 1; t < XR_TRIS; ++t) {
+        if (xr_tri_first(t) || !live(t - 1) || !live(t)) continue;
+        double same = 0.0;                                 // both rows are multiples of ONE line, the projected edge: of one sign?
+        for (int j = 0; j < 3; ++j) same -= (double)out[t].he[j] * (double)out[t - 1].hb[j];
+        if (same > 0.0)
+            for (int j = 0; j < 3; ++j) out[t].he[j] = -out[t - 1].hb[j];
+    }
+}
 // H x W: the frame (and its chain, frosted only)
 inline void xr_frost_dev(const d2s_xr_frost* f, int H, int W, XrFrostDev& F) {
     F = XrFrostDev{};
@@ -418,9 +486,11 @@ struct XrEyes { XrEyeDev e[2]; int n; float clear[4]; };
 constexpr int XR_LDS_ROW = XR_ROW_FLOATS + 1;
 constexpr uint32_t XR_CURVED_LDS = (XR_PIECES * XR_LDS_ROW + XR_SEAMS * 3) * sizeof(float);
 // rows an eye's table occupies in the workspace (d2s_dibr_xr_workspace, d2s_dibr_xr_glow_curved_workspace, d2s_dibr_xr_frost_workspace,
-// the kernels' stride).  FROST: the screen's rows, then the four wall rows directly after the rows written (row nf .. nf + 3)
+// d2s_dibr_xr_frost_curved_workspace, the kernels' stride).  FROST: the screen's rows, then the four wall rows directly after the rows
+// written (row nf .. nf + 3); FROST_CURVED: the strip's 48 rows, then the 196 triangles
 constexpr int xr_table_rows(int kind) {
-    return kind == D2S_XR_KIND_GLOW_CURVED ? XR_PIECES : kind == D2S_XR_KIND_FROST ? XR_MAX_FACETS + XR_WALLS : XR_MAX_FACETS;
+    return kind == D2S_XR_KIND_FROST_CURVED ? XR_FROST_CURVED_ROWS : kind == D2S_XR_KIND_GLOW_CURVED ? XR_PIECES
+         : kind == D2S_XR_KIND_FROST ? XR_MAX_FACETS + XR_WALLS : XR_MAX_FACETS;
 }
 
 struct XrPlan {
@@ -428,11 +498,11 @@ struct XrPlan {
     DibrGeomProj g;
     XrEyes ex;
     XrGlowDev G;                                  // kind GLOW, GLOW_CURVED
-    XrFrostDev F;                                 // kind == FROST
+    XrFrostDev F;                                 // kind FROST, FROST_CURVED
     XrCurvedDev Q;                                // kind == GLOW_CURVED
     bool up;                                      // depth is not at the frame's resolution: the UpDep sampler
-    int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48), XR_PIECES, or FROST: facets + 4
-    XrFacet rows[2][XR_PIECES];
+    int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48), XR_PIECES, FROST: facets + 4,
+    XrFacet rows[2][XR_FROST_CURVED_ROWS];        // FROST_CURVED: 244
     int setup_launches;                           // all eyes': XR_CHUNK_FACETS rows travel in one launch's arguments
     unsigned grid[3];
     uint32_t lds_dynamic, lds_static;
@@ -440,9 +510,9 @@ struct XrPlan {
     uint64_t offs[2], total;                      // the out layout (xr_out_layout)
 };
 
-// entry: D2S_XR_ENTRY_* or XR_ENTRY_FROST, the public call that asks.  EYES takes no glow (the caller passes none); GLOW refuses a curved
-// screen with glow on; FROST takes the frost and no glow.  Every refusal of the four entries that needs no device pointer, in their
-// order; no HIP call.
+// entry: D2S_XR_ENTRY_*, XR_ENTRY_FROST or XR_ENTRY_FROST_CURVED, the public call that asks.  EYES takes no glow (the caller passes
+// none); GLOW refuses a curved screen with glow on; FROST takes the frost and no glow and refuses a curved screen with frost on,
+// FROST_CURVED draws it.  Every refusal of the five entries that needs no device pointer, in their order; no HIP call.
 inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, const d2s_xr_screen* screen,
                    const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, const d2s_xr_frost* frost, XrPlan& pl) {
     D2S_REQUIRE(p, "null pointer");
@@ -458,13 +528,15 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     if (rc) return rc;
     rc = xr_glow_check(screen, glow, entry == D2S_XR_ENTRY_GLOW_CURVED);
     if (rc) return rc;
-    rc = xr_frost_check(screen, entry == XR_ENTRY_FROST ? frost : nullptr);
+    const bool frost_entry = entry == XR_ENTRY_FROST || entry == XR_ENTRY_FROST_CURVED;
+    rc = xr_frost_check(screen, frost_entry ? frost : nullptr, entry == XR_ENTRY_FROST_CURVED);
     if (rc) return rc;
-    const bool glow_on = glow && glow->mode != 0, frost_on = entry == XR_ENTRY_FROST && xr_frost_on(frost);
+    const bool glow_on = glow && glow->mode != 0, frost_on = frost_entry && xr_frost_on(frost);
     D2S_REQUIRE(!(frost_on && frost->mode == 2) || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192),
                 "frame must be 2 .. 8192 on a side with the frosted look on (d2s_mip_chain's range)");
     D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
-    pl.kind = frost_on ? D2S_XR_KIND_FROST : !glow_on ? D2S_XR_KIND_PLAIN : screen->curve == D2S_XR_CURVE_FLAT ? D2S_XR_KIND_GLOW : D2S_XR_KIND_GLOW_CURVED;
+    const bool tris = frost_on && screen->curve != D2S_XR_CURVE_FLAT;      // (only XR_ENTRY_FROST_CURVED comes this far with one)
+    pl.kind = tris ? D2S_XR_KIND_FROST_CURVED : frost_on ? D2S_XR_KIND_FROST : !glow_on ? D2S_XR_KIND_PLAIN : screen->curve == D2S_XR_CURVE_FLAT ? D2S_XR_KIND_GLOW : D2S_XR_KIND_GLOW_CURVED;
     const bool curved = pl.kind == D2S_XR_KIND_GLOW_CURVED;
     xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, pl.offs, &pl.total);
     pl.G = XrGlowDev{};
@@ -485,7 +557,7 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
         }
     }
     pl.lds_dynamic = (uint32_t)pl.G.n_tex * 3 * sizeof(float);      // <= 65 532 bytes (an 8192 x 8192 frame)
-    pl.lds_static = curved ? XR_CURVED_LDS : 0;
+    pl.lds_static = curved ? XR_CURVED_LDS : tris ? XR_BIN_LDS : 0;
     if (pl.lds_dynamic + pl.lds_static > 65536) {                   // (only an 8192 x 8192 frame's 5 461 texels)
         set_error("unsupported: the frame's coarse mip levels and the piece table exceed 64 KB of LDS (a frame of 8192 x 8192)");
         return D2S_E_UNSUPPORTED;
@@ -509,7 +581,7 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     g.vpx = g.vpy = 0.f; g.vpw = g.vph = 1.f;
     g.cx = crop ? (float)crop[0] : 0.f; g.cy = crop ? (float)crop[1] : 0.f; g.cw = crop ? (float)crop[2] : 1.f; g.ch = crop ? (float)crop[3] : 1.f;
     pl.up = dh != H || dw != W;
-    pl.rows_per_eye = curved ? XR_PIECES : S.n + (frost_on ? XR_WALLS : 0);
+    pl.rows_per_eye = curved ? XR_PIECES : tris ? XR_FROST_CURVED_ROWS : S.n + (frost_on ? XR_WALLS : 0);
     pl.ex = XrEyes{};
     pl.ex.n = n_eyes;
     for (int k = 0; k < 4; ++k) pl.ex.clear[k] = screen->clear[k];
@@ -519,15 +591,17 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
         mw = std::max(mw, eyes[i].width); mh = std::max(mh, eyes[i].height);
         if (curved) xr_curved_table(S, P, glow->mode, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i]);
         else xr_facets(S, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i]);
-        if (frost_on) xr_frost_walls(screen, L, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i] + S.n);
+        if (tris) xr_frost_curved_tris(screen, S, L, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i] + S.n);
+        else if (frost_on) xr_frost_walls(screen, L, eyes[i].vp, eyes[i].width, eyes[i].height, pl.rows[i] + S.n);
     }
-    pl.setup_launches = n_eyes * cdiv(pl.rows_per_eye, XR_CHUNK_FACETS);               // per eye: 1 (flat, frost), 2 (curved), 3 (curved glow)
-    pl.grid[0] = cdiv(mw, 16); pl.grid[1] = cdiv(mh, 16); pl.grid[2] = n_eyes * batch;
+    pl.setup_launches = n_eyes * cdiv(pl.rows_per_eye, XR_CHUNK_FACETS);               // per eye: 1 (flat, frost), 2 (curved), 3 (curved glow), 11
+    const int side = tris ? 16 * XR_BIN_TILES : 16;                                    // the pixels a block draws, each way
+    pl.grid[0] = cdiv(mw, side); pl.grid[1] = cdiv(mh, side); pl.grid[2] = n_eyes * batch;
     pl.workspace_bytes = (uint64_t)n_eyes * xr_table_rows(pl.kind) * sizeof(XrFacet);
     return D2S_OK;
 }
 
-// The four entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
+// The five entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
 // every refusal, nothing launched (the view pipelines ask before they start the model).
 int dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                       const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,

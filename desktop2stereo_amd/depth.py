@@ -324,7 +324,7 @@ def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_tempor
     as the reference's _render_eye draws it (xr_viewer/effects.py:1023-1137).  Returns one device tensor per eye, [B,h,w,4|3].
     crop: None, (x, y, w, h) in uv, or "auto" (the MovieCrop of the first row's stream slot: the screen shows one crop).  The uniforms
     are the configured parameters', with the OpenXR screen's corner_radius (0.03) and frag_color.a kept (alpha="rgba") for the
-    compositor.  The glow: xr_eye_views_glow; the flat screen's veil and frosted looks: xr_eye_views_frost.  The border, controllers
+    compositor.  The glow: xr_eye_views_glow; the veil and frosted looks, flat or curved screen: xr_eye_views_frost.  The border, controllers
     and environment stay with the caller."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
@@ -351,7 +351,7 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
     xr_viewer/effects.py:476-585) and around a curved one (_render_curved_glow, effects.py:408-474; an eye outside the convex region the
     curved screen bounds, xr.XrScreen.eye_inside, is refused).  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
     frames' colour mip chain (ops.mip_chain); None builds it here, every call -- the reference refreshes its own every
-    _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  The flat screen's veil and frosted looks:
+    _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  The veil and frosted looks (flat or curved):
     xr_eye_views_frost.  The border, controllers and environment stay with the caller."""
     from . import xr as _xr
     p = _state["params"]
@@ -380,10 +380,10 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
 
 def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=None, multiplier=1.0, time=0.0, crop=None, corner_radius=0.03,
                        use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
-    """xr_eye_views with the reference's "veil" or "frosted" look around the FLAT screen drawn in the same launch
-    (_render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857).  frost: "veil" | "frosted" (the reference's defaults for
+    """xr_eye_views with the reference's "veil" or "frosted" look around the screen, flat or curved, drawn in the same launch
+    (_render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857; a curved screen: Engine.view_pipeline_xr_frost_curved).  frost: "veil" | "frosted" (the reference's defaults for
     head, multiplier = _glow_intensity_multiplier and time) | an xr.XrFrost.  levels: the frames' colour mip chain (ops.mip_chain) for
-    "frosted"; None builds it here, every call.  A curved screen's frost, the border, controllers and environment stay with the caller."""
+    "frosted"; None builds it here, every call.  The border, controllers and environment stay with the caller."""
     from . import xr as _xr
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
@@ -407,8 +407,9 @@ def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=Non
     if levels is None and frost.mode == "frosted" and frost.draws():
         levels = ops.mip_chain(t)
     dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
-    return eng.view_pipeline_xr_frost(t, p, dp, screen, eyes, frost, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
-                                      want_depth=want_depth, streams=streams)
+    run = eng.view_pipeline_xr_frost if getattr(screen, "curve", "flat") == "flat" else eng.view_pipeline_xr_frost_curved
+    return run(t, p, dp, screen, eyes, frost, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
+               streams=streams)
 
 
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,

@@ -402,7 +402,9 @@ _XR_WS: Dict[Tuple, torch.Tensor] = {}
 _XR_PIPELINES = {"eyes": ("d2s_view_pipeline_xr_streams", "view_pipeline_xr", "d2s_dibr_xr_workspace"),
                  "glow": ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow", "d2s_dibr_xr_workspace"),
                  "glow_curved": ("d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_glow_curved_workspace"),
-                 "frost": ("d2s_view_pipeline_xr_frost_streams", "view_pipeline_xr_frost", "d2s_dibr_xr_frost_workspace")}
+                 "frost": ("d2s_view_pipeline_xr_frost_streams", "view_pipeline_xr_frost", "d2s_dibr_xr_frost_workspace"),
+                 "frost_curved": ("d2s_view_pipeline_xr_frost_curved_streams", "view_pipeline_xr_frost_curved",
+                                  "d2s_dibr_xr_frost_curved_workspace")}
 
 
 def _xr_args(screen, eyes):
@@ -519,22 +521,39 @@ def dibr_xr_eyes_frost(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.Dibr
     """dibr_xr_eyes with the reference's "veil" or "frosted" look around the flat screen in the same launch (d2s_dibr_xr_eyes_frost;
     reference _render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857): frost = xr.XrFrost (None, mode "off", intensity
     <= 0 or a veil of alpha <= 0.002: exactly dibr_xr_eyes).  levels = mip_chain(frames) for "frosted"; the veil reads the frame alone.
-    A curved screen with frost on is refused.  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_frost_workspace bytes."""
+    A curved screen with frost on is refused here: dibr_xr_eyes_frost_curved draws it.  workspace: a caller-kept uint8 device tensor of
+    d2s_dibr_xr_frost_workspace bytes."""
     return _dibr_xr_call("d2s_dibr_xr_eyes_frost", "d2s_dibr_xr_frost_workspace", "dibr_xr_eyes_frost", frames, depth, dp, screen, eyes, crop,
                          out_u8, out, workspace, (frost, levels))
 
 
+def dibr_xr_eyes_frost_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, frost, levels=None, crop=None,
+                              out_u8: bool = True, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> list:
+    """dibr_xr_eyes_frost that also draws the veil or frosted look around a CURVED screen (d2s_dibr_xr_eyes_frost_curved; reference
+    _render_curved_frost_with_uniforms, xr_viewer/effects.py:759-787): the 196 triangles of xr.XrFrost.curved_wall_verts blended after
+    the curved strip in draw order; the eyes may be anywhere.  A flat screen is exactly dibr_xr_eyes_frost, a look that does not draw
+    exactly dibr_xr_eyes.  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_frost_curved_workspace bytes."""
+    return _dibr_xr_call("d2s_dibr_xr_eyes_frost_curved", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_frost_curved", frames, depth, dp,
+                         screen, eyes, crop, out_u8, out, workspace, (frost, levels))
+
+
+def dibr_xr_frost_curved_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, frost, crop=None,
+                              out_u8: bool = True) -> dict:
+    """dibr_xr_frost_plan for dibr_xr_eyes_frost_curved (d2s_dibr_xr_frost_curved_plan; host code, no GPU): kind "plain", "frost" or
+    "frost_curved" (244 rows per eye, blocks of 64 x 64 pixels), and the same fields."""
+    return dibr_xr_frost_plan(dh, dw, batch, H, W, dp, screen, eyes, frost, crop, out_u8, _query="d2s_dibr_xr_frost_curved_plan")
+
+
 def dibr_xr_frost_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, frost, crop=None,
-                       out_u8: bool = True) -> dict:
+                       out_u8: bool = True, _query: str = "d2s_dibr_xr_frost_plan") -> dict:
     """dibr_xr_plan for dibr_xr_eyes_frost (d2s_dibr_xr_frost_plan; host code, no GPU): kind "plain" or "frost", and the same fields."""
     sc, ea = _xr_args(screen, eyes)
     fs = None if frost is None else frost if isinstance(frost, _lib.XrFrost) else frost.c_struct()
     r = _lib.XrPlanResult()
     r.struct_size = C.sizeof(_lib.XrPlanResult)
-    check(_lib.load().d2s_dibr_xr_frost_plan(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
-                                             _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
-                                             FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None, C.byref(r)),
-          "d2s_dibr_xr_frost_plan")
+    check(getattr(_lib.load(), _query)(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
+                                       _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
+                                       FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None, C.byref(r)), _query)
     return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
             "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
             "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
@@ -949,6 +968,16 @@ class Engine:
         if frost is None:
             raise ValueError("view_pipeline_xr_frost: frost must be an xr.XrFrost (mode \"off\" for none)")
         return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels, "frost")
+
+    def view_pipeline_xr_frost_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, frost, levels=None,
+                                      crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
+                                      out: Optional[torch.Tensor] = None, streams=None):
+        """view_pipeline_xr_frost that also draws the look around a curved screen (d2s_view_pipeline_xr_frost_curved_streams).
+        Bit-identical to pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_frost_curved."""
+        if frost is None:
+            raise ValueError("view_pipeline_xr_frost_curved: frost must be an xr.XrFrost (mode \"off\" for none)")
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels,
+                                      "frost_curved")
 
     def close(self):
         if getattr(self, "_h", None):

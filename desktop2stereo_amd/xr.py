@@ -262,6 +262,39 @@ class XrFrost:
             out.append(wall)
         return np.array(out, np.float64)
 
+    def curved_wall_verts(self, screen: "XrScreen") -> np.ndarray:
+        """[588, 8] = world x y z, v_uv = (u, 1 - v), v_local = (2u - 1, 2v - 1, t): the one TRIANGLES draw of
+        _build_curved_frost_verts (effects.py:189-254) around a curved screen, in float64 -- 98 quads (rear0, rear1, front0), (front0,
+        rear1, front1): two long walls of 48 quads along the arc's curved edges (horizontal: the top edge, then the bottom; vertical:
+        u = 0, then u = 1), then one quad at each end of the arc.  rear: a strip vertex (t = 0, uv as the strip stores it, float32);
+        front: centre + R @ ((2u - 1) * front_half_w, (2v - 1) * front_half_h, front_depth) (t = 1).  The library
+        (d2s_dibr_xr_eyes_frost_curved) draws these 196 triangles."""
+        if screen.curve == "flat":
+            raise ValueError("curved_wall_verts: the screen is flat")
+        fd, fhw, fhh = self.layout(screen)
+        R, centre = screen.basis()
+        strip = screen.curved_verts()
+        strip[:, 3:] = strip[:, 3:].astype(np.float32)
+        n = CURVED_SEGMENTS
+
+        def pair(col, side):
+            x, y, z, u, v = strip[col * 2 + side]
+            f = centre + R[:3, :3] @ np.array([(u * 2.0 - 1.0) * fhw, (v * 2.0 - 1.0) * fhh, fd])
+            attr = [u, 1.0 - v, u * 2.0 - 1.0, v * 2.0 - 1.0]
+            return [x, y, z, *attr, 0.0], [f[0], f[1], f[2], *attr, 1.0]
+
+        out = []
+
+        def quad(a, b):
+            (r0, f0), (r1, f1) = a, b
+            out.extend([r0, r1, f0, f0, r1, f1])
+        for side in ((0, 1) if screen.curve == "vertical" else (1, 0)):
+            for i in range(n):
+                quad(pair(i, side), pair(i + 1, side))
+        for col in (0, n):
+            quad(pair(col, 0), pair(col, 1))
+        return np.array(out, np.float64)
+
     def uniforms(self, screen: "XrScreen" = None, crop=(0.0, 0.0, 1.0, 1.0)) -> dict:
         """What the mode's setter hands its program (effects.py:651-718): the veil's five, frosted's eleven, and u_source_crop."""
         u = dict(u_source_crop=tuple(float(v) for v in crop), u_edge_inset=float(self.edge_inset), u_intensity=float(self.intensity),

@@ -524,7 +524,7 @@ int d2s_dibr_xr_eyes_glow(const uint8_t* rgb, const float* depth, int dh, int dw
  * on the inner side of all 50 outer piece planes by 1e-4 of the arc's radius -- a viewer behind the screen or beyond an end of the arc.
  * There translucent pieces overlap and would have to be blended in draw order: an ordered multi-hit kernel, not built.  Also
  * D2S_E_UNSUPPORTED: a frame of 8192 x 8192 (its coarse levels and the piece table exceed 64 KB of LDS).  The curved screen's frost and
- * veil (_build_curved_frost_verts), the border and the trilinear screen pass stay with the caller. */
+ * veil (_build_curved_frost_verts): d2s_dibr_xr_eyes_frost_curved below.  The border and the trilinear screen pass stay with the caller. */
 int d2s_dibr_xr_glow_curved_workspace(int n_eyes, uint64_t* bytes);
 int d2s_dibr_xr_eyes_glow_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                                  const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
@@ -614,6 +614,38 @@ int d2s_dibr_xr_eyes_frost(const uint8_t* rgb, const float* depth, int dh, int d
 int d2s_dibr_xr_frost_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
                            const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
                            d2s_xr_plan_result* res);
+
+/* The veil and frosted looks around the CURVED screen (d2s_version() >= 126): d2s_dibr_xr_eyes_frost's argument list; screen->curve 1 or
+ * 2 with a look that draws runs what EffectsMixin._render_curved_frost_with_uniforms draws (xr_viewer/effects.py:759-787; mesh
+ * _build_curved_frost_verts, effects.py:189-254; program _FROST_CURVED_VERT, xr_viewer/glsl.py:683-696, with the flat look's fragment
+ * programs) in _render_eye's order: clear; the curved strip exactly as d2s_dibr_xr_eyes draws it; then ONE draw of 588 vertices, 196
+ * triangles, with the depth test off, every covering triangle blended src + dst * (1 - src.a) in draw order -- two long walls of 48
+ * quads along the arc's curved edges (horizontal: top, then bottom; vertical: u = 0, then u = 1), then one quad at each end of the arc,
+ * each from two strip vertices (t = 0) to their points on the front rectangle of _frost_front_layout (t = 1).  A long wall's quad is
+ * not planar, so the unit is the triangle: v_uv = (u, 1 - v) and t are affine over it, interpolated perspective-correctly; a triangle
+ * is drawn where its plane point has clip w > 0 and NDC z in [-1, 1].  Consecutive triangles of a wall share one float32 edge function,
+ * so no pixel along an interior edge is drawn twice or not at all; between two different walls nothing of the kind is done.  An eye
+ * may be anywhere, outside the tube the walls form included: what overlaps is blended in draw order.
+ *   The triangles' rows follow the strip's 48 in the table: 244 rows of 96 bytes per eye, d2s_dibr_xr_frost_curved_workspace bytes,
+ *   written by 11 set-up launches per eye.  A block of the render launch draws 64 x 64 pixels: it first keeps, as four 64-bit masks in
+ *   LDS, the rows that can cover a pixel of that square grown by one pixel, and its pixels walk those alone.  The environment variable
+ *   D2S_XR_BIN=0, read at the call, makes every pixel walk all 244 rows: the same output bit for bit, for checks and timing.
+ * A flat screen: d2s_dibr_xr_eyes_frost, bit-identical.  A look that does not draw (frost NULL, mode 0, intensity <= 0, a veil with
+ * alpha <= 0.002): d2s_dibr_xr_eyes on the curved screen, bit-identical.  Refused, nothing launched, out untouched: everything
+ * d2s_dibr_xr_eyes_frost refuses apart from the curvature; D2S_E_INVALID: normal_offset != 0 with frost on; D2S_E_UNSUPPORTED: a
+ * vertex of the SCREEN with clip w <= 1e-6 (the walls' vertices may lie behind the eye); then the pointers, workspace (below
+ * d2s_dibr_xr_frost_curved_workspace) and levels for frosted.  The border and the trilinear screen pass stay with the caller.
+ * d2s_dibr_xr_frost_curved_plan: d2s_dibr_xr_frost_plan for this entry -- kind PLAIN, FROST or FROST_CURVED; FROST_CURVED: rows_per_eye
+ * 244, setup_launches 11 per eye, grid (ceil(max width / 64), ceil(max height / 64), n_eyes * batch), lds_static_bytes 32. */
+enum { D2S_XR_KIND_FROST_CURVED = 4 };
+int d2s_dibr_xr_frost_curved_workspace(int n_eyes, uint64_t* bytes);
+int d2s_dibr_xr_eyes_frost_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                  const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                  int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                  void* stream);
+int d2s_dibr_xr_frost_curved_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                  const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
+                                  d2s_xr_plan_result* res);
 
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
@@ -758,6 +790,15 @@ int d2s_view_pipeline_xr_frost_streams(d2s_engine* e, const uint8_t* frames, int
                                        const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int use_ema,
                                        void* out, int out_fmt, float* depth_full, void* workspace, uint64_t workspace_bytes,
                                        const d2s_xr_frost* frost, const uint8_t* levels, void* stream);
+/* d2s_view_pipeline_xr_frost_streams with d2s_dibr_xr_eyes_frost_curved as its last stage (d2s_version() >= 126): workspace as
+ * d2s_dibr_xr_frost_curved_workspace.  Bit-identical to d2s_pipeline(depth_full) followed by d2s_dibr_xr_eyes_frost_curved on the
+ * engine's map. */
+int d2s_view_pipeline_xr_frost_curved_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                              int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                              const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                              const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                              void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                              void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

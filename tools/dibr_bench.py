@@ -27,6 +27,10 @@
         d2s_dibr_xr_eyes_glow (the flat screen with the reference's glow in the same launch, every pixel of both eye images drawn) and
         d2s_mip_chain (the 1080p frame's colour mip chain, which the glow samples), alternated in one process with the flat eye call
         without glow through the old entry (d2s_dibr_xr_eyes) and through the new one (glow off): us per launch, ns per image pixel.
+    python tools/dibr_bench.py --xr-eye --curve h|v --frost veil|frosted [--ab-lib other/libd2s_hip.so]
+        d2s_dibr_xr_eyes_frost_curved against its ceiling (a) the plain curved call + (b) the flat call with the same look - (c) the
+        flat plain call, alternated in one process, with the D2S_XR_BIN=0 time (every pixel walks all 244 rows) and the curved glow
+        for scale.  --ab-lib: the other build's plain, curved-glow and flat-frost calls in the same rounds, each with its own margin.
     python tools/dibr_bench.py --xr-eye --frost veil|frosted [--ab-lib other/libd2s_hip.so]
         d2s_dibr_xr_eyes_frost (the flat screen with the reference's veil or frosted walls in the same launch), alternated in one
         process with the plain eye call through d2s_dibr_xr_eyes and through the new entry (frost off), the flat glow (for scale) and
@@ -151,7 +155,7 @@ if a.xr_eye:
     eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
     img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
     dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
-    for B in a.batch if a.frost else ():
+    for B in a.batch if a.frost and not a.curve else ():
         import ctypes as C
         from desktop2stereo_amd import _lib
         f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
@@ -215,6 +219,85 @@ if a.xr_eye:
             worst = max(med["this_lib_eyes"], med["this_lib_eyes_again"]) - max(med["other_lib_eyes"], med["other_lib_eyes_again"])
             print(f"    other build against itself: {med['other_lib_eyes_again'] - med['other_lib_eyes']:+.1f} us (the margin: {margin:.1f} us); this build's "
                   f"slower run - the other's slower run = {worst:+.1f} us: {'within' if worst <= margin else 'BEYOND'} the margin", flush=True)
+    for B in a.batch if a.frost and a.curve else ():
+        import ctypes as C
+        import dataclasses
+        from desktop2stereo_amd import _lib
+        flat = dataclasses.replace(screen, curve="flat")
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        frost = xr.XrFrost.veil() if a.frost == "veil" else xr.XrFrost.frosted(time=1.0)
+        glow = xr.XrGlow("glow", xr.glow_range_m(screen))
+        levels = ops.mip_chain(f)
+        out = torch.empty(ops.dibr_xr_shape(eyes, B, dp.alpha_mode)[1], dtype=torch.uint8, device=dev)
+        probe_s = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)      # clear alpha 0.5 marks the pixels nothing drew
+        probe_f = ops.dibr_xr_eyes_frost_curved(f[:1], d[:1], dp, screen, eyes, frost, levels[:1], out_u8=False)
+        n_px = 2 * ew * eh
+        share_screen = sum(int((e[..., 3] != 0.5).sum()) for e in probe_s) / n_px
+        share_wall = sum(int((p != q).any(-1).sum()) for p, q in zip(probe_s, probe_f)) / n_px
+
+        def all_rows():      # D2S_XR_BIN=0 is read at the call
+            os.environ["D2S_XR_BIN"] = "0"
+            ops.dibr_xr_eyes_frost_curved(f, d, dp, screen, eyes, frost, levels, out=out)
+            del os.environ["D2S_XR_BIN"]
+        runs = {"a_curved_plain": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out),
+                f"b_flat_{a.frost}": lambda: ops.dibr_xr_eyes_frost(f, d, dp, flat, eyes, frost, levels, out=out),
+                "c_flat_plain": lambda: ops.dibr_xr_eyes(f, d, dp, flat, eyes, out=out),
+                f"curved_{a.frost}": lambda: ops.dibr_xr_eyes_frost_curved(f, d, dp, screen, eyes, frost, levels, out=out),
+                f"curved_{a.frost}_all_rows": all_rows,
+                "curved_glow": lambda: ops.dibr_xr_eyes_glow_curved(f, d, dp, screen, eyes, glow, levels, out=out),
+                "a_curved_plain_again": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)}
+        pairs = []
+        if a.ab_lib:      # the other build's plain, glow and flat-frost calls on the same tensors and stream, through ctypes alone
+            other = C.CDLL(os.path.abspath(a.ab_lib))
+            other.d2s_version.restype = C.c_int
+            sc, fl, ea = screen.c_struct(), flat.c_struct(), xr.eye_array(eyes)
+            gs, fs = glow.c_struct(), frost.c_struct()
+            ws = torch.empty(2 * 52 * 96, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+
+            def raw(lib, name, scr, extra):      # both builds through the SAME host path: the C call alone
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = _lib.SYMBOLS[name]
+
+                def call():
+                    rc = fn(f.data_ptr(), d.data_ptr(), d.shape[1], d.shape[2], B, a.height, a.width, C.byref(dp), None, C.byref(scr), ea, 2,
+                            out.data_ptr(), _lib.FMT_U8_HWC, ws.data_ptr(), ws.numel(), *extra, st)
+                    assert rc == 0, rc
+                return call
+            print(f"--ab-lib {a.ab_lib}: d2s_version {other.d2s_version()} (this build {_lib.load().d2s_version()})", flush=True)
+            for label, name, scr, extra in (("plain_curved", "d2s_dibr_xr_eyes", sc, ()),
+                                            ("glow_curved", "d2s_dibr_xr_eyes_glow_curved", sc, (C.byref(gs), levels.data_ptr())),
+                                            (f"flat_{a.frost}", "d2s_dibr_xr_eyes_frost", fl, (C.byref(fs), levels.data_ptr()))):
+                o, m = raw(other, name, scr, extra), raw(_lib.load(), name, scr, extra)
+                m(); torch.cuda.synchronize(); mine = out.clone()
+                o(); torch.cuda.synchronize()
+                print(f"    {label}: the other build's output is {'bit-identical to' if torch.equal(mine, out) else 'DIFFERENT from'} this build's", flush=True)
+                runs.update({f"other_{label}": o, f"this_{label}": m, f"other_{label}_again": o, f"this_{label}_again": m})
+                pairs.append(label)
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"xr-eye {screen.curve} {a.frost} {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}, medians of {a.rounds} rounds x {a.iters} launches; the "
+              f"screen covers {share_screen:.3f} of the images, the walls change {share_wall:.3f}:", flush=True)
+        for k in runs:
+            print(f"    {k:30s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {1e3 * med[k] / (B * n_px):.4f} ns / image pixel)", flush=True)
+        ceiling = med["a_curved_plain"] + med[f"b_flat_{a.frost}"] - med["c_flat_plain"]
+        print(f"    ceiling (a) + (b) - (c) = {ceiling:.1f} us; curved {a.frost} - ceiling = {med[f'curved_{a.frost}'] - ceiling:+.1f} us "
+              f"({100.0 * (med[f'curved_{a.frost}'] / ceiling - 1.0):+.1f} %); all 244 rows per pixel (D2S_XR_BIN=0): {med[f'curved_{a.frost}_all_rows']:.1f} us; "
+              f"(a) against itself {med['a_curved_plain_again'] - med['a_curved_plain']:+.1f} us", flush=True)
+        for label in pairs:
+            margin = abs(med[f"other_{label}_again"] - med[f"other_{label}"])
+            worst = max(med[f"this_{label}"], med[f"this_{label}_again"]) - max(med[f"other_{label}"], med[f"other_{label}_again"])
+            print(f"    {label}: other build against itself {med[f'other_{label}_again'] - med[f'other_{label}']:+.1f} us (the margin: {margin:.1f} us); this "
+                  f"build's slower run - the other's slower run = {worst:+.1f} us: {'within' if worst <= margin else 'BEYOND'} the margin", flush=True)
     for B in a.batch if a.glow and a.curve and not a.frost else ():
         import dataclasses
         flat = dataclasses.replace(screen, curve="flat")
