@@ -75,6 +75,12 @@ class XrFrost(C.Structure):
                 ("threshold", C.c_double), ("noise_scale", C.c_double), ("blend", C.c_double), ("diffuse", C.c_double), ("time", C.c_double)]
 
 
+class XrPanorama(C.Structure):
+    """d2s_xr_panorama: the panorama background behind the screen (ray: per eye image, NDC (x, y, 1) -> world direction, row-major)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flip_y", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("yaw_offset", C.c_double), ("exposure", C.c_double), ("ray", (C.c_double * 9) * 2)]
+
+
 XR_GLOW = {"off": 0, "glow": 1, "glow2": 2}
 XR_FROST = {"off": 0, "veil": 1, "frosted": 2}
 XR_CURVE = {"flat": 0, "horizontal": 1, "vertical": 2}      # D2S_XR_CURVE_*
@@ -272,6 +278,18 @@ SYMBOLS = {
                                                             C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                             C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,
                                                             C.c_uint64, C.POINTER(XrFrost), _P, _P]),
+    # the panorama background behind the screen (xr_viewer/effects.py:930-1021, xr_viewer/glsl.py:57-94): the frost entries' argument
+    # lists, then the glow, the panorama, its image and its chain
+    "d2s_dibr_xr_eyes_panorama": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P, C.c_uint64, C.POINTER(XrFrost), _P,
+                                            C.POINTER(XrGlow), C.POINTER(XrPanorama), _P, _P, _P]),
+    "d2s_dibr_xr_panorama_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, C.POINTER(XrFrost), C.POINTER(XrGlow),
+                                            C.POINTER(XrPanorama), C.POINTER(XrPlanResult)]),
+    "d2s_view_pipeline_xr_panorama_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
+                                                        C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                                        C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,
+                                                        C.c_uint64, C.POINTER(XrFrost), _P, C.POINTER(XrGlow), C.POINTER(XrPanorama), _P, _P, _P]),
     "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,

@@ -582,16 +582,17 @@ struct XrWalls {
         return drew;
     }
 };
-template <int OUT_FMT, class D, int N, class WALLS = XrNoWalls>
+// BG: the background an uncovered pixel starts from (dibr_pano.h): XrClearBg, the clear colour, or XrPanoBg, the panorama.
+template <int OUT_FMT, class D, int N, class WALLS = XrNoWalls, class BG = XrClearBg>
 __device__ __forceinline__ void xr_tail(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
                                         const DibrGeomProj& g, const XrEyes& ex, const XrGlowDev& G, const float* __restrict__ lds,
                                         const XrPix& px, bool covered, float sa, float sb, bool plane, float ga, float gb, const XrDraw* draws,
-                                        const WALLS walls = WALLS()) {
+                                        const WALLS walls = WALLS(), const BG bg = BG()) {
     const int nch = g.alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
     const long o = px.e.out_off + (((long)px.b * px.e.h + px.y) * px.e.w + px.x) * nch;
     float c[4], src[4];
     if (!covered) {
-        c[0] = ex.clear[0] * 255.0f; c[1] = ex.clear[1] * 255.0f; c[2] = ex.clear[2] * 255.0f; c[3] = ex.clear[3];
+        bg(ex, px, c);
         if (N > 0 && plane && glow_frag(lds, G, g, ga, gb, false, src)) {
             glow_blend(c, src);
             if (g.alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) { c[0] *= c[3]; c[1] *= c[3]; c[2] *= c[3]; }
@@ -613,26 +614,33 @@ __device__ __forceinline__ void xr_tail(const uint8_t* __restrict__ rgb_all, con
 }
 
 // d2s_dibr_xr_eyes: every facet of the eye's table is tested.  No barrier in this kernel: a thread outside its image leaves at once.
-template <int OUT_FMT, class D>
+// BG (here and in the two kernels below): XrClearBg, or XrPanoBg with the panorama's XrPanoDev, image and chain behind it.
+template <class BG> __device__ __forceinline__ BG xr_bg(const typename BG::Dev& P, const uint8_t* __restrict__ pano_rgb, const uint8_t* __restrict__ pano_chain) {
+    if constexpr (BG::ON) return BG{P, pano_rgb, pano_chain}; else return BG{};
+}
+template <int OUT_FMT, class D, class BG = XrClearBg>
 __global__ void __launch_bounds__(256)
 dibr_xr_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
-               const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex) {
+               const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, typename BG::Dev P = {},
+               const uint8_t* __restrict__ pano_rgb = nullptr, const uint8_t* __restrict__ pano_chain = nullptr) {
     const XrPix px = xr_pix(ex);
     if (!px.inside) return;
     const float* __restrict__ tab = (const float*)(tab_all + px.ei * XR_MAX_FACETS);
     const XrHit h = xr_search_all(tab, px.e.nf, px.xc, px.yc);
     float sa = 0.f, sb = 0.f;
     if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
-    xr_tail<OUT_FMT, D, 0>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f, nullptr);
+    xr_tail<OUT_FMT, D, 0, XrNoWalls, BG>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f, nullptr,
+                                          XrNoWalls(), xr_bg<BG>(P, pano_rgb, pano_chain));
 }
 // d2s_dibr_xr_eyes_glow (flat screen, one facet).  The glow quad is the screen's plane: facet 0's homography without the 0..1 bound
 // gives its coordinates; it is drawn where clip w > 0 and NDC z is in [-1, 1].  (The quad ends at screen + range; the glow reaches 0
 // there or sooner -- edge_t = 1 -- so the quad's own bound is not tested.)  The chain is staged unless the block's whole tile is plain
 // screen or undrawn.  Barriers: xr_stage_chain's, reached by every thread; the threads outside the image leave after it.
-template <int OUT_FMT, class D>
+template <int OUT_FMT, class D, class BG = XrClearBg>
 __global__ void __launch_bounds__(256)
 dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
-                    const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrGlowDev G, const uint8_t* __restrict__ levels) {
+                    const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrGlowDev G, const uint8_t* __restrict__ levels,
+                    typename BG::Dev P = {}, const uint8_t* __restrict__ pano_rgb = nullptr, const uint8_t* __restrict__ pano_chain = nullptr) {
     extern __shared__ float xr_glow_lds[];               // [n_tex][3]
     const XrPix px = xr_pix(ex);
     const float* __restrict__ tab = (const float*)(tab_all + px.ei * XR_MAX_FACETS);
@@ -646,16 +654,18 @@ dibr_xr_glow_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict
     float sa = 0.f, sb = 0.f;
     if (h.best >= 0) xr_hit_uv(tab + h.best * XR_ROW_FLOATS, h, sa, sb);
     const XrDraw inner = {G.mode == 1 && plane, ga, gb};
-    xr_tail<OUT_FMT, D, 1>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, &inner);
+    xr_tail<OUT_FMT, D, 1, XrNoWalls, BG>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, &inner,
+                                          XrNoWalls(), xr_bg<BG>(P, pano_rgb, pano_chain));
 }
 
 // d2s_dibr_xr_eyes_frost (flat screen): dibr_xr_kernel with the four walls of the veil (MODE 1) or frosted (MODE 2) look blended after
 // the screen.  No barrier and no LDS: the wall rows are block-uniform global reads as the facet's are; the frosted taps read the two
 // chain levels textureLod(u_lod) mixes from global memory (at the default LOD 5.4 of a 1080p frame 60 x 33 and 30 x 16 texels).
-template <int OUT_FMT, class D, int MODE>
+template <int OUT_FMT, class D, int MODE, class BG = XrClearBg>
 __global__ void __launch_bounds__(256)
 dibr_xr_frost_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
-                     const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrFrostDev F, const uint8_t* __restrict__ levels) {
+                     const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrFrostDev F, const uint8_t* __restrict__ levels,
+                     typename BG::Dev P = {}, const uint8_t* __restrict__ pano_rgb = nullptr, const uint8_t* __restrict__ pano_chain = nullptr) {
     const XrPix px = xr_pix(ex);
     if (!px.inside) return;
     const float* __restrict__ tab = (const float*)(tab_all + px.ei * xr_table_rows(D2S_XR_KIND_FROST));
@@ -666,8 +676,8 @@ dibr_xr_frost_kernel(const uint8_t* __restrict__ rgb_all, const float* __restric
     const uint8_t* __restrict__ chain = MODE == 2 ? levels + (long)px.b * F.chain_total : nullptr;      // (the veil never reads levels)
     const XrWalls<MODE> walls = {tab + px.e.nf * XR_ROW_FLOATS, px.xc, px.yc, F, g, (MODE == 2 && F.l0 > 0) ? chain + F.off0 : frame,
                                  (MODE == 2 && F.l1 > 0) ? chain + F.off1 : frame};
-    xr_tail<OUT_FMT, D, 0, XrWalls<MODE>>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f,
-                                          nullptr, walls);
+    xr_tail<OUT_FMT, D, 0, XrWalls<MODE>, BG>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f,
+                                              nullptr, walls, xr_bg<BG>(P, pano_rgb, pano_chain));
 }
 
 // d2s_dibr_xr_eyes_frost_curved: the curved screen with the 196 triangles of its veil (MODE 1) or frosted (MODE 2) walls blended after it
@@ -1000,7 +1010,7 @@ extern "C" int d2s_dibr_xr_frost_curved_workspace(int n_eyes, uint64_t* bytes) {
 
 static void xr_plan_result(const XrPlan& pl, d2s_xr_plan_result* res) {
     *res = d2s_xr_plan_result{sizeof(d2s_xr_plan_result), pl.kind, pl.rows_per_eye, pl.setup_launches, {pl.grid[0], pl.grid[1], pl.grid[2]},
-                              pl.lds_dynamic, pl.lds_static, 0, pl.workspace_bytes, pl.total, {pl.offs[0], pl.offs[1]}};
+                              pl.lds_dynamic, pl.lds_static, pl.pano ? 1u : 0u, pl.workspace_bytes, pl.total, {pl.offs[0], pl.offs[1]}};
 }
 extern "C" int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
                                 const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow,
@@ -1016,9 +1026,25 @@ extern "C" int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int
     return D2S_OK;
 }
 
+// xr_launch's render launch with the panorama behind the screen: kind PLAIN, GLOW or FROST (xr_plan refused the others)
+static int xr_launch_pano(const XrPlan& pl, const uint8_t* rgb, const float* depth, void* out, int out_fmt, const XrFacet* tab, const uint8_t* levels,
+                          const uint8_t* pano_rgb, const uint8_t* pano_levels, hipStream_t st) {
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
+#define DIBR_XR_PANO(FMT, D) do { \
+        if (pl.kind == D2S_XR_KIND_PLAIN) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.P, pano_rgb, pano_levels); \
+        else if (pl.kind == D2S_XR_KIND_FROST && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 1, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, pl.P, pano_rgb, pano_levels); \
+        else if (pl.kind == D2S_XR_KIND_FROST) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 2, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, pl.P, pano_rgb, pano_levels); \
+        else hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D, XrPanoBg>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, levels, pl.P, pano_rgb, pano_levels); } while (0)
+    if (out_fmt == D2S_FMT_U8_HWC) { if (pl.up) DIBR_XR_PANO(D2S_FMT_U8_HWC, UpDep); else DIBR_XR_PANO(D2S_FMT_U8_HWC, FullDep); }
+    else { if (pl.up) DIBR_XR_PANO(D2S_FMT_F32_HWC, UpDep); else DIBR_XR_PANO(D2S_FMT_F32_HWC, FullDep); }
+#undef DIBR_XR_PANO
+    D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
 // The device pointers and the workspace, the rows' upload, the render launch.
 static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, void* out, int out_fmt, void* workspace, uint64_t workspace_bytes,
-                     const uint8_t* levels, void* stream, bool check_only) {
+                     const uint8_t* levels, void* stream, bool check_only, const uint8_t* pano_rgb = nullptr, const uint8_t* pano_levels = nullptr) {
     D2S_REQUIRE(workspace, "null pointer (workspace)");
     D2S_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
     D2S_REQUIRE(workspace_bytes >= pl.workspace_bytes, (pl.kind == D2S_XR_KIND_GLOW_CURVED    ? "workspace_bytes below d2s_dibr_xr_glow_curved_workspace"
@@ -1028,6 +1054,7 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
     if (pl.kind == D2S_XR_KIND_FROST || pl.kind == D2S_XR_KIND_FROST_CURVED) D2S_REQUIRE(pl.F.mode != 2 || levels, "null pointer (levels: the frosted look reads d2s_mip_chain's output)");
     else D2S_REQUIRE(pl.kind == D2S_XR_KIND_PLAIN || levels, "null pointer (levels: the glow reads d2s_mip_chain's output)");
     D2S_REQUIRE(rgb && depth && out, "null pointer");
+    D2S_REQUIRE(!pl.pano || (pano_rgb && pano_levels), "null pointer (pano_rgb, pano_levels: the panorama and its d2s_mip_chain)");
     if (check_only) return D2S_OK;
     hipStream_t st = (hipStream_t)stream;
     const XrFacet* tab = (const XrFacet*)workspace;
@@ -1039,6 +1066,7 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
             for (int f = 0; f < nf; ++f) chunk.f[f] = pl.rows[i][f0 + f];
             hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, st, chunk, (float*)(tab + i * stride + f0), n_floats);
         }
+    if (pl.pano) return xr_launch_pano(pl, rgb, depth, out, out_fmt, tab, levels, pano_rgb, pano_levels, st);
     const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
     const char* bin_env = getenv("D2S_XR_BIN");      // "0": the binned kernel walks every row (read at the call)
     const int bin = !(bin_env && bin_env[0] == '0' && bin_env[1] == 0);
@@ -1056,14 +1084,14 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
     D2S_CHECK_LAUNCH();
     return D2S_OK;
 }
-
 int d2s::dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                            const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
                            void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const d2s_xr_frost* frost,
-                           const uint8_t* levels, void* stream, bool check_only) {
+                           const uint8_t* levels, void* stream, bool check_only, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
+                           const uint8_t* pano_levels) {
     XrPlan pl;
-    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl);
-    return rc ? rc : xr_launch(pl, rgb, depth, out, out_fmt, workspace, workspace_bytes, levels, stream, check_only);
+    const int rc = xr_plan(entry, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl, pano);
+    return rc ? rc : xr_launch(pl, rgb, depth, out, out_fmt, workspace, workspace_bytes, levels, stream, check_only, pano_rgb, pano_levels);
 }
 
 extern "C" int d2s_dibr_xr_eyes(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
@@ -1126,6 +1154,28 @@ extern "C" int d2s_dibr_xr_frost_curved_plan(int dh, int dw, int batch, int H, i
     D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
     XrPlan pl;
     const int rc = xr_plan(XR_ENTRY_FROST_CURVED, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, nullptr, frost, pl);
+    if (rc) return rc;
+    xr_plan_result(pl, res);
+    return D2S_OK;
+}
+
+// The panorama background behind the screen (xr_viewer/effects.py:930-1021): xr_plan's sixth entry and its host-only query.
+extern "C" int d2s_dibr_xr_eyes_panorama(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                                         const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                                         int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                         const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
+                                         const uint8_t* pano_levels, void* stream) {
+    return dibr_xr_entry_any(XR_ENTRY_PANORAMA, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, glow, frost, levels, stream, false, pano, pano_rgb, pano_levels);
+}
+
+extern "C" int d2s_dibr_xr_panorama_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                         const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
+                                         const d2s_xr_glow* glow, const d2s_xr_panorama* pano, d2s_xr_plan_result* res) {
+    D2S_REQUIRE(res, "null pointer (res)");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
+    XrPlan pl;
+    const int rc = xr_plan(XR_ENTRY_PANORAMA, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl, pano);
     if (rc) return rc;
     xr_plan_result(pl, res);
     return D2S_OK;

@@ -3,6 +3,7 @@
 // _build_model_mat4 (xr_viewer/screen.py:29-70), _build_curved_screen_verts (screen.py:110-173), _screen_effect_basis
 // (xr_viewer/effects.py:65-82), _CURVED_HALF_ANGLE_RAD (xr_viewer/constants.py:50-51), _render_eye (effects.py:1023-1137).
 #pragma once
+#include "dibr_pano.h"
 #include "dibr_tex.h"
 #include "mip.h"
 #include <cmath>
@@ -412,6 +413,7 @@ inline void xr_frost_walls(const d2s_xr_screen* s, const XrFrostLayout& L, const
 // only their first and last edges; there nothing of the kind is done.
 constexpr int XR_TRIS = 4 * XR_MAX_FACETS + 4, XR_FROST_CURVED_ROWS = XR_MAX_FACETS + XR_TRIS;      // 196, 244
 constexpr int XR_ENTRY_FROST_CURVED = 4;                // xr_plan's fifth entry
+constexpr int XR_ENTRY_PANORAMA = 5;                    // the sixth: d2s_dibr_xr_eyes_panorama, which takes a glow OR a frost, and the panorama
 constexpr int XR_BIN_TILES = 4;                         // a block bins for XR_BIN_TILES x XR_BIN_TILES tiles of 16 x 16 pixels
 constexpr uint32_t XR_BIN_LDS = 4 * sizeof(uint64_t);   // the bin list: one ballot per wave of the block
 // triangle k (0 .. 195) opens its wall: its he is its own edge, tested >= 0
@@ -500,6 +502,8 @@ struct XrPlan {
     XrGlowDev G;                                  // kind GLOW, GLOW_CURVED
     XrFrostDev F;                                 // kind FROST, FROST_CURVED
     XrCurvedDev Q;                                // kind == GLOW_CURVED
+    bool pano;                                    // the background is the panorama P (kind PLAIN, GLOW or FROST)
+    XrPanoDev P;
     bool up;                                      // depth is not at the frame's resolution: the UpDep sampler
     int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48), XR_PIECES, FROST: facets + 4,
     XrFacet rows[2][XR_FROST_CURVED_ROWS];        // FROST_CURVED: 244
@@ -512,9 +516,11 @@ struct XrPlan {
 
 // entry: D2S_XR_ENTRY_*, XR_ENTRY_FROST or XR_ENTRY_FROST_CURVED, the public call that asks.  EYES takes no glow (the caller passes
 // none); GLOW refuses a curved screen with glow on; FROST takes the frost and no glow and refuses a curved screen with frost on,
-// FROST_CURVED draws it.  Every refusal of the five entries that needs no device pointer, in their order; no HIP call.
+// FROST_CURVED draws it; PANORAMA takes a glow or a frost, flat or curved, as GLOW_CURVED and FROST_CURVED do, and with a panorama
+// refuses the two curved looks.  Every refusal of the six entries that needs no device pointer, in their order; no HIP call.
 inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, const d2s_xr_screen* screen,
-                   const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, const d2s_xr_frost* frost, XrPlan& pl) {
+                   const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, const d2s_xr_frost* frost, XrPlan& pl,
+                   const d2s_xr_panorama* pano = nullptr) {
     D2S_REQUIRE(p, "null pointer");
     int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
     if (rc) return rc;
@@ -526,12 +532,21 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     }
     rc = xr_screen_check(screen, eyes, n_eyes, batch);
     if (rc) return rc;
-    rc = xr_glow_check(screen, glow, entry == D2S_XR_ENTRY_GLOW_CURVED);
+    rc = xr_glow_check(screen, glow, entry == D2S_XR_ENTRY_GLOW_CURVED || entry == XR_ENTRY_PANORAMA);
     if (rc) return rc;
-    const bool frost_entry = entry == XR_ENTRY_FROST || entry == XR_ENTRY_FROST_CURVED;
-    rc = xr_frost_check(screen, frost_entry ? frost : nullptr, entry == XR_ENTRY_FROST_CURVED);
+    const bool frost_entry = entry == XR_ENTRY_FROST || entry == XR_ENTRY_FROST_CURVED || entry == XR_ENTRY_PANORAMA;
+    rc = xr_frost_check(screen, frost_entry ? frost : nullptr, entry == XR_ENTRY_FROST_CURVED || entry == XR_ENTRY_PANORAMA);
     if (rc) return rc;
     const bool glow_on = glow && glow->mode != 0, frost_on = frost_entry && xr_frost_on(frost);
+    D2S_REQUIRE(!(glow_on && frost_on), "at most one of glow and frost may be on (the reference draws one look)");
+    rc = xr_pano_check(entry == XR_ENTRY_PANORAMA ? pano : nullptr, n_eyes);
+    if (rc) return rc;
+    pl.pano = entry == XR_ENTRY_PANORAMA && pano;
+    if (pl.pano && screen->curve != D2S_XR_CURVE_FLAT && (glow_on || frost_on)) {
+        set_error("unsupported: a panorama behind the glow, veil or frosted look of a CURVED screen is not built (the two heaviest eye "
+                  "kernels get the background in a change of their own); with a panorama, curve must be 0 or glow and frost off");
+        return D2S_E_UNSUPPORTED;
+    }
     D2S_REQUIRE(!(frost_on && frost->mode == 2) || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192),
                 "frame must be 2 .. 8192 on a side with the frosted look on (d2s_mip_chain's range)");
     D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
@@ -542,6 +557,11 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     pl.G = XrGlowDev{};
     pl.Q = XrCurvedDev{};
     pl.F = XrFrostDev{};
+    pl.P = XrPanoDev{};
+    if (pl.pano) {
+        const XrEyeSize es[2] = {{eyes[0].width, eyes[0].height}, {eyes[n_eyes - 1].width, eyes[n_eyes - 1].height}};
+        xr_pano_dev(pano, es, n_eyes, pl.P);
+    }
     XrFrostLayout L{};
     if (frost_on) { xr_frost_dev(frost, H, W, pl.F); L = xr_frost_layout(screen, frost); }
     XrSurface S;
@@ -601,11 +621,12 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     return D2S_OK;
 }
 
-// The five entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
+// The six entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
 // every refusal, nothing launched (the view pipelines ask before they start the model).
 int dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                       const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,
                       void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const d2s_xr_frost* frost, const uint8_t* levels, void* stream,
-                      bool check_only);
+                      bool check_only, const d2s_xr_panorama* pano = nullptr, const uint8_t* pano_rgb = nullptr,
+                      const uint8_t* pano_levels = nullptr);
 
 }  // namespace d2s

@@ -1214,7 +1214,8 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
                                 const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
                                 const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
                                 void* workspace, uint64_t workspace_bytes, const d2s_xr_glow* glow, const uint8_t* levels, void* stream,
-                                int entry, const d2s_xr_frost* frost = nullptr) {
+                                int entry, const d2s_xr_frost* frost = nullptr, const d2s_xr_panorama* pano = nullptr,
+                                const uint8_t* pano_rgb = nullptr, const uint8_t* pano_levels = nullptr) {
     D2S_REQUIRE(frames && pp && dp && out && screen && eyes, "null pointer");
     D2S_REQUIRE(dp->struct_size == sizeof(d2s_dibr_params), "d2s_dibr_params.struct_size must be sizeof(d2s_dibr_params) = 80");
     uint64_t offs[2], total = 0;
@@ -1224,7 +1225,7 @@ static int view_pipeline_xr_any(d2s_engine* e, const uint8_t* frames, int batch,
     RC(pipeline_check(e, batch, stream_ids, H, W, depth_resolution, pre, &stride));
     auto warp = [&](bool check_only) {
         return dibr_xr_entry_any(entry, frames, e->depth_post, e->h, e->w, batch, H, W, dp, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
-                                 workspace_bytes, glow, frost, levels, stream, check_only);
+                                 workspace_bytes, glow, frost, levels, stream, check_only, pano, pano_rgb, pano_levels);
     };
     RC(warp(true));
     D2S_ON_DEVICE(e->device);
@@ -1285,6 +1286,19 @@ extern "C" int d2s_view_pipeline_xr_frost_curved_streams(d2s_engine* e, const ui
                                                          const d2s_xr_frost* frost, const uint8_t* levels, void* stream) {
     return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
                                 out_fmt, depth_full, workspace, workspace_bytes, nullptr, levels, stream, XR_ENTRY_FROST_CURVED, frost);
+}
+
+// the engine's pipeline up to the EMA step, then d2s_dibr_xr_eyes_panorama on the model-resolution depth
+extern "C" int d2s_view_pipeline_xr_panorama_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                                     int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                                     const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                                     const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                                     void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                                     const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
+                                                     const uint8_t* pano_levels, void* stream) {
+    return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
+                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, XR_ENTRY_PANORAMA, frost, pano, pano_rgb,
+                                pano_levels);
 }
 
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {

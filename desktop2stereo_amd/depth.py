@@ -324,8 +324,8 @@ def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_tempor
     as the reference's _render_eye draws it (xr_viewer/effects.py:1023-1137).  Returns one device tensor per eye, [B,h,w,4|3].
     crop: None, (x, y, w, h) in uv, or "auto" (the MovieCrop of the first row's stream slot: the screen shows one crop).  The uniforms
     are the configured parameters', with the OpenXR screen's corner_radius (0.03) and frag_color.a kept (alpha="rgba") for the
-    compositor.  The glow: xr_eye_views_glow; the veil and frosted looks, flat or curved screen: xr_eye_views_frost.  The border, controllers
-    and environment stay with the caller."""
+    compositor.  The glow: xr_eye_views_glow; the veil and frosted looks, flat or curved screen: xr_eye_views_frost; the panorama
+    background: xr_eye_views_panorama.  The controllers and the glTF environment stay with the caller."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -352,7 +352,7 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
     curved screen bounds, xr.XrScreen.eye_inside, is refused).  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
     frames' colour mip chain (ops.mip_chain); None builds it here, every call -- the reference refreshes its own every
     _glow_mipmap_interval frames, and a caller who wants that keeps a chain and passes it.  The veil and frosted looks (flat or curved):
-    xr_eye_views_frost.  The border, controllers and environment stay with the caller."""
+    xr_eye_views_frost; the panorama background: xr_eye_views_panorama.  The controllers and the glTF environment stay with the caller."""
     from . import xr as _xr
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
@@ -383,7 +383,8 @@ def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=Non
     """xr_eye_views with the reference's "veil" or "frosted" look around the screen, flat or curved, drawn in the same launch
     (_render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857; a curved screen: Engine.view_pipeline_xr_frost_curved).  frost: "veil" | "frosted" (the reference's defaults for
     head, multiplier = _glow_intensity_multiplier and time) | an xr.XrFrost.  levels: the frames' colour mip chain (ops.mip_chain) for
-    "frosted"; None builds it here, every call.  The border, controllers and environment stay with the caller."""
+    "frosted"; None builds it here, every call.  The panorama background: xr_eye_views_panorama.  The controllers and the glTF
+    environment stay with the caller."""
     from . import xr as _xr
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
@@ -410,6 +411,44 @@ def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=Non
     run = eng.view_pipeline_xr_frost if getattr(screen, "curve", "flat") == "flat" else eng.view_pipeline_xr_frost_curved
     return run(t, p, dp, screen, eyes, frost, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
                streams=streams)
+
+
+def xr_eye_views_panorama(frames, screen, eyes, panorama, pano_rgb, eyes_proj_view, glow=None, frost=None, levels=None, crop=None,
+                          corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
+    """xr_eye_views with the reference's panorama background behind the screen in the same launch (_render_panorama_background,
+    xr_viewer/effects.py:930-1021).  panorama: an xr.XrPanorama (yaw_offset_deg, exposure, flip_y); pano_rgb: the equirectangular image,
+    uint8 [h, w, 3] (numpy or device tensor), row 0 up; eyes_proj_view: one (proj, view) pair per entry of eyes (proj y-flipped where
+    the eye is), from which the rays are formed.  The panorama's mip chain is built once and kept while pano_rgb is the same object.
+    glow: an xr.XrGlow, or frost: an xr.XrFrost (at most one on; levels: the frames' mip chain, None builds it when the look reads
+    one); a curved screen takes a panorama only without a look.  The glTF environment, controllers and occlusion stay with the caller."""
+    p = _state["params"]
+    t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+    t = t.to(device=_device())
+    B, H, W, _ = t.shape
+    h, w, _s = engine_shape(H, W, p.depth_resolution, _state["cfg"].patch, p.square_input)
+    if B > _state["max_batch"]:
+        raise _lib.D2SError(f"batch {B} > configured max_batch {_state['max_batch']}")
+    eng = _ensure_engine_built(h, w, _fp8_first_inputs(t, (h, w)))
+    if isinstance(crop, str):
+        if crop != "auto":
+            raise ValueError('crop must be None, (x, y, w, h) or "auto"')
+        mc = movie_crop(0 if streams is None else int(streams[0]))
+        mc.update(t[0])
+        crop = tuple(mc.crop_uv)
+    kept = _state.get("panorama_chain")
+    if kept is None or kept[0] is not pano_rgb:
+        img = torch.from_numpy(np.ascontiguousarray(pano_rgb)) if isinstance(pano_rgb, np.ndarray) else pano_rgb
+        img = img.to(device=_device()).contiguous()
+        kept = _state["panorama_chain"] = (pano_rgb, img, ops.mip_chain(img).view(-1))
+    _, img, chain = kept
+    glow_on = glow is not None and glow.mode != "off"
+    frosted = frost is not None and frost.mode == "frosted" and frost.draws()
+    if levels is None and (glow_on or frosted):
+        levels = ops.mip_chain(t)
+    dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
+    ps = panorama.c_struct(eyes_proj_view, tuple(img.shape[:2]))
+    return eng.view_pipeline_xr_panorama(t, p, dp, screen, eyes, ps, img, chain, glow=glow, frost=frost, levels=levels, crop=crop,
+                                         use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth, streams=streams)
 
 
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,

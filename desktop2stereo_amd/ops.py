@@ -404,7 +404,9 @@ _XR_PIPELINES = {"eyes": ("d2s_view_pipeline_xr_streams", "view_pipeline_xr", "d
                  "glow_curved": ("d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_glow_curved_workspace"),
                  "frost": ("d2s_view_pipeline_xr_frost_streams", "view_pipeline_xr_frost", "d2s_dibr_xr_frost_workspace"),
                  "frost_curved": ("d2s_view_pipeline_xr_frost_curved_streams", "view_pipeline_xr_frost_curved",
-                                  "d2s_dibr_xr_frost_curved_workspace")}
+                                  "d2s_dibr_xr_frost_curved_workspace"),
+                 # (the panorama entry draws whichever kind the looks ask for: the largest table's workspace serves them all)
+                 "panorama": ("d2s_view_pipeline_xr_panorama_streams", "view_pipeline_xr_panorama", "d2s_dibr_xr_frost_curved_workspace")}
 
 
 def _xr_args(screen, eyes):
@@ -559,9 +561,65 @@ def dibr_xr_frost_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.D
             "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
 
 
-def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow_levels=None) -> list:
-    """The tensor checks and the call of the three eye-view entries.  glow_levels: None for d2s_dibr_xr_eyes, whose argument list has
-    no glow; (glow, levels) for the two that take them."""
+def _xr_pano_args(panorama, pano_rgb, pano_levels, device, who: str):
+    """(d2s_xr_panorama or None, the image, its chain) of a _lib.XrPanorama (xr.XrPanorama.c_struct; None = no panorama), the
+    panorama uint8 [h, w, 3] and mip_chain(pano_rgb).  The tensors are returned so that the caller keeps them alive over the call."""
+    if panorama is None:
+        return None, None, None
+    if not isinstance(panorama, _lib.XrPanorama):
+        raise ValueError(f"{who}: panorama must be xr.XrPanorama.c_struct(...)'s result (it carries the eyes' ray matrices) or None")
+    if pano_rgb is None or pano_levels is None:
+        return panorama, None, None                       # (the library refuses a missing image or chain with a panorama set)
+    _need_cuda(pano_rgb, "pano_rgb")
+    _need_cuda(pano_levels, "pano_levels")
+    h, w = panorama.height, panorama.width
+    if pano_rgb.dtype != torch.uint8 or tuple(pano_rgb.shape) != (h, w, 3) or pano_rgb.device != device or not pano_rgb.is_contiguous():
+        raise ValueError(f"{who}: pano_rgb must be a contiguous uint8 tensor of {(h, w, 3)} on {device}")
+    total = mip_shape(h, w)[1] if 2 <= h <= 8192 and 2 <= w <= 8192 else -1      # (the library refuses the size itself)
+    if pano_levels.dtype != torch.uint8 or pano_levels.device != device or not pano_levels.is_contiguous() or \
+            (total >= 0 and pano_levels.numel() != total):
+        raise ValueError(f"{who}: pano_levels must be mip_chain(pano_rgb), a contiguous uint8 tensor of {total} bytes on {device}")
+    return panorama, pano_rgb, pano_levels
+
+
+def dibr_xr_eyes_panorama(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, panorama, pano_rgb, pano_levels,
+                          glow=None, frost=None, levels=None, crop=None, out_u8: bool = True, out: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> list:
+    """dibr_xr_eyes with the reference's panorama background behind the screen (d2s_dibr_xr_eyes_panorama; reference
+    _render_panorama_background, xr_viewer/effects.py:930-1021): every pixel no facet covers starts from the equirectangular panorama
+    instead of screen.clear, sampled as the reference's texture() samples it (mipmapped, one LOD per 2 x 2 quad); the glow's outer
+    band and the walls blend over it.  panorama = xr.XrPanorama(...).c_struct([(proj, view), ...], pano_rgb.shape[:2]); pano_rgb
+    uint8 [h, w, 3], one image for the whole batch, row 0 up; pano_levels = mip_chain(pano_rgb).  glow = xr.XrGlow or frost =
+    xr.XrFrost (at most one on) with levels = mip_chain(frames) as their own calls take it.  A curved screen with a look on and a
+    panorama is refused.  panorama None: exactly the call of that look.  workspace: a caller-kept uint8 device tensor of
+    d2s_dibr_xr_frost_curved_workspace bytes (the largest table serves every kind)."""
+    return _dibr_xr_call("d2s_dibr_xr_eyes_panorama", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_panorama", frames, depth, dp,
+                         screen, eyes, crop, out_u8, out, workspace, (frost, levels), pano=(glow, panorama, pano_rgb, pano_levels))
+
+
+def dibr_xr_panorama_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, panorama, glow=None, frost=None,
+                          crop=None, out_u8: bool = True) -> dict:
+    """dibr_xr_plan for dibr_xr_eyes_panorama (d2s_dibr_xr_panorama_plan; host code, no GPU): the kind the looks ask for, the same
+    fields, and "panorama": whether the background is drawn."""
+    sc, ea = _xr_args(screen, eyes)
+    fs = None if frost is None else frost if isinstance(frost, _lib.XrFrost) else frost.c_struct()
+    gs = None if glow is None else glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
+    r = _lib.XrPlanResult()
+    r.struct_size = C.sizeof(_lib.XrPlanResult)
+    check(_lib.load().d2s_dibr_xr_panorama_plan(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
+                                                _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
+                                                FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None,
+                                                C.byref(gs) if gs is not None else None,
+                                                C.byref(panorama) if panorama is not None else None, C.byref(r)), "d2s_dibr_xr_panorama_plan")
+    return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
+            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
+            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)]), "panorama": bool(r.reserved)}
+
+
+def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow_levels=None, pano=None) -> list:
+    """The tensor checks and the call of the eye-view entries.  glow_levels: None for d2s_dibr_xr_eyes, whose argument list has
+    no glow; (glow, levels) for those that take them.  pano: d2s_dibr_xr_eyes_panorama's further arguments (glow, panorama, pano_rgb,
+    pano_levels) -- glow_levels is then its (frost, levels)."""
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
@@ -581,6 +639,15 @@ def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, o
             levels = levels.unsqueeze(0)
         gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, who)
         glow_args = (C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None)
+    if pano is not None:
+        glow2, panorama, pano_rgb, pano_levels = pano
+        g2 = None if glow2 is None else glow2 if isinstance(glow2, _lib.XrGlow) else glow2.c_struct()
+        if glow_args[1] is None and g2 is not None and levels is not None:      # the chain serves the glow when no frost was given
+            _, lv = _xr_glow_args(g2, levels, B, H, W, f.device, who)
+            glow_args = (glow_args[0], _ptr(lv))
+        ps, pr, pl_ = _xr_pano_args(panorama, pano_rgb, pano_levels, f.device, who)
+        glow_args += (C.byref(g2) if g2 is not None else None, C.byref(ps) if ps is not None else None,
+                      _ptr(pr) if pr is not None else None, _ptr(pl_) if pl_ is not None else None)
     offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
     nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
     dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
@@ -914,7 +981,7 @@ class Engine:
         view_pipeline_crop is: view_pipeline's parameter list is pinned by the ABI tests.)"""
         return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, None, None, "eyes")
 
-    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, entry):
+    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, entry, pano=None):
         sc, ea = _xr_args(screen, eyes)
         nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
         name, who, ws_query = _XR_PIPELINES[entry]
@@ -925,19 +992,39 @@ class Engine:
             lay["B"] = B
             if glow is not None:
                 lay["glow"] = _xr_glow_args(glow, levels, B, H, W, self.device, who)
+            if pano is not None:                          # (glow: the panorama entry's frost; its own glow travels in pano)
+                g2 = None if pano[0] is None else pano[0] if isinstance(pano[0], _lib.XrGlow) else pano[0].c_struct()
+                lv = lay.get("glow", (None, None))[1]
+                if lv is None and g2 is not None and levels is not None:
+                    lv = _xr_glow_args(g2, levels, B, H, W, self.device, who)[1]
+                lay["glow"] = (lay.get("glow", (None, None))[0], lv)
+                lay["pano"] = (g2,) + _xr_pano_args(pano[1], pano[2], pano[3], self.device, who)
             return (lay["total"],), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
         ws = _xr_workspace(len(ea), self.device, ws_query)
         nbytes = ws.numel()
 
         def fn(*a):      # (_run_pipeline ends every call with out, out_fmt, depth_full, stream: the workspace goes in front of the stream)
             gs, lv = lay.get("glow", (None, None))
-            glow_args = () if glow is None else (C.byref(gs), _ptr(lv) if lv is not None else None)
+            glow_args = () if glow is None and pano is None else (C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None)
+            if pano is not None:
+                g2, ps, pr, pl_ = lay["pano"]
+                glow_args += (C.byref(g2) if g2 is not None else None, C.byref(ps) if ps is not None else None,
+                              _ptr(pr) if pr is not None else None, _ptr(pl_) if pl_ is not None else None)
             return getattr(self.lib, name)(*a[:-1], _ptr(ws), nbytes, *glow_args, a[-1])
         mid = (C.byref(dp), _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea), int(use_ema))
         r = self._run_pipeline(fn, name, frames, p, spec, mid, want_depth, out, streams, who=who)
         flat = (r[0] if want_depth else r).view(-1)
         views = _xr_views(flat, ea, lay["B"], nch, lay["offs"])
         return (views, r[1]) if want_depth else views
+
+    def view_pipeline_xr_panorama(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, panorama, pano_rgb,
+                                  pano_levels, glow=None, frost=None, levels=None, crop=None, use_ema: bool = False, out_u8: bool = True,
+                                  want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
+        """view_pipeline_xr with the panorama background behind the screen (d2s_view_pipeline_xr_panorama_streams): panorama,
+        pano_rgb, pano_levels, glow, frost and levels as dibr_xr_eyes_panorama takes them.  Bit-identical to
+        pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_panorama."""
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels, "panorama",
+                                      pano=(glow, panorama, pano_rgb, pano_levels))
 
     def view_pipeline_xr_glow(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
                               use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,

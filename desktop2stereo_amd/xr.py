@@ -364,3 +364,40 @@ def eye_array(eyes) -> "C.Array":
     if len(es) not in (1, 2):
         raise ValueError("eyes must name 1 or 2 eye images")
     return (_lib.XrEye * len(es))(*es)
+
+
+def panorama_rays(proj, view) -> np.ndarray:
+    """[3,3] float64, NDC (x, y, 1) -> the un-normalised world direction of that pixel's ray, as _render_panorama_background and
+    _PANORAMA_FRAG form it (xr_viewer/effects.py:992-1015, xr_viewer/glsl.py:81-83): view's rotation transposed times inv(proj)
+    applied to (x, y, 1, 1).  The shader's division by max(|w|, 1e-6) and its two normalisations scale by a positive number, which the
+    direction's angles do not see.  proj is passed in already y-flipped when the eye is, as _render_eye does."""
+    a = np.linalg.inv(np.array(proj, np.float64).reshape(4, 4))
+    n = np.stack([a[:3, 0], a[:3, 1], a[:3, 2] + a[:3, 3]], 1)
+    return np.array(view, np.float64).reshape(4, 4)[:3, :3].T @ n
+
+
+@dataclass
+class XrPanorama:
+    """The reference's panorama background (include/d2s.h d2s_xr_panorama): _panorama_background_settings' yaw_offset_deg, exposure
+    and flip_y (xr_viewer/effects.py:981-990).  The image itself (uint8 [height, width, 3], row 0 up) and its mip_chain travel beside
+    it as tensors."""
+    yaw_offset_deg: float = 0.0
+    exposure: float = 1.0
+    flip_y: bool = False
+
+    def c_struct(self, eyes_proj_view, image_shape) -> "_lib.XrPanorama":
+        """eyes_proj_view: one (proj, view) pair per eye image, in the order of eyes[] (proj y-flipped where the eye is);
+        image_shape: the panorama's (height, width)."""
+        pv = list(eyes_proj_view)
+        if len(pv) not in (1, 2):
+            raise ValueError("eyes_proj_view must name 1 or 2 (proj, view) pairs")
+        s = _lib.XrPanorama()
+        s.struct_size = C.sizeof(_lib.XrPanorama)
+        s.flip_y = 1 if self.flip_y else 0
+        s.height, s.width = int(image_shape[0]), int(image_shape[1])
+        s.yaw_offset = float(self.yaw_offset_deg) / 360.0
+        s.exposure = float(self.exposure)
+        for i, (proj, view) in enumerate(pv):
+            for k, v in enumerate(panorama_rays(proj, view).ravel()):
+                s.ray[i][k] = float(v)
+        return s

@@ -647,6 +647,51 @@ int d2s_dibr_xr_frost_curved_plan(int dh, int dw, int batch, int H, int W, const
                                   const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
                                   d2s_xr_plan_result* res);
 
+/* The panorama background behind the screen (d2s_version() >= 127): what EffectsMixin._render_panorama_background draws into an eye
+ * image before everything else (xr_viewer/effects.py:930-1021, shader _PANORAMA_FRAG, xr_viewer/glsl.py:57-94).  Every pixel no screen
+ * facet covers starts from the panorama instead of screen->clear; the outer glow band and the walls then blend over it, alpha_mode
+ * acts, one store -- d2s_dibr_xr_eyes' own tail.  Covered pixels do not change at all.  Per uncovered pixel, in float:
+ *   dir = ray[eye] . (ndc.x, ndc.y, 1), the pixel's world direction (the reference's inv_view_rot . normalize((inv_proj . (ndc, 1, 1)).xyz
+ *   / max(|w|, 1e-6)); for the viewer's frustum projections w does not depend on the pixel, so this is one 3 x 3 matrix per eye);
+ *   u = atan(dir.x, -dir.z) / 2 pi + 0.5 + yaw_offset;  v = 0.5 - asin(dir.y / |dir|) / pi;  flip_y: v = 1 - v;
+ *   the coordinate sampled AND differenced is (fract(u), clamp(v, 0, 1));
+ *   texture(): LINEAR_MIPMAP_LINEAR / LINEAR, REPEAT in s with the level's own width, CLAMP_TO_EDGE in t, level 0 = pano_rgb, levels
+ *   1 .. q = pano_levels.  The implicit LOD is ONE per 2 x 2 quad of GL window pixels, quads aligned to even window x and y counted from
+ *   the bottom-left (row y of out is window row height - 1 - y), from the forward differences of the quad's lower-left pixel:
+ *   rho = max(|(du * width, dv * height)| over x + 1, the same over window y + 1), lambda = clamp(log2 rho, 0, q); the three points are
+ *   evaluated analytically also outside the image and under the screen.  Where fract(u) wraps inside a quad the difference is about 1
+ *   and the quad takes the coarsest levels: a seam two pixels wide, which the reference's render shows too.
+ *   background = (rgb * max(exposure, 0), 1) clamped to 0..255; the 8-bit framebuffer's quantisation before the blends is not
+ *   reproduced, as everywhere in these calls.
+ * Arguments: d2s_dibr_xr_eyes_frost's, then glow (d2s_dibr_xr_eyes_glow's; `levels` serves whichever look is on -- at most one of glow
+ * and frost may be), pano, pano_rgb = device uint8 [height, width, 3], ONE image for the whole batch, row 0 = v 0 = up, and
+ * pano_levels = d2s_mip_chain(pano_rgb, 1, height, width).  Kinds drawn with a panorama: PLAIN on a flat or curved screen, GLOW and
+ * FROST (veil and frosted) on a flat one.  D2S_E_UNSUPPORTED, nothing launched: a CURVED screen with glow or frost on and a panorama --
+ * those two kernels are the heaviest of the family and get the background in a change of their own.  pano == NULL: the call launches
+ * the kernel d2s_dibr_xr_eyes / _glow / _glow_curved / _frost / _frost_curved launches for these arguments, bit-identical, and asks
+ * that call's workspace.  D2S_E_INVALID: a bad struct_size; flip_y outside 0..1; height or width outside 2 .. 8192; a non-finite
+ * field; a ray matrix of an eye in use that is all zero; pano_rgb or pano_levels NULL with pano set; glow and frost both on; everything
+ * the underlying call refuses.  A negative exposure is 0, as the reference clamps it.  A refused call leaves out untouched.
+ * d2s_dibr_xr_panorama_plan: d2s_dibr_xr_frost_plan for this entry (host code, no GPU): the same refusals bar the device pointers;
+ * kind PLAIN, GLOW, GLOW_CURVED, FROST or FROST_CURVED; reserved = 1 when the panorama is drawn.
+ * Pinned by tests/golden/xr_panorama.npz: the reference's shader drawn off-screen (make_golden_xr_panorama.py). */
+typedef struct d2s_xr_panorama {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_panorama) = 176 */
+    int32_t  flip_y;           /* u_flip_y: the panorama settings' flip_y, 0 or 1 (NOT the eye's) */
+    int32_t  height, width;    /* the panorama, 2 .. 8192 each */
+    double   yaw_offset;       /* u_yaw_offset in turns: yaw_offset_deg / 360 */
+    double   exposure;         /* u_exposure; negative is 0 */
+    double   ray[2][9];        /* per entry of eyes[]: row-major 3 x 3, NDC (x, y, 1) -> un-normalised world direction */
+} d2s_xr_panorama;
+int d2s_dibr_xr_eyes_panorama(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                              const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out,
+                              int out_fmt, void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                              const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb, const uint8_t* pano_levels,
+                              void* stream);
+int d2s_dibr_xr_panorama_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                              const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
+                              const d2s_xr_glow* glow, const d2s_xr_panorama* pano, d2s_xr_plan_result* res);
+
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
  * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.
@@ -799,6 +844,16 @@ int d2s_view_pipeline_xr_frost_curved_streams(d2s_engine* e, const uint8_t* fram
                                               const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
                                               void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
                                               void* stream);
+/* d2s_view_pipeline_xr_frost_streams with d2s_dibr_xr_eyes_panorama as its last stage (d2s_version() >= 127): glow, pano, pano_rgb and
+ * pano_levels as that call takes them, the workspace as it asks.  Every refusal is made before the model starts.  Bit-identical to
+ * d2s_pipeline(depth_full) followed by d2s_dibr_xr_eyes_panorama on the engine's map. */
+int d2s_view_pipeline_xr_panorama_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                          int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                          const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                          const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                          void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                          const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
+                                          const uint8_t* pano_levels, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

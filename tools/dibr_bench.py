@@ -36,7 +36,15 @@
         process with the plain eye call through d2s_dibr_xr_eyes and through the new entry (frost off), the flat glow (for scale) and
         d2s_mip_chain.  --ab-lib: another build of the library (the parent commit's), loaded beside this one; its d2s_dibr_xr_eyes
         and this build's take the same arguments through the same bare C call in the same rounds, twice each, so that the other
-        build's spread against itself is the margin of the comparison."""
+        build's spread against itself is the margin of the comparison.
+    python tools/dibr_bench.py --xr-eye --panorama 4096 2048 [--glow glow|glow2 | --frost veil|frosted | --curve h|v] [--ab-lib other/libd2s_hip.so]
+        d2s_dibr_xr_eyes_panorama (the reference's equirectangular panorama behind the screen, in the same launch) against the same
+        look without a panorama, alternated in one process: us per launch and ns per BACKGROUND pixel (the pixels no facet covers),
+        the existing entry of that look against the new one with pano == NULL, and the panorama's d2s_mip_chain once.  With a flat
+        screen a look may be on; a curved screen takes the panorama without one.  --ab-lib: the other build's existing entry of the
+        look and this build's new entry with pano == NULL through the same bare C call in the same rounds, twice each: the other
+        build's spread against itself is the margin.  D2S_HIPCC_DEFS=-DD2S_PANO_NO_FETCH (tools/build_variant.sh) builds the variant
+        whose background skips the eight texel fetches: what is left is the coordinate and LOD arithmetic."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -61,6 +69,7 @@ ap.add_argument("--eye-size", type=int, nargs=2, default=[2064, 2208], help="--x
 ap.add_argument("--glow", default=None, choices=["glow", "glow2"], help="--xr-eye: time the glow eye call and mip_chain")
 ap.add_argument("--glow-range", type=float, default=None, help="--glow: range_m (default: xr.glow_range_m of the screen)")
 ap.add_argument("--frost", default=None, choices=["veil", "frosted"], help="--xr-eye: time the veil / frosted eye call (flat screen)")
+ap.add_argument("--panorama", type=int, nargs=2, default=None, metavar=("W", "H"), help="--xr-eye: time the panorama background of this size")
 ap.add_argument("--ab-lib", default=None, help="--frost: another build of libd2s_hip.so whose d2s_dibr_xr_eyes is timed in the same rounds")
 a = ap.parse_args()
 dev = torch.device("cuda")
@@ -155,6 +164,100 @@ if a.xr_eye:
     eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
     img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
     dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
+    for B in a.batch if a.panorama else ():
+        import ctypes as C
+        from desktop2stereo_amd import _lib
+        if a.curve and (a.glow or a.frost):
+            sys.exit("--panorama: a curved screen takes the panorama without a look (d2s_dibr_xr_eyes_panorama refuses the other)")
+        if a.glow and a.frost:
+            sys.exit("--panorama: at most one of --glow and --frost")
+        pw, ph = a.panorama
+        yy, xx = np.meshgrid((np.arange(ph) + 0.5) / ph, (np.arange(pw) + 0.5) / pw, indexing="ij")
+        rng = np.random.default_rng(3)
+        pano = np.stack([118 + 80 * (yy - 0.5) + 45 * np.sin(2 * np.pi * ((k + 1) * xx + 1.5 * yy)) + 45 * np.sin(2 * np.pi * (3 * xx - (k + 1) * yy))
+                         + rng.uniform(-3, 3, (ph, pw)) for k in range(3)], -1)
+        pr = torch.from_numpy(np.rint(np.clip(pano, 0, 255)).astype(np.uint8)).to(dev)
+        pl = ops.mip_chain(pr).view(-1)
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        frost = None if not a.frost else xr.XrFrost.veil() if a.frost == "veil" else xr.XrFrost.frosted(time=1.0)
+        glow = xr.XrGlow(a.glow, xr.glow_range_m(screen) if a.glow_range is None else a.glow_range) if a.glow else None
+        levels = ops.mip_chain(f) if glow is not None or frost is not None else None
+        pv = [(xr.fov_to_proj_mat4(*fovs[i]), xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0))) for i in range(2)]
+        ps = xr.XrPanorama().c_struct(pv, (ph, pw))
+        out = torch.empty(ops.dibr_xr_shape(eyes, B, dp.alpha_mode)[1], dtype=torch.uint8, device=dev)
+        n_px = 2 * ew * eh
+        probe = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)        # clear alpha 0.5 marks the pixels no facet covers
+        n_bg = sum(int((e[..., 3] == 0.5).sum()) for e in probe)
+        look = "glow" if glow is not None else "frost" if frost is not None else "plain"
+        if look == "glow":
+            old = lambda: ops.dibr_xr_eyes_glow(f, d, dp, screen, eyes, glow, levels, out=out)
+        elif look == "frost":
+            old = lambda: ops.dibr_xr_eyes_frost(f, d, dp, screen, eyes, frost, levels, out=out)
+        else:
+            old = lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)
+        new = lambda p, r, l: (lambda: ops.dibr_xr_eyes_panorama(f, d, dp, screen, eyes, p, r, l, glow=glow, frost=frost, levels=levels, out=out))
+        a0, b0 = [t.clone() for t in old()], [t.clone() for t in new(None, None, None)()]
+        assert all(torch.equal(x, y) for x, y in zip(a0, b0)), "pano == NULL differs from the existing entry"
+        runs = {f"{look}_old_entry": old, f"{look}_new_entry_no_panorama": new(None, None, None), f"{look}_panorama": new(ps, pr, pl),
+                f"{look}_old_entry_again": old, f"{look}_panorama_again": new(ps, pr, pl)}
+        if a.ab_lib:      # the other build's existing entry of the look and this build's new entry with pano == NULL: the bare C calls
+            other = C.CDLL(os.path.abspath(a.ab_lib))
+            name = {"plain": "d2s_dibr_xr_eyes", "glow": "d2s_dibr_xr_eyes_glow", "frost": "d2s_dibr_xr_eyes_frost"}[look]
+            getattr(other, name).restype, getattr(other, name).argtypes = _lib.SYMBOLS[name]
+            other.d2s_version.restype = C.c_int
+            sc, ea = screen.c_struct(), xr.eye_array(eyes)
+            ws = torch.empty(2 * 244 * 96, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            gs, fs = (glow.c_struct() if glow is not None else None), (frost.c_struct() if frost is not None else None)
+            lv = levels.data_ptr() if levels is not None else None
+            head = lambda: (f.data_ptr(), d.data_ptr(), d.shape[1], d.shape[2], B, a.height, a.width, C.byref(dp), None, C.byref(sc), ea, 2,
+                            out.data_ptr(), _lib.FMT_U8_HWC, ws.data_ptr(), ws.numel())
+            tail = {"plain": (), "glow": (C.byref(gs) if gs else None, lv), "frost": (C.byref(fs) if fs else None, lv)}[look]
+
+            def other_old():
+                rc = getattr(other, name)(*head(), *tail, st)
+                assert rc == 0, rc
+
+            def this_new():
+                rc = _lib.load().d2s_dibr_xr_eyes_panorama(*head(), C.byref(fs) if fs else None, lv, C.byref(gs) if gs else None, None, None, None, st)
+                assert rc == 0, rc
+            other_old()
+            torch.cuda.synchronize()
+            same = bool(torch.equal(a0[0], out[:a0[0].numel()].view(a0[0].shape)))
+            print(f"--ab-lib {a.ab_lib}: d2s_version {other.d2s_version()} (this build {_lib.load().d2s_version()}); its eye 0 is "
+                  f"{'bit-identical to' if same else 'DIFFERENT from'} this build's", flush=True)
+            runs = dict({"other_lib_old_entry": other_old, "this_lib_new_entry_no_panorama": this_new}, **runs, other_lib_old_entry_again=other_old,
+                        this_lib_new_entry_no_panorama_again=this_new)
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ops.mip_chain(pr, out=pl.view(1, -1)); torch.cuda.synchronize(); e0.record()
+        ops.mip_chain(pr, out=pl.view(1, -1))
+        e1.record(); torch.cuda.synchronize()
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        print(f"xr-eye {screen.curve} {look} + panorama {pw}x{ph} {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}, medians of {a.rounds} rounds x {a.iters} "
+              f"launches; {n_bg / n_px:.3f} of the images is background:", flush=True)
+        for k in runs:
+            print(f"    {k:40s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {1e3 * med[k] / (B * n_px):.4f} ns / image pixel)", flush=True)
+        cost = med[f"{look}_panorama"] - med[f"{look}_new_entry_no_panorama"]
+        print(f"    the panorama costs {cost:+.1f} us = {1e3 * cost / (B * n_bg):.4f} ns per background pixel; new entry without it - old entry = "
+              f"{med[f'{look}_new_entry_no_panorama'] - med[f'{look}_old_entry']:+.1f} us; old entry against itself {med[f'{look}_old_entry_again'] - med[f'{look}_old_entry']:+.1f} us; "
+              f"the panorama's mip_chain, once: {e0.elapsed_time(e1) * 1e3:.1f} us", flush=True)
+        if a.ab_lib:
+            margin = abs(med["other_lib_old_entry_again"] - med["other_lib_old_entry"])
+            worst = max(med["this_lib_new_entry_no_panorama"], med["this_lib_new_entry_no_panorama_again"]) - max(med["other_lib_old_entry"], med["other_lib_old_entry_again"])
+            print(f"    other build against itself: {med['other_lib_old_entry_again'] - med['other_lib_old_entry']:+.1f} us (the margin: {margin:.1f} us); this "
+                  f"build's slower run - the other's slower run = {worst:+.1f} us: {'within' if worst <= margin else 'BEYOND'} the margin", flush=True)
+    if a.panorama:
+        sys.exit(0)
     for B in a.batch if a.frost and not a.curve else ():
         import ctypes as C
         from desktop2stereo_amd import _lib
