@@ -189,6 +189,19 @@ class PrepatchProbeParams(C.Structure):
                 ("resid_elems", C.c_uint64), ("kernel", C.c_char * 64)]
 
 
+class VitProbeParams(C.Structure):
+    """d2s_vit_probe_params (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("op", C.c_int32), ("precision", C.c_int32), ("B", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("p", C.c_int32), ("Kp", C.c_int32), ("N", C.c_int32), ("D", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32),
+                ("Ho", C.c_int32), ("Wo", C.c_int32), ("C", C.c_int32), ("b3", C.c_float), ("max_depth", C.c_float), ("reserved", C.c_int32),
+                ("n", C.c_int64), ("x", C.c_void_p), ("out", C.c_void_p), ("addend", C.c_void_p), ("w3", C.c_void_p), ("cls", C.c_void_p),
+                ("pos", C.c_void_p), ("resid", C.c_void_p), ("x_elems", C.c_uint64), ("out_elems", C.c_uint64), ("addend_elems", C.c_uint64),
+                ("w3_elems", C.c_uint64), ("cls_elems", C.c_uint64), ("pos_elems", C.c_uint64), ("resid_elems", C.c_uint64),
+                ("kernel", C.c_char * 64)]
+
+
+VIT_OPS = {"patchify": 0, "bilinear": 1, "head_final": 2, "to_f32": 3, "amax": 4}      # D2S_VP_*
+
 TEMPORAL_OPS = {"groupnorm": 0, "temporal_attn": 1, "cache_store": 2, "geglu": 3, "cast_f32": 4, "layernorm": 5}      # D2S_TP_*
 
 LINEAR_SITES = {"patch": 0, "qkv": 1, "proj": 2, "fc1": 3, "fc2": 4, "neck_proj": 5, "neck_resize": 6, "tm_proj_in": 7,    # D2S_LIN_*
@@ -335,6 +348,7 @@ SYMBOLS = {
     "d2s_warp_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SbsParams), C.c_int, C.c_int, C.c_int,
                                 C.POINTER(WarpPlanResult)]),
     "d2s_preprocess_patches_probe": (C.c_int, [C.POINTER(PrepatchProbeParams), _P]),
+    "d2s_vit_probe": (C.c_int, [C.POINTER(VitProbeParams), _P]),
 }
 
 _lib = None

@@ -10,7 +10,6 @@ int launch_patchify(int prec, const float* x, void* A, int B, int h, int w, int 
 bool preprocess_patches_ok(int prec, int fmt, const d2s_pre_params* pre, int H, int W, int h, int w, int p, int Kp);
 int launch_preprocess_patches(int prec, const void* frames, int fmt, int batch, int H, int W, int decim_stride, const d2s_pre_params* pre,
                               void* A, int h, int w, int p, int Kp, const float* cls, const float* pos, float* resid, int N, int D, hipStream_t st);
-int launch_cls_rows(const float* cls, const float* pos, float* resid, int B, int N, int D, hipStream_t st);
 // The output type launch_layernorm writes for (engine precision, e4m3 scale, unit-format flag): the one place that decision is made;
 // the launcher switches on it and d2s_temporal_probe names the kernel by it.
 enum LnOut { LN_OUT_F32, LN_OUT_BF16, LN_OUT_BX3, LN_OUT_E4M3 };

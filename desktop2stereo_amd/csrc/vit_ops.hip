@@ -1,10 +1,11 @@
 // Small model-side kernels around the GEMMs (HBM / L2 bound):
-//   patchify        Conv2d(3->D, k=s=14) as im2col rows            (HF Dinov2PatchEmbeddings)
-//   cls_rows        cls token + pos[0] rows of the residual stream  (HF Dinov2Embeddings.forward)
+//   patchify        Conv2d(3->D, k=s=14) as im2col rows, and the cls token + pos[0] row of every frame's residual stream
+//                                                                   (HF Dinov2PatchEmbeddings, Dinov2Embeddings.forward)
 //   layernorm       fp32 residual -> T, eps 1e-6, optional cls drop (HF Dinov2Layer norm1/norm2, Dinov2Backbone.layernorm)
 //   bilinear_nhwc   align_corners=True up-sample of NHWC maps       (HF DepthAnythingFeatureFusionLayer / head)
 //   head_final      conv3 (1x1, C->1) + ReLU | sigmoid*max_depth                      (HF DepthAnythingDepthEstimationHead)
 #include "vit_ops.h"
+#include <cstdio>
 
 namespace d2s {
 
@@ -51,15 +52,6 @@ patchify_kernel(const float* __restrict__ x, T* __restrict__ A, int B, int h, in
         v = x[(((long)b * 3 + c) * h + py * p + i) * w + px * p + j];
     }
     A[idx] = cvt<T>(v);
-}
-
-__global__ void __launch_bounds__(256)
-cls_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos, float* __restrict__ resid,
-                int B, int N, int D) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= B * D) return;
-    int b = idx / D, d = idx % D;
-    resid[(long)b * N * D + d] = cls[d] + pos[d];
 }
 
 // one wave per row; D <= 1024 (4 float4 per lane)
@@ -176,12 +168,6 @@ int launch_patchify(int prec, const float* x, void* A, int B, int h, int w, int 
     return D2S_OK;
 }
 
-int launch_cls_rows(const float* cls, const float* pos, float* resid, int B, int N, int D, hipStream_t st) {
-    hipLaunchKernelGGL(cls_rows_kernel, dim3(cdiv((long)B * D, 256)), dim3(256), 0, st, cls, pos, resid, B, N, D);
-    D2S_CHECK_LAUNCH();
-    return D2S_OK;
-}
-
 LnOut layernorm_out_type(int prec, float fp8_qscale, bool bx3_out) {
     if (bx3_out) return LN_OUT_BX3;                 // bf16x3 engines: the unit format, so the consuming linear's A operand can travel by LDS-DMA
     if (fp8_qscale > 0.f) return LN_OUT_E4M3;       // e4m3 output for an fp8 linear: out = sat(LN(x) * qscale)
@@ -258,3 +244,82 @@ int launch_to_f32(int prec, const void* in, float* out, long n, hipStream_t st) 
 }
 
 }  // namespace d2s
+
+// ---- test probe ------------------------------------------------------------------------------------
+// One call of one launcher above on the caller's device buffers, as they are: nothing is packed, allocated or copied.  Every element the
+// kernel will index is checked against the element counts the caller states, and the up-sample's 16-byte accesses against the pointers,
+// before the launcher is reached; a launcher's own refusal (D2S_E_INVALID / D2S_E_UNSUPPORTED) launches nothing either.
+extern "C" int d2s_vit_probe(d2s_vit_probe_params* p, void* stream) {
+    using namespace d2s;
+    D2S_REQUIRE(p && p->struct_size == sizeof(d2s_vit_probe_params), "d2s_vit_probe_params.struct_size must be sizeof(d2s_vit_probe_params)");
+    p->kernel[0] = 0;
+    const int prec = p->precision;
+    D2S_REQUIRE(prec == D2S_PREC_BF16 || prec == D2S_PREC_FP32, "bad precision (bf16 or fp32)");
+    const char* tag = prec == D2S_PREC_BF16 ? "bf16" : "f32";
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t LIM = 1ull << 31;                       // (a b and c d at most 2^31 each: the product stays inside 64 bits)
+    auto holds = [&](uint64_t have, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {      // have >= a b c d, without overflow
+        return a <= LIM && b <= LIM && a * b <= LIM && c <= LIM && d <= LIM && c * d <= LIM && a * b * (c * d) <= have;
+    };
+    int rc = D2S_OK;
+    const char* name = "";
+    switch (p->op) {
+    case D2S_VP_PATCHIFY: {
+        const int B = p->B, h = p->h, w = p->w, ps = p->p, Kp = p->Kp, N = p->N, D = p->D;
+        D2S_REQUIRE(p->x && p->out, "patchify: null buffer");
+        D2S_REQUIRE(B >= 1 && ps >= 1 && ps <= 256 && h >= ps && w >= ps && h % ps == 0 && w % ps == 0 && Kp >= 3 * ps * ps, "patchify: bad shape");
+        D2S_REQUIRE(holds(p->x_elems, B, 3, h, w) && holds(p->out_elems, B, h / ps, w / ps, Kp), "patchify: x / A smaller than B * 3 * h * w / B * P * Kp");
+        if (p->cls) {
+            D2S_REQUIRE(p->pos && p->resid && N >= 1 && D >= 1, "patchify: cls without pos / resid, or bad N / D");
+            D2S_REQUIRE(p->cls_elems >= (uint64_t)D && p->pos_elems >= (uint64_t)D, "patchify: cls / pos smaller than D");
+            D2S_REQUIRE(holds(p->resid_elems, B, N, D, 1), "patchify: resid smaller than B * N * D");
+        }
+        rc = launch_patchify(prec, (const float*)p->x, p->out, B, h, w, ps, Kp, p->cls, p->pos, p->resid, N, D, st);
+        name = "patchify_kernel";
+        break;
+    }
+    case D2S_VP_BILINEAR: {
+        const int B = p->B, Hi = p->Hi, Wi = p->Wi, Ho = p->Ho, Wo = p->Wo, C = p->C;
+        D2S_REQUIRE(p->x && p->out, "bilinear_nhwc: null buffer");
+        D2S_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1 && C >= 1, "bilinear_nhwc: bad shape");
+        D2S_REQUIRE((uint64_t)Wi * C < LIM && (uint64_t)Wo * C < LIM, "bilinear_nhwc: a row of Wi * C / Wo * C elements must stay below 2^31");
+        D2S_REQUIRE(holds(p->x_elems, B, Hi, Wi, C) && holds(p->out_elems, B, Ho, Wo, C), "bilinear_nhwc: in / out smaller than B * H * W * C");
+        D2S_REQUIRE(!p->addend || holds(p->addend_elems, B, Ho, Wo, C), "bilinear_nhwc: addend smaller than B * Ho * Wo * C");
+        D2S_REQUIRE(((uintptr_t)p->x & 15) == 0 && ((uintptr_t)p->out & 15) == 0 && ((uintptr_t)p->addend & 15) == 0,
+                    "bilinear_nhwc: in / out / addend must be 16-byte aligned");
+        rc = launch_bilinear_nhwc(prec, p->x, p->out, B, Hi, Wi, Ho, Wo, C, st, p->addend);
+        name = "bilinear_nhwc_kernel";
+        break;
+    }
+    case D2S_VP_HEAD_FINAL: {
+        D2S_REQUIRE(p->x && p->out && p->w3, "head_final: null buffer");
+        D2S_REQUIRE(p->n >= 1 && p->n <= (int64_t)LIM && p->C >= 1, "head_final: bad shape");
+        D2S_REQUIRE(p->max_depth >= 0.f && p->max_depth <= 3.0e38f && p->b3 == p->b3, "head_final: bad max_depth / b3");
+        D2S_REQUIRE(holds(p->x_elems, p->n, p->C, 1, 1) && p->out_elems >= (uint64_t)p->n && p->w3_elems >= (uint64_t)p->C,
+                    "head_final: x / depth / w3 smaller than npix * C / npix / C");
+        rc = launch_head_final(prec, p->x, p->w3, p->b3, p->max_depth, (float*)p->out, p->n, p->C, st);
+        name = "head_final_kernel";
+        break;
+    }
+    case D2S_VP_TO_F32: {
+        D2S_REQUIRE(p->x && p->out && p->n >= 1 && p->n <= (1ll << 38), "to_f32: null buffer or bad count");
+        D2S_REQUIRE(p->x_elems >= (uint64_t)p->n && p->out_elems >= (uint64_t)p->n, "to_f32: in / out smaller than n");
+        rc = launch_to_f32(prec, p->x, (float*)p->out, p->n, st);
+        name = "to_f32_kernel";
+        break;
+    }
+    case D2S_VP_AMAX: {
+        D2S_REQUIRE(p->x && p->out && p->n >= 1 && p->n <= (1ll << 40), "amax: null buffer or bad count");
+        D2S_REQUIRE(p->x_elems >= (uint64_t)p->n && p->out_elems >= 1 && ((uintptr_t)p->out & 3) == 0, "amax: x smaller than n, or no aligned slot");
+        rc = launch_amax(prec, p->x, p->n, (float*)p->out, st);
+        name = "amax_kernel";
+        break;
+    }
+    default:
+        D2S_REQUIRE(false, "d2s_vit_probe: unknown op");
+    }
+    if (rc != D2S_OK) return rc;
+    D2S_HIP(hipStreamSynchronize(st));
+    snprintf(p->kernel, sizeof(p->kernel), "%s<%s>", name, tag);
+    return D2S_OK;
+}

@@ -1409,3 +1409,32 @@ def preprocess_patches_probe(precision: str, frames: torch.Tensor, A: torch.Tens
     with _on(frames.device) as st:
         check(_lib.load().d2s_preprocess_patches_probe(C.byref(q), st), "d2s_preprocess_patches_probe")
     return q.kernel.decode()
+
+
+def vit_probe(op: str, precision: str, x: torch.Tensor, out: torch.Tensor, *, B: int = 0, h: int = 0, w: int = 0, p: int = 0, Kp: int = 0,
+              N: int = 0, D: int = 0, Hi: int = 0, Wi: int = 0, Ho: int = 0, Wo: int = 0, channels: int = 0, n: int = 0, b3: float = 0.0,
+              max_depth: float = 0.0, addend: Optional[torch.Tensor] = None, w3: Optional[torch.Tensor] = None,
+              cls: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None) -> str:
+    """One launch of a small model-side launcher of vit_ops.hip (test probe, include/d2s.h d2s_vit_probe).  op: "patchify" | "bilinear" |
+    "head_final" | "to_f32" | "amax"; precision "bf16" | "fp32".  The tensors are device buffers ALREADY in the kernel's storage type and
+    are used in place -- views into larger guarded buffers are fine; the element counts the library checks against are what each tensor
+    holds from its first element.  out: A (patchify), the up-sampled map, the depth, the float32 copy, or the slot (amax: the tensor whose
+    first element is the slot).  Returns the name of the kernel that ran; raises D2SError where the library refuses."""
+    _need_cuda(x, "x")
+    q = _lib.VitProbeParams()
+    q.struct_size = C.sizeof(_lib.VitProbeParams)
+    q.op = _lib.VIT_OPS[op]
+    q.precision = {"bf16": PREC_BF16, "fp32": PREC_FP32}[precision]
+    q.B, q.h, q.w, q.p, q.Kp, q.N, q.D = int(B), int(h), int(w), int(p), int(Kp), int(N), int(D)
+    q.Hi, q.Wi, q.Ho, q.Wo, q.C, q.n = int(Hi), int(Wi), int(Ho), int(Wo), int(channels), int(n)
+    q.b3, q.max_depth = float(b3), float(max_depth)
+    for name, t in (("x", x), ("out", out), ("addend", addend), ("w3", w3), ("cls", cls), ("pos", pos), ("resid", resid)):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError("vit_probe: tensors must be contiguous")
+        setattr(q, name, t.data_ptr())
+        setattr(q, name + "_elems", t.numel())
+    with _on(x.device) as st:
+        check(_lib.load().d2s_vit_probe(C.byref(q), st), "d2s_vit_probe")
+    return q.kernel.decode()

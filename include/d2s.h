@@ -1078,6 +1078,40 @@ typedef struct d2s_prepatch_probe_params {
 } d2s_prepatch_probe_params;
 int d2s_preprocess_patches_probe(d2s_prepatch_probe_params* p, void* stream);
 
+/* Stand-alone probe of the small model-side launchers of vit_ops.hip (tests; d2s_version() >= 128): one call of one launcher on the
+ * caller's device buffers as they are (bf16 = raw bf16 bits).  The probe packs, allocates and copies nothing.  Every element the kernel
+ * will index is checked against the element counts stated here, and the up-sample's in / out / addend against 16-byte alignment, before
+ * the launcher is reached; a malformed case is an error return and nothing is launched.  Reports the kernel that ran. */
+enum {
+    D2S_VP_PATCHIFY = 0,       /* launch_patchify: x float [B,3,h,w] -> out = A [B (h/p) (w/p)][Kp] of the precision's type (columns >= 3 p^2
+                                  zero); cls != NULL: resid [B][N][D] row 0 of every frame = cls + pos[0:D], nothing else of resid */
+    D2S_VP_BILINEAR = 1,       /* launch_bilinear_nhwc: x [B,Hi,Wi,C] -> out [B,Ho,Wo,C] (align_corners) + addend [B,Ho,Wo,C] or NULL */
+    D2S_VP_HEAD_FINAL = 2,     /* launch_head_final: x [n][C], w3 float [C], b3 -> out float [n]: ReLU (max_depth 0) or sigmoid * max_depth */
+    D2S_VP_TO_F32 = 3,         /* launch_to_f32: x [n] of the precision's type -> out float [n] */
+    D2S_VP_AMAX = 4            /* launch_amax: out[0] = max(out[0], max |x[0:n]|), x of the precision's type, out float (4-byte aligned) */
+};
+typedef struct d2s_vit_probe_params {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_vit_probe_params) */
+    int32_t op;                /* D2S_VP_* */
+    int32_t precision;         /* D2S_PREC_BF16 / D2S_PREC_FP32: the storage type (see the ops) */
+    int32_t B;                 /* PATCHIFY, BILINEAR: frames */
+    int32_t h, w, p, Kp, N, D; /* PATCHIFY */
+    int32_t Hi, Wi, Ho, Wo, C; /* BILINEAR; HEAD_FINAL: C */
+    float   b3, max_depth;     /* HEAD_FINAL */
+    int32_t reserved;          /* 0 */
+    int64_t n;                 /* HEAD_FINAL: pixels; TO_F32, AMAX: elements */
+    const void* x;             /* the input (device) */
+    void* out;                 /* the output (device): A / out / depth / out / the slot */
+    const void* addend;        /* BILINEAR, or NULL */
+    const float* w3;           /* HEAD_FINAL */
+    const float* cls;          /* PATCHIFY: [D] or NULL */
+    const float* pos;          /* PATCHIFY: [>= D], row 0 of the position embedding */
+    float* resid;              /* PATCHIFY */
+    uint64_t x_elems, out_elems, addend_elems, w3_elems, cls_elems, pos_elems, resid_elems;   /* elements each buffer holds */
+    char kernel[64];           /* out: the kernel that ran, e.g. "patchify_kernel<bf16>", "bilinear_nhwc_kernel<f32>" */
+} d2s_vit_probe_params;
+int d2s_vit_probe(d2s_vit_probe_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ def test_header_symbols_exported(lib):
         assert getattr(lib, name) is not None
     assert lib.d2s_version() >= 110          # 110: d2s_dibr_params.struct_size
     assert lib.d2s_version() >= 118 and {"d2s_warp_plan", "d2s_preprocess_patches_probe"} <= declared
+    assert lib.d2s_version() >= 128 and "d2s_vit_probe" in declared
 
 
 def test_struct_layout_matches_header():
@@ -57,6 +58,11 @@ def test_struct_layout_matches_header():
     Q = _lib.PrepatchProbeParams                                                             # d2s_prepatch_probe_params
     assert (C.sizeof(Q) == 208 and Q.precision.offset == 4 and Q.decim_stride.offset == 24 and Q.D.offset == 48 and Q.pre.offset == 56
             and Q.frames.offset == 64 and Q.resid.offset == 96 and Q.frames_elems.offset == 104 and Q.kernel.offset == 144)
+    V = _lib.VitProbeParams                                                                  # d2s_vit_probe_params
+    assert (C.sizeof(V) == 256 and V.op.offset == 4 and V.precision.offset == 8 and V.B.offset == 12 and V.h.offset == 16 and V.D.offset == 36
+            and V.Hi.offset == 40 and V.C.offset == 56 and V.b3.offset == 60 and V.max_depth.offset == 64 and V.n.offset == 72
+            and V.x.offset == 80 and V.out.offset == 88 and V.addend.offset == 96 and V.w3.offset == 104 and V.cls.offset == 112
+            and V.resid.offset == 128 and V.x_elems.offset == 136 and V.resid_elems.offset == 184 and V.kernel.offset == 192)
 
 
 def test_sbs_shape_matches_reference_padding(lib):
