@@ -303,6 +303,18 @@ SYMBOLS = {
                                                         C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                         C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,
                                                         C.c_uint64, C.POINTER(XrFrost), _P, C.POINTER(XrGlow), C.POINTER(XrPanorama), _P, _P, _P]),
+    # the panorama also behind the curved screen's glow, veil and frosted looks: the panorama entries' argument lists
+    "d2s_dibr_xr_eyes_panorama_curved": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams),
+                                                   C.POINTER(C.c_double), C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, _P, C.c_int, _P,
+                                                   C.c_uint64, C.POINTER(XrFrost), _P, C.POINTER(XrGlow), C.POINTER(XrPanorama), _P, _P, _P]),
+    "d2s_dibr_xr_panorama_curved_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
+                                                   C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, C.POINTER(XrFrost),
+                                                   C.POINTER(XrGlow), C.POINTER(XrPanorama), C.POINTER(XrPlanResult)]),
+    "d2s_view_pipeline_xr_panorama_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                                               C.POINTER(PreParams), C.POINTER(PostParams), C.POINTER(DibrParams),
+                                                               C.POINTER(C.c_double), C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int,
+                                                               _P, C.c_int, _P, _P, C.c_uint64, C.POINTER(XrFrost), _P, C.POINTER(XrGlow),
+                                                               C.POINTER(XrPanorama), _P, _P, _P]),
     "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,

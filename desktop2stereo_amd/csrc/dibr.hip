@@ -738,11 +738,13 @@ struct XrTriWalls {
         return drew;
     }
 };
-template <int OUT_FMT, class D, int MODE>
+// BG: dibr_xr_kernel's.  The background is block-invariant: it is built once, outside the tile loop, and adds no barrier.
+template <int OUT_FMT, class D, int MODE, class BG = XrClearBg>
 __global__ void __launch_bounds__(256)
 dibr_xr_frost_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
                             const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrFrostDev F, const uint8_t* __restrict__ levels,
-                            int bin) {
+                            int bin, typename BG::Dev P = {}, const uint8_t* __restrict__ pano_rgb = nullptr,
+                            const uint8_t* __restrict__ pano_chain = nullptr) {
     __shared__ uint64_t kept[4];
     const int ei = blockIdx.z % ex.n;
     const float* __restrict__ tab = (const float*)(tab_all + ei * XR_FROST_CURVED_ROWS);
@@ -759,6 +761,7 @@ dibr_xr_frost_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __
     }
     __syncthreads();
     const uint64_t facets = xr_uniform64(kept[0]) & ((1ull << XR_MAX_FACETS) - 1);
+    const BG bg = xr_bg<BG>(P, pano_rgb, pano_chain);
 #pragma unroll 1
     for (int t = 0; t < XR_BIN_TILES * XR_BIN_TILES; ++t) {
         const XrPix px = xr_pix_at(ex, blockIdx.x * XR_BIN_TILES + t % XR_BIN_TILES, blockIdx.y * XR_BIN_TILES + t / XR_BIN_TILES);
@@ -775,8 +778,8 @@ dibr_xr_frost_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __
         const uint8_t* __restrict__ chain = MODE == 2 ? levels + (long)px.b * F.chain_total : nullptr;      // (the veil never reads levels)
         const XrTriWalls<MODE> walls = {tab, kept, px.xc, px.yc, F, g, (MODE == 2 && F.l0 > 0) ? chain + F.off0 : frame,
                                         (MODE == 2 && F.l1 > 0) ? chain + F.off1 : frame};
-        xr_tail<OUT_FMT, D, 0, XrTriWalls<MODE>>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f, 0.f,
-                                                 nullptr, walls);
+        xr_tail<OUT_FMT, D, 0, XrTriWalls<MODE>, BG>(rgb_all, dep_all, out_all, g, ex, XrGlowDev{}, nullptr, px, h.best >= 0, sa, sb, false, 0.f,
+                                                     0.f, nullptr, walls, bg);
     }
 }
 
@@ -789,12 +792,13 @@ dibr_xr_frost_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __
 // go through xr_cover, so a screen pixel has the facet, a / w and b / w of dibr_xr_kernel; a pixel no facet covers takes the band on
 // the piece the seams gave it.  Homographies per pixel: at most 3 facets + 2 others, whatever the strip's 48.
 // Barriers: the one after the rows' staging and xr_stage_chain's, each reached by every thread; the threads outside the image leave
-// after the second.
-template <int OUT_FMT, class D>
+// after the second.  BG: dibr_xr_kernel's; the background is formed in xr_tail, after both barriers.
+template <int OUT_FMT, class D, class BG = XrClearBg>
 __global__ void __launch_bounds__(256)
 dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all,
                            const XrFacet* __restrict__ tab_all, DibrGeomProj g, XrEyes ex, XrGlowDev G, XrCurvedDev Q,
-                           const uint8_t* __restrict__ levels) {
+                           const uint8_t* __restrict__ levels, typename BG::Dev P = {}, const uint8_t* __restrict__ pano_rgb = nullptr,
+                           const uint8_t* __restrict__ pano_chain = nullptr) {
     extern __shared__ float xr_glow_lds[];               // [n_tex][3]
     __shared__ float rows[XR_PIECES * XR_LDS_ROW];
     __shared__ float seams[XR_SEAMS * 3];
@@ -864,7 +868,8 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
     // the mesh's draw order (_build_curved_glow_band_verts:401-404): the u-long bands, then the v-long ones
     const XrDraw on_facet = {fband, sa, sb}, on_chord = {cband, ca, cb};
     const XrDraw draws[2] = {Q.vertical ? on_chord : on_facet, Q.vertical ? on_facet : on_chord};
-    xr_tail<OUT_FMT, D, 2>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, draws);
+    xr_tail<OUT_FMT, D, 2, XrNoWalls, BG>(rgb_all, dep_all, out_all, g, ex, G, xr_glow_lds, px, h.best >= 0, sa, sb, plane, ga, gb, draws,
+                                          XrNoWalls(), xr_bg<BG>(P, pano_rgb, pano_chain));
 }
 
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
@@ -1026,15 +1031,19 @@ extern "C" int d2s_dibr_xr_plan(int entry, int dh, int dw, int batch, int H, int
     return D2S_OK;
 }
 
-// xr_launch's render launch with the panorama behind the screen: kind PLAIN, GLOW or FROST (xr_plan refused the others)
+// xr_launch's render launch with the panorama behind the screen: every kind (the two curved looks: d2s_dibr_xr_eyes_panorama_curved's
+// plan only, xr_plan refuses them to d2s_dibr_xr_eyes_panorama).  bin: xr_launch's, the curved frost's.
 static int xr_launch_pano(const XrPlan& pl, const uint8_t* rgb, const float* depth, void* out, int out_fmt, const XrFacet* tab, const uint8_t* levels,
-                          const uint8_t* pano_rgb, const uint8_t* pano_levels, hipStream_t st) {
+                          const uint8_t* pano_rgb, const uint8_t* pano_levels, int bin, hipStream_t st) {
     const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
 #define DIBR_XR_PANO(FMT, D) do { \
         if (pl.kind == D2S_XR_KIND_PLAIN) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.P, pano_rgb, pano_levels); \
         else if (pl.kind == D2S_XR_KIND_FROST && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 1, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, pl.P, pano_rgb, pano_levels); \
         else if (pl.kind == D2S_XR_KIND_FROST) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 2, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, pl.P, pano_rgb, pano_levels); \
-        else hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D, XrPanoBg>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, levels, pl.P, pano_rgb, pano_levels); } while (0)
+        else if (pl.kind == D2S_XR_KIND_FROST_CURVED && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_curved_kernel<FMT, D, 1, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, bin, pl.P, pano_rgb, pano_levels); \
+        else if (pl.kind == D2S_XR_KIND_FROST_CURVED) hipLaunchKernelGGL((dibr_xr_frost_curved_kernel<FMT, D, 2, XrPanoBg>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels, bin, pl.P, pano_rgb, pano_levels); \
+        else if (pl.kind == D2S_XR_KIND_GLOW) hipLaunchKernelGGL((dibr_xr_glow_kernel<FMT, D, XrPanoBg>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, levels, pl.P, pano_rgb, pano_levels); \
+        else hipLaunchKernelGGL((dibr_xr_glow_curved_kernel<FMT, D, XrPanoBg>), grid, block, pl.lds_dynamic, st, rgb, depth, out, tab, pl.g, pl.ex, pl.G, pl.Q, levels, pl.P, pano_rgb, pano_levels); } while (0)
     if (out_fmt == D2S_FMT_U8_HWC) { if (pl.up) DIBR_XR_PANO(D2S_FMT_U8_HWC, UpDep); else DIBR_XR_PANO(D2S_FMT_U8_HWC, FullDep); }
     else { if (pl.up) DIBR_XR_PANO(D2S_FMT_F32_HWC, UpDep); else DIBR_XR_PANO(D2S_FMT_F32_HWC, FullDep); }
 #undef DIBR_XR_PANO
@@ -1066,10 +1075,10 @@ static int xr_launch(const XrPlan& pl, const uint8_t* rgb, const float* depth, v
             for (int f = 0; f < nf; ++f) chunk.f[f] = pl.rows[i][f0 + f];
             hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, st, chunk, (float*)(tab + i * stride + f0), n_floats);
         }
-    if (pl.pano) return xr_launch_pano(pl, rgb, depth, out, out_fmt, tab, levels, pano_rgb, pano_levels, st);
-    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
     const char* bin_env = getenv("D2S_XR_BIN");      // "0": the binned kernel walks every row (read at the call)
     const int bin = !(bin_env && bin_env[0] == '0' && bin_env[1] == 0);
+    if (pl.pano) return xr_launch_pano(pl, rgb, depth, out, out_fmt, tab, levels, pano_rgb, pano_levels, bin, st);
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
 #define DIBR_XR(FMT, D) do { \
         if (pl.kind == D2S_XR_KIND_PLAIN) hipLaunchKernelGGL((dibr_xr_kernel<FMT, D>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex); \
         else if (pl.kind == D2S_XR_KIND_FROST && pl.F.mode == 1) hipLaunchKernelGGL((dibr_xr_frost_kernel<FMT, D, 1>), grid, block, 0, st, rgb, depth, out, tab, pl.g, pl.ex, pl.F, levels); \
@@ -1176,6 +1185,31 @@ extern "C" int d2s_dibr_xr_panorama_plan(int dh, int dw, int batch, int H, int W
     D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
     XrPlan pl;
     const int rc = xr_plan(XR_ENTRY_PANORAMA, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl, pano);
+    if (rc) return rc;
+    xr_plan_result(pl, res);
+    return D2S_OK;
+}
+
+// The panorama behind every look, the curved screen's glow, veil and frosted included: xr_plan's seventh entry and its host-only
+// query.  d2s_dibr_xr_eyes_panorama's argument lists; that entry keeps refusing the curved looks with a panorama.
+extern "C" int d2s_dibr_xr_eyes_panorama_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                                const d2s_dibr_params* p, const double crop[4], const d2s_xr_screen* screen,
+                                                const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt, void* workspace,
+                                                uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                                const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
+                                                const uint8_t* pano_levels, void* stream) {
+    return dibr_xr_entry_any(XR_ENTRY_PANORAMA_CURVED, rgb, depth, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out, out_fmt, workspace,
+                             workspace_bytes, glow, frost, levels, stream, false, pano, pano_rgb, pano_levels);
+}
+
+extern "C" int d2s_dibr_xr_panorama_curved_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                                const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt,
+                                                const d2s_xr_frost* frost, const d2s_xr_glow* glow, const d2s_xr_panorama* pano,
+                                                d2s_xr_plan_result* res) {
+    D2S_REQUIRE(res, "null pointer (res)");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_plan_result), "d2s_xr_plan_result.struct_size must be sizeof(d2s_xr_plan_result)");
+    XrPlan pl;
+    const int rc = xr_plan(XR_ENTRY_PANORAMA_CURVED, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl, pano);
     if (rc) return rc;
     xr_plan_result(pl, res);
     return D2S_OK;

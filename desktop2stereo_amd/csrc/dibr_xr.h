@@ -414,6 +414,7 @@ inline void xr_frost_walls(const d2s_xr_screen* s, const XrFrostLayout& L, const
 constexpr int XR_TRIS = 4 * XR_MAX_FACETS + 4, XR_FROST_CURVED_ROWS = XR_MAX_FACETS + XR_TRIS;      // 196, 244
 constexpr int XR_ENTRY_FROST_CURVED = 4;                // xr_plan's fifth entry
 constexpr int XR_ENTRY_PANORAMA = 5;                    // the sixth: d2s_dibr_xr_eyes_panorama, which takes a glow OR a frost, and the panorama
+constexpr int XR_ENTRY_PANORAMA_CURVED = 6;             // the seventh: d2s_dibr_xr_eyes_panorama_curved, PANORAMA without its one refusal
 constexpr int XR_BIN_TILES = 4;                         // a block bins for XR_BIN_TILES x XR_BIN_TILES tiles of 16 x 16 pixels
 constexpr uint32_t XR_BIN_LDS = 4 * sizeof(uint64_t);   // the bin list: one ballot per wave of the block
 // triangle k (0 .. 195) opens its wall: its he is its own edge, tested >= 0
@@ -502,7 +503,7 @@ struct XrPlan {
     XrGlowDev G;                                  // kind GLOW, GLOW_CURVED
     XrFrostDev F;                                 // kind FROST, FROST_CURVED
     XrCurvedDev Q;                                // kind == GLOW_CURVED
-    bool pano;                                    // the background is the panorama P (kind PLAIN, GLOW or FROST)
+    bool pano;                                    // the background is the panorama P (GLOW_CURVED, FROST_CURVED: XR_ENTRY_PANORAMA_CURVED only)
     XrPanoDev P;
     bool up;                                      // depth is not at the frame's resolution: the UpDep sampler
     int rows_per_eye;                             // rows written per eye: the surface's facets (1 | 48), XR_PIECES, FROST: facets + 4,
@@ -517,10 +518,13 @@ struct XrPlan {
 // entry: D2S_XR_ENTRY_*, XR_ENTRY_FROST or XR_ENTRY_FROST_CURVED, the public call that asks.  EYES takes no glow (the caller passes
 // none); GLOW refuses a curved screen with glow on; FROST takes the frost and no glow and refuses a curved screen with frost on,
 // FROST_CURVED draws it; PANORAMA takes a glow or a frost, flat or curved, as GLOW_CURVED and FROST_CURVED do, and with a panorama
-// refuses the two curved looks.  Every refusal of the six entries that needs no device pointer, in their order; no HIP call.
+// refuses the two curved looks; PANORAMA_CURVED is PANORAMA in every check but that refusal, which it does not make.  Every refusal of
+// the seven entries that needs no device pointer, in their order; no HIP call.
 inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, const d2s_xr_screen* screen,
                    const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_glow* glow, const d2s_xr_frost* frost, XrPlan& pl,
                    const d2s_xr_panorama* pano = nullptr) {
+    const bool curved_pano = entry == XR_ENTRY_PANORAMA_CURVED;
+    if (curved_pano) entry = XR_ENTRY_PANORAMA;
     D2S_REQUIRE(p, "null pointer");
     int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
     if (rc) return rc;
@@ -542,7 +546,7 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     rc = xr_pano_check(entry == XR_ENTRY_PANORAMA ? pano : nullptr, n_eyes);
     if (rc) return rc;
     pl.pano = entry == XR_ENTRY_PANORAMA && pano;
-    if (pl.pano && screen->curve != D2S_XR_CURVE_FLAT && (glow_on || frost_on)) {
+    if (pl.pano && !curved_pano && screen->curve != D2S_XR_CURVE_FLAT && (glow_on || frost_on)) {
         set_error("unsupported: a panorama behind the glow, veil or frosted look of a CURVED screen is not built (the two heaviest eye "
                   "kernels get the background in a change of their own); with a panorama, curve must be 0 or glow and frost off");
         return D2S_E_UNSUPPORTED;
@@ -550,7 +554,7 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     D2S_REQUIRE(!(frost_on && frost->mode == 2) || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192),
                 "frame must be 2 .. 8192 on a side with the frosted look on (d2s_mip_chain's range)");
     D2S_REQUIRE(!glow_on || (H >= 2 && W >= 2 && H <= 8192 && W <= 8192), "frame must be 2 .. 8192 on a side with glow on (d2s_mip_chain's range)");
-    const bool tris = frost_on && screen->curve != D2S_XR_CURVE_FLAT;      // (only XR_ENTRY_FROST_CURVED comes this far with one)
+    const bool tris = frost_on && screen->curve != D2S_XR_CURVE_FLAT;      // (only FROST_CURVED and the two panorama entries come this far with one)
     pl.kind = tris ? D2S_XR_KIND_FROST_CURVED : frost_on ? D2S_XR_KIND_FROST : !glow_on ? D2S_XR_KIND_PLAIN : screen->curve == D2S_XR_CURVE_FLAT ? D2S_XR_KIND_GLOW : D2S_XR_KIND_GLOW_CURVED;
     const bool curved = pl.kind == D2S_XR_KIND_GLOW_CURVED;
     xr_out_layout(eyes, n_eyes, batch, p->alpha_mode, pl.offs, &pl.total);
@@ -621,7 +625,7 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     return D2S_OK;
 }
 
-// The six entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
+// The seven entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
 // every refusal, nothing launched (the view pipelines ask before they start the model).
 int dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                       const double* crop, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, void* out, int out_fmt,

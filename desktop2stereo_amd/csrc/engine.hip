@@ -1301,6 +1301,20 @@ extern "C" int d2s_view_pipeline_xr_panorama_streams(d2s_engine* e, const uint8_
                                 pano_levels);
 }
 
+// the same with d2s_dibr_xr_eyes_panorama_curved as the last stage: the panorama also behind the curved screen's looks
+extern "C" int d2s_view_pipeline_xr_panorama_curved_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                                            int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                                            const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                                            const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt,
+                                                            float* depth_full, void* workspace, uint64_t workspace_bytes,
+                                                            const d2s_xr_frost* frost, const uint8_t* levels, const d2s_xr_glow* glow,
+                                                            const d2s_xr_panorama* pano, const uint8_t* pano_rgb, const uint8_t* pano_levels,
+                                                            void* stream) {
+    return view_pipeline_xr_any(e, frames, batch, stream_ids, H, W, depth_resolution, pre, pp, dp, crop, screen, eyes, n_eyes, use_ema, out,
+                                out_fmt, depth_full, workspace, workspace_bytes, glow, levels, stream, XR_ENTRY_PANORAMA_CURVED, frost, pano,
+                                pano_rgb, pano_levels);
+}
+
 extern "C" int d2s_engine_tap(d2s_engine* e, const char* name, float* out, uint64_t out_elems, int* rows, int* cols, void* stream) {
     D2S_REQUIRE(e && name && out && rows && cols, "null pointer");
     if (!e->finalized || e->last_batch == 0) { set_error("d2s_engine_tap: no forward pass yet"); return D2S_E_STATE; }

@@ -420,7 +420,8 @@ def xr_eye_views_panorama(frames, screen, eyes, panorama, pano_rgb, eyes_proj_vi
     uint8 [h, w, 3] (numpy or device tensor), row 0 up; eyes_proj_view: one (proj, view) pair per entry of eyes (proj y-flipped where
     the eye is), from which the rays are formed.  The panorama's mip chain is built once and kept while pano_rgb is the same object.
     glow: an xr.XrGlow, or frost: an xr.XrFrost (at most one on; levels: the frames' mip chain, None builds it when the look reads
-    one); a curved screen takes a panorama only without a look.  The glTF environment, controllers and occlusion stay with the caller."""
+    one).  A curved screen with a glow or a frost that draws goes through Engine.view_pipeline_xr_panorama_curved, every other call
+    through Engine.view_pipeline_xr_panorama.  The glTF environment, controllers and occlusion stay with the caller."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -447,8 +448,10 @@ def xr_eye_views_panorama(frames, screen, eyes, panorama, pano_rgb, eyes_proj_vi
         levels = ops.mip_chain(t)
     dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
     ps = panorama.c_struct(eyes_proj_view, tuple(img.shape[:2]))
-    return eng.view_pipeline_xr_panorama(t, p, dp, screen, eyes, ps, img, chain, glow=glow, frost=frost, levels=levels, crop=crop,
-                                         use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth, streams=streams)
+    curved_look = getattr(screen, "curve", "flat") not in ("flat", 0) and (glow_on or (frost is not None and frost.draws()))
+    view = eng.view_pipeline_xr_panorama_curved if curved_look else eng.view_pipeline_xr_panorama
+    return view(t, p, dp, screen, eyes, ps, img, chain, glow=glow, frost=frost, levels=levels, crop=crop, use_ema=use_temporal_smooth,
+                out_u8=out_u8, want_depth=want_depth, streams=streams)
 
 
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,

@@ -406,7 +406,9 @@ _XR_PIPELINES = {"eyes": ("d2s_view_pipeline_xr_streams", "view_pipeline_xr", "d
                  "frost_curved": ("d2s_view_pipeline_xr_frost_curved_streams", "view_pipeline_xr_frost_curved",
                                   "d2s_dibr_xr_frost_curved_workspace"),
                  # (the panorama entry draws whichever kind the looks ask for: the largest table's workspace serves them all)
-                 "panorama": ("d2s_view_pipeline_xr_panorama_streams", "view_pipeline_xr_panorama", "d2s_dibr_xr_frost_curved_workspace")}
+                 "panorama": ("d2s_view_pipeline_xr_panorama_streams", "view_pipeline_xr_panorama", "d2s_dibr_xr_frost_curved_workspace"),
+                 "panorama_curved": ("d2s_view_pipeline_xr_panorama_curved_streams", "view_pipeline_xr_panorama_curved",
+                                     "d2s_dibr_xr_frost_curved_workspace")}
 
 
 def _xr_args(screen, eyes):
@@ -591,14 +593,33 @@ def dibr_xr_eyes_panorama(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.D
     band and the walls blend over it.  panorama = xr.XrPanorama(...).c_struct([(proj, view), ...], pano_rgb.shape[:2]); pano_rgb
     uint8 [h, w, 3], one image for the whole batch, row 0 up; pano_levels = mip_chain(pano_rgb).  glow = xr.XrGlow or frost =
     xr.XrFrost (at most one on) with levels = mip_chain(frames) as their own calls take it.  A curved screen with a look on and a
-    panorama is refused.  panorama None: exactly the call of that look.  workspace: a caller-kept uint8 device tensor of
+    panorama is refused here: dibr_xr_eyes_panorama_curved draws it.  panorama None: exactly the call of that look.  workspace: a caller-kept uint8 device tensor of
     d2s_dibr_xr_frost_curved_workspace bytes (the largest table serves every kind)."""
     return _dibr_xr_call("d2s_dibr_xr_eyes_panorama", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_panorama", frames, depth, dp,
                          screen, eyes, crop, out_u8, out, workspace, (frost, levels), pano=(glow, panorama, pano_rgb, pano_levels))
 
 
+def dibr_xr_eyes_panorama_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, panorama, pano_rgb,
+                                 pano_levels, glow=None, frost=None, levels=None, crop=None, out_u8: bool = True,
+                                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> list:
+    """dibr_xr_eyes_panorama, which also draws the panorama behind the CURVED screen's glow, glow2, veil and frosted looks
+    (d2s_dibr_xr_eyes_panorama_curved): the same arguments.  A flat screen, or a curved one without a look: exactly
+    dibr_xr_eyes_panorama's launch; panorama None: exactly dibr_xr_eyes_glow_curved's / dibr_xr_eyes_frost_curved's.  An eye outside
+    the convex region of the curved glow (xr.XrScreen.eye_inside) stays refused."""
+    return _dibr_xr_call("d2s_dibr_xr_eyes_panorama_curved", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_panorama_curved", frames,
+                         depth, dp, screen, eyes, crop, out_u8, out, workspace, (frost, levels), pano=(glow, panorama, pano_rgb, pano_levels))
+
+
+def dibr_xr_panorama_curved_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, panorama, glow=None,
+                                 frost=None, crop=None, out_u8: bool = True) -> dict:
+    """dibr_xr_panorama_plan for dibr_xr_eyes_panorama_curved (d2s_dibr_xr_panorama_curved_plan; host code, no GPU): kind "glow_curved"
+    or "frost_curved" where those draw, with "panorama" true when the background is drawn behind them."""
+    return dibr_xr_panorama_plan(dh, dw, batch, H, W, dp, screen, eyes, panorama, glow=glow, frost=frost, crop=crop, out_u8=out_u8,
+                                 _symbol="d2s_dibr_xr_panorama_curved_plan")
+
+
 def dibr_xr_panorama_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, panorama, glow=None, frost=None,
-                          crop=None, out_u8: bool = True) -> dict:
+                          crop=None, out_u8: bool = True, _symbol: str = "d2s_dibr_xr_panorama_plan") -> dict:
     """dibr_xr_plan for dibr_xr_eyes_panorama (d2s_dibr_xr_panorama_plan; host code, no GPU): the kind the looks ask for, the same
     fields, and "panorama": whether the background is drawn."""
     sc, ea = _xr_args(screen, eyes)
@@ -606,11 +627,11 @@ def dibr_xr_panorama_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_li
     gs = None if glow is None else glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
     r = _lib.XrPlanResult()
     r.struct_size = C.sizeof(_lib.XrPlanResult)
-    check(_lib.load().d2s_dibr_xr_panorama_plan(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
-                                                _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
-                                                FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None,
-                                                C.byref(gs) if gs is not None else None,
-                                                C.byref(panorama) if panorama is not None else None, C.byref(r)), "d2s_dibr_xr_panorama_plan")
+    check(getattr(_lib.load(), _symbol)(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
+                                        _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
+                                        FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None,
+                                        C.byref(gs) if gs is not None else None,
+                                        C.byref(panorama) if panorama is not None else None, C.byref(r)), _symbol)
     return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
             "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
             "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)]), "panorama": bool(r.reserved)}
@@ -1025,6 +1046,15 @@ class Engine:
         pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_panorama."""
         return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels, "panorama",
                                       pano=(glow, panorama, pano_rgb, pano_levels))
+
+    def view_pipeline_xr_panorama_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, panorama,
+                                         pano_rgb, pano_levels, glow=None, frost=None, levels=None, crop=None, use_ema: bool = False,
+                                         out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None, streams=None):
+        """view_pipeline_xr_panorama with the panorama also behind the curved screen's looks
+        (d2s_view_pipeline_xr_panorama_curved_streams).  Bit-identical to pipeline(want_depth=True)'s engine depth followed by
+        dibr_xr_eyes_panorama_curved."""
+        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels,
+                                      "panorama_curved", pano=(glow, panorama, pano_rgb, pano_levels))
 
     def view_pipeline_xr_glow(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
                               use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,

@@ -380,7 +380,8 @@ def panorama_rays(proj, view) -> np.ndarray:
 class XrPanorama:
     """The reference's panorama background (include/d2s.h d2s_xr_panorama): _panorama_background_settings' yaw_offset_deg, exposure
     and flip_y (xr_viewer/effects.py:981-990).  The image itself (uint8 [height, width, 3], row 0 up) and its mip_chain travel beside
-    it as tensors."""
+    it as tensors.  Drawn behind every look: ops.dibr_xr_eyes_panorama (plain, and the flat screen's glow, veil and frosted) and
+    ops.dibr_xr_eyes_panorama_curved (those, and the curved screen's)."""
     yaw_offset_deg: float = 0.0
     exposure: float = 1.0
     flip_y: bool = False

@@ -692,6 +692,33 @@ int d2s_dibr_xr_panorama_plan(int dh, int dw, int batch, int H, int W, const d2s
                               const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt, const d2s_xr_frost* frost,
                               const d2s_xr_glow* glow, const d2s_xr_panorama* pano, d2s_xr_plan_result* res);
 
+/* The panorama behind EVERY look, the curved screen's glow, glow2, veil and frosted included (d2s_version() >= 129): the door to what
+ * d2s_dibr_xr_eyes_panorama refuses.  d2s_dibr_xr_eyes_panorama's arguments, its per-pixel rule (the same sampler, the same 2 x 2 quad
+ * LOD evaluated analytically per thread) and its workspace (d2s_dibr_xr_frost_curved_workspace, the largest table, serves every kind).
+ * Drawn with a panorama: kinds PLAIN, GLOW, FROST as there, and GLOW_CURVED (_render_curved_glow's band mesh, effects.py:314-474) and
+ * FROST_CURVED (the 196 wall triangles, effects.py:189-254, 759-787): an uncovered pixel starts from the panorama, the outer band or the
+ * walls blend over it in draw order, alpha_mode acts, one store.  Covered pixels are d2s_dibr_xr_eyes_glow_curved's /
+ * d2s_dibr_xr_eyes_frost_curved's, bit for bit.  Bit-identity: a flat screen (any look) or a curved one without a look launches exactly
+ * what d2s_dibr_xr_eyes_panorama launches; pano == NULL launches exactly what d2s_dibr_xr_eyes / _glow / _glow_curved / _frost /
+ * _frost_curved launch for these arguments.  Refused, with the words of the entry that owns the check, nothing launched, out untouched:
+ * everything d2s_dibr_xr_eyes_panorama refuses except the curved looks with a panorama -- D2S_E_UNSUPPORTED: an eye outside the convex
+ * region the curved screen and its tangent planes bound with the glow on (the draw-order case), a screen vertex with clip w <= 1e-6, an
+ * 8192 x 8192 frame's LDS; D2S_E_INVALID: normal_offset != 0 with a look on, a bad struct_size anywhere, glow and frost both on, the
+ * panorama's own fields, a missing pointer or workspace.  d2s_dibr_xr_eyes_panorama itself is unchanged and keeps refusing.
+ * d2s_dibr_xr_panorama_curved_plan: d2s_dibr_xr_panorama_plan for this entry (host code, no GPU): kind GLOW_CURVED or FROST_CURVED
+ * where those draw; reserved = 1 when the panorama is drawn.
+ * Pinned by tests/golden/xr_panorama_curved.npz: the reference's own shaders drawn off-screen in _render_eye's order, clear, panorama
+ * quad, then the curved glow's or the curved frost's draws (make_golden_xr_panorama_curved.py). */
+int d2s_dibr_xr_eyes_panorama_curved(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
+                                     const d2s_dibr_params* p, const double crop[4], const d2s_xr_screen* screen, const d2s_xr_eye* eyes,
+                                     int n_eyes, void* out, int out_fmt, void* workspace, uint64_t workspace_bytes,
+                                     const d2s_xr_frost* frost, const uint8_t* levels, const d2s_xr_glow* glow, const d2s_xr_panorama* pano,
+                                     const uint8_t* pano_rgb, const uint8_t* pano_levels, void* stream);
+int d2s_dibr_xr_panorama_curved_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double crop[4],
+                                     const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes, int out_fmt,
+                                     const d2s_xr_frost* frost, const d2s_xr_glow* glow, const d2s_xr_panorama* pano,
+                                     d2s_xr_plan_result* res);
+
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
  * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.
@@ -854,6 +881,15 @@ int d2s_view_pipeline_xr_panorama_streams(d2s_engine* e, const uint8_t* frames, 
                                           void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
                                           const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
                                           const uint8_t* pano_levels, void* stream);
+/* The same with d2s_dibr_xr_eyes_panorama_curved as the last stage (d2s_version() >= 129).  Bit-identical to d2s_pipeline(depth_full)
+ * followed by d2s_dibr_xr_eyes_panorama_curved on the engine's map. */
+int d2s_view_pipeline_xr_panorama_curved_streams(d2s_engine* e, const uint8_t* frames, int batch, const int* stream_ids, int H, int W,
+                                                 int depth_resolution, const d2s_pre_params* pre, const d2s_post_params* pp,
+                                                 const d2s_dibr_params* dp, const double* crop, const d2s_xr_screen* screen,
+                                                 const d2s_xr_eye* eyes, int n_eyes, int use_ema, void* out, int out_fmt, float* depth_full,
+                                                 void* workspace, uint64_t workspace_bytes, const d2s_xr_frost* frost, const uint8_t* levels,
+                                                 const d2s_xr_glow* glow, const d2s_xr_panorama* pano, const uint8_t* pano_rgb,
+                                                 const uint8_t* pano_levels, void* stream);
 int d2s_engine_reset_stream(d2s_engine* e);      /* every slot: temporal windows and EMA state */
 
 /* Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the

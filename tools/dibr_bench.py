@@ -44,7 +44,12 @@
         screen a look may be on; a curved screen takes the panorama without one.  --ab-lib: the other build's existing entry of the
         look and this build's new entry with pano == NULL through the same bare C call in the same rounds, twice each: the other
         build's spread against itself is the margin.  D2S_HIPCC_DEFS=-DD2S_PANO_NO_FETCH (tools/build_variant.sh) builds the variant
-        whose background skips the eight texel fetches: what is left is the coordinate and LOD arithmetic."""
+        whose background skips the eight texel fetches: what is left is the coordinate and LOD arithmetic.
+    python tools/dibr_bench.py --xr-eye --panorama 4096 2048 --curve h|v (--glow glow|glow2 | --frost veil|frosted) [--ab-lib other/libd2s_hip.so]
+        d2s_dibr_xr_eyes_panorama_curved (the panorama behind the curved screen's glow or walls) in the same scheme: the look's own
+        curved entry, the new entry with pano == NULL, the new entry with the panorama, the first two again; us per launch and ns
+        per background pixel.  --ab-lib: the other build's curved entry of the look, this build's curved entry and this build's new
+        entry with pano == NULL through the same bare C call in the same rounds, twice each."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -167,8 +172,7 @@ if a.xr_eye:
     for B in a.batch if a.panorama else ():
         import ctypes as C
         from desktop2stereo_amd import _lib
-        if a.curve and (a.glow or a.frost):
-            sys.exit("--panorama: a curved screen takes the panorama without a look (d2s_dibr_xr_eyes_panorama refuses the other)")
+        curved_look = bool(a.curve and (a.glow or a.frost))      # d2s_dibr_xr_eyes_panorama_curved's own ground: the old entry refuses it
         if a.glow and a.frost:
             sys.exit("--panorama: at most one of --glow and --frost")
         pw, ph = a.panorama
@@ -190,20 +194,26 @@ if a.xr_eye:
         probe = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)        # clear alpha 0.5 marks the pixels no facet covers
         n_bg = sum(int((e[..., 3] == 0.5).sum()) for e in probe)
         look = "glow" if glow is not None else "frost" if frost is not None else "plain"
-        if look == "glow":
+        if curved_look and look == "glow":
+            old = lambda: ops.dibr_xr_eyes_glow_curved(f, d, dp, screen, eyes, glow, levels, out=out)
+        elif curved_look:
+            old = lambda: ops.dibr_xr_eyes_frost_curved(f, d, dp, screen, eyes, frost, levels, out=out)
+        elif look == "glow":
             old = lambda: ops.dibr_xr_eyes_glow(f, d, dp, screen, eyes, glow, levels, out=out)
         elif look == "frost":
             old = lambda: ops.dibr_xr_eyes_frost(f, d, dp, screen, eyes, frost, levels, out=out)
         else:
             old = lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)
-        new = lambda p, r, l: (lambda: ops.dibr_xr_eyes_panorama(f, d, dp, screen, eyes, p, r, l, glow=glow, frost=frost, levels=levels, out=out))
+        entry = ops.dibr_xr_eyes_panorama_curved if curved_look else ops.dibr_xr_eyes_panorama
+        new = lambda p, r, l: (lambda: entry(f, d, dp, screen, eyes, p, r, l, glow=glow, frost=frost, levels=levels, out=out))
         a0, b0 = [t.clone() for t in old()], [t.clone() for t in new(None, None, None)()]
         assert all(torch.equal(x, y) for x, y in zip(a0, b0)), "pano == NULL differs from the existing entry"
         runs = {f"{look}_old_entry": old, f"{look}_new_entry_no_panorama": new(None, None, None), f"{look}_panorama": new(ps, pr, pl),
-                f"{look}_old_entry_again": old, f"{look}_panorama_again": new(ps, pr, pl)}
+                f"{look}_old_entry_again": old, f"{look}_new_entry_no_panorama_again": new(None, None, None), f"{look}_panorama_again": new(ps, pr, pl)}
         if a.ab_lib:      # the other build's existing entry of the look and this build's new entry with pano == NULL: the bare C calls
             other = C.CDLL(os.path.abspath(a.ab_lib))
-            name = {"plain": "d2s_dibr_xr_eyes", "glow": "d2s_dibr_xr_eyes_glow", "frost": "d2s_dibr_xr_eyes_frost"}[look]
+            name = {"plain": "d2s_dibr_xr_eyes", "glow": "d2s_dibr_xr_eyes_glow", "frost": "d2s_dibr_xr_eyes_frost"}[look] + ("_curved" if curved_look else "")
+            new_name = "d2s_dibr_xr_eyes_panorama_curved" if curved_look else "d2s_dibr_xr_eyes_panorama"
             getattr(other, name).restype, getattr(other, name).argtypes = _lib.SYMBOLS[name]
             other.d2s_version.restype = C.c_int
             sc, ea = screen.c_struct(), xr.eye_array(eyes)
@@ -219,16 +229,20 @@ if a.xr_eye:
                 rc = getattr(other, name)(*head(), *tail, st)
                 assert rc == 0, rc
 
+            def this_old():
+                rc = getattr(_lib.load(), name)(*head(), *tail, st)
+                assert rc == 0, rc
+
             def this_new():
-                rc = _lib.load().d2s_dibr_xr_eyes_panorama(*head(), C.byref(fs) if fs else None, lv, C.byref(gs) if gs else None, None, None, None, st)
+                rc = getattr(_lib.load(), new_name)(*head(), C.byref(fs) if fs else None, lv, C.byref(gs) if gs else None, None, None, None, st)
                 assert rc == 0, rc
             other_old()
             torch.cuda.synchronize()
             same = bool(torch.equal(a0[0], out[:a0[0].numel()].view(a0[0].shape)))
             print(f"--ab-lib {a.ab_lib}: d2s_version {other.d2s_version()} (this build {_lib.load().d2s_version()}); its eye 0 is "
                   f"{'bit-identical to' if same else 'DIFFERENT from'} this build's", flush=True)
-            runs = dict({"other_lib_old_entry": other_old, "this_lib_new_entry_no_panorama": this_new}, **runs, other_lib_old_entry_again=other_old,
-                        this_lib_new_entry_no_panorama_again=this_new)
+            runs = dict({"other_lib_old_entry": other_old, "this_lib_old_entry": this_old, "this_lib_new_entry_no_panorama": this_new}, **runs,
+                        other_lib_old_entry_again=other_old, this_lib_old_entry_again=this_old, this_lib_new_entry_no_panorama_again=this_new)
         t = {k: [] for k in runs}
         for _ in range(a.rounds):
             for k, fn in runs.items():
@@ -248,14 +262,17 @@ if a.xr_eye:
         for k in runs:
             print(f"    {k:40s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f}; {1e3 * med[k] / (B * n_px):.4f} ns / image pixel)", flush=True)
         cost = med[f"{look}_panorama"] - med[f"{look}_new_entry_no_panorama"]
-        print(f"    the panorama costs {cost:+.1f} us = {1e3 * cost / (B * n_bg):.4f} ns per background pixel; new entry without it - old entry = "
+        spread = max(abs(med[f"{look}_panorama_again"] - med[f"{look}_panorama"]), abs(med[f"{look}_new_entry_no_panorama_again"] - med[f"{look}_new_entry_no_panorama"]))
+        print(f"    the panorama costs {cost:+.1f} us = {1e3 * cost / (B * n_bg):.4f} ns per background pixel (the rounds' spread: {spread:.1f} us = "
+              f"{1e3 * spread / (B * n_bg):.4f} ns); new entry without it - old entry = "
               f"{med[f'{look}_new_entry_no_panorama'] - med[f'{look}_old_entry']:+.1f} us; old entry against itself {med[f'{look}_old_entry_again'] - med[f'{look}_old_entry']:+.1f} us; "
               f"the panorama's mip_chain, once: {e0.elapsed_time(e1) * 1e3:.1f} us", flush=True)
         if a.ab_lib:
             margin = abs(med["other_lib_old_entry_again"] - med["other_lib_old_entry"])
-            worst = max(med["this_lib_new_entry_no_panorama"], med["this_lib_new_entry_no_panorama_again"]) - max(med["other_lib_old_entry"], med["other_lib_old_entry_again"])
-            print(f"    other build against itself: {med['other_lib_old_entry_again'] - med['other_lib_old_entry']:+.1f} us (the margin: {margin:.1f} us); this "
-                  f"build's slower run - the other's slower run = {worst:+.1f} us: {'within' if worst <= margin else 'BEYOND'} the margin", flush=True)
+            print(f"    other build against itself: {med['other_lib_old_entry_again'] - med['other_lib_old_entry']:+.1f} us (the margin: {margin:.1f} us)", flush=True)
+            for k, what in (("this_lib_old_entry", "this build's existing entry"), ("this_lib_new_entry_no_panorama", "this build's new entry, pano == NULL")):
+                worst = max(med[k], med[k + "_again"]) - max(med["other_lib_old_entry"], med["other_lib_old_entry_again"])
+                print(f"    {what}: its slower run - the other's slower run = {worst:+.1f} us: {'within' if worst <= margin else 'BEYOND'} the margin", flush=True)
     if a.panorama:
         sys.exit(0)
     for B in a.batch if a.frost and not a.curve else ():
