@@ -1198,7 +1198,10 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
 // Every value is formed as the separate launches form it -- one accumulator per output, K tiles tap-major with 64 channels each,
 // the same MFMA and fragment slotting as conv3_halo2_kernel / gemm_glds_kernel / gemm_sk_kernel, bias / residual / rounding in
 // epilogue4's order -- so the result equals theirs bit for bit (tests/test_gpu_rcu_fused.py).
-// LDS: 7 x 16 KiB ring + 26 112 B (h0 | h2) + 16 320 B (h1) = 157 120 B.
+//   * no barrier in the K loops: the ring is wave-private (below), the block meets three times -- after the halo fill, at the seam
+//     conv1 -> conv2 (h1) and at the seam conv2 -> projection (h2);
+//   * every A-fragment read is conflict-free (the maps and their proof: rcu_c1_row ... rcu_b128_cycles below).
+// LDS: 7 x 16 KiB ring + 29 184 B (h0 | h2) + 17 280 B (h1) = 161 152 B.
 // ================================================================================================
 struct RcuArgs {
     const bf16_t* x;                 // [nimg, H, W, 128]
@@ -1208,6 +1211,76 @@ struct RcuArgs {
     int H, W, nimg, Kpad, KpadP;
 };
 constexpr int RCU_TH = 4, RCU_TW = 8;
+// ---- where a lane's pixels sit, and the bank arithmetic of the A-fragment reads (the rule at c3_lane_pixel: a ds_read_b128 is served
+// in four groups of 16 lanes, 4 LDS-array cycles per read if the 16 chunk slots mod 16 of every group differ).  A group holds the
+// eight lanes fr in S = {0-3, 12-15} of one k group and the eight lanes fr in S' = {4-11} of the next one.  All three regions use an
+// EVEN pixel stride, 18 chunks: a pixel's slot mod 16 is even, the neighbouring k group is one chunk on, so S and S' never meet and a
+// read is conflict-free iff the eight pixels of each HALF differ in  (slot / 2) mod 8.  With the row pitches below that class is
+// (2 row + column) mod 8 in h0 and in h1, and the pixel number mod 8 in h2:
+//   * conv2 (h1, 6 x 10 positions, pitch 10 pixels): S takes the eight pixels of tile row 2 f, S' those of row 2 f + 1 -- eight
+//     consecutive columns of one row, at every tap;
+//   * conv1 (h0, 8 x 12 pixels, row pitch 12 pixels + 12 chunks = 228 = 4 mod 16): fragments 0-2 take columns 0-7 of rows 2 f (S) and
+//     2 f + 1 (S') of the 6 x 10 ring-extended tile; fragment 3 takes columns 8-9: rows 0-3 in S (classes 0-7) and rows 2-5 in S',
+//     whose rows 2-3 repeat S's and are not stored (with the plain pitch 12 x 18 the class is (4 row + column) mod 8, one class holds
+//     nine of the 60 positions and no assignment of lanes is conflict-free);
+//   * projection (h2): pixel 16 f + fr, classes fr mod 8.
+// Reached: 4 cycles per read for every fragment of conv1, conv2 and the projection -- the floor (8 each with stride 17 and
+// position = 16 f + fr); the static_asserts below enumerate every group of every fragment.  Tap and K-step offsets are the same for
+// all lanes, so they shift a group's slots together and change nothing.
+constexpr int RCU_PST = 18;                                   // pixel stride of h0, h1 and h2, in chunks
+constexpr int RCU_W0 = RCU_TW + 4, RCU_W1 = RCU_TW + 2;       // pixels per row of h0 / positions per row of h1
+constexpr int RCU_RP0 = RCU_W0 * RCU_PST + 12;                // h0 row pitch in chunks
+constexpr int RCU_RP1 = RCU_W1 * RCU_PST;                     // h1 row pitch in chunks
+__host__ __device__ constexpr int rcu_half(int fr) { return fr >= 4 && fr < 12; }                  // 0: S, 1: S'
+__host__ __device__ constexpr int rcu_idx(int fr) { return fr < 4 ? fr : (fr < 12 ? fr - 4 : fr - 8); }   // 0 .. 7 inside the half
+// conv1: position (row, column) on the 6 x 10 ring-extended tile of lane fr in fragment f, and whether the lane owns (stores) it
+__host__ __device__ constexpr int rcu_c1_row(int f, int fr) { return f < 3 ? 2 * f + rcu_half(fr) : (rcu_idx(fr) >> 1) + 2 * rcu_half(fr); }
+__host__ __device__ constexpr int rcu_c1_col(int f, int fr) { return f < 3 ? rcu_idx(fr) : 8 + (rcu_idx(fr) & 1); }
+__host__ __device__ constexpr bool rcu_c1_owns(int f, int fr) { return f < 3 || !(rcu_half(fr) && rcu_idx(fr) < 4); }
+// conv2 / output: tile pixel (row 2 f + rcu_half, column rcu_idx)
+struct RcuSlots { int s[64]; };                               // chunk slot of each lane of one ds_read_b128 (lane = 16 fg + fr)
+constexpr int rcu_b128_cycles(const RcuSlots& t) {
+    int cyc = 0;
+    for (int g = 0; g < 4; ++g) {
+        int n[16] = {}, worst = 0;
+        for (int lane = 0; lane < 64; ++lane) {
+            const int l = lane & 31;
+            const int grp = 2 * (lane >> 5) + ((l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28)) ? 0 : 1);
+            if (grp != g) continue;
+            const int c = ++n[t.s[lane] & 15];
+            worst = c > worst ? c : worst;
+        }
+        cyc += worst;
+    }
+    return cyc;
+}
+constexpr RcuSlots rcu_slots(int region, int f) {             // region 0: conv1 on h0, 1: conv2 on h1, 2: the projection on h2
+    RcuSlots t{};
+    for (int lane = 0; lane < 64; ++lane) {
+        const int fr = lane & 15, fg = lane >> 4;
+        t.s[lane] = fg + (region == 0 ? rcu_c1_row(f, fr) * RCU_RP0 + rcu_c1_col(f, fr) * RCU_PST
+                        : region == 1 ? (2 * f + rcu_half(fr)) * RCU_RP1 + rcu_idx(fr) * RCU_PST
+                                      : (16 * f + fr) * RCU_PST);
+    }
+    return t;
+}
+constexpr bool rcu_c1_covers() {                              // every position of the 6 x 10 tile is owned by exactly one lane
+    int n[6 * RCU_W1] = {};
+    for (int f = 0; f < 4; ++f)
+        for (int fr = 0; fr < 16; ++fr) {
+            const int row = rcu_c1_row(f, fr), col = rcu_c1_col(f, fr);
+            if (row < 0 || row >= 6 || col < 0 || col >= RCU_W1) return false;
+            if (rcu_c1_owns(f, fr)) ++n[row * RCU_W1 + col];
+        }
+    for (int p = 0; p < 6 * RCU_W1; ++p)
+        if (n[p] != 1) return false;
+    return true;
+}
+static_assert(rcu_c1_covers(), "conv1's lanes must own every ring-extended position once");
+static_assert(rcu_b128_cycles(rcu_slots(0, 0)) == 4 && rcu_b128_cycles(rcu_slots(0, 1)) == 4 && rcu_b128_cycles(rcu_slots(0, 2)) == 4 &&
+              rcu_b128_cycles(rcu_slots(0, 3)) == 4, "conv1's A-fragment reads must be conflict-free");
+static_assert(rcu_b128_cycles(rcu_slots(1, 0)) == 4 && rcu_b128_cycles(rcu_slots(1, 1)) == 4, "conv2's A-fragment reads must be conflict-free");
+static_assert(rcu_b128_cycles(rcu_slots(2, 0)) == 4 && rcu_b128_cycles(rcu_slots(2, 1)) == 4, "the projection's A-fragment reads must be conflict-free");
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 // four floats -> four bf16 (RNE, as store4 rounds them); relu: max(., 0) on the ROUNDED values, as relu_frag does on load
 __device__ __forceinline__ uint2 rcu_pack4(const float v[4], bool relu) {
@@ -1217,7 +1290,7 @@ __device__ __forceinline__ uint2 rcu_pack4(const float v[4], bool relu) {
 }
 // 8 bytes to LDS as inline asm: written as a plain store the compiler puts s_waitcnt vmcnt(0) in front of it (for all it knows the
 // store may alias what an LDS-DMA in flight writes), which drains the weight ring at every seam.  The regions written this way (h1,
-// h2) are no ring stage; their readers sit behind ring_step's lgkmcnt(0) and barrier.
+// h2) are no ring stage; their readers sit behind the seam's lgkmcnt(0) and barrier.
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void rcu_lds_write_b64(const u32x4* chunk, int half, uint2 v) {
     const unsigned addr = (unsigned)(unsigned long)((__attribute__((address_space(3))) const char*)chunk) + (unsigned)half * 8u;
@@ -1227,17 +1300,19 @@ __device__ __forceinline__ void rcu_lds_write_b64(const u32x4* chunk, int half, 
 template <int PROJ>
 __global__ void __launch_bounds__(512)
 conv3_rcu_kernel(RcuArgs r) {
-    constexpr int TH = RCU_TH, TW = RCU_TW, CPP = 16, PST = 17, NW = 8;
-    constexpr int W0 = TW + 4, P0 = (TH + 4) * W0;          // input halo: 8 x 12 pixels
-    constexpr int W1 = TW + 2, P1 = (TH + 2) * W1;          // conv1's ring-extended tile: 6 x 10 pixels
+    constexpr int TH = RCU_TH, TW = RCU_TW, CPP = 16, PST = RCU_PST, NW = 8;
+    constexpr int W0 = RCU_W0, P0 = (TH + 4) * W0, RP0 = RCU_RP0;   // input halo: 8 x 12 pixels, rows RP0 chunks apart
+    constexpr int W1 = RCU_W1, P1 = (TH + 2) * W1, RP1 = RCU_RP1;   // conv1's ring-extended tile: 6 x 10 positions
+    constexpr int L0 = (TH + 4) * RP0, L1 = (TH + 2) * RP1;         // chunks of h0 (| h2) and of h1
     constexpr int NKT = 18, NG = 2 * NKT + (PROJ ? 2 : 0);  // K tiles per convolution; tiles through the ring in all
     constexpr int WST = 128 * 8;                            // chunks per ring stage: 128 rows x 128 bytes
     constexpr int NS = 7, PD = NS - 1, BI = 128 / (8 * NW); // stages, tiles requested ahead, LDS-DMA instructions per wave per tile
     static_assert(P1 <= 64 && TH * TW == 32 && BI == 2 && NG > PD, "fragment counts below are for a 4 x 8 tile");
-    __shared__ __attribute__((aligned(16))) u32x4 lds[NS * WST + P0 * PST + P1 * PST];
-    D2S_POISON_LDS(lds, NS * WST + P0 * PST + P1 * PST)
+    static_assert(TH * TW * PST <= L0 && (NS * WST + L0 + L1) * 16 <= 160 * 1024, "h2 lies over h0; one block's LDS");
+    __shared__ __attribute__((aligned(16))) u32x4 lds[NS * WST + L0 + L1];
+    D2S_POISON_LDS(lds, NS * WST + L0 + L1)
     u32x4* const h0 = lds + NS * WST;
-    u32x4* const h1 = h0 + P0 * PST;
+    u32x4* const h1 = h0 + L0;
     u32x4* const h2 = h0;                                   // PROJ: the rounded RCU tile, once conv1 has read h0 out
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1257,7 +1332,9 @@ conv3_rcu_kernel(RcuArgs r) {
     if constexpr (PROJ) load4(r.bp + n0, cp);
 
     // ---- the weight ring (conv3_halo2_kernel's: lane -> row lane / 8 of the instruction's 8, physical chunk lane % 8, the row
-    // swizzle (row >> 1) & 7 on the source chunk and on the fragment read); tile g of the ring is K tile g of w1, g - 18 of w2, g - 36 of wp
+    // swizzle (row >> 1) & 7 on the source chunk and on the fragment read); tile g of the ring is K tile g of w1, g - 18 of w2, g - 36 of wp.
+    // WAVE-PRIVATE: a wave requests exactly the rows 16 wid .. + 15 whose fragments it reads, so nobody else touches its 2 KiB of
+    // a stage and the wave's own counters order everything -- vmcnt before it reads a tile, lgkmcnt before it re-requests the stage.
     const unsigned wbytes = 256u * (unsigned)r.Kpad * 2u, pbytes = 256u * (unsigned)r.KpadP * 2u;
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r.w1), 0, wbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r.w2), 0, wbytes, 0x00020000);
@@ -1265,7 +1342,7 @@ conv3_rcu_kernel(RcuArgs r) {
     unsigned voW[BI], voP[BI];
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
-        const int row = (i * NW + wid) * 8 + (lane >> 3);
+        const int row = (wid * BI + i) * 8 + (lane >> 3);
         const unsigned ch = (unsigned)(((lane & 7) ^ ((row >> 1) & 7)) * 16);
         voW[i] = (unsigned)(row * r.Kpad * 2) + ch;
         voP[i] = (unsigned)(row * r.KpadP * 2) + ch;
@@ -1274,13 +1351,13 @@ conv3_rcu_kernel(RcuArgs r) {
         u32x4* st_ = lds + slot * WST;
         if (g < NKT) {
 #pragma unroll
-            for (int i = 0; i < BI; ++i) lds_dma16(rs1, st_ + (i * NW + wid) * 64, voW[i], g * 128);
+            for (int i = 0; i < BI; ++i) lds_dma16(rs1, st_ + (wid * BI + i) * 64, voW[i], g * 128);
         } else if (!PROJ || g < 2 * NKT) {
 #pragma unroll
-            for (int i = 0; i < BI; ++i) lds_dma16(rs2, st_ + (i * NW + wid) * 64, voW[i], (g - NKT) * 128);
+            for (int i = 0; i < BI; ++i) lds_dma16(rs2, st_ + (wid * BI + i) * 64, voW[i], (g - NKT) * 128);
         } else {
 #pragma unroll
-            for (int i = 0; i < BI; ++i) lds_dma16(rsP, st_ + (i * NW + wid) * 64, voP[i], (g - 2 * NKT) * 128);
+            for (int i = 0; i < BI; ++i) lds_dma16(rsP, st_ + (wid * BI + i) * 64, voP[i], (g - 2 * NKT) * 128);
         }
     };
 #pragma unroll
@@ -1288,14 +1365,21 @@ conv3_rcu_kernel(RcuArgs r) {
 
     // ---- the input halo, once: rows ty0 - 2 .. ty0 + 5, columns tx0 - 2 .. tx0 + 9, zero outside the image, ReLU-on-load
     conv_halo_fill<bf16_t, 64 * NW, 3>(a, b, ty0 - 1, tx0 - 1, W0, P0, CPP, tid, h0,
-        [&](int p, int c) { return p * PST + c; },
+        [&](int p, int c) { return (p / W0) * RP0 + (p % W0) * PST + c; },
         [&](u32x4 v) { return relu_frag(v, relu_floor_bf16(a), bf16_t()); });
 #pragma unroll
     for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(c1[q]), "+v"(c2[q]), "+v"(cp[q]));
+    // the block's three barriers: h0, h1 and h2 are written by all waves and read by all waves.  My LDS writes are done, then
+    // everybody's; the weight ring is not waited for and keeps flowing across the seams
+    auto seam = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    };
+    seam();
 
     // ring bookkeeping: tile g sits in stage g % NS; before it is read, the wave's own requests for it have landed (at most the
-    // min(PD - 1, NG - 1 - g) younger tiles may still be out: vmcnt retires in order), then everybody's (the barrier, which also says
-    // that tile g - 1 is read out: its stage takes tile g + PD)
+    // min(PD - 1, NG - 1 - g) younger tiles may still be out: vmcnt retires in order); the same wait has lgkmcnt(0), i.e. the wave's
+    // fragment reads of tile g - 1 are complete before its stage is requested again for tile g + PD.  No barrier: the waves run free.
     int g = 0, slot = 0, islot = PD;
     auto ring_step = [&]() -> const u32x4* {
         const int rem = NG - 1 - g;
@@ -1305,7 +1389,6 @@ conv3_rcu_kernel(RcuArgs r) {
         else if (rem == 2) c3_wait_vm<2 * BI>();
         else if (rem == 1) c3_wait_vm<1 * BI>();
         else c3_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
         if (g + PD < NG) issue(g + PD, islot);
         const u32x4* B_l = lds + slot * WST;
         ++g;
@@ -1322,22 +1405,20 @@ conv3_rcu_kernel(RcuArgs r) {
         for (int ks = 0; ks < 2; ++ks) wo[ks] = row * 8 + ((ks * 4 + fg) ^ ((row >> 1) & 7));
     }
 
-    // ---- conv1 on the ring-extended tile: position p = 16 f + fr -> (p / 10, p % 10), image pixel (ty0 - 1 + py, tx0 - 1 + px);
-    // positions 60 .. 63 repeat 59 and are not stored.  A fragment: h0 pixel (py + ky, px + kx), chunk 8 sub + 4 ks + fg
+    // ---- conv1 on the ring-extended tile: lane fr of fragment f has position (py, px) = (rcu_c1_row, rcu_c1_col), image pixel
+    // (ty0 - 1 + py, tx0 - 1 + px); four lanes of fragment 3 repeat a position and do not store it.  A fragment: h0 pixel
+    // (py + ky, px + kx), chunk 8 sub + 4 ks + fg
     {
         const u32x4* hb[4];
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const int p = f * 16 + fr < P1 ? f * 16 + fr : P1 - 1;
-            hb[f] = h0 + ((p / W1) * W0 + p % W1) * PST + fg;
-        }
+        for (int f = 0; f < 4; ++f) hb[f] = h0 + rcu_c1_row(f, fr) * RP0 + rcu_c1_col(f, fr) * PST + fg;
         f32x4 acc[4];
 #pragma unroll
         for (int f = 0; f < 4; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int kt = 0; kt < NKT; ++kt) {
             const int tap = kt >> 1, ky = (tap * 11) >> 5, kx = tap - 3 * ky;
-            const int toff = (ky * W0 + kx) * PST + (kt & 1) * 8;
+            const int toff = ky * RP0 + kx * PST + (kt & 1) * 8;
             const u32x4* B_l = ring_step();
             u32x4 fb[2], fa[2][4];                           // all ten fragments requested before the first MFMA: one LDS round trip per tile
 #pragma unroll
@@ -1354,30 +1435,30 @@ conv3_rcu_kernel(RcuArgs r) {
         }
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
-            const int p = f * 16 + fr;
-            const int py = p / W1, px = p - py * W1;
+            const int py = rcu_c1_row(f, fr), px = rcu_c1_col(f, fr);
             const int iy = ty0 - 1 + py, ix = tx0 - 1 + px;
             const float v[4] = {acc[f][0] + c1[0], acc[f][1] + c1[1], acc[f][2] + c1[2], acc[f][3] + c1[3]};
             uint2 t = rcu_pack4(v, true);
             if (!(iy >= 0 && iy < r.H && ix >= 0 && ix < r.W)) t = make_uint2(0u, 0u);
-            if (p < P1) rcu_lds_write_b64(h1 + p * PST + 2 * wid + (fg >> 1), fg & 1, t);
+            if (rcu_c1_owns(f, fr)) rcu_lds_write_b64(h1 + py * RP1 + px * PST + 2 * wid + (fg >> 1), fg & 1, t);
         }
     }
+    seam();                                                  // h1 is complete (and h0 is read out: h2 may overwrite it)
 
-    // ---- conv2 on the tile: pixel p = 16 f + fr -> (p / 8, p % 8); A fragment: h1 position (oy + ky, ox + kx)
-    const int oy0 = fr >> 3, ox = fr & 7;                    // fragment f: tile row 2 f + oy0
+    // ---- conv2 on the tile: lane fr of fragment f has tile pixel (2 f + oy0, ox); A fragment: h1 position (oy + ky, ox + kx)
+    const int oy0 = rcu_half(fr), ox = rcu_idx(fr);
     uint2 rcu[2];
     {
         const u32x4* hb[2];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) hb[f] = h1 + ((2 * f + oy0) * W1 + ox) * PST + fg;
+        for (int f = 0; f < 2; ++f) hb[f] = h1 + (2 * f + oy0) * RP1 + ox * PST + fg;
         f32x4 acc[2];
 #pragma unroll
         for (int f = 0; f < 2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int kt = 0; kt < NKT; ++kt) {
             const int tap = kt >> 1, ky = (tap * 11) >> 5, kx = tap - 3 * ky;
-            const int toff = (ky * W1 + kx) * PST + (kt & 1) * 8;
+            const int toff = ky * RP1 + kx * PST + (kt & 1) * 8;
             const u32x4* B_l = ring_step();
             u32x4 fb[2], fa[2][2];
 #pragma unroll
@@ -1417,6 +1498,7 @@ conv3_rcu_kernel(RcuArgs r) {
         // ---- the 1x1 projection of the rounded tile: K = 128 = the ring's last two tiles; A fragment: h2 pixel p, chunk 8 kt + 4 ks + fg
 #pragma unroll
         for (int f = 0; f < 2; ++f) rcu_lds_write_b64(h2 + (f * 16 + fr) * PST + 2 * wid + (fg >> 1), fg & 1, rcu[f]);
+        seam();
         f32x4 acc[2];
 #pragma unroll
         for (int f = 0; f < 2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
