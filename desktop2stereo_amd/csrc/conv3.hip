@@ -1202,6 +1202,9 @@ conv3_wide_kernel(GemmA a, const bf16_t* __restrict__ W, int N, int Kpad, GemmEp
 //     conv1 -> conv2 (h1) and at the seam conv2 -> projection (h2);
 //   * every A-fragment read is conflict-free (the maps and their proof: rcu_c1_row ... rcu_b128_cycles below).
 // LDS: 7 x 16 KiB ring + 29 184 B (h0 | h2) + 17 280 B (h1) = 161 152 B.
+// conv3_rcu_kernel<PROJ, 1> is the WIDE form of the same body (RcuGeo below): 8 x 8 output pixels per block for a map whose 4 x 8 tiles
+// outnumber the CUs -- a 12 x 12 halo, conv1 on 10 x 10 positions in seven fragments, conv2 and the projection on 64 pixels in four,
+// and a ring of five stages (four tiles ahead): 5 x 16 KiB + 43 776 B (h0 | h2) + 28 800 B (h1) = 154 496 B.
 // ================================================================================================
 struct RcuArgs {
     const bf16_t* x;                 // [nimg, H, W, 128]
@@ -1281,6 +1284,68 @@ static_assert(rcu_b128_cycles(rcu_slots(0, 0)) == 4 && rcu_b128_cycles(rcu_slots
               rcu_b128_cycles(rcu_slots(0, 3)) == 4, "conv1's A-fragment reads must be conflict-free");
 static_assert(rcu_b128_cycles(rcu_slots(1, 0)) == 4 && rcu_b128_cycles(rcu_slots(1, 1)) == 4, "conv2's A-fragment reads must be conflict-free");
 static_assert(rcu_b128_cycles(rcu_slots(2, 0)) == 4 && rcu_b128_cycles(rcu_slots(2, 1)) == 4, "the projection's A-fragment reads must be conflict-free");
+// ---- the WIDE form: 8 x 8 output pixels per block, for a map whose 4 x 8 tiles outnumber the CUs (c3_rcu_wide_ok).  The launch is
+// bound by one block streaming the 622 KB of weights, not by its MFMA work, so twice the pixels per block cost little and halve the
+// blocks.  Same stride, same class arithmetic: h0 is 12 x 12 pixels with the row pitch 12 pixels + 12 chunks = 228 = 4 mod 16, h1 is
+// 10 x 10 positions with the pitch 10 pixels = 180 = 4 mod 16, so the class is (2 row + column) mod 8 in both, as above.
+//   * conv2 (four fragments): S takes the eight pixels of tile row 2 f, S' those of row 2 f + 1;
+//   * conv1 (seven fragments for 100 positions): fragments 0-4 take columns 0-7 of rows 2 f (S) and 2 f + 1 (S'); fragment 5 takes
+//     columns 8-9 of rows 0-3 (S) and 4-7 (S'); fragment 6 takes columns 8-9 of rows 6-9 in both halves and stores rows 8-9 from S
+//     only -- twelve of the 112 lanes repeat a position;
+//   * projection (four fragments): pixel 16 f + fr.
+constexpr int RCUW_TH = 8, RCUW_TW = 8;
+constexpr int RCUW_W0 = RCUW_TW + 4, RCUW_W1 = RCUW_TW + 2;
+constexpr int RCUW_RP0 = RCUW_W0 * RCU_PST + 12;
+constexpr int RCUW_RP1 = RCUW_W1 * RCU_PST;
+__host__ __device__ constexpr int rcuw_c1_row(int f, int fr) { return f < 5 ? 2 * f + rcu_half(fr) : (f == 5 ? (rcu_idx(fr) >> 1) + 4 * rcu_half(fr) : 6 + (rcu_idx(fr) >> 1)); }
+__host__ __device__ constexpr int rcuw_c1_col(int f, int fr) { return f < 5 ? rcu_idx(fr) : 8 + (rcu_idx(fr) & 1); }
+__host__ __device__ constexpr bool rcuw_c1_owns(int f, int fr) { return f < 6 || (!rcu_half(fr) && rcu_idx(fr) >= 4); }
+constexpr RcuSlots rcuw_slots(int region, int f) {
+    RcuSlots t{};
+    for (int lane = 0; lane < 64; ++lane) {
+        const int fr = lane & 15, fg = lane >> 4;
+        t.s[lane] = fg + (region == 0 ? rcuw_c1_row(f, fr) * RCUW_RP0 + rcuw_c1_col(f, fr) * RCU_PST
+                        : region == 1 ? (2 * f + rcu_half(fr)) * RCUW_RP1 + rcu_idx(fr) * RCU_PST
+                                      : (16 * f + fr) * RCU_PST);
+    }
+    return t;
+}
+constexpr bool rcuw_c1_covers() {                             // every position of the 10 x 10 tile is owned by exactly one lane
+    int n[(RCUW_TH + 2) * RCUW_W1] = {};
+    for (int f = 0; f < 7; ++f)
+        for (int fr = 0; fr < 16; ++fr) {
+            const int row = rcuw_c1_row(f, fr), col = rcuw_c1_col(f, fr);
+            if (row < 0 || row >= RCUW_TH + 2 || col < 0 || col >= RCUW_W1) return false;
+            if (rcuw_c1_owns(f, fr)) ++n[row * RCUW_W1 + col];
+        }
+    for (int p = 0; p < (RCUW_TH + 2) * RCUW_W1; ++p)
+        if (n[p] != 1) return false;
+    return true;
+}
+constexpr bool rcuw_conflict_free(int region, int nf) {
+    for (int f = 0; f < nf; ++f)
+        if (rcu_b128_cycles(rcuw_slots(region, f)) != 4) return false;
+    return true;
+}
+static_assert(rcuw_c1_covers(), "wide form: conv1's lanes must own every ring-extended position once");
+static_assert(rcuw_conflict_free(0, 7), "wide form: conv1's A-fragment reads must be conflict-free");
+static_assert(rcuw_conflict_free(1, 4), "wide form: conv2's A-fragment reads must be conflict-free");
+static_assert(rcuw_conflict_free(2, 4), "wide form: the projection's A-fragment reads must be conflict-free");
+// what the kernel body takes from its tile form: WIDE = 0 the 4 x 8 tile above, 1 the 8 x 8 tile.  NF1 / NF2: 16-lane fragments of
+// conv1's ring-extended positions / of the tile's pixels; NS: 16 KiB ring stages that fit beside h0 and h1 in 160 KiB
+template <int WIDE> struct RcuGeo;
+template <> struct RcuGeo<0> {
+    static constexpr int TH = RCU_TH, TW = RCU_TW, RP0 = RCU_RP0, RP1 = RCU_RP1, NF1 = 4, NF2 = 2, NS = 7;
+    __host__ __device__ static constexpr int c1_row(int f, int fr) { return rcu_c1_row(f, fr); }
+    __host__ __device__ static constexpr int c1_col(int f, int fr) { return rcu_c1_col(f, fr); }
+    __host__ __device__ static constexpr bool c1_owns(int f, int fr) { return rcu_c1_owns(f, fr); }
+};
+template <> struct RcuGeo<1> {
+    static constexpr int TH = RCUW_TH, TW = RCUW_TW, RP0 = RCUW_RP0, RP1 = RCUW_RP1, NF1 = 7, NF2 = 4, NS = 5;
+    __host__ __device__ static constexpr int c1_row(int f, int fr) { return rcuw_c1_row(f, fr); }
+    __host__ __device__ static constexpr int c1_col(int f, int fr) { return rcuw_c1_col(f, fr); }
+    __host__ __device__ static constexpr bool c1_owns(int f, int fr) { return rcuw_c1_owns(f, fr); }
+};
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 // four floats -> four bf16 (RNE, as store4 rounds them); relu: max(., 0) on the ROUNDED values, as relu_frag does on load
 __device__ __forceinline__ uint2 rcu_pack4(const float v[4], bool relu) {
@@ -1297,17 +1362,19 @@ __device__ __forceinline__ void rcu_lds_write_b64(const u32x4* chunk, int half, 
     const u32x2 d = {v.x, v.y};
     asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(d) : "memory");
 }
-template <int PROJ>
+template <int PROJ, int WIDE = 0>
 __global__ void __launch_bounds__(512)
 conv3_rcu_kernel(RcuArgs r) {
-    constexpr int TH = RCU_TH, TW = RCU_TW, CPP = 16, PST = RCU_PST, NW = 8;
-    constexpr int W0 = RCU_W0, P0 = (TH + 4) * W0, RP0 = RCU_RP0;   // input halo: 8 x 12 pixels, rows RP0 chunks apart
-    constexpr int W1 = RCU_W1, P1 = (TH + 2) * W1, RP1 = RCU_RP1;   // conv1's ring-extended tile: 6 x 10 positions
+    using G = RcuGeo<WIDE>;
+    constexpr int TH = G::TH, TW = G::TW, CPP = 16, PST = RCU_PST, NW = 8;
+    constexpr int W0 = TW + 4, P0 = (TH + 4) * W0, RP0 = G::RP0;    // input halo: 8 x 12 (wide: 12 x 12) pixels, rows RP0 chunks apart
+    constexpr int W1 = TW + 2, P1 = (TH + 2) * W1, RP1 = G::RP1;    // conv1's ring-extended tile: 6 x 10 (wide: 10 x 10) positions
     constexpr int L0 = (TH + 4) * RP0, L1 = (TH + 2) * RP1;         // chunks of h0 (| h2) and of h1
+    constexpr int NF1 = G::NF1, NF2 = G::NF2;               // 16-lane fragments of conv1's positions / of the tile's pixels
     constexpr int NKT = 18, NG = 2 * NKT + (PROJ ? 2 : 0);  // K tiles per convolution; tiles through the ring in all
     constexpr int WST = 128 * 8;                            // chunks per ring stage: 128 rows x 128 bytes
-    constexpr int NS = 7, PD = NS - 1, BI = 128 / (8 * NW); // stages, tiles requested ahead, LDS-DMA instructions per wave per tile
-    static_assert(P1 <= 64 && TH * TW == 32 && BI == 2 && NG > PD, "fragment counts below are for a 4 x 8 tile");
+    constexpr int NS = G::NS, PD = NS - 1, BI = 128 / (8 * NW); // stages, tiles requested ahead, LDS-DMA instructions per wave per tile
+    static_assert(P1 <= 16 * NF1 && TH * TW == 16 * NF2 && BI == 2 && NG > PD, "fragment counts of the tile form");
     static_assert(TH * TW * PST <= L0 && (NS * WST + L0 + L1) * 16 <= 160 * 1024, "h2 lies over h0; one block's LDS");
     __shared__ __attribute__((aligned(16))) u32x4 lds[NS * WST + L0 + L1];
     D2S_POISON_LDS(lds, NS * WST + L0 + L1)
@@ -1384,8 +1451,8 @@ conv3_rcu_kernel(RcuArgs r) {
     auto ring_step = [&]() -> const u32x4* {
         const int rem = NG - 1 - g;
         if (rem >= PD - 1) c3_wait_vm<(PD - 1) * BI>();
-        else if (rem == 4) c3_wait_vm<4 * BI>();
-        else if (rem == 3) c3_wait_vm<3 * BI>();
+        else if (PD > 5 && rem == 4) c3_wait_vm<4 * BI>();
+        else if (PD > 4 && rem == 3) c3_wait_vm<3 * BI>();
         else if (rem == 2) c3_wait_vm<2 * BI>();
         else if (rem == 1) c3_wait_vm<1 * BI>();
         else c3_wait_vm<0>();
@@ -1396,7 +1463,7 @@ conv3_rcu_kernel(RcuArgs r) {
         islot = islot + 1 == NS ? 0 : islot + 1;
         return B_l;
     };
-    static_assert(PD == 6, "ring_step spells out the waits of the last PD - 1 tiles");
+    static_assert(PD == 6 || PD == 4, "ring_step spells out the waits of the last PD - 1 tiles");
     // W fragment of this wave: row 16 wid + fr, chunk (4 ks + fg) ^ swizzle(row)
     int wo[2];
     {
@@ -1406,83 +1473,83 @@ conv3_rcu_kernel(RcuArgs r) {
     }
 
     // ---- conv1 on the ring-extended tile: lane fr of fragment f has position (py, px) = (rcu_c1_row, rcu_c1_col), image pixel
-    // (ty0 - 1 + py, tx0 - 1 + px); four lanes of fragment 3 repeat a position and do not store it.  A fragment: h0 pixel
-    // (py + ky, px + kx), chunk 8 sub + 4 ks + fg
+    // (ty0 - 1 + py, tx0 - 1 + px); four lanes of fragment 3 (wide: twelve of fragment 6) repeat a position and do not store it.
+    // A fragment: h0 pixel (py + ky, px + kx), chunk 8 sub + 4 ks + fg
     {
-        const u32x4* hb[4];
+        const u32x4* hb[NF1];
 #pragma unroll
-        for (int f = 0; f < 4; ++f) hb[f] = h0 + rcu_c1_row(f, fr) * RP0 + rcu_c1_col(f, fr) * PST + fg;
-        f32x4 acc[4];
+        for (int f = 0; f < NF1; ++f) hb[f] = h0 + G::c1_row(f, fr) * RP0 + G::c1_col(f, fr) * PST + fg;
+        f32x4 acc[NF1];
 #pragma unroll
-        for (int f = 0; f < 4; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int f = 0; f < NF1; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int kt = 0; kt < NKT; ++kt) {
             const int tap = kt >> 1, ky = (tap * 11) >> 5, kx = tap - 3 * ky;
             const int toff = ky * RP0 + kx * PST + (kt & 1) * 8;
             const u32x4* B_l = ring_step();
-            u32x4 fb[2], fa[2][4];                           // all ten fragments requested before the first MFMA: one LDS round trip per tile
+            u32x4 fb[2], fa[2][NF1];                         // all ten (wide: sixteen) fragments requested before the first MFMA: one LDS round trip per tile
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 fb[ks] = B_l[wo[ks]];
 #pragma unroll
-                for (int f = 0; f < 4; ++f) fa[ks][f] = hb[f][toff + ks * 4];
+                for (int f = 0; f < NF1; ++f) fa[ks][f] = hb[f][toff + ks * 4];
             }
             __builtin_amdgcn_sched_barrier(0);               // (the scheduler otherwise sinks each read to just in front of its MFMA)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int f = 0; f < 4; ++f) mma_chunk(acc[f], fb[ks], fa[ks][f], bf16_t());
+                for (int f = 0; f < NF1; ++f) mma_chunk(acc[f], fb[ks], fa[ks][f], bf16_t());
         }
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const int py = rcu_c1_row(f, fr), px = rcu_c1_col(f, fr);
+        for (int f = 0; f < NF1; ++f) {
+            const int py = G::c1_row(f, fr), px = G::c1_col(f, fr);
             const int iy = ty0 - 1 + py, ix = tx0 - 1 + px;
             const float v[4] = {acc[f][0] + c1[0], acc[f][1] + c1[1], acc[f][2] + c1[2], acc[f][3] + c1[3]};
             uint2 t = rcu_pack4(v, true);
             if (!(iy >= 0 && iy < r.H && ix >= 0 && ix < r.W)) t = make_uint2(0u, 0u);
-            if (rcu_c1_owns(f, fr)) rcu_lds_write_b64(h1 + py * RP1 + px * PST + 2 * wid + (fg >> 1), fg & 1, t);
+            if (G::c1_owns(f, fr)) rcu_lds_write_b64(h1 + py * RP1 + px * PST + 2 * wid + (fg >> 1), fg & 1, t);
         }
     }
     seam();                                                  // h1 is complete (and h0 is read out: h2 may overwrite it)
 
     // ---- conv2 on the tile: lane fr of fragment f has tile pixel (2 f + oy0, ox); A fragment: h1 position (oy + ky, ox + kx)
     const int oy0 = rcu_half(fr), ox = rcu_idx(fr);
-    uint2 rcu[2];
+    uint2 rcu[NF2];
     {
-        const u32x4* hb[2];
+        const u32x4* hb[NF2];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) hb[f] = h1 + (2 * f + oy0) * RP1 + ox * PST + fg;
-        f32x4 acc[2];
+        for (int f = 0; f < NF2; ++f) hb[f] = h1 + (2 * f + oy0) * RP1 + ox * PST + fg;
+        f32x4 acc[NF2];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int f = 0; f < NF2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int kt = 0; kt < NKT; ++kt) {
             const int tap = kt >> 1, ky = (tap * 11) >> 5, kx = tap - 3 * ky;
             const int toff = ky * RP1 + kx * PST + (kt & 1) * 8;
             const u32x4* B_l = ring_step();
-            u32x4 fb[2], fa[2][2];
+            u32x4 fb[2], fa[2][NF2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 fb[ks] = B_l[wo[ks]];
 #pragma unroll
-                for (int f = 0; f < 2; ++f) fa[ks][f] = hb[f][toff + ks * 4];
+                for (int f = 0; f < NF2; ++f) fa[ks][f] = hb[f][toff + ks * 4];
             }
             __builtin_amdgcn_sched_barrier(0);               // (the scheduler otherwise sinks each read to just in front of its MFMA)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int f = 0; f < 2; ++f) mma_chunk(acc[f], fb[ks], fa[ks][f], bf16_t());
+                for (int f = 0; f < NF2; ++f) mma_chunk(acc[f], fb[ks], fa[ks][f], bf16_t());
         }
         // epilogue4's order: + bias, + the residual x, round
-        float xr[2][4];
+        float xr[NF2][4];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
+        for (int f = 0; f < NF2; ++f) {
             const int y = ty0 + 2 * f + oy0, x = tx0 + ox;
             const bool ok = y < r.H && x < r.W;
             load4(r.x + ((long)(b * r.H + (ok ? y : 0)) * r.W + (ok ? x : 0)) * 128 + n0, xr[f]);
         }
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
+        for (int f = 0; f < NF2; ++f) {
             float v[4] = {acc[f][0] + c2[0], acc[f][1] + c2[1], acc[f][2] + c2[2], acc[f][3] + c2[3]};
             v[0] += xr[f][0]; v[1] += xr[f][1]; v[2] += xr[f][2]; v[3] += xr[f][3];
             rcu[f] = rcu_pack4(v, false);
@@ -1490,18 +1557,18 @@ conv3_rcu_kernel(RcuArgs r) {
     }
     if constexpr (!PROJ) {
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
+        for (int f = 0; f < NF2; ++f) {
             const int y = ty0 + 2 * f + oy0, x = tx0 + ox;
             if (y < r.H && x < r.W) *(uint2*)(r.out + ((long)(b * r.H + y) * r.W + x) * 128 + n0) = rcu[f];
         }
     } else {
         // ---- the 1x1 projection of the rounded tile: K = 128 = the ring's last two tiles; A fragment: h2 pixel p, chunk 8 kt + 4 ks + fg
 #pragma unroll
-        for (int f = 0; f < 2; ++f) rcu_lds_write_b64(h2 + (f * 16 + fr) * PST + 2 * wid + (fg >> 1), fg & 1, rcu[f]);
+        for (int f = 0; f < NF2; ++f) rcu_lds_write_b64(h2 + (f * 16 + fr) * PST + 2 * wid + (fg >> 1), fg & 1, rcu[f]);
         seam();
-        f32x4 acc[2];
+        f32x4 acc[NF2];
 #pragma unroll
-        for (int f = 0; f < 2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int f = 0; f < NF2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int kt = 0; kt < 2; ++kt) {
             const u32x4* B_l = ring_step();
@@ -1509,11 +1576,11 @@ conv3_rcu_kernel(RcuArgs r) {
             for (int ks = 0; ks < 2; ++ks) {
                 const u32x4 fb = B_l[wo[ks]];
 #pragma unroll
-                for (int f = 0; f < 2; ++f) mma_chunk(acc[f], fb, h2[(f * 16 + fr) * PST + fg + kt * 8 + ks * 4], bf16_t());
+                for (int f = 0; f < NF2; ++f) mma_chunk(acc[f], fb, h2[(f * 16 + fr) * PST + fg + kt * 8 + ks * 4], bf16_t());
             }
         }
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
+        for (int f = 0; f < NF2; ++f) {
             const int y = ty0 + 2 * f + oy0, x = tx0 + ox;
             const float v[4] = {acc[f][0] + cp[0], acc[f][1] + cp[1], acc[f][2] + cp[2], acc[f][3] + cp[3]};
             if (y < r.H && x < r.W) *(uint2*)(r.out + ((long)(b * r.H + y) * r.W + x) * 128 + n0) = rcu_pack4(v, false);
@@ -1528,6 +1595,8 @@ conv3_rcu_kernel(RcuArgs r) {
 #define C3_INSTANCES(P, H, R)                                                                                                    \
     R(C3_RCU, conv3_rcu_kernel<0>)                                                                                               \
     R(C3_RCU_PROJ, conv3_rcu_kernel<1>)                                                                                          \
+    R(C3_RCU_WIDE, conv3_rcu_kernel<0,1>)      /* the 8 x 8-pixel tile form (c3_rcu_wide_ok) */                                  \
+    R(C3_RCU_WIDE_PROJ, conv3_rcu_kernel<1,1>)                                                                                   \
     P(C3_HEAD_UPS, conv3_head_ups_kernel)                                                                                        \
     P(C3_HEAD_1, conv3_head_kernel<1>)                                                                                           \
     P(C3_HEAD_0, conv3_head_kernel<0>)                                                                                           \
@@ -1667,12 +1736,27 @@ bool c3_rcu_ok(bool plain_bf16, int C, int nimg, int H, int W) {
     return plain_bf16 && C == 128 && nimg > 0 && H > 0 && W > 0 && (long)nimg * H * W * 128 < (1L << 31) &&
            (long)nimg * cdiv(H, RCU_TH) * cdiv(W, RCU_TW) <= device_cu_count();
 }
-bool plan_conv3_rcu(bool plain_bf16, int C, int nimg, int H, int W, bool proj, GemmPlan& p) {
-    if (!c3_rcu_ok(plain_bf16, C, nimg, H, W)) return false;
+// The wide form (8 x 8-pixel tiles, conv3_rcu_kernel<PROJ, 1>).  c3_rcu_wide_fits: what the kernel itself needs, the same conditions
+// with its own tile count (what d2s_rcu_probe asks).  c3_rcu_wide_ok: the rule a frame's plan follows -- a map takes the wide form when
+// the 4 x 8 form does not admit it and the wide form fits.
+bool c3_rcu_wide_fits(bool plain_bf16, int C, int nimg, int H, int W) {
+    return plain_bf16 && C == 128 && nimg > 0 && H > 0 && W > 0 && (long)nimg * H * W * 128 < (1L << 31) &&
+           (long)nimg * cdiv(H, RCUW_TH) * cdiv(W, RCUW_TW) <= device_cu_count();
+}
+// MEASURED (profiles/rcu_wide_ab.txt): the launch takes 19 us with the projection on the 84 x 148 map at batch 1 (209 blocks) against
+// 13.4 + 13.4 us + the projection's launch separately, and 26 us as two rounds of 399 4 x 8 blocks; bracketed, every admitted map at batch
+// 1, 4, 9 and 17 is 14-32 us shorter as one launch.  RCUW_MAX_IMAGES: the largest batch that table covers; beyond it (the 11 x 19 map
+// would fit again at 29-42 frames) a map keeps its launches.
+constexpr int RCUW_MAX_IMAGES = 17;
+bool c3_rcu_wide_ok(bool plain_bf16, int C, int nimg, int H, int W) {
+    return nimg <= RCUW_MAX_IMAGES && !c3_rcu_ok(plain_bf16, C, nimg, H, W) && c3_rcu_wide_fits(plain_bf16, C, nimg, H, W);
+}
+bool plan_conv3_rcu(bool plain_bf16, int C, int nimg, int H, int W, bool proj, bool wide, GemmPlan& p) {
+    if (!(wide ? c3_rcu_wide_fits(plain_bf16, C, nimg, H, W) : c3_rcu_ok(plain_bf16, C, nimg, H, W))) return false;
     p = GemmPlan{};
-    const int inst = proj ? C3_RCU_PROJ : C3_RCU;
+    const int inst = wide ? (proj ? C3_RCU_WIDE_PROJ : C3_RCU_WIDE) : (proj ? C3_RCU_PROJ : C3_RCU);
     p.family = GEMM_CONV3; p.inst = inst; p.name = c3_inst[inst].name; p.block = c3_inst[inst].block;
-    p.grid = (unsigned)(nimg * cdiv(H, RCU_TH) * cdiv(W, RCU_TW)); p.ksplit = 1;
+    p.grid = (unsigned)(wide ? nimg * cdiv(H, RCUW_TH) * cdiv(W, RCUW_TW) : nimg * cdiv(H, RCU_TH) * cdiv(W, RCU_TW)); p.ksplit = 1;
     return true;
 }
 void launch_conv3_rcu(const GemmPlan& p, const RcuOp& o, hipStream_t st) {

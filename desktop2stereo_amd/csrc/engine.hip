@@ -320,9 +320,9 @@ int conv3(d2s_engine* e, const void* in, int B, int Hi, int Wi, int C, int strid
 
 // A fusion stage's residual unit as one launch (pl.rcu_fused / pl.rcu1_fused; conv3.hip conv3_rcu_kernel):
 // out = x + c2(relu(c1(relu(x)))), through proj where given -- what conv3, conv3 (+ linear) compute in two (three) launches, bit for bit
-int rcu(d2s_engine* e, const void* x, int B, int H, int W, const DevLinear& c1, const DevLinear& c2, const DevLinear* proj, void* out, hipStream_t st) {
+int rcu(d2s_engine* e, const void* x, int B, int H, int W, const DevLinear& c1, const DevLinear& c2, const DevLinear* proj, bool wide, void* out, hipStream_t st) {
     GemmPlan p;
-    if (!plan_conv3_rcu(true, e->d.fusion, B, H, W, proj != nullptr, p) || c1.Kpad != c2.Kpad || !c1.bias || !c2.bias || (proj && !proj->bias)) {
+    if (!plan_conv3_rcu(true, e->d.fusion, B, H, W, proj != nullptr, wide, p) || c1.Kpad != c2.Kpad || !c1.bias || !c2.bias || (proj && !proj->bias)) {
         set_error("forward: the frame's plan fuses a residual unit that conv3_rcu_kernel does not take");
         return D2S_E_STATE;
     }
@@ -455,7 +455,7 @@ int neck_rest(d2s_engine* e, const ForwardPlan& pl, int i, int B, hipStream_t st
     RC(conv3(e, src, B, Hs, Ws, c, 1, 0, e->re[i].conv, e->feat[i], ACT_NONE, nullptr, nullptr, st));
     if (i < 3) {
         const int idx = 3 - i;                          // the fusion layer that consumes this map
-        if (pl.rcu1_fused[i]) RC(rcu(e, e->feat[i], B, Hs, Ws, e->fu[idx].r1c1, e->fu[idx].r1c2, nullptr, e->r1[i], st));
+        if (pl.rcu1_fused[i] || pl.rcu1_wide[i]) RC(rcu(e, e->feat[i], B, Hs, Ws, e->fu[idx].r1c1, e->fu[idx].r1c2, nullptr, pl.rcu1_wide[i], e->r1[i], st));
         else {
             RC(conv3(e, e->feat[i], B, Hs, Ws, F, 1, 1, e->fu[idx].r1c1, e->r1tmp, ACT_NONE, nullptr, nullptr, st));
             RC(conv3(e, e->r1tmp, B, Hs, Ws, F, 1, 1, e->fu[idx].r1c2, e->r1[i], ACT_NONE, e->feat[i], nullptr, st));
@@ -582,7 +582,8 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         Hc = e->g.fH[mi]; Wc = e->g.fW[mi];
         const void* hcur = idx == 0 ? m : fused;
         // RCU2 and the projection behind it (below): X = proj(h + r2c2(relu(r2c1(relu(h))))), one launch where the plan fuses the stage
-        if (pl.rcu_fused[idx]) RC(rcu(e, hcur, B, Hc, Wc, e->fu[idx].r2c1, e->fu[idx].r2c2, &e->fu[idx].proj, X, st));
+        const bool one_launch = pl.rcu_fused[idx] || pl.rcu_wide[idx];
+        if (one_launch) RC(rcu(e, hcur, B, Hc, Wc, e->fu[idx].r2c1, e->fu[idx].r2c2, &e->fu[idx].proj, pl.rcu_wide[idx], X, st));
         else {
             RC(conv3(e, hcur, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c1, X, ACT_NONE, nullptr, nullptr, st));
             RC(conv3(e, X, B, Hc, Wc, F, 1, 1, e->fu[idx].r2c2, Z, ACT_NONE, hcur, nullptr, st));
@@ -593,7 +594,7 @@ int forward(d2s_engine* e, const float* x, float* depth, int B, hipStream_t st) 
         // (interpolation weights sum to 1), so it runs BEFORE the up-sample on 4x fewer pixels.
         void* pout = e->scr[3 + (idx & 1)];
         const void* next_r1 = idx < 3 ? e->r1[2 - idx] : nullptr;      // RCU1 of the next (shallower) stage's map
-        if (!pl.rcu_fused[idx]) RC(linear(e, plainA(Z, F), e->fu[idx].proj, B * Hc * Wc, rowsE(X, OUT_T, F, e->fu[idx].proj.bias), st));
+        if (!one_launch) RC(linear(e, plainA(Z, F), e->fu[idx].proj, B * Hc * Wc, rowsE(X, OUT_T, F, e->fu[idx].proj.bias), st));
         if (d.temporal && idx < 2) {                     // path_4 / path_3 (dpt_temporal.py:98-103)
             PROF(PC_ELT, 0, 0, launch_bilinear_nhwc(prec, X, pout, B, Hc, Wc, Ho, Wo, F, st));
             void* alt = e->scr[3 + ((idx + 1) & 1)];
@@ -998,7 +999,8 @@ extern "C" int d2s_forward_plan(const d2s_model_desc* desc, int h, int w, int ba
     r.gh = g.gh; r.gw = g.gw; r.P = g.P; r.N = g.N; r.Npad = g.Npad;
     for (int i = 0; i < 4; ++i) { r.fH[i] = g.fH[i]; r.fW[i] = g.fW[i]; r.tm_C[i] = d.temporal ? g.tmC[i] : 0; r.tm_sites[i] = d.temporal ? g.tmS[i] : 0; }
     r.ln_launches = pl.ln_launches;
-    for (int i = 0; i < 4; ++i) r.rcu_fused |= (pl.rcu_fused[i] ? 1 << i : 0) | (pl.rcu1_fused[i] ? 256 << i : 0);
+    for (int i = 0; i < 4; ++i)
+        r.rcu_fused |= (pl.rcu_fused[i] ? 1 << i : 0) | (pl.rcu1_fused[i] ? 256 << i : 0) | (pl.rcu_wide[i] ? 1 << (16 + i) : 0) | (pl.rcu1_wide[i] ? 1 << (24 + i) : 0);
     r.splitk_elems = g.splitk_elems; r.scr_elems = g.scr_elems;
     *res = r;
     return D2S_OK;

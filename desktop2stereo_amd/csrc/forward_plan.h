@@ -118,6 +118,7 @@ struct ForwardPlan {
     int bn;
     bool rcu_fused[4];              // fusion stage idx: r2c1 + r2c2 + the 1x1 projection as one launch (conv3.hip conv3_rcu_kernel<1>)
     bool rcu1_fused[4];             // tap i (< 3): the RCU1 of its fusion layer, r1c1 + r1c2, as one launch (conv3_rcu_kernel<0>)
+    bool rcu_wide[4], rcu1_wide[4]; // the same as one launch of the kernel's wide form (conv3_rcu_kernel<PROJ, 1>, 8 x 8-pixel tiles)
     bool tm_fold;                   // temporal modules: proj_in / to_out / ff2 leave the bf16 copy (and statistics) of the folded forms
     struct { int slots[3]; bool folded[3]; } tm[4];   // per temporal module: norms.0 -> kvq[0], norms.1 -> kvq[1], ff_norm -> ff1
     int ln_launches;                // LayerNorm launches of the frame
@@ -139,6 +140,9 @@ struct ForwardPlan {
 //                                statistics and the raw residual of a tap layer are still in lnbuf / lnstats when its projection runs).
 //   rcu_fused                    bf16, fusion width 128, a map whose 4 x 8-pixel tiles x B fit the CUs: the stage's residual unit and
 //                                projection (the taps' RCU1) are one launch; at 294 x 518 the three small maps at B = 1, two at B = 2-4.
+//   rcu_wide                     the same engines, a map the 4 x 8 tiles do not fit and whose 8 x 8-pixel tiles x B do (c3_rcu_wide_ok): one
+//                                launch of the kernel's wide form; at 294 x 518 the 84 x 148 map (stage 3, tap 0's RCU1) at B = 1, the
+//                                42 x 74 map at B = 3-4, 21 x 37 at B = 9-17 (each faster than its launches: profiles/rcu_wide_ab.txt).
 //   calibrating, D2S_TAPS        calibration folds nothing (it measures the LayerNorm outputs); taps keep pp_fold off.
 static inline int plan_forward(const d2s_model_desc& d, const EngineGeom& g, int h, int w, int B, const FrameState& s, ForwardPlan& pl) {
     pl = ForwardPlan{};
@@ -194,6 +198,9 @@ static inline int plan_forward(const d2s_model_desc& d, const EngineGeom& g, int
             const bool ok = c3_rcu_ok(plain_bf16, F, B, g.fH[i], g.fW[i]);
             pl.rcu_fused[3 - i] = ok;
             pl.rcu1_fused[i] = ok && i < 3;
+            const bool wide = c3_rcu_wide_ok(plain_bf16, F, B, g.fH[i], g.fW[i]);     // (never with ok: the rule asks that c3_rcu_ok refuses)
+            pl.rcu_wide[3 - i] = wide;
+            pl.rcu1_wide[i] = wide && i < 3;
         }
     }
     // ---- temporal modules: the LayerNorm in front of kvq[0] / kvq[1] / ff1 folds where its producer (proj_in / to_out[0] / to_out[1])

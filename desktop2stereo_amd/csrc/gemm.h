@@ -133,7 +133,9 @@ struct RcuOp {
     int Kpad, KpadP;
 };
 bool c3_rcu_ok(bool plain_bf16, int C, int nimg, int H, int W);
-bool plan_conv3_rcu(bool plain_bf16, int C, int nimg, int H, int W, bool proj, GemmPlan& p);
+bool c3_rcu_wide_fits(bool plain_bf16, int C, int nimg, int H, int W);   // the wide form (8 x 8-pixel tiles): its own residency
+bool c3_rcu_wide_ok(bool plain_bf16, int C, int nimg, int H, int W);     // ... and the plan's rule: c3_rcu_ok refuses, the wide form fits
+bool plan_conv3_rcu(bool plain_bf16, int C, int nimg, int H, int W, bool proj, bool wide, GemmPlan& p);
 void launch_conv3_rcu(const GemmPlan& p, const RcuOp& o, hipStream_t st);
 // 256 x 256 ping-pong kernel (gemm_pp.hip): batched plain linears
 bool pp_supported(int precision, const GemmA& a, int M, int N, int K, int Kpad, const GemmEpi& e);

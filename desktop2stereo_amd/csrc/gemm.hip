@@ -1122,8 +1122,10 @@ extern "C" int d2s_rcu_probe(d2s_rcu_probe_params* p, void* stream) {
     const long npx = (long)B * H * W;
     D2S_REQUIRE(npx * C < (1L << 31), "too large");
     GemmPlan plan;
-    if (!plan_conv3_rcu(true, C, B, H, W, p->wp != nullptr, plan)) {
-        set_error("d2s_rcu_probe: c3_rcu_ok refuses this map (C = 128 and tiles x images <= CU count)");
+    D2S_REQUIRE(p->reserved == 0 || p->reserved == 1, "reserved selects the tile form: 0 or 1");
+    if (!plan_conv3_rcu(true, C, B, H, W, p->wp != nullptr, p->reserved == 1, plan)) {
+        set_error(p->reserved ? "d2s_rcu_probe: c3_rcu_wide_fits refuses this map (C = 128 and 8 x 8-pixel tiles x images <= CU count)"
+                              : "d2s_rcu_probe: c3_rcu_ok refuses this map (C = 128 and tiles x images <= CU count)");
         return D2S_E_UNSUPPORTED;
     }
     // the weights packed as pack_conv3 / pack_linear pack them

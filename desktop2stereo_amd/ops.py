@@ -823,6 +823,8 @@ def forward_plan(cfg: ModelConfig, h: int, w: int, batch: int = 1, precision: st
     out["tm_folded"] = [[bool(v) for v in m] for m in r.tm_folded]
     out["rcu_fused"] = [bool(r.rcu_fused >> i & 1) for i in range(4)]            # fusion stages, deep -> shallow
     out["rcu1_fused"] = [bool(r.rcu_fused >> (8 + i) & 1) for i in range(3)]     # the RCU1 of taps 0..2
+    out["rcu_wide"] = [bool(r.rcu_fused >> (16 + i) & 1) for i in range(4)]      # ... as one launch of the wide (8 x 8-pixel tile) form
+    out["rcu1_wide"] = [bool(r.rcu_fused >> (24 + i) & 1) for i in range(3)]
     return out
 
 
@@ -1172,10 +1174,11 @@ def conv3_probe(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
 
 
 def rcu_probe(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
-              wp: Optional[torch.Tensor] = None, bp: Optional[torch.Tensor] = None):
+              wp: Optional[torch.Tensor] = None, bp: Optional[torch.Tensor] = None, *, wide: bool = False):
     """A fusion stage's residual unit as the one launch the engine makes of it on a small map (test probe, include/d2s.h d2s_rcu_probe):
     x + conv2(relu(conv1(relu(x)))), through the 1x1 projection (wp [C, C], bp) where given.  x: float32 [B, H, W, C], w1 / w2: float32
-    [C, C, 3, 3], biases [C].  Returns (out bfloat16 [B, H, W, C], kernel name); D2SError where the engine would keep the separate launches."""
+    [C, C, 3, 3], biases [C].  wide: the kernel's 8 x 8-pixel tile form (refused where those tiles x B exceed the CUs) instead of the 4 x 8
+    one.  Returns (out bfloat16 [B, H, W, C], kernel name); D2SError where the engine would keep the separate launches."""
     _need_cuda(x, "x")
     B, H, W, Cc = x.shape
     if tuple(w1.shape) != (Cc, Cc, 3, 3) or tuple(w2.shape) != (Cc, Cc, 3, 3) or (wp is not None and tuple(wp.shape) != (Cc, Cc)):
@@ -1186,6 +1189,7 @@ def rcu_probe(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Ten
     p = _lib.RcuProbeParams()
     p.struct_size = C.sizeof(_lib.RcuProbeParams)
     p.batch, p.H, p.W, p.C = B, H, W, Cc
+    p.reserved = 1 if wide else 0
     p.x, p.w1, p.b1, p.w2, p.b2 = (_ptr(t) for t in keep[:5])
     if wp is not None:
         p.wp, p.bp = _ptr(keep[5]), _ptr(keep[6])

@@ -304,7 +304,8 @@ int d2s_engine_calibrate(d2s_engine* e, const float* x, int batch, void* stream)
  *   geometry     what d2s_engine_finalize sizes the engine with: patch grid, tokens, the four neck maps, split-K / scratch elements,
  *                the temporal modules' channels and sites
  *   rcu_fused    the fusion stages (deep -> shallow) whose RCU2 + 1x1 projection, and the taps whose RCU1, are one launch (bf16,
- *                fusion width 128, maps whose 4 x 8-pixel tiles x batch fit the CUs; D2S_RCU_FUSE=0: none)
+ *                fusion width 128, maps whose 4 x 8-pixel tiles x batch fit the CUs; D2S_RCU_FUSE=0: none); and those that are one
+ *                launch of the kernel's wide form (8 x 8-pixel tiles: a map the 4 x 8 tiles do not fit and the 8 x 8 tiles do)
  *   ln_launches  LayerNorm launches of the call (d2s_engine_profile_read's "layernorm" class) */
 #define D2S_PLAN_CALIBRATING    1   /* the forward pass inside d2s_engine_calibrate */
 #define D2S_PLAN_PROFILING      2   /* d2s_engine_profile is on */
@@ -324,7 +325,8 @@ typedef struct d2s_forward_plan_result {
     int32_t gh, gw, P, N, Npad, fH[4], fW[4], tm_C[4], tm_sites[4];
     int32_t ln_launches;
     int32_t rcu_fused;         /* d2s_version() >= 125 (the word was padding, zero before): bit idx = fusion stage idx runs its residual
-                                  unit and projection as one launch; bit 8 + i = the RCU1 of tap i does */
+                                  unit and projection as one launch; bit 8 + i = the RCU1 of tap i does.  d2s_version() >= 131: bit
+                                  16 + idx / bit 24 + i = the same as one launch of the wide form (never set together with the former) */
     uint64_t splitk_elems, scr_elems;
 } d2s_forward_plan_result;
 int d2s_forward_plan(const d2s_model_desc* desc, int h, int w, int batch, int flags, d2s_forward_plan_result* res);
@@ -972,11 +974,11 @@ int d2s_conv3_probe(d2s_conv3_probe_params* p, void* stream);
 /* Stand-alone probe of a fusion stage's fused residual unit (tests; d2s_version() >= 125): out = x + conv2(relu(conv1(relu(x)))), and
  * with wp its 1x1 projection wp (.) + bp, as ONE launch (conv3_rcu_kernel), bf16, weights packed through the functions the engine packs
  * them with.  It plans (the engine's rule: C = 128, 4 x 8-pixel tiles x batch <= CU count; D2S_E_UNSUPPORTED otherwise), launches that
- * plan and reports the kernel.  The reference is the same chain through d2s_conv3_probe (relu_in, res) and d2s_linear_probe. */
+ * plan and reports the kernel.  reserved = 1 (d2s_version() >= 131): the kernel's wide form, 8 x 8-pixel tiles x batch <= CU count.  The reference is the same chain through d2s_conv3_probe (relu_in, res) and d2s_linear_probe. */
 typedef struct d2s_rcu_probe_params {
     uint32_t struct_size;      /* MUST be sizeof(d2s_rcu_probe_params) = 216 */
     int32_t batch, H, W, C;    /* the map x [batch, H, W, C] */
-    int32_t reserved;          /* 0 */
+    int32_t reserved;          /* 0: the 4 x 8-pixel tile form; 1: the wide form */
     const float* x;            /* device, [batch, H, W, C] */
     const float* w1;           /* device, PyTorch layout [C, C, 3, 3] */
     const float* b1;           /* device, [C] */
@@ -985,7 +987,7 @@ typedef struct d2s_rcu_probe_params {
     const float* wp;           /* device, [C, C], or null: no projection */
     const float* bp;           /* device, [C] (with wp) */
     void* out;                 /* device, [batch, H, W, C] bf16 */
-    char kernel[128];          /* out: "conv3_rcu_kernel<0>" | "conv3_rcu_kernel<1>" */
+    char kernel[128];          /* out: "conv3_rcu_kernel<0>" | "conv3_rcu_kernel<1>"; wide: "conv3_rcu_kernel<0,1>" | "conv3_rcu_kernel<1,1>" */
 } d2s_rcu_probe_params;
 int d2s_rcu_probe(d2s_rcu_probe_params* p, void* stream);
 
