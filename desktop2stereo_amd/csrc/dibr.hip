@@ -236,6 +236,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIBR_W
 dibr_rows_kernel(const uint8_t* __restrict__ rgb_all, const float* __restrict__ dep_all, void* __restrict__ out_all, G g, int margin, int WW) {
     extern __shared__ float dibr_win[];                // [2][WW] the row pair of the depth texture | [6][WW] R0 G0 B0 R1 G1 B1 as floats
     __shared__ int queue[2 * COLS], qn;                // (column - xb) * 2 + eye of the pixels that need the in-painting
+    static_assert(sizeof(queue) + sizeof(qn) == dibr_rows_static_lds(COLS), "the launch plan's LDS bound counts these arrays (dibr_tex.h)");
     const int tid = threadIdx.x, xb = blockIdx.x * COLS;
     const int y = blockIdx.y, b = blockIdx.z;
     const uint8_t* rgb = rgb_all + (long)b * g.H * g.W * 3;
@@ -887,20 +888,31 @@ extern "C" int d2s_dibr_shape(int H, int W, int display_mode, int* out_h, int* o
     return dibr_eye_shape(H, W, display_mode, &oh, &ow, out_h, out_w);
 }
 
-// d2s_dibr_warp (dh == H && dw == W: depth IS the texture, the FullDep kernels) and d2s_dibr_warp_depth (any other [dh, dw]: the
-// UpDep kernels).  Every argument is checked before any HIP call.
-// G = DibrGeom: crop == nullptr; G = DibrGeomCrop: d2s_dibr_warp_crop.
+// Everything dibr_warp_impl decides, stated once on the host (d2s_dibr_warp_plan reports it; tests/test_cpu_dibr_plan.py pins it):
+// the checks of everything that is no pointer, the uniforms, the eye shape, the three switches, the window plan, and from them the
+// kernel, its grid and its LDS.  No HIP call.
+struct DibrWarpPlan {
+    DibrWindow win;
+    bool roll0, up, fx, u8;
+    dim3 grid, block;
+    unsigned lds_dynamic, lds_static;      // the row kernel's request; 0 for the gather kernel
+};
+// the kernel's name with its template arguments (formed for d2s_dibr_warp_plan only: the launch path formats nothing)
+static void dibr_plan_name(const DibrWarpPlan& pl, bool crop, char* name, size_t n) {
+    const char* fmt = pl.u8 ? "u8" : "f32";
+    const char* dname = pl.up ? "UpDep" : "FullDep";
+    if (pl.win.rows) snprintf(name, n, "dibr_rows<%s,fx=%d,%d,%s%s>", fmt, pl.fx ? 1 : 0, pl.win.cols, dname, crop ? ",crop" : "");
+    else snprintf(name, n, "dibr<%s,%s,%s%s>", fmt, pl.roll0 ? "roll0" : "general", dname, crop ? ",crop" : "");
+}
 template <class G>
-static int dibr_warp_impl(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
-                          const double* crop, void* out, int out_fmt, void* stream, bool check_only) {
+static int dibr_warp_plan_impl(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, int out_fmt,
+                               G& g, DibrWarpPlan& pl) {
     constexpr bool CR = G::crop;
-    D2S_REQUIRE(rgb && depth && p && out, "null pointer");
     int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
     if (rc) return rc;
-    G g;
     dibr_fill_geom(g, p, H, W, dh, dw);
     g.mode = p->display_mode;
-    const bool up = dh != H || dw != W;
+    pl.up = dh != H || dw != W;
     rc = CR ? crop_eye_shape(H, W, crop, p->display_mode, &g.oh, &g.ow, &g.out_h, &g.out_w)
             : dibr_eye_shape(H, W, p->display_mode, &g.oh, &g.ow, &g.out_h, &g.out_w);
     if (rc) return rc;
@@ -910,27 +922,56 @@ static int dibr_warp_impl(const uint8_t* rgb, const float* depth, int dh, int dw
     g.vpx = vp0 ? 0.f : p->viewport[0]; g.vpy = vp0 ? 0.f : p->viewport[1];
     g.vpw = vp0 ? (float)g.ow : p->viewport[2]; g.vph = vp0 ? (float)g.oh : p->viewport[3];
     D2S_REQUIRE(2 * g.oh <= 65535, "frame too large for one launch");
-    if (check_only) return D2S_OK;
-    dim3 grid(cdiv(g.ow, 256), 2 * g.oh, batch), block(256);
     static EnvInt no_roll0{"D2S_DIBR_NO_ROLL0", 0};        // (A/B aids: the general per-tap evaluation for roll == 0 too;
     static EnvInt no_rows{"D2S_DIBR_NO_ROWS", 0};          //  the gather kernel instead of the LDS-window kernel;
     static EnvInt cols_env{"D2S_DIBR_COLS", 512};          //  256 | 512 | 1024 caps the columns per block)
-    const bool roll0 = g.s == 0.f && g.c == 1.f && !no_roll0.get();
+    pl.roll0 = g.s == 0.f && g.c == 1.f && !no_roll0.get();
     // source texels per output column: W / ow, of the cropped span with a crop (1 when the eye viewport is the crop's pixel size)
     double tex_per_col = (double)W / (double)g.ow;
     if constexpr (CR) tex_per_col *= (double)g.cw;
     // columns per block: 512 while the window stays <= 640 texels (20 KB of LDS: seven blocks per CU either way).  1080p Full-SBS
     // 50.8 -> 46.8 us (half the second-pass waves); Half-SBS (two source texels per column) keeps 256: 24.4 us against 26.8;
     // 1024 columns: 63.9 us (34 KB per block), an A/B aid of the uncropped FullDep kernels only, up to 1536 texels (48 KB).
-    // Windows above 2048 texels take the gather kernel.
-    const bool wide = cols_env.get() >= 1024 && !up && !CR;
-    const DibrWindow win = dibr_plan_window(g, tex_per_col, roll0 && !no_rows.get(), wide ? 1024 : (cols_env.get() >= 512 ? 512 : 256),
-                                            wide ? 1536 : 640, 2048);
-    if (win.rows) {
-        const int margin = win.margin, cols = win.cols, WWc = win.WW;
-        dim3 rgrid(cdiv(g.ow, cols), g.oh, batch);
-        const size_t lds = (size_t)8 * WWc * sizeof(float);
-        const bool fx = g.feather || g.corner_r > 0.f;
+    // Windows above DIBR_F1_ROWS_WORDS = 1983 texels -- the largest whose 8 planes fit 64 KB of LDS beside the 256-column kernel's
+    // static queue -- take the gather kernel.
+    const bool wide = cols_env.get() >= 1024 && !pl.up && !CR;
+    pl.win = dibr_plan_window(g, tex_per_col, pl.roll0 && !no_rows.get(), wide ? 1024 : (cols_env.get() >= 512 ? 512 : 256),
+                              wide ? 1536 : 640, DIBR_F1_ROWS_WORDS);
+    pl.fx = g.feather || g.corner_r > 0.f;
+    pl.u8 = out_fmt == D2S_FMT_U8_HWC;
+    pl.block = dim3(256);
+    if (pl.win.rows) {
+        pl.grid = dim3(cdiv(g.ow, pl.win.cols), g.oh, batch);
+        pl.lds_dynamic = dibr_rows_dynamic_lds(pl.win.WW);
+        pl.lds_static = dibr_rows_static_lds(pl.win.cols);
+        D2S_REQUIRE(pl.lds_dynamic + pl.lds_static <= DIBR_LDS_LIMIT, "internal: the window plan exceeds the LDS of a block");
+    } else {
+        pl.grid = dim3(cdiv(g.ow, 256), 2 * g.oh, batch);
+        pl.lds_dynamic = pl.lds_static = 0;
+    }
+    return D2S_OK;
+}
+
+// d2s_dibr_warp (dh == H && dw == W: depth IS the texture, the FullDep kernels) and d2s_dibr_warp_depth (any other [dh, dw]: the
+// UpDep kernels).  Every argument is checked before any HIP call.
+// G = DibrGeom: crop == nullptr; G = DibrGeomCrop: d2s_dibr_warp_crop.
+// The decision is dibr_warp_plan_impl's; this function looks at the pointers and launches what the plan says.
+template <class G>
+static int dibr_warp_impl(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
+                          const double* crop, void* out, int out_fmt, void* stream, bool check_only) {
+    constexpr bool CR = G::crop;
+    D2S_REQUIRE(rgb && depth && p && out, "null pointer");
+    G g;
+    DibrWarpPlan pl;
+    const int rc = dibr_warp_plan_impl<G>(dh, dw, batch, H, W, p, crop, out_fmt, g, pl);
+    if (rc) return rc;
+    if (check_only) return D2S_OK;
+    const bool up = pl.up, roll0 = pl.roll0, fx = pl.fx;
+    const dim3 grid = pl.grid, block = pl.block;
+    if (pl.win.rows) {
+        const int margin = pl.win.margin, cols = pl.win.cols, WWc = pl.win.WW;
+        const dim3 rgrid = grid;
+        const size_t lds = pl.lds_dynamic;
 #define DIBR_ROWS(FMT, FXV, COLS, D) hipLaunchKernelGGL((dibr_rows_kernel<FMT, FXV, COLS, D, G>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, g, margin, WWc)
 // (the 1 024-column form exists for the uncropped FullDep kernels only: `wide` is false otherwise, and it is not instantiated with a crop)
 #define DIBR_ROWS_C(FMT, FXV) do { bool wide_done = false; \
@@ -939,14 +980,14 @@ static int dibr_warp_impl(const uint8_t* rgb, const float* depth, int dh, int dw
                                    if (up) { if (cols == 512) DIBR_ROWS(FMT, FXV, 512, UpDep); else DIBR_ROWS(FMT, FXV, 256, UpDep); } \
                                    else if (cols == 512) DIBR_ROWS(FMT, FXV, 512, FullDep); \
                                    else DIBR_ROWS(FMT, FXV, 256, FullDep); } while (0)
-        if (out_fmt == D2S_FMT_U8_HWC) { if (fx) DIBR_ROWS_C(D2S_FMT_U8_HWC, true); else DIBR_ROWS_C(D2S_FMT_U8_HWC, false); }
+        if (pl.u8) { if (fx) DIBR_ROWS_C(D2S_FMT_U8_HWC, true); else DIBR_ROWS_C(D2S_FMT_U8_HWC, false); }
         else { if (fx) DIBR_ROWS_C(D2S_FMT_F32_HWC, true); else DIBR_ROWS_C(D2S_FMT_F32_HWC, false); }
 #undef DIBR_ROWS_C
 #undef DIBR_ROWS
     } else {
 #define DIBR_GEN(FMT, R0, D) hipLaunchKernelGGL((dibr_kernel<FMT, R0, D, G>), grid, block, 0, (hipStream_t)stream, rgb, depth, out, g)
 #define DIBR_GEN_D(FMT, R0) do { if (up) DIBR_GEN(FMT, R0, UpDep); else DIBR_GEN(FMT, R0, FullDep); } while (0)
-        if (out_fmt == D2S_FMT_U8_HWC) { if (roll0) DIBR_GEN_D(D2S_FMT_U8_HWC, true); else DIBR_GEN_D(D2S_FMT_U8_HWC, false); }
+        if (pl.u8) { if (roll0) DIBR_GEN_D(D2S_FMT_U8_HWC, true); else DIBR_GEN_D(D2S_FMT_U8_HWC, false); }
         else { if (roll0) DIBR_GEN_D(D2S_FMT_F32_HWC, true); else DIBR_GEN_D(D2S_FMT_F32_HWC, false); }
 #undef DIBR_GEN_D
 #undef DIBR_GEN
@@ -985,6 +1026,23 @@ extern "C" int d2s_dibr_crop_shape(int H, int W, const double crop[4], int displ
 extern "C" int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                                   const d2s_dibr_params* p, const double crop[4], void* out, int out_fmt, void* stream) {
     return dibr_warp_crop_any(rgb, depth, dh, dw, batch, H, W, p, crop, out, out_fmt, stream, false);
+}
+
+// What the three entries above would launch: dibr_warp_plan_impl, the function the launcher takes its decision from.
+extern "C" int d2s_dibr_warp_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop, int out_fmt,
+                                  d2s_dibr_warp_plan_result* res) {
+    D2S_REQUIRE(p && res, "null pointer");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_dibr_warp_plan_result), "d2s_dibr_warp_plan_result.struct_size must be sizeof(d2s_dibr_warp_plan_result)");
+    DibrWarpPlan pl;
+    DibrGeomCrop g;      // (a DibrGeom with the crop's four floats: either instantiation fills it)
+    const int rc = crop ? dibr_warp_plan_impl<DibrGeomCrop>(dh, dw, batch, H, W, p, crop, out_fmt, g, pl)
+                        : dibr_warp_plan_impl<DibrGeom>(dh, dw, batch, H, W, p, nullptr, out_fmt, g, pl);
+    if (rc) return rc;
+    *res = d2s_dibr_warp_plan_result{sizeof(d2s_dibr_warp_plan_result), pl.win.rows ? 1 : 0, pl.win.cols, pl.win.margin, pl.win.WW,
+                                     pl.roll0 ? 1 : 0, pl.up ? 1 : 0, pl.fx ? 1 : 0, g.oh, g.ow, g.out_h, g.out_w,
+                                     {pl.grid.x, pl.grid.y, pl.grid.z}, pl.block.x, pl.lds_dynamic, pl.lds_static, {}};
+    dibr_plan_name(pl, crop != nullptr, res->kernel, sizeof(res->kernel));
+    return D2S_OK;
 }
 
 // The OpenXR eye views (xr_viewer/effects.py:1023-1137; the curved screen's glow: effects.py:408-474).  xr_plan (dibr_xr.h) checks

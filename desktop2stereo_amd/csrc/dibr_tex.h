@@ -440,6 +440,16 @@ inline int crop_eye_shape(int H, int W, const double* crop, int display_mode, in
 // win_words(cols) texels of 8 float planes.  cols starts at col_cap and halves down to 256 while the window exceeds widen_words or
 // half the block would lie past the viewport; the row kernel is taken when rows_ok (roll == 0 and the launcher's own switches)
 // and the 256-column window fits rows_words, else the gather kernel.
+// A block's LDS: 8 float planes of WW words (dynamic) and the row kernel's static second-pass queue, int[2 * COLS] and its counter
+// (dibr_rows_kernel asserts that its arrays have this size).  A block's request may not exceed 64 KB, and the row kernel is taken on
+// the 256-column window: f1's rows_words is the largest WW with planes * 4 * WW + static(256) <= 65 536, which is 1 983.
+constexpr int DIBR_WIN_PLANES = 8;
+constexpr unsigned DIBR_LDS_LIMIT = 64u * 1024u;
+constexpr unsigned dibr_rows_static_lds(int cols) { return (unsigned)(sizeof(int[2]) * (size_t)cols + sizeof(int)); }
+constexpr unsigned dibr_rows_dynamic_lds(int WW) { return (unsigned)(DIBR_WIN_PLANES * sizeof(float)) * (unsigned)WW; }
+constexpr int DIBR_F1_ROWS_WORDS = (int)((DIBR_LDS_LIMIT - dibr_rows_static_lds(256)) / (DIBR_WIN_PLANES * sizeof(float)));
+static_assert(dibr_rows_dynamic_lds(DIBR_F1_ROWS_WORDS) + dibr_rows_static_lds(256) <= DIBR_LDS_LIMIT &&
+              dibr_rows_dynamic_lds(DIBR_F1_ROWS_WORDS + 1) + dibr_rows_static_lds(256) > DIBR_LDS_LIMIT, "f1's rows_words is the LDS bound");
 struct DibrWindow { int margin, cols, WW; bool rows; };
 inline DibrWindow dibr_plan_window(const DibrGeom& g, double tex_per_col, bool rows_ok, int col_cap, int widen_words, int rows_words) {
     const double tex_per_px = (double)g.W * (double)g.psx;

@@ -361,12 +361,14 @@ def _dibr_out_spec(B: int, oh: int, ow: int, dp: "_lib.DibrParams", out_u8: bool
     return (B, oh, ow, nch), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
 
 
-def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", out_u8: bool = True, crop=None) -> torch.Tensor:
+def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", out_u8: bool = True, crop=None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """f1 (reference viewer.py:386-631): uint8 HWC frames [B,H,W,3] or [H,W,3] + depth [B,dh,dw] or [dh,dw] -> both eyes
     with disocclusion in-painting, packed per dp.display_mode.  Depth of the frame's size is the shader's depth texture itself;
     any other size (the model's) is up-sampled inside the kernel, bit-identical to upsample_depth(depth, H, W) first.
     crop = (x, y, w, h) in uv, top-left origin: the OpenXR screen shader's u_source_crop (xr_viewer/implementation.py:111-126) --
-    each eye is the crop's pixel size (crop.pixel_bounds), the texture taps follow the cropped coordinate."""
+    each eye is the crop's pixel size (crop.pixel_bounds), the texture taps follow the cropped coordinate.
+    out: a caller-kept contiguous tensor of the result's batched shape [B, out_h, out_w, 3 | 4] and dtype (written in place)."""
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
@@ -387,7 +389,10 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
     else:
         check(lib.d2s_dibr_shape(H, W, dp.display_mode, C.byref(oh), C.byref(ow)), "d2s_dibr_shape")
     shape, dtype, fmt = _dibr_out_spec(B, oh.value, ow.value, dp, out_u8)
-    out = torch.empty(shape, dtype=dtype, device=f.device)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=f.device)
+    elif tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != f.device:
+        raise ValueError(f"dibr_warp: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {f.device}")
     _same_device(f, d, "dibr_warp")
     with _on(f.device) as st:
         if crop is not None:
@@ -395,6 +400,19 @@ def dibr_warp(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", 
         else:
             check(lib.d2s_dibr_warp_depth(_ptr(f), _ptr(d), dh, dw, B, H, W, C.byref(dp), _ptr(out), fmt, st), "d2s_dibr_warp_depth")
     return out if batched else out[0]
+
+
+def dibr_warp_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", out_u8: bool = True, crop=None) -> dict:
+    """What dibr_warp would launch for these arguments (include/d2s.h d2s_dibr_warp_plan; host code, no GPU): the kernel's name, whether
+    it is the LDS-window row kernel, the window plan (cols, margin, WW), grid, block and the LDS request."""
+    r = _lib.DibrWarpPlanResult()
+    r.struct_size = C.sizeof(_lib.DibrWarpPlanResult)
+    check(_lib.load().d2s_dibr_warp_plan(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp), None if crop is None else _crop4(crop),
+                                         FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(r)), "d2s_dibr_warp_plan")
+    return {"kernel": r.kernel.decode(), "rows": bool(r.rows), "cols": r.cols, "margin": r.margin, "WW": r.ww, "roll0": bool(r.roll0),
+            "up": bool(r.up), "fx": bool(r.fx), "oh": r.oh, "ow": r.ow, "out_h": r.out_h, "out_w": r.out_w, "grid": tuple(r.grid),
+            "block": r.block, "lds_dynamic": r.lds_dynamic_bytes, "lds_static": r.lds_static_bytes,
+            "lds_bytes": r.lds_dynamic_bytes + r.lds_static_bytes}
 
 
 _XR_WS: Dict[Tuple, torch.Tensor] = {}

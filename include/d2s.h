@@ -426,6 +426,24 @@ int d2s_dibr_warp_depth(const uint8_t* rgb, const float* depth, int dh, int dw, 
 int d2s_dibr_crop_shape(int H, int W, const double crop[4], int display_mode, int* out_h, int* out_w);
 int d2s_dibr_warp_crop(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                        const d2s_dibr_params* p, const double crop[4], void* out, int out_fmt, void* stream);
+/* What d2s_dibr_warp / d2s_dibr_warp_depth (crop == NULL) or d2s_dibr_warp_crop would launch for these arguments (d2s_version() >= 132;
+ * pure host code: launches nothing, needs no GPU).  It runs the launcher's own code up to the launch -- the checks, the uniforms, the
+ * eye shape, the D2S_DIBR_NO_ROLL0 / D2S_DIBR_NO_ROWS / D2S_DIBR_COLS switches and the window plan -- and refuses what the launcher
+ * refuses of these arguments.  kernel: "dibr_rows<u8|f32,fx=0|1,256|512|1024,FullDep|UpDep[,crop]>" (the LDS-window row kernel, roll == 0)
+ * or "dibr<u8|f32,roll0|general,FullDep|UpDep[,crop]>" (the gather kernel).  rows = 1: the row kernel; cols, margin, ww are the
+ * window plan's (columns per block, reach in source texels, words per plane) -- with rows = 0 the window the row kernel would have
+ * needed.  grid / block are the launch's; lds_*_bytes the row kernel's request (0 for the gather kernel), never above 65 536. */
+typedef struct d2s_dibr_warp_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_dibr_warp_plan_result) */
+    int32_t rows, cols, margin, ww;
+    int32_t roll0, up, fx;     /* the row pair formed once per pixel or block; depth up-sampled in the kernel; feather / corner code */
+    int32_t oh, ow, out_h, out_w;
+    uint32_t grid[3], block;
+    uint32_t lds_dynamic_bytes, lds_static_bytes;
+    char kernel[64];
+} d2s_dibr_warp_plan_result;
+int d2s_dibr_warp_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, const double* crop /* NULL = uncropped */,
+                       int out_fmt, d2s_dibr_warp_plan_result* res);
 
 /* The OpenXR viewer's eye views (d2s_version() >= 115): the screen of d2s_xr_screen drawn into each eye's swapchain image with that
  * eye's own view-projection matrix, as EffectsMixin._render_eye does (xr_viewer/effects.py:1023-1137: depth test LESS against a

@@ -32,6 +32,7 @@ def test_header_symbols_exported(lib):
     assert lib.d2s_version() >= 110          # 110: d2s_dibr_params.struct_size
     assert lib.d2s_version() >= 118 and {"d2s_warp_plan", "d2s_preprocess_patches_probe"} <= declared
     assert lib.d2s_version() >= 128 and "d2s_vit_probe" in declared
+    assert lib.d2s_version() >= 132 and "d2s_dibr_warp_plan" in declared
 
 
 def test_struct_layout_matches_header():
@@ -55,6 +56,9 @@ def test_struct_layout_matches_header():
     Wp = _lib.WarpPlanResult                                                                 # d2s_warp_plan_result
     assert (C.sizeof(Wp) == 112 and Wp.gather.offset == 4 and Wp.rpw.offset == 24 and Wp.out_h.offset == 28 and Wp.grid.offset == 36
             and Wp.waves.offset == 40 and Wp.kernel.offset == 48)
+    Dp = _lib.DibrWarpPlanResult                                                             # d2s_dibr_warp_plan_result
+    assert (C.sizeof(Dp) == 136 and Dp.rows.offset == 4 and Dp.ww.offset == 16 and Dp.oh.offset == 32 and Dp.grid.offset == 48
+            and Dp.block.offset == 60 and Dp.lds_dynamic_bytes.offset == 64 and Dp.kernel.offset == 72)
     Q = _lib.PrepatchProbeParams                                                             # d2s_prepatch_probe_params
     assert (C.sizeof(Q) == 208 and Q.precision.offset == 4 and Q.decim_stride.offset == 24 and Q.D.offset == 48 and Q.pre.offset == 56
             and Q.frames.offset == 64 and Q.resid.offset == 96 and Q.frames_elems.offset == 104 and Q.kernel.offset == 144)

@@ -163,6 +163,7 @@ def test_dibr_row_kernels_are_bit_identical_to_the_gather_kernel(dev, monkeypatc
     non-default u_resolution, rgba, a strong parallax, and a depth map beyond 0..1 (shifts past the window margin: the fallback)."""
     from desktop2stereo_amd import ops, synth
     keys = ("D2S_DIBR_NO_ROLL0", "D2S_DIBR_NO_ROWS", "D2S_DIBR_COLS")
+    seen = set()
     try:
         for (H, W, seed, dscale, kw) in [(270, 480, 3, 1.0, {}), (180, 322, 4, 1.0, dict(convergence=0.03, feather=True, corner_radius=0.03)),
                                          (1080, 1920, 5, 1.0, dict(depth_ratio=3.0)), (200, 300, 6, 1.0, dict(resolution=(640.0, 360.0), alpha="rgba")),
@@ -179,6 +180,19 @@ def test_dibr_row_kernels_are_bit_identical_to_the_gather_kernel(dev, monkeypatc
                     for k, v in env.items():
                         monkeypatch.setenv(k, v)
                     ops.reload_env()
+                    # the kernel each switch setting selects, from the launcher's own plan: without it "rows equals general" could
+                    # compare the gather kernel with itself (every shape here, the 120 x 700 strong-parallax one included, has a
+                    # 256-column window within rows_words and takes the row kernel under the three "rows" settings)
+                    pl = ops.dibr_warp_plan(H, W, 1, H, W, dp, out_u8=False)
+                    fxs = int(bool(kw.get("feather")) or kw.get("corner_radius", 0.0) > 0)
+                    if name.startswith("rows"):
+                        cap = {"rows": 512, "rows_256": 256, "rows_1024": 1024}[name]
+                        assert pl["rows"] and pl["cols"] <= cap and pl["kernel"] == f"dibr_rows<f32,fx={fxs},{pl['cols']},FullDep>", (H, W, mode, name, pl)
+                        assert pl["lds_bytes"] <= 65536, pl
+                        seen.add(pl["cols"])
+                    else:
+                        want = "dibr<f32,roll0,FullDep>" if name == "row_gather" else "dibr<f32,general,FullDep>"
+                        assert not pl["rows"] and pl["kernel"] == want, (H, W, mode, name, pl)
                     outs[name] = ops.dibr_warp(f, d, dp, out_u8=False).cpu().numpy()
                 for name in ("rows", "rows_256", "rows_1024", "row_gather"):
                     assert np.array_equal(outs[name], outs["general"]), (H, W, mode, kw, name, float(np.abs(outs[name] - outs["general"]).max()))
@@ -187,6 +201,7 @@ def test_dibr_row_kernels_are_bit_identical_to_the_gather_kernel(dev, monkeypatc
                     monkeypatch.delenv(k, raising=False)
                 ops.reload_env()
                 assert np.array_equal(ops.dibr_warp(f, d, dp).cpu().numpy(), u8), (H, W, mode, "uint8")
+        assert seen == {256, 512, 1024}, seen          # all three widths of the row kernel ran
     finally:
         for k in keys:
             monkeypatch.delenv(k, raising=False)
