@@ -8,7 +8,7 @@ torch ops, and nothing falls back to the CPU.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -416,17 +416,32 @@ def dibr_warp_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrP
 
 
 _XR_WS: Dict[Tuple, torch.Tensor] = {}
-# Engine._view_pipeline_xr's entry: (C name, the Python method's name for messages, the workspace size query)
-_XR_PIPELINES = {"eyes": ("d2s_view_pipeline_xr_streams", "view_pipeline_xr", "d2s_dibr_xr_workspace"),
-                 "glow": ("d2s_view_pipeline_xr_glow_streams", "view_pipeline_xr_glow", "d2s_dibr_xr_workspace"),
-                 "glow_curved": ("d2s_view_pipeline_xr_glow_curved_streams", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_glow_curved_workspace"),
-                 "frost": ("d2s_view_pipeline_xr_frost_streams", "view_pipeline_xr_frost", "d2s_dibr_xr_frost_workspace"),
-                 "frost_curved": ("d2s_view_pipeline_xr_frost_curved_streams", "view_pipeline_xr_frost_curved",
-                                  "d2s_dibr_xr_frost_curved_workspace"),
-                 # (the panorama entry draws whichever kind the looks ask for: the largest table's workspace serves them all)
-                 "panorama": ("d2s_view_pipeline_xr_panorama_streams", "view_pipeline_xr_panorama", "d2s_dibr_xr_frost_curved_workspace"),
-                 "panorama_curved": ("d2s_view_pipeline_xr_panorama_curved_streams", "view_pipeline_xr_panorama_curved",
-                                     "d2s_dibr_xr_frost_curved_workspace")}
+
+
+class _XrEntry(NamedTuple):
+    """One eye-view entry.  direct / pipeline: the function here and the Engine method, as messages name them -- the C entries are
+    d2s_<direct> and d2s_<pipeline>_streams.  tail: what the C argument list has between workspace_bytes and the stream -- "" nothing,
+    "glow" (glow, levels), "frost" (frost, levels), "panorama" (frost, levels, glow, panorama, pano_rgb, pano_levels)."""
+    direct: str
+    pipeline: str
+    plan: str
+    workspace: str
+    tail: str
+
+
+# (the two panorama entries draw whichever kind the looks ask for: the largest table's workspace serves them all)
+_XR_ENTRIES = {
+    "eyes": _XrEntry("dibr_xr_eyes", "view_pipeline_xr", "d2s_dibr_xr_plan", "d2s_dibr_xr_workspace", ""),
+    "glow": _XrEntry("dibr_xr_eyes_glow", "view_pipeline_xr_glow", "d2s_dibr_xr_plan", "d2s_dibr_xr_workspace", "glow"),
+    "glow_curved": _XrEntry("dibr_xr_eyes_glow_curved", "view_pipeline_xr_glow_curved", "d2s_dibr_xr_plan",
+                            "d2s_dibr_xr_glow_curved_workspace", "glow"),
+    "frost": _XrEntry("dibr_xr_eyes_frost", "view_pipeline_xr_frost", "d2s_dibr_xr_frost_plan", "d2s_dibr_xr_frost_workspace", "frost"),
+    "frost_curved": _XrEntry("dibr_xr_eyes_frost_curved", "view_pipeline_xr_frost_curved", "d2s_dibr_xr_frost_curved_plan",
+                             "d2s_dibr_xr_frost_curved_workspace", "frost"),
+    "panorama": _XrEntry("dibr_xr_eyes_panorama", "view_pipeline_xr_panorama", "d2s_dibr_xr_panorama_plan",
+                         "d2s_dibr_xr_frost_curved_workspace", "panorama"),
+    "panorama_curved": _XrEntry("dibr_xr_eyes_panorama_curved", "view_pipeline_xr_panorama_curved", "d2s_dibr_xr_panorama_curved_plan",
+                                "d2s_dibr_xr_frost_curved_workspace", "panorama")}
 
 
 def _xr_args(screen, eyes):
@@ -473,7 +488,7 @@ def dibr_xr_eyes(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams
     None; dp as dibr_warp(crop=) reads it except display_mode, viewport and roll (screen.roll is u_roll); feathering is refused.
     Returns one tensor per eye, [B,h,w,3|4] uint8 / float32 0..255 (views of one flat buffer: `out`, a caller-kept 1-D tensor of
     dibr_xr_shape's total, or a new one).  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_workspace bytes."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes", "d2s_dibr_xr_workspace", "dibr_xr_eyes", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace)
+    return _dibr_xr_call("eyes", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace)
 
 
 def mip_shape(H: int, W: int) -> Tuple[list, int]:
@@ -504,19 +519,66 @@ def mip_chain(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
     return out
 
 
-def _xr_glow_args(glow, levels, B: int, H: int, W: int, device, who: str):
-    """(d2s_xr_glow or None, the chain's pointer or None) of an xr.XrGlow (or the struct, or None = off) and mip_chain's result.
-    An xr.XrFrost (d2s_xr_frost) travels the same way."""
-    if glow is None:
-        return None, None
-    gs = glow if isinstance(glow, (_lib.XrGlow, _lib.XrFrost)) else glow.c_struct()
-    if levels is None:
-        return gs, None                                   # (the library refuses a missing chain with glow on)
-    _need_cuda(levels, "levels")
-    _, total = mip_shape(H, W)
-    if levels.dtype != torch.uint8 or levels.device != device or tuple(levels.shape) != (B, total) or not levels.is_contiguous():
-        raise ValueError(f"{who}: levels must be mip_chain's result for these frames, a contiguous uint8 tensor of {(B, total)} on {device}")
-    return gs, levels
+def _xr_struct(look):
+    """d2s_xr_glow / d2s_xr_frost of an xr.XrGlow / xr.XrFrost (or the struct itself; None = off)."""
+    return look if look is None or isinstance(look, (_lib.XrGlow, _lib.XrFrost)) else look.c_struct()
+
+
+def _xr_tail(tail: str, who: str, B: int, H: int, W: int, device, glow=None, frost=None, levels=None, panorama=None, pano_rgb=None,
+             pano_levels=None):
+    """(the C arguments an entry of that tail (_XrEntry) has between workspace_bytes and the stream, what the caller keeps alive over
+    the call).  glow = xr.XrGlow, frost = xr.XrFrost (or their structs; None = off); levels = mip_chain's result for these frames,
+    which serves whichever look is given and is not looked at without one; panorama = a _lib.XrPanorama (xr.XrPanorama.c_struct; None =
+    no panorama) with pano_rgb uint8 [h, w, 3] and pano_levels = mip_chain(pano_rgb).  The tensor checks of all of them, in that order."""
+    fs, gs = _xr_struct(frost), _xr_struct(glow)
+    lv = pr = pl = None
+    if (fs is not None or gs is not None) and levels is not None:      # (the library refuses a missing chain with a look on)
+        _need_cuda(levels, "levels")
+        _, total = mip_shape(H, W)
+        if levels.dtype != torch.uint8 or levels.device != device or tuple(levels.shape) != (B, total) or not levels.is_contiguous():
+            raise ValueError(f"{who}: levels must be mip_chain's result for these frames, a contiguous uint8 tensor of {(B, total)} on {device}")
+        lv = levels
+    if panorama is not None and not isinstance(panorama, _lib.XrPanorama):
+        raise ValueError(f"{who}: panorama must be xr.XrPanorama.c_struct(...)'s result (it carries the eyes' ray matrices) or None")
+    if panorama is not None and pano_rgb is not None and pano_levels is not None:      # (the library refuses a missing image or chain)
+        _need_cuda(pano_rgb, "pano_rgb")
+        _need_cuda(pano_levels, "pano_levels")
+        h, w = panorama.height, panorama.width
+        if pano_rgb.dtype != torch.uint8 or tuple(pano_rgb.shape) != (h, w, 3) or pano_rgb.device != device or not pano_rgb.is_contiguous():
+            raise ValueError(f"{who}: pano_rgb must be a contiguous uint8 tensor of {(h, w, 3)} on {device}")
+        total = mip_shape(h, w)[1] if 2 <= h <= 8192 and 2 <= w <= 8192 else -1      # (the library refuses the size itself)
+        if pano_levels.dtype != torch.uint8 or pano_levels.device != device or not pano_levels.is_contiguous() or \
+                (total >= 0 and pano_levels.numel() != total):
+            raise ValueError(f"{who}: pano_levels must be mip_chain(pano_rgb), a contiguous uint8 tensor of {total} bytes on {device}")
+        pr, pl = pano_rgb, pano_levels
+
+    def ref(s):
+        return C.byref(s) if s is not None else None
+
+    def ptr(t):
+        return _ptr(t) if t is not None else None
+    args = {"": (), "glow": (ref(gs), ptr(lv)), "frost": (ref(fs), ptr(lv)),
+            "panorama": (ref(fs), ptr(lv), ref(gs), ref(panorama), ptr(pr), ptr(pl))}[tail]
+    return args, (fs, gs, lv, panorama, pr, pl)
+
+
+def _xr_plan_query(entry: str, dh: int, dw: int, batch: int, H: int, W: int, dp, screen, eyes, crop, out_u8: bool, looks, lead=()) -> dict:
+    """The entry's plan door (host code, no GPU) and its answer as a dictionary.  looks: the structs the door takes after out_fmt
+    (None = NULL); lead: what it takes in front."""
+    sc, ea = _xr_args(screen, eyes)
+    row = _XR_ENTRIES[entry]
+    r = _lib.XrPlanResult()
+    r.struct_size = C.sizeof(_lib.XrPlanResult)
+    check(getattr(_lib.load(), row.plan)(*lead, int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
+                                         _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
+                                         FMT_U8_HWC if out_u8 else FMT_F32_HWC, *(C.byref(s) if s is not None else None for s in looks),
+                                         C.byref(r)), row.plan)
+    plan = {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
+            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
+            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
+    if row.tail == "panorama":
+        plan["panorama"] = bool(r.reserved)
+    return plan
 
 
 def dibr_xr_eyes_glow(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
@@ -524,8 +586,7 @@ def dibr_xr_eyes_glow(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrP
     """dibr_xr_eyes with the reference's glow around the flat screen in the same launch (d2s_dibr_xr_eyes_glow; reference
     _render_glow, xr_viewer/effects.py:476-585): glow = xr.XrGlow (None or mode "off": exactly dibr_xr_eyes), levels = mip_chain(frames)
     -- or an older chain: the reference refreshes its mipmaps every few frames only.  Everything else as dibr_xr_eyes."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes_glow", "d2s_dibr_xr_workspace", "dibr_xr_eyes_glow", frames, depth, dp, screen, eyes, crop, out_u8,
-                         out, workspace, (glow, levels))
+    return _dibr_xr_call("glow", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow=glow, levels=levels)
 
 
 def dibr_xr_eyes_glow_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
@@ -534,8 +595,7 @@ def dibr_xr_eyes_glow_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_li
     xr_viewer/effects.py:408-474): screen.curve "horizontal" | "vertical" with glow mode "glow" | "glow2".  A flat screen or no glow is
     exactly dibr_xr_eyes_glow.  An eye outside the convex region the screen bounds (xr.XrScreen.eye_inside) is refused.  workspace: a
     caller-kept uint8 device tensor of d2s_dibr_xr_glow_curved_workspace bytes."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes_glow_curved", "d2s_dibr_xr_glow_curved_workspace", "dibr_xr_eyes_glow_curved", frames, depth, dp,
-                         screen, eyes, crop, out_u8, out, workspace, (glow, levels))
+    return _dibr_xr_call("glow_curved", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow=glow, levels=levels)
 
 
 def dibr_xr_eyes_frost(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, frost, levels=None, crop=None,
@@ -545,8 +605,7 @@ def dibr_xr_eyes_frost(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.Dibr
     <= 0 or a veil of alpha <= 0.002: exactly dibr_xr_eyes).  levels = mip_chain(frames) for "frosted"; the veil reads the frame alone.
     A curved screen with frost on is refused here: dibr_xr_eyes_frost_curved draws it.  workspace: a caller-kept uint8 device tensor of
     d2s_dibr_xr_frost_workspace bytes."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes_frost", "d2s_dibr_xr_frost_workspace", "dibr_xr_eyes_frost", frames, depth, dp, screen, eyes, crop,
-                         out_u8, out, workspace, (frost, levels))
+    return _dibr_xr_call("frost", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, frost=frost, levels=levels)
 
 
 def dibr_xr_eyes_frost_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, frost, levels=None, crop=None,
@@ -555,51 +614,20 @@ def dibr_xr_eyes_frost_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_l
     _render_curved_frost_with_uniforms, xr_viewer/effects.py:759-787): the 196 triangles of xr.XrFrost.curved_wall_verts blended after
     the curved strip in draw order; the eyes may be anywhere.  A flat screen is exactly dibr_xr_eyes_frost, a look that does not draw
     exactly dibr_xr_eyes.  workspace: a caller-kept uint8 device tensor of d2s_dibr_xr_frost_curved_workspace bytes."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes_frost_curved", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_frost_curved", frames, depth, dp,
-                         screen, eyes, crop, out_u8, out, workspace, (frost, levels))
+    return _dibr_xr_call("frost_curved", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, frost=frost, levels=levels)
 
 
 def dibr_xr_frost_curved_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, frost, crop=None,
                               out_u8: bool = True) -> dict:
     """dibr_xr_frost_plan for dibr_xr_eyes_frost_curved (d2s_dibr_xr_frost_curved_plan; host code, no GPU): kind "plain", "frost" or
     "frost_curved" (244 rows per eye, blocks of 64 x 64 pixels), and the same fields."""
-    return dibr_xr_frost_plan(dh, dw, batch, H, W, dp, screen, eyes, frost, crop, out_u8, _query="d2s_dibr_xr_frost_curved_plan")
+    return _xr_plan_query("frost_curved", dh, dw, batch, H, W, dp, screen, eyes, crop, out_u8, (_xr_struct(frost),))
 
 
 def dibr_xr_frost_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, frost, crop=None,
-                       out_u8: bool = True, _query: str = "d2s_dibr_xr_frost_plan") -> dict:
+                       out_u8: bool = True) -> dict:
     """dibr_xr_plan for dibr_xr_eyes_frost (d2s_dibr_xr_frost_plan; host code, no GPU): kind "plain" or "frost", and the same fields."""
-    sc, ea = _xr_args(screen, eyes)
-    fs = None if frost is None else frost if isinstance(frost, _lib.XrFrost) else frost.c_struct()
-    r = _lib.XrPlanResult()
-    r.struct_size = C.sizeof(_lib.XrPlanResult)
-    check(getattr(_lib.load(), _query)(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
-                                       _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
-                                       FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None, C.byref(r)), _query)
-    return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
-            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
-            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
-
-
-def _xr_pano_args(panorama, pano_rgb, pano_levels, device, who: str):
-    """(d2s_xr_panorama or None, the image, its chain) of a _lib.XrPanorama (xr.XrPanorama.c_struct; None = no panorama), the
-    panorama uint8 [h, w, 3] and mip_chain(pano_rgb).  The tensors are returned so that the caller keeps them alive over the call."""
-    if panorama is None:
-        return None, None, None
-    if not isinstance(panorama, _lib.XrPanorama):
-        raise ValueError(f"{who}: panorama must be xr.XrPanorama.c_struct(...)'s result (it carries the eyes' ray matrices) or None")
-    if pano_rgb is None or pano_levels is None:
-        return panorama, None, None                       # (the library refuses a missing image or chain with a panorama set)
-    _need_cuda(pano_rgb, "pano_rgb")
-    _need_cuda(pano_levels, "pano_levels")
-    h, w = panorama.height, panorama.width
-    if pano_rgb.dtype != torch.uint8 or tuple(pano_rgb.shape) != (h, w, 3) or pano_rgb.device != device or not pano_rgb.is_contiguous():
-        raise ValueError(f"{who}: pano_rgb must be a contiguous uint8 tensor of {(h, w, 3)} on {device}")
-    total = mip_shape(h, w)[1] if 2 <= h <= 8192 and 2 <= w <= 8192 else -1      # (the library refuses the size itself)
-    if pano_levels.dtype != torch.uint8 or pano_levels.device != device or not pano_levels.is_contiguous() or \
-            (total >= 0 and pano_levels.numel() != total):
-        raise ValueError(f"{who}: pano_levels must be mip_chain(pano_rgb), a contiguous uint8 tensor of {total} bytes on {device}")
-    return panorama, pano_rgb, pano_levels
+    return _xr_plan_query("frost", dh, dw, batch, H, W, dp, screen, eyes, crop, out_u8, (_xr_struct(frost),))
 
 
 def dibr_xr_eyes_panorama(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, panorama, pano_rgb, pano_levels,
@@ -613,8 +641,8 @@ def dibr_xr_eyes_panorama(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.D
     xr.XrFrost (at most one on) with levels = mip_chain(frames) as their own calls take it.  A curved screen with a look on and a
     panorama is refused here: dibr_xr_eyes_panorama_curved draws it.  panorama None: exactly the call of that look.  workspace: a caller-kept uint8 device tensor of
     d2s_dibr_xr_frost_curved_workspace bytes (the largest table serves every kind)."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes_panorama", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_panorama", frames, depth, dp,
-                         screen, eyes, crop, out_u8, out, workspace, (frost, levels), pano=(glow, panorama, pano_rgb, pano_levels))
+    return _dibr_xr_call("panorama", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow=glow, frost=frost, levels=levels,
+                         panorama=panorama, pano_rgb=pano_rgb, pano_levels=pano_levels)
 
 
 def dibr_xr_eyes_panorama_curved(frames: torch.Tensor, depth: torch.Tensor, dp: "_lib.DibrParams", screen, eyes, panorama, pano_rgb,
@@ -624,41 +652,30 @@ def dibr_xr_eyes_panorama_curved(frames: torch.Tensor, depth: torch.Tensor, dp: 
     (d2s_dibr_xr_eyes_panorama_curved): the same arguments.  A flat screen, or a curved one without a look: exactly
     dibr_xr_eyes_panorama's launch; panorama None: exactly dibr_xr_eyes_glow_curved's / dibr_xr_eyes_frost_curved's.  An eye outside
     the convex region of the curved glow (xr.XrScreen.eye_inside) stays refused."""
-    return _dibr_xr_call("d2s_dibr_xr_eyes_panorama_curved", "d2s_dibr_xr_frost_curved_workspace", "dibr_xr_eyes_panorama_curved", frames,
-                         depth, dp, screen, eyes, crop, out_u8, out, workspace, (frost, levels), pano=(glow, panorama, pano_rgb, pano_levels))
+    return _dibr_xr_call("panorama_curved", frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow=glow, frost=frost,
+                         levels=levels, panorama=panorama, pano_rgb=pano_rgb, pano_levels=pano_levels)
 
 
 def dibr_xr_panorama_curved_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, panorama, glow=None,
                                  frost=None, crop=None, out_u8: bool = True) -> dict:
     """dibr_xr_panorama_plan for dibr_xr_eyes_panorama_curved (d2s_dibr_xr_panorama_curved_plan; host code, no GPU): kind "glow_curved"
     or "frost_curved" where those draw, with "panorama" true when the background is drawn behind them."""
-    return dibr_xr_panorama_plan(dh, dw, batch, H, W, dp, screen, eyes, panorama, glow=glow, frost=frost, crop=crop, out_u8=out_u8,
-                                 _symbol="d2s_dibr_xr_panorama_curved_plan")
+    return _xr_plan_query("panorama_curved", dh, dw, batch, H, W, dp, screen, eyes, crop, out_u8,
+                          (_xr_struct(frost), _xr_struct(glow), panorama))
 
 
 def dibr_xr_panorama_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", screen, eyes, panorama, glow=None, frost=None,
-                          crop=None, out_u8: bool = True, _symbol: str = "d2s_dibr_xr_panorama_plan") -> dict:
+                          crop=None, out_u8: bool = True) -> dict:
     """dibr_xr_plan for dibr_xr_eyes_panorama (d2s_dibr_xr_panorama_plan; host code, no GPU): the kind the looks ask for, the same
     fields, and "panorama": whether the background is drawn."""
-    sc, ea = _xr_args(screen, eyes)
-    fs = None if frost is None else frost if isinstance(frost, _lib.XrFrost) else frost.c_struct()
-    gs = None if glow is None else glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
-    r = _lib.XrPlanResult()
-    r.struct_size = C.sizeof(_lib.XrPlanResult)
-    check(getattr(_lib.load(), _symbol)(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
-                                        _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
-                                        FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(fs) if fs is not None else None,
-                                        C.byref(gs) if gs is not None else None,
-                                        C.byref(panorama) if panorama is not None else None, C.byref(r)), _symbol)
-    return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
-            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
-            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)]), "panorama": bool(r.reserved)}
+    return _xr_plan_query("panorama", dh, dw, batch, H, W, dp, screen, eyes, crop, out_u8, (_xr_struct(frost), _xr_struct(glow), panorama))
 
 
-def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, glow_levels=None, pano=None) -> list:
-    """The tensor checks and the call of the eye-view entries.  glow_levels: None for d2s_dibr_xr_eyes, whose argument list has
-    no glow; (glow, levels) for those that take them.  pano: d2s_dibr_xr_eyes_panorama's further arguments (glow, panorama, pano_rgb,
-    pano_levels) -- glow_levels is then its (frost, levels)."""
+def _dibr_xr_call(entry, frames, depth, dp, screen, eyes, crop, out_u8, out, workspace, **looks) -> list:
+    """The tensor checks and the call of the eye-view entry `entry` (_XR_ENTRIES).  looks: what its tail takes of glow, frost, levels,
+    panorama, pano_rgb, pano_levels (_xr_tail)."""
+    row = _XR_ENTRIES[entry]
+    who, symbol = row.direct, "d2s_" + row.direct
     _need_cuda(frames, "frames")
     _need_cuda(depth, "depth")
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
@@ -671,22 +688,9 @@ def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, o
         raise ValueError(f"{who}: depth must be [{B},dh,dw] for frames {tuple(f.shape)}, got {tuple(d.shape)}")
     _same_device(f, d, who)
     sc, ea = _xr_args(screen, eyes)
-    glow_args = ()
-    if glow_levels is not None:
-        glow, levels = glow_levels
-        if levels is not None and levels.dim() == 1:
-            levels = levels.unsqueeze(0)
-        gs, lv = _xr_glow_args(glow, levels, B, H, W, f.device, who)
-        glow_args = (C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None)
-    if pano is not None:
-        glow2, panorama, pano_rgb, pano_levels = pano
-        g2 = None if glow2 is None else glow2 if isinstance(glow2, _lib.XrGlow) else glow2.c_struct()
-        if glow_args[1] is None and g2 is not None and levels is not None:      # the chain serves the glow when no frost was given
-            _, lv = _xr_glow_args(g2, levels, B, H, W, f.device, who)
-            glow_args = (glow_args[0], _ptr(lv))
-        ps, pr, pl_ = _xr_pano_args(panorama, pano_rgb, pano_levels, f.device, who)
-        glow_args += (C.byref(g2) if g2 is not None else None, C.byref(ps) if ps is not None else None,
-                      _ptr(pr) if pr is not None else None, _ptr(pl_) if pl_ is not None else None)
+    if looks.get("levels") is not None and looks["levels"].dim() == 1:
+        looks["levels"] = looks["levels"].unsqueeze(0)
+    tail, _keep = _xr_tail(row.tail, who, B, H, W, f.device, **looks)      # (_keep: alive until the call has returned)
     offs, total = dibr_xr_shape(ea, B, dp.alpha_mode)
     nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
     dtype, fmt = (torch.uint8, FMT_U8_HWC) if out_u8 else (torch.float32, FMT_F32_HWC)
@@ -694,13 +698,13 @@ def _dibr_xr_call(entry, ws_query, who, frames, depth, dp, screen, eyes, crop, o
         out = torch.empty(total, dtype=dtype, device=f.device)
     elif not out.is_cuda or out.device != f.device or out.dtype != dtype or out.numel() != total or not out.is_contiguous():
         raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of {total} elements on {f.device}")
-    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device, ws_query)
+    ws = workspace if workspace is not None else _xr_workspace(len(ea), f.device, row.workspace)
     _need_cuda(ws, "workspace")
     _same_device(f, ws, f"{who} workspace")
     c4 = _crop4(crop) if crop is not None else None
     with _on(f.device) as st:
-        check(getattr(_lib.load(), entry)(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
-                                          _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(), *glow_args, st), entry)
+        check(getattr(_lib.load(), symbol)(_ptr(f), _ptr(d), d.shape[1], d.shape[2], B, H, W, C.byref(dp), c4, C.byref(sc), ea, len(ea),
+                                           _ptr(out), fmt, _ptr(ws), ws.numel() * ws.element_size(), *tail, st), symbol)
     return _xr_views(out.view(-1), ea, B, nch, offs)
 
 
@@ -709,17 +713,7 @@ def dibr_xr_plan(entry: str, dh: int, dw: int, batch: int, H: int, W: int, dp: "
     """What the eye-view call `entry` ("eyes" | "glow" | "glow_curved") decides for these arguments before it looks at a device pointer
     (include/d2s.h d2s_dibr_xr_plan; host code, no GPU): the kind of kernel, the table rows per eye and the launches that write them, the
     render launch's grid and LDS bytes, the workspace bytes and the out layout.  Raises D2SError with the entry's own refusal."""
-    sc, ea = _xr_args(screen, eyes)
-    gs = None if glow is None else glow if isinstance(glow, _lib.XrGlow) else glow.c_struct()
-    r = _lib.XrPlanResult()
-    r.struct_size = C.sizeof(_lib.XrPlanResult)
-    check(_lib.load().d2s_dibr_xr_plan(_lib.XR_ENTRY[entry], int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp),
-                                       _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea),
-                                       FMT_U8_HWC if out_u8 else FMT_F32_HWC, C.byref(gs) if gs is not None else None, C.byref(r)),
-          "d2s_dibr_xr_plan")
-    return {"kind": _lib.XR_KIND[r.kind], "rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "grid": tuple(r.grid),
-            "lds_dynamic_bytes": r.lds_dynamic_bytes, "lds_static_bytes": r.lds_static_bytes, "workspace_bytes": r.workspace_bytes,
-            "out_elems": r.out_elems, "offsets": list(r.offsets[:len(ea)])}
+    return _xr_plan_query(entry, dh, dw, batch, H, W, dp, screen, eyes, crop, out_u8, (_xr_struct(glow),), lead=(_lib.XR_ENTRY[entry],))
 
 
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
@@ -1020,38 +1014,26 @@ class Engine:
         ops.dibr_xr_eyes.  Returns one tensor per eye (with want_depth: (list, depth)); bit-identical to pipeline(want_depth=True)'s
         engine depth followed by dibr_xr_eyes.  out: a caller-kept 1-D tensor of dibr_xr_shape's total.  (A method of its own, as
         view_pipeline_crop is: view_pipeline's parameter list is pinned by the ABI tests.)"""
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, None, None, "eyes")
+        return self._view_pipeline_xr("eyes", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams)
 
-    def _view_pipeline_xr(self, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, entry, pano=None):
+    def _view_pipeline_xr(self, entry, frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, **looks):
+        """The view pipeline of the eye-view entry `entry` (_XR_ENTRIES); looks as _dibr_xr_call takes them."""
         sc, ea = _xr_args(screen, eyes)
         nch = 4 if dp.alpha_mode == _lib.DIBR_ALPHA["rgba"] else 3
-        name, who, ws_query = _XR_PIPELINES[entry]
+        row = _XR_ENTRIES[entry]
+        name, who = "d2s_" + row.pipeline + "_streams", row.pipeline
         lay = {}
 
         def spec(B, H, W):
             lay["offs"], lay["total"] = dibr_xr_shape(ea, B, dp.alpha_mode)
             lay["B"] = B
-            if glow is not None:
-                lay["glow"] = _xr_glow_args(glow, levels, B, H, W, self.device, who)
-            if pano is not None:                          # (glow: the panorama entry's frost; its own glow travels in pano)
-                g2 = None if pano[0] is None else pano[0] if isinstance(pano[0], _lib.XrGlow) else pano[0].c_struct()
-                lv = lay.get("glow", (None, None))[1]
-                if lv is None and g2 is not None and levels is not None:
-                    lv = _xr_glow_args(g2, levels, B, H, W, self.device, who)[1]
-                lay["glow"] = (lay.get("glow", (None, None))[0], lv)
-                lay["pano"] = (g2,) + _xr_pano_args(pano[1], pano[2], pano[3], self.device, who)
+            lay["tail"], lay["keep"] = _xr_tail(row.tail, who, B, H, W, self.device, **looks)
             return (lay["total"],), torch.uint8 if out_u8 else torch.float32, FMT_U8_HWC if out_u8 else FMT_F32_HWC
-        ws = _xr_workspace(len(ea), self.device, ws_query)
+        ws = _xr_workspace(len(ea), self.device, row.workspace)
         nbytes = ws.numel()
 
         def fn(*a):      # (_run_pipeline ends every call with out, out_fmt, depth_full, stream: the workspace goes in front of the stream)
-            gs, lv = lay.get("glow", (None, None))
-            glow_args = () if glow is None and pano is None else (C.byref(gs) if gs is not None else None, _ptr(lv) if lv is not None else None)
-            if pano is not None:
-                g2, ps, pr, pl_ = lay["pano"]
-                glow_args += (C.byref(g2) if g2 is not None else None, C.byref(ps) if ps is not None else None,
-                              _ptr(pr) if pr is not None else None, _ptr(pl_) if pl_ is not None else None)
-            return getattr(self.lib, name)(*a[:-1], _ptr(ws), nbytes, *glow_args, a[-1])
+            return getattr(self.lib, name)(*a[:-1], _ptr(ws), nbytes, *lay["tail"], a[-1])
         mid = (C.byref(dp), _crop4(crop) if crop is not None else None, C.byref(sc), ea, len(ea), int(use_ema))
         r = self._run_pipeline(fn, name, frames, p, spec, mid, want_depth, out, streams, who=who)
         flat = (r[0] if want_depth else r).view(-1)
@@ -1064,8 +1046,8 @@ class Engine:
         """view_pipeline_xr with the panorama background behind the screen (d2s_view_pipeline_xr_panorama_streams): panorama,
         pano_rgb, pano_levels, glow, frost and levels as dibr_xr_eyes_panorama takes them.  Bit-identical to
         pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_panorama."""
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels, "panorama",
-                                      pano=(glow, panorama, pano_rgb, pano_levels))
+        return self._view_pipeline_xr("panorama", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow=glow,
+                                      frost=frost, levels=levels, panorama=panorama, pano_rgb=pano_rgb, pano_levels=pano_levels)
 
     def view_pipeline_xr_panorama_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, panorama,
                                          pano_rgb, pano_levels, glow=None, frost=None, levels=None, crop=None, use_ema: bool = False,
@@ -1073,8 +1055,8 @@ class Engine:
         """view_pipeline_xr_panorama with the panorama also behind the curved screen's looks
         (d2s_view_pipeline_xr_panorama_curved_streams).  Bit-identical to pipeline(want_depth=True)'s engine depth followed by
         dibr_xr_eyes_panorama_curved."""
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels,
-                                      "panorama_curved", pano=(glow, panorama, pano_rgb, pano_levels))
+        return self._view_pipeline_xr("panorama_curved", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams,
+                                      glow=glow, frost=frost, levels=levels, panorama=panorama, pano_rgb=pano_rgb, pano_levels=pano_levels)
 
     def view_pipeline_xr_glow(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels, crop=None,
                               use_ema: bool = False, out_u8: bool = True, want_depth: bool = False, out: Optional[torch.Tensor] = None,
@@ -1084,7 +1066,7 @@ class Engine:
         engine depth followed by dibr_xr_eyes_glow."""
         if glow is None:
             raise ValueError("view_pipeline_xr_glow: glow must be an xr.XrGlow (mode \"off\" for none)")
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, "glow")
+        return self._view_pipeline_xr("glow", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow=glow, levels=levels)
 
     def view_pipeline_xr_glow_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, glow, levels,
                                      crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
@@ -1094,7 +1076,8 @@ class Engine:
         dibr_xr_eyes_glow_curved."""
         if glow is None:
             raise ValueError("view_pipeline_xr_glow_curved: glow must be an xr.XrGlow (mode \"off\" for none)")
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow, levels, "glow_curved")
+        return self._view_pipeline_xr("glow_curved", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, glow=glow,
+                                      levels=levels)
 
     def view_pipeline_xr_frost(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, frost, levels=None,
                                crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
@@ -1104,7 +1087,7 @@ class Engine:
         pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_frost."""
         if frost is None:
             raise ValueError("view_pipeline_xr_frost: frost must be an xr.XrFrost (mode \"off\" for none)")
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels, "frost")
+        return self._view_pipeline_xr("frost", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost=frost, levels=levels)
 
     def view_pipeline_xr_frost_curved(self, frames: torch.Tensor, p: PipelineParams, dp: "_lib.DibrParams", screen, eyes, frost, levels=None,
                                       crop=None, use_ema: bool = False, out_u8: bool = True, want_depth: bool = False,
@@ -1113,8 +1096,8 @@ class Engine:
         Bit-identical to pipeline(want_depth=True)'s engine depth followed by dibr_xr_eyes_frost_curved."""
         if frost is None:
             raise ValueError("view_pipeline_xr_frost_curved: frost must be an xr.XrFrost (mode \"off\" for none)")
-        return self._view_pipeline_xr(frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost, levels,
-                                      "frost_curved")
+        return self._view_pipeline_xr("frost_curved", frames, p, dp, screen, eyes, crop, use_ema, out_u8, want_depth, out, streams, frost=frost,
+                                      levels=levels)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -80,8 +80,9 @@ def test_symbols_version_and_header(lib):
                   "keeps refusing", "a change of their own"):
         assert words in hdr, words
     assert callable(ops.dibr_xr_eyes_panorama_curved) and callable(ops.dibr_xr_panorama_curved_plan)
-    assert "view_pipeline_xr_panorama_curved" in dir(ops.Engine) and "panorama_curved" in ops._XR_PIPELINES
-    assert ops._XR_PIPELINES["panorama_curved"][0] == NEW[2]
+    assert "view_pipeline_xr_panorama_curved" in dir(ops.Engine) and "panorama_curved" in ops._XR_ENTRIES
+    row = ops._XR_ENTRIES["panorama_curved"]
+    assert ("d2s_" + row.direct, row.plan, "d2s_" + row.pipeline + "_streams") == NEW
     assert callable(depth.xr_eye_views_panorama) and "view_pipeline_xr_panorama_curved" in depth.xr_eye_views_panorama.__doc__
 
 
