@@ -81,6 +81,27 @@ class XrPanorama(C.Structure):
                 ("yaw_offset", C.c_double), ("exposure", C.c_double), ("ray", (C.c_double * 9) * 2)]
 
 
+class XrPanel(C.Structure):
+    """d2s_xr_panel: one world-space panel -- the unit quad under `model` (row-major), textured (index) or solid (-1, color)."""
+    _fields_ = [("model", C.c_double * 16), ("texture", C.c_int32), ("flags", C.c_uint32), ("color", C.c_float * 4), ("alpha", C.c_float),
+                ("struct_size", C.c_uint32)]
+
+
+class XrTexture(C.Structure):
+    """d2s_xr_texture: a panel's RGBA8 picture on the device, row 0 = its top row."""
+    _fields_ = [("rgba", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("wrap", C.c_int32), ("struct_size", C.c_uint32)]
+
+
+class XrPanelsPlanResult(C.Structure):
+    """d2s_xr_panels_plan_result (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rows_per_eye", C.c_int32), ("setup_launches", C.c_int32), ("render_launches", C.c_int32),
+                ("drawn", C.c_int32 * 2), ("tile0", (C.c_int32 * 2) * 2), ("tiles", (C.c_int32 * 2) * 2), ("grid", C.c_uint32 * 3),
+                ("reserved", C.c_uint32), ("workspace_bytes", C.c_uint64), ("out_elems", C.c_uint64), ("offsets", C.c_uint64 * 2)]
+
+
+XR_PANEL_DEPTH_TEST, XR_PANEL_DEPTH_WRITE, XR_PANEL_BLEND = 1, 2, 4      # D2S_XR_PANEL_*
+XR_WRAP = {"repeat": 0, "clamp": 1}      # D2S_XR_WRAP_*
+XR_MAX_PANELS = 32
 XR_GLOW = {"off": 0, "glow": 1, "glow2": 2}
 XR_FROST = {"off": 0, "veil": 1, "frosted": 2}
 XR_CURVE = {"flat": 0, "horizontal": 1, "vertical": 2}      # D2S_XR_CURVE_*
@@ -325,6 +346,12 @@ SYMBOLS = {
                                                                C.POINTER(C.c_double), C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int,
                                                                _P, C.c_int, _P, _P, C.c_uint64, C.POINTER(XrFrost), _P, C.POINTER(XrGlow),
                                                                C.POINTER(XrPanorama), _P, _P, _P]),
+    # the world-space panels drawn in place over finished eye images (xr_viewer/overlay.py:81-249, 1427-1510)
+    "d2s_dibr_xr_panels_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "d2s_dibr_xr_panels": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.POINTER(XrPanel), C.c_int,
+                                     C.POINTER(XrTexture), C.c_int, _P, C.c_uint64, _P]),
+    "d2s_dibr_xr_panels_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.POINTER(XrPanel), C.c_int,
+                                          C.POINTER(XrTexture), C.c_int, C.POINTER(XrPanelsPlanResult)]),
     "d2s_view_pipeline_xr_glow_curved_streams": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(PreParams),
                                                            C.POINTER(PostParams), C.POINTER(DibrParams), C.POINTER(C.c_double),
                                                            C.POINTER(XrScreen), C.POINTER(XrEye), C.c_int, C.c_int, _P, C.c_int, _P, _P,

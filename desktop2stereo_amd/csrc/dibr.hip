@@ -873,6 +873,86 @@ dibr_xr_glow_curved_kernel(const uint8_t* __restrict__ rgb_all, const float* __r
                                           XrNoWalls(), xr_bg<BG>(P, pano_rgb, pano_chain));
 }
 
+// d2s_dibr_xr_panels: the world-space panels, in place over finished eye images (rows: dibr_xr.h; _OVERLAY_FRAG and _SOLID_FRAG,
+// xr_viewer/glsl.py:28-40, 106-112).  Threads and tiles as dibr_xr_kernel's, over the rectangle of tiles the panels' boxes touch; a
+// block whose tile no box touches leaves before it reads anything but the boxes.  No barrier, no LDS: the rows and the textures'
+// records are block-uniform reads.  Per pixel: z = the screen's depth from xr_search_all (1.0 uncovered), the destination read once,
+// the panels in order, one store if a panel passed.
+// One GL_LINEAR tap of an RGBA8 texture whose row 0 is the picture's top: GL's row coordinate v * h - 0.5 counted from the top is
+// (1 - v) * h - 0.5.  -> rgb in levels, alpha 0..1
+__device__ __forceinline__ void panel_texture(const XrTexDev& t, float u, float v, float s[4]) {
+    const float x = u * (float)t.w - 0.5f, y = (1.0f - v) * (float)t.h - 0.5f;
+    const float xf = floorf(x), yf = floorf(y), fx = x - xf, fy = y - yf;
+    int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
+    if (t.wrap == D2S_XR_WRAP_REPEAT) {
+        x0 %= t.w; x0 += x0 < 0 ? t.w : 0; x1 %= t.w; x1 += x1 < 0 ? t.w : 0;
+        y0 %= t.h; y0 += y0 < 0 ? t.h : 0; y1 %= t.h; y1 += y1 < 0 ? t.h : 0;
+    } else {
+        x0 = min(max(x0, 0), t.w - 1); x1 = min(max(x1, 0), t.w - 1); y0 = min(max(y0, 0), t.h - 1); y1 = min(max(y1, 0), t.h - 1);
+    }
+    const uint32_t* __restrict__ px = (const uint32_t*)t.rgba;
+    const uint32_t a = px[(long)y0 * t.w + x0], b = px[(long)y0 * t.w + x1], c = px[(long)y1 * t.w + x0], d = px[(long)y1 * t.w + x1];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float fa = (float)((a >> (8 * k)) & 255u), fb = (float)((b >> (8 * k)) & 255u);
+        const float fc = (float)((c >> (8 * k)) & 255u), fd = (float)((d >> (8 * k)) & 255u);
+        const float top = fa + (fb - fa) * fx, bot = fc + (fd - fc) * fx;
+        s[k] = top + (bot - top) * fy;
+    }
+    s[3] *= 1.0f / 255.0f;
+}
+template <int OUT_FMT>
+__global__ void __launch_bounds__(256)
+dibr_xr_panels_kernel(void* __restrict__ out_all, const XrFacet* __restrict__ tab_all, XrEyes ex, XrPanelsDev P) {
+    const int ei = blockIdx.z % ex.n;
+    if ((int)blockIdx.x >= P.tiles[ei][0] || (int)blockIdx.y >= P.tiles[ei][1]) return;
+    const int tx = P.tile0[ei][0] + (int)blockIdx.x, ty = P.tile0[ei][1] + (int)blockIdx.y;
+    const float* __restrict__ tab = (const float*)(tab_all + ei * XR_PANEL_ROWS);
+    const int nf = ex.e[ei].nf;
+    uint32_t live = 0;                                     // the panels whose box touches this tile (block-uniform)
+    for (int k = 0; k < P.n; ++k) {
+        const float* __restrict__ r = tab + (nf + k) * XR_ROW_FLOATS;
+        if ((float)(tx * 16) < r[14] && (float)(tx * 16 + 16) > r[12] && (float)(ty * 16) < r[15] && (float)(ty * 16 + 16) > r[13]) live |= 1u << k;
+    }
+    if (!live) return;
+    const XrPix px = xr_pix_at(ex, tx, ty);
+    if (!px.inside) return;
+    float z = xr_search_all(tab, nf, px.xc, px.yc).bz;
+    const long o = px.e.out_off + (((long)px.b * px.e.h + px.y) * px.e.w + px.x) * P.nch;
+    float c[4] = {0.f, 0.f, 0.f, 1.f};
+    if (OUT_FMT == D2S_FMT_U8_HWC) {
+        const uint8_t* __restrict__ d = (const uint8_t*)out_all + o;
+        c[0] = (float)d[0]; c[1] = (float)d[1]; c[2] = (float)d[2];
+        if (P.nch == 4) c[3] = (float)d[3] * (1.0f / 255.0f);
+    } else {
+        const float* __restrict__ d = (const float*)out_all + o;
+        c[0] = d[0]; c[1] = d[1]; c[2] = d[2];
+        if (P.nch == 4) c[3] = d[3];
+    }
+    bool drew = false;
+    for (uint32_t m = live; m; m &= m - 1) {
+        const float* __restrict__ r = tab + (nf + __builtin_ctz(m)) * XR_ROW_FLOATS;
+        const XrPt p = xr_row_at(r, px.xc, px.yc);
+        if (!(p.na >= 0.f && p.nb >= 0.f && p.na <= p.nw && p.nb <= p.nw && p.nw > 0.f && p.z >= -1.0f && p.z <= 1.0f)) continue;
+        const uint32_t flags = (uint32_t)r[17];
+        if ((flags & D2S_XR_PANEL_DEPTH_TEST) && !(p.z < z)) continue;      // GL_LESS
+        float s[4] = {r[18], r[19], r[20], r[21]};
+        const int tex = (int)r[16];
+        if (tex >= 0) {
+            panel_texture(P.t[tex], p.na / p.nw, p.nb / p.nw, s);
+            s[3] *= r[22];
+        }
+        if (flags & D2S_XR_PANEL_BLEND) {                    // SRC_ALPHA, ONE_MINUS_SRC_ALPHA, alpha included
+            const float sa = s[3], ia = 1.0f - sa;
+            c[0] = sa * s[0] + ia * c[0]; c[1] = sa * s[1] + ia * c[1]; c[2] = sa * s[2] + ia * c[2]; c[3] = sa * sa + ia * c[3];
+        } else { c[0] = s[0]; c[1] = s[1]; c[2] = s[2]; c[3] = s[3]; }
+        // (GL writes depth only where the depth test is enabled)
+        if ((flags & (D2S_XR_PANEL_DEPTH_TEST | D2S_XR_PANEL_DEPTH_WRITE)) == (D2S_XR_PANEL_DEPTH_TEST | D2S_XR_PANEL_DEPTH_WRITE)) z = p.z;
+        drew = true;
+    }
+    if (drew) dibr_store<OUT_FMT>(out_all, o, P.nch, c);
+}
+
 int dibr_warp_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                   void* out, int out_fmt, void* stream, bool check_only);      // (also called by d2s_view_pipeline_streams, engine.hip)
 int dibr_warp_crop_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
@@ -1270,5 +1350,67 @@ extern "C" int d2s_dibr_xr_panorama_curved_plan(int dh, int dw, int batch, int H
     const int rc = xr_plan(XR_ENTRY_PANORAMA_CURVED, dh, dw, batch, H, W, p, crop, screen, eyes, n_eyes, out_fmt, glow, frost, pl, pano);
     if (rc) return rc;
     xr_plan_result(pl, res);
+    return D2S_OK;
+}
+
+// The world-space panels over finished eye images (xr_viewer/overlay.py:81-249, 1427-1510; xr_viewer/effects.py:1157-1225):
+// xr_panels_plan (dibr_xr.h) checks every argument that is no device pointer and forms both eyes' rows; the launcher looks at the
+// pointers, writes the rows with the eye views' set-up launches and draws.
+extern "C" int d2s_dibr_xr_panels_workspace(int n_eyes, uint64_t* bytes) {
+    D2S_REQUIRE(bytes, "null pointer (bytes)");
+    D2S_REQUIRE(n_eyes >= 1 && n_eyes <= 2, "n_eyes must be 1 or 2");
+    *bytes = (uint64_t)n_eyes * XR_PANEL_ROWS * sizeof(XrFacet);
+    return D2S_OK;
+}
+
+extern "C" int d2s_dibr_xr_panels_plan(int out_fmt, int batch, int alpha_mode, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes,
+                                       const d2s_xr_panel* panels, int n_panels, const d2s_xr_texture* textures, int n_textures,
+                                       d2s_xr_panels_plan_result* res) {
+    D2S_REQUIRE(res, "null pointer (res)");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_xr_panels_plan_result), "d2s_xr_panels_plan_result.struct_size must be sizeof(d2s_xr_panels_plan_result) = 104");
+    XrPanelsPlan pl;
+    const int rc = xr_panels_plan(out_fmt, batch, alpha_mode, screen, eyes, n_eyes, panels, n_panels, textures, n_textures, pl);
+    if (rc) return rc;
+    *res = d2s_xr_panels_plan_result{};
+    res->struct_size = sizeof(d2s_xr_panels_plan_result);
+    res->rows_per_eye = pl.rows_per_eye; res->setup_launches = pl.setup_launches; res->render_launches = pl.render_launches;
+    for (int i = 0; i < n_eyes; ++i) {
+        res->drawn[i] = pl.drawn[i]; res->offsets[i] = pl.offs[i];
+        for (int k = 0; k < 2; ++k) { res->tile0[i][k] = pl.P.tile0[i][k]; res->tiles[i][k] = pl.P.tiles[i][k]; }
+    }
+    for (int k = 0; k < 3; ++k) res->grid[k] = pl.grid[k];
+    res->workspace_bytes = pl.workspace_bytes; res->out_elems = pl.total;
+    return D2S_OK;
+}
+
+extern "C" int d2s_dibr_xr_panels(void* out, int out_fmt, int batch, int alpha_mode, const d2s_xr_screen* screen, const d2s_xr_eye* eyes,
+                                  int n_eyes, const d2s_xr_panel* panels, int n_panels, const d2s_xr_texture* textures, int n_textures,
+                                  void* workspace, uint64_t workspace_bytes, void* stream) {
+    XrPanelsPlan pl;
+    const int rc = xr_panels_plan(out_fmt, batch, alpha_mode, screen, eyes, n_eyes, panels, n_panels, textures, n_textures, pl);
+    if (rc) return rc;
+    D2S_REQUIRE(workspace, "null pointer (workspace)");
+    D2S_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+    D2S_REQUIRE(workspace_bytes >= pl.workspace_bytes, "workspace_bytes below d2s_dibr_xr_panels_workspace");
+    D2S_REQUIRE(out, "null pointer (out)");
+    for (int k = 0; k < n_panels; ++k) {
+        if (panels[k].texture < 0) continue;
+        const uint8_t* t = textures[panels[k].texture].rgba;
+        D2S_REQUIRE(t && ((uintptr_t)t & 3) == 0, "a panel's texture needs a 4-byte aligned device pointer (rgba)");
+    }
+    if (!pl.render_launches) return D2S_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const XrFacet* tab = (const XrFacet*)workspace;
+    for (int i = 0; i < pl.ex.n; ++i)
+        for (int f0 = 0; f0 < pl.rows_per_eye; f0 += XR_CHUNK_FACETS) {
+            const int nf = std::min(XR_CHUNK_FACETS, pl.rows_per_eye - f0), n_floats = nf * XR_ROW_FLOATS;
+            XrFacetChunk chunk;
+            for (int f = 0; f < nf; ++f) chunk.f[f] = pl.rows[i][f0 + f];
+            hipLaunchKernelGGL(dibr_xr_table_kernel, dim3(cdiv(n_floats, 256)), dim3(256), 0, st, chunk, (float*)(tab + i * XR_PANEL_ROWS + f0), n_floats);
+        }
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(256);
+    if (out_fmt == D2S_FMT_U8_HWC) hipLaunchKernelGGL((dibr_xr_panels_kernel<D2S_FMT_U8_HWC>), grid, block, 0, st, out, tab, pl.ex, pl.P);
+    else hipLaunchKernelGGL((dibr_xr_panels_kernel<D2S_FMT_F32_HWC>), grid, block, 0, st, out, tab, pl.ex, pl.P);
+    D2S_CHECK_LAUNCH();
     return D2S_OK;
 }

@@ -625,6 +625,131 @@ inline int xr_plan(int entry, int dh, int dw, int batch, int H, int W, const d2s
     return D2S_OK;
 }
 
+// ---- the world-space panels drawn after the screen and its look (d2s_dibr_xr_panels; _render_fps_overlay and _render_keyboard,
+// xr_viewer/overlay.py:81-249, 1427-1510; the OSDs and lasers of _render_eye, xr_viewer/effects.py:1157-1225) ----
+// A panel is the unit quad under an affine model matrix: one facet row per eye, written after the screen's own rows (row nf + k) by
+// the same set-up launches.  ha, hb, hw, hz are a facet's; the other twelve floats carry what the pass needs instead of he and a uv
+// affine (a panel's uv IS (a, b)), every one a small integer or a colour, exact in float:
+//   12 .. 15  the panel's pixel box on this eye image, x0, y0, x1, y1 (x1 <= x0: not on this image): the projected corners' bounds
+//             grown by one pixel (the per-pixel test rounds by about 1e-4 pixel) and clamped to the image;
+//   16 texture index or -1;  17 flags (D2S_XR_PANEL_*);  18 .. 21 colour, rgb in levels (0..255);  22 u_alpha;  23 unused.
+constexpr int XR_MAX_PANELS = D2S_XR_MAX_PANELS, XR_MAX_TEXTURES = 32;
+constexpr int XR_PANEL_ROWS = XR_MAX_FACETS + XR_MAX_PANELS;      // an eye's table in the workspace (d2s_dibr_xr_panels_workspace)
+struct XrTexDev { const uint8_t* rgba; int w, h, wrap, pad; };
+// tile0, tiles: per eye, the 16 x 16 tiles the boxes touch, as a rectangle of tiles (a block whose tile no box touches leaves at once)
+struct XrPanelsDev { int n, nch; int tile0[2][2], tiles[2][2]; XrTexDev t[XR_MAX_TEXTURES]; };
+
+struct XrPanelsPlan {
+    XrEyes ex;
+    XrPanelsDev P;
+    int rows_per_eye, setup_launches, render_launches, drawn[2];
+    XrFacet rows[2][XR_PANEL_ROWS];
+    unsigned grid[3];
+    uint64_t workspace_bytes, offs[2], total;
+};
+
+// Everything d2s_dibr_xr_panels decides from the arguments that are no device pointers, and every refusal of that kind; no HIP call.
+inline int xr_panels_plan(int out_fmt, int batch, int alpha_mode, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes,
+                          const d2s_xr_panel* panels, int n_panels, const d2s_xr_texture* textures, int n_textures, XrPanelsPlan& pl) {
+    D2S_REQUIRE(out_fmt == D2S_FMT_U8_HWC || out_fmt == D2S_FMT_F32_HWC, "bad out_fmt (U8_HWC or F32_HWC)");
+    D2S_REQUIRE(batch > 0 && batch <= 65535, "bad batch (1 .. 65535)");
+    D2S_REQUIRE(alpha_mode >= D2S_DIBR_ALPHA_WINDOW && alpha_mode <= D2S_DIBR_ALPHA_RGBA, "bad alpha_mode");
+    if (alpha_mode == D2S_DIBR_ALPHA_PREMULTIPLIED) {
+        set_error("unsupported: D2S_DIBR_ALPHA_PREMULTIPLIED eye images (rgb already times alpha: the destination the reference blends "
+                  "its panels over cannot be formed); draw the panels over D2S_DIBR_ALPHA_RGBA or D2S_DIBR_ALPHA_WINDOW images");
+        return D2S_E_UNSUPPORTED;
+    }
+    int rc = xr_screen_check(screen, eyes, n_eyes, batch);
+    if (rc) return rc;
+    D2S_REQUIRE(n_panels >= 0 && n_panels <= XR_MAX_PANELS, "n_panels must be 0 .. 32 (D2S_XR_MAX_PANELS)");
+    D2S_REQUIRE(n_textures >= 0 && n_textures <= XR_MAX_TEXTURES, "n_textures must be 0 .. 32");
+    D2S_REQUIRE((n_panels == 0 || panels) && (n_textures == 0 || textures), "null pointer (panels, textures)");
+    pl.P = XrPanelsDev{};
+    for (int t = 0; t < n_textures; ++t) {
+        D2S_REQUIRE(textures[t].struct_size == sizeof(d2s_xr_texture), "d2s_xr_texture.struct_size must be sizeof(d2s_xr_texture) = 24");
+        D2S_REQUIRE(textures[t].width >= 1 && textures[t].height >= 1 && textures[t].width <= 8192 && textures[t].height <= 8192,
+                    "a panel texture must be 1 .. 8192 on a side");
+        D2S_REQUIRE(textures[t].wrap == D2S_XR_WRAP_REPEAT || textures[t].wrap == D2S_XR_WRAP_CLAMP, "bad texture wrap (D2S_XR_WRAP_*)");
+        pl.P.t[t] = XrTexDev{textures[t].rgba, textures[t].width, textures[t].height, textures[t].wrap, 0};
+    }
+    for (int k = 0; k < n_panels; ++k) {
+        const d2s_xr_panel& q = panels[k];
+        D2S_REQUIRE(q.struct_size == sizeof(d2s_xr_panel), "d2s_xr_panel.struct_size must be sizeof(d2s_xr_panel) = 160");
+        D2S_REQUIRE(xr_finite(q.model, 16), "a panel's model matrix must be finite");
+        D2S_REQUIRE(q.model[12] == 0.0 && q.model[13] == 0.0 && q.model[14] == 0.0 && q.model[15] == 1.0,
+                    "a panel's model matrix must be affine (last row 0 0 0 1)");
+        D2S_REQUIRE(q.texture >= -1 && q.texture < n_textures, "a panel's texture must be -1 (solid) or an index into textures");
+        D2S_REQUIRE((q.flags & ~(uint32_t)(D2S_XR_PANEL_DEPTH_TEST | D2S_XR_PANEL_DEPTH_WRITE | D2S_XR_PANEL_BLEND)) == 0, "unknown panel flags (D2S_XR_PANEL_*)");
+        D2S_REQUIRE(std::isfinite(q.alpha) && std::isfinite(q.color[0]) && std::isfinite(q.color[1]) && std::isfinite(q.color[2]) &&
+                    std::isfinite(q.color[3]), "a panel's alpha and color must be finite");
+    }
+    XrSurface S;
+    xr_surface(screen, S);
+    for (int i = 0; i < n_eyes; ++i)
+        if (!(xr_min_w(S, eyes[i].vp) > 1e-6)) {
+            set_error("unsupported: a vertex of the screen has clip w <= 1e-6 (the screen crosses the eye plane)");
+            return D2S_E_UNSUPPORTED;
+        }
+    xr_out_layout(eyes, n_eyes, batch, alpha_mode, pl.offs, &pl.total);
+    pl.P.n = n_panels; pl.P.nch = alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    pl.ex = XrEyes{};
+    pl.ex.n = n_eyes;
+    pl.rows_per_eye = S.n + n_panels;
+    pl.workspace_bytes = (uint64_t)n_eyes * XR_PANEL_ROWS * sizeof(XrFacet);
+    int mx = 0, my = 0, any = 0;
+    for (int i = 0; i < n_eyes; ++i) {
+        const int w = eyes[i].width, h = eyes[i].height;
+        pl.ex.e[i] = XrEyeDev{w, h, eyes[i].eye, S.n, (long)pl.offs[i]};
+        xr_facets(S, eyes[i].vp, w, h, pl.rows[i]);
+        pl.drawn[i] = 0;
+        int bx0 = w, by0 = h, bx1 = 0, by1 = 0;
+        for (int k = 0; k < n_panels; ++k) {
+            const d2s_xr_panel& q = panels[k];
+            XrVert v[4];                                   // (-1, -1), (1, -1), (-1, 1), (1, 1): uv (0, 0), (1, 0), (0, 1), (1, 1)
+            int behind = 0;
+            double x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+            for (int c = 0; c < 4; ++c) {
+                const double lx = (c & 1) ? 1.0 : -1.0, ly = (c & 2) ? 1.0 : -1.0;
+                for (int r = 0; r < 3; ++r) v[c].p[r] = q.model[4 * r] * lx + q.model[4 * r + 1] * ly + q.model[4 * r + 3];
+                v[c].u = (c & 1) ? 1.0 : 0.0; v[c].v = (c & 2) ? 1.0 : 0.0;
+                double cl[4];
+                xr_clip(eyes[i].vp, v[c].p, 1.0, cl);
+                if (!(cl[3] > 1e-6)) { ++behind; continue; }
+                const double px = (cl[0] / cl[3] + 1.0) * 0.5 * w, py = (1.0 - cl[1] / cl[3]) * 0.5 * h;
+                x0 = fmin(x0, px); x1 = fmax(x1, px); y0 = fmin(y0, py); y1 = fmax(y1, py);
+            }
+            if (behind != 0 && behind != 4) {
+                set_error("unsupported: a vertex of a panel has clip w <= 1e-6 but not all four (the panel crosses the eye plane)");
+                return D2S_E_UNSUPPORTED;
+            }
+            XrFacet& F = pl.rows[i][S.n + k];
+            xr_facet_row(v[0], v[1], v[2], eyes[i].vp, w, h, F);
+            const bool live = !(F.ha[0] == 0.f && F.ha[1] == 0.f && F.ha[2] == -1.f);      // (edge-on: covers no pixel centre)
+            int ix0 = 0, iy0 = 0, ix1 = 0, iy1 = 0;
+            if (behind == 0 && live && std::isfinite(x0) && std::isfinite(x1) && std::isfinite(y0) && std::isfinite(y1)) {
+                ix0 = (int)fmax(0.0, floor(x0) - 1.0); iy0 = (int)fmax(0.0, floor(y0) - 1.0);
+                ix1 = (int)fmin((double)w, ceil(x1) + 1.0); iy1 = (int)fmin((double)h, ceil(y1) + 1.0);
+            }
+            if (ix1 <= ix0 || iy1 <= iy0) ix0 = iy0 = ix1 = iy1 = 0;
+            else { ++pl.drawn[i]; bx0 = std::min(bx0, ix0); by0 = std::min(by0, iy0); bx1 = std::max(bx1, ix1); by1 = std::max(by1, iy1); }
+            F.he[0] = (float)ix0; F.he[1] = (float)iy0; F.he[2] = (float)ix1; F.u0 = (float)iy1;
+            F.ua = (float)q.texture; F.ub = (float)q.flags;
+            F.v0 = q.color[0] * 255.0f; F.va = q.color[1] * 255.0f; F.vb = q.color[2] * 255.0f; F.pad[0] = q.color[3];
+            F.pad[1] = q.alpha; F.pad[2] = 0.f;
+        }
+        if (pl.drawn[i]) {
+            pl.P.tile0[i][0] = bx0 / 16; pl.P.tile0[i][1] = by0 / 16;
+            pl.P.tiles[i][0] = cdiv(bx1, 16) - bx0 / 16; pl.P.tiles[i][1] = cdiv(by1, 16) - by0 / 16;
+            mx = std::max(mx, pl.P.tiles[i][0]); my = std::max(my, pl.P.tiles[i][1]);
+            any = 1;
+        }
+    }
+    pl.render_launches = any;
+    pl.setup_launches = any ? n_eyes * cdiv(pl.rows_per_eye, XR_CHUNK_FACETS) : 0;
+    pl.grid[0] = mx; pl.grid[1] = my; pl.grid[2] = any ? n_eyes * batch : 0;
+    return D2S_OK;
+}
+
 // The seven entries as one call (dibr.hip): xr_plan, then the device pointers and the workspace, then the launches.  check_only:
 // every refusal, nothing launched (the view pipelines ask before they start the model).
 int dibr_xr_entry_any(int entry, const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,

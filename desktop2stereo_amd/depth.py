@@ -318,14 +318,17 @@ def movie_crop(stream: int = 0):
 
 
 def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False,
-                 streams=None, alpha="rgba"):
+                 streams=None, alpha="rgba", panels=None, panel_textures=None):
     """The OpenXR viewer's frame in one stream-ordered native call: uint8 [B,H,W,3] frames (numpy or device tensor) -> predict_depth ->
     the screen `screen` (xr.XrScreen) drawn into each eye image of `eyes` (xr.xr_eye, 1 or 2) with that eye's view-projection matrix,
     as the reference's _render_eye draws it (xr_viewer/effects.py:1023-1137).  Returns one device tensor per eye, [B,h,w,4|3].
     crop: None, (x, y, w, h) in uv, or "auto" (the MovieCrop of the first row's stream slot: the screen shows one crop).  The uniforms
     are the configured parameters', with the OpenXR screen's corner_radius (0.03) and frag_color.a kept (alpha="rgba") for the
     compositor.  The glow: xr_eye_views_glow; the veil and frosted looks, flat or curved screen: xr_eye_views_frost; the panorama
-    background: xr_eye_views_panorama.  The controllers and the glTF environment stay with the caller."""
+    background: xr_eye_views_panorama.  panels: xr.XrPanel objects (the status panel, OSDs, keyboard group, laser quads) that
+    ops.dibr_xr_panels blends over the finished eye images in the same stream, with panel_textures their uint8 [h, w, 4] pictures, top
+    row first; None: exactly the call without them (every xr_eye_views* takes the pair).  The beams, the controllers and the glTF
+    environment stay with the caller."""
     p = _state["params"]
     t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
     t = t.to(device=_device())
@@ -341,12 +344,20 @@ def xr_eye_views(frames, screen, eyes, crop=None, corner_radius=0.03, use_tempor
         mc.update(t[0])
         crop = tuple(mc.crop_uv)
     dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
-    return eng.view_pipeline_xr(t, p, dp, screen, eyes, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
-                                streams=streams)
+    return _with_panels(eng.view_pipeline_xr(t, p, dp, screen, eyes, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
+                                             want_depth=want_depth, streams=streams), want_depth, screen, eyes, alpha, panels, panel_textures)
+
+
+def _with_panels(r, want_depth, screen, eyes, alpha, panels, panel_textures):
+    """An eye-view pipeline's result with the panels blended over its eye images in place (ops.dibr_xr_panels); panels None: r."""
+    if panels is not None:
+        ops.dibr_xr_panels(r[0] if want_depth else r, screen, eyes, panels, panel_textures or (), alpha_mode=_lib.DIBR_ALPHA[alpha])
+    return r
 
 
 def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=None, inner_edge_fraction=0.075, head=None, crop=None,
-                      corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
+                      corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba", panels=None,
+                      panel_textures=None):
     """xr_eye_views with the reference's "Default with Glow" looks drawn in the same launch: around the flat screen (_render_glow,
     xr_viewer/effects.py:476-585) and around a curved one (_render_curved_glow, effects.py:408-474; an eye outside the convex region the
     curved screen bounds, xr.XrScreen.eye_inside, is refused).  glow: "glow" | "glow2" | an xr.XrGlow; range_m: None = xr.glow_range_m(screen, head).  levels: the
@@ -374,12 +385,13 @@ def xr_eye_views_glow(frames, screen, eyes, glow="glow", levels=None, range_m=No
         levels = ops.mip_chain(t)
     dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
     run = eng.view_pipeline_xr_glow if getattr(screen, "curve", "flat") == "flat" else eng.view_pipeline_xr_glow_curved
-    return run(t, p, dp, screen, eyes, glow, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
-               streams=streams)
+    return _with_panels(run(t, p, dp, screen, eyes, glow, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
+                            want_depth=want_depth, streams=streams), want_depth, screen, eyes, alpha, panels, panel_textures)
 
 
 def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=None, multiplier=1.0, time=0.0, crop=None, corner_radius=0.03,
-                       use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
+                       use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba", panels=None,
+                       panel_textures=None):
     """xr_eye_views with the reference's "veil" or "frosted" look around the screen, flat or curved, drawn in the same launch
     (_render_frost_veil / _render_frost_glow, xr_viewer/effects.py:789-857; a curved screen: Engine.view_pipeline_xr_frost_curved).  frost: "veil" | "frosted" (the reference's defaults for
     head, multiplier = _glow_intensity_multiplier and time) | an xr.XrFrost.  levels: the frames' colour mip chain (ops.mip_chain) for
@@ -409,12 +421,13 @@ def xr_eye_views_frost(frames, screen, eyes, frost="veil", levels=None, head=Non
         levels = ops.mip_chain(t)
     dp = ops.dibr_params(p.ipd, p.depth_strength, p.convergence, corner_radius=corner_radius, alpha=alpha)
     run = eng.view_pipeline_xr_frost if getattr(screen, "curve", "flat") == "flat" else eng.view_pipeline_xr_frost_curved
-    return run(t, p, dp, screen, eyes, frost, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth,
-               streams=streams)
+    return _with_panels(run(t, p, dp, screen, eyes, frost, levels, crop=crop, use_ema=use_temporal_smooth, out_u8=out_u8,
+                            want_depth=want_depth, streams=streams), want_depth, screen, eyes, alpha, panels, panel_textures)
 
 
 def xr_eye_views_panorama(frames, screen, eyes, panorama, pano_rgb, eyes_proj_view, glow=None, frost=None, levels=None, crop=None,
-                          corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba"):
+                          corner_radius=0.03, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, alpha="rgba",
+                          panels=None, panel_textures=None):
     """xr_eye_views with the reference's panorama background behind the screen in the same launch (_render_panorama_background,
     xr_viewer/effects.py:930-1021).  panorama: an xr.XrPanorama (yaw_offset_deg, exposure, flip_y); pano_rgb: the equirectangular image,
     uint8 [h, w, 3] (numpy or device tensor), row 0 up; eyes_proj_view: one (proj, view) pair per entry of eyes (proj y-flipped where
@@ -450,8 +463,9 @@ def xr_eye_views_panorama(frames, screen, eyes, panorama, pano_rgb, eyes_proj_vi
     ps = panorama.c_struct(eyes_proj_view, tuple(img.shape[:2]))
     curved_look = getattr(screen, "curve", "flat") not in ("flat", 0) and (glow_on or (frost is not None and frost.draws()))
     view = eng.view_pipeline_xr_panorama_curved if curved_look else eng.view_pipeline_xr_panorama
-    return view(t, p, dp, screen, eyes, ps, img, chain, glow=glow, frost=frost, levels=levels, crop=crop, use_ema=use_temporal_smooth,
-                out_u8=out_u8, want_depth=want_depth, streams=streams)
+    return _with_panels(view(t, p, dp, screen, eyes, ps, img, chain, glow=glow, frost=frost, levels=levels, crop=crop,
+                             use_ema=use_temporal_smooth, out_u8=out_u8, want_depth=want_depth, streams=streams), want_depth, screen, eyes,
+                        alpha, panels, panel_textures)
 
 
 def pipeline(frames, display_mode=None, use_temporal_smooth=False, out_u8=True, want_depth=False, streams=None, inpaint=False,

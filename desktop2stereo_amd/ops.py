@@ -441,7 +441,9 @@ _XR_ENTRIES = {
     "panorama": _XrEntry("dibr_xr_eyes_panorama", "view_pipeline_xr_panorama", "d2s_dibr_xr_panorama_plan",
                          "d2s_dibr_xr_frost_curved_workspace", "panorama"),
     "panorama_curved": _XrEntry("dibr_xr_eyes_panorama_curved", "view_pipeline_xr_panorama_curved", "d2s_dibr_xr_panorama_curved_plan",
-                                "d2s_dibr_xr_frost_curved_workspace", "panorama")}
+                                "d2s_dibr_xr_frost_curved_workspace", "panorama"),
+    # the pass over finished eye images: no frames, no view pipeline of its own (depth.xr_eye_views* chain it); tail: panels, textures
+    "panels": _XrEntry("dibr_xr_panels", "", "d2s_dibr_xr_panels_plan", "d2s_dibr_xr_panels_workspace", "panels")}
 
 
 def _xr_args(screen, eyes):
@@ -714,6 +716,89 @@ def dibr_xr_plan(entry: str, dh: int, dw: int, batch: int, H: int, W: int, dp: "
     (include/d2s.h d2s_dibr_xr_plan; host code, no GPU): the kind of kernel, the table rows per eye and the launches that write them, the
     render launch's grid and LDS bytes, the workspace bytes and the out layout.  Raises D2SError with the entry's own refusal."""
     return _xr_plan_query(entry, dh, dw, batch, H, W, dp, screen, eyes, crop, out_u8, (_xr_struct(glow),), lead=(_lib.XR_ENTRY[entry],))
+
+
+def _xr_panel_args(who: str, panels, textures, device, wrap: str):
+    """(d2s_xr_panel array or None, d2s_xr_texture array or None, what the caller keeps alive) of xr.XrPanel objects (or their
+    structs) and [h, w, 4] uint8 tensors, TOP ROW FIRST -- the library takes them that way and accounts for GL's bottom-first rows
+    itself (include/d2s.h), so no copy is made here.  device None: the plan door, which looks at no tensor's device."""
+    ps = [q if isinstance(q, _lib.XrPanel) else q.c_struct() for q in (panels or ())]
+    ts, keep = [], []
+    for t in (textures or ()):
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 4:
+            raise ValueError(f"{who}: a panel texture must be a uint8 [h, w, 4] tensor, top row first")
+        if device is not None:
+            _need_cuda(t, "panel texture")
+            if t.device != device:
+                raise ValueError(f"{who}: a panel texture is on {t.device}, the eye images on {device}")
+            t = t.contiguous()
+        keep.append(t)
+        ts.append(_lib.XrTexture(t.data_ptr() if device is not None else None, int(t.shape[1]), int(t.shape[0]), _lib.XR_WRAP[wrap],
+                                 C.sizeof(_lib.XrTexture)))
+    pa = (_lib.XrPanel * len(ps))(*ps) if ps else None
+    ta = (_lib.XrTexture * len(ts))(*ts) if ts else None
+    return pa, len(ps), ta, len(ts), keep
+
+
+def dibr_xr_panels(images, screen, eyes, panels, textures=(), alpha_mode: Optional[int] = None, wrap: str = "repeat",
+                   workspace: Optional[torch.Tensor] = None) -> list:
+    """The world-space panels the reference draws after the screen and its look -- the FPS / status panel, the OSDs, the calibration
+    and help panels, the keyboard with its border and key highlights, the laser quads (d2s_dibr_xr_panels; reference
+    xr_viewer/overlay.py:81-249, 1427-1510, xr_viewer/effects.py:1157-1225) -- blended IN PLACE into `images`: what any
+    ops.dibr_xr_eyes* or Engine.view_pipeline_xr* returned for this screen and these eyes (views of one flat buffer, in the eyes'
+    order).  panels: xr.XrPanel, drawn in order, each depth-tested against the screen (whose depth the pass forms itself) and the
+    earlier panels that wrote depth.  textures: uint8 [h, w, 4] tensors, top row first; wrap: the GL wrap of the bilinear taps at a
+    panel's edge ("repeat": the reference's; "clamp").  alpha_mode: the images' (None: 4 channels = rgba, 3 = window); premultiplied
+    images are refused.  Returns `images`.  The rainbow beams, hit circles and controller meshes are not drawn."""
+    who = "dibr_xr_panels"
+    row = _XR_ENTRIES["panels"]
+    sc, ea = _xr_args(screen, eyes)
+    imgs = list(images)
+    if len(imgs) != len(ea) or not imgs:
+        raise ValueError(f"{who}: images must be one tensor per eye")
+    first = imgs[0]
+    _need_cuda(first, "images")
+    B, nch = first.shape[0], first.shape[-1]
+    if first.dtype not in (torch.uint8, torch.float32) or nch not in (3, 4):
+        raise ValueError(f"{who}: images must be uint8 or float32 [B,h,w,3|4]")
+    if alpha_mode is None:
+        alpha_mode = _lib.DIBR_ALPHA["rgba"] if nch == 4 else _lib.DIBR_ALPHA["window"]
+    offs, total = dibr_xr_shape(ea, B, alpha_mode)
+    base = first.data_ptr()
+    for t, e, o in zip(imgs, ea, offs):
+        if t.dtype != first.dtype or t.device != first.device or tuple(t.shape) != (B, e.height, e.width, nch) or not t.is_contiguous() or \
+                t.data_ptr() != base + o * first.element_size():
+            raise ValueError(f"{who}: images must be the tensors an eye-view call returned for these eyes (views of one flat buffer, "
+                             f"eye i [B,{e.height},{e.width},{nch}] at dibr_xr_shape's offset)")
+    pa, n_p, ta, n_t, _keep = _xr_panel_args(who, panels, textures, first.device, wrap)
+    ws = workspace if workspace is not None else _xr_workspace(len(ea), first.device, row.workspace)
+    _need_cuda(ws, "workspace")
+    _same_device(first, ws, f"{who} workspace")
+    fmt = FMT_U8_HWC if first.dtype == torch.uint8 else FMT_F32_HWC
+    with _on(first.device) as st:
+        check(_lib.load().d2s_dibr_xr_panels(C.c_void_p(base), fmt, B, int(alpha_mode), C.byref(sc), ea, len(ea), pa, n_p, ta, n_t,
+                                             _ptr(ws), ws.numel() * ws.element_size(), st), "d2s_" + row.direct)
+    return imgs
+
+
+def dibr_xr_panels_plan(batch: int, screen, eyes, panels, textures=(), alpha_mode: int = 2, out_u8: bool = True, wrap: str = "repeat") -> dict:
+    """What dibr_xr_panels decides for these arguments before it looks at a device pointer (d2s_dibr_xr_panels_plan; host code, no
+    GPU): the table rows per eye (the screen's facets, then one per panel), the set-up launches that write them, the render launches
+    (0 with no panel on any image: the call does nothing), per eye the panels drawn and the rectangle of 16 x 16 tiles their pixel
+    boxes touch, the render grid, the workspace bytes and the images' layout.  textures: tensors (any device) or (h, w) pairs.
+    Raises D2SError with the call's own refusal."""
+    row = _XR_ENTRIES["panels"]
+    sc, ea = _xr_args(screen, eyes)
+    tex = [t if isinstance(t, torch.Tensor) else torch.empty((int(t[0]), int(t[1]), 4), dtype=torch.uint8, device="meta") for t in textures]
+    pa, n_p, ta, n_t, _keep = _xr_panel_args("dibr_xr_panels_plan", panels, tex, None, wrap)
+    r = _lib.XrPanelsPlanResult()
+    r.struct_size = C.sizeof(_lib.XrPanelsPlanResult)
+    check(getattr(_lib.load(), row.plan)(FMT_U8_HWC if out_u8 else FMT_F32_HWC, int(batch), int(alpha_mode), C.byref(sc), ea, len(ea), pa, n_p,
+                                         ta, n_t, C.byref(r)), row.plan)
+    n = len(ea)
+    return {"rows_per_eye": r.rows_per_eye, "setup_launches": r.setup_launches, "render_launches": r.render_launches,
+            "drawn": list(r.drawn[:n]), "tile0": [tuple(r.tile0[i]) for i in range(n)], "tiles": [tuple(r.tiles[i]) for i in range(n)],
+            "grid": tuple(r.grid), "workspace_bytes": r.workspace_bytes, "out_elems": r.out_elems, "offsets": list(r.offsets[:n])}
 
 
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,

@@ -305,6 +305,84 @@ class XrFrost:
         return u
 
 
+def _rot_yx(yaw: float, pitch: float) -> np.ndarray:
+    """rot_y(yaw) @ rot_x(pitch) [4,4]: the rotation the reference gives its panels (no roll; overlay.py:210-219, 1363-1372)."""
+    cy, sy, cp, sp = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch)
+    return (np.array([[cy, 0.0, sy, 0.0], [0.0, 1.0, 0.0, 0.0], [-sy, 0.0, cy, 0.0], [0.0, 0.0, 0.0, 1.0]]) @
+            np.array([[1.0, 0.0, 0.0, 0.0], [0.0, cp, -sp, 0.0], [0.0, sp, cp, 0.0], [0.0, 0.0, 0.0, 1.0]]))
+
+
+@dataclass
+class XrPanel:
+    """One world-space panel of the eye image (include/d2s.h d2s_xr_panel; ops.dibr_xr_panels): the unit quad (+-1, +-1, 0, 1) under
+    the affine `model` [4,4], as the reference draws its status panel, OSDs, keyboard, key highlights and laser quads after the
+    screen.  texture: an index into the call's textures (the reference's _OVERLAY_FRAG: the picture at uv, alpha times `alpha`), or
+    None: the solid `color` (r, g, b in 0..1, a; _SOLID_FRAG).  depth_test: GL_LESS against the screen and the earlier panels that
+    wrote depth; depth_write (acts only with depth_test, as in GL); blend: SRC_ALPHA, ONE_MINUS_SRC_ALPHA, alpha included.  The
+    constructors restate the reference's placements in float64 (the reference rounds each matrix to float32)."""
+    model: np.ndarray
+    texture: int = None
+    color: Tuple[float, float, float, float] = (1.0, 1.0, 1.0, 1.0)
+    alpha: float = 1.0
+    depth_test: bool = True
+    depth_write: bool = True
+    blend: bool = True
+
+    def c_struct(self) -> "_lib.XrPanel":
+        m = np.asarray(self.model, np.float64)
+        if m.shape != (4, 4):
+            raise ValueError("XrPanel.model must be [4,4]")
+        if len(self.color) != 4:
+            raise ValueError("XrPanel.color must be (r, g, b, a)")
+        flags = (_lib.XR_PANEL_DEPTH_TEST if self.depth_test else 0) | (_lib.XR_PANEL_DEPTH_WRITE if self.depth_write else 0) | \
+            (_lib.XR_PANEL_BLEND if self.blend else 0)
+        return _lib.XrPanel((C.c_double * 16)(*m.ravel()), -1 if self.texture is None else int(self.texture), flags,
+                            (C.c_float * 4)(*[float(v) for v in self.color]), float(self.alpha), C.sizeof(_lib.XrPanel))
+
+    @classmethod
+    def below_screen(cls, screen: "XrScreen", tex_size, texture: int = 0, alpha: float = 1.0) -> "XrPanel":
+        """The FPS / status panel's placement (_render_fps_overlay, xr_viewer/overlay.py:194-229): T @ R @ T_local @ S -- in the
+        screen's plane (yaw and pitch; the reference leaves the roll out), below its bottom edge by 2 % of the screen's height,
+        left-aligned, an eighth of the screen's height tall and tex_size = (width, height)'s aspect wide.  alpha: u_alpha (the
+        reference fades it to 0.15 while a trigger is held on it).  Blended, depth-tested, writes depth."""
+        ow, oh = tex_size
+        sh, sx, sy = float(screen.height), screen.width / 2.0, screen.height / 2.0
+        h = sh / 8.0
+        w = h * (float(ow) / float(oh))
+        T, Tl = np.eye(4), np.eye(4)
+        T[:3, 3] = (screen.pan_x, screen.pan_y, -screen.distance)
+        Tl[0, 3], Tl[1, 3] = -sx + w / 2.0, -sy - sh * 0.02 - h / 2.0
+        return cls(T @ _rot_yx(screen.yaw, screen.pitch) @ Tl @ np.diag([w / 2.0, h / 2.0, 1.0, 1.0]), texture=texture, alpha=alpha)
+
+    @staticmethod
+    def keyboard_world(pan_x: float, pan_y: float, distance: float, yaw: float, pitch: float) -> np.ndarray:
+        """_kb_world_mat (xr_viewer/overlay.py:1356-1379): translate(pan_x, pan_y, -distance) @ rot_y(yaw) @ rot_x(pitch)."""
+        T = np.eye(4)
+        T[:3, 3] = (pan_x, pan_y, -distance)
+        return T @ _rot_yx(yaw, pitch)
+
+    @classmethod
+    def keyboard_group(cls, kb_world, width: float, height: float, border_alpha: float = 0.0, highlights=(), texture: int = 0) -> list:
+        """The keyboard's draws in order (_render_keyboard, xr_viewer/overlay.py:1427-1510), all blended and depth-tested, none writing
+        depth: with border_alpha > 0 the solid border (0.3, 0.7, 1.0, border_alpha), 8 mm larger each way and 1 mm behind the
+        surface; the keyboard, `texture` over width x height metres; then one solid quad 1 mm in front per highlight =
+        ((x0, y0, x1, y1) in metres in the keyboard's frame, (r, g, b, a))."""
+        kb = np.asarray(kb_world, np.float64).reshape(4, 4)
+        kw2, kh2 = width / 2.0, height / 2.0
+        flags = dict(depth_test=True, depth_write=False, blend=True)
+        out = []
+        if border_alpha > 0.0:
+            m = np.diag([kw2 + 0.008, kh2 + 0.008, 1.0, 1.0])
+            m[2, 3] = -0.001
+            out.append(cls(kb @ m, color=(0.3, 0.7, 1.0, float(border_alpha)), **flags))
+        out.append(cls(kb @ np.diag([kw2, kh2, 1.0, 1.0]), texture=texture, **flags))
+        for (x0, y0, x1, y1), color in highlights:
+            m = np.diag([(x1 - x0) / 2.0, (y1 - y0) / 2.0, 1.0, 1.0])
+            m[:3, 3] = ((x0 + x1) / 2.0, (y0 + y1) / 2.0, 0.001)
+            out.append(cls(kb @ m, color=tuple(float(v) for v in color), **flags))
+        return out
+
+
 def glow_range_m(screen: XrScreen, head=None, width_m: float = 0.75, ref_screen: float = 2.4) -> float:
     """_glow_range_m (xr_viewer/effects.py:280-312) without its rounded-key cache: the glow's reach in metres, growing with the
     screen's longer side (rounded to centimetres, as the reference's key rounds it) and with the head's distance from the screen's

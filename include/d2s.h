@@ -739,6 +739,74 @@ int d2s_dibr_xr_panorama_curved_plan(int dh, int dw, int batch, int H, int W, co
                                      const d2s_xr_frost* frost, const d2s_xr_glow* glow, const d2s_xr_panorama* pano,
                                      d2s_xr_plan_result* res);
 
+/* The world-space panels of the eye image (d2s_version() >= 133): what EffectsMixin._render_eye (xr_viewer/effects.py:1023-1225) draws
+ * after the screen and its look as the unit quad (+-1, +-1, 0, 1) under an affine model matrix -- the FPS / status panel
+ * (_render_fps_overlay, xr_viewer/overlay.py:81-249), the eight OSDs (effects.py:1157-1187), the calibration and help panels, the
+ * keyboard with its border and key highlights (_render_keyboard, overlay.py:1427-1510) and the thin laser quads.  Textured panels are
+ * _WORLD_VERT + _OVERLAY_FRAG (xr_viewer/glsl.py:3-13, 28-40: the RGBA texture at uv, alpha times u_alpha), solid ones _SOLID_VERT +
+ * _SOLID_FRAG (glsl.py:97-112: one colour).  The rainbow beams, the hit circles and the controller meshes are not drawn.
+ * One stream-ordered pass IN PLACE over the eye images any of the seven eye-view entries wrote into `out` (the layout of
+ * d2s_dibr_xr_shape for these eyes, batch and alpha_mode), with the same screen and eyes.  Per pixel: z starts at the screen's own
+ * depth there (the entries' cover rule over the screen's facets, normal_offset included; 1.0 where the screen does not cover: the
+ * reference's depth buffer when its first panel is drawn, rounded corners included, since the XR fragment shader never discards);
+ * then the panels in array order: covered where the panel's own coordinates a, b are in 0..1 with clip w > 0 and NDC z in [-1, 1];
+ * GL_LESS against z with D2S_XR_PANEL_DEPTH_TEST; the colour is color[] or the bilinear RGBA sample at uv = (a, b) (GL_LINEAR, no mip
+ * levels) with alpha times `alpha`; with D2S_XR_PANEL_BLEND it is blended SRC_ALPHA, ONE_MINUS_SRC_ALPHA, which GL applies to alpha
+ * too (a = s * s + (1 - s) * d), else it overwrites; with D2S_XR_PANEL_DEPTH_WRITE and D2S_XR_PANEL_DEPTH_TEST z becomes the panel's depth (GL writes depth only under
+ * an enabled depth test).  The destination is
+ * read once and stored once; a pixel no panel passes is not written.  Only the 16 x 16 tiles some panel's pixel box touches run.
+ * A panel with every vertex behind the eye (clip w <= 1e-6) is skipped; with no panel on any image nothing is launched.
+ * textures[i].rgba: device, uint8 [height][width][4], row 0 = the TOP row of the picture (the reference uploads np.flipud of it,
+ * overlay.py:191: GL's v = 1 is this row 0; this is the one place the flip is stated).  wrap: the GL wrap mode of the bilinear taps at
+ * a panel's edge -- D2S_XR_WRAP_REPEAT is moderngl's default, which the reference never changes.
+ * Refused, nothing launched, out untouched -- D2S_E_INVALID: a null pointer, a bad struct_size, n_panels outside 0 .. 32, n_textures
+ * outside 0 .. 32, a texture index outside -1 .. n_textures - 1, a texture outside 1 .. 8192 on a side, a model matrix that is not
+ * finite or not affine (last row 0 0 0 1), alpha or color not finite, unknown flags, a bad alpha_mode or out_fmt, a workspace that is
+ * missing, misaligned or below d2s_dibr_xr_panels_workspace, and what the entries refuse about the screen and the eyes;
+ * D2S_E_UNSUPPORTED: D2S_DIBR_ALPHA_PREMULTIPLIED (the destination's own alpha is gone: the reference's result cannot be formed), a
+ * panel that crosses the eye plane (a vertex with clip w <= 1e-6, but not all four), a screen vertex with clip w <= 1e-6.
+ * d2s_dibr_xr_panels_plan: what the call decides, host code, no GPU, the same refusals in the same words.
+ * Pinned by tests/golden/xr_panels.npz: the reference's own shaders and its own _render_fps_overlay / _render_keyboard state drawn
+ * off-screen into an RGBA8 + DEPTH24 target (tests/golden/make_golden_xr_panels.py). */
+enum { D2S_XR_PANEL_DEPTH_TEST = 1, D2S_XR_PANEL_DEPTH_WRITE = 2, D2S_XR_PANEL_BLEND = 4 };
+enum { D2S_XR_WRAP_REPEAT = 0, D2S_XR_WRAP_CLAMP = 1 };
+enum { D2S_XR_MAX_PANELS = 32 };
+typedef struct d2s_xr_panel {
+    double   model[16];        /* row-major as numpy writes it: the quad's corners are model @ (+-1, +-1, 0, 1) */
+    int32_t  texture;          /* index into textures[], or -1: the solid colour */
+    uint32_t flags;            /* D2S_XR_PANEL_* */
+    float    color[4];         /* u_color of a solid panel (r, g, b in 0..1, a) */
+    float    alpha;            /* u_alpha of a textured panel */
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_panel) = 160 */
+} d2s_xr_panel;
+typedef struct d2s_xr_texture {
+    const uint8_t* rgba;       /* device, [height][width][4], row 0 = the top row */
+    int32_t  width, height;
+    int32_t  wrap;             /* D2S_XR_WRAP_* */
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_texture) = 24 */
+} d2s_xr_texture;
+typedef struct d2s_xr_panels_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_xr_panels_plan_result) = 104 */
+    int32_t  rows_per_eye;     /* table rows written per eye: the screen's facets (1 | 48), then one per panel */
+    int32_t  setup_launches;   /* all eyes'; 0 when nothing is drawn */
+    int32_t  render_launches;  /* 1, or 0: no panel on any image */
+    int32_t  drawn[2];         /* per eye: panels with a pixel box on the image */
+    int32_t  tile0[2][2];      /* per eye: the first tile (x, y) of the tiles the boxes touch */
+    int32_t  tiles[2][2];      /* per eye: how many tiles across and down (0, 0: none) */
+    uint32_t grid[3];          /* the render launch: the larger of the eyes' tile counts, n_eyes * batch */
+    uint32_t reserved;
+    uint64_t workspace_bytes;
+    uint64_t out_elems;        /* d2s_dibr_xr_shape's total */
+    uint64_t offsets[2];
+} d2s_xr_panels_plan_result;
+int d2s_dibr_xr_panels_workspace(int n_eyes, uint64_t* bytes);
+int d2s_dibr_xr_panels(void* out, int out_fmt, int batch, int alpha_mode, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes,
+                       const d2s_xr_panel* panels, int n_panels, const d2s_xr_texture* textures, int n_textures, void* workspace,
+                       uint64_t workspace_bytes, void* stream);
+int d2s_dibr_xr_panels_plan(int out_fmt, int batch, int alpha_mode, const d2s_xr_screen* screen, const d2s_xr_eye* eyes, int n_eyes,
+                            const d2s_xr_panel* panels, int n_panels, const d2s_xr_texture* textures, int n_textures,
+                            d2s_xr_panels_plan_result* res);
+
 /* Detection half (d2s_version() >= 114): the six numbers of the reference's tensor path (xr_viewer/crop.py:368-435,
  * _detect_movie_letterbox_crop; sample plan :298-353) for `batch` frames in TWO launches, stream-ordered, no host synchronisation,
  * no allocation.  frames: D2S_FMT_U8_HWC, D2S_FMT_U8_CHW or D2S_FMT_F32_CHW (0..255; the reference's capture tensor is CHW), device.

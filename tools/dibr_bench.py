@@ -49,7 +49,12 @@
         d2s_dibr_xr_eyes_panorama_curved (the panorama behind the curved screen's glow or walls) in the same scheme: the look's own
         curved entry, the new entry with pano == NULL, the new entry with the panorama, the first two again; us per launch and ns
         per background pixel.  --ab-lib: the other build's curved entry of the look, this build's curved entry and this build's new
-        entry with pano == NULL through the same bare C call in the same rounds, twice each."""
+        entry with pano == NULL through the same bare C call in the same rounds, twice each.
+    python tools/dibr_bench.py --xr-eye --panels [--curve h|v]
+        d2s_dibr_xr_panels: the status panel below the screen and the keyboard group (border, keyboard, one highlight) at the
+        reference's default sizes, blended over the plain eye call's images.  In alternating rounds: the eye call alone, the eye call
+        followed by the panels pass, the pass alone, the pass with no panel (its host path: 0 launches), the eye call again; us per
+        call, and ns per pixel the pass changed beside the eye call's ns per covered screen pixel."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -75,6 +80,7 @@ ap.add_argument("--glow", default=None, choices=["glow", "glow2"], help="--xr-ey
 ap.add_argument("--glow-range", type=float, default=None, help="--glow: range_m (default: xr.glow_range_m of the screen)")
 ap.add_argument("--frost", default=None, choices=["veil", "frosted"], help="--xr-eye: time the veil / frosted eye call (flat screen)")
 ap.add_argument("--panorama", type=int, nargs=2, default=None, metavar=("W", "H"), help="--xr-eye: time the panorama background of this size")
+ap.add_argument("--panels", action="store_true", help="--xr-eye: time the plain eye call against the eye call + d2s_dibr_xr_panels (status panel + keyboard group)")
 ap.add_argument("--ab-lib", default=None, help="--frost: another build of libd2s_hip.so whose d2s_dibr_xr_eyes is timed in the same rounds")
 a = ap.parse_args()
 dev = torch.device("cuda")
@@ -169,6 +175,52 @@ if a.xr_eye:
     eyes = [xr.xr_eye(xr.fov_to_proj_mat4(*fovs[i]) @ xr.pose_to_view_mat4((0, 0, 0, 1), ((-0.032, 0.032)[i], 0, 0)), ew, eh, i) for i in range(2)]
     img, dep = synth.dibr_scene(a.height, a.width, 11, a.kind)
     dp = ops.dibr_params(corner_radius=0.03, alpha="rgba")
+    for B in a.batch if a.panels else ():
+        # the status panel below the screen and the keyboard group (border, keyboard, one highlight) at the reference's default sizes
+        # (xr_viewer/implementation.py:621-632, 723; xr_viewer/constants.py:119), over the plain eye call's images
+        rng = np.random.default_rng(7)
+        texs = [torch.from_numpy(rng.integers(0, 256, (h_, w_, 4), dtype=np.uint8)).to(dev) for w_, h_ in ((768, 238), (1280, 384))]
+        kb = xr.XrPanel.keyboard_world(0.0, -0.2, 0.7, 0.0, math.radians(-35.0))
+        panels = [xr.XrPanel.below_screen(screen, (768, 238), texture=0)] + \
+            xr.XrPanel.keyboard_group(kb, 1.6, 0.33, 1.0, [((-0.3, -0.05, -0.2, 0.0), (0.5, 0.85, 1.0, 0.70))], texture=1)
+        f = torch.from_numpy(img).to(dev)[None].expand(B, -1, -1, -1).contiguous()
+        d = torch.from_numpy(dep).to(dev)[None].expand(B, -1, -1).contiguous()
+        plan = ops.dibr_xr_panels_plan(B, screen, eyes, panels, texs)
+        probe = ops.dibr_xr_eyes(f[:1], d[:1], dp, screen, eyes, out_u8=False)
+        before = [t.clone() for t in probe]
+        ops.dibr_xr_panels(probe, screen, eyes, panels, texs)
+        drawn = B * sum(int((x != y).any(-1).sum()) for x, y in zip(probe, before))      # pixels the pass changed
+        screen_px = B * sum(int((e[..., 3] != 0.5).sum()) for e in before)             # clear alpha 0.5 marks the uncovered pixels
+        out = torch.empty(ops.dibr_xr_shape(eyes, B, dp.alpha_mode)[1], dtype=torch.uint8, device=dev)
+        views = ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)
+
+        def both():
+            ops.dibr_xr_panels(ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out), screen, eyes, panels, texs)
+        runs = {"eyes": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out), "eyes_then_panels": both,
+                "panels_alone": lambda: ops.dibr_xr_panels(views, screen, eyes, panels, texs),
+                "panels_none_on_screen": lambda: ops.dibr_xr_panels(views, screen, eyes, [], []),      # the host path alone: 0 launches
+                "eyes_again": lambda: ops.dibr_xr_eyes(f, d, dp, screen, eyes, out=out)}
+        t = {k: [] for k in runs}
+        for _ in range(a.rounds):
+            for k, fn in runs.items():
+                for _ in range(3): fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                for _ in range(a.iters): fn()
+                e1.record(); torch.cuda.synchronize()
+                t[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        extra = med["eyes_then_panels"] - med["eyes"]
+        print(f"xr-eye panels {screen.curve} {a.height}x{a.width} -> 2 x {ew}x{eh} B={B}, uint8, {len(panels)} panels, medians of {a.rounds} rounds x {a.iters} calls; "
+              f"plan: {plan['rows_per_eye']} rows per eye, {plan['setup_launches']} set-up + {plan['render_launches']} render launches, tiles {plan['tiles']} "
+              f"of {[(-(-ew // 16), -(-eh // 16))] * 2}, grid {plan['grid']}; the pass changed {drawn // B} pixels per frame ({drawn / (B * 2 * ew * eh):.4f} of the images)", flush=True)
+        for k in runs:
+            print(f"    {k:24s} {med[k]:8.1f} us  (min {min(t[k]):.1f} max {max(t[k]):.1f})", flush=True)
+        print(f"    eyes + panels - eyes = {extra:+.1f} us = {1e3 * extra / max(drawn, 1):.4f} ns per panel-covered pixel; panels alone "
+              f"{1e3 * med['panels_alone'] / max(drawn, 1):.4f} ns per panel-covered pixel; the eye call {1e3 * med['eyes'] / screen_px:.4f} ns per covered "
+              f"screen pixel; eyes against itself {med['eyes_again'] - med['eyes']:+.1f} us", flush=True)
+    if a.panels:
+        sys.exit(0)
     for B in a.batch if a.panorama else ():
         import ctypes as C
         from desktop2stereo_amd import _lib
