@@ -172,6 +172,14 @@ class DibrWarpPlanResult(C.Structure):
                 ("lds_static_bytes", C.c_uint32), ("kernel", C.c_char * 64)]
 
 
+class DibrCompositePlanResult(C.Structure):
+    """d2s_dibr_composite_plan_result (include/d2s.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_int32), ("cols", C.c_int32), ("margin", C.c_int32), ("ww", C.c_int32),
+                ("roll0", C.c_int32), ("up", C.c_int32), ("fx", C.c_int32), ("vec", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("grid", C.c_uint32 * 3), ("block", C.c_uint32), ("lds_dynamic_bytes", C.c_uint32), ("lds_static_bytes", C.c_uint32),
+                ("kernel", C.c_char * 64)]
+
+
 class PostPlanResult(C.Structure):
     """d2s_post_plan_result (include/d2s.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("form", C.c_int32), ("launches", C.c_int32), ("k", C.c_int32), ("r", C.c_int32),
@@ -283,6 +291,8 @@ SYMBOLS = {
     "d2s_dibr_warp_crop": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double),
                                      _P, C.c_int, _P]),
     # the OpenXR eye views (xr_viewer/effects.py:1023-1137, xr_viewer/screen.py:29-173)
+    "d2s_dibr_composite_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.c_int, C.c_int, C.c_uint,
+                                          C.POINTER(DibrCompositePlanResult)]),
     "d2s_dibr_warp_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DibrParams), C.POINTER(C.c_double), C.c_int,
                                      C.POINTER(DibrWarpPlanResult)]),
     "d2s_dibr_xr_shape": (C.c_int, [C.POINTER(XrEye), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -56,4 +56,5 @@ extern "C" const char* d2s_last_error(void) { return d2s::g_err.c_str(); }
 // 111: d2s_dibr_composite / d2s_dibr_composite_shape (the viewer's Anaglyph, Interleaved, Interleaved-V and Depth Map modes).
 // 131: the wide (8 x 8-pixel tile) form of the fused residual unit: d2s_forward_plan_result.rcu_fused bits 16-19 / 24-26, d2s_rcu_probe_params.reserved = 1.
 // 132: d2s_dibr_warp_plan (what the f1 warp would launch); f1's row-kernel window is capped at the 64 KB of LDS a block may request.
-extern "C" int d2s_version(void) { return 133; }
+// 134: d2s_dibr_composite_plan (what the composite display modes would launch; the launcher takes its decision from it).
+extern "C" int d2s_version(void) { return 134; }

@@ -362,32 +362,96 @@ extern "C" int d2s_dibr_composite_shape(int H, int W, const d2s_dibr_params* p, 
     return D2S_OK;
 }
 
-// d2s_dibr_composite (dh == H && dw == W: depth IS the texture) and d2s_dibr_composite_depth (any other [dh, dw]: the UpDep kernels)
+// Everything dibr_composite_any decides, stated once on the host (d2s_dibr_composite_plan reports it; tests/test_cpu_composite_f64.py
+// and test_cpu_dibr_plan.py pin it): the checks of everything that is no pointer, the viewport, the uniforms, the window plan
+// (512 columns per block while the window stays <= 640 texels, as f1 chooses; windows above 1536 texels -- 8 planes x 1536 floats =
+// 48 KB beside the queue -- take the gather kernel), the Depth Map's store form, and from them the kernel, its grid
+// and its LDS.  No HIP call.  out_align = the output address modulo 16 (only the Depth Map looks at it).
+struct CompPlan {
+    int composite;
+    DibrWindow win;                        // (rows = false and all zero for the Depth Map)
+    bool roll0, up, fx, u8, vec;           // vec: the Depth Map's 16-byte vector stores
+    int nch, vw, vh;
+    long npix;                             // the Depth Map's flattened output
+    UpArgs ua;
+    dim3 grid, block;
+    unsigned lds_dynamic, lds_static;      // the row kernel's request; 0 otherwise
+};
+constexpr unsigned comp_rows_static_lds(int cols) { return (unsigned)(sizeof(int) * (size_t)cols + sizeof(int)); }      // queue[COLS], qn
+// the kernel's name with its template arguments (formed for d2s_dibr_composite_plan only: the launch path formats nothing)
+static void comp_plan_name(const CompPlan& pl, char* name, size_t n) {
+    const char* fmt = pl.u8 ? "u8" : "f32";
+    const char* dname = pl.up ? "UpDep" : "FullDep";
+    const char* m = pl.composite == D2S_COMPOSITE_ANAGLYPH ? "ana" : pl.composite == D2S_COMPOSITE_INTERLEAVED ? "il" : "ilv";
+    if (pl.composite == D2S_COMPOSITE_DEPTH_MAP) snprintf(name, n, "depth_map<%s,%d,%s,%s>", fmt, pl.nch, pl.vec ? "vec" : "scalar", dname);
+    else if (pl.win.rows) snprintf(name, n, "comp_rows<%s,%s,fx=%d,%d,%s>", m, fmt, pl.fx ? 1 : 0, pl.win.cols, dname);
+    else snprintf(name, n, "comp<%s,%s,%s,%s>", m, fmt, pl.roll0 ? "roll0" : "general", dname);
+}
+static int comp_plan_impl(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, int composite, int out_fmt,
+                          unsigned out_align, CompGeom& G, CompPlan& pl) {
+    D2S_REQUIRE(composite >= D2S_COMPOSITE_ANAGLYPH && composite <= D2S_COMPOSITE_DEPTH_MAP, "bad composite (D2S_COMPOSITE_*)");
+    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
+    if (rc) return rc;
+    DibrGeom& g = G.g;
+    rc = comp_viewport(H, W, p, &G.vx, &G.vy, &pl.vw, &pl.vh);
+    if (rc) return rc;
+    const int vw = pl.vw, vh = pl.vh;
+    pl.composite = composite;
+    pl.nch = p->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
+    pl.up = dh != H || dw != W;
+    pl.u8 = out_fmt == D2S_FMT_U8_HWC;
+    pl.ua = UpArgs{dh, dw, linear_scale(dh, H, false), linear_scale(dw, W, false)};      // (d2s_upsample_depth's scales)
+    pl.block = dim3(256);
+    pl.win = DibrWindow{0, 0, 0, false};
+    pl.roll0 = pl.fx = pl.vec = false;
+    pl.npix = 0;
+    pl.lds_dynamic = pl.lds_static = 0;
+    if (composite == D2S_COMPOSITE_DEPTH_MAP) {
+        pl.npix = (long)batch * vh * vw;
+        D2S_REQUIRE((pl.npix + 1023L) / 1024L < (1L << 31), "output too large for one launch");      // (cdiv returns int)
+        pl.grid = dim3((unsigned)cdiv(pl.npix, 1024L));
+        pl.vec = (out_align & 15u) == 0;
+        return D2S_OK;
+    }
+    dibr_fill_geom(g, p, H, W, dh, dw);
+    g.oh = vh; g.ow = vw; g.mode = -1; g.out_h = vh; g.out_w = vw;
+    g.vpx = (float)G.vx; g.vpy = (float)G.vy; g.vpw = (float)vw; g.vph = (float)vh;   // u_viewport
+    pl.roll0 = g.s == 0.f && g.c == 1.f;
+    pl.win = dibr_plan_window(g, (double)W / (double)vw, pl.roll0, 512, 640, 1536);
+    pl.fx = g.feather || g.corner_r > 0.f;
+    if (pl.win.rows) {
+        pl.grid = dim3(cdiv(vw, pl.win.cols), vh, batch);
+        pl.lds_dynamic = dibr_rows_dynamic_lds(pl.win.WW);
+        pl.lds_static = comp_rows_static_lds(pl.win.cols);
+        D2S_REQUIRE(pl.lds_dynamic + pl.lds_static <= DIBR_LDS_LIMIT, "internal: the window plan exceeds the LDS of a block");
+    } else {
+        pl.grid = dim3(cdiv(vw, 256), vh, batch);
+    }
+    return D2S_OK;
+}
+
+// d2s_dibr_composite (dh == H && dw == W: depth IS the texture) and d2s_dibr_composite_depth (any other [dh, dw]: the UpDep kernels).
+// The decision is comp_plan_impl's; this function looks at the pointers and launches what the plan says.
 int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p,
                             int composite, void* out, int out_fmt, void* stream, bool check_only) {
     D2S_REQUIRE(depth && p && out, "null pointer");
     D2S_REQUIRE(composite >= D2S_COMPOSITE_ANAGLYPH && composite <= D2S_COMPOSITE_DEPTH_MAP, "bad composite (D2S_COMPOSITE_*)");
     D2S_REQUIRE(rgb || composite == D2S_COMPOSITE_DEPTH_MAP, "rgb may be NULL for D2S_COMPOSITE_DEPTH_MAP only");
-    int rc = dibr_check(p, dh, dw, batch, H, W, out_fmt);
-    if (rc) return rc;
     CompGeom G;
-    DibrGeom& g = G.g;
-    int vw, vh;
-    rc = comp_viewport(H, W, p, &G.vx, &G.vy, &vw, &vh);
+    CompPlan pl;
+    const int rc = comp_plan_impl(dh, dw, batch, H, W, p, composite, out_fmt, (unsigned)((uintptr_t)out & 15), G, pl);
     if (rc) return rc;
-    const int nch = p->alpha_mode == D2S_DIBR_ALPHA_RGBA ? 4 : 3;
-    const bool up = dh != H || dw != W;
-    const UpArgs ua = {dh, dw, linear_scale(dh, H, false), linear_scale(dw, W, false)};      // (d2s_upsample_depth's scales)
+    if (check_only) return D2S_OK;
+    const bool up = pl.up, roll0 = pl.roll0, fx = pl.fx, vec = pl.vec;
+    const int nch = pl.nch, vw = pl.vw, vh = pl.vh;
+    const dim3 grid = pl.grid, block = pl.block;
     if (composite == D2S_COMPOSITE_DEPTH_MAP) {
-        const long npix = (long)batch * vh * vw;
-        D2S_REQUIRE(cdiv(npix, 1024L) < (1L << 31), "output too large for one launch");
-        if (check_only) return D2S_OK;
-        dim3 grid((unsigned)cdiv(npix, 1024L)), block(256);
-        const bool vec = ((uintptr_t)out & 15) == 0;
+        const long npix = pl.npix;
+        const UpArgs ua = pl.ua;
 #define DM(FMT, N, V, D) hipLaunchKernelGGL((depth_map_kernel<FMT, N, V, D>), grid, block, 0, (hipStream_t)stream, depth, out, H, W, vh, vw, npix, ua)
 #define DM_D(FMT, N, V) do { if (up) DM(FMT, N, V, UpDep); else DM(FMT, N, V, FullDep); } while (0)
 #define DM_V(FMT, N) do { if (vec) DM_D(FMT, N, true); else DM_D(FMT, N, false); } while (0)
-        if (out_fmt == D2S_FMT_U8_HWC) { if (nch == 4) DM_V(D2S_FMT_U8_HWC, 4); else DM_V(D2S_FMT_U8_HWC, 3); }
+        if (pl.u8) { if (nch == 4) DM_V(D2S_FMT_U8_HWC, 4); else DM_V(D2S_FMT_U8_HWC, 3); }
         else { if (nch == 4) DM_V(D2S_FMT_F32_HWC, 4); else DM_V(D2S_FMT_F32_HWC, 3); }
 #undef DM_V
 #undef DM_D
@@ -395,20 +459,10 @@ int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int 
         D2S_CHECK_LAUNCH();
         return D2S_OK;
     }
-    if (check_only) return D2S_OK;
-    dibr_fill_geom(g, p, H, W, dh, dw);
-    g.oh = vh; g.ow = vw; g.mode = -1; g.out_h = vh; g.out_w = vw;
-    g.vpx = (float)G.vx; g.vpy = (float)G.vy; g.vpw = (float)vw; g.vph = (float)vh;   // u_viewport
-    const bool roll0 = g.s == 0.f && g.c == 1.f;
-    // 512 columns per block while the window stays <= 640 texels, as f1 chooses; windows above 1536 texels (8 planes x 1536 floats =
-    // 48 KB + the queue) take the gather kernel
-    const DibrWindow win = dibr_plan_window(g, (double)W / (double)vw, roll0, 512, 640, 1536);
-    const int margin = win.margin, cols = win.cols, WW = win.WW;
-    const bool fx = g.feather || g.corner_r > 0.f;
-    dim3 block(256), grid(cdiv(vw, 256), vh, batch);
-    if (win.rows) {
-        const size_t lds = (size_t)8 * WW * sizeof(float);
-        dim3 rgrid(cdiv(vw, cols), vh, batch);
+    if (pl.win.rows) {
+        const int margin = pl.win.margin, cols = pl.win.cols, WW = pl.win.WW;
+        const size_t lds = pl.lds_dynamic;
+        const dim3 rgrid = grid;
 #define CR_K(M, FMT, FXV, COLS, D) hipLaunchKernelGGL((comp_rows_kernel<M, FMT, FXV, COLS, D>), rgrid, block, lds, (hipStream_t)stream, rgb, depth, out, G, margin, WW)
 #define CR(M, FMT, FXV, D) do { if (cols == 512) CR_K(M, FMT, FXV, 512, D); else CR_K(M, FMT, FXV, 256, D); } while (0)
 #define CR_F(M, FMT) do { if (up) { if (fx) CR(M, FMT, true, UpDep); else CR(M, FMT, false, UpDep); } \
@@ -416,7 +470,7 @@ int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int 
 #define CR_M(FMT) do { if (composite == D2S_COMPOSITE_ANAGLYPH) CR_F(D2S_COMPOSITE_ANAGLYPH, FMT); \
                        else if (composite == D2S_COMPOSITE_INTERLEAVED) CR_F(D2S_COMPOSITE_INTERLEAVED, FMT); \
                        else CR_F(D2S_COMPOSITE_INTERLEAVED_V, FMT); } while (0)
-        if (out_fmt == D2S_FMT_U8_HWC) CR_M(D2S_FMT_U8_HWC); else CR_M(D2S_FMT_F32_HWC);
+        if (pl.u8) CR_M(D2S_FMT_U8_HWC); else CR_M(D2S_FMT_F32_HWC);
 #undef CR_M
 #undef CR_F
 #undef CR
@@ -428,12 +482,30 @@ int d2s::dibr_composite_any(const uint8_t* rgb, const float* depth, int dh, int 
 #define CG_M(FMT) do { if (composite == D2S_COMPOSITE_ANAGLYPH) CG_R(D2S_COMPOSITE_ANAGLYPH, FMT); \
                        else if (composite == D2S_COMPOSITE_INTERLEAVED) CG_R(D2S_COMPOSITE_INTERLEAVED, FMT); \
                        else CG_R(D2S_COMPOSITE_INTERLEAVED_V, FMT); } while (0)
-        if (out_fmt == D2S_FMT_U8_HWC) CG_M(D2S_FMT_U8_HWC); else CG_M(D2S_FMT_F32_HWC);
+        if (pl.u8) CG_M(D2S_FMT_U8_HWC); else CG_M(D2S_FMT_F32_HWC);
 #undef CG_M
 #undef CG_R
 #undef CG
     }
     D2S_CHECK_LAUNCH();
+    return D2S_OK;
+}
+
+// What d2s_dibr_composite / d2s_dibr_composite_depth would launch: comp_plan_impl, the function the launcher takes its decision from.
+static_assert(sizeof(d2s_dibr_composite_plan_result) == 132, "d2s_dibr_composite_plan_result is part of the ABI (tests/test_cpu_composite_abi.py)");
+extern "C" int d2s_dibr_composite_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, int composite, int out_fmt,
+                                       unsigned out_align, d2s_dibr_composite_plan_result* res) {
+    D2S_REQUIRE(p && res, "null pointer");
+    D2S_REQUIRE(res->struct_size == sizeof(d2s_dibr_composite_plan_result),
+                "d2s_dibr_composite_plan_result.struct_size must be sizeof(d2s_dibr_composite_plan_result)");
+    CompGeom G;
+    CompPlan pl;
+    const int rc = comp_plan_impl(dh, dw, batch, H, W, p, composite, out_fmt, out_align, G, pl);
+    if (rc) return rc;
+    *res = d2s_dibr_composite_plan_result{sizeof(d2s_dibr_composite_plan_result), pl.win.rows ? 1 : 0, pl.win.cols, pl.win.margin, pl.win.WW,
+                                          pl.roll0 ? 1 : 0, pl.up ? 1 : 0, pl.fx ? 1 : 0, pl.vec ? 1 : 0, pl.vh, pl.vw,
+                                          {pl.grid.x, pl.grid.y, pl.grid.z}, pl.block.x, pl.lds_dynamic, pl.lds_static, {}};
+    comp_plan_name(pl, res->kernel, sizeof(res->kernel));
     return D2S_OK;
 }
 

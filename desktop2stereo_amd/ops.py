@@ -801,13 +801,31 @@ def dibr_xr_panels_plan(batch: int, screen, eyes, panels, textures=(), alpha_mod
             "grid": tuple(r.grid), "workspace_bytes": r.workspace_bytes, "out_elems": r.out_elems, "offsets": list(r.offsets[:n])}
 
 
+def dibr_composite_plan(dh: int, dw: int, batch: int, H: int, W: int, dp: "_lib.DibrParams", mode: str, out_u8: bool = True,
+                        out_align: int = 0) -> dict:
+    """What dibr_composite would launch for these arguments (include/d2s.h d2s_dibr_composite_plan; host code, no GPU): the kernel's
+    name, whether it is the LDS-window row kernel, the window plan (cols, margin, WW), the viewport's size, grid, block and the LDS
+    request.  out_align = the output address modulo 16 ("Depth Map": vector or scalar stores)."""
+    if mode not in _lib.COMPOSITE:
+        raise ValueError(f"mode must be one of {list(_lib.COMPOSITE)}")
+    r = _lib.DibrCompositePlanResult()
+    r.struct_size = C.sizeof(_lib.DibrCompositePlanResult)
+    check(_lib.load().d2s_dibr_composite_plan(int(dh), int(dw), int(batch), int(H), int(W), C.byref(dp), _lib.COMPOSITE[mode],
+                                              FMT_U8_HWC if out_u8 else FMT_F32_HWC, int(out_align) & 15, C.byref(r)), "d2s_dibr_composite_plan")
+    return {"kernel": r.kernel.decode(), "rows": bool(r.rows), "cols": r.cols, "margin": r.margin, "WW": r.ww, "roll0": bool(r.roll0),
+            "up": bool(r.up), "fx": bool(r.fx), "vec": bool(r.vec), "out_h": r.out_h, "out_w": r.out_w, "grid": tuple(r.grid),
+            "block": r.block, "lds_dynamic": r.lds_dynamic_bytes, "lds_static": r.lds_static_bytes,
+            "lds_bytes": r.lds_dynamic_bytes + r.lds_static_bytes}
+
+
 def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_lib.DibrParams", mode: str,
-                   out_u8: bool = True, size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+                   out_u8: bool = True, size: Optional[Tuple[int, int]] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The viewer's composite display modes (reference viewer.py:633-1197): "Anaglyph" | "Interleaved" | "Interleaved-V" |
     "Depth Map".  uint8 HWC frames [B,H,W,3] or [H,W,3] (None for "Depth Map") + depth [B,dh,dw] or [dh,dw] -> the program's viewport,
     dp.viewport = (x, y, w, h) in window pixels, y up (zeros: the frame itself); dp.display_mode is not used (include/d2s.h).
     Depth of another size than the frame's (the model's) is up-sampled inside the kernel, bit-identical to upsample_depth first.
-    size = (H, W): the frame size when there are no frames ("Depth Map" from a model-resolution map); default: the depth's own."""
+    size = (H, W): the frame size when there are no frames ("Depth Map" from a model-resolution map); default: the depth's own.
+    out: a caller-kept contiguous tensor of the result's batched shape [B, h, w, 3 | 4] and dtype (written in place)."""
     if mode not in _lib.COMPOSITE:
         raise ValueError(f"mode must be one of {list(_lib.COMPOSITE)}")
     _need_cuda(depth, "depth")
@@ -834,7 +852,10 @@ def dibr_composite(frames: Optional[torch.Tensor], depth: torch.Tensor, dp: "_li
     oh, ow = C.c_int(), C.c_int()
     check(lib.d2s_dibr_composite_shape(H, W, C.byref(dp), _lib.COMPOSITE[mode], C.byref(oh), C.byref(ow)), "d2s_dibr_composite_shape")
     shape, dtype, fmt = _dibr_out_spec(B, oh.value, ow.value, dp, out_u8)
-    out = torch.empty(shape, dtype=dtype, device=d.device)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=d.device)
+    elif tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != d.device:
+        raise ValueError(f"dibr_composite: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {d.device}")
     with _on(d.device) as st:
         check(lib.d2s_dibr_composite_depth(_ptr(f) if f is not None else None, _ptr(d), dh, dw, B, H, W, C.byref(dp), _lib.COMPOSITE[mode],
                                            _ptr(out), fmt, st), "d2s_dibr_composite_depth")

@@ -845,6 +845,27 @@ int d2s_dibr_composite(const uint8_t* rgb, const float* depth, int batch, int H,
  * to d2s_upsample_depth + d2s_dibr_composite; dh == H && dw == W is exactly d2s_dibr_composite.  Shape from d2s_dibr_composite_shape. */
 int d2s_dibr_composite_depth(const uint8_t* rgb, const float* depth, int dh, int dw, int batch, int H, int W,
                              const d2s_dibr_params* p, int composite, void* out, int out_fmt, void* stream);
+/* What d2s_dibr_composite / d2s_dibr_composite_depth would launch for these arguments (d2s_version() >= 134; pure host code: launches
+ * nothing, needs no GPU).  It runs the launcher's own code up to the launch -- the checks, the viewport, the uniforms, the window
+ * plan (512 columns per block while the window stays <= 640 words, the row kernel while the 256-column window stays <= 1536) and the
+ * Depth Map's store form -- and refuses what the launcher refuses of these arguments.  out_align = the output address modulo 16: the
+ * Depth Map stores 16-byte vectors when it is 0, bytes / floats otherwise; the other programs ignore it.  kernel:
+ *   "comp_rows<ana|il|ilv,u8|f32,fx=0|1,256|512,FullDep|UpDep>"   the LDS-window row kernel (roll == 0),
+ *   "comp<ana|il|ilv,u8|f32,roll0|general,FullDep|UpDep>"         the gather kernel,
+ *   "depth_map<u8|f32,3|4,vec|scalar,FullDep|UpDep>"              the Depth Map.
+ * rows, cols, margin, ww: the window plan, as in the warp plan's result above -- all zero for the Depth Map; out_h x out_w: the viewport;
+ * grid / block: the launch's; lds_*_bytes: the row kernel's request (0 otherwise), never above 65 536. */
+typedef struct d2s_dibr_composite_plan_result {
+    uint32_t struct_size;      /* MUST be sizeof(d2s_dibr_composite_plan_result) */
+    int32_t rows, cols, margin, ww;
+    int32_t roll0, up, fx, vec;
+    int32_t out_h, out_w;
+    uint32_t grid[3], block;
+    uint32_t lds_dynamic_bytes, lds_static_bytes;
+    char kernel[64];
+} d2s_dibr_composite_plan_result;
+int d2s_dibr_composite_plan(int dh, int dw, int batch, int H, int W, const d2s_dibr_params* p, int composite, int out_fmt,
+                            unsigned out_align, d2s_dibr_composite_plan_result* res);
 
 /* f3: the MJPEG sink of the Streamer modes.  Replaces `cv2.imencode('.jpg', bgr, [IMWRITE_JPEG_QUALITY, q])` on the
  * frame make_sbs returns (reference streamer.py:249-256, 285-291; quality = settings.yaml "Stream Quality",

@@ -35,6 +35,40 @@ def test_symbols_and_version(lib):
         assert f"{enum} = {v}" in hdr, enum
 
 
+def test_plan_symbol_struct_and_refusals(lib):
+    """d2s_dibr_composite_plan (d2s_version() >= 134): declared, exported, its result 128 bytes, a wrong struct_size refused, and what
+    the launcher refuses of these arguments refused here too"""
+    assert lib.d2s_version() >= 134
+    assert "d2s_dibr_composite_plan" in _lib.SYMBOLS and lib.d2s_dibr_composite_plan is not None
+    hdr = open(os.path.join(REPO, "include", "d2s.h")).read()
+    assert "int d2s_dibr_composite_plan(" in hdr and "} d2s_dibr_composite_plan_result;" in hdr
+    R = _lib.DibrCompositePlanResult
+    assert C.sizeof(R) == 4 + 4 * 4 + 4 * 4 + 2 * 4 + 4 * 4 + 2 * 4 + 64 == 132
+    assert [f[0] for f in R._fields_] == ["struct_size", "rows", "cols", "margin", "ww", "roll0", "up", "fx", "vec", "out_h", "out_w", "grid",
+                                          "block", "lds_dynamic_bytes", "lds_static_bytes", "kernel"]
+    dp = ops.dibr_params()
+    r = R()
+
+    def call(dh=90, dw=160, batch=1, H=90, W=160, p=dp, mode=0, fmt=_lib.FMT_U8_HWC, align=0, res=r):
+        return lib.d2s_dibr_composite_plan(dh, dw, batch, H, W, C.byref(p) if p is not None else None, mode, fmt, align,
+                                           C.byref(res) if res is not None else None)
+    assert call() == 1 and b"struct_size" in lib.d2s_last_error()              # struct_size 0
+    r.struct_size = C.sizeof(R) - 4
+    assert call() == 1 and b"struct_size" in lib.d2s_last_error()
+    r.struct_size = C.sizeof(R)
+    assert call() == 0 and r.kernel == b"comp_rows<ana,u8,fx=0,256,FullDep>" and (r.out_h, r.out_w) == (90, 160)
+    assert call(p=None) == 1 and b"null pointer" in lib.d2s_last_error() and call(res=None) == 1
+    assert call(mode=4) == 1 and b"composite" in lib.d2s_last_error()
+    for kw, msg in ((dict(batch=0), b"bad batch"), (dict(H=1), b"bad shape"), (dict(dh=0), b"bad depth shape"), (dict(fmt=99), b"out_fmt"),
+                    (dict(p=ops.dibr_params(viewport=(0.5, 0, 10, 10))), b"viewport"), (dict(p=ops.dibr_params(search_radius=16.0)), b"search_radius")):
+        assert call(**kw) == 1 and msg in lib.d2s_last_error(), kw
+    assert call(mode=3, align=4) == 0 and r.kernel == b"depth_map<u8,3,scalar,FullDep>" and r.vec == 0
+    assert call(mode=3, dh=5, dw=19, fmt=_lib.FMT_F32_HWC, p=ops.dibr_params(alpha="rgba")) == 0 and r.kernel == b"depth_map<f32,4,vec,UpDep>"
+    assert ops.dibr_composite_plan(90, 160, 1, 90, 160, dp, "Interleaved-V", out_u8=False)["kernel"] == "comp_rows<ilv,f32,fx=0,256,FullDep>"
+    with pytest.raises(ValueError):
+        ops.dibr_composite_plan(90, 160, 1, 90, 160, dp, "Full-SBS")
+
+
 def test_shape(lib):
     dp = ops.dibr_params()
     for mode in range(4):

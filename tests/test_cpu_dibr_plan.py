@@ -139,15 +139,30 @@ def test_rows_words_is_the_lds_bound(lib, env):
     assert pl["rows"] and pl["kernel"] == "dibr_rows<f32,fx=0,256,UpDep,crop>" and pl["WW"] == 1983
 
 
-def test_the_composites_bound_is_unchanged():
-    """The composites plan their window with rows_words = 1 536 (48 KB of planes): not part of this change.  They have no plan query;
-    the call is read from the source."""
-    src = open(os.path.join(REPO, "desktop2stereo_amd", "csrc", "dibr_composite.hip")).read()
-    calls = re.findall(r"dibr_plan_window\(([^;]*)\);", src)
-    assert len(calls) == 1 and [a.strip() for a in calls[0].split(",")][-3:] == ["512", "640", "1536"], calls
+def test_the_composites_bound_is_unchanged(lib):
+    """The composites plan their window with 512 columns while it stays <= 640 words and take the row kernel while the 256-column window
+    stays <= 1 536 words (48 KB of planes), stated through their own plan query one case either side of each number; f1's rows_words
+    is the named constant, no literal."""
+    from desktop2stereo_amd import ops
     f1 = open(os.path.join(REPO, "desktop2stereo_amd", "csrc", "dibr.hip")).read()
     calls = re.findall(r"dibr_plan_window\(([^;]*)\);", f1)
     assert len(calls) == 1 and calls[0].split(",")[-1].strip() == "DIBR_F1_ROWS_WORDS", calls      # no literal
+
+    def plan(H, W, mode="Anaglyph", **kw):
+        return ops.dibr_composite_plan(H, W, 1, H, W, ops.dibr_params(**kw), mode)
+    for mode, tag in (("Anaglyph", "ana"), ("Interleaved", "il"), ("Interleaved-V", "ilv")):
+        pl = plan(8, 1200, mode, viewport=(0, 0, 204, 8))                       # ceil(255 * 1200 / 204) + 2 * 15 + 4 = 1 534 <= 1 536
+        assert (pl["rows"], pl["cols"], pl["margin"], pl["WW"], pl["kernel"]) == (True, 256, 15, 1534, f"comp_rows<{tag},u8,fx=0,256,FullDep>"), pl
+        assert pl["lds_dynamic"] == 32 * 1534 and pl["lds_static"] == 4 * 256 + 4 and pl["lds_bytes"] <= LDS_LIMIT, pl
+        pl = plan(8, 1200, mode, viewport=(0, 0, 200, 8))                       # 1 530 + 34 = 1 564 > 1 536: the gather kernel
+        assert (pl["rows"], pl["WW"], pl["kernel"], pl["lds_bytes"]) == (False, 1564, f"comp<{tag},u8,roll0,FullDep>", 0), pl
+        pl = plan(24, 512, mode, search_radius=15.0, resolution=(128.0, 6.0))   # 511 + 124 + 4 = 639 <= 640: 512 columns
+        assert (pl["rows"], pl["cols"], pl["margin"], pl["WW"]) == (True, 512, 62, 639), pl
+        assert pl["kernel"] == f"comp_rows<{tag},u8,fx=0,512,FullDep>" and pl["lds_static"] == 4 * 512 + 4, pl
+        pl = plan(24, 512, mode, search_radius=15.0, resolution=(126.0, 6.0))   # 641 > 640: 256 columns, margin 63
+        assert (pl["rows"], pl["cols"], pl["margin"], pl["WW"]) == (True, 256, 63, 255 + 126 + 4), pl
+    # the largest row plan the composites can form stays inside a block's LDS
+    assert 32 * 1536 + 4 * 256 + 4 <= LDS_LIMIT
 
 
 def test_cols_follow_the_halving_rule(lib, env):

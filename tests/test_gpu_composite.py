@@ -110,23 +110,17 @@ def test_kernel_vs_restatement_sweeps(dev, mode):
             _check(g, composite(ti, td, mode, alpha=alpha, depth_ratio=4.0), (mode, "tiny", h, w, alpha))
 
 
-def _lds_window_words(W, vw, ipd_uv, depth_ratio, convergence=0.0, search=12):
-    """The LDS window the launcher sizes for 256-column blocks (dibr_composite.hip): > 1536 words -> the gather kernel."""
-    import math
-    reach = max(max(2.0, search) * 1.0, abs(ipd_uv / 2) * (1 + abs(convergence)) * abs(0.1 * depth_ratio) * W)
-    margin = math.ceil(reach) + 2
-    return math.ceil(255.0 * W / vw) + 2 * margin + 4
-
-
 @pytest.mark.parametrize("mode", ["Anaglyph", "Interleaved", "Interleaved-V"])
 def test_gather_kernel_when_the_window_does_not_fit(dev, mode):
     """roll == 0 but the LDS window would exceed 1536 words: a wide frame with very large parallax, and a viewport 16x narrower than
-    the frame -- both take the gather kernel (comp_kernel), which must compute what the restatement computes."""
-    from desktop2stereo_amd import synth
+    the frame -- both take the gather kernel (comp_kernel, asserted from the launch plan), which must compute what the restatement
+    computes."""
+    from desktop2stereo_amd import ops, synth
     img, dep = synth.dibr_scene(24, 1600, 8, "boxes")
+    tag = {"Anaglyph": "ana", "Interleaved": "il", "Interleaved-V": "ilv"}[mode]
     for kw in (dict(depth_ratio=150.0), dict(depth_ratio=4.0, viewport=(1, 0, 100, 24))):
-        vw = kw.get("viewport", (0, 0, 1600, 24))[2]
-        assert _lds_window_words(1600, vw, 0.064, kw["depth_ratio"]) > 1536, kw
+        pl = ops.dibr_composite_plan(24, 1600, 1, 24, 1600, ops.dibr_params(0.064, **kw), mode, out_u8=False)
+        assert pl["rows"] is False and pl["WW"] > 1536 and pl["kernel"] == f"comp<{tag},f32,roll0,FullDep>", (kw, pl)
         for alpha in ("window", "rgba"):
             got = _run(dev, img, dep, mode, alpha=alpha, **dict(kw))
             _check(got, composite(img, dep, mode, alpha=alpha, **kw), (mode, kw, alpha))
